@@ -4,7 +4,9 @@
 A "step" is one full denoise of one synthetic 1920x1080 frame (BASELINE.json configs[2]: 3-scale, b=6, w=1, tau=1, m=1,
 seeded random order): the pyramid build, and per scale the pair-distance / mask kernels, the marking fixed point, the
 Bayesian patch kernel, finalisation and merge.  Inputs are resident in HBM before the timed region.
-After the timed region (N = 1, untimed, skipped by --no-extras): the pair-distance kernel with the scales serialised
+A plain run sets up, warms up, times --steps steps, writes the last step's output frame if --dump-outputs DIR is given, and
+prints its line.  Everything else is measured or checked only with --full (the --no-* switches then leave parts of it out).
+After the timed region (--full, N = 1, untimed, skipped by --no-extras): the pair-distance kernel with the scales serialised
 (`roofline.isolated_*`), the host-buffer call a drop-in user makes (`end_to_end`: PCIe both ways inside), the low-noise variant of
 the frame (`low_noise`), a textured frame whose similar sets depend on the noise (`textured`), the same frame with -m 0 (`m0`), two frames in flight on two engine
 contexts (`pipelined_2frames`), frames with general sample counts (`nonuniform_*`), the 3840x2160
@@ -14,10 +16,13 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the SAME frame is s
 main pixels (strong scaling); every rank owns a band plus (b+w)*2^(S-1) halo lines of input, rebuilds the pyramid
 for its band, and exchanges marking states, accumulator and output halo lines with its two neighbours over RCCL
 (native driver, bcd_hip_multi_rank_*; the marking follows the visiting order of the whole frame, so the gathered
-frame IS the single-GPU frame -- checked on rank 0 at a reduced size before the timed region).
+frame IS the single-GPU frame -- checked on rank 0 at a reduced size before the timed region with --full).
 
 One JSON line on rank 0 (contract in the task statement), with the extra objects `roofline` (pair-distance
-kernel, HIP-event timed inside this process) and `cpu_baseline` (oracle on host cores, bounded sample).
+kernel, HIP-event timed inside this process) and, with --full, `cpu_baseline` (oracle on host cores, bounded sample).
+--dump-outputs DIR: the denoised frame of the last timed step as DIR/denoised.npy (float32, H x W x 3); a frame above
+DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its pixels instead (denoised.npy: n x 3, denoised_pixel_index.npy:
+the row-major pixel indices as float64).
 """
 import argparse
 import ctypes
@@ -50,19 +55,47 @@ def parse():
     ap.add_argument("--search-radius", type=int, default=6)
     ap.add_argument("--skip-prob", type=float, default=1.0, help="-m of bcd_cli")
     ap.add_argument("--random-order", type=int, default=1, help="-r of bcd_cli")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed legs after the timed region (isolated kernel timing, low-noise frame, -m 0)")
-    ap.add_argument("--no-4k", action="store_true", help="skip the untimed 3840x2160 leg (frame_4k in the JSON line)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: the untimed legs (other frames, sizes and "
+                    "configurations), the distance kernel's arithmetic and isolated timing, the predicted 8-GPU leg, the CPU baseline, and at N > 1 the band "
+                    "equality check and the 4K legs; the --no-* switches below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the denoised frame of the last timed step to DIR/denoised.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed legs after the timed region (isolated kernel timing, low-noise frame, -m 0)")
+    ap.add_argument("--no-4k", action="store_true", help="with --full: skip the untimed 3840x2160 leg (frame_4k in the JSON line)")
     ap.add_argument("--python-bands", action="store_true", help="N > 1: the torch.distributed orchestration of bcd_amd/tiling.py instead of the native driver (test harness)")
     ap.add_argument("--band-marking", action="store_true", help="with --python-bands: every band marks on its own (a valid order, NOT the single-GPU frame)")
     ap.add_argument("--band-path", action="store_true", help="use the multi-GPU row-band code path even with one rank (debug)")
     ap.add_argument("--check-size", default="640x576", help="N > 1: frame size of the equality check against a single-GPU run on rank 0")
     ap.add_argument("--watchdog", type=int, default=900, help="N > 1: seconds after which a run that has not reached its JSON line dumps every thread's stack and exits (a blocked collective would otherwise hang the launcher)")
-    ap.add_argument("--no-predict", action="store_true", help="skip the `predicted_8gpu` leg (one rank's band of the 4K frame through the band driver with RCCL in loopback, in a child process)")
+    ap.add_argument("--no-predict", action="store_true", help="with --full: skip the `predicted_8gpu` leg (one rank's band of the 4K frame through the band driver with RCCL in loopback, in a child process)")
     ap.add_argument("--predict-band-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-sample", default=None, help="frame size of the CPU-baseline sample on all host cores (default: the headline frame itself on hosts with >= 64 cores, 960x540 below)")
     ap.add_argument("--cpu-sample-1core", default="320x240", help="frame size of the one-core CPU-baseline sample")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run is the headline alone: everything else it used to measure or check beside it is asked for with --full
+        args.no_extras = args.no_cpu_baseline = args.no_4k = args.no_predict = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, frame):
+    """the frame a caller of the timed path receives, as float32 .npy files under `path` (at most DUMP_LIMIT_BYTES in all)"""
+    os.makedirs(path, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(path, "denoised.npy"), frame)
+        return
+    # a fixed, seeded sample of pixels: the same pixels for the same frame size in every run
+    H, W, C = frame.shape
+    n = (DUMP_LIMIT_BYTES // 2) // (C * 4)
+    idx = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+    np.save(os.path.join(path, "denoised.npy"), frame.reshape(H * W, C)[idx])
+    np.save(os.path.join(path, "denoised_pixel_index.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(args):
@@ -231,6 +264,9 @@ def main():
 
         def step():
             ctx.denoise(*d_in, S, prm, out)
+
+        def result():
+            return out.cpu().numpy()
     else:
         def python_bands(exact):
             """the same decomposition over torch.distributed (bcd_amd/tiling.py)"""
@@ -238,7 +274,7 @@ def main():
             band = BandDenoiser(ctx, dist, rank, world, W, H, 60, S, prm, exact_marking=exact)
             g0, g1 = band.input_lines()
             band.upload(*core.synthetic_scene(W, H, args.spp, 1234, args.sigma, args.spikes, g0, g1 - g0))
-            return band.step, "rowband%d-%s-torchdist" % (world, "exactmark" if exact else "bandmark")
+            return band.step, "rowband%d-%s-torchdist" % (world, "exactmark" if exact else "bandmark"), lambda: band.out.cpu().numpy()
 
         def native_bands():
             """native driver, one process per GPU: RCCL unique ids from rank 0, one communicator per scale + one for the merges"""
@@ -250,17 +286,18 @@ def main():
             def load(w_, h_):
                 l0, nl, _, _ = rd.configure(w_, h_, 60, S, prm)
                 rd.upload(*core.synthetic_scene(w_, h_, args.spp, 1234, args.sigma, args.spikes, l0, nl))
-            # ---- the band path must reproduce the single-GPU frame: checked at a reduced size, outside the timed region
-            cw, ch = [int(v) for v in args.check_size.split("x")]
-            load(cw, ch)
-            rd.step()
-            parts = [None] * world
-            if world > 1:
-                dist.all_gather_object(parts, rd.download())
-            else:
-                parts = [rd.download()]
+            # ---- the band path must reproduce the single-GPU frame: checked at a reduced size, outside the timed region (--full)
             check = None
-            if rank == 0:
+            if args.full:
+                cw, ch = [int(v) for v in args.check_size.split("x")]
+                load(cw, ch)
+                rd.step()
+                parts = [None] * world
+                if world > 1:
+                    dist.all_gather_object(parts, rd.download())
+                else:
+                    parts = [rd.download()]
+            if args.full and rank == 0:
                 frame = core.synthetic_scene(cw, ch, args.spp, 1234, args.sigma, args.spikes)
                 want = ctx.denoise(*[torch.from_numpy(a).cuda() for a in frame], S, prm).cpu().numpy()
                 got = np.concatenate(parts, 0)
@@ -320,14 +357,14 @@ def main():
             load(W, H)
             rd.step()   # (workspaces and the size of the first marking batch settle in two steps at a new frame size; untimed,
             rd.step()   # before the warm-up steps the caller asked for)
-            return rd.step, "rowband%d-exactmark-native" % world, check
+            return rd.step, "rowband%d-exactmark-native" % world, check, rd.download
 
         band_check, native_error = None, None
         if args.python_bands:
-            step, parallelism = python_bands(not args.band_marking)
+            step, parallelism, result = python_bands(not args.band_marking)
         else:
             try:
-                step, parallelism, band_check = native_bands()
+                step, parallelism, band_check, result = native_bands()
             except Exception as e:   # reported in the JSON line, never silent; every rank must take the same decision
                 native_error = "%s: %s" % (type(e).__name__, e)
             failed = torch.tensor([1 if native_error else 0], device="cuda")
@@ -359,6 +396,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs:
+        # the last timed step's frame, before any untimed leg reuses the output buffer; at N > 1 rank 0 writes the gathered bands
+        part = result()
+        parts = [part]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, np.concatenate(parts, 0))
 
     # ---- roofline of the dominant kernel (pair-distance planes), HIP events on the engine's streams over the timed region
     kt_timed = ctx.kernel_time()

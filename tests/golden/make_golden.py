@@ -6,6 +6,11 @@
                 CovarianceMatrix,MultiscaleDenoiser}.cpp): samples accumulator, pyramid reducers, interpolate, merge,
                 spike filter, histogram/sample-count packing.  These pin the oracle (and, on the GPU box where
                 /root/reference does not exist, the HIP kernels) to the reference bit for bit.
+  ref_units_seeded.npz  (`make_golden.py units`) the seeded inputs of test_oracle_equals_live_reference_units and what the reference's
+                compiled units return for them (accumulator, reducers, interpolate, merge, spike filter), so that the test also runs where
+                oracle/_ref cannot be built.
+  ref_cli_imports.txt  (`make_golden.py cli <reference tree>`) the symbols of namespace bcd that the reference's command-line front-end
+                (src/cli/main.cpp), compiled against this repository's include/bcd, leaves for a library to define (`nm -u` of its object).
   core_patch_trace.npz  (`make_golden.py trace`) SURVEY 8c fixture F3: every intermediate of the two Bayesian steps (noise mean, mean, C,
                 C - N, clamped, + N, inverse, Step-1 estimates, Step-2 mean / covariance / inverse / estimates) for three full-estimate
                 pixels (smallest, median and largest similar set) and one fallback pixel of the core_regression frame, by the ORACLE.
@@ -76,6 +81,46 @@ def main():
     print("fixtures written to", HERE)
 
 
+UNIT_CASES = [(31, 22), (16, 16), (3, 3), (50, 9)]   # (W, H); case i is seeded with i
+
+
+def make_units():
+    r = ol.ref_ops()
+    assert r is not None, "oracle/_ref/libbcd_ref.so missing: run `make -C oracle ref` (needs the reference tree: oracle/Makefile REF)"
+    out = {}
+    for seed, (W, H) in enumerate(UNIT_CASES):
+        p = "c%d_" % seed
+        samples, _ = ol.synth_samples(W, H, 5, seed=seed, sigma=0.5, spike_prob=0.1)
+        ns, mean, cov, hist = r["accumulate"](samples, W, H)
+        out.update({p + "samples": samples, p + "ns": ns, p + "mean": mean, p + "cov": cov, p + "hist": hist})
+        if W >= 4 and H >= 4:
+            lo = r["davg"](mean)
+            out.update({p + "dsum_hist": r["dsum"](hist), p + "dcov": r["dcov"](cov, ns), p + "davg": lo,
+                        p + "interp": r["interp"](lo, H, W), p + "merge": r["merge"](mean, lo)})
+        for k, v in zip(("o_mean", "o_ns", "o_hist", "o_cov"), r["spike"](mean, ns, hist, cov, 1.5)):
+            out[p + k] = v
+    np.savez_compressed(os.path.join(HERE, "ref_units_seeded.npz"), **out)
+    print("reference-unit fixture:", len(UNIT_CASES), "cases")
+
+
+def make_cli_imports(ref_tree):
+    import subprocess
+    import tempfile
+    inc = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+    with tempfile.TemporaryDirectory() as tmp:
+        os.mkdir(os.path.join(tmp, "Eigen"))
+        open(os.path.join(tmp, "Eigen", "Dense"), "w").close()   # main.cpp's vestigial include, as in test_host_library.py
+        obj = os.path.join(tmp, "main.o")
+        subprocess.check_call(["g++", "-std=c++17", "-include", "cstring", "-include", "cmath", "-I", tmp, "-I", inc, "-I", os.path.join(inc, "bcd", "core"),
+                               "-I", os.path.join(inc, "bcd", "io"), "-c", os.path.join(ref_tree, "src", "cli", "main.cpp"), "-o", obj])
+        und = subprocess.check_output(["nm", "-u", obj], text=True).split()
+    syms = sorted(s for s in und if "3bcd" in s)
+    with open(os.path.join(HERE, "ref_cli_imports.txt"), "w") as f:
+        f.write("# symbols of namespace bcd left undefined by the reference's src/cli/main.cpp compiled against include/bcd (make_golden.py cli)\n")
+        f.write("".join(s + "\n" for s in syms))
+    print("reference CLI imports:", len(syms))
+
+
 def trace_pixels(nsim):
     """three full-estimate pixels (smallest / median / largest similar set) + one fallback pixel of the regression frame"""
     H, W = nsim.shape
@@ -103,5 +148,9 @@ def make_trace():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "trace":
         make_trace()
+    elif len(sys.argv) > 1 and sys.argv[1] == "units":
+        make_units()
+    elif len(sys.argv) > 2 and sys.argv[1] == "cli":
+        make_cli_imports(sys.argv[2])
     else:
         main()

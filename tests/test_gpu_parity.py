@@ -1639,7 +1639,8 @@ def test_4k_config4_large_window_prefilter_eight_row_bands(hipctx):
 
 
 def _run_band_bench(extra, nproc, port):
-    """bench.py through its row-band branch in a child process; returns the parsed JSON line"""
+    """bench.py --full through its row-band branch in a child process (the band equality check and the 4K legs are --full parts); returns
+    the parsed JSON line"""
     import json
     import subprocess
     import sys
@@ -1650,7 +1651,7 @@ def _run_band_bench(extra, nproc, port):
         launcher += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(port)]
     else:
         env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    r = subprocess.run(launcher + [_os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--watchdog", "300"] + extra,
+    r = subprocess.run(launcher + [_os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--watchdog", "300", "--full"] + extra,
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -166,3 +166,23 @@ def test_reference_cli_source_compiles_and_links_unchanged_against_this_library(
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True)
     assert "Missing required program argument(s): -i -h -c -o" in r.stdout and "--use-cuda" in r.stdout
+
+
+def test_reference_cli_imports_resolve_against_this_library(tmp_path):
+    """The link half of the test above without the reference tree: every symbol of namespace bcd that the reference's src/cli/main.cpp,
+    compiled against include/bcd, leaves for a library to define (tests/golden/ref_cli_imports.txt, `make_golden.py cli`) is referenced
+    by a stub that must link against libbcdcore.so without undefined symbols and load with every reference bound at start (-z now)."""
+    import subprocess
+    syms = [ln.strip() for ln in open(os.path.join(G, "ref_cli_imports.txt")) if ln.strip() and not ln.startswith("#")]
+    assert len(syms) >= 5
+    lib_dir = os.path.dirname(core.LIB_PATH)
+    src = tmp_path / "stub.c"
+    src.write_text("".join("extern char %s[];\n" % s for s in syms) +
+                   "void *volatile keep[] = {%s};\nint main(void) { return keep[0] == 0; }\n" % ", ".join(syms))
+    exe = str(tmp_path / "stub")
+    cmd = ["gcc", "-fPIC", str(src), "-o", exe, "-Wl,--no-as-needed", "-L" + lib_dir, "-lbcdcore", "-lbcd_hip", "-L/opt/rocm/lib", "-lamdhip64",
+           "-Wl,-rpath," + lib_dir, "-Wl,-z,now"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

@@ -47,10 +47,24 @@ def test_spike_filter_matches_reference_bits():
         assert same(g, f[k]), k
 
 
-@pytest.mark.skipif(not ol.ref_available(), reason="oracle/_ref not built (needs /root/reference; authoring container only)")
 def test_oracle_equals_live_reference_units():
-    """fresh seeded inputs through the compiled reference units and the oracle, bit for bit"""
-    o, r = ol.oracle_ops(), ol.ref_ops()
+    """seeded inputs through the oracle, bit for bit against what the compiled reference units returned for them (ref_units_seeded.npz,
+    tests/golden/make_golden.py units); where oracle/_ref is built, fresh inputs through the live units as well"""
+    o = ol.oracle_ops()
+    f = load("ref_units_seeded.npz")
+    for seed, (W, H) in enumerate([(31, 22), (16, 16), (3, 3), (50, 9)]):
+        g = lambda k: f["c%d_%s" % (seed, k)]
+        ns, mean, cov, hist = o["accumulate"](g("samples"), W, H)
+        assert all(same(x, g(k)) for x, k in zip((ns, mean, cov, hist), ("ns", "mean", "cov", "hist")))
+        if W >= 4 and H >= 4:
+            assert same(o["dsum"](hist), g("dsum_hist")) and same(o["dcov"](cov, ns), g("dcov"))
+            lo = o["davg"](mean)
+            assert same(lo, g("davg")) and same(o["interp"](lo, H, W), g("interp"))
+            assert same(o["merge"](mean, lo), g("merge"))
+        assert all(same(x, g(k)) for x, k in zip(o["spike"](mean, ns, hist, cov, 1.5), ("o_mean", "o_ns", "o_hist", "o_cov")))
+    if not ol.ref_available():
+        return
+    r = ol.ref_ops()
     for seed, (W, H) in enumerate([(31, 22), (16, 16), (3, 3), (50, 9)]):
         samples, _ = ol.synth_samples(W, H, 5, seed=seed, sigma=0.5, spike_prob=0.1)
         a, b = o["accumulate"](samples, W, H), r["accumulate"](samples, W, H)

@@ -3,12 +3,13 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 tools/prof.sh final_noextras --no-extras --steps 10 --warmup 2 > /dev/null
-tools/prof.sh final_default --steps 10 --warmup 2 > /dev/null
+tools/prof.sh final_default --full --steps 10 --warmup 2 > /dev/null
 BCD_HIP_SERIAL_SCALES=1 tools/prof.sh final_serial --no-extras --steps 10 --warmup 2 > /dev/null
 DB=$(ls gpurun_out/prof_final_noextras/*.db | head -1)
 python tools/timeline.py $DB 6.2 > gpurun_out/final_timeline.txt
 for t in final_noextras final_default final_serial; do grep '^{' gpurun_out/${t}_bench.log | tail -1 > gpurun_out/${t}_line.json; done
-python bench.py --steps 30 --warmup 5 > gpurun_out/final_bench_unprofiled.log 2>&1
+OUT=$(dirname "$(dirname "$DB")")   # the folder tools/prof.sh writes to
+python bench.py --full --steps 30 --warmup 5 > $OUT/final_bench_unprofiled.log 2>&1
 grep '^{' gpurun_out/final_bench_unprofiled.log | tail -1 > gpurun_out/final_unprofiled_line.json
 # BASELINE configs[3] / [4] on one GPU (round 4): per-kernel tables of the 4K frame and of the 4K b = 12 frame
 tools/prof.sh final_4k --no-extras --width 3840 --height 2160 --spp 8 --sigma 0.15 --spikes 0 --steps 6 --warmup 2 > /dev/null
