@@ -2,6 +2,7 @@
     libbcd_hip.so   HIP kernels + the C ABI of include/bcd_hip.h
     libbcdcore.so   C++ host library mirroring the reference's include/bcd API (calls the C ABI)
     bcd_cli         the reference's command-line front-end re-implemented on top of libbcdcore
+    raw2bcd         the reference's raw-samples converter, streaming through the device accumulator
 Incremental by mtime; `python -m bcd_amd.build` or `bcd_amd.build.build_all()`."""
 import os
 import subprocess
@@ -21,6 +22,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall",
              "-Wno-unused-result", "-Wno-unused-value", "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt"] + os.environ.get("HIPCC_EXTRA", "").split()
 CXX_FLAGS = ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-fopenmp"]
+
+
+# host sources built as programs (not linked into libbcdcore)
+EXECUTABLES = ("bcd_cli.cpp", "raw2bcd.cpp")
 
 
 def _newer(target, deps):
@@ -67,7 +72,7 @@ def build_host(verbose=False):
     hdrs = []
     for d, _, fs in os.walk(os.path.join(ROOT, "include")):
         hdrs += [os.path.join(d, f) for f in fs]
-    lib_srcs = sorted(f for f in os.listdir(HOST) if f.endswith(".cpp") and f != "bcd_cli.cpp")
+    lib_srcs = sorted(f for f in os.listdir(HOST) if f.endswith(".cpp") and f not in EXECUTABLES)
     if not lib_srcs:
         return None
     objs, jobs = [], []
@@ -81,11 +86,12 @@ def build_host(verbose=False):
     so = os.path.join(LIB, "libbcdcore.so")
     if _newer(so, objs + [os.path.join(LIB, "libbcd_hip.so")]):
         _run(["g++", "-shared", "-fPIC", "-fopenmp", "-o", so] + objs + ["-L" + LIB, "-lbcd_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-Wl,-rpath,$ORIGIN"])
-    cli_src = os.path.join(HOST, "bcd_cli.cpp")
-    if os.path.exists(cli_src):
-        exe = os.path.join(LIB, "bcd_cli")
-        if _newer(exe, [cli_src, so] + hdrs):
-            _run(["g++"] + CXX_FLAGS + inc + [cli_src, "-o", exe, "-L" + LIB, "-lbcdcore", "-lbcd_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-Wl,-rpath,$ORIGIN"])
+    for src in EXECUTABLES:
+        cli_src = os.path.join(HOST, src)
+        if os.path.exists(cli_src):
+            exe = os.path.join(LIB, src[:-4])
+            if _newer(exe, [cli_src, so] + hdrs):
+                _run(["g++"] + CXX_FLAGS + inc + [cli_src, "-o", exe, "-L" + LIB, "-lbcdcore", "-lbcd_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-Wl,-rpath,$ORIGIN"])
     return so
 
 

@@ -51,6 +51,22 @@ def accumulate(samples, W, H, nbins=20, gamma=2.2, maxval=2.5):
     return ns, mean, cov, hist
 
 
+def device_accumulate(samples, W, H, nbins=20, gamma=2.2, maxval=2.5, device=0, snapshot_at=0):
+    """the same stream through bcd::DeviceSamplesAccumulator::addSample (HBM running sums); snapshot_at > 0: a host snapshot after that many
+    samples, then the accumulation goes on"""
+    samples = np.ascontiguousarray(samples, np.float32)
+    ns = np.empty((H, W, 1), np.float32)
+    mean = np.empty((H, W, 3), np.float32)
+    cov = np.empty((H, W, 6), np.float32)
+    hist = np.empty((H, W, 3 * nbins), np.float32)
+    rc = lib().bcdcore_device_accumulate(_fp(samples), C.c_longlong(samples.shape[0]), W, H, nbins, C.c_float(gamma), C.c_float(maxval), int(device),
+                                         C.c_longlong(snapshot_at), _fp(ns), _fp(mean), _fp(cov), _fp(hist))
+    if rc != 0:
+        lib().bcdcore_device_accumulate_error.restype = C.c_char_p
+        raise RuntimeError("DeviceSamplesAccumulator: " + lib().bcdcore_device_accumulate_error().decode())
+    return ns, mean, cov, hist
+
+
 def denoise(col, ns, hist, cov, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, hist_width_override=0,
             use_cuda=True, devices=None, prefilter_factor=0.0):
     """bcd::Denoiser / bcd::MultiscaleDenoiser via IDenoiser; returns (ok, out, progress_monotone).

@@ -68,6 +68,13 @@ hipError_t bcd_launch_sum_counter_lines(const int *, int, int *, hipStream_t, lo
 hipError_t bcd_launch_active_lists(const uint8_t *, const int32_t *, int64_t, int64_t, int, int32_t *, int32_t *, int32_t *, hipStream_t, const long long *);
 hipError_t bcd_launch_jacobi27_batch(const float *, int, int *, int, float *, float *, hipStream_t, float = 1e-12f, float * = nullptr, const int * = nullptr, int = 0);
 size_t bcd_bayes_lds_bytes(int w, int b);
+size_t bcd_accum_snapshot_lds(int D);
+hipError_t bcd_launch_accum_dense(const float *, const float *, int64_t, int64_t, int64_t, int, int, int, float, float, float *, hipStream_t);
+hipError_t bcd_launch_accum_keys(const int32_t *, int64_t, int64_t, uint32_t *, uint32_t *, unsigned long long *, hipStream_t);
+hipError_t bcd_accum_sort(void *, size_t *, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, int64_t, int, hipStream_t);
+hipError_t bcd_launch_accum_segments(const uint32_t *, const uint32_t *, int64_t, int64_t, const float *, const float *, int, float, float, float *,
+                                     hipStream_t);
+hipError_t bcd_launch_accum_snapshot(const float *, int64_t, int, float *, float *, float *, float *, hipStream_t);
 size_t bcd_bayes_scratch_bytes_per_block(int w, int b);
 size_t bcd_bayes27_record_bytes();
 hipError_t bcd_launch_bayes27(const float *, const float *, const uint32_t *, const int32_t *, int, int, int *, int, int, int, int, float, float *, float *,
@@ -1671,6 +1678,148 @@ int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n)
     if (!ctx || !d_img || n <= 0) return bad(ctx, "bad argument");
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, bcd_launch_zero_bad(d_img, n, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+// ---- persistent device SamplesAccumulator (k_accumulate.hip) ----------------------------------------------------
+struct bcd_hip_accum {
+    bcd_hip_ctx *ctx = nullptr;
+    int W = 0, H = 0, nbins = 0;
+    float gamma = 0.f, maxval = 0.f;
+    int64_t N = 0;
+    DevBuf state;                  // (11 + 3 nbins) planes of N floats
+    DevBuf dropped;                // unsigned long long: scattered samples with an index outside [0, N)
+    DevBuf keys[2], vals[2], sort; // scattered-add scratch (grow-only)
+    int64_t capacity = 0;          // > 0: samples per sorted chunk, scratch allocated at create time
+    int64_t submitted = 0;         // samples handed to add_* since the last reset
+};
+
+namespace {
+
+size_t accum_state_bytes(const bcd_hip_accum *a) { return (size_t)(11 + 3 * a->nbins) * (size_t)a->N * sizeof(float); }
+
+// scratch of the scattered path for chunks of n samples
+int accum_scratch(bcd_hip_accum *a, int64_t n)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    for (int i = 0; i < 2; ++i) {
+        RCCHK(ensure(ctx, a->keys[i], (size_t)n * sizeof(uint32_t)));
+        RCCHK(ensure(ctx, a->vals[i], (size_t)n * sizeof(uint32_t)));
+    }
+    size_t bytes = 0;
+    const int end_bit = 64 - __builtin_clzll((unsigned long long)a->N); // keys are <= N (N = dropped)
+    HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, n, end_bit, ctx->stream));
+    RCCHK(ensure(ctx, a->sort, bytes));
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!acc) return bad(ctx, "null accumulator handle");
+    *acc = nullptr;
+    if (W <= 0 || H <= 0 || (int64_t)W * H >= ((int64_t)1 << 31)) return bad(ctx, "frame size must be positive and below 2^31 pixels");
+    if (nb_bins < 2) return bad(ctx, "nb_bins must be >= 2");
+    if (bcd_accum_snapshot_lds(3 * nb_bins) > 64 * 1024) { set_err(ctx, "more than 85 bins per channel are not supported"); return BCD_HIP_EUNSUPPORTED; }
+    if (max_batch_samples < 0 || max_batch_samples >= ((int64_t)1 << 31)) return bad(ctx, "max_batch_samples must be in [0, 2^31)");
+    DEVICE_GUARD(ctx);
+    bcd_hip_accum *a = new (std::nothrow) bcd_hip_accum();
+    if (!a) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
+    a->ctx = ctx; a->W = W; a->H = H; a->nbins = nb_bins; a->gamma = gamma; a->maxval = max_value;
+    a->N = (int64_t)W * H;
+    a->capacity = max_batch_samples;
+    int rc = ensure(ctx, a->state, accum_state_bytes(a));
+    if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
+    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_scratch(a, a->capacity);
+    if (rc == BCD_HIP_OK) rc = bcd_hip_accum_reset(a);
+    if (rc != BCD_HIP_OK) { bcd_hip_accum_destroy(a); return rc; }
+    *acc = a;
+    return BCD_HIP_OK;
+}
+
+void bcd_hip_accum_destroy(bcd_hip_accum *acc)
+{
+    if (!acc) return;
+    DeviceGuard guard(acc->ctx);
+    (void)hipStreamSynchronize(acc->ctx->stream);
+    for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort })
+        if (b->p) (void)hipFree(b->p);
+    delete acc;
+}
+
+int bcd_hip_accum_reset(bcd_hip_accum *acc)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, hipMemsetAsync(acc->state.p, 0, accum_state_bytes(acc), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(acc->dropped.p, 0, sizeof(unsigned long long), ctx->stream));
+    acc->submitted = 0;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!d_samples) return bad(ctx, "null samples");
+    if (channels != 3 && channels != 4) return bad(ctx, "channels must be 3 or 4");
+    if (spp < 1) return bad(ctx, "spp must be >= 1");
+    if (rows < 1 || row_begin < 0 || row_begin > acc->H - rows) return bad(ctx, "row range outside the frame");
+    DEVICE_GUARD(ctx);
+    const int64_t npix = (int64_t)rows * acc->W;
+    HIPCHK(ctx, bcd_launch_accum_dense(d_samples, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, channels, acc->nbins, acc->gamma,
+                                       acc->maxval, (float *)acc->state.p, ctx->stream));
+    acc->submitted += npix * spp;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (n < 0) return bad(ctx, "negative sample count");
+    if (n == 0) return BCD_HIP_OK;
+    if (!d_pixel || !d_rgb) return bad(ctx, "null samples");
+    DEVICE_GUARD(ctx);
+    const int64_t chunk = acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30);
+    if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
+    const int end_bit = 64 - __builtin_clzll((unsigned long long)acc->N);
+    uint32_t *k0 = (uint32_t *)acc->keys[0].p, *k1 = (uint32_t *)acc->keys[1].p, *v0 = (uint32_t *)acc->vals[0].p, *v1 = (uint32_t *)acc->vals[1].p;
+    for (int64_t b = 0; b < n; b += chunk) { // chunks in stream order: a pixel's samples of chunk c are applied after those of chunk c - 1
+        const int64_t m = std::min(chunk, n - b);
+        size_t bytes = acc->sort.bytes;
+        HIPCHK(ctx, bcd_launch_accum_keys(d_pixel + b, m, acc->N, k0, v0, (unsigned long long *)acc->dropped.p, ctx->stream));
+        HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
+        HIPCHK(ctx, bcd_launch_accum_segments(k1, v1, m, acc->N, d_rgb + b * 3, d_weights ? d_weights + b : nullptr, acc->nbins, acc->gamma,
+                                              acc->maxval, (float *)acc->state.p, ctx->stream));
+    }
+    acc->submitted += n;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!d_nsamples || !d_mean || !d_cov || !d_hist) return bad(ctx, "null output");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_accum_snapshot((const float *)acc->state.p, acc->N, 3 * acc->nbins, d_nsamples, d_mean, d_cov, d_hist, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    DEVICE_GUARD(ctx);
+    unsigned long long d = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&d, acc->dropped.p, sizeof(d), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (samples_added) *samples_added = acc->submitted - (int64_t)d;
+    if (dropped) *dropped = (int64_t)d;
     return BCD_HIP_OK;
 }
 

@@ -46,7 +46,8 @@ SYMBOLS = [
     "bcd_hip_multi_rank_download", "bcd_hip_multi_rank_renew_ids", "bcd_hip_multi_set_loopback", "bcd_hip_multi_selftest_transport",
     "bcd_hip_scale_begin", "bcd_hip_pixel_cov", "bcd_hip_similarity_masks", "bcd_hip_similarity_masks_deferred", "bcd_hip_similarity_masks_verdict", "bcd_hip_similarity_masks_exact", "bcd_hip_window_distances", "bcd_hip_active_set", "bcd_hip_active_init", "bcd_hip_active_step", "bcd_hip_active_step_enqueue", "bcd_hip_active_step_collect",
     "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
-    "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_zero_bad_values",
+    "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
+    "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_zero_bad_values",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch",
 ]
 
@@ -296,6 +297,11 @@ class Context:
                                                    C.c_float(gamma), C.c_float(maxval), _dp(ns), _dp(mean), _dp(cov), _dp(hist)))
         return ns, mean, cov, hist
 
+    def accumulator(self, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0):
+        """persistent device SamplesAccumulator of a W x H frame (bcd_hip_accum_*); capacity > 0: scattered batches of up to that many
+        samples never allocate"""
+        return Accumulator(self, W, H, nbins, gamma, maxval, capacity)
+
     def zero_bad_values(self, img):
         self._chk(lib().bcd_hip_zero_bad_values(self.h, _dp(img), C.c_int64(img.numel())))
         return img
@@ -366,6 +372,69 @@ class Context:
 
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
+
+
+class Accumulator:
+    """bcd_hip_accum: running sums in HBM, fed in batches (dense rows or scattered samples, each pixel in stream order), snapshots
+    that go straight into Context.denoise"""
+
+    def __init__(self, ctx, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0):
+        L = lib()
+        L.bcd_hip_accum_create.argtypes = [_VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int64, C.POINTER(_VP)]
+        L.bcd_hip_accum_destroy.argtypes = [_VP]
+        L.bcd_hip_accum_destroy.restype = None
+        L.bcd_hip_accum_add_dense.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.bcd_hip_accum_add_scattered.argtypes = [_VP, _VP, _VP, _VP, C.c_int64]
+        self.ctx, self.W, self.H, self.nbins = ctx, W, H, nbins
+        h = _VP()
+        ctx._chk(L.bcd_hip_accum_create(ctx.h, W, H, nbins, gamma, maxval, capacity, C.byref(h)))
+        self.h = h
+
+    def _chk(self, rc):
+        self.ctx._chk(rc)
+
+    def add_dense(self, samples, weights=None, row0=0):
+        """samples: (rows, W, k, 3 | 4) device tensor, the k samples of a pixel in accumulation order; weights: (rows, W, k) or None"""
+        rows, W, k, ch = samples.shape
+        assert W == self.W, "samples must cover whole rows of the frame"
+        assert weights is None or tuple(weights.shape) == (rows, W, k)
+        self._chk(lib().bcd_hip_accum_add_dense(self.h, _dp(samples), _dp(weights) if weights is not None else None, int(row0), rows, k, ch))
+
+    def add_samples(self, pixel, rgb, weights=None):
+        """pixel: (n,) int32 line * W + col (others are dropped and counted); rgb: (n, 3); weights: (n,) or None"""
+        n = pixel.shape[0]
+        assert pixel.dtype == self.ctx.torch.int32 and tuple(rgb.shape) == (n, 3)
+        assert weights is None or tuple(weights.shape) == (n,)
+        self._chk(lib().bcd_hip_accum_add_scattered(self.h, _dp(pixel), _dp(rgb), _dp(weights) if weights is not None else None, n))
+
+    def statistics(self, out=None):
+        """-> (ns (H, W, 1), mean (H, W, 3), cov (H, W, 6), hist (H, W, 3 nbins)), fresh tensors or the four of `out`; state unchanged"""
+        torch = self.ctx.torch
+        if out is None:
+            mk = lambda d: torch.empty((self.H, self.W, d), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+            out = (mk(1), mk(3), mk(6), mk(3 * self.nbins))
+        self._chk(lib().bcd_hip_accum_statistics(self.h, *[_dp(t) for t in out]))
+        return out
+
+    def reset(self):
+        self._chk(lib().bcd_hip_accum_reset(self.h))
+
+    def info(self):
+        """(samples accumulated, samples dropped) since create / the last reset; synchronises"""
+        a, d = C.c_int64(0), C.c_int64(0)
+        self._chk(lib().bcd_hip_accum_info(self.h, C.byref(a), C.byref(d)))
+        return a.value, d.value
+
+    def close(self):
+        if self.h:
+            lib().bcd_hip_accum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class MultiStats(C.Structure):

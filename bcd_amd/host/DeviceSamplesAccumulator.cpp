@@ -1,0 +1,211 @@
+// DeviceSamplesAccumulator.cpp -- bcd::SamplesAccumulator with its running sums in HBM (bcd_hip_accum_*, k_accumulate.hip).
+// addSample appends to a pinned host batch; a full batch (or a snapshot) copies it to the device and applies it through the
+// scattered add, which keeps every pixel's samples in call order.  While the device works on one batch the next one fills.
+#include "DeviceSamplesAccumulator.h"
+#include "bcd_hip.h"
+
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <utility>
+
+namespace bcd
+{
+
+	DeviceSamplesAccumulator::DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_device) :
+			m_width(i_width), m_height(i_height), m_nbOfBins(i_rHistogramParameters.m_nbOfBins)
+	{
+		int prev = -1;
+		(void)hipGetDevice(&prev);
+		hipStream_t stream = nullptr;
+		if(hipSetDevice(i_device) != hipSuccess || hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess)
+		{
+			m_error = "no usable HIP device";
+			if(prev >= 0) (void)hipSetDevice(prev);
+			return;
+		}
+		m_stream = stream;
+		hipEvent_t ev = nullptr;
+		const size_t batchBytes = size_t(s_batchCapacity) * (sizeof(int32_t) + 4 * sizeof(float));
+		const size_t statsBytes = size_t(i_width) * size_t(i_height) * (10 + 3 * size_t(m_nbOfBins)) * sizeof(float);
+		if(hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess
+				|| hipHostMalloc((void**)&m_pHostPixel, size_t(s_batchCapacity) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess
+				|| hipHostMalloc((void**)&m_pHostRgbw, size_t(s_batchCapacity) * 4 * sizeof(float), hipHostMallocDefault) != hipSuccess
+				|| hipMalloc(&m_pDeviceBatch, batchBytes) != hipSuccess || hipMalloc(&m_pDeviceStats, statsBytes) != hipSuccess)
+		{
+			m_batchCopied = ev;
+			m_error = "out of device or pinned host memory";
+			if(prev >= 0) (void)hipSetDevice(prev);
+			return;
+		}
+		m_batchCopied = ev;
+		if(bcd_hip_ctx_create(&m_pContext, i_device, m_stream) != BCD_HIP_OK)
+			m_error = "bcd_hip_ctx_create failed";
+		else if(bcd_hip_accum_create(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma, i_rHistogramParameters.m_maxValue,
+				s_batchCapacity, &m_pAccum) != BCD_HIP_OK)
+		{
+			m_error = bcd_hip_last_error(m_pContext);
+			m_pAccum = nullptr;
+		}
+		if(prev >= 0) (void)hipSetDevice(prev);
+	}
+
+	DeviceSamplesAccumulator::~DeviceSamplesAccumulator()
+	{
+		if(m_stream) (void)hipStreamSynchronize((hipStream_t)m_stream);
+		bcd_hip_accum_destroy(m_pAccum);
+		bcd_hip_ctx_destroy(m_pContext);
+		if(m_pDeviceBatch) (void)hipFree(m_pDeviceBatch);
+		if(m_pDeviceStats) (void)hipFree(m_pDeviceStats);
+		if(m_pHostPixel) (void)hipHostFree(m_pHostPixel);
+		if(m_pHostRgbw) (void)hipHostFree(m_pHostRgbw);
+		if(m_batchCopied) (void)hipEventDestroy((hipEvent_t)m_batchCopied);
+		if(m_stream) (void)hipStreamDestroy((hipStream_t)m_stream);
+	}
+
+	void DeviceSamplesAccumulator::fail(const char* i_pWhat) const
+	{
+		m_error = std::string(i_pWhat) + ": " + (m_pContext ? bcd_hip_last_error(m_pContext) : "no context");
+	}
+
+	void DeviceSamplesAccumulator::addSample(int i_line, int i_column, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight)
+	{
+		if(!isValid())
+			return;
+		if(m_pending == 0 && m_copyInFlight)
+		{	// the previous batch is still being copied out of the pinned buffer
+			(void)hipEventSynchronize((hipEvent_t)m_batchCopied);
+			m_copyInFlight = false;
+		}
+		const int64_t i = m_pending++;
+		m_pHostPixel[i] = (i_line < 0 || i_line >= m_height || i_column < 0 || i_column >= m_width) ? -1 : i_line * m_width + i_column;
+		float* rgb = m_pHostRgbw + 3 * i;
+		rgb[0] = i_sampleR; rgb[1] = i_sampleG; rgb[2] = i_sampleB;
+		m_pHostRgbw[3 * s_batchCapacity + i] = i_weight;
+		if(m_pending == s_batchCapacity)
+			flush();
+	}
+
+	void DeviceSamplesAccumulator::addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples)
+	{
+		if(!isValid())
+			return;
+		for(int64_t done = 0; done < i_nbOfSamples; )
+		{
+			if(m_pending == 0 && m_copyInFlight)
+			{
+				(void)hipEventSynchronize((hipEvent_t)m_batchCopied);
+				m_copyInFlight = false;
+			}
+			const int64_t n = std::min(s_batchCapacity - m_pending, i_nbOfSamples - done);
+			std::memcpy(m_pHostPixel + m_pending, i_pPixelIndices + done, size_t(n) * sizeof(int32_t));
+			std::memcpy(m_pHostRgbw + 3 * m_pending, i_pRgb + 3 * done, size_t(n) * 3 * sizeof(float));
+			float* w = m_pHostRgbw + 3 * s_batchCapacity + m_pending;
+			if(i_pWeights) std::memcpy(w, i_pWeights + done, size_t(n) * sizeof(float));
+			else std::fill(w, w + n, 1.f);
+			m_pending += n;
+			done += n;
+			if(m_pending == s_batchCapacity)
+				flush();
+		}
+	}
+
+	void DeviceSamplesAccumulator::flush() const
+	{
+		if(!isValid() || m_pending == 0)
+			return;
+		const int64_t n = m_pending, cap = s_batchCapacity;
+		hipStream_t st = (hipStream_t)m_stream;
+		int32_t* dPix = (int32_t*)m_pDeviceBatch;
+		float* dRgb = (float*)(dPix + cap);
+		float* dW = dRgb + 3 * cap;
+		if(hipMemcpyAsync(dPix, m_pHostPixel, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess
+				|| hipMemcpyAsync(dRgb, m_pHostRgbw, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess
+				|| hipMemcpyAsync(dW, m_pHostRgbw + 3 * cap, size_t(n) * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess
+				|| hipEventRecord((hipEvent_t)m_batchCopied, st) != hipSuccess)
+		{
+			m_error = "batch upload failed";
+			return;
+		}
+		m_copyInFlight = true;
+		m_pending = 0;
+		if(bcd_hip_accum_add_scattered(m_pAccum, dPix, dRgb, dW, n) != BCD_HIP_OK)
+			fail("bcd_hip_accum_add_scattered");
+	}
+
+	DeviceSamplesAccumulator::DeviceStatistics DeviceSamplesAccumulator::computeDeviceStatistics() const
+	{
+		DeviceStatistics s;
+		if(!isValid())
+			return s;
+		flush();
+		const size_t n = size_t(m_width) * size_t(m_height);
+		float* p = (float*)m_pDeviceStats;
+		s.m_pContext = m_pContext;
+		s.m_pNbOfSamples = p;
+		s.m_pMean = p + n;
+		s.m_pCovariances = p + 4 * n;
+		s.m_pHistograms = p + 10 * n;
+		s.m_width = m_width; s.m_height = m_height; s.m_depth = 3 * m_nbOfBins;
+		if(bcd_hip_accum_statistics(m_pAccum, p, p + n, p + 4 * n, p + 10 * n) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_statistics");
+			return DeviceStatistics();
+		}
+		return s;
+	}
+
+	SamplesStatisticsImages DeviceSamplesAccumulator::getSamplesStatistics() const
+	{
+		SamplesStatisticsImages out(m_width, m_height, m_nbOfBins);
+		const DeviceStatistics d = computeDeviceStatistics();
+		if(!d.m_pNbOfSamples)
+			return out;
+		hipStream_t st = (hipStream_t)m_stream;
+		const std::pair<DeepImage<float>*, const float*> parts[4] = { { &out.m_nbOfSamplesImage, d.m_pNbOfSamples }, { &out.m_meanImage, d.m_pMean },
+				{ &out.m_covarImage, d.m_pCovariances }, { &out.m_histoImage, d.m_pHistograms } };
+		for(const auto& pr : parts)
+			if(hipMemcpyAsync(pr.first->getDataPtr(), pr.second, pr.first->getDataPtr() ? size_t(m_width) * m_height * pr.first->getDepth() * sizeof(float) : 0,
+					hipMemcpyDeviceToHost, st) != hipSuccess)
+				m_error = "statistics download failed";
+		if(hipStreamSynchronize(st) != hipSuccess)
+			m_error = "statistics download failed";
+		return out;
+	}
+
+	SamplesStatisticsImages DeviceSamplesAccumulator::extractSamplesStatistics()
+	{
+		SamplesStatisticsImages out = getSamplesStatistics();
+		m_isValid = false;
+		return out;
+	}
+
+	void DeviceSamplesAccumulator::reset()
+	{
+		if(!isValid())
+			return;
+		m_pending = 0;
+		if(bcd_hip_accum_reset(m_pAccum) != BCD_HIP_OK)
+			fail("bcd_hip_accum_reset");
+	}
+
+	int64_t DeviceSamplesAccumulator::nbOfAccumulatedSamples() const
+	{
+		flush();
+		int64_t added = 0;
+		if(m_pAccum && bcd_hip_accum_info(m_pAccum, &added, nullptr) != BCD_HIP_OK)
+			fail("bcd_hip_accum_info");
+		return added;
+	}
+
+	int64_t DeviceSamplesAccumulator::nbOfDroppedSamples() const
+	{
+		flush();
+		int64_t dropped = 0;
+		if(m_pAccum && bcd_hip_accum_info(m_pAccum, nullptr, &dropped) != BCD_HIP_OK)
+			fail("bcd_hip_accum_info");
+		return dropped;
+	}
+
+} // namespace bcd

@@ -1,6 +1,7 @@
 // capi.cpp -- plain-C exports of libbcdcore for the Python plumbing (bench.py, tests): synthetic scenes,
 // the SamplesAccumulator, Utils packing, and the bcd::Denoiser / bcd::MultiscaleDenoiser classes themselves.
 #include "Denoiser.h"
+#include "DeviceSamplesAccumulator.h"
 #include "MultiscaleDenoiser.h"
 #include "SamplesAccumulator.h"
 #include "SpikeRemovalFilter.h"
@@ -9,6 +10,7 @@
 
 #include <cstdio>
 #include <memory>
+#include <string>
 
 using namespace bcd;
 
@@ -70,6 +72,34 @@ int bcdcore_accumulate_threadsafe(const float* s, long long n, int W, int H, int
 		acc.addSampleThreadSafely(int(p[0]), int(p[1]), p[2], p[3], p[4], p[5]);
 	}
 	SamplesStatisticsImages st = acc.getSamplesStatistics();
+	st.m_nbOfSamplesImage.copyDataTo(ns);
+	st.m_meanImage.copyDataTo(mean);
+	st.m_covarImage.copyDataTo(cov);
+	st.m_histoImage.copyDataTo(hist);
+	return 0;
+}
+
+// the same stream through bcd::DeviceSamplesAccumulator::addSample on `device`; a non-destructive host snapshot is taken after the first
+// `snapshot_at` samples (0: none) and the accumulation goes on.  Returns 0, or -1 with the class's message in bcdcore_device_accumulate_error()
+static std::string g_deviceAccumulateError;
+const char* bcdcore_device_accumulate_error() { return g_deviceAccumulateError.c_str(); }
+
+int bcdcore_device_accumulate(const float* s, long long n, int W, int H, int nbins, float gamma, float maxval, int device, long long snapshot_at,
+		float* ns, float* mean, float* cov, float* hist)
+{
+	HistogramParameters hp;
+	hp.m_nbOfBins = nbins; hp.m_gamma = gamma; hp.m_maxValue = maxval;
+	DeviceSamplesAccumulator acc(W, H, hp, device);
+	g_deviceAccumulateError.clear();
+	if(!acc.isValid()) { g_deviceAccumulateError = acc.lastError(); return -1; }
+	for(long long i = 0; i < n; ++i, s += 6)
+	{
+		if(i == snapshot_at && snapshot_at > 0)
+			(void)acc.getSamplesStatistics();
+		acc.addSample(int(s[0]), int(s[1]), s[2], s[3], s[4], s[5]);
+	}
+	SamplesStatisticsImages st = acc.extractSamplesStatistics();
+	if(!acc.lastError().empty()) { g_deviceAccumulateError = acc.lastError(); return -1; }
 	st.m_nbOfSamplesImage.copyDataTo(ns);
 	st.m_meanImage.copyDataTo(mean);
 	st.m_covarImage.copyDataTo(cov);

@@ -1,0 +1,87 @@
+// DeviceSamplesAccumulator.h -- SamplesAccumulator whose running sums live in HBM (the bcd_hip_accum_* entry points of bcd_hip.h).
+// Same public surface as bcd::SamplesAccumulator (SamplesAccumulator.h): addSample buffers on the host in call order and the buffer
+// is flushed through the device's scattered add, so every pixel accumulates its samples in call order with the host class's float
+// operations (nSamples, mean and covariance bit-identical; histograms to the device powf's round-off).  Snapshots are non-destructive
+// and can stay on the device for bcd_hip_denoise.
+#ifndef DEVICE_SAMPLES_ACCUMULATOR_H
+#define DEVICE_SAMPLES_ACCUMULATOR_H
+
+#include "SamplesAccumulator.h"
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+struct bcd_hip_ctx;
+struct bcd_hip_accum;
+
+namespace bcd
+{
+
+	class DeviceSamplesAccumulator
+	{
+	public:
+		/// device statistics images in DeepImage layout, owned by the accumulator and valid until the next snapshot or destruction;
+		/// the arguments of bcd_hip_denoise(context, m_pMean, m_pNbOfSamples, m_pHistograms, m_pCovariances, width, height, depth, ...)
+		struct DeviceStatistics
+		{
+			bcd_hip_ctx* m_pContext = nullptr; ///< the context whose stream orders the snapshot
+			const float* m_pNbOfSamples = nullptr;
+			const float* m_pMean = nullptr;
+			const float* m_pCovariances = nullptr;
+			const float* m_pHistograms = nullptr;
+			int m_width = 0, m_height = 0, m_depth = 0;
+		};
+
+		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_device = 0);
+		~DeviceSamplesAccumulator();
+		DeviceSamplesAccumulator(const DeviceSamplesAccumulator&) = delete;
+		DeviceSamplesAccumulator& operator=(const DeviceSamplesAccumulator&) = delete;
+
+		/// false when the device could not be set up (message in lastError()); every other call is then a no-op
+		bool isValid() const { return m_pAccum != nullptr && m_isValid; }
+		const std::string& lastError() const { return m_error; }
+
+		void addSample(int i_line, int i_column, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight = 1.f);
+		/// n samples from host memory, in order: pixel index line * width + column, rgb [n][3], weights [n] or nullptr (all 1).
+		/// Indices outside the frame are skipped (and counted by nbOfDroppedSamples()).
+		void addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples);
+
+		/// copy of the statistics accumulated so far (the accumulator goes on)
+		SamplesStatisticsImages getSamplesStatistics() const;
+		/// moves the statistics out; the accumulator must not be used afterwards
+		SamplesStatisticsImages extractSamplesStatistics();
+		/// enqueues a snapshot into device buffers owned by the accumulator (no host copy, no synchronisation) and returns them
+		DeviceStatistics computeDeviceStatistics() const;
+
+		/// back to an empty accumulator (the frame geometry and the device buffers are kept)
+		void reset();
+		/// samples accumulated / skipped since construction or the last reset (synchronises)
+		int64_t nbOfAccumulatedSamples() const;
+		int64_t nbOfDroppedSamples() const;
+
+	private:
+		void flush() const;
+		void fail(const char* i_pWhat) const;
+
+	private:
+		int m_width, m_height, m_nbOfBins;
+		bcd_hip_ctx* m_pContext = nullptr;
+		bcd_hip_accum* m_pAccum = nullptr;
+		bool m_isValid = true;
+		mutable std::string m_error;
+		// host-side batch of addSample calls (pinned), and its device copy
+		static const int64_t s_batchCapacity = int64_t(1) << 20;
+		mutable int64_t m_pending = 0;
+		int32_t* m_pHostPixel = nullptr;
+		float* m_pHostRgbw = nullptr; // rgb [capacity][3] then weights [capacity]
+		void* m_pDeviceBatch = nullptr;
+		void* m_stream = nullptr;        // hipStream_t of the context
+		void* m_batchCopied = nullptr;   // hipEvent_t: the pinned batch has reached the device
+		mutable bool m_copyInFlight = false;
+		void* m_pDeviceStats = nullptr; // ns | mean | cov | hist of computeDeviceStatistics
+	};
+
+} // namespace bcd
+
+#endif // DEVICE_SAMPLES_ACCUMULATOR_H

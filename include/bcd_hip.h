@@ -330,6 +330,28 @@ int bcd_hip_spike_filter(bcd_hip_ctx *ctx, const float *d_colors, const float *d
  * and in accumulation order; d_weights: W*H*spp floats or NULL (all 1).  Outputs in DeepImage layout, hist depth 3*nb_bins. */
 int bcd_hip_accumulate_samples(bcd_hip_ctx *ctx, const float *d_samples, const float *d_weights, int W, int H, int spp, int nb_bins,
                                float gamma, float max_value, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist);
+/* Persistent device SamplesAccumulator: the running sums of SamplesAccumulator (src/core/SamplesAccumulator.cpp:44-105) kept in HBM
+ * between calls, fed in batches of any pixel order and any per-pixel count, snapshotted into the four statistics images in DeepImage
+ * layout (the inputs of bcd_hip_denoise) without being changed.  Each pixel accumulates its samples in stream order -- batch after
+ * batch, and within a scattered batch in the order given -- with the host class's float operations, so nSamples, mean and covariance
+ * are bit-identical to bcd::SamplesAccumulator fed the same stream (histograms: device powf round-off); no float atomics.
+ * Work is enqueued on the context's stream; only _info synchronises it.  The context must outlive the accumulator.
+ *   create: nb_bins in [2, 85]; max_batch_samples > 0 allocates the scattered-add scratch for batches of that many samples at once
+ *           (larger batches are applied in chunks of that size; no add allocates), 0 grows it with the batches
+ *   add_dense: rows [row_begin, row_begin + rows), spp >= 1 samples per pixel, contiguous, in accumulation order:
+ *           d_samples[((line - row_begin) * W + col) * spp + i][channels], channels 3 or 4 (the 4th is ignored);
+ *           d_weights [rows * W * spp] or NULL (all 1)
+ *   add_scattered: n samples: d_pixel[n] = line * W + col (int32; others are skipped and counted), d_rgb[n][3], d_weights[n] or NULL
+ *   statistics: d_nsamples W*H, d_mean W*H*3, d_cov W*H*6, d_hist W*H*3*nb_bins (a pixel without samples: 1/0 -> NaN / inf, as the host)
+ *   info: samples accumulated and samples dropped (out-of-range indices) since create / the last reset; synchronises */
+typedef struct bcd_hip_accum bcd_hip_accum;
+int  bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc);
+void bcd_hip_accum_destroy(bcd_hip_accum *acc);
+int  bcd_hip_accum_reset(bcd_hip_accum *acc);
+int  bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels);
+int  bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n);
+int  bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist);
+int  bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped);
 /* checkAndPutToZeroNegativeInfNaNValues   src/cli/main.cpp:389-420 */
 int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n);
 
