@@ -67,6 +67,28 @@ def device_accumulate(samples, W, H, nbins=20, gamma=2.2, maxval=2.5, device=0, 
     return ns, mean, cov, hist
 
 
+def device_plan(samples, W, H, budget, offset=0, threshold=0.0, eps=1e-3, min_samples=2.0, max_per_pixel=16, nbins=20, gamma=2.2, maxval=2.5,
+                device=0, invalid_first=False):
+    """the stream through bcd::DeviceSamplesAccumulator::addSample (left in its host buffer), then planSamples -> (pixel list, summary dict);
+    invalid_first: two planSamples calls with invalid arguments come first and must fail"""
+    samples = np.ascontiguousarray(samples, np.float32)
+    pixels = np.empty(max(int(budget), 1), np.int32)
+    summary = np.zeros(4, np.float64)
+    L = lib()
+    L.bcdcore_device_plan.restype = C.c_longlong
+    T = L.bcdcore_device_plan(_fp(samples), C.c_longlong(samples.shape[0]), W, H, nbins, C.c_float(gamma), C.c_float(maxval), int(device),
+                              C.c_longlong(budget), C.c_ulonglong(offset), C.c_float(threshold), C.c_float(eps), C.c_float(min_samples),
+                              int(max_per_pixel), int(bool(invalid_first)), pixels.ctypes.data_as(C.POINTER(C.c_int)),
+                              summary.ctypes.data_as(C.POINTER(C.c_double)))
+    if T == -2:
+        raise RuntimeError("DeviceSamplesAccumulator::planSamples accepted invalid arguments")
+    if T < 0:
+        L.bcdcore_device_accumulate_error.restype = C.c_char_p
+        raise RuntimeError("DeviceSamplesAccumulator: " + L.bcdcore_device_accumulate_error().decode())
+    return pixels[:T].copy(), {"planned": int(summary[0]), "active": int(summary[1]), "unsampled": int(summary[2]),
+                               "max_error": float(np.float32(summary[3]))}
+
+
 def denoise(col, ns, hist, cov, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, hist_width_override=0,
             use_cuda=True, devices=None, prefilter_factor=0.0):
     """bcd::Denoiser / bcd::MultiscaleDenoiser via IDenoiser; returns (ok, out, progress_monotone).

@@ -75,6 +75,10 @@ hipError_t bcd_accum_sort(void *, size_t *, const uint32_t *, uint32_t *, const 
 hipError_t bcd_launch_accum_segments(const uint32_t *, const uint32_t *, int64_t, int64_t, const float *, const float *, int, float, float, float *,
                                      hipStream_t);
 hipError_t bcd_launch_accum_snapshot(const float *, int64_t, int, float *, float *, float *, float *, hipStream_t);
+size_t bcd_plan_red_bytes();
+hipError_t bcd_plan_scan_bytes(int64_t, size_t *);
+hipError_t bcd_launch_accum_plan(const float *, int64_t, float, float, float, int, int64_t, uint64_t, float *, int32_t *, int32_t *, int64_t, int64_t *,
+                                 void *, uint64_t *, int32_t *, void *, size_t, hipStream_t);
 size_t bcd_bayes_scratch_bytes_per_block(int w, int b);
 size_t bcd_bayes27_record_bytes();
 hipError_t bcd_launch_bayes27(const float *, const float *, const uint32_t *, const int32_t *, int, int, int *, int, int, int, int, float, float *, float *,
@@ -1692,6 +1696,8 @@ struct bcd_hip_accum {
     DevBuf keys[2], vals[2], sort; // scattered-add scratch (grow-only)
     int64_t capacity = 0;          // > 0: samples per sorted chunk, scratch allocated at create time
     int64_t submitted = 0;         // samples handed to add_* since the last reset
+    DevBuf plan_red, plan_c, plan_ends, plan_err, plan_cnt, plan_tmp; // adaptive-plan scratch (allocated once per accumulator)
+    bool plan_ready = false;       // the plan scratch is allocated (N is fixed, so it is never resized)
 };
 
 namespace {
@@ -1710,6 +1716,25 @@ int accum_scratch(bcd_hip_accum *a, int64_t n)
     const int end_bit = 64 - __builtin_clzll((unsigned long long)a->N); // keys are <= N (N = dropped)
     HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, n, end_bit, ctx->stream));
     RCCHK(ensure(ctx, a->sort, bytes));
+    return BCD_HIP_OK;
+}
+
+// scratch of the adaptive plan: reductions, C (uint64), ends (int32), the error and counts images used when the caller passes none, and
+// the scans' temporary storage; the frame size is fixed, so this sizes and allocates once (a failed attempt is retried by the next plan)
+int accum_plan_scratch(bcd_hip_accum *a)
+{
+    if (a->plan_ready) return BCD_HIP_OK;
+    bcd_hip_ctx *ctx = a->ctx;
+    const size_t N = (size_t)a->N;
+    size_t tmp = 0;
+    HIPCHK(ctx, bcd_plan_scan_bytes(a->N, &tmp));
+    RCCHK(ensure(ctx, a->plan_red, bcd_plan_red_bytes()));
+    RCCHK(ensure(ctx, a->plan_c, N * sizeof(uint64_t)));
+    RCCHK(ensure(ctx, a->plan_ends, N * sizeof(int32_t)));
+    RCCHK(ensure(ctx, a->plan_err, N * sizeof(float)));
+    RCCHK(ensure(ctx, a->plan_cnt, N * sizeof(int32_t)));
+    RCCHK(ensure(ctx, a->plan_tmp, tmp));
+    a->plan_ready = true;
     return BCD_HIP_OK;
 }
 
@@ -1733,6 +1758,7 @@ int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamm
     int rc = ensure(ctx, a->state, accum_state_bytes(a));
     if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
     if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_scratch(a, a->capacity);
+    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_plan_scratch(a);
     if (rc == BCD_HIP_OK) rc = bcd_hip_accum_reset(a);
     if (rc != BCD_HIP_OK) { bcd_hip_accum_destroy(a); return rc; }
     *acc = a;
@@ -1744,7 +1770,8 @@ void bcd_hip_accum_destroy(bcd_hip_accum *acc)
     if (!acc) return;
     DeviceGuard guard(acc->ctx);
     (void)hipStreamSynchronize(acc->ctx->stream);
-    for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort })
+    for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
+                       &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
         if (b->p) (void)hipFree(b->p);
     delete acc;
 }
@@ -1820,6 +1847,41 @@ int bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *drop
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (samples_added) *samples_added = acc->submitted - (int64_t)d;
     if (dropped) *dropped = (int64_t)d;
+    return BCD_HIP_OK;
+}
+
+// k_plan_summary writes the summary as int64[3] then a float
+static_assert(sizeof(bcd_hip_plan_summary) == 32 && offsetof(bcd_hip_plan_summary, max_error) == 24, "bcd_hip_plan_summary layout");
+
+void bcd_hip_default_plan_params(bcd_hip_plan_params *p)
+{
+    if (!p) return;
+    p->threshold = 0.f;
+    p->eps = 1e-3f;
+    p->min_samples = 2.f;
+    p->max_per_pixel = 16;
+}
+
+int bcd_hip_accum_plan(bcd_hip_accum *acc, const bcd_hip_plan_params *prm, int64_t budget, uint64_t offset, float *d_error, int32_t *d_counts,
+                       int32_t *d_pixels, int64_t capacity, bcd_hip_plan_summary *d_summary)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!prm) return bad(ctx, "null plan parameters");
+    if (!d_pixels || !d_summary) return bad(ctx, "null pixel list or summary");
+    if (budget < 0 || budget > INT32_MAX) return bad(ctx, "budget must be in [0, 2^31)");
+    if (capacity < budget) return bad(ctx, "pixel list capacity below the budget");
+    if (!std::isfinite(prm->threshold) || prm->threshold < 0.f) return bad(ctx, "threshold must be finite and >= 0");
+    if (!std::isfinite(prm->eps) || !(prm->eps > 0.f)) return bad(ctx, "eps must be finite and > 0");
+    if (!std::isfinite(prm->min_samples) || prm->min_samples < 0.f) return bad(ctx, "min_samples must be finite and >= 0");
+    if (prm->max_per_pixel < 1 || prm->max_per_pixel > 65535) return bad(ctx, "max_per_pixel must be in [1, 65535]");
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_plan_scratch(acc));
+    HIPCHK(ctx, hipMemsetAsync(acc->plan_red.p, 0, bcd_plan_red_bytes(), ctx->stream));
+    HIPCHK(ctx, bcd_launch_accum_plan((const float *)acc->state.p, acc->N, prm->eps, prm->min_samples, prm->threshold, prm->max_per_pixel, budget,
+                                      offset, d_error ? d_error : (float *)acc->plan_err.p, d_counts ? d_counts : (int32_t *)acc->plan_cnt.p,
+                                      d_pixels, capacity, (int64_t *)d_summary, acc->plan_red.p, (uint64_t *)acc->plan_c.p,
+                                      (int32_t *)acc->plan_ends.p, acc->plan_tmp.p, acc->plan_tmp.bytes, ctx->stream));
     return BCD_HIP_OK;
 }
 

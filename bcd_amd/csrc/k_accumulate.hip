@@ -60,6 +60,20 @@ struct AccSums {
     }
 };
 
+// computeSampleStatistics of one pixel (SamplesAccumulator.cpp:108-141): the mean and the bias-corrected covariance (xx,yy,zz,yz,xz,xy);
+// the number of samples is s.wsum.  Shared by the snapshot and the plan's error pass, so that both see the same bits.
+__device__ inline void acc_statistics(const AccSums &s, float mean[3], float cov[6])
+{
+    const float inv = 1.f / s.wsum;
+    for (int i = 0; i < 3; ++i) mean[i] = inv * s.m[i];
+    float cv[6];
+    for (int i = 0; i < 6; ++i) cv[i] = s.c[i] * inv;
+    cv[0] -= mean[0] * mean[0]; cv[1] -= mean[1] * mean[1]; cv[2] -= mean[2] * mean[2];
+    cv[3] -= mean[1] * mean[2]; cv[4] -= mean[0] * mean[2]; cv[5] -= mean[0] * mean[1];
+    const float bias = 1.f / (1 - s.w2sum / (s.wsum * s.wsum));
+    for (int i = 0; i < 6; ++i) cov[i] = cv[i] * bias;
+}
+
 // (a) dense add: pixels [p0, p0 + npix) of the frame, k samples each (contiguous, `channels` floats per sample, the 4th ignored).
 // STAGED = false: the 6k touched bins are read-modified-written in HBM directly (a progressive pass of k = 1 moves 6 of the D bins);
 // STAGED = true: the pixel's D bins are loaded into LDS ([bin][thread], bank-conflict free), accumulated there and written back once.
@@ -164,15 +178,10 @@ __global__ __launch_bounds__(64) void k_accum_snapshot(const float *__restrict__
     if (t < cnt) {
         AccSums s;
         s.load(st, N, p);
-        const float inv = 1.f / s.wsum;
-        float mean[3];
-        for (int i = 0; i < 3; ++i) { mean[i] = inv * s.m[i]; omean[p * 3 + i] = mean[i]; }
-        float cv[6];
-        for (int i = 0; i < 6; ++i) cv[i] = s.c[i] * inv;
-        cv[0] -= mean[0] * mean[0]; cv[1] -= mean[1] * mean[1]; cv[2] -= mean[2] * mean[2];
-        cv[3] -= mean[1] * mean[2]; cv[4] -= mean[0] * mean[2]; cv[5] -= mean[0] * mean[1];
-        const float bias = 1.f / (1 - s.w2sum / (s.wsum * s.wsum));
-        for (int i = 0; i < 6; ++i) ocov[p * 6 + i] = cv[i] * bias;
+        float mean[3], cov[6];
+        acc_statistics(s, mean, cov);
+        for (int i = 0; i < 3; ++i) omean[p * 3 + i] = mean[i];
+        for (int i = 0; i < 6; ++i) ocov[p * 6 + i] = cov[i];
         ons[p] = s.wsum;
         const float *hp = st + (int64_t)ACC_H * N + p;
         for (int b = 0; b < D; ++b) lds_t[t * (D + 1) + b] = hp[b * N];
@@ -182,6 +191,143 @@ __global__ __launch_bounds__(64) void k_accum_snapshot(const float *__restrict__
     for (int e = t; e < cnt * D; e += 64) {
         const int q = e / D;
         oh[e] = lds_t[q * (D + 1) + (e - q * D)];
+    }
+}
+
+// (d) adaptive plan (bcd_hip_accum_plan).  Reductions of the error pass: the largest finite error of the active
+// pixels as float bits (errors are >= 0, so the bits order like the values: an integer max is exact and order-independent), and the
+// active / unsampled counts packed in one word (active << 32 | unsampled; both < 2^31, so the low half never carries).
+struct PlanRed {
+    unsigned int emax, pad;
+    unsigned long long counts;
+};
+
+// e_p: the relative standard error of the pixel's mean, sqrt(trace(cov / n) / 3) / (eps + luminance), from the snapshot's statistics;
+// +inf for pixels below min_samples and for non-finite statistics
+__device__ inline float plan_error(const AccSums &s, float eps, float min_samples)
+{
+    float mean[3], cov[6];
+    acc_statistics(s, mean, cov);
+    const float ns = s.wsum, inv = 1.f / ns;
+    const float t = (cov[0] * inv + cov[1] * inv) + cov[2] * inv;
+    const float l = (mean[0] + mean[1]) + mean[2];
+    if (!(ns >= min_samples) || !__builtin_isfinite(t) || !__builtin_isfinite(l)) return __builtin_inff();
+    return sqrtf(fmaxf(t / 3.f, 0.f)) / (eps + fmaxf(l / 3.f, 0.f));
+}
+
+// plane-major error pass: 11 state planes in, e out, over a grid of at most PLAN_ERROR_BLOCKS workgroups striding the frame; one
+// wavefront reduction per wave, then one integer atomic per workgroup and word (the atomics all hit one address and serialise in L2,
+// so their number is kept near the CU count rather than N / 256)
+#define PLAN_ERROR_BLOCKS 1024
+__global__ __launch_bounds__(256) void k_plan_error(const float *__restrict__ st, int64_t N, float eps, float min_samples, float tau,
+                                                    float *__restrict__ err, PlanRed *__restrict__ red)
+{
+    __shared__ unsigned int s_e[4];
+    __shared__ unsigned long long s_c[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned int eb = 0;
+    unsigned long long cnt = 0;
+    for (int64_t p0 = (int64_t)blockIdx.x * 256; p0 < N; p0 += (int64_t)gridDim.x * 256) {
+        const int64_t p = p0 + t;
+        bool act = false, uns = false;
+        if (p < N) {
+            AccSums s;
+            s.load(st, N, p);
+            const float e = plan_error(s, eps, min_samples);
+            err[p] = e;
+            act = e > tau;
+            uns = act && __builtin_isinf(e);
+            if (act && !uns && __float_as_uint(e) > eb) eb = __float_as_uint(e);
+        }
+        cnt += ((unsigned long long)__popcll(__ballot(act)) << 32) + (unsigned long long)__popcll(__ballot(uns));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned int x = __shfl_xor(eb, o);
+        eb = x > eb ? x : eb;
+    }
+    if (lane == 0) { s_e[wave] = eb; s_c[wave] = cnt; }
+    __syncthreads();
+    if (t == 0) {
+        unsigned int e = s_e[0];
+        unsigned long long c = s_c[0];
+        for (int w = 1; w < 4; ++w) { e = s_e[w] > e ? s_e[w] : e; c += s_c[w]; }
+        if (e) atomicMax(&red->emax, e);
+        if (c) atomicAdd(&red->counts, c);
+    }
+}
+
+// q_p, the integer weight of a pixel: 0 (converged), 2^24 (e = inf), else max(1, floor(2^24 e / E)); E is read from the device
+struct PlanWeight {
+    const PlanRed *red;
+    float tau;
+    __device__ uint64_t operator()(float e) const
+    {
+        if (!(e > tau)) return 0;
+        if (__builtin_isinf(e)) return (uint64_t)1 << 24;
+        const uint32_t q = (uint32_t)((e / __uint_as_float(red->emax)) * 16777216.f);
+        return q > 1 ? q : 1;
+    }
+};
+
+// floor((c B + u) / Q) for c <= Q <= 2^55, B < 2^31, u < Q: the quotient is at most B, so a double estimate is off by at most one and is
+// corrected exactly in 128 bits
+__device__ inline uint64_t plan_floor(uint64_t c, uint64_t B, uint64_t u, uint64_t Q)
+{
+    const unsigned __int128 x = (unsigned __int128)c * B + u;
+    uint64_t f = (uint64_t)(((double)c * (double)B + (double)u) / (double)Q);
+    unsigned __int128 m = (unsigned __int128)f * Q;
+    while (m > x) { --f; m -= Q; }
+    while (x - m >= Q) { ++f; m += Q; }
+    return f;
+}
+
+// n_p = min(K, F(C_p) - F(C_{p-1})), F(c) = floor((c B + u mod Q) / Q): the budget split in proportion to q, exactly B before the cap
+__global__ __launch_bounds__(256) void k_plan_counts(const uint64_t *__restrict__ C, int64_t N, int64_t B, uint64_t offset, int K,
+                                                     int32_t *__restrict__ counts)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    const uint64_t Q = C[N - 1];
+    int32_t n = 0;
+    if (Q != 0 && B != 0) {
+        const uint64_t u = offset % Q, c1 = C[p], c0 = p > 0 ? C[p - 1] : 0;
+        const uint64_t d = plan_floor(c1, (uint64_t)B, u, Q) - plan_floor(c0, (uint64_t)B, u, Q);
+        n = d < (uint64_t)K ? (int32_t)d : K;
+    }
+    counts[p] = n;
+}
+
+// the summary, once the positions are known
+__global__ void k_plan_summary(const PlanRed *__restrict__ red, const int32_t *__restrict__ ends, int64_t N, int64_t *__restrict__ summary)
+{
+    summary[0] = ends[N - 1];
+    summary[1] = (int64_t)(red->counts >> 32);
+    summary[2] = (int64_t)(red->counts & 0xffffffffu);
+    *(float *)(summary + 3) = __uint_as_float(red->emax);
+}
+
+// the pixel list: pixel p at [ends[p-1], ends[p]).  Short runs are written by their pixel's thread; runs longer than PLAN_SHORT_RUN are
+// taken one at a time by the whole wavefront, 64 entries per store
+#define PLAN_SHORT_RUN 16
+__global__ __launch_bounds__(256) void k_plan_expand(const int32_t *__restrict__ ends, int64_t N, int32_t *__restrict__ pixels, int64_t capacity)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int64_t e0 = 0, n = 0;
+    if (p < N) {
+        e0 = p > 0 ? ends[p - 1] : 0;
+        n = ends[p] - e0;
+        if (e0 + n > capacity) n = capacity > e0 ? capacity - e0 : 0; // (T <= budget <= capacity: never taken)
+    }
+    if (n <= PLAN_SHORT_RUN)
+        for (int64_t j = 0; j < n; ++j) pixels[e0 + j] = (int32_t)p;
+    unsigned long long longs = __ballot(n > PLAN_SHORT_RUN);
+    while (longs) {
+        const int src = __ffsll((long long)longs) - 1;
+        longs &= longs - 1;
+        const int64_t b = __shfl(e0, src), m = __shfl(n, src);
+        const int32_t q = (int32_t)__shfl(p, src);
+        for (int64_t j = lane; j < m; j += 64) pixels[b + j] = q;
     }
 }
 
@@ -236,5 +382,46 @@ hipError_t bcd_launch_accum_segments(const uint32_t *keys, const uint32_t *vals,
 hipError_t bcd_launch_accum_snapshot(const float *st, int64_t N, int D, float *ons, float *omean, float *ocov, float *ohist, hipStream_t s)
 {
     hipLaunchKernelGGL(k_accum_snapshot, dim3(nblk(N, 64)), dim3(64), bcd_accum_snapshot_lds(D), s, st, N, D, ons, omean, ocov, ohist);
+    return hipGetLastError();
+}
+
+// ---- adaptive plan ------------------------------------------------------------------------------------------------------------------
+size_t bcd_plan_red_bytes() { return sizeof(PlanRed); }
+
+// the two scans' temporary storage for N pixels
+hipError_t bcd_plan_scan_bytes(int64_t N, size_t *bytes)
+{
+    size_t a = 0, b = 0;
+    rocprim::transform_iterator<const float *, PlanWeight, uint64_t> it((const float *)nullptr, PlanWeight{ nullptr, 0.f });
+    hipError_t e = rocprim::inclusive_scan(nullptr, a, it, (uint64_t *)nullptr, (size_t)N, rocprim::plus<uint64_t>());
+    if (e != hipSuccess) return e;
+    e = rocprim::inclusive_scan(nullptr, b, (const int32_t *)nullptr, (int32_t *)nullptr, (size_t)N, rocprim::plus<int32_t>());
+    *bytes = a > b ? a : b;
+    return e;
+}
+
+// error pass -> C = inclusive scan of q -> capped counts -> their inclusive scan (ends) -> summary -> pixel list.  `red` must be zeroed
+// before; Q, E and T stay on the device
+hipError_t bcd_launch_accum_plan(const float *st, int64_t N, float eps, float min_samples, float tau, int K, int64_t B, uint64_t offset, float *err,
+                                 int32_t *counts, int32_t *pixels, int64_t capacity, int64_t *summary, void *red, uint64_t *C, int32_t *ends,
+                                 void *tmp, size_t tmp_bytes, hipStream_t s)
+{
+    PlanRed *r = (PlanRed *)red;
+    const unsigned eblk = nblk(N, 256) < PLAN_ERROR_BLOCKS ? nblk(N, 256) : PLAN_ERROR_BLOCKS;
+    hipLaunchKernelGGL(k_plan_error, dim3(eblk), dim3(256), 0, s, st, N, eps, min_samples, tau, err, r);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    rocprim::transform_iterator<const float *, PlanWeight, uint64_t> q(err, PlanWeight{ r, tau });
+    size_t bytes = tmp_bytes;
+    e = rocprim::inclusive_scan(tmp, bytes, q, C, (size_t)N, rocprim::plus<uint64_t>(), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_plan_counts, dim3(nblk(N, 256)), dim3(256), 0, s, C, N, B, offset, K, counts);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    bytes = tmp_bytes;
+    e = rocprim::inclusive_scan(tmp, bytes, (const int32_t *)counts, ends, (size_t)N, rocprim::plus<int32_t>(), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_plan_summary, dim3(1), dim3(1), 0, s, r, ends, N, summary);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (B > 0) hipLaunchKernelGGL(k_plan_expand, dim3(nblk(N, 256)), dim3(256), 0, s, ends, N, pixels, capacity);
     return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 """ctypes binding of include/bcd_hip.h.  Fails loudly when libbcd_hip.so is missing: there is no CPU fallback."""
 import ctypes as C
 import os
+import weakref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BCD_HIP_LIB") or os.path.join(_HERE, "lib", "libbcd_hip.so")   # (BCD_HIP_LIB: tools load instrumented builds)
@@ -26,6 +27,26 @@ class HostOptions(C.Structure):
     _fields_ = [("spike_factor", C.c_float), ("zero_bad_values", C.c_int32)]
 
 
+class PlanParams(C.Structure):
+    """bcd_hip_plan_params (adaptive sample planning, bcd_hip_accum_plan)"""
+    _fields_ = [("threshold", C.c_float), ("eps", C.c_float), ("min_samples", C.c_float), ("max_per_pixel", C.c_int32)]
+
+
+class PlanSummary(C.Structure):
+    _fields_ = [("planned", C.c_int64), ("active", C.c_int64), ("unsampled", C.c_int64), ("max_error", C.c_float)]
+
+
+PLAN_ARGTYPES = [_VP, C.POINTER(PlanParams), C.c_int64, C.c_uint64, _VP, _VP, _VP, C.c_int64, _VP]
+
+
+def default_plan_params(**kw):
+    p = PlanParams()
+    lib().bcd_hip_default_plan_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_float, C.c_void_p)
 
 
@@ -47,7 +68,7 @@ SYMBOLS = [
     "bcd_hip_scale_begin", "bcd_hip_pixel_cov", "bcd_hip_similarity_masks", "bcd_hip_similarity_masks_deferred", "bcd_hip_similarity_masks_verdict", "bcd_hip_similarity_masks_exact", "bcd_hip_window_distances", "bcd_hip_active_set", "bcd_hip_active_init", "bcd_hip_active_step", "bcd_hip_active_step_enqueue", "bcd_hip_active_step_collect",
     "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
     "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
-    "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_zero_bad_values",
+    "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_default_plan_params", "bcd_hip_accum_plan", "bcd_hip_zero_bad_values",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch",
 ]
 
@@ -106,9 +127,12 @@ class Context:
         if rc != 0:
             raise BcdHipError("bcd_hip_ctx_create failed: rc=%d" % rc)
         self.h = h
+        self._accumulators = weakref.WeakSet()
 
     def close(self):
         if self.h:
+            for a in list(self._accumulators):               # an accumulator must not outlive its context (bcd_hip.h)
+                a.close()
             lib().bcd_hip_ctx_destroy(self.h)
             self.h = None
 
@@ -389,6 +413,7 @@ class Accumulator:
         h = _VP()
         ctx._chk(L.bcd_hip_accum_create(ctx.h, W, H, nbins, gamma, maxval, capacity, C.byref(h)))
         self.h = h
+        ctx._accumulators.add(self)
 
     def _chk(self, rc):
         self.ctx._chk(rc)
@@ -418,6 +443,31 @@ class Accumulator:
 
     def reset(self):
         self._chk(lib().bcd_hip_accum_reset(self.h))
+
+    def plan(self, budget, offset=0, threshold=0.0, eps=1e-3, min_samples=2.0, max_per_pixel=16, error=False):
+        """where the next `budget` samples go (bcd_hip_accum_plan); the state is unchanged.
+        -> (pixels (T,) int32 device tensor in ascending order, pixel p repeated counts[p] times -- the `pixel` of add_samples;
+            counts (H, W) int32; the error image (H, W) float32 if `error` else None;
+            summary dict: planned (T), active, unsampled, max_error).
+        The kernels keep T on the device; this convenience synchronises the stream once to read the summary and trim the list."""
+        if not 0 <= int(budget) < 2 ** 31:                           # (before the list buffer is allocated)
+            raise ValueError("budget must be in [0, 2^31), got %d" % int(budget))
+        torch = self.ctx.torch
+        dev = "cuda:%d" % self.ctx.device
+        prm = PlanParams(threshold, eps, min_samples, max_per_pixel)
+        pixels = torch.empty((max(int(budget), 1),), dtype=torch.int32, device=dev)
+        counts = torch.empty((self.H, self.W), dtype=torch.int32, device=dev)
+        err = torch.empty((self.H, self.W), dtype=torch.float32, device=dev) if error else None
+        summ = torch.empty((C.sizeof(PlanSummary) // 8,), dtype=torch.int64, device=dev)
+        L = lib()
+        L.bcd_hip_accum_plan.argtypes = PLAN_ARGTYPES
+        self._chk(L.bcd_hip_accum_plan(self.h, C.byref(prm), int(budget), int(offset), _dp(err) if error else None, _dp(counts), _dp(pixels),
+                                       pixels.numel(), _dp(summ)))
+        torch.cuda.synchronize(self.ctx.device)                     # the context's stream may not be torch's
+        s = summ.cpu()
+        T = int(s[0])
+        summary = {"planned": T, "active": int(s[1]), "unsampled": int(s[2]), "max_error": float(s[3:4].view(torch.float32)[0])}
+        return pixels[:T], counts, err, summary
 
     def info(self):
         """(samples accumulated, samples dropped) since create / the last reset; synchronises"""

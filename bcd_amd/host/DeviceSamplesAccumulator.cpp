@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <cstring>
 #include <utility>
 
@@ -58,6 +59,7 @@ namespace bcd
 		bcd_hip_ctx_destroy(m_pContext);
 		if(m_pDeviceBatch) (void)hipFree(m_pDeviceBatch);
 		if(m_pDeviceStats) (void)hipFree(m_pDeviceStats);
+		if(m_pDevicePlan) (void)hipFree(m_pDevicePlan);
 		if(m_pHostPixel) (void)hipHostFree(m_pHostPixel);
 		if(m_pHostRgbw) (void)hipHostFree(m_pHostRgbw);
 		if(m_batchCopied) (void)hipEventDestroy((hipEvent_t)m_batchCopied);
@@ -111,10 +113,12 @@ namespace bcd
 		}
 	}
 
-	void DeviceSamplesAccumulator::flush() const
+	bool DeviceSamplesAccumulator::flush() const
 	{
-		if(!isValid() || m_pending == 0)
-			return;
+		if(!isValid())
+			return false;
+		if(m_pending == 0)
+			return true;
 		const int64_t n = m_pending, cap = s_batchCapacity;
 		hipStream_t st = (hipStream_t)m_stream;
 		int32_t* dPix = (int32_t*)m_pDeviceBatch;
@@ -126,12 +130,16 @@ namespace bcd
 				|| hipEventRecord((hipEvent_t)m_batchCopied, st) != hipSuccess)
 		{
 			m_error = "batch upload failed";
-			return;
+			return false;
 		}
 		m_copyInFlight = true;
 		m_pending = 0;
 		if(bcd_hip_accum_add_scattered(m_pAccum, dPix, dRgb, dW, n) != BCD_HIP_OK)
+		{
 			fail("bcd_hip_accum_add_scattered");
+			return false;
+		}
+		return true;
 	}
 
 	DeviceSamplesAccumulator::DeviceStatistics DeviceSamplesAccumulator::computeDeviceStatistics() const
@@ -179,6 +187,74 @@ namespace bcd
 		SamplesStatisticsImages out = getSamplesStatistics();
 		m_isValid = false;
 		return out;
+	}
+
+	bool DeviceSamplesAccumulator::planSamples(int64_t i_budget, uint64_t i_offset, const PlanParameters& i_rParameters,
+			std::vector<int32_t>& o_pixelIndices, PlanSummary* o_pSummary)
+	{
+		o_pixelIndices.clear();
+		if(!isValid())
+			return false;
+		if(i_budget < 0 || i_budget > INT32_MAX)
+		{	// (before the list buffer grows to the budget)
+			m_error = "planSamples: the budget must be in [0, 2^31)";
+			return false;
+		}
+		if(!flush()) // this call's own flush; an earlier failure (still in lastError()) does not block the plan
+			return false;
+		const int64_t capacity = std::max<int64_t>(i_budget, 1);
+		if(capacity > m_planCapacity)
+		{
+			if(m_pDevicePlan && (hipStreamSynchronize((hipStream_t)m_stream) != hipSuccess || hipFree(m_pDevicePlan) != hipSuccess))
+			{
+				m_error = "plan buffer release failed";
+				return false;
+			}
+			m_pDevicePlan = nullptr;
+			m_planCapacity = -1;
+			if(hipMalloc(&m_pDevicePlan, sizeof(bcd_hip_plan_summary) + size_t(capacity) * sizeof(int32_t)) != hipSuccess)
+			{
+				m_pDevicePlan = nullptr;
+				m_error = "out of device memory for the plan";
+				return false;
+			}
+			m_planCapacity = capacity;
+		}
+		bcd_hip_plan_params prm;
+		prm.threshold = i_rParameters.m_threshold;
+		prm.eps = i_rParameters.m_eps;
+		prm.min_samples = i_rParameters.m_minSamples;
+		prm.max_per_pixel = i_rParameters.m_maxPerPixel;
+		bcd_hip_plan_summary* dSummary = (bcd_hip_plan_summary*)m_pDevicePlan;
+		int32_t* dPixels = (int32_t*)(dSummary + 1);
+		if(bcd_hip_accum_plan(m_pAccum, &prm, i_budget, i_offset, nullptr, nullptr, dPixels, m_planCapacity, dSummary) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_plan");
+			return false;
+		}
+		bcd_hip_plan_summary summary;
+		hipStream_t st = (hipStream_t)m_stream;
+		if(hipMemcpyAsync(&summary, dSummary, sizeof(summary), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+		{
+			m_error = "plan download failed";
+			return false;
+		}
+		o_pixelIndices.resize(size_t(summary.planned));
+		if(summary.planned > 0 && (hipMemcpyAsync(o_pixelIndices.data(), dPixels, size_t(summary.planned) * sizeof(int32_t), hipMemcpyDeviceToHost, st)
+				!= hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+		{
+			o_pixelIndices.clear();
+			m_error = "plan download failed";
+			return false;
+		}
+		if(o_pSummary)
+		{
+			o_pSummary->m_planned = summary.planned;
+			o_pSummary->m_active = summary.active;
+			o_pSummary->m_unsampled = summary.unsampled;
+			o_pSummary->m_maxError = summary.max_error;
+		}
+		return true;
 	}
 
 	void DeviceSamplesAccumulator::reset()

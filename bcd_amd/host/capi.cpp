@@ -8,9 +8,11 @@
 #include "SyntheticScene.h"
 #include "Utils.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <memory>
 #include <string>
+#include <vector>
 
 using namespace bcd;
 
@@ -105,6 +107,39 @@ int bcdcore_device_accumulate(const float* s, long long n, int W, int H, int nbi
 	st.m_covarImage.copyDataTo(cov);
 	st.m_histoImage.copyDataTo(hist);
 	return 0;
+}
+
+// the same stream through bcd::DeviceSamplesAccumulator::addSample (no explicit flush), then one planSamples; pixels[budget] receives the
+// list, summary[4] planned / active / unsampled / max_error.  invalidFirst: two invalid planSamples come first (a budget of 2^31 while the
+// samples are still buffered, then max_per_pixel 0), and each must return false with a message.  Returns the number of planned samples,
+// -1 (message as above) or -2 (an invalid call was accepted)
+long long bcdcore_device_plan(const float* s, long long n, int W, int H, int nbins, float gamma, float maxval, int device, long long budget,
+		unsigned long long offset, float threshold, float eps, float minSamples, int maxPerPixel, int invalidFirst, int* pixels, double* summary)
+{
+	HistogramParameters hp;
+	hp.m_nbOfBins = nbins; hp.m_gamma = gamma; hp.m_maxValue = maxval;
+	DeviceSamplesAccumulator acc(W, H, hp, device);
+	g_deviceAccumulateError.clear();
+	if(!acc.isValid()) { g_deviceAccumulateError = acc.lastError(); return -1; }
+	for(long long i = 0; i < n; ++i, s += 6)
+		acc.addSample(int(s[0]), int(s[1]), s[2], s[3], s[4], s[5]);
+	DeviceSamplesAccumulator::PlanParameters prm;
+	prm.m_threshold = threshold; prm.m_eps = eps; prm.m_minSamples = minSamples; prm.m_maxPerPixel = maxPerPixel;
+	DeviceSamplesAccumulator::PlanSummary sum;
+	std::vector<int32_t> list;
+	if(invalidFirst)
+	{
+		DeviceSamplesAccumulator::PlanParameters bad = prm;
+		bad.m_maxPerPixel = 0;
+		if(acc.planSamples((long long)1 << 31, offset, prm, list, &sum) || acc.lastError().empty())
+			return -2;
+		if(acc.planSamples(budget, offset, bad, list, &sum) || acc.lastError().empty())
+			return -2;
+	}
+	if(!acc.planSamples(budget, offset, prm, list, &sum)) { g_deviceAccumulateError = acc.lastError(); return -1; }
+	std::copy(list.begin(), list.end(), pixels);
+	summary[0] = double(sum.m_planned); summary[1] = double(sum.m_active); summary[2] = double(sum.m_unsampled); summary[3] = sum.m_maxError;
+	return (long long)list.size();
 }
 
 void bcdcore_release_engines() { releaseEngines(); }

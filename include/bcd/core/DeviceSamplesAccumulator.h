@@ -33,6 +33,22 @@ namespace bcd
 			int m_width = 0, m_height = 0, m_depth = 0;
 		};
 
+		/// adaptive sample planning (bcd_hip_accum_plan in bcd_hip.h, which defines the plan exactly)
+		struct PlanParameters
+		{
+			float m_threshold = 0.f;  ///< pixels whose relative error is at most this get no samples
+			float m_eps = 1e-3f;      ///< added to the luminance in the relative error
+			float m_minSamples = 2.f; ///< pixels with a smaller weight sum have an infinite error
+			int m_maxPerPixel = 16;   ///< cap of the samples one pixel gets in one plan, in [1, 65535]
+		};
+		struct PlanSummary
+		{
+			int64_t m_planned = 0;   ///< entries of the pixel list
+			int64_t m_active = 0;    ///< pixels with an error above the threshold
+			int64_t m_unsampled = 0; ///< active pixels with an infinite error
+			float m_maxError = 0.f;  ///< largest finite error of the active pixels
+		};
+
 		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_device = 0);
 		~DeviceSamplesAccumulator();
 		DeviceSamplesAccumulator(const DeviceSamplesAccumulator&) = delete;
@@ -54,6 +70,13 @@ namespace bcd
 		/// enqueues a snapshot into device buffers owned by the accumulator (no host copy, no synchronisation) and returns them
 		DeviceStatistics computeDeviceStatistics() const;
 
+		/// where the next i_budget samples go: o_pixelIndices receives the planned pixel indices (line * width + column) in ascending order,
+		/// each pixel repeated as many times as it gets samples.  The samples buffered by addSample are applied first; the statistics are
+		/// not changed.  Synchronises.  false (message in lastError()) for invalid parameters or a device error; a failed call does not
+		/// affect the next one.
+		bool planSamples(int64_t i_budget, uint64_t i_offset, const PlanParameters& i_rParameters, std::vector<int32_t>& o_pixelIndices,
+				PlanSummary* o_pSummary = nullptr);
+
 		/// back to an empty accumulator (the frame geometry and the device buffers are kept)
 		void reset();
 		/// samples accumulated / skipped since construction or the last reset (synchronises)
@@ -61,7 +84,8 @@ namespace bcd
 		int64_t nbOfDroppedSamples() const;
 
 	private:
-		void flush() const;
+		/// applies the pending addSample batch; false (message in lastError()) if this flush failed
+		bool flush() const;
 		void fail(const char* i_pWhat) const;
 
 	private:
@@ -80,6 +104,8 @@ namespace bcd
 		void* m_batchCopied = nullptr;   // hipEvent_t: the pinned batch has reached the device
 		mutable bool m_copyInFlight = false;
 		void* m_pDeviceStats = nullptr; // ns | mean | cov | hist of computeDeviceStatistics
+		void* m_pDevicePlan = nullptr;  // summary (32 bytes) | pixel list of planSamples (grow-only)
+		int64_t m_planCapacity = -1;
 	};
 
 } // namespace bcd

@@ -352,6 +352,38 @@ int  bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const f
 int  bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n);
 int  bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist);
 int  bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped);
+/* Adaptive sample planning on the accumulator's state: where the next `budget` samples go, decided on the device
+ * from the noise model the denoiser uses (cov / n), with no host copy and no float atomics; reproducible bit for bit.  Per pixel, from
+ * the snapshot's statistics (ns, mean m, covariance c, float32, IEEE division and sqrtf):
+ *     t = (c_xx / ns + c_yy / ns) + c_zz / ns   (as c * (1 / ns)),   l = (m_r + m_g) + m_b
+ *     e = +inf if !(ns >= min_samples) or t, l not finite, else sqrtf(max(t / 3, 0)) / (eps + max(l / 3, 0))
+ * A pixel is active when e > threshold; E = the largest finite e of the active pixels.  Weight q = 0 (inactive), 2^24 (e = inf), else
+ * max(1, (uint32)((e / E) * 2^24)).  With C the inclusive scan of q in pixel order (line * W + col), Q its total and u = offset mod Q:
+ *     n_p = min(max_per_pixel, floor((C_p B + u) / Q) - floor((C_{p-1} B + u) / Q))        (exact integers; Q = 0 or B = 0: all 0)
+ * so before the cap the counts sum to B exactly and each is the floor or the ceiling of B q_p / Q; changing `offset` from pass to pass
+ * rotates the leftover fractions over the pixels.
+ *   plan: budget B in [0, 2^31); d_error W*H floats or NULL; d_counts W*H int32 or NULL; d_pixels[capacity], capacity >= budget,
+ *         receives T = sum n_p pixel indices in ascending order, pixel p repeated n_p times (the d_pixel of add_scattered); d_summary
+ *         receives planned T, the active pixels, the unsampled ones (active with e = inf) and E.  Enqueued on the context's stream, no
+ *         synchronisation; the state is not changed.  EINVAL with nothing enqueued for null acc / params / d_pixels / d_summary,
+ *         capacity < budget, threshold not finite or < 0, eps not finite or <= 0, min_samples not finite or < 0, max_per_pixel outside
+ *         [1, 65535].  The scratch is allocated by create when max_batch_samples > 0, else by the first plan; later plans never allocate.
+ *   default_plan_params: threshold 0, eps 1e-3, min_samples 2, max_per_pixel 16 */
+typedef struct bcd_hip_plan_params {
+    float   threshold;      /* tau: pixels with e <= tau get no samples               default 0     */
+    float   eps;            /* added to the luminance of the relative error            default 1e-3  */
+    float   min_samples;    /* pixels whose weight sum is below it have e = inf         default 2     */
+    int32_t max_per_pixel;  /* K: cap of n_p                                             default 16    */
+} bcd_hip_plan_params;
+typedef struct bcd_hip_plan_summary {
+    int64_t planned;        /* T, the entries written to d_pixels                                    */
+    int64_t active;         /* pixels with e > threshold                                              */
+    int64_t unsampled;      /* active pixels with e = inf (below min_samples, or non-finite statistics) */
+    float   max_error;      /* E, the largest finite e of the active pixels (0 if none)               */
+} bcd_hip_plan_summary;
+void bcd_hip_default_plan_params(bcd_hip_plan_params *p);
+int  bcd_hip_accum_plan(bcd_hip_accum *acc, const bcd_hip_plan_params *params, int64_t budget, uint64_t offset, float *d_error, int32_t *d_counts,
+                        int32_t *d_pixels, int64_t capacity, bcd_hip_plan_summary *d_summary);
 /* checkAndPutToZeroNegativeInfNaNValues   src/cli/main.cpp:389-420 */
 int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n);
 
