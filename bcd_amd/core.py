@@ -89,6 +89,83 @@ def device_plan(samples, W, H, budget, offset=0, threshold=0.0, eps=1e-3, min_sa
                                "max_error": float(np.float32(summary[3]))}
 
 
+class DeviceAccumulator:
+    """a bcd::DeviceSamplesAccumulator kept alive between calls (capi.cpp bcdcore_device_acc_*), for its state methods: exportState,
+    saveState, loadState, mergeState and merge.  Failing methods raise RuntimeError with the class's lastError()"""
+
+    def __init__(self, W, H, nbins=20, gamma=2.2, maxval=2.5, device=0):
+        L = lib()
+        L.bcdcore_device_acc_create.restype = C.c_void_p
+        L.bcdcore_device_acc_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]
+        L.bcdcore_device_acc_destroy.argtypes = [C.c_void_p]
+        L.bcdcore_device_acc_destroy.restype = None
+        L.bcdcore_device_acc_error.argtypes = [C.c_void_p]
+        L.bcdcore_device_acc_error.restype = C.c_char_p
+        L.bcdcore_device_acc_valid.argtypes = [C.c_void_p]
+        L.bcdcore_device_acc_add.argtypes = [C.c_void_p, _F, C.c_longlong]
+        L.bcdcore_device_acc_add.restype = None
+        L.bcdcore_device_acc_export.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong]
+        L.bcdcore_device_acc_export.restype = C.c_longlong
+        for name in ("save", "load", "merge_state"):
+            getattr(L, "bcdcore_device_acc_" + name).argtypes = [C.c_void_p, C.c_char_p]
+        L.bcdcore_device_acc_merge.argtypes = [C.c_void_p, C.c_void_p]
+        L.bcdcore_device_acc_statistics.argtypes = [C.c_void_p, _F, _F, _F, _F, C.POINTER(C.c_longlong)]
+        self.W, self.H, self.nbins = W, H, nbins
+        self.h = L.bcdcore_device_acc_create(W, H, nbins, gamma, maxval, int(device))
+        if not L.bcdcore_device_acc_valid(self.h):
+            msg = L.bcdcore_device_acc_error(self.h).decode()
+            self.close()
+            raise RuntimeError("DeviceSamplesAccumulator: " + msg)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise RuntimeError("DeviceSamplesAccumulator: " + lib().bcdcore_device_acc_error(self.h).decode())
+
+    def add(self, samples):
+        """(n, 6) stream (line, col, r, g, b, w) through addSample"""
+        samples = np.ascontiguousarray(samples, np.float32)
+        lib().bcdcore_device_acc_add(self.h, _fp(samples), samples.shape[0])
+
+    def export_state(self):
+        n = lib().bcdcore_device_acc_export(self.h, None, 0)
+        self._chk(0 if n >= 0 else -1)
+        out = np.empty(n, np.uint8)
+        self._chk(0 if lib().bcdcore_device_acc_export(self.h, out.ctypes.data_as(C.c_void_p), n) == n else -1)
+        return out
+
+    def save_state(self, path):
+        self._chk(lib().bcdcore_device_acc_save(self.h, os.fsencode(path)))
+
+    def load_state(self, path):
+        self._chk(lib().bcdcore_device_acc_load(self.h, os.fsencode(path)))
+
+    def merge_state(self, path):
+        self._chk(lib().bcdcore_device_acc_merge_state(self.h, os.fsencode(path)))
+
+    def merge(self, other):
+        self._chk(lib().bcdcore_device_acc_merge(self.h, other.h))
+
+    def statistics(self):
+        """host snapshot (ns, mean, cov, hist) and (samples accumulated, dropped)"""
+        H, W = self.H, self.W
+        ns, mean, cov = np.empty((H, W, 1), np.float32), np.empty((H, W, 3), np.float32), np.empty((H, W, 6), np.float32)
+        hist = np.empty((H, W, 3 * self.nbins), np.float32)
+        counts = (C.c_longlong * 2)()
+        self._chk(lib().bcdcore_device_acc_statistics(self.h, _fp(ns), _fp(mean), _fp(cov), _fp(hist), counts))
+        return (ns, mean, cov, hist), (counts[0], counts[1])
+
+    def close(self):
+        if self.h:
+            lib().bcdcore_device_acc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def denoise(col, ns, hist, cov, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, hist_width_override=0,
             use_cuda=True, devices=None, prefilter_factor=0.0):
     """bcd::Denoiser / bcd::MultiscaleDenoiser via IDenoiser; returns (ok, out, progress_monotone).

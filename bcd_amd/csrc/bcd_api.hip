@@ -79,6 +79,8 @@ size_t bcd_plan_red_bytes();
 hipError_t bcd_plan_scan_bytes(int64_t, size_t *);
 hipError_t bcd_launch_accum_plan(const float *, int64_t, float, float, float, int, int64_t, uint64_t, float *, int32_t *, int32_t *, int64_t, int64_t *,
                                  void *, uint64_t *, int32_t *, void *, size_t, hipStream_t);
+hipError_t bcd_launch_accum_merge(float *, const float *, int64_t, int, hipStream_t);
+hipError_t bcd_launch_accum_counter(unsigned long long *, const unsigned long long *, unsigned long long, int, hipStream_t);
 size_t bcd_bayes_scratch_bytes_per_block(int w, int b);
 size_t bcd_bayes27_record_bytes();
 hipError_t bcd_launch_bayes27(const float *, const float *, const uint32_t *, const int32_t *, int, int, int *, int, int, int, int, float, float *, float *,
@@ -1698,6 +1700,14 @@ struct bcd_hip_accum {
     int64_t submitted = 0;         // samples handed to add_* since the last reset
     DevBuf plan_red, plan_c, plan_ends, plan_err, plan_cnt, plan_tmp; // adaptive-plan scratch (allocated once per accumulator)
     bool plan_ready = false;       // the plan scratch is allocated (N is fixed, so it is never resized)
+    // states (export / import / merge): two pinned staging chunks and two device chunks of at most STATE_CHUNK bytes, allocated on first
+    // use; stage_busy[i]: a copy out of stage[i] may still be in flight (stage_ev[i] marks its end)
+    void *stage[2] = { nullptr, nullptr };
+    void *chunk[2] = { nullptr, nullptr };
+    hipEvent_t stage_ev[2] = { nullptr, nullptr };
+    bool stage_busy[2] = { false, false };
+    size_t chunk_bytes = 0;
+    hipEvent_t ev_merge = nullptr; // recorded on the context's stream around a merge (the source's work so far / the destination's reads)
 };
 
 namespace {
@@ -1757,6 +1767,11 @@ int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamm
     a->capacity = max_batch_samples;
     int rc = ensure(ctx, a->state, accum_state_bytes(a));
     if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
+    if (rc == BCD_HIP_OK && hipEventCreateWithFlags(&a->ev_merge, hipEventDisableTiming) != hipSuccess) {
+        a->ev_merge = nullptr;
+        set_err(ctx, "hipEventCreateWithFlags failed");
+        rc = BCD_HIP_EDEVICE;
+    }
     if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_scratch(a, a->capacity);
     if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_plan_scratch(a);
     if (rc == BCD_HIP_OK) rc = bcd_hip_accum_reset(a);
@@ -1773,6 +1788,12 @@ void bcd_hip_accum_destroy(bcd_hip_accum *acc)
     for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
                        &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
         if (b->p) (void)hipFree(b->p);
+    for (int i = 0; i < 2; ++i) {
+        if (acc->stage[i]) (void)hipHostFree(acc->stage[i]);
+        if (acc->chunk[i]) (void)hipFree(acc->chunk[i]);
+        if (acc->stage_ev[i]) (void)hipEventDestroy(acc->stage_ev[i]);
+    }
+    if (acc->ev_merge) (void)hipEventDestroy(acc->ev_merge);
     delete acc;
 }
 
@@ -1882,6 +1903,235 @@ int bcd_hip_accum_plan(bcd_hip_accum *acc, const bcd_hip_plan_params *prm, int64
                                       offset, d_error ? d_error : (float *)acc->plan_err.p, d_counts ? d_counts : (int32_t *)acc->plan_cnt.p,
                                       d_pixels, capacity, (int64_t *)d_summary, acc->plan_red.p, (uint64_t *)acc->plan_c.p,
                                       (int32_t *)acc->plan_ends.p, acc->plan_tmp.p, acc->plan_tmp.bytes, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+// ---- states: export, import, merge -----------------------------------------------------------------------------
+static_assert(sizeof(bcd_hip_accum_state_header) == BCD_HIP_ACCUM_STATE_HEADER_BYTES && offsetof(bcd_hip_accum_state_header, version) == 8 &&
+                  offsetof(bcd_hip_accum_state_header, header_bytes) == 12 && offsetof(bcd_hip_accum_state_header, width) == 16 &&
+                  offsetof(bcd_hip_accum_state_header, height) == 20 && offsetof(bcd_hip_accum_state_header, nb_bins) == 24 &&
+                  offsetof(bcd_hip_accum_state_header, gamma) == 28 && offsetof(bcd_hip_accum_state_header, max_value) == 32 &&
+                  offsetof(bcd_hip_accum_state_header, nb_planes) == 36 && offsetof(bcd_hip_accum_state_header, samples_added) == 40 &&
+                  offsetof(bcd_hip_accum_state_header, dropped) == 48 && offsetof(bcd_hip_accum_state_header, reserved) == 56,
+              "bcd_hip_accum_state_header layout (format v1)");
+
+namespace {
+
+constexpr size_t STATE_CHUNK = (size_t)64 << 20; // bound of a staging / scratch chunk
+const char STATE_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'S', 'T' };
+
+// what is wrong with a serialised state of `bytes` bytes (its header copied to *hd), or nullptr
+const char *state_problem(const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
+{
+    if (!h) return "null state";
+    if (bytes < BCD_HIP_ACCUM_STATE_HEADER_BYTES) return "shorter than the 64-byte header";
+    memcpy(hd, h, sizeof(*hd));
+    if (memcmp(hd->magic, STATE_MAGIC, 8) != 0) return "bad magic (not BCDACCST)";
+    if (hd->version != BCD_HIP_ACCUM_STATE_VERSION) return "unsupported version (not 1)";
+    if (hd->header_bytes != BCD_HIP_ACCUM_STATE_HEADER_BYTES) return "header_bytes is not 64";
+    if (hd->nb_bins < 2 || hd->nb_bins > 85) return "nb_bins outside [2, 85]";
+    if (hd->width <= 0 || hd->height <= 0 || (int64_t)hd->width * hd->height >= ((int64_t)1 << 31)) return "width and height must be positive, below 2^31 pixels";
+    if (hd->nb_planes != (uint32_t)(11 + 3 * hd->nb_bins)) return "nb_planes is not 11 + 3 nb_bins";
+    if (bytes != BCD_HIP_ACCUM_STATE_HEADER_BYTES + 4 * (int64_t)hd->nb_planes * hd->width * hd->height) return "size is not 64 + 4 nb_planes W H bytes";
+    for (uint8_t r : hd->reserved)
+        if (r != 0) return "reserved bytes are not zero";
+    if (hd->samples_added < 0 || hd->dropped < 0) return "negative counters";
+    return nullptr;
+}
+
+// a well-formed state of this accumulator's geometry and parameters (gamma and max value bit for bit)?
+int accum_check_state(bcd_hip_accum *a, const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
+{
+    if (const char *why = state_problem(h, bytes, hd)) return bad(a->ctx, (std::string("not an accumulator state (format v1): ") + why).c_str());
+    if (hd->width != a->W || hd->height != a->H || hd->nb_bins != a->nbins) return bad(a->ctx, "state of another frame size or bin count");
+    if (memcmp(&hd->gamma, &a->gamma, sizeof(float)) != 0 || memcmp(&hd->max_value, &a->maxval, sizeof(float)) != 0)
+        return bad(a->ctx, "state with another gamma or max value");
+    return BCD_HIP_OK;
+}
+
+int accum_check_pair(bcd_hip_accum *dst, bcd_hip_accum *src)
+{
+    if (!src) return bad(dst->ctx, "null source accumulator");
+    if (dst == src) return bad(dst->ctx, "an accumulator cannot be merged into itself");
+    if (dst->W != src->W || dst->H != src->H || dst->nbins != src->nbins) return bad(dst->ctx, "accumulators of different frame sizes or bin counts");
+    if (memcmp(&dst->gamma, &src->gamma, sizeof(float)) != 0 || memcmp(&dst->maxval, &src->maxval, sizeof(float)) != 0)
+        return bad(dst->ctx, "accumulators with different gamma or max value");
+    return BCD_HIP_OK;
+}
+
+// the pinned staging (host_side) or the device chunks, allocated once; the context's device is current
+int accum_chunks(bcd_hip_accum *a, bool host_side)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    a->chunk_bytes = std::min(STATE_CHUNK, accum_state_bytes(a));
+    for (int i = 0; i < 2; ++i) {
+        if (host_side && !a->stage_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&a->stage_ev[i], hipEventDisableTiming));
+        void *&p = host_side ? a->stage[i] : a->chunk[i];
+        if (p) continue;
+        const hipError_t e = host_side ? hipHostMalloc(&p, a->chunk_bytes, hipHostMallocDefault) : hipMalloc(&p, a->chunk_bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            set_err(ctx, std::string(host_side ? "hipHostMalloc" : "hipMalloc") + " of a state chunk failed: " + hipGetErrorString(e));
+            return BCD_HIP_ENOMEM;
+        }
+    }
+    return BCD_HIP_OK;
+}
+
+// the planes at h (accum_state_bytes) replace the state (merge = false) or are added to it, chunk by chunk through the pinned staging:
+// the host copy of chunk i + 1 runs while chunk i crosses PCIe.  Returns when h is no longer needed.
+int accum_from_host(bcd_hip_accum *a, const uint8_t *h, bool merge)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    RCCHK(accum_chunks(a, true));
+    if (merge) RCCHK(accum_chunks(a, false));
+    const size_t S = accum_state_bytes(a), c = a->chunk_bytes;
+    uint8_t *st = (uint8_t *)a->state.p;
+    for (size_t off = 0, i = 0; off < S; off += c, ++i) {
+        const int b = (int)(i & 1);
+        const size_t len = std::min(c, S - off);
+        if (a->stage_busy[b]) {
+            HIPCHK(ctx, hipEventSynchronize(a->stage_ev[b]));
+            a->stage_busy[b] = false;
+        }
+        memcpy(a->stage[b], h + off, len);
+        // (merge: chunk[b] was last read by the merge of chunk i - 2, earlier on the same stream)
+        HIPCHK(ctx, hipMemcpyAsync(merge ? a->chunk[b] : st + off, a->stage[b], len, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(a->stage_ev[b], ctx->stream));
+        a->stage_busy[b] = true;
+        if (merge) HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)a->chunk[b], (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+    }
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+int bcd_hip_accum_state_info(const void *h_state, int64_t bytes, bcd_hip_accum_state_header *out)
+{
+    bcd_hip_accum_state_header hd;
+    if (state_problem(h_state, bytes, &hd)) return BCD_HIP_EINVAL;
+    if (out) *out = hd;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_state_bytes(bcd_hip_accum *acc, int64_t *bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    if (!bytes) return bad(acc->ctx, "null size");
+    *bytes = BCD_HIP_ACCUM_STATE_HEADER_BYTES + (int64_t)accum_state_bytes(acc);
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    const size_t S = accum_state_bytes(acc);
+    if (!h_state) return bad(ctx, "null state buffer");
+    if (capacity < BCD_HIP_ACCUM_STATE_HEADER_BYTES + (int64_t)S) return bad(ctx, "state buffer smaller than bcd_hip_accum_state_bytes");
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_chunks(acc, true));
+    int64_t added = 0, dropped = 0;
+    RCCHK(bcd_hip_accum_info(acc, &added, &dropped)); // (synchronises: no staging copy is in flight after it)
+    acc->stage_busy[0] = acc->stage_busy[1] = false;
+    bcd_hip_accum_state_header hd;
+    memset(&hd, 0, sizeof(hd));
+    memcpy(hd.magic, STATE_MAGIC, 8);
+    hd.version = BCD_HIP_ACCUM_STATE_VERSION;
+    hd.header_bytes = BCD_HIP_ACCUM_STATE_HEADER_BYTES;
+    hd.width = acc->W; hd.height = acc->H; hd.nb_bins = acc->nbins;
+    hd.gamma = acc->gamma; hd.max_value = acc->maxval;
+    hd.nb_planes = (uint32_t)(11 + 3 * acc->nbins);
+    hd.samples_added = added; hd.dropped = dropped;
+    uint8_t *out = (uint8_t *)h_state;
+    memcpy(out, &hd, sizeof(hd));
+    out += BCD_HIP_ACCUM_STATE_HEADER_BYTES;
+    // chunk i + 2 crosses PCIe into one pinned buffer while the host copies chunk i + 1 out of the other
+    const size_t c = acc->chunk_bytes, nch = (S + c - 1) / c;
+    const uint8_t *st = (const uint8_t *)acc->state.p;
+    auto enqueue = [&](size_t i) {
+        const int b = (int)(i & 1);
+        hipError_t e = hipMemcpyAsync(acc->stage[b], st + i * c, std::min(c, S - i * c), hipMemcpyDeviceToHost, ctx->stream);
+        return e == hipSuccess ? hipEventRecord(acc->stage_ev[b], ctx->stream) : e;
+    };
+    for (size_t i = 0; i < std::min<size_t>(2, nch); ++i) HIPCHK(ctx, enqueue(i));
+    for (size_t i = 0; i < nch; ++i) {
+        const int b = (int)(i & 1);
+        HIPCHK(ctx, hipEventSynchronize(acc->stage_ev[b]));
+        memcpy(out + i * c, acc->stage[b], std::min(c, S - i * c));
+        if (i + 2 < nch) HIPCHK(ctx, enqueue(i + 2));
+    }
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    bcd_hip_accum_state_header hd;
+    RCCHK(accum_check_state(acc, h_state, bytes, &hd));
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, false));
+    HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 0, ctx->stream));
+    acc->submitted = hd.samples_added + hd.dropped;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_merge_state(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    bcd_hip_accum_state_header hd;
+    RCCHK(accum_check_state(acc, h_state, bytes, &hd));
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, true));
+    HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 1, ctx->stream));
+    acc->submitted += hd.samples_added + hd.dropped;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src)
+{
+    if (!dst) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = dst->ctx;
+    RCCHK(accum_check_pair(dst, src));
+    bcd_hip_ctx *sctx = src->ctx;
+    { // everything enqueued on src's stream so far ...
+        DeviceGuard g(sctx);
+        if (!g.ok) { set_err(ctx, "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
+        HIPCHK(ctx, hipEventRecord(src->ev_merge, sctx->stream));
+    }
+    DEVICE_GUARD(ctx);
+    // ... comes before the reads on dst's stream
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->ev_merge, 0));
+    const size_t S = accum_state_bytes(dst);
+    const char *env = getenv("BCD_HIP_ACCUM_MERGE_COPY"); // 1: the chunked copy of a cross-device merge on one device too (tests)
+    if (sctx->device == ctx->device && !(env && env[0] == '1')) {
+        HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->state.p, (const float *)src->state.p, (int64_t)(S / 4), ctx->num_cus, ctx->stream));
+        HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)src->dropped.p, 0, 1, ctx->stream));
+    } else {
+        // src's state in chunks into dst-side scratch (peer copies; no peer access needed), each chunk merged after its copy
+        RCCHK(accum_chunks(dst, false));
+        const size_t c = dst->chunk_bytes;
+        uint8_t *st = (uint8_t *)dst->state.p;
+        const uint8_t *ss = (const uint8_t *)src->state.p;
+        for (size_t off = 0, i = 0; off < S; off += c, ++i) {
+            void *buf = dst->chunk[i & 1];
+            const size_t len = std::min(c, S - off);
+            HIPCHK(ctx, hipMemcpyPeerAsync(buf, ctx->device, ss + off, sctx->device, len, ctx->stream));
+            HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)buf, (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+        }
+        HIPCHK(ctx, hipMemcpyPeerAsync(dst->chunk[0], ctx->device, src->dropped.p, sctx->device, sizeof(unsigned long long), ctx->stream));
+        HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)dst->chunk[0], 0, 1, ctx->stream));
+    }
+    // dst's reads come before whatever is enqueued on src's stream from now on
+    HIPCHK(ctx, hipEventRecord(dst->ev_merge, ctx->stream));
+    {
+        DeviceGuard g(sctx);
+        if (!g.ok) { set_err(ctx, "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
+        HIPCHK(ctx, hipStreamWaitEvent(sctx->stream, dst->ev_merge, 0));
+    }
+    dst->submitted += src->submitted;
     return BCD_HIP_OK;
 }
 

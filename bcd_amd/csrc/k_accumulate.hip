@@ -9,7 +9,9 @@
 //
 // Determinism: every pixel's samples are applied by one thread, in stream order, with the same float operations in the same order as
 // SamplesAccumulator::addSample and k_accumulate_samples (-ffp-contract=off).  No float atomics anywhere; the scattered path sorts
-// (pixel, sample index) with a stable radix sort and walks each pixel's run in order.
+// (pixel, sample index) with a stable radix sort and walks each pixel's run in order.  A merge of two states is one fp32 add per element
+// (the sums are plain running sums), so it is as deterministic as the rest.
+#include <algorithm>
 #include <cstring> // (before rocprim: texture_cache_iterator.hpp uses memset)
 #include <rocprim/rocprim.hpp>
 
@@ -331,6 +333,31 @@ __global__ __launch_bounds__(256) void k_plan_expand(const int32_t *__restrict__
     }
 }
 
+// (e) merge of two states (bcd_hip_accum_merge*): dst[i] = dst[i] + src[i] over a flat range of the state, one fp32
+// add per element and nothing else.  Elements [head, head + 4 nvec) go as float4 (the launcher found dst + head and src + head both
+// 16-byte aligned), [0, head) and the tail one at a time; bases that are not co-aligned take the scalar loop for everything (head = n).
+// Grid-stride over a grid capped from the CU count.
+__global__ __launch_bounds__(256) void k_accum_merge(float *__restrict__ dst, const float *__restrict__ src, int64_t n, int64_t head, int64_t nvec)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    float4 *dv = reinterpret_cast<float4 *>(dst + head);
+    const float4 *sv = reinterpret_cast<const float4 *>(src + head);
+    for (int64_t j = t; j < nvec; j += stride) {
+        float4 a = dv[j];
+        const float4 b = sv[j];
+        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+        dv[j] = a;
+    }
+    for (int64_t j = t; j < head; j += stride) dst[j] += src[j];
+    for (int64_t j = head + 4 * nvec + t; j < n; j += stride) dst[j] += src[j];
+}
+
+// the drop counter of an import or a merge: *dst = (keep ? *dst : 0) + (src ? *src : 0) + add
+__global__ void k_accum_counter(unsigned long long *dst, const unsigned long long *src, unsigned long long add, int keep)
+{
+    *dst = (keep ? *dst : 0ull) + (src ? *src : 0ull) + add;
+}
+
 inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 } // namespace
@@ -423,5 +450,30 @@ hipError_t bcd_launch_accum_plan(const float *st, int64_t N, float eps, float mi
     hipLaunchKernelGGL(k_plan_summary, dim3(1), dim3(1), 0, s, r, ends, N, summary);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (B > 0) hipLaunchKernelGGL(k_plan_expand, dim3(nblk(N, 256)), dim3(256), 0, s, ends, N, pixels, capacity);
+    return hipGetLastError();
+}
+
+// ---- merge ------------------------------------------------------------------------------------------------------------------------
+// workgroups of 256 per CU in a merge grid: 8 fill the 8 wave slots of every SIMD
+#define MERGE_BLOCKS_PER_CU 8
+
+hipError_t bcd_launch_accum_merge(float *dst, const float *src, int64_t n, int num_cus, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    const uintptr_t a = (uintptr_t)dst & 15, b = (uintptr_t)src & 15;
+    int64_t head = n, nvec = 0;
+    if (a == b && (a & 3) == 0) {
+        head = std::min<int64_t>(n, (int64_t)((16 - a) & 15) / 4);
+        nvec = (n - head) / 4;
+    }
+    const int64_t work = std::max<int64_t>(nvec, n - 4 * nvec);
+    const unsigned cap = (unsigned)std::max(1, num_cus) * MERGE_BLOCKS_PER_CU;
+    hipLaunchKernelGGL(k_accum_merge, dim3(std::min(nblk(work, 256), cap)), dim3(256), 0, s, dst, src, n, head, nvec);
+    return hipGetLastError();
+}
+
+hipError_t bcd_launch_accum_counter(unsigned long long *dst, const unsigned long long *src, unsigned long long add, int keep, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_accum_counter, dim3(1), dim3(1), 0, s, dst, src, add, keep);
     return hipGetLastError();
 }

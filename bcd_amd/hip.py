@@ -39,6 +39,56 @@ class PlanSummary(C.Structure):
 PLAN_ARGTYPES = [_VP, C.POINTER(PlanParams), C.c_int64, C.c_uint64, _VP, _VP, _VP, C.c_int64, _VP]
 
 
+class StateHeader(C.Structure):
+    """bcd_hip_accum_state_header: the 64-byte header of a serialised accumulator state (format v1, include/bcd_hip.h)"""
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("nb_bins", C.c_int32), ("gamma", C.c_float), ("max_value", C.c_float), ("nb_planes", C.c_uint32),
+                ("samples_added", C.c_int64), ("dropped", C.c_int64), ("reserved", C.c_uint8 * 8)]
+
+
+STATE_HEADER_BYTES = 64
+
+
+def _state_api():
+    L = lib()
+    L.bcd_hip_accum_state_info.argtypes = [_VP, C.c_int64, C.POINTER(StateHeader)]
+    L.bcd_hip_accum_state_bytes.argtypes = [_VP, C.POINTER(C.c_int64)]
+    L.bcd_hip_accum_export.argtypes = [_VP, _VP, C.c_int64]
+    L.bcd_hip_accum_import.argtypes = [_VP, _VP, C.c_int64]
+    L.bcd_hip_accum_merge_state.argtypes = [_VP, _VP, C.c_int64]
+    L.bcd_hip_accum_merge.argtypes = [_VP, _VP]
+    return L
+
+
+def _state_buffer(buf):
+    """a contiguous uint8 numpy view of a serialised state (numpy array, bytes, bytearray, memoryview, mmap)"""
+    import numpy as np
+    a = buf if isinstance(buf, np.ndarray) else np.frombuffer(buf, np.uint8)
+    return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+
+
+def accum_state_info(buf):
+    """the header of a serialised accumulator state as a dict (bcd_hip_accum_state_info: host only, no GPU needed); ValueError if the
+    buffer is not a well-formed state of its exact size"""
+    a = _state_buffer(buf)
+    h = StateHeader()
+    rc = _state_api().bcd_hip_accum_state_info(a.ctypes.data_as(_VP) if a.size else None, a.size, C.byref(h))
+    if rc != 0:
+        raise ValueError("not a serialised accumulator state (format v1) of %d bytes: rc=%d" % (a.size, rc))
+    return {"magic": bytes(h.magic), "version": h.version, "header_bytes": h.header_bytes, "width": h.width, "height": h.height,
+            "nb_bins": h.nb_bins, "gamma": h.gamma, "max_value": h.max_value, "nb_planes": h.nb_planes,
+            "samples_added": h.samples_added, "dropped": h.dropped}
+
+
+def accum_state_planes(buf):
+    """(header dict, float32 (nb_planes, H, W) view of the planes) of a serialised state: weight sum, squared-weight sum, 3 colour sums,
+    6 second moments (xx, yy, zz, yz, xz, xy), then the bins channel-major"""
+    a = _state_buffer(buf)
+    info = accum_state_info(a)
+    planes = a[STATE_HEADER_BYTES:].view("<f4").reshape(info["nb_planes"], info["height"], info["width"])
+    return info, planes
+
+
 def default_plan_params(**kw):
     p = PlanParams()
     lib().bcd_hip_default_plan_params(C.byref(p))
@@ -69,6 +119,7 @@ SYMBOLS = [
     "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
     "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
     "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_default_plan_params", "bcd_hip_accum_plan", "bcd_hip_zero_bad_values",
+    "bcd_hip_accum_state_info", "bcd_hip_accum_state_bytes", "bcd_hip_accum_export", "bcd_hip_accum_import", "bcd_hip_accum_merge_state", "bcd_hip_accum_merge",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch",
 ]
 
@@ -468,6 +519,33 @@ class Accumulator:
         T = int(s[0])
         summary = {"planned": T, "active": int(s[1]), "unsampled": int(s[2]), "max_error": float(s[3:4].view(torch.float32)[0])}
         return pixels[:T], counts, err, summary
+
+    # ---- states (bcd_hip_accum_export / _import / _merge_state / _merge; format v1 and merge definition in include/bcd_hip.h)
+    def state_bytes(self):
+        n = C.c_int64(0)
+        self._chk(_state_api().bcd_hip_accum_state_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def export_state(self):
+        """the serialised state (header + planes) as a numpy uint8 array; synchronises, the state is unchanged"""
+        import numpy as np
+        out = np.empty(self.state_bytes(), np.uint8)
+        self._chk(_state_api().bcd_hip_accum_export(self.h, out.ctypes.data_as(_VP), out.size))
+        return out
+
+    def import_state(self, buf):
+        """replaces the state and the counters with a serialised state of the same geometry and parameters"""
+        a = _state_buffer(buf)
+        self._chk(_state_api().bcd_hip_accum_import(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
+
+    def merge_state(self, buf):
+        """adds a serialised state into this one (one fp32 add per element); returns once buf is no longer needed"""
+        a = _state_buffer(buf)
+        self._chk(_state_api().bcd_hip_accum_merge_state(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
+
+    def merge(self, other):
+        """adds other's state into this one, in stream order on both contexts (other may live on another context or device)"""
+        self._chk(_state_api().bcd_hip_accum_merge(self.h, other.h if other is not None else None))
 
     def info(self):
         """(samples accumulated, samples dropped) since create / the last reset; synchronises"""

@@ -6,7 +6,13 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <cstdint>
 #include <cstring>
 #include <utility>
@@ -253,6 +259,136 @@ namespace bcd
 			o_pSummary->m_active = summary.active;
 			o_pSummary->m_unsampled = summary.unsampled;
 			o_pSummary->m_maxError = summary.max_error;
+		}
+		return true;
+	}
+
+	bool DeviceSamplesAccumulator::exportState(std::vector<uint8_t>& o_state) const
+	{
+		o_state.clear();
+		if(!isValid() || !flush())
+			return false;
+		int64_t bytes = 0;
+		if(bcd_hip_accum_state_bytes(m_pAccum, &bytes) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_state_bytes");
+			return false;
+		}
+		o_state.resize(size_t(bytes));
+		if(bcd_hip_accum_export(m_pAccum, o_state.data(), bytes) != BCD_HIP_OK)
+		{
+			o_state.clear();
+			fail("bcd_hip_accum_export");
+			return false;
+		}
+		return true;
+	}
+
+	bool DeviceSamplesAccumulator::saveState(const std::string& i_rPath) const
+	{
+		if(!isValid() || !flush())
+			return false;
+		int64_t bytes = 0;
+		if(bcd_hip_accum_state_bytes(m_pAccum, &bytes) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_state_bytes");
+			return false;
+		}
+		const int fd = open(i_rPath.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
+		if(fd < 0)
+		{
+			m_error = "saveState: cannot create '" + i_rPath + "': " + std::strerror(errno);
+			return false;
+		}
+		// the blocks are reserved before the mapping is written (a full disk fails here, not with a fault on a page of the mapping)
+		const int err = posix_fallocate(fd, 0, off_t(bytes));
+		void* p = err == 0 ? mmap(nullptr, size_t(bytes), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0) : MAP_FAILED;
+		close(fd);
+		if(p == MAP_FAILED)
+		{
+			m_error = "saveState: cannot write " + std::to_string(bytes) + " bytes to '" + i_rPath + "': " + std::strerror(err ? err : errno);
+			unlink(i_rPath.c_str());
+			return false;
+		}
+		const int rc = bcd_hip_accum_export(m_pAccum, p, bytes);
+		munmap(p, size_t(bytes));
+		if(rc != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_export");
+			unlink(i_rPath.c_str());
+			return false;
+		}
+		return true;
+	}
+
+	bool DeviceSamplesAccumulator::fromFile(const std::string& i_rPath, bool i_merge)
+	{
+		const char* what = i_merge ? "mergeState" : "loadState";
+		if(!isValid() || !flush())
+			return false;
+		const int fd = open(i_rPath.c_str(), O_RDONLY);
+		if(fd < 0)
+		{
+			m_error = std::string(what) + ": cannot open '" + i_rPath + "': " + std::strerror(errno);
+			return false;
+		}
+		struct stat sb;
+		if(fstat(fd, &sb) != 0 || sb.st_size < BCD_HIP_ACCUM_STATE_HEADER_BYTES)
+		{
+			close(fd);
+			m_error = std::string(what) + ": '" + i_rPath + "' is not an accumulator state (shorter than its 64-byte header)";
+			return false;
+		}
+		const size_t bytes = size_t(sb.st_size);
+		void* p = mmap(nullptr, bytes, PROT_READ, MAP_PRIVATE, fd, 0);
+		close(fd);
+		if(p == MAP_FAILED)
+		{
+			m_error = std::string(what) + ": cannot map '" + i_rPath + "': " + std::strerror(errno);
+			return false;
+		}
+		(void)madvise(p, bytes, MADV_SEQUENTIAL);
+		// both calls return once the mapping is no longer needed
+		const int rc = i_merge ? bcd_hip_accum_merge_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import(m_pAccum, p, int64_t(bytes));
+		munmap(p, bytes);
+		if(rc != BCD_HIP_OK)
+		{
+			fail((std::string(what) + " '" + i_rPath + "'").c_str());
+			return false;
+		}
+		return true;
+	}
+
+	bool DeviceSamplesAccumulator::loadState(const std::string& i_rPath)
+	{
+		return fromFile(i_rPath, false);
+	}
+
+	bool DeviceSamplesAccumulator::mergeState(const std::string& i_rPath)
+	{
+		return fromFile(i_rPath, true);
+	}
+
+	bool DeviceSamplesAccumulator::merge(const DeviceSamplesAccumulator& i_rOther)
+	{
+		if(!isValid())
+			return false;
+		if(!i_rOther.isValid())
+		{
+			m_error = "merge: the other accumulator is not valid";
+			return false;
+		}
+		if(!flush())
+			return false;
+		if(!i_rOther.flush())
+		{
+			m_error = "merge: the other accumulator: " + i_rOther.lastError();
+			return false;
+		}
+		if(bcd_hip_accum_merge(m_pAccum, i_rOther.m_pAccum) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_merge");
+			return false;
 		}
 		return true;
 	}

@@ -142,6 +142,63 @@ long long bcdcore_device_plan(const float* s, long long n, int W, int H, int nbi
 	return (long long)list.size();
 }
 
+// a bcd::DeviceSamplesAccumulator kept between calls, so that tests drive its state methods (exportState, saveState, loadState, mergeState,
+// merge).  Every int call returns 0, or -1 with the class's message in bcdcore_device_acc_error(handle)
+void* bcdcore_device_acc_create(int W, int H, int nbins, float gamma, float maxval, int device)
+{
+	HistogramParameters hp;
+	hp.m_nbOfBins = nbins; hp.m_gamma = gamma; hp.m_maxValue = maxval;
+	return new DeviceSamplesAccumulator(W, H, hp, device);
+}
+
+void bcdcore_device_acc_destroy(void* h) { delete (DeviceSamplesAccumulator*)h; }
+
+const char* bcdcore_device_acc_error(void* h) { return ((DeviceSamplesAccumulator*)h)->lastError().c_str(); }
+
+int bcdcore_device_acc_valid(void* h) { return ((DeviceSamplesAccumulator*)h)->isValid() ? 1 : 0; }
+
+// samples: n x (line, col, r, g, b, weight) through addSample (left in the class's host batch until a call flushes it)
+void bcdcore_device_acc_add(void* h, const float* s, long long n)
+{
+	DeviceSamplesAccumulator* a = (DeviceSamplesAccumulator*)h;
+	for(long long i = 0; i < n; ++i, s += 6)
+		a->addSample(int(s[0]), int(s[1]), s[2], s[3], s[4], s[5]);
+}
+
+// exportState into out[capacity]: the state's size, -1 on failure, -2 if capacity is too small (out == nullptr: the size only)
+long long bcdcore_device_acc_export(void* h, unsigned char* out, long long capacity)
+{
+	std::vector<uint8_t> st;
+	if(!((DeviceSamplesAccumulator*)h)->exportState(st)) return -1;
+	if(!out) return (long long)st.size();
+	if(capacity < (long long)st.size()) return -2;
+	std::copy(st.begin(), st.end(), out);
+	return (long long)st.size();
+}
+
+int bcdcore_device_acc_save(void* h, const char* path) { return ((DeviceSamplesAccumulator*)h)->saveState(path) ? 0 : -1; }
+int bcdcore_device_acc_load(void* h, const char* path) { return ((DeviceSamplesAccumulator*)h)->loadState(path) ? 0 : -1; }
+int bcdcore_device_acc_merge_state(void* h, const char* path) { return ((DeviceSamplesAccumulator*)h)->mergeState(path) ? 0 : -1; }
+int bcdcore_device_acc_merge(void* dst, void* src)
+{
+	return ((DeviceSamplesAccumulator*)dst)->merge(*(const DeviceSamplesAccumulator*)src) ? 0 : -1;
+}
+
+// host snapshot (getSamplesStatistics) and the counters (lastError() keeps the message of an earlier refused call, so it is not checked)
+int bcdcore_device_acc_statistics(void* h, float* ns, float* mean, float* cov, float* hist, long long* counts)
+{
+	DeviceSamplesAccumulator* a = (DeviceSamplesAccumulator*)h;
+	if(!a->isValid()) return -1;
+	SamplesStatisticsImages st = a->getSamplesStatistics();
+	st.m_nbOfSamplesImage.copyDataTo(ns);
+	st.m_meanImage.copyDataTo(mean);
+	st.m_covarImage.copyDataTo(cov);
+	st.m_histoImage.copyDataTo(hist);
+	counts[0] = a->nbOfAccumulatedSamples();
+	counts[1] = a->nbOfDroppedSamples();
+	return 0;
+}
+
 void bcdcore_release_engines() { releaseEngines(); }
 
 // runs bcd::Denoiser (nscales == 1) or bcd::MultiscaleDenoiser through the IDenoiser interface; returns denoise()'s bool.

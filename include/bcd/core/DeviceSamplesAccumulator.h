@@ -77,6 +77,20 @@ namespace bcd
 		bool planSamples(int64_t i_budget, uint64_t i_offset, const PlanParameters& i_rParameters, std::vector<int32_t>& o_pixelIndices,
 				PlanSummary* o_pSummary = nullptr);
 
+		/// States (bcd_hip_accum_export / _import / _merge_state / _merge in bcd_hip.h, which define the format v1 and the merge).  Each call
+		/// applies the samples buffered by addSample first (on both accumulators for merge) and returns false with lastError() on failure;
+		/// the accumulator stays usable.  Files are mapped, not read into a second host copy.
+		/// the serialised state (header + planes); synchronises
+		bool exportState(std::vector<uint8_t>& o_state) const;
+		/// the serialised state written to a file (replaced if it exists)
+		bool saveState(const std::string& i_rPath) const;
+		/// replaces the state and counters with a file's; its frame size, bins, gamma and max value must be this accumulator's
+		bool loadState(const std::string& i_rPath);
+		/// adds a file's state into this one (one fp32 add per running sum)
+		bool mergeState(const std::string& i_rPath);
+		/// adds another accumulator's state into this one; the other may live on another device and is not changed
+		bool merge(const DeviceSamplesAccumulator& i_rOther);
+
 		/// back to an empty accumulator (the frame geometry and the device buffers are kept)
 		void reset();
 		/// samples accumulated / skipped since construction or the last reset (synchronises)
@@ -87,6 +101,8 @@ namespace bcd
 		/// applies the pending addSample batch; false (message in lastError()) if this flush failed
 		bool flush() const;
 		void fail(const char* i_pWhat) const;
+		/// loadState / mergeState: the mapped file through bcd_hip_accum_import (merge = false) or _merge_state
+		bool fromFile(const std::string& i_rPath, bool i_merge);
 
 	private:
 		int m_width, m_height, m_nbOfBins;

@@ -384,6 +384,48 @@ typedef struct bcd_hip_plan_summary {
 void bcd_hip_default_plan_params(bcd_hip_plan_params *p);
 int  bcd_hip_accum_plan(bcd_hip_accum *acc, const bcd_hip_plan_params *params, int64_t budget, uint64_t offset, float *d_error, int32_t *d_counts,
                         int32_t *d_pixels, int64_t capacity, bcd_hip_plan_summary *d_summary);
+/* States: export, import, merge.  Serialised state, format v1: a 64-byte little-endian header, then the
+ * nb_planes = 11 + 3 * nb_bins planes exactly as they sit in HBM, nb_planes * height * width fp32 values: ACC_W (weight sum), ACC_W2
+ * (squared-weight sum), the 3 weighted colour sums, the 6 weighted second moments (xx, yy, zz, yz, xz, xy), then the bins channel-major
+ * (bin index ch * nb_bins + bin); each plane in pixel order line * width + col.  The total size is exactly 64 + 4 * nb_planes * W * H
+ * bytes.  Field offsets: magic 0, version 8, header_bytes 12, width 16, height 20, nb_bins 24, gamma 28, max_value 32, nb_planes 36,
+ * samples_added 40, dropped 48, reserved 56.
+ *   state_info: host only (no device, no context): reads the first 64 bytes at h_state, `bytes` being the size of the whole state;
+ *           EINVAL unless magic, version, header_bytes, nb_bins in [2, 85], positive sizes below 2^31 pixels, nb_planes, the exact size,
+ *           zero reserved bytes and non-negative counters hold.  out may be NULL.
+ *   state_bytes: the serialised size of the accumulator's state (no synchronisation).
+ *   export: header + planes into h_state[capacity]; synchronises; the state is unchanged.
+ *   import: replaces the state and the counters; W, H, nb_bins, gamma and max_value must equal the accumulator's (gamma and max_value
+ *           bit for bit).
+ *   merge_state / merge: dst[i] = dst[i] + src[i] for every float of the state, one IEEE fp32 add and nothing else; samples_added and
+ *           dropped add up.  A merge of A into B has the bits of a merge of B into A; addition is not associative, so a caller that
+ *           merges several states fixes the order.
+ * Import and merge refuse a malformed state, a geometry or parameter mismatch, dst == src and null pointers with EINVAL before any
+ * device work, the state untouched; a refused call does not block the next one (after EDEVICE the state is undefined).  import and
+ * merge_state return once h_state is no longer needed (it goes through two pinned staging chunks of at most 64 MiB owned by the
+ * accumulator, allocated on first use); their device work stays ordered on the context's stream.  merge reads everything already
+ * enqueued on src's stream and nothing enqueued there after the call (events in both directions, the host is not blocked); src may
+ * belong to another context, on the same or another device (another device: chunks of at most 64 MiB through two dst-side scratch
+ * buffers, peer copies; no peer access needed).  No scratch of the state's size is ever allocated. */
+typedef struct bcd_hip_accum_state_header {
+    char     magic[8];       /* the 8 bytes BCDACCST, no terminator */
+    uint32_t version;        /* 1 */
+    uint32_t header_bytes;   /* 64: offset of the first plane */
+    int32_t  width, height, nb_bins;
+    float    gamma, max_value;
+    uint32_t nb_planes;      /* 11 + 3 * nb_bins */
+    int64_t  samples_added;  /* as bcd_hip_accum_info */
+    int64_t  dropped;
+    uint8_t  reserved[8];    /* zero */
+} bcd_hip_accum_state_header;
+#define BCD_HIP_ACCUM_STATE_VERSION 1
+#define BCD_HIP_ACCUM_STATE_HEADER_BYTES 64
+int  bcd_hip_accum_state_info(const void *h_state, int64_t bytes, bcd_hip_accum_state_header *out);
+int  bcd_hip_accum_state_bytes(bcd_hip_accum *acc, int64_t *bytes);
+int  bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity);
+int  bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes);
+int  bcd_hip_accum_merge_state(bcd_hip_accum *acc, const void *h_state, int64_t bytes);
+int  bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src);
 /* checkAndPutToZeroNegativeInfNaNValues   src/cli/main.cpp:389-420 */
 int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n);
 
