@@ -67,6 +67,27 @@ def device_accumulate(samples, W, H, nbins=20, gamma=2.2, maxval=2.5, device=0, 
     return ns, mean, cov, hist
 
 
+def device_splat(calls, W, H, radius, table, nbins=20, gamma=2.2, maxval=2.5, device=0):
+    """a stream of mixed calls through bcd::DeviceSamplesAccumulator with a reconstruction filter set: calls (n, 7) float32, each
+    (kind, a, b, r, g, b, w); kind 0: addSample(line = a, col = b, ...), kind 1: splatSample(x = a, y = b, ...).  radius: (radius_x, radius_y);
+    table: square float32.  -> ((ns, mean, cov, hist), (samples accumulated, dropped))"""
+    calls = np.ascontiguousarray(calls, np.float32)
+    table = np.ascontiguousarray(table, np.float32)
+    assert calls.ndim == 2 and calls.shape[1] == 7 and table.ndim == 2 and table.shape[0] == table.shape[1]
+    ns = np.empty((H, W, 1), np.float32)
+    mean = np.empty((H, W, 3), np.float32)
+    cov = np.empty((H, W, 6), np.float32)
+    hist = np.empty((H, W, 3 * nbins), np.float32)
+    counts = (C.c_longlong * 2)()
+    rc = lib().bcdcore_device_splat(_fp(calls), C.c_longlong(calls.shape[0]), W, H, nbins, C.c_float(gamma), C.c_float(maxval), int(device),
+                                    C.c_float(radius[0]), C.c_float(radius[1]), int(table.shape[0]), _fp(table), _fp(ns), _fp(mean), _fp(cov),
+                                    _fp(hist), counts)
+    if rc != 0:
+        lib().bcdcore_device_accumulate_error.restype = C.c_char_p
+        raise RuntimeError("DeviceSamplesAccumulator: " + lib().bcdcore_device_accumulate_error().decode())
+    return (ns, mean, cov, hist), (counts[0], counts[1])
+
+
 def device_plan(samples, W, H, budget, offset=0, threshold=0.0, eps=1e-3, min_samples=2.0, max_per_pixel=16, nbins=20, gamma=2.2, maxval=2.5,
                 device=0, invalid_first=False):
     """the stream through bcd::DeviceSamplesAccumulator::addSample (left in its host buffer), then planSamples -> (pixel list, summary dict);

@@ -75,6 +75,13 @@ hipError_t bcd_accum_sort(void *, size_t *, const uint32_t *, uint32_t *, const 
 hipError_t bcd_launch_accum_segments(const uint32_t *, const uint32_t *, int64_t, int64_t, const float *, const float *, int, float, float, float *,
                                      hipStream_t);
 hipError_t bcd_launch_accum_snapshot(const float *, int64_t, int, float *, float *, float *, float *, hipStream_t);
+int bcd_splat_ring_cells(int nx, int ny);
+int bcd_splat_max_staged(int ts);
+hipError_t bcd_launch_splat_keys(const float *, int64_t, int, int, const float *, const int *, const float *, uint32_t *, uint32_t *, unsigned long long *,
+                                 hipStream_t);
+hipError_t bcd_launch_splat_cells(const uint32_t *, int64_t, int64_t, void *, hipStream_t);
+hipError_t bcd_launch_splat(const void *, const uint32_t *, const float *, const float *, const float *, int, int, const float *, const int *,
+                            const float *, int, int, float, float, float *, hipStream_t);
 size_t bcd_plan_red_bytes();
 hipError_t bcd_plan_scan_bytes(int64_t, size_t *);
 hipError_t bcd_launch_accum_plan(const float *, int64_t, float, float, float, int, int64_t, uint64_t, float *, int32_t *, int32_t *, int64_t, int64_t *,
@@ -1708,6 +1715,15 @@ struct bcd_hip_accum {
     bool stage_busy[2] = { false, false };
     size_t chunk_bytes = 0;
     hipEvent_t ev_merge = nullptr; // recorded on the context's stream around a merge (the source's work so far / the destination's reads)
+    // reconstruction filter of the splatted add (bcd_hip_accum_set_filter): the parameters are kernel arguments, the table lives on the
+    // device and is replaced in stream order through a pinned staging copy (filter_ev: that copy has left the staging buffer)
+    bool has_filter = false;
+    float filter_f[4] = { 0.f, 0.f, 0.f, 0.f }; // rx, ry, inv_rx, inv_ry
+    int filter_g[5] = { 0, 0, 0, 0, 0 };        // table size, kx, ky, nx, ny
+    DevBuf table, cells;                        // the table (64 x 64 floats at most); the runs of the extended frame's cells (grow-only)
+    float *table_stage = nullptr;
+    hipEvent_t filter_ev = nullptr;
+    bool filter_busy = false;
 };
 
 namespace {
@@ -1748,6 +1764,23 @@ int accum_plan_scratch(bcd_hip_accum *a)
     return BCD_HIP_OK;
 }
 
+// cells of the frame extended by (kx, ky) on each side (the key space of the splatted add)
+#define SPLAT_MAX_K 4
+int64_t accum_extended_cells(const bcd_hip_accum *a, int kx, int ky) { return ((int64_t)a->W + 2 * kx) * ((int64_t)a->H + 2 * ky); }
+
+// scratch of the splatted add for any filter, beside accum_scratch's: the cell runs and the sort's storage for the wider keys
+int accum_splat_scratch(bcd_hip_accum *a)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    const int64_t NE = accum_extended_cells(a, SPLAT_MAX_K, SPLAT_MAX_K);
+    if (NE >= ((int64_t)1 << 32) - 1) return BCD_HIP_OK; // (set_filter refuses such frames)
+    RCCHK(ensure(ctx, a->cells, (size_t)NE * 2 * sizeof(uint32_t)));
+    size_t bytes = 0;
+    HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, a->capacity, 64 - __builtin_clzll((unsigned long long)NE), ctx->stream));
+    if (bytes > a->sort.bytes) RCCHK(ensure(ctx, a->sort, bytes));
+    return BCD_HIP_OK;
+}
+
 } // namespace
 
 int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc)
@@ -1774,6 +1807,7 @@ int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamm
     }
     if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_scratch(a, a->capacity);
     if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_plan_scratch(a);
+    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_splat_scratch(a);
     if (rc == BCD_HIP_OK) rc = bcd_hip_accum_reset(a);
     if (rc != BCD_HIP_OK) { bcd_hip_accum_destroy(a); return rc; }
     *acc = a;
@@ -1788,6 +1822,10 @@ void bcd_hip_accum_destroy(bcd_hip_accum *acc)
     for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
                        &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
         if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : { &acc->table, &acc->cells })
+        if (b->p) (void)hipFree(b->p);
+    if (acc->table_stage) (void)hipHostFree(acc->table_stage);
+    if (acc->filter_ev) (void)hipEventDestroy(acc->filter_ev);
     for (int i = 0; i < 2; ++i) {
         if (acc->stage[i]) (void)hipHostFree(acc->stage[i]);
         if (acc->chunk[i]) (void)hipFree(acc->chunk[i]);
@@ -1845,6 +1883,112 @@ int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, cons
                                               acc->maxval, (float *)acc->state.p, ctx->stream));
     }
     acc->submitted += n;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y, int table_size, const float *h_table)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!h_table) { acc->has_filter = false; return BCD_HIP_OK; }
+    if (!(radius_x > 0.f && radius_x <= 3.f) || !(radius_y > 0.f && radius_y <= 3.f)) return bad(ctx, "filter radii must be in (0, 3]");
+    if (table_size < 1 || table_size > 64) return bad(ctx, "filter table size must be in [1, 64]");
+    const int tt = table_size * table_size;
+    for (int i = 0; i < tt; ++i)
+        if (!std::isfinite(h_table[i]) || h_table[i] < 0.f)
+            return bad(ctx, "filter table entries must be finite and >= 0 (filters with negative lobes are not supported)");
+    const int kx = (int)ceilf(radius_x + 0.5f), ky = (int)ceilf(radius_y + 0.5f);
+    // (col + 0.5f must be exact for the kernel's neighbour range, and the cells' keys are 32 bits wide)
+    if (accum_extended_cells(acc, kx, ky) >= ((int64_t)1 << 32) - 1 || std::max(acc->W, acc->H) >= (1 << 22)) {
+        set_err(ctx, "frames of 2^22 pixels or more on a side are not supported with a filter");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    DEVICE_GUARD(ctx);
+    RCCHK(ensure(ctx, acc->table, 64 * 64 * sizeof(float)));
+    if (!acc->table_stage) HIPCHK(ctx, hipHostMalloc((void **)&acc->table_stage, 64 * 64 * sizeof(float), hipHostMallocDefault));
+    if (!acc->filter_ev) HIPCHK(ctx, hipEventCreateWithFlags(&acc->filter_ev, hipEventDisableTiming));
+    if (acc->filter_busy) { HIPCHK(ctx, hipEventSynchronize(acc->filter_ev)); acc->filter_busy = false; }
+    std::memcpy(acc->table_stage, h_table, (size_t)tt * sizeof(float));
+    HIPCHK(ctx, hipMemcpyAsync(acc->table.p, acc->table_stage, (size_t)tt * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(acc->filter_ev, ctx->stream));
+    acc->filter_busy = true;
+    // cells further than n from a pixel hold no sample within the radius: a sample of a cell at offset n + 1 is at least n + 0.5 away
+    // (exactly representable, and the rounded subtraction is monotone), so n is the smallest integer with n + 0.5 >= r -- never more
+    // than K, the candidate range of the definition
+    int nx = 0, ny = 0;
+    while ((float)nx + 0.5f < radius_x) ++nx;
+    while ((float)ny + 0.5f < radius_y) ++ny;
+    acc->filter_f[0] = radius_x; acc->filter_f[1] = radius_y; acc->filter_f[2] = 1.f / radius_x; acc->filter_f[3] = 1.f / radius_y;
+    acc->filter_g[0] = table_size; acc->filter_g[1] = kx; acc->filter_g[2] = ky;
+    acc->filter_g[3] = std::min(nx, kx); acc->filter_g[4] = std::min(ny, ky);
+    acc->has_filter = true;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!acc->has_filter) return bad(ctx, "the accumulator has no filter (bcd_hip_accum_set_filter)");
+    if (n < 0) return bad(ctx, "negative sample count");
+    if (n == 0) return BCD_HIP_OK;
+    if (!d_xy || !d_rgb) return bad(ctx, "null samples");
+    DEVICE_GUARD(ctx);
+    const int *g = acc->filter_g;
+    const int64_t NE = accum_extended_cells(acc, g[1], g[2]);
+    // a chunk holds at most as many samples as keep the average ring of a tile within 0.55 of the staging arrays (chunks are applied in
+    // stream order, so splitting a batch changes no bit); denser tiles take the kernel's global-memory path
+    const int max_staged = bcd_splat_max_staged(g[0]), ring = bcd_splat_ring_cells(g[3], g[4]);
+    const int64_t dense = std::max<int64_t>((int64_t)1 << 16, (int64_t)((double)acc->N * 0.55 * max_staged / ring));
+    const int64_t chunk = std::min(dense, acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30));
+    if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
+    RCCHK(ensure(ctx, acc->cells, (size_t)NE * 2 * sizeof(uint32_t)));
+    const int end_bit = 64 - __builtin_clzll((unsigned long long)NE); // keys are <= NE (NE = dropped)
+    size_t need = 0;
+    HIPCHK(ctx, bcd_accum_sort(nullptr, &need, nullptr, nullptr, nullptr, nullptr, std::min(n, chunk), end_bit, ctx->stream));
+    RCCHK(ensure(ctx, acc->sort, need)); // (more key bits than the scattered add's: the storage may differ)
+    uint32_t *k0 = (uint32_t *)acc->keys[0].p, *k1 = (uint32_t *)acc->keys[1].p, *v0 = (uint32_t *)acc->vals[0].p, *v1 = (uint32_t *)acc->vals[1].p;
+    for (int64_t b = 0; b < n; b += chunk) {
+        const int64_t m = std::min(chunk, n - b);
+        const float *xy = d_xy + 2 * b, *rgb = d_rgb + 3 * b, *w = d_weights ? d_weights + b : nullptr;
+        size_t bytes = acc->sort.bytes;
+        HIPCHK(ctx, bcd_launch_splat_keys(xy, m, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, k0, v0,
+                                          (unsigned long long *)acc->dropped.p, ctx->stream));
+        HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
+        HIPCHK(ctx, bcd_launch_splat_cells(k1, m, NE, acc->cells.p, ctx->stream));
+        // staging arrays for 1.5 times the average ring of this chunk plus 8 sigma of a uniform distribution
+        const double avg = (double)m * ring / (double)acc->N;
+        const int cap = (int)std::min<double>(max_staged, 1.5 * avg + 8.0 * std::sqrt(avg) + 64.0);
+        HIPCHK(ctx, bcd_launch_splat(acc->cells.p, v1, xy, rgb, w, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, cap, acc->nbins,
+                                     acc->gamma, acc->maxval, (float *)acc->state.p, ctx->stream));
+    }
+    acc->submitted += n;
+    return BCD_HIP_OK;
+}
+
+// separable table of a standard filter (host only); 1-D factors at d = (i + 0.5) / TS * r in double, product rounded to float once
+int bcd_hip_filter_table(int kind, float radius_x, float radius_y, float param, int table_size, float *h_out)
+{
+    if (!h_out || table_size < 1 || table_size > 64) return BCD_HIP_EINVAL;
+    if (!(radius_x > 0.f && radius_x <= 3.f) || !(radius_y > 0.f && radius_y <= 3.f)) return BCD_HIP_EINVAL;
+    if (kind < BCD_HIP_FILTER_BOX || kind > BCD_HIP_FILTER_BLACKMAN_HARRIS) return BCD_HIP_EINVAL;
+    if (kind == BCD_HIP_FILTER_GAUSSIAN && !(std::isfinite(param) && param >= 0.f)) return BCD_HIP_EINVAL;
+    auto f1 = [&](double d, double r) -> double {
+        switch (kind) {
+        case BCD_HIP_FILTER_BOX: return 1.0;
+        case BCD_HIP_FILTER_TENT: return std::max(0.0, 1.0 - d / r);
+        case BCD_HIP_FILTER_GAUSSIAN: return std::max(0.0, std::exp(-(double)param * d * d) - std::exp(-(double)param * r * r));
+        default: { // Blackman-Harris window of width 2 r centred on the sample
+            const double pi = 3.14159265358979323846, u = (d + r) / (2.0 * r);
+            return std::max(0.0, 0.35875 - 0.48829 * std::cos(2.0 * pi * u) + 0.14128 * std::cos(4.0 * pi * u) - 0.01168 * std::cos(6.0 * pi * u));
+        }
+        }
+    };
+    for (int iy = 0; iy < table_size; ++iy)
+        for (int ix = 0; ix < table_size; ++ix) {
+            const double dx = (ix + 0.5) / table_size * (double)radius_x, dy = (iy + 0.5) / table_size * (double)radius_y;
+            h_out[iy * table_size + ix] = (float)(f1(dx, (double)radius_x) * f1(dy, (double)radius_y));
+        }
     return BCD_HIP_OK;
 }
 

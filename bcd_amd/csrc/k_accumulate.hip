@@ -137,6 +137,23 @@ __global__ __launch_bounds__(256) void k_accum_keys(const int32_t *__restrict__ 
     if (bal && (threadIdx.x & 63) == __ffsll((long long)bal) - 1) atomicAdd(dropped, (unsigned long long)__popcll(bal));
 }
 
+// one sample into a pixel's running sums (registers) and its bins in HBM (hp[b * N] = bin b of the pixel): addSample of the scattered and
+// the splatted paths
+__device__ inline void acc_add_sample(AccSums &s, float *__restrict__ hp, int64_t N, float R, float G, float B, float w, int nbins, float gamma,
+                                      float maxval)
+{
+    s.add(R, G, B, w);
+    const float c3[3] = { R, G, B };
+    for (int ch = 0; ch < 3; ++ch) {
+        int lo;
+        float lw, hw;
+        acc_bin(c3[ch], nbins, gamma, maxval, lo, lw, hw);
+        const int b = ch * nbins + lo;
+        hp[b * N] += w * lw;
+        hp[(b + 1) * N] += w * hw;
+    }
+}
+
 // (b) step 3: one thread per run of equal keys in the stably sorted batch walks the run -- the pixel's samples in stream order
 __global__ __launch_bounds__(256) void k_accum_segments(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, int64_t n, int64_t N,
                                                         const float *__restrict__ rgb, const float *__restrict__ weights, int nbins, float gamma,
@@ -152,20 +169,255 @@ __global__ __launch_bounds__(256) void k_accum_segments(const uint32_t *__restri
     s.load(st, N, p);
     for (int64_t j = i; j < n && keys[j] == key; ++j) {
         const int64_t e = vals[j];
-        const float R = rgb[e * 3], G = rgb[e * 3 + 1], B = rgb[e * 3 + 2];
-        const float w = weights ? weights[e] : 1.f;
-        s.add(R, G, B, w);
-        const float c3[3] = { R, G, B };
-        for (int ch = 0; ch < 3; ++ch) {
-            int lo;
-            float lw, hw;
-            acc_bin(c3[ch], nbins, gamma, maxval, lo, lw, hw);
-            const int b = ch * nbins + lo;
-            hp[b * N] += w * lw;
-            hp[(b + 1) * N] += w * hw;
-        }
+        acc_add_sample(s, hp, N, rgb[e * 3], rgb[e * 3 + 1], rgb[e * 3 + 2], weights ? weights[e] : 1.f, nbins, gamma, maxval);
     }
     s.store(st, N, p);
+}
+
+// (b') splatted add (bcd_hip_accum_add_splatted; the definition is in include/bcd_hip.h, the design in DESIGN.md section 10): samples at
+// continuous positions go through the accumulator's reconstruction filter to every pixel of their footprint.  Gather form: the n samples
+// are sorted by their CELL (the pixel floor(x), floor(y) on the frame extended by (kx, ky)), and one thread per destination pixel merges
+// the runs of the cells around it by batch position -- the pixel's contributions in stream order, no float atomics.
+struct SplatFilter {
+    float rx, ry, inv_rx, inv_ry;
+    int ts;     // the table is ts x ts
+    int kx, ky; // K of the definition: the key frame is extended by it, the candidate pixels of a sample are c0 +- kx, l0 +- ky
+    int nx, ny; // cells further than this from a pixel hold no sample that passes dx < rx (nx <= kx: smallest m with m + 0.5 >= rx)
+};
+
+// the filter value of the definition for pixel (col, line) and a sample at (x, y); 0: the pixel is not in the sample's footprint
+__device__ inline float splat_weight(const SplatFilter &F, const float *T, float x, float y, int col, int line)
+{
+    const float dx = fabsf(((float)col + 0.5f) - x), dy = fabsf(((float)line + 0.5f) - y);
+    if (!(dx < F.rx && dy < F.ry)) return 0.f;
+    int ix = (int)(dx * F.inv_rx * (float)F.ts), iy = (int)(dy * F.inv_ry * (float)F.ts);
+    ix = ix < F.ts - 1 ? ix : F.ts - 1;
+    iy = iy < F.ts - 1 ? iy : F.ts - 1;
+    return T[iy * F.ts + ix];
+}
+
+// step 1: key = the sample's cell on the extended frame, value = position in the batch.  Samples that contribute nothing (position not
+// finite or outside the extended frame, empty footprint: a pure function of the sample and the filter) get the past-the-end key and are
+// counted as dropped (integer atomics, one per wavefront)
+__global__ __launch_bounds__(256) void k_accum_splat_keys(const float *__restrict__ xy, int64_t n, int W, int H, SplatFilter F,
+                                                          const float *__restrict__ T, uint32_t *__restrict__ keys, uint32_t *__restrict__ vals,
+                                                          unsigned long long *__restrict__ dropped)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool drop = false;
+    if (i < n) {
+        const int We = W + 2 * F.kx, He = H + 2 * F.ky;
+        const float x = xy[2 * i], y = xy[2 * i + 1];
+        uint32_t key = (uint32_t)((int64_t)We * He);
+        bool ok = __builtin_isfinite(x) && __builtin_isfinite(y) && x >= -(float)F.kx && x < (float)(W + F.kx) && y >= -(float)F.ky &&
+                  y < (float)(H + F.ky);
+        if (ok) {
+            const int c0 = (int)floorf(x), l0 = (int)floorf(y);
+            const int ca = c0 - F.nx > 0 ? c0 - F.nx : 0, cb = c0 + F.nx < W - 1 ? c0 + F.nx : W - 1;
+            const int la = l0 - F.ny > 0 ? l0 - F.ny : 0, lb = l0 + F.ny < H - 1 ? l0 + F.ny : H - 1;
+            bool any = false;
+            for (int line = la; line <= lb && !any; ++line)
+                for (int col = ca; col <= cb && !any; ++col) any = splat_weight(F, T, x, y, col, line) != 0.f;
+            ok = any;
+            if (any) key = (uint32_t)((int64_t)(l0 + F.ky) * We + (c0 + F.kx));
+        }
+        keys[i] = key;
+        vals[i] = (uint32_t)i;
+        drop = !ok;
+    }
+    const unsigned long long bal = __ballot(drop);
+    if (bal && (threadIdx.x & 63) == __ffsll((long long)bal) - 1) atomicAdd(dropped, (unsigned long long)__popcll(bal));
+}
+
+// step 3: the run of every cell in the sorted batch, [cells[c].x, cells[c].y) (the array is zeroed before: empty cells stay (0, 0))
+__global__ __launch_bounds__(256) void k_accum_splat_cells(const uint32_t *__restrict__ keys, int64_t n, uint32_t NE, uint2 *__restrict__ cells)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t key = keys[i];
+    if (key >= NE) return;
+    if (i == 0 || keys[i - 1] != key) cells[key].x = (uint32_t)i;
+    if (i == n - 1 || keys[i + 1] != key) cells[key].y = (uint32_t)(i + 1);
+}
+
+// step 4.  A workgroup of 256 threads owns a tile of SPLAT_TX x SPLAT_TY destination pixels (a wavefront: 2 lines of 32 pixels, 128
+// consecutive bytes of every plane per line).  Its RING: the cells of the tile's pixels plus (nx, ny) on each side, row-major.
+#define SPLAT_TX 32
+#define SPLAT_TY 8
+#define SPLAT_MAX_NB 3                                                                       // nx, ny <= 3 (radii <= 3)
+#define SPLAT_RING_MAX ((SPLAT_TX + 2 * SPLAT_MAX_NB) * (SPLAT_TY + 2 * SPLAT_MAX_NB))       // 38 x 14 = 532 cells
+#define SPLAT_ROWS_MAX (2 * SPLAT_MAX_NB + 1)
+#define SPLAT_SAMPLE_BYTES 28                                                                // staged: position, x, y, r, g, b, weight
+#define SPLAT_LDS_BYTES (64 * 1024)
+#define SPLAT_NONE 0xffffffffu
+
+// the samples of the ring's cells: STAGED in LDS (index = slot in the staged arrays), or read from the sorted arrays in global memory
+// (index = place in the sorted batch) when the ring's samples do not fit the staging arrays -- the same values in the same order
+template <bool STAGED>
+struct SplatRuns {
+    const uint32_t *g0, *b0;                          // LDS, per ring cell: start in the sorted batch; start in the staged arrays (b0[rc + 1]: end)
+    const uint32_t *s_pos;                            // LDS staging arrays
+    const float *s_x, *s_y, *s_r, *s_g, *s_b, *s_w;
+    const uint32_t *vals;                             // the sorted batch positions and the batch itself
+    const float *xy, *rgb, *weights;
+    __device__ uint32_t begin(int rc) const { return STAGED ? b0[rc] : g0[rc]; }
+    __device__ uint32_t count(int rc) const { return b0[rc + 1] - b0[rc]; }
+    __device__ uint32_t pos(uint32_t i) const { return STAGED ? s_pos[i] : vals[i]; }
+    __device__ void position(uint32_t i, float &x, float &y) const
+    {
+        if (STAGED) { x = s_x[i]; y = s_y[i]; }
+        else { const int64_t e = vals[i]; x = xy[2 * e]; y = xy[2 * e + 1]; }
+    }
+    __device__ void colour(uint32_t i, float &R, float &G, float &B, float &w) const
+    {
+        if (STAGED) { R = s_r[i]; G = s_g[i]; B = s_b[i]; w = s_w[i]; }
+        else { const int64_t e = vals[i]; R = rgb[3 * e]; G = rgb[3 * e + 1]; B = rgb[3 * e + 2]; w = weights ? weights[e] : 1.f; }
+    }
+};
+
+// the earliest sample at batch position >= next, in the 2 nx + 1 cells rc0.. of one ring row, that has pixel (col, line) in its footprint:
+// its position (SPLAT_NONE: none), index and filter value.  Every run ascends in position.
+template <bool STAGED>
+__device__ inline void splat_row_next(const SplatRuns<STAGED> &S, const SplatFilter &F, const float *T, int rc0, int col, int line, uint32_t next,
+                                      uint32_t &bpos, uint32_t &bidx, float &bf)
+{
+    bpos = SPLAT_NONE; bidx = 0; bf = 0.f;
+    for (int c = 0; c <= 2 * F.nx; ++c) {
+        const uint32_t b = S.begin(rc0 + c), cnt = S.count(rc0 + c);
+        uint32_t lo = 0, hi = cnt;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (S.pos(b + mid) < next) lo = mid + 1;
+            else hi = mid;
+        }
+        for (uint32_t k = lo; k < cnt; ++k) {
+            const uint32_t p = S.pos(b + k);
+            if (p >= bpos) break; // (later than the best of the cells before)
+            float x, y;
+            S.position(b + k, x, y);
+            const float f = splat_weight(F, T, x, y, col, line);
+            if (f != 0.f) { bpos = p; bidx = b + k; bf = f; break; }
+        }
+    }
+}
+
+// one destination pixel: merges the 2 ny + 1 ring rows' candidates by batch position and adds each contribution as k_accum_segments does.
+// rc0: the ring cell at the top left of the pixel's neighbourhood; RW: cells per ring row
+template <bool STAGED>
+__device__ inline void splat_pixel(const SplatRuns<STAGED> &S, const SplatFilter &F, const float *T, int rc0, int RW, int col, int line, int64_t p,
+                                   int64_t N, int nbins, float gamma, float maxval, float *__restrict__ st)
+{
+    uint32_t cpos[SPLAT_ROWS_MAX], cidx[SPLAT_ROWS_MAX];
+    float cf[SPLAT_ROWS_MAX];
+#pragma unroll
+    for (int r = 0; r < SPLAT_ROWS_MAX; ++r) { cpos[r] = SPLAT_NONE; cidx[r] = 0; cf[r] = 0.f; }
+    for (int r = 0; r <= 2 * F.ny; ++r) {
+        uint32_t np, ni;
+        float nf;
+        splat_row_next(S, F, T, rc0 + r * RW, col, line, 0u, np, ni, nf);
+#pragma unroll
+        for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
+            if (q == r) { cpos[q] = np; cidx[q] = ni; cf[q] = nf; }
+    }
+    float *hp = st + (int64_t)ACC_H * N + p;
+    AccSums s;
+    bool loaded = false;
+    for (;;) {
+        uint32_t best = SPLAT_NONE, idx = 0;
+        float f = 0.f;
+        int br = 0;
+#pragma unroll
+        for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
+            if (cpos[q] < best) { best = cpos[q]; idx = cidx[q]; f = cf[q]; br = q; }
+        if (best == SPLAT_NONE) break;
+        if (!loaded) { s.load(st, N, p); loaded = true; }
+        float R, G, B, w;
+        S.colour(idx, R, G, B, w);
+        acc_add_sample(s, hp, N, R, G, B, w * f, nbins, gamma, maxval);
+        uint32_t np, ni;
+        float nf;
+        splat_row_next(S, F, T, rc0 + br * RW, col, line, best + 1u, np, ni, nf);
+#pragma unroll
+        for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
+            if (q == br) { cpos[q] = np; cidx[q] = ni; cf[q] = nf; }
+    }
+    if (loaded) s.store(st, N, p); // (a pixel without contributions does not touch its planes)
+}
+
+// dynamic LDS: the table (ts * ts), g0[SPLAT_RING_MAX], b0[SPLAT_RING_MAX + 4], then 7 staging arrays of `cap` entries
+__global__ __launch_bounds__(256) void k_accum_splat(const uint2 *__restrict__ cells, const uint32_t *__restrict__ vals, const float *__restrict__ xy,
+                                                     const float *__restrict__ rgb, const float *__restrict__ weights, int W, int H, int tiles_x,
+                                                     SplatFilter F, const float *__restrict__ T, int cap, int nbins, float gamma, float maxval,
+                                                     float *__restrict__ st)
+{
+    extern __shared__ float lds_s[];
+    const int t = threadIdx.x, tt = F.ts * F.ts;
+    float *s_T = lds_s;
+    uint32_t *s_g0 = (uint32_t *)(lds_s + tt), *s_b0 = s_g0 + SPLAT_RING_MAX, *s_pos = s_b0 + SPLAT_RING_MAX + 4;
+    float *s_x = (float *)(s_pos + cap), *s_y = s_x + cap, *s_r = s_y + cap, *s_g = s_r + cap, *s_b = s_g + cap, *s_w = s_b + cap;
+    const int px0 = (int)(blockIdx.x % (unsigned)tiles_x) * SPLAT_TX, py0 = (int)(blockIdx.x / (unsigned)tiles_x) * SPLAT_TY;
+    const int RW = SPLAT_TX + 2 * F.nx, RC = RW * (SPLAT_TY + 2 * F.ny);
+    const int We = W + 2 * F.kx, He = H + 2 * F.ky;
+    for (int e = t; e < tt; e += 256) s_T[e] = T[e];
+    // pixel (col, line) is cell (col + kx, line + ky) of the extended frame
+    for (int rc = t; rc < RC; rc += 256) {
+        const int ex = px0 + F.kx - F.nx + rc % RW, ey = py0 + F.ky - F.ny + rc / RW;
+        uint2 c = make_uint2(0u, 0u);
+        if (ex < We && ey < He) c = cells[(int64_t)ey * We + ex];
+        s_g0[rc] = c.x;
+        s_b0[rc] = c.y - c.x;
+    }
+    __syncthreads();
+    if (t < 64) { // counts -> exclusive scan (one wavefront, `per` consecutive cells per lane)
+        const int per = (RC + 63) / 64, a = t * per;
+        uint32_t sum = 0;
+        for (int k = 0; k < per; ++k)
+            if (a + k < RC) sum += s_b0[a + k];
+        uint32_t incl = sum;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t v = __shfl_up(incl, o);
+            if (t >= o) incl += v;
+        }
+        uint32_t run = incl - sum;
+        for (int k = 0; k < per; ++k)
+            if (a + k < RC) {
+                const uint32_t c = s_b0[a + k];
+                s_b0[a + k] = run;
+                run += c;
+            }
+        if (t == 63) s_b0[RC] = incl;
+    }
+    __syncthreads();
+    const uint32_t total = s_b0[RC];
+    if (total == 0) return;
+    const bool staged = total <= (uint32_t)cap; // (uniform over the workgroup)
+    if (staged) {
+        for (uint32_t j = t; j < total; j += 256) {
+            int lo = 0, hi = RC; // the cell of slot j: the last one with b0 <= j
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_b0[mid] <= j) lo = mid;
+                else hi = mid;
+            }
+            const int64_t e = vals[s_g0[lo] + (j - s_b0[lo])];
+            s_pos[j] = (uint32_t)e;
+            s_x[j] = xy[2 * e]; s_y[j] = xy[2 * e + 1];
+            s_r[j] = rgb[3 * e]; s_g[j] = rgb[3 * e + 1]; s_b[j] = rgb[3 * e + 2];
+            s_w[j] = weights ? weights[e] : 1.f;
+        }
+        __syncthreads();
+    }
+    const int lx = t % SPLAT_TX, ly = t / SPLAT_TX, col = px0 + lx, line = py0 + ly;
+    if (col >= W || line >= H) return;
+    const int64_t N = (int64_t)W * H, p = (int64_t)line * W + col;
+    const int rc0 = ly * RW + lx;
+    if (staged) {
+        const SplatRuns<true> S = { s_g0, s_b0, s_pos, s_x, s_y, s_r, s_g, s_b, s_w, vals, xy, rgb, weights };
+        splat_pixel<true>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
+    } else {
+        const SplatRuns<false> S = { s_g0, s_b0, s_pos, s_x, s_y, s_r, s_g, s_b, s_w, vals, xy, rgb, weights };
+        splat_pixel<false>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
+    }
 }
 
 // (c) snapshot: computeSampleStatistics (SamplesAccumulator.cpp:108-141) of 64 pixels per workgroup into DeepImage layout; the bin planes
@@ -403,6 +655,56 @@ hipError_t bcd_launch_accum_segments(const uint32_t *keys, const uint32_t *vals,
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_accum_segments, dim3(nblk(n, 256)), dim3(256), 0, s, keys, vals, n, N, rgb, weights, nbins, gamma, maxval, st);
+    return hipGetLastError();
+}
+
+// ---- splatted add ---------------------------------------------------------------------------------------------------------------------
+namespace {
+SplatFilter splat_filter(const float *f, const int *g)
+{
+    SplatFilter F;
+    F.rx = f[0]; F.ry = f[1]; F.inv_rx = f[2]; F.inv_ry = f[3];
+    F.ts = g[0]; F.kx = g[1]; F.ky = g[2]; F.nx = g[3]; F.ny = g[4];
+    return F;
+}
+size_t splat_fixed_lds(int ts) { return ((size_t)ts * ts + 2 * SPLAT_RING_MAX + 4) * sizeof(float); }
+} // namespace
+
+// cells of a tile's ring, and the largest number of samples the staging arrays of a workgroup can hold beside a ts x ts table
+int bcd_splat_ring_cells(int nx, int ny) { return (SPLAT_TX + 2 * nx) * (SPLAT_TY + 2 * ny); }
+int bcd_splat_max_staged(int ts) { return (int)((SPLAT_LDS_BYTES - splat_fixed_lds(ts)) / SPLAT_SAMPLE_BYTES); }
+
+// filter: rx, ry, inv_rx, inv_ry; geom: ts, kx, ky, nx, ny (the definition in include/bcd_hip.h); T: the table on the device
+hipError_t bcd_launch_splat_keys(const float *xy, int64_t n, int W, int H, const float *filter, const int *geom, const float *T, uint32_t *keys,
+                                 uint32_t *vals, unsigned long long *dropped, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_accum_splat_keys, dim3(nblk(n, 256)), dim3(256), 0, s, xy, n, W, H, splat_filter(filter, geom), T, keys, vals, dropped);
+    return hipGetLastError();
+}
+
+// cells: (W + 2 kx) * (H + 2 ky) pairs
+hipError_t bcd_launch_splat_cells(const uint32_t *keys, int64_t n, int64_t NE, void *cells, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(cells, 0, (size_t)NE * sizeof(uint2), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_accum_splat_cells, dim3(nblk(n, 256)), dim3(256), 0, s, keys, n, (uint32_t)NE, (uint2 *)cells);
+    return hipGetLastError();
+}
+
+// cap: samples the staging arrays hold (<= bcd_splat_max_staged); a tile whose ring holds more reads the sorted batch from global memory
+hipError_t bcd_launch_splat(const void *cells, const uint32_t *vals, const float *xy, const float *rgb, const float *weights, int W, int H,
+                            const float *filter, const int *geom, const float *T, int cap, int nbins, float gamma, float maxval, float *st,
+                            hipStream_t s)
+{
+    const SplatFilter F = splat_filter(filter, geom);
+    const int tiles_x = (W + SPLAT_TX - 1) / SPLAT_TX;
+    const int64_t tiles = (int64_t)tiles_x * ((H + SPLAT_TY - 1) / SPLAT_TY);
+    cap = std::max(0, std::min(cap, bcd_splat_max_staged(F.ts)));
+    const size_t lds = splat_fixed_lds(F.ts) + (size_t)cap * SPLAT_SAMPLE_BYTES;
+    hipLaunchKernelGGL(k_accum_splat, dim3((unsigned)tiles), dim3(256), lds, s, (const uint2 *)cells, vals, xy, rgb, weights, W, H, tiles_x, F, T,
+                       cap, nbins, gamma, maxval, st);
     return hipGetLastError();
 }
 

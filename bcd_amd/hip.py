@@ -97,6 +97,37 @@ def default_plan_params(**kw):
     return p
 
 
+FILTER_KINDS = {"box": 0, "tent": 1, "gaussian": 2, "blackman_harris": 3}
+
+
+def _radii(radius):
+    rx, ry = (radius, radius) if not hasattr(radius, "__len__") else radius
+    return float(rx), float(ry)
+
+
+def _splat_api():
+    L = lib()
+    L.bcd_hip_accum_set_filter.argtypes = [_VP, C.c_float, C.c_float, C.c_int, _VP]
+    L.bcd_hip_accum_add_splatted.argtypes = [_VP, _VP, _VP, _VP, C.c_int64]
+    L.bcd_hip_filter_table.argtypes = [C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _VP]
+    return L
+
+
+def filter_table(kind, radius, param=2.0, table_size=16):
+    """the (table_size, table_size) float32 table of a standard separable filter (bcd_hip_filter_table: host only, no GPU needed).
+    kind: "box", "tent", "gaussian" (param = alpha) or "blackman_harris"; radius: a number or (radius_x, radius_y), each in (0, 3]"""
+    import numpy as np
+    if kind not in FILTER_KINDS:
+        raise ValueError("unknown filter kind %r (one of %s)" % (kind, ", ".join(sorted(FILTER_KINDS))))
+    rx, ry = _radii(radius)
+    ts = int(table_size)
+    out = np.empty((max(ts, 1), max(ts, 1)), np.float32)
+    rc = _splat_api().bcd_hip_filter_table(FILTER_KINDS[kind], rx, ry, float(param), ts, out.ctypes.data_as(_VP))
+    if rc != 0:
+        raise ValueError("bcd_hip_filter_table(%s, radius (%g, %g), param %g, table_size %d): rc=%d" % (kind, rx, ry, param, ts, rc))
+    return out
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_float, C.c_void_p)
 
 
@@ -119,6 +150,7 @@ SYMBOLS = [
     "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
     "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
     "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_default_plan_params", "bcd_hip_accum_plan", "bcd_hip_zero_bad_values",
+    "bcd_hip_accum_set_filter", "bcd_hip_accum_add_splatted", "bcd_hip_filter_table",
     "bcd_hip_accum_state_info", "bcd_hip_accum_state_bytes", "bcd_hip_accum_export", "bcd_hip_accum_import", "bcd_hip_accum_merge_state", "bcd_hip_accum_merge",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch",
 ]
@@ -482,6 +514,34 @@ class Accumulator:
         assert pixel.dtype == self.ctx.torch.int32 and tuple(rgb.shape) == (n, 3)
         assert weights is None or tuple(weights.shape) == (n,)
         self._chk(lib().bcd_hip_accum_add_scattered(self.h, _dp(pixel), _dp(rgb), _dp(weights) if weights is not None else None, n))
+
+    def set_filter(self, kind_or_table, radius=None, param=2.0, table_size=16):
+        """the pixel reconstruction filter of add_splatted (bcd_hip_accum_set_filter; definition in include/bcd_hip.h).  kind_or_table: a
+        kind of filter_table() ("box", "tent", "gaussian", "blackman_harris"; param = the Gaussian's alpha), a square float32 array of
+        finite values >= 0 (row = y index), or None to remove the filter; radius: a number or (radius_x, radius_y), each in (0, 3].
+        The filter is not part of an exported state."""
+        import numpy as np
+        L = _splat_api()
+        if kind_or_table is None:
+            self._chk(L.bcd_hip_accum_set_filter(self.h, 0.0, 0.0, 0, None))
+            return
+        rx, ry = _radii(radius)
+        if isinstance(kind_or_table, str):
+            table = filter_table(kind_or_table, (rx, ry), param, table_size)
+        else:
+            table = np.ascontiguousarray(kind_or_table, np.float32)
+            if table.ndim != 2 or table.shape[0] != table.shape[1]:
+                raise ValueError("a filter table must be a square 2-D array")
+        self._chk(L.bcd_hip_accum_set_filter(self.h, rx, ry, table.shape[0], table.ctypes.data_as(_VP)))
+
+    def add_splatted(self, xy, rgb, weights=None):
+        """xy: (n, 2) float32 continuous positions (x, y), pixel (col, line) covering [col, col + 1) x [line, line + 1); rgb: (n, 3);
+        weights: (n,) or None.  Every sample goes to the pixels of its filter footprint, each pixel in stream order"""
+        n = xy.shape[0]
+        assert tuple(xy.shape) == (n, 2) and tuple(rgb.shape) == (n, 3) and xy.dtype == self.ctx.torch.float32
+        assert weights is None or tuple(weights.shape) == (n,)
+        self._chk(_splat_api().bcd_hip_accum_add_splatted(self.h, _dp(xy) if n else None, _dp(rgb) if n else None,
+                                                          _dp(weights) if weights is not None and n else None, n))
 
     def statistics(self, out=None):
         """-> (ns (H, W, 1), mean (H, W, 3), cov (H, W, 6), hist (H, W, 3 nbins)), fresh tensors or the four of `out`; state unchanged"""

@@ -1,6 +1,7 @@
 // DeviceSamplesAccumulator.cpp -- bcd::SamplesAccumulator with its running sums in HBM (bcd_hip_accum_*, k_accumulate.hip).
 // addSample appends to a pinned host batch; a full batch (or a snapshot) copies it to the device and applies it through the
 // scattered add, which keeps every pixel's samples in call order.  While the device works on one batch the next one fills.
+// splatSample does the same with continuous positions through the splatted add; a batch holds calls of one kind only.
 #include "DeviceSamplesAccumulator.h"
 #include "bcd_hip.h"
 
@@ -68,6 +69,8 @@ namespace bcd
 		if(m_pDevicePlan) (void)hipFree(m_pDevicePlan);
 		if(m_pHostPixel) (void)hipHostFree(m_pHostPixel);
 		if(m_pHostRgbw) (void)hipHostFree(m_pHostRgbw);
+		if(m_pHostXy) (void)hipHostFree(m_pHostXy);
+		if(m_pDeviceXy) (void)hipFree(m_pDeviceXy);
 		if(m_batchCopied) (void)hipEventDestroy((hipEvent_t)m_batchCopied);
 		if(m_stream) (void)hipStreamDestroy((hipStream_t)m_stream);
 	}
@@ -79,13 +82,8 @@ namespace bcd
 
 	void DeviceSamplesAccumulator::addSample(int i_line, int i_column, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight)
 	{
-		if(!isValid())
+		if(!isValid() || !beginAppend(false))
 			return;
-		if(m_pending == 0 && m_copyInFlight)
-		{	// the previous batch is still being copied out of the pinned buffer
-			(void)hipEventSynchronize((hipEvent_t)m_batchCopied);
-			m_copyInFlight = false;
-		}
 		const int64_t i = m_pending++;
 		m_pHostPixel[i] = (i_line < 0 || i_line >= m_height || i_column < 0 || i_column >= m_width) ? -1 : i_line * m_width + i_column;
 		float* rgb = m_pHostRgbw + 3 * i;
@@ -101,13 +99,105 @@ namespace bcd
 			return;
 		for(int64_t done = 0; done < i_nbOfSamples; )
 		{
-			if(m_pending == 0 && m_copyInFlight)
-			{
+			if(!beginAppend(false))
+				return;
+			const int64_t n = std::min(s_batchCapacity - m_pending, i_nbOfSamples - done);
+			std::memcpy(m_pHostPixel + m_pending, i_pPixelIndices + done, size_t(n) * sizeof(int32_t));
+			std::memcpy(m_pHostRgbw + 3 * m_pending, i_pRgb + 3 * done, size_t(n) * 3 * sizeof(float));
+			float* w = m_pHostRgbw + 3 * s_batchCapacity + m_pending;
+			if(i_pWeights) std::memcpy(w, i_pWeights + done, size_t(n) * sizeof(float));
+			else std::fill(w, w + n, 1.f);
+			m_pending += n;
+			done += n;
+			if(m_pending == s_batchCapacity)
+				flush();
+		}
+	}
+
+	bool DeviceSamplesAccumulator::beginAppend(bool i_splat)
+	{
+		if(m_pending > 0 && m_pendingSplats != i_splat && !flush()) // the kind changes: the pending batch goes first, so that pixels see call order
+			return false;
+		if(m_pending == 0)
+		{
+			if(m_copyInFlight)
+			{	// the previous batch is still being copied out of the pinned buffers
 				(void)hipEventSynchronize((hipEvent_t)m_batchCopied);
 				m_copyInFlight = false;
 			}
+			m_pendingSplats = i_splat;
+		}
+		if(i_splat && !m_pHostXy)
+		{
+			if(hipHostMalloc((void**)&m_pHostXy, size_t(s_batchCapacity) * 2 * sizeof(float), hipHostMallocDefault) != hipSuccess
+					|| hipMalloc(&m_pDeviceXy, size_t(s_batchCapacity) * 2 * sizeof(float)) != hipSuccess)
+			{
+				m_error = "out of device or pinned host memory for the positions";
+				return false;
+			}
+		}
+		return true;
+	}
+
+	bool DeviceSamplesAccumulator::setFilter(float i_radiusX, float i_radiusY, int i_tableSize, const float* i_pTable)
+	{
+		if(!isValid() || !flush())
+			return false;
+		if(bcd_hip_accum_set_filter(m_pAccum, i_radiusX, i_radiusY, i_tableSize, i_pTable) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_set_filter");
+			return false;
+		}
+		m_hasFilter = i_pTable != nullptr;
+		return true;
+	}
+
+	bool DeviceSamplesAccumulator::setFilter(int i_kind, float i_radiusX, float i_radiusY, float i_param, int i_tableSize)
+	{
+		std::vector<float> table(i_tableSize >= 1 && i_tableSize <= 64 ? size_t(i_tableSize) * i_tableSize : 0);
+		if(table.empty() || bcd_hip_filter_table(i_kind, i_radiusX, i_radiusY, i_param, i_tableSize, table.data()) != BCD_HIP_OK)
+		{
+			m_error = "setFilter: invalid filter kind, radii, parameter or table size";
+			return false;
+		}
+		return setFilter(i_radiusX, i_radiusY, i_tableSize, table.data());
+	}
+
+	void DeviceSamplesAccumulator::splatSample(float i_x, float i_y, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight)
+	{
+		if(!isValid())
+			return;
+		if(!m_hasFilter)
+		{
+			m_error = "splatSample: no filter (setFilter)";
+			return;
+		}
+		if(!beginAppend(true))
+			return;
+		const int64_t i = m_pending++;
+		m_pHostXy[2 * i] = i_x; m_pHostXy[2 * i + 1] = i_y;
+		float* rgb = m_pHostRgbw + 3 * i;
+		rgb[0] = i_sampleR; rgb[1] = i_sampleG; rgb[2] = i_sampleB;
+		m_pHostRgbw[3 * s_batchCapacity + i] = i_weight;
+		if(m_pending == s_batchCapacity)
+			flush();
+	}
+
+	void DeviceSamplesAccumulator::splatSamples(const float* i_pPositions, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples)
+	{
+		if(!isValid())
+			return;
+		if(!m_hasFilter)
+		{
+			m_error = "splatSamples: no filter (setFilter)";
+			return;
+		}
+		for(int64_t done = 0; done < i_nbOfSamples; )
+		{
+			if(!beginAppend(true))
+				return;
 			const int64_t n = std::min(s_batchCapacity - m_pending, i_nbOfSamples - done);
-			std::memcpy(m_pHostPixel + m_pending, i_pPixelIndices + done, size_t(n) * sizeof(int32_t));
+			std::memcpy(m_pHostXy + 2 * m_pending, i_pPositions + 2 * done, size_t(n) * 2 * sizeof(float));
 			std::memcpy(m_pHostRgbw + 3 * m_pending, i_pRgb + 3 * done, size_t(n) * 3 * sizeof(float));
 			float* w = m_pHostRgbw + 3 * s_batchCapacity + m_pending;
 			if(i_pWeights) std::memcpy(w, i_pWeights + done, size_t(n) * sizeof(float));
@@ -130,7 +220,9 @@ namespace bcd
 		int32_t* dPix = (int32_t*)m_pDeviceBatch;
 		float* dRgb = (float*)(dPix + cap);
 		float* dW = dRgb + 3 * cap;
-		if(hipMemcpyAsync(dPix, m_pHostPixel, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess
+		const void* hostKeys = m_pendingSplats ? (const void*)m_pHostXy : (const void*)m_pHostPixel;
+		void* deviceKeys = m_pendingSplats ? m_pDeviceXy : (void*)dPix;
+		if(hipMemcpyAsync(deviceKeys, hostKeys, size_t(n) * (m_pendingSplats ? 2 * sizeof(float) : sizeof(int32_t)), hipMemcpyHostToDevice, st) != hipSuccess
 				|| hipMemcpyAsync(dRgb, m_pHostRgbw, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess
 				|| hipMemcpyAsync(dW, m_pHostRgbw + 3 * cap, size_t(n) * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess
 				|| hipEventRecord((hipEvent_t)m_batchCopied, st) != hipSuccess)
@@ -140,6 +232,15 @@ namespace bcd
 		}
 		m_copyInFlight = true;
 		m_pending = 0;
+		if(m_pendingSplats)
+		{
+			if(bcd_hip_accum_add_splatted(m_pAccum, (const float*)m_pDeviceXy, dRgb, dW, n) != BCD_HIP_OK)
+			{
+				fail("bcd_hip_accum_add_splatted");
+				return false;
+			}
+			return true;
+		}
 		if(bcd_hip_accum_add_scattered(m_pAccum, dPix, dRgb, dW, n) != BCD_HIP_OK)
 		{
 			fail("bcd_hip_accum_add_scattered");

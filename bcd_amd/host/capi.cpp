@@ -109,6 +109,33 @@ int bcdcore_device_accumulate(const float* s, long long n, int W, int H, int nbi
 	return 0;
 }
 
+// a stream of mixed calls through bcd::DeviceSamplesAccumulator: n x (kind, a, b, r, g, b, weight); kind 0: addSample(line = a, col = b),
+// kind 1: splatSample(x = a, y = b), with the filter (radii, table[tableSize^2]) set first.  counts[2]: samples accumulated / dropped
+int bcdcore_device_splat(const float* s, long long n, int W, int H, int nbins, float gamma, float maxval, int device, float radiusX, float radiusY,
+		int tableSize, const float* table, float* ns, float* mean, float* cov, float* hist, long long* counts)
+{
+	HistogramParameters hp;
+	hp.m_nbOfBins = nbins; hp.m_gamma = gamma; hp.m_maxValue = maxval;
+	DeviceSamplesAccumulator acc(W, H, hp, device);
+	g_deviceAccumulateError.clear();
+	if(!acc.isValid()) { g_deviceAccumulateError = acc.lastError(); return -1; }
+	if(!acc.setFilter(radiusX, radiusY, tableSize, table)) { g_deviceAccumulateError = acc.lastError(); return -1; }
+	for(long long i = 0; i < n; ++i, s += 7)
+	{
+		if(s[0] != 0.f) acc.splatSample(s[1], s[2], s[3], s[4], s[5], s[6]);
+		else acc.addSample(int(s[1]), int(s[2]), s[3], s[4], s[5], s[6]);
+	}
+	counts[0] = acc.nbOfAccumulatedSamples();
+	counts[1] = acc.nbOfDroppedSamples();
+	SamplesStatisticsImages st = acc.extractSamplesStatistics();
+	if(!acc.lastError().empty()) { g_deviceAccumulateError = acc.lastError(); return -1; }
+	st.m_nbOfSamplesImage.copyDataTo(ns);
+	st.m_meanImage.copyDataTo(mean);
+	st.m_covarImage.copyDataTo(cov);
+	st.m_histoImage.copyDataTo(hist);
+	return 0;
+}
+
 // the same stream through bcd::DeviceSamplesAccumulator::addSample (no explicit flush), then one planSamples; pixels[budget] receives the
 // list, summary[4] planned / active / unsampled / max_error.  invalidFirst: two invalid planSamples come first (a budget of 2^31 while the
 // samples are still buffered, then max_per_pixel 0), and each must return false with a message.  Returns the number of planned samples,

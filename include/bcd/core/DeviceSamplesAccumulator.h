@@ -63,6 +63,20 @@ namespace bcd
 		/// Indices outside the frame are skipped (and counted by nbOfDroppedSamples()).
 		void addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples);
 
+		/// Pixel reconstruction filter of splatSample / splatSamples (bcd_hip_accum_set_filter in bcd_hip.h, which defines the splat exactly):
+		/// radii in (0, 3], a table of i_tableSize x i_tableSize finite values >= 0 (row = y index), i_tableSize in [1, 64]; a null table
+		/// removes the filter.  The samples buffered so far are applied first (splats with the previous filter).  false with lastError()
+		/// for invalid arguments, the previous filter kept.  The filter is not part of a saved state.
+		bool setFilter(float i_radiusX, float i_radiusY, int i_tableSize, const float* i_pTable);
+		/// a standard separable filter (bcd_hip_filter_table): i_kind BCD_HIP_FILTER_BOX, _TENT, _GAUSSIAN (i_param = alpha), _BLACKMAN_HARRIS
+		bool setFilter(int i_kind, float i_radiusX, float i_radiusY, float i_param = 2.f, int i_tableSize = 16);
+		/// a sample at the continuous position (i_x, i_y) -- pixel (column, line) covers [column, column + 1) x [line, line + 1) -- given to
+		/// every pixel of its filter footprint with weight i_weight * filter value.  Buffered like addSample; calls of addSample and
+		/// splatSample may interleave, every pixel still sees call order.  Without a filter the sample is refused (lastError()).
+		void splatSample(float i_x, float i_y, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight = 1.f);
+		/// n samples from host memory, in order: positions [n][2] (x, y), rgb [n][3], weights [n] or nullptr (all 1)
+		void splatSamples(const float* i_pPositions, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples);
+
 		/// copy of the statistics accumulated so far (the accumulator goes on)
 		SamplesStatisticsImages getSamplesStatistics() const;
 		/// moves the statistics out; the accumulator must not be used afterwards
@@ -113,6 +127,13 @@ namespace bcd
 		// host-side batch of addSample calls (pinned), and its device copy
 		static const int64_t s_batchCapacity = int64_t(1) << 20;
 		mutable int64_t m_pending = 0;
+		bool m_pendingSplats = false;   // the pending batch holds splatSample calls (positions in m_pHostXy), not addSample calls
+		bool m_hasFilter = false;
+		float* m_pHostXy = nullptr;     // positions [capacity][2] (pinned) and their device copy, allocated by the first splat
+		void* m_pDeviceXy = nullptr;
+		/// the batch buffers of the kind about to be appended to are free: flushes a pending batch of the other kind, waits for the copy
+		/// of the previous batch
+		bool beginAppend(bool i_splat);
 		int32_t* m_pHostPixel = nullptr;
 		float* m_pHostRgbw = nullptr; // rgb [capacity][3] then weights [capacity]
 		void* m_pDeviceBatch = nullptr;

@@ -352,6 +352,45 @@ int  bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const f
 int  bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n);
 int  bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist);
 int  bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped);
+/* Splatting through a pixel reconstruction filter: samples at continuous positions go to every pixel of their
+ * filter footprint, each with its own filter weight, by the rules of the accumulator: no float atomics, every pixel's contributions
+ * applied by one thread in stream order, nSamples / mean / covariance bit-identical to bcd::SamplesAccumulator fed the expanded stream.
+ * Definition (all arithmetic float32, no contraction, nothing but the operations written here):
+ *   Geometry: pixel (col, line) covers [col, col + 1) x [line, line + 1), its centre is (col + 0.5, line + 0.5).  A sample has a position
+ *     (x, y) in these units, a colour and a weight w (1 when no weights are given).
+ *   Filter: an accumulator has at most one: radii rx, ry in (0, 3], a table size TS in [1, 64], a table T[TS][TS] of finite, non-negative
+ *     floats (row = y index); inv_rx = 1.f / rx, inv_ry = 1.f / ry, Kx = (int)ceilf(rx + 0.5f), Ky likewise (at most 4).
+ *   Footprint: c0 = (int)floorf(x), l0 = (int)floorf(y); candidates col = c0 - Kx .. c0 + Kx, line = l0 - Ky .. l0 + Ky.  With
+ *     dx = fabsf(((float)col + 0.5f) - x), dy likewise, a candidate belongs to the footprint iff dx < rx && dy < ry, it lies in the frame,
+ *     and f = T[iy * TS + ix] != 0 with ix = min((int)(dx * inv_rx * (float)TS), TS - 1) (product evaluated left to right), iy likewise.
+ *     Its contribution is addSample(line, col, r, g, b, w * f): one float multiplication for the weight.
+ *   Order: a pixel receives its contributions in stream order of the samples (batch after batch, inside a batch in the order given; a
+ *     sample contributes to a pixel at most once).  The host restatement: for each sample in order, for line ascending, for col
+ *     ascending, addSample.
+ *   Counters: a sample whose position is not finite, which lies outside [-Kx, W + Kx) x [-Ky, H + Ky), or whose footprint is empty
+ *     contributes nothing and counts as dropped; every other sample adds 1 to samples_added (samples, not contributions).  A sample
+ *     just outside the frame whose footprint reaches into it does contribute.
+ *   set_filter: copies the table (h_table[table_size * table_size], host memory); ordered on the stream after the adds already enqueued.
+ *           h_table == NULL removes the filter.  EINVAL, the previous filter kept, for radii outside (0, 3], a table size outside [1, 64]
+ *           and negative, NaN or infinite entries.  Filters with negative lobes (Mitchell, Lanczos) are refused on purpose: negative weights
+ *           give negative histogram bins, which the similarity kernels' guards send to the slow exact path.  The filter is not part of a
+ *           serialised state: a resumed render sets its filter again.
+ *   add_splatted: d_xy[n][2] (x, y), d_rgb[n][3], d_weights[n] or NULL.  EINVAL without a filter, for null pointers or n < 0; n == 0 is a
+ *           no-op.  Batches above max_batch_samples are applied in chunks in order (a denser chunk than the kernel's staging holds is split
+ *           further; no bit depends on it).  Enqueued on the context's stream, no synchronisation.  The running sums, the state format,
+ *           export / import / merge, plan and the snapshot are those of the other adds: a splat is another way of adding to the same sums.
+ *   filter_table: host only, no device: the separable table of a standard filter into h_out[table_size * table_size]; the 1-D factors
+ *           are evaluated at d = (i + 0.5) / table_size * radius in double, multiplied in double and rounded to float once.  BOX: 1;
+ *           TENT: 1 - d / r; GAUSSIAN: exp(-param d^2) - exp(-param r^2), param = alpha >= 0; BLACKMAN_HARRIS: the 4-term window
+ *           0.35875 - 0.48829 cos(2 pi u) + 0.14128 cos(4 pi u) - 0.01168 cos(6 pi u) at u = (d + r) / (2 r); each clamped at 0.
+ *           EINVAL for an unknown kind, radii outside (0, 3], a table size outside [1, 64], a null output or a bad alpha. */
+#define BCD_HIP_FILTER_BOX 0
+#define BCD_HIP_FILTER_TENT 1
+#define BCD_HIP_FILTER_GAUSSIAN 2
+#define BCD_HIP_FILTER_BLACKMAN_HARRIS 3
+int  bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y, int table_size, const float *h_table);
+int  bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n);
+int  bcd_hip_filter_table(int kind, float radius_x, float radius_y, float param, int table_size, float *h_out);
 /* Adaptive sample planning on the accumulator's state: where the next `budget` samples go, decided on the device
  * from the noise model the denoiser uses (cov / n), with no host copy and no float atomics; reproducible bit for bit.  Per pixel, from
  * the snapshot's statistics (ns, mean m, covariance c, float32, IEEE division and sqrtf):
