@@ -41,6 +41,7 @@ void bcd_sparse_frame_begin(BcdSparseUploader *);
 void bcd_sparse_frame_bytes(const BcdSparseUploader *, long long *, long long *);
 hipError_t bcd_sparse_upload(BcdSparseUploader *, float *, const float *, size_t, hipStream_t);
 void bcd_bayes27_set_strict_eigensolver(int on);
+float bcd_bayes27_conv2(int strict);
 hipError_t bcd_launch_pairdist_rw_counting(const float *, const float *, int, int, int, int, void *, uint8_t *, int *, float, unsigned long long *, hipStream_t);
 hipError_t bcd_launch_spike_rows(const float *, const float *, const float *, const float *, int, int, int, float, float *, float *, float *, float *, int, int,
                                  hipStream_t);
@@ -1593,6 +1594,15 @@ int bcd_hip_bayes_accumulate(bcd_hip_ctx *ctx, const float *d_colors, const floa
     return bayes(ctx, ctx->main, d_colors, d_pixcov, d_mask, d_nsim, d_state, W, H, w, b, min_eig, d_sum, d_count);
 }
 
+int bcd_hip_bayes_last_redo_count(bcd_hip_ctx *ctx, int32_t *count)
+{
+    if (!ctx || !count) return bad(ctx, "bad argument");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream)); // (the counter's copy is the last thing bayes() enqueues)
+    *count = ctx->main.h_counters[23];
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_bayes_accumulate_rows(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixcov, const uint32_t *d_mask,
                                   const int32_t *d_nsim, const uint8_t *d_state, int W, int H, int w, int b, float min_eig,
                                   float *d_sum, int32_t *d_count, int row_begin, int row_end, const int64_t *d_skip_if, const int64_t *h_skip_if, int *skipped)
@@ -2448,6 +2458,11 @@ int bcd_hip_selftest_approx_distance(bcd_hip_ctx *ctx, const float *d_hist, cons
 
 int bcd_hip_eig27_batch(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms)
 {
+    return bcd_hip_eig27_batch_rule(ctx, d_A, n, d_eig, d_V, ms, 0);
+}
+
+int bcd_hip_eig27_batch_rule(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms, int production_rule)
+{
     if (!ctx || !d_A || !d_eig || !d_V || n <= 0) return bad(ctx, "bad argument");
     DEVICE_GUARD(ctx);
     touch(ctx->main);
@@ -2457,7 +2472,7 @@ int bcd_hip_eig27_batch(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig,
     int32_t *d_c = (int32_t *)wk.work_q.p; // work queues
     HIPCHK(ctx, hipMemsetAsync(d_c, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
     HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
-    HIPCHK(ctx, bcd_launch_jacobi27_batch(d_A, n, d_c, std::min(ctx->num_cus * 12, (n + 1) / 2), d_eig, d_V, wk.stream));
+    HIPCHK(ctx, bcd_launch_jacobi27_batch(d_A, n, d_c, std::min(ctx->num_cus * 12, (n + 1) / 2), d_eig, d_V, wk.stream, bcd_bayes27_conv2(production_rule ? 0 : 1)));
     HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     if (ms) *ms = stage_ms(wk, 0, 1);

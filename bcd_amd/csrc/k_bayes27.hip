@@ -78,6 +78,12 @@ __device__ inline float wsum(float v)
     return v;
 }
 
+__device__ inline float wmax(float v)
+{
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+
 // Work distribution of the persistent kernels.  One counter serves 50-90 same-address atomics per microsecond: with a single counter per
 // kernel the 36 000 grabs of a 1080p scale were 0.4 ms (finish kernel with its body skipped) to 0.7 ms (prepare kernel) on their own.
 // Items are dealt round-robin to BCD_WORK_QUEUES counters in cache lines of their own (item = queue + 8 k); a wavefront starts on
@@ -683,6 +689,24 @@ __device__ inline bool sweep_regs(v16f &acc, int idx, int h, float min_eig)
     // of the OTHER half, which would feed zeros: A = -2 delta_ik, B = delta_jk.)
     const float half0 = h == 0 ? 1.f : 0.f, half1 = 1.f - half0;
     const float sgn0 = h == 0 ? -1.f : 1.f, sgn1 = -sgn0; // feeding half: u = m - e_k; other half: + e_k
+    // The rank-1 form of a pivot step evaluates N_rk = m_rk - m_rk (d - 1) / d and N_kk = d - (d - 1)^2 / d - 2: for a pivot d > 1 these are
+    // cancellations that lose log2(d) bits -- the inverse of a matrix with elements around 300 (radiances around 30) was wrong by 1e-4, around 1e6
+    // by more than its size, while every d <= 1 is harmless (the terms then have one sign).  The pivots of a positive definite matrix never exceed its
+    // largest element, so a matrix with an element above 1 is swept in units in which that element lies in [1/2, 1): s is a power of two, the products
+    // are exact, -(s M)^-1 * s = -(M^-1), and ||M^-1||_F = s ||(s M)^-1||_F in the acceptance test.  Matrices within [-1, 1] -- every frame with radiances
+    // of the order of 1 -- take no part in this: s = 1, the same bits as before.  (s is wave-uniform: a scalar register.)
+    float mx = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fabsf(acc[e]));
+    mx = wmax(mx);
+    float s = 1.f;
+    if (__builtin_amdgcn_readfirstlane(__float_as_int(mx)) > 0x3f800000 && mx < 1e37f) {
+        int ex;
+        (void)frexpf(mx, &ex);
+        s = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ldexpf(1.f, -ex))));
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] *= s;
+    }
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -702,7 +726,11 @@ __device__ inline bool sweep_regs(v16f &acc, int idx, int h, float min_eig)
 #pragma unroll
     for (int e = 0; e < 16; ++e) fro = fmaf(acc[e], acc[e], fro);
     fro = wsum(fro);
-    return ok && isfinite(fro) && sqrtf(fro) * min_eig <= 1.f;
+    if (s != 1.f) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] *= s;
+    }
+    return ok && isfinite(fro) && sqrtf(fro) * s * min_eig <= 1.f;
 }
 
 __device__ bool sweep_inverse27(float *M, int lane, float min_eig)
@@ -1061,6 +1089,17 @@ __device__ __attribute__((noinline)) void final_pass27(const float *Cm, float *c
 //   PHASE 2  k_bayes27<2>  reads C, N, m, eigenvalues and eigenvectors; clamp, inverses, Step 2, final estimate, aggregation.
 // Splitting costs ~20 KB of HBM traffic per pixel (nothing next to the ~300 us a pixel takes) and buys a solver that is not
 // tied to the LDS footprint and register pressure of the other phases (12 -> 24 matrices per CU, shared rotations).
+// A non-finite entry of the noise mean makes the whole estimate of the item NaN in the reference: its eigensolver turns C - N with one NaN (or
+// inf: the matrix is scaled by its largest element first) into NaNs throughout, and every later product inherits them.  Here the NaN would stay in the
+// rows and columns of its 3 x 3 block -- the solver skips a rotation whose angle is not a number, V stays finite -- and max(0, NaN) = 0 and
+// max(min_eig, NaN) = min_eig launder the rest: part of the item's output came out finite.  The prepare kernels therefore record a NaN colour mean for
+// such an item: xhat = (m - F m) + F x is then NaN in every component in both finish kernels, the way a non-finite COLOUR already reaches every
+// component through m.  (wave-uniform; the noise mean is in LDS at this point)
+__device__ inline bool noise_poisons_item(const float *noise, int lane)
+{
+    return __builtin_amdgcn_ballot_w64(lane < P * 6 && !isfinite(noise[lane])) != 0;
+}
+
 struct Records27 {
     float *A, *V, *C, *aux, *eig; // [items][784], [items][784], [items][784], [items][AUX27], [items][28]
 };
@@ -1132,8 +1171,9 @@ __global__ __launch_bounds__(64) void k_bayes27(const float *__restrict__ colors
     // product fused; A and B operands are the same centred value, so the result is bitwise symmetric).
     // Operand layout: lane l holds element i = l & 31 of member 2s + (l >> 5); rows/columns 27..31 are zero.
     covariance27(recA, recC, chunk, mean, noise, colors, mem, p, g.b, n, W, lane);
+    const bool poisoned = noise_poisons_item(noise, lane); // (all 64 lanes take part)
     if (lane < P * 6) recX[lane] = noise[lane];
-    if (lane < K) recX[P * 6 + lane] = mean[lane];
+    if (lane < K) recX[P * 6 + lane] = poisoned ? __builtin_nanf("") : mean[lane];
     __syncthreads(); // the next item reuses the LDS
   } else {
     // ---- state of PHASE 1 and the eigen-decomposition
@@ -1522,8 +1562,9 @@ __device__ __attribute__((noinline)) void win_write_records(float *__restrict__ 
         const float *src = tile + r * LD + 4 * q; // (rows of the tile are 29 floats apart: four 4-byte reads)
         reinterpret_cast<float4 *>(recA)[e] = make_float4(src[0], src[1], src[2], src[3]);
     }
+    const bool poisoned = noise_poisons_item(noise, lane); // (all 64 lanes take part)
     if (lane < P * 6) recX[lane] = noise[lane];
-    if (lane < K) recX[P * 6 + lane] = mean[lane];
+    if (lane < K) recX[P * 6 + lane] = poisoned ? __builtin_nanf("") : mean[lane];
 }
 
 template <int PHASE, int B = WB>
@@ -1987,6 +2028,9 @@ static float jacobi_conv2()
     if (v < 0) { const char *e = getenv("BCD_HIP_STRICT_EIGEN"); v = (e && e[0] == '1') ? 1 : 0; g_strict_eigen.store(v); }
     return v ? JACOBI_CONV2_STRICT : JACOBI_CONV2_CORRECTED;
 }
+
+// the two rules by name, for the stand-alone eigensolver entry point (bcd_hip_eig27_batch_rule)
+float bcd_bayes27_conv2(int strict) { return strict ? JACOBI_CONV2_STRICT : JACOBI_CONV2_CORRECTED; }
 
 // Full estimate of items [first_item, first_item + nb_items) of `list`: three launches; `records` holds nb_items records
 // (bcd_bayes27_record_bytes() each), d_work BCD_WORK_INTS zeroed ints (the work queues of the three kernels).

@@ -147,12 +147,12 @@ SYMBOLS = [
     "bcd_hip_multi_unique_id", "bcd_hip_multi_rccl_info", "bcd_hip_multi_create_rank", "bcd_hip_multi_rank_configure", "bcd_hip_multi_rank_upload", "bcd_hip_multi_rank_step",
     "bcd_hip_multi_rank_download", "bcd_hip_multi_rank_renew_ids", "bcd_hip_multi_set_loopback", "bcd_hip_multi_selftest_transport",
     "bcd_hip_scale_begin", "bcd_hip_pixel_cov", "bcd_hip_similarity_masks", "bcd_hip_similarity_masks_deferred", "bcd_hip_similarity_masks_verdict", "bcd_hip_similarity_masks_exact", "bcd_hip_window_distances", "bcd_hip_active_set", "bcd_hip_active_init", "bcd_hip_active_step", "bcd_hip_active_step_enqueue", "bcd_hip_active_step_collect",
-    "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
+    "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_bayes_last_redo_count", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
     "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
     "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_default_plan_params", "bcd_hip_accum_plan", "bcd_hip_zero_bad_values",
     "bcd_hip_accum_set_filter", "bcd_hip_accum_add_splatted", "bcd_hip_filter_table",
     "bcd_hip_accum_state_info", "bcd_hip_accum_state_bytes", "bcd_hip_accum_export", "bcd_hip_accum_import", "bcd_hip_accum_merge_state", "bcd_hip_accum_merge",
-    "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch",
+    "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch", "bcd_hip_eig27_batch_rule",
 ]
 
 _lib = None
@@ -338,6 +338,12 @@ class Context:
                                                  C.c_float(min_eig), _dp(s), _dp(c)))
         return s, c
 
+    def bayes_last_redo_count(self):
+        """items of the last bayes_accumulate call (patch radius 1) whose inverse took the spectral branch through the redo list"""
+        n = C.c_int32(0)
+        self._chk(lib().bcd_hip_bayes_last_redo_count(self.h, C.byref(n)))
+        return n.value
+
     def finalize(self, s, c):
         out = self.torch.empty_like(s)
         self._chk(lib().bcd_hip_finalize(self.h, _dp(s), _dp(c), C.c_int64(c.numel()), _dp(out)))
@@ -462,14 +468,15 @@ class Context:
         self._chk(lib().bcd_hip_selftest_bin_work(self.h, _dp(hist), _dp(ns), W, H, D, int(b), int(reps), C.byref(a), C.byref(b_), C.byref(c), C.byref(ms)))
         return a.value, b_.value, c.value, ms.value
 
-    def eig27_batch(self, A):
-        """A: (n, 28, 28) symmetric device tensor (row / column 27 zero) -> (eigenvalues (n, 28), eigenvectors (n, 28, 28), kernel ms)"""
+    def eig27_batch(self, A, production_rule=False):
+        """A: (n, 28, 28) symmetric device tensor (row / column 27 zero) -> (eigenvalues (n, 28), eigenvectors (n, 28, 28), kernel ms);
+        production_rule: stop at 2e-9 like the estimate chain (no first-order correction) instead of the strict 1e-12"""
         torch = self.torch
         n = A.shape[0]
         eig = torch.zeros((n, 28), dtype=torch.float32, device=A.device)
         V = torch.zeros((n, 28, 28), dtype=torch.float32, device=A.device)
         ms = C.c_float(0)
-        self._chk(lib().bcd_hip_eig27_batch(self.h, _dp(A), n, _dp(eig), _dp(V), C.byref(ms)))
+        self._chk(lib().bcd_hip_eig27_batch_rule(self.h, _dp(A), n, _dp(eig), _dp(V), C.byref(ms), 1 if production_rule else 0))
         return eig, V, ms.value
 
     def selftest_division(self, samples, seed=1):

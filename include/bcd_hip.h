@@ -297,6 +297,10 @@ int bcd_hip_bayes_accumulate(bcd_hip_ctx *ctx, const float *d_colors, const floa
                              const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state,
                              int W, int H, int patch_radius, int search_radius, float min_eigen_value,
                              float *d_sum, int32_t *d_count);
+/* Items of the last bcd_hip_bayes_accumulate[_rows] call on this context (patch radius 1) that the register-resident finish kernel handed to the redo
+ * list because the sweep inverse failed its checks (the spectral branch of inverseSymmetricMatrix, DenoisingUnit.cpp:578-604).  Read-only; waits for
+ * the context's stream.  What bcd_hip_get_stats reports as spectral_inverses after bcd_hip_denoise, for a stage-level call. */
+int bcd_hip_bayes_last_redo_count(bcd_hip_ctx *ctx, int32_t *count);
 /* The same for the processed pixels of lines [row_begin, row_end) only (a row band's owned lines), optionally SPECULATIVE (round 6; patch radius 1):
  * d_skip_if points at a device word that the work already enqueued on the context's stream leaves at zero when this estimate is wanted (the band
  * driver: the all-reduced count of undecided pixels of the marking batch just enqueued), h_skip_if at the host copy of that word, copied on the same
@@ -497,6 +501,10 @@ int bcd_hip_selftest_approx_distance(bcd_hip_ctx *ctx, const float *d_hist, cons
  * d_A = n symmetric matrices, 28 x 28 floats each, row-major, row / column 27 zero; d_eig[n][28] = eigenvalues (unordered, entry 27 = 0),
  * d_V[n][28][28] = eigenvectors in columns, same order (rows 0..26 written); *ms = kernel time (may be NULL).  Parity / timing aid. */
 int bcd_hip_eig27_batch(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms);
+/* bcd_hip_eig27_batch always stops at off^2 <= 1e-12 diag^2 (the strict rule; bcd_hip_set_strict_eigensolver does not reach it).  This one selects:
+ * production_rule != 0 stops where the estimate chain stops by default, off^2 <= 2e-9 diag^2 -- WITHOUT the first-order correction the finish kernels
+ * apply to the residual (it is not returned), so V diag(eig) V^T is then only accurate to sqrt(2e-9) |A|_F; 0 is bcd_hip_eig27_batch. */
+int bcd_hip_eig27_batch_rule(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms, int production_rule);
 
 /* ---- host utilities (no device work) ----------------------------------------------------------- */
 /* the visiting order implied by (random_order, seed): main-pixel linear indices line*W+col in

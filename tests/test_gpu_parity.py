@@ -25,6 +25,18 @@ def rel_linf(a, b):
     return v
 
 
+def rel_local(a, b):
+    """max |a - b| relative to the largest |b| of the pixel's 15 x 15 neighbourhood (tests/bayes_ref.py): the error rel_linf cannot see in the dark
+    parts of a frame with spikes.  REPORTED through BCD_TEST_REPORT for the full-size frames, not asserted yet: the first numbers belong in the log."""
+    if not os.environ.get("BCD_TEST_REPORT"):
+        return None
+    import bayes_ref
+    v = bayes_ref.rel_local(a, b)
+    with open(os.environ["BCD_TEST_REPORT"], "a") as f:
+        f.write("%s rel_local %.3e\n" % (os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0], v))
+    return v
+
+
 def bits_equal(a, b):
     a = np.ascontiguousarray(a, np.float32).view(np.uint32)
     b = np.ascontiguousarray(b, np.float32).view(np.uint32)
@@ -646,6 +658,7 @@ def test_720p_three_scale_frame_against_the_oracle(hipctx):
     want = ol.denoise_multiscale(col, ns, hist, cov, 3, ol.params(m=0.0, threads=threads))
     ok = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), ok)
+    rel_local(np.where(ok, got, 0), np.where(ok, want, 0))
     assert rel_linf(np.where(ok, got, 0), np.where(ok, want, 0)) < TOL_FULL_SIZE
 
 
@@ -665,6 +678,7 @@ def test_1080p_headline_frame_against_the_oracle(hipctx):
     want = ol.denoise_multiscale(col, ns, hist, cov, 3, ol.params(m=0.0, threads=threads))
     ok = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), ok)
+    rel_local(np.where(ok, got, 0), np.where(ok, want, 0))
     assert rel_linf(np.where(ok, got, 0), np.where(ok, want, 0)) < TOL_FULL_SIZE
 
 
@@ -685,6 +699,7 @@ def test_1080p_bench_workload_against_the_oracle(hipctx):
     want = ol.denoise_multiscale(col, ns, hist, cov, S, ol.params(m=1.0, skip_seed=1234, threads=threads), orders=_orders(W, H, 1, 1, 1234, S))
     ok = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), ok)
+    rel_local(np.where(ok, got, 0), np.where(ok, want, 0))
     assert rel_linf(np.where(ok, got, 0), np.where(ok, want, 0)) < TOL_FULL_SIZE
 
 
@@ -709,6 +724,7 @@ def _nonuniform_full_size_check(hipctx, W, H, frame, seed, expect_paths):
     want = ol.denoise_multiscale(col, ns, hist, cov, S, ol.params(m=1.0, skip_seed=seed, threads=threads), orders=_orders(W, H, 1, 1, seed, S))
     ok = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), ok)
+    rel_local(np.where(ok, got, 0), np.where(ok, want, 0))
     assert rel_linf(np.where(ok, got, 0), np.where(ok, want, 0)) < TOL_FULL_SIZE
     return paths
 
@@ -752,6 +768,7 @@ def test_4k_config3_frame_against_the_oracle(hipctx):
     want = ol.denoise_multiscale(col, ns, hist, cov, S, ol.params(m=1.0, skip_seed=17, threads=threads), orders=_orders(W, H, 1, 1, 17, S))
     ok = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), ok)
+    rel_local(np.where(ok, got, 0), np.where(ok, want, 0))
     assert rel_linf(np.where(ok, got, 0), np.where(ok, want, 0)) < TOL_FULL_SIZE
 
 
@@ -771,6 +788,7 @@ def test_4k_config4_frame_against_the_oracle(hipctx):
     want = ol.denoise_multiscale(fc, fn, fh, fv, S, ol.params(b=b, m=1.0, skip_seed=23, threads=threads), orders=_orders(W, H, 1, 1, 23, S))
     ok = np.isfinite(want)
     assert np.array_equal(np.isfinite(got), ok)
+    rel_local(np.where(ok, got, 0), np.where(ok, want, 0))
     assert rel_linf(np.where(ok, got, 0), np.where(ok, want, 0)) < TOL_FULL_SIZE
 
 
@@ -1069,6 +1087,128 @@ def test_batched_eigensolver_against_lapack(hipctx):
         assert np.linalg.norm((Vi * eig[i, :27]) @ Vi.T - a) / nrm < 1e-5, i
         assert np.linalg.norm(Vi.T @ Vi - np.eye(27)) < 1e-5, i
         assert np.max(np.abs(np.sort(eig[i, :27]) - np.linalg.eigvalsh(a))) / nrm < 1e-5, i
+
+
+def _hard_spectra():
+    """27 x 27 float32 matrices where an eigensolver goes wrong without the frame noticing: (name, matrix) pairs, each also scaled by 2^20 and 2^-20"""
+    import bayes_cases as bc
+    import bayes_ref as br
+    rng = np.random.default_rng(9)
+    q = lambda: np.linalg.qr(rng.standard_normal((27, 27)))[0]
+    sym = lambda lam, Q: (Q * lam) @ Q.T
+    base = []
+    for i in range(4):
+        base.append(("graded 1 .. 1e-8", sym(np.logspace(0, -8, 27), q())))
+        base.append(("graded, both signs", sym(np.logspace(0, -8, 27) * np.where(rng.random(27) < 0.5, -1.0, 1.0), q())))
+    base.append(("27 equal", sym(np.full(27, 0.37), q())))
+    base.append(("27 equal, exactly", 0.37 * np.eye(27)))
+    for i in range(3):
+        base.append(("two clusters 1e-6 apart", sym(np.where(np.arange(27) < 13, 1.0, 1.0 + 1e-6), q())))
+        base.append(("two clusters 1e-6 apart around 0", sym(np.where(np.arange(27) < 13, -5e-7, 5e-7), q()) + 0.0))
+        X = rng.standard_normal((40, 27))
+        base.append(("negative definite", -(X.T @ X / 39 + 0.01 * np.eye(27))))
+    base.append(("zero", np.zeros((27, 27))))
+    for fam, pick in (("pure noise", 0), ("low rank", 0), ("low rank", 1), ("low rank", 2)):   # C - N of the constructed families
+        case = bc.FAMILIES[fam]()[pick]
+        _, _, items = br.accumulate(*case.args())
+        base += [("C - N: " + case.name, it["cov1_minus_noise"]) for it in items[:6]]
+    out = []
+    for name, A in base:
+        A = ((A + A.T) / 2).astype(np.float32)
+        out += [(name, A), (name + " x 2^20", A * np.float32(2.0 ** 20)), (name + " x 2^-20", A * np.float32(2.0 ** -20))]
+    return out
+
+
+_EIG_CLASSES = ("graded 1 .. 1e-8", "graded, both signs", "27 equal", "27 equal, exactly", "two clusters 1e-6 apart", "two clusters 1e-6 apart around 0",
+                "negative definite", "zero", "C - N: pure noise", "C - N: low rank: zero channel", "C - N: low rank: 10 patches x 4", "C - N: low rank: grey")
+
+# Class x quantity x rule that miss the bar below on the MI355X, in units of u |A|_2 (docs/EXPERIMENTS.md section 6 has every figure).  Each is a strict
+# expected failure of ITS OWN case; every other class, quantity and rule is asserted.
+#   Eigenvalues.  The solver rotates every diagonal element about 150 times (26 rotations a sweep, 5 to 6 sweeps), each rotation rounding it by about
+#   u times the norm of its row: the error of an eigenvalue is a random walk of about sqrt(150) u |row| = 12 u |row|, measured 18 ... 26 u |A|_2 at worst
+#   over a matrix -- LAPACK tridiagonalises with 26 reflections and is at 3 ... 7 u.  In a graded or covariance-like spectrum only a few rows have the
+#   size of |A|_2, and the maximum over those few stays under the floor of 27 u.  In "two clusters around 0" all 27 eigenvalues are +-|A|_2 (A = c (2 P - I)):
+#   27 full-size random walks instead of a few, and their maximum is 47 u (strict) / 40 u (production).
+#   Positive part, strict rule.  V max(0, L) V^T adds V's distance from an orthogonal matrix (the same 150 rotations per column, |V^T V - I| about 20 u)
+#   to the eigenvalue error, which alone nearly fills the floor: 28 ... 83 u wherever positive eigenvalues of the size of |A|_2 exist.
+_EIG_MISSES = {("strict", "eigenvalues", "two clusters 1e-6 apart around 0"): "47 u against max(4 x ssyev, 27 u): 27 eigenvalues of full size, see above",
+               ("production", "eigenvalues", "two clusters 1e-6 apart around 0"): "40 u against max(4 x ssyev, 27 u): 27 eigenvalues of full size, see above"}
+_EIG_MISSES.update({("strict", "positive part", c): "%s u against max(4 x ssyev, 27 u): eigenvalue error + V's orthogonality error, see above" % v for c, v in
+                    (("graded 1 .. 1e-8", "31"), ("graded, both signs", "53"), ("two clusters 1e-6 apart around 0", "83"), ("C - N: pure noise", "29"),
+                     ("C - N: low rank: zero channel", "28"), ("C - N: low rank: 10 patches x 4", "48"), ("C - N: low rank: grey", "32"))})
+
+_eig_cache = {}
+
+
+def _eig_measure(hipctx, rule):
+    """-> {class: [(description, eigenvalue error, its bar, positive-part error, its bar), ...]} over batches of 1, 2, 3 and 2 (#CUs) 12 + 1 matrices (one more
+    than the persistent grid of two-matrix wavefronts takes in a round); the copies of a matrix in the large batch must give the same bits"""
+    if rule in _eig_cache:
+        return _eig_cache[rule]
+    import torch
+    u = 2.0 ** -24
+    mats = _hard_spectra()
+    big = 2 * torch.cuda.get_device_properties(0).multi_processor_count * 12 + 1
+    out = {c: [] for c in _EIG_CLASSES}
+    for n in (1, 2, 3, big):
+        sel = [mats[(i * 7 + n) % len(mats)] for i in range(n)] if n <= 3 else [mats[i % len(mats)] for i in range(n)]
+        A = np.zeros((n, 28, 28), np.float32)
+        for i, (_, a) in enumerate(sel):
+            A[i, :27, :27] = a
+        eig, V, _ = hipctx.eig27_batch(torch.from_numpy(A).cuda(), production_rule=(rule == "production"))
+        eig, V = eig.cpu().numpy().astype(np.float64), V.cpu().numpy().astype(np.float64)
+        assert np.all(eig[:, 27] == 0)
+        for i, (name, a32) in enumerate(sel):
+            if n > 3 and i >= len(mats) and i < n - 1:
+                assert np.array_equal(eig[i], eig[i % len(mats)]) and np.array_equal(V[i], V[i % len(mats)]), (n, i, name)   # a slot, partner or round must not matter
+                continue
+            a = a32.astype(np.float64)
+            l64, v64 = np.linalg.eigh(a)
+            l32, v32 = np.linalg.eigh(a32)
+            n2, nf = float(np.max(np.abs(l64))), float(np.linalg.norm(a))
+            first_order = np.sqrt(2e-9) * nf if rule == "production" else 0.0
+            cal = float(np.max(np.abs(l32.astype(np.float64) - l64)))
+            err = float(np.max(np.abs(np.sort(eig[i, :27]) - l64)))
+            pos64 = (v64 * np.maximum(l64, 0.0)) @ v64.T
+            pos32 = ((v32 * np.maximum(l32, np.float32(0))) @ v32.T).astype(np.float64)
+            Vi = V[i, :27, :27]
+            pos = (Vi * np.maximum(eig[i, :27], 0.0)) @ Vi.T
+            cal_p = float(np.linalg.norm(pos32 - pos64, 2))
+            err_p = float(np.linalg.norm(pos - pos64, 2))
+            out[name.split(" x 2^")[0]].append(("%s, batch of %d, matrix %d, |A|_2 %.3e" % (name, n, i, n2), err, max(4 * cal, 27 * u * n2),
+                                                err_p, max(4 * cal_p, 27 * u * n2) + first_order))
+    _eig_cache[rule] = out
+    if os.environ.get("BCD_TEST_REPORT"):
+        with open(os.environ["BCD_TEST_REPORT"], "a") as f:
+            for c, rows in out.items():
+                f.write("eig27 %-10s %-36s %3d matrices; worst error / bar: eigenvalues %.2f, positive part %.2f\n" % (
+                    rule, c, len(rows), max(e / b_ if b_ else 0.0 for (_, e, b_, _, _) in rows), max(e / b_ if b_ else 0.0 for (_, _, _, e, b_) in rows)))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rule,quantity,cls", [pytest.param(r, q, c, marks=pytest.mark.xfail(strict=True, reason=_EIG_MISSES[(r, q, c)])) if (r, q, c) in _EIG_MISSES else (r, q, c)
+                                               for r in ("strict", "production") for q in ("eigenvalues", "positive part") for c in _EIG_CLASSES])
+def test_batched_eigensolver_on_hard_spectra_per_eigenvalue(hipctx, rule, quantity, cls):
+    """bcd_hip_eig27_batch on graded spectra, clusters, definite and zero matrices and the clamp inputs C - N of the constructed families (each also
+    x 2^+-20), in batches of 1, 2, 3 and 2 (#CUs) 12 + 1 matrices; one case per class of spectrum, quantity and stopping rule.
+
+    The rule: bcd_hip_eig27_batch ALWAYS stops at off^2 <= 1e-12 diag^2 (bcd_api.hip passes no threshold: the launcher's default); the process-wide
+    bcd_hip_set_strict_eigensolver only reaches the estimate chain (jacobi_conv2() in bcd_launch_bayes27), not this entry point.  The production
+    rule 2e-9 is selected here through bcd_hip_eig27_batch_rule -- without the first-order correction, which lives in the finish kernels.
+
+    Per eigenvalue (sorted, against LAPACK dsyev on the same float32 matrix): |lambda - lambda_64| <= max(4 x the error of LAPACK ssyev on that
+    matrix, 27 u |A|_2), u = 2^-24 -- the calibrator again, nothing from a GPU run.  And the quantity the estimate uses, the positive part
+    A+ = V max(0, Lambda) V^T (spectral norm of the difference to float64 -- the norm the floor 27 u |A|_2 is stated in; it is below the Frobenius norm
+    that the first-order term bounds): under the strict rule the calibrator term alone (4 x what ssyev's V and lambda give in float32, floor 27 u);
+    under the production rule + sqrt(2e-9) |A|_F -- the stop rule bounds the residual off-diagonal Frobenius norm by that, and the positive part is
+    1-Lipschitz in that norm.  The eigenvalues get no such term under either rule: their error is second order in the residual (residual^2 / gap)
+    wherever the spectrum is separated."""
+    rows = _eig_measure(hipctx, rule)[cls]
+    assert len(rows) >= 3                                                # every class: all three scalings at least once
+    k = 1 if quantity == "eigenvalues" else 3
+    bad = ["%s: %.3e > %.3e" % (r[0], r[k], r[k + 1]) for r in rows if r[k] > r[k + 1]]
+    assert not bad, "%d of %d matrices (%s, %s rule); the first: %s" % (len(bad), len(rows), quantity, rule, "; ".join(bad[:4]))
 
 
 @pytest.mark.gpu

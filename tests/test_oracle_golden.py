@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import bayes_ref
 import oracle_lib as ol
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -279,58 +280,11 @@ def test_float64_numpy_restatement_of_the_bayesian_steps_agrees_with_the_oracle(
     mask, _, _ = _np32_similar_sets(f["ns"], f["hist"], 1, 6, 1.0)
     col, ns, cov, want = f["col"].astype(np.float64), f["ns"].astype(np.float64), f["cov"].astype(np.float64), f["out_m0"]
     H, W, _ = col.shape
-    b, w, min_eig = 6, 1, 1e-8
-    side = 2 * b + 1
     pixcov = cov * (1.0 / ns)                                            # Denoiser.cpp:357-373
-    offs = [(ol_, oc) for ol_ in (-1, 0, 1) for oc in (-1, 0, 1)]        # patch pixels, row-major (DeepImage.hpp window iteration)
-
-    def block(v6):                                                       # CovarianceMatrix.h:18-27: xx,yy,zz,yz,xz,xy
-        xx, yy, zz, yz, xz, xy = v6
-        return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
-
-    def patch_vec(img, l, c):                                            # :483-498: pixel-major, RGB
-        return np.concatenate([img[l + a, c + d] for (a, d) in offs])
-
-    def spectral(M, fn):                                                 # :578-630
-        lam, V = np.linalg.eigh(M)
-        return (V * fn(lam)) @ V.T
-
-    acc = np.zeros((H, W, 3))
-    cnt = np.zeros((H, W))
-    for l in range(w, H - w):
-        for c in range(w, W - w):
-            bits = np.unpackbits(mask[l, c].view(np.uint8), bitorder="little")[:side * side]
-            members = [(l + k // side - b, c + k % side - b) for k in np.nonzero(bits)[0]]   # window order (:196-219)
-            n = len(members)
-            X = np.stack([patch_vec(col, ql, qc) for (ql, qc) in members])
-            if n < 3 * 9 + 1:                                            # :182 -> denoiseOnlyMainPatch (:455-481)
-                est = X.mean(axis=0)
-                for o, (a, d) in enumerate(offs):
-                    acc[l + a, c + d] += est[3 * o:3 * o + 3]
-                    cnt[l + a, c + d] += 1
-                continue
-            N = np.zeros((27, 27))                                       # computeNoiseCovPatchesMean (:400-419)
-            for (ql, qc) in members:
-                for o, (a, d) in enumerate(offs):
-                    N[3 * o:3 * o + 3, 3 * o:3 * o + 3] += block(pixcov[ql + a, qc + d])
-            N /= n
-            # Step 1 (:421-436)
-            m1 = X.mean(axis=0)
-            Xc = X - m1
-            C = Xc.T @ Xc / (n - 1)
-            C1 = spectral(C - N, lambda lam: np.maximum(0.0, lam)) + N
-            I1 = spectral(C1, lambda lam: 1.0 / np.maximum(min_eig, lam))
-            X1 = X - (N @ (I1 @ Xc.T)).T                                 # finalDenoisingMatrixMultiplication (:656-670)
-            # Step 2 (:438-453): no clamp; the noisy patches are centred on the mean of the Step-1 estimates
-            m2 = X1.mean(axis=0)
-            X1c = X1 - m2
-            C2 = X1c.T @ X1c / (n - 1) + N
-            I2 = spectral(C2, lambda lam: 1.0 / np.maximum(min_eig, lam))
-            X2 = X - (N @ (I2 @ (X - m2).T)).T
-            for (ql, qc), est in zip(members, X2):                       # aggregateOutputPatches (:672-693)
-                for o, (a, d) in enumerate(offs):
-                    acc[ql + a, qc + d] += est[3 * o:3 * o + 3]
-                    cnt[ql + a, qc + d] += 1
+    nsim = bayes_ref.popcount(mask)
+    state = np.zeros((H, W), np.uint8)
+    state[1:H - 1, 1:W - 1] = 1                                          # -m 0: every main pixel is processed
+    acc, cnt, _ = bayes_ref.accumulate(col, pixcov, mask, nsim, state, 1, 6, 1e-8, keep_stages=False)   # (the loop that stood here: tests/bayes_ref.py)
     got = acc / cnt[..., None]                                           # finalAggregation (Denoiser.cpp:458-469)
     assert (f["fallback"] > 0).any() and (f["nsim"] >= 28).any()         # both paths are exercised on this frame
     err = np.max(np.abs(got - want)) / np.max(np.abs(want))
@@ -338,44 +292,11 @@ def test_float64_numpy_restatement_of_the_bayesian_steps_agrees_with_the_oracle(
 
 
 def _np64_stages(col, ns, cov, members, W, min_eig=1e-8):
-    """float64 restatement of denoiseSelectedPatches written from /root/reference/src/core/DenoisingUnit.cpp:388-453,483-670 (not from
-    the oracle): every intermediate, numpy.linalg.eigh in place of Eigen's solver"""
+    """float64 restatement of denoiseSelectedPatches (tests/bayes_ref.py, written from /root/reference/src/core/DenoisingUnit.cpp:388-453,483-670, not
+    from the oracle): every intermediate, numpy.linalg.eigh in place of Eigen's solver"""
     col, ns, cov = col.astype(np.float64), ns.astype(np.float64), cov.astype(np.float64)
     pixcov = cov * (1.0 / ns)                                            # Denoiser.cpp:357-373
-    offs = [(a, d) for a in (-1, 0, 1) for d in (-1, 0, 1)]
-    pos = [(int(m) // W, int(m) % W) for m in members]
-    X = np.stack([np.concatenate([col[l + a, c + d] for (a, d) in offs]) for (l, c) in pos])
-    n = len(pos)
-    st = {"x": X, "mean1": X.mean(axis=0)}
-    if n < 28:
-        return st
-    noise6 = np.zeros((9, 6))
-    for (l, c) in pos:
-        for o, (a, d) in enumerate(offs):
-            noise6[o] += pixcov[l + a, c + d]
-    noise6 /= n                                                          # :400-419
-    N = np.zeros((27, 27))
-    for o in range(9):
-        xx, yy, zz, yz, xz, xy = noise6[o]                               # CovarianceMatrix.h:18-27
-        N[3 * o:3 * o + 3, 3 * o:3 * o + 3] = [[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]
-
-    def spectral(M, fn):
-        lam, V = np.linalg.eigh(M)
-        return (V * fn(lam)) @ V.T
-
-    Xc = X - st["mean1"]
-    C = Xc.T @ Xc / (n - 1)                                              # :522-536
-    clamped = spectral(C - N, lambda lam: np.maximum(0.0, lam))          # :606-630
-    inv1 = spectral(clamped + N, lambda lam: 1.0 / np.maximum(min_eig, lam))   # :578-604
-    X1 = X - (N @ (inv1 @ Xc.T)).T                                       # :656-670
-    m2 = X1.mean(axis=0)
-    X1c = X1 - m2
-    C2 = X1c.T @ X1c / (n - 1)
-    inv2 = spectral(C2 + N, lambda lam: 1.0 / np.maximum(min_eig, lam))
-    X2 = X - (N @ (inv2 @ (X - m2).T)).T                                 # :449-450: the NOISY patches centred on the Step-2 mean
-    st.update(noise=noise6, cov1=C, cov1_minus_noise=C - N, clamped=clamped, clamped_plus_noise=clamped + N, inverse1=inv1, step1=X1,
-              mean2=m2, cov2=C2, inverse2=inv2, step2=X2)
-    return st
+    return bayes_ref.stages(col, pixcov, [(int(m) // W, int(m) % W) for m in members], 1, min_eig)
 
 
 # stage -> tolerance of the fp32 oracle against the float64 restatement, relative to the largest magnitude of the stage: about 5x the
