@@ -100,6 +100,13 @@ hipError_t bcd_launch_bayes_strong(const float *, const float *, const uint32_t 
 hipError_t bcd_launch_bayes_weak(const float *, const uint32_t *, const int32_t *, const int32_t *, int, int, int, int, int, float *,
                                  int32_t *, hipStream_t);
 hipError_t bcd_launch_bayes_weak_tiles(const float *, const uint32_t *, const uint8_t *, const int32_t *, int, int, int, int, float *, int32_t *, hipStream_t, int, int, const long long *);
+hipError_t bcd_launch_bayes_weak_tiles_layers(const BcdLayerTable &, int, const uint32_t *, const uint8_t *, const int32_t *, int, int, int, int, hipStream_t, int, int);
+hipError_t bcd_launch_layers_pixel_cov_clear(const BcdLayerTable &, int, const float *, int64_t, float *, float *, hipStream_t);
+hipError_t bcd_launch_layers_finalize(const BcdLayerTable &, int, const int32_t *, int64_t, hipStream_t);
+hipError_t bcd_launch_layers_downscale_avg(const BcdLayerTable &, int, int, int, hipStream_t);
+hipError_t bcd_launch_layers_downscale_cov(const BcdLayerTable &, int, const float *, int, int, hipStream_t);
+hipError_t bcd_launch_layers_merge(const BcdLayerTable &, int, int, int, int, int, hipStream_t);
+static_assert(BCD_MAX_LAYERS == BCD_HIP_MAX_LAYERS, "the layer tables of the kernels hold what the C ABI admits");
 
 namespace {
 
@@ -112,6 +119,13 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// the colour layers of a bcd_hip_denoise_layers call BEYOND the first, at one scale: the first layer travels through the arguments bcd_hip_denoise has
+struct LayerView {
+    int n = 0;
+    const float *col[BCD_MAX_LAYERS], *cov[BCD_MAX_LAYERS];
+    float *out[BCD_MAX_LAYERS];
+};
+
 } // namespace
 
 // everything one scale's pipeline needs: a multiscale run drives one Work per scale concurrently (own stream, own host
@@ -120,6 +134,7 @@ struct Work {
     hipStream_t stream = nullptr;
     bool owns_stream = false;
     DevBuf T, Cn, mask, fwd, nsim, state, strong, weak, counters, cnt_lines, work_q, pixcov, sum, cnt, gscratch, dep, tmp_lo, border, ratio_stats; // grow-only
+    DevBuf lay_pixcov, lay_sum, lay_tmp_lo; // extra colour layers (bcd_hip_denoise_layers): per-pixel covariances, sums, merge scratch -- one slice per layer
     int border_capacity = 0;       // entries of `border` offered to the last fast similarity pass (0: the exact kernels ran)
     int rounds_hint = 0;           // marking launches the last problem needed
     int last_batch = 0;            // launches of the batch active_step_enqueue left in flight
@@ -180,6 +195,10 @@ struct bcd_hip_ctx {
     Work extra[MAX_SCALES];  // lazily created streams for scales 1.. of a multiscale run
     DevBuf tmp_lo;
     DevBuf pyr[MAX_SCALES][5]; // colours, nsamples, hist, cov, out
+    DevBuf lay_host[3];            // host-buffer entry point of the layers: device copies of the extra layers' colours, covariances, outputs
+    DevBuf lay_pyr[MAX_SCALES][3]; // extra colour layers: colours, cov, out of every layer at that pyramid level, one slice per layer
+    int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
+    int layer_count = 0;                                // layers of that call (0: none yet)
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
     hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
@@ -723,10 +742,77 @@ float stage_ms(Work &wk, int a, int b)
     return ms;
 }
 
+// The estimate stage of the extra colour layers of a scale, on the selection the first layer's chain has just decided (mono_accumulate; the stream is
+// synchronised, wk.h_counters hold the list lengths): nothing is selected, marked or listed again.  The fallback pixels of ALL layers go through one
+// launch of the layered tile kernel on the side stream (3 x 3 patches; other radii: the list kernel per layer), the full-estimate chain runs once per
+// layer over the same item list and work queues with that layer's colours and covariances -- its 9.9 KB records are reused from layer to layer, its redo
+// list (items whose sweep inverse failed ITS matrices' checks) is walked behind each layer's finish kernel.  No kernel gets the count image: it is the
+// first layer's.  One launch finalises every layer.
+int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int scale)
+{
+    const int E = lv.n;
+    const int64_t npix = (int64_t)W * H;
+    const int K = 3 * (2 * w + 1) * (2 * w + 1);
+    float *pixcov = (float *)wk.lay_pixcov.p, *sum = (float *)wk.lay_sum.p;
+    int32_t *d_c = (int32_t *)wk.counters.p + 16;
+    const int n_strong = wk.h_counters[16];
+    int32_t *spectral = ctx->layer_spectral[scale < MAX_SCALES ? scale : MAX_SCALES - 1];
+    spectral[0] = wk.h_counters[23];
+    const uint32_t *d_mask = (const uint32_t *)wk.mask.p;
+    const int32_t *d_nsim = (const int32_t *)wk.nsim.p;
+    int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100); // (as bayes())
+    if (&wk != &ctx->main) cus = std::max(1, cus * ctx->coarse_share / 100);
+    HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
+    HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
+    if (w == 1) {
+        BcdLayerTable t = {};
+        for (int k = 0; k < E; ++k) { t.a[k] = lv.col[k]; t.o[k] = sum + (size_t)k * npix * 3; }
+        HIPCHK(ctx, bcd_launch_bayes_weak_tiles_layers(t, E, d_mask, (const uint8_t *)wk.state.p, d_nsim, K + 1, W, H, b, wk.aux, 0, H));
+    } else {
+        const int weak_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), (int64_t)cus * 32);
+        for (int k = 0; k < E; ++k)
+            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, (const int32_t *)wk.weak.p, d_c + 1, weak_blocks, W, H, w, b, sum + (size_t)k * npix * 3, nullptr, wk.aux));
+    }
+    HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
+    if (w == 1) {
+        const size_t rec = bcd_bayes27_record_bytes();
+        const int chunk_max = 1 << 18; // (as bayes())
+        if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, rec * (size_t)std::min(n_strong, chunk_max)));
+        for (int k = 0; k < E; ++k) {
+            for (int first = 0; first < n_strong; first += chunk_max) {
+                HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
+                HIPCHK(ctx, bcd_launch_bayes27(lv.col[k], pixcov + (size_t)k * npix * 6, d_mask, (const int32_t *)wk.strong.p, first, std::min(chunk_max, n_strong - first),
+                                               (int *)wk.work_q.p, cus, W, H, b, min_eig, (float *)wk.gscratch.p, sum + (size_t)k * npix * 3, nullptr, d_c + 7, wk.stream, 0, nullptr));
+            }
+            HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 24 + k, d_c + 7, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
+        }
+    } else {
+        const size_t per_block = bcd_bayes_scratch_bytes_per_block(w, b);
+        const int strong_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), 1024);
+        if (per_block) RCCHK(ensure(ctx, wk.gscratch, per_block * (size_t)strong_blocks));
+        for (int k = 0; k < E; ++k) {
+            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov + (size_t)k * npix * 6, d_mask, (const int32_t *)wk.strong.p, d_c, d_c + 4, strong_blocks, W, H, w, b, min_eig,
+                                                sum + (size_t)k * npix * 3, nullptr, (float *)wk.gscratch.p, wk.gscratch.bytes, wk.stream));
+            wk.h_counters[24 + k] = wk.h_counters[23];
+        }
+    }
+    HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_join, 0));
+    {
+        BcdLayerTable t = {};
+        for (int k = 0; k < E; ++k) { t.a[k] = sum + (size_t)k * npix * 3; t.o[k] = lv.out[k]; }
+        HIPCHK(ctx, bcd_launch_layers_finalize(t, E, d_count, npix, wk.stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    for (int k = 0; k < E; ++k) spectral[k + 1] = wk.h_counters[24 + k] - (k == 0 ? wk.h_counters[23] : wk.h_counters[24 + k - 1]);
+    wk.h_counters[23] = wk.h_counters[24 + E - 1]; // the scale's figure: the sum over the layers
+    return BCD_HIP_OK;
+}
+
 // one scale: accumulators only (d_sum / d_count are zeroed here)
 int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
                     int W, int H, int D, int row_begin, int row_end, const bcd_hip_params *prm, uint32_t seed, int scale,
-                    float *d_sum, int32_t *d_count, float *d_out = nullptr /* finalised image, optional */)
+                    float *d_sum, int32_t *d_count, float *d_out = nullptr /* finalised image, optional */,
+                    const LayerView *lv = nullptr /* further colour layers on the same selection (needs d_out and the whole frame), optional */)
 {
     const int w = prm->patch_radius, b = prm->search_radius;
     const size_t npix = (size_t)W * H;
@@ -749,6 +835,13 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream)); // (the inputs are ready at this point of the scale's stream)
     HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
     HIPCHK(ctx, bcd_launch_pixel_cov_clear(d_cov, d_ns, (int64_t)npix, (float *)wk.pixcov.p, d_sum, d_count, wk.aux)); // (+ the accumulators cleared: one launch)
+    if (lv && lv->n > 0) { // the same for every further layer, one launch (their sums; the count image is shared)
+        RCCHK(ensure(ctx, wk.lay_pixcov, (size_t)lv->n * npix * 6 * sizeof(float)));
+        RCCHK(ensure(ctx, wk.lay_sum, (size_t)lv->n * npix * 3 * sizeof(float)));
+        BcdLayerTable t = {};
+        for (int k = 0; k < lv->n; ++k) t.a[k] = lv->cov[k];
+        HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, lv->n, d_ns, (int64_t)npix, (float *)wk.lay_pixcov.p, (float *)wk.lay_sum.p, wk.aux));
+    }
     HIPCHK(ctx, hipEventRecord(wk.ev_pixcov, wk.aux));
     // every counter, flag and work queue of the chain in one launch at the head of the scale's stream (round 4: they were ~7 fills between
     // the kernels of the critical path); flags raised by distance planes computed ahead of this call are kept
@@ -831,6 +924,7 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
         HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     }
     wk.redo.pending = false;
+    if (lv && lv->n > 0) RCCHK(layers_follow(ctx, wk, *lv, W, H, w, b, prm->min_eigen_value, d_count, scale));
     progress_add(ctx, 0.5 * (double)npix);
     int64_t ns = 0, nw = 0, tot = 0;
     bayes_counts(wk, &ns, &nw, &tot);
@@ -870,12 +964,37 @@ int build_level(bcd_hip_ctx *ctx, const float *col, const float *ns, const float
 }
 
 int mono(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov, int W, int H, int D,
-         const bcd_hip_params *prm, uint32_t seed, int scale, float *d_out)
+         const bcd_hip_params *prm, uint32_t seed, int scale, float *d_out, const LayerView *lv = nullptr)
 {
     const size_t npix = (size_t)W * H;
     RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
     RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
-    return mono_accumulate(ctx, wk, d_colors, d_ns, d_hist, d_cov, W, H, D, 0, H, prm, seed, scale, (float *)wk.sum.p, (int32_t *)wk.cnt.p, d_out);
+    return mono_accumulate(ctx, wk, d_colors, d_ns, d_hist, d_cov, W, H, D, 0, H, prm, seed, scale, (float *)wk.sum.p, (int32_t *)wk.cnt.p, d_out, lv);
+}
+
+// the pyramid level of the extra layers (colour averaged, covariance weighted by the SHARED sample counts of the finer level): two launches for all of them
+int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &coarse, const float *ns_fine, int W, int H, hipStream_t st)
+{
+    BcdLayerTable t = {};
+    for (int k = 0; k < fine.n; ++k) { t.a[k] = fine.col[k]; t.o[k] = const_cast<float *>(coarse.col[k]); }
+    HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, fine.n, W, H, st));
+    for (int k = 0; k < fine.n; ++k) { t.a[k] = fine.cov[k]; t.o[k] = const_cast<float *>(coarse.cov[k]); }
+    HIPCHK(ctx, bcd_launch_layers_downscale_cov(t, fine.n, ns_fine, W, H, st));
+    return BCD_HIP_OK;
+}
+
+// merge_on for the extra layers' outputs: two launches for all of them
+int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int H, const LayerView &lo)
+{
+    const int w2 = W / 2, h2 = H / 2;
+    const size_t slice = (size_t)w2 * h2 * 3;
+    RCCHK(ensure(ctx, wk.lay_tmp_lo, (size_t)hi.n * slice * sizeof(float)));
+    BcdLayerTable t = {};
+    for (int k = 0; k < hi.n; ++k) { t.a[k] = hi.out[k]; t.o[k] = (float *)wk.lay_tmp_lo.p + k * slice; }
+    HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, hi.n, W, H, wk.stream));
+    for (int k = 0; k < hi.n; ++k) { t.a[k] = (const float *)wk.lay_tmp_lo.p + k * slice; t.b[k] = lo.out[k]; t.o[k] = hi.out[k]; }
+    HIPCHK(ctx, bcd_launch_layers_merge(t, hi.n, w2, h2, W, H, wk.stream));
+    return BCD_HIP_OK;
 }
 
 
@@ -903,7 +1022,7 @@ int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream)
 
 void work_destroy(Work &w)
 {
-    DevBuf *bufs[] = { &w.T, &w.Cn, &w.mask, &w.fwd, &w.nsim, &w.state, &w.strong, &w.weak, &w.counters, &w.cnt_lines, &w.work_q, &w.pixcov, &w.sum, &w.cnt, &w.gscratch, &w.dep, &w.tmp_lo, &w.border, &w.ratio_stats };
+    DevBuf *bufs[] = { &w.T, &w.Cn, &w.mask, &w.fwd, &w.nsim, &w.state, &w.strong, &w.weak, &w.counters, &w.cnt_lines, &w.work_q, &w.pixcov, &w.sum, &w.cnt, &w.gscratch, &w.dep, &w.tmp_lo, &w.border, &w.ratio_stats, &w.lay_pixcov, &w.lay_sum, &w.lay_tmp_lo };
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (w.h_counters) (void)hipHostFree(w.h_counters);
     for (auto &pr : w.ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -954,6 +1073,7 @@ int bcd_hip_ctx_create(bcd_hip_ctx **out, int device, void *hip_stream)
     DeviceGuard guard(ctx);
     if (!guard.ok) { delete ctx; return BCD_HIP_EDEVICE; }
     memset(ctx->stats, 0, sizeof(ctx->stats));
+    memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
     if (hip_stream) ctx->stream = (hipStream_t)hip_stream;
     else {
         if (hipStreamCreate(&ctx->stream) != hipSuccess) { delete ctx; return BCD_HIP_EDEVICE; }
@@ -993,8 +1113,11 @@ void bcd_hip_ctx_destroy(bcd_hip_ctx *ctx)
     for (int s = 0; s < MAX_SCALES; ++s) work_destroy(ctx->extra[s]);
     if (ctx->tmp_lo.p) (void)hipFree(ctx->tmp_lo.p);
     for (DevBuf &hb : ctx->host_stage) if (hb.p) (void)hipFree(hb.p);
+    for (DevBuf &hb : ctx->lay_host) if (hb.p) (void)hipFree(hb.p);
     for (int s = 0; s < MAX_SCALES; ++s)
         for (int k = 0; k < 5; ++k) if (ctx->pyr[s][k].p) (void)hipFree(ctx->pyr[s][k].p);
+    for (int s = 0; s < MAX_SCALES; ++s)
+        for (int k = 0; k < 3; ++k) if (ctx->lay_pyr[s][k].p) (void)hipFree(ctx->lay_pyr[s][k].p);
     if (ctx->ev_pyramid) (void)hipEventDestroy(ctx->ev_pyramid);
     for (hipEvent_t ev : ctx->ev_upload) (void)hipEventDestroy(ev);
     if (ctx->upload_stream) (void)hipStreamDestroy(ctx->upload_stream);
@@ -1081,21 +1204,24 @@ int bcd_hip_reset_kernel_time(bcd_hip_ctx *ctx)
     return BCD_HIP_OK;
 }
 
-int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
-                    int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+// bcd_hip_denoise, and -- with `lv0`: the layers beyond the first at full resolution -- bcd_hip_denoise_layers: the first layer takes exactly the path of a
+// plain call, the others follow it scale by scale (pyramid level, estimate on the decided selection, merge)
+static int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
+                        int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out, const LayerView *lv0)
 {
     if (!ctx) return BCD_HIP_EINVAL;
     if (!d_colors || !d_ns || !d_hist || !d_cov || !d_out) return bad(ctx, "null image pointer"); // Denoiser.cpp:266-293
     RCCHK(check_params(ctx, W, H, D, prm));
     if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
     DEVICE_GUARD(ctx);
+    const int E = lv0 ? lv0->n : 0; // extra layers
     {
         std::lock_guard<std::mutex> lock(ctx->progress_mutex);
         ctx->progress_done = 0.0;
         ctx->progress_total = 0.0;
         for (int s = 0; s < nb_scales; ++s) ctx->progress_total += (double)(W >> s) * (double)(H >> s);
     }
-    if (nb_scales == 1) return mono(ctx, ctx->main, d_colors, d_ns, d_hist, d_cov, W, H, D, prm, bcd_hip_scale_seed(prm->order_seed, 0), 0, d_out);
+    if (nb_scales == 1) return mono(ctx, ctx->main, d_colors, d_ns, d_hist, d_cov, W, H, D, prm, bcd_hip_scale_seed(prm->order_seed, 0), 0, d_out, E ? lv0 : nullptr);
 
     // ---- pyramids (MultiscaleDenoiser.cpp:41-53): level s has dims of level s-1 // 2
     const float *col[MAX_SCALES], *ns[MAX_SCALES], *hs[MAX_SCALES], *cv[MAX_SCALES];
@@ -1114,6 +1240,21 @@ int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, 
         col[s] = (float *)ctx->pyr[s][0].p; ns[s] = (float *)ctx->pyr[s][1].p; hs[s] = (float *)ctx->pyr[s][2].p;
         cv[s] = (float *)ctx->pyr[s][3].p; out[s] = (float *)ctx->pyr[s][4].p;
     }
+    std::vector<LayerView> lvs(E ? nb_scales : 0); // the extra layers at every pyramid level
+    if (E) lvs[0] = *lv0;
+    for (int s = 1; E && s < nb_scales; ++s) {
+        const size_t np = (size_t)ws[s] * hh[s];
+        RCCHK(ensure(ctx, ctx->lay_pyr[s][0], (size_t)E * np * 3 * sizeof(float)));
+        RCCHK(ensure(ctx, ctx->lay_pyr[s][1], (size_t)E * np * 6 * sizeof(float)));
+        RCCHK(ensure(ctx, ctx->lay_pyr[s][2], (size_t)E * np * 3 * sizeof(float)));
+        lvs[s].n = E;
+        for (int k = 0; k < E; ++k) {
+            lvs[s].col[k] = (const float *)ctx->lay_pyr[s][0].p + k * np * 3;
+            lvs[s].cov[k] = (const float *)ctx->lay_pyr[s][1].p + k * np * 6;
+            lvs[s].out[k] = (float *)ctx->lay_pyr[s][2].p + k * np * 3;
+        }
+    }
+    const LayerView *lvp = E ? lvs.data() : nullptr;
     // ---- the scales are independent until the merges (MultiscaleDenoiser.cpp:79-134 runs them coarse to fine, but each
     // Denoiser only reads its own pyramid level): one stream + host thread + workspace per scale.  Scale s > 0 builds its
     // own pyramid level on its stream (from level s-1, once that is complete), so that the finest scale -- the critical
@@ -1122,7 +1263,7 @@ int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, 
         // The coarse scales' share of the CU slots (bayes()) follows the previous call on the same geometry: they should be through when
         // the finest scale is at 80 - 92 % of its chain -- earlier means their persistent kernels took more room than they needed next to
         // the finest scale's short kernels, later means they have become the critical path.  Small steps down, larger ones up.
-        const int64_t key = ((int64_t)W << 40) ^ ((int64_t)H << 20) ^ ((int64_t)nb_scales << 12) ^ ((int64_t)prm->search_radius << 4) ^ (prm->marked_skip_probability > 0.f);
+        const int64_t key = ((int64_t)W << 40) ^ ((int64_t)H << 20) ^ ((int64_t)nb_scales << 12) ^ ((int64_t)prm->search_radius << 4) ^ (prm->marked_skip_probability > 0.f) ^ ((int64_t)E << 56);
         if (key != ctx->share_key) { ctx->coarse_share = 25; ctx->share_key = key; }
         const auto t_start = std::chrono::steady_clock::now();
         double t_done[MAX_SCALES] = { 0 };
@@ -1149,16 +1290,20 @@ int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, 
                         }
                         rc = build_level(ctx, col[s - 1], ns[s - 1], hs[s - 1], cv[s - 1], ws[s - 1], hh[s - 1], D, ctx->pyr[s], w->stream);
                         if (rc != BCD_HIP_OK) break;
+                        if (lvp) rc = build_level_layers(ctx, lvp[s - 1], lvp[s], ns[s - 1], ws[s - 1], hh[s - 1], w->stream);
+                        if (rc != BCD_HIP_OK) break;
                         if (hipEventRecord(w->ev_built, w->stream) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
                         built[s].store(1); built_set = true;
                     }
-                    rc = mono(ctx, *w, col[s], ns[s], hs[s], cv[s], ws[s], hh[s], D, prm, bcd_hip_scale_seed(prm->order_seed, s), s, out[s]);
+                    rc = mono(ctx, *w, col[s], ns[s], hs[s], cv[s], ws[s], hh[s], D, prm, bcd_hip_scale_seed(prm->order_seed, s), s, out[s], lvp ? &lvp[s] : nullptr);
                     if (rc != BCD_HIP_OK) break;
                     t_done[s] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); // (mono ends with a stream synchronisation)
                     if (s < nb_scales - 1) {
                         if (await(done[s + 1]) < 0) { rc = BCD_HIP_EDEVICE; break; }
                         if (hipStreamWaitEvent(w->stream, ctx->extra[s + 1].ev_done, 0) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
                         rc = merge_on(ctx, *w, out[s], ws[s], hh[s], out[s + 1], 3);
+                        if (rc != BCD_HIP_OK) break;
+                        if (lvp) rc = merge_layers_on(ctx, *w, lvp[s], ws[s], hh[s], lvp[s + 1]);
                         if (rc != BCD_HIP_OK) break;
                     }
                     if (s != 0) {
@@ -1174,6 +1319,7 @@ int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, 
         }
         for (int s = 1; s < nb_scales; ++s) threads[s].join();
         for (int s = 0; s < nb_scales; ++s) RCCHK(rcs[s]);
+        if (lvp) HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream)); // (the last merge of the extra layers)
         if (nb_scales > 1 && t_done[0] > 0.0) {
             double last = 0.0;
             for (int s = 1; s < nb_scales; ++s) last = std::max(last, t_done[s]);
@@ -1183,13 +1329,73 @@ int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, 
         }
         return BCD_HIP_OK;
     }
-    for (int s = 1; s < nb_scales; ++s)
+    for (int s = 1; s < nb_scales; ++s) {
         RCCHK(build_level(ctx, col[s - 1], ns[s - 1], hs[s - 1], cv[s - 1], ws[s - 1], hh[s - 1], D, ctx->pyr[s], ctx->stream));
+        if (lvp) RCCHK(build_level_layers(ctx, lvp[s - 1], lvp[s], ns[s - 1], ws[s - 1], hh[s - 1], ctx->stream));
+    }
     // ---- coarse to fine, one after the other
     for (int s = nb_scales - 1; s >= 0; --s) {
-        RCCHK(mono(ctx, ctx->main, col[s], ns[s], hs[s], cv[s], ws[s], hh[s], D, prm, bcd_hip_scale_seed(prm->order_seed, s), s, out[s]));
+        RCCHK(mono(ctx, ctx->main, col[s], ns[s], hs[s], cv[s], ws[s], hh[s], D, prm, bcd_hip_scale_seed(prm->order_seed, s), s, out[s], lvp ? &lvp[s] : nullptr));
         if (s < nb_scales - 1) RCCHK(bcd_hip_merge(ctx, out[s], ws[s], hh[s], out[s + 1], 3));
+        if (s < nb_scales - 1 && lvp) RCCHK(merge_layers_on(ctx, ctx->main, lvp[s], ws[s], hh[s], lvp[s + 1]));
     }
+    if (lvp) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
+                    int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+{
+    return denoise_impl(ctx, d_colors, d_ns, d_hist, d_cov, W, H, D, nb_scales, prm, d_out, nullptr);
+}
+
+int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                           const bcd_hip_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    // ---- everything is checked before any device work
+    if (!d_ns || !d_hist) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k)
+        if (!layers[k].d_colors || !layers[k].d_covariances || !layers[k].d_out) return bad(ctx, "null image pointer in a layer");
+    RCCHK(check_params(ctx, W, H, D, prm));
+    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
+        ws /= 2; hs /= 2;
+        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
+    }
+    {
+        const size_t npix = (size_t)W * H;
+        auto overlap = [](const float *a, size_t na, const float *b, size_t nb) {
+            const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + nb * sizeof(float);
+            return a0 < b1 && b0 < a1;
+        };
+        for (int k = 0; k < nb_layers; ++k) {
+            const float *o = layers[k].d_out;
+            if (overlap(o, npix * 3, d_ns, npix) || overlap(o, npix * 3, d_hist, npix * D)) return bad(ctx, "a layer's output overlaps the sample counts or the histograms");
+            for (int j = 0; j < nb_layers; ++j) {
+                if (overlap(o, npix * 3, layers[j].d_colors, npix * 3) || overlap(o, npix * 3, layers[j].d_covariances, npix * 6))
+                    return bad(ctx, "a layer's output overlaps an input image");
+                if (j != k && overlap(o, npix * 3, layers[j].d_out, npix * 3)) return bad(ctx, "two layers share (part of) an output image");
+            }
+        }
+    }
+    LayerView lv;
+    lv.n = nb_layers - 1;
+    for (int k = 1; k < nb_layers; ++k) { lv.col[k - 1] = layers[k].d_colors; lv.cov[k - 1] = layers[k].d_covariances; lv.out[k - 1] = layers[k].d_out; }
+    memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+    ctx->layer_count = 0;
+    RCCHK(denoise_impl(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, W, H, D, nb_scales, prm, layers[0].d_out, &lv));
+    if (lv.n == 0) for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
+    ctx->layer_count = nb_layers;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_layer_spectral_inverses(const bcd_hip_ctx *ctx, int scale, int layer, int32_t *count)
+{
+    if (!ctx || !count || scale < 0 || scale >= MAX_SCALES || layer < 0 || layer >= ctx->layer_count) return BCD_HIP_EINVAL;
+    *count = ctx->layer_spectral[scale][layer];
     return BCD_HIP_OK;
 }
 
@@ -1289,8 +1495,11 @@ int bcd_hip_denoise_bands(bcd_hip_ctx *ctx, const bcd_hip_band_job *jobs, int nj
     return BCD_HIP_OK;
 }
 
-int bcd_hip_denoise_host_ex(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
-                            int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out)
+// bcd_hip_denoise_host_ex, and -- with `extra`: host images of further colour layers -- bcd_hip_denoise_layers_host: the primary inputs travel as they always
+// did (streamed, the histograms without their zeros), the extra layers as plain copies behind them
+static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
+                             int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out,
+                             const bcd_hip_host_layer *extra, int nb_extra)
 {
     if (!ctx) return BCD_HIP_EINVAL;
     if (!h_colors || !h_ns || !h_hist || !h_cov || !h_out) return bad(ctx, "null image pointer");
@@ -1414,16 +1623,60 @@ int bcd_hip_denoise_host_ex(bcd_hip_ctx *ctx, const float *h_colors, const float
         wk.planes.ready = true; wk.planes.hist = d[7]; wk.planes.ns = d[6]; wk.planes.W = W; wk.planes.H = H; wk.planes.D = D; wk.planes.b = b;
         wk.planes.tau = prm->hist_dist_threshold; wk.planes.uni_n = uni_n;
     }
+    LayerView lv;
+    if (nb_extra > 0) { // device copies of the extra layers: colours | covariances | outputs, one slice per layer
+        auto fail = [&](int rc) { ctx->main.planes.ready = false; return rc; };
+        for (int i = 0; i < 3; ++i)
+            if (ensure(ctx, ctx->lay_host[i], (size_t)nb_extra * np * (i == 1 ? 6 : 3) * sizeof(float)) != BCD_HIP_OK) return fail(BCD_HIP_ENOMEM);
+        lv.n = nb_extra;
+        for (int k = 0; k < nb_extra; ++k) {
+            float *dc = (float *)ctx->lay_host[0].p + k * np * 3, *dv = (float *)ctx->lay_host[1].p + k * np * 6;
+            lv.col[k] = dc; lv.cov[k] = dv; lv.out[k] = (float *)ctx->lay_host[2].p + k * np * 3;
+            if (hipMemcpyAsync(dc, extra[k].h_colors, np * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+                hipMemcpyAsync(dv, extra[k].h_covariances, np * 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+                set_err(ctx, "upload of a colour layer failed");
+                return fail(BCD_HIP_EDEVICE);
+            }
+        }
+    }
     {
-        const int rc = bcd_hip_denoise(ctx, d[5], d[6], d[7], d[8], W, H, D, nb_scales, prm, d[4]);
+        const int rc = denoise_impl(ctx, d[5], d[6], d[7], d[8], W, H, D, nb_scales, prm, d[4], nb_extra > 0 ? &lv : nullptr);
         ctx->main.planes.ready = false; // (consumed by the finest scale's similarity stage; never left behind by a call that failed earlier)
         if (rc != BCD_HIP_OK) return rc;
     }
     // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:389-420, 470)
     if (opt && opt->zero_bad_values) HIPCHK(ctx, bcd_launch_zero_bad(d[4], (int64_t)np * 3, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(h_out, d[4], sz[4] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (nb_extra > 0) {
+        if (opt && opt->zero_bad_values) HIPCHK(ctx, bcd_launch_zero_bad(lv.out[0], (int64_t)nb_extra * np * 3, ctx->stream)); // (the outputs lie one behind the other)
+        for (int k = 0; k < nb_extra; ++k) HIPCHK(ctx, hipMemcpyAsync(extra[k].h_out, lv.out[k], np * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BCD_HIP_OK;
+}
+
+int bcd_hip_denoise_host_ex(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
+                            int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out)
+{
+    return denoise_host_impl(ctx, h_colors, h_ns, h_hist, h_cov, W, H, D, nb_scales, prm, opt, h_out, nullptr, 0);
+}
+
+int bcd_hip_denoise_layers_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                                const bcd_hip_host_options *opt, const bcd_hip_host_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!h_ns || !h_hist) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k) {
+        if (!layers[k].h_colors || !layers[k].h_covariances || !layers[k].h_out) return bad(ctx, "null image pointer in a layer");
+        for (int j = 0; j < k; ++j) if (layers[j].h_out == layers[k].h_out) return bad(ctx, "two layers share an output image");
+    }
+    if (nb_layers > 1 && opt && opt->spike_factor > 0.f) {
+        set_err(ctx, "the spike prefilter moves whole pixels by the first layer's colours: it is not available with several layers");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    return denoise_host_impl(ctx, layers[0].h_colors, h_ns, h_hist, layers[0].h_covariances, W, H, D, nb_scales, prm, opt, layers[0].h_out, layers + 1, nb_layers - 1);
 }
 
 int bcd_hip_last_upload_bytes(const bcd_hip_ctx *ctx, int64_t *hist_bytes, int64_t *hist_bytes_sent)

@@ -82,3 +82,13 @@ struct BcdBorderline {
     int *counter;      // number of appended pairs (may exceed capacity: then the host falls back to the exact kernels)
     int capacity;
 };
+
+// ---- colour layers (bcd_hip_denoise_layers) -----------------------------------------------------------
+// One launch of a layer-batched kernel serves every layer: the layer is blockIdx.y (streaming kernels) or a loop / blockIdx.z group inside
+// the kernel (tiled fallback), its device pointers travel by value in this table.  What a, b, o mean is the kernel's business.
+#define BCD_MAX_LAYERS 16
+struct BcdLayerTable {
+    const float *a[BCD_MAX_LAYERS];
+    const float *b[BCD_MAX_LAYERS];
+    float *o[BCD_MAX_LAYERS];
+};

@@ -10,6 +10,7 @@
 // the same order here.  Compiled with -ffp-contract=off; fmaf() is used explicitly where contraction is wanted.
 #include "bcd_common.h"
 #include <algorithm>
+#include <cstdlib>
 
 namespace {
 
@@ -180,7 +181,7 @@ __device__ void apply_estimate(const float *X, const float *Cinv, const float *m
             unsafeAtomicAdd(sum + (size_t)q * 3 + 0, e0);
             unsafeAtomicAdd(sum + (size_t)q * 3 + 1, e1);
             unsafeAtomicAdd(sum + (size_t)q * 3 + 2, e2);
-            atomicAdd(cnt + q, 1);
+            if (cnt) atomicAdd(cnt + q, 1);
         } else {
             Xd[i * K + 3 * o] = e0; Xd[i * K + 3 * o + 1] = e1; Xd[i * K + 3 * o + 2] = e2;
         }
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(64) void k_bayes_weak(const float *__restrict__ col
             unsafeAtomicAdd(dst, n_inv * a0);
             unsafeAtomicAdd(dst + 1, n_inv * a1);
             unsafeAtomicAdd(dst + 2, n_inv * a2);
-            atomicAdd(cnt + p + offp, 1);
+            if (cnt) atomicAdd(cnt + p + offp, 1);
         }
     }
 }
@@ -409,7 +410,7 @@ __global__ __launch_bounds__(64) void k_bayes_weak_w1(const float *__restrict__ 
 #pragma unroll
         for (int e = 0; e < 9; ++e) unsafeAtomicAdd(dst + e, n_inv * a[e]);
 #pragma unroll
-        for (int e = 0; e < 3; ++e) atomicAdd(cnt + p + offp + e, 1);
+        for (int e = 0; e < 3; ++e) if (cnt) atomicAdd(cnt + p + offp + e, 1);
     }
 }
 
@@ -561,6 +562,160 @@ __global__ __launch_bounds__(256) void k_bayes_weak_tile(const float *__restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The tiled fallback for SEVERAL colour layers that share one selection (bcd_hip_denoise_layers): the tile's fallback pixels, their (pixel, patch
+// row) pairs and every pixel's mask words are found / decoded ONCE, and each decoded member adds its patch row of G layers' colour windows to G
+// register accumulators.  The member order is the window order for every layer, so a layer's sums are those of k_bayes_weak_tile on that layer alone.
+// t.a[k]: colours of layer k, t.o[k]: its sum image; blockIdx.z takes layers [z G, z G + G).  No count image is written: the layers share the one
+// the single-layer kernel filled for the first layer (the LDS flags below only say which values of the 18 x 18 window were touched).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int G>
+__global__ __launch_bounds__(256) void k_bayes_weak_tile_layers(BcdLayerTable t, int nlayers, const uint32_t *__restrict__ mask,
+                                                                const uint8_t *__restrict__ state, const int32_t *__restrict__ nsim, int min_strong,
+                                                                BayesGeom g, int row_begin, int row_end)
+{
+    extern __shared__ float lds[];
+    constexpr int ACC = (WT + 2) * (WT + 2);
+    const int b1 = g.b + 1, TW = WT + 2 * b1, row3 = TW * 3;
+    const int WINSZ = (TW * row3 + 3) & ~3;
+    float *win = lds;                                         // G x (TW x TW x 3 colours)
+    float *accS = win + G * WINSZ;                            // G x (WT + 2)^2 x 3 sums
+    int *accC = reinterpret_cast<int *>(accS + G * ACC * 3);  // (WT + 2)^2 "touched" flags, shared by the layers
+    uint16_t *wlist = reinterpret_cast<uint16_t *>(accC + ACC);
+    __shared__ int n_weak;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tx0 = blockIdx.x * WT, ty0 = blockIdx.y * WT;
+    const int k0 = blockIdx.z * G, ng = min(G, nlayers - k0);
+    const int W = g.W, H = g.H;
+    // ---- fallback pixels of the tile (as k_bayes_weak_tile)
+    const int lx = tid & (WT - 1), ly = tid >> 4, gx = tx0 + lx, gy = ty0 + ly;
+    const bool inside = gx < W && gy < H;
+    const long long pg = (long long)gy * W + gx;
+    const bool weak = inside && gy >= row_begin && gy < row_end && state[pg] == BCD_ST_IN && nsim[pg] < min_strong;
+    if (tid == 0) n_weak = 0;
+    __syncthreads();
+    {
+        const unsigned long long bal = __ballot(weak);
+        int base = 0;
+        if (lane == 0 && bal) base = atomicAdd(&n_weak, __popcll(bal));
+        base = __shfl(base, 0);
+        if (weak) wlist[base + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)tid;
+    }
+    __syncthreads();
+    const int nw = n_weak;
+    if (nw == 0) return;                                      // (uniform)
+    // ---- the layers' colour windows (clamped addresses) and the accumulators
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        if (j < ng) {                                         // (uniform)
+            const float *__restrict__ colors = t.a[k0 + j];
+            float *wj = win + j * WINSZ;
+            for (int e = tid; e < TW * row3; e += 256) {
+                const int wy = e / row3, r = e - wy * row3, px = r / 3, ch = r - px * 3;
+                const int yy = min(max(ty0 - b1 + wy, 0), H - 1), xx = min(max(tx0 - b1 + px, 0), W - 1);
+                wj[e] = colors[((long long)yy * W + xx) * 3 + ch];
+            }
+        }
+    }
+    for (int e = tid; e < G * ACC * 3 + ACC; e += 256) accS[e] = 0.f; // (sums and flags are contiguous)
+    __syncthreads();
+    // ---- one lane per (fallback pixel, patch row); wavefront w owns the rows of the 18 x 18 window that are w mod 4, the adds go in nine turns
+    // (see k_bayes_weak_tile for why neither needs atomics)
+    uint16_t *pairs = wlist + 256 + wave * 192;
+    int npairs = 0;
+    for (int i0 = 0; i0 < nw; i0 += 64) {
+        const int i = i0 + lane;
+        int code = 0;
+        bool take = false;
+        if (i < nw) {
+            const int lp = wlist[i], tt = (wave - (lp >> 4)) & 3;
+            take = tt < 3;
+            code = lp | (tt << 8);
+        }
+        const unsigned long long bal = __ballot(take);
+        if (take) pairs[npairs + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)code;
+        npairs += __popcll(bal);
+    }
+    __syncthreads();
+    const float inv_side = 1.f / (float)g.side;
+    const int cell0 = (g.b & 15) * ((TW & 63) + 1);             // window offset (-b, -b) in cells
+    for (int base = 0; base < npairs; base += 64) {
+        const bool live = base + lane < npairs;
+        const int code = pairs[live ? base + lane : 0];
+        const int lp = code & 255, prow = code >> 8, plx = lp & (WT - 1), ply = lp >> 4;
+        float a[G][9];
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+#pragma unroll
+            for (int e = 0; e < 9; ++e) a[j][e] = 0.f;
+        if (live) {
+            const long long p = (long long)(ty0 + ply) * W + tx0 + plx;
+            const float *src = win + ((ply + b1 + prow - 1) * TW + plx + b1 - 1) * 3; // this lane's patch row of the pixel itself, first layer of the group
+            const uint32_t *mw = mask + (size_t)p * g.words;
+            int n = 0;
+            for (int w0 = 0; w0 < g.words; w0 += 6) {
+                uint32_t mreg[6];
+#pragma unroll
+                for (int u = 0; u < 6; ++u) mreg[u] = (w0 + u < g.words) ? mw[w0 + u] : 0u;
+#pragma unroll
+                for (int u = 0; u < 6; ++u) {
+                    uint32_t m = mreg[u];
+                    while (m) {
+                        const int k = (w0 + u) * 32 + __ffs(m) - 1;
+                        m &= m - 1;
+                        const int kl = (int)(((float)k + 0.5f) * inv_side) & 31, kc = k - kl * (g.side & 31); // k / side, see k_bayes_weak
+                        const int cell = kl * (TW & 63) + kc - cell0;
+                        const float *q = src + cell * 3;
+#pragma unroll
+                        for (int j = 0; j < G; ++j) {   // (windows of layers beyond ng hold whatever the LDS held: summed, never flushed)
+#pragma unroll
+                            for (int e = 0; e < 9; ++e) a[j][e] += q[j * WINSZ + e];
+                        }
+                        ++n;
+                    }
+                }
+            }
+            const float n_inv = 1.f / (float)n;
+#pragma unroll
+            for (int j = 0; j < G; ++j)
+#pragma unroll
+                for (int e = 0; e < 9; ++e) a[j][e] *= n_inv;
+        }
+        float *dS = accS + ((ply + prow) * (WT + 2) + plx) * 3;
+        int *dC = accC + (ply + prow) * (WT + 2) + plx;
+        const int turn = (plx % 3) * 3 + prow;
+#pragma unroll
+        for (int tn = 0; tn < 9; ++tn) {
+            if (live && turn == tn) {
+#pragma unroll
+                for (int j = 0; j < G; ++j)
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) dS[j * ACC * 3 + e] += a[j][e];
+            }
+            asm volatile("" ::: "memory"); // (program order of the LDS accesses)
+        }
+        if (live) { dC[0] = 1; dC[1] = 1; dC[2] = 1; } // (every writer stores the same value)
+    }
+    __syncthreads();
+    // ---- flush: one global atomic per touched value and layer
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        if (j < ng) {
+            float *sum = t.o[k0 + j];
+            const float *aj = accS + j * ACC * 3;
+            for (int e = tid; e < ACC; e += 256) {
+                if (accC[e] != 0) {
+                    const int wy = e / (WT + 2), wx = e - wy * (WT + 2);
+                    const long long q = (long long)(ty0 - 1 + wy) * W + (tx0 - 1 + wx);
+                    unsafeAtomicAdd(sum + q * 3, aj[e * 3]);
+                    unsafeAtomicAdd(sum + q * 3 + 1, aj[e * 3 + 1]);
+                    unsafeAtomicAdd(sum + q * 3 + 2, aj[e * 3 + 2]);
+                }
+            }
+        }
+    }
+}
+
 BayesGeom make_geom(int W, int H, int w, int b)
 {
     BayesGeom g;
@@ -648,5 +803,41 @@ hipError_t bcd_launch_bayes_weak(const float *colors, const uint32_t *mask, cons
     if (g.words > 32) return hipErrorInvalidValue;
     if (w == 1) hipLaunchKernelGGL(k_bayes_weak_w1, dim3(blocks), dim3(64), 0, st, colors, mask, list, d_nlist, g, sum, cnt);
     else hipLaunchKernelGGL(k_bayes_weak, dim3(blocks), dim3(64), 0, st, colors, mask, list, d_nlist, g, sum, cnt);
+    return hipGetLastError();
+}
+
+// LDS of the layered tiled fallback kernel with G layers per workgroup
+static size_t weak_tile_layers_lds(int b, int G)
+{
+    const int TW = WT + 2 * (b + 1);
+    return ((size_t)G * ((TW * TW * 3 + 3) & ~3) + (size_t)G * (WT + 2) * (WT + 2) * 3 + (size_t)(WT + 2) * (WT + 2)) * 4 + (256 + 4 * 192) * sizeof(uint16_t);
+}
+
+// layers per workgroup of the layered tiled fallback kernel for `layers` layers: as many as fit 64 KiB of LDS, four at most (36 accumulators per lane)
+int bcd_bayes_weak_tiles_layers_group(int layers, int b)
+{
+    static const int cap = [] { const char *e = getenv("BCD_HIP_WEAK_LAYERS_GROUP"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4 ? v : 4; }(); // (A/B)
+    int G = std::min(cap, layers);
+    while (G > 1 && weak_tile_layers_lds(b, G) > 64 * 1024) --G;
+    return G;
+}
+
+// the tiled fallback kernel over `layers` colour layers with one selection (3 x 3 patches); t.a: colours, t.o: sums; no counts
+hipError_t bcd_launch_bayes_weak_tiles_layers(const BcdLayerTable &t, int layers, const uint32_t *mask, const uint8_t *state, const int32_t *nsim, int min_strong,
+                                              int W, int H, int b, hipStream_t st, int row_begin, int row_end)
+{
+    if (layers < 1 || layers > BCD_MAX_LAYERS) return hipErrorInvalidValue;
+    BayesGeom g = make_geom(W, H, 1, b);
+    if (g.words > 32) return hipErrorInvalidValue;
+    const int G = bcd_bayes_weak_tiles_layers_group(layers, b);
+    const size_t lds = weak_tile_layers_lds(b, G);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    const dim3 grid((W + WT - 1) / WT, (H + WT - 1) / WT, (layers + G - 1) / G);
+    switch (G) {
+    case 1: hipLaunchKernelGGL(k_bayes_weak_tile_layers<1>, grid, dim3(256), lds, st, t, layers, mask, state, nsim, min_strong, g, row_begin, row_end); break;
+    case 2: hipLaunchKernelGGL(k_bayes_weak_tile_layers<2>, grid, dim3(256), lds, st, t, layers, mask, state, nsim, min_strong, g, row_begin, row_end); break;
+    case 3: hipLaunchKernelGGL(k_bayes_weak_tile_layers<3>, grid, dim3(256), lds, st, t, layers, mask, state, nsim, min_strong, g, row_begin, row_end); break;
+    default: hipLaunchKernelGGL(k_bayes_weak_tile_layers<4>, grid, dim3(256), lds, st, t, layers, mask, state, nsim, min_strong, g, row_begin, row_end); break;
+    }
     return hipGetLastError();
 }

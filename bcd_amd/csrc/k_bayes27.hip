@@ -1058,7 +1058,7 @@ __device__ __attribute__((noinline)) void final_chunk27(const float *Cm, const f
                         } else {
                             const int q = q0 + oy * W + ox;
                             unsafeAtomicAdd(sum + (size_t)q * 3 + ch, v);
-                            if (ch == 0) atomicAdd(cnt + q, 1);
+                            if (ch == 0 && cnt) atomicAdd(cnt + q, 1);
                         }
                     }
                 }
@@ -1228,7 +1228,7 @@ __global__ __launch_bounds__(64) void k_bayes27(const float *__restrict__ colors
         }
         for (int e = lane; e < AW * AW; e += 64) {
             int wy = e / AW, wx = e - wy * AW, c = accC[e];
-            if (c != 0) atomicAdd(cnt + (base + (long long)wy * W + wx), c);
+            if (c != 0 && cnt) atomicAdd(cnt + (base + (long long)wy * W + wx), c);
         }
     }
     __syncthreads(); // the next item reuses the LDS
@@ -1735,7 +1735,7 @@ __global__ __launch_bounds__(64, PHASE == 1 ? 5 : 3) void k_bayes27w(const float
         }
         for (int e = lane; e < WPIX; e += 64) {
             int wy = e / WAW, wx = e - wy * WAW, c = accC[e];
-            if (c != 0) atomicAdd(cnt + (base + (long long)wy * W + wx), c);
+            if (c != 0 && cnt) atomicAdd(cnt + (base + (long long)wy * W + wx), c);
         }
     }
     __syncthreads(); // the next item reuses the LDS
@@ -1995,7 +1995,7 @@ __global__ __launch_bounds__(64, 3) void k_finish27w(const float *__restrict__ c
             }
             for (int e = lane; e < PIX; e += 64) {
                 int wy = e / AW, wx = e - wy * AW, c = accC[e];
-                if (c != 0) atomicAdd(cnt + (base + (long long)wy * W + wx), c);
+                if (c != 0 && cnt) atomicAdd(cnt + (base + (long long)wy * W + wx), c);
             }
         }
         __syncthreads(); // the next item reuses the LDS

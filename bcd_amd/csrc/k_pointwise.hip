@@ -397,6 +397,94 @@ __global__ __launch_bounds__(64) void k_accumulate_samples(const float *__restri
     for (int k = 0; k < D; ++k) ohist[p * D + k] = lds_h[k * 64 + t];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Layer-batched forms (bcd_hip_denoise_layers): ONE launch serves every extra colour layer of a scale -- blockIdx.y is the layer, its device
+// pointers come from the table.  Per value these are the expressions of the single-image kernels above (k_pixel_cov_clear2, k_finalize_px,
+// k_downscale_px<1>, k_downscale_cov_px, k_merge_px), so a layer's result does not depend on how it was launched.  No count image is cleared or
+// written: the layers share the one of the first layer.
+// ---------------------------------------------------------------------------------------------------------------------
+// t.a: sample covariances; the per-pixel covariances and the sums of the layers lie one behind the other in the workspace (npix x 6, npix x 3 each)
+__global__ __launch_bounds__(256) void k_layers_pixel_cov_clear(BcdLayerTable t, const float *__restrict__ ns, uint32_t npix, float *__restrict__ pixcov,
+                                                                float *__restrict__ sum)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const size_t k = blockIdx.y;
+    const float inv = 1.f / ns[i];
+    const float *src = t.a[k] + 6 * (size_t)i;
+    float *dst = pixcov + (k * npix + i) * 6;
+#pragma unroll
+    for (int z = 0; z < 6; ++z) dst[z] = src[z] * inv;
+    float *s3 = sum + (k * npix + i) * 3;
+    s3[0] = 0.f; s3[1] = 0.f; s3[2] = 0.f;
+}
+// t.a: the layer's sum image, t.o: its output; cnt: the shared count image
+__global__ __launch_bounds__(256) void k_layers_finalize(BcdLayerTable t, const int32_t *__restrict__ cnt, uint32_t npix)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const int k = blockIdx.y;
+    const float inv = 1.f / (float)cnt[i];
+    const float *s3 = t.a[k] + 3 * (size_t)i;
+    float *o3 = t.o[k] + 3 * (size_t)i;
+    o3[0] = inv * s3[0]; o3[1] = inv * s3[1]; o3[2] = inv * s3[2];
+}
+// t.a: W x H x 3 image, t.o: its (W / 2) x (H / 2) average
+__global__ __launch_bounds__(256) void k_layers_downscale_avg(BcdLayerTable t, int W, int H, uint32_t npix2)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix2) return;
+    const float *in = t.a[blockIdx.y];
+    float *out = t.o[blockIdx.y];
+    const uint32_t w2 = (uint32_t)W / 2u;
+    const int l = (int)(i / w2), c = (int)(i - (uint32_t)l * w2);
+    size_t p[4];
+    block_pos(W, H, l, c, p);
+#pragma unroll
+    for (int z = 0; z < 3; ++z) {
+        const float v = in[p[0] * 3 + z] + in[p[1] * 3 + z] + in[p[2] * 3 + z] + in[p[3] * 3 + z];
+        out[(size_t)i * 3 + z] = 0.25f * v;
+    }
+}
+// t.a: sample covariances of the fine level, t.o: those of the coarse level, weighted by the shared sample counts
+__global__ __launch_bounds__(256) void k_layers_downscale_cov(BcdLayerTable t, const float *__restrict__ ns, int W, int H, uint32_t npix2)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix2) return;
+    const float *cov = t.a[blockIdx.y];
+    float *out = t.o[blockIdx.y];
+    const uint32_t w2 = (uint32_t)W / 2u;
+    const int l = (int)(i / w2), c = (int)(i - (uint32_t)l * w2);
+    size_t p[4];
+    block_pos(W, H, l, c, p);
+    const float sq = (1.f / 4.f) * (1.f / 4.f);
+    const float n1 = ns[p[0]], n2 = ns[p[1]], n3 = ns[p[2]], n4 = ns[p[3]];
+    const float nsum = n1 + n2 + n3 + n4;
+    const float w1 = sq * nsum / n1, w2_ = sq * nsum / n2, w3 = sq * nsum / n3, w4 = sq * nsum / n4;
+#pragma unroll
+    for (int z = 0; z < 6; ++z)
+        out[(size_t)i * 6 + z] = w1 * cov[p[0] * 6 + z] + w2_ * cov[p[1] * 6 + z] + w3 * cov[p[2] * 6 + z] + w4 * cov[p[3] * 6 + z];
+}
+// mergeOutputs: t.o (fine output, W x H x 3) = (t.o - up(t.a)) + up(t.b), t.a = down(t.o) made by k_layers_downscale_avg, t.b = the coarser output
+__global__ __launch_bounds__(256) void k_layers_merge(BcdLayerTable t, int w, int h, int W, uint32_t npix)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const float *a = t.a[blockIdx.y], *b = t.b[blockIdx.y];
+    float *hi = t.o[blockIdx.y];
+    const int ul = (int)(i / (uint32_t)W), uc = (int)(i - (uint32_t)ul * (uint32_t)W);
+    uint32_t q[4];
+    interp_pos(ul, uc, w, h, q);
+#pragma unroll
+    for (int z = 0; z < 3; ++z) {
+        float *dst = hi + (size_t)i * 3 + z;
+        float r = *dst;
+        r -= interp_value(a, q, 3, z);
+        r += interp_value(b, q, 3, z);
+        *dst = r;
+    }
+}
+
 inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 } // namespace
@@ -528,5 +616,42 @@ hipError_t bcd_launch_accumulate_samples(const float *samples, const float *weig
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_accumulate_samples, dim3(nblk(npix, 64)), dim3(64), lds, st, samples, weights, npix, spp, nbins, gamma, maxval, ons, omean, ocov, ohist);
+    return hipGetLastError();
+}
+
+// ---- layer-batched launchers: `layers` >= 1 entries of the table are used; the frames are smaller than 2^31 pixels (check_params)
+hipError_t bcd_launch_layers_pixel_cov_clear(const BcdLayerTable &t, int layers, const float *ns, int64_t npix, float *pixcov, float *sum, hipStream_t st)
+{
+    if (layers < 1 || layers > BCD_MAX_LAYERS || npix <= 0 || npix >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_layers_pixel_cov_clear, dim3(nblk(npix, 256), layers), dim3(256), 0, st, t, ns, (uint32_t)npix, pixcov, sum);
+    return hipGetLastError();
+}
+hipError_t bcd_launch_layers_finalize(const BcdLayerTable &t, int layers, const int32_t *cnt, int64_t npix, hipStream_t st)
+{
+    if (layers < 1 || layers > BCD_MAX_LAYERS || npix <= 0 || npix >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_layers_finalize, dim3(nblk(npix, 256), layers), dim3(256), 0, st, t, cnt, (uint32_t)npix);
+    return hipGetLastError();
+}
+hipError_t bcd_launch_layers_downscale_avg(const BcdLayerTable &t, int layers, int W, int H, hipStream_t st)
+{
+    const int64_t n2 = (int64_t)(W / 2) * (H / 2);
+    if (layers < 1 || layers > BCD_MAX_LAYERS || n2 >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    if (n2 <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_layers_downscale_avg, dim3(nblk(n2, 256), layers), dim3(256), 0, st, t, W, H, (uint32_t)n2);
+    return hipGetLastError();
+}
+hipError_t bcd_launch_layers_downscale_cov(const BcdLayerTable &t, int layers, const float *ns, int W, int H, hipStream_t st)
+{
+    const int64_t n2 = (int64_t)(W / 2) * (H / 2);
+    if (layers < 1 || layers > BCD_MAX_LAYERS || n2 >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    if (n2 <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_layers_downscale_cov, dim3(nblk(n2, 256), layers), dim3(256), 0, st, t, ns, W, H, (uint32_t)n2);
+    return hipGetLastError();
+}
+hipError_t bcd_launch_layers_merge(const BcdLayerTable &t, int layers, int w, int h, int W, int H, hipStream_t st)
+{
+    const int64_t n = (int64_t)W * H;
+    if (layers < 1 || layers > BCD_MAX_LAYERS || n <= 0 || n >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_layers_merge, dim3(nblk(n, 256), layers), dim3(256), 0, st, t, w, h, W, (uint32_t)n);
     return hipGetLastError();
 }

@@ -17,6 +17,14 @@ class Params(C.Structure):
                 ("marked_skip_probability", C.c_float), ("order_seed", C.c_uint32)]
 
 
+MAX_LAYERS = 16  # BCD_HIP_MAX_LAYERS
+
+
+class Layer(C.Structure):
+    """bcd_hip_layer"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p), ("d_out", C.c_void_p)]
+
+
 class BandJob(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p),
                 ("W", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("main_row_begin", C.c_int32), ("main_row_end", C.c_int32),
@@ -142,7 +150,7 @@ class ScaleStats(C.Structure):
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
     "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
-    "bcd_hip_denoise", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
+    "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
     "bcd_hip_multi_unique_id", "bcd_hip_multi_rccl_info", "bcd_hip_multi_create_rank", "bcd_hip_multi_rank_configure", "bcd_hip_multi_rank_upload", "bcd_hip_multi_rank_step",
     "bcd_hip_multi_rank_download", "bcd_hip_multi_rank_renew_ids", "bcd_hip_multi_set_loopback", "bcd_hip_multi_selftest_transport",
@@ -237,6 +245,35 @@ class Context:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=hist.device)
         self._chk(lib().bcd_hip_denoise(self.h, _dp(col), _dp(ns), _dp(hist), _dp(cov), W, H, D, nscales, C.byref(prm), _dp(out)))
         return out
+
+    def denoise_layers(self, ns, hist, layers, nscales, prm, outs=None):
+        """bcd_hip_denoise_layers: `layers` is a list of (colours, covariances) tensors that share `ns` and `hist`; one selection of similar patches
+        serves them all.  Returns the list of outputs (`outs`: tensors to write into, optional)."""
+        torch = self.torch
+        H, W, D = hist.shape
+        layers = list(layers)
+        if outs is None:
+            outs = [torch.empty((H, W, 3), dtype=torch.float32, device=hist.device) for _ in layers]
+        outs = list(outs)
+        if len(outs) != len(layers):
+            raise ValueError("one output per layer expected")
+        arr = (Layer * max(1, len(layers)))()
+        for k, ((col, cov), out) in enumerate(zip(layers, outs)):
+            if tuple(col.shape) != (H, W, 3) or tuple(cov.shape) != (H, W, 6) or tuple(out.shape) != (H, W, 3):
+                raise ValueError("layer %d: colours / output must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
+            arr[k].d_colors, arr[k].d_covariances, arr[k].d_out = _dp(col).value, _dp(cov).value, _dp(out).value
+        L = lib()
+        L.bcd_hip_denoise_layers.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Layer), C.c_int]
+        self._chk(L.bcd_hip_denoise_layers(self.h, _dp(ns), _dp(hist), W, H, D, nscales, C.byref(prm), arr, len(layers)))
+        return outs
+
+    def layer_spectral_inverses(self, scale, layer):
+        """full estimates of one layer of the last denoise_layers call that took the spectral inverse (stats().spectral_inverses is their sum)"""
+        n = C.c_int32(0)
+        L = lib()
+        L.bcd_hip_layer_spectral_inverses.argtypes = [_VP, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        self._chk(L.bcd_hip_layer_spectral_inverses(self.h, scale, layer, C.byref(n)))
+        return n.value
 
     def denoise_begin(self, col, ns, hist, cov, nscales, prm, out):
         """bcd_hip_denoise_begin: returns at once; the tensors must stay alive and untouched until denoise_wait()"""

@@ -66,6 +66,56 @@ namespace bcd
 		return true;
 	}
 
+	bool Denoiser::layersAreOk()
+	{
+		if(m_layers.empty())
+			return true;
+		if(m_layers.size() > size_t(BCD_HIP_MAX_LAYERS - 1))
+		{
+			cerr << "Aborting denoising: " << m_layers.size() << " added colour layers, at most " << (BCD_HIP_MAX_LAYERS - 1) << " are supported" << endl;
+			return false;
+		}
+		if(m_devices.size() > 1)
+		{
+			cerr << "Aborting denoising: colour layers are not available over several devices (row bands take one layer per call)" << endl;
+			return false;
+		}
+		if(m_prefilterThresholdStDevFactor > 0.f)
+		{
+			cerr << "Aborting denoising: the spike prefilter moves whole pixels by the primary colours and is not available with added colour layers" << endl;
+			return false;
+		}
+		const int w = m_inputs.m_pColors->getWidth(), h = m_inputs.m_pColors->getHeight();
+		for(size_t k = 0; k < m_layers.size(); ++k)
+		{
+			const ColorLayer& rLayer = m_layers[k];
+			if(!rLayer.m_pColors || !rLayer.m_pSampleCovariances || !rLayer.m_pDenoisedColors)
+			{
+				cerr << "Aborting denoising: nullptr for an image of added colour layer " << k + 1 << endl;
+				return false;
+			}
+			if(rLayer.m_pColors->getWidth() != w || rLayer.m_pColors->getHeight() != h || rLayer.m_pColors->getDepth() != 3 ||
+					rLayer.m_pSampleCovariances->getWidth() != w || rLayer.m_pSampleCovariances->getHeight() != h || rLayer.m_pSampleCovariances->getDepth() != 6)
+			{
+				cerr << "Aborting denoising: added colour layer " << k + 1 << " must bring a " << w << "x" << h << "x3 color image and a "
+						<< w << "x" << h << "x6 covariance image like the primary inputs" << endl;
+				return false;
+			}
+			if(rLayer.m_pDenoisedColors == m_outputs.m_pDenoisedColors)
+			{
+				cerr << "Aborting denoising: added colour layer " << k + 1 << " writes into the primary output image" << endl;
+				return false;
+			}
+			for(size_t j = 0; j < k; ++j)
+				if(m_layers[j].m_pDenoisedColors == rLayer.m_pDenoisedColors)
+				{
+					cerr << "Aborting denoising: added colour layers " << j + 1 << " and " << k + 1 << " share an output image" << endl;
+					return false;
+				}
+		}
+		return true;
+	}
+
 	namespace
 	{
 		/// Engine handles are kept for the life of the process, one per device (and one per device list): workspace, pyramid
@@ -117,7 +167,7 @@ namespace bcd
 
 	bool Denoiser::denoiseWithNbOfScales(int i_nbOfScales)
 	{
-		if(!inputsOutputsAreOk())
+		if(!inputsOutputsAreOk() || !layersAreOk())
 			return false;
 		m_width = m_inputs.m_pColors->getWidth();
 		m_height = m_inputs.m_pColors->getHeight();
@@ -172,6 +222,7 @@ namespace bcd
 		std::lock_guard<std::mutex> lock(rSlot.m_mutex);
 		m_progressCallback(0.f);
 		Deepimf result(m_width, m_height, 3); // inputs may alias the output image (the CLI pre-copies colours into it)
+		std::vector<Deepimf> layerResults(m_layers.size());
 		const float* pIn[4] = { m_inputs.m_pColors->getDataPtr(), m_inputs.m_pNbOfSamples->getDataPtr(), m_inputs.m_pHistograms->getDataPtr(),
 				m_inputs.m_pSampleCovariances->getDataPtr() };
 		const int depth = m_inputs.m_pHistograms->getDepth();
@@ -227,7 +278,21 @@ namespace bcd
 			bcd_hip_host_options opt;
 			opt.spike_factor = m_prefilterThresholdStDevFactor;
 			opt.zero_bad_values = m_zeroBadOutputValues ? 1 : 0;
-			rc = bcd_hip_denoise_host_ex(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], m_width, m_height, depth, i_nbOfScales, &prm, &opt, result.getDataPtr());
+			if(m_layers.empty())
+				rc = bcd_hip_denoise_host_ex(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], m_width, m_height, depth, i_nbOfScales, &prm, &opt, result.getDataPtr());
+			else
+			{	// the primary images are layer 0: one selection of similar patches serves every layer
+				std::vector<bcd_hip_host_layer> layers(m_layers.size() + 1);
+				layers[0].h_colors = pIn[0]; layers[0].h_covariances = pIn[3]; layers[0].h_out = result.getDataPtr();
+				for(size_t k = 0; k < m_layers.size(); ++k)
+				{
+					layerResults[k].resize(m_width, m_height, 3);
+					layers[k + 1].h_colors = m_layers[k].m_pColors->getDataPtr();
+					layers[k + 1].h_covariances = m_layers[k].m_pSampleCovariances->getDataPtr();
+					layers[k + 1].h_out = layerResults[k].getDataPtr();
+				}
+				rc = bcd_hip_denoise_layers_host(rSlot.m_pCtx, pIn[1], pIn[2], m_width, m_height, depth, i_nbOfScales, &prm, &opt, layers.data(), int(layers.size()));
+			}
 			bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
 			if(rc != BCD_HIP_OK)
 			{
@@ -242,6 +307,8 @@ namespace bcd
 		if(rc != BCD_HIP_OK)
 			return false;
 		*m_outputs.m_pDenoisedColors = std::move(result); // resized to W x H x 3 and overwritten (Denoiser.cpp:207-208)
+		for(size_t k = 0; k < m_layers.size(); ++k)
+			*m_layers[k].m_pDenoisedColors = std::move(layerResults[k]);
 		m_progressCallback(1.f);
 		return true;
 	}
@@ -269,6 +336,7 @@ namespace bcd
 		engine.setDevices(m_devices);
 		engine.setSpikePrefilter(m_prefilterThresholdStDevFactor);
 		engine.setZeroBadOutputValues(m_zeroBadOutputValues);
+		engine.setLayers(m_layers);
 		const bool ok = engine.denoiseWithNbOfScales(m_nbOfScales);
 		m_parameters.m_nbOfCores = engine.getParameters().m_nbOfCores;
 		return ok;

@@ -4,6 +4,7 @@
 // inferred as <input>_hist.exr / <input>_cov.exr (:344-370).  Extra flags of this build: --seed <n> (visiting
 // order), --device <n>.  --ncores only selects the visiting order (n > 1 with -r 0: the reference's strip list; the loop runs on the HIP device); --use-cuda 0 (a request for the CPU path this
 // build does not have) is declined with a note and served by the device; under BCD_STRICT_CPU_REQUEST=1 it is refused with an error before any file is read.
+// --layer <color.exr> <cov.exr> <out.exr> (repeatable) denoises a further colour layer with the filter of the -i image (one selection of similar patches for all).
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
 #include "Chronometer.h"
 #include "DeepImage.h"
@@ -45,6 +46,8 @@ namespace
 		bool m_useCuda = true;
 		unsigned m_orderSeed = 1234u;
 		std::vector<int> m_devices = std::vector<int>(1, 0);
+		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
+		std::vector<Layer> m_layers; // --layer, in command-line order
 	};
 
 	const char* g_pProgramPath = "bcd_cli";
@@ -76,6 +79,10 @@ namespace
 		cout << "    --seed <int>         Seed of the random pixel order (default: " << d.m_orderSeed << ")" << endl;
 		cout << "    --device <int>       HIP device index (default: 0)" << endl;
 		cout << "    --devices <list>     several HIP devices, e.g. 0-7 or 0,2,4: the frame is split into row bands (RCCL halo exchange)" << endl;
+		cout << "    --layer <color> <cov> <output>" << endl;
+		cout << "                         a further colour layer (light group, diffuse / specular pass, ...) of the same render: its mean colours and" << endl;
+		cout << "                         sample covariances, denoised with the similar patches of the -i image and written to <output>; repeatable" << endl;
+		cout << "                         (at most 15), shares -h; needs -p 0 and a single device" << endl;
 	}
 
 	bool badValue(const char* flag, const char* what)
@@ -92,6 +99,17 @@ namespace
 		{
 			const string flag = argv[i];
 			if(flag == "--help") { printUsage(); return false; }
+			if(flag == "--layer")
+			{
+				if(i + 3 >= argc) { cout << "ERROR in program arguments: expecting <color.exr> <cov.exr> <output.exr> after --layer" << endl; return false; }
+				a.m_layers.emplace_back();
+				ProgramArguments::Layer& rLayer = a.m_layers.back();
+				rLayer.m_colorPath = argv[i + 1]; rLayer.m_covariancePath = argv[i + 2]; rLayer.m_outputPath = argv[i + 3];
+				i += 3;
+				if(!ImageIO::loadEXR(rLayer.m_colorImage, rLayer.m_colorPath.c_str())) { cout << "ERROR in program arguments: couldn't load layer color image file '" << rLayer.m_colorPath << "'" << endl; return false; }
+				if(!ImageIO::loadMultiChannelsEXR(rLayer.m_covarianceImage, rLayer.m_covariancePath.c_str())) { cout << "ERROR in program arguments: couldn't load layer covariance matrix image file '" << rLayer.m_covariancePath << "'" << endl; return false; }
+				continue;
+			}
 			if(i + 1 >= argc) { cout << "ERROR in program arguments: expecting a value after " << flag << endl; return false; }
 			const char* value = argv[++i];
 			if(flag == "-o") { a.m_denoisedOutputFilePath = value; missingOutput = false; }
@@ -214,6 +232,38 @@ namespace
 			printUsage();
 			return false;
 		}
+		// the layers share the geometry of the -i image (checked here: nothing has touched a device yet)
+		if(a.m_layers.size() > 15) { cout << "ERROR in program arguments: at most 15 --layer arguments are supported" << endl; return false; }
+		for(ProgramArguments::Layer& rLayer : a.m_layers)
+		{
+			if(rLayer.m_colorImage.getDepth() == 1)
+			{	// grey colour file, as for -i
+				Deepimf rgb(rLayer.m_colorImage.getWidth(), rLayer.m_colorImage.getHeight(), 3);
+				for(int i = 0, n = rLayer.m_colorImage.getSize(); i < n; ++i)
+					rgb.get(3 * i) = rgb.get(3 * i + 1) = rgb.get(3 * i + 2) = rLayer.m_colorImage.get(i);
+				rLayer.m_colorImage = std::move(rgb);
+			}
+			const int w = a.m_colorImage.getWidth(), h = a.m_colorImage.getHeight();
+			if(rLayer.m_colorImage.getWidth() != w || rLayer.m_colorImage.getHeight() != h || rLayer.m_colorImage.getDepth() != 3)
+			{
+				cout << "ERROR in program arguments: layer color image '" << rLayer.m_colorPath << "' is " << rLayer.m_colorImage.getWidth() << "x" << rLayer.m_colorImage.getHeight()
+						<< "x" << rLayer.m_colorImage.getDepth() << " but the input color image is " << w << "x" << h << endl;
+				return false;
+			}
+			if(rLayer.m_covarianceImage.getWidth() != w || rLayer.m_covarianceImage.getHeight() != h || rLayer.m_covarianceImage.getDepth() != 6)
+			{
+				cout << "ERROR in program arguments: layer covariance image '" << rLayer.m_covariancePath << "' is " << rLayer.m_covarianceImage.getWidth() << "x"
+						<< rLayer.m_covarianceImage.getHeight() << "x" << rLayer.m_covarianceImage.getDepth() << " but " << w << "x" << h << "x6 is expected" << endl;
+				return false;
+			}
+			if(rLayer.m_outputPath == a.m_denoisedOutputFilePath) { cout << "ERROR in program arguments: layer output '" << rLayer.m_outputPath << "' is also the -o output" << endl; return false; }
+		}
+		if(!a.m_layers.empty() && a.m_prefilterSpikes)
+		{
+			cout << "ERROR in program arguments: --layer is not available with the spike prefilter (it moves whole pixels by the -i colours): add -p 0" << endl;
+			return false;
+		}
+		if(!a.m_layers.empty() && a.m_devices.size() > 1) { cout << "ERROR in program arguments: --layer is not available with several devices" << endl; return false; }
 		return true;
 	}
 
@@ -284,6 +334,9 @@ namespace
 		if(prefilterOnDevice)
 			pSettings->setSpikePrefilter(args.m_prefilterThresholdStDevFactor);
 		pSettings->setZeroBadOutputValues(true); // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:470) before the download
+		std::vector<Deepimf> layerOutputs(args.m_layers.size());
+		for(size_t k = 0; k < args.m_layers.size(); ++k)
+			pSettings->addLayer(&args.m_layers[k].m_colorImage, &args.m_layers[k].m_covarianceImage, &layerOutputs[k]);
 		uDenoiser->setInputs(inputs);
 		uDenoiser->setOutputs(outputs);
 		uDenoiser->setParameters(parameters);
@@ -297,6 +350,16 @@ namespace
 			return 3;
 		}
 		cout << "Written denoised output in file " << args.m_denoisedOutputFilePath << endl;
+		for(size_t k = 0; k < args.m_layers.size(); ++k)
+		{	// the same last line of defence and the same writer as the main output
+			checkAndPutToZeroNegativeInfNaNValues(layerOutputs[k]);
+			if(!ImageIO::writeEXR(layerOutputs[k], args.m_layers[k].m_outputPath.c_str()))
+			{
+				cerr << "Couldn't write " << args.m_layers[k].m_outputPath << ": " << ImageIO::lastError() << endl;
+				return 3;
+			}
+			cout << "Written denoised layer " << k + 1 << " in file " << args.m_layers[k].m_outputPath << endl;
+		}
 		return 0;
 	}
 

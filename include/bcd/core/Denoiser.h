@@ -33,11 +33,32 @@ namespace bcd
 		/// put negative / infinite / NaN output values to zero on the device (src/cli/main.cpp:389-420)
 		void setZeroBadOutputValues(bool i_enabled) { m_zeroBadOutputValues = i_enabled; }
 
+		/// A further colour layer (light group, diffuse / specular / ... pass) denoised WITH THE FILTER OF THE PRIMARY INPUTS: same similar
+		/// patches, same processed pixels, one selection for all layers (bcd_hip_denoise_layers).  The DenoiserInputs colour and covariance
+		/// images are layer 0; every added layer brings its own mean colours (W x H x 3) and sample covariances (W x H x 6) and shares the
+		/// sample counts and histograms.  Non-owning pointers, like DenoiserInputs; the output is resized and overwritten.  At most
+		/// 15 added layers, one device, no spike prefilter.  With no added layer denoise() is what it always was.
+		struct ColorLayer
+		{
+			const DeepImage<float>* m_pColors;
+			const DeepImage<float>* m_pSampleCovariances;
+			DeepImage<float>* m_pDenoisedColors;
+		};
+		void addLayer(const DeepImage<float>* i_pColors, const DeepImage<float>* i_pSampleCovariances, DeepImage<float>* o_pDenoisedColors)
+		{
+			ColorLayer layer = { i_pColors, i_pSampleCovariances, o_pDenoisedColors };
+			m_layers.push_back(layer);
+		}
+		void clearLayers() { m_layers.clear(); }
+		const std::vector<ColorLayer>& getLayers() const { return m_layers; }
+		void setLayers(const std::vector<ColorLayer>& i_rLayers) { m_layers = i_rLayers; }
+
 	protected:
 		uint32_t m_orderSeed;
 		std::vector<int> m_devices;
 		float m_prefilterThresholdStDevFactor;
 		bool m_zeroBadOutputValues;
+		std::vector<ColorLayer> m_layers;
 	};
 
 	/// The engine contexts behind denoise() (device workspaces, pyramids, staging buffers: grow-only, sized by the largest frame seen,
@@ -57,6 +78,8 @@ namespace bcd
 
 		/// null / empty / size-mismatch checks of the reference (src/core/Denoiser.cpp:238-348); prints to cerr
 		bool inputsOutputsAreOk();
+		/// the same for the added colour layers (sizes against the primary colour image)
+		bool layersAreOk();
 
 		int getImagesWidth() const { return m_width; }
 		int getImagesHeight() const { return m_height; }

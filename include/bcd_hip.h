@@ -124,6 +124,25 @@ int bcd_hip_denoise_begin(bcd_hip_ctx *ctx, const float *d_colors, const float *
                           int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out);
 int bcd_hip_denoise_wait(bcd_hip_ctx *ctx);
 
+/* ---- several colour layers, one similar-patch selection -----------------------------------------
+ * A renderer's beauty image plus its light groups / diffuse / specular / ... layers, denoised with ONE filter: the similar sets, |S|, the marking,
+ * the processed / fallback lists and the count image depend only on the histograms, the sample counts and the visiting order, so they are computed
+ * once per scale; only the estimate stage runs per layer.  Layer k of the result is what
+ *     bcd_hip_denoise(ctx, layers[k].d_colors, d_nsamples, d_histograms, layers[k].d_covariances, ..., layers[k].d_out)
+ * returns with the same parameters (same arithmetic; the float atomics of the aggregation may arrive in another order), at far less than the cost of
+ * nb_layers such calls, and without a histogram image per layer.  Layer 0 goes through the code path of bcd_hip_denoise.
+ *   d_colors, d_out: W*H*3 floats, d_covariances: W*H*6 floats, all device pointers; 1 <= nb_layers <= BCD_HIP_MAX_LAYERS.
+ * Every argument is checked before any device work: a null pointer, a layer count out of range, an output that is (or overlaps) an input or another
+ * output, or a geometry bcd_hip_denoise refuses give BCD_HIP_EINVAL / BCD_HIP_EUNSUPPORTED and a message.
+ * bcd_hip_get_stats describes the shared selection; spectral_inverses is the SUM over the layers (acceptance of a sweep inverse depends on the layer's
+ * matrices), bcd_hip_layer_spectral_inverses gives one layer's share.  Row bands and bcd_hip_multi_* take one layer per call. */
+#define BCD_HIP_MAX_LAYERS 16
+typedef struct { const float *d_colors; const float *d_covariances; float *d_out; } bcd_hip_layer;
+int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms, int W, int H, int D, int nb_scales,
+                           const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers);
+/* full estimates of `layer` at `scale` of the last bcd_hip_denoise_layers call whose sweep inverse failed its checks (see bcd_hip_scale_stats) */
+int bcd_hip_layer_spectral_inverses(const bcd_hip_ctx *ctx, int scale, int layer, int32_t *count);
+
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
  * finalised colours the raw accumulators are returned (d_sum W*H*3 floats, d_count W*H int32), so
@@ -226,6 +245,12 @@ typedef struct bcd_hip_host_options {
 int bcd_hip_denoise_host_ex(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples,
                             const float *h_histograms, const float *h_covariances,
                             int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out);
+/* bcd_hip_denoise_layers for host images (layers[0] is the primary layer: its images and the shared inputs travel like those of
+ * bcd_hip_denoise_host_ex, the other layers as plain copies).  opt->zero_bad_values applies to every output; the spike prefilter moves whole pixels
+ * by the first layer's colours and is refused (BCD_HIP_EUNSUPPORTED) with more than one layer. */
+typedef struct { const float *h_colors; const float *h_covariances; float *h_out; } bcd_hip_host_layer;
+int bcd_hip_denoise_layers_host(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, int W, int H, int D, int nb_scales,
+                                const bcd_hip_params *prm, const bcd_hip_host_options *opt, const bcd_hip_host_layer *layers, int nb_layers);
 
 /* The histogram image of the last bcd_hip_denoise_host(_ex) call: its size, and the bytes that crossed the link.  On frames of >= 256 lines the
  * image travels without its zeros -- host threads pack every piece into one bit per value ("is not +0.0f", a test on the bit pattern: lossless)
