@@ -748,30 +748,30 @@ float stage_ms(Work &wk, int a, int b)
 // layer over the same item list and work queues with that layer's colours and covariances -- its 9.9 KB records are reused from layer to layer, its redo
 // list (items whose sweep inverse failed ITS matrices' checks) is walked behind each layer's finish kernel.  No kernel gets the count image: it is the
 // first layer's.  One launch finalises every layer.
-int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int scale)
+// d_mask / d_nsim / d_state: the selection (a frame: the workspace's); pixcov[k] / sum[k]: per-pixel covariances and (cleared) sums of extra layer k (a frame:
+// slices of wk.lay_pixcov / wk.lay_sum); spectral[1 + E]: per layer, the items that took the redo list; lv.out[k] null for every k (the stage-level entry
+// point): the sums are left as they are, nothing is finalised.
+int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state,
+                  const float *const *pixcov, float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral)
 {
     const int E = lv.n;
     const int64_t npix = (int64_t)W * H;
     const int K = 3 * (2 * w + 1) * (2 * w + 1);
-    float *pixcov = (float *)wk.lay_pixcov.p, *sum = (float *)wk.lay_sum.p;
     int32_t *d_c = (int32_t *)wk.counters.p + 16;
     const int n_strong = wk.h_counters[16];
-    int32_t *spectral = ctx->layer_spectral[scale < MAX_SCALES ? scale : MAX_SCALES - 1];
     spectral[0] = wk.h_counters[23];
-    const uint32_t *d_mask = (const uint32_t *)wk.mask.p;
-    const int32_t *d_nsim = (const int32_t *)wk.nsim.p;
     int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100); // (as bayes())
     if (&wk != &ctx->main) cus = std::max(1, cus * ctx->coarse_share / 100);
     HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
     HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
     if (w == 1) {
         BcdLayerTable t = {};
-        for (int k = 0; k < E; ++k) { t.a[k] = lv.col[k]; t.o[k] = sum + (size_t)k * npix * 3; }
-        HIPCHK(ctx, bcd_launch_bayes_weak_tiles_layers(t, E, d_mask, (const uint8_t *)wk.state.p, d_nsim, K + 1, W, H, b, wk.aux, 0, H));
+        for (int k = 0; k < E; ++k) { t.a[k] = lv.col[k]; t.o[k] = sum[k]; }
+        HIPCHK(ctx, bcd_launch_bayes_weak_tiles_layers(t, E, d_mask, d_state, d_nsim, K + 1, W, H, b, wk.aux, 0, H));
     } else {
         const int weak_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), (int64_t)cus * 32);
         for (int k = 0; k < E; ++k)
-            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, (const int32_t *)wk.weak.p, d_c + 1, weak_blocks, W, H, w, b, sum + (size_t)k * npix * 3, nullptr, wk.aux));
+            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, (const int32_t *)wk.weak.p, d_c + 1, weak_blocks, W, H, w, b, sum[k], nullptr, wk.aux));
     }
     HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
     if (w == 1) {
@@ -781,8 +781,8 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, int W, int H,
         for (int k = 0; k < E; ++k) {
             for (int first = 0; first < n_strong; first += chunk_max) {
                 HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
-                HIPCHK(ctx, bcd_launch_bayes27(lv.col[k], pixcov + (size_t)k * npix * 6, d_mask, (const int32_t *)wk.strong.p, first, std::min(chunk_max, n_strong - first),
-                                               (int *)wk.work_q.p, cus, W, H, b, min_eig, (float *)wk.gscratch.p, sum + (size_t)k * npix * 3, nullptr, d_c + 7, wk.stream, 0, nullptr));
+                HIPCHK(ctx, bcd_launch_bayes27(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, first, std::min(chunk_max, n_strong - first),
+                                               (int *)wk.work_q.p, cus, W, H, b, min_eig, (float *)wk.gscratch.p, sum[k], nullptr, d_c + 7, wk.stream, 0, nullptr));
             }
             HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 24 + k, d_c + 7, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
         }
@@ -791,15 +791,15 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, int W, int H,
         const int strong_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), 1024);
         if (per_block) RCCHK(ensure(ctx, wk.gscratch, per_block * (size_t)strong_blocks));
         for (int k = 0; k < E; ++k) {
-            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov + (size_t)k * npix * 6, d_mask, (const int32_t *)wk.strong.p, d_c, d_c + 4, strong_blocks, W, H, w, b, min_eig,
-                                                sum + (size_t)k * npix * 3, nullptr, (float *)wk.gscratch.p, wk.gscratch.bytes, wk.stream));
+            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, d_c, d_c + 4, strong_blocks, W, H, w, b, min_eig,
+                                                sum[k], nullptr, (float *)wk.gscratch.p, wk.gscratch.bytes, wk.stream));
             wk.h_counters[24 + k] = wk.h_counters[23];
         }
     }
     HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_join, 0));
-    {
+    if (lv.out[0]) {
         BcdLayerTable t = {};
-        for (int k = 0; k < E; ++k) { t.a[k] = sum + (size_t)k * npix * 3; t.o[k] = lv.out[k]; }
+        for (int k = 0; k < E; ++k) { t.a[k] = sum[k]; t.o[k] = lv.out[k]; }
         HIPCHK(ctx, bcd_launch_layers_finalize(t, E, d_count, npix, wk.stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
@@ -924,7 +924,13 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
         HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     }
     wk.redo.pending = false;
-    if (lv && lv->n > 0) RCCHK(layers_follow(ctx, wk, *lv, W, H, w, b, prm->min_eigen_value, d_count, scale));
+    if (lv && lv->n > 0) {
+        const float *lay_pixcov[BCD_MAX_LAYERS];
+        float *lay_sum[BCD_MAX_LAYERS];
+        for (int k = 0; k < lv->n; ++k) { lay_pixcov[k] = (const float *)wk.lay_pixcov.p + (size_t)k * npix * 6; lay_sum[k] = (float *)wk.lay_sum.p + (size_t)k * npix * 3; }
+        RCCHK(layers_follow(ctx, wk, *lv, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, lay_pixcov, lay_sum, W, H, w, b,
+                            prm->min_eigen_value, d_count, ctx->layer_spectral[scale < MAX_SCALES ? scale : MAX_SCALES - 1]));
+    }
     progress_add(ctx, 0.5 * (double)npix);
     int64_t ns = 0, nw = 0, tot = 0;
     bayes_counts(wk, &ns, &nw, &tot);
@@ -1845,6 +1851,125 @@ int bcd_hip_bayes_accumulate(bcd_hip_ctx *ctx, const float *d_colors, const floa
     if (!ctx || !d_colors || !d_pixcov || !d_mask || !d_nsim || !d_state || !d_sum || !d_count) return bad(ctx, "bad argument");
     DEVICE_GUARD(ctx);
     return bayes(ctx, ctx->main, d_colors, d_pixcov, d_mask, d_nsim, d_state, W, H, w, b, min_eig, d_sum, d_count);
+}
+
+int bcd_hip_bayes_accumulate_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_layer *layers, int nb_layers, const uint32_t *d_mask, const int32_t *d_nsim,
+                                    const uint8_t *d_state, int W, int H, int w, int b, float min_eig, int32_t *d_count, int32_t *h_redo)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    // ---- everything is checked before any device work (as bcd_hip_denoise_layers)
+    if (!d_mask || !d_nsim || !d_state || !d_count) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k)
+        if (!layers[k].d_colors || !layers[k].d_pixel_cov || !layers[k].d_sum) return bad(ctx, "null image pointer in a layer");
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    RCCHK(check_params(ctx, W, H, 1, &p));
+    {
+        const size_t npix = (size_t)W * H;
+        const size_t words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+        auto overlap = [](const void *a, size_t na, const void *b_, size_t nb) {
+            const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b_, b1 = b0 + nb;
+            return a0 < b1 && b0 < a1;
+        };
+        for (int k = 0; k < nb_layers; ++k) {
+            const float *o = layers[k].d_sum;
+            const size_t no = npix * 3 * sizeof(float);
+            if (overlap(o, no, d_mask, npix * words * 4) || overlap(o, no, d_nsim, npix * 4) || overlap(o, no, d_state, npix) || overlap(o, no, d_count, npix * 4))
+                return bad(ctx, "a layer's sum image overlaps the selection or the count image");
+            for (int j = 0; j < nb_layers; ++j) {
+                if (overlap(o, no, layers[j].d_colors, npix * 3 * sizeof(float)) || overlap(o, no, layers[j].d_pixel_cov, npix * 6 * sizeof(float)))
+                    return bad(ctx, "a layer's sum image overlaps an input image");
+                if (j != k && overlap(o, no, layers[j].d_sum, no)) return bad(ctx, "two layers share (part of) a sum image");
+            }
+        }
+    }
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    RCCHK(bayes(ctx, wk, layers[0].d_colors, layers[0].d_pixel_cov, d_mask, d_nsim, d_state, W, H, w, b, min_eig, layers[0].d_sum, d_count));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream)); // (the list lengths and the first layer's redo counter are on the host: what mono_accumulate hands over)
+    int32_t spectral[BCD_MAX_LAYERS] = { wk.h_counters[23] };
+    if (nb_layers > 1) {
+        LayerView lv;
+        lv.n = nb_layers - 1;
+        const float *pixcov[BCD_MAX_LAYERS];
+        float *sum[BCD_MAX_LAYERS];
+        for (int k = 1; k < nb_layers; ++k) { lv.col[k - 1] = layers[k].d_colors; lv.cov[k - 1] = nullptr; lv.out[k - 1] = nullptr; pixcov[k - 1] = layers[k].d_pixel_cov; sum[k - 1] = layers[k].d_sum; }
+        RCCHK(layers_follow(ctx, wk, lv, d_mask, d_nsim, d_state, pixcov, sum, W, H, w, b, min_eig, d_count, spectral));
+    }
+    if (h_redo) for (int k = 0; k < nb_layers; ++k) h_redo[k] = spectral[k];
+    return BCD_HIP_OK;
+}
+
+namespace {
+int layer_list_ok(bcd_hip_ctx *ctx, const void *const *a, const void *const *b, int nb_layers)
+{
+    if (!a || !b) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k)
+        if (!a[k] || !b[k]) return bad(ctx, "null image pointer in a layer");
+    return BCD_HIP_OK;
+}
+} // namespace
+
+int bcd_hip_layers_pixel_cov(bcd_hip_ctx *ctx, const float *const *d_cov, int nb_layers, const float *d_ns, int W, int H, float *d_pixcov, float *d_sum)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_ns || !d_pixcov || !d_sum || W <= 0 || H <= 0) return bad(ctx, "bad argument");
+    RCCHK(layer_list_ok(ctx, (const void *const *)d_cov, (const void *const *)d_cov, nb_layers));
+    DEVICE_GUARD(ctx);
+    BcdLayerTable t = {};
+    for (int k = 0; k < nb_layers; ++k) t.a[k] = d_cov[k];
+    HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, nb_layers, d_ns, (int64_t)W * H, d_pixcov, d_sum, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_layers_finalize(bcd_hip_ctx *ctx, const float *const *d_sum, float *const *d_out, int nb_layers, const int32_t *d_count, int64_t npix)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_count || npix <= 0) return bad(ctx, "bad argument");
+    RCCHK(layer_list_ok(ctx, (const void *const *)d_sum, (const void *const *)d_out, nb_layers));
+    DEVICE_GUARD(ctx);
+    BcdLayerTable t = {};
+    for (int k = 0; k < nb_layers; ++k) { t.a[k] = d_sum[k]; t.o[k] = d_out[k]; }
+    HIPCHK(ctx, bcd_launch_layers_finalize(t, nb_layers, d_count, npix, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_layers_downscale_avg(bcd_hip_ctx *ctx, const float *const *d_in, float *const *d_out, int nb_layers, int W, int H)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (W < 2 || H < 2) return bad(ctx, "bad argument");
+    RCCHK(layer_list_ok(ctx, (const void *const *)d_in, (const void *const *)d_out, nb_layers));
+    DEVICE_GUARD(ctx);
+    BcdLayerTable t = {};
+    for (int k = 0; k < nb_layers; ++k) { t.a[k] = d_in[k]; t.o[k] = d_out[k]; }
+    HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, nb_layers, W, H, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_layers_downscale_cov(bcd_hip_ctx *ctx, const float *const *d_cov, float *const *d_out, int nb_layers, const float *d_ns, int W, int H)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_ns || W < 2 || H < 2) return bad(ctx, "bad argument");
+    RCCHK(layer_list_ok(ctx, (const void *const *)d_cov, (const void *const *)d_out, nb_layers));
+    DEVICE_GUARD(ctx);
+    BcdLayerTable t = {};
+    for (int k = 0; k < nb_layers; ++k) { t.a[k] = d_cov[k]; t.o[k] = d_out[k]; }
+    HIPCHK(ctx, bcd_launch_layers_downscale_cov(t, nb_layers, d_ns, W, H, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_layers_merge(bcd_hip_ctx *ctx, float *const *d_hi, const float *const *d_lo, int nb_layers, int W, int H)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (W < 2 || H < 2) return bad(ctx, "bad argument");
+    RCCHK(layer_list_ok(ctx, (const void *const *)d_hi, (const void *const *)d_lo, nb_layers));
+    DEVICE_GUARD(ctx);
+    LayerView hi, lo;
+    hi.n = lo.n = nb_layers;
+    for (int k = 0; k < nb_layers; ++k) { hi.out[k] = d_hi[k]; lo.out[k] = const_cast<float *>(d_lo[k]); }
+    return merge_layers_on(ctx, ctx->main, hi, W, H, lo); // (the frame's own two launches)
 }
 
 int bcd_hip_bayes_last_redo_count(bcd_hip_ctx *ctx, int32_t *count)

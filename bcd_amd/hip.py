@@ -25,6 +25,11 @@ class Layer(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p), ("d_out", C.c_void_p)]
 
 
+class StageLayer(C.Structure):
+    """bcd_hip_stage_layer: one layer of bcd_hip_bayes_accumulate_layers"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_pixel_cov", C.c_void_p), ("d_sum", C.c_void_p)]
+
+
 class BandJob(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p),
                 ("W", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("main_row_begin", C.c_int32), ("main_row_end", C.c_int32),
@@ -155,7 +160,8 @@ SYMBOLS = [
     "bcd_hip_multi_unique_id", "bcd_hip_multi_rccl_info", "bcd_hip_multi_create_rank", "bcd_hip_multi_rank_configure", "bcd_hip_multi_rank_upload", "bcd_hip_multi_rank_step",
     "bcd_hip_multi_rank_download", "bcd_hip_multi_rank_renew_ids", "bcd_hip_multi_set_loopback", "bcd_hip_multi_selftest_transport",
     "bcd_hip_scale_begin", "bcd_hip_pixel_cov", "bcd_hip_similarity_masks", "bcd_hip_similarity_masks_deferred", "bcd_hip_similarity_masks_verdict", "bcd_hip_similarity_masks_exact", "bcd_hip_window_distances", "bcd_hip_active_set", "bcd_hip_active_init", "bcd_hip_active_step", "bcd_hip_active_step_enqueue", "bcd_hip_active_step_collect",
-    "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_rows", "bcd_hip_bayes_last_redo_count", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
+    "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_layers", "bcd_hip_layers_pixel_cov", "bcd_hip_layers_finalize", "bcd_hip_layers_downscale_avg", "bcd_hip_layers_downscale_cov", "bcd_hip_layers_merge",
+    "bcd_hip_bayes_accumulate_rows", "bcd_hip_bayes_last_redo_count", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
     "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
     "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_default_plan_params", "bcd_hip_accum_plan", "bcd_hip_zero_bad_values",
     "bcd_hip_accum_set_filter", "bcd_hip_accum_add_splatted", "bcd_hip_filter_table",
@@ -374,6 +380,76 @@ class Context:
         self._chk(lib().bcd_hip_bayes_accumulate(self.h, _dp(col), _dp(pixcov), _dp(mask), _dp(nsim), _dp(state), W, H, w, b,
                                                  C.c_float(min_eig), _dp(s), _dp(c)))
         return s, c
+
+    def bayes_accumulate_layers(self, layers, mask, nsim, state, w, b, min_eig):
+        """bcd_hip_bayes_accumulate_layers: `layers` is a list of (colours, per-pixel covariances) tensors on one selection.
+        -> (list of sum images, the shared count image, items per layer that took the redo list)"""
+        torch = self.torch
+        layers = list(layers)
+        H, W = nsim.shape
+        sums = [torch.zeros((H, W, 3), dtype=torch.float32, device=nsim.device) for _ in layers]
+        c = torch.zeros((H, W), dtype=torch.int32, device=nsim.device)
+        arr = (StageLayer * max(1, len(layers)))()
+        for k, ((col, pc), s) in enumerate(zip(layers, sums)):
+            if tuple(col.shape) != (H, W, 3) or tuple(pc.shape) != (H, W, 6):
+                raise ValueError("layer %d: colours must be %dx%dx3 and per-pixel covariances %dx%dx6" % (k, H, W, H, W))
+            arr[k].d_colors, arr[k].d_pixel_cov, arr[k].d_sum = _dp(col).value, _dp(pc).value, _dp(s).value
+        redo = (C.c_int32 * max(1, len(layers)))()
+        L = lib()
+        L.bcd_hip_bayes_accumulate_layers.argtypes = [_VP, C.POINTER(StageLayer), C.c_int, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.POINTER(C.c_int32)]
+        self._chk(L.bcd_hip_bayes_accumulate_layers(self.h, arr, len(layers), _dp(mask), _dp(nsim), _dp(state), W, H, w, b, min_eig, _dp(c), redo))
+        return sums, c, list(redo)[:len(layers)]
+
+    @staticmethod
+    def _ptr_list(tensors):
+        return (C.c_void_p * max(1, len(tensors)))(*[_dp(t).value for t in tensors])
+
+    def layers_pixel_cov(self, covs, ns):
+        """bcd_hip_layers_pixel_cov -> (per-pixel covariances L x H x W x 6, sums L x H x W x 3: cleared by the call, handed over filled with ones)"""
+        covs = list(covs)
+        H, W = ns.shape[:2]
+        pc = self.torch.empty((len(covs), H, W, 6), dtype=ns.dtype, device=ns.device)
+        s = self.torch.ones((len(covs), H, W, 3), dtype=ns.dtype, device=ns.device)
+        L = lib()
+        L.bcd_hip_layers_pixel_cov.argtypes = [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]
+        self._chk(L.bcd_hip_layers_pixel_cov(self.h, self._ptr_list(covs), len(covs), _dp(ns), W, H, _dp(pc), _dp(s)))
+        return pc, s
+
+    def layers_finalize(self, sums, c):
+        sums = list(sums)
+        outs = [self.torch.empty_like(s) for s in sums]
+        L = lib()
+        L.bcd_hip_layers_finalize.argtypes = [_VP, _VP, _VP, C.c_int, _VP, C.c_int64]
+        self._chk(L.bcd_hip_layers_finalize(self.h, self._ptr_list(sums), self._ptr_list(outs), len(sums), _dp(c), c.numel()))
+        return outs
+
+    def layers_downscale_avg(self, imgs):
+        imgs = list(imgs)
+        H, W, D = imgs[0].shape
+        outs = [self.torch.empty((H // 2, W // 2, D), dtype=a.dtype, device=a.device) for a in imgs]
+        L = lib()
+        L.bcd_hip_layers_downscale_avg.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int]
+        self._chk(L.bcd_hip_layers_downscale_avg(self.h, self._ptr_list(imgs), self._ptr_list(outs), len(imgs), W, H))
+        return outs
+
+    def layers_downscale_cov(self, covs, ns):
+        covs = list(covs)
+        H, W, D = covs[0].shape
+        outs = [self.torch.empty((H // 2, W // 2, D), dtype=a.dtype, device=a.device) for a in covs]
+        L = lib()
+        L.bcd_hip_layers_downscale_cov.argtypes = [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int]
+        self._chk(L.bcd_hip_layers_downscale_cov(self.h, self._ptr_list(covs), self._ptr_list(outs), len(covs), _dp(ns), W, H))
+        return outs
+
+    def layers_merge(self, his, los):
+        """out of place: clones of `his` merged with `los`"""
+        outs = [h.clone() for h in his]
+        los = list(los)
+        H, W, _ = outs[0].shape
+        L = lib()
+        L.bcd_hip_layers_merge.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int]
+        self._chk(L.bcd_hip_layers_merge(self.h, self._ptr_list(outs), self._ptr_list(los), len(outs), W, H))
+        return outs
 
     def bayes_last_redo_count(self):
         """items of the last bayes_accumulate call (patch radius 1) whose inverse took the spectral branch through the redo list"""

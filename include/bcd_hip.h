@@ -326,6 +326,28 @@ int bcd_hip_bayes_accumulate(bcd_hip_ctx *ctx, const float *d_colors, const floa
  * list because the sweep inverse failed its checks (the spectral branch of inverseSymmetricMatrix, DenoisingUnit.cpp:578-604).  Read-only; waits for
  * the context's stream.  What bcd_hip_get_stats reports as spectral_inverses after bcd_hip_denoise, for a stage-level call. */
 int bcd_hip_bayes_last_redo_count(bcd_hip_ctx *ctx, int32_t *count);
+/* The estimate stage of bcd_hip_denoise_layers on a selection the caller supplies (parity tests: constructed similar sets handed to the layered kernels):
+ * bcd_hip_bayes_accumulate on layers[0], then -- once its lists are on the host -- the code that serves the further layers of a scale inside
+ * bcd_hip_denoise_layers (one launch of the layered tile kernel for the fallback pixels of all of them, the full-estimate chain per layer over the first
+ * layer's item list), in the order a frame runs them.  Every layer brings its colours (W*H*3), per-pixel covariances (W*H*6) and a ZEROED sum image
+ * (W*H*3); d_count (W*H, zeroed) is shared and written by the first layer only.  h_redo[nb_layers] (host, may be NULL) receives per layer the items that
+ * took the redo list (what bcd_hip_bayes_last_redo_count reports for a single layer, and bcd_hip_layer_spectral_inverses after a frame);
+ * bcd_hip_bayes_last_redo_count then returns their sum.  Synchronises the context's stream.  Checked before any device work, as bcd_hip_denoise_layers:
+ * null pointers, 1 <= nb_layers <= BCD_HIP_MAX_LAYERS, a sum image that is (or overlaps) an input, the count image or another sum image, a refused geometry. */
+typedef struct { const float *d_colors; const float *d_pixel_cov; float *d_sum; } bcd_hip_stage_layer;
+int bcd_hip_bayes_accumulate_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_layer *layers, int nb_layers,
+                                    const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state,
+                                    int W, int H, int patch_radius, int search_radius, float min_eigen_value,
+                                    int32_t *d_count, int32_t *h_redo);
+/* The layer-batched streaming kernels of bcd_hip_denoise_layers, one launch for 1 <= nb_layers <= BCD_HIP_MAX_LAYERS images each (parity tests: per value
+ * they are bcd_hip_pixel_cov / _finalize / _downscale_avg / _downscale_cov / _merge).  The lists are HOST arrays of nb_layers device pointers; no image of
+ * a list may be null.  _pixel_cov writes layer k's per-pixel covariances to d_pixcov + k*W*H*6 and clears d_sum + k*W*H*3 (the workspace layout of a frame);
+ * d_nsamples (W*H) and d_count (npix) are the shared images.  _merge: d_hi[k] (W*H*3) <- d_hi[k] - up(down(d_hi[k])) + up(d_lo[k]), d_lo[k] being (W/2)*(H/2)*3. */
+int bcd_hip_layers_pixel_cov(bcd_hip_ctx *ctx, const float *const *d_cov, int nb_layers, const float *d_nsamples, int W, int H, float *d_pixcov, float *d_sum);
+int bcd_hip_layers_finalize(bcd_hip_ctx *ctx, const float *const *d_sum, float *const *d_out, int nb_layers, const int32_t *d_count, int64_t npix);
+int bcd_hip_layers_downscale_avg(bcd_hip_ctx *ctx, const float *const *d_in, float *const *d_out, int nb_layers, int W, int H);
+int bcd_hip_layers_downscale_cov(bcd_hip_ctx *ctx, const float *const *d_cov, float *const *d_out, int nb_layers, const float *d_nsamples, int W, int H);
+int bcd_hip_layers_merge(bcd_hip_ctx *ctx, float *const *d_hi, const float *const *d_lo, int nb_layers, int W, int H);
 /* The same for the processed pixels of lines [row_begin, row_end) only (a row band's owned lines), optionally SPECULATIVE (round 6; patch radius 1):
  * d_skip_if points at a device word that the work already enqueued on the context's stream leaves at zero when this estimate is wanted (the band
  * driver: the all-reduced count of undecided pixels of the marking batch just enqueued), h_skip_if at the host copy of that word, copied on the same

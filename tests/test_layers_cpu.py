@@ -26,6 +26,14 @@ def test_header_declares_and_library_exports_the_layered_call():
     for s in ("bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_layer_spectral_inverses"):
         assert hasattr(lib, s) and s in bh.SYMBOLS
     assert C.sizeof(bh.Layer) == 3 * C.sizeof(C.c_void_p)
+    # the stage entry points of the layered kernels (parity tests)
+    assert re.search(r"typedef struct \{ const float \*d_colors; const float \*d_pixel_cov; float \*d_sum; \} bcd_hip_stage_layer;", txt)
+    assert re.search(r"int bcd_hip_bayes_accumulate_layers\(bcd_hip_ctx \*ctx, const bcd_hip_stage_layer \*layers, int nb_layers,\s*const uint32_t \*d_mask, const int32_t \*d_nsim, "
+                     r"const uint8_t \*d_state,\s*int W, int H, int patch_radius, int search_radius, float min_eigen_value,\s*int32_t \*d_count, int32_t \*h_redo\);", txt)
+    for s in ("bcd_hip_bayes_accumulate_layers", "bcd_hip_layers_pixel_cov", "bcd_hip_layers_finalize", "bcd_hip_layers_downscale_avg", "bcd_hip_layers_downscale_cov",
+              "bcd_hip_layers_merge"):
+        assert hasattr(lib, s) and s in bh.SYMBOLS and re.search(r"int %s\(bcd_hip_ctx \*ctx, " % s, txt), s
+    assert C.sizeof(bh.StageLayer) == 3 * C.sizeof(C.c_void_p)
 
 
 def test_layered_call_without_a_context_is_an_error_not_a_crash():
@@ -36,6 +44,13 @@ def test_layered_call_without_a_context_is_an_error_not_a_crash():
     n = C.c_int32(7)
     L.bcd_hip_layer_spectral_inverses.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
     assert L.bcd_hip_layer_spectral_inverses(None, 0, 0, C.byref(n)) == -1
+    arr = (bh.StageLayer * 1)()
+    L.bcd_hip_bayes_accumulate_layers.argtypes = [C.c_void_p, C.POINTER(bh.StageLayer), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                  C.c_void_p, C.POINTER(C.c_int32)]
+    assert L.bcd_hip_bayes_accumulate_layers(None, arr, 1, None, None, None, 8, 8, 1, 6, 1e-8, None, None) == -1
+    for fn, args in (("bcd_hip_layers_pixel_cov", (None, 1, None, 8, 8, None, None)), ("bcd_hip_layers_finalize", (None, None, 1, None, C.c_int64(64))),
+                     ("bcd_hip_layers_downscale_avg", (None, None, 1, 8, 8)), ("bcd_hip_layers_downscale_cov", (None, None, 1, None, 8, 8)), ("bcd_hip_layers_merge", (None, None, 1, 8, 8))):
+        assert getattr(L, fn)(None, *args) == -1, fn
 
 
 def _write_frame(tmp_path, W=24, H=20):
