@@ -1,0 +1,600 @@
+// bcd_accum.hip -- the persistent device SamplesAccumulator of the C ABI (bcd_hip_accum_*): its own handle type, which uses the context it was
+// created on for the device, the stream and the error string only.
+#include "bcd_ctx.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+
+extern "C" {
+
+// ---- persistent device SamplesAccumulator (k_accumulate.hip) ----------------------------------------------------
+struct bcd_hip_accum {
+    bcd_hip_ctx *ctx = nullptr;
+    int W = 0, H = 0, nbins = 0;
+    float gamma = 0.f, maxval = 0.f;
+    int64_t N = 0;
+    DevBuf state;                  // (11 + 3 nbins) planes of N floats
+    DevBuf dropped;                // unsigned long long: scattered samples with an index outside [0, N)
+    DevBuf keys[2], vals[2], sort; // scattered-add scratch (grow-only)
+    int64_t capacity = 0;          // > 0: samples per sorted chunk, scratch allocated at create time
+    int64_t submitted = 0;         // samples handed to add_* since the last reset
+    DevBuf plan_red, plan_c, plan_ends, plan_err, plan_cnt, plan_tmp; // adaptive-plan scratch (allocated once per accumulator)
+    bool plan_ready = false;       // the plan scratch is allocated (N is fixed, so it is never resized)
+    // states (export / import / merge): two pinned staging chunks and two device chunks of at most STATE_CHUNK bytes, allocated on first
+    // use; stage_busy[i]: a copy out of stage[i] may still be in flight (stage_ev[i] marks its end)
+    void *stage[2] = { nullptr, nullptr };
+    void *chunk[2] = { nullptr, nullptr };
+    hipEvent_t stage_ev[2] = { nullptr, nullptr };
+    bool stage_busy[2] = { false, false };
+    size_t chunk_bytes = 0;
+    hipEvent_t ev_merge = nullptr; // recorded on the context's stream around a merge (the source's work so far / the destination's reads)
+    // reconstruction filter of the splatted add (bcd_hip_accum_set_filter): the parameters are kernel arguments, the table lives on the
+    // device and is replaced in stream order through a pinned staging copy (filter_ev: that copy has left the staging buffer)
+    bool has_filter = false;
+    float filter_f[4] = { 0.f, 0.f, 0.f, 0.f }; // rx, ry, inv_rx, inv_ry
+    int filter_g[5] = { 0, 0, 0, 0, 0 };        // table size, kx, ky, nx, ny
+    DevBuf table, cells;                        // the table (64 x 64 floats at most); the runs of the extended frame's cells (grow-only)
+    float *table_stage = nullptr;
+    hipEvent_t filter_ev = nullptr;
+    bool filter_busy = false;
+};
+
+namespace {
+
+size_t accum_state_bytes(const bcd_hip_accum *a) { return (size_t)(11 + 3 * a->nbins) * (size_t)a->N * sizeof(float); }
+
+// scratch of the scattered path for chunks of n samples
+int accum_scratch(bcd_hip_accum *a, int64_t n)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    for (int i = 0; i < 2; ++i) {
+        RCCHK(ensure(ctx, a->keys[i], (size_t)n * sizeof(uint32_t)));
+        RCCHK(ensure(ctx, a->vals[i], (size_t)n * sizeof(uint32_t)));
+    }
+    size_t bytes = 0;
+    const int end_bit = 64 - __builtin_clzll((unsigned long long)a->N); // keys are <= N (N = dropped)
+    HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, n, end_bit, ctx->stream));
+    RCCHK(ensure(ctx, a->sort, bytes));
+    return BCD_HIP_OK;
+}
+
+// scratch of the adaptive plan: reductions, C (uint64), ends (int32), the error and counts images used when the caller passes none, and
+// the scans' temporary storage; the frame size is fixed, so this sizes and allocates once (a failed attempt is retried by the next plan)
+int accum_plan_scratch(bcd_hip_accum *a)
+{
+    if (a->plan_ready) return BCD_HIP_OK;
+    bcd_hip_ctx *ctx = a->ctx;
+    const size_t N = (size_t)a->N;
+    size_t tmp = 0;
+    HIPCHK(ctx, bcd_plan_scan_bytes(a->N, &tmp));
+    RCCHK(ensure(ctx, a->plan_red, bcd_plan_red_bytes()));
+    RCCHK(ensure(ctx, a->plan_c, N * sizeof(uint64_t)));
+    RCCHK(ensure(ctx, a->plan_ends, N * sizeof(int32_t)));
+    RCCHK(ensure(ctx, a->plan_err, N * sizeof(float)));
+    RCCHK(ensure(ctx, a->plan_cnt, N * sizeof(int32_t)));
+    RCCHK(ensure(ctx, a->plan_tmp, tmp));
+    a->plan_ready = true;
+    return BCD_HIP_OK;
+}
+
+// cells of the frame extended by (kx, ky) on each side (the key space of the splatted add)
+#define SPLAT_MAX_K 4
+int64_t accum_extended_cells(const bcd_hip_accum *a, int kx, int ky) { return ((int64_t)a->W + 2 * kx) * ((int64_t)a->H + 2 * ky); }
+
+// scratch of the splatted add for any filter, beside accum_scratch's: the cell runs and the sort's storage for the wider keys
+int accum_splat_scratch(bcd_hip_accum *a)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    const int64_t NE = accum_extended_cells(a, SPLAT_MAX_K, SPLAT_MAX_K);
+    if (NE >= ((int64_t)1 << 32) - 1) return BCD_HIP_OK; // (set_filter refuses such frames)
+    RCCHK(ensure(ctx, a->cells, (size_t)NE * 2 * sizeof(uint32_t)));
+    size_t bytes = 0;
+    HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, a->capacity, 64 - __builtin_clzll((unsigned long long)NE), ctx->stream));
+    if (bytes > a->sort.bytes) RCCHK(ensure(ctx, a->sort, bytes));
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!acc) return bad(ctx, "null accumulator handle");
+    *acc = nullptr;
+    if (W <= 0 || H <= 0 || (int64_t)W * H >= ((int64_t)1 << 31)) return bad(ctx, "frame size must be positive and below 2^31 pixels");
+    if (nb_bins < 2) return bad(ctx, "nb_bins must be >= 2");
+    if (bcd_accum_snapshot_lds(3 * nb_bins) > 64 * 1024) { set_err(ctx, "more than 85 bins per channel are not supported"); return BCD_HIP_EUNSUPPORTED; }
+    if (max_batch_samples < 0 || max_batch_samples >= ((int64_t)1 << 31)) return bad(ctx, "max_batch_samples must be in [0, 2^31)");
+    DEVICE_GUARD(ctx);
+    bcd_hip_accum *a = new (std::nothrow) bcd_hip_accum();
+    if (!a) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
+    a->ctx = ctx; a->W = W; a->H = H; a->nbins = nb_bins; a->gamma = gamma; a->maxval = max_value;
+    a->N = (int64_t)W * H;
+    a->capacity = max_batch_samples;
+    int rc = ensure(ctx, a->state, accum_state_bytes(a));
+    if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
+    if (rc == BCD_HIP_OK && hipEventCreateWithFlags(&a->ev_merge, hipEventDisableTiming) != hipSuccess) {
+        a->ev_merge = nullptr;
+        set_err(ctx, "hipEventCreateWithFlags failed");
+        rc = BCD_HIP_EDEVICE;
+    }
+    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_scratch(a, a->capacity);
+    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_plan_scratch(a);
+    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_splat_scratch(a);
+    if (rc == BCD_HIP_OK) rc = bcd_hip_accum_reset(a);
+    if (rc != BCD_HIP_OK) { bcd_hip_accum_destroy(a); return rc; }
+    *acc = a;
+    return BCD_HIP_OK;
+}
+
+void bcd_hip_accum_destroy(bcd_hip_accum *acc)
+{
+    if (!acc) return;
+    DeviceGuard guard(acc->ctx);
+    (void)hipStreamSynchronize(acc->ctx->stream);
+    for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
+                       &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
+        if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : { &acc->table, &acc->cells })
+        if (b->p) (void)hipFree(b->p);
+    if (acc->table_stage) (void)hipHostFree(acc->table_stage);
+    if (acc->filter_ev) (void)hipEventDestroy(acc->filter_ev);
+    for (int i = 0; i < 2; ++i) {
+        if (acc->stage[i]) (void)hipHostFree(acc->stage[i]);
+        if (acc->chunk[i]) (void)hipFree(acc->chunk[i]);
+        if (acc->stage_ev[i]) (void)hipEventDestroy(acc->stage_ev[i]);
+    }
+    if (acc->ev_merge) (void)hipEventDestroy(acc->ev_merge);
+    delete acc;
+}
+
+int bcd_hip_accum_reset(bcd_hip_accum *acc)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, hipMemsetAsync(acc->state.p, 0, accum_state_bytes(acc), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(acc->dropped.p, 0, sizeof(unsigned long long), ctx->stream));
+    acc->submitted = 0;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!d_samples) return bad(ctx, "null samples");
+    if (channels != 3 && channels != 4) return bad(ctx, "channels must be 3 or 4");
+    if (spp < 1) return bad(ctx, "spp must be >= 1");
+    if (rows < 1 || row_begin < 0 || row_begin > acc->H - rows) return bad(ctx, "row range outside the frame");
+    DEVICE_GUARD(ctx);
+    const int64_t npix = (int64_t)rows * acc->W;
+    HIPCHK(ctx, bcd_launch_accum_dense(d_samples, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, channels, acc->nbins, acc->gamma,
+                                       acc->maxval, (float *)acc->state.p, ctx->stream));
+    acc->submitted += npix * spp;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (n < 0) return bad(ctx, "negative sample count");
+    if (n == 0) return BCD_HIP_OK;
+    if (!d_pixel || !d_rgb) return bad(ctx, "null samples");
+    DEVICE_GUARD(ctx);
+    const int64_t chunk = acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30);
+    if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
+    const int end_bit = 64 - __builtin_clzll((unsigned long long)acc->N);
+    uint32_t *k0 = (uint32_t *)acc->keys[0].p, *k1 = (uint32_t *)acc->keys[1].p, *v0 = (uint32_t *)acc->vals[0].p, *v1 = (uint32_t *)acc->vals[1].p;
+    for (int64_t b = 0; b < n; b += chunk) { // chunks in stream order: a pixel's samples of chunk c are applied after those of chunk c - 1
+        const int64_t m = std::min(chunk, n - b);
+        size_t bytes = acc->sort.bytes;
+        HIPCHK(ctx, bcd_launch_accum_keys(d_pixel + b, m, acc->N, k0, v0, (unsigned long long *)acc->dropped.p, ctx->stream));
+        HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
+        HIPCHK(ctx, bcd_launch_accum_segments(k1, v1, m, acc->N, d_rgb + b * 3, d_weights ? d_weights + b : nullptr, acc->nbins, acc->gamma,
+                                              acc->maxval, (float *)acc->state.p, ctx->stream));
+    }
+    acc->submitted += n;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y, int table_size, const float *h_table)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!h_table) { acc->has_filter = false; return BCD_HIP_OK; }
+    if (!(radius_x > 0.f && radius_x <= 3.f) || !(radius_y > 0.f && radius_y <= 3.f)) return bad(ctx, "filter radii must be in (0, 3]");
+    if (table_size < 1 || table_size > 64) return bad(ctx, "filter table size must be in [1, 64]");
+    const int tt = table_size * table_size;
+    for (int i = 0; i < tt; ++i)
+        if (!std::isfinite(h_table[i]) || h_table[i] < 0.f)
+            return bad(ctx, "filter table entries must be finite and >= 0 (filters with negative lobes are not supported)");
+    const int kx = (int)ceilf(radius_x + 0.5f), ky = (int)ceilf(radius_y + 0.5f);
+    // (col + 0.5f must be exact for the kernel's neighbour range, and the cells' keys are 32 bits wide)
+    if (accum_extended_cells(acc, kx, ky) >= ((int64_t)1 << 32) - 1 || std::max(acc->W, acc->H) >= (1 << 22)) {
+        set_err(ctx, "frames of 2^22 pixels or more on a side are not supported with a filter");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    DEVICE_GUARD(ctx);
+    RCCHK(ensure(ctx, acc->table, 64 * 64 * sizeof(float)));
+    if (!acc->table_stage) HIPCHK(ctx, hipHostMalloc((void **)&acc->table_stage, 64 * 64 * sizeof(float), hipHostMallocDefault));
+    if (!acc->filter_ev) HIPCHK(ctx, hipEventCreateWithFlags(&acc->filter_ev, hipEventDisableTiming));
+    if (acc->filter_busy) { HIPCHK(ctx, hipEventSynchronize(acc->filter_ev)); acc->filter_busy = false; }
+    std::memcpy(acc->table_stage, h_table, (size_t)tt * sizeof(float));
+    HIPCHK(ctx, hipMemcpyAsync(acc->table.p, acc->table_stage, (size_t)tt * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipEventRecord(acc->filter_ev, ctx->stream));
+    acc->filter_busy = true;
+    // cells further than n from a pixel hold no sample within the radius: a sample of a cell at offset n + 1 is at least n + 0.5 away
+    // (exactly representable, and the rounded subtraction is monotone), so n is the smallest integer with n + 0.5 >= r -- never more
+    // than K, the candidate range of the definition
+    int nx = 0, ny = 0;
+    while ((float)nx + 0.5f < radius_x) ++nx;
+    while ((float)ny + 0.5f < radius_y) ++ny;
+    acc->filter_f[0] = radius_x; acc->filter_f[1] = radius_y; acc->filter_f[2] = 1.f / radius_x; acc->filter_f[3] = 1.f / radius_y;
+    acc->filter_g[0] = table_size; acc->filter_g[1] = kx; acc->filter_g[2] = ky;
+    acc->filter_g[3] = std::min(nx, kx); acc->filter_g[4] = std::min(ny, ky);
+    acc->has_filter = true;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!acc->has_filter) return bad(ctx, "the accumulator has no filter (bcd_hip_accum_set_filter)");
+    if (n < 0) return bad(ctx, "negative sample count");
+    if (n == 0) return BCD_HIP_OK;
+    if (!d_xy || !d_rgb) return bad(ctx, "null samples");
+    DEVICE_GUARD(ctx);
+    const int *g = acc->filter_g;
+    const int64_t NE = accum_extended_cells(acc, g[1], g[2]);
+    // a chunk holds at most as many samples as keep the average ring of a tile within 0.55 of the staging arrays (chunks are applied in
+    // stream order, so splitting a batch changes no bit); denser tiles take the kernel's global-memory path
+    const int max_staged = bcd_splat_max_staged(g[0]), ring = bcd_splat_ring_cells(g[3], g[4]);
+    const int64_t dense = std::max<int64_t>((int64_t)1 << 16, (int64_t)((double)acc->N * 0.55 * max_staged / ring));
+    const int64_t chunk = std::min(dense, acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30));
+    if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
+    RCCHK(ensure(ctx, acc->cells, (size_t)NE * 2 * sizeof(uint32_t)));
+    const int end_bit = 64 - __builtin_clzll((unsigned long long)NE); // keys are <= NE (NE = dropped)
+    size_t need = 0;
+    HIPCHK(ctx, bcd_accum_sort(nullptr, &need, nullptr, nullptr, nullptr, nullptr, std::min(n, chunk), end_bit, ctx->stream));
+    RCCHK(ensure(ctx, acc->sort, need)); // (more key bits than the scattered add's: the storage may differ)
+    uint32_t *k0 = (uint32_t *)acc->keys[0].p, *k1 = (uint32_t *)acc->keys[1].p, *v0 = (uint32_t *)acc->vals[0].p, *v1 = (uint32_t *)acc->vals[1].p;
+    for (int64_t b = 0; b < n; b += chunk) {
+        const int64_t m = std::min(chunk, n - b);
+        const float *xy = d_xy + 2 * b, *rgb = d_rgb + 3 * b, *w = d_weights ? d_weights + b : nullptr;
+        size_t bytes = acc->sort.bytes;
+        HIPCHK(ctx, bcd_launch_splat_keys(xy, m, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, k0, v0,
+                                          (unsigned long long *)acc->dropped.p, ctx->stream));
+        HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
+        HIPCHK(ctx, bcd_launch_splat_cells(k1, m, NE, acc->cells.p, ctx->stream));
+        // staging arrays for 1.5 times the average ring of this chunk plus 8 sigma of a uniform distribution
+        const double avg = (double)m * ring / (double)acc->N;
+        const int cap = (int)std::min<double>(max_staged, 1.5 * avg + 8.0 * std::sqrt(avg) + 64.0);
+        HIPCHK(ctx, bcd_launch_splat(acc->cells.p, v1, xy, rgb, w, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, cap, acc->nbins,
+                                     acc->gamma, acc->maxval, (float *)acc->state.p, ctx->stream));
+    }
+    acc->submitted += n;
+    return BCD_HIP_OK;
+}
+
+// separable table of a standard filter (host only); 1-D factors at d = (i + 0.5) / TS * r in double, product rounded to float once
+int bcd_hip_filter_table(int kind, float radius_x, float radius_y, float param, int table_size, float *h_out)
+{
+    if (!h_out || table_size < 1 || table_size > 64) return BCD_HIP_EINVAL;
+    if (!(radius_x > 0.f && radius_x <= 3.f) || !(radius_y > 0.f && radius_y <= 3.f)) return BCD_HIP_EINVAL;
+    if (kind < BCD_HIP_FILTER_BOX || kind > BCD_HIP_FILTER_BLACKMAN_HARRIS) return BCD_HIP_EINVAL;
+    if (kind == BCD_HIP_FILTER_GAUSSIAN && !(std::isfinite(param) && param >= 0.f)) return BCD_HIP_EINVAL;
+    auto f1 = [&](double d, double r) -> double {
+        switch (kind) {
+        case BCD_HIP_FILTER_BOX: return 1.0;
+        case BCD_HIP_FILTER_TENT: return std::max(0.0, 1.0 - d / r);
+        case BCD_HIP_FILTER_GAUSSIAN: return std::max(0.0, std::exp(-(double)param * d * d) - std::exp(-(double)param * r * r));
+        default: { // Blackman-Harris window of width 2 r centred on the sample
+            const double pi = 3.14159265358979323846, u = (d + r) / (2.0 * r);
+            return std::max(0.0, 0.35875 - 0.48829 * std::cos(2.0 * pi * u) + 0.14128 * std::cos(4.0 * pi * u) - 0.01168 * std::cos(6.0 * pi * u));
+        }
+        }
+    };
+    for (int iy = 0; iy < table_size; ++iy)
+        for (int ix = 0; ix < table_size; ++ix) {
+            const double dx = (ix + 0.5) / table_size * (double)radius_x, dy = (iy + 0.5) / table_size * (double)radius_y;
+            h_out[iy * table_size + ix] = (float)(f1(dx, (double)radius_x) * f1(dy, (double)radius_y));
+        }
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!d_nsamples || !d_mean || !d_cov || !d_hist) return bad(ctx, "null output");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_accum_snapshot((const float *)acc->state.p, acc->N, 3 * acc->nbins, d_nsamples, d_mean, d_cov, d_hist, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    DEVICE_GUARD(ctx);
+    unsigned long long d = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&d, acc->dropped.p, sizeof(d), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (samples_added) *samples_added = acc->submitted - (int64_t)d;
+    if (dropped) *dropped = (int64_t)d;
+    return BCD_HIP_OK;
+}
+
+// k_plan_summary writes the summary as int64[3] then a float
+static_assert(sizeof(bcd_hip_plan_summary) == 32 && offsetof(bcd_hip_plan_summary, max_error) == 24, "bcd_hip_plan_summary layout");
+
+void bcd_hip_default_plan_params(bcd_hip_plan_params *p)
+{
+    if (!p) return;
+    p->threshold = 0.f;
+    p->eps = 1e-3f;
+    p->min_samples = 2.f;
+    p->max_per_pixel = 16;
+}
+
+int bcd_hip_accum_plan(bcd_hip_accum *acc, const bcd_hip_plan_params *prm, int64_t budget, uint64_t offset, float *d_error, int32_t *d_counts,
+                       int32_t *d_pixels, int64_t capacity, bcd_hip_plan_summary *d_summary)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!prm) return bad(ctx, "null plan parameters");
+    if (!d_pixels || !d_summary) return bad(ctx, "null pixel list or summary");
+    if (budget < 0 || budget > INT32_MAX) return bad(ctx, "budget must be in [0, 2^31)");
+    if (capacity < budget) return bad(ctx, "pixel list capacity below the budget");
+    if (!std::isfinite(prm->threshold) || prm->threshold < 0.f) return bad(ctx, "threshold must be finite and >= 0");
+    if (!std::isfinite(prm->eps) || !(prm->eps > 0.f)) return bad(ctx, "eps must be finite and > 0");
+    if (!std::isfinite(prm->min_samples) || prm->min_samples < 0.f) return bad(ctx, "min_samples must be finite and >= 0");
+    if (prm->max_per_pixel < 1 || prm->max_per_pixel > 65535) return bad(ctx, "max_per_pixel must be in [1, 65535]");
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_plan_scratch(acc));
+    HIPCHK(ctx, hipMemsetAsync(acc->plan_red.p, 0, bcd_plan_red_bytes(), ctx->stream));
+    HIPCHK(ctx, bcd_launch_accum_plan((const float *)acc->state.p, acc->N, prm->eps, prm->min_samples, prm->threshold, prm->max_per_pixel, budget,
+                                      offset, d_error ? d_error : (float *)acc->plan_err.p, d_counts ? d_counts : (int32_t *)acc->plan_cnt.p,
+                                      d_pixels, capacity, (int64_t *)d_summary, acc->plan_red.p, (uint64_t *)acc->plan_c.p,
+                                      (int32_t *)acc->plan_ends.p, acc->plan_tmp.p, acc->plan_tmp.bytes, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+// ---- states: export, import, merge -----------------------------------------------------------------------------
+static_assert(sizeof(bcd_hip_accum_state_header) == BCD_HIP_ACCUM_STATE_HEADER_BYTES && offsetof(bcd_hip_accum_state_header, version) == 8 &&
+                  offsetof(bcd_hip_accum_state_header, header_bytes) == 12 && offsetof(bcd_hip_accum_state_header, width) == 16 &&
+                  offsetof(bcd_hip_accum_state_header, height) == 20 && offsetof(bcd_hip_accum_state_header, nb_bins) == 24 &&
+                  offsetof(bcd_hip_accum_state_header, gamma) == 28 && offsetof(bcd_hip_accum_state_header, max_value) == 32 &&
+                  offsetof(bcd_hip_accum_state_header, nb_planes) == 36 && offsetof(bcd_hip_accum_state_header, samples_added) == 40 &&
+                  offsetof(bcd_hip_accum_state_header, dropped) == 48 && offsetof(bcd_hip_accum_state_header, reserved) == 56,
+              "bcd_hip_accum_state_header layout (format v1)");
+
+namespace {
+
+constexpr size_t STATE_CHUNK = (size_t)64 << 20; // bound of a staging / scratch chunk
+const char STATE_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'S', 'T' };
+
+// what is wrong with a serialised state of `bytes` bytes (its header copied to *hd), or nullptr
+const char *state_problem(const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
+{
+    if (!h) return "null state";
+    if (bytes < BCD_HIP_ACCUM_STATE_HEADER_BYTES) return "shorter than the 64-byte header";
+    memcpy(hd, h, sizeof(*hd));
+    if (memcmp(hd->magic, STATE_MAGIC, 8) != 0) return "bad magic (not BCDACCST)";
+    if (hd->version != BCD_HIP_ACCUM_STATE_VERSION) return "unsupported version (not 1)";
+    if (hd->header_bytes != BCD_HIP_ACCUM_STATE_HEADER_BYTES) return "header_bytes is not 64";
+    if (hd->nb_bins < 2 || hd->nb_bins > 85) return "nb_bins outside [2, 85]";
+    if (hd->width <= 0 || hd->height <= 0 || (int64_t)hd->width * hd->height >= ((int64_t)1 << 31)) return "width and height must be positive, below 2^31 pixels";
+    if (hd->nb_planes != (uint32_t)(11 + 3 * hd->nb_bins)) return "nb_planes is not 11 + 3 nb_bins";
+    if (bytes != BCD_HIP_ACCUM_STATE_HEADER_BYTES + 4 * (int64_t)hd->nb_planes * hd->width * hd->height) return "size is not 64 + 4 nb_planes W H bytes";
+    for (uint8_t r : hd->reserved)
+        if (r != 0) return "reserved bytes are not zero";
+    if (hd->samples_added < 0 || hd->dropped < 0) return "negative counters";
+    return nullptr;
+}
+
+// a well-formed state of this accumulator's geometry and parameters (gamma and max value bit for bit)?
+int accum_check_state(bcd_hip_accum *a, const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
+{
+    if (const char *why = state_problem(h, bytes, hd)) return bad(a->ctx, (std::string("not an accumulator state (format v1): ") + why).c_str());
+    if (hd->width != a->W || hd->height != a->H || hd->nb_bins != a->nbins) return bad(a->ctx, "state of another frame size or bin count");
+    if (memcmp(&hd->gamma, &a->gamma, sizeof(float)) != 0 || memcmp(&hd->max_value, &a->maxval, sizeof(float)) != 0)
+        return bad(a->ctx, "state with another gamma or max value");
+    return BCD_HIP_OK;
+}
+
+int accum_check_pair(bcd_hip_accum *dst, bcd_hip_accum *src)
+{
+    if (!src) return bad(dst->ctx, "null source accumulator");
+    if (dst == src) return bad(dst->ctx, "an accumulator cannot be merged into itself");
+    if (dst->W != src->W || dst->H != src->H || dst->nbins != src->nbins) return bad(dst->ctx, "accumulators of different frame sizes or bin counts");
+    if (memcmp(&dst->gamma, &src->gamma, sizeof(float)) != 0 || memcmp(&dst->maxval, &src->maxval, sizeof(float)) != 0)
+        return bad(dst->ctx, "accumulators with different gamma or max value");
+    return BCD_HIP_OK;
+}
+
+// the pinned staging (host_side) or the device chunks, allocated once; the context's device is current
+int accum_chunks(bcd_hip_accum *a, bool host_side)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    a->chunk_bytes = std::min(STATE_CHUNK, accum_state_bytes(a));
+    for (int i = 0; i < 2; ++i) {
+        if (host_side && !a->stage_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&a->stage_ev[i], hipEventDisableTiming));
+        void *&p = host_side ? a->stage[i] : a->chunk[i];
+        if (p) continue;
+        const hipError_t e = host_side ? hipHostMalloc(&p, a->chunk_bytes, hipHostMallocDefault) : hipMalloc(&p, a->chunk_bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            set_err(ctx, std::string(host_side ? "hipHostMalloc" : "hipMalloc") + " of a state chunk failed: " + hipGetErrorString(e));
+            return BCD_HIP_ENOMEM;
+        }
+    }
+    return BCD_HIP_OK;
+}
+
+// the planes at h (accum_state_bytes) replace the state (merge = false) or are added to it, chunk by chunk through the pinned staging:
+// the host copy of chunk i + 1 runs while chunk i crosses PCIe.  Returns when h is no longer needed.
+int accum_from_host(bcd_hip_accum *a, const uint8_t *h, bool merge)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    RCCHK(accum_chunks(a, true));
+    if (merge) RCCHK(accum_chunks(a, false));
+    const size_t S = accum_state_bytes(a), c = a->chunk_bytes;
+    uint8_t *st = (uint8_t *)a->state.p;
+    for (size_t off = 0, i = 0; off < S; off += c, ++i) {
+        const int b = (int)(i & 1);
+        const size_t len = std::min(c, S - off);
+        if (a->stage_busy[b]) {
+            HIPCHK(ctx, hipEventSynchronize(a->stage_ev[b]));
+            a->stage_busy[b] = false;
+        }
+        memcpy(a->stage[b], h + off, len);
+        // (merge: chunk[b] was last read by the merge of chunk i - 2, earlier on the same stream)
+        HIPCHK(ctx, hipMemcpyAsync(merge ? a->chunk[b] : st + off, a->stage[b], len, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(a->stage_ev[b], ctx->stream));
+        a->stage_busy[b] = true;
+        if (merge) HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)a->chunk[b], (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+    }
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+int bcd_hip_accum_state_info(const void *h_state, int64_t bytes, bcd_hip_accum_state_header *out)
+{
+    bcd_hip_accum_state_header hd;
+    if (state_problem(h_state, bytes, &hd)) return BCD_HIP_EINVAL;
+    if (out) *out = hd;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_state_bytes(bcd_hip_accum *acc, int64_t *bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    if (!bytes) return bad(acc->ctx, "null size");
+    *bytes = BCD_HIP_ACCUM_STATE_HEADER_BYTES + (int64_t)accum_state_bytes(acc);
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    const size_t S = accum_state_bytes(acc);
+    if (!h_state) return bad(ctx, "null state buffer");
+    if (capacity < BCD_HIP_ACCUM_STATE_HEADER_BYTES + (int64_t)S) return bad(ctx, "state buffer smaller than bcd_hip_accum_state_bytes");
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_chunks(acc, true));
+    int64_t added = 0, dropped = 0;
+    RCCHK(bcd_hip_accum_info(acc, &added, &dropped)); // (synchronises: no staging copy is in flight after it)
+    acc->stage_busy[0] = acc->stage_busy[1] = false;
+    bcd_hip_accum_state_header hd;
+    memset(&hd, 0, sizeof(hd));
+    memcpy(hd.magic, STATE_MAGIC, 8);
+    hd.version = BCD_HIP_ACCUM_STATE_VERSION;
+    hd.header_bytes = BCD_HIP_ACCUM_STATE_HEADER_BYTES;
+    hd.width = acc->W; hd.height = acc->H; hd.nb_bins = acc->nbins;
+    hd.gamma = acc->gamma; hd.max_value = acc->maxval;
+    hd.nb_planes = (uint32_t)(11 + 3 * acc->nbins);
+    hd.samples_added = added; hd.dropped = dropped;
+    uint8_t *out = (uint8_t *)h_state;
+    memcpy(out, &hd, sizeof(hd));
+    out += BCD_HIP_ACCUM_STATE_HEADER_BYTES;
+    // chunk i + 2 crosses PCIe into one pinned buffer while the host copies chunk i + 1 out of the other
+    const size_t c = acc->chunk_bytes, nch = (S + c - 1) / c;
+    const uint8_t *st = (const uint8_t *)acc->state.p;
+    auto enqueue = [&](size_t i) {
+        const int b = (int)(i & 1);
+        hipError_t e = hipMemcpyAsync(acc->stage[b], st + i * c, std::min(c, S - i * c), hipMemcpyDeviceToHost, ctx->stream);
+        return e == hipSuccess ? hipEventRecord(acc->stage_ev[b], ctx->stream) : e;
+    };
+    for (size_t i = 0; i < std::min<size_t>(2, nch); ++i) HIPCHK(ctx, enqueue(i));
+    for (size_t i = 0; i < nch; ++i) {
+        const int b = (int)(i & 1);
+        HIPCHK(ctx, hipEventSynchronize(acc->stage_ev[b]));
+        memcpy(out + i * c, acc->stage[b], std::min(c, S - i * c));
+        if (i + 2 < nch) HIPCHK(ctx, enqueue(i + 2));
+    }
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    bcd_hip_accum_state_header hd;
+    RCCHK(accum_check_state(acc, h_state, bytes, &hd));
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, false));
+    HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 0, ctx->stream));
+    acc->submitted = hd.samples_added + hd.dropped;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_merge_state(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    bcd_hip_accum_state_header hd;
+    RCCHK(accum_check_state(acc, h_state, bytes, &hd));
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, true));
+    HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 1, ctx->stream));
+    acc->submitted += hd.samples_added + hd.dropped;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src)
+{
+    if (!dst) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = dst->ctx;
+    RCCHK(accum_check_pair(dst, src));
+    bcd_hip_ctx *sctx = src->ctx;
+    { // everything enqueued on src's stream so far ...
+        DeviceGuard g(sctx);
+        if (!g.ok) { set_err(ctx, "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
+        HIPCHK(ctx, hipEventRecord(src->ev_merge, sctx->stream));
+    }
+    DEVICE_GUARD(ctx);
+    // ... comes before the reads on dst's stream
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->ev_merge, 0));
+    const size_t S = accum_state_bytes(dst);
+    const char *env = getenv("BCD_HIP_ACCUM_MERGE_COPY"); // 1: the chunked copy of a cross-device merge on one device too (tests)
+    if (sctx->device == ctx->device && !(env && env[0] == '1')) {
+        HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->state.p, (const float *)src->state.p, (int64_t)(S / 4), ctx->num_cus, ctx->stream));
+        HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)src->dropped.p, 0, 1, ctx->stream));
+    } else {
+        // src's state in chunks into dst-side scratch (peer copies; no peer access needed), each chunk merged after its copy
+        RCCHK(accum_chunks(dst, false));
+        const size_t c = dst->chunk_bytes;
+        uint8_t *st = (uint8_t *)dst->state.p;
+        const uint8_t *ss = (const uint8_t *)src->state.p;
+        for (size_t off = 0, i = 0; off < S; off += c, ++i) {
+            void *buf = dst->chunk[i & 1];
+            const size_t len = std::min(c, S - off);
+            HIPCHK(ctx, hipMemcpyPeerAsync(buf, ctx->device, ss + off, sctx->device, len, ctx->stream));
+            HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)buf, (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+        }
+        HIPCHK(ctx, hipMemcpyPeerAsync(dst->chunk[0], ctx->device, src->dropped.p, sctx->device, sizeof(unsigned long long), ctx->stream));
+        HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)dst->chunk[0], 0, 1, ctx->stream));
+    }
+    // dst's reads come before whatever is enqueued on src's stream from now on
+    HIPCHK(ctx, hipEventRecord(dst->ev_merge, ctx->stream));
+    {
+        DeviceGuard g(sctx);
+        if (!g.ok) { set_err(ctx, "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
+        HIPCHK(ctx, hipStreamWaitEvent(sctx->stream, dst->ev_merge, 0));
+    }
+    dst->submitted += src->submitted;
+    return BCD_HIP_OK;
+}
+
+} // extern "C"

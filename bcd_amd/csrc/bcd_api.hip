@@ -1,8 +1,8 @@
 // bcd_api.hip -- implementation of the C ABI declared in include/bcd_hip.h: context, workspace,
 // the per-scale driver (Denoiser::denoise, src/core/Denoiser.cpp:84-212) and the multiscale driver
-// (MultiscaleDenoiser::denoise, src/core/MultiscaleDenoiser.cpp:31-136) on device-resident images.
-#include "../../include/bcd_hip.h"
-#include "bcd_common.h"
+// (MultiscaleDenoiser::denoise, src/core/MultiscaleDenoiser.cpp:31-136) on device-resident images, and the stage-level entry points.
+// The host-buffer entry points are in bcd_host.hip, the sample accumulator in bcd_accum.hip, the self-tests in bcd_selftest.hip.
+#include "bcd_ctx.h"
 
 #include <algorithm>
 #include <chrono>
@@ -20,259 +20,13 @@
 #include <utility>
 #include <vector>
 
-// launchers implemented in the k_*.hip files
-size_t bcd_pairdist_lds_bytes(int D, int b);
-hipError_t bcd_launch_pairdist(const float *, const float *, int, int, int, int, float *, uint8_t *, int, int *, float, hipStream_t);
-hipError_t bcd_launch_uniform_n(const float *, int64_t, int *, hipStream_t);
-hipError_t bcd_launch_compare_planes(const float *, const uint8_t *, const float *, const uint8_t *, int64_t, unsigned long long *, hipStream_t);
-hipError_t bcd_launch_selftest_div(uint32_t, int, int, unsigned long long *, hipStream_t);
-hipError_t bcd_launch_masks(const float *, const uint8_t *, int, int, int, int, float, uint32_t *, int32_t *, uint32_t *, hipStream_t,
-                            const BcdBorderline *, const float *, const float *, int);
-hipError_t bcd_launch_masks_finish(int, int, int, float, uint32_t *, int32_t *, uint32_t *, hipStream_t, const BcdBorderline *, const float *, const float *, int);
-int bcd_pairdist_rw_supported(int D);
-hipError_t bcd_launch_pairdist_rw(const float *, const float *, int, int, int, int, void * /* binary16 T planes */, uint8_t *, int *, float, hipStream_t);
-hipError_t bcd_launch_pairdist_rw_rows(const float *, const float *, int, int, int, int, void *, uint8_t *, int *, float, int, int, hipStream_t);
-hipError_t bcd_launch_pairdist_rw_ratio(const float *, const float *, int, int, int, int, void *, uint8_t *, int *, float, unsigned int *, hipStream_t);
-int bcd_pairdist_rw_tile_lines();
-struct BcdSparseUploader;
-BcdSparseUploader *bcd_sparse_create();
-void bcd_sparse_destroy(BcdSparseUploader *);
-void bcd_sparse_frame_begin(BcdSparseUploader *);
-void bcd_sparse_frame_bytes(const BcdSparseUploader *, long long *, long long *);
-hipError_t bcd_sparse_upload(BcdSparseUploader *, float *, const float *, size_t, hipStream_t);
-void bcd_bayes27_set_strict_eigensolver(int on);
-float bcd_bayes27_conv2(int strict);
-hipError_t bcd_launch_pairdist_rw_counting(const float *, const float *, int, int, int, int, void *, uint8_t *, int *, float, unsigned long long *, hipStream_t);
-hipError_t bcd_launch_spike_rows(const float *, const float *, const float *, const float *, int, int, int, float, float *, float *, float *, float *, int, int,
-                                 hipStream_t);
-hipError_t bcd_launch_max_rel_dev(const float *, const float *, const uint8_t *, const uint8_t *, int, int, int, unsigned int *, hipStream_t);
-hipError_t bcd_launch_window_distances(const float *, const uint8_t *, int, int, int, int, int, int, float *, hipStream_t);
-hipError_t bcd_launch_pixel_cov(const float *, const float *, int64_t, float *, hipStream_t);
-hipError_t bcd_launch_pixel_cov_clear(const float *, const float *, int64_t, float *, float *, int32_t *, hipStream_t);
-hipError_t bcd_launch_scale_begin(int *, int, int, int, int *, int, int *, int, hipStream_t);
-hipError_t bcd_launch_finalize_band(const float *, const int32_t *, int, int, int, const float *, const int32_t *, const float *, const int32_t *, float *,
-                                    hipStream_t);
-hipError_t bcd_launch_finalize(const float *, const int32_t *, int64_t, float *, hipStream_t);
-hipError_t bcd_launch_zero_bad(float *, int64_t, hipStream_t);
-hipError_t bcd_launch_downscale(int, const float *, int, int, int, float *, hipStream_t);
-hipError_t bcd_launch_downscale_cov(const float *, const float *, int, int, float *, hipStream_t);
-hipError_t bcd_launch_interpolate(int, const float *, int, int, int, float *, int, int, hipStream_t);
-hipError_t bcd_launch_merge_interpolate(const float *, const float *, int, int, int, float *, int, int, hipStream_t);
-hipError_t bcd_launch_spike(const float *, const float *, const float *, const float *, int, int, int, float, float *, float *,
-                            float *, float *, hipStream_t);
-hipError_t bcd_launch_accumulate_samples(const float *, const float *, int64_t, int, int, float, float, float *, float *, float *, float *, hipStream_t);
-hipError_t bcd_launch_active_init(const int32_t *, int, int, int, int, int, float, uint32_t, int, uint8_t *, hipStream_t);
-hipError_t bcd_launch_active_round(const uint32_t *, const int32_t *, uint8_t *, int, int, int, int, int, uint32_t, int, int, int, int *, hipStream_t);
-hipError_t bcd_launch_mark_deps(const uint32_t *, const int32_t *, uint8_t *, uint32_t *, int, int, int, int, int, uint32_t, int, int, int, int *, hipStream_t);
-hipError_t bcd_launch_mark_round(const uint32_t *, uint8_t *, int, int, int, int, int, int, int *, hipStream_t);
-hipError_t bcd_launch_sum_counter_lines(const int *, int, int *, hipStream_t, long long * = nullptr, const int * = nullptr, int = 0);
-hipError_t bcd_launch_active_lists(const uint8_t *, const int32_t *, int64_t, int64_t, int, int32_t *, int32_t *, int32_t *, hipStream_t, const long long *);
-hipError_t bcd_launch_jacobi27_batch(const float *, int, int *, int, float *, float *, hipStream_t, float = 1e-12f, float * = nullptr, const int * = nullptr, int = 0);
-size_t bcd_bayes_lds_bytes(int w, int b);
-size_t bcd_accum_snapshot_lds(int D);
-hipError_t bcd_launch_accum_dense(const float *, const float *, int64_t, int64_t, int64_t, int, int, int, float, float, float *, hipStream_t);
-hipError_t bcd_launch_accum_keys(const int32_t *, int64_t, int64_t, uint32_t *, uint32_t *, unsigned long long *, hipStream_t);
-hipError_t bcd_accum_sort(void *, size_t *, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, int64_t, int, hipStream_t);
-hipError_t bcd_launch_accum_segments(const uint32_t *, const uint32_t *, int64_t, int64_t, const float *, const float *, int, float, float, float *,
-                                     hipStream_t);
-hipError_t bcd_launch_accum_snapshot(const float *, int64_t, int, float *, float *, float *, float *, hipStream_t);
-int bcd_splat_ring_cells(int nx, int ny);
-int bcd_splat_max_staged(int ts);
-hipError_t bcd_launch_splat_keys(const float *, int64_t, int, int, const float *, const int *, const float *, uint32_t *, uint32_t *, unsigned long long *,
-                                 hipStream_t);
-hipError_t bcd_launch_splat_cells(const uint32_t *, int64_t, int64_t, void *, hipStream_t);
-hipError_t bcd_launch_splat(const void *, const uint32_t *, const float *, const float *, const float *, int, int, const float *, const int *,
-                            const float *, int, int, float, float, float *, hipStream_t);
-size_t bcd_plan_red_bytes();
-hipError_t bcd_plan_scan_bytes(int64_t, size_t *);
-hipError_t bcd_launch_accum_plan(const float *, int64_t, float, float, float, int, int64_t, uint64_t, float *, int32_t *, int32_t *, int64_t, int64_t *,
-                                 void *, uint64_t *, int32_t *, void *, size_t, hipStream_t);
-hipError_t bcd_launch_accum_merge(float *, const float *, int64_t, int, hipStream_t);
-hipError_t bcd_launch_accum_counter(unsigned long long *, const unsigned long long *, unsigned long long, int, hipStream_t);
-size_t bcd_bayes_scratch_bytes_per_block(int w, int b);
-size_t bcd_bayes27_record_bytes();
-hipError_t bcd_launch_bayes27(const float *, const float *, const uint32_t *, const int32_t *, int, int, int *, int, int, int, int, float, float *, float *,
-                              int32_t *, int *, hipStream_t, int, const int *d_nb_items);
-hipError_t bcd_launch_bayes27_redo(const float *, const float *, const uint32_t *, const int32_t *, int, int, int *, int, int, int, int, float, float *, float *,
-                                   int32_t *, hipStream_t);
-hipError_t bcd_launch_bayes_strong(const float *, const float *, const uint32_t *, const int32_t *, const int32_t *, int *, int, int, int, int,
-                                   int, float, float *, int32_t *, float *, size_t, hipStream_t);
-hipError_t bcd_launch_bayes_weak(const float *, const uint32_t *, const int32_t *, const int32_t *, int, int, int, int, int, float *,
-                                 int32_t *, hipStream_t);
-hipError_t bcd_launch_bayes_weak_tiles(const float *, const uint32_t *, const uint8_t *, const int32_t *, int, int, int, int, float *, int32_t *, hipStream_t, int, int, const long long *);
-hipError_t bcd_launch_bayes_weak_tiles_layers(const BcdLayerTable &, int, const uint32_t *, const uint8_t *, const int32_t *, int, int, int, int, hipStream_t, int, int);
-hipError_t bcd_launch_layers_pixel_cov_clear(const BcdLayerTable &, int, const float *, int64_t, float *, float *, hipStream_t);
-hipError_t bcd_launch_layers_finalize(const BcdLayerTable &, int, const int32_t *, int64_t, hipStream_t);
-hipError_t bcd_launch_layers_downscale_avg(const BcdLayerTable &, int, int, int, hipStream_t);
-hipError_t bcd_launch_layers_downscale_cov(const BcdLayerTable &, int, const float *, int, int, hipStream_t);
-hipError_t bcd_launch_layers_merge(const BcdLayerTable &, int, int, int, int, int, hipStream_t);
-static_assert(BCD_MAX_LAYERS == BCD_HIP_MAX_LAYERS, "the layer tables of the kernels hold what the C ABI admits");
-
-namespace {
-
-constexpr int MAX_SCALES = 16;
-constexpr int ROUND_BATCH = 16;
-constexpr int MAX_EVENT_PAIRS = 4096;
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
-// the colour layers of a bcd_hip_denoise_layers call BEYOND the first, at one scale: the first layer travels through the arguments bcd_hip_denoise has
-struct LayerView {
-    int n = 0;
-    const float *col[BCD_MAX_LAYERS], *cov[BCD_MAX_LAYERS];
-    float *out[BCD_MAX_LAYERS];
-};
-
-} // namespace
-
-// everything one scale's pipeline needs: a multiscale run drives one Work per scale concurrently (own stream, own host
-// thread), because the scales are independent until the merge and the coarse ones cannot fill 256 CUs on their own
-struct Work {
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
-    DevBuf T, Cn, mask, fwd, nsim, state, strong, weak, counters, cnt_lines, work_q, pixcov, sum, cnt, gscratch, dep, tmp_lo, border, ratio_stats; // grow-only
-    DevBuf lay_pixcov, lay_sum, lay_tmp_lo; // extra colour layers (bcd_hip_denoise_layers): per-pixel covariances, sums, merge scratch -- one slice per layer
-    int border_capacity = 0;       // entries of `border` offered to the last fast similarity pass (0: the exact kernels ran)
-    int rounds_hint = 0;           // marking launches the last problem needed
-    int last_batch = 0;            // launches of the batch active_step_enqueue left in flight
-    bool dep_ready = false;        // dependency lists of the current marking problem are in `dep` (reset by active_init)
-    const void *dep_mask = nullptr, *dep_state = nullptr; // ... extracted for these buffers (another problem on the same context rebuilds them)
-    int32_t *h_counters = nullptr; // pinned
-    bool initialised = false;      // set once every stream / event / pinned buffer below exists
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool; // pair-distance kernel timing
-    int ev_used = 0;
-    hipEvent_t ev_stage[4] = { nullptr, nullptr, nullptr, nullptr };
-    hipEvent_t ev_done = nullptr;
-    hipEvent_t ev_built = nullptr; // this scale's pyramid level is complete
-    hipStream_t aux = nullptr;     // side stream: the fallback-pixel kernel runs beside the (latency-bound) full estimate kernel
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_pixcov = nullptr; // the per-pixel covariances (side stream, beside the distance kernel) are complete
-    hipEvent_t ev_counts = nullptr; // the list lengths of bayes() are on the host
-    // (round 6) full-estimate items of the last frame of this geometry on this workspace: the next frame's first chunk of estimate kernels is launched for
-    // that many (+ 1/8) BEFORE the host knows the new count
-    int strong_hint = 0, strong_hint_W = 0, strong_hint_H = 0;
-    // approximate distance planes computed ahead of similarity() by a caller that streams the frame in (bcd_hip_denoise_host_ex): valid for
-    // exactly this problem; similarity() consumes the note
-    struct { bool ready = false; const float *hist = nullptr, *ns = nullptr; int W = 0, H = 0, D = 0, b = 0; float tau = 0.f, uni_n = 0.f; } planes;
-    // uniform-sample-count speculation of the approximate distance kernel (similarity()): did the last frames on this workspace fail it?
-    bool nonuniform = false;
-    bool speculated = false;       // the current pass launched the uniform kernel on the first pixel's count, unchecked by the host
-    // the RATIO form of the distance kernel raised its absolute-error flag on frames of these sizes on this workspace: the reference's operations serve them (a small
-    // set, oldest replaced: serialised scales share one workspace, a caller may alternate frame sizes)
-    struct { int W = 0, H = 0; } ratio_declined[4];
-    int ratio_declined_next = 0;
-    bool ratio_is_declined(int W, int H) const { for (const auto &k : ratio_declined) if (k.W == W && k.H == H) return true; return false; }
-    bool ratio_used = false;          // the current pass ran the RATIO form of the distance kernel (general sample counts)
-    int ratio_W = 0, ratio_H = 0;        // ... on a frame of this size
-    // (round 4) k_scale_begin cleared these at the head of the scale's stream: the first user takes them as they are, a repeated use (second
-    // similarity attempt, second marking batch, second chunk of a long list) clears its own as before
-    bool clean_flags = false, clean_lines = false, clean_dc = false, clean_wq = false;
-    // the redo kernel of the register-resident finish (k_bayes27w<2> over the -- normally empty -- list of items whose sweep inverse failed its
-    // checks) is only launched when the list's counter, read with the scale's last synchronisation, says so
-    struct { bool pending = false; int first = 0, n = 0, cus = 0; } redo;
-};
-
-struct bcd_hip_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool owns_stream = false;
-    bool profiling = false;
-    bool concurrent_scales = true;
-    bool fast_similarity = true; // approximate distance planes + exact re-evaluation at the threshold (k_similarity_fast.hip)
-    int num_cus = 256;
-    int cu_share_pct = 100;  // bcd_hip_set_cu_share
-    // share of the CU slots the coarse scales' persistent estimate kernels take inside bcd_hip_denoise (bayes()); adjusted from call to
-    // call on the same geometry so that the coarse scales end shortly before the finest one (see bcd_hip_denoise)
-    int coarse_share = 25;
-    int64_t share_key = 0;          // geometry the current value was tuned on
-    std::mutex err_mutex;
-    std::string err;
-    bcd_hip_scale_stats stats[MAX_SCALES];
-    Work main;               // bound to `stream`
-    Work extra[MAX_SCALES];  // lazily created streams for scales 1.. of a multiscale run
-    DevBuf tmp_lo;
-    DevBuf pyr[MAX_SCALES][5]; // colours, nsamples, hist, cov, out
-    DevBuf lay_host[3];            // host-buffer entry point of the layers: device copies of the extra layers' colours, covariances, outputs
-    DevBuf lay_pyr[MAX_SCALES][3]; // extra colour layers: colours, cov, out of every layer at that pyramid level, one slice per layer
-    int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
-    int layer_count = 0;                                // layers of that call (0: none yet)
-    DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
-    hipEvent_t ev_pyramid = nullptr;
-    hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
-    hipStream_t upload_stream2 = nullptr;       // ... colours and covariances beside the histogram pieces (helper thread)
-    hipEvent_t ev_upload2 = nullptr;
-    std::vector<hipEvent_t> ev_upload;
-    bool stream_uploads = true;                 // BCD_HIP_STREAM_UPLOADS=0: upload everything, then compute
-    // (round 4) the histogram image crosses PCIe without its zeros (bcd_sparse_upload.hip); BCD_HIP_SPARSE_UPLOAD=0: plain copies
-    bool sparse_uploads = true;
-    BcdSparseUploader *sparse = nullptr;
-    long long upload_raw_bytes = 0, upload_sent_bytes = 0; // histogram image of the last host-buffer frame: as it is / as it travelled
-    // progress reporting (IDenoiser::setProgressCallback; Denoiser.cpp:181-192 of the reference): every scale adds its share when
-    // its marking is done and when its estimate is done; calls are serialised and monotone
-    bcd_hip_progress_fn progress_fn = nullptr;
-    void *progress_user = nullptr;
-    std::mutex progress_mutex;
-    double progress_done = 0.0, progress_total = 0.0;
-    // bcd_hip_denoise_begin / _wait (round 6): one frame of this context in flight on a worker thread of its own, so that a caller can keep a second
-    // context busy meanwhile (frames of a sequence, AOV passes: the distance kernels of one frame fill the chip under the latency-bound tail of another)
-    struct Async {
-        std::thread th;
-        std::mutex mu;
-        std::condition_variable cv;
-        bool has_job = false, in_flight = false, quit = false;
-        int rc = 0;
-        const float *col = nullptr, *ns = nullptr, *hist = nullptr, *cov = nullptr;
-        float *out = nullptr;
-        int W = 0, H = 0, D = 0, S = 0;
-        bcd_hip_params prm;
-    } async;
-};
-
-namespace {
-
+// ---- helpers shared with the other host files (declared in bcd_ctx.h) ----------------------------------------------------------------
 void set_err(bcd_hip_ctx *ctx, const std::string &msg)
 {
     if (!ctx) return;
     std::lock_guard<std::mutex> lock(ctx->err_mutex);
     ctx->err = msg;
 }
-
-// every entry point that allocates or launches runs on the context's device and leaves the caller's current device as it was
-struct DeviceGuard {
-    int prev = -1, dev;
-    bool ok = true;
-    explicit DeviceGuard(const bcd_hip_ctx *ctx) : dev(ctx ? ctx->device : -1)
-    {
-        if (dev < 0) return;
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (dev >= 0 && prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-};
-#define DEVICE_GUARD(ctx)                                                                                             \
-    DeviceGuard guard__(ctx);                                                                                         \
-    if (!guard__.ok) { set_err((ctx), "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
-
-#define HIPCHK(ctx, expr)                                                                                             \
-    do {                                                                                                              \
-        hipError_t e__ = (expr);                                                                                      \
-        if (e__ != hipSuccess) {                                                                                      \
-            set_err((ctx), std::string(#expr) + ": " + hipGetErrorString(e__));                                       \
-            return BCD_HIP_EDEVICE;                                                                                   \
-        }                                                                                                             \
-    } while (0)
-
-#define RCCHK(expr)                                                                                                   \
-    do {                                                                                                              \
-        int rc__ = (expr);                                                                                            \
-        if (rc__ != BCD_HIP_OK) return rc__;                                                                          \
-    } while (0)
 
 int ensure(bcd_hip_ctx *ctx, DevBuf &b, size_t bytes)
 {
@@ -283,15 +37,6 @@ int ensure(bcd_hip_ctx *ctx, DevBuf &b, size_t bytes)
     if (e != hipSuccess) { set_err(ctx, "hipMalloc failed: " + std::string(hipGetErrorString(e))); b.p = nullptr; return BCD_HIP_ENOMEM; }
     b.bytes = want;
     return BCD_HIP_OK;
-}
-
-// `share` of the frame's work (pixels of a scale, weighted) is done
-void progress_add(bcd_hip_ctx *ctx, double share)
-{
-    if (!ctx->progress_fn || !(ctx->progress_total > 0.0)) return;
-    std::lock_guard<std::mutex> lock(ctx->progress_mutex);
-    ctx->progress_done = std::min(ctx->progress_total, ctx->progress_done + share);
-    ctx->progress_fn((float)(ctx->progress_done / ctx->progress_total), ctx->progress_user);
 }
 
 int bad(bcd_hip_ctx *ctx, const char *msg)
@@ -320,19 +65,76 @@ int check_params(bcd_hip_ctx *ctx, int W, int H, int D, const bcd_hip_params *pr
     return BCD_HIP_OK;
 }
 
-// bytes of the count planes of a scale.  ONE place: the host-buffer entry point computes planes ahead of similarity(), and a larger request there
-// would free them (round 6: it happened when one of the two grew, found by the environment-switch test on a fresh context)
-size_t count_plane_bytes(size_t npix, int nd) { return npix * (size_t)nd; }
+// can the approximate-planes path serve this problem?  (w = 1, a supported depth, a threshold binary16 can decide: bcd_common.h)
+bool fast_similarity_applies(const bcd_hip_ctx *ctx, int D, int w, float tau)
+{
+    return ctx->fast_similarity && w == 1 && bcd_pairdist_rw_supported(D) && tau >= BCD_APPROX_TAU_MIN && tau <= BCD_APPROX_TAU_MAX;
+}
+
+// one small reduction and one host round trip (~30 us): *uni_n = the frame's power-of-two sample count, or left as it is when the frame has none
+int scan_uniform_count(bcd_hip_ctx *ctx, Work &wk, const float *d_ns, size_t npix, float *uni_n)
+{
+    Counters *d = wk.d_counters(), *h = wk.h_counters;
+    HIPCHK(ctx, bcd_launch_uniform_n(d_ns, (int64_t)npix, &d->flags.scan, wk.stream));
+    HIPCHK(ctx, hipMemcpyAsync(&h->flags.scan, &d->flags.scan, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipMemcpyAsync(&h->first_count, d_ns, sizeof(float), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    if (h->flags.scan == 0 && is_pow2_sample_count(h->first_count)) *uni_n = h->first_count;
+    return BCD_HIP_OK;
+}
+
+float stage_ms(Work &wk, int a, int b)
+{
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, wk.ev_stage[a], wk.ev_stage[b]);
+    return ms;
+}
+
+namespace {
+
+// `share` of the frame's work (pixels of a scale, weighted) is done
+void progress_add(bcd_hip_ctx *ctx, double share)
+{
+    if (!ctx->progress_fn || !(ctx->progress_total > 0.0)) return;
+    std::lock_guard<std::mutex> lock(ctx->progress_mutex);
+    ctx->progress_done = std::min(ctx->progress_total, ctx->progress_done + share);
+    ctx->progress_fn((float)(ctx->progress_done / ctx->progress_total), ctx->progress_user);
+}
+
+// the estimate chunk: full-estimate items whose records (bcd_bayes27_record_bytes() each) are in flight at a time
+// (round 6: 2^18 instead of 2^17 -- half as many drains of the three persistent kernels on a -m 0 frame: 60.9 -> 60.2-60.5 ms at 1080p; sizes aligned to
+// the eigensolver's 6 144 matrices per round of the grid made no difference)
+constexpr int ESTIMATE_CHUNK = 1 << 18; // 262144 pixels = 2.6 GB of records
+
+// The estimate kernels are persistent (a wavefront per CU slot, items from a counter), so whatever they occupy stays
+// occupied until they end.  In a multiscale call the finest scale is the critical path and the coarse scales have slack: they
+// take a quarter of the slots, which leaves LDS and wave slots on every CU to the finest scale's short kernels (masks,
+// marking, lists) running beside them -- measured 1080p: 306 -> 315 Mpix/s (100 % -> 25 %; 12 %: 320, 6 %: 250).  The share is
+// ctx->coarse_share: 25 on a new geometry, then steered by bcd_hip_denoise.
+int estimate_cus(const bcd_hip_ctx *ctx, const Work &wk)
+{
+    int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
+    if (&wk != &ctx->main) cus = std::max(1, cus * ctx->coarse_share / 100);
+    return cus;
+}
+
+// ... the same share as a percentage of the chip (bcd_hip_scale_stats::cu_share)
+int estimate_share_pct(const bcd_hip_ctx *ctx, const Work &wk) { return ctx->cu_share_pct * (&wk != &ctx->main ? ctx->coarse_share : 100) / 100; }
+
+// what follows on the workspace's side stream comes after what the scale's own stream holds so far
+int fork_aux(bcd_hip_ctx *ctx, Work &wk)
+{
+    HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
+    HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
+    return BCD_HIP_OK;
+}
 
 // did the last similarity() pass on this workspace leave the range flag raised or overflow its borderline list?  (valid after the
 // stream has been synchronised; the caller then repeats the pass with exact_mode = 1)
-// a user of the workspace's counters / flags / work queues / sub-counter lines outside the scale chain (self-tests, the eigensolver entry point): whatever
-// k_scale_begin left clean is not clean any more
-void touch(Work &wk) { wk.clean_flags = wk.clean_lines = wk.clean_dc = wk.clean_wq = false; }
-
 bool similarity_needs_redo(const Work &wk)
 {
-    return wk.h_counters[40] != 0 || (wk.border_capacity > 0 && (wk.h_counters[42] != 0 || wk.h_counters[43] > wk.border_capacity));
+    const Counters::Flags &f = wk.h_counters->flags;
+    return f.range != 0 || (wk.border_capacity > 0 && (f.other_count != 0 || f.borderline > wk.border_capacity));
 }
 
 // ... and with which kernels: 0 = no redo; 3 = the approximate kernels again with the general (non-uniform) formula -- the only complaint
@@ -340,10 +142,10 @@ bool similarity_needs_redo(const Work &wk)
 // memory of whether its frames have uniform counts (valid after the stream has been synchronised).
 int similarity_redo_mode(Work &wk)
 {
-    const int flag = wk.h_counters[40];
+    const int flag = wk.h_counters->flags.range;
     const bool fast = wk.border_capacity > 0;
-    const bool other_count = fast && wk.h_counters[42] != 0; // a pixel carries another sample count than the uniform kernel was launched for
-    const bool overflow = fast && wk.h_counters[43] > wk.border_capacity;
+    const bool other_count = fast && wk.h_counters->flags.other_count != 0; // a pixel carries another sample count than the uniform kernel was launched for
+    const bool overflow = fast && wk.h_counters->flags.borderline > wk.border_capacity;
     if (fast && (wk.speculated || other_count)) wk.nonuniform = other_count;
     if (flag == 0 && !other_count && !overflow) return 0;
     if (fast && wk.ratio_used && (flag & 4) != 0) { // the RATIO form's absolute-error check: the reference's operations serve this frame size on this workspace from now on
@@ -353,14 +155,8 @@ int similarity_redo_mode(Work &wk)
     return (flag == 0 && other_count) ? 3 : 1; // (a void launch has no meaningful list count: other_count alone decides)
 }
 
-// can the approximate-planes path serve this problem?  (w = 1, a supported depth, a threshold binary16 can decide: bcd_common.h)
-bool fast_similarity_applies(const bcd_hip_ctx *ctx, int D, int w, float tau)
-{
-    return ctx->fast_similarity && w == 1 && bcd_pairdist_rw_supported(D) && tau >= BCD_APPROX_TAU_MIN && tau <= BCD_APPROX_TAU_MAX;
-}
-
 // exact_mode: 0 = production kernels, flags checked here (one stream synchronisation); 1 = exact kernels with the compiler's division;
-// 2 = production kernels, flags copied to wk.h_counters[40] / [43] but NOT checked: the caller validates after its own
+// 2 = production kernels, flags copied to wk.h_counters->flags but NOT checked: the caller validates after its own
 // synchronisation with similarity_needs_redo() / similarity_redo_mode(); 3 = like 2 with the general (non-uniform) formula forced.
 // Production kernels: w = 1 and a supported depth -> approximate planes (k_pairdist_rw) + exact verification of the borderline
 // pairs; otherwise the exact planes with the scale-free division (k_pairdist<FAST>).
@@ -384,8 +180,8 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         e1 = wk.ev_pool[wk.ev_used].second;
         ++wk.ev_used;
     }
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    int *d_flag = (int *)wk.counters.p + 40; // [0] range / count flag, [1] uniform-count scan, [3] borderline pairs
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    Counters::Flags *d_flag = &wk.d_counters()->flags, *h_flag = &wk.h_counters->flags;
     // planes of exactly this problem already computed by the caller (its launches raised the flags in d_flag[0] themselves)?
     const bool pre = wk.planes.ready && exact_mode != 1 && wk.planes.hist == d_hist && wk.planes.ns == d_ns && wk.planes.W == W && wk.planes.H == H &&
                      wk.planes.D == D && wk.planes.b == b && wk.planes.tau == tau && w == 1;
@@ -394,16 +190,16 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
     if (wk.clean_flags) { // cleared by k_scale_begin, which kept the words of planes computed ahead ...
         wk.clean_flags = false;
         if (planes_kept && !pre) { // ... of ANOTHER problem (serialised scales: the coarsest scale runs first on this workspace): their flags are not this pass's
-            HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), wk.stream));
-            HIPCHK(ctx, hipMemsetAsync(d_flag + 2, 0, sizeof(int), wk.stream));
+            HIPCHK(ctx, hipMemsetAsync(&d_flag->range, 0, sizeof(int), wk.stream));
+            HIPCHK(ctx, hipMemsetAsync(&d_flag->other_count, 0, sizeof(int), wk.stream));
         }
     } else if (pre) { // (flags [0] and [2] belong to the launches that made the planes)
-        HIPCHK(ctx, hipMemsetAsync(d_flag + 1, 0, sizeof(int), wk.stream));
-        HIPCHK(ctx, hipMemsetAsync(d_flag + 3, 0, sizeof(int), wk.stream));
-    } else HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4 * sizeof(int), wk.stream));
-    wk.h_counters[40] = 0;
-    wk.h_counters[42] = 0;
-    wk.h_counters[43] = 0;
+        HIPCHK(ctx, hipMemsetAsync(&d_flag->scan, 0, sizeof(int), wk.stream));
+        HIPCHK(ctx, hipMemsetAsync(&d_flag->borderline, 0, sizeof(int), wk.stream));
+    } else HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(*d_flag), wk.stream));
+    h_flag->range = 0;
+    h_flag->other_count = 0;
+    h_flag->borderline = 0;
     wk.border_capacity = 0;
     wk.ratio_used = false;
     wk.ratio_W = W; wk.ratio_H = H;
@@ -412,18 +208,6 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
     float uni_n = pre ? wk.planes.uni_n : 0.f;
     const bool fast_path = exact_mode != 1 && fast_similarity_applies(ctx, D, w, tau);
     wk.speculated = false;
-    auto scan_uniform_count = [&]() -> int { // one small reduction and one host round trip (~30 us): uni_n = the frame's power-of-two count, or 0
-        HIPCHK(ctx, bcd_launch_uniform_n(d_ns, (int64_t)npix, d_flag + 1, wk.stream));
-        HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 41, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
-        HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 42, d_ns, sizeof(float), hipMemcpyDeviceToHost, wk.stream));
-        HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-        float n0;
-        memcpy(&n0, wk.h_counters + 42, sizeof(n0));
-        wk.h_counters[42] = 0;
-        int e = 0;
-        if (wk.h_counters[41] == 0 && n0 >= 1.f && n0 <= 65536.f && frexpf(n0, &e) == 0.5f) uni_n = n0;
-        return BCD_HIP_OK;
-    };
     if (fast_path && !pre) {
         // No scan and no round trip at the head of the chain: the approximate kernel takes the first pixel's count as THE count and checks
         // every pixel against it itself (flag bit 1 -> the pass is repeated with the general formula).  A workspace whose LAST frame was not
@@ -431,18 +215,18 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         // cost a uniform frame that followed frames with mixed counts the general formula for up to 31 passes).
         if (exact_mode != 3 && !wk.nonuniform) { uni_n = -1.f; wk.speculated = true; }
         else if (exact_mode != 3) {
-            RCCHK(scan_uniform_count());
+            RCCHK(scan_uniform_count(ctx, wk, d_ns, npix, &uni_n));
             wk.nonuniform = uni_n == 0.f;
         }
     } else if (exact_mode != 1 && !pre)
-        RCCHK(scan_uniform_count());
+        RCCHK(scan_uniform_count(ctx, wk, d_ns, npix, &uni_n));
     // the approximate path keeps its T plane in binary16: thresholds it cannot decide safely take the exact kernels (bcd_common.h)
     const bool fast = fast_path;
     if (fast) {
         const int capacity = (int)std::min<size_t>(std::max<size_t>(npix, 1u << 16), 1u << 28);
         RCCHK(ensure(ctx, wk.border, (size_t)capacity * sizeof(uint2)));
         wk.border_capacity = capacity;
-        BcdBorderline bl = { 0.f, (uint2 *)wk.border.p, d_flag + 3, capacity };
+        BcdBorderline bl = { 0.f, (uint2 *)wk.border.p, &d_flag->borderline, capacity };
         // General sample counts (adaptive sampling, 24 spp, ...; src/core/DenoisingUnit.cpp:371-383 handles any n1, n2): the RATIO form of the dense kernel
         // (round 6, k_similarity_fast.hip) evaluates them at the cost of uniform ones -- 1.83 ms at 1080p against 1.73 for the uniform kernel, 3.0 ms for the
         // reference's operations and 1.97 + 0.07 ms for the own-list kernel of round 5, which it replaced -- and checks afterwards that the absolute errors it
@@ -453,18 +237,18 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         else if (use_ratio) {
             RCCHK(ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)));
             if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
-            HIPCHK(ctx, bcd_launch_pairdist_rw_ratio(d_hist, d_ns, W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, tau, (unsigned int *)wk.ratio_stats.p, wk.stream));
+            HIPCHK(ctx, bcd_launch_pairdist_rw_ratio(d_hist, d_ns, W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, tau, (unsigned int *)wk.ratio_stats.p, wk.stream));
             if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
         } else {
             if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
-            HIPCHK(ctx, bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, uni_n, wk.stream));
+            HIPCHK(ctx, bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, wk.stream));
             if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
         }
-        HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 40, d_flag, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
-        HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 42, d_flag + 2, sizeof(int), hipMemcpyDeviceToHost, wk.stream)); // "another sample count" (plain-store flag)
+        HIPCHK(ctx, hipMemcpyAsync(&h_flag->range, &d_flag->range, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
+        HIPCHK(ctx, hipMemcpyAsync(&h_flag->other_count, &d_flag->other_count, sizeof(int), hipMemcpyDeviceToHost, wk.stream)); // "another sample count" (plain-store flag)
         HIPCHK(ctx, bcd_launch_masks((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask, d_count, (uint32_t *)wk.fwd.p, wk.stream,
                                      &bl, d_hist, d_ns, D));
-        HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 43, d_flag + 3, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
+        HIPCHK(ctx, hipMemcpyAsync(&h_flag->borderline, &d_flag->borderline, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
         if (exact_mode == 0) {
             HIPCHK(ctx, hipStreamSynchronize(wk.stream));
             const int redo = similarity_redo_mode(wk);
@@ -482,14 +266,14 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         return BCD_HIP_OK;
     }
     if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
-    HIPCHK(ctx, bcd_launch_pairdist(d_hist, d_ns, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, exact_mode == 1 ? 0 : 1, d_flag, uni_n, wk.stream));
+    HIPCHK(ctx, bcd_launch_pairdist(d_hist, d_ns, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, exact_mode == 1 ? 0 : 1, &d_flag->range, uni_n, wk.stream));
     if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
     // the fast kernel flags inputs outside the range where its division is proven exact: redo with the compiler's division
-    if (exact_mode != 1) HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 40, d_flag, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
+    if (exact_mode != 1) HIPCHK(ctx, hipMemcpyAsync(&h_flag->range, &d_flag->range, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
     if (exact_mode == 0) {
         HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-        if (wk.h_counters[40] != 0)
-            HIPCHK(ctx, bcd_launch_pairdist(d_hist, d_ns, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, 0, d_flag, 0.f, wk.stream));
+        if (h_flag->range != 0)
+            HIPCHK(ctx, bcd_launch_pairdist(d_hist, d_ns, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, 0, &d_flag->range, 0.f, wk.stream));
     }
     HIPCHK(ctx, bcd_launch_masks((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask, d_count, (uint32_t *)wk.fwd.p, wk.stream,
                                  nullptr, nullptr, nullptr, 0));
@@ -505,8 +289,8 @@ int active_step_enqueue(bcd_hip_ctx *ctx, Work &wk, const uint32_t *d_mask, cons
                         int row_end, int random_order, uint32_t seed, int row_offset, uint8_t *d_state, long long *d_total, bool with_verdict)
 {
     const int K = 3 * (2 * w + 1) * (2 * w + 1);
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    int *d_cnt = (int *)wk.counters.p;
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    int *d_cnt = wk.d_counters()->undecided;
     // every launch counts the pixels it leaves undecided into its own set of BCD_CNT_LINES sub-counters (one per cache line: a single
     // counter is a serial resource, k_active.hip); one small kernel folds them into d_cnt[launch] for the host
     constexpr size_t LINE_INTS = (size_t)BCD_CNT_LINES * BCD_CNT_STRIDE;
@@ -546,8 +330,8 @@ int active_step_enqueue(bcd_hip_ctx *ctx, Work &wk, const uint32_t *d_mask, cons
             HIPCHK(ctx, bcd_launch_active_round(d_mask, d_nsim, d_state, W, H, b, K + 1, random_order, seed, row_begin, row_end, row_offset,
                                                 d_lines + LINE_INTS * i, wk.stream));
     }
-    HIPCHK(ctx, bcd_launch_sum_counter_lines(d_lines, batch, d_cnt, wk.stream, d_total, with_verdict ? (const int *)wk.counters.p + 40 : nullptr, wk.border_capacity));
-    HIPCHK(ctx, hipMemcpyAsync(wk.h_counters, d_cnt, ROUND_BATCH * sizeof(int), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, bcd_launch_sum_counter_lines(d_lines, batch, d_cnt, wk.stream, d_total, with_verdict ? &wk.d_counters()->flags.range : nullptr, wk.border_capacity));
+    HIPCHK(ctx, hipMemcpyAsync(wk.h_counters->undecided, d_cnt, ROUND_BATCH * sizeof(int), hipMemcpyDeviceToHost, wk.stream));
     wk.last_batch = batch;
     return BCD_HIP_OK;
 }
@@ -557,8 +341,8 @@ void active_step_collect(Work &wk, int *undecided_out, int *launches_out)
     const int batch = wk.last_batch;
     int n = batch;
     for (int i = 0; i < batch; ++i)
-        if (wk.h_counters[i] == 0) { n = i + 1; break; }
-    *undecided_out = wk.h_counters[n - 1];
+        if (wk.h_counters->undecided[i] == 0) { n = i + 1; break; }
+    *undecided_out = wk.h_counters->undecided[n - 1];
     if (launches_out) *launches_out = n;
 }
 
@@ -600,7 +384,7 @@ int active_set(bcd_hip_ctx *ctx, Work &wk, const uint32_t *d_mask, const int32_t
     return BCD_HIP_OK;
 }
 
-// lists of processed pixels + the estimate kernels.  The list lengths and the sum of |S| are copied to wk.h_counters[16..20):
+// lists of processed pixels + the estimate kernels.  The list lengths and the sum of |S| are copied to wk.h_counters->lists:
 // read them with bayes_counts() after the stream has been synchronised.
 // w = 1: the full estimate is three kernels with a per-pixel record in HBM between them (k_bayes27.hip); the host reads the
 // number of full-estimate pixels (one short round trip, the fallback kernel is already running on its side stream) to size the
@@ -624,53 +408,43 @@ int bayes(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixc
     wk.redo.pending = false;
     RCCHK(ensure(ctx, wk.strong, npix * sizeof(int32_t)));
     RCCHK(ensure(ctx, wk.weak, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    int32_t *d_c = (int32_t *)wk.counters.p + 16; // [0] strong, [1] weak, [2..3] sum |S|, [4..6] work counters of the generic estimate kernel, [7] spectral inverses
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    Counters::Lists *d_c = &wk.d_counters()->lists, *h_c = &wk.h_counters->lists;
     const bool weak_tiles = w == 1; // (other patch radii: the list kernel below)
-    wk.h_counters[23] = 0;
+    h_c->spectral = 0;
     // the two paths only meet in the atomic accumulators: the fallback pixels run on a side stream.  The tiled fallback kernel needs no
     // list (it reads states and |S| itself), so it starts at once -- beside the list compaction and the host round trip for the number of
     // full estimates, during which this scale would otherwise leave the chip idle -- and is out of the way when the prepare kernel arrives
     auto fork_weak_tiles = [&]() -> int {
-        HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
-        HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
+        RCCHK(fork_aux(ctx, wk));
         HIPCHK(ctx, bcd_launch_bayes_weak_tiles(d_colors, d_mask, d_state, d_nsim, K + 1, W, H, b, d_sum, d_count, wk.aux, row_begin, row_end, d_skip));
         HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
         return BCD_HIP_OK;
     };
     if (wk.clean_dc) wk.clean_dc = false; // (k_scale_begin)
-    else HIPCHK(ctx, hipMemsetAsync(d_c, 0, 8 * sizeof(int32_t), wk.stream));
-    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim, (int64_t)row_begin * W, (int64_t)row_end * W, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, d_c, wk.stream, d_skip));
-    HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 16, d_c, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream));
+    else HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
+    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim, (int64_t)row_begin * W, (int64_t)row_end * W, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, &d_c->n_strong, wk.stream, d_skip));
+    HIPCHK(ctx, hipMemcpyAsync(h_c, d_c, offsetof(Counters::Lists, generic_work), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
     // (round 5) the list compaction is 253 workgroups of 1024 threads: 18 us alone, 150 us when the fallback kernel's 8 160 tiles were launched
     // first and every CU had to drain before one of them fitted.  The fallback kernel starts BEHIND it (it still overlaps the host round trip).
     if (weak_tiles) RCCHK(fork_weak_tiles());
     const int64_t cap = std::max<int64_t>(1, npix);
-    // The estimate kernels are persistent (a wavefront per CU slot, items from a counter), so whatever they occupy stays
-    // occupied until they end.  In a multiscale call the finest scale is the critical path and the coarse scales have slack: they
-    // take a quarter of the slots, which leaves LDS and wave slots on every CU to the finest scale's short kernels (masks,
-    // marking, lists) running beside them -- measured 1080p: 306 -> 315 Mpix/s (100 % -> 25 %; 12 %: 320, 6 %: 250).  The share is
-    // ctx->coarse_share: 25 on a new geometry, then steered by bcd_hip_denoise.
-    int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
-    if (&wk != &ctx->main) cus = std::max(1, cus * ctx->coarse_share / 100);
+    const int cus = estimate_cus(ctx, wk);
     const int weak_blocks = (int)std::min<int64_t>(cap, (int64_t)cus * 32);
     if (!weak_tiles) { // the list kernel (other patch radii): many cheap items beside the full estimate's few long ones
-        HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
-        HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
-        HIPCHK(ctx, bcd_launch_bayes_weak(d_colors, d_mask, (const int32_t *)wk.weak.p, d_c + 1, weak_blocks, W, H, w, b, d_sum, d_count, wk.aux));
+        RCCHK(fork_aux(ctx, wk));
+        HIPCHK(ctx, bcd_launch_bayes_weak(d_colors, d_mask, (const int32_t *)wk.weak.p, &d_c->n_weak, weak_blocks, W, H, w, b, d_sum, d_count, wk.aux));
         HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
     }
     if (w == 1) {
         const size_t rec = bcd_bayes27_record_bytes();
-        // (round 6: 2^18 instead of 2^17 -- half as many drains of the three persistent kernels on a -m 0 frame: 60.9 -> 60.2-60.5 ms at 1080p; sizes aligned to
-        // the eigensolver's 6 144 matrices per round of the grid made no difference)
-        const int chunk_max = 1 << 18; // 262144 pixels = 2.6 GB of records
+        const int chunk_max = ESTIMATE_CHUNK;
         RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
         auto launch_chunk = [&](int first, int n, bool defer, const int *d_n) -> int {
             if (wk.clean_wq) wk.clean_wq = false; // (k_scale_begin)
             else HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream)); // the work queues of the three kernels
             HIPCHK(ctx, bcd_launch_bayes27(d_colors, d_pixcov, d_mask, (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, H, b, min_eig,
-                                           (float *)wk.gscratch.p, d_sum, d_count, d_c + 7, wk.stream, defer ? 1 : 0, d_n));
+                                           (float *)wk.gscratch.p, d_sum, d_count, &d_c->spectral, wk.stream, defer ? 1 : 0, d_n));
             return BCD_HIP_OK;
         };
         // Round 6: the first chunk does not wait for the host.  The list's length is on its way back (the copy above), the previous frame of this
@@ -683,7 +457,7 @@ int bayes(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixc
         if (wk.strong_hint_W == W && wk.strong_hint_H == H && wk.strong_hint >= 512 && wk.strong_hint + wk.strong_hint / 8 + 1024 <= chunk_max) {
             ahead = wk.strong_hint + wk.strong_hint / 8 + 1024;
             RCCHK(ensure(ctx, wk.gscratch, rec * (size_t)ahead));
-            RCCHK(launch_chunk(0, ahead, defer_redo, d_c));
+            RCCHK(launch_chunk(0, ahead, defer_redo, &d_c->n_strong));
         }
         HIPCHK(ctx, hipEventSynchronize(wk.ev_counts));
         if (h_skip && *h_skip != 0) { // the speculation failed: nothing was listed, the kernels enqueued above found nothing to do
@@ -691,10 +465,10 @@ int bayes(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixc
             HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_join, 0));
             return BCD_HIP_OK;
         }
-        const int n_strong = wk.h_counters[16];
+        const int n_strong = h_c->n_strong;
         wk.strong_hint = n_strong; wk.strong_hint_W = W; wk.strong_hint_H = H;
         if (ahead > 0 && n_strong <= ahead) {
-            if (defer_redo) { wk.redo.pending = true; wk.redo.first = 0; wk.redo.n = ahead; wk.redo.cus = cus; } // (the counter is h_counters[23], below)
+            if (defer_redo) { wk.redo.pending = true; wk.redo.first = 0; wk.redo.n = ahead; wk.redo.cus = cus; } // (the counter is h_counters->lists.spectral, below)
         } else {
             if (ahead > 0 && defer_redo) // the first chunk's records are about to be reused: its redo list (normally empty) is walked now
                 HIPCHK(ctx, bcd_launch_bayes27_redo(d_colors, d_pixcov, d_mask, (const int32_t *)wk.strong.p, 0, ahead, (int *)wk.work_q.p, cus, W, H, b, min_eig,
@@ -716,12 +490,12 @@ int bayes(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixc
                 RCCHK(ensure(ctx, wk.gscratch, rec * (size_t)std::min(n_strong, chunk_max)));
             }
         }
-        HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 23, d_c + 7, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // read after the scale's last synchronisation
+        HIPCHK(ctx, hipMemcpyAsync(&h_c->spectral, &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // read after the scale's last synchronisation
     } else {
         const size_t per_block = bcd_bayes_scratch_bytes_per_block(w, b);
         const int strong_blocks = (int)std::min<int64_t>(cap, 1024); // generic kernel: 1024 scratch slices
         if (per_block) RCCHK(ensure(ctx, wk.gscratch, per_block * (size_t)strong_blocks));
-        HIPCHK(ctx, bcd_launch_bayes_strong(d_colors, d_pixcov, d_mask, (const int32_t *)wk.strong.p, d_c, d_c + 4, strong_blocks, W, H, w, b, min_eig,
+        HIPCHK(ctx, bcd_launch_bayes_strong(d_colors, d_pixcov, d_mask, (const int32_t *)wk.strong.p, &d_c->n_strong, d_c->generic_work, strong_blocks, W, H, w, b, min_eig,
                                             d_sum, d_count, (float *)wk.gscratch.p, wk.gscratch.bytes, wk.stream));
     }
     HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_join, 0));
@@ -730,20 +504,13 @@ int bayes(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixc
 
 void bayes_counts(const Work &wk, int64_t *n_strong, int64_t *n_weak, int64_t *sim_total)
 {
-    *n_strong = wk.h_counters[16];
-    *n_weak = wk.h_counters[17];
-    memcpy(sim_total, wk.h_counters + 18, sizeof(*sim_total));
-}
-
-float stage_ms(Work &wk, int a, int b)
-{
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, wk.ev_stage[a], wk.ev_stage[b]);
-    return ms;
+    *n_strong = wk.h_counters->lists.n_strong;
+    *n_weak = wk.h_counters->lists.n_weak;
+    *sim_total = wk.h_counters->lists.sim_total;
 }
 
 // The estimate stage of the extra colour layers of a scale, on the selection the first layer's chain has just decided (mono_accumulate; the stream is
-// synchronised, wk.h_counters hold the list lengths): nothing is selected, marked or listed again.  The fallback pixels of ALL layers go through one
+// synchronised, wk.h_counters->lists holds the list lengths): nothing is selected, marked or listed again.  The fallback pixels of ALL layers go through one
 // launch of the layered tile kernel on the side stream (3 x 3 patches; other radii: the list kernel per layer), the full-estimate chain runs once per
 // layer over the same item list and work queues with that layer's colours and covariances -- its 9.9 KB records are reused from layer to layer, its redo
 // list (items whose sweep inverse failed ITS matrices' checks) is walked behind each layer's finish kernel.  No kernel gets the count image: it is the
@@ -757,13 +524,12 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
     const int E = lv.n;
     const int64_t npix = (int64_t)W * H;
     const int K = 3 * (2 * w + 1) * (2 * w + 1);
-    int32_t *d_c = (int32_t *)wk.counters.p + 16;
-    const int n_strong = wk.h_counters[16];
-    spectral[0] = wk.h_counters[23];
-    int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100); // (as bayes())
-    if (&wk != &ctx->main) cus = std::max(1, cus * ctx->coarse_share / 100);
-    HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
-    HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
+    Counters::Lists *d_c = &wk.d_counters()->lists;
+    Counters *h = wk.h_counters;
+    const int n_strong = h->lists.n_strong;
+    spectral[0] = h->lists.spectral;
+    const int cus = estimate_cus(ctx, wk);
+    RCCHK(fork_aux(ctx, wk));
     if (w == 1) {
         BcdLayerTable t = {};
         for (int k = 0; k < E; ++k) { t.a[k] = lv.col[k]; t.o[k] = sum[k]; }
@@ -771,29 +537,29 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
     } else {
         const int weak_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), (int64_t)cus * 32);
         for (int k = 0; k < E; ++k)
-            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, (const int32_t *)wk.weak.p, d_c + 1, weak_blocks, W, H, w, b, sum[k], nullptr, wk.aux));
+            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, (const int32_t *)wk.weak.p, &d_c->n_weak, weak_blocks, W, H, w, b, sum[k], nullptr, wk.aux));
     }
     HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
     if (w == 1) {
         const size_t rec = bcd_bayes27_record_bytes();
-        const int chunk_max = 1 << 18; // (as bayes())
+        const int chunk_max = ESTIMATE_CHUNK;
         if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, rec * (size_t)std::min(n_strong, chunk_max)));
         for (int k = 0; k < E; ++k) {
             for (int first = 0; first < n_strong; first += chunk_max) {
                 HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
                 HIPCHK(ctx, bcd_launch_bayes27(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, first, std::min(chunk_max, n_strong - first),
-                                               (int *)wk.work_q.p, cus, W, H, b, min_eig, (float *)wk.gscratch.p, sum[k], nullptr, d_c + 7, wk.stream, 0, nullptr));
+                                               (int *)wk.work_q.p, cus, W, H, b, min_eig, (float *)wk.gscratch.p, sum[k], nullptr, &d_c->spectral, wk.stream, 0, nullptr));
             }
-            HIPCHK(ctx, hipMemcpyAsync(wk.h_counters + 24 + k, d_c + 7, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
+            HIPCHK(ctx, hipMemcpyAsync(&h->layer_redo_total[k], &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
         }
     } else {
         const size_t per_block = bcd_bayes_scratch_bytes_per_block(w, b);
         const int strong_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), 1024);
         if (per_block) RCCHK(ensure(ctx, wk.gscratch, per_block * (size_t)strong_blocks));
         for (int k = 0; k < E; ++k) {
-            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, d_c, d_c + 4, strong_blocks, W, H, w, b, min_eig,
+            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, &d_c->n_strong, d_c->generic_work, strong_blocks, W, H, w, b, min_eig,
                                                 sum[k], nullptr, (float *)wk.gscratch.p, wk.gscratch.bytes, wk.stream));
-            wk.h_counters[24 + k] = wk.h_counters[23];
+            h->layer_redo_total[k] = h->lists.spectral;
         }
     }
     HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_join, 0));
@@ -803,8 +569,8 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
         HIPCHK(ctx, bcd_launch_layers_finalize(t, E, d_count, npix, wk.stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    for (int k = 0; k < E; ++k) spectral[k + 1] = wk.h_counters[24 + k] - (k == 0 ? wk.h_counters[23] : wk.h_counters[24 + k - 1]);
-    wk.h_counters[23] = wk.h_counters[24 + E - 1]; // the scale's figure: the sum over the layers
+    for (int k = 0; k < E; ++k) spectral[k + 1] = h->layer_redo_total[k] - (k == 0 ? h->lists.spectral : h->layer_redo_total[k - 1]);
+    h->lists.spectral = h->layer_redo_total[E - 1]; // the scale's figure: the sum over the layers
     return BCD_HIP_OK;
 }
 
@@ -832,8 +598,7 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
     // The per-pixel covariances (only the estimate stage reads them) and the clearing of the accumulators go to the side stream: the scale's
     // own stream starts with the distance kernel, they run beside it instead of ahead of it / between marking and estimate
-    HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream)); // (the inputs are ready at this point of the scale's stream)
-    HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
+    RCCHK(fork_aux(ctx, wk)); // (the inputs are ready at this point of the scale's stream)
     HIPCHK(ctx, bcd_launch_pixel_cov_clear(d_cov, d_ns, (int64_t)npix, (float *)wk.pixcov.p, d_sum, d_count, wk.aux)); // (+ the accumulators cleared: one launch)
     if (lv && lv->n > 0) { // the same for every further layer, one launch (their sums; the count image is shared)
         RCCHK(ensure(ctx, wk.lay_pixcov, (size_t)lv->n * npix * 6 * sizeof(float)));
@@ -847,12 +612,12 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     // the kernels of the critical path); flags raised by distance planes computed ahead of this call are kept
     {
         constexpr size_t LINE_INTS = (size_t)BCD_CNT_LINES * BCD_CNT_STRIDE;
-        RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
+        RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
         RCCHK(ensure(ctx, wk.cnt_lines, ROUND_BATCH * LINE_INTS * sizeof(int)));
         RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
-        const bool ahead = wk.planes.ready;
-        HIPCHK(ctx, bcd_launch_scale_begin((int *)wk.counters.p, 64, ahead ? 40 : -1, ahead ? 42 : -1, (int *)wk.cnt_lines.p, (int)(ROUND_BATCH * LINE_INTS),
-                                           (int *)wk.work_q.p, BCD_WORK_INTS, wk.stream));
+        const bool ahead = wk.planes.ready; // (its launches raise flags.range and flags.other_count)
+        HIPCHK(ctx, bcd_launch_scale_begin((int *)wk.counters.p, COUNTER_WORDS, ahead ? COUNTER_WORD(flags.range) : -1, ahead ? COUNTER_WORD(flags.other_count) : -1,
+                                           (int *)wk.cnt_lines.p, (int)(ROUND_BATCH * LINE_INTS), (int *)wk.work_q.p, BCD_WORK_INTS, wk.stream));
         wk.clean_flags = wk.clean_lines = wk.clean_dc = wk.clean_wq = true;
     }
     const bool marking = prm->marked_skip_probability > 0.f;
@@ -875,7 +640,7 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
             HIPCHK(ctx, bcd_launch_active_init((const int32_t *)wk.nsim.p, W, H, w, row_begin, row_end, prm->marked_skip_probability, seed, 0, (uint8_t *)wk.state.p, wk.stream));
             wk.dep_ready = false;
             if (attempt == 0) HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_pixcov, 0)); // covariances computed, accumulators cleared (long done)
-            long long *d_total = reinterpret_cast<long long *>((int *)wk.counters.p + 48), *h_total = reinterpret_cast<long long *>(wk.h_counters + 48);
+            long long *d_total = &wk.d_counters()->marking_total, *h_total = &wk.h_counters->marking_total;
             const uint32_t key_seed = prm->use_random_pixel_order == 2 ? bcd_strip_order_seed(W, H, w, b) : seed; // (as active_set)
             int rounds = 0;
             long long before = -1;
@@ -915,7 +680,7 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
     if (d_out) HIPCHK(ctx, bcd_launch_finalize(d_sum, d_count, (int64_t)npix, d_out, wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    if (wk.redo.pending && wk.h_counters[23] > 0) {
+    if (wk.redo.pending && wk.h_counters->lists.spectral > 0) {
         // items whose sweep inverse failed its checks (large -e, ill-conditioned frames): their list goes through the LDS kernel now
         // (spectral inverse), and the finalisation is repeated on the completed accumulators
         HIPCHK(ctx, bcd_launch_bayes27_redo(d_colors, (const float *)wk.pixcov.p, (const uint32_t *)wk.mask.p, (const int32_t *)wk.strong.p, wk.redo.first, wk.redo.n,
@@ -936,9 +701,9 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     bayes_counts(wk, &ns, &nw, &tot);
     st.processed = ns + nw; st.fallback = nw; st.similar_total = tot;
     st.similarity_path = wk.border_capacity > 0 ? (wk.ratio_used ? 2 : 1) : 0;
-    st.borderline_pairs = wk.border_capacity > 0 ? wk.h_counters[43] : 0;
-    st.cu_share = ctx->cu_share_pct * (&wk != &ctx->main ? ctx->coarse_share : 100) / 100;
-    st.spectral_inverses = wk.h_counters[23];
+    st.borderline_pairs = wk.border_capacity > 0 ? wk.h_counters->flags.borderline : 0;
+    st.cu_share = estimate_share_pct(ctx, wk);
+    st.spectral_inverses = wk.h_counters->lists.spectral;
     if (prof) {
         st.ms_similarity = stage_ms(wk, 0, 1);
         st.ms_active = stage_ms(wk, 1, 2);
@@ -1013,7 +778,7 @@ int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream)
         HIPCHK(ctx, hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
         w.owns_stream = true;
     }
-    HIPCHK(ctx, hipHostMalloc((void **)&w.h_counters, 64 * sizeof(int32_t), hipHostMallocDefault));
+    HIPCHK(ctx, hipHostMalloc((void **)&w.h_counters, sizeof(Counters), hipHostMallocDefault));
     for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipEventCreate(&w.ev_stage[i]));
     HIPCHK(ctx, hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
     HIPCHK(ctx, hipEventCreateWithFlags(&w.ev_built, hipEventDisableTiming));
@@ -1210,10 +975,12 @@ int bcd_hip_reset_kernel_time(bcd_hip_ctx *ctx)
     return BCD_HIP_OK;
 }
 
+} // extern "C"
+
 // bcd_hip_denoise, and -- with `lv0`: the layers beyond the first at full resolution -- bcd_hip_denoise_layers: the first layer takes exactly the path of a
 // plain call, the others follow it scale by scale (pyramid level, estimate on the decided selection, merge)
-static int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
-                        int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out, const LayerView *lv0)
+int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
+                 int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out, const LayerView *lv0)
 {
     if (!ctx) return BCD_HIP_EINVAL;
     if (!d_colors || !d_ns || !d_hist || !d_cov || !d_out) return bad(ctx, "null image pointer"); // Denoiser.cpp:266-293
@@ -1348,6 +1115,8 @@ static int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_
     if (lvp) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BCD_HIP_OK;
 }
+
+extern "C" {
 
 int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
                     int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
@@ -1501,204 +1270,6 @@ int bcd_hip_denoise_bands(bcd_hip_ctx *ctx, const bcd_hip_band_job *jobs, int nj
     return BCD_HIP_OK;
 }
 
-// bcd_hip_denoise_host_ex, and -- with `extra`: host images of further colour layers -- bcd_hip_denoise_layers_host: the primary inputs travel as they always
-// did (streamed, the histograms without their zeros), the extra layers as plain copies behind them
-static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
-                             int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out,
-                             const bcd_hip_host_layer *extra, int nb_extra)
-{
-    if (!ctx) return BCD_HIP_EINVAL;
-    if (!h_colors || !h_ns || !h_hist || !h_cov || !h_out) return bad(ctx, "null image pointer");
-    RCCHK(check_params(ctx, W, H, D, prm));
-    DEVICE_GUARD(ctx);
-    const size_t np = (size_t)W * H;
-    const size_t sz[5] = { np * 3, np, np * D, np * 6, np * 3 };
-    const float *src[4] = { h_colors, h_ns, h_hist, h_cov };
-    const bool prefilter = opt && opt->spike_factor > 0.f;
-    if (prefilter && (W < 3 || H < 3)) return bad(ctx, "image smaller than 3x3");
-    // device copies live in the context (grow-only): a sequence of frames pays for the allocations once
-    float *d[9];
-    for (int i = 0; i < 5; ++i) { RCCHK(ensure(ctx, ctx->host_stage[i], sz[i] * sizeof(float))); d[i] = (float *)ctx->host_stage[i].p; }
-    for (int i = 0; i < 4; ++i) {
-        d[5 + i] = d[i];
-        if (prefilter) { RCCHK(ensure(ctx, ctx->host_stage[5 + i], sz[i] * sizeof(float))); d[5 + i] = (float *)ctx->host_stage[5 + i].p; }
-    }
-    // The frame arrives in row chunks on an upload stream; the lines that have arrived are prefiltered (SpikeRemovalFilter::filter,
-    // src/cli/main.cpp:428-441, on the device copies: no second trip over PCIe) and the finest scale's approximate distance planes -- the
-    // largest single kernel of the frame, and a function of the histograms alone -- are computed for them while the next chunk travels.
-    // Everything else needs the whole frame (pyramid, the marking order) and follows the last chunk.
-    const int b = prm->search_radius, tile = bcd_pairdist_rw_tile_lines();
-    const bool stream_in = ctx->stream_uploads && fast_similarity_applies(ctx, D, prm->patch_radius, prm->hist_dist_threshold) && H >= 256;
-    if (!stream_in) {
-        for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipMemcpyAsync(d[i], src[i], sz[i] * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (prefilter) HIPCHK(ctx, bcd_launch_spike(d[0], d[1], d[2], d[3], W, H, D, opt->spike_factor, d[5], d[6], d[7], d[8], ctx->stream));
-    } else {
-        Work &wk = ctx->main;
-        if (!ctx->upload_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
-        const int nd = bcd_delta_count(b);
-        RCCHK(ensure(ctx, wk.T, np * nd * sizeof(float)));
-        RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(np, nd))); // (the size similarity() will ask for: a larger request there would REALLOCATE the planes computed here)
-        RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-        int *d_flag = (int *)wk.counters.p + 40;
-        HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4 * sizeof(int), ctx->stream));
-        // uniform power-of-two sample count: taken from the first pixel; the distance kernel checks every pixel against it and raises the
-        // flag that sends the scale to the exact kernels if the guess was wrong (k_pairdist_rw, range_flag bit 1)
-        // (a strided sample of 1024 pixels settles the usual non-uniform case -- adaptive sampling -- on the host at no cost)
-        float uni_n = 0.f;
-        {
-            int e = 0;
-            const float n0 = h_ns[0];
-            if (n0 >= 1.f && n0 <= 65536.f && frexpf(n0, &e) == 0.5f) uni_n = n0;
-            const size_t stride = std::max<size_t>(1, np / 1024);
-            for (size_t i = 0; i < np && uni_n > 0.f; i += stride)
-                if (h_ns[i] != n0) uni_n = 0.f;
-        }
-        const int chunk = std::max(64, ((H + 7) / 8 + tile - 1) / tile * tile); // ~8 chunks, whole tile rows
-        const int tile_rows = (H + tile - 1) / tile;
-        int filtered = 0, tiles_done = 0, k = 0;
-        // the upload stream must not overwrite device copies an earlier frame's kernels may still read
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        // colours, sample counts and covariances first, whole (83 MB at 1080p; the prefilter and the distance kernel need them with the
-        // first histogram lines), then the histograms -- 87 % of the bytes -- in row chunks
-        // Without the prefilter only the sample counts are needed with the first histogram lines (the distance kernel); colours and covariances
-        // are first read by the pyramid and the estimate stage.  Their (pageable, host-blocking) copies then run on a helper thread and a
-        // stream of their own beside the histogram pieces, whose pace is set by the host-side packing and leaves the link half idle (round 4).
-        std::thread side_copy;
-        hipError_t side_rc = hipSuccess;
-        struct SideJoin { std::thread &t; ~SideJoin() { if (t.joinable()) t.join(); } } side_join{ side_copy };
-        const bool side = !prefilter && ctx->sparse_uploads && (D & 3) == 0;
-        if (side) {
-            if (!ctx->upload_stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream2, hipStreamNonBlocking));
-            if (!ctx->ev_upload2) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_upload2, hipEventDisableTiming));
-            HIPCHK(ctx, hipMemcpyAsync(d[1], src[1], sz[1] * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
-            const int dev = ctx->device;
-            hipStream_t s2 = ctx->upload_stream2;
-            hipEvent_t e2 = ctx->ev_upload2;
-            float *dc = d[0], *dv = d[3];
-            const float *hc = src[0], *hv = src[3];
-            const size_t nc = sz[0] * sizeof(float), nv = sz[3] * sizeof(float);
-            side_copy = std::thread([=, &side_rc]() {
-                hipError_t e = hipSetDevice(dev);
-                if (e == hipSuccess) e = hipMemcpyAsync(dc, hc, nc, hipMemcpyHostToDevice, s2);
-                if (e == hipSuccess) e = hipMemcpyAsync(dv, hv, nv, hipMemcpyHostToDevice, s2);
-                if (e == hipSuccess) e = hipEventRecord(e2, s2);
-                side_rc = e;
-            });
-        } else
-            for (int i : { 0, 1, 3 }) HIPCHK(ctx, hipMemcpyAsync(d[i], src[i], sz[i] * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
-        const bool sparse = ctx->sparse_uploads && (D & 3) == 0;
-        if (sparse) {
-            if (!ctx->sparse && !(ctx->sparse = bcd_sparse_create())) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
-            bcd_sparse_frame_begin(ctx->sparse);
-        }
-        ctx->upload_raw_bytes = ctx->upload_sent_bytes = (long long)sz[2] * 4;
-        for (int r0 = 0; r0 < H; r0 += chunk, ++k) {
-            const int r1 = std::min(H, r0 + chunk);
-            {
-                const size_t off = (size_t)r0 * W * D, n = (size_t)(r1 - r0) * W * D;
-                if (sparse) HIPCHK(ctx, bcd_sparse_upload(ctx->sparse, d[2] + off, h_hist + off, n, ctx->upload_stream)); // (off % 4 == 0: D % 4 == 0 on this path)
-                else HIPCHK(ctx, hipMemcpyAsync(d[2] + off, h_hist + off, n * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
-            }
-            if ((int)ctx->ev_upload.size() <= k) {
-                hipEvent_t ev;
-                HIPCHK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                ctx->ev_upload.push_back(ev);
-            }
-            HIPCHK(ctx, hipEventRecord(ctx->ev_upload[k], ctx->upload_stream));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload[k], 0));
-            int avail = r1;
-            if (prefilter) { // a filtered line reads its own and the two adjacent input lines (clamped inward at the frame border)
-                const int upto = r1 == H ? H : std::max(0, r1 - 1);
-                HIPCHK(ctx, bcd_launch_spike_rows(d[0], d[1], d[2], d[3], W, H, D, opt->spike_factor, d[5], d[6], d[7], d[8], filtered, upto, ctx->stream));
-                filtered = std::max(filtered, upto);
-                avail = filtered;
-            }
-            // a tile row reads its own lines and the b lines below them
-            const int t_end = avail == H ? tile_rows : std::max(0, (avail - b) / tile);
-            if (t_end > tiles_done) {
-                HIPCHK(ctx, bcd_launch_pairdist_rw_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, uni_n, tiles_done, t_end, ctx->stream));
-                tiles_done = t_end;
-            }
-        }
-        if (sparse) bcd_sparse_frame_bytes(ctx->sparse, &ctx->upload_raw_bytes, &ctx->upload_sent_bytes);
-        if (side) { // colours and covariances have been enqueued by now (the helper thread is joined), the frame's kernels wait for their arrival
-            side_copy.join();
-            HIPCHK(ctx, side_rc);
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload2, 0));
-        }
-        wk.planes.ready = true; wk.planes.hist = d[7]; wk.planes.ns = d[6]; wk.planes.W = W; wk.planes.H = H; wk.planes.D = D; wk.planes.b = b;
-        wk.planes.tau = prm->hist_dist_threshold; wk.planes.uni_n = uni_n;
-    }
-    LayerView lv;
-    if (nb_extra > 0) { // device copies of the extra layers: colours | covariances | outputs, one slice per layer
-        auto fail = [&](int rc) { ctx->main.planes.ready = false; return rc; };
-        for (int i = 0; i < 3; ++i)
-            if (ensure(ctx, ctx->lay_host[i], (size_t)nb_extra * np * (i == 1 ? 6 : 3) * sizeof(float)) != BCD_HIP_OK) return fail(BCD_HIP_ENOMEM);
-        lv.n = nb_extra;
-        for (int k = 0; k < nb_extra; ++k) {
-            float *dc = (float *)ctx->lay_host[0].p + k * np * 3, *dv = (float *)ctx->lay_host[1].p + k * np * 6;
-            lv.col[k] = dc; lv.cov[k] = dv; lv.out[k] = (float *)ctx->lay_host[2].p + k * np * 3;
-            if (hipMemcpyAsync(dc, extra[k].h_colors, np * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(dv, extra[k].h_covariances, np * 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-                set_err(ctx, "upload of a colour layer failed");
-                return fail(BCD_HIP_EDEVICE);
-            }
-        }
-    }
-    {
-        const int rc = denoise_impl(ctx, d[5], d[6], d[7], d[8], W, H, D, nb_scales, prm, d[4], nb_extra > 0 ? &lv : nullptr);
-        ctx->main.planes.ready = false; // (consumed by the finest scale's similarity stage; never left behind by a call that failed earlier)
-        if (rc != BCD_HIP_OK) return rc;
-    }
-    // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:389-420, 470)
-    if (opt && opt->zero_bad_values) HIPCHK(ctx, bcd_launch_zero_bad(d[4], (int64_t)np * 3, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, d[4], sz[4] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (nb_extra > 0) {
-        if (opt && opt->zero_bad_values) HIPCHK(ctx, bcd_launch_zero_bad(lv.out[0], (int64_t)nb_extra * np * 3, ctx->stream)); // (the outputs lie one behind the other)
-        for (int k = 0; k < nb_extra; ++k) HIPCHK(ctx, hipMemcpyAsync(extra[k].h_out, lv.out[k], np * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_denoise_host_ex(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
-                            int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out)
-{
-    return denoise_host_impl(ctx, h_colors, h_ns, h_hist, h_cov, W, H, D, nb_scales, prm, opt, h_out, nullptr, 0);
-}
-
-int bcd_hip_denoise_layers_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
-                                const bcd_hip_host_options *opt, const bcd_hip_host_layer *layers, int nb_layers)
-{
-    if (!ctx) return BCD_HIP_EINVAL;
-    if (!h_ns || !h_hist) return bad(ctx, "null image pointer");
-    if (!layers) return bad(ctx, "null layer list");
-    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
-    for (int k = 0; k < nb_layers; ++k) {
-        if (!layers[k].h_colors || !layers[k].h_covariances || !layers[k].h_out) return bad(ctx, "null image pointer in a layer");
-        for (int j = 0; j < k; ++j) if (layers[j].h_out == layers[k].h_out) return bad(ctx, "two layers share an output image");
-    }
-    if (nb_layers > 1 && opt && opt->spike_factor > 0.f) {
-        set_err(ctx, "the spike prefilter moves whole pixels by the first layer's colours: it is not available with several layers");
-        return BCD_HIP_EUNSUPPORTED;
-    }
-    return denoise_host_impl(ctx, layers[0].h_colors, h_ns, h_hist, layers[0].h_covariances, W, H, D, nb_scales, prm, opt, layers[0].h_out, layers + 1, nb_layers - 1);
-}
-
-int bcd_hip_last_upload_bytes(const bcd_hip_ctx *ctx, int64_t *hist_bytes, int64_t *hist_bytes_sent)
-{
-    if (!ctx || !hist_bytes || !hist_bytes_sent) return BCD_HIP_EINVAL;
-    *hist_bytes = ctx->upload_raw_bytes;
-    *hist_bytes_sent = ctx->upload_sent_bytes;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_denoise_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
-                         int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *h_out)
-{
-    return bcd_hip_denoise_host_ex(ctx, h_colors, h_ns, h_hist, h_cov, W, H, D, nb_scales, prm, nullptr, h_out);
-}
-
 int bcd_hip_set_progress_callback(bcd_hip_ctx *ctx, bcd_hip_progress_fn fn, void *user)
 {
     if (!ctx) return BCD_HIP_EINVAL;
@@ -1723,11 +1294,11 @@ int bcd_hip_scale_begin(bcd_hip_ctx *ctx, const float *d_cov, const float *d_ns,
     DEVICE_GUARD(ctx);
     Work &wk = ctx->main;
     constexpr size_t LINE_INTS = (size_t)BCD_CNT_LINES * BCD_CNT_STRIDE;
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
     RCCHK(ensure(ctx, wk.cnt_lines, ROUND_BATCH * LINE_INTS * sizeof(int)));
     RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
     HIPCHK(ctx, bcd_launch_pixel_cov_clear(d_cov, d_ns, (int64_t)W * H, d_pixcov, d_sum, d_count, wk.stream));
-    HIPCHK(ctx, bcd_launch_scale_begin((int *)wk.counters.p, 64, -1, -1, (int *)wk.cnt_lines.p, (int)(ROUND_BATCH * LINE_INTS), (int *)wk.work_q.p, BCD_WORK_INTS, wk.stream));
+    HIPCHK(ctx, bcd_launch_scale_begin((int *)wk.counters.p, COUNTER_WORDS, -1, -1, (int *)wk.cnt_lines.p, (int)(ROUND_BATCH * LINE_INTS), (int *)wk.work_q.p, BCD_WORK_INTS, wk.stream));
     // ("clean" = zero because nobody has used it since: every user of these buffers takes the note and clears it)
     wk.clean_flags = wk.clean_lines = wk.clean_dc = wk.clean_wq = true;
     wk.planes.ready = false;
@@ -1888,7 +1459,7 @@ int bcd_hip_bayes_accumulate_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_layer 
     Work &wk = ctx->main;
     RCCHK(bayes(ctx, wk, layers[0].d_colors, layers[0].d_pixel_cov, d_mask, d_nsim, d_state, W, H, w, b, min_eig, layers[0].d_sum, d_count));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream)); // (the list lengths and the first layer's redo counter are on the host: what mono_accumulate hands over)
-    int32_t spectral[BCD_MAX_LAYERS] = { wk.h_counters[23] };
+    int32_t spectral[BCD_MAX_LAYERS] = { wk.h_counters->lists.spectral };
     if (nb_layers > 1) {
         LayerView lv;
         lv.n = nb_layers - 1;
@@ -1977,7 +1548,7 @@ int bcd_hip_bayes_last_redo_count(bcd_hip_ctx *ctx, int32_t *count)
     if (!ctx || !count) return bad(ctx, "bad argument");
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream)); // (the counter's copy is the last thing bayes() enqueues)
-    *count = ctx->main.h_counters[23];
+    *count = ctx->main.h_counters->lists.spectral;
     return BCD_HIP_OK;
 }
 
@@ -2079,798 +1650,6 @@ int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n)
     if (!ctx || !d_img || n <= 0) return bad(ctx, "bad argument");
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, bcd_launch_zero_bad(d_img, n, ctx->stream));
-    return BCD_HIP_OK;
-}
-
-// ---- persistent device SamplesAccumulator (k_accumulate.hip) ----------------------------------------------------
-struct bcd_hip_accum {
-    bcd_hip_ctx *ctx = nullptr;
-    int W = 0, H = 0, nbins = 0;
-    float gamma = 0.f, maxval = 0.f;
-    int64_t N = 0;
-    DevBuf state;                  // (11 + 3 nbins) planes of N floats
-    DevBuf dropped;                // unsigned long long: scattered samples with an index outside [0, N)
-    DevBuf keys[2], vals[2], sort; // scattered-add scratch (grow-only)
-    int64_t capacity = 0;          // > 0: samples per sorted chunk, scratch allocated at create time
-    int64_t submitted = 0;         // samples handed to add_* since the last reset
-    DevBuf plan_red, plan_c, plan_ends, plan_err, plan_cnt, plan_tmp; // adaptive-plan scratch (allocated once per accumulator)
-    bool plan_ready = false;       // the plan scratch is allocated (N is fixed, so it is never resized)
-    // states (export / import / merge): two pinned staging chunks and two device chunks of at most STATE_CHUNK bytes, allocated on first
-    // use; stage_busy[i]: a copy out of stage[i] may still be in flight (stage_ev[i] marks its end)
-    void *stage[2] = { nullptr, nullptr };
-    void *chunk[2] = { nullptr, nullptr };
-    hipEvent_t stage_ev[2] = { nullptr, nullptr };
-    bool stage_busy[2] = { false, false };
-    size_t chunk_bytes = 0;
-    hipEvent_t ev_merge = nullptr; // recorded on the context's stream around a merge (the source's work so far / the destination's reads)
-    // reconstruction filter of the splatted add (bcd_hip_accum_set_filter): the parameters are kernel arguments, the table lives on the
-    // device and is replaced in stream order through a pinned staging copy (filter_ev: that copy has left the staging buffer)
-    bool has_filter = false;
-    float filter_f[4] = { 0.f, 0.f, 0.f, 0.f }; // rx, ry, inv_rx, inv_ry
-    int filter_g[5] = { 0, 0, 0, 0, 0 };        // table size, kx, ky, nx, ny
-    DevBuf table, cells;                        // the table (64 x 64 floats at most); the runs of the extended frame's cells (grow-only)
-    float *table_stage = nullptr;
-    hipEvent_t filter_ev = nullptr;
-    bool filter_busy = false;
-};
-
-namespace {
-
-size_t accum_state_bytes(const bcd_hip_accum *a) { return (size_t)(11 + 3 * a->nbins) * (size_t)a->N * sizeof(float); }
-
-// scratch of the scattered path for chunks of n samples
-int accum_scratch(bcd_hip_accum *a, int64_t n)
-{
-    bcd_hip_ctx *ctx = a->ctx;
-    for (int i = 0; i < 2; ++i) {
-        RCCHK(ensure(ctx, a->keys[i], (size_t)n * sizeof(uint32_t)));
-        RCCHK(ensure(ctx, a->vals[i], (size_t)n * sizeof(uint32_t)));
-    }
-    size_t bytes = 0;
-    const int end_bit = 64 - __builtin_clzll((unsigned long long)a->N); // keys are <= N (N = dropped)
-    HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, n, end_bit, ctx->stream));
-    RCCHK(ensure(ctx, a->sort, bytes));
-    return BCD_HIP_OK;
-}
-
-// scratch of the adaptive plan: reductions, C (uint64), ends (int32), the error and counts images used when the caller passes none, and
-// the scans' temporary storage; the frame size is fixed, so this sizes and allocates once (a failed attempt is retried by the next plan)
-int accum_plan_scratch(bcd_hip_accum *a)
-{
-    if (a->plan_ready) return BCD_HIP_OK;
-    bcd_hip_ctx *ctx = a->ctx;
-    const size_t N = (size_t)a->N;
-    size_t tmp = 0;
-    HIPCHK(ctx, bcd_plan_scan_bytes(a->N, &tmp));
-    RCCHK(ensure(ctx, a->plan_red, bcd_plan_red_bytes()));
-    RCCHK(ensure(ctx, a->plan_c, N * sizeof(uint64_t)));
-    RCCHK(ensure(ctx, a->plan_ends, N * sizeof(int32_t)));
-    RCCHK(ensure(ctx, a->plan_err, N * sizeof(float)));
-    RCCHK(ensure(ctx, a->plan_cnt, N * sizeof(int32_t)));
-    RCCHK(ensure(ctx, a->plan_tmp, tmp));
-    a->plan_ready = true;
-    return BCD_HIP_OK;
-}
-
-// cells of the frame extended by (kx, ky) on each side (the key space of the splatted add)
-#define SPLAT_MAX_K 4
-int64_t accum_extended_cells(const bcd_hip_accum *a, int kx, int ky) { return ((int64_t)a->W + 2 * kx) * ((int64_t)a->H + 2 * ky); }
-
-// scratch of the splatted add for any filter, beside accum_scratch's: the cell runs and the sort's storage for the wider keys
-int accum_splat_scratch(bcd_hip_accum *a)
-{
-    bcd_hip_ctx *ctx = a->ctx;
-    const int64_t NE = accum_extended_cells(a, SPLAT_MAX_K, SPLAT_MAX_K);
-    if (NE >= ((int64_t)1 << 32) - 1) return BCD_HIP_OK; // (set_filter refuses such frames)
-    RCCHK(ensure(ctx, a->cells, (size_t)NE * 2 * sizeof(uint32_t)));
-    size_t bytes = 0;
-    HIPCHK(ctx, bcd_accum_sort(nullptr, &bytes, nullptr, nullptr, nullptr, nullptr, a->capacity, 64 - __builtin_clzll((unsigned long long)NE), ctx->stream));
-    if (bytes > a->sort.bytes) RCCHK(ensure(ctx, a->sort, bytes));
-    return BCD_HIP_OK;
-}
-
-} // namespace
-
-int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc)
-{
-    if (!ctx) return BCD_HIP_EINVAL;
-    if (!acc) return bad(ctx, "null accumulator handle");
-    *acc = nullptr;
-    if (W <= 0 || H <= 0 || (int64_t)W * H >= ((int64_t)1 << 31)) return bad(ctx, "frame size must be positive and below 2^31 pixels");
-    if (nb_bins < 2) return bad(ctx, "nb_bins must be >= 2");
-    if (bcd_accum_snapshot_lds(3 * nb_bins) > 64 * 1024) { set_err(ctx, "more than 85 bins per channel are not supported"); return BCD_HIP_EUNSUPPORTED; }
-    if (max_batch_samples < 0 || max_batch_samples >= ((int64_t)1 << 31)) return bad(ctx, "max_batch_samples must be in [0, 2^31)");
-    DEVICE_GUARD(ctx);
-    bcd_hip_accum *a = new (std::nothrow) bcd_hip_accum();
-    if (!a) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
-    a->ctx = ctx; a->W = W; a->H = H; a->nbins = nb_bins; a->gamma = gamma; a->maxval = max_value;
-    a->N = (int64_t)W * H;
-    a->capacity = max_batch_samples;
-    int rc = ensure(ctx, a->state, accum_state_bytes(a));
-    if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
-    if (rc == BCD_HIP_OK && hipEventCreateWithFlags(&a->ev_merge, hipEventDisableTiming) != hipSuccess) {
-        a->ev_merge = nullptr;
-        set_err(ctx, "hipEventCreateWithFlags failed");
-        rc = BCD_HIP_EDEVICE;
-    }
-    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_scratch(a, a->capacity);
-    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_plan_scratch(a);
-    if (rc == BCD_HIP_OK && a->capacity > 0) rc = accum_splat_scratch(a);
-    if (rc == BCD_HIP_OK) rc = bcd_hip_accum_reset(a);
-    if (rc != BCD_HIP_OK) { bcd_hip_accum_destroy(a); return rc; }
-    *acc = a;
-    return BCD_HIP_OK;
-}
-
-void bcd_hip_accum_destroy(bcd_hip_accum *acc)
-{
-    if (!acc) return;
-    DeviceGuard guard(acc->ctx);
-    (void)hipStreamSynchronize(acc->ctx->stream);
-    for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
-                       &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
-        if (b->p) (void)hipFree(b->p);
-    for (DevBuf *b : { &acc->table, &acc->cells })
-        if (b->p) (void)hipFree(b->p);
-    if (acc->table_stage) (void)hipHostFree(acc->table_stage);
-    if (acc->filter_ev) (void)hipEventDestroy(acc->filter_ev);
-    for (int i = 0; i < 2; ++i) {
-        if (acc->stage[i]) (void)hipHostFree(acc->stage[i]);
-        if (acc->chunk[i]) (void)hipFree(acc->chunk[i]);
-        if (acc->stage_ev[i]) (void)hipEventDestroy(acc->stage_ev[i]);
-    }
-    if (acc->ev_merge) (void)hipEventDestroy(acc->ev_merge);
-    delete acc;
-}
-
-int bcd_hip_accum_reset(bcd_hip_accum *acc)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    DEVICE_GUARD(ctx);
-    HIPCHK(ctx, hipMemsetAsync(acc->state.p, 0, accum_state_bytes(acc), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(acc->dropped.p, 0, sizeof(unsigned long long), ctx->stream));
-    acc->submitted = 0;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (!d_samples) return bad(ctx, "null samples");
-    if (channels != 3 && channels != 4) return bad(ctx, "channels must be 3 or 4");
-    if (spp < 1) return bad(ctx, "spp must be >= 1");
-    if (rows < 1 || row_begin < 0 || row_begin > acc->H - rows) return bad(ctx, "row range outside the frame");
-    DEVICE_GUARD(ctx);
-    const int64_t npix = (int64_t)rows * acc->W;
-    HIPCHK(ctx, bcd_launch_accum_dense(d_samples, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, channels, acc->nbins, acc->gamma,
-                                       acc->maxval, (float *)acc->state.p, ctx->stream));
-    acc->submitted += npix * spp;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (n < 0) return bad(ctx, "negative sample count");
-    if (n == 0) return BCD_HIP_OK;
-    if (!d_pixel || !d_rgb) return bad(ctx, "null samples");
-    DEVICE_GUARD(ctx);
-    const int64_t chunk = acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30);
-    if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
-    const int end_bit = 64 - __builtin_clzll((unsigned long long)acc->N);
-    uint32_t *k0 = (uint32_t *)acc->keys[0].p, *k1 = (uint32_t *)acc->keys[1].p, *v0 = (uint32_t *)acc->vals[0].p, *v1 = (uint32_t *)acc->vals[1].p;
-    for (int64_t b = 0; b < n; b += chunk) { // chunks in stream order: a pixel's samples of chunk c are applied after those of chunk c - 1
-        const int64_t m = std::min(chunk, n - b);
-        size_t bytes = acc->sort.bytes;
-        HIPCHK(ctx, bcd_launch_accum_keys(d_pixel + b, m, acc->N, k0, v0, (unsigned long long *)acc->dropped.p, ctx->stream));
-        HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
-        HIPCHK(ctx, bcd_launch_accum_segments(k1, v1, m, acc->N, d_rgb + b * 3, d_weights ? d_weights + b : nullptr, acc->nbins, acc->gamma,
-                                              acc->maxval, (float *)acc->state.p, ctx->stream));
-    }
-    acc->submitted += n;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y, int table_size, const float *h_table)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (!h_table) { acc->has_filter = false; return BCD_HIP_OK; }
-    if (!(radius_x > 0.f && radius_x <= 3.f) || !(radius_y > 0.f && radius_y <= 3.f)) return bad(ctx, "filter radii must be in (0, 3]");
-    if (table_size < 1 || table_size > 64) return bad(ctx, "filter table size must be in [1, 64]");
-    const int tt = table_size * table_size;
-    for (int i = 0; i < tt; ++i)
-        if (!std::isfinite(h_table[i]) || h_table[i] < 0.f)
-            return bad(ctx, "filter table entries must be finite and >= 0 (filters with negative lobes are not supported)");
-    const int kx = (int)ceilf(radius_x + 0.5f), ky = (int)ceilf(radius_y + 0.5f);
-    // (col + 0.5f must be exact for the kernel's neighbour range, and the cells' keys are 32 bits wide)
-    if (accum_extended_cells(acc, kx, ky) >= ((int64_t)1 << 32) - 1 || std::max(acc->W, acc->H) >= (1 << 22)) {
-        set_err(ctx, "frames of 2^22 pixels or more on a side are not supported with a filter");
-        return BCD_HIP_EUNSUPPORTED;
-    }
-    DEVICE_GUARD(ctx);
-    RCCHK(ensure(ctx, acc->table, 64 * 64 * sizeof(float)));
-    if (!acc->table_stage) HIPCHK(ctx, hipHostMalloc((void **)&acc->table_stage, 64 * 64 * sizeof(float), hipHostMallocDefault));
-    if (!acc->filter_ev) HIPCHK(ctx, hipEventCreateWithFlags(&acc->filter_ev, hipEventDisableTiming));
-    if (acc->filter_busy) { HIPCHK(ctx, hipEventSynchronize(acc->filter_ev)); acc->filter_busy = false; }
-    std::memcpy(acc->table_stage, h_table, (size_t)tt * sizeof(float));
-    HIPCHK(ctx, hipMemcpyAsync(acc->table.p, acc->table_stage, (size_t)tt * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipEventRecord(acc->filter_ev, ctx->stream));
-    acc->filter_busy = true;
-    // cells further than n from a pixel hold no sample within the radius: a sample of a cell at offset n + 1 is at least n + 0.5 away
-    // (exactly representable, and the rounded subtraction is monotone), so n is the smallest integer with n + 0.5 >= r -- never more
-    // than K, the candidate range of the definition
-    int nx = 0, ny = 0;
-    while ((float)nx + 0.5f < radius_x) ++nx;
-    while ((float)ny + 0.5f < radius_y) ++ny;
-    acc->filter_f[0] = radius_x; acc->filter_f[1] = radius_y; acc->filter_f[2] = 1.f / radius_x; acc->filter_f[3] = 1.f / radius_y;
-    acc->filter_g[0] = table_size; acc->filter_g[1] = kx; acc->filter_g[2] = ky;
-    acc->filter_g[3] = std::min(nx, kx); acc->filter_g[4] = std::min(ny, ky);
-    acc->has_filter = true;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (!acc->has_filter) return bad(ctx, "the accumulator has no filter (bcd_hip_accum_set_filter)");
-    if (n < 0) return bad(ctx, "negative sample count");
-    if (n == 0) return BCD_HIP_OK;
-    if (!d_xy || !d_rgb) return bad(ctx, "null samples");
-    DEVICE_GUARD(ctx);
-    const int *g = acc->filter_g;
-    const int64_t NE = accum_extended_cells(acc, g[1], g[2]);
-    // a chunk holds at most as many samples as keep the average ring of a tile within 0.55 of the staging arrays (chunks are applied in
-    // stream order, so splitting a batch changes no bit); denser tiles take the kernel's global-memory path
-    const int max_staged = bcd_splat_max_staged(g[0]), ring = bcd_splat_ring_cells(g[3], g[4]);
-    const int64_t dense = std::max<int64_t>((int64_t)1 << 16, (int64_t)((double)acc->N * 0.55 * max_staged / ring));
-    const int64_t chunk = std::min(dense, acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30));
-    if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
-    RCCHK(ensure(ctx, acc->cells, (size_t)NE * 2 * sizeof(uint32_t)));
-    const int end_bit = 64 - __builtin_clzll((unsigned long long)NE); // keys are <= NE (NE = dropped)
-    size_t need = 0;
-    HIPCHK(ctx, bcd_accum_sort(nullptr, &need, nullptr, nullptr, nullptr, nullptr, std::min(n, chunk), end_bit, ctx->stream));
-    RCCHK(ensure(ctx, acc->sort, need)); // (more key bits than the scattered add's: the storage may differ)
-    uint32_t *k0 = (uint32_t *)acc->keys[0].p, *k1 = (uint32_t *)acc->keys[1].p, *v0 = (uint32_t *)acc->vals[0].p, *v1 = (uint32_t *)acc->vals[1].p;
-    for (int64_t b = 0; b < n; b += chunk) {
-        const int64_t m = std::min(chunk, n - b);
-        const float *xy = d_xy + 2 * b, *rgb = d_rgb + 3 * b, *w = d_weights ? d_weights + b : nullptr;
-        size_t bytes = acc->sort.bytes;
-        HIPCHK(ctx, bcd_launch_splat_keys(xy, m, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, k0, v0,
-                                          (unsigned long long *)acc->dropped.p, ctx->stream));
-        HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
-        HIPCHK(ctx, bcd_launch_splat_cells(k1, m, NE, acc->cells.p, ctx->stream));
-        // staging arrays for 1.5 times the average ring of this chunk plus 8 sigma of a uniform distribution
-        const double avg = (double)m * ring / (double)acc->N;
-        const int cap = (int)std::min<double>(max_staged, 1.5 * avg + 8.0 * std::sqrt(avg) + 64.0);
-        HIPCHK(ctx, bcd_launch_splat(acc->cells.p, v1, xy, rgb, w, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, cap, acc->nbins,
-                                     acc->gamma, acc->maxval, (float *)acc->state.p, ctx->stream));
-    }
-    acc->submitted += n;
-    return BCD_HIP_OK;
-}
-
-// separable table of a standard filter (host only); 1-D factors at d = (i + 0.5) / TS * r in double, product rounded to float once
-int bcd_hip_filter_table(int kind, float radius_x, float radius_y, float param, int table_size, float *h_out)
-{
-    if (!h_out || table_size < 1 || table_size > 64) return BCD_HIP_EINVAL;
-    if (!(radius_x > 0.f && radius_x <= 3.f) || !(radius_y > 0.f && radius_y <= 3.f)) return BCD_HIP_EINVAL;
-    if (kind < BCD_HIP_FILTER_BOX || kind > BCD_HIP_FILTER_BLACKMAN_HARRIS) return BCD_HIP_EINVAL;
-    if (kind == BCD_HIP_FILTER_GAUSSIAN && !(std::isfinite(param) && param >= 0.f)) return BCD_HIP_EINVAL;
-    auto f1 = [&](double d, double r) -> double {
-        switch (kind) {
-        case BCD_HIP_FILTER_BOX: return 1.0;
-        case BCD_HIP_FILTER_TENT: return std::max(0.0, 1.0 - d / r);
-        case BCD_HIP_FILTER_GAUSSIAN: return std::max(0.0, std::exp(-(double)param * d * d) - std::exp(-(double)param * r * r));
-        default: { // Blackman-Harris window of width 2 r centred on the sample
-            const double pi = 3.14159265358979323846, u = (d + r) / (2.0 * r);
-            return std::max(0.0, 0.35875 - 0.48829 * std::cos(2.0 * pi * u) + 0.14128 * std::cos(4.0 * pi * u) - 0.01168 * std::cos(6.0 * pi * u));
-        }
-        }
-    };
-    for (int iy = 0; iy < table_size; ++iy)
-        for (int ix = 0; ix < table_size; ++ix) {
-            const double dx = (ix + 0.5) / table_size * (double)radius_x, dy = (iy + 0.5) / table_size * (double)radius_y;
-            h_out[iy * table_size + ix] = (float)(f1(dx, (double)radius_x) * f1(dy, (double)radius_y));
-        }
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (!d_nsamples || !d_mean || !d_cov || !d_hist) return bad(ctx, "null output");
-    DEVICE_GUARD(ctx);
-    HIPCHK(ctx, bcd_launch_accum_snapshot((const float *)acc->state.p, acc->N, 3 * acc->nbins, d_nsamples, d_mean, d_cov, d_hist, ctx->stream));
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    DEVICE_GUARD(ctx);
-    unsigned long long d = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&d, acc->dropped.p, sizeof(d), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (samples_added) *samples_added = acc->submitted - (int64_t)d;
-    if (dropped) *dropped = (int64_t)d;
-    return BCD_HIP_OK;
-}
-
-// k_plan_summary writes the summary as int64[3] then a float
-static_assert(sizeof(bcd_hip_plan_summary) == 32 && offsetof(bcd_hip_plan_summary, max_error) == 24, "bcd_hip_plan_summary layout");
-
-void bcd_hip_default_plan_params(bcd_hip_plan_params *p)
-{
-    if (!p) return;
-    p->threshold = 0.f;
-    p->eps = 1e-3f;
-    p->min_samples = 2.f;
-    p->max_per_pixel = 16;
-}
-
-int bcd_hip_accum_plan(bcd_hip_accum *acc, const bcd_hip_plan_params *prm, int64_t budget, uint64_t offset, float *d_error, int32_t *d_counts,
-                       int32_t *d_pixels, int64_t capacity, bcd_hip_plan_summary *d_summary)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (!prm) return bad(ctx, "null plan parameters");
-    if (!d_pixels || !d_summary) return bad(ctx, "null pixel list or summary");
-    if (budget < 0 || budget > INT32_MAX) return bad(ctx, "budget must be in [0, 2^31)");
-    if (capacity < budget) return bad(ctx, "pixel list capacity below the budget");
-    if (!std::isfinite(prm->threshold) || prm->threshold < 0.f) return bad(ctx, "threshold must be finite and >= 0");
-    if (!std::isfinite(prm->eps) || !(prm->eps > 0.f)) return bad(ctx, "eps must be finite and > 0");
-    if (!std::isfinite(prm->min_samples) || prm->min_samples < 0.f) return bad(ctx, "min_samples must be finite and >= 0");
-    if (prm->max_per_pixel < 1 || prm->max_per_pixel > 65535) return bad(ctx, "max_per_pixel must be in [1, 65535]");
-    DEVICE_GUARD(ctx);
-    RCCHK(accum_plan_scratch(acc));
-    HIPCHK(ctx, hipMemsetAsync(acc->plan_red.p, 0, bcd_plan_red_bytes(), ctx->stream));
-    HIPCHK(ctx, bcd_launch_accum_plan((const float *)acc->state.p, acc->N, prm->eps, prm->min_samples, prm->threshold, prm->max_per_pixel, budget,
-                                      offset, d_error ? d_error : (float *)acc->plan_err.p, d_counts ? d_counts : (int32_t *)acc->plan_cnt.p,
-                                      d_pixels, capacity, (int64_t *)d_summary, acc->plan_red.p, (uint64_t *)acc->plan_c.p,
-                                      (int32_t *)acc->plan_ends.p, acc->plan_tmp.p, acc->plan_tmp.bytes, ctx->stream));
-    return BCD_HIP_OK;
-}
-
-// ---- states: export, import, merge -----------------------------------------------------------------------------
-static_assert(sizeof(bcd_hip_accum_state_header) == BCD_HIP_ACCUM_STATE_HEADER_BYTES && offsetof(bcd_hip_accum_state_header, version) == 8 &&
-                  offsetof(bcd_hip_accum_state_header, header_bytes) == 12 && offsetof(bcd_hip_accum_state_header, width) == 16 &&
-                  offsetof(bcd_hip_accum_state_header, height) == 20 && offsetof(bcd_hip_accum_state_header, nb_bins) == 24 &&
-                  offsetof(bcd_hip_accum_state_header, gamma) == 28 && offsetof(bcd_hip_accum_state_header, max_value) == 32 &&
-                  offsetof(bcd_hip_accum_state_header, nb_planes) == 36 && offsetof(bcd_hip_accum_state_header, samples_added) == 40 &&
-                  offsetof(bcd_hip_accum_state_header, dropped) == 48 && offsetof(bcd_hip_accum_state_header, reserved) == 56,
-              "bcd_hip_accum_state_header layout (format v1)");
-
-namespace {
-
-constexpr size_t STATE_CHUNK = (size_t)64 << 20; // bound of a staging / scratch chunk
-const char STATE_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'S', 'T' };
-
-// what is wrong with a serialised state of `bytes` bytes (its header copied to *hd), or nullptr
-const char *state_problem(const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
-{
-    if (!h) return "null state";
-    if (bytes < BCD_HIP_ACCUM_STATE_HEADER_BYTES) return "shorter than the 64-byte header";
-    memcpy(hd, h, sizeof(*hd));
-    if (memcmp(hd->magic, STATE_MAGIC, 8) != 0) return "bad magic (not BCDACCST)";
-    if (hd->version != BCD_HIP_ACCUM_STATE_VERSION) return "unsupported version (not 1)";
-    if (hd->header_bytes != BCD_HIP_ACCUM_STATE_HEADER_BYTES) return "header_bytes is not 64";
-    if (hd->nb_bins < 2 || hd->nb_bins > 85) return "nb_bins outside [2, 85]";
-    if (hd->width <= 0 || hd->height <= 0 || (int64_t)hd->width * hd->height >= ((int64_t)1 << 31)) return "width and height must be positive, below 2^31 pixels";
-    if (hd->nb_planes != (uint32_t)(11 + 3 * hd->nb_bins)) return "nb_planes is not 11 + 3 nb_bins";
-    if (bytes != BCD_HIP_ACCUM_STATE_HEADER_BYTES + 4 * (int64_t)hd->nb_planes * hd->width * hd->height) return "size is not 64 + 4 nb_planes W H bytes";
-    for (uint8_t r : hd->reserved)
-        if (r != 0) return "reserved bytes are not zero";
-    if (hd->samples_added < 0 || hd->dropped < 0) return "negative counters";
-    return nullptr;
-}
-
-// a well-formed state of this accumulator's geometry and parameters (gamma and max value bit for bit)?
-int accum_check_state(bcd_hip_accum *a, const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
-{
-    if (const char *why = state_problem(h, bytes, hd)) return bad(a->ctx, (std::string("not an accumulator state (format v1): ") + why).c_str());
-    if (hd->width != a->W || hd->height != a->H || hd->nb_bins != a->nbins) return bad(a->ctx, "state of another frame size or bin count");
-    if (memcmp(&hd->gamma, &a->gamma, sizeof(float)) != 0 || memcmp(&hd->max_value, &a->maxval, sizeof(float)) != 0)
-        return bad(a->ctx, "state with another gamma or max value");
-    return BCD_HIP_OK;
-}
-
-int accum_check_pair(bcd_hip_accum *dst, bcd_hip_accum *src)
-{
-    if (!src) return bad(dst->ctx, "null source accumulator");
-    if (dst == src) return bad(dst->ctx, "an accumulator cannot be merged into itself");
-    if (dst->W != src->W || dst->H != src->H || dst->nbins != src->nbins) return bad(dst->ctx, "accumulators of different frame sizes or bin counts");
-    if (memcmp(&dst->gamma, &src->gamma, sizeof(float)) != 0 || memcmp(&dst->maxval, &src->maxval, sizeof(float)) != 0)
-        return bad(dst->ctx, "accumulators with different gamma or max value");
-    return BCD_HIP_OK;
-}
-
-// the pinned staging (host_side) or the device chunks, allocated once; the context's device is current
-int accum_chunks(bcd_hip_accum *a, bool host_side)
-{
-    bcd_hip_ctx *ctx = a->ctx;
-    a->chunk_bytes = std::min(STATE_CHUNK, accum_state_bytes(a));
-    for (int i = 0; i < 2; ++i) {
-        if (host_side && !a->stage_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&a->stage_ev[i], hipEventDisableTiming));
-        void *&p = host_side ? a->stage[i] : a->chunk[i];
-        if (p) continue;
-        const hipError_t e = host_side ? hipHostMalloc(&p, a->chunk_bytes, hipHostMallocDefault) : hipMalloc(&p, a->chunk_bytes);
-        if (e != hipSuccess) {
-            p = nullptr;
-            set_err(ctx, std::string(host_side ? "hipHostMalloc" : "hipMalloc") + " of a state chunk failed: " + hipGetErrorString(e));
-            return BCD_HIP_ENOMEM;
-        }
-    }
-    return BCD_HIP_OK;
-}
-
-// the planes at h (accum_state_bytes) replace the state (merge = false) or are added to it, chunk by chunk through the pinned staging:
-// the host copy of chunk i + 1 runs while chunk i crosses PCIe.  Returns when h is no longer needed.
-int accum_from_host(bcd_hip_accum *a, const uint8_t *h, bool merge)
-{
-    bcd_hip_ctx *ctx = a->ctx;
-    RCCHK(accum_chunks(a, true));
-    if (merge) RCCHK(accum_chunks(a, false));
-    const size_t S = accum_state_bytes(a), c = a->chunk_bytes;
-    uint8_t *st = (uint8_t *)a->state.p;
-    for (size_t off = 0, i = 0; off < S; off += c, ++i) {
-        const int b = (int)(i & 1);
-        const size_t len = std::min(c, S - off);
-        if (a->stage_busy[b]) {
-            HIPCHK(ctx, hipEventSynchronize(a->stage_ev[b]));
-            a->stage_busy[b] = false;
-        }
-        memcpy(a->stage[b], h + off, len);
-        // (merge: chunk[b] was last read by the merge of chunk i - 2, earlier on the same stream)
-        HIPCHK(ctx, hipMemcpyAsync(merge ? a->chunk[b] : st + off, a->stage[b], len, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(a->stage_ev[b], ctx->stream));
-        a->stage_busy[b] = true;
-        if (merge) HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)a->chunk[b], (int64_t)(len / 4), ctx->num_cus, ctx->stream));
-    }
-    return BCD_HIP_OK;
-}
-
-} // namespace
-
-int bcd_hip_accum_state_info(const void *h_state, int64_t bytes, bcd_hip_accum_state_header *out)
-{
-    bcd_hip_accum_state_header hd;
-    if (state_problem(h_state, bytes, &hd)) return BCD_HIP_EINVAL;
-    if (out) *out = hd;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_state_bytes(bcd_hip_accum *acc, int64_t *bytes)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    if (!bytes) return bad(acc->ctx, "null size");
-    *bytes = BCD_HIP_ACCUM_STATE_HEADER_BYTES + (int64_t)accum_state_bytes(acc);
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    const size_t S = accum_state_bytes(acc);
-    if (!h_state) return bad(ctx, "null state buffer");
-    if (capacity < BCD_HIP_ACCUM_STATE_HEADER_BYTES + (int64_t)S) return bad(ctx, "state buffer smaller than bcd_hip_accum_state_bytes");
-    DEVICE_GUARD(ctx);
-    RCCHK(accum_chunks(acc, true));
-    int64_t added = 0, dropped = 0;
-    RCCHK(bcd_hip_accum_info(acc, &added, &dropped)); // (synchronises: no staging copy is in flight after it)
-    acc->stage_busy[0] = acc->stage_busy[1] = false;
-    bcd_hip_accum_state_header hd;
-    memset(&hd, 0, sizeof(hd));
-    memcpy(hd.magic, STATE_MAGIC, 8);
-    hd.version = BCD_HIP_ACCUM_STATE_VERSION;
-    hd.header_bytes = BCD_HIP_ACCUM_STATE_HEADER_BYTES;
-    hd.width = acc->W; hd.height = acc->H; hd.nb_bins = acc->nbins;
-    hd.gamma = acc->gamma; hd.max_value = acc->maxval;
-    hd.nb_planes = (uint32_t)(11 + 3 * acc->nbins);
-    hd.samples_added = added; hd.dropped = dropped;
-    uint8_t *out = (uint8_t *)h_state;
-    memcpy(out, &hd, sizeof(hd));
-    out += BCD_HIP_ACCUM_STATE_HEADER_BYTES;
-    // chunk i + 2 crosses PCIe into one pinned buffer while the host copies chunk i + 1 out of the other
-    const size_t c = acc->chunk_bytes, nch = (S + c - 1) / c;
-    const uint8_t *st = (const uint8_t *)acc->state.p;
-    auto enqueue = [&](size_t i) {
-        const int b = (int)(i & 1);
-        hipError_t e = hipMemcpyAsync(acc->stage[b], st + i * c, std::min(c, S - i * c), hipMemcpyDeviceToHost, ctx->stream);
-        return e == hipSuccess ? hipEventRecord(acc->stage_ev[b], ctx->stream) : e;
-    };
-    for (size_t i = 0; i < std::min<size_t>(2, nch); ++i) HIPCHK(ctx, enqueue(i));
-    for (size_t i = 0; i < nch; ++i) {
-        const int b = (int)(i & 1);
-        HIPCHK(ctx, hipEventSynchronize(acc->stage_ev[b]));
-        memcpy(out + i * c, acc->stage[b], std::min(c, S - i * c));
-        if (i + 2 < nch) HIPCHK(ctx, enqueue(i + 2));
-    }
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    bcd_hip_accum_state_header hd;
-    RCCHK(accum_check_state(acc, h_state, bytes, &hd));
-    DEVICE_GUARD(ctx);
-    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, false));
-    HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 0, ctx->stream));
-    acc->submitted = hd.samples_added + hd.dropped;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_merge_state(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
-{
-    if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    bcd_hip_accum_state_header hd;
-    RCCHK(accum_check_state(acc, h_state, bytes, &hd));
-    DEVICE_GUARD(ctx);
-    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, true));
-    HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 1, ctx->stream));
-    acc->submitted += hd.samples_added + hd.dropped;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src)
-{
-    if (!dst) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = dst->ctx;
-    RCCHK(accum_check_pair(dst, src));
-    bcd_hip_ctx *sctx = src->ctx;
-    { // everything enqueued on src's stream so far ...
-        DeviceGuard g(sctx);
-        if (!g.ok) { set_err(ctx, "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
-        HIPCHK(ctx, hipEventRecord(src->ev_merge, sctx->stream));
-    }
-    DEVICE_GUARD(ctx);
-    // ... comes before the reads on dst's stream
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->ev_merge, 0));
-    const size_t S = accum_state_bytes(dst);
-    const char *env = getenv("BCD_HIP_ACCUM_MERGE_COPY"); // 1: the chunked copy of a cross-device merge on one device too (tests)
-    if (sctx->device == ctx->device && !(env && env[0] == '1')) {
-        HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->state.p, (const float *)src->state.p, (int64_t)(S / 4), ctx->num_cus, ctx->stream));
-        HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)src->dropped.p, 0, 1, ctx->stream));
-    } else {
-        // src's state in chunks into dst-side scratch (peer copies; no peer access needed), each chunk merged after its copy
-        RCCHK(accum_chunks(dst, false));
-        const size_t c = dst->chunk_bytes;
-        uint8_t *st = (uint8_t *)dst->state.p;
-        const uint8_t *ss = (const uint8_t *)src->state.p;
-        for (size_t off = 0, i = 0; off < S; off += c, ++i) {
-            void *buf = dst->chunk[i & 1];
-            const size_t len = std::min(c, S - off);
-            HIPCHK(ctx, hipMemcpyPeerAsync(buf, ctx->device, ss + off, sctx->device, len, ctx->stream));
-            HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)buf, (int64_t)(len / 4), ctx->num_cus, ctx->stream));
-        }
-        HIPCHK(ctx, hipMemcpyPeerAsync(dst->chunk[0], ctx->device, src->dropped.p, sctx->device, sizeof(unsigned long long), ctx->stream));
-        HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)dst->chunk[0], 0, 1, ctx->stream));
-    }
-    // dst's reads come before whatever is enqueued on src's stream from now on
-    HIPCHK(ctx, hipEventRecord(dst->ev_merge, ctx->stream));
-    {
-        DeviceGuard g(sctx);
-        if (!g.ok) { set_err(ctx, "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
-        HIPCHK(ctx, hipStreamWaitEvent(sctx->stream, dst->ev_merge, 0));
-    }
-    dst->submitted += src->submitted;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_selftest_distance_kernels(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, int W, int H, int D, int search_radius,
-                                      int *variant, int64_t *mismatches)
-{
-    if (!ctx || !d_hist || !d_ns || !mismatches || W <= 0 || H <= 0 || D <= 0 || search_radius < 1) return bad(ctx, "bad argument");
-    DEVICE_GUARD(ctx);
-    touch(ctx->main);
-    Work &wk = ctx->main;
-    const size_t npix = (size_t)W * H;
-    const int nd = bcd_delta_count(search_radius);
-    RCCHK(ensure(ctx, wk.T, npix * nd * sizeof(float)));
-    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    float *T2 = nullptr;
-    uint8_t *C2 = nullptr;
-    HIPCHK(ctx, hipMalloc((void **)&T2, npix * nd * sizeof(float)));
-    if (hipMalloc((void **)&C2, npix * nd) != hipSuccess) { (void)hipFree(T2); set_err(ctx, "hipMalloc"); return BCD_HIP_EDEVICE; }
-    int rc = BCD_HIP_OK;
-    do {
-        int *d_flag = (int *)wk.counters.p + 40;
-        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>((int32_t *)wk.counters.p + 32);
-        if (hipMemsetAsync(d_flag, 0, 2 * sizeof(int), wk.stream) != hipSuccess || hipMemsetAsync(d_cnt, 0, sizeof(*d_cnt), wk.stream) != hipSuccess ||
-            bcd_launch_uniform_n(d_ns, (int64_t)npix, d_flag + 1, wk.stream) != hipSuccess ||
-            hipMemcpyAsync(wk.h_counters + 41, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipMemcpyAsync(wk.h_counters + 42, d_ns, sizeof(float), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipStreamSynchronize(wk.stream) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
-        float n0, uni_n = 0.f;
-        memcpy(&n0, wk.h_counters + 42, sizeof(n0));
-        int e = 0;
-        if (wk.h_counters[41] == 0 && n0 >= 1.f && n0 <= 65536.f && frexpf(n0, &e) == 0.5f) uni_n = n0;
-        // (entries whose neighbour lies outside the image are never written: clear both sets first)
-        if (hipMemsetAsync(wk.T.p, 0, npix * nd * sizeof(float), wk.stream) != hipSuccess || hipMemsetAsync(wk.Cn.p, 0, npix * nd, wk.stream) != hipSuccess ||
-            hipMemsetAsync(T2, 0, npix * nd * sizeof(float), wk.stream) != hipSuccess || hipMemsetAsync(C2, 0, npix * nd, wk.stream) != hipSuccess) {
-            rc = BCD_HIP_EDEVICE; break;
-        }
-        // production choice (fast division, uniform-count formula when it applies) against the compiler's division + general formula
-        if (bcd_launch_pairdist(d_hist, d_ns, W, H, D, search_radius, (float *)wk.T.p, (uint8_t *)wk.Cn.p, 1, d_flag, uni_n, wk.stream) != hipSuccess ||
-            bcd_launch_pairdist(d_hist, d_ns, W, H, D, search_radius, T2, C2, 0, d_flag, 0.f, wk.stream) != hipSuccess ||
-            bcd_launch_compare_planes((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, T2, C2, (int64_t)(npix * nd), d_cnt, wk.stream) != hipSuccess) {
-            rc = BCD_HIP_EDEVICE; break;
-        }
-        unsigned long long h = 0;
-        int flag = 0;
-        if (hipMemcpyAsync(&h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipStreamSynchronize(wk.stream) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
-        *mismatches = (int64_t)h;
-        if (variant) *variant = (uni_n > 0.f ? 2 : 1) | (flag << 4); // 1 = fast division, 2 = + uniform counts; bits 4.. = range / count flags raised
-    } while (false);
-    (void)hipFree(T2);
-    (void)hipFree(C2);
-    if (rc != BCD_HIP_OK) set_err(ctx, "distance kernel self-test failed to run");
-    return rc;
-}
-
-// Measurement (bench.py `roofline.valu`): what the production distance kernel computes on this frame -- the (pixel pair, bin) terms it
-// evaluates (exactly the reference's count of bins with b1 + b2 > 1 over the half plane), the bins a wavefront issues because one of its 64
-// pairs needs them, the groups of four bins it enters -- from a counting instantiation of the kernel, and the duration of the PRODUCTION
-// instantiation on the same input (HIP events, best of `reps`).
-int bcd_hip_selftest_bin_work(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, int W, int H, int D, int search_radius, int reps,
-                              int64_t *lane_bins, int64_t *wave_bins, int64_t *wave_groups, float *kernel_ms)
-{
-    if (!ctx || !d_hist || !d_ns || !lane_bins || !wave_bins || !wave_groups || !kernel_ms || W <= 0 || H <= 0 || search_radius < 1 || reps < 1) return bad(ctx, "bad argument");
-    DEVICE_GUARD(ctx);
-    touch(ctx->main);
-    if (!bcd_pairdist_rw_supported(D)) { set_err(ctx, "no approximate kernel for this histogram depth"); return BCD_HIP_EUNSUPPORTED; }
-    Work &wk = ctx->main;
-    const size_t npix = (size_t)W * H;
-    const int nd = bcd_delta_count(search_radius);
-    RCCHK(ensure(ctx, wk.T, npix * nd * sizeof(float)));
-    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    int *d_flag = (int *)wk.counters.p + 40;
-    unsigned long long *d_work = reinterpret_cast<unsigned long long *>((int32_t *)wk.counters.p + 48); // (8-byte aligned: words 48..53)
-    HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4 * sizeof(int), wk.stream));
-    HIPCHK(ctx, hipMemsetAsync(d_work, 0, 3 * sizeof(unsigned long long), wk.stream));
-    // the uniform kernel on the first pixel's count if every pixel carries it (the kernel checks), else the general formula -- like similarity()
-    float uni_n = -1.f;
-    HIPCHK(ctx, bcd_launch_pairdist_rw_counting(d_hist, d_ns, W, H, D, search_radius, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, uni_n, d_work, wk.stream));
-    int flags[4] = { 0, 0, 0, 0 };
-    HIPCHK(ctx, hipMemcpyAsync(flags, d_flag, sizeof(flags), hipMemcpyDeviceToHost, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    if (flags[2] != 0) { // not one power-of-two count: count again with the general formula
-        uni_n = 0.f;
-        HIPCHK(ctx, hipMemsetAsync(d_flag, 0, 4 * sizeof(int), wk.stream));
-        HIPCHK(ctx, hipMemsetAsync(d_work, 0, 3 * sizeof(unsigned long long), wk.stream));
-        HIPCHK(ctx, bcd_launch_pairdist_rw_counting(d_hist, d_ns, W, H, D, search_radius, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, uni_n, d_work, wk.stream));
-    }
-    unsigned long long h[3] = { 0, 0, 0 };
-    HIPCHK(ctx, hipMemcpyAsync(h, d_work, sizeof(h), hipMemcpyDeviceToHost, wk.stream));
-    hipEvent_t e0, e1;
-    HIPCHK(ctx, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_err(ctx, "hipEventCreate"); return BCD_HIP_EDEVICE; }
-    float best = -1.f;
-    int rc = BCD_HIP_OK;
-    for (int r = 0; r < reps + 1 && rc == BCD_HIP_OK; ++r) { // (the first one warms up)
-        if (hipEventRecord(e0, wk.stream) != hipSuccess ||
-            bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, search_radius, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, uni_n, wk.stream) != hipSuccess ||
-            hipEventRecord(e1, wk.stream) != hipSuccess || hipStreamSynchronize(wk.stream) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        if (r > 0 && (best < 0.f || ms < best)) best = ms;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != BCD_HIP_OK) { set_err(ctx, "bin-work self-test failed to run"); return rc; }
-    *lane_bins = (int64_t)h[0]; *wave_bins = (int64_t)h[1]; *wave_groups = (int64_t)h[2]; *kernel_ms = best;
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_selftest_approx_distance(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, int W, int H, int D, int search_radius,
-                                     float *max_rel_dev, int64_t *count_mismatches, int *flags)
-{
-    if (!ctx || !d_hist || !d_ns || !max_rel_dev || !count_mismatches || W <= 0 || H <= 0 || search_radius < 1) return bad(ctx, "bad argument");
-    DEVICE_GUARD(ctx);
-    touch(ctx->main);
-    if (!bcd_pairdist_rw_supported(D)) { set_err(ctx, "no approximate kernel for this histogram depth"); return BCD_HIP_EUNSUPPORTED; }
-    Work &wk = ctx->main;
-    const size_t npix = (size_t)W * H;
-    const int nd = bcd_delta_count(search_radius);
-    RCCHK(ensure(ctx, wk.T, npix * nd * sizeof(float)));
-    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    float *T2 = nullptr;
-    uint8_t *C2 = nullptr;
-    HIPCHK(ctx, hipMalloc((void **)&T2, npix * nd * sizeof(float)));
-    if (hipMalloc((void **)&C2, npix * nd) != hipSuccess) { (void)hipFree(T2); set_err(ctx, "hipMalloc"); return BCD_HIP_EDEVICE; }
-    int rc = BCD_HIP_OK;
-    do {
-        int *d_flag = (int *)wk.counters.p + 40;
-        unsigned int *d_res = reinterpret_cast<unsigned int *>((int32_t *)wk.counters.p + 32);
-        if (hipMemsetAsync(d_flag, 0, 4 * sizeof(int), wk.stream) != hipSuccess || hipMemsetAsync(d_res, 0, 2 * sizeof(unsigned int), wk.stream) != hipSuccess ||
-            bcd_launch_uniform_n(d_ns, (int64_t)npix, d_flag + 1, wk.stream) != hipSuccess ||
-            hipMemcpyAsync(wk.h_counters + 41, d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipMemcpyAsync(wk.h_counters + 42, d_ns, sizeof(float), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipStreamSynchronize(wk.stream) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
-        float n0, uni_n = 0.f;
-        memcpy(&n0, wk.h_counters + 42, sizeof(n0));
-        int e = 0;
-        if (wk.h_counters[41] == 0 && n0 >= 1.f && n0 <= 65536.f && frexpf(n0, &e) == 0.5f) uni_n = n0;
-        if (hipMemsetAsync(wk.T.p, 0, npix * nd * sizeof(float), wk.stream) != hipSuccess || hipMemsetAsync(wk.Cn.p, 0, npix * nd, wk.stream) != hipSuccess ||
-            hipMemsetAsync(T2, 0, npix * nd * sizeof(float), wk.stream) != hipSuccess || hipMemsetAsync(C2, 0, npix * nd, wk.stream) != hipSuccess) {
-            rc = BCD_HIP_EDEVICE; break;
-        }
-        // approximate planes (production variant: the uniform kernel, or -- general sample counts -- the RATIO form with its verdict in flag bit 2) against the
-        // exact planes (compiler's division, general formula)
-        if (uni_n == 0.f && ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)) != BCD_HIP_OK) { rc = BCD_HIP_ENOMEM; break; }
-        if ((uni_n != 0.f ? bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, search_radius, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, uni_n, wk.stream)
-                          : bcd_launch_pairdist_rw_ratio(d_hist, d_ns, W, H, D, search_radius, wk.T.p, (uint8_t *)wk.Cn.p, d_flag, 1.f, (unsigned int *)wk.ratio_stats.p, wk.stream)) != hipSuccess ||
-            bcd_launch_pairdist(d_hist, d_ns, W, H, D, search_radius, T2, C2, 0, d_flag, 0.f, wk.stream) != hipSuccess ||
-            bcd_launch_max_rel_dev((const float *)wk.T.p, T2, (const uint8_t *)wk.Cn.p, C2, W, H, search_radius, d_res, wk.stream) != hipSuccess) {
-            rc = BCD_HIP_EDEVICE; break;
-        }
-        unsigned int h[2] = { 0u, 0u };
-        int flag = 0;
-        if (hipMemcpyAsync(h, d_res, sizeof(h), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, wk.stream) != hipSuccess ||
-            hipStreamSynchronize(wk.stream) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
-        memcpy(max_rel_dev, &h[0], sizeof(float));
-        *count_mismatches = (int64_t)h[1];
-        if (flags) *flags = (uni_n > 0.f ? 2 : 3) | (flag << 4); // low nibble: 2 = uniform kernel, 3 = RATIO form; above: the kernels' flag word (4: the RATIO form declined)
-    } while (false);
-    (void)hipFree(T2);
-    (void)hipFree(C2);
-    if (rc != BCD_HIP_OK) set_err(ctx, "approximate-distance self-test failed to run");
-    return rc;
-}
-
-int bcd_hip_eig27_batch(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms)
-{
-    return bcd_hip_eig27_batch_rule(ctx, d_A, n, d_eig, d_V, ms, 0);
-}
-
-int bcd_hip_eig27_batch_rule(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms, int production_rule)
-{
-    if (!ctx || !d_A || !d_eig || !d_V || n <= 0) return bad(ctx, "bad argument");
-    DEVICE_GUARD(ctx);
-    touch(ctx->main);
-    Work &wk = ctx->main;
-    RCCHK(ensure(ctx, wk.counters, 64 * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
-    int32_t *d_c = (int32_t *)wk.work_q.p; // work queues
-    HIPCHK(ctx, hipMemsetAsync(d_c, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
-    HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
-    HIPCHK(ctx, bcd_launch_jacobi27_batch(d_A, n, d_c, std::min(ctx->num_cus * 12, (n + 1) / 2), d_eig, d_V, wk.stream, bcd_bayes27_conv2(production_rule ? 0 : 1)));
-    HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    if (ms) *ms = stage_ms(wk, 0, 1);
-    return BCD_HIP_OK;
-}
-
-int bcd_hip_selftest_division(bcd_hip_ctx *ctx, uint32_t seed, int64_t samples, int64_t *mismatches)
-{
-    if (!ctx || !mismatches || samples <= 0) return bad(ctx, "bad argument");
-    DEVICE_GUARD(ctx);
-    touch(ctx->main);
-    RCCHK(ensure(ctx, ctx->main.counters, 64 * sizeof(int32_t)));
-    unsigned long long *d = reinterpret_cast<unsigned long long *>((int32_t *)ctx->main.counters.p + 32);
-    HIPCHK(ctx, hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream));
-    const int per_thread = 1024, blocks = (int)std::min<int64_t>(1 << 20, (samples + 256ll * per_thread - 1) / (256ll * per_thread));
-    HIPCHK(ctx, bcd_launch_selftest_div(seed, blocks, per_thread, d, ctx->stream));
-    unsigned long long h = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *mismatches = (int64_t)h;
     return BCD_HIP_OK;
 }
 

@@ -1,0 +1,265 @@
+// bcd_ctx.h -- internal to the host orchestration files (bcd_api.hip, bcd_host.hip, bcd_accum.hip, bcd_selftest.hip): the context, the per-scale
+// workspace with its counter block, the error-handling macros and the helpers more than one of those files needs.  Nothing declared here is part
+// of the C ABI (include/bcd_hip.h): the helpers have hidden visibility.
+#pragma once
+#include "../../include/bcd_hip.h"
+#include "bcd_common.h"
+#include "bcd_launch.h"
+
+#include <condition_variable>
+#include <cstddef>
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+
+static_assert(BCD_MAX_LAYERS == BCD_HIP_MAX_LAYERS, "the layer tables of the kernels hold what the C ABI admits");
+
+constexpr int MAX_SCALES = 16;
+constexpr int ROUND_BATCH = 16;
+constexpr int MAX_EVENT_PAIRS = 4096;
+
+// (hidden: what the host files instantiate on these types stays out of the dynamic symbol table, as when they were file-local)
+#pragma GCC visibility push(hidden)
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
+// the colour layers of a bcd_hip_denoise_layers call BEYOND the first, at one scale: the first layer travels through the arguments bcd_hip_denoise has
+struct LayerView {
+    int n = 0;
+    const float *col[BCD_MAX_LAYERS], *cov[BCD_MAX_LAYERS];
+    float *out[BCD_MAX_LAYERS];
+};
+
+// The counter block of a workspace: 64 words on the device (Work::counters) and a pinned host mirror of the same layout (Work::h_counters).
+//
+// | words  | device                                                                  | host mirror                                                      |
+// |--------|-------------------------------------------------------------------------|------------------------------------------------------------------|
+// | 0..15  | undecided pixels per marking launch of a batch (k_sum_counter_lines)    | the same, copied per batch                                       |
+// | 16, 17 | list lengths: full estimate (strong), fallback (weak)                   | the same                                                         |
+// | 18..19 | sum of |S| (64 bit)                                                     | the same                                                         |
+// | 20..22 | work counters of the generic estimate kernel                            | --                                                               |
+// | 23     | spectral-inverse (redo) count                                           | the same; layers_follow leaves the sum over the layers here      |
+// | 24..39 | 32..33: scratch of the self-tests                                       | 24 + k: running redo total after extra layer k                   |
+// | 40..43 | range / count flag, uniform-count scan, "another sample count",         | the same                                                         |
+// |        | borderline pairs (k_sum_counter_lines reads [0], [2], [3] of them)      |                                                                  |
+// | 44     | --                                                                      | the first pixel's sample count (scan_uniform_count)              |
+// | 48..53 | marking total (64 bit), or the three 64-bit counters of the bin-work    | 48..49: marking total                                            |
+// |        | self-test                                                               |                                                                  |
+//
+// The kernels see two groups relative to a base pointer: `lists` (d_c[0..7], from word 16) and `flags` (d_flag[0..3], from word 40).
+struct Counters {
+    int32_t undecided[ROUND_BATCH];
+    struct Lists {
+        int32_t n_strong, n_weak;
+        int64_t sim_total;        // sum of |S|
+        int32_t generic_work[3];  // DEVICE ONLY: work counters of the generic estimate kernel
+        int32_t spectral;         // full estimates that took the spectral inverse (the redo list's length)
+    } lists;
+    struct SelftestScratch { int32_t below[8]; unsigned long long result; };
+    union {
+        int32_t layer_redo_total[BCD_MAX_LAYERS]; // HOST ONLY: [k] = `spectral` after extra layer k (BCD_MAX_LAYERS - 1 in use)
+        SelftestScratch selftest;                 // DEVICE ONLY: result word(s) of the self-tests
+    };
+    struct Flags {
+        int32_t range;            // the distance kernels' range / count flag (bit 1: not one sample count, bit 2: the RATIO form declined)
+        int32_t scan;             // != 0: k_uniform_n found two sample counts
+        int32_t other_count;      // a pixel carries another sample count than the uniform kernel was launched for (plain-store flag)
+        int32_t borderline;       // borderline pairs listed (may exceed the list's capacity)
+    } flags;
+    float first_count;            // HOST ONLY: the first pixel's sample count
+    int32_t unused_45[3];
+    union {
+        long long marking_total;        // all-reduced count of undecided pixels of a marking batch (+ 2^40: the masks did not pass)
+        unsigned long long bin_work[3]; // DEVICE ONLY: bcd_hip_selftest_bin_work
+    };
+    int32_t unused_54[10];
+};
+constexpr int COUNTER_WORDS = (int)(sizeof(Counters) / sizeof(int32_t));
+#define COUNTER_WORD(member) ((int)(offsetof(Counters, member) / sizeof(int32_t)))
+static_assert(COUNTER_WORDS == 64, "the counter block is 64 ints");
+static_assert(COUNTER_WORD(lists) == 16 && COUNTER_WORD(lists.spectral) == 23 && sizeof(Counters::Lists) == 8 * sizeof(int32_t), "d_c[0..7] of the list and estimate kernels");
+static_assert(COUNTER_WORD(flags) == 40 && COUNTER_WORD(flags.other_count) == 42 && COUNTER_WORD(flags.borderline) == 43 && sizeof(Counters::Flags) == 4 * sizeof(int32_t),
+              "d_flag[0..3] of the distance, mask and k_sum_counter_lines kernels");
+static_assert(COUNTER_WORD(marking_total) == 48 && COUNTER_WORD(selftest.result) == 32, "words the kernels are handed");
+static_assert(offsetof(Counters, lists.sim_total) % 8 == 0 && offsetof(Counters, selftest.result) % 8 == 0 && offsetof(Counters, marking_total) % 8 == 0 &&
+                  offsetof(Counters, bin_work) % 8 == 0, "64-bit counters are 8-byte aligned");
+static_assert(COUNTER_WORD(layer_redo_total) + (BCD_MAX_LAYERS - 1) <= COUNTER_WORD(flags), "the per-layer running totals end below the flag words");
+static_assert(COUNTER_WORD(first_count) > COUNTER_WORD(flags.borderline), "the first pixel's count does not alias a flag word");
+
+#pragma GCC visibility pop
+
+// everything one scale's pipeline needs: a multiscale run drives one Work per scale concurrently (own stream, own host
+// thread), because the scales are independent until the merge and the coarse ones cannot fill 256 CUs on their own
+struct Work {
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    DevBuf T, Cn, mask, fwd, nsim, state, strong, weak, counters, cnt_lines, work_q, pixcov, sum, cnt, gscratch, dep, tmp_lo, border, ratio_stats; // grow-only
+    DevBuf lay_pixcov, lay_sum, lay_tmp_lo; // extra colour layers (bcd_hip_denoise_layers): per-pixel covariances, sums, merge scratch -- one slice per layer
+    int border_capacity = 0;       // entries of `border` offered to the last fast similarity pass (0: the exact kernels ran)
+    int rounds_hint = 0;           // marking launches the last problem needed
+    int last_batch = 0;            // launches of the batch active_step_enqueue left in flight
+    bool dep_ready = false;        // dependency lists of the current marking problem are in `dep` (reset by active_init)
+    const void *dep_mask = nullptr, *dep_state = nullptr; // ... extracted for these buffers (another problem on the same context rebuilds them)
+    Counters *h_counters = nullptr; // pinned
+    Counters *d_counters() const { return static_cast<Counters *>(counters.p); } // (after ensure(ctx, wk.counters, sizeof(Counters)))
+    bool initialised = false;      // set once every stream / event / pinned buffer below exists
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool; // pair-distance kernel timing
+    int ev_used = 0;
+    hipEvent_t ev_stage[4] = { nullptr, nullptr, nullptr, nullptr };
+    hipEvent_t ev_done = nullptr;
+    hipEvent_t ev_built = nullptr; // this scale's pyramid level is complete
+    hipStream_t aux = nullptr;     // side stream: the fallback-pixel kernel runs beside the (latency-bound) full estimate kernel
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_pixcov = nullptr; // the per-pixel covariances (side stream, beside the distance kernel) are complete
+    hipEvent_t ev_counts = nullptr; // the list lengths of bayes() are on the host
+    // (round 6) full-estimate items of the last frame of this geometry on this workspace: the next frame's first chunk of estimate kernels is launched for
+    // that many (+ 1/8) BEFORE the host knows the new count
+    int strong_hint = 0, strong_hint_W = 0, strong_hint_H = 0;
+    // approximate distance planes computed ahead of similarity() by a caller that streams the frame in (bcd_hip_denoise_host_ex): valid for
+    // exactly this problem; similarity() consumes the note
+    struct { bool ready = false; const float *hist = nullptr, *ns = nullptr; int W = 0, H = 0, D = 0, b = 0; float tau = 0.f, uni_n = 0.f; } planes;
+    // uniform-sample-count speculation of the approximate distance kernel (similarity()): did the last frames on this workspace fail it?
+    bool nonuniform = false;
+    bool speculated = false;       // the current pass launched the uniform kernel on the first pixel's count, unchecked by the host
+    // the RATIO form of the distance kernel raised its absolute-error flag on frames of these sizes on this workspace: the reference's operations serve them (a small
+    // set, oldest replaced: serialised scales share one workspace, a caller may alternate frame sizes)
+    struct { int W = 0, H = 0; } ratio_declined[4];
+    int ratio_declined_next = 0;
+    bool ratio_is_declined(int W, int H) const { for (const auto &k : ratio_declined) if (k.W == W && k.H == H) return true; return false; }
+    bool ratio_used = false;          // the current pass ran the RATIO form of the distance kernel (general sample counts)
+    int ratio_W = 0, ratio_H = 0;        // ... on a frame of this size
+    // (round 4) k_scale_begin cleared these at the head of the scale's stream: the first user takes them as they are, a repeated use (second
+    // similarity attempt, second marking batch, second chunk of a long list) clears its own as before
+    bool clean_flags = false, clean_lines = false, clean_dc = false, clean_wq = false;
+    // the redo kernel of the register-resident finish (k_bayes27w<2> over the -- normally empty -- list of items whose sweep inverse failed its
+    // checks) is only launched when the list's counter, read with the scale's last synchronisation, says so
+    struct { bool pending = false; int first = 0, n = 0, cus = 0; } redo;
+};
+
+struct bcd_hip_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    bool profiling = false;
+    bool concurrent_scales = true;
+    bool fast_similarity = true; // approximate distance planes + exact re-evaluation at the threshold (k_similarity_fast.hip)
+    int num_cus = 256;
+    int cu_share_pct = 100;  // bcd_hip_set_cu_share
+    // share of the CU slots the coarse scales' persistent estimate kernels take inside bcd_hip_denoise (bayes()); adjusted from call to
+    // call on the same geometry so that the coarse scales end shortly before the finest one (see bcd_hip_denoise)
+    int coarse_share = 25;
+    int64_t share_key = 0;          // geometry the current value was tuned on
+    std::mutex err_mutex;
+    std::string err;
+    bcd_hip_scale_stats stats[MAX_SCALES];
+    Work main;               // bound to `stream`
+    Work extra[MAX_SCALES];  // lazily created streams for scales 1.. of a multiscale run
+    DevBuf tmp_lo;
+    DevBuf pyr[MAX_SCALES][5]; // colours, nsamples, hist, cov, out
+    DevBuf lay_host[3];            // host-buffer entry point of the layers: device copies of the extra layers' colours, covariances, outputs
+    DevBuf lay_pyr[MAX_SCALES][3]; // extra colour layers: colours, cov, out of every layer at that pyramid level, one slice per layer
+    int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
+    int layer_count = 0;                                // layers of that call (0: none yet)
+    DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
+    hipEvent_t ev_pyramid = nullptr;
+    hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
+    hipStream_t upload_stream2 = nullptr;       // ... colours and covariances beside the histogram pieces (helper thread)
+    hipEvent_t ev_upload2 = nullptr;
+    std::vector<hipEvent_t> ev_upload;
+    bool stream_uploads = true;                 // BCD_HIP_STREAM_UPLOADS=0: upload everything, then compute
+    // (round 4) the histogram image crosses PCIe without its zeros (bcd_sparse_upload.hip); BCD_HIP_SPARSE_UPLOAD=0: plain copies
+    bool sparse_uploads = true;
+    BcdSparseUploader *sparse = nullptr;
+    long long upload_raw_bytes = 0, upload_sent_bytes = 0; // histogram image of the last host-buffer frame: as it is / as it travelled
+    // progress reporting (IDenoiser::setProgressCallback; Denoiser.cpp:181-192 of the reference): every scale adds its share when
+    // its marking is done and when its estimate is done; calls are serialised and monotone
+    bcd_hip_progress_fn progress_fn = nullptr;
+    void *progress_user = nullptr;
+    std::mutex progress_mutex;
+    double progress_done = 0.0, progress_total = 0.0;
+    // bcd_hip_denoise_begin / _wait (round 6): one frame of this context in flight on a worker thread of its own, so that a caller can keep a second
+    // context busy meanwhile (frames of a sequence, AOV passes: the distance kernels of one frame fill the chip under the latency-bound tail of another)
+    struct Async {
+        std::thread th;
+        std::mutex mu;
+        std::condition_variable cv;
+        bool has_job = false, in_flight = false, quit = false;
+        int rc = 0;
+        const float *col = nullptr, *ns = nullptr, *hist = nullptr, *cov = nullptr;
+        float *out = nullptr;
+        int W = 0, H = 0, D = 0, S = 0;
+        bcd_hip_params prm;
+    } async;
+};
+
+// ---- helpers shared between the host files: not part of the dynamic symbol table
+#pragma GCC visibility push(hidden)
+
+void set_err(bcd_hip_ctx *ctx, const std::string &msg); // (bcd_api.hip)
+
+// every entry point that allocates or launches runs on the context's device and leaves the caller's current device as it was
+struct DeviceGuard {
+    int prev = -1, dev;
+    bool ok = true;
+    explicit DeviceGuard(const bcd_hip_ctx *ctx) : dev(ctx ? ctx->device : -1)
+    {
+        if (dev < 0) return;
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard()
+    {
+        if (dev >= 0 && prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+};
+#define DEVICE_GUARD(ctx)                                                                                             \
+    DeviceGuard guard__(ctx);                                                                                         \
+    if (!guard__.ok) { set_err((ctx), "hipSetDevice failed"); return BCD_HIP_EDEVICE; }
+
+#define HIPCHK(ctx, expr)                                                                                             \
+    do {                                                                                                              \
+        hipError_t e__ = (expr);                                                                                      \
+        if (e__ != hipSuccess) {                                                                                      \
+            set_err((ctx), std::string(#expr) + ": " + hipGetErrorString(e__));                                       \
+            return BCD_HIP_EDEVICE;                                                                                   \
+        }                                                                                                             \
+    } while (0)
+
+#define RCCHK(expr)                                                                                                   \
+    do {                                                                                                              \
+        int rc__ = (expr);                                                                                            \
+        if (rc__ != BCD_HIP_OK) return rc__;                                                                          \
+    } while (0)
+
+// ---- defined in bcd_api.hip
+int ensure(bcd_hip_ctx *ctx, DevBuf &b, size_t bytes);
+int bad(bcd_hip_ctx *ctx, const char *msg);
+int check_params(bcd_hip_ctx *ctx, int W, int H, int D, const bcd_hip_params *prm);
+bool fast_similarity_applies(const bcd_hip_ctx *ctx, int D, int w, float tau);
+int scan_uniform_count(bcd_hip_ctx *ctx, Work &wk, const float *d_ns, size_t npix, float *uni_n);
+float stage_ms(Work &wk, int a, int b);
+int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov, int W, int H, int D, int nb_scales,
+                 const bcd_hip_params *prm, float *d_out, const LayerView *lv0);
+
+// bytes of the count planes of a scale.  ONE place: the host-buffer entry point computes planes ahead of similarity(), and a larger request there
+// would free them (round 6: it happened when one of the two grew, found by the environment-switch test on a fresh context)
+inline size_t count_plane_bytes(size_t npix, int nd) { return npix * (size_t)nd; }
+
+// a user of the workspace's counters / flags / work queues / sub-counter lines outside the scale chain (self-tests, the eigensolver entry point): whatever
+// k_scale_begin left clean is not clean any more
+inline void touch(Work &wk) { wk.clean_flags = wk.clean_lines = wk.clean_dc = wk.clean_wq = false; }
+
+// a sample count the uniform form of the distance kernels serves: a power of two in [1, 65536] (k_pairdist drops the sample-count products exactly)
+inline bool is_pow2_sample_count(float n)
+{
+    int e = 0;
+    return n >= 1.f && n <= 65536.f && frexpf(n, &e) == 0.5f;
+}
+
+#pragma GCC visibility pop

@@ -1193,7 +1193,7 @@ def test_batched_eigensolver_on_hard_spectra_per_eigenvalue(hipctx, rule, quanti
     """bcd_hip_eig27_batch on graded spectra, clusters, definite and zero matrices and the clamp inputs C - N of the constructed families (each also
     x 2^+-20), in batches of 1, 2, 3 and 2 (#CUs) 12 + 1 matrices; one case per class of spectrum, quantity and stopping rule.
 
-    The rule: bcd_hip_eig27_batch ALWAYS stops at off^2 <= 1e-12 diag^2 (bcd_api.hip passes no threshold: the launcher's default); the process-wide
+    The rule: bcd_hip_eig27_batch ALWAYS stops at off^2 <= 1e-12 diag^2 (bcd_selftest.hip passes no threshold: the launcher's default); the process-wide
     bcd_hip_set_strict_eigensolver only reaches the estimate chain (jacobi_conv2() in bcd_launch_bayes27), not this entry point.  The production
     rule 2e-9 is selected here through bcd_hip_eig27_batch_rule -- without the first-order correction, which lives in the finish kernels.
 
