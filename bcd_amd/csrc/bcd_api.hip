@@ -232,7 +232,7 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         // reference's operations and 1.97 + 0.07 ms for the own-list kernel of round 5, which it replaced -- and checks afterwards that the absolute errors it
         // adds stay inside the verified band (flag bit 2: the pass is then repeated with the reference's operations, and the workspace remembers the size).
         const bool use_ratio = !pre && uni_n == 0.f && !wk.ratio_is_declined(W, H);
-        wk.ratio_used = use_ratio;
+        wk.ratio_used = pre ? wk.planes.ratio : use_ratio; // (planes computed ahead: the form their launches took; its verdict is in flag word [0])
         if (pre) { if (e0) --wk.ev_used; } // (nothing to time: the planes are there)
         else if (use_ratio) {
             RCCHK(ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)));

@@ -123,7 +123,7 @@ struct Work {
     int strong_hint = 0, strong_hint_W = 0, strong_hint_H = 0;
     // approximate distance planes computed ahead of similarity() by a caller that streams the frame in (bcd_hip_denoise_host_ex): valid for
     // exactly this problem; similarity() consumes the note
-    struct { bool ready = false; const float *hist = nullptr, *ns = nullptr; int W = 0, H = 0, D = 0, b = 0; float tau = 0.f, uni_n = 0.f; } planes;
+    struct { bool ready = false; const float *hist = nullptr, *ns = nullptr; int W = 0, H = 0, D = 0, b = 0; float tau = 0.f, uni_n = 0.f; bool ratio = false; /* by the RATIO form */ } planes;
     // uniform-sample-count speculation of the approximate distance kernel (similarity()): did the last frames on this workspace fail it?
     bool nonuniform = false;
     bool speculated = false;       // the current pass launched the uniform kernel on the first pixel's count, unchecked by the host
@@ -246,6 +246,23 @@ int scan_uniform_count(bcd_hip_ctx *ctx, Work &wk, const float *d_ns, size_t npi
 float stage_ms(Work &wk, int a, int b);
 int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov, int W, int H, int D, int nb_scales,
                  const bcd_hip_params *prm, float *d_out, const LayerView *lv0);
+
+// ---- defined in bcd_host.hip (shared with the self-tests of the upload path in bcd_selftest.hip)
+struct HostStreamProgress {
+    int chunk_lines = 0, chunks = 0;           // lines per row chunk, chunks uploaded and scheduled
+    int rows_filtered = 0, tile_rows_done = 0; // prefiltered lines [0, rows_filtered) (0 without the prefilter), plane tile rows [0, tile_rows_done)
+    float uni_n = 0.f;                         // the uniform sample count the planes were launched for (0: general sample counts)
+    bool ratio = false;                        // general sample counts by the RATIO form of the kernel (as similarity() would choose), else the reference's operations
+};
+int host_upload_stream(bcd_hip_ctx *ctx);
+int host_sparse_uploader(bcd_hip_ctx *ctx);
+int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *const d[9], int W, int H, int D, int b, float tau, bool prefilter, float spike_factor,
+                      int stop_after_chunks, bool poison, HostStreamProgress *out);
+// does bcd_hip_denoise_host_ex stream a frame of this geometry in (row chunks, planes ahead of the last chunk)?
+inline bool host_frame_streams(const bcd_hip_ctx *ctx, int H, int D, const bcd_hip_params *prm)
+{
+    return ctx->stream_uploads && fast_similarity_applies(ctx, D, prm->patch_radius, prm->hist_dist_threshold) && H >= 256;
+}
 
 // bytes of the count planes of a scale.  ONE place: the host-buffer entry point computes planes ahead of similarity(), and a larger request there
 // would free them (round 6: it happened when one of the two grew, found by the environment-switch test on a fresh context)

@@ -5,6 +5,142 @@
 #include <algorithm>
 #include <thread>
 
+// the upload stream and the sparse uploader of the host-buffer entry points, created on first use
+int host_upload_stream(bcd_hip_ctx *ctx)
+{
+    if (!ctx->upload_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
+    return BCD_HIP_OK;
+}
+
+int host_sparse_uploader(bcd_hip_ctx *ctx)
+{
+    if (!ctx->sparse && !(ctx->sparse = bcd_sparse_create())) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
+    return BCD_HIP_OK;
+}
+
+// The streamed upload of a frame (bcd_hip_denoise_host_ex on frames of >= 256 lines, and bcd_hip_selftest_host_stream): the four host images h_src
+// (colours, sample counts, histograms, covariances) go to the device copies d[0..3]; d[5..8] are the prefiltered copies (== d[0..3] without the prefilter).
+// Returns with everything enqueued: the main stream waits for what the upload streams carry.  stop_after_chunks >= 0: only that many row chunks are
+// uploaded and scheduled; poison: see below (both for the self-test; the host path passes -1 and false).
+int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *const d[9], int W, int H, int D, int b, float tau, bool prefilter, float spike_factor,
+                      int stop_after_chunks, bool poison, HostStreamProgress *out)
+{
+    Work &wk = ctx->main;
+    RCCHK(host_upload_stream(ctx));
+    const size_t np = (size_t)W * H;
+    const size_t sz[4] = { np * 3, np, np * D, np * 6 };
+    const int nd = bcd_delta_count(b), tile = bcd_pairdist_rw_tile_lines();
+    RCCHK(ensure(ctx, wk.T, np * nd * sizeof(float)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(np, nd))); // (the size similarity() will ask for: a larger request there would REALLOCATE the planes computed here)
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    Counters::Flags *d_flag = &wk.d_counters()->flags;
+    HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(*d_flag), ctx->stream));
+    // uniform power-of-two sample count: taken from the first pixel; the distance kernel checks every pixel against it and raises the
+    // flag that sends the scale to the exact kernels if the guess was wrong (k_pairdist_rw, range_flag bit 1)
+    // (a strided sample of 1024 pixels settles the usual non-uniform case -- adaptive sampling -- on the host at no cost)
+    float uni_n = 0.f;
+    {
+        const float *h_ns = h_src[1];
+        const float n0 = h_ns[0];
+        if (is_pow2_sample_count(n0)) uni_n = n0;
+        const size_t stride = std::max<size_t>(1, np / 1024);
+        for (size_t i = 0; i < np && uni_n > 0.f; i += stride)
+            if (h_ns[i] != n0) uni_n = 0.f;
+    }
+    // general sample counts: the RATIO form of the kernel, as similarity() chooses it for a resident frame, unless this workspace has seen it decline
+    // on frames of this size.  Its statistics are cleared here and judged behind the last tile row (the verdict needs the whole frame).
+    const bool ratio = uni_n == 0.f && !wk.ratio_is_declined(W, H);
+    if (ratio) {
+        RCCHK(ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)));
+        HIPCHK(ctx, bcd_launch_ratio_begin((unsigned int *)wk.ratio_stats.p, ctx->stream));
+    }
+    const int chunk = std::max(64, ((H + 7) / 8 + tile - 1) / tile * tile); // ~8 chunks, whole tile rows
+    const int tile_rows = (H + tile - 1) / tile;
+    int filtered = 0, tiles_done = 0, k = 0;
+    if (poison) { // (self-test) whatever this function reads or writes holds 0xFF bytes before the first transfer: a line that is read before it has arrived shows
+        for (int i = 0; i < 4; ++i) {
+            HIPCHK(ctx, hipMemsetAsync(d[i], 0xFF, sz[i] * sizeof(float), ctx->stream));
+            if (d[5 + i] != d[i]) HIPCHK(ctx, hipMemsetAsync(d[5 + i], 0xFF, sz[i] * sizeof(float), ctx->stream));
+        }
+        HIPCHK(ctx, hipMemsetAsync(wk.T.p, 0xFF, np * nd * sizeof(float), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(wk.Cn.p, 0xFF, count_plane_bytes(np, nd), ctx->stream));
+    }
+    // the upload stream must not overwrite device copies an earlier frame's kernels may still read
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // colours, sample counts and covariances first, whole (83 MB at 1080p; the prefilter and the distance kernel need them with the
+    // first histogram lines), then the histograms -- 87 % of the bytes -- in row chunks
+    // Without the prefilter only the sample counts are needed with the first histogram lines (the distance kernel); colours and covariances
+    // are first read by the pyramid and the estimate stage.  Their (pageable, host-blocking) copies then run on a helper thread and a
+    // stream of their own beside the histogram pieces, whose pace is set by the host-side packing and leaves the link half idle (round 4).
+    std::thread side_copy;
+    hipError_t side_rc = hipSuccess;
+    struct SideJoin { std::thread &t; ~SideJoin() { if (t.joinable()) t.join(); } } side_join{ side_copy };
+    const bool side = !prefilter && ctx->sparse_uploads && (D & 3) == 0;
+    if (side) {
+        if (!ctx->upload_stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream2, hipStreamNonBlocking));
+        if (!ctx->ev_upload2) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_upload2, hipEventDisableTiming));
+        HIPCHK(ctx, hipMemcpyAsync(d[1], h_src[1], sz[1] * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
+        const int dev = ctx->device;
+        hipStream_t s2 = ctx->upload_stream2;
+        hipEvent_t e2 = ctx->ev_upload2;
+        float *dc = d[0], *dv = d[3];
+        const float *hc = h_src[0], *hv = h_src[3];
+        const size_t nc = sz[0] * sizeof(float), nv = sz[3] * sizeof(float);
+        side_copy = std::thread([=, &side_rc]() {
+            hipError_t e = hipSetDevice(dev);
+            if (e == hipSuccess) e = hipMemcpyAsync(dc, hc, nc, hipMemcpyHostToDevice, s2);
+            if (e == hipSuccess) e = hipMemcpyAsync(dv, hv, nv, hipMemcpyHostToDevice, s2);
+            if (e == hipSuccess) e = hipEventRecord(e2, s2);
+            side_rc = e;
+        });
+    } else
+        for (int i : { 0, 1, 3 }) HIPCHK(ctx, hipMemcpyAsync(d[i], h_src[i], sz[i] * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
+    const bool sparse = ctx->sparse_uploads && (D & 3) == 0;
+    if (sparse) {
+        RCCHK(host_sparse_uploader(ctx));
+        bcd_sparse_frame_begin(ctx->sparse);
+    }
+    ctx->upload_raw_bytes = ctx->upload_sent_bytes = (long long)sz[2] * 4;
+    for (int r0 = 0; r0 < H && (stop_after_chunks < 0 || k < stop_after_chunks); r0 += chunk, ++k) {
+        const int r1 = std::min(H, r0 + chunk);
+        {
+            const size_t off = (size_t)r0 * W * D, n = (size_t)(r1 - r0) * W * D;
+            if (sparse) HIPCHK(ctx, bcd_sparse_upload(ctx->sparse, d[2] + off, h_src[2] + off, n, ctx->upload_stream)); // (off % 4 == 0: D % 4 == 0 on this path)
+            else HIPCHK(ctx, hipMemcpyAsync(d[2] + off, h_src[2] + off, n * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
+        }
+        if ((int)ctx->ev_upload.size() <= k) {
+            hipEvent_t ev;
+            HIPCHK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            ctx->ev_upload.push_back(ev);
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upload[k], ctx->upload_stream));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload[k], 0));
+        int avail = r1;
+        if (prefilter) { // a filtered line reads its own and the two adjacent input lines (clamped inward at the frame border)
+            const int upto = r1 == H ? H : std::max(0, r1 - 1);
+            HIPCHK(ctx, bcd_launch_spike_rows(d[0], d[1], d[2], d[3], W, H, D, spike_factor, d[5], d[6], d[7], d[8], filtered, upto, ctx->stream));
+            filtered = std::max(filtered, upto);
+            avail = filtered;
+        }
+        // a tile row reads its own lines and the b lines below them
+        const int t_end = avail == H ? tile_rows : std::max(0, (avail - b) / tile);
+        if (t_end > tiles_done) {
+            if (ratio) HIPCHK(ctx, bcd_launch_pairdist_rw_ratio_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, (unsigned int *)wk.ratio_stats.p, tiles_done, t_end, ctx->stream));
+            else HIPCHK(ctx, bcd_launch_pairdist_rw_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, tiles_done, t_end, ctx->stream));
+            tiles_done = t_end;
+            if (ratio && tiles_done == tile_rows) HIPCHK(ctx, bcd_launch_ratio_verdict((const unsigned int *)wk.ratio_stats.p, tau, &d_flag->range, ctx->stream));
+        }
+    }
+    if (sparse) bcd_sparse_frame_bytes(ctx->sparse, &ctx->upload_raw_bytes, &ctx->upload_sent_bytes);
+    if (side) { // colours and covariances have been enqueued by now (the helper thread is joined), the frame's kernels wait for their arrival
+        side_copy.join();
+        HIPCHK(ctx, side_rc);
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload2, 0));
+    }
+    out->chunk_lines = chunk; out->chunks = k; out->rows_filtered = filtered; out->tile_rows_done = tiles_done; out->uni_n = uni_n; out->ratio = ratio;
+    return BCD_HIP_OK;
+}
+
 // bcd_hip_denoise_host_ex, and -- with `extra`: host images of further colour layers -- bcd_hip_denoise_layers_host: the primary inputs travel as they always
 // did (streamed, the histograms without their zeros), the extra layers as plain copies behind them
 static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
@@ -31,106 +167,17 @@ static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const floa
     // src/cli/main.cpp:428-441, on the device copies: no second trip over PCIe) and the finest scale's approximate distance planes -- the
     // largest single kernel of the frame, and a function of the histograms alone -- are computed for them while the next chunk travels.
     // Everything else needs the whole frame (pyramid, the marking order) and follows the last chunk.
-    const int b = prm->search_radius, tile = bcd_pairdist_rw_tile_lines();
-    const bool stream_in = ctx->stream_uploads && fast_similarity_applies(ctx, D, prm->patch_radius, prm->hist_dist_threshold) && H >= 256;
+    const int b = prm->search_radius;
+    const bool stream_in = host_frame_streams(ctx, H, D, prm);
     if (!stream_in) {
         for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipMemcpyAsync(d[i], src[i], sz[i] * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         if (prefilter) HIPCHK(ctx, bcd_launch_spike(d[0], d[1], d[2], d[3], W, H, D, opt->spike_factor, d[5], d[6], d[7], d[8], ctx->stream));
     } else {
+        HostStreamProgress done;
+        RCCHK(host_stream_frame(ctx, src, d, W, H, D, b, prm->hist_dist_threshold, prefilter, prefilter ? opt->spike_factor : 0.f, -1, false, &done));
         Work &wk = ctx->main;
-        if (!ctx->upload_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
-        const int nd = bcd_delta_count(b);
-        RCCHK(ensure(ctx, wk.T, np * nd * sizeof(float)));
-        RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(np, nd))); // (the size similarity() will ask for: a larger request there would REALLOCATE the planes computed here)
-        RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
-        Counters::Flags *d_flag = &wk.d_counters()->flags;
-        HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(*d_flag), ctx->stream));
-        // uniform power-of-two sample count: taken from the first pixel; the distance kernel checks every pixel against it and raises the
-        // flag that sends the scale to the exact kernels if the guess was wrong (k_pairdist_rw, range_flag bit 1)
-        // (a strided sample of 1024 pixels settles the usual non-uniform case -- adaptive sampling -- on the host at no cost)
-        float uni_n = 0.f;
-        {
-            const float n0 = h_ns[0];
-            if (is_pow2_sample_count(n0)) uni_n = n0;
-            const size_t stride = std::max<size_t>(1, np / 1024);
-            for (size_t i = 0; i < np && uni_n > 0.f; i += stride)
-                if (h_ns[i] != n0) uni_n = 0.f;
-        }
-        const int chunk = std::max(64, ((H + 7) / 8 + tile - 1) / tile * tile); // ~8 chunks, whole tile rows
-        const int tile_rows = (H + tile - 1) / tile;
-        int filtered = 0, tiles_done = 0, k = 0;
-        // the upload stream must not overwrite device copies an earlier frame's kernels may still read
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        // colours, sample counts and covariances first, whole (83 MB at 1080p; the prefilter and the distance kernel need them with the
-        // first histogram lines), then the histograms -- 87 % of the bytes -- in row chunks
-        // Without the prefilter only the sample counts are needed with the first histogram lines (the distance kernel); colours and covariances
-        // are first read by the pyramid and the estimate stage.  Their (pageable, host-blocking) copies then run on a helper thread and a
-        // stream of their own beside the histogram pieces, whose pace is set by the host-side packing and leaves the link half idle (round 4).
-        std::thread side_copy;
-        hipError_t side_rc = hipSuccess;
-        struct SideJoin { std::thread &t; ~SideJoin() { if (t.joinable()) t.join(); } } side_join{ side_copy };
-        const bool side = !prefilter && ctx->sparse_uploads && (D & 3) == 0;
-        if (side) {
-            if (!ctx->upload_stream2) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream2, hipStreamNonBlocking));
-            if (!ctx->ev_upload2) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_upload2, hipEventDisableTiming));
-            HIPCHK(ctx, hipMemcpyAsync(d[1], src[1], sz[1] * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
-            const int dev = ctx->device;
-            hipStream_t s2 = ctx->upload_stream2;
-            hipEvent_t e2 = ctx->ev_upload2;
-            float *dc = d[0], *dv = d[3];
-            const float *hc = src[0], *hv = src[3];
-            const size_t nc = sz[0] * sizeof(float), nv = sz[3] * sizeof(float);
-            side_copy = std::thread([=, &side_rc]() {
-                hipError_t e = hipSetDevice(dev);
-                if (e == hipSuccess) e = hipMemcpyAsync(dc, hc, nc, hipMemcpyHostToDevice, s2);
-                if (e == hipSuccess) e = hipMemcpyAsync(dv, hv, nv, hipMemcpyHostToDevice, s2);
-                if (e == hipSuccess) e = hipEventRecord(e2, s2);
-                side_rc = e;
-            });
-        } else
-            for (int i : { 0, 1, 3 }) HIPCHK(ctx, hipMemcpyAsync(d[i], src[i], sz[i] * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
-        const bool sparse = ctx->sparse_uploads && (D & 3) == 0;
-        if (sparse) {
-            if (!ctx->sparse && !(ctx->sparse = bcd_sparse_create())) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
-            bcd_sparse_frame_begin(ctx->sparse);
-        }
-        ctx->upload_raw_bytes = ctx->upload_sent_bytes = (long long)sz[2] * 4;
-        for (int r0 = 0; r0 < H; r0 += chunk, ++k) {
-            const int r1 = std::min(H, r0 + chunk);
-            {
-                const size_t off = (size_t)r0 * W * D, n = (size_t)(r1 - r0) * W * D;
-                if (sparse) HIPCHK(ctx, bcd_sparse_upload(ctx->sparse, d[2] + off, h_hist + off, n, ctx->upload_stream)); // (off % 4 == 0: D % 4 == 0 on this path)
-                else HIPCHK(ctx, hipMemcpyAsync(d[2] + off, h_hist + off, n * sizeof(float), hipMemcpyHostToDevice, ctx->upload_stream));
-            }
-            if ((int)ctx->ev_upload.size() <= k) {
-                hipEvent_t ev;
-                HIPCHK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                ctx->ev_upload.push_back(ev);
-            }
-            HIPCHK(ctx, hipEventRecord(ctx->ev_upload[k], ctx->upload_stream));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload[k], 0));
-            int avail = r1;
-            if (prefilter) { // a filtered line reads its own and the two adjacent input lines (clamped inward at the frame border)
-                const int upto = r1 == H ? H : std::max(0, r1 - 1);
-                HIPCHK(ctx, bcd_launch_spike_rows(d[0], d[1], d[2], d[3], W, H, D, opt->spike_factor, d[5], d[6], d[7], d[8], filtered, upto, ctx->stream));
-                filtered = std::max(filtered, upto);
-                avail = filtered;
-            }
-            // a tile row reads its own lines and the b lines below them
-            const int t_end = avail == H ? tile_rows : std::max(0, (avail - b) / tile);
-            if (t_end > tiles_done) {
-                HIPCHK(ctx, bcd_launch_pairdist_rw_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, tiles_done, t_end, ctx->stream));
-                tiles_done = t_end;
-            }
-        }
-        if (sparse) bcd_sparse_frame_bytes(ctx->sparse, &ctx->upload_raw_bytes, &ctx->upload_sent_bytes);
-        if (side) { // colours and covariances have been enqueued by now (the helper thread is joined), the frame's kernels wait for their arrival
-            side_copy.join();
-            HIPCHK(ctx, side_rc);
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload2, 0));
-        }
         wk.planes.ready = true; wk.planes.hist = d[7]; wk.planes.ns = d[6]; wk.planes.W = W; wk.planes.H = H; wk.planes.D = D; wk.planes.b = b;
-        wk.planes.tau = prm->hist_dist_threshold; wk.planes.uni_n = uni_n;
+        wk.planes.tau = prm->hist_dist_threshold; wk.planes.uni_n = done.uni_n; wk.planes.ratio = done.ratio;
     }
     LayerView lv;
     if (nb_extra > 0) { // device copies of the extra layers: colours | covariances | outputs, one slice per layer

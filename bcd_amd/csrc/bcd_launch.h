@@ -28,6 +28,10 @@ hipError_t bcd_launch_pairdist_rw_rows(const float *hist, const float *ns, int W
                                        float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st);
 hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
                                         float tau, unsigned int *stats, hipStream_t st);
+hipError_t bcd_launch_ratio_begin(unsigned int *stats, hipStream_t st);
+hipError_t bcd_launch_pairdist_rw_ratio_rows(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
+                                             unsigned int *stats, int tile_row_begin, int tile_row_end, hipStream_t st);
+hipError_t bcd_launch_ratio_verdict(const unsigned int *stats, float tau, int *d_range_flag, hipStream_t st);
 hipError_t bcd_launch_pairdist_rw_counting(const float *hist, const float *ns, int W, int H, int D, int b, void *T, uint8_t *Cn, int *d_range_flag, float uni_n,
                                            unsigned long long *work_count, hipStream_t st);
 hipError_t bcd_launch_max_rel_dev(const float *Ta, const float *Tb, const uint8_t *Ca, const uint8_t *Cb, int W, int H, int b, unsigned int *out, hipStream_t st);
@@ -38,6 +42,7 @@ BcdSparseUploader *bcd_sparse_create();
 void bcd_sparse_destroy(BcdSparseUploader *u);
 void bcd_sparse_frame_begin(BcdSparseUploader *u);
 void bcd_sparse_frame_bytes(const BcdSparseUploader *u, long long *raw, long long *sent);
+void bcd_sparse_set_piece(BcdSparseUploader *u, size_t floats);
 hipError_t bcd_sparse_upload(BcdSparseUploader *u, float *dst, const float *src, size_t n, hipStream_t st);
 
 // ---- k_pointwise.hip

@@ -209,4 +209,100 @@ int bcd_hip_selftest_division(bcd_hip_ctx *ctx, uint32_t seed, int64_t samples, 
     return BCD_HIP_OK;
 }
 
+// ---- the host-buffer upload path piece by piece (tests/test_gpu_sparse_upload.py, tests/test_gpu_host_stream.py)
+
+int bcd_hip_selftest_sparse_upload(bcd_hip_ctx *ctx, const float *h_src, int64_t n, float *d_dst, int new_frame, int64_t piece_floats,
+                                   int64_t *raw_bytes, int64_t *sent_bytes)
+{
+    if (!ctx || !h_src || !d_dst || n < 0 || piece_floats < 0 || (piece_floats & 3) != 0 || !raw_bytes || !sent_bytes) return bad(ctx, "bad argument");
+    DEVICE_GUARD(ctx);
+    RCCHK(host_upload_stream(ctx));
+    RCCHK(host_sparse_uploader(ctx));
+    if (new_frame) bcd_sparse_frame_begin(ctx->sparse);
+    bcd_sparse_set_piece(ctx->sparse, (size_t)piece_floats);
+    const hipError_t e = bcd_sparse_upload(ctx->sparse, d_dst, h_src, (size_t)n, ctx->upload_stream);
+    bcd_sparse_set_piece(ctx->sparse, 0); // (the host path keeps the default)
+    const hipError_t e2 = hipStreamSynchronize(ctx->upload_stream);
+    HIPCHK(ctx, e);
+    HIPCHK(ctx, e2);
+    long long raw = 0, sent = 0;
+    bcd_sparse_frame_bytes(ctx->sparse, &raw, &sent);
+    *raw_bytes = raw; *sent_bytes = sent;
+    return BCD_HIP_OK;
+}
+
+// the flag words of the distance kernels as the upload self-tests return them: bit 0 range, bit 1 "a pixel carries another sample count"
+static int read_plane_flags(bcd_hip_ctx *ctx, Work &wk, int *out)
+{
+    Counters::Flags flags = {};
+    HIPCHK(ctx, hipMemcpyAsync(&flags, &wk.d_counters()->flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out = (flags.range & ~2) | (flags.other_count ? 2 : 0);
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_selftest_host_stream(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov, int W, int H, int D,
+                                 const bcd_hip_params *prm, float spike_factor, int stop_after_chunks, int poison, void *d_planes, uint8_t *d_counts,
+                                 float *d_colors_out, float *d_ns_out, float *d_hist_out, float *d_cov_out, float *d_hist_uploaded,
+                                 bcd_hip_host_stream_result *res)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!h_colors || !h_ns || !h_hist || !h_cov || !d_planes || !d_counts || !d_colors_out || !d_ns_out || !d_hist_out || !d_cov_out || !res) return bad(ctx, "null pointer");
+    RCCHK(check_params(ctx, W, H, D, prm));
+    DEVICE_GUARD(ctx);
+    const bool prefilter = spike_factor > 0.f;
+    if (prefilter && (W < 3 || H < 3)) return bad(ctx, "image smaller than 3x3");
+    if (!host_frame_streams(ctx, H, D, prm)) { set_err(ctx, "bcd_hip_denoise_host_ex would not stream this frame in"); return BCD_HIP_EUNSUPPORTED; }
+    touch(ctx->main);
+    const size_t np = (size_t)W * H;
+    const size_t sz[4] = { np * 3, np, np * D, np * 6 };
+    const float *src[4] = { h_colors, h_ns, h_hist, h_cov };
+    // the device copies bcd_hip_denoise_host_ex uses
+    float *d[9];
+    for (int i = 0; i < 4; ++i) { RCCHK(ensure(ctx, ctx->host_stage[i], sz[i] * sizeof(float))); d[i] = (float *)ctx->host_stage[i].p; }
+    d[4] = nullptr;
+    for (int i = 0; i < 4; ++i) {
+        d[5 + i] = d[i];
+        if (prefilter) { RCCHK(ensure(ctx, ctx->host_stage[5 + i], sz[i] * sizeof(float))); d[5 + i] = (float *)ctx->host_stage[5 + i].p; }
+    }
+    const int b = prm->search_radius, nd = bcd_delta_count(b);
+    HostStreamProgress done;
+    const int rc = host_stream_frame(ctx, src, d, W, H, D, b, prm->hist_dist_threshold, prefilter, spike_factor, stop_after_chunks, poison != 0, &done);
+    // (also after a failure: nothing of this call stays in flight on the upload streams)
+    hipError_t e = ctx->upload_stream ? hipStreamSynchronize(ctx->upload_stream) : hipSuccess;
+    if (ctx->upload_stream2) { const hipError_t e2 = hipStreamSynchronize(ctx->upload_stream2); if (e == hipSuccess) e = e2; }
+    RCCHK(rc);
+    HIPCHK(ctx, e);
+    Work &wk = ctx->main;
+    float *outs[4] = { d_colors_out, d_ns_out, d_hist_out, d_cov_out };
+    for (int i = 0; i < 4; ++i) HIPCHK(ctx, hipMemcpyAsync(outs[i], d[5 + i], sz[i] * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_hist_uploaded) HIPCHK(ctx, hipMemcpyAsync(d_hist_uploaded, d[2], sz[2] * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_planes, wk.T.p, np * nd * 2, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_counts, wk.Cn.p, np * nd, hipMemcpyDeviceToDevice, ctx->stream));
+    int flag = 0;
+    RCCHK(read_plane_flags(ctx, wk, &flag));
+    res->rows_filtered = done.rows_filtered; res->tile_rows_done = done.tile_rows_done; res->chunk_lines = done.chunk_lines; res->chunks_done = done.chunks;
+    res->range_flag = flag; res->uni_n = done.uni_n; res->ratio_form = done.ratio ? 1 : 0;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_approx_planes(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, int W, int H, int D, int search_radius, float uni_n, int ratio_form, float tau,
+                          void *d_planes, uint8_t *d_counts, int *range_flag)
+{
+    if (!ctx || !d_hist || !d_ns || !d_planes || !d_counts || !range_flag || W <= 0 || H <= 0 || search_radius < 1 || !(uni_n >= 0.f) || (ratio_form && uni_n != 0.f))
+        return bad(ctx, "bad argument");
+    DEVICE_GUARD(ctx);
+    touch(ctx->main);
+    if (!bcd_pairdist_rw_supported(D)) { set_err(ctx, "no approximate kernel for this histogram depth"); return BCD_HIP_EUNSUPPORTED; }
+    Work &wk = ctx->main;
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    Counters::Flags *d_flag = &wk.d_counters()->flags;
+    HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(*d_flag), ctx->stream));
+    if (ratio_form) {
+        RCCHK(ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)));
+        HIPCHK(ctx, bcd_launch_pairdist_rw_ratio(d_hist, d_ns, W, H, D, search_radius, d_planes, d_counts, &d_flag->range, tau, (unsigned int *)wk.ratio_stats.p, ctx->stream));
+    } else HIPCHK(ctx, bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, search_radius, d_planes, d_counts, &d_flag->range, uni_n, ctx->stream));
+    return read_plane_flags(ctx, wk, range_flag);
+}
+
 } // extern "C"

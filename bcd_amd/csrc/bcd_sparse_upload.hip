@@ -184,6 +184,7 @@ struct BcdSparseUploader {
     Piece buf[SP_BUFFERS];
     int cur = 0;                    // buffer the next submit() packs into
     bool dense = false;             // this frame's image turned out dense: plain copies from here on
+    size_t piece = SP_PIECE;        // floats per piece (bcd_sparse_set_piece: the self-test of the upload walks many pieces of a small image)
     long long raw_bytes = 0, sent_bytes = 0; // of the last frame
 
     // one task = SP_TASK consecutive blocks: packed into a scratch buffer of the thread (stays in its cache), then appended to the piece's
@@ -345,6 +346,9 @@ BcdSparseUploader *bcd_sparse_create() { return new (std::nothrow) BcdSparseUplo
 void bcd_sparse_destroy(BcdSparseUploader *u) { delete u; }
 void bcd_sparse_frame_begin(BcdSparseUploader *u) { u->dense = false; u->raw_bytes = 0; u->sent_bytes = 0; }
 void bcd_sparse_frame_bytes(const BcdSparseUploader *u, long long *raw, long long *sent) { *raw = u->raw_bytes; *sent = u->sent_bytes; }
+// floats per piece: a multiple of 4 (every piece's destination stays 16-byte aligned), 0 = the default.  The staging buffers are sized for
+// max(piece, default) either way.  For bcd_hip_selftest_sparse_upload alone: the host path keeps the default.
+void bcd_sparse_set_piece(BcdSparseUploader *u, size_t floats) { u->piece = floats ? floats : SP_PIECE; }
 
 // `n` floats from host memory `src` to device memory `dst` (both 16-byte aligned) on `st`, in pieces: piece k + 1 is packed while piece k
 // travels.  Returns when everything is enqueued; the host buffer must stay valid until `st` has passed these operations (dense images are
@@ -362,11 +366,11 @@ hipError_t bcd_sparse_upload(BcdSparseUploader *u, float *dst, const float *src,
         return rc;
     };
     if (!u->dense) {
-        if ((e = u->submit(src, std::min(n, SP_PIECE))) != hipSuccess) return e;
+        if ((e = u->submit(src, std::min(n, u->piece))) != hipSuccess) return e;
         packing = true;
     }
     while (done < n) {
-        const size_t len = std::min(n - done, SP_PIECE);
+        const size_t len = std::min(n - done, u->piece);
         if (u->dense) { // (found out on an earlier piece)
             u->raw_bytes += (long long)(n - done) * 4; u->sent_bytes += (long long)(n - done) * 4;
             return settle(hipMemcpyAsync(dst + done, src + done, (n - done) * 4, hipMemcpyHostToDevice, st));
@@ -376,7 +380,7 @@ hipError_t bcd_sparse_upload(BcdSparseUploader *u, float *dst, const float *src,
         if ((e = u->flush(dst + done, st)) != hipSuccess) return e;
         done += len;
         if (done < n && !u->dense) {
-            if ((e = u->submit(src + done, std::min(n - done, SP_PIECE))) != hipSuccess) return e;
+            if ((e = u->submit(src + done, std::min(n - done, u->piece))) != hipSuccess) return e;
             packing = true;
         }
     }

@@ -515,17 +515,33 @@ static hipError_t pairdist_rw_rows(const float *hist, const float *ns, int W, in
     return hipErrorInvalidValue;
 }
 
-// general sample counts by the RATIO form (whole frame): clears `stats` (128 words), runs the kernel and its verdict (flag value 4 in d_range_flag[0]
-// when the form's absolute-error check fails: the caller repeats the pass with bcd_launch_pairdist_rw(..., uni_n = 0))
-hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
-                                        float tau, unsigned int *stats, hipStream_t st)
+// general sample counts by the RATIO form, tile rows [tile_row_begin, tile_row_end) (end < 0: to the last one).  The launches of a frame share `stats` (128 words):
+// bcd_launch_ratio_begin clears them before the first launch, bcd_launch_ratio_verdict judges them after the last one (flag value 4 in d_range_flag[0] when the
+// form's absolute-error check fails: the caller repeats the pass with bcd_launch_pairdist_rw(..., uni_n = 0)).  The maxima in `stats` do not depend on the partition.
+hipError_t bcd_launch_ratio_begin(unsigned int *stats, hipStream_t st)
 {
     if (!stats) return hipErrorInvalidValue;
-    dim3 grid((W + RW_TW - 1) / RW_TW, (H + RW_TH - 1) / RW_TH), block(RW_THREADS);
+    return hipMemsetAsync(stats, 0, 128 * sizeof(unsigned int), st);
+}
+
+hipError_t bcd_launch_ratio_verdict(const unsigned int *stats, float tau, int *d_range_flag, hipStream_t st)
+{
+    if (!stats) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ratio_verdict, dim3(1), dim3(64), 0, st, stats, tau, d_range_flag);
+    return hipGetLastError();
+}
+
+hipError_t bcd_launch_pairdist_rw_ratio_rows(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
+                                             unsigned int *stats, int tile_row_begin, int tile_row_end, hipStream_t st)
+{
+    if (!stats) return hipErrorInvalidValue;
+    const int tile_rows = (H + RW_TH - 1) / RW_TH;
+    if (tile_row_end < 0 || tile_row_end > tile_rows) tile_row_end = tile_rows;
+    if (tile_row_begin < 0 || tile_row_begin >= tile_row_end) return tile_row_begin == tile_row_end ? hipSuccess : hipErrorInvalidValue;
+    dim3 grid((W + RW_TW - 1) / RW_TW, tile_row_end - tile_row_begin), block(RW_THREADS);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    hipError_t e = hipMemsetAsync(stats, 0, 128 * sizeof(unsigned int), st);
-    if (e != hipSuccess) return e;
+    hipError_t e;
 #define BCD_RW_RATIO(DD)                                                                                             \
     case DD: {                                                                                                       \
         const size_t lds = (size_t)RwLayout<DD>::LDS_DWORDS * 4;                                                     \
@@ -535,7 +551,7 @@ hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int 
             if (e != hipSuccess) return e;                                                                           \
             if (dev >= 0 && dev < 64) granted[dev].store(1);                                                         \
         }                                                                                                            \
-        hipLaunchKernelGGL((k_pairdist_rw<DD, false, false, true>), grid, block, lds, st, hist, ns, W, H, b, static_cast<__half *>(T), Cn, d_range_flag, 0.f, 0, \
+        hipLaunchKernelGGL((k_pairdist_rw<DD, false, false, true>), grid, block, lds, st, hist, ns, W, H, b, static_cast<__half *>(T), Cn, d_range_flag, 0.f, tile_row_begin, \
                            (unsigned long long *)nullptr, stats);                                                    \
     } break;
     switch (D) {
@@ -545,8 +561,17 @@ hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int 
     default: return hipErrorInvalidValue;
     }
 #undef BCD_RW_RATIO
-    hipLaunchKernelGGL(k_ratio_verdict, dim3(1), dim3(64), 0, st, stats, tau, d_range_flag);
     return hipGetLastError();
+}
+
+// the whole frame: clears `stats`, runs the kernel and its verdict
+hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
+                                        float tau, unsigned int *stats, hipStream_t st)
+{
+    hipError_t e = bcd_launch_ratio_begin(stats, st);
+    if (e != hipSuccess) return e;
+    if ((e = bcd_launch_pairdist_rw_ratio_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, stats, 0, -1, st)) != hipSuccess) return e;
+    return bcd_launch_ratio_verdict(stats, tau, d_range_flag, st);
 }
 
 hipError_t bcd_launch_pairdist_rw_rows(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,

@@ -40,6 +40,17 @@ class HostOptions(C.Structure):
     _fields_ = [("spike_factor", C.c_float), ("zero_bad_values", C.c_int32)]
 
 
+class HostStreamResult(C.Structure):
+    """bcd_hip_host_stream_result"""
+    _fields_ = [("rows_filtered", C.c_int32), ("tile_rows_done", C.c_int32), ("chunk_lines", C.c_int32), ("chunks_done", C.c_int32),
+                ("range_flag", C.c_int32), ("uni_n", C.c_float), ("ratio_form", C.c_int32)]
+
+
+def delta_count(b):
+    """planes of a search radius b: the half plane of displacements (bcd_delta_count)"""
+    return (b + 1) + b * (2 * b + 1)
+
+
 class PlanParams(C.Structure):
     """bcd_hip_plan_params (adaptive sample planning, bcd_hip_accum_plan)"""
     _fields_ = [("threshold", C.c_float), ("eps", C.c_float), ("min_samples", C.c_float), ("max_per_pixel", C.c_int32)]
@@ -167,6 +178,7 @@ SYMBOLS = [
     "bcd_hip_accum_set_filter", "bcd_hip_accum_add_splatted", "bcd_hip_filter_table",
     "bcd_hip_accum_state_info", "bcd_hip_accum_state_bytes", "bcd_hip_accum_export", "bcd_hip_accum_import", "bcd_hip_accum_merge_state", "bcd_hip_accum_merge",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch", "bcd_hip_eig27_batch_rule",
+    "bcd_hip_selftest_sparse_upload", "bcd_hip_selftest_host_stream", "bcd_hip_approx_planes",
 ]
 
 _lib = None
@@ -320,6 +332,60 @@ class Context:
         a, b = C.c_int64(0), C.c_int64(0)
         self._chk(lib().bcd_hip_last_upload_bytes(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def selftest_sparse_upload(self, src, dst=None, new_frame=True, piece_floats=0):
+        """bcd_hip_selftest_sparse_upload: the float32 / uint32 numpy array `src` through the context's sparse uploader into the device tensor `dst`
+        (same number of 4-byte elements, any alignment; default: a fresh tensor) -> (dst, (raw bytes, sent bytes) of the frame so far)"""
+        import numpy as np
+        torch = self.torch
+        assert src.dtype.itemsize == 4 and src.flags["C_CONTIGUOUS"]
+        if dst is None:
+            dst = torch.empty((max(src.size, 1),), dtype=torch.float32, device="cuda:%d" % self.device)[:src.size]
+        assert dst.is_cuda and dst.is_contiguous() and dst.element_size() == 4 and dst.numel() == src.size
+        a, b = C.c_int64(0), C.c_int64(0)
+        L = lib()
+        L.bcd_hip_selftest_sparse_upload.argtypes = [_VP, _VP, C.c_int64, _VP, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        hp = src.ctypes.data_as(_VP) if src.size else np.zeros(1, np.float32).ctypes.data_as(_VP)
+        self._chk(L.bcd_hip_selftest_sparse_upload(self.h, hp, src.size, C.c_void_p(dst.data_ptr()), 1 if new_frame else 0, int(piece_floats),
+                                                   C.byref(a), C.byref(b)))
+        return dst, (a.value, b.value)
+
+    def selftest_host_stream(self, col, ns, hist, cov, prm, spike_factor=0.0, stop_after_chunks=-1, poison=True):
+        """bcd_hip_selftest_host_stream on host (numpy) images -> dict: planes (nd, H, W) float16, counts (nd, H, W) uint8, images (the four the
+        planes were computed on), hist_uploaded, and the fields of bcd_hip_host_stream_result"""
+        torch = self.torch
+        H, W, D = hist.shape
+        dev = "cuda:%d" % self.device
+        nd = delta_count(prm.search_radius)
+        planes = torch.empty((nd, H, W), dtype=torch.float16, device=dev)
+        counts = torch.empty((nd, H, W), dtype=torch.uint8, device=dev)
+        imgs = [torch.empty(a.shape, dtype=torch.float32, device=dev) for a in (col, ns, hist, cov)]
+        up = torch.empty(hist.shape, dtype=torch.float32, device=dev)
+        res = HostStreamResult()
+        f = lambda a: a.ctypes.data_as(_F)
+        L = lib()
+        L.bcd_hip_selftest_host_stream.argtypes = [_VP, _F, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_float, C.c_int, C.c_int,
+                                                   _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(HostStreamResult)]
+        self._chk(L.bcd_hip_selftest_host_stream(self.h, f(col), f(ns), f(hist), f(cov), W, H, D, C.byref(prm), spike_factor, int(stop_after_chunks),
+                                                 1 if poison else 0, _dp(planes), _dp(counts), *[_dp(t) for t in imgs], _dp(up), C.byref(res)))
+        out = {k: getattr(res, k) for k, _ in HostStreamResult._fields_}
+        out.update(planes=planes, counts=counts, images=imgs, hist_uploaded=up)
+        return out
+
+    def approx_planes(self, hist, ns, b, uni_n, ratio_form=False, tau=1.0, fill=0xFF):
+        """bcd_hip_approx_planes on resident tensors -> (planes (nd, H, W) float16, counts (nd, H, W) uint8, range flag); entries the kernel does not
+        write (the neighbour lies outside the image) keep the `fill` byte"""
+        torch = self.torch
+        H, W, D = hist.shape
+        nd = delta_count(b)
+        planes = torch.full((nd, H, W, 2), fill, dtype=torch.uint8, device=hist.device).view(torch.float16).reshape(nd, H, W)
+        counts = torch.full((nd, H, W), fill, dtype=torch.uint8, device=hist.device)
+        flag = C.c_int(0)
+        L = lib()
+        L.bcd_hip_approx_planes.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _VP, _VP, C.POINTER(C.c_int)]
+        self.torch.cuda.synchronize(self.device)                     # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_approx_planes(self.h, _dp(hist), _dp(ns), W, H, D, int(b), float(uni_n), 1 if ratio_form else 0, float(tau), _dp(planes), _dp(counts), C.byref(flag)))
+        return planes, counts, flag.value
 
     def set_progress_callback(self, fn):
         """fn(progress) or None; the ctypes thunk is kept alive on the context"""

@@ -544,6 +544,42 @@ int bcd_hip_selftest_bin_work(bcd_hip_ctx *ctx, const float *d_hist, const float
 int bcd_hip_selftest_approx_distance(bcd_hip_ctx *ctx, const float *d_hist, const float *d_nsamples, int W, int H, int D, int search_radius,
                                      float *max_rel_dev, int64_t *count_mismatches, int *flags);
 
+/* ---- the host-buffer upload path piece by piece (self-tests; what the host-buffer entry points run, not copies of it) ---- */
+/* The sparse histogram upload on its own: n host floats through the context's uploader (created as bcd_hip_denoise_host_ex creates it) to d_dst -- any
+ * alignment; a destination that is not 16-byte aligned travels as a plain copy -- on the upload stream, synchronised before the call returns.
+ * new_frame != 0 starts a frame first (byte counters cleared, the "this frame is dense" decision forgotten); piece_floats: the length of a piece, a
+ * multiple of 4, 0 = the 12 Mi floats of the host path (the length is set for this call alone).  *raw_bytes, *sent_bytes: the frame's counters so far.
+ * The packed form of a piece of n floats is 66 words per block of 2048 floats (64 mask words, the offset and the count of the block's values) plus
+ * the values whose bit pattern is not zero; a piece with more than 60 % of them travels as it is, and so does the rest of its frame. */
+int bcd_hip_selftest_sparse_upload(bcd_hip_ctx *ctx, const float *h_src, int64_t n, float *d_dst, int new_frame, int64_t piece_floats,
+                                   int64_t *raw_bytes, int64_t *sent_bytes);
+/* The streamed upload of bcd_hip_denoise_host_ex on its own (frames of >= 256 lines on the approximate-planes path; BCD_HIP_EUNSUPPORTED otherwise): the
+ * frame arrives in row chunks, the lines that have arrived are prefiltered (spike_factor > 0) and the approximate distance planes of the tile rows
+ * whose lines are complete are launched.  stop_after_chunks = k >= 0: only chunks 0 .. k-1 are uploaded and scheduled (< 0: all); poison != 0: every
+ * device buffer the schedule reads or writes (uploaded copies, filtered copies, planes) holds 0xFF bytes before the first transfer.  Copied out
+ * afterwards: d_planes (binary16, delta-major: bcd_delta_count(b) planes of W*H), d_counts (one byte per entry, same layout), the four images the
+ * planes were computed on (the filtered copies with the prefilter, else the uploaded ones), and -- d_hist_uploaded, optional -- the uploaded histograms. */
+typedef struct bcd_hip_host_stream_result {
+    int32_t rows_filtered;   /* prefiltered lines [0, rows_filtered); 0 without the prefilter */
+    int32_t tile_rows_done;  /* plane tile rows (4 lines each) [0, tile_rows_done) */
+    int32_t chunk_lines;     /* lines per chunk */
+    int32_t chunks_done;
+    int32_t range_flag;      /* the distance kernel's flags: bit 0 a value out of range, bit 1 a pixel carries another sample count than uni_n,
+                              * bit 2 (all chunks in) the RATIO form's verdict declined */
+    float   uni_n;           /* the uniform sample count the planes were launched for (0: general sample counts) */
+    int32_t ratio_form;      /* general sample counts: 1 = by the RATIO form of the kernel (what a resident frame gets), 0 = by the reference's operations */
+} bcd_hip_host_stream_result;
+int bcd_hip_selftest_host_stream(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                                 int W, int H, int D, const bcd_hip_params *prm, float spike_factor, int stop_after_chunks, int poison,
+                                 void *d_planes, uint8_t *d_counts, float *d_colors_out, float *d_nsamples_out, float *d_histograms_out,
+                                 float *d_covariances_out, float *d_hist_uploaded, bcd_hip_host_stream_result *res);
+/* the approximate distance planes of a resident frame in ONE launch of a full-frame launcher (uni_n: the uniform power-of-two sample count, 0 = general
+ * sample counts: by the reference's operations, or -- ratio_form != 0 -- by the RATIO form with its verdict for threshold tau), written to d_planes /
+ * d_counts (layout as above; entries whose neighbour lies outside the image are not written); *range_flag as above.  What the partitioned launches of
+ * the streamed upload must equal bit for bit. */
+int bcd_hip_approx_planes(bcd_hip_ctx *ctx, const float *d_hist, const float *d_nsamples, int W, int H, int D, int search_radius, float uni_n,
+                          int ratio_form, float tau, void *d_planes, uint8_t *d_counts, int *range_flag);
+
 /* the eigensolver of the Bayesian steps on its own (Eigen::SelfAdjointEigenSolver of DenoisingUnit.cpp:589,617 for 27 x 27 matrices):
  * d_A = n symmetric matrices, 28 x 28 floats each, row-major, row / column 27 zero; d_eig[n][28] = eigenvalues (unordered, entry 27 = 0),
  * d_V[n][28][28] = eigenvectors in columns, same order (rows 0..26 written); *ms = kernel time (may be NULL).  Parity / timing aid. */

@@ -1970,7 +1970,9 @@ def test_streamed_host_upload_equals_the_resident_path(hipctx, spike_factor):
     """bcd_hip_denoise_host_ex on frames of >= 256 lines uploads in row chunks and computes the finest scale's distance planes (and
     the prefilter) for the lines that have arrived: the result must be the resident-input result -- same kernels, another launch
     partition -- with and without the prefilter, and also when the uniform-sample-count guess taken from the first pixel is wrong
-    (the kernel's own check sends the scale to the exact kernels)"""
+    (the kernel's own check sends the scale to the exact kernels).
+    A frame cannot show one line computed too early or left over from the last frame: the schedule itself -- which lines are filtered and which tile
+    rows of planes are launched after every chunk, bit for bit -- is tests/test_gpu_host_stream.py"""
     import bcd_amd.core as core
     import bcd_amd.hip as bh
     W, H = 200, 300
@@ -2000,7 +2002,9 @@ def test_streamed_host_upload_equals_the_resident_path(hipctx, spike_factor):
 def test_sparse_histogram_upload_is_lossless_and_falls_back_on_dense_images(hipctx, monkeypatch):
     """bcd_hip_denoise_host on frames of >= 256 lines sends the histogram image without its zeros (bit-pattern test: -0.0f and denormals travel as
     values), packed by host threads piece by piece and rebuilt by a kernel: the result must be bit-identical to the plain-copy path's inputs --
-    checked through the frame (same kernels afterwards) and through the byte counters -- and an image that is mostly non-zero is copied as it is"""
+    checked through the frame (same kernels afterwards) and through the byte counters -- and an image that is mostly non-zero is copied as it is.
+    The bits themselves (every packer and thread count, several pieces, the rotation of the staging buffers, ragged tails, the 60 % boundary) are
+    tests/test_gpu_sparse_upload.py: one lost histogram value does not move a frame by 1e-6 of its brightest pixel"""
     import bcd_amd.core as core
     import bcd_amd.hip as bh
     W, H, S = 320, 288, 3
