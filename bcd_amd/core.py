@@ -88,6 +88,40 @@ def device_splat(calls, W, H, radius, table, nbins=20, gamma=2.2, maxval=2.5, de
     return (ns, mean, cov, hist), (counts[0], counts[1])
 
 
+def device_accumulate_layers(calls, layer_rgb, W, H, radius=None, table=None, batch=0, snapshot_at=0, state_path=None, layers_path=None, nbins=20,
+                             gamma=2.2, maxval=2.5, device=0):
+    """mixed calls through the batch forms of a bcd::DeviceSamplesAccumulator with colour layers: calls (n, 7) float32 as for device_splat,
+    layer_rgb (L, n, 3) the layers' colours of the same calls; runs of one kind go through addSamples / splatSamples in pieces of at most
+    `batch` calls; snapshot_at > 0: host snapshots before that call; state_path and layers_path: saveState + saveLayers at the end, loaded
+    into a second accumulator whose statistics are returned.
+    -> ((ns, mean, cov, hist), [(mean, cov) per layer], (samples accumulated, dropped))"""
+    calls = np.ascontiguousarray(calls, np.float32)
+    layer_rgb = np.ascontiguousarray(layer_rgb, np.float32)
+    n, L = calls.shape[0], layer_rgb.shape[0]
+    assert calls.ndim == 2 and calls.shape[1] == 7 and layer_rgb.shape == (L, n, 3)
+    if table is not None:
+        table = np.ascontiguousarray(table, np.float32)
+        assert table.ndim == 2 and table.shape[0] == table.shape[1]
+    ns = np.empty((H, W, 1), np.float32)
+    mean = np.empty((H, W, 3), np.float32)
+    cov = np.empty((H, W, 6), np.float32)
+    hist = np.empty((H, W, 3 * nbins), np.float32)
+    lmean = np.empty((L, H, W, 3), np.float32)
+    lcov = np.empty((L, H, W, 6), np.float32)
+    counts = (C.c_longlong * 2)()
+    rx, ry = radius if radius is not None else (0.0, 0.0)
+    path = lambda p: None if p is None else os.fsencode(str(p))
+    rc = lib().bcdcore_device_accumulate_layers(_fp(calls), C.c_longlong(n), _fp(layer_rgb), int(L), W, H, nbins, C.c_float(gamma), C.c_float(maxval),
+                                                int(device), C.c_float(rx), C.c_float(ry), int(table.shape[0]) if table is not None else 0,
+                                                _fp(table) if table is not None else None, C.c_longlong(batch), C.c_longlong(snapshot_at),
+                                                C.c_char_p(path(state_path)), C.c_char_p(path(layers_path)), _fp(ns), _fp(mean), _fp(cov), _fp(hist),
+                                                _fp(lmean), _fp(lcov), counts)
+    if rc != 0:
+        lib().bcdcore_device_accumulate_error.restype = C.c_char_p
+        raise RuntimeError("DeviceSamplesAccumulator: " + lib().bcdcore_device_accumulate_error().decode())
+    return (ns, mean, cov, hist), [(lmean[k], lcov[k]) for k in range(L)], (counts[0], counts[1])
+
+
 def device_plan(samples, W, H, budget, offset=0, threshold=0.0, eps=1e-3, min_samples=2.0, max_per_pixel=16, nbins=20, gamma=2.2, maxval=2.5,
                 device=0, invalid_first=False):
     """the stream through bcd::DeviceSamplesAccumulator::addSample (left in its host buffer), then planSamples -> (pixel list, summary dict);

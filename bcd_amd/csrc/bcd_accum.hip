@@ -19,6 +19,8 @@ struct bcd_hip_accum {
     float gamma = 0.f, maxval = 0.f;
     int64_t N = 0;
     DevBuf state;                  // (11 + 3 nbins) planes of N floats
+    int nlayers = 0;               // extra colour layers (bcd_hip_accum_create_layers)
+    DevBuf layers;                 // nlayers x 9 planes of N floats: 3 colour sums, 6 second moments, layer after layer
     DevBuf dropped;                // unsigned long long: scattered samples with an index outside [0, N)
     DevBuf keys[2], vals[2], sort; // scattered-add scratch (grow-only)
     int64_t capacity = 0;          // > 0: samples per sorted chunk, scratch allocated at create time
@@ -47,6 +49,7 @@ struct bcd_hip_accum {
 namespace {
 
 size_t accum_state_bytes(const bcd_hip_accum *a) { return (size_t)(11 + 3 * a->nbins) * (size_t)a->N * sizeof(float); }
+size_t accum_layer_bytes(const bcd_hip_accum *a) { return (size_t)(9 * a->nlayers) * (size_t)a->N * sizeof(float); }
 
 // scratch of the scattered path for chunks of n samples
 int accum_scratch(bcd_hip_accum *a, int64_t n)
@@ -101,11 +104,10 @@ int accum_splat_scratch(bcd_hip_accum *a)
 
 } // namespace
 
-int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc)
+// create and create_layers (nb_layers = 0: no layer planes)
+static int accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
+                        bcd_hip_accum **acc)
 {
-    if (!ctx) return BCD_HIP_EINVAL;
-    if (!acc) return bad(ctx, "null accumulator handle");
-    *acc = nullptr;
     if (W <= 0 || H <= 0 || (int64_t)W * H >= ((int64_t)1 << 31)) return bad(ctx, "frame size must be positive and below 2^31 pixels");
     if (nb_bins < 2) return bad(ctx, "nb_bins must be >= 2");
     if (bcd_accum_snapshot_lds(3 * nb_bins) > 64 * 1024) { set_err(ctx, "more than 85 bins per channel are not supported"); return BCD_HIP_EUNSUPPORTED; }
@@ -116,7 +118,9 @@ int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamm
     a->ctx = ctx; a->W = W; a->H = H; a->nbins = nb_bins; a->gamma = gamma; a->maxval = max_value;
     a->N = (int64_t)W * H;
     a->capacity = max_batch_samples;
+    a->nlayers = nb_layers;
     int rc = ensure(ctx, a->state, accum_state_bytes(a));
+    if (rc == BCD_HIP_OK && nb_layers > 0) rc = ensure(ctx, a->layers, accum_layer_bytes(a));
     if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
     if (rc == BCD_HIP_OK && hipEventCreateWithFlags(&a->ev_merge, hipEventDisableTiming) != hipSuccess) {
         a->ev_merge = nullptr;
@@ -132,6 +136,32 @@ int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamm
     return BCD_HIP_OK;
 }
 
+int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, bcd_hip_accum **acc)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!acc) return bad(ctx, "null accumulator handle");
+    *acc = nullptr;
+    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, 0, acc);
+}
+
+int bcd_hip_accum_create_layers(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
+                                bcd_hip_accum **acc)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!acc) return bad(ctx, "null accumulator handle");
+    *acc = nullptr;
+    if (nb_layers < 1 || nb_layers > BCD_HIP_ACCUM_MAX_LAYERS) return bad(ctx, "nb_layers must be in [1, 15]");
+    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, nb_layers, acc);
+}
+
+int bcd_hip_accum_nb_layers(bcd_hip_accum *acc, int *nb_layers)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    if (!nb_layers) return bad(acc->ctx, "null layer count");
+    *nb_layers = acc->nlayers;
+    return BCD_HIP_OK;
+}
+
 void bcd_hip_accum_destroy(bcd_hip_accum *acc)
 {
     if (!acc) return;
@@ -140,7 +170,7 @@ void bcd_hip_accum_destroy(bcd_hip_accum *acc)
     for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
                        &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
         if (b->p) (void)hipFree(b->p);
-    for (DevBuf *b : { &acc->table, &acc->cells })
+    for (DevBuf *b : { &acc->table, &acc->cells, &acc->layers })
         if (b->p) (void)hipFree(b->p);
     if (acc->table_stage) (void)hipHostFree(acc->table_stage);
     if (acc->filter_ev) (void)hipEventDestroy(acc->filter_ev);
@@ -159,34 +189,126 @@ int bcd_hip_accum_reset(bcd_hip_accum *acc)
     bcd_hip_ctx *ctx = acc->ctx;
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, hipMemsetAsync(acc->state.p, 0, accum_state_bytes(acc), ctx->stream));
+    if (acc->nlayers > 0) HIPCHK(ctx, hipMemsetAsync(acc->layers.p, 0, accum_layer_bytes(acc), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(acc->dropped.p, 0, sizeof(unsigned long long), ctx->stream));
     acc->submitted = 0;
     return BCD_HIP_OK;
 }
 
+namespace {
+
+// the refusals of the adds: a plain add would move a layered accumulator's weight sums without its layers
+int accum_check_layered(bcd_hip_accum *acc, bool layered_call)
+{
+    if (layered_call && acc->nlayers == 0) return bad(acc->ctx, "the accumulator has no layers (bcd_hip_accum_create_layers)");
+    if (!layered_call && acc->nlayers > 0) return bad(acc->ctx, "the accumulator has colour layers: use the _layers form of this add");
+    return BCD_HIP_OK;
+}
+
+// the layers' pointer list of a _layers add (host array of nlayers device pointers) into a table, each advanced by `offset` floats
+int accum_layer_table(bcd_hip_accum *acc, const float *const *d_layers, BcdAccumLayerIn &in)
+{
+    if (!d_layers) return bad(acc->ctx, "null layer list");
+    for (int l = 0; l < BCD_ACCUM_MAX_LAYERS; ++l) in.src[l] = nullptr;
+    for (int l = 0; l < acc->nlayers; ++l) {
+        if (!d_layers[l]) return bad(acc->ctx, "null layer samples");
+        in.src[l] = d_layers[l];
+    }
+    return BCD_HIP_OK;
+}
+
+BcdAccumLayerIn accum_layer_offset(const bcd_hip_accum *acc, const BcdAccumLayerIn &in, int64_t offset)
+{
+    BcdAccumLayerIn o = in;
+    for (int l = 0; l < acc->nlayers; ++l) o.src[l] = in.src[l] + offset;
+    return o;
+}
+
+// the three adds; layers: the table of a _layers call, or nullptr on an accumulator without layers
+int accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
+                    const float *const *d_layer_samples, int layer_channels);
+int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb);
+int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb);
+
+} // namespace
+
 int bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels)
 {
     if (!acc) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = acc->ctx;
-    if (!d_samples) return bad(ctx, "null samples");
-    if (channels != 3 && channels != 4) return bad(ctx, "channels must be 3 or 4");
-    if (spp < 1) return bad(ctx, "spp must be >= 1");
-    if (rows < 1 || row_begin < 0 || row_begin > acc->H - rows) return bad(ctx, "row range outside the frame");
-    DEVICE_GUARD(ctx);
-    const int64_t npix = (int64_t)rows * acc->W;
-    HIPCHK(ctx, bcd_launch_accum_dense(d_samples, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, channels, acc->nbins, acc->gamma,
-                                       acc->maxval, (float *)acc->state.p, ctx->stream));
-    acc->submitted += npix * spp;
-    return BCD_HIP_OK;
+    RCCHK(accum_check_layered(acc, false));
+    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, nullptr, 3);
+}
+
+int bcd_hip_accum_add_dense_layers(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
+                                   const float *const *d_layer_samples, int layer_channels)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_layered(acc, true));
+    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, d_layer_samples, layer_channels);
 }
 
 int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n)
 {
     if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_layered(acc, false));
+    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, nullptr);
+}
+
+int bcd_hip_accum_add_scattered_layers(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n,
+                                       const float *const *d_layer_rgb)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_layered(acc, true));
+    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, d_layer_rgb);
+}
+
+int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_layered(acc, false));
+    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, nullptr);
+}
+
+int bcd_hip_accum_add_splatted_layers(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n,
+                                      const float *const *d_layer_rgb)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_layered(acc, true));
+    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, d_layer_rgb);
+}
+
+namespace {
+
+int accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
+                    const float *const *d_layer_samples, int layer_channels)
+{
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!d_samples) return bad(ctx, "null samples");
+    if (channels != 3 && channels != 4) return bad(ctx, "channels must be 3 or 4");
+    if (layer_channels != 3 && layer_channels != 4) return bad(ctx, "layer_channels must be 3 or 4");
+    if (spp < 1) return bad(ctx, "spp must be >= 1");
+    if (rows < 1 || row_begin < 0 || row_begin > acc->H - rows) return bad(ctx, "row range outside the frame");
+    BcdAccumLayerIn in;
+    if (acc->nlayers > 0) RCCHK(accum_layer_table(acc, d_layer_samples, in));
+    DEVICE_GUARD(ctx);
+    const int64_t npix = (int64_t)rows * acc->W;
+    HIPCHK(ctx, bcd_launch_accum_dense(d_samples, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, channels, acc->nbins, acc->gamma,
+                                       acc->maxval, (float *)acc->state.p, ctx->stream));
+    if (acc->nlayers > 0)
+        HIPCHK(ctx, bcd_launch_accum_dense_layers(in, acc->nlayers, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, layer_channels,
+                                                  (float *)acc->layers.p, ctx->stream));
+    acc->submitted += npix * spp;
+    return BCD_HIP_OK;
+}
+
+int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb)
+{
     bcd_hip_ctx *ctx = acc->ctx;
     if (n < 0) return bad(ctx, "negative sample count");
     if (n == 0) return BCD_HIP_OK;
     if (!d_pixel || !d_rgb) return bad(ctx, "null samples");
+    BcdAccumLayerIn in;
+    if (acc->nlayers > 0) RCCHK(accum_layer_table(acc, d_layer_rgb, in));
     DEVICE_GUARD(ctx);
     const int64_t chunk = acc->capacity > 0 ? acc->capacity : std::min<int64_t>(n, (int64_t)1 << 30);
     if (acc->capacity == 0) RCCHK(accum_scratch(acc, std::min(n, chunk)));
@@ -199,10 +321,15 @@ int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, cons
         HIPCHK(ctx, bcd_accum_sort(acc->sort.p, &bytes, k0, k1, v0, v1, m, end_bit, ctx->stream));
         HIPCHK(ctx, bcd_launch_accum_segments(k1, v1, m, acc->N, d_rgb + b * 3, d_weights ? d_weights + b : nullptr, acc->nbins, acc->gamma,
                                               acc->maxval, (float *)acc->state.p, ctx->stream));
+        if (acc->nlayers > 0) // (on the chunk's sorted keys and values, before the next chunk overwrites them)
+            HIPCHK(ctx, bcd_launch_accum_segments_layers(k1, v1, m, acc->N, accum_layer_offset(acc, in, b * 3), acc->nlayers,
+                                                         d_weights ? d_weights + b : nullptr, (float *)acc->layers.p, ctx->stream));
     }
     acc->submitted += n;
     return BCD_HIP_OK;
 }
+
+} // namespace
 
 int bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y, int table_size, const float *h_table)
 {
@@ -243,14 +370,17 @@ int bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y,
     return BCD_HIP_OK;
 }
 
-int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n)
+namespace {
+
+int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb)
 {
-    if (!acc) return BCD_HIP_EINVAL;
     bcd_hip_ctx *ctx = acc->ctx;
     if (!acc->has_filter) return bad(ctx, "the accumulator has no filter (bcd_hip_accum_set_filter)");
     if (n < 0) return bad(ctx, "negative sample count");
     if (n == 0) return BCD_HIP_OK;
     if (!d_xy || !d_rgb) return bad(ctx, "null samples");
+    BcdAccumLayerIn in;
+    if (acc->nlayers > 0) RCCHK(accum_layer_table(acc, d_layer_rgb, in));
     DEVICE_GUARD(ctx);
     const int *g = acc->filter_g;
     const int64_t NE = accum_extended_cells(acc, g[1], g[2]);
@@ -279,10 +409,16 @@ int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const floa
         const int cap = (int)std::min<double>(max_staged, 1.5 * avg + 8.0 * std::sqrt(avg) + 64.0);
         HIPCHK(ctx, bcd_launch_splat(acc->cells.p, v1, xy, rgb, w, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, cap, acc->nbins,
                                      acc->gamma, acc->maxval, (float *)acc->state.p, ctx->stream));
+        // the layers on the same cells and sorted values, each with its own colours into its own nine planes
+        for (int l = 0; l < acc->nlayers; ++l)
+            HIPCHK(ctx, bcd_launch_splat(acc->cells.p, v1, xy, in.src[l] + 3 * b, w, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, cap,
+                                         acc->nbins, acc->gamma, acc->maxval, (float *)acc->layers.p + (size_t)l * 9 * (size_t)acc->N, ctx->stream, true));
     }
     acc->submitted += n;
     return BCD_HIP_OK;
 }
+
+} // namespace
 
 // separable table of a standard filter (host only); 1-D factors at d = (i + 0.5) / TS * r in double, product rounded to float once
 int bcd_hip_filter_table(int kind, float radius_x, float radius_y, float param, int table_size, float *h_out)
@@ -317,6 +453,24 @@ int bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mea
     if (!d_nsamples || !d_mean || !d_cov || !d_hist) return bad(ctx, "null output");
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, bcd_launch_accum_snapshot((const float *)acc->state.p, acc->N, 3 * acc->nbins, d_nsamples, d_mean, d_cov, d_hist, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_layer_statistics(bcd_hip_accum *acc, float *const *d_mean, float *const *d_cov)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (acc->nlayers == 0) return bad(ctx, "the accumulator has no layers (bcd_hip_accum_create_layers)");
+    if (!d_mean || !d_cov) return bad(ctx, "null output list");
+    BcdAccumLayerOut out;
+    for (int l = 0; l < BCD_ACCUM_MAX_LAYERS; ++l) out.mean[l] = out.cov[l] = nullptr;
+    for (int l = 0; l < acc->nlayers; ++l) {
+        if (!d_mean[l] || !d_cov[l]) return bad(ctx, "null output");
+        out.mean[l] = d_mean[l];
+        out.cov[l] = d_cov[l];
+    }
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_accum_snapshot_layers((const float *)acc->state.p, (const float *)acc->layers.p, acc->N, out, acc->nlayers, ctx->stream));
     return BCD_HIP_OK;
 }
 
@@ -381,6 +535,36 @@ namespace {
 
 constexpr size_t STATE_CHUNK = (size_t)64 << 20; // bound of a staging / scratch chunk
 const char STATE_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'S', 'T' };
+const char LAYERS_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'L', 'Y' };
+
+// what is wrong with a serialised layer block of `bytes` bytes (its header copied to *hd), or nullptr
+const char *layers_problem(const void *h, int64_t bytes, bcd_hip_accum_layers_header *hd)
+{
+    if (!h) return "null layer block";
+    if (bytes < BCD_HIP_ACCUM_LAYERS_HEADER_BYTES) return "shorter than the 64-byte header";
+    memcpy(hd, h, sizeof(*hd));
+    if (memcmp(hd->magic, LAYERS_MAGIC, 8) != 0) return "bad magic (not BCDACCLY)";
+    if (hd->version != BCD_HIP_ACCUM_LAYERS_VERSION) return "unsupported version (not 1)";
+    if (hd->header_bytes != BCD_HIP_ACCUM_LAYERS_HEADER_BYTES) return "header_bytes is not 64";
+    if (hd->nb_layers < 1 || hd->nb_layers > BCD_HIP_ACCUM_MAX_LAYERS) return "nb_layers outside [1, 15]";
+    if (hd->width <= 0 || hd->height <= 0 || (int64_t)hd->width * hd->height >= ((int64_t)1 << 31)) return "width and height must be positive, below 2^31 pixels";
+    if (hd->nb_planes != (uint32_t)(9 * hd->nb_layers)) return "nb_planes is not 9 nb_layers";
+    if (bytes != BCD_HIP_ACCUM_LAYERS_HEADER_BYTES + 4 * (int64_t)hd->nb_planes * hd->width * hd->height) return "size is not 64 + 36 nb_layers W H bytes";
+    for (uint8_t r : hd->reserved)
+        if (r != 0) return "reserved bytes are not zero";
+    return nullptr;
+}
+
+// a well-formed layer block of this accumulator's frame size and layer count?
+int accum_check_layers(bcd_hip_accum *a, const void *h, int64_t bytes)
+{
+    if (a->nlayers == 0) return bad(a->ctx, "the accumulator has no layers (bcd_hip_accum_create_layers)");
+    bcd_hip_accum_layers_header hd;
+    if (const char *why = layers_problem(h, bytes, &hd)) return bad(a->ctx, (std::string("not an accumulator layer block (version 1): ") + why).c_str());
+    if (hd.width != a->W || hd.height != a->H) return bad(a->ctx, "layer block of another frame size");
+    if (hd.nb_layers != a->nlayers) return bad(a->ctx, "layer block with another number of layers");
+    return BCD_HIP_OK;
+}
 
 // what is wrong with a serialised state of `bytes` bytes (its header copied to *hd), or nullptr
 const char *state_problem(const void *h, int64_t bytes, bcd_hip_accum_state_header *hd)
@@ -416,6 +600,7 @@ int accum_check_pair(bcd_hip_accum *dst, bcd_hip_accum *src)
     if (!src) return bad(dst->ctx, "null source accumulator");
     if (dst == src) return bad(dst->ctx, "an accumulator cannot be merged into itself");
     if (dst->W != src->W || dst->H != src->H || dst->nbins != src->nbins) return bad(dst->ctx, "accumulators of different frame sizes or bin counts");
+    if (dst->nlayers != src->nlayers) return bad(dst->ctx, "accumulators with different numbers of layers");
     if (memcmp(&dst->gamma, &src->gamma, sizeof(float)) != 0 || memcmp(&dst->maxval, &src->maxval, sizeof(float)) != 0)
         return bad(dst->ctx, "accumulators with different gamma or max value");
     return BCD_HIP_OK;
@@ -440,15 +625,15 @@ int accum_chunks(bcd_hip_accum *a, bool host_side)
     return BCD_HIP_OK;
 }
 
-// the planes at h (accum_state_bytes) replace the state (merge = false) or are added to it, chunk by chunk through the pinned staging:
-// the host copy of chunk i + 1 runs while chunk i crosses PCIe.  Returns when h is no longer needed.
-int accum_from_host(bcd_hip_accum *a, const uint8_t *h, bool merge)
+// the S bytes of planes at h replace the device buffer `buf` (merge = false) or are added to it, chunk by chunk through the pinned
+// staging: the host copy of chunk i + 1 runs while chunk i crosses PCIe.  Returns when h is no longer needed.
+int accum_from_host(bcd_hip_accum *a, void *buf, size_t S, const uint8_t *h, bool merge)
 {
     bcd_hip_ctx *ctx = a->ctx;
     RCCHK(accum_chunks(a, true));
     if (merge) RCCHK(accum_chunks(a, false));
-    const size_t S = accum_state_bytes(a), c = a->chunk_bytes;
-    uint8_t *st = (uint8_t *)a->state.p;
+    const size_t c = a->chunk_bytes;
+    uint8_t *st = (uint8_t *)buf;
     for (size_t off = 0, i = 0; off < S; off += c, ++i) {
         const int b = (int)(i & 1);
         const size_t len = std::min(c, S - off);
@@ -462,6 +647,29 @@ int accum_from_host(bcd_hip_accum *a, const uint8_t *h, bool merge)
         HIPCHK(ctx, hipEventRecord(a->stage_ev[b], ctx->stream));
         a->stage_busy[b] = true;
         if (merge) HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)a->chunk[b], (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+    }
+    return BCD_HIP_OK;
+}
+
+// the S bytes of the device buffer `buf` to `out`, chunk by chunk; the stream has been synchronised, so no staging copy is in flight
+int accum_to_host(bcd_hip_accum *a, const void *buf, size_t S, uint8_t *out)
+{
+    bcd_hip_ctx *ctx = a->ctx;
+    a->stage_busy[0] = a->stage_busy[1] = false;
+    // chunk i + 2 crosses PCIe into one pinned buffer while the host copies chunk i + 1 out of the other
+    const size_t c = a->chunk_bytes, nch = (S + c - 1) / c;
+    const uint8_t *st = (const uint8_t *)buf;
+    auto enqueue = [&](size_t i) {
+        const int b = (int)(i & 1);
+        hipError_t e = hipMemcpyAsync(a->stage[b], st + i * c, std::min(c, S - i * c), hipMemcpyDeviceToHost, ctx->stream);
+        return e == hipSuccess ? hipEventRecord(a->stage_ev[b], ctx->stream) : e;
+    };
+    for (size_t i = 0; i < std::min<size_t>(2, nch); ++i) HIPCHK(ctx, enqueue(i));
+    for (size_t i = 0; i < nch; ++i) {
+        const int b = (int)(i & 1);
+        HIPCHK(ctx, hipEventSynchronize(a->stage_ev[b]));
+        memcpy(out + i * c, a->stage[b], std::min(c, S - i * c));
+        if (i + 2 < nch) HIPCHK(ctx, enqueue(i + 2));
     }
     return BCD_HIP_OK;
 }
@@ -495,7 +703,6 @@ int bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity)
     RCCHK(accum_chunks(acc, true));
     int64_t added = 0, dropped = 0;
     RCCHK(bcd_hip_accum_info(acc, &added, &dropped)); // (synchronises: no staging copy is in flight after it)
-    acc->stage_busy[0] = acc->stage_busy[1] = false;
     bcd_hip_accum_state_header hd;
     memset(&hd, 0, sizeof(hd));
     memcpy(hd.magic, STATE_MAGIC, 8);
@@ -508,22 +715,7 @@ int bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity)
     uint8_t *out = (uint8_t *)h_state;
     memcpy(out, &hd, sizeof(hd));
     out += BCD_HIP_ACCUM_STATE_HEADER_BYTES;
-    // chunk i + 2 crosses PCIe into one pinned buffer while the host copies chunk i + 1 out of the other
-    const size_t c = acc->chunk_bytes, nch = (S + c - 1) / c;
-    const uint8_t *st = (const uint8_t *)acc->state.p;
-    auto enqueue = [&](size_t i) {
-        const int b = (int)(i & 1);
-        hipError_t e = hipMemcpyAsync(acc->stage[b], st + i * c, std::min(c, S - i * c), hipMemcpyDeviceToHost, ctx->stream);
-        return e == hipSuccess ? hipEventRecord(acc->stage_ev[b], ctx->stream) : e;
-    };
-    for (size_t i = 0; i < std::min<size_t>(2, nch); ++i) HIPCHK(ctx, enqueue(i));
-    for (size_t i = 0; i < nch; ++i) {
-        const int b = (int)(i & 1);
-        HIPCHK(ctx, hipEventSynchronize(acc->stage_ev[b]));
-        memcpy(out + i * c, acc->stage[b], std::min(c, S - i * c));
-        if (i + 2 < nch) HIPCHK(ctx, enqueue(i + 2));
-    }
-    return BCD_HIP_OK;
+    return accum_to_host(acc, acc->state.p, S, out);
 }
 
 int bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
@@ -533,7 +725,7 @@ int bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes)
     bcd_hip_accum_state_header hd;
     RCCHK(accum_check_state(acc, h_state, bytes, &hd));
     DEVICE_GUARD(ctx);
-    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, false));
+    RCCHK(accum_from_host(acc, acc->state.p, accum_state_bytes(acc), (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, false));
     HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 0, ctx->stream));
     acc->submitted = hd.samples_added + hd.dropped;
     return BCD_HIP_OK;
@@ -546,7 +738,7 @@ int bcd_hip_accum_merge_state(bcd_hip_accum *acc, const void *h_state, int64_t b
     bcd_hip_accum_state_header hd;
     RCCHK(accum_check_state(acc, h_state, bytes, &hd));
     DEVICE_GUARD(ctx);
-    RCCHK(accum_from_host(acc, (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, true));
+    RCCHK(accum_from_host(acc, acc->state.p, accum_state_bytes(acc), (const uint8_t *)h_state + BCD_HIP_ACCUM_STATE_HEADER_BYTES, true));
     HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)acc->dropped.p, nullptr, (unsigned long long)hd.dropped, 1, ctx->stream));
     acc->submitted += hd.samples_added + hd.dropped;
     return BCD_HIP_OK;
@@ -566,22 +758,26 @@ int bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src)
     DEVICE_GUARD(ctx);
     // ... comes before the reads on dst's stream
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->ev_merge, 0));
-    const size_t S = accum_state_bytes(dst);
+    const size_t S = accum_state_bytes(dst), SL = accum_layer_bytes(dst);
     const char *env = getenv("BCD_HIP_ACCUM_MERGE_COPY"); // 1: the chunked copy of a cross-device merge on one device too (tests)
     if (sctx->device == ctx->device && !(env && env[0] == '1')) {
         HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->state.p, (const float *)src->state.p, (int64_t)(S / 4), ctx->num_cus, ctx->stream));
+        if (SL) HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->layers.p, (const float *)src->layers.p, (int64_t)(SL / 4), ctx->num_cus, ctx->stream));
         HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)src->dropped.p, 0, 1, ctx->stream));
     } else {
         // src's state in chunks into dst-side scratch (peer copies; no peer access needed), each chunk merged after its copy
         RCCHK(accum_chunks(dst, false));
         const size_t c = dst->chunk_bytes;
-        uint8_t *st = (uint8_t *)dst->state.p;
-        const uint8_t *ss = (const uint8_t *)src->state.p;
-        for (size_t off = 0, i = 0; off < S; off += c, ++i) {
-            void *buf = dst->chunk[i & 1];
-            const size_t len = std::min(c, S - off);
-            HIPCHK(ctx, hipMemcpyPeerAsync(buf, ctx->device, ss + off, sctx->device, len, ctx->stream));
-            HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)buf, (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+        for (int part = 0; part < 2; ++part) { // the shared state, then the layer planes
+            uint8_t *st = (uint8_t *)(part ? dst->layers.p : dst->state.p);
+            const uint8_t *ss = (const uint8_t *)(part ? src->layers.p : src->state.p);
+            const size_t bytes = part ? SL : S;
+            for (size_t off = 0, i = 0; off < bytes; off += c, ++i) {
+                void *buf = dst->chunk[i & 1];
+                const size_t len = std::min(c, bytes - off);
+                HIPCHK(ctx, hipMemcpyPeerAsync(buf, ctx->device, ss + off, sctx->device, len, ctx->stream));
+                HIPCHK(ctx, bcd_launch_accum_merge((float *)(st + off), (const float *)buf, (int64_t)(len / 4), ctx->num_cus, ctx->stream));
+            }
         }
         HIPCHK(ctx, hipMemcpyPeerAsync(dst->chunk[0], ctx->device, src->dropped.p, sctx->device, sizeof(unsigned long long), ctx->stream));
         HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)dst->chunk[0], 0, 1, ctx->stream));
@@ -595,6 +791,70 @@ int bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src)
     }
     dst->submitted += src->submitted;
     return BCD_HIP_OK;
+}
+
+// ---- the layer block: the layers' planes beside the v1 state ---------------------------------------------------
+static_assert(sizeof(bcd_hip_accum_layers_header) == BCD_HIP_ACCUM_LAYERS_HEADER_BYTES && offsetof(bcd_hip_accum_layers_header, version) == 8 &&
+                  offsetof(bcd_hip_accum_layers_header, header_bytes) == 12 && offsetof(bcd_hip_accum_layers_header, width) == 16 &&
+                  offsetof(bcd_hip_accum_layers_header, height) == 20 && offsetof(bcd_hip_accum_layers_header, nb_layers) == 24 &&
+                  offsetof(bcd_hip_accum_layers_header, nb_planes) == 28 && offsetof(bcd_hip_accum_layers_header, reserved) == 32,
+              "bcd_hip_accum_layers_header layout (version 1)");
+
+int bcd_hip_accum_layers_state_info(const void *h_layers, int64_t bytes, bcd_hip_accum_layers_header *out)
+{
+    bcd_hip_accum_layers_header hd;
+    if (layers_problem(h_layers, bytes, &hd)) return BCD_HIP_EINVAL;
+    if (out) *out = hd;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_layers_state_bytes(bcd_hip_accum *acc, int64_t *bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    if (!bytes) return bad(acc->ctx, "null size");
+    if (acc->nlayers == 0) return bad(acc->ctx, "the accumulator has no layers (bcd_hip_accum_create_layers)");
+    *bytes = BCD_HIP_ACCUM_LAYERS_HEADER_BYTES + (int64_t)accum_layer_bytes(acc);
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_export_layers(bcd_hip_accum *acc, void *h_layers, int64_t capacity)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (acc->nlayers == 0) return bad(ctx, "the accumulator has no layers (bcd_hip_accum_create_layers)");
+    const size_t S = accum_layer_bytes(acc);
+    if (!h_layers) return bad(ctx, "null layer block buffer");
+    if (capacity < BCD_HIP_ACCUM_LAYERS_HEADER_BYTES + (int64_t)S) return bad(ctx, "buffer smaller than bcd_hip_accum_layers_state_bytes");
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_chunks(acc, true));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (no staging copy is in flight after it)
+    bcd_hip_accum_layers_header hd;
+    memset(&hd, 0, sizeof(hd));
+    memcpy(hd.magic, LAYERS_MAGIC, 8);
+    hd.version = BCD_HIP_ACCUM_LAYERS_VERSION;
+    hd.header_bytes = BCD_HIP_ACCUM_LAYERS_HEADER_BYTES;
+    hd.width = acc->W; hd.height = acc->H; hd.nb_layers = acc->nlayers;
+    hd.nb_planes = (uint32_t)(9 * acc->nlayers);
+    memcpy(h_layers, &hd, sizeof(hd));
+    return accum_to_host(acc, acc->layers.p, S, (uint8_t *)h_layers + BCD_HIP_ACCUM_LAYERS_HEADER_BYTES);
+}
+
+int bcd_hip_accum_import_layers(bcd_hip_accum *acc, const void *h_layers, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    RCCHK(accum_check_layers(acc, h_layers, bytes));
+    DEVICE_GUARD(ctx);
+    return accum_from_host(acc, acc->layers.p, accum_layer_bytes(acc), (const uint8_t *)h_layers + BCD_HIP_ACCUM_LAYERS_HEADER_BYTES, false);
+}
+
+int bcd_hip_accum_merge_layers_state(bcd_hip_accum *acc, const void *h_layers, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    RCCHK(accum_check_layers(acc, h_layers, bytes));
+    DEVICE_GUARD(ctx);
+    return accum_from_host(acc, acc->layers.p, accum_layer_bytes(acc), (const uint8_t *)h_layers + BCD_HIP_ACCUM_LAYERS_HEADER_BYTES, true);
 }
 
 } // extern "C"

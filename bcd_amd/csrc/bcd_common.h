@@ -92,3 +92,15 @@ struct BcdLayerTable {
     const float *b[BCD_MAX_LAYERS];
     float *o[BCD_MAX_LAYERS];
 };
+
+// ---- colour layers of the device accumulator (bcd_hip_accum_*_layers) ----------------------------------
+// The layer is blockIdx.y; the per-layer device pointers of one launch travel by value.  The beauty is layer 0 of bcd_hip_denoise_layers,
+// so an accumulator carries at most BCD_MAX_LAYERS - 1 further ones.
+#define BCD_ACCUM_MAX_LAYERS (BCD_MAX_LAYERS - 1)
+struct BcdAccumLayerIn {
+    const float *src[BCD_ACCUM_MAX_LAYERS]; // the layer's colours, laid out like the beauty's buffer of the call
+};
+struct BcdAccumLayerOut {
+    float *mean[BCD_ACCUM_MAX_LAYERS];
+    float *cov[BCD_ACCUM_MAX_LAYERS];
+};

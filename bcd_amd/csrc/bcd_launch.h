@@ -112,6 +112,11 @@ hipError_t bcd_launch_bayes27_redo(const float *colors, const float *pixcov, con
 size_t bcd_accum_snapshot_lds(int D);
 hipError_t bcd_launch_accum_dense(const float *samples, const float *weights, int64_t p0, int64_t npix, int64_t N, int k, int channels, int nbins, float gamma,
                                   float maxval, float *st, hipStream_t s);
+hipError_t bcd_launch_accum_dense_layers(const BcdAccumLayerIn &in, int nb_layers, const float *weights, int64_t p0, int64_t npix, int64_t N, int k, int channels,
+                                         float *layers, hipStream_t s);
+hipError_t bcd_launch_accum_segments_layers(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t N, const BcdAccumLayerIn &in, int nb_layers,
+                                            const float *weights, float *layers, hipStream_t s);
+hipError_t bcd_launch_accum_snapshot_layers(const float *st, const float *layers, int64_t N, const BcdAccumLayerOut &out, int nb_layers, hipStream_t s);
 hipError_t bcd_launch_accum_keys(const int32_t *pix, int64_t n, int64_t N, uint32_t *keys, uint32_t *vals, unsigned long long *dropped, hipStream_t s);
 hipError_t bcd_accum_sort(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, int64_t n, int end_bit,
                           hipStream_t s);
@@ -125,7 +130,7 @@ hipError_t bcd_launch_splat_keys(const float *xy, int64_t n, int W, int H, const
                                  unsigned long long *dropped, hipStream_t s);
 hipError_t bcd_launch_splat_cells(const uint32_t *keys, int64_t n, int64_t NE, void *cells, hipStream_t s);
 hipError_t bcd_launch_splat(const void *cells, const uint32_t *vals, const float *xy, const float *rgb, const float *weights, int W, int H, const float *filter,
-                            const int *geom, const float *T, int cap, int nbins, float gamma, float maxval, float *st, hipStream_t s);
+                            const int *geom, const float *T, int cap, int nbins, float gamma, float maxval, float *st, hipStream_t s, bool layer = false);
 size_t bcd_plan_red_bytes();
 hipError_t bcd_plan_scan_bytes(int64_t N, size_t *bytes);
 hipError_t bcd_launch_accum_plan(const float *st, int64_t N, float eps, float min_samples, float tau, int K, int64_t B, uint64_t offset, float *err, int32_t *counts,

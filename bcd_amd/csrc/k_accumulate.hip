@@ -12,11 +12,14 @@
 // (pixel, sample index) with a stable radix sort and walks each pixel's run in order.  A merge of two states is one fp32 add per element
 // (the sums are plain running sums), so it is as deterministic as the rest.
 #include <algorithm>
+#include <type_traits>
 #include <cstring> // (before rocprim: texture_cache_iterator.hpp uses memset)
 #include <rocprim/rocprim.hpp>
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "bcd_common.h"
 
 namespace {
 
@@ -76,6 +79,31 @@ __device__ inline void acc_statistics(const AccSums &s, float mean[3], float cov
     for (int i = 0; i < 6; ++i) cov[i] = cv[i] * bias;
 }
 
+// Colour layers (bcd_hip_accum_*_layers): a layer keeps the nine colour sums only, ACC_LAYER_PLANES planes of N floats
+// in the order of ACC_M / ACC_C, layer after layer in a buffer of its own; the weight sum and the squared-weight sum are the beauty's.
+// One thread owns one (pixel, layer) and applies its contributions in stream order: the nine m / c lines of AccSums::add with the same
+// weight, so a layer has the bits of a separate accumulator fed its colours.
+#define ACC_LAYER_PLANES 9
+struct LayerSums {
+    float m[3], c[6];
+    __device__ void load(const float *__restrict__ ly, int64_t N, int64_t p)
+    {
+        for (int i = 0; i < 3; ++i) m[i] = ly[i * N + p];
+        for (int i = 0; i < 6; ++i) c[i] = ly[(3 + i) * N + p];
+    }
+    __device__ void store(float *__restrict__ ly, int64_t N, int64_t p) const
+    {
+        for (int i = 0; i < 3; ++i) ly[i * N + p] = m[i];
+        for (int i = 0; i < 6; ++i) ly[(3 + i) * N + p] = c[i];
+    }
+    __device__ void add(float R, float G, float B, float w)
+    {
+        m[0] += w * R; m[1] += w * G; m[2] += w * B;
+        c[0] += w * R * R; c[1] += w * G * G; c[2] += w * B * B;
+        c[3] += w * G * B; c[4] += w * R * B; c[5] += w * R * G;
+    }
+};
+
 // (a) dense add: pixels [p0, p0 + npix) of the frame, k samples each (contiguous, `channels` floats per sample, the 4th ignored).
 // STAGED = false: the 6k touched bins are read-modified-written in HBM directly (a progressive pass of k = 1 moves 6 of the D bins);
 // STAGED = true: the pixel's D bins are loaded into LDS ([bin][thread], bank-conflict free), accumulated there and written back once.
@@ -117,6 +145,23 @@ __global__ __launch_bounds__(64) void k_accum_dense(const float *__restrict__ sa
     s.store(st, N, p);
     if (STAGED)
         for (int b = 0; b < D; ++b) hp[b * N] = lds_h[b * 64 + t];
+}
+
+// (a') dense add of the layers: blockIdx.y = layer, one thread per (pixel, layer); a 1-sample pass moves the sample, its weight and the
+// nine planes twice
+__global__ __launch_bounds__(256) void k_accum_dense_layers(BcdAccumLayerIn in, const float *__restrict__ weights, int64_t p0, int64_t npix,
+                                                            int64_t N, int k, int channels, float *__restrict__ layers)
+{
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= npix) return;
+    const int64_t p = p0 + q;
+    float *ly = layers + (int64_t)blockIdx.y * ACC_LAYER_PLANES * N;
+    LayerSums s;
+    s.load(ly, N, p);
+    const float *sp = in.src[blockIdx.y] + q * k * channels;
+    const float *wp = weights ? weights + q * k : nullptr;
+    for (int i = 0; i < k; ++i) s.add(sp[i * channels], sp[i * channels + 1], sp[i * channels + 2], wp ? wp[i] : 1.f);
+    s.store(ly, N, p);
 }
 
 // (b) scattered add, step 1: key = pixel index (out-of-range indices -> N, sorted past every pixel and skipped), value = position in the
@@ -172,6 +217,27 @@ __global__ __launch_bounds__(256) void k_accum_segments(const uint32_t *__restri
         acc_add_sample(s, hp, N, rgb[e * 3], rgb[e * 3 + 1], rgb[e * 3 + 2], weights ? weights[e] : 1.f, nbins, gamma, maxval);
     }
     s.store(st, N, p);
+}
+
+// (b) step 3 for the layers, on the same sorted keys and values: blockIdx.y = layer
+__global__ __launch_bounds__(256) void k_accum_segments_layers(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, int64_t n,
+                                                               int64_t N, BcdAccumLayerIn in, const float *__restrict__ weights,
+                                                               float *__restrict__ layers)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t key = keys[i];
+    if ((int64_t)key >= N || (i > 0 && keys[i - 1] == key)) return;
+    const int64_t p = key;
+    float *ly = layers + (int64_t)blockIdx.y * ACC_LAYER_PLANES * N;
+    const float *rgb = in.src[blockIdx.y];
+    LayerSums s;
+    s.load(ly, N, p);
+    for (int64_t j = i; j < n && keys[j] == key; ++j) {
+        const int64_t e = vals[j];
+        s.add(rgb[e * 3], rgb[e * 3 + 1], rgb[e * 3 + 2], weights ? weights[e] : 1.f);
+    }
+    s.store(ly, N, p);
 }
 
 // (b') splatted add (bcd_hip_accum_add_splatted; the definition is in include/bcd_hip.h, the design in DESIGN.md section 10): samples at
@@ -302,8 +368,9 @@ __device__ inline void splat_row_next(const SplatRuns<STAGED> &S, const SplatFil
 }
 
 // one destination pixel: merges the 2 ny + 1 ring rows' candidates by batch position and adds each contribution as k_accum_segments does.
-// rc0: the ring cell at the top left of the pixel's neighbourhood; RW: cells per ring row
-template <bool STAGED>
+// rc0: the ring cell at the top left of the pixel's neighbourhood; RW: cells per ring row.  LAYER: st is a layer's nine planes and the
+// colours are the layer's -- the sums alone, no bins
+template <bool STAGED, bool LAYER>
 __device__ inline void splat_pixel(const SplatRuns<STAGED> &S, const SplatFilter &F, const float *T, int rc0, int RW, int col, int line, int64_t p,
                                    int64_t N, int nbins, float gamma, float maxval, float *__restrict__ st)
 {
@@ -319,8 +386,8 @@ __device__ inline void splat_pixel(const SplatRuns<STAGED> &S, const SplatFilter
         for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
             if (q == r) { cpos[q] = np; cidx[q] = ni; cf[q] = nf; }
     }
-    float *hp = st + (int64_t)ACC_H * N + p;
-    AccSums s;
+    float *hp = LAYER ? st : st + (int64_t)ACC_H * N + p;
+    typename std::conditional<LAYER, LayerSums, AccSums>::type s;
     bool loaded = false;
     for (;;) {
         uint32_t best = SPLAT_NONE, idx = 0;
@@ -333,7 +400,8 @@ __device__ inline void splat_pixel(const SplatRuns<STAGED> &S, const SplatFilter
         if (!loaded) { s.load(st, N, p); loaded = true; }
         float R, G, B, w;
         S.colour(idx, R, G, B, w);
-        acc_add_sample(s, hp, N, R, G, B, w * f, nbins, gamma, maxval);
+        if constexpr (LAYER) s.add(R, G, B, w * f);
+        else acc_add_sample(s, hp, N, R, G, B, w * f, nbins, gamma, maxval);
         uint32_t np, ni;
         float nf;
         splat_row_next(S, F, T, rc0 + br * RW, col, line, best + 1u, np, ni, nf);
@@ -344,7 +412,9 @@ __device__ inline void splat_pixel(const SplatRuns<STAGED> &S, const SplatFilter
     if (loaded) s.store(st, N, p); // (a pixel without contributions does not touch its planes)
 }
 
-// dynamic LDS: the table (ts * ts), g0[SPLAT_RING_MAX], b0[SPLAT_RING_MAX + 4], then 7 staging arrays of `cap` entries
+// dynamic LDS: the table (ts * ts), g0[SPLAT_RING_MAX], b0[SPLAT_RING_MAX + 4], then 7 staging arrays of `cap` entries.
+// LAYER: one colour layer of the chunk the beauty's launch has just served (rgb: the layer's colours, st: its nine planes)
+template <bool LAYER>
 __global__ __launch_bounds__(256) void k_accum_splat(const uint2 *__restrict__ cells, const uint32_t *__restrict__ vals, const float *__restrict__ xy,
                                                      const float *__restrict__ rgb, const float *__restrict__ weights, int W, int H, int tiles_x,
                                                      SplatFilter F, const float *__restrict__ T, int cap, int nbins, float gamma, float maxval,
@@ -413,10 +483,10 @@ __global__ __launch_bounds__(256) void k_accum_splat(const uint2 *__restrict__ c
     const int rc0 = ly * RW + lx;
     if (staged) {
         const SplatRuns<true> S = { s_g0, s_b0, s_pos, s_x, s_y, s_r, s_g, s_b, s_w, vals, xy, rgb, weights };
-        splat_pixel<true>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
+        splat_pixel<true, LAYER>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
     } else {
         const SplatRuns<false> S = { s_g0, s_b0, s_pos, s_x, s_y, s_r, s_g, s_b, s_w, vals, xy, rgb, weights };
-        splat_pixel<false>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
+        splat_pixel<false, LAYER>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
     }
 }
 
@@ -446,6 +516,26 @@ __global__ __launch_bounds__(64) void k_accum_snapshot(const float *__restrict__
         const int q = e / D;
         oh[e] = lds_t[q * (D + 1) + (e - q * D)];
     }
+}
+
+// (c') snapshot of the layers: acc_statistics on a layer's nine sums with the beauty's weight sum and squared-weight sum; blockIdx.y =
+// layer.  Reads 8 + 36 B and writes 36 B per pixel and layer; state and layers are read only.
+__global__ __launch_bounds__(256) void k_accum_snapshot_layers(const float *__restrict__ st, const float *__restrict__ layers, int64_t N,
+                                                               BcdAccumLayerOut out)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    LayerSums l;
+    l.load(layers + (int64_t)blockIdx.y * ACC_LAYER_PLANES * N, N, p);
+    AccSums s;
+    s.wsum = st[ACC_W * N + p]; s.w2sum = st[ACC_W2 * N + p];
+    for (int i = 0; i < 3; ++i) s.m[i] = l.m[i];
+    for (int i = 0; i < 6; ++i) s.c[i] = l.c[i];
+    float mean[3], cov[6];
+    acc_statistics(s, mean, cov);
+    float *omean = out.mean[blockIdx.y], *ocov = out.cov[blockIdx.y];
+    for (int i = 0; i < 3; ++i) omean[p * 3 + i] = mean[i];
+    for (int i = 0; i < 6; ++i) ocov[p * 6 + i] = cov[i];
 }
 
 // (d) adaptive plan (bcd_hip_accum_plan).  Reductions of the error pass: the largest finite error of the active
@@ -633,6 +723,15 @@ hipError_t bcd_launch_accum_dense(const float *samples, const float *weights, in
     return hipGetLastError();
 }
 
+// layers: nb_layers x 9 planes of N floats; in.src[l]: the layer's samples of the pass, `channels` floats each
+hipError_t bcd_launch_accum_dense_layers(const BcdAccumLayerIn &in, int nb_layers, const float *weights, int64_t p0, int64_t npix, int64_t N, int k,
+                                         int channels, float *layers, hipStream_t s)
+{
+    if (npix <= 0 || nb_layers <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_accum_dense_layers, dim3(nblk(npix, 256), (unsigned)nb_layers), dim3(256), 0, s, in, weights, p0, npix, N, k, channels, layers);
+    return hipGetLastError();
+}
+
 hipError_t bcd_launch_accum_keys(const int32_t *pix, int64_t n, int64_t N, uint32_t *keys, uint32_t *vals, unsigned long long *dropped, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
@@ -655,6 +754,14 @@ hipError_t bcd_launch_accum_segments(const uint32_t *keys, const uint32_t *vals,
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_accum_segments, dim3(nblk(n, 256)), dim3(256), 0, s, keys, vals, n, N, rgb, weights, nbins, gamma, maxval, st);
+    return hipGetLastError();
+}
+
+hipError_t bcd_launch_accum_segments_layers(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t N, const BcdAccumLayerIn &in, int nb_layers,
+                                            const float *weights, float *layers, hipStream_t s)
+{
+    if (n <= 0 || nb_layers <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_accum_segments_layers, dim3(nblk(n, 256), (unsigned)nb_layers), dim3(256), 0, s, keys, vals, n, N, in, weights, layers);
     return hipGetLastError();
 }
 
@@ -693,24 +800,36 @@ hipError_t bcd_launch_splat_cells(const uint32_t *keys, int64_t n, int64_t NE, v
     return hipGetLastError();
 }
 
-// cap: samples the staging arrays hold (<= bcd_splat_max_staged); a tile whose ring holds more reads the sorted batch from global memory
+// cap: samples the staging arrays hold (<= bcd_splat_max_staged); a tile whose ring holds more reads the sorted batch from global memory.
+// layer: st is one layer's nine planes and rgb its colours (nbins, gamma and maxval are not used)
 hipError_t bcd_launch_splat(const void *cells, const uint32_t *vals, const float *xy, const float *rgb, const float *weights, int W, int H,
                             const float *filter, const int *geom, const float *T, int cap, int nbins, float gamma, float maxval, float *st,
-                            hipStream_t s)
+                            hipStream_t s, bool layer)
 {
     const SplatFilter F = splat_filter(filter, geom);
     const int tiles_x = (W + SPLAT_TX - 1) / SPLAT_TX;
     const int64_t tiles = (int64_t)tiles_x * ((H + SPLAT_TY - 1) / SPLAT_TY);
     cap = std::max(0, std::min(cap, bcd_splat_max_staged(F.ts)));
     const size_t lds = splat_fixed_lds(F.ts) + (size_t)cap * SPLAT_SAMPLE_BYTES;
-    hipLaunchKernelGGL(k_accum_splat, dim3((unsigned)tiles), dim3(256), lds, s, (const uint2 *)cells, vals, xy, rgb, weights, W, H, tiles_x, F, T,
-                       cap, nbins, gamma, maxval, st);
+    if (layer)
+        hipLaunchKernelGGL(k_accum_splat<true>, dim3((unsigned)tiles), dim3(256), lds, s, (const uint2 *)cells, vals, xy, rgb, weights, W, H, tiles_x,
+                           F, T, cap, nbins, gamma, maxval, st);
+    else
+        hipLaunchKernelGGL(k_accum_splat<false>, dim3((unsigned)tiles), dim3(256), lds, s, (const uint2 *)cells, vals, xy, rgb, weights, W, H, tiles_x,
+                           F, T, cap, nbins, gamma, maxval, st);
     return hipGetLastError();
 }
 
 hipError_t bcd_launch_accum_snapshot(const float *st, int64_t N, int D, float *ons, float *omean, float *ocov, float *ohist, hipStream_t s)
 {
     hipLaunchKernelGGL(k_accum_snapshot, dim3(nblk(N, 64)), dim3(64), bcd_accum_snapshot_lds(D), s, st, N, D, ons, omean, ocov, ohist);
+    return hipGetLastError();
+}
+
+hipError_t bcd_launch_accum_snapshot_layers(const float *st, const float *layers, int64_t N, const BcdAccumLayerOut &out, int nb_layers, hipStream_t s)
+{
+    if (nb_layers <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_accum_snapshot_layers, dim3(nblk(N, 256), (unsigned)nb_layers), dim3(256), 0, s, st, layers, N, out);
     return hipGetLastError();
 }
 

@@ -113,6 +113,52 @@ def accum_state_planes(buf):
     return info, planes
 
 
+class LayersHeader(C.Structure):
+    """bcd_hip_accum_layers_header: the 64-byte header of a serialised layer block (version 1, include/bcd_hip.h)"""
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("nb_layers", C.c_int32), ("nb_planes", C.c_uint32), ("reserved", C.c_uint8 * 32)]
+
+
+ACCUM_MAX_LAYERS = MAX_LAYERS - 1  # BCD_HIP_ACCUM_MAX_LAYERS
+_PP = C.POINTER(_VP)
+
+
+def _layers_api():
+    L = lib()
+    L.bcd_hip_accum_create_layers.argtypes = [_VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int64, C.c_int, C.POINTER(_VP)]
+    L.bcd_hip_accum_nb_layers.argtypes = [_VP, C.POINTER(C.c_int)]
+    L.bcd_hip_accum_add_dense_layers.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _PP, C.c_int]
+    L.bcd_hip_accum_add_scattered_layers.argtypes = [_VP, _VP, _VP, _VP, C.c_int64, _PP]
+    L.bcd_hip_accum_add_splatted_layers.argtypes = [_VP, _VP, _VP, _VP, C.c_int64, _PP]
+    L.bcd_hip_accum_layer_statistics.argtypes = [_VP, _PP, _PP]
+    L.bcd_hip_accum_layers_state_info.argtypes = [_VP, C.c_int64, C.POINTER(LayersHeader)]
+    L.bcd_hip_accum_layers_state_bytes.argtypes = [_VP, C.POINTER(C.c_int64)]
+    L.bcd_hip_accum_export_layers.argtypes = [_VP, _VP, C.c_int64]
+    L.bcd_hip_accum_import_layers.argtypes = [_VP, _VP, C.c_int64]
+    L.bcd_hip_accum_merge_layers_state.argtypes = [_VP, _VP, C.c_int64]
+    return L
+
+
+def accum_layers_state_info(buf):
+    """the header of a serialised layer block as a dict (bcd_hip_accum_layers_state_info: host only, no GPU needed); ValueError if the
+    buffer is not a well-formed block of its exact size"""
+    a = _state_buffer(buf)
+    h = LayersHeader()
+    rc = _layers_api().bcd_hip_accum_layers_state_info(a.ctypes.data_as(_VP) if a.size else None, a.size, C.byref(h))
+    if rc != 0:
+        raise ValueError("not a serialised accumulator layer block (version 1) of %d bytes: rc=%d" % (a.size, rc))
+    return {"magic": bytes(h.magic), "version": h.version, "header_bytes": h.header_bytes, "width": h.width, "height": h.height,
+            "nb_layers": h.nb_layers, "nb_planes": h.nb_planes}
+
+
+def accum_layers_state_planes(buf):
+    """(header dict, float32 (nb_layers, 9, H, W) view of the planes) of a serialised layer block: per layer 3 colour sums, then the 6
+    second moments (xx, yy, zz, yz, xz, xy)"""
+    a = _state_buffer(buf)
+    info = accum_layers_state_info(a)
+    return info, a[STATE_HEADER_BYTES:].view("<f4").reshape(info["nb_layers"], 9, info["height"], info["width"])
+
+
 def default_plan_params(**kw):
     p = PlanParams()
     lib().bcd_hip_default_plan_params(C.byref(p))
@@ -177,6 +223,9 @@ SYMBOLS = [
     "bcd_hip_accum_add_scattered", "bcd_hip_accum_statistics", "bcd_hip_accum_info", "bcd_hip_default_plan_params", "bcd_hip_accum_plan", "bcd_hip_zero_bad_values",
     "bcd_hip_accum_set_filter", "bcd_hip_accum_add_splatted", "bcd_hip_filter_table",
     "bcd_hip_accum_state_info", "bcd_hip_accum_state_bytes", "bcd_hip_accum_export", "bcd_hip_accum_import", "bcd_hip_accum_merge_state", "bcd_hip_accum_merge",
+    "bcd_hip_accum_create_layers", "bcd_hip_accum_nb_layers", "bcd_hip_accum_add_dense_layers", "bcd_hip_accum_add_scattered_layers", "bcd_hip_accum_add_splatted_layers",
+    "bcd_hip_accum_layer_statistics", "bcd_hip_accum_layers_state_info", "bcd_hip_accum_layers_state_bytes", "bcd_hip_accum_export_layers", "bcd_hip_accum_import_layers",
+    "bcd_hip_accum_merge_layers_state",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch", "bcd_hip_eig27_batch_rule",
     "bcd_hip_selftest_sparse_upload", "bcd_hip_selftest_host_stream", "bcd_hip_approx_planes",
 ]
@@ -589,10 +638,10 @@ class Context:
                                                    C.c_float(gamma), C.c_float(maxval), _dp(ns), _dp(mean), _dp(cov), _dp(hist)))
         return ns, mean, cov, hist
 
-    def accumulator(self, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0):
+    def accumulator(self, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0, layers=0):
         """persistent device SamplesAccumulator of a W x H frame (bcd_hip_accum_*); capacity > 0: scattered batches of up to that many
-        samples never allocate"""
-        return Accumulator(self, W, H, nbins, gamma, maxval, capacity)
+        samples never allocate; layers > 0: that many extra colour layers accumulated beside the beauty (bcd_hip_accum_create_layers)"""
+        return Accumulator(self, W, H, nbins, gamma, maxval, capacity, layers)
 
     def zero_bad_values(self, img):
         self._chk(lib().bcd_hip_zero_bad_values(self.h, _dp(img), C.c_int64(img.numel())))
@@ -671,35 +720,71 @@ class Accumulator:
     """bcd_hip_accum: running sums in HBM, fed in batches (dense rows or scattered samples, each pixel in stream order), snapshots
     that go straight into Context.denoise"""
 
-    def __init__(self, ctx, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0):
+    def __init__(self, ctx, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0, layers=0):
         L = lib()
         L.bcd_hip_accum_create.argtypes = [_VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int64, C.POINTER(_VP)]
         L.bcd_hip_accum_destroy.argtypes = [_VP]
         L.bcd_hip_accum_destroy.restype = None
         L.bcd_hip_accum_add_dense.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int]
         L.bcd_hip_accum_add_scattered.argtypes = [_VP, _VP, _VP, _VP, C.c_int64]
-        self.ctx, self.W, self.H, self.nbins = ctx, W, H, nbins
+        self.ctx, self.W, self.H, self.nbins, self.layers = ctx, W, H, nbins, int(layers)
         h = _VP()
-        ctx._chk(L.bcd_hip_accum_create(ctx.h, W, H, nbins, gamma, maxval, capacity, C.byref(h)))
+        if layers:                                                   # (0: the plain accumulator; anything else is checked by the library)
+            ctx._chk(_layers_api().bcd_hip_accum_create_layers(ctx.h, W, H, nbins, gamma, maxval, capacity, int(layers), C.byref(h)))
+        else:
+            ctx._chk(L.bcd_hip_accum_create(ctx.h, W, H, nbins, gamma, maxval, capacity, C.byref(h)))
         self.h = h
         ctx._accumulators.add(self)
 
     def _chk(self, rc):
         self.ctx._chk(rc)
 
-    def add_dense(self, samples, weights=None, row0=0):
-        """samples: (rows, W, k, 3 | 4) device tensor, the k samples of a pixel in accumulation order; weights: (rows, W, k) or None"""
+    @staticmethod
+    def _layer_list(layers, shape):
+        """the host array of device pointers of a _layers add (None for a tensor that is None: the library refuses it)"""
+        layers = list(layers)
+        arr = (_VP * max(1, len(layers)))()
+        for k, t in enumerate(layers):
+            if t is not None:
+                assert shape(t), "layer %d: not laid out like the beauty's buffer" % k
+                arr[k] = _dp(t).value
+        return arr
+
+    def nb_layers(self):
+        n = C.c_int(0)
+        self._chk(_layers_api().bcd_hip_accum_nb_layers(self.h, C.byref(n)))
+        return n.value
+
+    def add_dense(self, samples, weights=None, row0=0, layers=None):
+        """samples: (rows, W, k, 3 | 4) device tensor, the k samples of a pixel in accumulation order; weights: (rows, W, k) or None;
+        layers: on an accumulator with layers, one (rows, W, k, 3 | 4) tensor per layer (all of one channel count)"""
         rows, W, k, ch = samples.shape
         assert W == self.W, "samples must cover whole rows of the frame"
         assert weights is None or tuple(weights.shape) == (rows, W, k)
-        self._chk(lib().bcd_hip_accum_add_dense(self.h, _dp(samples), _dp(weights) if weights is not None else None, int(row0), rows, k, ch))
+        wp = _dp(weights) if weights is not None else None
+        if layers is None:
+            self._chk(lib().bcd_hip_accum_add_dense(self.h, _dp(samples), wp, int(row0), rows, k, ch))
+            return
+        layers = list(layers)
+        assert len(layers) == self.layers, "one tensor per layer expected"
+        lch = next((t.shape[3] for t in layers if t is not None), 3)
+        arr = self._layer_list(layers, lambda t: tuple(t.shape) == (rows, W, k, lch))
+        self._chk(_layers_api().bcd_hip_accum_add_dense_layers(self.h, _dp(samples), wp, int(row0), rows, k, ch, arr, lch))
 
-    def add_samples(self, pixel, rgb, weights=None):
-        """pixel: (n,) int32 line * W + col (others are dropped and counted); rgb: (n, 3); weights: (n,) or None"""
+    def add_samples(self, pixel, rgb, weights=None, layers=None):
+        """pixel: (n,) int32 line * W + col (others are dropped and counted); rgb: (n, 3); weights: (n,) or None; layers: on an
+        accumulator with layers, one (n, 3) tensor per layer"""
         n = pixel.shape[0]
         assert pixel.dtype == self.ctx.torch.int32 and tuple(rgb.shape) == (n, 3)
         assert weights is None or tuple(weights.shape) == (n,)
-        self._chk(lib().bcd_hip_accum_add_scattered(self.h, _dp(pixel), _dp(rgb), _dp(weights) if weights is not None else None, n))
+        wp = _dp(weights) if weights is not None else None
+        if layers is None:
+            self._chk(lib().bcd_hip_accum_add_scattered(self.h, _dp(pixel), _dp(rgb), wp, n))
+            return
+        layers = list(layers)
+        assert len(layers) == self.layers, "one tensor per layer expected"
+        arr = self._layer_list(layers, lambda t: tuple(t.shape) == (n, 3))
+        self._chk(_layers_api().bcd_hip_accum_add_scattered_layers(self.h, _dp(pixel), _dp(rgb), wp, n, arr))
 
     def set_filter(self, kind_or_table, radius=None, param=2.0, table_size=16):
         """the pixel reconstruction filter of add_splatted (bcd_hip_accum_set_filter; definition in include/bcd_hip.h).  kind_or_table: a
@@ -720,14 +805,38 @@ class Accumulator:
                 raise ValueError("a filter table must be a square 2-D array")
         self._chk(L.bcd_hip_accum_set_filter(self.h, rx, ry, table.shape[0], table.ctypes.data_as(_VP)))
 
-    def add_splatted(self, xy, rgb, weights=None):
+    def add_splatted(self, xy, rgb, weights=None, layers=None):
         """xy: (n, 2) float32 continuous positions (x, y), pixel (col, line) covering [col, col + 1) x [line, line + 1); rgb: (n, 3);
-        weights: (n,) or None.  Every sample goes to the pixels of its filter footprint, each pixel in stream order"""
+        weights: (n,) or None.  Every sample goes to the pixels of its filter footprint, each pixel in stream order.  layers: on an
+        accumulator with layers, one (n, 3) tensor per layer"""
         n = xy.shape[0]
         assert tuple(xy.shape) == (n, 2) and tuple(rgb.shape) == (n, 3) and xy.dtype == self.ctx.torch.float32
         assert weights is None or tuple(weights.shape) == (n,)
-        self._chk(_splat_api().bcd_hip_accum_add_splatted(self.h, _dp(xy) if n else None, _dp(rgb) if n else None,
-                                                          _dp(weights) if weights is not None and n else None, n))
+        args = (self.h, _dp(xy) if n else None, _dp(rgb) if n else None, _dp(weights) if weights is not None and n else None, n)
+        if layers is None:
+            self._chk(_splat_api().bcd_hip_accum_add_splatted(*args))
+            return
+        layers = list(layers)
+        assert len(layers) == self.layers, "one tensor per layer expected"
+        arr = self._layer_list(layers, lambda t: tuple(t.shape) == (n, 3)) if n else (_VP * max(1, len(layers)))()
+        self._chk(_layers_api().bcd_hip_accum_add_splatted_layers(*args, arr))
+
+    def layer_statistics(self, out=None):
+        """-> [(mean (H, W, 3), cov (H, W, 6)) per layer], fresh tensors or the pairs of `out`, from the layers' sums and the shared weight
+        sums (bcd_hip_accum_layer_statistics); state unchanged.  Appended to [(mean, cov)] of statistics() it is the layer list of
+        Context.denoise_layers"""
+        torch = self.ctx.torch
+        if out is None:
+            mk = lambda d: torch.empty((self.H, self.W, d), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+            out = [(mk(3), mk(6)) for _ in range(self.layers)]
+        out = [tuple(o) for o in out]
+        assert len(out) == self.layers or self.layers == 0, "one (mean, cov) pair per layer expected"
+        means, covs = (_VP * max(1, len(out)))(), (_VP * max(1, len(out)))()
+        for k, (m, c) in enumerate(out):
+            assert tuple(m.shape) == (self.H, self.W, 3) and tuple(c.shape) == (self.H, self.W, 6)
+            means[k], covs[k] = _dp(m).value, _dp(c).value
+        self._chk(_layers_api().bcd_hip_accum_layer_statistics(self.h, means, covs))
+        return out
 
     def statistics(self, out=None):
         """-> (ns (H, W, 1), mean (H, W, 3), cov (H, W, 6), hist (H, W, 3 nbins)), fresh tensors or the four of `out`; state unchanged"""
@@ -790,8 +899,33 @@ class Accumulator:
         self._chk(_state_api().bcd_hip_accum_merge_state(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
 
     def merge(self, other):
-        """adds other's state into this one, in stream order on both contexts (other may live on another context or device)"""
+        """adds other's state into this one, in stream order on both contexts (other may live on another context or device); the layer
+        planes too (both sides must have the same number of layers)"""
         self._chk(_state_api().bcd_hip_accum_merge(self.h, other.h if other is not None else None))
+
+    # ---- the layer block (bcd_hip_accum_export_layers / _import_layers / _merge_layers_state): a checkpoint of an accumulator with layers
+    # is export_state() plus export_layers_state()
+    def layers_state_bytes(self):
+        n = C.c_int64(0)
+        self._chk(_layers_api().bcd_hip_accum_layers_state_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def export_layers_state(self):
+        """the serialised layer block (header + the layers' planes) as a numpy uint8 array; synchronises, the state is unchanged"""
+        import numpy as np
+        out = np.empty(self.layers_state_bytes(), np.uint8)
+        self._chk(_layers_api().bcd_hip_accum_export_layers(self.h, out.ctypes.data_as(_VP), out.size))
+        return out
+
+    def import_layers_state(self, buf):
+        """replaces the layers' planes with a serialised block of the same frame size and layer count"""
+        a = _state_buffer(buf)
+        self._chk(_layers_api().bcd_hip_accum_import_layers(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
+
+    def merge_layers_state(self, buf):
+        """adds a serialised layer block into the layers' planes (one fp32 add per element)"""
+        a = _state_buffer(buf)
+        self._chk(_layers_api().bcd_hip_accum_merge_layers_state(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
 
     def info(self):
         """(samples accumulated, samples dropped) since create / the last reset; synchronises"""

@@ -22,8 +22,20 @@ namespace bcd
 {
 
 	DeviceSamplesAccumulator::DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_device) :
-			m_width(i_width), m_height(i_height), m_nbOfBins(i_rHistogramParameters.m_nbOfBins)
+			DeviceSamplesAccumulator(i_width, i_height, i_rHistogramParameters, 0, i_device)
 	{
+	}
+
+	DeviceSamplesAccumulator::DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_nbOfLayers,
+			int i_device) :
+			m_width(i_width), m_height(i_height), m_nbOfBins(i_rHistogramParameters.m_nbOfBins), m_nbOfLayers(i_nbOfLayers)
+	{
+		if(i_nbOfLayers < 0 || i_nbOfLayers > BCD_HIP_ACCUM_MAX_LAYERS)
+		{
+			m_error = "the number of layers must be in [0, 15]";
+			m_nbOfLayers = 0;
+			return;
+		}
 		int prev = -1;
 		(void)hipGetDevice(&prev);
 		hipStream_t stream = nullptr;
@@ -37,10 +49,14 @@ namespace bcd
 		hipEvent_t ev = nullptr;
 		const size_t batchBytes = size_t(s_batchCapacity) * (sizeof(int32_t) + 4 * sizeof(float));
 		const size_t statsBytes = size_t(i_width) * size_t(i_height) * (10 + 3 * size_t(m_nbOfBins)) * sizeof(float);
+		const size_t layerBatchBytes = size_t(m_nbOfLayers) * size_t(s_batchCapacity) * 3 * sizeof(float);
+		const size_t layerStatsBytes = size_t(m_nbOfLayers) * size_t(i_width) * size_t(i_height) * 9 * sizeof(float);
 		if(hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess
 				|| hipHostMalloc((void**)&m_pHostPixel, size_t(s_batchCapacity) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess
 				|| hipHostMalloc((void**)&m_pHostRgbw, size_t(s_batchCapacity) * 4 * sizeof(float), hipHostMallocDefault) != hipSuccess
-				|| hipMalloc(&m_pDeviceBatch, batchBytes) != hipSuccess || hipMalloc(&m_pDeviceStats, statsBytes) != hipSuccess)
+				|| hipMalloc(&m_pDeviceBatch, batchBytes) != hipSuccess || hipMalloc(&m_pDeviceStats, statsBytes) != hipSuccess
+				|| (m_nbOfLayers > 0 && (hipHostMalloc((void**)&m_pHostLayerRgb, layerBatchBytes, hipHostMallocDefault) != hipSuccess
+						|| hipMalloc(&m_pDeviceLayerRgb, layerBatchBytes) != hipSuccess || hipMalloc(&m_pDeviceLayerStats, layerStatsBytes) != hipSuccess)))
 		{
 			m_batchCopied = ev;
 			m_error = "out of device or pinned host memory";
@@ -50,8 +66,10 @@ namespace bcd
 		m_batchCopied = ev;
 		if(bcd_hip_ctx_create(&m_pContext, i_device, m_stream) != BCD_HIP_OK)
 			m_error = "bcd_hip_ctx_create failed";
-		else if(bcd_hip_accum_create(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma, i_rHistogramParameters.m_maxValue,
-				s_batchCapacity, &m_pAccum) != BCD_HIP_OK)
+		else if((m_nbOfLayers > 0 ? bcd_hip_accum_create_layers(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma,
+						i_rHistogramParameters.m_maxValue, s_batchCapacity, m_nbOfLayers, &m_pAccum)
+				: bcd_hip_accum_create(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma, i_rHistogramParameters.m_maxValue,
+						s_batchCapacity, &m_pAccum)) != BCD_HIP_OK)
 		{
 			m_error = bcd_hip_last_error(m_pContext);
 			m_pAccum = nullptr;
@@ -67,6 +85,9 @@ namespace bcd
 		if(m_pDeviceBatch) (void)hipFree(m_pDeviceBatch);
 		if(m_pDeviceStats) (void)hipFree(m_pDeviceStats);
 		if(m_pDevicePlan) (void)hipFree(m_pDevicePlan);
+		if(m_pDeviceLayerRgb) (void)hipFree(m_pDeviceLayerRgb);
+		if(m_pDeviceLayerStats) (void)hipFree(m_pDeviceLayerStats);
+		if(m_pHostLayerRgb) (void)hipHostFree(m_pHostLayerRgb);
 		if(m_pHostPixel) (void)hipHostFree(m_pHostPixel);
 		if(m_pHostRgbw) (void)hipHostFree(m_pHostRgbw);
 		if(m_pHostXy) (void)hipHostFree(m_pHostXy);
@@ -82,7 +103,14 @@ namespace bcd
 
 	void DeviceSamplesAccumulator::addSample(int i_line, int i_column, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight)
 	{
-		if(!isValid() || !beginAppend(false))
+		if(!isValid())
+			return;
+		if(m_nbOfLayers > 0)
+		{
+			m_error = "addSample: an accumulator with layers takes addSamples with the layers' colours";
+			return;
+		}
+		if(!beginAppend(false))
 			return;
 		const int64_t i = m_pending++;
 		m_pHostPixel[i] = (i_line < 0 || i_line >= m_height || i_column < 0 || i_column >= m_width) ? -1 : i_line * m_width + i_column;
@@ -97,13 +125,47 @@ namespace bcd
 	{
 		if(!isValid())
 			return;
+		if(m_nbOfLayers > 0)
+		{
+			m_error = "addSamples: an accumulator with layers takes the layers' colours too";
+			return;
+		}
+		appendBatch(false, i_pPixelIndices, i_pRgb, nullptr, i_pWeights, i_nbOfSamples);
+	}
+
+	void DeviceSamplesAccumulator::addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights,
+			int64_t i_nbOfSamples)
+	{
+		if(!isValid())
+			return;
+		if(m_nbOfLayers == 0 || !i_ppLayerRgb)
+		{
+			m_error = m_nbOfLayers == 0 ? "addSamples: the accumulator has no layers" : "addSamples: null layer colours";
+			return;
+		}
+		appendBatch(false, i_pPixelIndices, i_pRgb, i_ppLayerRgb, i_pWeights, i_nbOfSamples);
+	}
+
+	// n samples into the pending batch (i_pKeys: pixel indices, or positions for splats), flushed whenever it is full
+	void DeviceSamplesAccumulator::appendBatch(bool i_splat, const void* i_pKeys, const float* i_pRgb, const float* const* i_ppLayerRgb,
+			const float* i_pWeights, int64_t i_nbOfSamples)
+	{
+		for(int l = 0; i_ppLayerRgb && l < m_nbOfLayers; ++l)
+			if(!i_ppLayerRgb[l])
+			{
+				m_error = "null layer colours";
+				return;
+			}
 		for(int64_t done = 0; done < i_nbOfSamples; )
 		{
-			if(!beginAppend(false))
+			if(!beginAppend(i_splat))
 				return;
 			const int64_t n = std::min(s_batchCapacity - m_pending, i_nbOfSamples - done);
-			std::memcpy(m_pHostPixel + m_pending, i_pPixelIndices + done, size_t(n) * sizeof(int32_t));
+			if(i_splat) std::memcpy(m_pHostXy + 2 * m_pending, (const float*)i_pKeys + 2 * done, size_t(n) * 2 * sizeof(float));
+			else std::memcpy(m_pHostPixel + m_pending, (const int32_t*)i_pKeys + done, size_t(n) * sizeof(int32_t));
 			std::memcpy(m_pHostRgbw + 3 * m_pending, i_pRgb + 3 * done, size_t(n) * 3 * sizeof(float));
+			for(int l = 0; i_ppLayerRgb && l < m_nbOfLayers; ++l)
+				std::memcpy(m_pHostLayerRgb + 3 * (size_t(l) * s_batchCapacity + m_pending), i_ppLayerRgb[l] + 3 * done, size_t(n) * 3 * sizeof(float));
 			float* w = m_pHostRgbw + 3 * s_batchCapacity + m_pending;
 			if(i_pWeights) std::memcpy(w, i_pWeights + done, size_t(n) * sizeof(float));
 			else std::fill(w, w + n, 1.f);
@@ -167,6 +229,11 @@ namespace bcd
 	{
 		if(!isValid())
 			return;
+		if(m_nbOfLayers > 0)
+		{
+			m_error = "splatSample: an accumulator with layers takes splatSamples with the layers' colours";
+			return;
+		}
 		if(!m_hasFilter)
 		{
 			m_error = "splatSample: no filter (setFilter)";
@@ -192,21 +259,30 @@ namespace bcd
 			m_error = "splatSamples: no filter (setFilter)";
 			return;
 		}
-		for(int64_t done = 0; done < i_nbOfSamples; )
+		if(m_nbOfLayers > 0)
 		{
-			if(!beginAppend(true))
-				return;
-			const int64_t n = std::min(s_batchCapacity - m_pending, i_nbOfSamples - done);
-			std::memcpy(m_pHostXy + 2 * m_pending, i_pPositions + 2 * done, size_t(n) * 2 * sizeof(float));
-			std::memcpy(m_pHostRgbw + 3 * m_pending, i_pRgb + 3 * done, size_t(n) * 3 * sizeof(float));
-			float* w = m_pHostRgbw + 3 * s_batchCapacity + m_pending;
-			if(i_pWeights) std::memcpy(w, i_pWeights + done, size_t(n) * sizeof(float));
-			else std::fill(w, w + n, 1.f);
-			m_pending += n;
-			done += n;
-			if(m_pending == s_batchCapacity)
-				flush();
+			m_error = "splatSamples: an accumulator with layers takes the layers' colours too";
+			return;
 		}
+		appendBatch(true, i_pPositions, i_pRgb, nullptr, i_pWeights, i_nbOfSamples);
+	}
+
+	void DeviceSamplesAccumulator::splatSamples(const float* i_pPositions, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights,
+			int64_t i_nbOfSamples)
+	{
+		if(!isValid())
+			return;
+		if(!m_hasFilter)
+		{
+			m_error = "splatSamples: no filter (setFilter)";
+			return;
+		}
+		if(m_nbOfLayers == 0 || !i_ppLayerRgb)
+		{
+			m_error = m_nbOfLayers == 0 ? "splatSamples: the accumulator has no layers" : "splatSamples: null layer colours";
+			return;
+		}
+		appendBatch(true, i_pPositions, i_pRgb, i_ppLayerRgb, i_pWeights, i_nbOfSamples);
 	}
 
 	bool DeviceSamplesAccumulator::flush() const
@@ -222,16 +298,34 @@ namespace bcd
 		float* dW = dRgb + 3 * cap;
 		const void* hostKeys = m_pendingSplats ? (const void*)m_pHostXy : (const void*)m_pHostPixel;
 		void* deviceKeys = m_pendingSplats ? m_pDeviceXy : (void*)dPix;
-		if(hipMemcpyAsync(deviceKeys, hostKeys, size_t(n) * (m_pendingSplats ? 2 * sizeof(float) : sizeof(int32_t)), hipMemcpyHostToDevice, st) != hipSuccess
-				|| hipMemcpyAsync(dRgb, m_pHostRgbw, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess
-				|| hipMemcpyAsync(dW, m_pHostRgbw + 3 * cap, size_t(n) * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess
-				|| hipEventRecord((hipEvent_t)m_batchCopied, st) != hipSuccess)
+		const float* dLayers[BCD_HIP_ACCUM_MAX_LAYERS] = { nullptr };
+		bool ok = hipMemcpyAsync(deviceKeys, hostKeys, size_t(n) * (m_pendingSplats ? 2 * sizeof(float) : sizeof(int32_t)), hipMemcpyHostToDevice, st) == hipSuccess
+				&& hipMemcpyAsync(dRgb, m_pHostRgbw, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess
+				&& hipMemcpyAsync(dW, m_pHostRgbw + 3 * cap, size_t(n) * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
+		for(int l = 0; ok && l < m_nbOfLayers; ++l)
+		{	// the layers' colours leave their pinned buffer ahead of the event too
+			float* d = (float*)m_pDeviceLayerRgb + 3 * size_t(l) * cap;
+			dLayers[l] = d;
+			ok = hipMemcpyAsync(d, m_pHostLayerRgb + 3 * size_t(l) * cap, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
+		}
+		if(!ok || hipEventRecord((hipEvent_t)m_batchCopied, st) != hipSuccess)
 		{
 			m_error = "batch upload failed";
 			return false;
 		}
 		m_copyInFlight = true;
 		m_pending = 0;
+		if(m_nbOfLayers > 0)
+		{
+			const int rc = m_pendingSplats ? bcd_hip_accum_add_splatted_layers(m_pAccum, (const float*)m_pDeviceXy, dRgb, dW, n, dLayers)
+					: bcd_hip_accum_add_scattered_layers(m_pAccum, dPix, dRgb, dW, n, dLayers);
+			if(rc != BCD_HIP_OK)
+			{
+				fail(m_pendingSplats ? "bcd_hip_accum_add_splatted_layers" : "bcd_hip_accum_add_scattered_layers");
+				return false;
+			}
+			return true;
+		}
 		if(m_pendingSplats)
 		{
 			if(bcd_hip_accum_add_splatted(m_pAccum, (const float*)m_pDeviceXy, dRgb, dW, n) != BCD_HIP_OK)
@@ -287,6 +381,60 @@ namespace bcd
 		if(hipStreamSynchronize(st) != hipSuccess)
 			m_error = "statistics download failed";
 		return out;
+	}
+
+	std::vector<DeviceSamplesAccumulator::DeviceLayerStatistics> DeviceSamplesAccumulator::computeDeviceLayerStatistics() const
+	{
+		std::vector<DeviceLayerStatistics> out;
+		if(!isValid() || m_nbOfLayers == 0)
+			return out;
+		flush();
+		const size_t n = size_t(m_width) * size_t(m_height);
+		float* means[BCD_HIP_ACCUM_MAX_LAYERS];
+		float* covs[BCD_HIP_ACCUM_MAX_LAYERS];
+		for(int l = 0; l < m_nbOfLayers; ++l)
+		{
+			means[l] = (float*)m_pDeviceLayerStats + size_t(l) * 9 * n;
+			covs[l] = means[l] + 3 * n;
+		}
+		if(bcd_hip_accum_layer_statistics(m_pAccum, means, covs) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_layer_statistics");
+			return out;
+		}
+		out.resize(size_t(m_nbOfLayers));
+		for(int l = 0; l < m_nbOfLayers; ++l)
+		{
+			out[size_t(l)].m_pMean = means[l];
+			out[size_t(l)].m_pCovariances = covs[l];
+		}
+		return out;
+	}
+
+	bool DeviceSamplesAccumulator::getLayerStatistics(int i_layer, Deepimf& o_rMean, Deepimf& o_rCovariances) const
+	{
+		if(!isValid())
+			return false;
+		if(i_layer < 0 || i_layer >= m_nbOfLayers)
+		{
+			m_error = "getLayerStatistics: no such layer";
+			return false;
+		}
+		const std::vector<DeviceLayerStatistics> d = computeDeviceLayerStatistics();
+		if(d.empty())
+			return false;
+		o_rMean.resize(m_width, m_height, 3);
+		o_rCovariances.resize(m_width, m_height, 6);
+		const size_t n = size_t(m_width) * size_t(m_height);
+		hipStream_t st = (hipStream_t)m_stream;
+		if(hipMemcpyAsync(o_rMean.getDataPtr(), d[size_t(i_layer)].m_pMean, n * 3 * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess
+				|| hipMemcpyAsync(o_rCovariances.getDataPtr(), d[size_t(i_layer)].m_pCovariances, n * 6 * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess
+				|| hipStreamSynchronize(st) != hipSuccess)
+		{
+			m_error = "layer statistics download failed";
+			return false;
+		}
+		return true;
 	}
 
 	SamplesStatisticsImages DeviceSamplesAccumulator::extractSamplesStatistics()
@@ -387,12 +535,32 @@ namespace bcd
 
 	bool DeviceSamplesAccumulator::saveState(const std::string& i_rPath) const
 	{
+		return toFile(i_rPath, false);
+	}
+
+	bool DeviceSamplesAccumulator::saveLayers(const std::string& i_rPath) const
+	{
+		return toFile(i_rPath, true);
+	}
+
+	bool DeviceSamplesAccumulator::loadLayers(const std::string& i_rPath)
+	{
+		return fromFile(i_rPath, false, true);
+	}
+
+	bool DeviceSamplesAccumulator::mergeLayers(const std::string& i_rPath)
+	{
+		return fromFile(i_rPath, true, true);
+	}
+
+	bool DeviceSamplesAccumulator::toFile(const std::string& i_rPath, bool i_layers) const
+	{
 		if(!isValid() || !flush())
 			return false;
 		int64_t bytes = 0;
-		if(bcd_hip_accum_state_bytes(m_pAccum, &bytes) != BCD_HIP_OK)
+		if((i_layers ? bcd_hip_accum_layers_state_bytes(m_pAccum, &bytes) : bcd_hip_accum_state_bytes(m_pAccum, &bytes)) != BCD_HIP_OK)
 		{
-			fail("bcd_hip_accum_state_bytes");
+			fail(i_layers ? "bcd_hip_accum_layers_state_bytes" : "bcd_hip_accum_state_bytes");
 			return false;
 		}
 		const int fd = open(i_rPath.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
@@ -411,20 +579,20 @@ namespace bcd
 			unlink(i_rPath.c_str());
 			return false;
 		}
-		const int rc = bcd_hip_accum_export(m_pAccum, p, bytes);
+		const int rc = i_layers ? bcd_hip_accum_export_layers(m_pAccum, p, bytes) : bcd_hip_accum_export(m_pAccum, p, bytes);
 		munmap(p, size_t(bytes));
 		if(rc != BCD_HIP_OK)
 		{
-			fail("bcd_hip_accum_export");
+			fail(i_layers ? "bcd_hip_accum_export_layers" : "bcd_hip_accum_export");
 			unlink(i_rPath.c_str());
 			return false;
 		}
 		return true;
 	}
 
-	bool DeviceSamplesAccumulator::fromFile(const std::string& i_rPath, bool i_merge)
+	bool DeviceSamplesAccumulator::fromFile(const std::string& i_rPath, bool i_merge, bool i_layers)
 	{
-		const char* what = i_merge ? "mergeState" : "loadState";
+		const char* what = i_layers ? (i_merge ? "mergeLayers" : "loadLayers") : (i_merge ? "mergeState" : "loadState");
 		if(!isValid() || !flush())
 			return false;
 		const int fd = open(i_rPath.c_str(), O_RDONLY);
@@ -450,7 +618,8 @@ namespace bcd
 		}
 		(void)madvise(p, bytes, MADV_SEQUENTIAL);
 		// both calls return once the mapping is no longer needed
-		const int rc = i_merge ? bcd_hip_accum_merge_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import(m_pAccum, p, int64_t(bytes));
+		const int rc = i_layers ? (i_merge ? bcd_hip_accum_merge_layers_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import_layers(m_pAccum, p, int64_t(bytes)))
+				: (i_merge ? bcd_hip_accum_merge_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import(m_pAccum, p, int64_t(bytes)));
 		munmap(p, bytes);
 		if(rc != BCD_HIP_OK)
 		{

@@ -136,6 +136,92 @@ int bcdcore_device_splat(const float* s, long long n, int W, int H, int nbins, f
 	return 0;
 }
 
+// mixed calls through the batch forms of a bcd::DeviceSamplesAccumulator with `nbLayers` colour layers: s is n x (kind, a, b, r, g, b, weight)
+// as for bcdcore_device_splat, layerRgb [nbLayers][n][3] the layers' colours of the same calls.  Runs of one kind go through addSamples /
+// splatSamples in pieces of at most `batch` calls; a host snapshot of the beauty and of one layer is taken before call `snapshotAt` (0: none).
+// statePath / layersPath (both or neither): the state and the layer block are saved at the end and loaded into a second accumulator, whose
+// statistics are the ones returned.  lmean [nbLayers][H][W][3], lcov [nbLayers][H][W][6]; counts[2]: samples accumulated / dropped
+int bcdcore_device_accumulate_layers(const float* s, long long n, const float* layerRgb, int nbLayers, int W, int H, int nbins, float gamma,
+		float maxval, int device, float radiusX, float radiusY, int tableSize, const float* table, long long batch, long long snapshotAt,
+		const char* statePath, const char* layersPath, float* ns, float* mean, float* cov, float* hist, float* lmean, float* lcov, long long* counts)
+{
+	HistogramParameters hp;
+	hp.m_nbOfBins = nbins; hp.m_gamma = gamma; hp.m_maxValue = maxval;
+	g_deviceAccumulateError.clear();
+	DeviceSamplesAccumulator first(W, H, hp, nbLayers, device);
+	if(!first.isValid() || first.nbOfLayers() != nbLayers) { g_deviceAccumulateError = first.lastError(); return -1; }
+	if(table && !first.setFilter(radiusX, radiusY, tableSize, table)) { g_deviceAccumulateError = first.lastError(); return -1; }
+	std::vector<int32_t> pixels;
+	std::vector<float> keys, rgb, weights;
+	std::vector<std::vector<float>> layers((size_t)nbLayers);
+	std::vector<const float*> layerPointers((size_t)nbLayers);
+	if(batch < 1) batch = n > 0 ? n : 1;
+	for(long long i = 0; i < n; )
+	{
+		const bool splat = s[7 * i] != 0.f;
+		long long e = i + 1;
+		while(e < n && e - i < batch && (s[7 * e] != 0.f) == splat && !(snapshotAt > 0 && e == snapshotAt)) ++e;
+		if(snapshotAt > 0 && i == snapshotAt)
+		{
+			Deepimf m, c;
+			(void)first.getSamplesStatistics();
+			if(!first.getLayerStatistics(nbLayers - 1, m, c)) { g_deviceAccumulateError = first.lastError(); return -1; }
+		}
+		const size_t m = size_t(e - i);
+		pixels.resize(m); keys.resize(2 * m); rgb.resize(3 * m); weights.resize(m);
+		for(size_t j = 0; j < m; ++j)
+		{
+			const float* p = s + 7 * (i + (long long)j);
+			const int line = int(p[1]), col = int(p[2]);
+			pixels[j] = (line < 0 || line >= H || col < 0 || col >= W) ? -1 : line * W + col;
+			keys[2 * j] = p[1]; keys[2 * j + 1] = p[2];
+			rgb[3 * j] = p[3]; rgb[3 * j + 1] = p[4]; rgb[3 * j + 2] = p[5];
+			weights[j] = p[6];
+		}
+		for(int l = 0; l < nbLayers; ++l)
+			layerPointers[(size_t)l] = layerRgb + 3 * ((long long)l * n + i);
+		if(splat) first.splatSamples(keys.data(), rgb.data(), layerPointers.data(), weights.data(), (int64_t)m);
+		else first.addSamples(pixels.data(), rgb.data(), layerPointers.data(), weights.data(), (int64_t)m);
+		i = e;
+	}
+	std::unique_ptr<DeviceSamplesAccumulator> second;
+	DeviceSamplesAccumulator* acc = &first;
+	if(statePath && layersPath)
+	{
+		if(!first.saveState(statePath) || !first.saveLayers(layersPath)) { g_deviceAccumulateError = first.lastError(); return -1; }
+		second.reset(new DeviceSamplesAccumulator(W, H, hp, nbLayers, device));
+		if(!second->isValid() || !second->loadState(statePath) || !second->loadLayers(layersPath)) { g_deviceAccumulateError = second->lastError(); return -1; }
+		acc = second.get();
+	}
+	counts[0] = acc->nbOfAccumulatedSamples();
+	counts[1] = acc->nbOfDroppedSamples();
+	for(int l = 0; l < nbLayers; ++l)
+	{
+		Deepimf m, c;
+		if(!acc->getLayerStatistics(l, m, c)) { g_deviceAccumulateError = acc->lastError(); return -1; }
+		m.copyDataTo(lmean + (size_t)l * W * H * 3);
+		c.copyDataTo(lcov + (size_t)l * W * H * 6);
+	}
+	// the forms without layers are refused on this accumulator, each with a message and without touching the sums
+	const float one[3] = { 1.f, 1.f, 1.f };
+	const int32_t zero = 0;
+	acc->addSample(0, 0, 1.f, 1.f, 1.f);
+	const bool refusedSingle = acc->lastError().find("addSample") != std::string::npos;
+	acc->addSamples(&zero, one, nullptr, 1);
+	const bool refusedBatch = acc->lastError().find("addSamples") != std::string::npos;
+	if(!refusedSingle || !refusedBatch || acc->nbOfAccumulatedSamples() != counts[0])
+	{
+		g_deviceAccumulateError = "an add without layers was accepted by an accumulator with layers";
+		return -1;
+	}
+	SamplesStatisticsImages st = acc->getSamplesStatistics();
+	st.m_nbOfSamplesImage.copyDataTo(ns);
+	st.m_meanImage.copyDataTo(mean);
+	st.m_covarImage.copyDataTo(cov);
+	st.m_histoImage.copyDataTo(hist);
+	return 0;
+}
+
 // the same stream through bcd::DeviceSamplesAccumulator::addSample (no explicit flush), then one planSamples; pixels[budget] receives the
 // list, summary[4] planned / active / unsampled / max_error.  invalidFirst: two invalid planSamples come first (a budget of 2^31 while the
 // samples are still buffered, then max_per_pixel 0), and each must return false with a message.  Returns the number of planned samples,

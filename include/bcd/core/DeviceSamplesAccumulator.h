@@ -3,6 +3,10 @@
 // is flushed through the device's scattered add, so every pixel accumulates its samples in call order with the host class's float
 // operations (nSamples, mean and covariance bit-identical; histograms to the device powf's round-off).  Snapshots are non-destructive
 // and can stay on the device for bcd_hip_denoise.
+// Colour layers: an accumulator constructed with a layer count keeps nine more running sums per layer beside the beauty's (the
+// bcd_hip_accum_*_layers entry points of bcd_hip.h, which define them exactly).  Such an accumulator is fed through the batch forms of
+// addSamples / splatSamples that take the layers' colour arrays; the single-sample addSample / splatSample have no form with layers and
+// are refused on it (message in lastError()), as are the batch forms without layers.
 #ifndef DEVICE_SAMPLES_ACCUMULATOR_H
 #define DEVICE_SAMPLES_ACCUMULATOR_H
 
@@ -49,7 +53,18 @@ namespace bcd
 			float m_maxError = 0.f;  ///< largest finite error of the active pixels
 		};
 
+		/// one layer's statistics on the device, owned by the accumulator and valid until the next layer snapshot or destruction: with the
+		/// beauty's DeviceStatistics (m_pMean, m_pCovariances) first, the layers of bcd_hip_denoise_layers
+		struct DeviceLayerStatistics
+		{
+			const float* m_pMean = nullptr;
+			const float* m_pCovariances = nullptr;
+		};
+
 		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_device = 0);
+		/// with i_nbOfLayers extra colour layers, in [1, 15] (otherwise the accumulator is not valid)
+		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_nbOfLayers, int i_device);
+		int nbOfLayers() const { return m_nbOfLayers; }
 		~DeviceSamplesAccumulator();
 		DeviceSamplesAccumulator(const DeviceSamplesAccumulator&) = delete;
 		DeviceSamplesAccumulator& operator=(const DeviceSamplesAccumulator&) = delete;
@@ -62,6 +77,9 @@ namespace bcd
 		/// n samples from host memory, in order: pixel index line * width + column, rgb [n][3], weights [n] or nullptr (all 1).
 		/// Indices outside the frame are skipped (and counted by nbOfDroppedSamples()).
 		void addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples);
+
+		/// the same with the layers' colours: i_ppLayerRgb[nbOfLayers()], each [n][3], same pixels, weights and order as the beauty's
+		void addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights, int64_t i_nbOfSamples);
 
 		/// Pixel reconstruction filter of splatSample / splatSamples (bcd_hip_accum_set_filter in bcd_hip.h, which defines the splat exactly):
 		/// radii in (0, 3], a table of i_tableSize x i_tableSize finite values >= 0 (row = y index), i_tableSize in [1, 64]; a null table
@@ -77,12 +95,21 @@ namespace bcd
 		/// n samples from host memory, in order: positions [n][2] (x, y), rgb [n][3], weights [n] or nullptr (all 1)
 		void splatSamples(const float* i_pPositions, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples);
 
+		/// the same with the layers' colours: i_ppLayerRgb[nbOfLayers()], each [n][3]
+		void splatSamples(const float* i_pPositions, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights, int64_t i_nbOfSamples);
+
 		/// copy of the statistics accumulated so far (the accumulator goes on)
 		SamplesStatisticsImages getSamplesStatistics() const;
 		/// moves the statistics out; the accumulator must not be used afterwards
 		SamplesStatisticsImages extractSamplesStatistics();
 		/// enqueues a snapshot into device buffers owned by the accumulator (no host copy, no synchronisation) and returns them
 		DeviceStatistics computeDeviceStatistics() const;
+
+		/// enqueues a snapshot of every layer into device buffers owned by the accumulator (no host copy, no synchronisation); empty on
+		/// failure or without layers
+		std::vector<DeviceLayerStatistics> computeDeviceLayerStatistics() const;
+		/// host copy of layer i_layer's mean (depth 3) and covariance (depth 6) images; synchronises
+		bool getLayerStatistics(int i_layer, Deepimf& o_rMean, Deepimf& o_rCovariances) const;
 
 		/// where the next i_budget samples go: o_pixelIndices receives the planned pixel indices (line * width + column) in ascending order,
 		/// each pixel repeated as many times as it gets samples.  The samples buffered by addSample are applied first; the statistics are
@@ -105,6 +132,12 @@ namespace bcd
 		/// adds another accumulator's state into this one; the other may live on another device and is not changed
 		bool merge(const DeviceSamplesAccumulator& i_rOther);
 
+		/// The layer block (bcd_hip_accum_export_layers / _import_layers / _merge_layers_state in bcd_hip.h): the layers' running sums, a file
+		/// of its own beside the state's.  A checkpoint of an accumulator with layers is saveState plus saveLayers.
+		bool saveLayers(const std::string& i_rPath) const;
+		bool loadLayers(const std::string& i_rPath);
+		bool mergeLayers(const std::string& i_rPath);
+
 		/// back to an empty accumulator (the frame geometry and the device buffers are kept)
 		void reset();
 		/// samples accumulated / skipped since construction or the last reset (synchronises)
@@ -116,10 +149,16 @@ namespace bcd
 		bool flush() const;
 		void fail(const char* i_pWhat) const;
 		/// loadState / mergeState: the mapped file through bcd_hip_accum_import (merge = false) or _merge_state
-		bool fromFile(const std::string& i_rPath, bool i_merge);
+		bool fromFile(const std::string& i_rPath, bool i_merge, bool i_layers = false);
+		bool toFile(const std::string& i_rPath, bool i_layers) const;
+		void appendBatch(bool i_splat, const void* i_pKeys, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights, int64_t i_nbOfSamples);
 
 	private:
 		int m_width, m_height, m_nbOfBins;
+		int m_nbOfLayers = 0;
+		float* m_pHostLayerRgb = nullptr;    // the layers' colours of the pending batch [layer][capacity][3] (pinned), and their device copy
+		void* m_pDeviceLayerRgb = nullptr;
+		void* m_pDeviceLayerStats = nullptr; // per layer mean | cov of computeDeviceLayerStatistics
 		bcd_hip_ctx* m_pContext = nullptr;
 		bcd_hip_accum* m_pAccum = nullptr;
 		bool m_isValid = true;

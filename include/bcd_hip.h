@@ -516,6 +516,67 @@ int  bcd_hip_accum_export(bcd_hip_accum *acc, void *h_state, int64_t capacity);
 int  bcd_hip_accum_import(bcd_hip_accum *acc, const void *h_state, int64_t bytes);
 int  bcd_hip_accum_merge_state(bcd_hip_accum *acc, const void *h_state, int64_t bytes);
 int  bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src);
+/* Colour layers beside the beauty: an accumulator created with nb_layers extra colour layers keeps, per layer, the
+ * nine running sums that bcd_hip_denoise_layers needs of it -- 3 weighted colour sums and 6 weighted second moments (xx, yy, zz, yz, xz,
+ * xy), 36 bytes per pixel -- in a buffer of its own, layer-major, each plane in pixel order.  The weight sum, the squared-weight sum and
+ * the histogram are the beauty's: every layer sees the same sample weights.  The shared state, its format v1 and every entry point
+ * above behave as on an accumulator without layers, except that the plain adds are refused.
+ *   Rule: every add takes the layers' colours beside the beauty's.  Each (pixel, layer) is owned by one thread and receives its
+ *     contributions in stream order, with the nine colour-sum operations of addSample in their order and the beauty's weight (for splats
+ *     w * f); no float atomics.  Layer k's mean and covariance are therefore bit for bit those of a separate accumulator (the host class
+ *     or bcd_hip_accum_*) fed layer k's colours with the same weights and stream, and the beauty's four statistics are bit for bit those
+ *     of an accumulator without layers.  The beauty goes through the kernels of the plain adds.
+ *   create_layers: nb_layers in [1, BCD_HIP_ACCUM_MAX_LAYERS], otherwise EINVAL; everything else is create.  With max_batch_samples > 0 no
+ *           later add allocates.  nb_layers: 0 for an accumulator made by create.
+ *   add_dense_layers / add_scattered_layers / add_splatted_layers: the plain add's arguments, then d_layer_*: a HOST array of nb_layers
+ *           DEVICE pointers, none null, each to data laid out like the beauty's buffer of that call (dense: layer_channels, 3 or 4, floats
+ *           per sample, independent of `channels`; scattered and splatted: [n][3]).  Dropped samples (out-of-range indices, non-finite
+ *           positions, empty footprints) are dropped for every layer and counted once.  Batches split into chunks as the plain forms
+ *           do; no bit depends on the split.
+ *   Refusals, EINVAL with a message before any device work, the state untouched: a plain add_dense / add_scattered / add_splatted on
+ *           an accumulator with layers (it would move the weight sums without the layers), a _layers add on one without, a null list or
+ *           a null entry.
+ *   layer_statistics: d_mean, d_cov: HOST arrays of nb_layers DEVICE pointers to W*H*3 and W*H*6 floats; the statistics of
+ *           bcd_hip_accum_statistics on each layer's sums with the shared weight sums.  Enqueued on the context's stream, no
+ *           synchronisation, the state unchanged.  bcd_hip_accum_statistics gives the beauty.  Together they are the inputs of
+ *           bcd_hip_denoise_layers (beauty first).
+ *   reset clears the layers; merge needs equal nb_layers on both sides (EINVAL otherwise) and adds the layer planes too, one fp32 add
+ *           per float on either of its paths; plan reads the beauty.
+ *   Layer block: the serialised layers, a block of its own, so that format v1 is not touched: a 64-byte little-endian header -- magic
+ *           "BCDACCLY" 0, version (1) 8, header_bytes (64) 12, width 16, height 20, nb_layers 24, nb_planes = 9 * nb_layers 28, 32 zero
+ *           reserved bytes 32 -- then the planes as they sit in HBM; exactly 64 + 36 * nb_layers * W * H bytes.  A checkpoint of an
+ *           accumulator with layers is its v1 state (export / import / merge_state, which act on the shared part alone) PLUS its layer
+ *           block (export_layers / import_layers / merge_layers_state); the caller keeps the two together.
+ *   layers_state_info: host only (no device, no context), as state_info: EINVAL unless magic, version, header_bytes, nb_layers in
+ *           [1, 15], positive sizes below 2^31 pixels, nb_planes, the exact size and zero reserved bytes hold.  out may be NULL.
+ *   layers_state_bytes / export_layers / import_layers / merge_layers_state: as their v1 counterparts, through the same staging chunks;
+ *           a malformed block, another frame size or another layer count give EINVAL before any device work.  export synchronises. */
+#define BCD_HIP_ACCUM_MAX_LAYERS (BCD_HIP_MAX_LAYERS - 1)
+int  bcd_hip_accum_create_layers(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
+                                 bcd_hip_accum **acc);
+int  bcd_hip_accum_nb_layers(bcd_hip_accum *acc, int *nb_layers);
+int  bcd_hip_accum_add_dense_layers(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
+                                    const float *const *d_layer_samples, int layer_channels);
+int  bcd_hip_accum_add_scattered_layers(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n,
+                                        const float *const *d_layer_rgb);
+int  bcd_hip_accum_add_splatted_layers(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n,
+                                       const float *const *d_layer_rgb);
+int  bcd_hip_accum_layer_statistics(bcd_hip_accum *acc, float *const *d_mean, float *const *d_cov);
+typedef struct bcd_hip_accum_layers_header {
+    char     magic[8];       /* the 8 bytes BCDACCLY, no terminator */
+    uint32_t version;        /* 1 */
+    uint32_t header_bytes;   /* 64: offset of the first plane */
+    int32_t  width, height, nb_layers;
+    uint32_t nb_planes;      /* 9 * nb_layers */
+    uint8_t  reserved[32];   /* zero */
+} bcd_hip_accum_layers_header;
+#define BCD_HIP_ACCUM_LAYERS_VERSION 1
+#define BCD_HIP_ACCUM_LAYERS_HEADER_BYTES 64
+int  bcd_hip_accum_layers_state_info(const void *h_layers, int64_t bytes, bcd_hip_accum_layers_header *out);
+int  bcd_hip_accum_layers_state_bytes(bcd_hip_accum *acc, int64_t *bytes);
+int  bcd_hip_accum_export_layers(bcd_hip_accum *acc, void *h_layers, int64_t capacity);
+int  bcd_hip_accum_import_layers(bcd_hip_accum *acc, const void *h_layers, int64_t bytes);
+int  bcd_hip_accum_merge_layers_state(bcd_hip_accum *acc, const void *h_layers, int64_t bytes);
 /* checkAndPutToZeroNegativeInfNaNValues   src/cli/main.cpp:389-420 */
 int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n);
 
