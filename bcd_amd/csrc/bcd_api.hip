@@ -1367,6 +1367,7 @@ int bcd_hip_active_set(bcd_hip_ctx *ctx, const uint32_t *d_mask, const int32_t *
                        uint8_t *d_state, int32_t *rounds)
 {
     if (!ctx || !d_mask || !d_count || !d_state) return bad(ctx, "bad argument");
+    if (W <= 0 || H <= 0 || w < 0 || b < 0) return bad(ctx, "marking: empty image or negative radius"); // (before any launch: a grid of no blocks is a launch error)
     DEVICE_GUARD(ctx);
     return active_set(ctx, ctx->main, d_mask, d_count, W, H, w, b, main_row_begin, main_row_end, skip_probability, random_order, seed, d_state, rounds);
 }
@@ -1374,8 +1375,10 @@ int bcd_hip_active_set(bcd_hip_ctx *ctx, const uint32_t *d_mask, const int32_t *
 int bcd_hip_active_init(bcd_hip_ctx *ctx, const int32_t *d_count, int W, int H, int w, int main_row_begin, int main_row_end,
                         float skip_probability, uint32_t seed, int row_offset, uint8_t *d_state)
 {
-    if (!ctx || !d_count || !d_state || W <= 0 || H <= 0) return bad(ctx, "bad argument");
+    if (!ctx || !d_count || !d_state) return bad(ctx, "bad argument");
+    if (W <= 0 || H <= 0 || w < 0) return bad(ctx, "marking: empty image or negative radius");
     DEVICE_GUARD(ctx);
+    // (ctx->stream IS ctx->main.stream -- work_init(ctx, ctx->main, ctx->stream) in bcd_hip_ctx_create --: the steps that follow are ordered behind this launch)
     HIPCHK(ctx, bcd_launch_active_init(d_count, W, H, w, main_row_begin, main_row_end, skip_probability, seed, row_offset, d_state, ctx->stream));
     ctx->main.dep_ready = false;
     return BCD_HIP_OK;
@@ -1385,6 +1388,7 @@ int bcd_hip_active_step(bcd_hip_ctx *ctx, const uint32_t *d_mask, const int32_t 
                         int main_row_end, int random_order, uint32_t seed, int row_offset, int first_pass, uint8_t *d_state, int32_t *undecided)
 {
     if (!ctx || !d_mask || !d_count || !d_state || !undecided) return bad(ctx, "bad argument");
+    if (W <= 0 || H <= 0 || w < 0 || b < 0) return bad(ctx, "marking: empty image or negative radius");
     DEVICE_GUARD(ctx);
     int u = 0;
     // the dependency lists extracted by the first step after bcd_hip_active_init stay valid for the following steps of the same
@@ -1399,6 +1403,7 @@ int bcd_hip_active_step_enqueue(bcd_hip_ctx *ctx, const uint32_t *d_mask, const 
                                 int main_row_end, int random_order, uint32_t seed, int row_offset, uint8_t *d_state, int64_t *d_total, int with_verdict)
 {
     if (!ctx || !d_mask || !d_count || !d_state) return bad(ctx, "bad argument");
+    if (W <= 0 || H <= 0 || w < 0 || b < 0) return bad(ctx, "marking: empty image or negative radius");
     DEVICE_GUARD(ctx);
     static_assert(sizeof(long long) == sizeof(int64_t), "64-bit counters");
     return active_step_enqueue(ctx, ctx->main, d_mask, d_count, W, H, w, b, main_row_begin, main_row_end, random_order, seed, row_offset, d_state,

@@ -209,6 +209,28 @@ int bcd_hip_selftest_division(bcd_hip_ctx *ctx, uint32_t seed, int64_t samples, 
     return BCD_HIP_OK;
 }
 
+// ---- the list compaction behind the marking stage on its own (tests/test_gpu_marking_stage.py): the estimate call is its only other caller
+
+int bcd_hip_selftest_active_lists(bcd_hip_ctx *ctx, const uint8_t *d_state, const int32_t *d_count, int W, int H, int patch_radius, int main_row_begin,
+                                  int main_row_end, const int64_t *d_skip_word, int32_t *d_strong, int32_t *d_weak, int32_t counts_out[4])
+{
+    if (!ctx || !d_state || !d_count || !d_strong || !d_weak || !counts_out || W <= 0 || H <= 0 || patch_radius < 0) return bad(ctx, "bad argument");
+    if (main_row_begin < 0 || main_row_end > H || main_row_begin > main_row_end) return bad(ctx, "bad main row range");
+    DEVICE_GUARD(ctx);
+    touch(ctx->main);
+    Work &wk = ctx->main;
+    static_assert(sizeof(long long) == sizeof(int64_t), "64-bit counters");
+    const int K = 3 * (2 * patch_radius + 1) * (2 * patch_radius + 1);
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    Counters::Lists *d_c = &wk.d_counters()->lists;
+    HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
+    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_count, (int64_t)main_row_begin * W, (int64_t)main_row_end * W, K + 1, d_strong, d_weak, &d_c->n_strong, wk.stream,
+                                        reinterpret_cast<const long long *>(d_skip_word)));
+    HIPCHK(ctx, hipMemcpyAsync(counts_out, d_c, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
 // ---- the host-buffer upload path piece by piece (tests/test_gpu_sparse_upload.py, tests/test_gpu_host_stream.py)
 
 int bcd_hip_selftest_sparse_upload(bcd_hip_ctx *ctx, const float *h_src, int64_t n, float *d_dst, int new_frame, int64_t piece_floats,

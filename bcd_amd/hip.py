@@ -227,7 +227,7 @@ SYMBOLS = [
     "bcd_hip_accum_layer_statistics", "bcd_hip_accum_layers_state_info", "bcd_hip_accum_layers_state_bytes", "bcd_hip_accum_export_layers", "bcd_hip_accum_import_layers",
     "bcd_hip_accum_merge_layers_state",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch", "bcd_hip_eig27_batch_rule",
-    "bcd_hip_selftest_sparse_upload", "bcd_hip_selftest_host_stream", "bcd_hip_approx_planes",
+    "bcd_hip_selftest_sparse_upload", "bcd_hip_selftest_host_stream", "bcd_hip_approx_planes", "bcd_hip_selftest_active_lists",
 ]
 
 _lib = None
@@ -486,6 +486,26 @@ class Context:
         self._chk(lib().bcd_hip_active_step(self.h, _dp(mask), _dp(cnt), W, H, w, b, row_begin, row_end, int(random_order), C.c_uint32(seed),
                                             row_offset, 1 if first_pass else 0, _dp(state), C.byref(u)))
         return u.value
+
+    def selftest_active_lists(self, state, cnt, w, row_begin, row_end, skip_word=None, fill=-1):
+        """bcd_hip_selftest_active_lists: the list compaction of the estimate call on its own, on the processed pixels (state 1) of lines
+        [row_begin, row_end) -> (strong list, weak list: int32 tensors pre-filled with `fill` -- W * H entries each, as the engine sizes its own; the
+        library needs room for the owned range only, which is what include/bcd_hip.h promises --, of which the first
+        n_strong / n_weak are written; n_strong; n_weak; the 64-bit sum of cnt over both lists).  skip_word: an int64 device tensor of one element;
+        when it is not zero the launch writes nothing"""
+        torch = self.torch
+        H, W = cnt.shape
+        n = max(1, H * W)
+        strong = torch.full((n,), fill, dtype=torch.int32, device=cnt.device)
+        weak = torch.full((n,), fill, dtype=torch.int32, device=cnt.device)
+        out = (C.c_int32 * 4)()
+        L = lib()
+        L.bcd_hip_selftest_active_lists.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.POINTER(C.c_int32)]
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_selftest_active_lists(self.h, _dp(state), _dp(cnt), W, H, int(w), int(row_begin), int(row_end),
+                                                  _dp(skip_word) if skip_word is not None else None, _dp(strong), _dp(weak), out))
+        total = (out[2] & 0xFFFFFFFF) | ((out[3] & 0xFFFFFFFF) << 32)
+        return strong, weak, out[0], out[1], total
 
     def bayes_accumulate(self, col, pixcov, mask, nsim, state, w, b, min_eig):
         torch = self.torch

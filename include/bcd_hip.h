@@ -605,6 +605,14 @@ int bcd_hip_selftest_bin_work(bcd_hip_ctx *ctx, const float *d_hist, const float
 int bcd_hip_selftest_approx_distance(bcd_hip_ctx *ctx, const float *d_hist, const float *d_nsamples, int W, int H, int D, int search_radius,
                                      float *max_rel_dev, int64_t *count_mismatches, int *flags);
 
+/* self-test: the compaction of the processed pixels into the two lists of the estimate call, on its own.  Of the pixels of lines [main_row_begin,
+ * main_row_end) with state 1 (processed), d_strong receives the indices line * W + col of those with d_count >= 3 (2 patch_radius + 1)^2 + 1 and d_weak
+ * the others, each list in no particular order (room for (main_row_end - main_row_begin) * W entries each); counts_out[0..1] = the two list lengths,
+ * counts_out[2..3] = the 64-bit sum of d_count over both lists (low word first).  d_skip_word (optional): a device word; when it is not zero the launch
+ * writes nothing -- the lists keep what they held and all four counts come back 0. */
+int bcd_hip_selftest_active_lists(bcd_hip_ctx *ctx, const uint8_t *d_state, const int32_t *d_count, int W, int H, int patch_radius, int main_row_begin,
+                                  int main_row_end, const int64_t *d_skip_word, int32_t *d_strong, int32_t *d_weak, int32_t counts_out[4]);
+
 /* ---- the host-buffer upload path piece by piece (self-tests; what the host-buffer entry points run, not copies of it) ---- */
 /* The sparse histogram upload on its own: n host floats through the context's uploader (created as bcd_hip_denoise_host_ex creates it) to d_dst -- any
  * alignment; a destination that is not 16-byte aligned travels as a plain copy -- on the upload stream, synchronised before the call returns.
