@@ -1342,6 +1342,19 @@ int bcd_hip_similarity_masks_exact(bcd_hip_ctx *ctx, const float *d_hist, const 
     return similarity(ctx, ctx->main, d_hist, d_ns, W, H, D, w, b, tau, d_mask, d_count, 1);
 }
 
+int bcd_hip_similarity_last_path(bcd_hip_ctx *ctx, int32_t *path, int32_t *borderline, int32_t *capacity)
+{
+    if (!ctx || !path || !borderline || !capacity) return bad(ctx, "bad argument");
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream)); // (the flags' copies are the last thing a deferred pass enqueues)
+    const bool fast = wk.border_capacity > 0 && wk.h_counters;
+    *path = fast ? (wk.ratio_used ? 2 : 1) : 0;
+    *borderline = fast ? wk.h_counters->flags.borderline : 0;
+    *capacity = fast ? wk.border_capacity : 0;
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_window_distances(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, int W, int H, int D, int w, int b,
                              int line, int col, float *h_out)
 {

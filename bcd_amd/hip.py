@@ -216,7 +216,7 @@ SYMBOLS = [
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
     "bcd_hip_multi_unique_id", "bcd_hip_multi_rccl_info", "bcd_hip_multi_create_rank", "bcd_hip_multi_rank_configure", "bcd_hip_multi_rank_upload", "bcd_hip_multi_rank_step",
     "bcd_hip_multi_rank_download", "bcd_hip_multi_rank_renew_ids", "bcd_hip_multi_set_loopback", "bcd_hip_multi_selftest_transport",
-    "bcd_hip_scale_begin", "bcd_hip_pixel_cov", "bcd_hip_similarity_masks", "bcd_hip_similarity_masks_deferred", "bcd_hip_similarity_masks_verdict", "bcd_hip_similarity_masks_exact", "bcd_hip_window_distances", "bcd_hip_active_set", "bcd_hip_active_init", "bcd_hip_active_step", "bcd_hip_active_step_enqueue", "bcd_hip_active_step_collect",
+    "bcd_hip_scale_begin", "bcd_hip_pixel_cov", "bcd_hip_similarity_masks", "bcd_hip_similarity_masks_deferred", "bcd_hip_similarity_masks_verdict", "bcd_hip_similarity_masks_exact", "bcd_hip_similarity_last_path", "bcd_hip_window_distances", "bcd_hip_active_set", "bcd_hip_active_init", "bcd_hip_active_step", "bcd_hip_active_step_enqueue", "bcd_hip_active_step_collect",
     "bcd_hip_bayes_accumulate", "bcd_hip_bayes_accumulate_layers", "bcd_hip_layers_pixel_cov", "bcd_hip_layers_finalize", "bcd_hip_layers_downscale_avg", "bcd_hip_layers_downscale_cov", "bcd_hip_layers_merge",
     "bcd_hip_bayes_accumulate_rows", "bcd_hip_bayes_last_redo_count", "bcd_hip_finalize", "bcd_hip_finalize_band", "bcd_hip_downscale_sum", "bcd_hip_downscale_avg",
     "bcd_hip_downscale_cov", "bcd_hip_interpolate", "bcd_hip_merge", "bcd_hip_spike_filter", "bcd_hip_accumulate_samples", "bcd_hip_accum_create", "bcd_hip_accum_destroy", "bcd_hip_accum_reset", "bcd_hip_accum_add_dense",
@@ -456,6 +456,22 @@ class Context:
         cnt = torch.zeros((H, W), dtype=torch.int32, device=hist.device)
         self._chk(lib().bcd_hip_similarity_masks(self.h, _dp(hist), _dp(ns), W, H, D, w, b, C.c_float(tau), _dp(mask), _dp(cnt)))
         return mask, cnt
+
+    def similarity_masks_exact(self, hist, ns, w, b, tau):
+        """bcd_hip_similarity_masks_exact: the exact planes with the compiler's division, whatever the fast path would do"""
+        torch = self.torch
+        H, W, D = hist.shape
+        words = ((2 * b + 1) ** 2 + 31) // 32
+        mask = torch.zeros((H, W, words), dtype=torch.int32, device=hist.device)
+        cnt = torch.zeros((H, W), dtype=torch.int32, device=hist.device)
+        self._chk(lib().bcd_hip_similarity_masks_exact(self.h, _dp(hist), _dp(ns), W, H, D, w, b, C.c_float(tau), _dp(mask), _dp(cnt)))
+        return mask, cnt
+
+    def similarity_last_path(self):
+        """(path, borderline pairs, list capacity) of the last similarity pass on the main workspace: path 0 exact, 1 approximate, 2 RATIO form"""
+        p, n, cap = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._chk(lib().bcd_hip_similarity_last_path(self.h, C.byref(p), C.byref(n), C.byref(cap)))
+        return p.value, n.value, cap.value
 
     def window_distances(self, hist, ns, w, b, line, col):
         import numpy as np

@@ -286,6 +286,11 @@ int bcd_hip_similarity_masks_verdict(bcd_hip_ctx *ctx, int *redo);
 int bcd_hip_similarity_masks_exact(bcd_hip_ctx *ctx, const float *d_histograms, const float *d_nsamples,
                                    int W, int H, int D, int patch_radius, int search_radius, float threshold,
                                    uint32_t *d_mask, int32_t *d_count);
+/* How the last similarity pass of this context's main workspace ended (bcd_hip_similarity_masks[_deferred / _exact], or the finest scale of a frame):
+ * *path = 0 exact planes, 1 approximate planes of one power-of-two sample count or of the reference's general formula, 2 approximate planes of the RATIO form;
+ * *borderline = pairs that pass listed for exact re-evaluation and *capacity = the pairs its list holds (both 0 on path 0).  A pass that had to be redone
+ * -- inputs outside the guarded range, list overflowed, RATIO form declined -- reports the pass that replaced it.  Read-only; waits for the context's stream. */
+int bcd_hip_similarity_last_path(bcd_hip_ctx *ctx, int32_t *path, int32_t *borderline, int32_t *capacity);
 /* raw patch distances of one main pixel to its window (debug / parity): (2b+1)^2 floats, +inf outside */
 int bcd_hip_window_distances(bcd_hip_ctx *ctx, const float *d_histograms, const float *d_nsamples,
                              int W, int H, int D, int patch_radius, int search_radius,
