@@ -456,6 +456,16 @@ int bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mea
     return BCD_HIP_OK;
 }
 
+int bcd_hip_accum_moments(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (!d_nsamples || !d_mean || !d_cov) return bad(ctx, "null output");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_accum_moments((const float *)acc->state.p, acc->N, d_nsamples, d_mean, d_cov, ctx->stream));
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_accum_layer_statistics(bcd_hip_accum *acc, float *const *d_mean, float *const *d_cov)
 {
     if (!acc) return BCD_HIP_EINVAL;

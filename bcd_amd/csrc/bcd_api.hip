@@ -1,7 +1,8 @@
 // bcd_api.hip -- implementation of the C ABI declared in include/bcd_hip.h: context, workspace,
 // the per-scale driver (Denoiser::denoise, src/core/Denoiser.cpp:84-212) and the multiscale driver
 // (MultiscaleDenoiser::denoise, src/core/MultiscaleDenoiser.cpp:31-136) on device-resident images, and the stage-level entry points.
-// The host-buffer entry points are in bcd_host.hip, the sample accumulator in bcd_accum.hip, the self-tests in bcd_selftest.hip.
+// The host-buffer entry points are in bcd_host.hip, the sample accumulator in bcd_accum.hip, a frame's kept selection in bcd_selection.hip, the self-tests in
+// bcd_selftest.hip.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -518,15 +519,26 @@ void bayes_counts(const Work &wk, int64_t *n_strong, int64_t *n_weak, int64_t *s
 // d_mask / d_nsim / d_state: the selection (a frame: the workspace's); pixcov[k] / sum[k]: per-pixel covariances and (cleared) sums of extra layer k (a frame:
 // slices of wk.lay_pixcov / wk.lay_sum); spectral[1 + E]: per layer, the items that took the redo list; lv.out[k] null for every k (the stage-level entry
 // point): the sums are left as they are, nothing is finalised.
+// `kept` (bcd_hip_selection_denoise): the lists and their lengths are a kept selection's, not the workspace's -- d_mask / d_nsim / d_state / d_count are then
+// its buffers too -- every layer of the call is a follower (up to BCD_MAX_LAYERS of them), and the redo counter starts at zero: spectral[0] = 0.
+} // namespace
+
 int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state,
-                  const float *const *pixcov, float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral)
+                  const float *const *pixcov, float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral,
+                  const KeptLists *kept)
 {
     const int E = lv.n;
     const int64_t npix = (int64_t)W * H;
     const int K = 3 * (2 * w + 1) * (2 * w + 1);
     Counters::Lists *d_c = &wk.d_counters()->lists;
     Counters *h = wk.h_counters;
-    const int n_strong = h->lists.n_strong;
+    const int32_t *strong = kept ? kept->strong : (const int32_t *)wk.strong.p, *weak = kept ? kept->weak : (const int32_t *)wk.weak.p;
+    const int32_t *d_n_strong = kept ? kept->d_len : &d_c->n_strong, *d_n_weak = kept ? kept->d_len + 1 : &d_c->n_weak;
+    const int n_strong = kept ? kept->n_strong : h->lists.n_strong;
+    if (kept) { // no first layer's chain left a redo count behind
+        HIPCHK(ctx, hipMemsetAsync(&d_c->spectral, 0, sizeof(int32_t), wk.stream));
+        h->lists.spectral = 0;
+    }
     spectral[0] = h->lists.spectral;
     const int cus = estimate_cus(ctx, wk);
     RCCHK(fork_aux(ctx, wk));
@@ -537,7 +549,7 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
     } else {
         const int weak_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), (int64_t)cus * 32);
         for (int k = 0; k < E; ++k)
-            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, (const int32_t *)wk.weak.p, &d_c->n_weak, weak_blocks, W, H, w, b, sum[k], nullptr, wk.aux));
+            HIPCHK(ctx, bcd_launch_bayes_weak(lv.col[k], d_mask, weak, d_n_weak, weak_blocks, W, H, w, b, sum[k], nullptr, wk.aux));
     }
     HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
     if (w == 1) {
@@ -547,7 +559,7 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
         for (int k = 0; k < E; ++k) {
             for (int first = 0; first < n_strong; first += chunk_max) {
                 HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
-                HIPCHK(ctx, bcd_launch_bayes27(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, first, std::min(chunk_max, n_strong - first),
+                HIPCHK(ctx, bcd_launch_bayes27(lv.col[k], pixcov[k], d_mask, strong, first, std::min(chunk_max, n_strong - first),
                                                (int *)wk.work_q.p, cus, W, H, b, min_eig, (float *)wk.gscratch.p, sum[k], nullptr, &d_c->spectral, wk.stream, 0, nullptr));
             }
             HIPCHK(ctx, hipMemcpyAsync(&h->layer_redo_total[k], &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
@@ -557,7 +569,7 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
         const int strong_blocks = (int)std::min<int64_t>(std::max<int64_t>(1, npix), 1024);
         if (per_block) RCCHK(ensure(ctx, wk.gscratch, per_block * (size_t)strong_blocks));
         for (int k = 0; k < E; ++k) {
-            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov[k], d_mask, (const int32_t *)wk.strong.p, &d_c->n_strong, d_c->generic_work, strong_blocks, W, H, w, b, min_eig,
+            HIPCHK(ctx, bcd_launch_bayes_strong(lv.col[k], pixcov[k], d_mask, strong, d_n_strong, d_c->generic_work, strong_blocks, W, H, w, b, min_eig,
                                                 sum[k], nullptr, (float *)wk.gscratch.p, wk.gscratch.bytes, wk.stream));
             h->layer_redo_total[k] = h->lists.spectral;
         }
@@ -573,6 +585,8 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
     h->lists.spectral = h->layer_redo_total[E - 1]; // the scale's figure: the sum over the layers
     return BCD_HIP_OK;
 }
+
+namespace {
 
 // one scale: accumulators only (d_sum / d_count are zeroed here)
 int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
@@ -710,6 +724,7 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
         st.ms_bayes = stage_ms(wk, 2, 3);
         st.ms_total = stage_ms(wk, 0, 3);
     }
+    if (ctx->keep) RCCHK(selection_store(ctx, wk, scale, d_ns, W, H, b, d_count, st)); // (bcd_hip_denoise_layers_keep: copies on this scale's stream)
     return BCD_HIP_OK;
 }
 
@@ -742,6 +757,8 @@ int mono(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_ns, c
     RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
     return mono_accumulate(ctx, wk, d_colors, d_ns, d_hist, d_cov, W, H, D, 0, H, prm, seed, scale, (float *)wk.sum.p, (int32_t *)wk.cnt.p, d_out, lv);
 }
+
+} // namespace
 
 // the pyramid level of the extra layers (colour averaged, covariance weighted by the SHARED sample counts of the finer level): two launches for all of them
 int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &coarse, const float *ns_fine, int W, int H, hipStream_t st)
@@ -790,6 +807,8 @@ int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream)
     w.initialised = true;
     return BCD_HIP_OK;
 }
+
+namespace {
 
 void work_destroy(Work &w)
 {
@@ -1116,19 +1135,10 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
     return BCD_HIP_OK;
 }
 
-extern "C" {
-
-int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
-                    int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+// the refusals of bcd_hip_denoise_layers (and of bcd_hip_denoise_layers_keep): everything is checked before any device work
+int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
+                      int nb_layers)
 {
-    return denoise_impl(ctx, d_colors, d_ns, d_hist, d_cov, W, H, D, nb_scales, prm, d_out, nullptr);
-}
-
-int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
-                           const bcd_hip_layer *layers, int nb_layers)
-{
-    if (!ctx) return BCD_HIP_EINVAL;
-    // ---- everything is checked before any device work
     if (!d_ns || !d_hist) return bad(ctx, "null image pointer");
     if (!layers) return bad(ctx, "null layer list");
     if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
@@ -1156,6 +1166,22 @@ int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_h
             }
         }
     }
+    return BCD_HIP_OK;
+}
+
+extern "C" {
+
+int bcd_hip_denoise(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov,
+                    int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+{
+    return denoise_impl(ctx, d_colors, d_ns, d_hist, d_cov, W, H, D, nb_scales, prm, d_out, nullptr);
+}
+
+int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                           const bcd_hip_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_layers_call(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers)); // everything is checked before any device work
     LayerView lv;
     lv.n = nb_layers - 1;
     for (int k = 1; k < nb_layers; ++k) { lv.col[k - 1] = layers[k].d_colors; lv.cov[k - 1] = layers[k].d_covariances; lv.out[k - 1] = layers[k].d_out; }

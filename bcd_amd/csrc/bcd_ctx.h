@@ -1,4 +1,4 @@
-// bcd_ctx.h -- internal to the host orchestration files (bcd_api.hip, bcd_host.hip, bcd_accum.hip, bcd_selftest.hip): the context, the per-scale
+// bcd_ctx.h -- internal to the host orchestration files (bcd_api.hip, bcd_host.hip, bcd_accum.hip, bcd_selection.hip, bcd_selftest.hip): the context, the per-scale
 // workspace with its counter block, the error-handling macros and the helpers more than one of those files needs.  Nothing declared here is part
 // of the C ABI (include/bcd_hip.h): the helpers have hidden visibility.
 #pragma once
@@ -45,7 +45,7 @@ struct LayerView {
 // | 18..19 | sum of |S| (64 bit)                                                     | the same                                                         |
 // | 20..22 | work counters of the generic estimate kernel                            | --                                                               |
 // | 23     | spectral-inverse (redo) count                                           | the same; layers_follow leaves the sum over the layers here      |
-// | 24..39 | 32..33: scratch of the self-tests                                       | 24 + k: running redo total after extra layer k                   |
+// | 24..39 | 32..33: scratch of the self-tests                                       | 24 + k: running redo total after follower layer k (up to 16)     |
 // | 40..43 | range / count flag, uniform-count scan, "another sample count",         | the same                                                         |
 // |        | borderline pairs (k_sum_counter_lines reads [0], [2], [3] of them)      |                                                                  |
 // | 44     | --                                                                      | the first pixel's sample count (scan_uniform_count)              |
@@ -63,7 +63,7 @@ struct Counters {
     } lists;
     struct SelftestScratch { int32_t below[8]; unsigned long long result; };
     union {
-        int32_t layer_redo_total[BCD_MAX_LAYERS]; // HOST ONLY: [k] = `spectral` after extra layer k (BCD_MAX_LAYERS - 1 in use)
+        int32_t layer_redo_total[BCD_MAX_LAYERS]; // HOST ONLY: [k] = `spectral` after follower layer k (a frame: BCD_MAX_LAYERS - 1 in use; a kept selection: all)
         SelftestScratch selftest;                 // DEVICE ONLY: result word(s) of the self-tests
     };
     struct Flags {
@@ -89,8 +89,15 @@ static_assert(COUNTER_WORD(flags) == 40 && COUNTER_WORD(flags.other_count) == 42
 static_assert(COUNTER_WORD(marking_total) == 48 && COUNTER_WORD(selftest.result) == 32, "words the kernels are handed");
 static_assert(offsetof(Counters, lists.sim_total) % 8 == 0 && offsetof(Counters, selftest.result) % 8 == 0 && offsetof(Counters, marking_total) % 8 == 0 &&
                   offsetof(Counters, bin_work) % 8 == 0, "64-bit counters are 8-byte aligned");
-static_assert(COUNTER_WORD(layer_redo_total) + (BCD_MAX_LAYERS - 1) <= COUNTER_WORD(flags), "the per-layer running totals end below the flag words");
+static_assert(COUNTER_WORD(layer_redo_total) + BCD_MAX_LAYERS <= COUNTER_WORD(flags), "the per-layer running totals end below the flag words");
 static_assert(COUNTER_WORD(first_count) > COUNTER_WORD(flags.borderline), "the first pixel's count does not alias a flag word");
+
+// the lists of a kept selection (bcd_selection.hip), handed to layers_follow in place of the workspace's own
+struct KeptLists {
+    const int32_t *strong, *weak; // full-estimate items, fallback pixels
+    const int32_t *d_len;         // on the device: their lengths (n_strong, n_weak), for the kernels that read them there
+    int n_strong;
+};
 
 #pragma GCC visibility pop
 
@@ -166,6 +173,7 @@ struct bcd_hip_ctx {
     DevBuf lay_pyr[MAX_SCALES][3]; // extra colour layers: colours, cov, out of every layer at that pyramid level, one slice per layer
     int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
     int layer_count = 0;                                // layers of that call (0: none yet)
+    bcd_hip_selection *keep = nullptr;                  // bcd_hip_denoise_layers_keep in progress: every scale leaves its selection here (mono_accumulate)
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
     hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
@@ -246,6 +254,18 @@ int scan_uniform_count(bcd_hip_ctx *ctx, Work &wk, const float *d_ns, size_t npi
 float stage_ms(Work &wk, int a, int b);
 int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov, int W, int H, int D, int nb_scales,
                  const bcd_hip_params *prm, float *d_out, const LayerView *lv0);
+int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream);
+int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
+                      int nb_layers);
+int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state, const float *const *pixcov,
+                  float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral, const KeptLists *kept = nullptr);
+int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &coarse, const float *ns_fine, int W, int H, hipStream_t st);
+int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int H, const LayerView &lo);
+
+// ---- defined in bcd_selection.hip
+// one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is
+// filled): device-to-device copies on the scale's stream into ctx->keep
+int selection_store(bcd_hip_ctx *ctx, Work &wk, int scale, const float *d_ns, int W, int H, int b, const int32_t *d_count, const bcd_hip_scale_stats &st);
 
 // ---- defined in bcd_host.hip (shared with the self-tests of the upload path in bcd_selftest.hip)
 struct HostStreamProgress {

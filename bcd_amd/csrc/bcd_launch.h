@@ -123,6 +123,7 @@ hipError_t bcd_accum_sort(void *tmp, size_t *tmp_bytes, const uint32_t *kin, uin
 hipError_t bcd_launch_accum_segments(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t N, const float *rgb, const float *weights, int nbins, float gamma,
                                      float maxval, float *st, hipStream_t s);
 hipError_t bcd_launch_accum_snapshot(const float *st, int64_t N, int D, float *ons, float *omean, float *ocov, float *ohist, hipStream_t s);
+hipError_t bcd_launch_accum_moments(const float *st, int64_t N, float *ons, float *omean, float *ocov, hipStream_t s);
 int bcd_splat_ring_cells(int nx, int ny);
 int bcd_splat_max_staged(int ts);
 // filter: rx, ry, inv_rx, inv_ry; geom: ts, kx, ky, nx, ny; T: the table on the device

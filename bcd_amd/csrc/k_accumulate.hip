@@ -518,6 +518,23 @@ __global__ __launch_bounds__(64) void k_accum_snapshot(const float *__restrict__
     }
 }
 
+// (c0) the snapshot without the bins: the AccSums planes in (11 plane-major reads of 64 consecutive floats per wavefront), nSamples / mean /
+// covariance out through acc_statistics -- the bits of k_accum_snapshot's three images -- 44 B read and 40 B written per pixel.  No LDS: the
+// transpose of k_accum_snapshot serves the bin planes only.  State is read only.
+__global__ __launch_bounds__(256) void k_accum_moments(const float *__restrict__ st, int64_t N, float *__restrict__ ons, float *__restrict__ omean,
+                                                       float *__restrict__ ocov)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= N) return;
+    AccSums s;
+    s.load(st, N, p);
+    float mean[3], cov[6];
+    acc_statistics(s, mean, cov);
+    for (int i = 0; i < 3; ++i) omean[p * 3 + i] = mean[i];
+    for (int i = 0; i < 6; ++i) ocov[p * 6 + i] = cov[i];
+    ons[p] = s.wsum;
+}
+
 // (c') snapshot of the layers: acc_statistics on a layer's nine sums with the beauty's weight sum and squared-weight sum; blockIdx.y =
 // layer.  Reads 8 + 36 B and writes 36 B per pixel and layer; state and layers are read only.
 __global__ __launch_bounds__(256) void k_accum_snapshot_layers(const float *__restrict__ st, const float *__restrict__ layers, int64_t N,
@@ -823,6 +840,12 @@ hipError_t bcd_launch_splat(const void *cells, const uint32_t *vals, const float
 hipError_t bcd_launch_accum_snapshot(const float *st, int64_t N, int D, float *ons, float *omean, float *ocov, float *ohist, hipStream_t s)
 {
     hipLaunchKernelGGL(k_accum_snapshot, dim3(nblk(N, 64)), dim3(64), bcd_accum_snapshot_lds(D), s, st, N, D, ons, omean, ocov, ohist);
+    return hipGetLastError();
+}
+
+hipError_t bcd_launch_accum_moments(const float *st, int64_t N, float *ons, float *omean, float *ocov, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_accum_moments, dim3(nblk(N, 256)), dim3(256), 0, s, st, N, ons, omean, ocov);
     return hipGetLastError();
 }
 

@@ -25,6 +25,21 @@ class Layer(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p), ("d_out", C.c_void_p)]
 
 
+class SelectionScale(C.Structure):
+    """bcd_hip_selection_scale"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("processed", C.c_int64), ("fallback", C.c_int64), ("similar_total", C.c_int64),
+                ("similarity_path", C.c_int32), ("reserved", C.c_int32)]
+
+
+SELECTION_MAX_SCALES = 16  # BCD_HIP_SELECTION_MAX_SCALES
+
+
+class SelectionInfo(C.Structure):
+    """struct bcd_hip_selection_info"""
+    _fields_ = [("valid", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("nb_scales", C.c_int32), ("params", Params),
+                ("device_bytes", C.c_int64), ("scale", SelectionScale * SELECTION_MAX_SCALES)]
+
+
 class StageLayer(C.Structure):
     """bcd_hip_stage_layer: one layer of bcd_hip_bayes_accumulate_layers"""
     _fields_ = [("d_colors", C.c_void_p), ("d_pixel_cov", C.c_void_p), ("d_sum", C.c_void_p)]
@@ -212,7 +227,9 @@ class ScaleStats(C.Structure):
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
     "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
-    "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
+    "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host",
+    "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
+    "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
     "bcd_hip_multi_unique_id", "bcd_hip_multi_rccl_info", "bcd_hip_multi_create_rank", "bcd_hip_multi_rank_configure", "bcd_hip_multi_rank_upload", "bcd_hip_multi_rank_step",
     "bcd_hip_multi_rank_download", "bcd_hip_multi_rank_renew_ids", "bcd_hip_multi_set_loopback", "bcd_hip_multi_selftest_transport",
@@ -286,10 +303,11 @@ class Context:
             raise BcdHipError("bcd_hip_ctx_create failed: rc=%d" % rc)
         self.h = h
         self._accumulators = weakref.WeakSet()
+        self._selections = weakref.WeakSet()
 
     def close(self):
         if self.h:
-            for a in list(self._accumulators):               # an accumulator must not outlive its context (bcd_hip.h)
+            for a in list(self._accumulators) + list(self._selections):   # an accumulator / a selection must not outlive its context (bcd_hip.h)
                 a.close()
             lib().bcd_hip_ctx_destroy(self.h)
             self.h = None
@@ -313,14 +331,12 @@ class Context:
         self._chk(lib().bcd_hip_denoise(self.h, _dp(col), _dp(ns), _dp(hist), _dp(cov), W, H, D, nscales, C.byref(prm), _dp(out)))
         return out
 
-    def denoise_layers(self, ns, hist, layers, nscales, prm, outs=None):
-        """bcd_hip_denoise_layers: `layers` is a list of (colours, covariances) tensors that share `ns` and `hist`; one selection of similar patches
-        serves them all.  Returns the list of outputs (`outs`: tensors to write into, optional)."""
+    def _layer_array(self, layers, outs, H, W, device):
+        """the bcd_hip_layer array of a list of (colours, covariances) tensors and their outputs (fresh ones when `outs` is None)"""
         torch = self.torch
-        H, W, D = hist.shape
         layers = list(layers)
         if outs is None:
-            outs = [torch.empty((H, W, 3), dtype=torch.float32, device=hist.device) for _ in layers]
+            outs = [torch.empty((H, W, 3), dtype=torch.float32, device=device) for _ in layers]
         outs = list(outs)
         if len(outs) != len(layers):
             raise ValueError("one output per layer expected")
@@ -329,10 +345,26 @@ class Context:
             if tuple(col.shape) != (H, W, 3) or tuple(cov.shape) != (H, W, 6) or tuple(out.shape) != (H, W, 3):
                 raise ValueError("layer %d: colours / output must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
             arr[k].d_colors, arr[k].d_covariances, arr[k].d_out = _dp(col).value, _dp(cov).value, _dp(out).value
+        return arr, layers, outs
+
+    def denoise_layers(self, ns, hist, layers, nscales, prm, outs=None, keep=None):
+        """bcd_hip_denoise_layers: `layers` is a list of (colours, covariances) tensors that share `ns` and `hist`; one selection of similar patches
+        serves them all.  Returns the list of outputs (`outs`: tensors to write into, optional).  keep: a Selection (Context.selection()) that takes
+        the selection of every scale with it (bcd_hip_denoise_layers_keep)"""
+        H, W, D = hist.shape
+        arr, layers, outs = self._layer_array(layers, outs, H, W, hist.device)
         L = lib()
         L.bcd_hip_denoise_layers.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Layer), C.c_int]
-        self._chk(L.bcd_hip_denoise_layers(self.h, _dp(ns), _dp(hist), W, H, D, nscales, C.byref(prm), arr, len(layers)))
+        if keep is None:
+            self._chk(L.bcd_hip_denoise_layers(self.h, _dp(ns), _dp(hist), W, H, D, nscales, C.byref(prm), arr, len(layers)))
+        else:
+            _selection_api()
+            self._chk(L.bcd_hip_denoise_layers_keep(self.h, _dp(ns), _dp(hist), W, H, D, nscales, C.byref(prm), arr, len(layers), keep._handle()))
         return outs
+
+    def selection(self):
+        """an empty Selection of this context (bcd_hip_selection_create); denoise_layers(..., keep=sel) fills it"""
+        return Selection(self)
 
     def layer_spectral_inverses(self, scale, layer):
         """full estimates of one layer of the last denoise_layers call that took the spectral inverse (stats().spectral_inverses is their sum)"""
@@ -874,6 +906,18 @@ class Accumulator:
         self._chk(_layers_api().bcd_hip_accum_layer_statistics(self.h, means, covs))
         return out
 
+    def moments(self, out=None):
+        """-> (ns (H, W, 1), mean (H, W, 3), cov (H, W, 6)), fresh tensors or the three of `out`: statistics() without the histograms, bit for bit
+        (bcd_hip_accum_moments: no bin is read or written); state unchanged"""
+        torch = self.ctx.torch
+        if out is None:
+            mk = lambda d: torch.empty((self.H, self.W, d), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+            out = (mk(1), mk(3), mk(6))
+        L = lib()
+        L.bcd_hip_accum_moments.argtypes = [_VP, _VP, _VP, _VP]
+        self._chk(L.bcd_hip_accum_moments(self.h, *[_dp(t) for t in out]))
+        return out
+
     def statistics(self, out=None):
         """-> (ns (H, W, 1), mean (H, W, 3), cov (H, W, 6), hist (H, W, 3 nbins)), fresh tensors or the four of `out`; state unchanged"""
         torch = self.ctx.torch
@@ -972,6 +1016,96 @@ class Accumulator:
     def close(self):
         if self.h:
             lib().bcd_hip_accum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _selection_api():
+    L = lib()
+    L.bcd_hip_selection_create.argtypes = [_VP, C.POINTER(_VP)]
+    L.bcd_hip_selection_destroy.argtypes = [_VP]
+    L.bcd_hip_selection_destroy.restype = None
+    L.bcd_hip_denoise_layers_keep.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Layer), C.c_int, _VP]
+    L.bcd_hip_selection_denoise.argtypes = [_VP, _VP, C.POINTER(Layer), C.c_int]
+    L.bcd_hip_selection_info.argtypes = [_VP, C.POINTER(SelectionInfo)]
+    L.bcd_hip_selection_read.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP]
+    return L
+
+
+class Selection:
+    """bcd_hip_selection: the similar-patch selection of a frame, kept by Context.denoise_layers(..., keep=sel) so that further layers of that frame
+    cost the estimate stage alone"""
+
+    def __init__(self, ctx):
+        h = _VP()
+        rc = _selection_api().bcd_hip_selection_create(ctx.h, C.byref(h))
+        if rc != 0 or not h.value:
+            raise BcdHipError("bcd_hip_selection_create failed: rc=%d" % rc)
+        self.ctx, self.h = ctx, h
+        ctx._selections.add(self)
+
+    def _handle(self):
+        if not self.h:
+            raise BcdHipError("the selection is closed")
+        return self.h
+
+    def denoise(self, layers, ns=None, outs=None):
+        """bcd_hip_selection_denoise: the estimate stage on the kept selection for a list of (colours, covariances) tensors of the kept frame size;
+        ns: sample counts that replace the kept ones in the estimate stage (None: the kept ones).  Returns the list of outputs"""
+        h = self._handle()
+        info = self.info()
+        layers = list(layers)
+        if info["valid"]:
+            H, W = info["H"], info["W"]
+        else:                                                        # (the library refuses the call; shapes from the first layer so that it gets there)
+            H, W = (layers[0][0].shape[0], layers[0][0].shape[1]) if layers else (1, 1)
+        dev = layers[0][0].device if layers else "cuda:%d" % self.ctx.device
+        arr, layers, outs = self.ctx._layer_array(layers, outs, H, W, dev)
+        if ns is not None and ns.numel() != H * W:
+            raise ValueError("sample counts must be %dx%d" % (H, W))
+        self.ctx._chk(_selection_api().bcd_hip_selection_denoise(h, _dp(ns) if ns is not None else None, arr, len(layers)))
+        return outs
+
+    def info(self):
+        """bcd_hip_selection_info as a dict (host only): valid, W, H, D, nb_scales, params, device_bytes, scales = [dict(width, height, processed,
+        fallback, similar_total, similarity_path)]"""
+        i = SelectionInfo()
+        rc = _selection_api().bcd_hip_selection_info(self._handle(), C.byref(i))
+        if rc != 0:
+            raise BcdHipError("bcd_hip_selection_info: rc=%d" % rc)
+        p = Params()
+        C.memmove(C.byref(p), C.byref(i.params), C.sizeof(Params))
+        return {"valid": bool(i.valid), "W": i.W, "H": i.H, "D": i.D, "nb_scales": i.nb_scales, "params": p, "device_bytes": i.device_bytes,
+                "scales": [{k: getattr(i.scale[s], k) for k, _ in SelectionScale._fields_ if k != "reserved"} for s in range(i.nb_scales)]}
+
+    def read(self, scale):
+        """bcd_hip_selection_read -> (mask (h, w, words) int32, |S| (h, w) int32, states (h, w) uint8, count image (h, w) int32) of one scale, in the
+        layouts of Context.similarity_masks / active_set"""
+        h = self._handle()
+        torch = self.ctx.torch
+        info = self.info()
+        if not info["valid"] or not 0 <= scale < info["nb_scales"]:
+            hh, ww, words = 1, 1, 1                                  # (the library refuses the call)
+        else:
+            hh, ww = info["scales"][scale]["height"], info["scales"][scale]["width"]
+            words = ((2 * info["params"].search_radius + 1) ** 2 + 31) // 32
+        dev = "cuda:%d" % self.ctx.device
+        mask = torch.zeros((hh, ww, words), dtype=torch.int32, device=dev)
+        nsim = torch.zeros((hh, ww), dtype=torch.int32, device=dev)
+        state = torch.zeros((hh, ww), dtype=torch.uint8, device=dev)
+        count = torch.zeros((hh, ww), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(self.ctx.device)                      # (the fills ran on torch's stream)
+        self.ctx._chk(_selection_api().bcd_hip_selection_read(h, int(scale), _dp(mask), _dp(nsim), _dp(state), _dp(count)))
+        return mask, nsim, state, count
+
+    def close(self):
+        if self.h:
+            lib().bcd_hip_selection_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -143,6 +143,52 @@ int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const floa
 /* full estimates of `layer` at `scale` of the last bcd_hip_denoise_layers call whose sweep inverse failed its checks (see bcd_hip_scale_stats) */
 int bcd_hip_layer_spectral_inverses(const bcd_hip_ctx *ctx, int scale, int layer, int32_t *count);
 
+/* ---- a frame's selection, kept ------------------------------------------------------------------
+ * What the estimate stage needs of a frame besides colours and covariances -- per scale the mask words, |S|, the pixel states, the full-estimate and
+ * the fallback list with their lengths, the count image and the sample counts of that level, plus the parameters -- held in buffers of its own, so
+ * that further layers of the frame (a light group a compositor asks for later; the previews of a progressive render between two refreshes of the
+ * selection) cost the estimate stage alone.  A selection belongs to the context it was created on, must be destroyed before it, and is left intact
+ * by every other call on that context.  Its buffers are allocated by the first _keep and only ever grow.
+ *   _keep:    bcd_hip_denoise_layers (same results, same bcd_hip_get_stats / bcd_hip_layer_spectral_inverses, same refusals), after which `sel` holds
+ *             the selection of every scale, replacing what it held.  A call that fails leaves `sel` invalid.
+ *   _denoise: the estimate stage on the kept selection for 1 .. BCD_HIP_MAX_LAYERS layers of the kept frame size (these need not be the layers of the
+ *             _keep call): no distance, mask, verification or marking kernel runs and no histogram is read.  d_nsamples NULL: the kept sample counts
+ *             -- every layer is then what bcd_hip_denoise_layers returns for it on the kept frame (same arithmetic, other order of the float atomics).
+ *             Other sample counts (W*H floats) replace the kept ones wherever the estimate stage reads counts (covariance / n, the sample-count
+ *             pyramid and the covariance pyramid weighted by it); the selection, the lists and the count images stay the kept ones.  Reusing a
+ *             selection on statistics that have moved on is an approximation the caller chooses.
+ *             Afterwards bcd_hip_get_stats reports the kept processed / fallback / similar_total / similarity_path with ms_similarity = ms_active = 0
+ *             and spectral_inverses summed over the layers of this call (bcd_hip_layer_spectral_inverses: one layer's share).
+ *             Refused before any device work (BCD_HIP_EINVAL and a message): a null or never-filled selection, one of another device, a layer count
+ *             out of range, null or overlapping images (the rules of bcd_hip_denoise_layers).
+ *   _info:    host only.  _read: one scale copied out in the layouts of bcd_hip_similarity_masks / bcd_hip_active_set (d_mask: w*h*words uint32,
+ *             d_nsim: w*h int32, d_state: w*h bytes, d_count: the count image, w*h int32); any pointer may be NULL; synchronises. */
+typedef struct bcd_hip_selection bcd_hip_selection;
+#define BCD_HIP_SELECTION_MAX_SCALES 16
+typedef struct bcd_hip_selection_scale {
+    int32_t width, height;
+    int64_t processed;        /* as bcd_hip_scale_stats */
+    int64_t fallback;
+    int64_t similar_total;
+    int32_t similarity_path;
+    int32_t reserved;
+} bcd_hip_selection_scale;
+/* (a struct tag, not a typedef: the entry point that fills it has the same name) */
+struct bcd_hip_selection_info {
+    int32_t valid;            /* 1: a _keep call has filled the selection */
+    int32_t W, H, D, nb_scales;
+    bcd_hip_params params;    /* of the _keep call */
+    int64_t device_bytes;     /* held by the selection */
+    bcd_hip_selection_scale scale[BCD_HIP_SELECTION_MAX_SCALES];
+};
+int  bcd_hip_selection_create(bcd_hip_ctx *ctx, bcd_hip_selection **sel);
+void bcd_hip_selection_destroy(bcd_hip_selection *sel);
+int  bcd_hip_denoise_layers_keep(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms, int W, int H, int D, int nb_scales,
+                                 const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, bcd_hip_selection *sel);
+int  bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, const bcd_hip_layer *layers, int nb_layers);
+int  bcd_hip_selection_info(const bcd_hip_selection *sel, struct bcd_hip_selection_info *out);
+int  bcd_hip_selection_read(bcd_hip_selection *sel, int scale, uint32_t *d_mask, int32_t *d_nsim, uint8_t *d_state, int32_t *d_count);
+
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
  * finalised colours the raw accumulators are returned (d_sum W*H*3 floats, d_count W*H int32), so
@@ -407,6 +453,9 @@ int  bcd_hip_accum_reset(bcd_hip_accum *acc);
 int  bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels);
 int  bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n);
 int  bcd_hip_accum_statistics(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist);
+/* the snapshot without the histograms: the three outputs have the bits of bcd_hip_accum_statistics, no bin is read or written (44 B in and 40 B out
+ * per pixel instead of 564 B at 20 bins) -- what bcd_hip_selection_denoise needs of a progressive render between two refreshes of the selection */
+int  bcd_hip_accum_moments(bcd_hip_accum *acc, float *d_nsamples, float *d_mean, float *d_cov);
 int  bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped);
 /* Splatting through a pixel reconstruction filter: samples at continuous positions go to every pixel of their
  * filter footprint, each with its own filter weight, by the rules of the accumulator: no float atomics, every pixel's contributions
