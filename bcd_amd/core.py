@@ -236,18 +236,19 @@ def denoise(col, ns, hist, cov, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, rand
 
 
 def denoise_layers(layers, ns, hist, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, zero_bad=False,
-                   prefilter_factor=0.0, size_mismatch_layer=0, after_clear=False):
+                   prefilter_factor=0.0, size_mismatch_layer=0, after_clear=False, prefilter_layers=False):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with colour layers: layers[0] = (colours, covariances) goes through DenoiserInputs, the others through
     addLayer.  Returns (ok, [output per layer]).  size_mismatch_layer > 0: that added layer gets a covariance image of the wrong size;
-    after_clear: clearLayers() and a second denoise() follow, whose result replaces the first output"""
+    after_clear: clearLayers() and a second denoise() follow, whose result replaces the first output; prefilter_layers -> setSpikePrefilterLayers: the
+    prefilter (prefilter_factor > 0) is accepted beside added layers and covers every layer"""
     H, W, D = hist.shape
     L = len(layers)
     cols = np.ascontiguousarray(np.stack([c for c, _ in layers]), np.float32)
     covs = np.ascontiguousarray(np.stack([v for _, v in layers]), np.float32)
     outs = np.zeros((L, H, W, 3), np.float32)
-    rc = lib().bcdcore_denoise_layers(_fp(cols), _fp(covs), _fp(ns), _fp(hist), W, H, D, nscales, L, C.c_float(tau), b, C.c_float(min_eig),
-                                      1 if random_order else 0, C.c_float(m), C.c_uint(seed), 1 if zero_bad else 0, C.c_float(prefilter_factor),
-                                      int(size_mismatch_layer), 1 if after_clear else 0, _fp(outs))
+    rc = lib().bcdcore_denoise_layers_ex(_fp(cols), _fp(covs), _fp(ns), _fp(hist), W, H, D, nscales, L, C.c_float(tau), b, C.c_float(min_eig),
+                                         1 if random_order else 0, C.c_float(m), C.c_uint(seed), 1 if zero_bad else 0, C.c_float(prefilter_factor),
+                                         int(size_mismatch_layer), 1 if after_clear else 0, 1 if prefilter_layers else 0, _fp(outs))
     return rc != 0, [outs[k] for k in range(L)]
 
 

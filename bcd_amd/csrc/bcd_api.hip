@@ -904,6 +904,8 @@ void bcd_hip_ctx_destroy(bcd_hip_ctx *ctx)
     if (ctx->tmp_lo.p) (void)hipFree(ctx->tmp_lo.p);
     for (DevBuf &hb : ctx->host_stage) if (hb.p) (void)hipFree(hb.p);
     for (DevBuf &hb : ctx->lay_host) if (hb.p) (void)hipFree(hb.p);
+    for (DevBuf &hb : ctx->lay_host_f) if (hb.p) (void)hipFree(hb.p);
+    if (ctx->spike_map.p) (void)hipFree(ctx->spike_map.p);
     for (int s = 0; s < MAX_SCALES; ++s)
         for (int k = 0; k < 5; ++k) if (ctx->pyr[s][k].p) (void)hipFree(ctx->pyr[s][k].p);
     for (int s = 0; s < MAX_SCALES; ++s)

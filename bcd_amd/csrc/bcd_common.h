@@ -93,6 +93,14 @@ struct BcdLayerTable {
     float *o[BCD_MAX_LAYERS];
 };
 
+// ---- spike prefilter through a source map (k_spike.hip) ---------------------------------------------------
+// One launch of k_spike_apply gathers up to BCD_SPIKE_MAX_IMAGES images of one depth; the image is blockIdx.y, the pointers travel by value.
+#define BCD_SPIKE_MAX_IMAGES 32
+struct BcdSpikeTable {
+    const float *src[BCD_SPIKE_MAX_IMAGES];
+    float *dst[BCD_SPIKE_MAX_IMAGES];
+};
+
 // ---- colour layers of the device accumulator (bcd_hip_accum_*_layers) ----------------------------------
 // The layer is blockIdx.y; the per-layer device pointers of one launch travel by value.  The beauty is layer 0 of bcd_hip_denoise_layers,
 // so an accumulator carries at most BCD_MAX_LAYERS - 1 further ones.

@@ -170,6 +170,8 @@ struct bcd_hip_ctx {
     DevBuf tmp_lo;
     DevBuf pyr[MAX_SCALES][5]; // colours, nsamples, hist, cov, out
     DevBuf lay_host[3];            // host-buffer entry point of the layers: device copies of the extra layers' colours, covariances, outputs
+    DevBuf lay_host_f[2];          // ... and, when the spike prefilter covers them, the second set of slices: their colours and covariances gathered through the map
+    DevBuf spike_map;              // the source map of the spike prefilter (bcd_hip_spike_filter_layers without a map of the caller's, the host-buffer layers): W*H int32
     DevBuf lay_pyr[MAX_SCALES][3]; // extra colour layers: colours, cov, out of every layer at that pyramid level, one slice per layer
     int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
     int layer_count = 0;                                // layers of that call (0: none yet)

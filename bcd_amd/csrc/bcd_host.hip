@@ -142,10 +142,11 @@ int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *cons
 }
 
 // bcd_hip_denoise_host_ex, and -- with `extra`: host images of further colour layers -- bcd_hip_denoise_layers_host: the primary inputs travel as they always
-// did (streamed, the histograms without their zeros), the extra layers as plain copies behind them
+// did (streamed, the histograms without their zeros), the extra layers as plain copies behind them.  filter_layers (bcd_hip_denoise_layers_host_ex): the
+// prefilter covers the extra layers too -- gathered on the device through the source map of the primary colours
 static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const float *h_ns, const float *h_hist, const float *h_cov,
                              int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out,
-                             const bcd_hip_host_layer *extra, int nb_extra)
+                             const bcd_hip_host_layer *extra, int nb_extra, bool filter_layers = false)
 {
     if (!ctx) return BCD_HIP_EINVAL;
     if (!h_colors || !h_ns || !h_hist || !h_cov || !h_out) return bad(ctx, "null image pointer");
@@ -194,6 +195,28 @@ static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const floa
                 return fail(BCD_HIP_EDEVICE);
             }
         }
+        if (prefilter && filter_layers) {
+            // The primary layer has been filtered above, line by line as it arrived.  The decision behind it is a function of the UNFILTERED primary colours,
+            // which are still resident (d[0]): it is taken once more as a source map (k_spike_map: 108 B read and 4 B written per pixel) and every extra
+            // layer's colours and covariances are gathered through it into a second set of slices, which the frame then reads.  No second trip over
+            // PCIe, and nothing in the upload schedule of the primary layer moves.
+            if (ensure(ctx, ctx->spike_map, np * sizeof(int32_t)) != BCD_HIP_OK) return fail(BCD_HIP_ENOMEM);
+            for (int i = 0; i < 2; ++i)
+                if (ensure(ctx, ctx->lay_host_f[i], (size_t)nb_extra * np * (i == 1 ? 6 : 3) * sizeof(float)) != BCD_HIP_OK) return fail(BCD_HIP_ENOMEM);
+            int32_t *d_map = (int32_t *)ctx->spike_map.p;
+            BcdSpikeTable tc = {}, tv = {};
+            for (int k = 0; k < nb_extra; ++k) {
+                tc.src[k] = lv.col[k]; tc.dst[k] = (float *)ctx->lay_host_f[0].p + k * np * 3;
+                tv.src[k] = lv.cov[k]; tv.dst[k] = (float *)ctx->lay_host_f[1].p + k * np * 6;
+                lv.col[k] = tc.dst[k]; lv.cov[k] = tv.dst[k];
+            }
+            if (bcd_launch_spike_map(d[0], W, H, opt->spike_factor, d_map, nullptr, ctx->stream) != hipSuccess ||
+                bcd_launch_spike_apply(tc, nb_extra, d_map, W, H, 3, ctx->stream) != hipSuccess ||
+                bcd_launch_spike_apply(tv, nb_extra, d_map, W, H, 6, ctx->stream) != hipSuccess) {
+                set_err(ctx, "the spike prefilter of the colour layers failed to launch");
+                return fail(BCD_HIP_EDEVICE);
+            }
+        }
     }
     {
         const int rc = denoise_impl(ctx, d[5], d[6], d[7], d[8], W, H, D, nb_scales, prm, d[4], nb_extra > 0 ? &lv : nullptr);
@@ -235,6 +258,24 @@ int bcd_hip_denoise_layers_host(bcd_hip_ctx *ctx, const float *h_ns, const float
         return BCD_HIP_EUNSUPPORTED;
     }
     return denoise_host_impl(ctx, layers[0].h_colors, h_ns, h_hist, layers[0].h_covariances, W, H, D, nb_scales, prm, opt, layers[0].h_out, layers + 1, nb_layers - 1);
+}
+
+int bcd_hip_denoise_layers_host_ex(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                                   const bcd_hip_layers_host_options *opt, const bcd_hip_host_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    bcd_hip_host_options o = { 0.f, 0 };
+    if (opt) { o.spike_factor = opt->spike_factor; o.zero_bad_values = opt->zero_bad_values; }
+    if (!opt || !opt->filter_layers || nb_layers < 2 || !(o.spike_factor > 0.f)) // nothing for the switch to do: the old call, with its refusal
+        return bcd_hip_denoise_layers_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, &o, layers, nb_layers);
+    if (!h_ns || !h_hist) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k) {
+        if (!layers[k].h_colors || !layers[k].h_covariances || !layers[k].h_out) return bad(ctx, "null image pointer in a layer");
+        for (int j = 0; j < k; ++j) if (layers[j].h_out == layers[k].h_out) return bad(ctx, "two layers share an output image");
+    }
+    return denoise_host_impl(ctx, layers[0].h_colors, h_ns, h_hist, layers[0].h_covariances, W, H, D, nb_scales, prm, &o, layers[0].h_out, layers + 1, nb_layers - 1, true);
 }
 
 int bcd_hip_last_upload_bytes(const bcd_hip_ctx *ctx, int64_t *hist_bytes, int64_t *hist_bytes_sent)

@@ -69,6 +69,10 @@ hipError_t bcd_launch_layers_downscale_avg(const BcdLayerTable &t, int layers, i
 hipError_t bcd_launch_layers_downscale_cov(const BcdLayerTable &t, int layers, const float *ns, int W, int H, hipStream_t st);
 hipError_t bcd_launch_layers_merge(const BcdLayerTable &t, int layers, int w, int h, int W, int H, hipStream_t st);
 
+// ---- k_spike.hip
+hipError_t bcd_launch_spike_map(const float *col, int W, int H, float factor, int32_t *map, int32_t *d_moved, hipStream_t st);
+hipError_t bcd_launch_spike_apply(const BcdSpikeTable &t, int n, const int32_t *map, int W, int H, int depth, hipStream_t st);
+
 // ---- k_active.hip
 hipError_t bcd_launch_active_init(const int32_t *nsim, int W, int H, int w, int row_begin, int row_end, float skip_prob, uint32_t seed, int row_offset, uint8_t *state,
                                   hipStream_t st);

@@ -2,6 +2,7 @@
 // All arithmetic is written in the reference's evaluation order and compiled with -ffp-contract=off,
 // so these kernels are bit-exact against the CPU path.
 #include "bcd_common.h"
+#include "bcd_spike.h"
 
 namespace {
 
@@ -295,39 +296,7 @@ __global__ void k_spike(const float *__restrict__ col, const float *__restrict__
     const bool in_row = c < W;
     const int ncols = min(64, W - c0);
     size_t dst = (size_t)l * W + min(c, W - 1), src = dst;
-    if (in_row) {
-    int cl = l < 1 ? 1 : (l > H - 2 ? H - 2 : l);
-    int cc = c < 1 ? 1 : (c > W - 2 ? W - 2 : c);
-    float v[3][9];
-    int k = 0;
-    for (int nl = cl - 1; nl <= cl + 1; ++nl)
-        for (int nc = cc - 1; nc <= cc + 1; ++nc, ++k) {
-            const float *px = col + ((size_t)nl * W + nc) * 3;
-            v[0][k] = px[0]; v[1][k] = px[1]; v[2][k] = px[2];
-        }
-    const float *me = col + ((size_t)l * W + c) * 3;
-    bool spike = false;
-    for (int ch = 0; ch < 3; ++ch) {
-        float total = 0.f;
-        for (int i = 0; i < 9; ++i) total += v[ch][i];
-        float avg = total / 9;
-        total = 0;
-        for (int i = 0; i < 9; ++i) total += (v[ch][i] - avg) * (v[ch][i] - avg);
-        float sd = sqrtf(total / 8);
-        spike = spike || (fabsf(me[ch] - avg) > factor * sd);
-    }
-    if (spike) {
-        int best = 0;
-        float bestd = -1.f;
-        for (int m = 0; m < 9; ++m) {
-            float tot = 0.f;
-            for (int i = 0; i < 9; ++i)
-                tot += fabsf(v[0][i] - v[0][m]) + fabsf(v[1][i] - v[1][m]) + fabsf(v[2][i] - v[2][m]);
-            if (bestd < 0 || tot < bestd) { bestd = tot; best = m; }
-        }
-        src = (size_t)(cl - 1 + best / 3) * W + (cc - 1 + best % 3);
-    }
-    }
+    if (in_row) src = bcd_spike_source(col, W, H, l, c, factor); // (bcd_spike.h: shared with k_spike_map)
     s_src[threadIdx.x] = (unsigned int)src; // (pixel indices fit 31 bits: checked by the host entry points)
     __syncthreads();
     const size_t row_base = (size_t)l * W + c0; // first destination pixel of the workgroup

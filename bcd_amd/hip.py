@@ -55,6 +55,24 @@ class HostOptions(C.Structure):
     _fields_ = [("spike_factor", C.c_float), ("zero_bad_values", C.c_int32)]
 
 
+class LayersHostOptions(C.Structure):
+    """bcd_hip_layers_host_options"""
+    _fields_ = [("spike_factor", C.c_float), ("zero_bad_values", C.c_int32), ("filter_layers", C.c_int32)]
+
+
+class HostLayer(C.Structure):
+    """bcd_hip_host_layer"""
+    _fields_ = [("h_colors", C.c_void_p), ("h_covariances", C.c_void_p), ("h_out", C.c_void_p)]
+
+
+class SpikeLayer(C.Structure):
+    """bcd_hip_spike_layer"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p), ("d_colors_out", C.c_void_p), ("d_covariances_out", C.c_void_p)]
+
+
+SPIKE_MAX_IMAGES = 32  # images of one bcd_hip_spike_apply call
+
+
 class HostStreamResult(C.Structure):
     """bcd_hip_host_stream_result"""
     _fields_ = [("rows_filtered", C.c_int32), ("tile_rows_done", C.c_int32), ("chunk_lines", C.c_int32), ("chunks_done", C.c_int32),
@@ -227,7 +245,8 @@ class ScaleStats(C.Structure):
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
     "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
-    "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host",
+    "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_denoise_layers_host_ex",
+    "bcd_hip_spike_map", "bcd_hip_spike_apply", "bcd_hip_spike_filter_layers",
     "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
     "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
@@ -407,6 +426,27 @@ class Context:
         opt = HostOptions(spike_factor, 1 if zero_bad_values else 0)
         self._chk(lib().bcd_hip_denoise_host_ex(self.h, f(col), f(ns), f(hist), f(cov), W, H, D, nscales, C.byref(prm), C.byref(opt), f(out)))
         return out
+
+    def denoise_layers_host(self, ns, hist, layers, nscales, prm, spike_factor=0.0, zero_bad_values=False, filter_layers=False):
+        """bcd_hip_denoise_layers_host_ex on NumPy images: `layers` is a list of (colours, covariances); layers[0] is the primary layer.  filter_layers:
+        the spike prefilter (spike_factor > 0) covers every layer, gathered through the source map of the primary colours; without it a factor beside
+        several layers is refused.  Returns the list of outputs"""
+        import numpy as np
+        H, W, D = hist.shape
+        layers = [(np.ascontiguousarray(c, np.float32), np.ascontiguousarray(v, np.float32)) for c, v in layers]
+        outs = [np.empty((H, W, 3), np.float32) for _ in layers]
+        arr = (HostLayer * max(1, len(layers)))()
+        for k, ((col, cov), out) in enumerate(zip(layers, outs)):
+            if col.shape != (H, W, 3) or cov.shape != (H, W, 6):
+                raise ValueError("layer %d: colours must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
+            arr[k].h_colors, arr[k].h_covariances, arr[k].h_out = col.ctypes.data, cov.ctypes.data, out.ctypes.data
+        f = lambda a: a.ctypes.data_as(_F)
+        opt = LayersHostOptions(spike_factor, 1 if zero_bad_values else 0, 1 if filter_layers else 0)
+        L = lib()
+        L.bcd_hip_denoise_layers_host_ex.argtypes = [_VP, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(LayersHostOptions),
+                                                     C.POINTER(HostLayer), C.c_int]
+        self._chk(L.bcd_hip_denoise_layers_host_ex(self.h, f(ns), f(hist), W, H, D, nscales, C.byref(prm), C.byref(opt), arr, len(layers)))
+        return outs
 
     def last_upload_bytes(self):
         """(bytes of the histogram image of the last denoise_host call, bytes of it that crossed PCIe)"""
@@ -695,6 +735,55 @@ class Context:
         self._chk(lib().bcd_hip_spike_filter(self.h, _dp(col), _dp(ns), _dp(hist), _dp(cov), W, H, D, C.c_float(factor),
                                              _dp(o[0]), _dp(o[1]), _dp(o[2]), _dp(o[3])))
         return o
+
+    def spike_map(self, col, factor, count=True):
+        """bcd_hip_spike_map -> (map: H x W int32 tensor of source pixel indices, moved: pixels with map[p] != p -- reading it synchronises; None
+        without `count`)"""
+        torch = self.torch
+        H, W, _ = col.shape
+        m = torch.empty((H, W), dtype=torch.int32, device=col.device)
+        moved = torch.empty(1, dtype=torch.int32, device=col.device) if count else None
+        L = lib()
+        L.bcd_hip_spike_map.argtypes = [_VP, _VP, C.c_int, C.c_int, C.c_float, _VP, _VP]
+        self._chk(L.bcd_hip_spike_map(self.h, _dp(col), W, H, factor, _dp(m), _dp(moved) if count else None))
+        return m, (int(moved.item()) if count else None)
+
+    def spike_apply(self, map, images, outs=None):
+        """bcd_hip_spike_apply: every image of the list (H x W x depth tensors of one depth, at most 32) gathered through the map in one launch.
+        Returns the outputs (`outs`: tensors to write into, optional)"""
+        images = list(images)
+        H, W = map.shape[:2]
+        depth = images[0].numel() // (H * W) if images else 1
+        if outs is None:
+            outs = [self.torch.empty_like(a) for a in images]
+        outs = list(outs)
+        L = lib()
+        L.bcd_hip_spike_apply.argtypes = [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int]
+        self._chk(L.bcd_hip_spike_apply(self.h, _dp(map), W, H, depth, self._ptr_list(images), self._ptr_list(outs), len(images)))
+        return outs
+
+    def spike_filter_layers(self, ns, hist, layers, factor, count=False, own_map=True):
+        """bcd_hip_spike_filter_layers: `layers` is a list of (colours, covariances); the map comes from layers[0]'s colours.  hist None: the form without
+        histograms.  Returns (ns, hist or None, [(colours, covariances), ...], map), all filtered copies; with `count` a fifth value, the moved pixels.
+        own_map False: the map stays in the context's scratch and None is returned in its place"""
+        torch = self.torch
+        layers = list(layers)
+        H, W = ns.shape[:2]
+        D = hist.shape[-1] if hist is not None else 0
+        o_ns = torch.empty_like(ns)
+        o_hist = torch.empty_like(hist) if hist is not None else None
+        outs = [(torch.empty_like(c), torch.empty_like(v)) for c, v in layers]
+        m = torch.empty((H, W), dtype=torch.int32, device=ns.device) if own_map else None
+        moved = torch.empty(1, dtype=torch.int32, device=ns.device) if count else None
+        arr = (SpikeLayer * max(1, len(layers)))()
+        for k, ((c, v), (oc, ov)) in enumerate(zip(layers, outs)):
+            arr[k].d_colors, arr[k].d_covariances, arr[k].d_colors_out, arr[k].d_covariances_out = _dp(c).value, _dp(v).value, _dp(oc).value, _dp(ov).value
+        L = lib()
+        L.bcd_hip_spike_filter_layers.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, C.POINTER(SpikeLayer), C.c_int, _VP, _VP]
+        self._chk(L.bcd_hip_spike_filter_layers(self.h, _dp(ns), _dp(hist) if hist is not None else None, W, H, D, factor, _dp(o_ns),
+                                                _dp(o_hist) if hist is not None else None, arr, len(layers), _dp(m) if own_map else None, _dp(moved) if count else None))
+        res = (o_ns, o_hist, outs, m)
+        return res + (int(moved.item()),) if count else res
 
     def accumulate_samples(self, samples, weights=None, nbins=20, gamma=2.2, maxval=2.5):
         """samples: (H, W, spp, 3) device tensor; weights: (H, W, spp) or None"""

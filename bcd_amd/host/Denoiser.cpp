@@ -80,9 +80,9 @@ namespace bcd
 			cerr << "Aborting denoising: colour layers are not available over several devices (row bands take one layer per call)" << endl;
 			return false;
 		}
-		if(m_prefilterThresholdStDevFactor > 0.f)
+		if(m_prefilterThresholdStDevFactor > 0.f && !m_prefilterLayers)
 		{
-			cerr << "Aborting denoising: the spike prefilter moves whole pixels by the primary colours and is not available with added colour layers" << endl;
+			cerr << "Aborting denoising: the spike prefilter moves whole pixels by the primary colours and is not available with added colour layers (setSpikePrefilterLayers(true) gathers every layer through its decision)" << endl;
 			return false;
 		}
 		const int w = m_inputs.m_pColors->getWidth(), h = m_inputs.m_pColors->getHeight();
@@ -291,7 +291,13 @@ namespace bcd
 					layers[k + 1].h_covariances = m_layers[k].m_pSampleCovariances->getDataPtr();
 					layers[k + 1].h_out = layerResults[k].getDataPtr();
 				}
-				rc = bcd_hip_denoise_layers_host(rSlot.m_pCtx, pIn[1], pIn[2], m_width, m_height, depth, i_nbOfScales, &prm, &opt, layers.data(), int(layers.size()));
+				if(m_prefilterLayers)
+				{	// the prefilter covers every layer: gathered on the device through the source map of the primary colours
+					bcd_hip_layers_host_options layersOpt = { opt.spike_factor, opt.zero_bad_values, 1 };
+					rc = bcd_hip_denoise_layers_host_ex(rSlot.m_pCtx, pIn[1], pIn[2], m_width, m_height, depth, i_nbOfScales, &prm, &layersOpt, layers.data(), int(layers.size()));
+				}
+				else
+					rc = bcd_hip_denoise_layers_host(rSlot.m_pCtx, pIn[1], pIn[2], m_width, m_height, depth, i_nbOfScales, &prm, &opt, layers.data(), int(layers.size()));
 			}
 			bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
 			if(rc != BCD_HIP_OK)
@@ -337,6 +343,7 @@ namespace bcd
 		engine.setSpikePrefilter(m_prefilterThresholdStDevFactor);
 		engine.setZeroBadOutputValues(m_zeroBadOutputValues);
 		engine.setLayers(m_layers);
+		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		const bool ok = engine.denoiseWithNbOfScales(m_nbOfScales);
 		m_parameters.m_nbOfCores = engine.getParameters().m_nbOfCores;
 		return ok;

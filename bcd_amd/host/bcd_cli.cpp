@@ -48,6 +48,7 @@ namespace
 		std::vector<int> m_devices = std::vector<int>(1, 0);
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
 		std::vector<Layer> m_layers; // --layer, in command-line order
+		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
 	};
 
 	const char* g_pProgramPath = "bcd_cli";
@@ -82,7 +83,10 @@ namespace
 		cout << "    --layer <color> <cov> <output>" << endl;
 		cout << "                         a further colour layer (light group, diffuse / specular pass, ...) of the same render: its mean colours and" << endl;
 		cout << "                         sample covariances, denoised with the similar patches of the -i image and written to <output>; repeatable" << endl;
-		cout << "                         (at most 15), shares -h; needs -p 0 and a single device" << endl;
+		cout << "                         (at most 15), shares -h; needs a single device, and -p 0 or --prefilter-layers" << endl;
+		cout << "    --prefilter-layers   with -p 1 (given or by default) and --layer: the spike prefilter decides on the -i colours which neighbour" << endl;
+		cout << "                         replaces a pixel, and every layer's colours and covariances are gathered through that decision on the device;" << endl;
+		cout << "                         no effect with -p 0" << endl;
 	}
 
 	bool badValue(const char* flag, const char* what)
@@ -99,6 +103,7 @@ namespace
 		{
 			const string flag = argv[i];
 			if(flag == "--help") { printUsage(); return false; }
+			if(flag == "--prefilter-layers") { a.m_prefilterLayers = true; continue; }
 			if(flag == "--layer")
 			{
 				if(i + 3 >= argc) { cout << "ERROR in program arguments: expecting <color.exr> <cov.exr> <output.exr> after --layer" << endl; return false; }
@@ -258,9 +263,9 @@ namespace
 			}
 			if(rLayer.m_outputPath == a.m_denoisedOutputFilePath) { cout << "ERROR in program arguments: layer output '" << rLayer.m_outputPath << "' is also the -o output" << endl; return false; }
 		}
-		if(!a.m_layers.empty() && a.m_prefilterSpikes)
+		if(!a.m_layers.empty() && a.m_prefilterSpikes && !a.m_prefilterLayers)
 		{
-			cout << "ERROR in program arguments: --layer is not available with the spike prefilter (it moves whole pixels by the -i colours): add -p 0" << endl;
+			cout << "ERROR in program arguments: --layer is not available with the spike prefilter (it moves whole pixels by the -i colours): add -p 0, or --prefilter-layers to gather every layer through its decision" << endl;
 			return false;
 		}
 		if(!a.m_layers.empty() && a.m_devices.size() > 1) { cout << "ERROR in program arguments: --layer is not available with several devices" << endl; return false; }
@@ -333,6 +338,7 @@ namespace
 		pSettings->setDevices(args.m_devices);
 		if(prefilterOnDevice)
 			pSettings->setSpikePrefilter(args.m_prefilterThresholdStDevFactor);
+		pSettings->setSpikePrefilterLayers(args.m_prefilterLayers);
 		pSettings->setZeroBadOutputValues(true); // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:470) before the download
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)

@@ -378,9 +378,10 @@ int bcdcore_denoise_ex(const float* col, const float* ns, const float* hist, con
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with `nbOfLayers` colour layers: layer 0 through DenoiserInputs / DenoiserOutputs, the others through
 /// addLayer.  cols / covs / outs: nbOfLayers images one behind the other.  sizeMismatchLayer > 0: that added layer gets a covariance image one
 /// line short (validation path).  afterClear != 0: clearLayers() and a second denoise() into outs[0] must still succeed.  Returns denoise()'s bool
-int bcdcore_denoise_layers(const float* cols, const float* covs, const float* ns, const float* hist, int W, int H, int D, int nscales, int nbOfLayers,
+/// prefilterLayers != 0: setSpikePrefilterLayers(true) -- the prefilter is accepted beside added layers and covers every layer
+int bcdcore_denoise_layers_ex(const float* cols, const float* covs, const float* ns, const float* hist, int W, int H, int D, int nscales, int nbOfLayers,
 		float tau, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int zeroBad, float prefilterFactor, int sizeMismatchLayer,
-		int afterClear, float* outs)
+		int afterClear, int prefilterLayers, float* outs)
 {
 	if(nbOfLayers < 1) return 0;
 	const size_t np = size_t(W) * H;
@@ -408,6 +409,7 @@ int bcdcore_denoise_layers(const float* cols, const float* covs, const float* ns
 	pSettings->setOrderSeed(seed);
 	pSettings->setZeroBadOutputValues(zeroBad != 0);
 	pSettings->setSpikePrefilter(prefilterFactor);
+	pSettings->setSpikePrefilterLayers(prefilterLayers != 0);
 	for(int k = 1; k < nbOfLayers; ++k)
 		pSettings->addLayer(&c[k], &v[k], &o[k]);
 	d->setInputs(in);
@@ -426,6 +428,14 @@ int bcdcore_denoise_layers(const float* cols, const float* covs, const float* ns
 		o[0].copyDataTo(outs);
 	}
 	return 1;
+}
+
+int bcdcore_denoise_layers(const float* cols, const float* covs, const float* ns, const float* hist, int W, int H, int D, int nscales, int nbOfLayers,
+		float tau, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int zeroBad, float prefilterFactor, int sizeMismatchLayer,
+		int afterClear, float* outs)
+{
+	return bcdcore_denoise_layers_ex(cols, covs, ns, hist, W, H, D, nscales, nbOfLayers, tau, b, minEig, randomOrder, skipProbability, seed, zeroBad, prefilterFactor,
+			sizeMismatchLayer, afterClear, 0, outs);
 }
 
 /// ONE MultiscaleDenoiser (or Denoiser), denoise() called twice with -r 0 and the given m_nbOfCores: the written-back core count must not

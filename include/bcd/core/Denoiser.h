@@ -19,7 +19,7 @@ namespace bcd
 	class HipEngineSettings
 	{
 	public:
-		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false) {}
+		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false) {}
 
 		/// seed of the visiting order of -r 1 (the reference seeds its shuffle from the wall clock, src/core/Denoiser.cpp:418)
 		void setOrderSeed(uint32_t i_seed) { m_orderSeed = i_seed; }
@@ -37,7 +37,8 @@ namespace bcd
 		/// patches, same processed pixels, one selection for all layers (bcd_hip_denoise_layers).  The DenoiserInputs colour and covariance
 		/// images are layer 0; every added layer brings its own mean colours (W x H x 3) and sample covariances (W x H x 6) and shares the
 		/// sample counts and histograms.  Non-owning pointers, like DenoiserInputs; the output is resized and overwritten.  At most
-		/// 15 added layers, one device, no spike prefilter.  With no added layer denoise() is what it always was.
+		/// 15 added layers, one device, and the spike prefilter only with setSpikePrefilterLayers(true).  With no added layer denoise() is
+		/// what it always was.
 		struct ColorLayer
 		{
 			const DeepImage<float>* m_pColors;
@@ -52,12 +53,18 @@ namespace bcd
 		void clearLayers() { m_layers.clear(); }
 		const std::vector<ColorLayer>& getLayers() const { return m_layers; }
 		void setLayers(const std::vector<ColorLayer>& i_rLayers) { m_layers = i_rLayers; }
+		/// true: a spike prefilter beside added colour layers is accepted and covers EVERY layer -- the filter decides from the primary
+		/// colours which neighbour replaces a pixel, and each layer's colours and covariances are gathered through that decision on the
+		/// device (bcd_hip_denoise_layers_host_ex).  false (default): the combination is refused, as it always was.
+		void setSpikePrefilterLayers(bool i_enabled) { m_prefilterLayers = i_enabled; }
+		bool getSpikePrefilterLayers() const { return m_prefilterLayers; }
 
 	protected:
 		uint32_t m_orderSeed;
 		std::vector<int> m_devices;
 		float m_prefilterThresholdStDevFactor;
 		bool m_zeroBadOutputValues;
+		bool m_prefilterLayers;
 		std::vector<ColorLayer> m_layers;
 	};
 

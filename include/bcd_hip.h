@@ -293,10 +293,20 @@ int bcd_hip_denoise_host_ex(bcd_hip_ctx *ctx, const float *h_colors, const float
                             int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_host_options *opt, float *h_out);
 /* bcd_hip_denoise_layers for host images (layers[0] is the primary layer: its images and the shared inputs travel like those of
  * bcd_hip_denoise_host_ex, the other layers as plain copies).  opt->zero_bad_values applies to every output; the spike prefilter moves whole pixels
- * by the first layer's colours and is refused (BCD_HIP_EUNSUPPORTED) with more than one layer. */
+ * by the first layer's colours and is refused (BCD_HIP_EUNSUPPORTED) with more than one layer by this call (bcd_hip_denoise_layers_host_ex offers it). */
 typedef struct { const float *h_colors; const float *h_covariances; float *h_out; } bcd_hip_host_layer;
 int bcd_hip_denoise_layers_host(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, int W, int H, int D, int nb_scales,
                                 const bcd_hip_params *prm, const bcd_hip_host_options *opt, const bcd_hip_host_layer *layers, int nb_layers);
+/* The same with the spike prefilter over EVERY layer, on request.  filter_layers == 0 (or one layer, or no factor): bcd_hip_denoise_layers_host, its
+ * refusal included.  filter_layers != 0 with spike_factor > 0 and several layers: the primary layer travels and is filtered as in
+ * bcd_hip_denoise_host_ex; the other layers are uploaded as plain copies, and once the frame has arrived the source map of the UNFILTERED primary
+ * colours (still resident) gathers their colours and covariances into a second set of device slices, which the frame reads -- no second trip over
+ * the link.  The outputs are those of bcd_hip_spike_filter_layers followed by bcd_hip_denoise_layers on resident copies (same arithmetic; the float
+ * atomics of the aggregation may arrive in another order); layer 0 is what bcd_hip_denoise_host_ex returns for it with the same factor. */
+typedef struct { float spike_factor; int32_t zero_bad_values; int32_t filter_layers; } bcd_hip_layers_host_options;
+int bcd_hip_denoise_layers_host_ex(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, int W, int H, int D, int nb_scales,
+                                   const bcd_hip_params *prm, const bcd_hip_layers_host_options *opt,
+                                   const bcd_hip_host_layer *layers, int nb_layers);
 
 /* The histogram image of the last bcd_hip_denoise_host(_ex) call: its size, and the bytes that crossed the link.  On frames of >= 256 lines the
  * image travels without its zeros -- host threads pack every piece into one bit per value ("is not +0.0f", a test on the bit pattern: lossless)
@@ -427,6 +437,32 @@ int bcd_hip_merge(bcd_hip_ctx *ctx, float *d_hi, int W, int H, const float *d_lo
 int bcd_hip_spike_filter(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples,
                          const float *d_histograms, const float *d_covariances, int W, int H, int D, float factor,
                          float *d_colors_out, float *d_nsamples_out, float *d_histograms_out, float *d_covariances_out);
+/* ---- the spike prefilter through a source map ------------------------------------------------
+ * SpikeRemovalFilter::filter decides from the colours alone which neighbour replaces a pixel and then copies that neighbour's whole pixel
+ * (src/core/SpikeRemovalFilter.cpp:61-72).  The decision, kept as an image, prefilters any number of further images consistently: the
+ * colour layers of a frame, or the moments of a preview that reads no histogram.
+ * Source map: M is an int32 image of W*H entries, W, H >= 3.  M[p] is the pixel (line * W + col) that SpikeRemovalFilter::filter with
+ *   factor f copies into p, decided from the colour image given; M[p] = p where the pixel is not a spike, and where the median neighbour
+ *   is the pixel itself.  It is the source index bcd_hip_spike_filter copies from, nothing else (one device function serves both).
+ *   `moved` is the number of pixels with M[p] != p.
+ * Apply: dst[p * depth + z] = src[M[p] * depth + z] for every p and z < depth.  A copy of bits: NaN payloads and -0 survive.  Any depth
+ *   >= 1; out of place (maps have chains: a moved pixel whose source is itself moved).  An entry of M outside [0, W*H) is read as p, so a
+ *   bad map cannot make the device read outside the images.
+ *   _map:    d_colors W*H*3 floats, d_map W*H int32, d_moved NULL or one device int32 (zeroed by the call, then counted into).
+ *   _apply:  nb_images (1..32) images of one depth in one launch; d_src / d_dst are HOST arrays of nb_images device pointers.
+ *   _filter_layers: the map from layers[0].d_colors, then _apply on the sample counts, the histograms (when given: d_histograms and
+ *            o_histograms are both NULL or both not; D is then not read), all colours (one launch) and all covariances (one launch),
+ *            1 <= nb_layers <= BCD_HIP_MAX_LAYERS.  With histograms, the sample counts, the histograms and layer 0 have the bits of
+ *            bcd_hip_spike_filter's four outputs.  d_map NULL: a scratch map of the context (grown on first use); d_moved as for _map.
+ * Everything is enqueued on the context's stream; no call synchronises.  Checked before any device work (BCD_HIP_EINVAL and a message):
+ * null pointers, W or H < 3, W*H >= 2^31, depth < 1, the image and layer counts, d_histograms / o_histograms null without the other, an
+ * output equal to or overlapping an input, the map or another output. */
+int bcd_hip_spike_map(bcd_hip_ctx *ctx, const float *d_colors, int W, int H, float factor, int32_t *d_map, int32_t *d_moved /* NULL or one device int32 */);
+int bcd_hip_spike_apply(bcd_hip_ctx *ctx, const int32_t *d_map, int W, int H, int depth, const float *const *d_src, float *const *d_dst, int nb_images /* 1..32 */);
+typedef struct { const float *d_colors, *d_covariances; float *d_colors_out, *d_covariances_out; } bcd_hip_spike_layer;
+int bcd_hip_spike_filter_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms /* NULL: no histogram */, int W, int H, int D, float factor,
+                                float *o_nsamples, float *o_histograms /* NULL iff d_histograms is */, const bcd_hip_spike_layer *layers, int nb_layers /* 1..16 */,
+                                int32_t *d_map /* NULL: the context's scratch */, int32_t *d_moved /* NULL or device int32 */);
 /* SamplesAccumulator::addSample + getSamplesStatistics for a whole frame   src/core/SamplesAccumulator.cpp:44-141
  * (lets a GPU renderer keep the statistics in HBM).  d_samples: W*H*spp*3 floats, the spp samples of a pixel contiguous
  * and in accumulation order; d_weights: W*H*spp floats or NULL (all 1).  Outputs in DeepImage layout, hist depth 3*nb_bins. */
