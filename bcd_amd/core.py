@@ -252,6 +252,22 @@ def denoise_layers(layers, ns, hist, nscales=1, tau=1.0, b=6, min_eig=1e-8, rand
     return rc != 0, [outs[k] for k in range(L)]
 
 
+def denoise_moments(layers, ns, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, zero_bad=False, prefilter_factor=0.0,
+                    prefilter_layers=False, var_floor=1e-8, devices=None):
+    """bcd::Denoiser / bcd::MultiscaleDenoiser with setMomentSelection(true, var_floor): no histogram image; layers[0] = (colours, covariances) is the
+    guide and goes through DenoiserInputs, the others through addLayer.  Returns (ok, [output per layer])"""
+    H, W = ns.shape[0], ns.shape[1]
+    L = len(layers)
+    cols = np.ascontiguousarray(np.stack([c for c, _ in layers]), np.float32)
+    covs = np.ascontiguousarray(np.stack([v for _, v in layers]), np.float32)
+    outs = np.zeros((L, H, W, 3), np.float32)
+    devs = (C.c_int * len(devices))(*devices) if devices else None
+    rc = lib().bcdcore_denoise_moments(_fp(cols), _fp(covs), _fp(np.ascontiguousarray(ns, np.float32)), W, H, nscales, L, C.c_float(tau), b, C.c_float(min_eig),
+                                       1 if random_order else 0, C.c_float(m), C.c_uint(seed), 1 if zero_bad else 0, C.c_float(prefilter_factor),
+                                       1 if prefilter_layers else 0, C.c_float(var_floor), devs, len(devices) if devices else 0, _fp(outs))
+    return rc != 0, [outs[k] for k in range(L)]
+
+
 def denoise_reuse(col, ns, hist, cov, nscales=3, b=6, nb_of_cores=0):
     """one IDenoiser object, denoise() twice with -r 0: (ok, first output, second output, (m_nbOfCores after call 1, after call 2))"""
     H, W, D = hist.shape

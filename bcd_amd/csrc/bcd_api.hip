@@ -156,6 +156,23 @@ int similarity_redo_mode(Work &wk)
     return (flag == 0 && other_count) ? 3 : 1; // (a void launch has no meaningful list count: other_count alone decides)
 }
 
+// an event pair around the distance kernel of a similarity pass (bcd_hip_kernel_time); both stay null once MAX_EVENT_PAIRS are in use
+int timing_events(bcd_hip_ctx *ctx, Work &wk, hipEvent_t *e0, hipEvent_t *e1)
+{
+    *e0 = *e1 = nullptr;
+    if (wk.ev_used >= MAX_EVENT_PAIRS) return BCD_HIP_OK;
+    if (wk.ev_used == (int)wk.ev_pool.size()) {
+        hipEvent_t a, c;
+        HIPCHK(ctx, hipEventCreate(&a));
+        HIPCHK(ctx, hipEventCreate(&c));
+        wk.ev_pool.emplace_back(a, c);
+    }
+    *e0 = wk.ev_pool[wk.ev_used].first;
+    *e1 = wk.ev_pool[wk.ev_used].second;
+    ++wk.ev_used;
+    return BCD_HIP_OK;
+}
+
 // exact_mode: 0 = production kernels, flags checked here (one stream synchronisation); 1 = exact kernels with the compiler's division;
 // 2 = production kernels, flags copied to wk.h_counters->flags but NOT checked: the caller validates after its own
 // synchronisation with similarity_needs_redo() / similarity_redo_mode(); 3 = like 2 with the general (non-uniform) formula forced.
@@ -170,17 +187,7 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
     RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
     RCCHK(ensure(ctx, wk.fwd, npix * ((nd + 31) / 32) * sizeof(uint32_t)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (wk.ev_used < MAX_EVENT_PAIRS) {
-        if (wk.ev_used == (int)wk.ev_pool.size()) {
-            hipEvent_t a, c;
-            HIPCHK(ctx, hipEventCreate(&a));
-            HIPCHK(ctx, hipEventCreate(&c));
-            wk.ev_pool.emplace_back(a, c);
-        }
-        e0 = wk.ev_pool[wk.ev_used].first;
-        e1 = wk.ev_pool[wk.ev_used].second;
-        ++wk.ev_used;
-    }
+    RCCHK(timing_events(ctx, wk, &e0, &e1));
     RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
     Counters::Flags *d_flag = &wk.d_counters()->flags, *h_flag = &wk.h_counters->flags;
     // planes of exactly this problem already computed by the caller (its launches raised the flags in d_flag[0] themselves)?
@@ -276,6 +283,38 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         if (h_flag->range != 0)
             HIPCHK(ctx, bcd_launch_pairdist(d_hist, d_ns, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, 0, &d_flag->range, 0.f, wk.stream));
     }
+    HIPCHK(ctx, bcd_launch_masks((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask, d_count, (uint32_t *)wk.fwd.p, wk.stream,
+                                 nullptr, nullptr, nullptr, 0));
+    return BCD_HIP_OK;
+}
+
+// The selection from means and covariances: the exact-path planes from the guide's colours and per-pixel covariances
+// (k_pairdist_moments), then the mask kernels of the exact histogram pass.  No flag is raised and nothing is ever redone: the pass enters
+// mono_accumulate's loop the way similarity(..., exact_mode = 1) does.  d_pixcov must be complete on wk.stream (a frame: wk.ev_pixcov).
+int similarity_moments(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixcov, int W, int H, int w, int b, float tau, float var_floor,
+                       uint32_t *d_mask, int32_t *d_count)
+{
+    const size_t npix = (size_t)W * H;
+    const int nd = bcd_delta_count(b);
+    RCCHK(ensure(ctx, wk.T, npix * nd * sizeof(float)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
+    RCCHK(ensure(ctx, wk.fwd, npix * ((nd + 31) / 32) * sizeof(uint32_t)));
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    // the planes of the workspace are this pass's from here on: planes a host-stream caller computed ahead are gone, and these are never noted as ready
+    wk.planes.ready = false;
+    wk.clean_flags = false; // (no flag word is used: the next histogram pass clears its own)
+    Counters::Flags *h_flag = &wk.h_counters->flags;
+    h_flag->range = 0;
+    h_flag->other_count = 0;
+    h_flag->borderline = 0;
+    wk.border_capacity = 0;
+    wk.ratio_used = false;
+    wk.speculated = false;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RCCHK(timing_events(ctx, wk, &e0, &e1));
+    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    HIPCHK(ctx, bcd_launch_pairdist_moments(d_colors, d_pixcov, W, H, b, var_floor, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
     HIPCHK(ctx, bcd_launch_masks((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask, d_count, (uint32_t *)wk.fwd.p, wk.stream,
                                  nullptr, nullptr, nullptr, 0));
     return BCD_HIP_OK;
@@ -642,8 +681,14 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     const bool speculate = marking && w == 1;
     const long long REDO = 1ll << 40;
     bool estimated = false;
-    for (int attempt = 0, mode = 2; attempt < 4; ++attempt) { // production kernels; if they complain: general sample counts (RATIO form, then the reference's operations), then exact kernels
-        RCCHK(similarity(ctx, wk, d_hist, d_ns, W, H, D, w, b, prm->hist_dist_threshold, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p, mode));
+    const bool moments = ctx->moments.on; // (bcd_hip_denoise_moments: one pass that needs no verdict, like the exact kernels)
+    for (int attempt = 0, mode = moments ? 1 : 2; attempt < 4; ++attempt) { // production kernels; if they complain: general sample counts (RATIO form, then the reference's operations), then exact kernels
+        if (moments) {
+            HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_pixcov, 0)); // the distance kernel reads the guide's per-pixel covariances (side stream)
+            RCCHK(similarity_moments(ctx, wk, d_colors, (const float *)wk.pixcov.p, W, H, w, b, prm->hist_dist_threshold, ctx->moments.var_floor, (uint32_t *)wk.mask.p,
+                                     (int32_t *)wk.nsim.p));
+        } else
+            RCCHK(similarity(ctx, wk, d_hist, d_ns, W, H, D, w, b, prm->hist_dist_threshold, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p, mode));
         if (prof && attempt == 0) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
         if (!speculate) {
             RCCHK(active_set(ctx, wk, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, W, H, w, b, row_begin, row_end,
@@ -714,7 +759,7 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     int64_t ns = 0, nw = 0, tot = 0;
     bayes_counts(wk, &ns, &nw, &tot);
     st.processed = ns + nw; st.fallback = nw; st.similar_total = tot;
-    st.similarity_path = wk.border_capacity > 0 ? (wk.ratio_used ? 2 : 1) : 0;
+    st.similarity_path = moments ? 3 : wk.border_capacity > 0 ? (wk.ratio_used ? 2 : 1) : 0;
     st.borderline_pairs = wk.border_capacity > 0 ? wk.h_counters->flags.borderline : 0;
     st.cu_share = estimate_share_pct(ctx, wk);
     st.spectral_inverses = wk.h_counters->lists.spectral;
@@ -744,7 +789,7 @@ int build_level(bcd_hip_ctx *ctx, const float *col, const float *ns, const float
 {
     HIPCHK(ctx, bcd_launch_downscale(1, col, W, H, 3, (float *)lvl[0].p, st));
     HIPCHK(ctx, bcd_launch_downscale(0, ns, W, H, 1, (float *)lvl[1].p, st));
-    HIPCHK(ctx, bcd_launch_downscale(0, hs, W, H, D, (float *)lvl[2].p, st));
+    if (hs) HIPCHK(ctx, bcd_launch_downscale(0, hs, W, H, D, (float *)lvl[2].p, st)); // (null: a selection from means and covariances has no histogram level)
     HIPCHK(ctx, bcd_launch_downscale_cov(cv, ns, W, H, (float *)lvl[3].p, st));
     return BCD_HIP_OK;
 }
@@ -1004,8 +1049,9 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
                  int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out, const LayerView *lv0)
 {
     if (!ctx) return BCD_HIP_EINVAL;
-    if (!d_colors || !d_ns || !d_hist || !d_cov || !d_out) return bad(ctx, "null image pointer"); // Denoiser.cpp:266-293
-    RCCHK(check_params(ctx, W, H, D, prm));
+    const bool moments = ctx->moments.on; // (bcd_hip_denoise_moments: d_hist is null and D is 0)
+    if (!d_colors || !d_ns || (!d_hist && !moments) || !d_cov || !d_out) return bad(ctx, "null image pointer"); // Denoiser.cpp:266-293
+    RCCHK(check_params(ctx, W, H, moments ? 1 : D, prm));
     if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
     DEVICE_GUARD(ctx);
     const int E = lv0 ? lv0->n : 0; // extra layers
@@ -1028,10 +1074,10 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
         size_t np = (size_t)ws[s] * hh[s];
         RCCHK(ensure(ctx, ctx->pyr[s][0], np * 3 * sizeof(float)));
         RCCHK(ensure(ctx, ctx->pyr[s][1], np * sizeof(float)));
-        RCCHK(ensure(ctx, ctx->pyr[s][2], np * D * sizeof(float)));
+        if (!moments) RCCHK(ensure(ctx, ctx->pyr[s][2], np * D * sizeof(float)));
         RCCHK(ensure(ctx, ctx->pyr[s][3], np * 6 * sizeof(float)));
         RCCHK(ensure(ctx, ctx->pyr[s][4], np * 3 * sizeof(float)));
-        col[s] = (float *)ctx->pyr[s][0].p; ns[s] = (float *)ctx->pyr[s][1].p; hs[s] = (float *)ctx->pyr[s][2].p;
+        col[s] = (float *)ctx->pyr[s][0].p; ns[s] = (float *)ctx->pyr[s][1].p; hs[s] = moments ? nullptr : (float *)ctx->pyr[s][2].p;
         cv[s] = (float *)ctx->pyr[s][3].p; out[s] = (float *)ctx->pyr[s][4].p;
     }
     std::vector<LayerView> lvs(E ? nb_scales : 0); // the extra layers at every pyramid level
@@ -1057,7 +1103,7 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
         // The coarse scales' share of the CU slots (bayes()) follows the previous call on the same geometry: they should be through when
         // the finest scale is at 80 - 92 % of its chain -- earlier means their persistent kernels took more room than they needed next to
         // the finest scale's short kernels, later means they have become the critical path.  Small steps down, larger ones up.
-        const int64_t key = ((int64_t)W << 40) ^ ((int64_t)H << 20) ^ ((int64_t)nb_scales << 12) ^ ((int64_t)prm->search_radius << 4) ^ (prm->marked_skip_probability > 0.f) ^ ((int64_t)E << 56);
+        const int64_t key = ((int64_t)W << 40) ^ ((int64_t)H << 20) ^ ((int64_t)nb_scales << 12) ^ ((int64_t)prm->search_radius << 4) ^ (prm->marked_skip_probability > 0.f) ^ ((int64_t)E << 56) ^ ((int64_t)moments << 62);
         if (key != ctx->share_key) { ctx->coarse_share = 25; ctx->share_key = key; }
         const auto t_start = std::chrono::steady_clock::now();
         double t_done[MAX_SCALES] = { 0 };
@@ -1138,15 +1184,16 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
 }
 
 // the refusals of bcd_hip_denoise_layers (and of bcd_hip_denoise_layers_keep): everything is checked before any device work
+// (no_hist: the call of bcd_hip_denoise_moments -- there is no histogram image, d_hist and D are not looked at)
 int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
-                      int nb_layers)
+                      int nb_layers, bool no_hist)
 {
-    if (!d_ns || !d_hist) return bad(ctx, "null image pointer");
+    if (!d_ns || (!d_hist && !no_hist)) return bad(ctx, "null image pointer");
     if (!layers) return bad(ctx, "null layer list");
     if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
     for (int k = 0; k < nb_layers; ++k)
         if (!layers[k].d_colors || !layers[k].d_covariances || !layers[k].d_out) return bad(ctx, "null image pointer in a layer");
-    RCCHK(check_params(ctx, W, H, D, prm));
+    RCCHK(check_params(ctx, W, H, no_hist ? 1 : D, prm));
     if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
     for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
         ws /= 2; hs /= 2;
@@ -1160,7 +1207,7 @@ int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
         };
         for (int k = 0; k < nb_layers; ++k) {
             const float *o = layers[k].d_out;
-            if (overlap(o, npix * 3, d_ns, npix) || overlap(o, npix * 3, d_hist, npix * D)) return bad(ctx, "a layer's output overlaps the sample counts or the histograms");
+            if (overlap(o, npix * 3, d_ns, npix) || (!no_hist && overlap(o, npix * 3, d_hist, npix * D))) return bad(ctx, "a layer's output overlaps the sample counts or the histograms");
             for (int j = 0; j < nb_layers; ++j) {
                 if (overlap(o, npix * 3, layers[j].d_colors, npix * 3) || overlap(o, npix * 3, layers[j].d_covariances, npix * 6))
                     return bad(ctx, "a layer's output overlaps an input image");
@@ -1184,6 +1231,15 @@ int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_h
 {
     if (!ctx) return BCD_HIP_EINVAL;
     RCCHK(check_layers_call(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers)); // everything is checked before any device work
+    return denoise_layers_checked(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
+}
+
+} // extern "C"
+
+// bcd_hip_denoise_layers behind its checks (bcd_hip_denoise_moments arrives here with checks of its own, ctx->moments set, no histograms and D = 0)
+int denoise_layers_checked(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                           const bcd_hip_layer *layers, int nb_layers)
+{
     LayerView lv;
     lv.n = nb_layers - 1;
     for (int k = 1; k < nb_layers; ++k) { lv.col[k - 1] = layers[k].d_colors; lv.cov[k - 1] = layers[k].d_covariances; lv.out[k - 1] = layers[k].d_out; }
@@ -1194,6 +1250,8 @@ int bcd_hip_denoise_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_h
     ctx->layer_count = nb_layers;
     return BCD_HIP_OK;
 }
+
+extern "C" {
 
 int bcd_hip_layer_spectral_inverses(const bcd_hip_ctx *ctx, int scale, int layer, int32_t *count)
 {
@@ -1397,6 +1455,47 @@ int bcd_hip_window_distances(bcd_hip_ctx *ctx, const float *d_hist, const float 
     RCCHK(ensure(ctx, ctx->main.Cn, npix * nd));
     RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
     HIPCHK(ctx, bcd_launch_pairdist(d_hist, d_ns, W, H, D, b, (float *)ctx->main.T.p, (uint8_t *)ctx->main.Cn.p, 0, nullptr, 0.f, ctx->stream));
+    HIPCHK(ctx, bcd_launch_window_distances((const float *)ctx->main.T.p, (const uint8_t *)ctx->main.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BCD_HIP_OK;
+}
+
+namespace {
+// the refusals the two stage calls of the moment selection share
+int check_moments_stage(bcd_hip_ctx *ctx, int W, int H, int w, int b, float var_floor)
+{
+    if (!(var_floor >= 0.f) || !std::isfinite(var_floor)) return bad(ctx, "the variance floor must be finite and not negative");
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    return check_params(ctx, W, H, 1, &p);
+}
+} // namespace
+
+int bcd_hip_similarity_masks_moments(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixcov, int W, int H, int w, int b, float tau, float var_floor,
+                                     uint32_t *d_mask, int32_t *d_count)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_colors || !d_pixcov || !d_mask || !d_count) return bad(ctx, "bad argument");
+    RCCHK(check_moments_stage(ctx, W, H, w, b, var_floor));
+    DEVICE_GUARD(ctx);
+    return similarity_moments(ctx, ctx->main, d_colors, d_pixcov, W, H, w, b, tau, var_floor, d_mask, d_count);
+}
+
+int bcd_hip_window_distances_moments(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixcov, int W, int H, int w, int b, float var_floor, int line, int col,
+                                     float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_colors || !d_pixcov || !h_out) return bad(ctx, "bad argument");
+    RCCHK(check_moments_stage(ctx, W, H, w, b, var_floor));
+    if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
+    DEVICE_GUARD(ctx);
+    const size_t npix = (size_t)W * H;
+    const int nd = bcd_delta_count(b), n = (2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, ctx->main.T, npix * nd * sizeof(float)));
+    RCCHK(ensure(ctx, ctx->main.Cn, count_plane_bytes(npix, nd)));
+    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
+    ctx->main.planes.ready = false; // (the workspace's planes are overwritten)
+    HIPCHK(ctx, bcd_launch_pairdist_moments(d_colors, d_pixcov, W, H, b, var_floor, (float *)ctx->main.T.p, (uint8_t *)ctx->main.Cn.p, ctx->stream));
     HIPCHK(ctx, bcd_launch_window_distances((const float *)ctx->main.T.p, (const uint8_t *)ctx->main.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

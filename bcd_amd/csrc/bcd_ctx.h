@@ -176,6 +176,8 @@ struct bcd_hip_ctx {
     int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
     int layer_count = 0;                                // layers of that call (0: none yet)
     bcd_hip_selection *keep = nullptr;                  // bcd_hip_denoise_layers_keep in progress: every scale leaves its selection here (mono_accumulate)
+    // bcd_hip_denoise_moments in progress: every scale selects from its guide's colours and per-pixel covariances (similarity_moments); no histogram is read
+    struct { bool on = false; float var_floor = 0.f; } moments;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
     hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
@@ -258,7 +260,9 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
                  const bcd_hip_params *prm, float *d_out, const LayerView *lv0);
 int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream);
 int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
-                      int nb_layers);
+                      int nb_layers, bool no_hist = false);
+int denoise_layers_checked(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                           const bcd_hip_layer *layers, int nb_layers);
 int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state, const float *const *pixcov,
                   float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral, const KeptLists *kept = nullptr);
 int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &coarse, const float *ns_fine, int W, int H, hipStream_t st);

@@ -278,6 +278,66 @@ int bcd_hip_denoise_layers_host_ex(bcd_hip_ctx *ctx, const float *h_ns, const fl
     return denoise_host_impl(ctx, layers[0].h_colors, h_ns, h_hist, layers[0].h_covariances, W, H, D, nb_scales, prm, &o, layers[0].h_out, layers + 1, nb_layers - 1, true);
 }
 
+// bcd_hip_denoise_moments for host images: plain uploads into the context's grow-only device copies, the resident call, downloads.  Nothing is streamed in:
+// 24 + 36 L bytes per pixel travel instead of the histogram image.
+int bcd_hip_denoise_moments_host(bcd_hip_ctx *ctx, const float *h_ns, int W, int H, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layers_host_options *opt,
+                                 float var_floor, const bcd_hip_host_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    // ---- everything is checked before any device work
+    if (!h_ns) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k) {
+        if (!layers[k].h_colors || !layers[k].h_covariances || !layers[k].h_out) return bad(ctx, "null image pointer in a layer");
+        for (int j = 0; j < k; ++j) if (layers[j].h_out == layers[k].h_out) return bad(ctx, "two layers share an output image");
+    }
+    if (!(var_floor >= 0.f) || !std::isfinite(var_floor)) return bad(ctx, "the variance floor must be finite and not negative");
+    const bool prefilter = opt && opt->spike_factor > 0.f;
+    if (prefilter && nb_layers > 1 && !opt->filter_layers) {
+        set_err(ctx, "the spike prefilter moves whole pixels by the first layer's colours: it is not available with several layers");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    RCCHK(check_params(ctx, W, H, 1, prm));
+    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
+        ws /= 2; hs /= 2;
+        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
+    }
+    if (prefilter && (W < 3 || H < 3)) return bad(ctx, "image smaller than 3x3");
+    DEVICE_GUARD(ctx);
+    const size_t np = (size_t)W * H, f = sizeof(float);
+    const int L = nb_layers;
+    RCCHK(ensure(ctx, ctx->host_stage[1], np * f));
+    for (int i = 0; i < 3; ++i) RCCHK(ensure(ctx, ctx->lay_host[i], (size_t)L * np * (i == 1 ? 6 : 3) * f));
+    const float *d_ns = (const float *)ctx->host_stage[1].p;
+    bcd_hip_layer dl[BCD_HIP_MAX_LAYERS];
+    HIPCHK(ctx, hipMemcpyAsync(ctx->host_stage[1].p, h_ns, np * f, hipMemcpyHostToDevice, ctx->stream));
+    for (int k = 0; k < L; ++k) {
+        float *dc = (float *)ctx->lay_host[0].p + k * np * 3, *dv = (float *)ctx->lay_host[1].p + k * np * 6;
+        HIPCHK(ctx, hipMemcpyAsync(dc, layers[k].h_colors, np * 3 * f, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(dv, layers[k].h_covariances, np * 6 * f, hipMemcpyHostToDevice, ctx->stream));
+        dl[k].d_colors = dc; dl[k].d_covariances = dv; dl[k].d_out = (float *)ctx->lay_host[2].p + k * np * 3;
+    }
+    if (prefilter) { // the source map of the first layer's colours moves the sample counts and every layer on the resident copies: no histogram to move
+        RCCHK(ensure(ctx, ctx->host_stage[6], np * f));
+        for (int i = 0; i < 2; ++i) RCCHK(ensure(ctx, ctx->lay_host_f[i], (size_t)L * np * (i == 1 ? 6 : 3) * f));
+        bcd_hip_spike_layer sl[BCD_HIP_MAX_LAYERS];
+        for (int k = 0; k < L; ++k) {
+            sl[k].d_colors = dl[k].d_colors; sl[k].d_covariances = dl[k].d_covariances;
+            sl[k].d_colors_out = (float *)ctx->lay_host_f[0].p + k * np * 3; sl[k].d_covariances_out = (float *)ctx->lay_host_f[1].p + k * np * 6;
+            dl[k].d_colors = sl[k].d_colors_out; dl[k].d_covariances = sl[k].d_covariances_out;
+        }
+        RCCHK(bcd_hip_spike_filter_layers(ctx, d_ns, nullptr, W, H, 0, opt->spike_factor, (float *)ctx->host_stage[6].p, nullptr, sl, L, nullptr, nullptr));
+        d_ns = (const float *)ctx->host_stage[6].p;
+    }
+    RCCHK(bcd_hip_denoise_moments(ctx, d_ns, W, H, nb_scales, prm, var_floor, dl, L, nullptr));
+    if (opt && opt->zero_bad_values) HIPCHK(ctx, bcd_launch_zero_bad(dl[0].d_out, (int64_t)L * np * 3, ctx->stream)); // (the outputs lie one behind the other)
+    for (int k = 0; k < L; ++k) HIPCHK(ctx, hipMemcpyAsync(layers[k].h_out, dl[k].d_out, np * 3 * f, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_last_upload_bytes(const bcd_hip_ctx *ctx, int64_t *hist_bytes, int64_t *hist_bytes_sent)
 {
     if (!ctx || !hist_bytes || !hist_bytes_sent) return BCD_HIP_EINVAL;

@@ -19,6 +19,9 @@ hipError_t bcd_launch_masks_finish(int W, int H, int b, float tau, uint32_t *mas
                                    const float *hist, const float *ns, int D);
 hipError_t bcd_launch_window_distances(const float *T, const uint8_t *Cn, int W, int H, int w, int b, int r, int c, float *out, hipStream_t st);
 
+// ---- k_similarity_moments.hip
+hipError_t bcd_launch_pairdist_moments(const float *colors, const float *pixcov, int W, int H, int b, float var_floor, float *T, uint8_t *Cn, hipStream_t st);
+
 // ---- k_similarity_fast.hip
 int bcd_pairdist_rw_supported(int D);
 int bcd_pairdist_rw_tile_lines();

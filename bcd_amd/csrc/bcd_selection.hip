@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <thread>
@@ -140,6 +141,21 @@ int selection_store(bcd_hip_ctx *ctx, Work &wk, int scale, const float *d_ns, in
     return BCD_HIP_OK;
 }
 
+namespace {
+// the end of a call that kept its selection: the copies went to the stream of each scale's workspace, a reuse call may drive the scales on other streams
+// (bcd_hip_set_concurrent_scales)
+int selection_complete(bcd_hip_ctx *ctx, bcd_hip_selection *sel, int W, int H, int D, int nb_scales, const bcd_hip_params *prm)
+{
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    for (int s = 1; s < nb_scales; ++s)
+        if (ctx->extra[s].initialised) HIPCHK(ctx, hipStreamSynchronize(ctx->extra[s].stream));
+    sel->W = W; sel->H = H; sel->D = D; sel->S = nb_scales; sel->prm = *prm;
+    sel->valid = true;
+    return BCD_HIP_OK;
+}
+} // namespace
+
 extern "C" {
 
 int bcd_hip_selection_create(bcd_hip_ctx *ctx, bcd_hip_selection **out)
@@ -179,17 +195,32 @@ int bcd_hip_denoise_layers_keep(bcd_hip_ctx *ctx, const float *d_ns, const float
         RCCHK(selection_reserve(ctx, sel, W, H, nb_scales, prm->search_radius));
     }
     ctx->keep = sel;
-    const int rc = bcd_hip_denoise_layers(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
+    const int rc = denoise_layers_checked(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
     ctx->keep = nullptr;
     RCCHK(rc);
-    DEVICE_GUARD(ctx);
-    // the copies went to the stream of each scale's workspace: a reuse call may drive the scales on other streams (bcd_hip_set_concurrent_scales)
-    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
-    for (int s = 1; s < nb_scales; ++s)
-        if (ctx->extra[s].initialised) HIPCHK(ctx, hipStreamSynchronize(ctx->extra[s].stream));
-    sel->W = W; sel->H = H; sel->D = D; sel->S = nb_scales; sel->prm = *prm;
-    sel->valid = true;
-    return BCD_HIP_OK;
+    return selection_complete(ctx, sel, W, H, D, nb_scales, prm);
+}
+
+int bcd_hip_denoise_moments(bcd_hip_ctx *ctx, const float *d_ns, int W, int H, int nb_scales, const bcd_hip_params *prm, float var_floor, const bcd_hip_layer *layers,
+                            int nb_layers, bcd_hip_selection *sel)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    // ---- everything is checked before any device work
+    if (!(var_floor >= 0.f) || !std::isfinite(var_floor)) return bad(ctx, "the variance floor must be finite and not negative");
+    if (sel && sel->ctx != ctx) return bad(ctx, "the selection belongs to another context");
+    if (sel) sel->valid = false; // (as bcd_hip_denoise_layers_keep)
+    RCCHK(check_layers_call(ctx, d_ns, nullptr, W, H, 0, nb_scales, prm, layers, nb_layers, true));
+    if (sel) {
+        DEVICE_GUARD(ctx);
+        RCCHK(selection_reserve(ctx, sel, W, H, nb_scales, prm->search_radius));
+    }
+    ctx->moments.on = true; ctx->moments.var_floor = var_floor;
+    ctx->keep = sel;
+    const int rc = denoise_layers_checked(ctx, d_ns, nullptr, W, H, 0, nb_scales, prm, layers, nb_layers);
+    ctx->keep = nullptr;
+    ctx->moments.on = false;
+    RCCHK(rc);
+    return sel ? selection_complete(ctx, sel, W, H, 0, nb_scales, prm) : BCD_HIP_OK;
 }
 
 int bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, const bcd_hip_layer *layers, int nb_layers)

@@ -247,6 +247,7 @@ SYMBOLS = [
     "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
     "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_denoise_layers_host_ex",
     "bcd_hip_spike_map", "bcd_hip_spike_apply", "bcd_hip_spike_filter_layers",
+    "bcd_hip_similarity_masks_moments", "bcd_hip_window_distances_moments", "bcd_hip_denoise_moments", "bcd_hip_denoise_moments_host",
     "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
     "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
@@ -379,6 +380,38 @@ class Context:
         else:
             _selection_api()
             self._chk(L.bcd_hip_denoise_layers_keep(self.h, _dp(ns), _dp(hist), W, H, D, nscales, C.byref(prm), arr, len(layers), keep._handle()))
+        return outs
+
+    def denoise_moments(self, ns, layers, nscales, prm, var_floor=1e-8, outs=None, keep=None):
+        """bcd_hip_denoise_moments: the similar patches are selected from the colours and per-pixel covariances of layers[0] (the guide), no histogram is
+        read; `layers` is a list of (colours, covariances) tensors that share `ns`, every one is denoised on the one selection.  keep: a Selection that
+        takes the selection of every scale with it.  Returns the list of outputs"""
+        layers = list(layers)
+        H, W = (layers[0][0].shape[0], layers[0][0].shape[1]) if layers else (ns.shape[0], ns.shape[1])
+        arr, layers, outs = self._layer_array(layers, outs, H, W, ns.device)
+        L = lib()
+        L.bcd_hip_denoise_moments.argtypes = [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_float, C.POINTER(Layer), C.c_int, _VP]
+        self._chk(L.bcd_hip_denoise_moments(self.h, _dp(ns), W, H, nscales, C.byref(prm), float(var_floor), arr, len(layers), keep._handle() if keep is not None else None))
+        return outs
+
+    def denoise_moments_host(self, ns, layers, nscales, prm, var_floor=1e-8, spike_factor=0.0, zero_bad_values=False, filter_layers=False):
+        """bcd_hip_denoise_moments_host on NumPy images: `layers` is a list of (colours, covariances), layers[0] the guide; the options are those of
+        denoise_layers_host (the spike prefilter runs without histograms).  Returns the list of outputs"""
+        import numpy as np
+        ns = np.ascontiguousarray(ns, np.float32)
+        H, W = ns.shape[0], ns.shape[1]
+        layers = [(np.ascontiguousarray(c, np.float32), np.ascontiguousarray(v, np.float32)) for c, v in layers]
+        outs = [np.empty((H, W, 3), np.float32) for _ in layers]
+        arr = (HostLayer * max(1, len(layers)))()
+        for k, ((col, cov), out) in enumerate(zip(layers, outs)):
+            if col.shape != (H, W, 3) or cov.shape != (H, W, 6):
+                raise ValueError("layer %d: colours must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
+            arr[k].h_colors, arr[k].h_covariances, arr[k].h_out = col.ctypes.data, cov.ctypes.data, out.ctypes.data
+        opt = LayersHostOptions(spike_factor, 1 if zero_bad_values else 0, 1 if filter_layers else 0)
+        L = lib()
+        L.bcd_hip_denoise_moments_host.argtypes = [_VP, _F, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(LayersHostOptions), C.c_float,
+                                                   C.POINTER(HostLayer), C.c_int]
+        self._chk(L.bcd_hip_denoise_moments_host(self.h, ns.ctypes.data_as(_F), W, H, nscales, C.byref(prm), C.byref(opt), float(var_floor), arr, len(layers)))
         return outs
 
     def selection(self):
@@ -520,6 +553,18 @@ class Context:
         self._chk(lib().bcd_hip_pixel_cov(self.h, _dp(cov), _dp(ns), W, H, _dp(out)))
         return out
 
+    def scale_begin(self, cov, ns):
+        """bcd_hip_scale_begin -> (per-pixel covariances, sum image, count image): the accumulators are handed over filled with ones and cleared by
+        the call, like every counter of the stage calls that follow on this context"""
+        torch = self.torch
+        H, W, _ = cov.shape
+        pixcov = torch.empty_like(cov)
+        s = torch.ones((H, W, 3), dtype=torch.float32, device=cov.device)
+        c = torch.ones((H, W), dtype=torch.int32, device=cov.device)
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(lib().bcd_hip_scale_begin(self.h, _dp(cov), _dp(ns), W, H, _dp(pixcov), _dp(s), _dp(c)))
+        return pixcov, s, c
+
     def similarity_masks(self, hist, ns, w, b, tau):
         torch = self.torch
         H, W, D = hist.shape
@@ -550,6 +595,30 @@ class Context:
         H, W, D = hist.shape
         out = np.empty(((2 * b + 1) ** 2,), np.float32)
         self._chk(lib().bcd_hip_window_distances(self.h, _dp(hist), _dp(ns), W, H, D, w, b, line, col, out.ctypes.data_as(_F)))
+        return out
+
+    def similarity_masks_moments(self, col, pixcov, w, b, tau, var_floor=1e-8):
+        """bcd_hip_similarity_masks_moments: masks and |S| from colours (H, W, 3) and per-pixel covariances (H, W, 6; pixel_cov), in the layouts of
+        similarity_masks"""
+        torch = self.torch
+        H, W, _ = col.shape
+        words = ((2 * b + 1) ** 2 + 31) // 32
+        mask = torch.zeros((H, W, words), dtype=torch.int32, device=col.device)
+        cnt = torch.zeros((H, W), dtype=torch.int32, device=col.device)
+        L = lib()
+        L.bcd_hip_similarity_masks_moments.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP, _VP]
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_similarity_masks_moments(self.h, _dp(col), _dp(pixcov), W, H, w, b, float(tau), float(var_floor), _dp(mask), _dp(cnt)))
+        return mask, cnt
+
+    def window_distances_moments(self, col, pixcov, w, b, line, column, var_floor=1e-8):
+        """bcd_hip_window_distances_moments: the (2b+1)^2 patch distances of one main pixel to its window, +inf outside"""
+        import numpy as np
+        H, W, _ = col.shape
+        out = np.empty(((2 * b + 1) ** 2,), np.float32)
+        L = lib()
+        L.bcd_hip_window_distances_moments.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _F]
+        self._chk(L.bcd_hip_window_distances_moments(self.h, _dp(col), _dp(pixcov), W, H, w, b, float(var_floor), line, column, out.ctypes.data_as(_F)))
         return out
 
     def active_set(self, mask, cnt, w, b, m, random_order, seed, row_begin=0, row_end=None):
@@ -595,11 +664,15 @@ class Context:
         total = (out[2] & 0xFFFFFFFF) | ((out[3] & 0xFFFFFFFF) << 32)
         return strong, weak, out[0], out[1], total
 
-    def bayes_accumulate(self, col, pixcov, mask, nsim, state, w, b, min_eig):
+    def bayes_accumulate(self, col, pixcov, mask, nsim, state, w, b, min_eig, out=None):
+        """out: the (sum, count) accumulators to add into (scale_begin clears a pair); default: fresh zeroed ones"""
         torch = self.torch
         H, W, _ = col.shape
-        s = torch.zeros((H, W, 3), dtype=torch.float32, device=col.device)
-        c = torch.zeros((H, W), dtype=torch.int32, device=col.device)
+        if out is None:
+            s = torch.zeros((H, W, 3), dtype=torch.float32, device=col.device)
+            c = torch.zeros((H, W), dtype=torch.int32, device=col.device)
+        else:
+            s, c = out
         self._chk(lib().bcd_hip_bayes_accumulate(self.h, _dp(col), _dp(pixcov), _dp(mask), _dp(nsim), _dp(state), W, H, w, b,
                                                  C.c_float(min_eig), _dp(s), _dp(c)))
         return s, c

@@ -27,6 +27,8 @@ namespace bcd
 		const DeepImage<float>* images[4] = { m_inputs.m_pColors, m_inputs.m_pNbOfSamples, m_inputs.m_pHistograms, m_inputs.m_pSampleCovariances };
 		const char* names[4] = { "color", "number of samples", "histogram", "covariance" };
 		bool ok = true;
+		if(m_momentSelection)
+			images[2] = images[0] ? images[0] : images[3]; // no histogram image is looked at: its slot repeats another image for the checks below
 		for(int i = 0; i < 4; ++i)
 			if(!images[i])
 			{
@@ -167,6 +169,11 @@ namespace bcd
 
 	bool Denoiser::denoiseWithNbOfScales(int i_nbOfScales)
 	{
+		if(m_momentSelection && m_devices.size() > 1)
+		{
+			cerr << "Aborting denoising: the selection from means and covariances (setMomentSelection) is not available over several devices" << endl;
+			return false;
+		}
 		if(!inputsOutputsAreOk() || !layersAreOk())
 			return false;
 		m_width = m_inputs.m_pColors->getWidth();
@@ -223,9 +230,9 @@ namespace bcd
 		m_progressCallback(0.f);
 		Deepimf result(m_width, m_height, 3); // inputs may alias the output image (the CLI pre-copies colours into it)
 		std::vector<Deepimf> layerResults(m_layers.size());
-		const float* pIn[4] = { m_inputs.m_pColors->getDataPtr(), m_inputs.m_pNbOfSamples->getDataPtr(), m_inputs.m_pHistograms->getDataPtr(),
-				m_inputs.m_pSampleCovariances->getDataPtr() };
-		const int depth = m_inputs.m_pHistograms->getDepth();
+		const float* pIn[4] = { m_inputs.m_pColors->getDataPtr(), m_inputs.m_pNbOfSamples->getDataPtr(),
+				m_momentSelection ? nullptr : m_inputs.m_pHistograms->getDataPtr(), m_inputs.m_pSampleCovariances->getDataPtr() };
+		const int depth = m_momentSelection ? 0 : m_inputs.m_pHistograms->getDepth();
 		int rc = BCD_HIP_OK;
 		if(m_devices.size() > 1)
 		{
@@ -278,7 +285,21 @@ namespace bcd
 			bcd_hip_host_options opt;
 			opt.spike_factor = m_prefilterThresholdStDevFactor;
 			opt.zero_bad_values = m_zeroBadOutputValues ? 1 : 0;
-			if(m_layers.empty())
+			if(m_momentSelection)
+			{	// no histogram: the primary images are the guide and layer 0, added layers follow on its selection
+				std::vector<bcd_hip_host_layer> layers(m_layers.size() + 1);
+				layers[0].h_colors = pIn[0]; layers[0].h_covariances = pIn[3]; layers[0].h_out = result.getDataPtr();
+				for(size_t k = 0; k < m_layers.size(); ++k)
+				{
+					layerResults[k].resize(m_width, m_height, 3);
+					layers[k + 1].h_colors = m_layers[k].m_pColors->getDataPtr();
+					layers[k + 1].h_covariances = m_layers[k].m_pSampleCovariances->getDataPtr();
+					layers[k + 1].h_out = layerResults[k].getDataPtr();
+				}
+				bcd_hip_layers_host_options layersOpt = { opt.spike_factor, opt.zero_bad_values, m_prefilterLayers ? 1 : 0 };
+				rc = bcd_hip_denoise_moments_host(rSlot.m_pCtx, pIn[1], m_width, m_height, i_nbOfScales, &prm, &layersOpt, m_momentVarianceFloor, layers.data(), int(layers.size()));
+			}
+			else if(m_layers.empty())
 				rc = bcd_hip_denoise_host_ex(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], m_width, m_height, depth, i_nbOfScales, &prm, &opt, result.getDataPtr());
 			else
 			{	// the primary images are layer 0: one selection of similar patches serves every layer
@@ -344,6 +365,7 @@ namespace bcd
 		engine.setZeroBadOutputValues(m_zeroBadOutputValues);
 		engine.setLayers(m_layers);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
+		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		const bool ok = engine.denoiseWithNbOfScales(m_nbOfScales);
 		m_parameters.m_nbOfCores = engine.getParameters().m_nbOfCores;
 		return ok;

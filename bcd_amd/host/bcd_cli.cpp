@@ -49,6 +49,8 @@ namespace
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
 		std::vector<Layer> m_layers; // --layer, in command-line order
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
+		bool m_momentSelection = false; // --moment-selection: similar patches from the -i colours and the -c covariances, no histogram file
+		float m_momentVarianceFloor = 1.e-8f;
 	};
 
 	const char* g_pProgramPath = "bcd_cli";
@@ -87,6 +89,12 @@ namespace
 		cout << "    --prefilter-layers   with -p 1 (given or by default) and --layer: the spike prefilter decides on the -i colours which neighbour" << endl;
 		cout << "                         replaces a pixel, and every layer's colours and covariances are gathered through that decision on the device;" << endl;
 		cout << "                         no effect with -p 0" << endl;
+		cout << "    --moment-selection [floor]" << endl;
+		cout << "                         select similar patches from the -i colours and the -c covariances instead of histograms: no histogram file is" << endl;
+		cout << "                         looked for, -d then thresholds the variance-normalised squared difference of the pixel means (1 on average between" << endl;
+		cout << "                         pixels of equal signal); floor (default " << d.m_momentVarianceFloor << ") is added to every summed variance.  Needs the" << endl;
+		cout << "                         sample counts from --nsamples (or from a -h file, whose histograms are then ignored) and a single device" << endl;
+		cout << "    --nsamples <file|n>  with --moment-selection: the sample counts, a one-channel EXR image or one number for every pixel" << endl;
 	}
 
 	bool badValue(const char* flag, const char* what)
@@ -98,12 +106,25 @@ namespace
 	bool parseProgramArguments(int argc, const char** argv, ProgramArguments& a)
 	{
 		bool missingColor = true, missingHist = true, missingCov = true, missingOutput = true;
-		string inputColorFilePath;
+		string inputColorFilePath, nbOfSamplesArgument;
 		for(int i = 1; i < argc; ++i)
 		{
 			const string flag = argv[i];
 			if(flag == "--help") { printUsage(); return false; }
 			if(flag == "--prefilter-layers") { a.m_prefilterLayers = true; continue; }
+			if(flag == "--moment-selection")
+			{
+				a.m_momentSelection = true;
+				char* pEnd = nullptr;
+				const float floor = i + 1 < argc ? strtof(argv[i + 1], &pEnd) : 0.f;
+				if(i + 1 < argc && pEnd != argv[i + 1] && *pEnd == '\0')
+				{	// the optional value: a number
+					if(!(floor >= 0.f) || std::isinf(floor)) return badValue("--moment-selection", "expecting a finite non-negative floating number");
+					a.m_momentVarianceFloor = floor;
+					++i;
+				}
+				continue;
+			}
 			if(flag == "--layer")
 			{
 				if(i + 3 >= argc) { cout << "ERROR in program arguments: expecting <color.exr> <cov.exr> <output.exr> after --layer" << endl; return false; }
@@ -185,6 +206,7 @@ namespace
 			else if(flag == "--ncores") { a.m_nbOfCores = atoi(value); }
 			else if(flag == "--use-cuda") { a.m_useCuda = atoi(value) == 1; }
 			else if(flag == "--seed") { a.m_orderSeed = unsigned(strtoul(value, nullptr, 10)); }
+			else if(flag == "--nsamples") { nbOfSamplesArgument = value; }
 			else if(flag == "--device") { a.m_devices.assign(1, atoi(value)); }
 			else if(flag == "--devices")
 			{	// "0-7", "0,1,2", "0-3,6"
@@ -206,10 +228,11 @@ namespace
 			}
 			else { cout << "ERROR in program arguments: unknown argument " << flag << endl << endl; printUsage(); return false; }
 		}
+		if(!a.m_momentSelection && !nbOfSamplesArgument.empty()) { cout << "ERROR in program arguments: --nsamples goes with --moment-selection" << endl; return false; }
 		if(!missingColor && inputColorFilePath.length() > 4)
 		{
 			const string stem = inputColorFilePath.substr(0, inputColorFilePath.length() - 4); // drops ".exr"
-			if(missingHist)
+			if(missingHist && !a.m_momentSelection)
 			{
 				const string path = stem + "_hist.exr";
 				cout << "Warning: input histogram file not provided by -h argument: assuming '" << path << "'" << endl;
@@ -225,6 +248,33 @@ namespace
 				if(!ImageIO::loadMultiChannelsEXR(a.m_covarianceImage, path.c_str())) { cout << "ERROR in program arguments: couldn't load input covariance matrix image file '" << path << "'" << endl; return false; }
 				missingCov = false;
 			}
+		}
+		if(a.m_momentSelection)
+		{	// no histogram: the sample counts come from --nsamples, else from the -h file that was given all the same
+			if(!nbOfSamplesArgument.empty() && !missingColor)
+			{
+				char* pEnd = nullptr;
+				const float count = strtof(nbOfSamplesArgument.c_str(), &pEnd);
+				if(pEnd != nbOfSamplesArgument.c_str() && *pEnd == '\0')
+				{
+					if(!(count > 0.f) || std::isinf(count)) return badValue("--nsamples", "expecting a positive number or an EXR file");
+					a.m_nbOfSamplesImage.resize(a.m_colorImage.getWidth(), a.m_colorImage.getHeight(), 1);
+					a.m_nbOfSamplesImage.fill(count);
+				}
+				else if(!ImageIO::loadMultiChannelsEXR(a.m_nbOfSamplesImage, nbOfSamplesArgument.c_str()) || a.m_nbOfSamplesImage.getDepth() != 1)
+				{
+					cout << "ERROR in program arguments: couldn't load a one-channel sample count image from '" << nbOfSamplesArgument << "'" << endl;
+					return false;
+				}
+			}
+			else if(missingHist && !missingColor)
+			{
+				cout << "ERROR in program arguments: --moment-selection needs the sample counts: --nsamples <file|n> (or a -h file)" << endl;
+				return false;
+			}
+			if(a.m_devices.size() > 1) { cout << "ERROR in program arguments: --moment-selection is not available with several devices" << endl; return false; }
+			a.m_histogramImage.clearAndFreeMemory();
+			missingHist = false;
 		}
 		if(missingColor || missingHist || missingCov || missingOutput)
 		{
@@ -315,7 +365,7 @@ namespace
 		DenoiserInputs inputs;
 		inputs.m_pColors = &args.m_colorImage;
 		inputs.m_pNbOfSamples = &args.m_nbOfSamplesImage;
-		inputs.m_pHistograms = &args.m_histogramImage;
+		inputs.m_pHistograms = args.m_momentSelection ? nullptr : &args.m_histogramImage;
 		inputs.m_pSampleCovariances = &args.m_covarianceImage;
 		Deepimf outputDenoisedColorImage(args.m_colorImage);
 		DenoiserOutputs outputs;
@@ -339,6 +389,7 @@ namespace
 		if(prefilterOnDevice)
 			pSettings->setSpikePrefilter(args.m_prefilterThresholdStDevFactor);
 		pSettings->setSpikePrefilterLayers(args.m_prefilterLayers);
+		pSettings->setMomentSelection(args.m_momentSelection, args.m_momentVarianceFloor);
 		pSettings->setZeroBadOutputValues(true); // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:470) before the download
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)

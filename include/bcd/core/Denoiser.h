@@ -19,7 +19,7 @@ namespace bcd
 	class HipEngineSettings
 	{
 	public:
-		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false) {}
+		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false), m_momentSelection(false), m_momentVarianceFloor(1e-8f) {}
 
 		/// seed of the visiting order of -r 1 (the reference seeds its shuffle from the wall clock, src/core/Denoiser.cpp:418)
 		void setOrderSeed(uint32_t i_seed) { m_orderSeed = i_seed; }
@@ -58,6 +58,13 @@ namespace bcd
 		/// device (bcd_hip_denoise_layers_host_ex).  false (default): the combination is refused, as it always was.
 		void setSpikePrefilterLayers(bool i_enabled) { m_prefilterLayers = i_enabled; }
 		bool getSpikePrefilterLayers() const { return m_prefilterLayers; }
+		/// true: similar patches are selected from the primary colours and sample covariances (bcd_hip_denoise_moments_host) and NO histogram image is
+		/// required -- DenoiserInputs::m_pHistograms may stay null.  m_histogramDistanceThreshold then thresholds the variance-normalised squared
+		/// difference of the pixel means (expectation 1 between pixels of equal signal), not the chi-square histogram distance.  i_varFloor (finite, >= 0)
+		/// is added to every summed variance.  Added layers and the prefilter switches work as with histograms; one device only.
+		void setMomentSelection(bool i_enabled, float i_varFloor = 1e-8f) { m_momentSelection = i_enabled; m_momentVarianceFloor = i_varFloor; }
+		bool getMomentSelection() const { return m_momentSelection; }
+		float getMomentVarianceFloor() const { return m_momentVarianceFloor; }
 
 	protected:
 		uint32_t m_orderSeed;
@@ -65,6 +72,8 @@ namespace bcd
 		float m_prefilterThresholdStDevFactor;
 		bool m_zeroBadOutputValues;
 		bool m_prefilterLayers;
+		bool m_momentSelection;
+		float m_momentVarianceFloor;
 		std::vector<ColorLayer> m_layers;
 	};
 

@@ -69,7 +69,8 @@ typedef struct bcd_hip_scale_stats {
     float   ms_bayes;
     float   ms_total;
     int32_t similarity_path;  /* 1 = approximate planes + exact verification at the threshold, 2 = the same with the RATIO form of the distance
-                               * kernel (general sample counts: any counts that are not one power of two), 0 = exact planes */
+                               * kernel (general sample counts: any counts that are not one power of two), 0 = exact planes,
+                               * 3 = planes from means and covariances (bcd_hip_denoise_moments: no histogram was read; borderline_pairs is 0) */
     int32_t borderline_pairs; /* pairs re-evaluated exactly (similarity_path >= 1)  */
     int32_t cu_share;         /* share (%) of the CU slots this scale's persistent estimate kernels took (100: all)  */
     int32_t spectral_inverses; /* full estimates (3x3 patches, default search radius) whose matrix inverse failed the sweep's checks and took
@@ -189,6 +190,39 @@ int  bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, 
 int  bcd_hip_selection_info(const bcd_hip_selection *sel, struct bcd_hip_selection_info *out);
 int  bcd_hip_selection_read(bcd_hip_selection *sel, int scale, uint32_t *d_mask, int32_t *d_nsim, uint8_t *d_state, int32_t *d_count);
 
+/* ---- similar patches from means and covariances, without histograms ----------
+ * For producers that keep a running mean and variance per pixel and no sample histogram (a film; bcd_hip_accum_moments): the selection is decided
+ * from the GUIDE's colours m and the xx, yy, zz entries v of its per-pixel covariances P -- bit for bit what bcd_hip_pixel_cov returns, i.e. the
+ * covariance of the pixel's mean -- in place of the chi-square histogram distance.  For pixels x and y = x + delta, channels k = 0, 1, 2 in order, from
+ * s = 0.f, n = 0, in float32 without contraction:
+ *     d = m_k(x) - m_k(y);   q = (v_k(x) + v_k(y)) + var_floor;   if (q > 0.f) { s = s + (d * d) / q; n = n + 1; }      (a NaN q is not counted)
+ *     T_delta(x) = s, C_delta(x) = n
+ * and the patch distance is that of the histogram path on these planes: the sum of T over the patch (row-major, from 0.f) divided by the float of the
+ * summed counts, similar iff <= prm->hist_dist_threshold; 0 / 0 is NaN and "not similar".  Window clipping, mask bit layout and |S| are those of
+ * bcd_hip_similarity_masks.  Between pixels of equal signal the distance has expectation 1; hist_dist_threshold thresholds ANOTHER quantity here than
+ * in the histogram calls ("Without histograms").  var_floor (finite, >= 0; 1e-8 is a usual value) keeps pixels of zero variance
+ * comparable; with 0 such a pixel is not similar to itself.
+ * Everything behind the masks -- marking, lists, estimate, further layers, kept selection, pyramid, merges -- is the code of bcd_hip_denoise_layers.
+ *   _similarity_masks_moments: the stage; d_colors W*H*3, d_pixel_cov W*H*6 (bcd_hip_pixel_cov), outputs as bcd_hip_similarity_masks.
+ *   _window_distances_moments: the twin of bcd_hip_window_distances: (2b+1)^2 floats, +inf outside.
+ *   _denoise_moments: layers[0] is the guide and is denoised like every other layer; layers 1.. follow on the one selection exactly as in
+ *             bcd_hip_denoise_layers.  Level s of the guide's pyramid is what the estimate stage uses there (colours averaged, counts summed, covariances
+ *             weighted by the counts, P of that level from them); no histogram level exists.  sel NULL, or a selection of this context that is
+ *             filled as by bcd_hip_denoise_layers_keep and served by the unchanged bcd_hip_selection_denoise / _read / _info (which reports D = 0).
+ *             bcd_hip_get_stats / bcd_hip_selection_info report similarity_path 3.
+ *             Refused before any device work, with a message, the context staying usable: everything bcd_hip_denoise_layers refuses, a var_floor
+ *             that is negative or not finite, a selection of another context.
+ *   _denoise_moments_host: plain uploads, the resident call, downloads.  opt (may be NULL) as in bcd_hip_denoise_layers_host_ex: spike_factor > 0 runs
+ *             bcd_hip_spike_filter_layers without histograms on the resident copies first (with several layers it needs filter_layers, else
+ *             BCD_HIP_EUNSUPPORTED); zero_bad_values applies to every output.
+ * NOT offered for this selection: row bands (bcd_hip_denoise_band[s]), bcd_hip_multi_*, and the _begin / _wait halves. */
+int bcd_hip_similarity_masks_moments(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, int W, int H, int patch_radius, int search_radius,
+                                     float threshold, float var_floor, uint32_t *d_mask, int32_t *d_count);
+int bcd_hip_window_distances_moments(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, int W, int H, int patch_radius, int search_radius,
+                                     float var_floor, int line, int col, float *h_out);
+int bcd_hip_denoise_moments(bcd_hip_ctx *ctx, const float *d_nsamples, int W, int H, int nb_scales, const bcd_hip_params *prm, float var_floor,
+                            const bcd_hip_layer *layers, int nb_layers, bcd_hip_selection *sel /* NULL, or kept as by _layers_keep */);
+
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
  * finalised colours the raw accumulators are returned (d_sum W*H*3 floats, d_count W*H int32), so
@@ -307,6 +341,10 @@ typedef struct { float spike_factor; int32_t zero_bad_values; int32_t filter_lay
 int bcd_hip_denoise_layers_host_ex(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, int W, int H, int D, int nb_scales,
                                    const bcd_hip_params *prm, const bcd_hip_layers_host_options *opt,
                                    const bcd_hip_host_layer *layers, int nb_layers);
+
+/* bcd_hip_denoise_moments for host images (see there) */
+int bcd_hip_denoise_moments_host(bcd_hip_ctx *ctx, const float *h_nsamples, int W, int H, int nb_scales, const bcd_hip_params *prm,
+                                 const bcd_hip_layers_host_options *opt, float var_floor, const bcd_hip_host_layer *layers, int nb_layers);
 
 /* The histogram image of the last bcd_hip_denoise_host(_ex) call: its size, and the bytes that crossed the link.  On frames of >= 256 lines the
  * image travels without its zeros -- host threads pack every piece into one bit per value ("is not +0.0f", a test on the bit pattern: lossless)
