@@ -1784,7 +1784,8 @@ int bcd_hip_accumulate_samples(bcd_hip_ctx *ctx, const float *d_samples, const f
 {
     if (!ctx || !d_samples || !d_nsamples || !d_mean || !d_cov || !d_hist) return bad(ctx, "null pointer");
     DEVICE_GUARD(ctx);
-    if (W <= 0 || H <= 0 || spp <= 0 || nb_bins < 3) return bad(ctx, "bad size");
+    // (2 bins: nb_bins - 2 = 0 puts every value in the saturation branch, bins 0 and 1 -- in bounds; the minimum of bcd_hip_accum_create)
+    if (W <= 0 || H <= 0 || spp <= 0 || nb_bins < 2) return bad(ctx, "bad size");
     if ((size_t)3 * nb_bins * 64 * sizeof(float) > 160 * 1024) { set_err(ctx, "more than 213 bins per channel are not supported"); return BCD_HIP_EUNSUPPORTED; }
     HIPCHK(ctx, bcd_launch_accumulate_samples(d_samples, d_weights, (int64_t)W * H, spp, nb_bins, gamma, max_value, d_nsamples, d_mean, d_cov, d_hist, ctx->stream));
     return BCD_HIP_OK;

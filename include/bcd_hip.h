@@ -503,7 +503,8 @@ int bcd_hip_spike_filter_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const
                                 int32_t *d_map /* NULL: the context's scratch */, int32_t *d_moved /* NULL or device int32 */);
 /* SamplesAccumulator::addSample + getSamplesStatistics for a whole frame   src/core/SamplesAccumulator.cpp:44-141
  * (lets a GPU renderer keep the statistics in HBM).  d_samples: W*H*spp*3 floats, the spp samples of a pixel contiguous
- * and in accumulation order; d_weights: W*H*spp floats or NULL (all 1).  Outputs in DeepImage layout, hist depth 3*nb_bins. */
+ * and in accumulation order; d_weights: W*H*spp floats or NULL (all 1).  Outputs in DeepImage layout, hist depth 3*nb_bins.
+ * nb_bins in [2, 213] (the accumulator below: [2, 85]); with 2 bins every value takes the saturation branch and lands in bins 0 and 1. */
 int bcd_hip_accumulate_samples(bcd_hip_ctx *ctx, const float *d_samples, const float *d_weights, int W, int H, int spp, int nb_bins,
                                float gamma, float max_value, float *d_nsamples, float *d_mean, float *d_cov, float *d_hist);
 /* Persistent device SamplesAccumulator: the running sums of SamplesAccumulator (src/core/SamplesAccumulator.cpp:44-105) kept in HBM

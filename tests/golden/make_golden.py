@@ -17,6 +17,9 @@
   core_*.npz    regression vectors of the Eigen-dependent core (distances, similar sets, processed sets, denoised
                 frames) computed by the ORACLE itself: the reference core cannot be built here (no Eigen), so these
                 are "parity unpinned" snapshots that guard against drift, not reference outputs.
+  ref_accum_cases.npz  (`make_golden.py accum`) the constructed streams of tests/accum_cases.py (bin edges, special values, weights, every
+                parameter set) and what the reference's compiled accumulator returns for them, so that test_accum_cases_cpu.py pins the
+                oracle on them where oracle/_ref is absent.
 Inputs are seeded (numpy default_rng) and stored in the fixtures, so the files are self-contained data.
 """
 import os
@@ -103,6 +106,22 @@ def make_units():
     print("reference-unit fixture:", len(UNIT_CASES), "cases")
 
 
+def make_accum_cases():
+    import accum_cases as ac
+    r = ol.ref_ops()
+    assert r is not None, "oracle/_ref/libbcd_ref.so missing: run `make -C oracle ref` (needs the reference tree: oracle/Makefile REF)"
+    out = {}
+    for name in ac.ALL:
+        c = ac.get(name)
+        out[name + "/samples"] = c.samples
+        if c.weights is not None:
+            out[name + "/weights"] = c.weights
+        for k, v in zip(("ns", "mean", "cov", "hist"), r["accumulate"](ac.stream(c), c.W, c.H, c.nbins, c.gamma, c.maxval)):
+            out[name + "/" + k] = v
+    np.savez_compressed(os.path.join(HERE, "ref_accum_cases.npz"), **out)
+    print("accumulator cases fixture:", len(ac.ALL), "cases")
+
+
 def make_cli_imports(ref_tree):
     import subprocess
     import tempfile
@@ -150,6 +169,8 @@ if __name__ == "__main__":
         make_trace()
     elif len(sys.argv) > 1 and sys.argv[1] == "units":
         make_units()
+    elif len(sys.argv) > 1 and sys.argv[1] == "accum":
+        make_accum_cases()
     elif len(sys.argv) > 2 and sys.argv[1] == "cli":
         make_cli_imports(sys.argv[2])
     else:
