@@ -268,6 +268,29 @@ def denoise_moments(layers, ns, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_or
     return rc != 0, [outs[k] for k in range(L)]
 
 
+def denoise_guided(layers, ns, hist, features, variances=None, floors=(), threshold=1.0, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234,
+                   zero_bad=False, prefilter_factor=0.0, prefilter_layers=False, var_floor=1e-8, devices=None, feature_width_override=0):
+    """bcd::Denoiser / bcd::MultiscaleDenoiser with setGuideFeatures(features, variances, floors, threshold): layers[0] = (colours, covariances) goes through
+    DenoiserInputs, the others through addLayer; hist None: setMomentSelection(true, var_floor) and no histogram image; features None: a null features pointer
+    (the gate is off); feature_width_override > 0: the feature image is given that width.  Returns (ok, [output per layer])"""
+    H, W = ns.shape[0], ns.shape[1]
+    D = hist.shape[2] if hist is not None else 0
+    L = len(layers)
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    p = lambda a: None if a is None else _fp(a)
+    cols = np.ascontiguousarray(np.stack([c for c, _ in layers]), np.float32)
+    covs = np.ascontiguousarray(np.stack([v for _, v in layers]), np.float32)
+    ns, hist, features, variances = f32(ns), f32(hist), f32(features), f32(variances)
+    fl = np.ascontiguousarray(np.asarray(floors, np.float32).reshape(-1))
+    outs = np.zeros((L, H, W, 3), np.float32)
+    devs = (C.c_int * len(devices))(*devices) if devices else None
+    rc = lib().bcdcore_denoise_guided(_fp(cols), _fp(covs), _fp(ns), p(hist), W, H, D, nscales, L, C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0,
+                                      C.c_float(m), C.c_uint(seed), 1 if zero_bad else 0, C.c_float(prefilter_factor), 1 if prefilter_layers else 0,
+                                      C.c_float(var_floor), p(features), p(variances), features.shape[2] if features is not None else 0, variances.shape[2] if variances is not None else 0,
+                                      _fp(fl) if fl.size else None, int(fl.size), C.c_float(threshold), int(feature_width_override), devs, len(devices) if devices else 0, _fp(outs))
+    return rc != 0, [outs[k] for k in range(L)]
+
+
 def denoise_reuse(col, ns, hist, cov, nscales=3, b=6, nb_of_cores=0):
     """one IDenoiser object, denoise() twice with -r 0: (ok, first output, second output, (m_nbOfCores after call 1, after call 2))"""
     H, W, D = hist.shape

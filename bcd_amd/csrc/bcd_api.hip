@@ -320,6 +320,42 @@ int similarity_moments(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const 
     return BCD_HIP_OK;
 }
 
+// The feature masks of a guide: the exact-path planes from the features and their variances (k_pairdist_guide), the mask kernels
+// of the exact histogram pass into d_gate / d_gate_count.  Nothing of the workspace's verdict on a preceding selection pass is touched: no flag word is
+// used, the host mirror of the flags and the borderline capacity stay what that pass left.  The planes and the forward-mask scratch of the workspace are
+// reused -- the selection pass that precedes is complete in stream order, a redo recomputes its own planes --, so planes computed ahead are gone.
+int guide_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const float *d_variances, int F, const float *floors, float tau_g, int W, int H, int w, int b,
+                uint32_t *d_gate, int32_t *d_gate_count)
+{
+    const size_t npix = (size_t)W * H;
+    const int nd = bcd_delta_count(b);
+    RCCHK(ensure(ctx, wk.T, npix * nd * sizeof(float)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
+    RCCHK(ensure(ctx, wk.fwd, npix * ((nd + 31) / 32) * sizeof(uint32_t)));
+    wk.planes.ready = false;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RCCHK(timing_events(ctx, wk, &e0, &e1));
+    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    HIPCHK(ctx, bcd_launch_pairdist_guide(d_features, d_variances, F, floors, W, H, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
+    HIPCHK(ctx, bcd_launch_masks((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau_g, d_gate, d_gate_count, (uint32_t *)wk.fwd.p, wk.stream,
+                                 nullptr, nullptr, nullptr, 0));
+    return BCD_HIP_OK;
+}
+
+// The gate of a guided selection: mask = selection mask AND feature mask, |S| = popcount, behind a selection pass on wk.stream.  A pure AND: no special
+// case for the centre bit, nothing else of the selection changes.
+int guide_gate(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const float *d_variances, int W, int H, int w, int b, uint32_t *d_mask, int32_t *d_count)
+{
+    const size_t npix = (size_t)W * H;
+    const int side = 2 * b + 1, words = (side * side + 31) / 32;
+    RCCHK(ensure(ctx, wk.gate_mask, npix * words * sizeof(uint32_t)));
+    RCCHK(ensure(ctx, wk.gate_nsim, npix * sizeof(int32_t)));
+    RCCHK(guide_masks(ctx, wk, d_features, d_variances, ctx->guide.F, ctx->guide.floors, ctx->guide.tau, W, H, w, b, (uint32_t *)wk.gate_mask.p, (int32_t *)wk.gate_nsim.p));
+    HIPCHK(ctx, bcd_launch_gate_masks(d_mask, (const uint32_t *)wk.gate_mask.p, d_count, W, H, b, wk.stream));
+    return BCD_HIP_OK;
+}
+
 // one batch of marking launches on lines [row_begin, row_end); *undecided_out = pixels of those lines still undecided
 // Two halves (round 6): active_step_enqueue launches the batch and the copy of its counters WITHOUT waiting -- with `d_total` it also leaves the rank's
 // contribution to the all-reduced count on the device (k_sum_counter_lines; `with_verdict`: + 2^40 when this workspace's last similarity pass has to be
@@ -682,6 +718,8 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
     const long long REDO = 1ll << 40;
     bool estimated = false;
     const bool moments = ctx->moments.on; // (bcd_hip_denoise_moments: one pass that needs no verdict, like the exact kernels)
+    const bool guided = ctx->guide.on;    // (bcd_hip_denoise_guided: level `scale` of the feature pyramid gates this scale's selection)
+    const int gs = scale >= 0 && scale < MAX_SCALES ? scale : 0;
     for (int attempt = 0, mode = moments ? 1 : 2; attempt < 4; ++attempt) { // production kernels; if they complain: general sample counts (RATIO form, then the reference's operations), then exact kernels
         if (moments) {
             HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_pixcov, 0)); // the distance kernel reads the guide's per-pixel covariances (side stream)
@@ -689,6 +727,8 @@ int mono_accumulate(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const flo
                                      (int32_t *)wk.nsim.p));
         } else
             RCCHK(similarity(ctx, wk, d_hist, d_ns, W, H, D, w, b, prm->hist_dist_threshold, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p, mode));
+        if (guided) // (bcd_hip_denoise_guided: the gate follows every run and re-run of the selection pass, ahead of the marking)
+            RCCHK(guide_gate(ctx, wk, ctx->guide.f[gs], ctx->guide.v[gs], W, H, w, b, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
         if (prof && attempt == 0) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
         if (!speculate) {
             RCCHK(active_set(ctx, wk, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, W, H, w, b, row_begin, row_end,
@@ -857,7 +897,7 @@ namespace {
 
 void work_destroy(Work &w)
 {
-    DevBuf *bufs[] = { &w.T, &w.Cn, &w.mask, &w.fwd, &w.nsim, &w.state, &w.strong, &w.weak, &w.counters, &w.cnt_lines, &w.work_q, &w.pixcov, &w.sum, &w.cnt, &w.gscratch, &w.dep, &w.tmp_lo, &w.border, &w.ratio_stats, &w.lay_pixcov, &w.lay_sum, &w.lay_tmp_lo };
+    DevBuf *bufs[] = { &w.T, &w.Cn, &w.mask, &w.fwd, &w.nsim, &w.state, &w.strong, &w.weak, &w.counters, &w.cnt_lines, &w.work_q, &w.pixcov, &w.sum, &w.cnt, &w.gscratch, &w.dep, &w.tmp_lo, &w.border, &w.ratio_stats, &w.lay_pixcov, &w.lay_sum, &w.lay_tmp_lo, &w.gate_mask, &w.gate_nsim };
     for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
     if (w.h_counters) (void)hipHostFree(w.h_counters);
     for (auto &pr : w.ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -955,6 +995,9 @@ void bcd_hip_ctx_destroy(bcd_hip_ctx *ctx)
         for (int k = 0; k < 5; ++k) if (ctx->pyr[s][k].p) (void)hipFree(ctx->pyr[s][k].p);
     for (int s = 0; s < MAX_SCALES; ++s)
         for (int k = 0; k < 3; ++k) if (ctx->lay_pyr[s][k].p) (void)hipFree(ctx->lay_pyr[s][k].p);
+    for (int s = 0; s < MAX_SCALES; ++s)
+        for (int k = 0; k < 2; ++k) if (ctx->guide_pyr[s][k].p) (void)hipFree(ctx->guide_pyr[s][k].p);
+    for (DevBuf &hb : ctx->guide_host) if (hb.p) (void)hipFree(hb.p);
     if (ctx->ev_pyramid) (void)hipEventDestroy(ctx->ev_pyramid);
     for (hipEvent_t ev : ctx->ev_upload) (void)hipEventDestroy(ev);
     if (ctx->upload_stream) (void)hipStreamDestroy(ctx->upload_stream);
@@ -1103,7 +1146,7 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
         // The coarse scales' share of the CU slots (bayes()) follows the previous call on the same geometry: they should be through when
         // the finest scale is at 80 - 92 % of its chain -- earlier means their persistent kernels took more room than they needed next to
         // the finest scale's short kernels, later means they have become the critical path.  Small steps down, larger ones up.
-        const int64_t key = ((int64_t)W << 40) ^ ((int64_t)H << 20) ^ ((int64_t)nb_scales << 12) ^ ((int64_t)prm->search_radius << 4) ^ (prm->marked_skip_probability > 0.f) ^ ((int64_t)E << 56) ^ ((int64_t)moments << 62);
+        const int64_t key = ((int64_t)W << 40) ^ ((int64_t)H << 20) ^ ((int64_t)nb_scales << 12) ^ ((int64_t)prm->search_radius << 4) ^ (prm->marked_skip_probability > 0.f) ^ ((int64_t)E << 56) ^ ((int64_t)moments << 62) ^ ((int64_t)ctx->guide.on << 61);
         if (key != ctx->share_key) { ctx->coarse_share = 25; ctx->share_key = key; }
         const auto t_start = std::chrono::steady_clock::now();
         double t_done[MAX_SCALES] = { 0 };
@@ -1180,6 +1223,55 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
         if (s < nb_scales - 1 && lvp) RCCHK(merge_layers_on(ctx, ctx->main, lvp[s], ws[s], hh[s], lvp[s + 1]));
     }
     if (lvp) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BCD_HIP_OK;
+}
+
+// the refusals a guide adds to a call; no device work: the kernel's LDS limit is a function attribute
+int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius)
+{
+    if (!g) return bad(ctx, "null guide");
+    if (g->nb_channels < 1 || g->nb_channels > BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "the number of feature channels must be between 1 and 8 (BCD_HIP_GUIDE_MAX_CHANNELS)");
+    if (!g->features) return bad(ctx, "null feature image");
+    if (!g->floors) return bad(ctx, "null feature floors");
+    bool counts = g->variances != nullptr;
+    for (int k = 0; k < g->nb_channels; ++k) {
+        if (!(g->floors[k] >= 0.f) || !std::isfinite(g->floors[k])) return bad(ctx, "a feature floor must be finite and not negative");
+        counts = counts || g->floors[k] > 0.f;
+    }
+    if (!(g->threshold >= 0.f) || !std::isfinite(g->threshold)) return bad(ctx, "the feature threshold must be finite and not negative");
+    if (!counts) return bad(ctx, "no feature channel can count: every floor is 0 and there are no variances");
+    if (search_radius >= 0 && search_radius <= 15 && bcd_pairdist_guide_launchable(g->nb_channels, g->variances != nullptr, search_radius) != hipSuccess) {
+        set_err(ctx, "the feature distance kernel cannot be launched for this number of channels and search radius (LDS)");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    return BCD_HIP_OK;
+}
+
+// level s + 1 of the features is downscale_avg of level s, level s + 1 of the variances downscale_avg of level s times 0.25f (the variance of a mean of
+// four); threshold and floors are those of level 0.  On the context's stream: every scale's stream waits for what that stream holds (ev_pyramid)
+int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales)
+{
+    const int F = g->nb_channels;
+    auto &G = ctx->guide;
+    G.on = false;
+    G.F = F; G.tau = g->threshold;
+    for (int k = 0; k < BCD_GUIDE_MAX_CHANNELS; ++k) G.floors[k] = k < F ? g->floors[k] : 0.f;
+    for (int s = 0; s < MAX_SCALES; ++s) G.f[s] = G.v[s] = nullptr;
+    G.f[0] = d_features; G.v[0] = d_variances;
+    for (int s = 1, ws = W, hs = H; s < nb_scales && s < MAX_SCALES; ++s) {
+        const size_t np = (size_t)(ws / 2) * (hs / 2);
+        RCCHK(ensure(ctx, ctx->guide_pyr[s][0], np * F * sizeof(float)));
+        HIPCHK(ctx, bcd_launch_downscale(1, G.f[s - 1], ws, hs, F, (float *)ctx->guide_pyr[s][0].p, ctx->stream));
+        G.f[s] = (const float *)ctx->guide_pyr[s][0].p;
+        if (d_variances) {
+            RCCHK(ensure(ctx, ctx->guide_pyr[s][1], np * F * sizeof(float)));
+            HIPCHK(ctx, bcd_launch_downscale(1, G.v[s - 1], ws, hs, F, (float *)ctx->guide_pyr[s][1].p, ctx->stream));
+            HIPCHK(ctx, bcd_launch_scale_inplace((float *)ctx->guide_pyr[s][1].p, 0.25f, (int64_t)np * F, ctx->stream));
+            G.v[s] = (const float *)ctx->guide_pyr[s][1].p;
+        }
+        ws /= 2; hs /= 2;
+    }
+    G.on = true;
     return BCD_HIP_OK;
 }
 
@@ -1499,6 +1591,57 @@ int bcd_hip_window_distances_moments(bcd_hip_ctx *ctx, const float *d_colors, co
     HIPCHK(ctx, bcd_launch_window_distances((const float *)ctx->main.T.p, (const uint8_t *)ctx->main.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BCD_HIP_OK;
+}
+
+namespace {
+// the refusals the stage calls of the feature gate share
+static int check_guide_stage(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int W, int H, int w, int b)
+{
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    RCCHK(check_params(ctx, W, H, BCD_HIP_GUIDE_MAX_CHANNELS, &p)); // (indices of W*H*F floats stay below 2^31 for every F)
+    return check_guide(ctx, g, b);
+}
+} // namespace
+
+int bcd_hip_similarity_masks_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int W, int H, int w, int b, uint32_t *d_mask, int32_t *d_count)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_mask || !d_count) return bad(ctx, "bad argument");
+    RCCHK(check_guide_stage(ctx, g, W, H, w, b));
+    DEVICE_GUARD(ctx);
+    return guide_masks(ctx, ctx->main, g->features, g->variances, g->nb_channels, g->floors, g->threshold, W, H, w, b, d_mask, d_count);
+}
+
+int bcd_hip_window_distances_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int W, int H, int w, int b, int line, int col, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!h_out) return bad(ctx, "bad argument");
+    RCCHK(check_guide_stage(ctx, g, W, H, w, b));
+    if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
+    DEVICE_GUARD(ctx);
+    const size_t npix = (size_t)W * H;
+    const int nd = bcd_delta_count(b), n = (2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, ctx->main.T, npix * nd * sizeof(float)));
+    RCCHK(ensure(ctx, ctx->main.Cn, count_plane_bytes(npix, nd)));
+    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
+    ctx->main.planes.ready = false; // (the workspace's planes are overwritten)
+    HIPCHK(ctx, bcd_launch_pairdist_guide(g->features, g->variances, g->nb_channels, g->floors, W, H, b, (float *)ctx->main.T.p, (uint8_t *)ctx->main.Cn.p, ctx->stream));
+    HIPCHK(ctx, bcd_launch_window_distances((const float *)ctx->main.T.p, (const uint8_t *)ctx->main.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_gate_masks(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_count, const uint32_t *d_gate, int W, int H, int b)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_mask || !d_count || !d_gate) return bad(ctx, "bad argument");
+    if (W <= 0 || H <= 0 || (int64_t)W * H >= (1ll << 31)) return bad(ctx, "empty input image");
+    if (b < 0) return bad(ctx, "negative radius");
+    if (b > 15) { set_err(ctx, "search radius > 15 is not supported"); return BCD_HIP_EUNSUPPORTED; }
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_gate_masks(d_mask, d_gate, d_count, W, H, b, ctx->stream));
     return BCD_HIP_OK;
 }
 

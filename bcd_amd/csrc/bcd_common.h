@@ -87,6 +87,7 @@ struct BcdBorderline {
 // One launch of a layer-batched kernel serves every layer: the layer is blockIdx.y (streaming kernels) or a loop / blockIdx.z group inside
 // the kernel (tiled fallback), its device pointers travel by value in this table.  What a, b, o mean is the kernel's business.
 #define BCD_MAX_LAYERS 16
+#define BCD_GUIDE_MAX_CHANNELS 8 // feature channels of a guide (k_similarity_guide.hip; BCD_HIP_GUIDE_MAX_CHANNELS of the C ABI)
 struct BcdLayerTable {
     const float *a[BCD_MAX_LAYERS];
     const float *b[BCD_MAX_LAYERS];

@@ -16,6 +16,7 @@
 #include <vector>
 
 static_assert(BCD_MAX_LAYERS == BCD_HIP_MAX_LAYERS, "the layer tables of the kernels hold what the C ABI admits");
+static_assert(BCD_GUIDE_MAX_CHANNELS == BCD_HIP_GUIDE_MAX_CHANNELS, "the floors table of the guide kernel holds what the C ABI admits");
 
 constexpr int MAX_SCALES = 16;
 constexpr int ROUND_BATCH = 16;
@@ -108,6 +109,7 @@ struct Work {
     bool owns_stream = false;
     DevBuf T, Cn, mask, fwd, nsim, state, strong, weak, counters, cnt_lines, work_q, pixcov, sum, cnt, gscratch, dep, tmp_lo, border, ratio_stats; // grow-only
     DevBuf lay_pixcov, lay_sum, lay_tmp_lo; // extra colour layers (bcd_hip_denoise_layers): per-pixel covariances, sums, merge scratch -- one slice per layer
+    DevBuf gate_mask, gate_nsim;   // the feature masks and their counts of a guided selection (guide_gate), ANDed into `mask` / `nsim`
     int border_capacity = 0;       // entries of `border` offered to the last fast similarity pass (0: the exact kernels ran)
     int rounds_hint = 0;           // marking launches the last problem needed
     int last_batch = 0;            // launches of the batch active_step_enqueue left in flight
@@ -178,6 +180,16 @@ struct bcd_hip_ctx {
     bcd_hip_selection *keep = nullptr;                  // bcd_hip_denoise_layers_keep in progress: every scale leaves its selection here (mono_accumulate)
     // bcd_hip_denoise_moments in progress: every scale selects from its guide's colours and per-pixel covariances (similarity_moments); no histogram is read
     struct { bool on = false; float var_floor = 0.f; } moments;
+    // bcd_hip_denoise_guided in progress: every scale gates its selection with the masks of its level of the feature pyramid (guide_gate)
+    struct {
+        bool on = false;
+        int F = 0;
+        const float *f[MAX_SCALES] = {}, *v[MAX_SCALES] = {}; // per pyramid level: features, variances (null: none)
+        float floors[BCD_GUIDE_MAX_CHANNELS] = {};
+        float tau = 0.f;
+    } guide;
+    DevBuf guide_pyr[MAX_SCALES][2]; // levels 1.. of the features and their variances
+    DevBuf guide_host[2];            // host-buffer entry point: device copies of the features and their variances
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
     hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
@@ -267,6 +279,10 @@ int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_
                   float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral, const KeptLists *kept = nullptr);
 int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &coarse, const float *ns_fine, int W, int H, hipStream_t st);
 int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int H, const LayerView &lo);
+// the guide of a bcd_hip_denoise_guided call: its refusals (no device work), then -- on the context's stream -- its pyramid and ctx->guide; guide_end switches it off
+int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius);
+int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales);
+inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
 
 // ---- defined in bcd_selection.hip
 // one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is

@@ -338,6 +338,54 @@ int bcd_hip_denoise_moments_host(bcd_hip_ctx *ctx, const float *h_ns, int W, int
     return BCD_HIP_OK;
 }
 
+// bcd_hip_denoise_guided for host images: plain uploads of the features and their variances into the context's grow-only device copies and their pyramid on
+// the context's stream, then -- with ctx->guide set -- the host call of the layers (histograms: streamed in as ever, the planes computed ahead are consumed
+// by the selection pass before the gate takes the workspace's planes) or of the moment selection.  Every refusal of those calls is made here first, so that
+// none follows device work.
+int bcd_hip_denoise_guided_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                                const bcd_hip_layers_host_options *opt, float var_floor, const bcd_hip_host_layer *layers, int nb_layers, const bcd_hip_guide *guide)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    const bool moments = h_hist == nullptr;
+    if (!h_ns) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k) {
+        if (!layers[k].h_colors || !layers[k].h_covariances || !layers[k].h_out) return bad(ctx, "null image pointer in a layer");
+        for (int j = 0; j < k; ++j) if (layers[j].h_out == layers[k].h_out) return bad(ctx, "two layers share an output image");
+    }
+    if (moments && (!(var_floor >= 0.f) || !std::isfinite(var_floor))) return bad(ctx, "the variance floor must be finite and not negative");
+    const bool prefilter = opt && opt->spike_factor > 0.f;
+    if (prefilter && nb_layers > 1 && !opt->filter_layers) {
+        set_err(ctx, "the spike prefilter moves whole pixels by the first layer's colours: it is not available with several layers");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    RCCHK(check_params(ctx, W, H, moments ? 1 : D, prm));
+    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
+        ws /= 2; hs /= 2;
+        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
+    }
+    if (prefilter && (W < 3 || H < 3)) return bad(ctx, "image smaller than 3x3");
+    if ((int64_t)W * H >= (1ll << 31) / BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "image too large for 32-bit DeepImage indices");
+    RCCHK(check_guide(ctx, guide, prm->search_radius));
+    {
+        DEVICE_GUARD(ctx);
+        const size_t bytes = (size_t)W * H * guide->nb_channels * sizeof(float);
+        RCCHK(ensure(ctx, ctx->guide_host[0], bytes));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->guide_host[0].p, guide->features, bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (guide->variances) {
+            RCCHK(ensure(ctx, ctx->guide_host[1], bytes));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->guide_host[1].p, guide->variances, bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        RCCHK(guide_begin(ctx, guide, (const float *)ctx->guide_host[0].p, guide->variances ? (const float *)ctx->guide_host[1].p : nullptr, W, H, nb_scales));
+    }
+    const int rc = moments ? bcd_hip_denoise_moments_host(ctx, h_ns, W, H, nb_scales, prm, opt, var_floor, layers, nb_layers)
+                           : bcd_hip_denoise_layers_host_ex(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, opt, layers, nb_layers);
+    guide_end(ctx);
+    return rc;
+}
+
 int bcd_hip_last_upload_bytes(const bcd_hip_ctx *ctx, int64_t *hist_bytes, int64_t *hist_bytes_sent)
 {
     if (!ctx || !hist_bytes || !hist_bytes_sent) return BCD_HIP_EINVAL;

@@ -22,6 +22,13 @@ hipError_t bcd_launch_window_distances(const float *T, const uint8_t *Cn, int W,
 // ---- k_similarity_moments.hip
 hipError_t bcd_launch_pairdist_moments(const float *colors, const float *pixcov, int W, int H, int b, float var_floor, float *T, uint8_t *Cn, hipStream_t st);
 
+// ---- k_similarity_guide.hip
+hipError_t bcd_pairdist_guide_launchable(int F, int has_var, int b);
+hipError_t bcd_launch_pairdist_guide(const float *features, const float *variances, int F, const float *floors, int W, int H, int b, float *T, uint8_t *Cn,
+                                     hipStream_t st);
+hipError_t bcd_launch_gate_masks(uint32_t *mask, const uint32_t *gate, int32_t *nsim, int W, int H, int b, hipStream_t st);
+hipError_t bcd_launch_scale_inplace(float *x, float a, int64_t n, hipStream_t st);
+
 // ---- k_similarity_fast.hip
 int bcd_pairdist_rw_supported(int D);
 int bcd_pairdist_rw_tile_lines();

@@ -223,6 +223,34 @@ int bcd_hip_denoise_moments(bcd_hip_ctx *ctx, const float *d_ns, int W, int H, i
     return sel ? selection_complete(ctx, sel, W, H, 0, nb_scales, prm) : BCD_HIP_OK;
 }
 
+int bcd_hip_denoise_guided(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float var_floor,
+                           const bcd_hip_layer *layers, int nb_layers, const bcd_hip_guide *guide, bcd_hip_selection *sel)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    const bool moments = d_hist == nullptr;
+    if (moments) D = 0;
+    // ---- everything is checked before any device work
+    if (moments && (!(var_floor >= 0.f) || !std::isfinite(var_floor))) return bad(ctx, "the variance floor must be finite and not negative");
+    if (sel && sel->ctx != ctx) return bad(ctx, "the selection belongs to another context");
+    if (sel) sel->valid = false; // (as bcd_hip_denoise_layers_keep)
+    RCCHK(check_layers_call(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers, moments));
+    if ((int64_t)W * H >= (1ll << 31) / BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "image too large for 32-bit DeepImage indices");
+    RCCHK(check_guide(ctx, guide, prm->search_radius));
+    {
+        DEVICE_GUARD(ctx);
+        if (sel) RCCHK(selection_reserve(ctx, sel, W, H, nb_scales, prm->search_radius));
+        RCCHK(guide_begin(ctx, guide, guide->features, guide->variances, W, H, nb_scales));
+    }
+    ctx->moments.on = moments; ctx->moments.var_floor = var_floor;
+    ctx->keep = sel;
+    const int rc = denoise_layers_checked(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
+    ctx->keep = nullptr;
+    ctx->moments.on = false;
+    guide_end(ctx);
+    RCCHK(rc);
+    return sel ? selection_complete(ctx, sel, W, H, D, nb_scales, prm) : BCD_HIP_OK;
+}
+
 int bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, const bcd_hip_layer *layers, int nb_layers)
 {
     if (!sel) return BCD_HIP_EINVAL;

@@ -40,6 +40,11 @@ class SelectionInfo(C.Structure):
                 ("device_bytes", C.c_int64), ("scale", SelectionScale * SELECTION_MAX_SCALES)]
 
 
+class Guide(C.Structure):
+    """bcd_hip_guide: auxiliary feature buffers that gate the similar-patch selection"""
+    _fields_ = [("features", C.c_void_p), ("variances", C.c_void_p), ("nb_channels", C.c_int32), ("floors", C.POINTER(C.c_float)), ("threshold", C.c_float)]
+
+
 class StageLayer(C.Structure):
     """bcd_hip_stage_layer: one layer of bcd_hip_bayes_accumulate_layers"""
     _fields_ = [("d_colors", C.c_void_p), ("d_pixel_cov", C.c_void_p), ("d_sum", C.c_void_p)]
@@ -248,6 +253,7 @@ SYMBOLS = [
     "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_denoise_layers_host_ex",
     "bcd_hip_spike_map", "bcd_hip_spike_apply", "bcd_hip_spike_filter_layers",
     "bcd_hip_similarity_masks_moments", "bcd_hip_window_distances_moments", "bcd_hip_denoise_moments", "bcd_hip_denoise_moments_host",
+    "bcd_hip_similarity_masks_guide", "bcd_hip_window_distances_guide", "bcd_hip_gate_masks", "bcd_hip_denoise_guided", "bcd_hip_denoise_guided_host",
     "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
     "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
@@ -412,6 +418,70 @@ class Context:
         L.bcd_hip_denoise_moments_host.argtypes = [_VP, _F, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(LayersHostOptions), C.c_float,
                                                    C.POINTER(HostLayer), C.c_int]
         self._chk(L.bcd_hip_denoise_moments_host(self.h, ns.ctypes.data_as(_F), W, H, nscales, C.byref(prm), C.byref(opt), float(var_floor), arr, len(layers)))
+        return outs
+
+    def _guide(self, features, variances, floors, threshold, host=False):
+        """-> (Guide, objects to keep alive): features / variances are (H, W, F) device tensors (host=True: NumPy arrays), floors F numbers"""
+        import numpy as np
+        if host:
+            features = np.ascontiguousarray(features, np.float32)
+            variances = None if variances is None else np.ascontiguousarray(variances, np.float32)
+        if features.ndim != 3 or (variances is not None and tuple(variances.shape) != tuple(features.shape)):
+            raise ValueError("features must be H x W x F and the variances of the same shape")
+        F = int(features.shape[2])
+        fl = np.ascontiguousarray(np.asarray(floors, np.float32).reshape(-1))
+        if fl.size != F:
+            raise ValueError("one floor per feature channel expected")
+        ptr = (lambda a: a.ctypes.data) if host else (lambda t: _dp(t).value)
+        g = Guide(ptr(features), None if variances is None else ptr(variances), F, fl.ctypes.data_as(C.POINTER(C.c_float)), float(threshold))
+        return g, (features, variances, fl)
+
+    def denoise_guided(self, ns, hist, layers, nscales, prm, features, variances=None, floors=(), threshold=1.0, var_floor=1e-8, outs=None, keep=None):
+        """bcd_hip_denoise_guided: denoise_layers (hist given) or denoise_moments (hist None) with the selection gated by the feature buffers:
+        features (H, W, F) and optional variances (H, W, F) device tensors, floors F numbers, threshold tau_g.  keep: a Selection.  Returns the outputs"""
+        layers = list(layers)
+        H, W = ns.shape[0], ns.shape[1]
+        D = hist.shape[2] if hist is not None else 0
+        arr, layers, outs = self._layer_array(layers, outs, H, W, ns.device)
+        if tuple(features.shape[:2]) != (H, W):
+            raise ValueError("features must be %dx%dxF" % (H, W))
+        g, alive = self._guide(features, variances, floors, threshold)
+        L = lib()
+        _selection_api()
+        L.bcd_hip_denoise_guided.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_float, C.POINTER(Layer), C.c_int,
+                                             C.POINTER(Guide), _VP]
+        self.torch.cuda.synchronize(self.device)                     # (the inputs may have been produced on torch's stream)
+        self._chk(L.bcd_hip_denoise_guided(self.h, _dp(ns), _dp(hist) if hist is not None else None, W, H, D, nscales, C.byref(prm), float(var_floor), arr,
+                                           len(layers), C.byref(g), keep._handle() if keep is not None else None))
+        del alive
+        return outs
+
+    def denoise_guided_host(self, ns, hist, layers, nscales, prm, features, variances=None, floors=(), threshold=1.0, var_floor=1e-8, spike_factor=0.0,
+                            zero_bad_values=False, filter_layers=False):
+        """bcd_hip_denoise_guided_host on NumPy images: `layers` is a list of (colours, covariances); hist None selects from means and covariances.
+        Returns the list of outputs"""
+        import numpy as np
+        ns = np.ascontiguousarray(ns, np.float32)
+        H, W = ns.shape[0], ns.shape[1]
+        hist = None if hist is None else np.ascontiguousarray(hist, np.float32)
+        D = hist.shape[2] if hist is not None else 0
+        layers = [(np.ascontiguousarray(c, np.float32), np.ascontiguousarray(v, np.float32)) for c, v in layers]
+        outs = [np.empty((H, W, 3), np.float32) for _ in layers]
+        arr = (HostLayer * max(1, len(layers)))()
+        for k, ((col, cov), out) in enumerate(zip(layers, outs)):
+            if col.shape != (H, W, 3) or cov.shape != (H, W, 6):
+                raise ValueError("layer %d: colours must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
+            arr[k].h_colors, arr[k].h_covariances, arr[k].h_out = col.ctypes.data, cov.ctypes.data, out.ctypes.data
+        g, alive = self._guide(features, variances, floors, threshold, host=True)
+        if tuple(alive[0].shape[:2]) != (H, W):
+            raise ValueError("features must be %dx%dxF" % (H, W))
+        opt = LayersHostOptions(spike_factor, 1 if zero_bad_values else 0, 1 if filter_layers else 0)
+        L = lib()
+        L.bcd_hip_denoise_guided_host.argtypes = [_VP, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(LayersHostOptions), C.c_float,
+                                                  C.POINTER(HostLayer), C.c_int, C.POINTER(Guide)]
+        self._chk(L.bcd_hip_denoise_guided_host(self.h, ns.ctypes.data_as(_F), hist.ctypes.data_as(_F) if hist is not None else None, W, H, D, nscales,
+                                                C.byref(prm), C.byref(opt), float(var_floor), arr, len(layers), C.byref(g)))
+        del alive
         return outs
 
     def selection(self):
@@ -620,6 +690,46 @@ class Context:
         L.bcd_hip_window_distances_moments.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _F]
         self._chk(L.bcd_hip_window_distances_moments(self.h, _dp(col), _dp(pixcov), W, H, w, b, float(var_floor), line, column, out.ctypes.data_as(_F)))
         return out
+
+    def similarity_masks_guide(self, features, variances, floors, threshold, w, b):
+        """bcd_hip_similarity_masks_guide: the feature masks and their counts from features (H, W, F), optional variances (H, W, F), F floors and the
+        threshold tau_g, in the layouts of similarity_masks"""
+        torch = self.torch
+        H, W, _ = features.shape
+        words = ((2 * b + 1) ** 2 + 31) // 32
+        mask = torch.zeros((H, W, words), dtype=torch.int32, device=features.device)
+        cnt = torch.zeros((H, W), dtype=torch.int32, device=features.device)
+        g, alive = self._guide(features, variances, floors, threshold)
+        L = lib()
+        L.bcd_hip_similarity_masks_guide.argtypes = [_VP, C.POINTER(Guide), C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP]
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_similarity_masks_guide(self.h, C.byref(g), W, H, w, b, _dp(mask), _dp(cnt)))
+        del alive
+        return mask, cnt
+
+    def window_distances_guide(self, features, variances, floors, w, b, line, column):
+        """bcd_hip_window_distances_guide: the (2b+1)^2 feature patch distances of one main pixel to its window, +inf outside"""
+        import numpy as np
+        H, W, _ = features.shape
+        out = np.empty(((2 * b + 1) ** 2,), np.float32)
+        g, alive = self._guide(features, variances, floors, 1.0)
+        L = lib()
+        L.bcd_hip_window_distances_guide.argtypes = [_VP, C.POINTER(Guide), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]
+        self.torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_window_distances_guide(self.h, C.byref(g), W, H, w, b, line, column, out.ctypes.data_as(_F)))
+        del alive
+        return out
+
+    def gate_masks(self, mask, cnt, gate, b):
+        """bcd_hip_gate_masks, in place: mask &= gate word by word, cnt = the bits that remain; returns (mask, cnt)"""
+        H, W, words = mask.shape
+        if words != ((2 * b + 1) ** 2 + 31) // 32 or tuple(gate.shape) != (H, W, words) or tuple(cnt.shape) != (H, W):
+            raise ValueError("masks of %d words per pixel and one count per pixel expected" % (((2 * b + 1) ** 2 + 31) // 32))
+        L = lib()
+        L.bcd_hip_gate_masks.argtypes = [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int]
+        self.torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_gate_masks(self.h, _dp(mask), _dp(cnt), _dp(gate), W, H, b))
+        return mask, cnt
 
     def active_set(self, mask, cnt, w, b, m, random_order, seed, row_begin=0, row_end=None):
         torch = self.torch

@@ -118,6 +118,36 @@ namespace bcd
 		return true;
 	}
 
+	bool Denoiser::guideIsOk()
+	{
+		if(!m_pGuideFeatures)
+			return true;
+		if(m_devices.size() > 1)
+		{
+			cerr << "Aborting denoising: feature buffers (setGuideFeatures) are not available over several devices" << endl;
+			return false;
+		}
+		const int w = m_inputs.m_pColors->getWidth(), h = m_inputs.m_pColors->getHeight();
+		const int depth = m_pGuideFeatures->getDepth();
+		if(m_pGuideFeatures->getWidth() != w || m_pGuideFeatures->getHeight() != h || depth < 1 || depth > BCD_HIP_GUIDE_MAX_CHANNELS)
+		{
+			cerr << "Aborting denoising: the feature image must be " << w << "x" << h << " like the input color image, with 1 to " << BCD_HIP_GUIDE_MAX_CHANNELS
+					<< " channels (it is " << m_pGuideFeatures->getWidth() << "x" << m_pGuideFeatures->getHeight() << "x" << depth << ")" << endl;
+			return false;
+		}
+		if(m_pGuideVariances && (m_pGuideVariances->getWidth() != w || m_pGuideVariances->getHeight() != h || m_pGuideVariances->getDepth() != depth))
+		{
+			cerr << "Aborting denoising: the feature variance image must be " << w << "x" << h << "x" << depth << " like the feature image" << endl;
+			return false;
+		}
+		if(int(m_guideFloors.size()) != depth)
+		{
+			cerr << "Aborting denoising: " << m_guideFloors.size() << " feature floors for " << depth << " feature channels" << endl;
+			return false;
+		}
+		return true;
+	}
+
 	namespace
 	{
 		/// Engine handles are kept for the life of the process, one per device (and one per device list): workspace, pyramid
@@ -174,7 +204,7 @@ namespace bcd
 			cerr << "Aborting denoising: the selection from means and covariances (setMomentSelection) is not available over several devices" << endl;
 			return false;
 		}
-		if(!inputsOutputsAreOk() || !layersAreOk())
+		if(!inputsOutputsAreOk() || !layersAreOk() || !guideIsOk())
 			return false;
 		m_width = m_inputs.m_pColors->getWidth();
 		m_height = m_inputs.m_pColors->getHeight();
@@ -285,7 +315,28 @@ namespace bcd
 			bcd_hip_host_options opt;
 			opt.spike_factor = m_prefilterThresholdStDevFactor;
 			opt.zero_bad_values = m_zeroBadOutputValues ? 1 : 0;
-			if(m_momentSelection)
+			if(m_pGuideFeatures)
+			{	// the selection gated by the feature buffers: with histograms or, under setMomentSelection, without; the primary images are layer 0
+				std::vector<bcd_hip_host_layer> layers(m_layers.size() + 1);
+				layers[0].h_colors = pIn[0]; layers[0].h_covariances = pIn[3]; layers[0].h_out = result.getDataPtr();
+				for(size_t k = 0; k < m_layers.size(); ++k)
+				{
+					layerResults[k].resize(m_width, m_height, 3);
+					layers[k + 1].h_colors = m_layers[k].m_pColors->getDataPtr();
+					layers[k + 1].h_covariances = m_layers[k].m_pSampleCovariances->getDataPtr();
+					layers[k + 1].h_out = layerResults[k].getDataPtr();
+				}
+				bcd_hip_layers_host_options layersOpt = { opt.spike_factor, opt.zero_bad_values, m_prefilterLayers ? 1 : 0 };
+				bcd_hip_guide guide;
+				guide.features = m_pGuideFeatures->getDataPtr();
+				guide.variances = m_pGuideVariances ? m_pGuideVariances->getDataPtr() : nullptr;
+				guide.nb_channels = m_pGuideFeatures->getDepth();
+				guide.floors = m_guideFloors.data();
+				guide.threshold = m_guideThreshold;
+				rc = bcd_hip_denoise_guided_host(rSlot.m_pCtx, pIn[1], pIn[2], m_width, m_height, depth, i_nbOfScales, &prm, &layersOpt, m_momentVarianceFloor, layers.data(),
+						int(layers.size()), &guide);
+			}
+			else if(m_momentSelection)
 			{	// no histogram: the primary images are the guide and layer 0, added layers follow on its selection
 				std::vector<bcd_hip_host_layer> layers(m_layers.size() + 1);
 				layers[0].h_colors = pIn[0]; layers[0].h_covariances = pIn[3]; layers[0].h_out = result.getDataPtr();
@@ -366,6 +417,7 @@ namespace bcd
 		engine.setLayers(m_layers);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
+		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);
 		const bool ok = engine.denoiseWithNbOfScales(m_nbOfScales);
 		m_parameters.m_nbOfCores = engine.getParameters().m_nbOfCores;
 		return ok;

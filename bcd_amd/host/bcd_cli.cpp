@@ -51,6 +51,10 @@ namespace
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
 		bool m_momentSelection = false; // --moment-selection: similar patches from the -i colours and the -c covariances, no histogram file
 		float m_momentVarianceFloor = 1.e-8f;
+		string m_featurePath, m_featureVariancePath; // --features / --feature-variances: auxiliary buffers that gate the similar-patch selection
+		Deepimf m_featureImage, m_featureVarianceImage;
+		std::vector<float> m_featureFloors;          // --feature-floors: one per channel
+		float m_featureThreshold = 1.f;              // --feature-threshold
 	};
 
 	const char* g_pProgramPath = "bcd_cli";
@@ -95,6 +99,16 @@ namespace
 		cout << "                         pixels of equal signal); floor (default " << d.m_momentVarianceFloor << ") is added to every summed variance.  Needs the" << endl;
 		cout << "                         sample counts from --nsamples (or from a -h file, whose histograms are then ignored) and a single device" << endl;
 		cout << "    --nsamples <file|n>  with --moment-selection: the sample counts, a one-channel EXR image or one number for every pixel" << endl;
+		cout << "    --features <file>    auxiliary feature buffers (albedo, normal, depth, object id, ...: a multi-channel float EXR of 1 to 8 channels): two" << endl;
+		cout << "                         patches stay similar only if their features agree as well, so nothing is averaged across an edge that only the" << endl;
+		cout << "                         features show.  Needs --feature-floors and a single device" << endl;
+		cout << "    --feature-variances <file>" << endl;
+		cout << "                         the variance of every pixel's feature mean, same channels as --features (default: none)" << endl;
+		cout << "    --feature-floors <a,b,...>" << endl;
+		cout << "                         one non-negative number per feature channel, added to the summed variances; without variances the squared" << endl;
+		cout << "                         tolerance of the channel (0.01: features within 0.1 agree), 0 switches the channel off" << endl;
+		cout << "    --feature-threshold <float>" << endl;
+		cout << "                         threshold of the mean squared normalised feature difference over a patch (default: " << d.m_featureThreshold << ")" << endl;
 	}
 
 	bool badValue(const char* flag, const char* what)
@@ -207,6 +221,40 @@ namespace
 			else if(flag == "--use-cuda") { a.m_useCuda = atoi(value) == 1; }
 			else if(flag == "--seed") { a.m_orderSeed = unsigned(strtoul(value, nullptr, 10)); }
 			else if(flag == "--nsamples") { nbOfSamplesArgument = value; }
+			else if(flag == "--features")
+			{
+				a.m_featurePath = value;
+				if(!ImageIO::loadMultiChannelsEXR(a.m_featureImage, value)) { cout << "ERROR in program arguments: couldn't load feature image file '" << value << "'" << endl; return false; }
+			}
+			else if(flag == "--feature-variances")
+			{
+				a.m_featureVariancePath = value;
+				if(!ImageIO::loadMultiChannelsEXR(a.m_featureVarianceImage, value)) { cout << "ERROR in program arguments: couldn't load feature variance image file '" << value << "'" << endl; return false; }
+			}
+			else if(flag == "--feature-floors")
+			{	// "0.01,0.01,1e-4"
+				a.m_featureFloors.clear();
+				const string list(value);
+				size_t pos = 0;
+				while(pos <= list.size())
+				{
+					size_t end = list.find(',', pos);
+					if(end == string::npos) end = list.size();
+					const string item = list.substr(pos, end - pos);
+					char* pEnd = nullptr;
+					const float floor = strtof(item.c_str(), &pEnd);
+					if(item.empty() || pEnd == item.c_str() || *pEnd != '\0' || !(floor >= 0.f) || std::isinf(floor))
+						return badValue("--feature-floors", "expecting a list of finite non-negative floating numbers like 0.01,0.01,1e-4");
+					a.m_featureFloors.push_back(floor);
+					pos = end + 1;
+				}
+			}
+			else if(flag == "--feature-threshold")
+			{
+				char* pEnd = nullptr;
+				a.m_featureThreshold = strtof(value, &pEnd);
+				if(pEnd == value || *pEnd != '\0' || !(a.m_featureThreshold >= 0.f) || std::isinf(a.m_featureThreshold)) return badValue("--feature-threshold", "expecting a finite non-negative floating number");
+			}
 			else if(flag == "--device") { a.m_devices.assign(1, atoi(value)); }
 			else if(flag == "--devices")
 			{	// "0-7", "0,1,2", "0-3,6"
@@ -229,6 +277,30 @@ namespace
 			else { cout << "ERROR in program arguments: unknown argument " << flag << endl << endl; printUsage(); return false; }
 		}
 		if(!a.m_momentSelection && !nbOfSamplesArgument.empty()) { cout << "ERROR in program arguments: --nsamples goes with --moment-selection" << endl; return false; }
+		if(a.m_featurePath.empty() && (!a.m_featureVariancePath.empty() || !a.m_featureFloors.empty())) { cout << "ERROR in program arguments: --feature-variances and --feature-floors go with --features" << endl; return false; }
+		if(!a.m_featurePath.empty())
+		{	// (checked here: nothing has touched a device yet)
+			const int depth = a.m_featureImage.getDepth();
+			if(depth < 1 || depth > 8) { cout << "ERROR in program arguments: feature image '" << a.m_featurePath << "' has " << depth << " channels, 1 to 8 are supported" << endl; return false; }
+			if(a.m_featureFloors.empty()) { cout << "ERROR in program arguments: --features needs --feature-floors <a,b,...>, one number per feature channel" << endl; return false; }
+			if(int(a.m_featureFloors.size()) != depth) { cout << "ERROR in program arguments: " << a.m_featureFloors.size() << " --feature-floors for " << depth << " feature channels" << endl; return false; }
+			if(!a.m_featureVariancePath.empty() && (a.m_featureVarianceImage.getWidth() != a.m_featureImage.getWidth() || a.m_featureVarianceImage.getHeight() != a.m_featureImage.getHeight() || a.m_featureVarianceImage.getDepth() != depth))
+			{
+				cout << "ERROR in program arguments: feature variance image '" << a.m_featureVariancePath << "' is " << a.m_featureVarianceImage.getWidth() << "x" << a.m_featureVarianceImage.getHeight()
+						<< "x" << a.m_featureVarianceImage.getDepth() << " but the feature image is " << a.m_featureImage.getWidth() << "x" << a.m_featureImage.getHeight() << "x" << depth << endl;
+				return false;
+			}
+			bool counts = !a.m_featureVariancePath.empty();
+			for(float floor : a.m_featureFloors) counts = counts || floor > 0.f;
+			if(!counts) { cout << "ERROR in program arguments: every --feature-floors value is 0 and there are no --feature-variances: no feature channel can count" << endl; return false; }
+			if(a.m_devices.size() > 1) { cout << "ERROR in program arguments: --features is not available with several devices" << endl; return false; }
+			if(!missingColor && (a.m_featureImage.getWidth() != a.m_colorImage.getWidth() || a.m_featureImage.getHeight() != a.m_colorImage.getHeight()))
+			{
+				cout << "ERROR in program arguments: feature image '" << a.m_featurePath << "' is " << a.m_featureImage.getWidth() << "x" << a.m_featureImage.getHeight()
+						<< " but the input color image is " << a.m_colorImage.getWidth() << "x" << a.m_colorImage.getHeight() << endl;
+				return false;
+			}
+		}
 		if(!missingColor && inputColorFilePath.length() > 4)
 		{
 			const string stem = inputColorFilePath.substr(0, inputColorFilePath.length() - 4); // drops ".exr"
@@ -390,6 +462,8 @@ namespace
 			pSettings->setSpikePrefilter(args.m_prefilterThresholdStDevFactor);
 		pSettings->setSpikePrefilterLayers(args.m_prefilterLayers);
 		pSettings->setMomentSelection(args.m_momentSelection, args.m_momentVarianceFloor);
+		if(!args.m_featurePath.empty())
+			pSettings->setGuideFeatures(&args.m_featureImage, args.m_featureVariancePath.empty() ? nullptr : &args.m_featureVarianceImage, args.m_featureFloors, args.m_featureThreshold);
 		pSettings->setZeroBadOutputValues(true); // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:470) before the download
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)

@@ -424,6 +424,64 @@ int bcdcore_denoise_moments(const float* cols, const float* covs, const float* n
 	return 1;
 }
 
+/// bcd::Denoiser / bcd::MultiscaleDenoiser with setGuideFeatures(features, variances, floors, threshold): `nbOfLayers` colour layers as in
+/// bcdcore_denoise_layers_ex; hist null: setMomentSelection(true, varFloor) and no histogram image.  features: W x H x nbOfChannels, null: a null features
+/// pointer is set (the gate is off); variances: W x H x nbOfVarianceChannels or null; nbOfFloors floors; featureWidthOverride > 0: the feature image gets that width
+/// (validation path).  Returns denoise()'s bool
+int bcdcore_denoise_guided(const float* cols, const float* covs, const float* ns, const float* hist, int W, int H, int D, int nscales, int nbOfLayers, float tau,
+		int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int zeroBad, float prefilterFactor, int prefilterLayers, float varFloor,
+		const float* features, const float* variances, int nbOfChannels, int nbOfVarianceChannels, const float* floors, int nbOfFloors, float threshold, int featureWidthOverride,
+		const int* devices, int nbOfDevices, float* outs)
+{
+	if(nbOfLayers < 1) return 0;
+	const size_t np = size_t(W) * H;
+	std::vector<Deepimf> c(nbOfLayers), v(nbOfLayers), o(nbOfLayers);
+	for(int k = 0; k < nbOfLayers; ++k)
+	{
+		c[k].resize(W, H, 3); c[k].copyDataFrom(cols + k * np * 3);
+		v[k].resize(W, H, 6); v[k].copyDataFrom(covs + k * np * 6);
+		o[k].resize(W, H, 3);
+	}
+	Deepimf nImg(W, H, 1), hImg, fImg, fvImg;
+	nImg.copyDataFrom(ns);
+	DenoiserInputs in;
+	in.m_pColors = &c[0]; in.m_pNbOfSamples = &nImg; in.m_pSampleCovariances = &v[0];
+	if(hist) { hImg.resize(W, H, D); hImg.copyDataFrom(hist); in.m_pHistograms = &hImg; }
+	if(features && featureWidthOverride > 0) { fImg.resize(featureWidthOverride, H, nbOfChannels); fImg.fill(0.f); } // deliberately mismatched size
+	else if(features) { fImg.resize(W, H, nbOfChannels); fImg.copyDataFrom(features); }
+	if(variances) { fvImg.resize(W, H, nbOfVarianceChannels); fvImg.copyDataFrom(variances); }
+	DenoiserOutputs out;
+	out.m_pDenoisedColors = &o[0];
+	DenoiserParameters p;
+	p.m_histogramDistanceThreshold = tau; p.m_searchWindowRadius = b; p.m_minEigenValue = minEig;
+	p.m_useRandomPixelOrder = randomOrder != 0; p.m_markedPixelsSkippingProbability = skipProbability;
+	std::unique_ptr<IDenoiser> d;
+	HipEngineSettings* pSettings = nullptr;
+	if(nscales > 1) { MultiscaleDenoiser* m = new MultiscaleDenoiser(nscales); pSettings = m; d.reset(m); }
+	else { Denoiser* m = new Denoiser(); pSettings = m; d.reset(m); }
+	pSettings->setOrderSeed(seed);
+	if(devices && nbOfDevices > 0)
+		pSettings->setDevices(std::vector<int>(devices, devices + nbOfDevices));
+	pSettings->setZeroBadOutputValues(zeroBad != 0);
+	pSettings->setSpikePrefilter(prefilterFactor);
+	pSettings->setSpikePrefilterLayers(prefilterLayers != 0);
+	if(!hist)
+		pSettings->setMomentSelection(true, varFloor);
+	pSettings->setGuideFeatures(features ? &fImg : nullptr, variances ? &fvImg : nullptr, std::vector<float>(floors, floors + (floors ? nbOfFloors : 0)), threshold);
+	if((pSettings->getGuideFeatures() != nullptr) != (features != nullptr) || pSettings->getGuideThreshold() != threshold || int(pSettings->getGuideFloors().size()) != (floors ? nbOfFloors : 0))
+		return 0;
+	for(int k = 1; k < nbOfLayers; ++k)
+		pSettings->addLayer(&c[k], &v[k], &o[k]);
+	d->setInputs(in);
+	d->setOutputs(out);
+	d->setParameters(p);
+	if(!d->denoise())
+		return 0;
+	for(int k = 0; k < nbOfLayers; ++k)
+		o[k].copyDataTo(outs + k * np * 3);
+	return 1;
+}
+
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with `nbOfLayers` colour layers: layer 0 through DenoiserInputs / DenoiserOutputs, the others through
 /// addLayer.  cols / covs / outs: nbOfLayers images one behind the other.  sizeMismatchLayer > 0: that added layer gets a covariance image one
 /// line short (validation path).  afterClear != 0: clearLayers() and a second denoise() into outs[0] must still succeed.  Returns denoise()'s bool

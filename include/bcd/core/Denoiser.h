@@ -19,7 +19,8 @@ namespace bcd
 	class HipEngineSettings
 	{
 	public:
-		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false), m_momentSelection(false), m_momentVarianceFloor(1e-8f) {}
+		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false), m_momentSelection(false), m_momentVarianceFloor(1e-8f),
+				m_pGuideFeatures(nullptr), m_pGuideVariances(nullptr), m_guideThreshold(1.f) {}
 
 		/// seed of the visiting order of -r 1 (the reference seeds its shuffle from the wall clock, src/core/Denoiser.cpp:418)
 		void setOrderSeed(uint32_t i_seed) { m_orderSeed = i_seed; }
@@ -65,6 +66,23 @@ namespace bcd
 		void setMomentSelection(bool i_enabled, float i_varFloor = 1e-8f) { m_momentSelection = i_enabled; m_momentVarianceFloor = i_varFloor; }
 		bool getMomentSelection() const { return m_momentSelection; }
 		float getMomentVarianceFloor() const { return m_momentVarianceFloor; }
+		/// Auxiliary feature buffers (albedo, shading normal, depth, object id, ...) that gate the similar-patch selection (bcd_hip_denoise_guided_host): two
+		/// patches stay similar only if their features agree as well, so nothing is averaged across a texture or geometry edge that the radiance statistics
+		/// cannot see.  i_pFeatures: W x H x F, 1 <= F <= 8; i_pVariances: the variance of each pixel's feature MEAN, same size, or null; i_rFloors: one
+		/// value per channel, finite and >= 0 (without variances: the squared tolerance of the channel; 0 switches the channel off); i_threshold: finite,
+		/// >= 0, 1 = "one tolerance rms".  Non-owning pointers, like DenoiserInputs.  A null features pointer switches the gate off.  Added layers, the
+		/// prefilter switches and the moment selection work as without it; one device only.
+		void setGuideFeatures(const DeepImage<float>* i_pFeatures, const DeepImage<float>* i_pVariances, const std::vector<float>& i_rFloors, float i_threshold = 1.f)
+		{
+			m_pGuideFeatures = i_pFeatures;
+			m_pGuideVariances = i_pFeatures ? i_pVariances : nullptr;
+			m_guideFloors = i_rFloors;
+			m_guideThreshold = i_threshold;
+		}
+		const DeepImage<float>* getGuideFeatures() const { return m_pGuideFeatures; }
+		const DeepImage<float>* getGuideVariances() const { return m_pGuideVariances; }
+		const std::vector<float>& getGuideFloors() const { return m_guideFloors; }
+		float getGuideThreshold() const { return m_guideThreshold; }
 
 	protected:
 		uint32_t m_orderSeed;
@@ -74,6 +92,10 @@ namespace bcd
 		bool m_prefilterLayers;
 		bool m_momentSelection;
 		float m_momentVarianceFloor;
+		const DeepImage<float>* m_pGuideFeatures;
+		const DeepImage<float>* m_pGuideVariances;
+		std::vector<float> m_guideFloors;
+		float m_guideThreshold;
 		std::vector<ColorLayer> m_layers;
 	};
 
@@ -96,6 +118,8 @@ namespace bcd
 		bool inputsOutputsAreOk();
 		/// the same for the added colour layers (sizes against the primary colour image)
 		bool layersAreOk();
+		/// ... and for the feature buffers of setGuideFeatures
+		bool guideIsOk();
 
 		int getImagesWidth() const { return m_width; }
 		int getImagesHeight() const { return m_height; }

@@ -223,6 +223,56 @@ int bcd_hip_window_distances_moments(bcd_hip_ctx *ctx, const float *d_colors, co
 int bcd_hip_denoise_moments(bcd_hip_ctx *ctx, const float *d_nsamples, int W, int H, int nb_scales, const bcd_hip_params *prm, float var_floor,
                             const bcd_hip_layer *layers, int nb_layers, bcd_hip_selection *sel /* NULL, or kept as by _layers_keep */);
 
+/* ---- the selection gated by auxiliary feature buffers ----------------------------
+ * Renderers hand a denoiser noise-free or nearly noise-free buffers beside the radiance: albedo, shading normal, depth, object id.  A guide makes them
+ * stop patches from being averaged across a texture or geometry edge that the radiance statistics cannot see at low sample counts.
+ * A guide is: F channels, 1 <= F <= BCD_HIP_GUIDE_MAX_CHANNELS; a feature image f of W*H*F floats, pixel-interleaved like every DeepImage; an optional
+ * variance image v of W*H*F floats, the variance of the pixel's feature MEAN (NULL: v == 0); per-channel floors eps_k, a HOST array of F floats, each
+ * finite and >= 0; a threshold tau_g, finite and >= 0.
+ * Definition (float32, no contraction, IEEE division).  For pixels x and y = x + delta, channels k = 0 .. F-1 in order, from s = 0.f, n = 0:
+ *     d = f_k(x) - f_k(y)
+ *     q = (v_k(x) + v_k(y)) + eps_k                                  (v absent: q = 0.f + eps_k)
+ *     if (q > 0.f) { t = (d * d) / q;  if (t == t) { s = s + t; n = n + 1; } }
+ *     T_delta(x) = s,  C_delta(x) = n
+ * A NaN term is skipped (depth inf against depth inf on a background).  An infinite term is counted and makes the pair dissimilar (inf against a finite
+ * depth).  T / C are bitwise symmetric, as for the moments.  The patch distance, the membership test (sum of T) / float(sum of C) <= tau_g, window
+ * clipping, bit layout and |S| are those of bcd_hip_similarity_masks -- the same kernels produce them --; in particular 0 / 0 is NaN and "not similar".
+ * The guided selection is  mask = selection mask AND feature mask, |S| = popcount.  A pure AND: no special case for the centre bit, nothing else of the
+ * selection changes, and the gate follows every run and re-run of the selection pass.
+ * Pyramid: level s + 1 of the features is bcd_hip_downscale_avg of level s (D = F); level s + 1 of the variances is bcd_hip_downscale_avg of level s
+ * times 0.25f; tau_g and the floors are the same at every level.
+ * Without variances eps_k is the squared tolerance sigma_k^2 of channel k, the distance is the mean over the patch and the counted channels of
+ * (delta f / sigma_k)^2 and tau_g = 1 means "one sigma rms"; a channel with eps_k = 0 and no variance is switched off ("Auxiliary
+ * features").
+ *   _similarity_masks_guide: the feature masks and their counts alone, outputs as bcd_hip_similarity_masks.
+ *   _window_distances_guide: the twin of bcd_hip_window_distances_moments: (2b+1)^2 floats, +inf outside.
+ *   _gate_masks: d_mask[p][j] &= d_gate[p][j] for the ((2b+1)^2 + 31) / 32 words of every pixel, d_count[p] = the bits that remain.
+ *   _denoise_guided: with d_histograms given, bcd_hip_denoise_layers (sel NULL) or bcd_hip_denoise_layers_keep with the gate; with d_histograms NULL
+ *             (D is not looked at), bcd_hip_denoise_moments with the gate -- var_floor is read only then.  The layers follow the gated selection; a kept
+ *             selection holds the gated masks and is served by the unchanged bcd_hip_selection_denoise / _read / _info, which need no features.
+ *             Refused before any device work, with a message, the context staying usable: everything the underlying call refuses; F outside 1..8; a NULL
+ *             guide, feature pointer or floors; a floor or threshold that is negative or not finite; no channel able to count (every floor 0 and no
+ *             variances); a selection of another context.
+ *   _denoise_guided_host: plain uploads of the features and variances, then the call on the resident copies by the route of
+ *             bcd_hip_denoise_layers_host_ex (h_histograms given) or bcd_hip_denoise_moments_host (NULL), with their options and refusals.
+ * With no guide given every other call is bit for bit what it was.  NOT offered with a guide: row bands, bcd_hip_multi_*, the _begin / _wait halves. */
+#define BCD_HIP_GUIDE_MAX_CHANNELS 8
+typedef struct bcd_hip_guide {
+    const float *features;   /* W*H*nb_channels floats (device for the resident calls, host for _denoise_guided_host) */
+    const float *variances;  /* the same size, or NULL */
+    int32_t      nb_channels;
+    const float *floors;     /* HOST array of nb_channels floats */
+    float        threshold;
+} bcd_hip_guide;
+int bcd_hip_similarity_masks_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *guide, int W, int H, int patch_radius, int search_radius, uint32_t *d_mask,
+                                   int32_t *d_count);
+int bcd_hip_window_distances_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *guide, int W, int H, int patch_radius, int search_radius, int line, int col,
+                                   float *h_out);
+int bcd_hip_gate_masks(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_count, const uint32_t *d_gate, int W, int H, int search_radius);
+int bcd_hip_denoise_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms /* NULL: selection from means and covariances */, int W, int H,
+                           int D, int nb_scales, const bcd_hip_params *prm, float var_floor, const bcd_hip_layer *layers, int nb_layers,
+                           const bcd_hip_guide *guide, bcd_hip_selection *sel /* NULL, or kept as by _layers_keep */);
+
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
  * finalised colours the raw accumulators are returned (d_sum W*H*3 floats, d_count W*H int32), so
@@ -345,6 +395,11 @@ int bcd_hip_denoise_layers_host_ex(bcd_hip_ctx *ctx, const float *h_nsamples, co
 /* bcd_hip_denoise_moments for host images (see there) */
 int bcd_hip_denoise_moments_host(bcd_hip_ctx *ctx, const float *h_nsamples, int W, int H, int nb_scales, const bcd_hip_params *prm,
                                  const bcd_hip_layers_host_options *opt, float var_floor, const bcd_hip_host_layer *layers, int nb_layers);
+
+/* bcd_hip_denoise_guided for host images (see there): guide->features and guide->variances are HOST images */
+int bcd_hip_denoise_guided_host(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms /* NULL: selection from means and covariances */, int W,
+                                int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layers_host_options *opt, float var_floor,
+                                const bcd_hip_host_layer *layers, int nb_layers, const bcd_hip_guide *guide);
 
 /* The histogram image of the last bcd_hip_denoise_host(_ex) call: its size, and the bytes that crossed the link.  On frames of >= 256 lines the
  * image travels without its zeros -- host threads pack every piece into one bit per value ("is not +0.0f", a test on the bit pattern: lossless)
