@@ -466,7 +466,10 @@ hipError_t bcd_launch_pixel_cov(const float *cov, const float *ns, int64_t npix,
 hipError_t bcd_launch_pixel_cov_clear(const float *cov, const float *ns, int64_t npix, float *out, float *sum, int32_t *cnt, hipStream_t st)
 {
     const int64_t npairs = npix / 2;
-    if (npairs > 0 && npairs < (int64_t)1 << 32) {
+    // (the public entry point takes any device pointers -- a view into a larger buffer may be 4-byte aligned only: the pair kernel moves the covariances
+    // 16 bytes and the counts, sums and counters 8 bytes at a time, so such views take the per-value kernel)
+    const bool vec = ((((uintptr_t)cov | (uintptr_t)out) & 15) | (((uintptr_t)ns | (uintptr_t)sum | (uintptr_t)cnt) & 7)) == 0;
+    if (vec && npairs > 0 && npairs < (int64_t)1 << 32) {
         hipLaunchKernelGGL(k_pixel_cov_clear2, dim3(nblk(npairs, 256)), dim3(256), 0, st, cov, ns, (uint32_t)npairs, out, sum, cnt);
         const int64_t done = 2 * npairs; // (an odd pixel count: the last pixel by the per-value kernel)
         if (done < npix)
@@ -503,7 +506,9 @@ hipError_t bcd_launch_downscale(int mode, const float *in, int W, int H, int D, 
 {
     int64_t n = (int64_t)(W / 2) * (H / 2) * D;
     if (n <= 0) return hipSuccess;
-    if (D % 4 == 0 && n / 4 < (int64_t)1 << 31) { // (histograms: four bins per thread)
+    // (as bcd_launch_spike_rows: a view that is 4-byte aligned only takes the scalar forms below)
+    const bool vec16 = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+    if (vec16 && D % 4 == 0 && n / 4 < (int64_t)1 << 31) { // (histograms: four bins per thread)
         const uint32_t n4 = (uint32_t)(n / 4);
         if (mode == 0) hipLaunchKernelGGL(k_downscale4<0>, dim3(nblk(n4, 256)), dim3(256), 0, st, in, W, H, D / 4, out, n4);
         else hipLaunchKernelGGL(k_downscale4<1>, dim3(nblk(n4, 256)), dim3(256), 0, st, in, W, H, D / 4, out, n4);

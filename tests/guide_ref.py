@@ -12,6 +12,7 @@ The guided selection is  mask = selection mask AND feature mask, |S| = popcount.
 import numpy as np
 
 import moments_ref as mr
+from pyramid_ref import downscale_avg  # noqa: F401  (the one restatement of bcd_hip_downscale_avg; pyramid() below and the guide tests use it)
 
 F32 = np.float32
 
@@ -114,20 +115,6 @@ def gate(mask, feature_mask):
     """the guided selection: (mask AND feature mask, popcount)"""
     m = (np.ascontiguousarray(mask).view(np.uint32) & np.ascontiguousarray(feature_mask).view(np.uint32)).view(np.int32)
     return m, popcount(m)
-
-
-def downscale_avg(a):
-    """bcd_hip_downscale_avg in NumPy float32: 0.25 * (((p1 + p2) + p3) + p4), p1 = (2l, 2c), p2 = next line, p3 = next column, p4 = both, clamped"""
-    a = np.asarray(a, F32)
-    H, W = a.shape[0], a.shape[1]
-    h2, w2 = H // 2, W // 2
-    l0 = 2 * np.arange(h2)
-    c0 = 2 * np.arange(w2)
-    l1 = np.minimum(l0 + 1, H - 1)
-    c1 = np.minimum(c0 + 1, W - 1)
-    with np.errstate(all="ignore"):
-        v = ((a[l0][:, c0] + a[l1][:, c0]) + a[l0][:, c1]) + a[l1][:, c1]
-        return (F32(0.25) * v).astype(F32)
 
 
 def pyramid(f, v, nb_scales):
