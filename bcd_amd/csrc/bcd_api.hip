@@ -1030,6 +1030,12 @@ int bcd_hip_set_strict_eigensolver(int enabled)
     return BCD_HIP_OK;
 }
 
+int bcd_hip_set_fused_prepare_solve(int enabled)
+{
+    bcd_bayes27_set_fused_prepare_solve(enabled);
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_set_fast_similarity(bcd_hip_ctx *ctx, int enabled)
 {
     if (!ctx) return BCD_HIP_EINVAL;

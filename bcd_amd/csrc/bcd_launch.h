@@ -112,6 +112,12 @@ hipError_t bcd_launch_bayes_weak_tiles_layers(const BcdLayerTable &t, int layers
 size_t bcd_bayes27_record_bytes();
 void bcd_bayes27_set_strict_eigensolver(int on);
 float bcd_bayes27_conv2(int strict);
+void bcd_bayes27_set_fused_prepare_solve(int on);
+int bcd_bayes27_fused_prepare_solve();
+// the prepare and eigensolver phases of a chunk on their own (default search radius; records laid out as by bcd_launch_bayes27), fused or as two launches
+hipError_t bcd_launch_prepare_solve27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
+                                      int *d_work, int num_cus, int W, int H, float *records, hipStream_t st, const int *d_nb_items, int fused);
+hipError_t bcd_launch_count_differing_words(const void *a, const void *b, size_t words, unsigned long long *d_count, hipStream_t st);
 hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blocks, float *eig, float *V, hipStream_t st, float conv2 = 1e-12f, float *Aout = nullptr,
                                      const int *d_n = nullptr, int first_item = 0);
 // d_spectral: += items whose inverse took the spectral branch; defer_redo != 0: the caller reads *d_spectral after its next synchronisation and calls

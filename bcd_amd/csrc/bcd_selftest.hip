@@ -192,6 +192,42 @@ int bcd_hip_eig27_batch_rule(bcd_hip_ctx *ctx, const float *d_A, int n, float *d
     return BCD_HIP_OK;
 }
 
+int bcd_hip_selftest_prepare_solve(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixcov, const uint32_t *d_mask, const int32_t *d_list,
+                                   int capacity, int list_len, int W, int H, int search_radius, int cu_share_pct, int64_t *differing_words)
+{
+    if (!ctx || !d_colors || !d_pixcov || !d_mask || !d_list || !differing_words || capacity <= 0 || W < 3 || H < 3) return bad(ctx, "bad argument");
+    if (search_radius != 6) { set_err(ctx, "the fused kernel serves search radius 6"); return BCD_HIP_EUNSUPPORTED; }
+    if (cu_share_pct < 1 || cu_share_pct > 100) return bad(ctx, "bad CU share");
+    DEVICE_GUARD(ctx);
+    touch(ctx->main);
+    Work &wk = ctx->main;
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
+    const size_t bytes = bcd_bayes27_record_bytes() * (size_t)capacity;
+    // what is compared: everything in front of the redo list, and the list's counter
+    const size_t words = (bytes - 2 * sizeof(int) * (size_t)capacity) / 4 + 1;
+    DevAlloc rec[2], len;
+    for (int i = 0; i < 2; ++i)
+        if (hipMalloc(&rec[i].p, bytes) != hipSuccess) { set_err(ctx, "hipMalloc"); return BCD_HIP_ENOMEM; }
+    HIPCHK(ctx, hipMalloc(&len.p, sizeof(int)));
+    const int cus = std::max(1, ctx->num_cus * cu_share_pct / 100);
+    unsigned long long *d_cnt = &wk.d_counters()->selftest.result;
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, sizeof(*d_cnt), wk.stream));
+    if (list_len >= 0) HIPCHK(ctx, hipMemcpyAsync(len.p, &list_len, sizeof(int), hipMemcpyHostToDevice, wk.stream));
+    for (int fused = 0; fused < 2; ++fused) {
+        HIPCHK(ctx, hipMemsetAsync(rec[fused].p, 0xA5, bytes, wk.stream)); // (row 27 of V, the padding of noise + mean and records past the list's end are never written)
+        HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream));
+        HIPCHK(ctx, bcd_launch_prepare_solve27(d_colors, d_pixcov, d_mask, d_list, 0, capacity, (int *)wk.work_q.p, cus, W, H, (float *)rec[fused].p, wk.stream,
+                                               list_len >= 0 ? (const int *)len.p : nullptr, fused));
+    }
+    HIPCHK(ctx, bcd_launch_count_differing_words(rec[0].p, rec[1].p, words, d_cnt, wk.stream));
+    unsigned long long h = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    *differing_words = (int64_t)h;
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_selftest_division(bcd_hip_ctx *ctx, uint32_t seed, int64_t samples, int64_t *mismatches)
 {
     if (!ctx || !mismatches || samples <= 0) return bad(ctx, "bad argument");

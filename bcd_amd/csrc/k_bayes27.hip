@@ -7,6 +7,8 @@
 //   k_finish27w                   FINISH   clamp, inverses, Step 2, final estimates, aggregation -- the 27 x 27 algebra in registers on the
 //                                          matrix core (default search radius); items whose inverse needs the spectral branch go to a redo list
 //   k_bayes27w<2> / k_bayes27<2>  FINISH   the same through LDS matrices: the redo list / the other search radii
+//   k_prepare_solve27             PREPARE + SOLVE in one kernel, a pair of items per task: what the default search radius launches in place of the
+//                                          first two (bcd_hip_set_fused_prepare_solve; the records are the same bits)
 // The `w` kernels serve the default search radius b = 6: the 15 x 15 pixel window around p is staged in LDS once and every member
 // access is an LDS read; other radii take the gather kernels (members fetched from global memory).
 //
@@ -550,28 +552,45 @@ __device__ __forceinline__ void jacobi_super_round(float (&vrow)[JLD], float *sr
         __builtin_amdgcn_sched_barrier(0);
 }
 
-__global__ __launch_bounds__(64, 3) void k_jacobi27_quads(const float *Ain, int n, int *work, float *__restrict__ eig,
-                                                          float *__restrict__ Vout, float conv2, float *Aout, const int *d_n, int first_item)
+// what a lane of k_jacobi27_quads knows about its place in the solver's LDS area (2 * JQ_HALF + 32 floats: two matrices with their scales and rotation
+// tables, then the placement table)
+struct JqLane {
+    float *Ah, *dv_h, *rot_h, *src, *dst_x, *dst_y;
+    const float *wsrc;
+    const int *place_tab;
+    int h, r, me, sx, sy;
+    bool isRow;
+};
+constexpr int JQ_LDS = 2 * JQ_HALF + 32;            // floats of the solver's LDS area
+
+// the lane's constants; writes the placement table (the caller orders it before the first solve with wave_sync)
+__device__ __forceinline__ JqLane jq_lane_setup(float *lds, int lane)
 {
-    n = items_on_device(d_n, first_item, n);
-    __shared__ float4 lds4[(2 * JQ_HALF + 32) / 4];
-    float *lds = reinterpret_cast<float *>(lds4);
+    JqLane L;
     int *place_tab = reinterpret_cast<int *>(lds + 2 * JQ_HALF);
-    const int lane = threadIdx.x, h = lane >> 5, r = lane & 31;
-    const bool isRow = r < KP;
+    L.place_tab = place_tab;
+    L.h = lane >> 5; L.r = lane & 31;
+    L.isRow = L.r < KP;
     if (lane < KP) place_tab[lane] = JPLACE[lane];
-    float *Ah = lds + h * JQ_HALF, *dv_h = Ah + JQ_MAT, *rot_h = dv_h + 32;
-    const int rr_ = isRow ? r : JIDLE_ROW;
-    const int sx = isRow ? JSX[rr_] : 0, sy = isRow ? JSY[rr_] : 0;
-    float *src = Ah + JPLACE[rr_];                  // (idle lanes: a row of their own ds_read_b128 bank group)
-    float *dst_x = Ah + JPLACE[sx], *dst_y = Ah + JPLACE[sy];
-    const float *wsrc = src + (isRow ? (r & ~3) : 0);   // the quad's columns of my row
-    const int me = r & 3;
-    wave_sync();
-    WorkCursor cursor = work_begin();
-    for (;;) {
-        const int pair = work_next(work, (n + 1) / 2, lane, cursor);
-        if (pair < 0) break;
+    L.Ah = lds + L.h * JQ_HALF; L.dv_h = L.Ah + JQ_MAT; L.rot_h = L.dv_h + 32;
+    const int rr_ = L.isRow ? L.r : JIDLE_ROW;
+    L.sx = L.isRow ? JSX[rr_] : 0; L.sy = L.isRow ? JSY[rr_] : 0;
+    L.src = L.Ah + JPLACE[rr_];                     // (idle lanes: a row of their own ds_read_b128 bank group)
+    L.dst_x = L.Ah + JPLACE[L.sx]; L.dst_y = L.Ah + JPLACE[L.sy];
+    L.wsrc = L.src + (L.isRow ? (L.r & ~3) : 0);    // the quad's columns of my row
+    L.me = L.r & 3;
+    return L;
+}
+
+// one task of k_jacobi27_quads: the matrices 2 pair and 2 pair + 1 of Ain (n in all) from memory through the sweeps to eig / Vout / Aout
+__device__ __forceinline__ void jacobi_quads_pair(const JqLane &L, int pair, int n, const float *Ain, float *__restrict__ eig, float *__restrict__ Vout,
+                                                  float conv2, float *Aout)
+{
+        const int h = L.h, r = L.r, me = L.me, sx = L.sx, sy = L.sy;
+        const bool isRow = L.isRow;
+        float *Ah = L.Ah, *dv_h = L.dv_h, *rot_h = L.rot_h, *src = L.src, *dst_x = L.dst_x, *dst_y = L.dst_y;
+        const float *wsrc = L.wsrc;
+        const int *place_tab = L.place_tab;
         const int first = 2 * pair;
         const int item = first + h;
         const bool live = item < n;
@@ -654,6 +673,21 @@ __global__ __launch_bounds__(64, 3) void k_jacobi27_quads(const float *Ain, int 
             }
         }
         wave_sync(); // the next pair reuses the LDS
+}
+
+__global__ __launch_bounds__(64, 3) void k_jacobi27_quads(const float *Ain, int n, int *work, float *__restrict__ eig,
+                                                          float *__restrict__ Vout, float conv2, float *Aout, const int *d_n, int first_item)
+{
+    n = items_on_device(d_n, first_item, n);
+    __shared__ float4 lds4[JQ_LDS / 4];
+    const int lane = threadIdx.x;
+    const JqLane L = jq_lane_setup(reinterpret_cast<float *>(lds4), lane);
+    wave_sync();
+    WorkCursor cursor = work_begin();
+    for (;;) {
+        const int pair = work_next(work, (n + 1) / 2, lane, cursor);
+        if (pair < 0) break;
+        jacobi_quads_pair(L, pair, n, Ain, eig, Vout, conv2, Aout);
     }
 }
 
@@ -1567,6 +1601,37 @@ __device__ __attribute__((noinline)) void win_write_records(float *__restrict__ 
     if (lane < K) recX[P * 6 + lane] = poisoned ? __builtin_nanf("") : mean[lane];
 }
 
+// PHASE 1 on an LDS area of W1L<B>::BYTES: what stays in it from item to item (member slots past |S| are read, never used: they hold codes -- x 3 --
+// inside the window; component 27 of the mean is the zero padding) ...
+template <int B>
+__device__ __forceinline__ void win_prepare_lds_init(float *lds, int lane)
+{
+    uint16_t *mem = reinterpret_cast<uint16_t *>(lds + W1L<B>::MEM);
+    float *mean = lds + W1L<B>::NOISE + 56;
+    for (int e = lane; e < W1L<B>::MEM_SLOTS; e += 64) mem[e] = (uint16_t)((WinT<B>::AW + 1) * 3);
+    if (lane == 0) mean[K] = 0.f;
+    __syncthreads();
+}
+
+// ... and one item: the records of item `slot` of the chunk from the windows around its pixel (the whole wavefront on one item)
+template <int B>
+__device__ __forceinline__ void win_prepare_item(float *lds, int slot, const float *__restrict__ colors, const float *__restrict__ pixcov,
+                                                 const uint32_t *__restrict__ mask, const int32_t *__restrict__ list, int first_item, const Geom27 &g,
+                                                 const Records27 &rec, int lane)
+{
+    // colour window | covariance window (later the 28 x 29 covariance tile) | noise | mean | members
+    float *cwin = lds, *nwin = cwin + W1L<B>::NWIN, *noise = lds + W1L<B>::NOISE, *mean = noise + 56; // (54 noise components; offsets stay multiples of 16 bytes)
+    uint16_t *mem = reinterpret_cast<uint16_t *>(lds + W1L<B>::MEM);
+    const int W = g.W, H = g.H;
+    const int p = __builtin_amdgcn_readfirstlane(list[first_item + slot]);
+    const int pr = p / W, pc = p - pr * W;
+    float *recA = rec.A + (size_t)slot * MSZ, *recC = rec.C + (size_t)slot * MSZ, *recX = rec.aux + (size_t)slot * AUX27;
+    const int n = win_stage_phase1<B>(cwin, nwin, mem, colors, pixcov, mask, p, pr, pc, W, H, g.words, lane);
+    win_noise_mean<B>(noise, mean, cwin, nwin, mem, n, lane, pixcov, (pr - (B + 1)) * W + pc - (B + 1), W);
+    win_covariance<B>(nwin /* tile: the covariance window (if there is one) is dead by then */, cwin, mean, mem, n, lane);
+    win_write_records(recA, recC, recX, nwin, noise, mean, lane);
+}
+
 template <int PHASE, int B = WB>
 __global__ __launch_bounds__(64, PHASE == 1 ? 5 : 3) void k_bayes27w(const float *__restrict__ colors, const float *__restrict__ pixcov,
                                                  const uint32_t *__restrict__ mask, const int32_t *__restrict__ list,
@@ -1592,9 +1657,12 @@ __global__ __launch_bounds__(64, PHASE == 1 ? 5 : 3) void k_bayes27w(const float
     float *fl = mean + KP;                         // PHASE 2 only
     uint16_t *mem = reinterpret_cast<uint16_t *>(PHASE == 1 ? lds + W1L<B>::MEM : fl + KP);
     static_assert(WPIX * 3 <= MSZ, "the colour window fits a matrix buffer");
-    for (int e = lane; e < (PHASE == 1 ? W1L<B>::MEM_SLOTS : WinT<B>::MEM); e += 64) mem[e] = (uint16_t)((WinT<B>::AW + 1) * (PHASE == 1 ? 3 : 1)); // (PHASE 1 keeps codes x 3; entries past |S| are read, never used: keep them inside the window)
-    if (lane == 0) mean[K] = 0.f;
-    __syncthreads();
+    if (PHASE == 1) win_prepare_lds_init<B>(lds, lane);
+    else {
+        for (int e = lane; e < WinT<B>::MEM; e += 64) mem[e] = (uint16_t)(WinT<B>::AW + 1); // (entries past |S| are read, never used: keep them inside the window)
+        if (lane == 0) mean[K] = 0.f;
+        __syncthreads();
+    }
     const int W = g.W, H = g.H;
 
   WorkCursor cursor = work_begin();
@@ -1607,10 +1675,7 @@ __global__ __launch_bounds__(64, PHASE == 1 ? 5 : 3) void k_bayes27w(const float
     float *recA = rec.A + (size_t)slot * MSZ, *recC = rec.C + (size_t)slot * MSZ, *recX = rec.aux + (size_t)slot * AUX27;
 
   if (PHASE == 1) {
-    const int n = win_stage_phase1<B>(cwin, nwin, mem, colors, pixcov, mask, p, pr, pc, W, H, g.words, lane);
-    win_noise_mean<B>(noise, mean, cwin, nwin, mem, n, lane, pixcov, (pr - (B + 1)) * W + pc - (B + 1), W);
-    win_covariance<B>(nwin /* tile: the covariance window (if there is one) is dead by then */, cwin, mean, mem, n, lane);
-    win_write_records(recA, recC, recX, nwin, noise, mean, lane);
+    win_prepare_item<B>(lds, slot, colors, pixcov, mask, list, first_item, g, rec, lane);
     __syncthreads(); // the next item reuses the LDS
   } else {
     const int n = decode_members_win<WB>(mask, p, g.words, mem, lane);
@@ -1741,6 +1806,62 @@ __global__ __launch_bounds__(64, PHASE == 1 ? 5 : 3) void k_bayes27w(const float
     __syncthreads(); // the next item reuses the LDS
   }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_prepare_solve27: PREPARE and SOLVE of the windowed path in one persistent kernel.  A task is a PAIR of items, as in k_jacobi27_quads: the
+// wavefront prepares item 2 k, then item 2 k + 1 (the out-of-line phases of k_bayes27w<1>, the whole wavefront on one item at a time), and
+// then solves the pair (the task of k_jacobi27_quads).  The prepare phase waits for its gathers and uses a third of a SIMD's issue slots, the
+// solver is issue-bound: as two kernels the chip ran at the first one's rate until its last item was done; here a wavefront that gathers
+// shares its SIMD with two that rotate.  The data flow is the two kernels': the records A, C, noise and mean go to memory, the solver reads the
+// pair's A back (L2-hot; written by other lanes of this wavefront: barrier + workgroup fence) and leaves eig, V and E o Phi in place of A --
+// the same bits as the two launches.
+// LDS: ONE area of W1L<B>::BYTES.  The solver's JQ_LDS floats overlay the two windows of the prepare phase, which are dead once an item's
+// records are written; the noise, the mean and the member slots lie behind them and keep what win_prepare_lds_init left there.  The solver's
+// placement table lies inside the overlay and is rewritten per task, with the lane's constants (derived per task from a lane number the
+// compiler cannot see through: kept across the out-of-line calls they would be spilled).
+// No wavefront waits for another one: the only barriers are those of the workgroup's own 64 lanes.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int B>
+__global__ __launch_bounds__(64, 3) void k_prepare_solve27(const float *__restrict__ colors, const float *__restrict__ pixcov,
+                                                           const uint32_t *__restrict__ mask, const int32_t *__restrict__ list, int first_item,
+                                                           int nb_items, int *work, Geom27 g, Records27 rec, int *redo /* optional: [0] is cleared */,
+                                                           float conv2, const int *d_n)
+{
+    static_assert(W1L<B>::COV_WINDOW, "the default search radius");
+    static_assert(JQ_LDS <= W1L<B>::NOISE && JQ_LDS * sizeof(float) <= W1L<B>::BYTES, "the solver's area overlays the windows only");
+    extern __shared__ float lds[];
+    const int lane0 = threadIdx.x;
+    const int n = items_on_device(d_n, first_item, nb_items);
+    // (the kernel opens the chunk: it clears the redo list's counter for the finish kernel that follows)
+    if (redo && blockIdx.x == 0 && lane0 == 0) redo[0] = 0;
+    win_prepare_lds_init<B>(lds, lane0);
+    WorkCursor cursor = work_begin();
+    for (;;) {
+        const int pair = work_next(work, (n + 1) / 2, lane0, cursor);
+        if (pair < 0) break;
+        win_prepare_item<B>(lds, 2 * pair, colors, pixcov, mask, list, first_item, g, rec, lane0);
+        if (2 * pair + 1 < n) { // (wave-uniform; an absent second item stays the identity matrix in the solver)
+            __syncthreads(); // the second item reuses the LDS
+            win_prepare_item<B>(lds, 2 * pair + 1, colors, pixcov, mask, list, first_item, g, rec, lane0);
+        }
+        // the pair's A is in memory, every lane is done with the windows
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        int lane = lane0;
+        asm volatile("" : "+v"(lane));
+        const JqLane L = jq_lane_setup(lds, lane);
+        wave_sync();
+        jacobi_quads_pair(L, pair, n, rec.A, rec.eig, rec.V, conv2, rec.A);
+    }
+}
+
+// number of 32-bit words in which two buffers differ (bcd_hip_selftest_prepare_solve)
+__global__ void k_count_differing_words(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, size_t words, unsigned long long *count)
+{
+    unsigned int mine = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) mine += a[i] != b[i];
+    if (mine) atomicAdd(count, (unsigned long long)mine);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2032,6 +2153,36 @@ static float jacobi_conv2()
 // the two rules by name, for the stand-alone eigensolver entry point (bcd_hip_eig27_batch_rule)
 float bcd_bayes27_conv2(int strict) { return strict ? JACOBI_CONV2_STRICT : JACOBI_CONV2_CORRECTED; }
 
+// PREPARE and SOLVE of the windowed path as one kernel or as two: BCD_HIP_PREPARE_SOLVE_SPLIT=1 or bcd_hip_set_fused_prepare_solve(0) keep the
+// two launches (the A/B partner: the records are the same bits either way, tests/test_gpu_prepare_solve_fused.py)
+static std::atomic<int> g_fused_prepare_solve{ -1 };
+void bcd_bayes27_set_fused_prepare_solve(int on) { g_fused_prepare_solve.store(on ? 1 : 0); }
+int bcd_bayes27_fused_prepare_solve()
+{
+    int v = g_fused_prepare_solve.load();
+    if (v < 0) { const char *e = getenv("BCD_HIP_PREPARE_SOLVE_SPLIT"); v = (e && e[0] == '1') ? 0 : 1; g_fused_prepare_solve.store(v); }
+    return v;
+}
+
+// the records A (then E o Phi), C, noise + mean, eig and V of a chunk, default search radius: k_prepare_solve27, or k_bayes27w<1> and the eigensolver
+// (which is also what BCD_HIP_JACOBI_PAIRS=1, the comparison eigensolver, gets).  d_work: the queues of the prepare kernel, then the solver's.
+static hipError_t launch_prepare_solve27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
+                                         int *d_work, int num_cus, const Geom27 &g, const Records27 &rec, int *redo, hipStream_t st, const int *dn, int fused)
+{
+    static const bool pairs = [] { const char *e = getenv("BCD_HIP_JACOBI_PAIRS"); return e && e[0] == '1'; }();
+    const size_t wl1 = W1L<WB>::BYTES;
+    if (fused && !pairs) {
+        hipLaunchKernelGGL(k_prepare_solve27<WB>, dim3(std::min((nb_items + 1) / 2, num_cus * 12)), dim3(64), wl1, st, colors, pixcov, mask, list, first_item,
+                           nb_items, d_work, g, rec, redo, jacobi_conv2(), dn);
+        return hipGetLastError();
+    }
+    const int w_cu1 = (int)std::min<size_t>(20, (size_t)160 * 1024 / wl1);
+    hipLaunchKernelGGL(k_bayes27w<1>, dim3(std::min(nb_items, num_cus * w_cu1)), dim3(64), wl1, st, colors, pixcov, mask, list, first_item, nb_items,
+                       d_work, g, 0.f, rec, (float *)nullptr, (int32_t *)nullptr, (const int *)redo, dn);
+    return bcd_launch_jacobi27_batch(rec.A, nb_items, d_work + BCD_WORK_QUEUES * BCD_WORK_STRIDE, std::min((nb_items + 1) / 2, num_cus * 12), rec.eig, rec.V, st,
+                                     jacobi_conv2(), rec.A, dn, first_item);
+}
+
 // Full estimate of items [first_item, first_item + nb_items) of `list`: three launches; `records` holds nb_items records
 // (bcd_bayes27_record_bytes() each), d_work BCD_WORK_INTS zeroed ints (the work queues of the three kernels).
 hipError_t bcd_launch_bayes27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
@@ -2056,14 +2207,12 @@ hipError_t bcd_launch_bayes27(const float *colors, const float *pixcov, const ui
     const int per_cu1 = (int)std::min<size_t>(20, (size_t)160 * 1024 / lds1), per_cu2 = (int)std::min<size_t>(12, (size_t)160 * 1024 / lds2);
     if (b == WB) {
         // default search radius: the windowed kernels (members read from LDS windows)
-        const size_t wl1 = W1L<WB>::BYTES;
         const size_t wl2 = (size_t)W2_MEM * sizeof(float) + WMEM * sizeof(uint16_t);
-        const int w_cu1 = (int)std::min<size_t>(20, (size_t)160 * 1024 / wl1), w_cu2 = (int)std::min<size_t>(12, (size_t)160 * 1024 / wl2);
+        const int w_cu2 = (int)std::min<size_t>(12, (size_t)160 * 1024 / wl2);
         static const bool lds_algebra = [] { const char *e = getenv("BCD_HIP_FINISH_LDS"); return e && e[0] == '1'; }();
         int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP); // (the register-resident finish; cleared by the prepare kernel)
-        hipLaunchKernelGGL(k_bayes27w<1>, dim3(std::min(nb_items, num_cus * w_cu1)), dim3(64), wl1, st, colors, pixcov, mask, list, first_item, nb_items,
-                           d_work, g, min_eig, rec, sum, cnt, lds_algebra ? nullptr : redo, dn);
-        { hipError_t e = bcd_launch_jacobi27_batch(rec.A, nb_items, d_work + BCD_WORK_QUEUES * BCD_WORK_STRIDE, std::min((nb_items + 1) / 2, num_cus * 12), rec.eig, rec.V, st, jacobi_conv2(), rec.A, dn, first_item); if (e != hipSuccess) return e; }
+        { hipError_t e = launch_prepare_solve27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, g, rec, lds_algebra ? nullptr : redo, st, dn,
+                                                bcd_bayes27_fused_prepare_solve()); if (e != hipSuccess) return e; }
         if (lds_algebra)
             hipLaunchKernelGGL(k_bayes27w<2>, dim3(std::min(nb_items, num_cus * w_cu2)), dim3(64), wl2, st, colors, pixcov, mask, list, first_item, nb_items,
                                d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, nullptr, dn);
@@ -2161,5 +2310,31 @@ hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blo
     // (the comparison kernel keeps the plain rule: its residual is then far below what the correction of the finish kernels would notice)
     if (pairs) hipLaunchKernelGGL((k_jacobi27_batch<true, true>), dim3(blocks), dim3(64), 0, st, A, n, d_work, eig, V, 1e-12f, Aout, d_n, first_item);
     else hipLaunchKernelGGL(k_jacobi27_quads, dim3(blocks), dim3(64), 0, st, A, n, d_work, eig, V, conv2, Aout, d_n, first_item);
+    return hipGetLastError();
+}
+
+// bcd_hip_selftest_prepare_solve: PREPARE and SOLVE of one chunk (default search radius) into `records` (bcd_bayes27_record_bytes() per item, as
+// bcd_launch_bayes27 lays them out), as two launches or fused; d_work: BCD_WORK_INTS zeroed ints
+hipError_t bcd_launch_prepare_solve27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
+                                      int *d_work, int num_cus, int W, int H, float *records, hipStream_t st, const int *d_nb_items, int fused)
+{
+    if (nb_items <= 0) return hipSuccess;
+    Geom27 g;
+    g.W = W; g.H = H; g.b = WB; g.side = 2 * WB + 1; g.words = (g.side * g.side + 31) / 32; g.maxS = g.side * g.side;
+    Records27 rec;
+    rec.A = records;
+    rec.V = rec.A + (size_t)nb_items * MSZ;
+    rec.C = rec.V + (size_t)nb_items * MSZ;
+    rec.aux = rec.C + (size_t)nb_items * MSZ;
+    rec.eig = rec.aux + (size_t)nb_items * AUX27;
+    int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP);
+    return launch_prepare_solve27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, g, rec, redo, st, d_nb_items, fused);
+}
+
+hipError_t bcd_launch_count_differing_words(const void *a, const void *b, size_t words, unsigned long long *d_count, hipStream_t st)
+{
+    if (words == 0) return hipSuccess;
+    const int blocks = (int)std::min<size_t>(1024, (words + 255) / 256);
+    hipLaunchKernelGGL(k_count_differing_words, dim3(blocks), dim3(256), 0, st, (const uint32_t *)a, (const uint32_t *)b, words, d_count);
     return hipGetLastError();
 }

@@ -249,7 +249,7 @@ class ScaleStats(C.Structure):
 # every symbol include/bcd_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
-    "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
+    "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_fused_prepare_solve", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
     "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_denoise_layers_host_ex",
     "bcd_hip_spike_map", "bcd_hip_spike_apply", "bcd_hip_spike_filter_layers",
     "bcd_hip_similarity_masks_moments", "bcd_hip_window_distances_moments", "bcd_hip_denoise_moments", "bcd_hip_denoise_moments_host",
@@ -270,7 +270,7 @@ SYMBOLS = [
     "bcd_hip_accum_layer_statistics", "bcd_hip_accum_layers_state_info", "bcd_hip_accum_layers_state_bytes", "bcd_hip_accum_export_layers", "bcd_hip_accum_import_layers",
     "bcd_hip_accum_merge_layers_state",
     "bcd_hip_visit_order", "bcd_hip_scale_seed", "bcd_hip_strip_order_seed", "bcd_hip_selftest_division", "bcd_hip_selftest_distance_kernels", "bcd_hip_selftest_approx_distance", "bcd_hip_selftest_bin_work", "bcd_hip_eig27_batch", "bcd_hip_eig27_batch_rule",
-    "bcd_hip_selftest_sparse_upload", "bcd_hip_selftest_host_stream", "bcd_hip_approx_planes", "bcd_hip_selftest_active_lists",
+    "bcd_hip_selftest_sparse_upload", "bcd_hip_selftest_host_stream", "bcd_hip_approx_planes", "bcd_hip_selftest_active_lists", "bcd_hip_selftest_prepare_solve",
 ]
 
 _lib = None
@@ -1047,6 +1047,19 @@ class Context:
         self._chk(lib().bcd_hip_eig27_batch_rule(self.h, _dp(A), n, _dp(eig), _dp(V), C.byref(ms), 1 if production_rule else 0))
         return eig, V, ms.value
 
+    def selftest_prepare_solve(self, col, pixcov, mask, items, capacity=None, list_len=None, b=6, cu_share_pct=100):
+        """bcd_hip_selftest_prepare_solve: the prepare and eigensolver phases on the list `items` (int32 device tensor of pixel indices line * W + column),
+        as two kernels and as the fused kernel, into records for `capacity` items (default: the list's length); list_len: None = the kernels take
+        `capacity` items, otherwise the list's length, which they read on the device.  -> number of 32-bit words in which the two sets of records differ"""
+        H, W, _ = col.shape
+        cap = int(items.numel() if capacity is None else capacity)
+        assert mask.shape[0] == H and mask.shape[1] == W and pixcov.shape[:2] == col.shape[:2]
+        assert min(cap, cap if list_len is None else int(list_len)) <= items.numel()
+        n = C.c_int64(-1)
+        self._chk(lib().bcd_hip_selftest_prepare_solve(self.h, _dp(col), _dp(pixcov), _dp(mask), _dp(items), cap, -1 if list_len is None else int(list_len),
+                                                       W, H, int(b), int(cu_share_pct), C.byref(n)))
+        return n.value
+
     def selftest_division(self, samples, seed=1):
         n = C.c_int64(-1)
         self._chk(lib().bcd_hip_selftest_division(self.h, C.c_uint32(seed), C.c_int64(samples), C.byref(n)))
@@ -1453,6 +1466,11 @@ MULTI_ID_BYTES = 128
 def set_strict_eigensolver(on):
     """process-wide: the fully converged stopping rule of the estimate chain's eigensolver (bcd_hip_set_strict_eigensolver)"""
     lib().bcd_hip_set_strict_eigensolver(1 if on else 0)
+
+
+def set_fused_prepare_solve(on):
+    """process-wide: the prepare and eigensolver phases of a full estimate as one kernel (default) or as two (bcd_hip_set_fused_prepare_solve)"""
+    lib().bcd_hip_set_fused_prepare_solve(1 if on else 0)
 
 
 def rccl_info():

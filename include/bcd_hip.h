@@ -97,6 +97,11 @@ int  bcd_hip_set_fast_similarity(bcd_hip_ctx *ctx, int enabled);
  * instead of the production rule (2e-9 + first-order correction of the positive part): ~1.5 % of a step for a 3x smaller deviation on
  * ill-conditioned low-sample frames (4K at 8 spp: 2.9e-6 instead of 9.8e-6 from the CPU path).  Default: the environment's BCD_HIP_STRICT_EIGEN (0). */
 int  bcd_hip_set_strict_eigensolver(int enabled);
+/* process-wide: 1 (default) = the prepare and eigensolver phases of a full estimate (patch radius 1, search radius 6) run as ONE persistent kernel,
+ * k_prepare_solve27 -- a wavefront prepares two items and solves the pair --, 0 = as two kernels, one after the other.  The records they leave, and
+ * therefore the results, are the same bits either way (bcd_hip_selftest_prepare_solve).  Initial value: 0 if the environment has
+ * BCD_HIP_PREPARE_SOLVE_SPLIT=1. */
+int  bcd_hip_set_fused_prepare_solve(int enabled);
 /* share (1..100 %, default 100) of the device's CU slots the persistent estimate kernels of this context occupy.  A caller that
  * runs several contexts on one device at once lowers it for the contexts that have slack, so that the short kernels of the one on
  * the critical path find room beside them (bcd_hip_denoise does this itself for its coarse scales; the multi-GPU driver uses
@@ -841,6 +846,15 @@ int bcd_hip_eig27_batch(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig,
  * production_rule != 0 stops where the estimate chain stops by default, off^2 <= 2e-9 diag^2 -- WITHOUT the first-order correction the finish kernels
  * apply to the residual (it is not returned), so V diag(eig) V^T is then only accurate to sqrt(2e-9) |A|_F; 0 is bcd_hip_eig27_batch. */
 int bcd_hip_eig27_batch_rule(bcd_hip_ctx *ctx, const float *d_A, int n, float *d_eig, float *d_V, float *ms, int production_rule);
+
+/* the prepare and eigensolver phases of a full estimate, as two kernels and as the fused kernel, on the same list: d_list holds main-pixel indices
+ * (line * W + column, |S| >= 28, masks of search radius 6), `capacity` is the number of records the chunk is sized for and list_len the list's length:
+ * list_len < 0: the kernels process `capacity` items; otherwise the length is read on the DEVICE and min(capacity, list_len) items are processed (the
+ * path of a chunk launched ahead of the host's count).  cu_share_pct (1..100): share of the CU slots the grids are sized for.  Both runs start from
+ * records filled with one byte pattern; *differing_words = number of 32-bit words of the records (A after the solver, V, C, noise + mean, eigenvalues)
+ * and of the redo list's counter in which they differ afterwards.  The same device functions on the same inputs in the same order: 0. */
+int bcd_hip_selftest_prepare_solve(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixcov, const uint32_t *d_mask, const int32_t *d_list,
+                                   int capacity, int list_len, int W, int H, int search_radius, int cu_share_pct, int64_t *differing_words);
 
 /* ---- host utilities (no device work) ----------------------------------------------------------- */
 /* the visiting order implied by (random_order, seed): main-pixel linear indices line*W+col in
