@@ -252,6 +252,20 @@ def denoise_layers(layers, ns, hist, nscales=1, tau=1.0, b=6, min_eig=1e-8, rand
     return rc != 0, [outs[k] for k in range(L)]
 
 
+def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, after_clear=False):
+    """bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames of the sequence (addNeighbourFrame): neighbours is a list of (col, ns, hist, cov)
+    arrays of the frame's size, at most four.  after_clear: clearNeighbourFrames() and a second denoise() follow, whose result replaces the first.
+    Returns (ok, denoised frame)"""
+    H, W, D = hist.shape
+    F = len(neighbours)
+    stack = lambda k, d: np.ascontiguousarray(np.stack([np.asarray(f[k], np.float32).reshape(H, W, d) for f in neighbours]) if F else np.zeros((1, H, W, d)), np.float32)
+    out = np.zeros((H, W, 3), np.float32)
+    rc = lib().bcdcore_denoise_temporal(_fp(col), _fp(ns), _fp(hist), _fp(cov), _fp(stack(0, 3)), _fp(stack(1, 1)), _fp(stack(2, D)), _fp(stack(3, 6)), F, W, H, D,
+                                        int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed),
+                                        1 if after_clear else 0, _fp(out))
+    return rc != 0, out
+
+
 def denoise_moments(layers, ns, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, zero_bad=False, prefilter_factor=0.0,
                     prefilter_layers=False, var_floor=1e-8, devices=None):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with setMomentSelection(true, var_floor): no histogram image; layers[0] = (colours, covariances) is the

@@ -998,6 +998,7 @@ void bcd_hip_ctx_destroy(bcd_hip_ctx *ctx)
     for (int s = 0; s < MAX_SCALES; ++s)
         for (int k = 0; k < 2; ++k) if (ctx->guide_pyr[s][k].p) (void)hipFree(ctx->guide_pyr[s][k].p);
     for (DevBuf &hb : ctx->guide_host) if (hb.p) (void)hipFree(hb.p);
+    temporal_free(ctx);
     if (ctx->ev_pyramid) (void)hipEventDestroy(ctx->ev_pyramid);
     for (hipEvent_t ev : ctx->ev_upload) (void)hipEventDestroy(ev);
     if (ctx->upload_stream) (void)hipStreamDestroy(ctx->upload_stream);

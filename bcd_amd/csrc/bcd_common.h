@@ -94,6 +94,17 @@ struct BcdLayerTable {
     float *o[BCD_MAX_LAYERS];
 };
 
+// ---- neighbouring frames of a sequence (k_bayes_temporal.hip) --------------------------------------------------
+// The frame itself is entry 0, its neighbours follow in the caller's order; the device pointers of one launch travel by value.  mask[f] holds, for
+// every pixel of the frame, its similar set in frame f (entry 0: the in-frame masks), all in the layout of the in-frame masks.
+#define BCD_MAX_NEIGHBOURS 4
+struct BcdFrameTable {
+    const float *col[BCD_MAX_NEIGHBOURS + 1];
+    const float *pixcov[BCD_MAX_NEIGHBOURS + 1];
+    const uint32_t *mask[BCD_MAX_NEIGHBOURS + 1];
+    int n; // frames in use, 1 .. BCD_MAX_NEIGHBOURS + 1
+};
+
 // ---- spike prefilter through a source map (k_spike.hip) ---------------------------------------------------
 // One launch of k_spike_apply gathers up to BCD_SPIKE_MAX_IMAGES images of one depth; the image is blockIdx.y, the pointers travel by value.
 #define BCD_SPIKE_MAX_IMAGES 32

@@ -190,6 +190,15 @@ struct bcd_hip_ctx {
     } guide;
     DevBuf guide_pyr[MAX_SCALES][2]; // levels 1.. of the features and their variances
     DevBuf guide_host[2];            // host-buffer entry point: device copies of the features and their variances
+    // bcd_hip_denoise_temporal (bcd_temporal.hip): frame 0 is the frame itself, 1.. its neighbours.  Grow-only, like every buffer here
+    struct {
+        DevBuf pyr[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES][4]; // levels 1.. of every frame: colours, sample counts, histograms, covariances
+        DevBuf out[MAX_SCALES];                            // the outputs of the levels 1..
+        DevBuf pixcov[BCD_MAX_NEIGHBOURS + 1];             // per-pixel covariances of every frame at the scale in progress
+        DevBuf mask[BCD_MAX_NEIGHBOURS + 1];               // [1..]: the cross masks of the scale in progress
+        DevBuf count_nb;                                   // |S_f| of the neighbour in progress
+        DevBuf host[BCD_MAX_NEIGHBOURS + 1][4], host_out;  // host-buffer entry point: device copies
+    } temporal;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
     hipStream_t upload_stream = nullptr;        // host-buffer entry points: uploads run beside the kernels of the lines that have arrived
@@ -283,6 +292,9 @@ int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int 
 int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius);
 int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales);
 inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
+
+// ---- defined in bcd_temporal.hip
+void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
 
 // ---- defined in bcd_selection.hip
 // one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is

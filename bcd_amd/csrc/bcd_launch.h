@@ -19,6 +19,21 @@ hipError_t bcd_launch_masks_finish(int W, int H, int b, float tau, uint32_t *mas
                                    const float *hist, const float *ns, int D);
 hipError_t bcd_launch_window_distances(const float *T, const uint8_t *Cn, int W, int H, int w, int b, int r, int c, float *out, hipStream_t st);
 
+// ---- k_similarity_cross.hip
+hipError_t bcd_launch_pairdist_cross(const float *histA, const float *nsA, const float *histB, const float *nsB, int W, int H, int D, int b, float *T, uint8_t *Cn,
+                                     hipStream_t st);
+hipError_t bcd_launch_masks_cross(const float *T, const uint8_t *Cn, int W, int H, int w, int b, float tau, uint32_t *mask, int32_t *count, hipStream_t st);
+hipError_t bcd_launch_add_counts(int32_t *nsim, const int32_t *add, int64_t npix, hipStream_t st);
+hipError_t bcd_launch_window_distances_cross(const float *T, const uint8_t *Cn, int W, int H, int w, int b, int r, int c, float *out, hipStream_t st);
+
+// ---- k_bayes_temporal.hip, and the launcher of k_bayes27.hip that runs behind its prepare kernel
+hipError_t bcd_launch_prepare27t(const BcdFrameTable &t, const int32_t *list, int first_item, int nb_items, int *d_work, int num_cus, int W, int b, float *records,
+                                 hipStream_t st);
+hipError_t bcd_launch_bayes_weak_temporal(const BcdFrameTable &t, const int32_t *list, const int32_t *d_nlist, int blocks, int W, int b, float *sum, int32_t *cnt,
+                                          hipStream_t st);
+hipError_t bcd_launch_solve_finish27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items, int *d_work,
+                                     int num_cus, int W, int H, float min_eig, float *records, float *sum, int32_t *cnt, int *d_spectral, hipStream_t st);
+
 // ---- k_similarity_moments.hip
 hipError_t bcd_launch_pairdist_moments(const float *colors, const float *pixcov, int W, int H, int b, float var_floor, float *T, uint8_t *Cn, hipStream_t st);
 

@@ -1,0 +1,340 @@
+// bcd_temporal.hip -- similar patches from neighbouring frames of a sequence: the frame calls bcd_hip_denoise_temporal[_host], the
+// stage entry points of the cross-frame selection and of the estimate over several frames, and the driver glue.  The kernels are in k_similarity_cross.hip
+// and k_bayes_temporal.hip; the planes of one neighbour live in the main workspace's plane buffers (grow-only) and are consumed before the next
+// neighbour's are written.
+#include "bcd_ctx.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+static_assert(BCD_MAX_NEIGHBOURS == BCD_HIP_MAX_NEIGHBOURS, "the frame table of the kernels holds what the C ABI admits");
+
+namespace {
+
+// the refusals the stage calls share: the geometry rules of bcd_hip_similarity_masks
+int check_cross_stage(bcd_hip_ctx *ctx, int W, int H, int D, int w, int b)
+{
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    return check_params(ctx, W, H, D, &p);
+}
+
+// the T / C planes of every displacement between the frame and one neighbour, in the main workspace
+int cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b)
+{
+    const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
+    wk.planes.ready = false; // (the workspace's planes are overwritten)
+    HIPCHK(ctx, bcd_launch_pairdist_cross(d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    return BCD_HIP_OK;
+}
+
+// The estimate chain over the members of several frames (patch radius 1, search radius 6): the lists of processed pixels from the states and the TOTAL
+// |S|, the fallback kernel over all frames, and per chunk of full estimates the temporal prepare kernel followed by the unchanged solver and finish
+// kernels on the frame's own colours and in-frame masks.  The list lengths and the sum of |S| are in wk.h_counters->lists when the call returns (it
+// waits for them once, before the first chunk, and synchronises the stream at its end).
+int bayes_temporal(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
+                   float *d_sum, int32_t *d_count)
+{
+    constexpr int K = 27, CHUNK_MAX = 1 << 18; // (the chunk of bayes(): records in flight at a time)
+    const int64_t npix = (int64_t)W * H;
+    wk.redo.pending = false;
+    RCCHK(ensure(ctx, wk.strong, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.weak, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
+    Counters::Lists *d_c = &wk.d_counters()->lists, *h_c = &wk.h_counters->lists;
+    touch(wk); // (the counters and work queues are cleared here, whatever k_scale_begin left)
+    h_c->spectral = 0;
+    HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
+    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim_total, 0, npix, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, &d_c->n_strong, wk.stream, nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(h_c, d_c, offsetof(Counters::Lists, generic_work), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
+    const int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
+    HIPCHK(ctx, bcd_launch_bayes_weak_temporal(t, (const int32_t *)wk.weak.p, &d_c->n_weak, (int)std::min<int64_t>(std::max<int64_t>(1, npix / 7), (int64_t)cus * 32), W, b,
+                                               d_sum, d_count, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    const int n_strong = h_c->n_strong;
+    if (n_strong < 0 || n_strong > npix) return bad(ctx, "temporal estimate: the list exceeds the frame");
+    if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, bcd_bayes27_record_bytes() * (size_t)std::min(n_strong, CHUNK_MAX)));
+    for (int first = 0; first < n_strong; first += CHUNK_MAX) {
+        const int n = std::min(CHUNK_MAX, n_strong - first);
+        HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream)); // the work queues of the four kernels
+        HIPCHK(ctx, bcd_launch_prepare27t(t, (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, b, (float *)wk.gscratch.p, wk.stream));
+        HIPCHK(ctx, bcd_launch_solve_finish27(t.col[0], t.pixcov[0], t.mask[0], (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, H, min_eig,
+                                              (float *)wk.gscratch.p, d_sum, d_count, &d_c->spectral, wk.stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(&h_c->spectral, &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
+} // namespace
+
+extern "C" {
+
+int bcd_hip_bayes_accumulate_temporal(bcd_hip_ctx *ctx, const bcd_hip_stage_frame *frames, int nb_frames, const int32_t *d_nsim_total, const uint8_t *d_state, int W,
+                                      int H, int w, int b, float min_eig, float *d_sum, int32_t *d_count)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    // ---- everything is checked before any device work
+    if (!frames) return bad(ctx, "null frame list");
+    if (nb_frames < 1 || nb_frames > BCD_HIP_MAX_NEIGHBOURS + 1) return bad(ctx, "the number of frames must be between 1 and 5 (the frame and up to BCD_HIP_MAX_NEIGHBOURS neighbours)");
+    if (!d_nsim_total || !d_state || !d_sum || !d_count) return bad(ctx, "null image pointer");
+    for (int f = 0; f < nb_frames; ++f)
+        if (!frames[f].d_colors || !frames[f].d_pixel_cov || !frames[f].d_mask) return bad(ctx, "null image pointer in a frame");
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    RCCHK(check_params(ctx, W, H, 1, &p));
+    if (w != 1 || b != 6) { set_err(ctx, "the estimate over several frames supports patch radius 1 and search radius 6"); return BCD_HIP_EUNSUPPORTED; }
+    {
+        const size_t npix = (size_t)W * H, f4 = sizeof(float), words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+        if (overlap(d_sum, npix * 3 * f4, d_count, npix * 4) || overlap(d_sum, npix * 3 * f4, d_nsim_total, npix * 4) || overlap(d_sum, npix * 3 * f4, d_state, npix) ||
+            overlap(d_count, npix * 4, d_nsim_total, npix * 4) || overlap(d_count, npix * 4, d_state, npix))
+            return bad(ctx, "the accumulators overlap each other or the selection");
+        for (int f = 0; f < nb_frames; ++f)
+            for (const void *o : { (const void *)d_sum, (const void *)d_count })
+                if (overlap(o, o == d_sum ? npix * 3 * f4 : npix * 4, frames[f].d_colors, npix * 3 * f4) || overlap(o, o == d_sum ? npix * 3 * f4 : npix * 4, frames[f].d_pixel_cov, npix * 6 * f4) ||
+                    overlap(o, o == d_sum ? npix * 3 * f4 : npix * 4, frames[f].d_mask, npix * words * 4))
+                    return bad(ctx, "an accumulator overlaps an input image");
+    }
+    DEVICE_GUARD(ctx);
+    BcdFrameTable t = {};
+    t.n = nb_frames;
+    for (int f = 0; f < nb_frames; ++f) { t.col[f] = frames[f].d_colors; t.pixcov[f] = frames[f].d_pixel_cov; t.mask[f] = frames[f].d_mask; }
+    return bayes_temporal(ctx, ctx->main, t, d_nsim_total, d_state, W, H, b, min_eig, d_sum, d_count);
+}
+
+int bcd_hip_similarity_masks_cross(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D,
+                                   int w, int b, float tau, uint32_t *d_mask_nb, int32_t *d_count_nb)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_hist || !d_ns || !d_hist_nb || !d_ns_nb || !d_mask_nb || !d_count_nb) return bad(ctx, "bad argument");
+    RCCHK(check_cross_stage(ctx, W, H, D, w, b));
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    RCCHK(cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
+    HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask_nb, d_count_nb, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D,
+                                   int w, int b, int line, int col, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_hist || !d_ns || !d_hist_nb || !d_ns_nb || !h_out) return bad(ctx, "bad argument");
+    RCCHK(check_cross_stage(ctx, W, H, D, w, b));
+    if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    const int n = (2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
+    RCCHK(cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
+    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+} // extern "C"
+
+// =====================================================================================================================
+// The frame call.  Every neighbour gets its own pyramid, built with the reducers of the frame's; scale s uses level s of every frame; the scales run
+// coarse to fine, one after the other, on the main workspace, each through the stage calls of this library in the order of DESIGN.md section 16: the
+// in-frame selection (the code that computes it today), one cross pass per neighbour ahead of the marking, the marking on the in-frame masks and the
+// total |S|, the estimate over all frames, the finalisation, then the merge of the (already merged) coarser scale as in bcd_hip_denoise.
+// =====================================================================================================================
+void temporal_free(bcd_hip_ctx *ctx)
+{
+    auto &t = ctx->temporal;
+    for (auto &frame : t.pyr) for (auto &level : frame) for (DevBuf &b : level) if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : t.out) if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : t.pixcov) if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : t.mask) if (b.p) (void)hipFree(b.p);
+    if (t.count_nb.p) (void)hipFree(t.count_nb.p);
+    for (auto &frame : t.host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    if (t.host_out.p) (void)hipFree(t.host_out.p);
+}
+
+namespace {
+
+struct FrameLevel { const float *col, *ns, *hist, *cov; };
+
+// one scale: frames[0] the frame itself at this level
+int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale, float *d_out)
+{
+    Work &wk = ctx->main;
+    auto &tp = ctx->temporal;
+    const int w = prm->patch_radius, b = prm->search_radius;
+    const float tau = prm->hist_dist_threshold;
+    const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+    RCCHK(ensure(ctx, wk.mask, npix * words * sizeof(uint32_t)));
+    RCCHK(ensure(ctx, wk.nsim, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.state, npix));
+    RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
+    RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, tp.count_nb, npix * sizeof(int32_t)));
+    for (int f = 0; f < nf; ++f) {
+        RCCHK(ensure(ctx, tp.pixcov[f], npix * 6 * sizeof(float)));
+        if (f > 0) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
+    }
+    bcd_hip_scale_stats &st = ctx->stats[scale];
+    memset(&st, 0, sizeof(st));
+    st.width = W; st.height = H;
+    st.main_pixels = (int64_t)std::max(0, W - 2 * w) * std::max(0, H - 2 * w);
+    const bool prof = ctx->profiling;
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
+    // S_0: today's set, by the code that computes it today (its verdict and re-runs are inside the call); the cross passes follow it, ahead of the marking
+    RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
+    int32_t path = 0, borderline = 0, capacity = 0;
+    RCCHK(bcd_hip_similarity_last_path(ctx, &path, &borderline, &capacity));
+    BcdFrameTable t = {};
+    t.n = nf;
+    for (int f = 0; f < nf; ++f) {
+        HIPCHK(ctx, bcd_launch_pixel_cov(frames[f].cov, frames[f].ns, (int64_t)npix, (float *)tp.pixcov[f].p, wk.stream));
+        t.col[f] = frames[f].col; t.pixcov[f] = (const float *)tp.pixcov[f].p;
+        t.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : (const uint32_t *)tp.mask[f].p;
+        if (f == 0) continue;
+        RCCHK(cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
+        HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
+        HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
+    }
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
+    RCCHK(bcd_hip_active_set(ctx, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, W, H, w, b, 0, H, prm->marked_skip_probability, prm->use_random_pixel_order,
+                             bcd_hip_scale_seed(prm->order_seed, scale), (uint8_t *)wk.state.p, &st.active_rounds));
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[2], wk.stream));
+    HIPCHK(ctx, hipMemsetAsync(wk.sum.p, 0, npix * 3 * sizeof(float), wk.stream));
+    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
+    RCCHK(bayes_temporal(ctx, wk, t, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, prm->min_eigen_value, (float *)wk.sum.p, (int32_t *)wk.cnt.p));
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
+    HIPCHK(ctx, bcd_launch_finalize((const float *)wk.sum.p, (const int32_t *)wk.cnt.p, (int64_t)npix, d_out, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    const Counters::Lists &h = wk.h_counters->lists;
+    st.processed = (int64_t)h.n_strong + h.n_weak; st.fallback = h.n_weak; st.similar_total = h.sim_total; // (the sum of the TOTAL |S|)
+    st.similarity_path = path; st.borderline_pairs = borderline;                                          // (those of the in-frame pass)
+    st.cu_share = ctx->cu_share_pct;
+    st.spectral_inverses = h.spectral;
+    if (prof) {
+        st.ms_similarity = stage_ms(wk, 0, 1); // (includes the cross passes)
+        st.ms_active = stage_ms(wk, 1, 2);
+        st.ms_bayes = stage_ms(wk, 2, 3);
+        st.ms_total = stage_ms(wk, 0, 3);
+    }
+    return BCD_HIP_OK;
+}
+
+// the refusals of the two frame calls, before any device work
+int check_temporal_call(bcd_hip_ctx *ctx, const void *col, const void *ns, const void *hist, const void *cov, const bcd_hip_frame *nb, int n, int W, int H, int D,
+                        int nb_scales, const bcd_hip_params *prm, const void *out)
+{
+    if (n < 0 || n > BCD_HIP_MAX_NEIGHBOURS) return bad(ctx, "the number of neighbour frames must be between 0 and 4 (BCD_HIP_MAX_NEIGHBOURS)");
+    if (!col || !ns || !hist || !cov || !out) return bad(ctx, "null image pointer");
+    if (n > 0 && !nb) return bad(ctx, "null neighbour list");
+    for (int f = 0; f < n; ++f) {
+        if (!nb[f].d_colors || !nb[f].d_nsamples || !nb[f].d_histograms || !nb[f].d_covariances) return bad(ctx, "null image pointer in a neighbour frame");
+        if (nb[f].reserved) return bad(ctx, "the reserved pointer of a neighbour frame must be NULL");
+    }
+    RCCHK(check_params(ctx, W, H, D, prm));
+    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
+    if (n > 0 && (prm->patch_radius != 1 || prm->search_radius != 6)) {
+        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
+        ws /= 2; hs /= 2;
+        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
+    }
+    const size_t npix = (size_t)W * H, f4 = sizeof(float), no = npix * 3 * f4;
+    if (overlap(out, no, col, npix * 3 * f4) || overlap(out, no, ns, npix * f4) || overlap(out, no, hist, npix * D * f4) || overlap(out, no, cov, npix * 6 * f4))
+        return bad(ctx, "the output overlaps an input image");
+    for (int f = 0; f < n; ++f)
+        if (overlap(out, no, nb[f].d_colors, npix * 3 * f4) || overlap(out, no, nb[f].d_nsamples, npix * f4) || overlap(out, no, nb[f].d_histograms, npix * D * f4) ||
+            overlap(out, no, nb[f].d_covariances, npix * 6 * f4))
+            return bad(ctx, "the output overlaps an image of a neighbour frame");
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bcd_hip_denoise_temporal(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
+                             const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_temporal_call(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out));
+    if (nb_neighbours == 0) return bcd_hip_denoise(ctx, d_colors, d_nsamples, d_histograms, d_covariances, W, H, D, nb_scales, prm, d_out);
+    DEVICE_GUARD(ctx);
+    const int nf = nb_neighbours + 1, S = nb_scales;
+    auto &tp = ctx->temporal;
+    // ---- the pyramids (MultiscaleDenoiser.cpp:41-53) of every frame: level s has the dimensions of level s - 1 halved
+    std::vector<FrameLevel> lv((size_t)S * nf);
+    int ws[MAX_SCALES], hs[MAX_SCALES];
+    ws[0] = W; hs[0] = H;
+    lv[0] = { d_colors, d_nsamples, d_histograms, d_covariances };
+    for (int f = 1; f < nf; ++f) lv[f] = { neighbours[f - 1].d_colors, neighbours[f - 1].d_nsamples, neighbours[f - 1].d_histograms, neighbours[f - 1].d_covariances };
+    for (int s = 1; s < S; ++s) {
+        ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
+        const size_t np = (size_t)ws[s] * hs[s];
+        RCCHK(ensure(ctx, tp.out[s], np * 3 * sizeof(float)));
+        for (int f = 0; f < nf; ++f) {
+            DevBuf(&l)[4] = tp.pyr[f][s];
+            RCCHK(ensure(ctx, l[0], np * 3 * sizeof(float)));
+            RCCHK(ensure(ctx, l[1], np * sizeof(float)));
+            RCCHK(ensure(ctx, l[2], np * D * sizeof(float)));
+            RCCHK(ensure(ctx, l[3], np * 6 * sizeof(float)));
+            const FrameLevel &fine = lv[(size_t)(s - 1) * nf + f];
+            hipStream_t st = ctx->main.stream;
+            HIPCHK(ctx, bcd_launch_downscale(1, fine.col, ws[s - 1], hs[s - 1], 3, (float *)l[0].p, st));
+            HIPCHK(ctx, bcd_launch_downscale(0, fine.ns, ws[s - 1], hs[s - 1], 1, (float *)l[1].p, st));
+            HIPCHK(ctx, bcd_launch_downscale(0, fine.hist, ws[s - 1], hs[s - 1], D, (float *)l[2].p, st));
+            HIPCHK(ctx, bcd_launch_downscale_cov(fine.cov, fine.ns, ws[s - 1], hs[s - 1], (float *)l[3].p, st));
+            lv[(size_t)s * nf + f] = { (const float *)l[0].p, (const float *)l[1].p, (const float *)l[2].p, (const float *)l[3].p };
+        }
+    }
+    for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs (MultiscaleDenoiser.cpp:453-466), as in bcd_hip_denoise
+        float *out = s == 0 ? d_out : (float *)tp.out[s].p;
+        RCCHK(temporal_scale(ctx, &lv[(size_t)s * nf], nf, ws[s], hs[s], D, prm, s, out));
+        if (s < S - 1) RCCHK(bcd_hip_merge(ctx, out, ws[s], hs[s], (const float *)tp.out[s + 1].p, 3));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_denoise_temporal_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                                  const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_temporal_call(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out));
+    if (nb_neighbours == 0) return bcd_hip_denoise_host(ctx, h_colors, h_nsamples, h_histograms, h_covariances, W, H, D, nb_scales, prm, h_out);
+    DEVICE_GUARD(ctx);
+    auto &tp = ctx->temporal;
+    const size_t npix = (size_t)W * H, bytes[4] = { npix * 3 * sizeof(float), npix * sizeof(float), npix * D * sizeof(float), npix * 6 * sizeof(float) };
+    hipStream_t st = ctx->main.stream;
+    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
+    for (int f = 0; f <= nb_neighbours; ++f) { // whole uploads, no streaming
+        const float *src[4] = { f ? neighbours[f - 1].d_colors : h_colors, f ? neighbours[f - 1].d_nsamples : h_nsamples, f ? neighbours[f - 1].d_histograms : h_histograms,
+                                f ? neighbours[f - 1].d_covariances : h_covariances };
+        for (int k = 0; k < 4; ++k) {
+            RCCHK(ensure(ctx, tp.host[f][k], bytes[k]));
+            HIPCHK(ctx, hipMemcpyAsync(tp.host[f][k].p, src[k], bytes[k], hipMemcpyHostToDevice, st));
+        }
+        dev[f] = { (const float *)tp.host[f][0].p, (const float *)tp.host[f][1].p, (const float *)tp.host[f][2].p, (const float *)tp.host[f][3].p, nullptr };
+    }
+    RCCHK(ensure(ctx, tp.host_out, bytes[0]));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    RCCHK(bcd_hip_denoise_temporal(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, W, H, D, nb_scales, prm,
+                                   (float *)tp.host_out.p));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, tp.host_out.p, bytes[0], hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+} // extern "C"

@@ -2298,6 +2298,33 @@ hipError_t bcd_launch_bayes27_redo(const float *colors, const float *pixcov, con
     return hipGetLastError();
 }
 
+// SOLVE and FINISH of a chunk whose records another prepare kernel has filled (k_prepare27t in k_bayes_temporal.hip: A = C - N, C, noise + mean, redo
+// counter cleared), default search radius: the eigensolver, the register-resident finish kernel and the walk over its (normally empty) redo list, exactly
+// as bcd_launch_bayes27 launches them behind its own prepare kernel.  colors / pixcov / mask: those of the frame the estimates are aggregated for -- the
+// finish kernels take everything else from the records.  d_work: BCD_WORK_INTS zeroed ints, of which the prepare kernel used the first queue group.
+hipError_t bcd_launch_solve_finish27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
+                                     int *d_work, int num_cus, int W, int H, float min_eig, float *records, float *sum, int32_t *cnt, int *d_spectral,
+                                     hipStream_t st)
+{
+    if (nb_items <= 0) return hipSuccess;
+    Geom27 g;
+    g.W = W; g.H = H; g.b = WB; g.side = 2 * WB + 1; g.words = (g.side * g.side + 31) / 32; g.maxS = g.side * g.side;
+    Records27 rec;
+    rec.A = records;
+    rec.V = rec.A + (size_t)nb_items * MSZ;
+    rec.C = rec.V + (size_t)nb_items * MSZ;
+    rec.aux = rec.C + (size_t)nb_items * MSZ;
+    rec.eig = rec.aux + (size_t)nb_items * AUX27;
+    int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP);
+    { hipError_t e = bcd_launch_jacobi27_batch(rec.A, nb_items, d_work + BCD_WORK_QUEUES * BCD_WORK_STRIDE, std::min((nb_items + 1) / 2, num_cus * 12), rec.eig, rec.V, st,
+                                               jacobi_conv2(), rec.A, nullptr, first_item); if (e != hipSuccess) return e; }
+    const size_t wl3 = WinT<WB>::F2_BYTES;
+    hipLaunchKernelGGL(k_finish27w<WB>, dim3(std::min(nb_items, num_cus * 12)), dim3(64), wl3, st, colors, mask, list, first_item, nb_items,
+                       d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, redo, d_spectral, (const int *)nullptr);
+    { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
+    return bcd_launch_bayes27_redo(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, W, H, WB, min_eig, records, sum, cnt, st);
+}
+
 // eigen-decomposition of n symmetric 27 x 27 matrices (28 x 28 zero-padded, row-major): persistent wavefronts, two matrices each
 hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blocks, float *eig, float *V, hipStream_t st, float conv2, float *Aout,
                                      const int *d_n /* optional: the number of matrices is min(n, *d_n - first_item), read on the device */, int first_item)

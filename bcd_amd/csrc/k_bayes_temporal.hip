@@ -1,0 +1,261 @@
+// k_bayes_temporal.hip -- the estimate of a processed pixel whose similar set spans several frames of a sequence, patch radius 1,
+// search radius 6.  The similar set is S = S_0 (in the frame itself) followed by S_1 .. S_F (in the neighbour frames, in the order given), each in window
+// row-major order; the neighbours lend statistics only:
+//   k_prepare27t           PREPARE  what k_bayes27<1> / k_bayes27w<1> do (k_bayes27.hip), over the members of all frames: computeNoiseCovPatchesMean
+//                                   (:400-419, each member's per-pixel covariance from its own frame), the colour mean (:500-509) and the empirical covariance
+//                                   (:511-536) in member order, the covariance on the f32 matrix core; the record it leaves -- A = C - N, C, N, m, the cleared
+//                                   redo counter -- is the record of those kernels, so the unchanged solver (k_jacobi27_quads) and finish kernels (k_finish27w,
+//                                   redo list k_bayes27w<2>) follow: they read the record, the IN-FRAME mask and the frame's colours, i.e. they compute and
+//                                   aggregate the estimates of the members in S_0 only
+//   k_bayes_weak_temporal  FALLBACK denoiseOnlyMainPatch (:455-481) with the average over the colour patches of all members of all frames, added to the main
+//                                   patch only
+// Members are gathered from global memory (the gather form of k_bayes27<1>): a member's frame is part of its code.
+#include "bcd_common.h"
+#include <algorithm>
+
+size_t bcd_bayes27_record_bytes(); // (k_bayes27.hip)
+
+namespace {
+
+constexpr int K = 27, KP = 28, LD = 29, JLD = 28, P = 9, MSZ = KP * KP, CHUNK = MSZ / K, AUX27 = 96; // the record geometry of k_bayes27.hip
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+// a frame's pointers by index: a chain of selects on the by-value table (a wave-uniform index keeps them on the scalar unit)
+__device__ inline const float *frame_col(const BcdFrameTable &t, int f)
+{
+    const float *r = t.col[0];
+#pragma unroll
+    for (int i = 1; i <= BCD_MAX_NEIGHBOURS; ++i) r = f == i ? t.col[i] : r;
+    return r;
+}
+__device__ inline const float *frame_pixcov(const BcdFrameTable &t, int f)
+{
+    const float *r = t.pixcov[0];
+#pragma unroll
+    for (int i = 1; i <= BCD_MAX_NEIGHBOURS; ++i) r = f == i ? t.pixcov[i] : r;
+    return r;
+}
+__device__ inline const uint32_t *frame_mask(const BcdFrameTable &t, int f)
+{
+    const uint32_t *r = t.mask[0];
+#pragma unroll
+    for (int i = 1; i <= BCD_MAX_NEIGHBOURS; ++i) r = f == i ? t.mask[i] : r;
+    return r;
+}
+
+// work distribution of the persistent kernels: the queues of k_bayes27.hip (item = queue + 8 k; a wavefront starts on the queue of its workgroup and
+// moves on when one is empty)
+struct WorkCursor { int q, tried; };
+__device__ inline int work_next(int *work, int nb_items, int lane, WorkCursor &c)
+{
+    while (c.tried < BCD_WORK_QUEUES) {
+        int k = 0;
+        if (lane == 0) k = atomicAdd(work + c.q * BCD_WORK_STRIDE, 1);
+        k = __builtin_amdgcn_readfirstlane(k);
+        const int item = c.q + BCD_WORK_QUEUES * k;
+        if (item < nb_items) return item;
+        c.q = (c.q + 1) % BCD_WORK_QUEUES;
+        ++c.tried;
+    }
+    return -1;
+}
+
+__device__ inline int noise_idx(int i, int j) { return i == j ? i : (i + j == 1 ? 5 : (i + j == 2 ? 4 : 3)); } // 3x3 symmetric block from xx,yy,zz,yz,xz,xy
+
+// member code: frame << 12 | (dl + B) << 8 | (dc + B)
+__device__ inline int code_frame(int code) { return code >> 12; }
+template <int B> __device__ inline int code_pixel(int code, int p, int W) { return p + (((code >> 8) & 15) - B) * W + ((code & 255) - B); }
+
+struct Records27t {
+    float *A, *C, *aux; // [items][784], [items][784], [items][AUX27]  (V and the eigenvalues are the solver's)
+    int *redo;          // the redo list of the finish kernel: its counter is cleared here
+};
+
+template <int B>
+__global__ __launch_bounds__(64) void k_prepare27t(BcdFrameTable t, const int32_t *__restrict__ list, int first_item, int nb_items, int *work, int W,
+                                                   Records27t rec)
+{
+    constexpr int SIDE = 2 * B + 1, WORDS = (SIDE * SIDE + 31) / 32, MAXM = SIDE * SIDE * (BCD_MAX_NEIGHBOURS + 1);
+    static_assert(SIDE <= 16 && WORDS <= 32, "a window line and column fit four bits of the member code, the mask words one per lane of a half");
+    __shared__ __attribute__((aligned(16))) float chunk[MSZ]; // member-staging chunk: CHUNK members x K components
+    __shared__ __attribute__((aligned(16))) float noise[56], mean[KP];
+    __shared__ uint16_t mem[(MAXM + 7) / 8 * 8];
+    const int lane = threadIdx.x;
+    if (blockIdx.x == 0 && lane == 0) rec.redo[0] = 0; // (the chunk's redo list is empty: the finish kernel appends to it two launches later)
+
+    WorkCursor cursor{ (int)(blockIdx.x % BCD_WORK_QUEUES), 0 };
+    for (;;) {
+        const int slot = work_next(work, nb_items, lane, cursor);
+        if (slot < 0) break;
+        const int p = __builtin_amdgcn_readfirstlane(list[first_item + slot]);
+        float *recA = rec.A + (size_t)slot * MSZ, *recC = rec.C + (size_t)slot * MSZ, *recX = rec.aux + (size_t)slot * AUX27;
+
+        // ---- the members: S_0 in window order, then S_1 .. S_F, each in window order
+        int n = 0;
+        for (int f = 0; f < t.n; ++f) {
+            uint32_t m = lane < WORDS ? frame_mask(t, f)[(size_t)p * WORDS + lane] : 0u;
+            if (lane == WORDS - 1 && (SIDE * SIDE) % 32 != 0) m &= (1u << ((SIDE * SIDE) % 32)) - 1u; // (bits beyond the window are no members: the list holds MAXM)
+            const int cntw = __popc(m);
+            int pre = cntw;
+            for (int off = 1; off < 32; off <<= 1) {
+                const int v = __shfl_up(pre, off);
+                if (lane >= off) pre += v;
+            }
+            const int total = __shfl(pre, WORDS - 1);
+            int pos = n + pre - cntw;
+            while (m) {
+                const int bit = __ffs(m) - 1;
+                m &= m - 1;
+                const int k = lane * 32 + bit, kl = k / SIDE, kc = k - kl * SIDE;
+                mem[pos++] = (uint16_t)((f << 12) | (kl << 8) | kc);
+            }
+            n += total;
+        }
+        __syncthreads();
+
+        // ---- computeNoiseCovPatchesMean (:400-419) and empiricalMean (:500-509) in one sweep over the members: lanes 0..53 own one noise component, lanes
+        // 0..26 also one colour component.  The loads of 8 members are issued back to back, the sums stay in member order.
+        {
+            const float n_inv = 1.f / (float)n;
+            int noff, coff; // (idle lanes repeat the loads of the last owner: no branches around the loads)
+            { const int l = min(lane, P * 6 - 1), o = l / 6, j = l - o * 6; noff = ((o / 3 - 1) * W + (o % 3 - 1)) * 6 + j; }
+            { const int l = min(lane, K - 1), o = l / 3, ch = l - o * 3; coff = ((o / 3 - 1) * W + (o % 3 - 1)) * 3 + ch; }
+            float accn = 0.f, accm = 0.f;
+            for (int i = 0; i < n; i += 8) {
+                float vn[8], vm[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int code = __builtin_amdgcn_readfirstlane((int)mem[min(i + u, n - 1)]); // (the same for every lane)
+                    const int f = code_frame(code);
+                    const long long q = code_pixel<B>(code, p, W);
+                    vn[u] = frame_pixcov(t, f)[q * 6 + noff];
+                    vm[u] = frame_col(t, f)[q * 3 + coff];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (i + u < n) { accn += vn[u]; accm += vm[u]; }
+            }
+            if (lane < P * 6) noise[lane] = accn * n_inv;
+            if (lane < K) mean[lane] = accm * n_inv;
+            __syncthreads();
+        }
+
+        // ---- centerPointCloud + empiricalCovarianceMatrix (:511-536) on the matrix core: C = Xc^T Xc, two members per v_mfma_f32_32x32x2_f32 (f32 in, f32
+        // accumulate: a chain of fma in member order; both operands are the same centred value, so the result is bitwise symmetric).
+        // Operand layout: lane l holds element i = l & 31 of member 2s + (l >> 5); rows / columns 27..31 are zero.
+        {
+            const int mi = lane & 31, mk = lane >> 5;
+            const float my_mean = mi < K ? mean[mi] : 0.f;
+            v16f acc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+            for (int i0 = 0; i0 < n; i0 += CHUNK) {
+                const int cn = min(CHUNK, n - i0);
+                // pickColorPatchesFromColorImage (:483-498): members [i0, i0 + cn), each from its own frame
+                for (int e = lane; e < cn * K; e += 64) {
+                    const int i = e / K, k = e - i * K, o = k / 3, ch = k - o * 3;
+                    const int code = mem[i0 + i];
+                    const long long q = code_pixel<B>(code, p, W) + (o / 3 - 1) * W + (o % 3 - 1);
+                    chunk[e] = frame_col(t, code_frame(code))[q * 3 + ch];
+                }
+                __syncthreads();
+                for (int s2 = 0; s2 < cn; s2 += 2) {
+                    const int m = s2 + mk;
+                    const float a = (m < cn && mi < K) ? chunk[m * K + mi] - my_mean : 0.f;
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, a, acc, 0, 0, 0);
+                }
+                __syncthreads();
+            }
+            const float inv = 1.f / (float)(n - 1);
+            // C/D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  C goes to the record in the LD layout, C - N -- the matrix whose
+            // negative eigenvalues are clamped, Step 1 (:421-436) -- in the eigensolver's 28 x 28 layout, padding row / column zero
+            const int mo = mi / 3, mj = mi - 3 * mo;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r = (e & 3) + 8 * (e >> 2) + 4 * mk;
+                const float v = acc[e] * inv; // rows / columns 27..31 of the product are exactly zero (zero operands)
+                if (r < K && mi < LD) recC[r * LD + mi] = v;
+                if (r < KP && mi < KP) {
+                    const int ro = r / 3, ri = r - 3 * ro;
+                    const float nv = (ro == mo && r < K && mi < K) ? noise[ro * 6 + noise_idx(ri, mj)] : 0.f;
+                    recA[r * JLD + mi] = v - nv;
+                }
+            }
+        }
+        // a non-finite entry of the noise mean makes the whole estimate of the item NaN in the reference: a NaN colour mean carries that through the
+        // finish kernels (noise_poisons_item in k_bayes27.hip; all 64 lanes take part)
+        const bool poisoned = __builtin_amdgcn_ballot_w64(lane < P * 6 && !isfinite(noise[lane])) != 0;
+        if (lane < P * 6) recX[lane] = noise[lane];
+        if (lane < K) recX[P * 6 + lane] = poisoned ? __builtin_nanf("") : mean[lane];
+        __syncthreads(); // the next item reuses the LDS
+    }
+}
+
+// denoiseOnlyMainPatch (:455-481) over several frames: one lane per (fallback pixel, patch pixel), seven pixels per wavefront; every lane walks the masks
+// of its pixel frame by frame in window order -- the member order, so the three channel sums are sequential sums in member order -- and adds its patch
+// pixel of every member.  No LDS, no barrier.  |S| = 0 gives 0 * inf = NaN like the reference.
+template <int B>
+__global__ __launch_bounds__(64) void k_bayes_weak_temporal(BcdFrameTable t, const int32_t *__restrict__ list, const int32_t *__restrict__ d_nlist, int W,
+                                                            float *sum, int32_t *cnt)
+{
+    constexpr int SIDE = 2 * B + 1, WORDS = (SIDE * SIDE + 31) / 32, PER_WAVE = 64 / P;
+    const int lane = threadIdx.x, slot = lane / P, o = lane - slot * P;
+    const int nlist = *d_nlist;
+    for (int base = blockIdx.x * PER_WAVE; base < nlist; base += gridDim.x * PER_WAVE) {
+        const int item = base + slot;
+        if (slot >= PER_WAVE || item >= nlist) continue;
+        const int p = list[item];
+        const long long pp = (long long)p + (o / 3 - 1) * W + (o % 3 - 1); // patch pixel o of the main patch
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        int n = 0;
+        for (int f = 0; f < t.n; ++f) {
+            const float *src = frame_col(t, f) + pp * 3;
+            const uint32_t *mw = frame_mask(t, f) + (size_t)p * WORDS;
+            for (int wd = 0; wd < WORDS; ++wd) {
+                uint32_t m = mw[wd];
+                while (m) {
+                    const int k = wd * 32 + __ffs(m) - 1;
+                    m &= m - 1;
+                    const int kl = k / SIDE, kc = k - kl * SIDE;
+                    const int rel = ((kl - B) * W + (kc - B)) * 3;
+                    a0 += src[rel]; a1 += src[rel + 1]; a2 += src[rel + 2];
+                    ++n;
+                }
+            }
+        }
+        const float n_inv = 1.f / (float)n;
+        float *dst = sum + pp * 3;
+        unsafeAtomicAdd(dst, n_inv * a0);
+        unsafeAtomicAdd(dst + 1, n_inv * a1);
+        unsafeAtomicAdd(dst + 2, n_inv * a2);
+        if (cnt) atomicAdd(cnt + pp, 1);
+    }
+}
+
+} // namespace
+
+// PREPARE of items [first_item, first_item + nb_items) of `list` into `records` (nb_items records as bcd_launch_bayes27 lays them out: A | V | C | aux | eig |
+// redo list); d_work: the first BCD_WORK_QUEUES * BCD_WORK_STRIDE ints of the chunk's zeroed work queues
+hipError_t bcd_launch_prepare27t(const BcdFrameTable &t, const int32_t *list, int first_item, int nb_items, int *d_work, int num_cus, int W, int b,
+                                 float *records, hipStream_t st)
+{
+    if (nb_items <= 0) return hipSuccess;
+    if (b != 6 || t.n < 1 || t.n > BCD_MAX_NEIGHBOURS + 1) return hipErrorInvalidValue;
+    if (bcd_bayes27_record_bytes() != (size_t)(3 * MSZ + AUX27 + KP) * sizeof(float) + 2 * sizeof(int)) return hipErrorInvalidValue; // (the layout below)
+    Records27t rec;
+    rec.A = records;
+    rec.C = rec.A + (size_t)nb_items * MSZ * 2;
+    rec.aux = rec.C + (size_t)nb_items * MSZ;
+    rec.redo = reinterpret_cast<int *>(rec.aux + (size_t)nb_items * AUX27 + (size_t)nb_items * KP);
+    hipLaunchKernelGGL(k_prepare27t<6>, dim3(std::min(nb_items, num_cus * 16)), dim3(64), 0, st, t, list, first_item, nb_items, d_work, W, rec);
+    return hipGetLastError();
+}
+
+hipError_t bcd_launch_bayes_weak_temporal(const BcdFrameTable &t, const int32_t *list, const int32_t *d_nlist, int blocks, int W, int b, float *sum,
+                                          int32_t *cnt, hipStream_t st)
+{
+    if (blocks <= 0) return hipSuccess;
+    if (b != 6 || t.n < 1 || t.n > BCD_MAX_NEIGHBOURS + 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bayes_weak_temporal<6>, dim3(blocks), dim3(64), 0, st, t, list, d_nlist, W, sum, cnt);
+    return hipGetLastError();
+}

@@ -246,6 +246,16 @@ class ScaleStats(C.Structure):
                 ("similarity_path", C.c_int32), ("borderline_pairs", C.c_int32), ("cu_share", C.c_int32), ("spectral_inverses", C.c_int32)]
 
 
+class Frame(C.Structure):
+    """bcd_hip_frame: one neighbour frame of bcd_hip_denoise_temporal[_host]"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p), ("reserved", C.c_void_p)]
+
+
+class StageFrame(C.Structure):
+    """bcd_hip_stage_frame: one frame of bcd_hip_bayes_accumulate_temporal"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_pixel_cov", C.c_void_p), ("d_mask", C.c_void_p)]
+
+
 # every symbol include/bcd_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
@@ -254,6 +264,7 @@ SYMBOLS = [
     "bcd_hip_spike_map", "bcd_hip_spike_apply", "bcd_hip_spike_filter_layers",
     "bcd_hip_similarity_masks_moments", "bcd_hip_window_distances_moments", "bcd_hip_denoise_moments", "bcd_hip_denoise_moments_host",
     "bcd_hip_similarity_masks_guide", "bcd_hip_window_distances_guide", "bcd_hip_gate_masks", "bcd_hip_denoise_guided", "bcd_hip_denoise_guided_host",
+    "bcd_hip_similarity_masks_cross", "bcd_hip_window_distances_cross", "bcd_hip_bayes_accumulate_temporal", "bcd_hip_denoise_temporal", "bcd_hip_denoise_temporal_host",
     "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
     "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
@@ -667,6 +678,38 @@ class Context:
         self._chk(lib().bcd_hip_window_distances(self.h, _dp(hist), _dp(ns), W, H, D, w, b, line, col, out.ctypes.data_as(_F)))
         return out
 
+    def similarity_masks_cross(self, hist, ns, hist_nb, ns_nb, w, b, tau, out=None):
+        """bcd_hip_similarity_masks_cross: masks and |S_f| of the main pixels of a neighbour frame (hist_nb, ns_nb) similar to each main pixel of the
+        frame (hist, ns), in the layouts of similarity_masks.  out: (mask (H, W, words) int32, count (H, W) int32) contiguous device tensors to fill"""
+        torch = self.torch
+        H, W, D = hist.shape
+        if tuple(hist_nb.shape) != (H, W, D) or ns_nb.numel() != H * W or ns.numel() != H * W:
+            raise ValueError("the neighbour frame must have the frame's width, height and histogram depth")
+        words = ((2 * b + 1) ** 2 + 31) // 32
+        if out is None:
+            out = (torch.zeros((H, W, words), dtype=torch.int32, device=hist.device), torch.zeros((H, W), dtype=torch.int32, device=hist.device))
+        mask, cnt = out
+        if tuple(mask.shape) != (H, W, words) or tuple(cnt.shape) != (H, W) or mask.dtype != torch.int32 or cnt.dtype != torch.int32:
+            raise ValueError("out must be ((H, W, words) int32, (H, W) int32)")
+        L = lib()
+        L.bcd_hip_similarity_masks_cross.argtypes = [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP]
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_similarity_masks_cross(self.h, _dp(hist), _dp(ns), _dp(hist_nb), _dp(ns_nb), W, H, D, w, b, float(tau), _dp(mask), _dp(cnt)))
+        return mask, cnt
+
+    def window_distances_cross(self, hist, ns, hist_nb, ns_nb, w, b, line, column):
+        """bcd_hip_window_distances_cross: the (2b+1)^2 patch distances of one main pixel of the frame to its window in the neighbour frame, +inf outside"""
+        import numpy as np
+        H, W, D = hist.shape
+        if tuple(hist_nb.shape) != (H, W, D) or ns_nb.numel() != H * W or ns.numel() != H * W:
+            raise ValueError("the neighbour frame must have the frame's width, height and histogram depth")
+        out = np.empty(((2 * b + 1) ** 2,), np.float32)
+        L = lib()
+        L.bcd_hip_window_distances_cross.argtypes = [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]
+        self.torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_window_distances_cross(self.h, _dp(hist), _dp(ns), _dp(hist_nb), _dp(ns_nb), W, H, D, w, b, line, column, out.ctypes.data_as(_F)))
+        return out
+
     def similarity_masks_moments(self, col, pixcov, w, b, tau, var_floor=1e-8):
         """bcd_hip_similarity_masks_moments: masks and |S| from colours (H, W, 3) and per-pixel covariances (H, W, 6; pixel_cov), in the layouts of
         similarity_masks"""
@@ -786,6 +829,93 @@ class Context:
         self._chk(lib().bcd_hip_bayes_accumulate(self.h, _dp(col), _dp(pixcov), _dp(mask), _dp(nsim), _dp(state), W, H, w, b,
                                                  C.c_float(min_eig), _dp(s), _dp(c)))
         return s, c
+
+    def bayes_accumulate_temporal(self, frames, nsim_total, state, w, b, min_eig, out=None):
+        """bcd_hip_bayes_accumulate_temporal: `frames` is a list of (colours, per-pixel covariances, masks) device tensors, [0] the frame itself and the
+        others its neighbour frames with their cross masks; nsim_total = |S_0| + sum |S_f|.  -> (sum, count), accumulated into `out` if given"""
+        torch = self.torch
+        H, W, _ = frames[0][0].shape
+        if out is None:
+            s = torch.zeros((H, W, 3), dtype=torch.float32, device=frames[0][0].device)
+            c = torch.zeros((H, W), dtype=torch.int32, device=frames[0][0].device)
+        else:
+            s, c = out
+        arr = (StageFrame * max(len(frames), 1))()
+        for i, (col, pixcov, mask) in enumerate(frames):
+            if tuple(col.shape) != (H, W, 3) or tuple(pixcov.shape) != (H, W, 6) or mask.numel() != H * W * (((2 * b + 1) ** 2 + 31) // 32):
+                raise ValueError("frame %d: colours (H, W, 3), per-pixel covariances (H, W, 6) and masks (H, W, words) of the frame's size are expected" % i)
+            arr[i].d_colors, arr[i].d_pixel_cov, arr[i].d_mask = col.data_ptr(), pixcov.data_ptr(), mask.data_ptr()
+            _dp(col), _dp(pixcov), _dp(mask)
+        L = lib()
+        L.bcd_hip_bayes_accumulate_temporal.argtypes = [_VP, C.POINTER(StageFrame), C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP]
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_bayes_accumulate_temporal(self.h, arr, len(frames), _dp(nsim_total), _dp(state), W, H, w, b, float(min_eig), _dp(s), _dp(c)))
+        return s, c
+
+    def denoise_temporal(self, col, ns, hist, cov, neighbours, nscales, prm, out=None):
+        """bcd_hip_denoise_temporal: the frame (col, ns, hist, cov) denoised with similar patches from up to four neighbour frames of its sequence,
+        each a (col, ns, hist, cov) tuple of device tensors of the frame's size.  No neighbour: denoise()."""
+        torch = self.torch
+        H, W, D = hist.shape
+        neighbours = list(neighbours)
+        arr = (Frame * max(len(neighbours), 1))()
+        for i, f in enumerate(neighbours):
+            if tuple(f[0].shape) != (H, W, 3) or f[1].numel() != H * W or tuple(f[2].shape) != (H, W, D) or tuple(f[3].shape) != (H, W, 6):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (_dp(t).value for t in f)
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=hist.device)
+        L = lib()
+        L.bcd_hip_denoise_temporal.argtypes = [_VP, _VP, _VP, _VP, _VP, C.POINTER(Frame), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), _VP]
+        torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_denoise_temporal(self.h, _dp(col), _dp(ns), _dp(hist), _dp(cov), arr, len(neighbours), W, H, D, int(nscales), C.byref(prm), _dp(out)))
+        return out
+
+    def denoise_temporal_host(self, col, ns, hist, cov, neighbours, nscales, prm):
+        """bcd_hip_denoise_temporal_host on NumPy float32 arrays -> the denoised frame (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        col, ns, hist, cov = (as32(a) for a in (col, ns, hist, cov))
+        H, W, D = hist.shape
+        keep = [tuple(as32(a) for a in f) for f in neighbours]
+        arr = (Frame * max(len(keep), 1))()
+        for i, f in enumerate(keep):
+            if f[0].shape != (H, W, 3) or f[1].size != H * W or f[2].shape != (H, W, D) or f[3].shape != (H, W, 6):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (a.ctypes.data for a in f)
+        out = np.empty((H, W, 3), np.float32)
+        L = lib()
+        L.bcd_hip_denoise_temporal_host.argtypes = [_VP, _VP, _VP, _VP, _VP, C.POINTER(Frame), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), _VP]
+        self._chk(L.bcd_hip_denoise_temporal_host(self.h, col.ctypes.data, ns.ctypes.data, hist.ctypes.data, cov.ctypes.data, arr, len(keep), W, H, D, int(nscales),
+                                                  C.byref(prm), out.ctypes.data))
+        return out
+
+    def denoise_temporal_stages(self, col, ns, hist, cov, neighbours, prm):
+        """One scale of the denoising of a frame with similar patches from neighbouring frames of its sequence, composed from the
+        stage calls: in-frame masks, cross masks of every neighbour, the marking on the in-frame masks and the total |S|, the estimate over the members of
+        all frames, the finalisation.  neighbours: a list of (colours, sample counts, histograms, covariances) device tensors of the frame's size, at most
+        four; patch radius 1 and search radius 6.  With no neighbour it computes what denoise(..., nscales=1, prm) computes.
+        -> (denoised frame (H, W, 3), dict(processed, fallback, similar_total))"""
+        torch = self.torch
+        w, b, tau = prm.patch_radius, prm.search_radius, prm.hist_dist_threshold
+        neighbours = list(neighbours)
+        mask, nsim = self.similarity_masks(hist, ns, w, b, tau)
+        frames = [(col, self.pixel_cov(cov, ns), mask)]
+        self.synchronize()
+        total = nsim.clone()
+        for (col_nb, ns_nb, hist_nb, cov_nb) in neighbours:
+            mask_nb, nsim_nb = self.similarity_masks_cross(hist, ns, hist_nb, ns_nb, w, b, tau)
+            total += nsim_nb
+            frames.append((col_nb, self.pixel_cov(cov_nb, ns_nb), mask_nb))
+        self.synchronize()
+        state, _ = self.active_set(mask, total, w, b, prm.marked_skip_probability, prm.use_random_pixel_order, prm.order_seed)
+        s, c = self.bayes_accumulate_temporal(frames, total, state, w, b, prm.min_eigen_value)
+        out = self.finalize(s, c)
+        self.synchronize()
+        processed = state == 1
+        strong = processed & (total >= 3 * (2 * w + 1) ** 2 + 1)
+        stats = dict(processed=int(processed.sum()), fallback=int(processed.sum()) - int(strong.sum()), similar_total=int(total[processed].sum()))
+        return out, stats
 
     def bayes_accumulate_layers(self, layers, mask, nsim, state, w, b, min_eig):
         """bcd_hip_bayes_accumulate_layers: `layers` is a list of (colours, per-pixel covariances) tensors on one selection.

@@ -204,6 +204,11 @@ namespace bcd
 			cerr << "Aborting denoising: the selection from means and covariances (setMomentSelection) is not available over several devices" << endl;
 			return false;
 		}
+		if(!m_neighbourFrames.empty() && (m_devices.size() > 1 || m_momentSelection || m_pGuideFeatures))
+		{
+			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available over several devices, with the moment selection or with feature buffers" << endl;
+			return false;
+		}
 		if(!inputsOutputsAreOk() || !layersAreOk() || !guideIsOk())
 			return false;
 		m_width = m_inputs.m_pColors->getWidth();
@@ -350,6 +355,37 @@ namespace bcd
 				bcd_hip_layers_host_options layersOpt = { opt.spike_factor, opt.zero_bad_values, m_prefilterLayers ? 1 : 0 };
 				rc = bcd_hip_denoise_moments_host(rSlot.m_pCtx, pIn[1], m_width, m_height, i_nbOfScales, &prm, &layersOpt, m_momentVarianceFloor, layers.data(), int(layers.size()));
 			}
+			else if(!m_neighbourFrames.empty())
+			{	// neighbouring frames of the sequence lend their statistics; checked here: sizes, and what the call does not combine with
+				std::vector<bcd_hip_frame> frames(m_neighbourFrames.size());
+				bool ok = m_layers.empty() && !(m_prefilterThresholdStDevFactor > 0.f);
+				for(size_t k = 0; ok && k < m_neighbourFrames.size(); ++k)
+				{
+					const DenoiserInputs& f = m_neighbourFrames[k];
+					ok = f.m_pColors && f.m_pNbOfSamples && f.m_pHistograms && f.m_pSampleCovariances
+							&& f.m_pColors->getWidth() == m_width && f.m_pColors->getHeight() == m_height && f.m_pColors->getDepth() == 3
+							&& f.m_pNbOfSamples->getWidth() == m_width && f.m_pNbOfSamples->getHeight() == m_height && f.m_pNbOfSamples->getDepth() == 1
+							&& f.m_pHistograms->getWidth() == m_width && f.m_pHistograms->getHeight() == m_height && f.m_pHistograms->getDepth() == depth
+							&& f.m_pSampleCovariances->getWidth() == m_width && f.m_pSampleCovariances->getHeight() == m_height && f.m_pSampleCovariances->getDepth() == 6;
+					if(ok)
+						frames[k] = { f.m_pColors->getDataPtr(), f.m_pNbOfSamples->getDataPtr(), f.m_pHistograms->getDataPtr(), f.m_pSampleCovariances->getDataPtr(), nullptr };
+				}
+				if(!ok)
+				{
+					cerr << "Aborting denoising: a neighbour frame needs all four images in the frame's size, and neighbour frames do not combine with added layers or the spike prefilter" << endl;
+					bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
+					return false;
+				}
+				rc = bcd_hip_denoise_temporal_host(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], frames.data(), int(frames.size()), m_width, m_height, depth, i_nbOfScales, &prm,
+						result.getDataPtr());
+				if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
+				{
+					float* p = result.getDataPtr();
+					for(size_t i = 0, n = size_t(m_nbOfPixels) * 3; i < n; ++i)
+						if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
+							p[i] = 0.f;
+				}
+			}
 			else if(m_layers.empty())
 				rc = bcd_hip_denoise_host_ex(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], m_width, m_height, depth, i_nbOfScales, &prm, &opt, result.getDataPtr());
 			else
@@ -415,6 +451,7 @@ namespace bcd
 		engine.setSpikePrefilter(m_prefilterThresholdStDevFactor);
 		engine.setZeroBadOutputValues(m_zeroBadOutputValues);
 		engine.setLayers(m_layers);
+		engine.setNeighbourFrames(m_neighbourFrames);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);

@@ -47,6 +47,8 @@ namespace
 		unsigned m_orderSeed = 1234u;
 		std::vector<int> m_devices = std::vector<int>(1, 0);
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
+		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; };
+		std::vector<Neighbour> m_neighbours; // --neighbour, in command-line order
 		std::vector<Layer> m_layers; // --layer, in command-line order
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
 		bool m_momentSelection = false; // --moment-selection: similar patches from the -i colours and the -c covariances, no histogram file
@@ -72,6 +74,7 @@ namespace
 		cout << "    -c <cov>             The file path to the input covariance matrices buffer (default: <input>_cov.exr)" << endl;
 		cout << "Optional arguments list:" << endl;
 		cout << "    -a <file>            The file path to the .bcd.json file containing arguments for the program" << endl;
+		cout << "    --neighbour <frame>  A neighbouring frame of the sequence that lends its statistics (repeatable, at most 4; expects <frame>_hist.exr / <frame>_cov.exr beside it)" << endl;
 		cout << "    -d <float>           Histogram patch distance threshold (default: " << d.m_histogramPatchDistanceThreshold << ")" << endl;
 		cout << "    -b <int>             Radius of search windows (default: " << d.m_searchWindowRadius << ")" << endl;
 		cout << "    -w <int>             Radius of patches (default: " << d.m_patchRadius << ")" << endl;
@@ -137,6 +140,21 @@ namespace
 					a.m_momentVarianceFloor = floor;
 					++i;
 				}
+				continue;
+			}
+			if(flag == "--neighbour")
+			{	// a neighbouring frame of the sequence: <frame>.exr with <frame>_hist.exr and <frame>_cov.exr beside it, as -i infers them
+				if(i + 1 >= argc) { cout << "ERROR in program arguments: expecting <frame.exr> after --neighbour" << endl; return false; }
+				a.m_neighbours.emplace_back();
+				ProgramArguments::Neighbour& rNb = a.m_neighbours.back();
+				rNb.m_colorPath = argv[++i];
+				if(rNb.m_colorPath.length() <= 4) { cout << "ERROR in program arguments: '" << rNb.m_colorPath << "' is no .exr file name" << endl; return false; }
+				const string stem = rNb.m_colorPath.substr(0, rNb.m_colorPath.length() - 4);
+				Deepimf histAndNbOfSamplesImage;
+				if(!ImageIO::loadEXR(rNb.m_colorImage, rNb.m_colorPath.c_str())) { cout << "ERROR in program arguments: couldn't load neighbour color image file '" << rNb.m_colorPath << "'" << endl; return false; }
+				if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamplesImage, (stem + "_hist.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour histogram image file '" << stem << "_hist.exr'" << endl; return false; }
+				Utils::separateNbOfSamplesFromHistogram(rNb.m_histogramImage, rNb.m_nbOfSamplesImage, histAndNbOfSamplesImage);
+				if(!ImageIO::loadMultiChannelsEXR(rNb.m_covarianceImage, (stem + "_cov.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour covariance matrix image file '" << stem << "_cov.exr'" << endl; return false; }
 				continue;
 			}
 			if(flag == "--layer")
@@ -465,6 +483,12 @@ namespace
 		if(!args.m_featurePath.empty())
 			pSettings->setGuideFeatures(&args.m_featureImage, args.m_featureVariancePath.empty() ? nullptr : &args.m_featureVarianceImage, args.m_featureFloors, args.m_featureThreshold);
 		pSettings->setZeroBadOutputValues(true); // checkAndPutToZeroNegativeInfNaNValues (src/cli/main.cpp:470) before the download
+		for(ProgramArguments::Neighbour& rNb : args.m_neighbours)
+		{
+			DenoiserInputs frame;
+			frame.m_pColors = &rNb.m_colorImage; frame.m_pNbOfSamples = &rNb.m_nbOfSamplesImage; frame.m_pHistograms = &rNb.m_histogramImage; frame.m_pSampleCovariances = &rNb.m_covarianceImage;
+			pSettings->addNeighbourFrame(frame);
+		}
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)
 			pSettings->addLayer(&args.m_layers[k].m_colorImage, &args.m_layers[k].m_covarianceImage, &layerOutputs[k]);

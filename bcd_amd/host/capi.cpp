@@ -545,6 +545,56 @@ int bcdcore_denoise_layers(const float* cols, const float* covs, const float* ns
 			sizeMismatchLayer, afterClear, 0, outs);
 }
 
+/// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames of the sequence (addNeighbourFrame): nbCols etc. hold nbOfNeighbours images one behind
+/// the other.  afterClear != 0: clearNeighbourFrames() and a second denoise() follow, whose result replaces the first.  Returns denoise()'s bool.
+int bcdcore_denoise_temporal(const float* col, const float* ns, const float* hist, const float* cov, const float* nbCols, const float* nbNs, const float* nbHists,
+		const float* nbCovs, int nbOfNeighbours, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder, float skipProbability, unsigned seed,
+		int afterClear, float* out)
+{
+	Deepimf cImg(W, H, 3), nImg(W, H, 1), hImg(W, H, D), vImg(W, H, 6), oImg(W, H, 3);
+	cImg.copyDataFrom(col); nImg.copyDataFrom(ns); hImg.copyDataFrom(hist); vImg.copyDataFrom(cov);
+	std::vector<Deepimf> c(nbOfNeighbours), n(nbOfNeighbours), h(nbOfNeighbours), v(nbOfNeighbours);
+	const size_t npix = size_t(W) * H;
+	DenoiserInputs in;
+	in.m_pColors = &cImg; in.m_pNbOfSamples = &nImg; in.m_pHistograms = &hImg; in.m_pSampleCovariances = &vImg;
+	DenoiserOutputs o;
+	o.m_pDenoisedColors = &oImg;
+	DenoiserParameters p;
+	p.m_histogramDistanceThreshold = tau;
+	p.m_searchWindowRadius = b;
+	p.m_minEigenValue = minEig;
+	p.m_useRandomPixelOrder = randomOrder != 0;
+	p.m_markedPixelsSkippingProbability = skipProbability;
+	std::unique_ptr<MultiscaleDenoiser> multi;
+	std::unique_ptr<Denoiser> mono;
+	IDenoiser* d;
+	HipEngineSettings* pSettings;
+	if(nscales > 1) { multi.reset(new MultiscaleDenoiser(nscales)); d = multi.get(); pSettings = multi.get(); }
+	else { mono.reset(new Denoiser()); d = mono.get(); pSettings = mono.get(); }
+	pSettings->setOrderSeed(seed);
+	for(int k = 0; k < nbOfNeighbours; ++k)
+	{
+		c[k].resize(W, H, 3); n[k].resize(W, H, 1); h[k].resize(W, H, D); v[k].resize(W, H, 6);
+		c[k].copyDataFrom(nbCols + k * npix * 3); n[k].copyDataFrom(nbNs + k * npix); h[k].copyDataFrom(nbHists + k * npix * D); v[k].copyDataFrom(nbCovs + k * npix * 6);
+		DenoiserInputs f;
+		f.m_pColors = &c[k]; f.m_pNbOfSamples = &n[k]; f.m_pHistograms = &h[k]; f.m_pSampleCovariances = &v[k];
+		pSettings->addNeighbourFrame(f);
+	}
+	d->setInputs(in);
+	d->setOutputs(o);
+	d->setParameters(p);
+	oImg = cImg; // (the multiscale path wants the output pre-sized like the input)
+	bool ok = d->denoise();
+	if(ok && afterClear)
+	{
+		pSettings->clearNeighbourFrames();
+		oImg = cImg;
+		ok = d->denoise();
+	}
+	if(ok) oImg.copyDataTo(out);
+	return ok ? 1 : 0;
+}
+
 /// ONE MultiscaleDenoiser (or Denoiser), denoise() called twice with -r 0 and the given m_nbOfCores: the written-back core count must not
 /// change what the second call does (returns 0 on failure, else 1; nbOfCoresAfter[2] = the field after each call)
 int bcdcore_denoise_reuse(const float* col, const float* ns, const float* hist, const float* cov, int W, int H, int D, int nscales, int b,

@@ -84,6 +84,16 @@ namespace bcd
 		const std::vector<float>& getGuideFloors() const { return m_guideFloors; }
 		float getGuideThreshold() const { return m_guideThreshold; }
 
+		/// A neighbouring frame of the sequence (t - 1, t + 1, ...) that lends its statistics to the frame in DenoiserInputs (bcd_hip_denoise_temporal_host):
+		/// similar patches are also searched in the same window of every neighbour frame, and mean, noise mean and covariance of the estimate come from the
+		/// union of the sets; only the frame itself is denoised.  Each neighbour brings all four images, of the frame's width, height and histogram depth.
+		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with added
+		/// layers, the spike prefilter, the moment selection or feature buffers.  With no neighbour denoise() is what it always was.
+		void addNeighbourFrame(const DenoiserInputs& i_rFrame) { m_neighbourFrames.push_back(i_rFrame); }
+		void clearNeighbourFrames() { m_neighbourFrames.clear(); }
+		const std::vector<DenoiserInputs>& getNeighbourFrames() const { return m_neighbourFrames; }
+		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames) { m_neighbourFrames = i_rFrames; }
+
 	protected:
 		uint32_t m_orderSeed;
 		std::vector<int> m_devices;
@@ -97,6 +107,7 @@ namespace bcd
 		std::vector<float> m_guideFloors;
 		float m_guideThreshold;
 		std::vector<ColorLayer> m_layers;
+		std::vector<DenoiserInputs> m_neighbourFrames;
 	};
 
 	/// The engine contexts behind denoise() (device workspaces, pyramids, staging buffers: grow-only, sized by the largest frame seen,

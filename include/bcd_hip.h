@@ -278,6 +278,64 @@ int bcd_hip_denoise_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const floa
                            int D, int nb_scales, const bcd_hip_params *prm, float var_floor, const bcd_hip_layer *layers, int nb_layers,
                            const bcd_hip_guide *guide, bcd_hip_selection *sel /* NULL, or kept as by _layers_keep */);
 
+/* ---- similar patches from a neighbouring frame of a sequence -------------------------
+ * Frames t - 1 and t + 1 of an animation show almost the same surfaces as frame t under independent noise.  The cross-frame selection finds, for every
+ * main pixel p of the frame, the main pixels q of a NEIGHBOUR frame (same W, H, D) that may lend their statistics to p:
+ *   - the cross set S_f(p) is the set of main pixels q of the neighbour inside the clipped window of p -- the same PixelWindow(p, radius b, border w) as in
+ *     the frame itself, displacement (0, 0) included -- with d_f(p, q) <= tau;
+ *   - d_f is histogramPatchDistance (DenoisingUnit.cpp:336-386) with the first patch read from the frame and the second from the neighbour, in the
+ *     reference's operations: per patch offset, in row-major order, a sequential sum over the bins with b1 + b2 > 1 of
+ *     (n2 b1 - n1 b2)^2 / (n1 n2 (b1 + b2)), n1 taken from the frame and n2 from the neighbour; integer bin counts; one IEEE division; no contraction;
+ *   - NaN (0 / 0: no counted bin in the patch pair) is never similar;
+ *   - the mask layout is that of bcd_hip_similarity_masks: bit (dl + b)(2b + 1) + (dc + b) in word bit >> 5 of the pixel's ((2b+1)^2 + 31) / 32 words;
+ *   - the pair-distance planes are not symmetric between two frames, so all (2b+1)^2 displacements are evaluated.
+ * A frame compared with itself gives the masks of bcd_hip_similarity_masks bit for bit.
+ *   _similarity_masks_cross: d_mask_nb W*H*words uint32 and d_count_nb W*H int32 (= |S_f|) of one neighbour; pixels that are not main pixels get zeros.
+ *   _window_distances_cross: the twin of bcd_hip_window_distances: the (2b+1)^2 cross distances of one main pixel, +inf outside its clipped window.
+ * Both accept what their in-frame twins accept (w <= 2, b <= 15, D <= 255), refuse the rest before any device work, and synchronise.
+ *
+ * The estimate over the union of the sets.  Frame 0 is the frame itself, frames 1 .. F its neighbours, 1 <= F <= BCD_HIP_MAX_NEIGHBOURS; every frame
+ * brings its colours, its per-pixel covariances (bcd_hip_pixel_cov of ITS covariances and sample counts) and the masks of its similar set for every pixel
+ * of frame 0 (frame 0: the in-frame masks of bcd_hip_similarity_masks, frame f: bcd_hip_similarity_masks_cross).
+ *   - member order: S_0 in window row-major order, then S_1 .. S_F in the order given, each in window row-major order; |S| = |S_0| + sum |S_f| is handed in
+ *     as d_nsim_total (the marking kernels take masks and |S| as separate tensors: they are handed the in-frame masks and the total |S|, so a processed
+ *     pixel marks its in-frame members only and other frames are never marked);
+ *   - full estimate (|S| >= 3P + 1): computeNoiseCovPatchesMean, the colour mean and the empirical covariance (DenoisingUnit.cpp:400-419, 500-536) run over all
+ *     members in member order, each member's per-pixel covariance coming from its own frame; Steps 1 and 2 are those of bcd_hip_bayes_accumulate; only the
+ *     estimates of the members in S_0 are computed and aggregated into d_sum / d_count -- the neighbours lend statistics only;
+ *   - fallback (|S| < 3P + 1): denoiseOnlyMainPatch (:455-481) with the average over the colour patches of all members, added to the main patch only.
+ *   _bayes_accumulate_temporal: the twin of bcd_hip_bayes_accumulate (d_sum / d_count are accumulated into: zero them first); patch radius 1 and search
+ *             radius 6 only (anything else: BCD_HIP_EUNSUPPORTED).  With nb_frames = 1 it computes what bcd_hip_bayes_accumulate computes.  Refused before any
+ *             device work, with a message, the context staying usable: a null pointer, nb_frames outside 1 .. 5, an accumulator that overlaps an input or the
+ *             other accumulator.  Synchronises; bcd_hip_bayes_last_redo_count reports its redo list. */
+#define BCD_HIP_MAX_NEIGHBOURS 4
+/* The frame call.  Inputs are the frame and nb_neighbours neighbour frames, 0 <= nb_neighbours <= BCD_HIP_MAX_NEIGHBOURS, each with colours, sample counts,
+ * histograms and covariances of the same W, H, D, all device-resident (all host buffers for _host).  Per scale the steps are those above: S_0 by the code
+ * of bcd_hip_denoise, one cross pass per neighbour ahead of the marking, the marking on the in-frame masks and the total |S|, the estimate over all frames.
+ * Multiscale: every neighbour gets its own pyramid, built with the reducers of the frame's (colours averaged, counts and histograms summed, covariances
+ * weighted by the counts); scale s uses level s of every frame; the merge, the visiting order, the per-scale seeds and the -m / -r semantics are those of
+ * bcd_hip_denoise.  The scales run one after the other on the context's main workspace.  With nb_neighbours = 0 the call IS bcd_hip_denoise
+ * (bcd_hip_denoise_host): it delegates.  Motion vectors (a per-pixel window centre in the neighbour frame) are not supported: `reserved` must be NULL.
+ * Refused before any device work, with a message, the context staying usable: with neighbours, any geometry but patch radius 1 and search radius 6
+ * (BCD_HIP_EUNSUPPORTED); nb_neighbours outside 0 .. 4; a null image; a non-NULL `reserved`; an output that is or overlaps an input; what bcd_hip_denoise
+ * refuses.  Layers, kept selections, the moment and the feature-gated selection, row bands and bcd_hip_multi_* do not combine with this call.
+ * bcd_hip_get_stats: similar_total is the sum of the total |S|, similarity_path that of the in-frame pass, ms_similarity includes the cross passes.
+ *   _host: whole uploads (no streaming), the resident call, one download: the same result. */
+typedef struct { const float *d_colors, *d_nsamples, *d_histograms, *d_covariances; const void *reserved; } bcd_hip_frame;
+int bcd_hip_denoise_temporal(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
+                             const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out);
+int bcd_hip_denoise_temporal_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                                  const bcd_hip_frame *neighbours /* host pointers */, int nb_neighbours, int W, int H, int D, int nb_scales,
+                                  const bcd_hip_params *prm, float *h_out);
+typedef struct { const float *d_colors; const float *d_pixel_cov; const uint32_t *d_mask; } bcd_hip_stage_frame;   /* [0] = the frame itself */
+int bcd_hip_bayes_accumulate_temporal(bcd_hip_ctx *ctx, const bcd_hip_stage_frame *frames, int nb_frames, const int32_t *d_nsim_total, const uint8_t *d_state,
+                                      int W, int H, int patch_radius, int search_radius, float min_eigen_value, float *d_sum, int32_t *d_count);
+int bcd_hip_similarity_masks_cross(bcd_hip_ctx *ctx, const float *d_histograms, const float *d_nsamples, const float *d_histograms_nb,
+                                   const float *d_nsamples_nb, int W, int H, int D, int patch_radius, int search_radius, float threshold,
+                                   uint32_t *d_mask_nb, int32_t *d_count_nb);
+int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, const float *d_nsamples, const float *d_histograms_nb,
+                                   const float *d_nsamples_nb, int W, int H, int D, int patch_radius, int search_radius, int line, int col, float *h_out);
+
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
  * finalised colours the raw accumulators are returned (d_sum W*H*3 floats, d_count W*H int32), so
