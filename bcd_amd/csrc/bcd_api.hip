@@ -183,7 +183,10 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
 {
     const size_t npix = (size_t)W * H;
     const int nd = bcd_delta_count(b);
-    RCCHK(ensure(ctx, wk.T, npix * nd * sizeof(float)));
+    // the approximate path keeps binary16 planes -- one margin plane, or (the RATIO form, BCD_HIP_TC_PLANES=1) T and counts --, the exact kernels fp32 T and counts
+    const bool fast_path = exact_mode != 1 && fast_similarity_applies(ctx, D, w, tau);
+    const bool margin_wanted = fast_path && ctx->margin_planes;
+    RCCHK(ensure(ctx, wk.T, fast_path ? half_plane_bytes(npix, nd) : npix * nd * sizeof(float)));
     RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, nd)));
     RCCHK(ensure(ctx, wk.fwd, npix * ((nd + 31) / 32) * sizeof(uint32_t)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -192,7 +195,7 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
     Counters::Flags *d_flag = &wk.d_counters()->flags, *h_flag = &wk.h_counters->flags;
     // planes of exactly this problem already computed by the caller (its launches raised the flags in d_flag[0] themselves)?
     const bool pre = wk.planes.ready && exact_mode != 1 && wk.planes.hist == d_hist && wk.planes.ns == d_ns && wk.planes.W == W && wk.planes.H == H &&
-                     wk.planes.D == D && wk.planes.b == b && wk.planes.tau == tau && w == 1;
+                     wk.planes.D == D && wk.planes.b == b && wk.planes.tau == tau && wk.planes.margin == (margin_wanted && !wk.planes.ratio) && w == 1;
     const bool planes_kept = wk.planes.ready; // (k_scale_begin kept words [0] and [2] for the launches that made them)
     wk.planes.ready = false;
     if (wk.clean_flags) { // cleared by k_scale_begin, which kept the words of planes computed ahead ...
@@ -214,7 +217,6 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
     // fixed samples per pixel, a power of two (the usual case): the distance kernel drops the sample-count products (exactly,
     // see k_pairdist).  One small reduction and one host round trip at the head of the chain (~30 us).
     float uni_n = pre ? wk.planes.uni_n : 0.f;
-    const bool fast_path = exact_mode != 1 && fast_similarity_applies(ctx, D, w, tau);
     wk.speculated = false;
     if (fast_path && !pre) {
         // No scan and no round trip at the head of the chain: the approximate kernel takes the first pixel's count as THE count and checks
@@ -234,13 +236,15 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
         const int capacity = (int)std::min<size_t>(std::max<size_t>(npix, 1u << 16), 1u << 28);
         RCCHK(ensure(ctx, wk.border, (size_t)capacity * sizeof(uint2)));
         wk.border_capacity = capacity;
-        BcdBorderline bl = { 0.f, (uint2 *)wk.border.p, &d_flag->borderline, capacity };
+        BcdBorderline bl = { 0.f, (uint2 *)wk.border.p, &d_flag->borderline, capacity, 0.f, 0.f };
         // General sample counts (adaptive sampling, 24 spp, ...; src/core/DenoisingUnit.cpp:371-383 handles any n1, n2): the RATIO form of the dense kernel
         // (round 6, k_similarity_fast.hip) evaluates them at the cost of uniform ones -- 1.83 ms at 1080p against 1.73 for the uniform kernel, 3.0 ms for the
         // reference's operations and 1.97 + 0.07 ms for the own-list kernel of round 5, which it replaced -- and checks afterwards that the absolute errors it
         // adds stay inside the verified band (flag bit 2: the pass is then repeated with the reference's operations, and the workspace remembers the size).
         const bool use_ratio = !pre && uni_n == 0.f && !wk.ratio_is_declined(W, H);
         wk.ratio_used = pre ? wk.planes.ratio : use_ratio; // (planes computed ahead: the form their launches took; its verdict is in flag word [0])
+        const bool margin = margin_wanted && !wk.ratio_used; // (the RATIO form's absolute error is per counted bin: it keeps T / C planes)
+        const float margin_tau = margin ? tau : 0.f;
         if (pre) { if (e0) --wk.ev_used; } // (nothing to time: the planes are there)
         else if (use_ratio) {
             RCCHK(ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)));
@@ -249,9 +253,10 @@ int similarity(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_n
             if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
         } else {
             if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
-            HIPCHK(ctx, bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, wk.stream));
+            HIPCHK(ctx, bcd_launch_pairdist_rw(d_hist, d_ns, W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, wk.stream, margin_tau));
             if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
         }
+        if (margin) bcd_margin_band(D, tau, &bl.band_rel, &bl.band_abs);
         HIPCHK(ctx, hipMemcpyAsync(&h_flag->range, &d_flag->range, sizeof(int), hipMemcpyDeviceToHost, wk.stream));
         HIPCHK(ctx, hipMemcpyAsync(&h_flag->other_count, &d_flag->other_count, sizeof(int), hipMemcpyDeviceToHost, wk.stream)); // "another sample count" (plain-store flag)
         HIPCHK(ctx, bcd_launch_masks((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask, d_count, (uint32_t *)wk.fwd.p, wk.stream,
@@ -966,6 +971,8 @@ int bcd_hip_ctx_create(bcd_hip_ctx **out, int device, void *hip_stream)
     ctx->concurrent_scales = !(env && env[0] == '1');
     env = getenv("BCD_HIP_EXACT_SIMILARITY");
     ctx->fast_similarity = !(env && env[0] == '1');
+    env = getenv("BCD_HIP_TC_PLANES");
+    ctx->margin_planes = !(env && env[0] == '1');
     env = getenv("BCD_HIP_STREAM_UPLOADS");
     ctx->stream_uploads = !(env && env[0] == '0');
     env = getenv("BCD_HIP_SPARSE_UPLOAD");
@@ -1041,6 +1048,13 @@ int bcd_hip_set_fast_similarity(bcd_hip_ctx *ctx, int enabled)
 {
     if (!ctx) return BCD_HIP_EINVAL;
     ctx->fast_similarity = enabled != 0;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_set_margin_planes(bcd_hip_ctx *ctx, int enabled)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    ctx->margin_planes = enabled != 0;
     return BCD_HIP_OK;
 }
 

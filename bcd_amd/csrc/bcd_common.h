@@ -81,7 +81,17 @@ struct BcdBorderline {
     uint2 *list;       // (pixel index, displacement index) of the pairs with tau_lo < d' <= tau_hi
     int *counter;      // number of appended pairs (may exceed capacity: then the host falls back to the exact kernels)
     int capacity;
+    // margin planes (one signed binary16 value E = T - tau C per pixel pair; derivation in k_similarity.hip): a patch pair with sum E < -B is similar,
+    // with sum E > B it is not, B = band_rel * sum |E| + band_abs; anything between is listed.  band_rel == 0: the T / C planes
+    float band_rel, band_abs;
 };
+// B of the margin planes for histograms of D bins (u = 2^-24):  B / 2 = (2^-11 + 8 u) A + (2 D + 32) u (A + 18 tau D) + 9 * 2^-24
+inline void bcd_margin_band(int D, float tau, float *band_rel, float *band_abs)
+{
+    const double u = 5.9604644775390625e-08, fp = (2.0 * D + 32.0) * u;
+    *band_rel = (float)(2.0 * (4.8828125e-04 + 8.0 * u + fp) * (1.0 + 1e-3));
+    *band_abs = (float)(2.0 * (fp * 18.0 * tau * D + 9.0 * u) * (1.0 + 1e-3));
+}
 
 // ---- colour layers (bcd_hip_denoise_layers) -----------------------------------------------------------
 // One launch of a layer-batched kernel serves every layer: the layer is blockIdx.y (streaming kernels) or a loop / blockIdx.z group inside

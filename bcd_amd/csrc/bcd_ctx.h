@@ -132,7 +132,7 @@ struct Work {
     int strong_hint = 0, strong_hint_W = 0, strong_hint_H = 0;
     // approximate distance planes computed ahead of similarity() by a caller that streams the frame in (bcd_hip_denoise_host_ex): valid for
     // exactly this problem; similarity() consumes the note
-    struct { bool ready = false; const float *hist = nullptr, *ns = nullptr; int W = 0, H = 0, D = 0, b = 0; float tau = 0.f, uni_n = 0.f; bool ratio = false; /* by the RATIO form */ } planes;
+    struct { bool ready = false; const float *hist = nullptr, *ns = nullptr; int W = 0, H = 0, D = 0, b = 0; float tau = 0.f, uni_n = 0.f; bool ratio = false; /* by the RATIO form */ bool margin = false; /* one margin plane for this tau */ } planes;
     // uniform-sample-count speculation of the approximate distance kernel (similarity()): did the last frames on this workspace fail it?
     bool nonuniform = false;
     bool speculated = false;       // the current pass launched the uniform kernel on the first pixel's count, unchecked by the host
@@ -158,6 +158,7 @@ struct bcd_hip_ctx {
     bool profiling = false;
     bool concurrent_scales = true;
     bool fast_similarity = true; // approximate distance planes + exact re-evaluation at the threshold (k_similarity_fast.hip)
+    bool margin_planes = true;   // ... as one signed margin plane E = T - tau C (k_similarity.hip); false (BCD_HIP_TC_PLANES=1): the T and C planes
     int num_cus = 256;
     int cu_share_pct = 100;  // bcd_hip_set_cu_share
     // share of the CU slots the coarse scales' persistent estimate kernels take inside bcd_hip_denoise (bayes()); adjusted from call to
@@ -307,11 +308,12 @@ struct HostStreamProgress {
     int rows_filtered = 0, tile_rows_done = 0; // prefiltered lines [0, rows_filtered) (0 without the prefilter), plane tile rows [0, tile_rows_done)
     float uni_n = 0.f;                         // the uniform sample count the planes were launched for (0: general sample counts)
     bool ratio = false;                        // general sample counts by the RATIO form of the kernel (as similarity() would choose), else the reference's operations
+    bool margin = false;                       // the planes are margin planes for the call's threshold
 };
 int host_upload_stream(bcd_hip_ctx *ctx);
 int host_sparse_uploader(bcd_hip_ctx *ctx);
 int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *const d[9], int W, int H, int D, int b, float tau, bool prefilter, float spike_factor,
-                      int stop_after_chunks, bool poison, HostStreamProgress *out);
+                      int stop_after_chunks, bool poison, HostStreamProgress *out, bool margin);
 // does bcd_hip_denoise_host_ex stream a frame of this geometry in (row chunks, planes ahead of the last chunk)?
 inline bool host_frame_streams(const bcd_hip_ctx *ctx, int H, int D, const bcd_hip_params *prm)
 {
@@ -321,6 +323,8 @@ inline bool host_frame_streams(const bcd_hip_ctx *ctx, int H, int D, const bcd_h
 // bytes of the count planes of a scale.  ONE place: the host-buffer entry point computes planes ahead of similarity(), and a larger request there
 // would free them (round 6: it happened when one of the two grew, found by the environment-switch test on a fresh context)
 inline size_t count_plane_bytes(size_t npix, int nd) { return npix * (size_t)nd; }
+// ... and of its binary16 planes (the approximate T plane, or the margin plane, which has no count plane beside it)
+inline size_t half_plane_bytes(size_t npix, int nd) { return npix * (size_t)nd * 2; }
 
 // a user of the workspace's counters / flags / work queues / sub-counter lines outside the scale chain (self-tests, the eigensolver entry point): whatever
 // k_scale_begin left clean is not clean any more

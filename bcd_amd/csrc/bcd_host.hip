@@ -23,15 +23,16 @@ int host_sparse_uploader(bcd_hip_ctx *ctx)
 // Returns with everything enqueued: the main stream waits for what the upload streams carry.  stop_after_chunks >= 0: only that many row chunks are
 // uploaded and scheduled; poison: see below (both for the self-test; the host path passes -1 and false).
 int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *const d[9], int W, int H, int D, int b, float tau, bool prefilter, float spike_factor,
-                      int stop_after_chunks, bool poison, HostStreamProgress *out)
+                      int stop_after_chunks, bool poison, HostStreamProgress *out, bool margin)
 {
     Work &wk = ctx->main;
     RCCHK(host_upload_stream(ctx));
     const size_t np = (size_t)W * H;
     const size_t sz[4] = { np * 3, np, np * D, np * 6 };
     const int nd = bcd_delta_count(b), tile = bcd_pairdist_rw_tile_lines();
-    RCCHK(ensure(ctx, wk.T, np * nd * sizeof(float)));
-    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(np, nd))); // (the size similarity() will ask for: a larger request there would REALLOCATE the planes computed here)
+    // (the sizes similarity() will ask for: a larger request there would REALLOCATE the planes computed here)
+    RCCHK(ensure(ctx, wk.T, half_plane_bytes(np, nd)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(np, nd)));
     RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
     Counters::Flags *d_flag = &wk.d_counters()->flags;
     HIPCHK(ctx, hipMemsetAsync(d_flag, 0, sizeof(*d_flag), ctx->stream));
@@ -54,6 +55,8 @@ int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *cons
         RCCHK(ensure(ctx, wk.ratio_stats, 128 * sizeof(unsigned int)));
         HIPCHK(ctx, bcd_launch_ratio_begin((unsigned int *)wk.ratio_stats.p, ctx->stream));
     }
+    margin = margin && !ratio; // (the RATIO form keeps T / C planes)
+    const float margin_tau = margin ? tau : 0.f; // the margin plane is a function of the threshold: known here, before the first launch
     const int chunk = std::max(64, ((H + 7) / 8 + tile - 1) / tile * tile); // ~8 chunks, whole tile rows
     const int tile_rows = (H + tile - 1) / tile;
     int filtered = 0, tiles_done = 0, k = 0;
@@ -62,7 +65,7 @@ int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *cons
             HIPCHK(ctx, hipMemsetAsync(d[i], 0xFF, sz[i] * sizeof(float), ctx->stream));
             if (d[5 + i] != d[i]) HIPCHK(ctx, hipMemsetAsync(d[5 + i], 0xFF, sz[i] * sizeof(float), ctx->stream));
         }
-        HIPCHK(ctx, hipMemsetAsync(wk.T.p, 0xFF, np * nd * sizeof(float), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(wk.T.p, 0xFF, half_plane_bytes(np, nd), ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(wk.Cn.p, 0xFF, count_plane_bytes(np, nd), ctx->stream));
     }
     // the upload stream must not overwrite device copies an earlier frame's kernels may still read
@@ -126,7 +129,7 @@ int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *cons
         const int t_end = avail == H ? tile_rows : std::max(0, (avail - b) / tile);
         if (t_end > tiles_done) {
             if (ratio) HIPCHK(ctx, bcd_launch_pairdist_rw_ratio_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, (unsigned int *)wk.ratio_stats.p, tiles_done, t_end, ctx->stream));
-            else HIPCHK(ctx, bcd_launch_pairdist_rw_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, tiles_done, t_end, ctx->stream));
+            else HIPCHK(ctx, bcd_launch_pairdist_rw_rows(d[7], d[6], W, H, D, b, wk.T.p, (uint8_t *)wk.Cn.p, &d_flag->range, uni_n, tiles_done, t_end, ctx->stream, margin_tau));
             tiles_done = t_end;
             if (ratio && tiles_done == tile_rows) HIPCHK(ctx, bcd_launch_ratio_verdict((const unsigned int *)wk.ratio_stats.p, tau, &d_flag->range, ctx->stream));
         }
@@ -137,7 +140,7 @@ int host_stream_frame(bcd_hip_ctx *ctx, const float *const h_src[4], float *cons
         HIPCHK(ctx, side_rc);
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload2, 0));
     }
-    out->chunk_lines = chunk; out->chunks = k; out->rows_filtered = filtered; out->tile_rows_done = tiles_done; out->uni_n = uni_n; out->ratio = ratio;
+    out->chunk_lines = chunk; out->chunks = k; out->rows_filtered = filtered; out->tile_rows_done = tiles_done; out->uni_n = uni_n; out->ratio = ratio; out->margin = margin;
     return BCD_HIP_OK;
 }
 
@@ -175,10 +178,10 @@ static int denoise_host_impl(bcd_hip_ctx *ctx, const float *h_colors, const floa
         if (prefilter) HIPCHK(ctx, bcd_launch_spike(d[0], d[1], d[2], d[3], W, H, D, opt->spike_factor, d[5], d[6], d[7], d[8], ctx->stream));
     } else {
         HostStreamProgress done;
-        RCCHK(host_stream_frame(ctx, src, d, W, H, D, b, prm->hist_dist_threshold, prefilter, prefilter ? opt->spike_factor : 0.f, -1, false, &done));
+        RCCHK(host_stream_frame(ctx, src, d, W, H, D, b, prm->hist_dist_threshold, prefilter, prefilter ? opt->spike_factor : 0.f, -1, false, &done, ctx->margin_planes));
         Work &wk = ctx->main;
         wk.planes.ready = true; wk.planes.hist = d[7]; wk.planes.ns = d[6]; wk.planes.W = W; wk.planes.H = H; wk.planes.D = D; wk.planes.b = b;
-        wk.planes.tau = prm->hist_dist_threshold; wk.planes.uni_n = done.uni_n; wk.planes.ratio = done.ratio;
+        wk.planes.tau = prm->hist_dist_threshold; wk.planes.uni_n = done.uni_n; wk.planes.ratio = done.ratio; wk.planes.margin = done.margin;
     }
     LayerView lv;
     if (nb_extra > 0) { // device copies of the extra layers: colours | covariances | outputs, one slice per layer

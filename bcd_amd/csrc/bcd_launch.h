@@ -47,10 +47,12 @@ hipError_t bcd_launch_scale_inplace(float *x, float a, int64_t n, hipStream_t st
 // ---- k_similarity_fast.hip
 int bcd_pairdist_rw_supported(int D);
 int bcd_pairdist_rw_tile_lines();
+// margin_tau > 0: the margin form -- one signed binary16 plane E = sum over the live bins of (d^2 / s - margin_tau) in T, Cn is not written; 0: the T / C planes
+// (the RATIO form always writes T / C planes)
 hipError_t bcd_launch_pairdist_rw(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
-                                  float uni_n, hipStream_t st);
+                                  float uni_n, hipStream_t st, float margin_tau = 0.f);
 hipError_t bcd_launch_pairdist_rw_rows(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
-                                       float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st);
+                                       float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st, float margin_tau = 0.f);
 hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
                                         float tau, unsigned int *stats, hipStream_t st);
 hipError_t bcd_launch_ratio_begin(unsigned int *stats, hipStream_t st);

@@ -325,7 +325,7 @@ int bcd_hip_selftest_host_stream(bcd_hip_ctx *ctx, const float *h_colors, const 
     }
     const int b = prm->search_radius, nd = bcd_delta_count(b);
     HostStreamProgress done;
-    const int rc = host_stream_frame(ctx, src, d, W, H, D, b, prm->hist_dist_threshold, prefilter, spike_factor, stop_after_chunks, poison != 0, &done);
+    const int rc = host_stream_frame(ctx, src, d, W, H, D, b, prm->hist_dist_threshold, prefilter, spike_factor, stop_after_chunks, poison != 0, &done, false /* the T / C planes this entry point returns */);
     // (also after a failure: nothing of this call stays in flight on the upload streams)
     hipError_t e = ctx->upload_stream ? hipStreamSynchronize(ctx->upload_stream) : hipSuccess;
     if (ctx->upload_stream2) { const hipError_t e2 = hipStreamSynchronize(ctx->upload_stream2); if (e == hipSuccess) e = e2; }

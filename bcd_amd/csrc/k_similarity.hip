@@ -650,6 +650,204 @@ __global__ __launch_bounds__(64) void k_fwd_masks_w1v4a(const __half *__restrict
     borderline_flush<FWD_RB * 4>(bl, bword, pix, wi, lane);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// MARGIN PLANES.  The T and C planes have one consumer, the test  sum T / sum C <= tau  over the nine pixel pairs of a patch pair, which is
+// sum (T - tau C) <= 0.  The margin form of k_pairdist_rw (k_similarity_fast.hip) therefore writes ONE signed binary16 value per pixel pair,
+//     E = sum over the live bins of (d^2 / s - tau)          (0x8000, "-0": no live bin; a touched value never carries that pattern)
+// -- 2 bytes per entry instead of 3, no count stream, no packed-byte sums -- and the kernels below decide a patch pair from  SE = sum of the nine E
+// and  A = sum of the nine |E|:  similar when SE < -B, not similar when SE > B, listed for k_verify_pairs otherwise, B = band_rel A + band_abs.
+// All nine entries 0x8000 <=> SE has the bit pattern of -0 (x + -0 = x, a sum that cancels is +0): the reference's 0 / 0, never similar.
+//
+// The bound B (u = 2^-24; t = d^2 / s the real term of a live bin, T, C, E = T - tau C the real sums of a pixel pair; S = sum T, C9 = sum C over the patch;
+// inputs inside the guarded range, so nothing overflows in fp32):
+//   reference:   its term RN(RN(d^2) / s) = t (1 + 2u), <= D - 1 additions per pixel pair, 8 per patch, one division by float(C9) (exact):
+//                d_ref = (S / C9) (1 + a), |a| <= (D + 11) u.  So d_ref <= tau is decided by the sign of M = S - tau C9 unless |M| <= (D + 11) u S;
+//   planes:      UNI  q = RN(d^2 - RN(tau s)) (tau == 1: RN(d^2 - s)), r = rcp(s) (1 ulp = 2u), the product q r enters the fma unrounded: it is
+//                (t - tau) within 4u (t + tau); <= D additions, each off by <= u times a partial sum <= sum |terms| <= T + tau C:
+//                |E' - E| <= (D + 4) u (T + tau C).  General counts (the reference's diff and den): T' as in the header of k_similarity_fast.hip, then
+//                E' = fma(-tau, C, T'), <= (D + 21) u (T + tau C) with room to spare.  (The RATIO form keeps T / C planes: its absolute error is per counted bin);
+//   binary16:    |E16 - E'| <= 2^-11 |E'|, or 2^-25 below 2^-14 (also for a touched value stored as +0); +inf (E' > 65504) makes SE = +inf: not similar,
+//                as it must be (the other eight are >= -tau D each), or, where B - SE is NaN, listed;
+//   here:        8 fp32 additions of the nine E16 in any order: <= 8 u A;
+//   T + tau C = E + 2 tau C <= |E| + 2 tau D, over the patch <= A + 18 tau D (the kernels do not know C; D bins is all a pixel pair can count).
+// Together a decision from SE can differ from the reference's only if
+//     |SE| <= (2^-11 + 8u) A + (2 D + 32) u (A + 18 tau D) + 9 * 2^-25
+// and B is twice that (bcd_margin_band, bcd_common.h).  At D = 60, tau = 1: B = 9.9e-4 A + 0.020 -- against the T / C planes' band 2^-10 tau C9,
+// narrower wherever the nine margins are small against tau C9, i.e. for exactly the pairs near the threshold whose pixel pairs are alike.
+// ---------------------------------------------------------------------------------------------------
+template <int NROWS>
+__device__ inline bool margin_decide(const float (&e)[NROWS][3], int i, float band_rel, float band_abs, bool &border)
+{
+    // (the narrow kernel: plain code; e[line][left, centre, right])
+    float se = e[i][0], a = fabsf(e[i][0]);
+#pragma unroll
+    for (int k = 1; k < 9; ++k) { const float v = e[i + k / 3][k % 3]; se += v; a += fabsf(v); }
+    const float B = fmaf(band_rel, a, band_abs);
+    const bool none = __float_as_uint(se) == 0x80000000u; // no counted bin in the whole patch
+    border = !none && !(se < -B) && !(se > B);            // (NaN from +inf entries of either sign: listed)
+    return !none && se < -B;
+}
+
+__global__ __launch_bounds__(64) void k_fwd_masks_w1m(const __half *__restrict__ E, int W, int H, int b, int fwords, int nd, uint32_t *__restrict__ fwd, BcdBorderline bl,
+                                                      int rb0 /* first block of FWD_RB lines */, int row_end /* lines written: < row_end */)
+{
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x * 62 + lane - 1; // lanes 1..62 produce output
+    const int rb = (blockIdx.y + rb0) * FWD_RB;
+    const int wi = blockIdx.z;
+    const bool writer = lane >= 1 && lane <= 62 && c < W;
+    const bool c_main = c >= 1 && c <= W - 2;
+    const size_t plane = (size_t)W * H;
+    const int cc = min(max(c, 0), W - 1), side = 2 * b + 1;
+    size_t off[FWD_RB + 2];
+#pragma unroll
+    for (int i = 0; i < FWD_RB + 2; ++i) off[i] = (size_t)min(max(rb - 1 + i, 0), H - 1) * W + cc;
+    uint32_t word[FWD_RB], bword[FWD_RB];
+#pragma unroll
+    for (int i = 0; i < FWD_RB; ++i) { word[i] = 0; bword[i] = 0; }
+    const int d_end = min(nd, 32 * wi + 32);
+    int dl = 0, dc = 32 * wi;
+    if (dc > b) { int e = dc - (b + 1); dl = 1 + e / side; dc = e - (dl - 1) * side - b; }
+    for (int didx = 32 * wi; didx < d_end; ++didx, dc = (dc == b ? -b : dc + 1), dl += (dc == -b ? 1 : 0)) {
+        const __half *Ep = E + (size_t)didx * plane;
+        float e[FWD_RB + 2][3];
+#pragma unroll
+        for (int i = 0; i < FWD_RB + 2; ++i) e[i][1] = __half2float(Ep[off[i]]);
+#pragma unroll
+        for (int i = 0; i < FWD_RB + 2; ++i) { e[i][0] = lane_up(e[i][1]); e[i][2] = lane_down(e[i][1]); }
+        const int qc = c + dc;
+        const bool cols_ok = c_main && qc >= 1 && qc <= W - 2;
+#pragma unroll
+        for (int i = 0; i < FWD_RB; ++i) {
+            const int r = rb + i;
+            if (cols_ok && r >= 1 && r <= H - 2 && r + dl <= H - 2) { // (entries of pairs that leave the image are never written: not looked at)
+                bool border;
+                if (margin_decide<FWD_RB + 2>(e, i, bl.band_rel, bl.band_abs, border)) word[i] |= 1u << (didx & 31);
+                else if (border && writer) bword[i] |= 1u << (didx & 31);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < FWD_RB; ++i)
+        if (writer && rb + i < row_end) fwd[(size_t)wi * plane + (size_t)(rb + i) * W + c] = word[i];
+    uint32_t pix[FWD_RB];
+#pragma unroll
+    for (int i = 0; i < FWD_RB; ++i) { pix[i] = (uint32_t)((rb + i) * W + c); if (rb + i >= row_end) bword[i] = 0; } // (lines of a later launch)
+    borderline_flush<FWD_RB>(bl, bword, pix, wi, lane);
+}
+
+// Four columns per lane, the structure of k_fwd_masks_w1v4a with one 8-byte load per line and plane: horizontal 3-sums of E and of |E| (the absolute value is an
+// operand modifier), per output SE and A by two additions each, B by one fma, the two signs  -B - SE  (bit 1: not decided similar)  and  B - SE  (bit 1: decided not
+// similar) shifted into the accumulators.  A patch without a counted bin (SE == -0) takes SE = +inf: both signs set.
+struct FwdRawM { fwd_u32x2 t[FWD_RB + 2]; };
+
+template <bool EDGE>
+__device__ inline void fwd_v4m_loop(const __half *__restrict__ E, size_t plane, const uint32_t (&off)[FWD_RB + 2], int W, int H, int b, int c, int rb, float band_rel,
+                                    float band_abs, int d_begin, int trips, int d_last, uint32_t (&alo)[FWD_RB * 4], uint32_t (&ahi)[FWD_RB * 4])
+{
+    const int side = 2 * b + 1;
+    auto load = [&](int didx, FwdRawM &x) __attribute__((always_inline)) {
+        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half *>(E + (size_t)didx * plane), 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < FWD_RB + 2; ++i) x.t[i] = __builtin_amdgcn_raw_buffer_load_b64(rt, 2u * off[i], 0, 0);
+    };
+    auto eval = [&](const FwdRawM &x, int dl, int dc) __attribute__((always_inline)) {
+        float hs[FWD_RB + 2][4], ha[FWD_RB + 2][4];
+#pragma unroll
+        for (int i = 0; i < FWD_RB + 2; ++i) {
+            const uint32_t t01 = x.t[i].x, t23 = x.t[i].y;
+            const __half2 h01 = *reinterpret_cast<const __half2 *>(&t01), h23 = *reinterpret_cast<const __half2 *>(&t23);
+            const float2 f01 = __half22float2(h01), f23 = __half22float2(h23);
+            const float tl = wave_prev(f23.y), tr = wave_next(f01.x);
+            hs[i][0] = (tl + f01.x) + f01.y; hs[i][1] = (f01.x + f01.y) + f23.x; hs[i][2] = (f01.y + f23.x) + f23.y; hs[i][3] = (f23.x + f23.y) + tr;
+            ha[i][0] = (fabsf(tl) + fabsf(f01.x)) + fabsf(f01.y); ha[i][1] = (fabsf(f01.x) + fabsf(f01.y)) + fabsf(f23.x);
+            ha[i][2] = (fabsf(f01.y) + fabsf(f23.x)) + fabsf(f23.y); ha[i][3] = (fabsf(f23.x) + fabsf(f23.y)) + fabsf(tr);
+        }
+        // (EDGE) columns: c + j and c + j + dc main pixels <=> c + j in [clo, clo + cspan]; lines: r and r + dl main pixels
+        const int clo = max(1, 1 - dc), cspan = min(W - 2, W - 2 - dc) - clo;
+#pragma unroll
+        for (int i = 0; i < FWD_RB; ++i) {
+            const int r = rb + i;
+            const bool row_ok = r >= 1 && r <= H - 2 && r + dl <= H - 2; // (wave-uniform; EDGE only)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float se = (hs[i][j] + hs[i + 1][j]) + hs[i + 2][j];
+                const float a = (ha[i][j] + ha[i + 1][j]) + ha[i + 2][j];
+                se = __float_as_uint(se) == 0x80000000u ? __builtin_huge_valf() : se; // no counted bin: never similar, never listed
+                const float B = fmaf(band_rel, a, band_abs);
+                float ylo = -B - se, yhi = B - se;
+                if (EDGE) { // (plane entries of pairs that leave the image are never written: whatever they hold must not reach the sign)
+                    const bool valid = row_ok && cspan >= 0 && (uint32_t)(c + j - clo) <= (uint32_t)cspan;
+                    ylo = valid ? ylo : -1.f; yhi = valid ? yhi : -1.f;
+                }
+                alo[i * 4 + j] = __builtin_amdgcn_alignbit(alo[i * 4 + j], __float_as_uint(ylo), 31);
+                ahi[i * 4 + j] = __builtin_amdgcn_alignbit(ahi[i * 4 + j], __float_as_uint(yhi), 31);
+            }
+        }
+    };
+    int dl = 0, dc = d_begin;
+    if (dc > b) { int e = dc - (b + 1); dl = 1 + e / side; dc = e - (dl - 1) * side - b; }
+    FwdRawM A, Bq;
+    load(d_begin, A);
+    // (the loop-carried set must not look like a plain load to the optimiser: see fwd_v4a_loop)
+#pragma unroll
+    for (int i = 0; i < FWD_RB + 2; ++i) asm volatile("" : "+v"(A.t[i]));
+    int didx = d_begin;
+    for (int t = 0; t < trips; ++t) {
+        load(min(didx + 1, d_last), Bq);
+        __builtin_amdgcn_sched_barrier(0);
+        eval(A, dl, dc);
+        dc = (dc == b ? -b : dc + 1); dl += (dc == -b ? 1 : 0);
+        load(min(didx + 2, d_last), A);
+        __builtin_amdgcn_sched_barrier(0);
+        eval(Bq, dl, dc);
+        dc = (dc == b ? -b : dc + 1); dl += (dc == -b ? 1 : 0);
+        didx += 2;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_fwd_masks_w1v4m(const __half *__restrict__ E, int W, int H, int b, int fwords, int nd, uint32_t *__restrict__ fwd, BcdBorderline bl,
+                                                        int rb0, int row_end)
+{
+    const int lane = threadIdx.x;
+    const int xb = blockIdx.x;
+    const int rb = (blockIdx.y + rb0) * FWD_RB;
+    const int c = xb * 248 - 4 + 4 * lane; // first of the lane's four columns
+    const int wi = blockIdx.z;
+    const bool writer = lane >= 1 && lane <= 62 && c < W;
+    const size_t plane = (size_t)W * H;
+    const int cc = min(max(c, 0), W - 4);
+    uint32_t off[FWD_RB + 2]; // (element offsets inside a plane: 32 bits -- the caller admits frames below 2^30 pixels)
+#pragma unroll
+    for (int i = 0; i < FWD_RB + 2; ++i) off[i] = (uint32_t)(min(max(rb - 1 + i, 0), H - 1) * W + cc);
+    uint32_t alo[FWD_RB * 4], ahi[FWD_RB * 4];
+#pragma unroll
+    for (int i = 0; i < FWD_RB * 4; ++i) { alo[i] = ~0u; ahi[i] = ~0u; }
+    const int d_begin = 32 * wi, k = min(nd, d_begin + 32) - d_begin, trips = (k + 1) >> 1; // 1 <= k <= 32 planes, evaluated two per trip
+    const int cfirst = xb * 248, clast = min(cfirst + 247, W - 1);
+    const bool edge = cfirst - b < 1 || clast + b > W - 2 || rb < 1 || rb + FWD_RB - 1 + b > H - 2;
+    if (edge) fwd_v4m_loop<true>(E, plane, off, W, H, b, c, rb, bl.band_rel, bl.band_abs, d_begin, trips, d_begin + k - 1, alo, ahi);
+    else fwd_v4m_loop<false>(E, plane, off, W, H, b, c, rb, bl.band_rel, bl.band_abs, d_begin, trips, d_begin + k - 1, alo, ahi);
+    // accumulators as in k_fwd_masks_w1v4a: lo = decided similar, hi = not decided dissimilar; the borderline word is hi & ~lo
+    const int sh = 32 - 2 * trips;
+    const uint32_t keep = k == 32 ? ~0u : ((1u << k) - 1u);
+    uint32_t bword[FWD_RB * 4], pix[FWD_RB * 4];
+#pragma unroll
+    for (int i = 0; i < FWD_RB; ++i) {
+        const bool mine = writer && rb + i < row_end; // (lines of a later launch are that launch's)
+        uint32_t wl[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t wlo = (__brev(~alo[i * 4 + j]) >> sh) & keep, whi = (__brev(~ahi[i * 4 + j]) >> sh) & keep;
+            wl[j] = wlo;
+            pix[i * 4 + j] = (uint32_t)((rb + i) * W + c + j);
+            bword[i * 4 + j] = mine ? (whi & ~wlo) : 0u;
+        }
+        if (mine) *reinterpret_cast<uint4 *>(fwd + (size_t)wi * plane + (size_t)(rb + i) * W + c) = make_uint4(wl[0], wl[1], wl[2], wl[3]);
+    }
+    borderline_flush<FWD_RB * 4>(bl, bword, pix, wi, lane);
+}
+
 // kernel 3: full (2b+1)^2-bit masks and |S| from the forward bits: bit(p, -delta) = bit(p - delta, +delta)
 __global__ __launch_bounds__(256) void k_sym_masks(const uint32_t *__restrict__ fwd, int W, int H, int b, int fwords, int words,
                                                    uint32_t *__restrict__ mask, int32_t *__restrict__ count)
@@ -921,7 +1119,10 @@ hipError_t bcd_launch_fwd_masks_rows(const float *T, const uint8_t *Cn, int W, i
     const bool wide = W % 4 == 0 && (int64_t)W * H >= 400000;
     const int rb0 = row_begin / FWD_RB, nrb = (row_end - row_begin + FWD_RB - 1) / FWD_RB;
     const dim3 gw((W + 247) / 248, nrb, fwords), gn((W + 61) / 62, nrb, fwords);
-    if (wide && ap)
+    if (ap && ap->band_rel > 0.f) { // margin planes: T holds E, there is no count plane
+        if (wide) hipLaunchKernelGGL(k_fwd_masks_w1v4m, gw, dim3(64), 0, st, reinterpret_cast<const __half *>(T), W, H, b, fwords, bcd_delta_count(b), fwd_scratch, bl, rb0, row_end);
+        else hipLaunchKernelGGL(k_fwd_masks_w1m, gn, dim3(64), 0, st, reinterpret_cast<const __half *>(T), W, H, b, fwords, bcd_delta_count(b), fwd_scratch, bl, rb0, row_end);
+    } else if (wide && ap)
         hipLaunchKernelGGL(k_fwd_masks_w1v4a, gw, dim3(64), 0, st, reinterpret_cast<const __half *>(T), Cn, W, H, b, tau_k, fwords, bcd_delta_count(b), fwd_scratch, bl, rb0, row_end);
     else if (wide)
         hipLaunchKernelGGL(k_fwd_masks_w1v4, gw, dim3(64), 0, st, T, Cn, W, H, b, tau_k, fwords, bcd_delta_count(b), fwd_scratch, rb0, row_end);

@@ -33,6 +33,11 @@
 //     test of its group of 4 bins: 49 % of the bins are evaluated on the noisy bench frame, 20 % on a clean one,
 //     ~7.5 instructions per bin on average (flat, select-based code: 9-10; the exact kernel: ~20);
 //   * 128 VGPRs -> 4 wavefronts per SIMD (the exact kernel: 2), neighbour histograms read two float4 ahead of their use.
+//
+// Margin form (template flag MARGIN, production for uniform counts and for the reference's operations on general counts): T and C are consumed only as
+// sum (T - tau C) <= 0, so the kernel writes the margin E = sum over the live bins of (d^2 / s - tau) as ONE signed binary16 plane -- per bin v_sub, v_fma
+// (d^2 - tau s), v_rcp, v_fma instead of the packed fma that carried term and count, 2 bytes per entry instead of 3.  Its consumers and the bound that
+// replaces the band above are in k_similarity.hip (margin kernels).  The T / C instantiations stay for the RATIO form, the self-tests and BCD_HIP_TC_PLANES=1.
 #include "bcd_common.h"
 #include <hip/hip_fp16.h>
 #include <atomic>
@@ -91,13 +96,16 @@ template <int D> struct RwLayout {
 // (so that 10 u r max(B1, B2) <= 10 u kappa G C for every pair), and k_ratio_verdict raises flag bit 2 (value 4) when
 //     10 u kappa G  >  2^-12 tau          (what the relative errors leave of the verified band: 2^-10 - 2^-11 [binary16] - 2e-5 [fp32] = 4.7e-4 > 2^-12)
 // -- the host then repeats the scale with the reference's operations (RATIO = false).  Pairs with C = 0 have T = 0 exactly either way.
-template <int D, bool UNI, bool COUNT = false, bool RATIO = false>
+template <int D, bool UNI, bool COUNT = false, bool RATIO = false, bool MARGIN = false, bool TAU1 = false>
 __global__ __launch_bounds__(RW_THREADS, (UNI || RATIO) ? 4 : 2) void k_pairdist_rw(const float *__restrict__ hist, const float *__restrict__ ns, int W, int H,
                                                               int b, __half *__restrict__ T, uint8_t *__restrict__ Cn, int *range_flag,
                                                               float uni_n, int tile_row0 /* first tile row of this launch */,
-                                                              unsigned long long *work_count = nullptr, unsigned int *ratio_stats = nullptr /* RATIO: 8 lines of (kappa, G) */)
+                                                              unsigned long long *work_count = nullptr, unsigned int *ratio_stats = nullptr /* RATIO: 8 lines of (kappa, G) */,
+                                                              float tau = 1.f /* MARGIN */)
 {
     static_assert(!(UNI && RATIO), "RATIO is a form of the general kernel");
+    static_assert(!(MARGIN && (COUNT || RATIO)), "the counting instantiation and the RATIO form write T / C planes");
+    static_assert(!TAU1 || (MARGIN && UNI), "TAU1 is the uniform margin body for tau == 1");
     using L = RwLayout<D>;
     constexpr int Q = D / 4, NPRE = L::NPRE;
     extern __shared__ float4 lds4[];
@@ -262,6 +270,9 @@ __global__ __launch_bounds__(RW_THREADS, (UNI || RATIO) ? 4 : 2) void k_pairdist
                 // (sum, number of bins counted) as one packed pair: the bin's term and its count go in with a single v_pk_fma_f32
                 v2f acc2 = { 0.f, 0.f };
                 v2f pd = { 0.f, 1.f }, pr = { 0.f, 1.f };
+                // (MARGIN, UNI) the margin E = sum over the live bins of (d^2 / s - tau) in one scalar accumulator: it starts at -0 and keeps that bit
+                // pattern exactly when no bin is live (x + -0 = x, and a sum that cancels is +0 under round to nearest)
+                float accm = -0.f;
 #pragma unroll
                 for (int q = 0; q < Q; ++q) {
                     const float4 v = pf[q % PF];
@@ -295,9 +306,15 @@ __global__ __launch_bounds__(RW_THREADS, (UNI || RATIO) ? 4 : 2) void k_pairdist
                         for (int e = 0; e < 4; ++e)
                             if (sg[e] > 1.f) {
                                 asm volatile(""); // keep the branch: no if-conversion into selects
-                                pd.x = term(e);
-                                pr.x = __builtin_amdgcn_rcpf(den(sg[e]));
-                                acc2 = __builtin_elementwise_fma(pd, pr, acc2);
+                                if (MARGIN && UNI) { // d^2 / s - tau = rcp(s) (d^2 - tau s): no packed fma, no count
+                                    const float d = h1[4 * q + e] - b2[e];
+                                    const float qm = TAU1 ? fmaf(d, d, -sg[e]) : fmaf(d, d, -(tau * sg[e]));
+                                    accm = fmaf(qm, __builtin_amdgcn_rcpf(sg[e]), accm);
+                                } else {
+                                    pd.x = term(e);
+                                    pr.x = __builtin_amdgcn_rcpf(den(sg[e]));
+                                    acc2 = __builtin_elementwise_fma(pd, pr, acc2);
+                                }
                             }
                     }
                 }
@@ -317,8 +334,16 @@ __global__ __launch_bounds__(RW_THREADS, (UNI || RATIO) ? 4 : 2) void k_pairdist
                         tv *= q;
                         if (acc2.y > 0.f) gmax = fmaxf(gmax, fmaxf(rho, q) * (n1 * fmaxf(1.f, q)) * __builtin_amdgcn_rcpf(acc2.y)); // r max(n1, n2) / C
                     }
-                    T[o] = __float2half_rn(tv); // binary16 plane (a sum beyond 65504 becomes +inf: far above any admitted tau)
-                    Cn[o] = (uint8_t)(int)acc2.y;
+                    if (MARGIN) {
+                        // one signed plane: 0x8000 = no live bin (the reference's 0 / 0); a touched value that rounds to -0 is stored as +0
+                        const float ev = UNI ? accm : (acc2.y > 0.f ? fmaf(-tau, acc2.y, tv) : -0.f); // (general counts: E formed once per pair)
+                        unsigned short hb = __half_as_ushort(__float2half_rn(ev));
+                        if (hb == 0x8000u && __float_as_uint(ev) != 0x80000000u) hb = 0;
+                        reinterpret_cast<unsigned short *>(T)[o] = hb; // (+inf: far above any admitted tau, as on the T plane)
+                    } else {
+                        T[o] = __float2half_rn(tv); // binary16 plane (a sum beyond 65504 becomes +inf: far above any admitted tau)
+                        Cn[o] = (uint8_t)(int)acc2.y;
+                    }
                 }
             }
             if (dl < b) {
@@ -477,35 +502,43 @@ int bcd_pairdist_rw_supported(int D) { return D == 60 || D == 36 || D == 24; }
 // whose lines have arrived.
 int bcd_pairdist_rw_tile_lines() { return RW_TH; }
 
+// one instantiation of k_pairdist_rw: grants its dynamic LDS once per device, then launches
+template <int DD, bool UU, bool CC, bool RR, bool MM, bool T1>
+static hipError_t rw_launch(dim3 grid, hipStream_t st, int dev, const float *hist, const float *ns, int W, int H, int b, void *T, uint8_t *Cn, int *d_range_flag, float uni_n,
+                            int tile_row_begin, unsigned long long *work_count, unsigned int *stats, float tau)
+{
+    const size_t lds = (size_t)RwLayout<DD>::LDS_DWORDS * 4;
+    static std::atomic<int> granted[64]; /* per instantiation and device */
+    if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || granted[dev].load() == 0)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pairdist_rw<DD, UU, CC, RR, MM, T1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) granted[dev].store(1);
+    }
+    hipLaunchKernelGGL((k_pairdist_rw<DD, UU, CC, RR, MM, T1>), grid, dim3(RW_THREADS), lds, st, hist, ns, W, H, b, static_cast<__half *>(T), Cn, d_range_flag, uni_n, tile_row_begin,
+                       work_count, stats, tau);
+    return hipGetLastError();
+}
+
+// margin_tau > 0: the margin form -- ONE signed binary16 plane E = sum over the live bins of (d^2 / s - tau) in T, Cn is not written (k_similarity.hip, margin kernels).
+// The RATIO form has none: its absolute error is bounded per COUNTED BIN (2^-12 tau C), and a consumer of margins does not know C -- with C <= 9 D in its place the
+// band of a patch with few live bins came out wider than the T / C planes' 2^-10 (measured: 6 514 listed pairs against 5 830 on the sparse plateau with mixed counts)
 static hipError_t pairdist_rw_rows(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
-                                   float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st, unsigned long long *work_count)
+                                   float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st, unsigned long long *work_count, float margin_tau)
 {
     const int tile_rows = (H + RW_TH - 1) / RW_TH;
     if (tile_row_end < 0 || tile_row_end > tile_rows) tile_row_end = tile_rows;
     if (tile_row_begin < 0 || tile_row_begin >= tile_row_end) return tile_row_begin == tile_row_end ? hipSuccess : hipErrorInvalidValue;
-    dim3 grid((W + RW_TW - 1) / RW_TW, tile_row_end - tile_row_begin), block(RW_THREADS);
+    if (work_count && margin_tau > 0.f) return hipErrorInvalidValue; // (the counting instantiation writes T / C planes)
+    dim3 grid((W + RW_TW - 1) / RW_TW, tile_row_end - tile_row_begin);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-#define BCD_RW_LAUNCH(DD, UU)                                                                                        \
-    {                                                                                                                \
-        const size_t lds = (size_t)RwLayout<DD>::LDS_DWORDS * 4;                                                     \
-        static std::atomic<int> granted[64]; /* per instantiation and device */                                     \
-        if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || granted[dev].load() == 0)) {                                 \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pairdist_rw<DD, UU>),               \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-            if (e != hipSuccess) return e;                                                                           \
-            if (dev >= 0 && dev < 64) granted[dev].store(1);                                                         \
-        }                                                                                                            \
-        if (work_count) { /* the counting instantiation (measurement only) */                                       \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pairdist_rw<DD, UU, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e;                                                                           \
-            hipLaunchKernelGGL((k_pairdist_rw<DD, UU, true>), grid, block, lds, st, hist, ns, W, H, b, static_cast<__half *>(T), Cn, d_range_flag, uni_n, tile_row_begin, work_count); \
-            return hipGetLastError();                                                                                \
-        }                                                                                                            \
-        hipLaunchKernelGGL((k_pairdist_rw<DD, UU>), grid, block, lds, st, hist, ns, W, H, b, static_cast<__half *>(T), Cn, d_range_flag, uni_n, tile_row_begin, (unsigned long long *)nullptr); \
-        return hipGetLastError();                                                                                    \
-    }
-#define BCD_RW_DEPTH(DD) case DD: if (uni_n != 0.f) BCD_RW_LAUNCH(DD, true) else BCD_RW_LAUNCH(DD, false)
+#define BCD_RW_ARGS grid, st, dev, hist, ns, W, H, b, T, Cn, d_range_flag, uni_n, tile_row_begin, work_count, (unsigned int *)nullptr, margin_tau
+#define BCD_RW_DEPTH(DD)                                                                                             \
+    case DD:                                                                                                         \
+        if (work_count) return uni_n != 0.f ? rw_launch<DD, true, true, false, false, false>(BCD_RW_ARGS) : rw_launch<DD, false, true, false, false, false>(BCD_RW_ARGS); \
+        if (margin_tau == 1.f && uni_n != 0.f) return rw_launch<DD, true, false, false, true, true>(BCD_RW_ARGS);    \
+        if (margin_tau > 0.f) return uni_n != 0.f ? rw_launch<DD, true, false, false, true, false>(BCD_RW_ARGS) : rw_launch<DD, false, false, false, true, false>(BCD_RW_ARGS); \
+        return uni_n != 0.f ? rw_launch<DD, true, false, false, false, false>(BCD_RW_ARGS) : rw_launch<DD, false, false, false, false, false>(BCD_RW_ARGS);
     switch (D) {
     BCD_RW_DEPTH(60)
     BCD_RW_DEPTH(36)
@@ -513,7 +546,7 @@ static hipError_t pairdist_rw_rows(const float *hist, const float *ns, int W, in
     default: break;
     }
 #undef BCD_RW_DEPTH
-#undef BCD_RW_LAUNCH
+#undef BCD_RW_ARGS
     return hipErrorInvalidValue;
 }
 
@@ -540,30 +573,20 @@ hipError_t bcd_launch_pairdist_rw_ratio_rows(const float *hist, const float *ns,
     const int tile_rows = (H + RW_TH - 1) / RW_TH;
     if (tile_row_end < 0 || tile_row_end > tile_rows) tile_row_end = tile_rows;
     if (tile_row_begin < 0 || tile_row_begin >= tile_row_end) return tile_row_begin == tile_row_end ? hipSuccess : hipErrorInvalidValue;
-    dim3 grid((W + RW_TW - 1) / RW_TW, tile_row_end - tile_row_begin), block(RW_THREADS);
+    dim3 grid((W + RW_TW - 1) / RW_TW, tile_row_end - tile_row_begin);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    hipError_t e;
-#define BCD_RW_RATIO(DD)                                                                                             \
-    case DD: {                                                                                                       \
-        const size_t lds = (size_t)RwLayout<DD>::LDS_DWORDS * 4;                                                     \
-        static std::atomic<int> granted[64];                                                                         \
-        if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || granted[dev].load() == 0)) {                                 \
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pairdist_rw<DD, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e;                                                                           \
-            if (dev >= 0 && dev < 64) granted[dev].store(1);                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL((k_pairdist_rw<DD, false, false, true>), grid, block, lds, st, hist, ns, W, H, b, static_cast<__half *>(T), Cn, d_range_flag, 0.f, tile_row_begin, \
-                           (unsigned long long *)nullptr, stats);                                                    \
-    } break;
+#define BCD_RW_ARGS grid, st, dev, hist, ns, W, H, b, T, Cn, d_range_flag, 0.f, tile_row_begin, (unsigned long long *)nullptr, stats, 0.f
+#define BCD_RW_RATIO(DD) case DD: return rw_launch<DD, false, false, true, false, false>(BCD_RW_ARGS);
     switch (D) {
     BCD_RW_RATIO(60)
     BCD_RW_RATIO(36)
     BCD_RW_RATIO(24)
-    default: return hipErrorInvalidValue;
+    default: break;
     }
 #undef BCD_RW_RATIO
-    return hipGetLastError();
+#undef BCD_RW_ARGS
+    return hipErrorInvalidValue;
 }
 
 // the whole frame: clears `stats`, runs the kernel and its verdict
@@ -577,22 +600,22 @@ hipError_t bcd_launch_pairdist_rw_ratio(const float *hist, const float *ns, int 
 }
 
 hipError_t bcd_launch_pairdist_rw_rows(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
-                                       float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st)
+                                       float uni_n, int tile_row_begin, int tile_row_end, hipStream_t st, float margin_tau)
 {
-    return pairdist_rw_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, uni_n, tile_row_begin, tile_row_end, st, nullptr);
+    return pairdist_rw_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, uni_n, tile_row_begin, tile_row_end, st, nullptr, margin_tau);
 }
 
 // measurement: the whole frame with the counting instantiation; work_count[0] += evaluated (pair, bin) terms, [1] += bins issued by a wavefront, [2] += groups of four entered
 hipError_t bcd_launch_pairdist_rw_counting(const float *hist, const float *ns, int W, int H, int D, int b, void *T, uint8_t *Cn, int *d_range_flag, float uni_n,
                                            unsigned long long *work_count, hipStream_t st)
 {
-    return pairdist_rw_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, uni_n, 0, -1, st, work_count);
+    return pairdist_rw_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, uni_n, 0, -1, st, work_count, 0.f);
 }
 
 hipError_t bcd_launch_pairdist_rw(const float *hist, const float *ns, int W, int H, int D, int b, void *T /* binary16 planes */, uint8_t *Cn, int *d_range_flag,
-                                  float uni_n, hipStream_t st)
+                                  float uni_n, hipStream_t st, float margin_tau)
 {
-    return bcd_launch_pairdist_rw_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, uni_n, 0, -1, st);
+    return bcd_launch_pairdist_rw_rows(hist, ns, W, H, D, b, T, Cn, d_range_flag, uni_n, 0, -1, st, margin_tau);
 }
 
 hipError_t bcd_launch_verify_pairs(const float *hist, const float *ns, int W, int H, int D, int b, float tau, const void *list, const int *d_count,

@@ -259,7 +259,7 @@ class StageFrame(C.Structure):
 # every symbol include/bcd_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
-    "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_fused_prepare_solve", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
+    "bcd_hip_set_profiling", "bcd_hip_set_concurrent_scales", "bcd_hip_set_fast_similarity", "bcd_hip_set_margin_planes", "bcd_hip_set_strict_eigensolver", "bcd_hip_set_fused_prepare_solve", "bcd_hip_set_cu_share", "bcd_hip_get_stats", "bcd_hip_kernel_time", "bcd_hip_reset_kernel_time",
     "bcd_hip_denoise", "bcd_hip_denoise_layers", "bcd_hip_denoise_layers_host", "bcd_hip_denoise_layers_host_ex",
     "bcd_hip_spike_map", "bcd_hip_spike_apply", "bcd_hip_spike_filter_layers",
     "bcd_hip_similarity_masks_moments", "bcd_hip_window_distances_moments", "bcd_hip_denoise_moments", "bcd_hip_denoise_moments_host",
@@ -1146,6 +1146,10 @@ class Context:
 
     def set_fast_similarity(self, on):
         self._chk(lib().bcd_hip_set_fast_similarity(self.h, 1 if on else 0))
+
+    def set_margin_planes(self, on):
+        """the approximate planes as one margin plane (default) or as the T and C planes (bcd_hip_set_margin_planes)"""
+        self._chk(lib().bcd_hip_set_margin_planes(self.h, 1 if on else 0))
 
     def set_cu_share(self, percent):
         self._chk(lib().bcd_hip_set_cu_share(self.h, int(percent)))

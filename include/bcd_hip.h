@@ -93,6 +93,9 @@ int  bcd_hip_set_concurrent_scales(bcd_hip_ctx *ctx, int enabled);
  * Default on for w = 1, D in {24, 36, 60} and tau in [2^-6, 64] -- other settings take the exact kernels; also disabled by
  * BCD_HIP_EXACT_SIMILARITY=1.  The masks are bit-identical either way; 0 forces the exact kernels. */
 int  bcd_hip_set_fast_similarity(bcd_hip_ctx *ctx, int enabled);
+/* the approximate planes as ONE signed binary16 margin plane E = T - tau C per pixel pair (2 bytes per entry, no count plane; default) or, 0 or
+ * BCD_HIP_TC_PLANES=1, as the T and C planes (3 bytes per entry) for A/B measurement.  The masks are bit-identical either way. */
+int  bcd_hip_set_margin_planes(bcd_hip_ctx *ctx, int enabled);
 /* process-wide: 1 = the eigensolver of the Bayesian steps (Eigen::SelfAdjointEigenSolver of DenoisingUnit.cpp:589,617) runs to off^2 <= 1e-12 diag^2
  * instead of the production rule (2e-9 + first-order correction of the positive part): ~1.5 % of a step for a 3x smaller deviation on
  * ill-conditioned low-sample frames (4K at 8 spp: 2.9e-6 instead of 9.8e-6 from the CPU path).  Default: the environment's BCD_HIP_STRICT_EIGEN (0). */
