@@ -221,6 +221,16 @@ def _splat_api():
     return L
 
 
+def _rows_api():
+    """the row-band estimate and the two halves of a marking step (the multi-GPU band driver's stage calls)"""
+    L = lib()
+    L.bcd_hip_bayes_accumulate_rows.argtypes = [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, _VP, C.c_int, C.c_int,
+                                                _VP, _VP, C.POINTER(C.c_int)]
+    L.bcd_hip_active_step_enqueue.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _VP, _VP, C.c_int]
+    L.bcd_hip_active_step_collect.argtypes = [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    return L
+
+
 def filter_table(kind, radius, param=2.0, table_size=16):
     """the (table_size, table_size) float32 table of a standard separable filter (bcd_hip_filter_table: host only, no GPU needed).
     kind: "box", "tent", "gaussian" (param = alpha) or "blackman_harris"; radius: a number or (radius_x, radius_y), each in (0, 3]"""
@@ -797,6 +807,24 @@ class Context:
                                             row_offset, 1 if first_pass else 0, _dp(state), C.byref(u)))
         return u.value
 
+    def active_step_enqueue(self, mask, cnt, state, w, b, row_begin, row_end, random_order, seed, row_offset, total=None, with_verdict=False):
+        """bcd_hip_active_step_enqueue: one batch of marking launches on the context's stream, without waiting.  total: an int64 device tensor of one
+        element that receives the count of undecided pixels after the batch (+ 2^40 with with_verdict when the masks of the last deferred similarity
+        pass are not valid).  After a synchronisation active_step_collect() returns the count"""
+        H, W = cnt.shape
+        _rows_api()
+        self._chk(lib().bcd_hip_active_step_enqueue(self.h, _dp(mask), _dp(cnt), W, H, int(w), int(b), int(row_begin), int(row_end), int(random_order),
+                                                    C.c_uint32(seed), int(row_offset), _dp(state), _dp(total) if total is not None else None,
+                                                    1 if with_verdict else 0))
+
+    def active_step_collect(self):
+        """bcd_hip_active_step_collect -> (pixels of the owned lines still undecided, launches the batch needed); the context's stream must have been
+        synchronised since active_step_enqueue"""
+        u, n = C.c_int32(0), C.c_int32(0)
+        _rows_api()
+        self._chk(lib().bcd_hip_active_step_collect(self.h, C.byref(u), C.byref(n)))
+        return u.value, n.value
+
     def selftest_active_lists(self, state, cnt, w, row_begin, row_end, skip_word=None, fill=-1):
         """bcd_hip_selftest_active_lists: the list compaction of the estimate call on its own, on the processed pixels (state 1) of lines
         [row_begin, row_end) -> (strong list, weak list: int32 tensors pre-filled with `fill` -- W * H entries each, as the engine sizes its own; the
@@ -829,6 +857,31 @@ class Context:
         self._chk(lib().bcd_hip_bayes_accumulate(self.h, _dp(col), _dp(pixcov), _dp(mask), _dp(nsim), _dp(state), W, H, w, b,
                                                  C.c_float(min_eig), _dp(s), _dp(c)))
         return s, c
+
+    def bayes_accumulate_rows(self, col, pixcov, mask, nsim, state, w, b, min_eig, row_begin, row_end, out=None, skip_word=None):
+        """bcd_hip_bayes_accumulate_rows: bayes_accumulate for the processed pixels of lines [row_begin, row_end) only -> (sum, count, skipped).
+        out: the (sum, count) accumulators to add into; default: fresh zeroed ones.  skip_word: (an int64 device tensor of one element, an int64
+        NumPy array of one element that holds the host copy of that word) makes the call speculative: when the word is not zero the kernels do
+        nothing and skipped is 1"""
+        torch = self.torch
+        H, W, _ = col.shape
+        if out is None:
+            s = torch.zeros((H, W, 3), dtype=torch.float32, device=col.device)
+            c = torch.zeros((H, W), dtype=torch.int32, device=col.device)
+        else:
+            s, c = out
+        d_word = h_word = None
+        skipped = C.c_int(0)
+        if skip_word is not None:
+            d, h = skip_word
+            if d.dtype != torch.int64 or d.numel() != 1 or str(h.dtype) != "int64" or h.size != 1:
+                raise ValueError("skip_word must be (a one-element int64 device tensor, a one-element int64 NumPy array)")
+            d_word, h_word = _dp(d), C.c_void_p(h.ctypes.data)
+        _rows_api()
+        self._chk(lib().bcd_hip_bayes_accumulate_rows(self.h, _dp(col), _dp(pixcov), _dp(mask), _dp(nsim), _dp(state), W, H, int(w), int(b), float(min_eig),
+                                                      _dp(s), _dp(c), int(row_begin), int(row_end), d_word, h_word,
+                                                      C.byref(skipped) if skip_word is not None else None))
+        return s, c, skipped.value
 
     def bayes_accumulate_temporal(self, frames, nsim_total, state, w, b, min_eig, out=None):
         """bcd_hip_bayes_accumulate_temporal: `frames` is a list of (colours, per-pixel covariances, masks) device tensors, [0] the frame itself and the
