@@ -50,7 +50,7 @@ __host__ __device__ inline float bcd_unit_hash(uint32_t idx, uint32_t seed)
 #define BCD_CNT_LINES 64
 #define BCD_CNT_STRIDE 32 /* ints */
 
-// work queues of the persistent estimate kernels (k_bayes27.hip): BCD_WORK_QUEUES counters per kernel, one per 128-byte line
+// work queues of the persistent estimate kernels (bayes27_record.h): BCD_WORK_QUEUES counters per kernel, one per 128-byte line
 #define BCD_WORK_QUEUES 8
 #define BCD_WORK_STRIDE 32 /* ints */
 #define BCD_WORK_INTS (4 * BCD_WORK_QUEUES * BCD_WORK_STRIDE) /* prepare | solve | finish | finish of the redo list */

@@ -1,6 +1,9 @@
 // bcd_launch.h -- the launchers implemented in the k_*.hip files and in bcd_sparse_upload.hip, as the host orchestration files (bcd_api.hip,
-// bcd_host.hip, bcd_accum.hip, bcd_selftest.hip) call them.  The parameter names are those of the definitions; the kernel files do not include
-// this header (k_similarity_fast.hip is hashed by bench.py), so a launcher whose signature changes is changed here by hand.
+// bcd_host.hip, bcd_accum.hip, bcd_selftest.hip) call them.  The parameter names are those of the definitions, and default arguments live here only.
+// The files of the estimate chain -- k_bayes27.hip, k_jacobi27.hip, k_bayes_temporal.hip and k_bayes.hip -- include this header, so the compiler
+// checks their launchers' definitions against these declarations.  The other kernel files do not: k_similarity_fast.hip must stay byte for byte what
+// it is, because bench.py keys its recorded profiles on that file's hash, and the rest have not been converted; a launcher of theirs whose signature
+// changes is changed here by hand.
 #pragma once
 #include "bcd_common.h"
 
@@ -125,18 +128,32 @@ hipError_t bcd_launch_bayes_weak_tiles(const float *colors, const uint32_t *mask
 hipError_t bcd_launch_bayes_weak_tiles_layers(const BcdLayerTable &t, int layers, const uint32_t *mask, const uint8_t *state, const int32_t *nsim, int min_strong,
                                               int W, int H, int b, hipStream_t st, int row_begin, int row_end);
 
-// ---- k_bayes27.hip
-size_t bcd_bayes27_record_bytes();
+// ---- k_jacobi27.hip
 void bcd_bayes27_set_strict_eigensolver(int on);
 float bcd_bayes27_conv2(int strict);
+float bcd_bayes27_chain_conv2(); // the rule the estimate chain runs with: the setter's, else the environment's
+hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blocks, float *eig, float *V, hipStream_t st, float conv2 = 1e-12f, float *Aout = nullptr,
+                                     const int *d_n = nullptr, int first_item = 0);
+
+// ---- k_bayes27.hip
+// the estimate chain's environment switches, read once per process; every one selects a comparison form that the README documents.  strict_eigen and
+// prepare_solve_split also have setters, which override the environment (bcd_bayes27_set_strict_eigensolver, bcd_bayes27_set_fused_prepare_solve)
+struct BcdBayes27Switches {
+    bool finish_lds;          // BCD_HIP_FINISH_LDS=1           the finish through LDS matrices instead of the register-resident kernel
+    bool jacobi_pairs;        // BCD_HIP_JACOBI_PAIRS=1         the eigensolver that moves its rows through LDS every round
+    bool prepare_gather;      // BCD_HIP_PREPARE_GATHER=1       b = 12: members gathered from memory instead of an LDS window
+    bool prepare_solve_split; // BCD_HIP_PREPARE_SOLVE_SPLIT=1  b = 6: prepare and solve as two launches
+    bool strict_eigen;        // BCD_HIP_STRICT_EIGEN=1         the eigensolver's fully converged stopping rule
+};
+const BcdBayes27Switches &bcd_bayes27_switches();
+size_t bcd_bayes27_lds_bytes(int b);
+size_t bcd_bayes27_record_bytes();
 void bcd_bayes27_set_fused_prepare_solve(int on);
 int bcd_bayes27_fused_prepare_solve();
 // the prepare and eigensolver phases of a chunk on their own (default search radius; records laid out as by bcd_launch_bayes27), fused or as two launches
 hipError_t bcd_launch_prepare_solve27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
                                       int *d_work, int num_cus, int W, int H, float *records, hipStream_t st, const int *d_nb_items, int fused);
 hipError_t bcd_launch_count_differing_words(const void *a, const void *b, size_t words, unsigned long long *d_count, hipStream_t st);
-hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blocks, float *eig, float *V, hipStream_t st, float conv2 = 1e-12f, float *Aout = nullptr,
-                                     const int *d_n = nullptr, int first_item = 0);
 // d_spectral: += items whose inverse took the spectral branch; defer_redo != 0: the caller reads *d_spectral after its next synchronisation and calls
 // bcd_launch_bayes27_redo if it is > 0; d_nb_items (optional): the list's length on the device, nb_items then being the capacity of `records`
 hipError_t bcd_launch_bayes27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items, int *d_work,

@@ -1,6 +1,7 @@
 // bcd_selftest.hip -- self-tests and measurement entry points of the C ABI (bcd_hip_selftest_*, bcd_hip_eig27_batch*): they run single kernels of the
 // chain on the context's main workspace, outside the scale drivers of bcd_api.hip.
 #include "bcd_ctx.h"
+#include "bayes27_record.h"
 
 #include <algorithm>
 #include <cstring>
@@ -205,7 +206,7 @@ int bcd_hip_selftest_prepare_solve(bcd_hip_ctx *ctx, const float *d_colors, cons
     RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
     const size_t bytes = bcd_bayes27_record_bytes() * (size_t)capacity;
     // what is compared: everything in front of the redo list, and the list's counter
-    const size_t words = (bytes - 2 * sizeof(int) * (size_t)capacity) / 4 + 1;
+    const size_t words = RECORD27_FLOATS * (size_t)capacity + 1;
     DevAlloc rec[2], len;
     for (int i = 0; i < 2; ++i)
         if (hipMalloc(&rec[i].p, bytes) != hipSuccess) { set_err(ctx, "hipMalloc"); return BCD_HIP_ENOMEM; }

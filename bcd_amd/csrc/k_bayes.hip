@@ -8,7 +8,7 @@
 // the eigenbasis, so any accurate symmetric eigensolver reproduces the reference within fp32 round-off.
 // Sums that the reference accumulates sequentially (means, covariances, noise mean) are accumulated in
 // the same order here.  Compiled with -ffp-contract=off; fmaf() is used explicitly where contraction is wanted.
-#include "bcd_common.h"
+#include "bcd_launch.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -731,8 +731,6 @@ BayesGeom make_geom(int W, int H, int w, int b)
 }
 
 } // namespace
-
-size_t bcd_bayes27_lds_bytes(int b);
 
 // LDS of the generic kernel; with_clouds = false: patch clouds in global scratch
 static size_t generic_lds_bytes(int w, int b, bool with_clouds)

@@ -1,14 +1,18 @@
-// k_bayes27.hip -- full Bayesian estimate of a processed pixel for the default patch radius w = 1 (K = 27): three kernels with a
-// per-pixel record in HBM between them (persistent single-wavefront workgroups, items from work queues):
+// k_bayes27.hip -- full Bayesian estimate of a processed pixel for the default patch radius w = 1 (K = 27): a chain of kernels with a
+// per-pixel record in HBM between them (persistent single-wavefront workgroups, items from work queues).  The map of the chain:
+//   bayes27_record.h   the contract: constants, the record and how `records` is carved, Geom27, the work queues and their groups, the switches
 //   k_bayes27w<1> / k_bayes27<1>  PREPARE  members of S(p), noise mean, colour mean, covariance C on the f32 matrix core;
 //                                          record: A = C - N (28 x 28, zero padded), C, N, m
-//   k_jacobi27_quads              SOLVE    eigen-decomposition of every A (clampNegativeEigenValues), two matrices per wavefront, the
-//                                          rows through LDS once per three rounds (k_jacobi27_batch: once per round, kept for comparison)
+//   k_jacobi27.hip                SOLVE    k_jacobi27_quads: eigen-decomposition of every A (clampNegativeEigenValues), two matrices per
+//                                          wavefront (k_jacobi27_batch: kept for comparison); its task as device functions: bayes27_jacobi.h
 //   k_finish27w                   FINISH   clamp, inverses, Step 2, final estimates, aggregation -- the 27 x 27 algebra in registers on the
-//                                          matrix core (default search radius); items whose inverse needs the spectral branch go to a redo list
+//                                          matrix core (b = 6 and b = 12); items whose inverse needs the spectral branch go to a redo list
 //   k_bayes27w<2> / k_bayes27<2>  FINISH   the same through LDS matrices: the redo list / the other search radii
 //   k_prepare_solve27             PREPARE + SOLVE in one kernel, a pair of items per task: what the default search radius launches in place of the
 //                                          first two (bcd_hip_set_fused_prepare_solve; the records are the same bits)
+// The host half, at the end of this file, decides a chunk's chain (chain27) and launches it through the stage launchers launch_prepare,
+// launch_solve, launch_prepare_solve, launch_finish and launch_redo; the public launchers bcd_launch_bayes27, bcd_launch_bayes27_redo,
+// bcd_launch_solve_finish27 and bcd_launch_prepare_solve27 are compositions of them.
 // The `w` kernels serve the default search radius b = 6: the 15 x 15 pixel window around p is staged in LDS once and every member
 // access is an LDS read; other radii take the gather kernels (members fetched from global memory).
 //
@@ -26,53 +30,17 @@
 //     accepted only if every pivot is positive and ||M^-1||_F * minEig <= 1 (which proves
 //     lambda_min(M) >= minEig); otherwise the spectral form is evaluated with a compact Jacobi solver;
 //   * sums into LDS windows are plain read-add-write, never ds_add_f32 (193 cycles per wavefront instruction on gfx950).
-#include "bcd_common.h"
+#include "bcd_launch.h"
+#include "bayes27_jacobi.h"
 #include <atomic>
-#include <cstdio>
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
-
-constexpr int K = 27, KP = 28, LD = 29, P = 9, MSZ = KP * KP, CHUNK = MSZ / K; // matrix buffer: 784 floats; 29 members per staging chunk
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-struct Geom27 {
-    int W, H, b, side, words, maxS;
-};
-
 // The out-of-line phases below receive their LDS buffers as plain pointers; without this hint the compiler addresses them with
 // FLAT instructions (aperture check, both memory counters, a fraction of the ds_read / ds_write rate).
 #define LDS_POINTER(p) __builtin_assume(__builtin_amdgcn_is_shared((const __attribute__((address_space(0))) void *)(p)))
-
-// divided difference of f = max(0, .) at two eigenvalue estimates (see pos_part_lds)
-__device__ inline float pos_phi(float di, float dj)
-{
-    const float hi = fmaxf(di, dj), lo = fminf(di, dj);
-    if (lo > 0.f) return 1.f;
-    if (hi <= 0.f) return 0.f;
-    return hi * __builtin_amdgcn_rcpf(hi - lo); // (hi > 0 >= lo: the denominator is >= hi)
-}
-
-// what the eigensolvers leave in the record next to the eigenvalue estimates and V: row r of E o Phi -- the residual off-diagonal part of
-// V^T A V times the divided differences of max(0, .) at the estimates, zero on the diagonal -- which the finish kernels turn into the
-// first-order correction V (E o Phi) V^T of the positive part (pos_part_lds).  row: the lane's row in LDS, diag: all 28 estimates in LDS.
-__device__ inline void jacobi_write_correction(float *out_row, const float *row, const float *diag, int r)
-{
-    const float d_r = diag[r];
-#pragma unroll
-    for (int q4 = 0; q4 < 7; ++q4) {
-        const float4 e4 = reinterpret_cast<const float4 *>(row)[q4], d4 = reinterpret_cast<const float4 *>(diag)[q4];
-        float4 o;
-        o.x = 4 * q4 == r ? 0.f : e4.x * pos_phi(d_r, d4.x);
-        o.y = 4 * q4 + 1 == r ? 0.f : e4.y * pos_phi(d_r, d4.y);
-        o.z = 4 * q4 + 2 == r ? 0.f : e4.z * pos_phi(d_r, d4.z);
-        o.w = 4 * q4 + 3 == r ? 0.f : e4.w * pos_phi(d_r, d4.w);
-        reinterpret_cast<float4 *>(out_row)[q4] = o;
-    }
-}
 
 __device__ inline float wsum(float v)
 {
@@ -84,611 +52,6 @@ __device__ inline float wmax(float v)
 {
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
     return v;
-}
-
-// Work distribution of the persistent kernels.  One counter serves 50-90 same-address atomics per microsecond: with a single counter per
-// kernel the 36 000 grabs of a 1080p scale were 0.4 ms (finish kernel with its body skipped) to 0.7 ms (prepare kernel) on their own.
-// Items are dealt round-robin to BCD_WORK_QUEUES counters in cache lines of their own (item = queue + 8 k); a wavefront starts on
-// the queue of its XCD (workgroups go round-robin over the 8 XCDs) and moves on to the next queue when one is empty, so nothing is
-// left behind and the tail stays balanced.
-struct WorkCursor { int q, tried; };
-__device__ inline WorkCursor work_begin() { return WorkCursor{ (int)(blockIdx.x % BCD_WORK_QUEUES), 0 }; }
-__device__ inline int work_next(int *work, int nb_items, int lane, WorkCursor &c)
-{
-    while (c.tried < BCD_WORK_QUEUES) {
-        int k = 0;
-        if (lane == 0) k = atomicAdd(work + c.q * BCD_WORK_STRIDE, 1);
-        k = __builtin_amdgcn_readfirstlane(k);
-        const int item = c.q + BCD_WORK_QUEUES * k;
-        if (item < nb_items) return item;
-        c.q = (c.q + 1) % BCD_WORK_QUEUES;
-        ++c.tried;
-    }
-    return -1;
-}
-
-// Round 6: the host launches the estimate kernels of a chunk BEFORE it knows how many items the list holds (the count is still on its way back:
-// bayes() in bcd_api.hip); `d_n` then points at the list's length on the device and `nb_items` is the capacity the records were sized for.
-__device__ inline int items_on_device(const int *d_n, int first_item, int nb_items)
-{
-    return d_n ? max(0, min(nb_items, *d_n - first_item)) : nb_items;
-}
-
-__device__ inline int noise_idx(int i, int j)
-{
-    // 3x3 symmetric block from xx,yy,zz,yz,xz,xy
-    return i == j ? i : (i + j == 1 ? 5 : (i + j == 2 ? 4 : 3));
-}
-
-// ---- parallel two-sided Jacobi, Brent-Luk ordering, rows held in registers ------------------------------
-// Slots 0..27 (27 = zero padding) are paired (2i, 2i+1).  One round: lanes i < 14 compute the rotation of pair i from
-// LDS; lanes 0..27 load ONE row of A each (7 x ds_read_b128), lanes 32..58 keep their row of V in registers; every lane applies
-// the 14 column-pair rotations on registers with static indices, lane pairs (2i, 2i+1) exchange their rows with a DPP
-// quad_perm (row rotation of A), and the rows of A are written back in place at their Brent-Luk permuted
-// position: slot s moves to sigma(s), 0->0, 1->2, 2i->2i+2, 26->27, 2i+1->2i-1.  After 27 rounds every pair of slots
-// has met once (one sweep).  Eigenvalues = diagonal of A (in slot order), eigenvectors = columns of V (same order):
-// V f(diag) V^T needs no bookkeeping of the permutation.  Matrices here use a leading dimension of 28 floats.
-constexpr int JLD = 28;
-static_assert(MSZ >= KP * JLD && MSZ >= (K - 1) * LD + K, "a matrix buffer holds 28 x 28 (Jacobi layout) or 27 rows of stride 29");
-
-__device__ inline float dpp_xor1(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, true));
-}
-
-// x[k] += ms * (x[k] of lane ^ 1) for the 28 elements of a row, in place: 28 v_fmac_f32_dpp.  One asm block: the leading s_nop covers
-// the two wait states the hardware wants between a VALU write of a VGPR and a DPP read of it (the compiler does not look inside an
-// asm statement for that hazard); inside the block every instruction touches its own register only.
-__device__ inline void rowrot_dpp(float (&x)[28], float ms)
-{
-#define BCD_F(i) "v_fmac_f32_dpp %" #i ", %" #i ", %28 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-    asm volatile("s_nop 1\n\t"
-                 BCD_F(0) BCD_F(1) BCD_F(2) BCD_F(3) BCD_F(4) BCD_F(5) BCD_F(6) BCD_F(7) BCD_F(8) BCD_F(9) BCD_F(10) BCD_F(11) BCD_F(12) BCD_F(13)
-                 BCD_F(14) BCD_F(15) BCD_F(16) BCD_F(17) BCD_F(18) BCD_F(19) BCD_F(20) BCD_F(21) BCD_F(22) BCD_F(23) BCD_F(24) BCD_F(25) BCD_F(26) BCD_F(27)
-                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]), "+v"(x[9]),
-                   "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]), "+v"(x[16]), "+v"(x[17]), "+v"(x[18]), "+v"(x[19]),
-                   "+v"(x[20]), "+v"(x[21]), "+v"(x[22]), "+v"(x[23]), "+v"(x[24]), "+v"(x[25]), "+v"(x[26]), "+v"(x[27])
-                 : "v"(ms));
-#undef BCD_F
-}
-
-__device__ inline int sigma_slot(int s)
-{
-    return s == 0 ? 0 : (s == 1 ? 2 : (s == 26 ? 27 : ((s & 1) ? s - 2 : s + 2)));
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Batched eigensolver: the same Brent-Luk two-sided Jacobi, two matrices per wavefront and nothing else in the kernel.
-// Matrix h of a pair lives in lanes 32 h .. 32 h + 27 (rows of A, moved through LDS every round) and, in a second register
-// set of the same lanes, the rows of V (never move).  The LDS traffic and the row / column rotations of A are shared by the
-// two matrices -- per matrix and round ~100 VALU and ~10 LDS instructions instead of ~140 and ~21 -- and with 6.5 KB of LDS
-// per wavefront the residency is bound by registers only (3 wavefronts per SIMD = 24 matrices per CU instead of 12).
-//   in:  A  [n][28 x 28] (JLD layout, row / column 27 zero)      out: eig [n][28] (slot order), V [n][28 x 28] (rows 0..26)
-// ---------------------------------------------------------------------------------------------------------------------
-// one wavefront per workgroup: no s_barrier is emitted for it, only the ordering of the LDS accesses
-__device__ inline void wave_sync() { __syncthreads(); }
-
-__device__ inline float half_sum(float v)
-{
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// LDS placement of row r of a matrix of the batched solver (bank facts: MI355X_MICROARCH.md, LDS).  ds_read_b128 serves the lane groups
-// {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of a half, banks (a / 4) mod 64; ds_write_b128 serves groups of 8 consecutive lanes, banks
-// (a / 4) mod 32.  With the rows at a stride of 28 dwords the LOADS of a round (lane r <- row r) are conflict free, but (a) the idle lanes
-// 28..31 used to re-read row 0, which shares its banks with row 16 of their group, and (b) the STORES go to the Brent-Luk permuted slots:
-// lanes 0..7 write the rows {0, 2, 4, 1, 6, 3, 8, 5}, and rows 0 and 8 start on the same bank mod 32 -- together SQ_LDS_BANK_CONFLICT =
-// 17 % of the LDS pipe's cycles (r3 counters).  Row 8 therefore lives behind the matrix at a start bank of its own (found by exhaustive
-// search over the load and store groups: every group conflict free), and the idle lanes re-read row 16.
-constexpr int JROW8 = 28 * 28 + 20;        // start of row 8: (JROW8 / 4) mod 16 = 9
-constexpr int JMAT = JROW8 + 28;           // floats per matrix in LDS (832)
-template <bool PAD> __device__ inline int jrow_t(int r) { return (PAD && r == 8) ? JROW8 : r * 28; }
-
-template <bool PAD, bool FUSE>
-__global__ __launch_bounds__(64, 3) void k_jacobi27_batch(const float *Ain, int n, int *work,
-                                                          float *__restrict__ eig, float *__restrict__ Vout,
-                                                          float conv2 /* stop at off^2 <= conv2 diag^2 */, float *Aout /* optional (may be Ain): the matrix as the sweeps left it, V^T A V */,
-                                                          const int *d_n, int first_item)
-{
-    n = items_on_device(d_n, first_item, n);
-    auto jrow = [](int r) { return jrow_t<PAD>(r); };
-    __shared__ float4 lds4[(2 * JMAT + 4 * KP) / 4];
-    float *Abuf = reinterpret_cast<float *>(lds4);
-    float *cs = Abuf + 2 * JMAT;      // [matrix][28]: per slot pair (-beta, alpha) of the current round
-    float *dv = cs + 2 * KP;          // [matrix][28]: scale of every slot (see below)
-    const int lane = threadIdx.x, h = lane >> 5, r = lane & 31;
-    float *Ah = Abuf + h * JMAT;
-    float *cs_h = cs + h * KP, *dv_h = dv + h * KP;
-    const bool isRow = r < KP;
-    const float *src = Ah + jrow(isRow ? r : (PAD ? 16 : 0)); // (idle lanes: the address of a lane of their own ds_read_b128 group)
-    float *dst = Ah + jrow(isRow ? sigma_slot(r) : 0);
-    WorkCursor cursor = work_begin();
-    for (;;) {
-        const int pair = work_next(work, (n + 1) / 2, lane, cursor);
-        if (pair < 0) break;
-        const int first = 2 * pair;
-        const int item = first + h;
-        const bool live = item < n;
-        // matrix -> LDS (an absent second matrix is the identity: converged from the start)
-        {
-            const float4 *g = reinterpret_cast<const float4 *>(Ain + (size_t)(live ? item : first) * (KP * JLD));
-            for (int e = r; e < KP * JLD / 4; e += 32) {
-                float4 v = g[e];
-                const int e0 = 4 * e, rr = e0 / JLD, c0 = e0 - rr * JLD;
-                if (!live) v = make_float4(rr == c0, rr == c0 + 1, rr == c0 + 2, rr == c0 + 3);
-                *reinterpret_cast<float4 *>(Ah + jrow(rr) + c0) = v;
-            }
-            if (isRow) dv_h[r] = 1.f;
-        }
-        wave_sync();
-        // Scaled ("fast") rotations: the matrices are kept as A = D A~ D and V = V~ D with a diagonal D (one scale per slot).
-        // J = [[c, s], [-s, c]] = [[1, t], [-t, 1]] diag(c, c), so rotating the slot pair (p, q) is
-        //     x' = x - beta y,  y' = y + alpha x   (beta = t d_q / d_p, alpha = t d_p / d_q)   and   d' = c d
-        // -- two fused multiply-adds per element pair instead of four operations; D is folded back into A~ and V~ at the start of
-        // every sweep (within a sweep a scale cannot fall below 2^(-27/2)).
-        float vrow[JLD];
-#pragma unroll
-        for (int k = 0; k < JLD; ++k) vrow[k] = (k == r) ? 1.f : 0.f; // V = identity
-        for (int sweep = 0; sweep < 12; ++sweep) {
-            // fold the scales: A~ <- D A~ D, V~ <- V~ D, D <- I; off / diagonal norms of the true matrix on the way
-            float off = 0.f, dg = 0.f;
-            {
-                float dk[JLD];
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4) {
-                    float4 w4 = reinterpret_cast<const float4 *>(dv_h)[q4];
-                    dk[4 * q4] = w4.x; dk[4 * q4 + 1] = w4.y; dk[4 * q4 + 2] = w4.z; dk[4 * q4 + 3] = w4.w;
-                }
-                const float dr = dv_h[isRow ? r : 0];
-                float row[JLD];
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4) {
-                    float4 v = reinterpret_cast<const float4 *>(src)[q4];
-                    row[4 * q4] = v.x; row[4 * q4 + 1] = v.y; row[4 * q4 + 2] = v.z; row[4 * q4 + 3] = v.w;
-                }
-#pragma unroll
-                for (int k = 0; k < JLD; ++k) {
-                    row[k] *= dr * dk[k];
-                    vrow[k] *= dk[k];
-                    if (isRow) { if (k == r) dg = fmaf(row[k], row[k], dg); else off = fmaf(row[k], row[k], off); }
-                }
-                wave_sync(); // every lane has read the scales and its row
-                if (isRow) {
-#pragma unroll
-                    for (int q4 = 0; q4 < JLD / 4; ++q4)
-                        reinterpret_cast<float4 *>(Ah + jrow(r))[q4] = make_float4(row[4 * q4], row[4 * q4 + 1], row[4 * q4 + 2], row[4 * q4 + 3]);
-                    dv_h[r] = 1.f;
-                }
-                wave_sync();
-            }
-            off = half_sum(off);
-            dg = half_sum(dg);
-            // off^2 <= 1e-12 diag^2: the positive part V max(0, lambda) V^T is Lipschitz in the matrix, so what is left off the diagonal moves it
-            // by <= 1e-6 |A|.  (1e-10 saved 3 % of the solver and was fine on the 32-spp frames, but the 8-spp 4K frame of configs[3] then
-            // differed from the oracle by 1.9e-5 -- its inverses are worse conditioned -- against 2.9e-6 with this threshold.)  A converged
-            // matrix is frozen -- identity rotations -- while its partner finishes: its result does not depend on who shares the wavefront
-            const bool settled = off <= conv2 * dg;
-            if (__builtin_amdgcn_ballot_w64(!settled) == 0) break; // both matrices converged
-            // fully unrolled: the Brent-Luk column move of the rows of V~ (a 27-cycle of the register names) costs no instruction
-#pragma unroll
-            for (int round = 0; round < KP - 1; ++round) {
-                // lanes 0..13 of each half: rotation of the slot pair (2 r, 2 r + 1); the other lanes compute on a harmless copy of pair 0
-                float mbeta = 0.f, alpha = 0.f;
-                {
-                    const int p = r < KP / 2 ? 2 * r : 0, q = p + 1;
-                    const float2 d2 = reinterpret_cast<const float2 *>(dv_h)[p >> 1];
-                    const float apq_s = Ah[jrow(p) + q], app_s = Ah[jrow(p) + p], aqq_s = Ah[jrow(q) + q];
-                    float dp = d2.x, dq = d2.y;
-                    if (apq_s != 0.f && !settled) {
-                        const float apq = dp * dq * apq_s, app = dp * dp * app_s, aqq = dq * dq * aqq_s;
-                        // 1-ulp hardware reciprocal / sqrt / rsqrt: a rotation only has to be orthogonal to working
-                        // precision (c^2 + s^2 = 1 +- 1e-7), not the exact minimiser
-                        const float theta = (aqq - app) * __builtin_amdgcn_rcpf(2.f * apq);
-                        if (fabsf(theta) < 1e18f) { // (otherwise theta^2 overflows: the rotation is the identity to fp32)
-                            float t = __builtin_amdgcn_rcpf(fabsf(theta) + __builtin_amdgcn_sqrtf(fmaf(theta, theta, 1.f)));
-                            t = theta < 0.f ? -t : t;
-                            const float c = __builtin_amdgcn_rsqf(fmaf(t, t, 1.f));
-                            const float ratio = dq * __builtin_amdgcn_rcpf(dp);
-                            mbeta = -t * ratio;
-                            alpha = t * __builtin_amdgcn_rcpf(ratio);
-                            dp *= c;
-                            dq *= c;
-                        }
-                    }
-                    float row[JLD];
-#pragma unroll
-                    for (int q4 = 0; q4 < JLD / 4; ++q4) {
-                        float4 v = reinterpret_cast<const float4 *>(src)[q4];
-                        row[4 * q4] = v.x; row[4 * q4 + 1] = v.y; row[4 * q4 + 2] = v.z; row[4 * q4 + 3] = v.w;
-                    }
-                    if (r < KP / 2) {
-                        reinterpret_cast<float2 *>(cs_h)[r] = make_float2(mbeta, alpha);
-                        dv_h[sigma_slot(p)] = dp; // the scales move with their slots
-                        dv_h[sigma_slot(q)] = dq;
-                    }
-                    wave_sync();
-                    float rot[JLD];
-#pragma unroll
-                    for (int q4 = 0; q4 < JLD / 4; ++q4) {
-                        float4 w4 = reinterpret_cast<const float4 *>(cs_h)[q4];
-                        rot[4 * q4] = w4.x; rot[4 * q4 + 1] = w4.y; rot[4 * q4 + 2] = w4.z; rot[4 * q4 + 3] = w4.w;
-                    }
-                    const float2 pcs = reinterpret_cast<const float2 *>(cs_h)[isRow ? (r >> 1) : 0];
-                    // column rotations of A~
-#pragma unroll
-                    for (int j = 0; j < KP / 2; ++j) {
-                        const float x = row[2 * j], y = row[2 * j + 1];
-                        row[2 * j] = fmaf(rot[2 * j], y, x);
-                        row[2 * j + 1] = fmaf(rot[2 * j + 1], x, y);
-                    }
-                    // row rotations of A~: rows (2i, 2i+1) live in lanes (2i, 2i+1) of their half and take the rotation of pair i
-                    {
-                        const float ms = (r & 1) ? pcs.y : pcs.x;
-                        // row[k] += ms * row[k] of the partner lane: ONE v_fmac_f32 with the lane exchange as its DPP modifier (the
-                        // compiler emits v_mov_b32_dpp + v_fma_f32; VOP3 has no DPP form on gfx9)
-                        float out[JLD];
-                        if (FUSE) {
-                            rowrot_dpp(row, ms);
-#pragma unroll
-                            for (int k = 0; k < JLD; ++k) out[sigma_slot(k)] = row[k]; // Brent-Luk column move (register renaming)
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < JLD; ++k) out[sigma_slot(k)] = fmaf(ms, dpp_xor1(row[k]), row[k]);
-                        }
-                        if (isRow) {
-#pragma unroll
-                            for (int q4 = 0; q4 < JLD / 4; ++q4)
-                                reinterpret_cast<float4 *>(dst)[q4] = make_float4(out[4 * q4], out[4 * q4 + 1], out[4 * q4 + 2], out[4 * q4 + 3]);
-                        }
-                    }
-                    // the same column rotations (and column move) on the rows of V~
-                    {
-                        float out[JLD];
-#pragma unroll
-                        for (int j = 0; j < KP / 2; ++j) {
-                            const float x = vrow[2 * j], y = vrow[2 * j + 1];
-                            out[sigma_slot(2 * j)] = fmaf(rot[2 * j], y, x);
-                            out[sigma_slot(2 * j + 1)] = fmaf(rot[2 * j + 1], x, y);
-                        }
-#pragma unroll
-                        for (int k = 0; k < JLD; ++k) vrow[k] = out[k];
-                    }
-                }
-                wave_sync(); // the rows of A~ are back in LDS before the next round reads its pivots
-            }
-        }
-        if (live) {
-            if (isRow) eig[(size_t)item * KP + r] = Ah[jrow(r) + r];
-        }
-        if (Aout) { // (wave-uniform)
-            if (isRow) cs_h[r] = Ah[jrow(r) + r];
-            wave_sync();
-            if (isRow && live) jacobi_write_correction(Aout + (size_t)item * (KP * JLD) + r * JLD, Ah + jrow(r), cs_h, r);
-        }
-        if (live) {
-            if (r < K) {
-                float4 *o = reinterpret_cast<float4 *>(Vout + (size_t)item * (KP * JLD) + r * JLD);
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4) o[q4] = make_float4(vrow[4 * q4], vrow[4 * q4 + 1], vrow[4 * q4 + 2], vrow[4 * q4 + 3]);
-            }
-        }
-        wave_sync(); // the next pair reuses the LDS
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// k_jacobi27_quads: the same two-sided Jacobi (two matrices per wavefront, rows in registers, scaled rotations, V~ accumulated in
-// registers), with the rows moved through LDS once per THREE rounds instead of once per round.
-// k_jacobi27_batch is bound by the LDS pipe, not by arithmetic: per wavefront and round ~97 cycles for the 7 ds_write_b128 of the rows
-// (a 16-byte store costs 13.9 cycles per wavefront instruction, three times a load: tools/ubench/lds_rate.hip) + 64 for the row and
-// rotation-table loads + ~25 for pivots and scales = ~186 cycles of a pipe that 12 wavefronts share, against ~130 CU-cycles of vector
-// work (r3: removing six of the seven row stores made the kernel 22 % faster).
-// Here a sweep is 9 "super-rounds".  In each the 28 slots form 7 quads of neighbouring lanes and ALL SIX pairs of a quad are rotated --
-// three rounds, partners at lane distance 1, 2, 3 (xor), every exchange a DPP quad_perm, every column pair a compile-time register
-// pair -- before the rows go back to LDS at their next positions.  The nine partitions into quads are the parallel classes of a
-// resolvable 2-(28,4,1) design (tools/jacobi_schedule.py: every pair of slots shares a quad exactly once per sweep; two lane
-// permutations, JSX and JSY, applied x x y x x y x x y, bring every slot home after the ninth).  The rotations of the second and third
-// round depend on the first's results, but only on the 4 x 4 diagonal block of the quad: each lane carries its row of that block along
-// (4 values, in xor-relative order: w[y] = A~[me][me ^ y], so that every index is a compile-time constant in every lane) and the three
-// rounds' angles come out of it before the 28-wide rows are touched.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int JSX[28] = { 1, 6, 12, 8, 10, 24, 0, 17, 19, 11, 20, 14, 23, 5, 9, 26, 15, 25, 22, 3, 4, 18, 21, 2, 13, 7, 16, 27 };
-constexpr int JSY[28] = { 7, 17, 1, 9, 18, 8, 25, 23, 11, 13, 22, 5, 6, 3, 24, 20, 10, 2, 26, 14, 21, 15, 16, 0, 19, 12, 4, 27 };
-// start of row r of a matrix in LDS, floats: no bank conflict in the loads (lane l reads row l) nor in the stores (lane l writes row
-// JSX[l] or JSY[l]) of ds_*_b128 -- found and checked by tools/jacobi_schedule.py
-constexpr int JPLACE[28] = { 196, 252, 308, 28, 364, 564, 392, 84, 112, 168, 280, 708, 596, 140, 748, 336, 476, 652, 0, 508, 624, 776, 536, 56, 224, 420, 448, 680 };
-constexpr int JIDLE_ROW = 15;                       // what the idle lanes 28..31 of a half read
-constexpr int JQ_MAT = 808;                         // floats per matrix (804 used)
-constexpr int JQ_HALF = JQ_MAT + 32 + 3 * 32;       // + scales + the three rounds' rotation tables
-
-// sum over the 32 lanes of a half, without address registers (ds_swizzle, xor mode)
-__device__ inline float half_sum_swz(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (16 << 10) | 0x1f));
-    v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (8 << 10) | 0x1f));
-    v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (4 << 10) | 0x1f));
-    v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (2 << 10) | 0x1f));
-    v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (1 << 10) | 0x1f));
-    return v;
-}
-
-template <int X> __device__ inline float dpp_xor(float v)   // v of lane ^ X inside the quad
-{
-    constexpr int ctrl = X == 1 ? 0xB1 /* [1,0,3,2] */ : (X == 2 ? 0x4E /* [2,3,0,1] */ : 0x1B /* [3,2,1,0] */);
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, true));
-}
-
-// x[k] += ms * (x[k] of lane ^ X): rowrot_dpp for the three partners of a quad
-#define BCD_ROWROT(NAME, PERM)                                                                                                              \
-    __device__ inline void NAME(float (&x)[28], float ms)                                                                                   \
-    {                                                                                                                                       \
-        asm volatile("s_nop 1\n\t" BCD_G(0, PERM) BCD_G(1, PERM) BCD_G(2, PERM) BCD_G(3, PERM) BCD_G(4, PERM) BCD_G(5, PERM) BCD_G(6, PERM)  \
-                     BCD_G(7, PERM) BCD_G(8, PERM) BCD_G(9, PERM) BCD_G(10, PERM) BCD_G(11, PERM) BCD_G(12, PERM) BCD_G(13, PERM)            \
-                     BCD_G(14, PERM) BCD_G(15, PERM) BCD_G(16, PERM) BCD_G(17, PERM) BCD_G(18, PERM) BCD_G(19, PERM) BCD_G(20, PERM)         \
-                     BCD_G(21, PERM) BCD_G(22, PERM) BCD_G(23, PERM) BCD_G(24, PERM) BCD_G(25, PERM) BCD_G(26, PERM) BCD_G(27, PERM)         \
-                     : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]),          \
-                       "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]), "+v"(x[16]), "+v"(x[17]),  \
-                       "+v"(x[18]), "+v"(x[19]), "+v"(x[20]), "+v"(x[21]), "+v"(x[22]), "+v"(x[23]), "+v"(x[24]), "+v"(x[25]), "+v"(x[26]), \
-                       "+v"(x[27])                                                                                                          \
-                     : "v"(ms));                                                                                                            \
-    }
-#define BCD_G(i, PERM) "v_fmac_f32_dpp %" #i ", %" #i ", %28 quad_perm:" PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-BCD_ROWROT(rowrot_x1, "[1,0,3,2]")
-BCD_ROWROT(rowrot_x2, "[2,3,0,1]")
-BCD_ROWROT(rowrot_x3, "[3,2,1,0]")
-#undef BCD_G
-#undef BCD_ROWROT
-template <int X> __device__ inline void rowrot_quad(float (&x)[28], float ms)
-{
-    if (X == 1) rowrot_x1(x, ms); else if (X == 2) rowrot_x2(x, ms); else rowrot_x3(x, ms);
-}
-
-// one round of a super-round in the quad's 4 x 4 block: my coefficient of the rotation of (me, me ^ X), the block row and scale updated.
-// Written from the lane's own point of view, the two lanes of a pair run the SAME instructions on mirrored operands: with
-// delta = a_partner - a_me (true values), theta = delta / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), the lower lane's theta is
-// the pair's and the upper lane's its exact negative, so that  mine = -t (d_partner / d_me)  is -beta in the lower lane (x' = x - beta y) and
-// +alpha in the upper one (y' = y + alpha x), and d' = c d in both: no lower / upper selects.  (Both lanes must see the same off-diagonal
-// element: the lower lane's copy -- the two copies of a symmetric element agree only to rounding, and two slightly different angles cost
-// 1.7e-4 of orthogonality.)
-template <int X>
-__device__ inline float quad_round(float (&w)[4], float &dme, bool lo, bool frozen)
-{
-    const float pdiag = dpp_xor<X>(w[0]), pd = dpp_xor<X>(dme), poff = dpp_xor<X>(w[X]);
-    const float apq_s = lo ? w[X] : poff;
-    float mine = 0.f, c = 1.f;
-    if (apq_s != 0.f && !frozen) {
-        const float apq = (dme * pd) * apq_s, a_me = (dme * dme) * w[0], a_pt = (pd * pd) * pdiag;
-        // 1-ulp hardware reciprocal / sqrt / rsqrt: a rotation only has to be orthogonal to working precision, not the exact minimiser
-        const float theta = (a_pt - a_me) * __builtin_amdgcn_rcpf(2.f * apq);
-        if (fabsf(theta) < 1e18f) { // (otherwise theta^2 overflows: the rotation is the identity to fp32)
-            float t = __builtin_amdgcn_rcpf(fabsf(theta) + __builtin_amdgcn_sqrtf(fmaf(theta, theta, 1.f)));
-            t = (lo ? theta < 0.f : !(theta > 0.f)) ? -t : t;   // (theta == 0, equal diagonal elements: the upper lane still takes the opposite sign)
-            c = __builtin_amdgcn_rsqf(fmaf(t, t, 1.f));
-            mine = -t * (pd * __builtin_amdgcn_rcpf(dme));
-        }
-    }
-    dme *= c;
-    // the block row: column rotations (the coefficient of column me ^ y is the one lane me ^ y holds), then the row rotation
-    const float rc1 = dpp_xor<1>(mine), rc2 = dpp_xor<2>(mine), rc3 = dpp_xor<3>(mine);
-    const float rc[4] = { mine, rc1, rc2, rc3 };
-    float nw[4];
-#pragma unroll
-    for (int y = 0; y < 4; ++y) nw[y] = fmaf(rc[y], w[y ^ X], w[y]);
-#pragma unroll
-    for (int y = 0; y < 4; ++y) w[y] = fmaf(mine, dpp_xor<X>(nw[y ^ X]), nw[y]);
-    return mine;
-}
-
-// one super-round (see k_jacobi27_quads); YSTEP: the rows then move by JSY, otherwise by JSX
-template <bool YSTEP>
-__device__ __forceinline__ void jacobi_super_round(float (&vrow)[JLD], float *src, const float *wsrc, float *dst, float *dv_h, float *rot_h, int r,
-                                                   int me, int snext, bool isRow, bool settled)
-{
-        float row[JLD];
-#pragma unroll
-        for (int q4 = 0; q4 < JLD / 4; ++q4) {
-            float4 v = reinterpret_cast<const float4 *>(src)[q4];
-            row[4 * q4] = v.x; row[4 * q4 + 1] = v.y; row[4 * q4 + 2] = v.z; row[4 * q4 + 3] = v.w;
-        }
-        // my row of the quad's diagonal block, xor-relative, and my scale
-        float w[4] = { wsrc[me], wsrc[me ^ 1], wsrc[me ^ 2], wsrc[me ^ 3] };
-        float dme = dv_h[isRow ? r : 0];
-        const float m1 = quad_round<1>(w, dme, (me & 1) == 0, settled);
-        const float m2 = quad_round<2>(w, dme, (me & 2) == 0, settled);
-        const float m3 = quad_round<3>(w, dme, me == 0 || me == 1, settled);   // pairs (0,3), (1,2): the lower lane is 0 resp. 1
-        if (isRow) {
-            rot_h[r] = m1; rot_h[32 + r] = m2; rot_h[64 + r] = m3;
-            dv_h[snext] = dme; // the scales move with their slots
-        }
-        wave_sync();
-        // the three rounds on the rows of A~ (columns in registers, rows by DPP) and on the rows of V~ (columns)
-#define BCD_ROUND(X, MINE)                                                                                                            \
-        {                                                                                                                      \
-            float rot[JLD];                                                                                                    \
-            _Pragma("unroll") for (int q4 = 0; q4 < JLD / 4; ++q4) {                                                           \
-                float4 w4 = reinterpret_cast<const float4 *>(rot_h + 32 * (X - 1))[q4];                                        \
-                rot[4 * q4] = w4.x; rot[4 * q4 + 1] = w4.y; rot[4 * q4 + 2] = w4.z; rot[4 * q4 + 3] = w4.w;                    \
-            }                                                                                                                  \
-            _Pragma("unroll") for (int k = 0; k < JLD; ++k)                                                                    \
-                if ((k & 3) < ((k ^ X) & 3)) {                                                                                 \
-                    const int q = k ^ X;                                                                                       \
-                    const float xv = vrow[k], yv = vrow[q];                                                                    \
-                    vrow[k] = fmaf(rot[k], yv, xv); vrow[q] = fmaf(rot[q], xv, yv);                                            \
-                }                                                                                                              \
-            /* (pinned here: the optimiser otherwise sinks all of a sweep's updates of V~ to the end of the sweep and keeps the    */ \
-            /* 27 rotation tables in scratch memory until then)                                                                 */ \
-            _Pragma("unroll") for (int k = 0; k < JLD; ++k) asm volatile("" : "+v"(vrow[k]));                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                                                 \
-            _Pragma("unroll") for (int k = 0; k < JLD; ++k)                                                                    \
-                if ((k & 3) < ((k ^ X) & 3)) {                                                                                 \
-                    const int q = k ^ X;                                                                                       \
-                    const float xa = row[k], ya = row[q];                                                                      \
-                    row[k] = fmaf(rot[k], ya, xa); row[q] = fmaf(rot[q], xa, ya);                                              \
-                }                                                                                                              \
-            rowrot_quad<X>(row, MINE);                                                                                         \
-        }
-        BCD_ROUND(1, m1)
-        __builtin_amdgcn_sched_barrier(0);
-        BCD_ROUND(2, m2)
-        __builtin_amdgcn_sched_barrier(0);
-        BCD_ROUND(3, m3)
-        __builtin_amdgcn_sched_barrier(0);
-#undef BCD_ROUND
-        // back to LDS at the next positions; the same move of the columns is a renaming of registers
-        {
-            float out[JLD], vout[JLD];
-#pragma unroll
-            for (int k = 0; k < JLD; ++k) { out[YSTEP ? JSY[k] : JSX[k]] = row[k]; vout[YSTEP ? JSY[k] : JSX[k]] = vrow[k]; }
-#pragma unroll
-            for (int k = 0; k < JLD; ++k) vrow[k] = vout[k];
-            if (isRow) {
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4)
-                    reinterpret_cast<float4 *>(dst)[q4] = make_float4(out[4 * q4], out[4 * q4 + 1], out[4 * q4 + 2], out[4 * q4 + 3]);
-            }
-        }
-        wave_sync(); // the rows of A~ are back in LDS before the next super-round reads them
-        __builtin_amdgcn_sched_barrier(0);
-}
-
-// what a lane of k_jacobi27_quads knows about its place in the solver's LDS area (2 * JQ_HALF + 32 floats: two matrices with their scales and rotation
-// tables, then the placement table)
-struct JqLane {
-    float *Ah, *dv_h, *rot_h, *src, *dst_x, *dst_y;
-    const float *wsrc;
-    const int *place_tab;
-    int h, r, me, sx, sy;
-    bool isRow;
-};
-constexpr int JQ_LDS = 2 * JQ_HALF + 32;            // floats of the solver's LDS area
-
-// the lane's constants; writes the placement table (the caller orders it before the first solve with wave_sync)
-__device__ __forceinline__ JqLane jq_lane_setup(float *lds, int lane)
-{
-    JqLane L;
-    int *place_tab = reinterpret_cast<int *>(lds + 2 * JQ_HALF);
-    L.place_tab = place_tab;
-    L.h = lane >> 5; L.r = lane & 31;
-    L.isRow = L.r < KP;
-    if (lane < KP) place_tab[lane] = JPLACE[lane];
-    L.Ah = lds + L.h * JQ_HALF; L.dv_h = L.Ah + JQ_MAT; L.rot_h = L.dv_h + 32;
-    const int rr_ = L.isRow ? L.r : JIDLE_ROW;
-    L.sx = L.isRow ? JSX[rr_] : 0; L.sy = L.isRow ? JSY[rr_] : 0;
-    L.src = L.Ah + JPLACE[rr_];                     // (idle lanes: a row of their own ds_read_b128 bank group)
-    L.dst_x = L.Ah + JPLACE[L.sx]; L.dst_y = L.Ah + JPLACE[L.sy];
-    L.wsrc = L.src + (L.isRow ? (L.r & ~3) : 0);    // the quad's columns of my row
-    L.me = L.r & 3;
-    return L;
-}
-
-// one task of k_jacobi27_quads: the matrices 2 pair and 2 pair + 1 of Ain (n in all) from memory through the sweeps to eig / Vout / Aout
-__device__ __forceinline__ void jacobi_quads_pair(const JqLane &L, int pair, int n, const float *Ain, float *__restrict__ eig, float *__restrict__ Vout,
-                                                  float conv2, float *Aout)
-{
-        const int h = L.h, r = L.r, me = L.me, sx = L.sx, sy = L.sy;
-        const bool isRow = L.isRow;
-        float *Ah = L.Ah, *dv_h = L.dv_h, *rot_h = L.rot_h, *src = L.src, *dst_x = L.dst_x, *dst_y = L.dst_y;
-        const float *wsrc = L.wsrc;
-        const int *place_tab = L.place_tab;
-        const int first = 2 * pair;
-        const int item = first + h;
-        const bool live = item < n;
-        // matrix -> LDS (an absent second matrix is the identity: converged from the start)
-        {
-            const float4 *gsrc = reinterpret_cast<const float4 *>(Ain + (size_t)(live ? item : first) * (KP * JLD));
-            for (int e = r; e < KP * JLD / 4; e += 32) {
-                float4 v = gsrc[e];
-                const int e0 = 4 * e, rr = e0 / JLD, c0 = e0 - rr * JLD;
-                if (!live) v = make_float4(rr == c0, rr == c0 + 1, rr == c0 + 2, rr == c0 + 3);
-                *reinterpret_cast<float4 *>(Ah + place_tab[rr] + c0) = v;
-            }
-            if (isRow) dv_h[r] = 1.f;
-        }
-        wave_sync();
-        float vrow[JLD];
-#pragma unroll
-        for (int k = 0; k < JLD; ++k) vrow[k] = (k == r) ? 1.f : 0.f; // V = identity
-        for (int sweep = 0; sweep < 12; ++sweep) {
-            // fold the scales: A~ <- D A~ D, V~ <- V~ D, D <- I; off / diagonal norms of the true matrix on the way (as k_jacobi27_batch)
-            float off = 0.f, dg = 0.f;
-            {
-                float dk[JLD];
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4) {
-                    float4 w4 = reinterpret_cast<const float4 *>(dv_h)[q4];
-                    dk[4 * q4] = w4.x; dk[4 * q4 + 1] = w4.y; dk[4 * q4 + 2] = w4.z; dk[4 * q4 + 3] = w4.w;
-                }
-                const float dr = dv_h[isRow ? r : 0];
-                float row[JLD];
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4) {
-                    float4 v = reinterpret_cast<const float4 *>(src)[q4];
-                    row[4 * q4] = v.x; row[4 * q4 + 1] = v.y; row[4 * q4 + 2] = v.z; row[4 * q4 + 3] = v.w;
-                }
-#pragma unroll
-                for (int k = 0; k < JLD; ++k) {
-                    row[k] *= dr * dk[k];
-                    vrow[k] *= dk[k];
-                    if (isRow) { if (k == r) dg = fmaf(row[k], row[k], dg); else off = fmaf(row[k], row[k], off); }
-                }
-                wave_sync(); // every lane has read the scales and its row
-                if (isRow) {
-#pragma unroll
-                    for (int q4 = 0; q4 < JLD / 4; ++q4)
-                        reinterpret_cast<float4 *>(src)[q4] = make_float4(row[4 * q4], row[4 * q4 + 1], row[4 * q4 + 2], row[4 * q4 + 3]);
-                    dv_h[r] = 1.f;
-                }
-                wave_sync();
-            }
-            off = half_sum_swz(off);
-            dg = half_sum_swz(dg);
-            // (threshold and freezing of a converged matrix: as k_jacobi27_batch)
-            const bool settled = off <= conv2 * dg;
-            if (__builtin_amdgcn_ballot_w64(!settled) == 0) break; // both matrices converged
-            // x x y x x y x x y: one sweep, every slot home again
-            jacobi_super_round<false>(vrow, src, wsrc, dst_x, dv_h, rot_h, r, me, sx, isRow, settled);
-            jacobi_super_round<false>(vrow, src, wsrc, dst_x, dv_h, rot_h, r, me, sx, isRow, settled);
-            jacobi_super_round<true>(vrow, src, wsrc, dst_y, dv_h, rot_h, r, me, sy, isRow, settled);
-            jacobi_super_round<false>(vrow, src, wsrc, dst_x, dv_h, rot_h, r, me, sx, isRow, settled);
-            jacobi_super_round<false>(vrow, src, wsrc, dst_x, dv_h, rot_h, r, me, sx, isRow, settled);
-            jacobi_super_round<true>(vrow, src, wsrc, dst_y, dv_h, rot_h, r, me, sy, isRow, settled);
-            jacobi_super_round<false>(vrow, src, wsrc, dst_x, dv_h, rot_h, r, me, sx, isRow, settled);
-            jacobi_super_round<false>(vrow, src, wsrc, dst_x, dv_h, rot_h, r, me, sx, isRow, settled);
-            jacobi_super_round<true>(vrow, src, wsrc, dst_y, dv_h, rot_h, r, me, sy, isRow, settled);
-        }
-        if (live) {
-            if (isRow) eig[(size_t)item * KP + r] = src[r];
-        }
-        if (Aout) { // (wave-uniform)
-            if (isRow) rot_h[r] = src[r];
-            wave_sync();
-            if (isRow && live) jacobi_write_correction(Aout + (size_t)item * (KP * JLD) + r * JLD, src, rot_h, r);
-        }
-        if (live) {
-            if (r < K) {
-                float4 *o = reinterpret_cast<float4 *>(Vout + (size_t)item * (KP * JLD) + r * JLD);
-#pragma unroll
-                for (int q4 = 0; q4 < JLD / 4; ++q4) o[q4] = make_float4(vrow[4 * q4], vrow[4 * q4 + 1], vrow[4 * q4 + 2], vrow[4 * q4 + 3]);
-            }
-        }
-        wave_sync(); // the next pair reuses the LDS
-}
-
-__global__ __launch_bounds__(64, 3) void k_jacobi27_quads(const float *Ain, int n, int *work, float *__restrict__ eig,
-                                                          float *__restrict__ Vout, float conv2, float *Aout, const int *d_n, int first_item)
-{
-    n = items_on_device(d_n, first_item, n);
-    __shared__ float4 lds4[JQ_LDS / 4];
-    const int lane = threadIdx.x;
-    const JqLane L = jq_lane_setup(reinterpret_cast<float *>(lds4), lane);
-    wave_sync();
-    WorkCursor cursor = work_begin();
-    for (;;) {
-        const int pair = work_next(work, (n + 1) / 2, lane, cursor);
-        if (pair < 0) break;
-        jacobi_quads_pair(L, pair, n, Ain, eig, Vout, conv2, Aout);
-    }
 }
 
 __device__ void add_noise27(float *M, const float *noise, int lane, float sign)
@@ -929,10 +292,7 @@ __device__ __attribute__((noinline)) void mfma27(float *out, int ldo, const floa
 // 9.8e-6 from the oracle at 2e-9 (1.6e-5 at 1e-8; 2.9e-6 with the plain rule at 1e-12; 2.9e-4 at 1e-6 corrected); the 32-spp frames stay at 4e-7 ... 9e-7.
 // A per-pair stopping rule (every opposite-sign pair decoupled, loose bound on the rest) was built and measured out: in fp32 it needs the
 // sixth sweep as often as the plain rule does, and its test costs 5 % of a sweep.
-constexpr float JACOBI_CONV2_CORRECTED = 2e-9f; // off / diag <= 4.5e-5
 constexpr bool FOLD_MAIN_TERM = true;             // k_finish27w: V (diag f + E o Phi) V^T as two products instead of three (round 5)
-constexpr float JACOBI_CONV2_STRICT = 1e-12f;   // the round-3 rule: one sweep more, the correction then has nothing left to do
-
 
 // Bm (LD layout) <- V f(D) V^T + V (E o Phi) V^T; Mb: 28 x 28 scratch (JLD layout), eigs: 28 floats of scratch, V: LDS copy of the record's V (JLD
 // layout), recAk / recEig: the solver's output in the record (global memory)
@@ -980,7 +340,6 @@ __device__ int decode_members27(const uint32_t *mask, int p, const Geom27 &g, ui
     return total;
 }
 
-// stage members [i0, i0+cn) of the similar set into the LDS chunk (pickColorPatchesFromColorImage :483-498)
 // staging of members [i0, i0+cn) of the similar set (pickColorPatchesFromColorImage :483-498) in two halves, so that the global
 // loads of the next chunk are in flight while the current one is being consumed: stage_load -> registers, stage_store -> LDS
 constexpr int STAGE_REGS = (CHUNK * K + 63) / 64;
@@ -1117,12 +476,6 @@ __device__ __attribute__((noinline)) void final_pass27(const float *Cm, float *c
     }
 }
 
-// Per processed pixel the estimate is three kernels; between them a pixel's state lives in a record in HBM (~9.9 KB):
-//   PHASE 1  k_bayes27<1>  members, noise / colour means, covariance C; writes  A = C - N (28 x 28, zero-padded), C, N, m
-//   (k_jacobi27_batch: eigen-decomposition of every A, two per wavefront)
-//   PHASE 2  k_bayes27<2>  reads C, N, m, eigenvalues and eigenvectors; clamp, inverses, Step 2, final estimate, aggregation.
-// Splitting costs ~20 KB of HBM traffic per pixel (nothing next to the ~300 us a pixel takes) and buys a solver that is not
-// tied to the LDS footprint and register pressure of the other phases (12 -> 24 matrices per CU, shared rotations).
 // A non-finite entry of the noise mean makes the whole estimate of the item NaN in the reference: its eigensolver turns C - N with one NaN (or
 // inf: the matrix is scaled by its largest element first) into NaNs throughout, and every later product inherits them.  Here the NaN would stay in the
 // rows and columns of its 3 x 3 block -- the solver skips a rotation whose angle is not a number, V stays finite -- and max(0, NaN) = 0 and
@@ -1133,11 +486,6 @@ __device__ inline bool noise_poisons_item(const float *noise, int lane)
 {
     return __builtin_amdgcn_ballot_w64(lane < P * 6 && !isfinite(noise[lane])) != 0;
 }
-
-struct Records27 {
-    float *A, *V, *C, *aux, *eig; // [items][784], [items][784], [items][784], [items][AUX27], [items][28]
-};
-constexpr int AUX27 = 96; // noise 54, mean 27, padding
 
 template <int PHASE>
 __global__ __launch_bounds__(64) void k_bayes27(const float *__restrict__ colors, const float *__restrict__ pixcov,
@@ -1269,7 +617,6 @@ __global__ __launch_bounds__(64) void k_bayes27(const float *__restrict__ colors
   }
   }
 }
-
 
 // =====================================================================================================================
 // Windowed variant for the default search radius (b = 6): every patch of every member of S(p) lies inside the 15 x 15 pixel
@@ -2125,6 +1472,22 @@ __global__ __launch_bounds__(64, 3) void k_finish27w(const float *__restrict__ c
 
 } // namespace
 
+// ---- the launchers: a chunk's chain is decided once (chain27) and launched stage by stage -- PREPARE, SOLVE (or both as one kernel), FINISH, the walk
+// over the REDO list --, each stage on the queue group of its name in d_work; the four public launchers are compositions of the stages
+const BcdBayes27Switches &bcd_bayes27_switches()
+{
+    static const auto on = [](const char *name) { const char *e = getenv(name); return e && e[0] == '1'; };
+    static const BcdBayes27Switches sw{ on("BCD_HIP_FINISH_LDS"), on("BCD_HIP_JACOBI_PAIRS"), on("BCD_HIP_PREPARE_GATHER"), on("BCD_HIP_PREPARE_SOLVE_SPLIT"),
+                                        on("BCD_HIP_STRICT_EIGEN") };
+    return sw;
+}
+
+// PREPARE and SOLVE of the windowed path as one kernel or as two: BCD_HIP_PREPARE_SOLVE_SPLIT=1 or bcd_hip_set_fused_prepare_solve(0) keep the
+// two launches (the A/B partner: the records are the same bits either way, tests/test_gpu_prepare_solve_fused.py)
+static std::atomic<int> g_fused_prepare_solve{ -1 }; // (-1: the setter was not called, the environment decides)
+void bcd_bayes27_set_fused_prepare_solve(int on) { g_fused_prepare_solve.store(on ? 1 : 0); }
+int bcd_bayes27_fused_prepare_solve() { const int v = g_fused_prepare_solve.load(); return v < 0 ? !bcd_bayes27_switches().prepare_solve_split : v; }
+
 // LDS of the widest phase (PHASE 2: four matrix buffers)
 size_t bcd_bayes27_lds_bytes(int b)
 {
@@ -2133,169 +1496,166 @@ size_t bcd_bayes27_lds_bytes(int b)
 }
 
 // bytes of HBM one processed pixel needs between the phases (A, V, C, noise + mean, eigenvalues, its entry of the redo list)
-size_t bcd_bayes27_record_bytes() { return (size_t)(3 * MSZ + AUX27 + KP) * sizeof(float) + 2 * sizeof(int); } // (+ the redo list: 1 + items ints)
+size_t bcd_bayes27_record_bytes() { return RECORD27_BYTES; }
 
-hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blocks, float *eig, float *V, hipStream_t st, float conv2 = 1e-12f, float *Aout = nullptr,
-                                     const int *d_n = nullptr, int first_item = 0);
+namespace {
 
-// Stopping rule of the estimate chain's eigensolver: 2e-9 + first-order correction (production), or -- strict mode, BCD_HIP_STRICT_EIGEN=1 or
-// bcd_hip_set_strict_eigensolver -- the fully converged 1e-12 (the looser rule spends accuracy on ill-conditioned low-spp frames, 9.8e-6
-// instead of 2.9e-6 on the 4K 8-spp frame; a caller who wants the margin back can have it for ~1.5 % of the step)
-static std::atomic<int> g_strict_eigen{ -1 };
-void bcd_bayes27_set_strict_eigensolver(int on) { g_strict_eigen.store(on ? 1 : 0); }
-static float jacobi_conv2()
+constexpr int WB2 = 12; // the large search window of BASELINE configs[4]: windowed prepare and register-resident finish on a 27 x 27 pixel window
+constexpr size_t FINISH_LDS_WINDOW_BYTES = (size_t)W2_MEM * sizeof(float) + WMEM * sizeof(uint16_t); // k_bayes27w<2>
+
+// which kernels a chunk's chain is made of
+enum Prepare27 { PREPARE_FUSED /* k_prepare_solve27: with SOLVE */, PREPARE_WINDOW /* k_bayes27w<1, b> */, PREPARE_GATHER /* k_bayes27<1> */ };
+enum Solver27 { SOLVE_QUADS /* k_jacobi27_quads */, SOLVE_PAIRS /* k_jacobi27_batch; bcd_launch_jacobi27_batch makes the same choice */ };
+enum Finish27 { FINISH_REGS /* k_finish27w<b> */, FINISH_LDS_WINDOW /* k_bayes27w<2> */, FINISH_LDS_GATHER /* k_bayes27<2> */ };
+enum Redo27 { REDO_NONE, REDO_WINDOW /* k_bayes27w<2> on the list */, REDO_GATHER /* k_bayes27<2> on the list */ };
+struct Chain27 { Prepare27 prepare; Solver27 solver; Finish27 finish; Redo27 redo; };
+
+// who walks the redo list that k_finish27w<b> leaves
+Redo27 redo_kernel27(int b) { return b == WB ? REDO_WINDOW : (b == WB2 ? REDO_GATHER : REDO_NONE); }
+
+Chain27 chain27(int b, const BcdBayes27Switches &sw, bool fused)
 {
-    int v = g_strict_eigen.load();
-    if (v < 0) { const char *e = getenv("BCD_HIP_STRICT_EIGEN"); v = (e && e[0] == '1') ? 1 : 0; g_strict_eigen.store(v); }
-    return v ? JACOBI_CONV2_STRICT : JACOBI_CONV2_CORRECTED;
-}
-
-// the two rules by name, for the stand-alone eigensolver entry point (bcd_hip_eig27_batch_rule)
-float bcd_bayes27_conv2(int strict) { return strict ? JACOBI_CONV2_STRICT : JACOBI_CONV2_CORRECTED; }
-
-// PREPARE and SOLVE of the windowed path as one kernel or as two: BCD_HIP_PREPARE_SOLVE_SPLIT=1 or bcd_hip_set_fused_prepare_solve(0) keep the
-// two launches (the A/B partner: the records are the same bits either way, tests/test_gpu_prepare_solve_fused.py)
-static std::atomic<int> g_fused_prepare_solve{ -1 };
-void bcd_bayes27_set_fused_prepare_solve(int on) { g_fused_prepare_solve.store(on ? 1 : 0); }
-int bcd_bayes27_fused_prepare_solve()
-{
-    int v = g_fused_prepare_solve.load();
-    if (v < 0) { const char *e = getenv("BCD_HIP_PREPARE_SOLVE_SPLIT"); v = (e && e[0] == '1') ? 0 : 1; g_fused_prepare_solve.store(v); }
-    return v;
-}
-
-// the records A (then E o Phi), C, noise + mean, eig and V of a chunk, default search radius: k_prepare_solve27, or k_bayes27w<1> and the eigensolver
-// (which is also what BCD_HIP_JACOBI_PAIRS=1, the comparison eigensolver, gets).  d_work: the queues of the prepare kernel, then the solver's.
-static hipError_t launch_prepare_solve27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
-                                         int *d_work, int num_cus, const Geom27 &g, const Records27 &rec, int *redo, hipStream_t st, const int *dn, int fused)
-{
-    static const bool pairs = [] { const char *e = getenv("BCD_HIP_JACOBI_PAIRS"); return e && e[0] == '1'; }();
-    const size_t wl1 = W1L<WB>::BYTES;
-    if (fused && !pairs) {
-        hipLaunchKernelGGL(k_prepare_solve27<WB>, dim3(std::min((nb_items + 1) / 2, num_cus * 12)), dim3(64), wl1, st, colors, pixcov, mask, list, first_item,
-                           nb_items, d_work, g, rec, redo, jacobi_conv2(), dn);
-        return hipGetLastError();
-    }
-    const int w_cu1 = (int)std::min<size_t>(20, (size_t)160 * 1024 / wl1);
-    hipLaunchKernelGGL(k_bayes27w<1>, dim3(std::min(nb_items, num_cus * w_cu1)), dim3(64), wl1, st, colors, pixcov, mask, list, first_item, nb_items,
-                       d_work, g, 0.f, rec, (float *)nullptr, (int32_t *)nullptr, (const int *)redo, dn);
-    return bcd_launch_jacobi27_batch(rec.A, nb_items, d_work + BCD_WORK_QUEUES * BCD_WORK_STRIDE, std::min((nb_items + 1) / 2, num_cus * 12), rec.eig, rec.V, st,
-                                     jacobi_conv2(), rec.A, dn, first_item);
-}
-
-// Full estimate of items [first_item, first_item + nb_items) of `list`: three launches; `records` holds nb_items records
-// (bcd_bayes27_record_bytes() each), d_work BCD_WORK_INTS zeroed ints (the work queues of the three kernels).
-hipError_t bcd_launch_bayes27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
-                              int *d_work, int num_cus, int W, int H, int b, float min_eig, float *records, float *sum,
-                              int32_t *cnt, int *d_spectral /* += items whose inverse took the spectral branch (windowed path) */, hipStream_t st,
-                              int defer_redo /* != 0: the caller reads *d_spectral after its next synchronisation and calls bcd_launch_bayes27_redo if it is > 0 */,
-                              const int *d_nb_items /* optional: the list's length on the device -- the chunk is then min(nb_items, *d_nb_items - first_item) items,
-                                                       nb_items being the capacity of `records` (grids are sized for it; wavefronts without an item leave at once) */)
-{
-    const int *dn = d_nb_items;
-    if (nb_items <= 0) return hipSuccess;
-    Geom27 g;
-    g.W = W; g.H = H; g.b = b; g.side = 2 * b + 1; g.words = (g.side * g.side + 31) / 32; g.maxS = g.side * g.side;
-    if (g.words > 32) return hipErrorInvalidValue;
-    Records27 rec;
-    rec.A = records;
-    rec.V = rec.A + (size_t)nb_items * MSZ;
-    rec.C = rec.V + (size_t)nb_items * MSZ;
-    rec.aux = rec.C + (size_t)nb_items * MSZ;
-    rec.eig = rec.aux + (size_t)nb_items * AUX27;
-    const size_t lds2 = bcd_bayes27_lds_bytes(b), lds1 = lds2 - 3 * MSZ * sizeof(float);
-    const int per_cu1 = (int)std::min<size_t>(20, (size_t)160 * 1024 / lds1), per_cu2 = (int)std::min<size_t>(12, (size_t)160 * 1024 / lds2);
-    if (b == WB) {
-        // default search radius: the windowed kernels (members read from LDS windows)
-        const size_t wl2 = (size_t)W2_MEM * sizeof(float) + WMEM * sizeof(uint16_t);
-        const int w_cu2 = (int)std::min<size_t>(12, (size_t)160 * 1024 / wl2);
-        static const bool lds_algebra = [] { const char *e = getenv("BCD_HIP_FINISH_LDS"); return e && e[0] == '1'; }();
-        int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP); // (the register-resident finish; cleared by the prepare kernel)
-        { hipError_t e = launch_prepare_solve27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, g, rec, lds_algebra ? nullptr : redo, st, dn,
-                                                bcd_bayes27_fused_prepare_solve()); if (e != hipSuccess) return e; }
-        if (lds_algebra)
-            hipLaunchKernelGGL(k_bayes27w<2>, dim3(std::min(nb_items, num_cus * w_cu2)), dim3(64), wl2, st, colors, pixcov, mask, list, first_item, nb_items,
-                               d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, nullptr, dn);
-        else {
-            // the register-resident finish; the items whose sweep inverse fails its checks (rare) come back on a list for the LDS kernel
-            const size_t wl3 = WinT<WB>::F2_BYTES;
-            hipLaunchKernelGGL(k_finish27w<WB>, dim3(std::min(nb_items, num_cus * 12)), dim3(64), wl3, st, colors, mask, list, first_item, nb_items,
-                               d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, redo, d_spectral, dn);
-            // (normally an empty list: a small grid, so that its 17 KB workgroups do not queue for LDS behind the kernels of the other scales --
-            // a full-size launch that only reads "0 items" was seen waiting 0.7 ms for room.  A long list is still processed, by fewer wavefronts.)
-            // Round 4: a caller that looks at the counter anyway does not launch it at all on an empty list -- beside the persistent kernels of the other
-            // scales even the small launch sat 170-470 us on a coarse scale's stream waiting for LDS, with nothing to do.
-            if (!defer_redo)
-                hipLaunchKernelGGL(k_bayes27w<2>, dim3(std::min(nb_items, num_cus * 2)), dim3(64), wl2, st, colors, pixcov, mask, list, first_item, nb_items,
-                                   d_work + 3 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, redo, dn);
-        }
-        return hipGetLastError();
-    }
-    constexpr int WB2 = 12; // the large search window of BASELINE configs[4]: register-resident finish on a 27 x 27 pixel window (round 4)
-    static const bool finish_lds_b12 = [] { const char *e = getenv("BCD_HIP_FINISH_LDS"); return e && e[0] == '1'; }();
-    const bool finish_regs = b == WB2 && !finish_lds_b12;
-    int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP);
+    Chain27 ch;
+    ch.solver = sw.jacobi_pairs ? SOLVE_PAIRS : SOLVE_QUADS;
+    const bool regs = (b == WB || b == WB2) && !sw.finish_lds;
+    ch.finish = regs ? FINISH_REGS : (b == WB ? FINISH_LDS_WINDOW : FINISH_LDS_GATHER);
+    ch.redo = regs ? redo_kernel27(b) : REDO_NONE;
     // (round 5) b = 12 prepares from LDS windows too: the gather kernel read 105 KB per item (325 members x 81 floats, scattered) where the
     // 27 x 27 window is 26 KB of whole rows; BCD_HIP_PREPARE_GATHER=1 keeps the gather form (A/B; the records are bit-identical)
-    static const bool prepare_gather = [] { const char *e = getenv("BCD_HIP_PREPARE_GATHER"); return e && e[0] == '1'; }();
-    const bool prepare_win = finish_regs && !prepare_gather;
-    if (prepare_win) {
-        const size_t wl1 = W1L<WB2>::BYTES;
-        const int w_cu1 = (int)std::min<size_t>(20, (size_t)160 * 1024 / wl1);
-        hipLaunchKernelGGL((k_bayes27w<1, WB2>), dim3(std::min(nb_items, num_cus * w_cu1)), dim3(64), wl1, st, colors, pixcov, mask, list, first_item, nb_items,
-                           d_work, g, min_eig, rec, sum, cnt, (const int *)redo, dn);
-    } else
-        hipLaunchKernelGGL(k_bayes27<1>, dim3(std::min(nb_items, num_cus * per_cu1)), dim3(64), lds1, st, colors, pixcov, mask, list, first_item, nb_items,
-                           d_work, g, min_eig, rec, sum, cnt, (const int *)nullptr, dn);
-    { hipError_t e = bcd_launch_jacobi27_batch(rec.A, nb_items, d_work + BCD_WORK_QUEUES * BCD_WORK_STRIDE, std::min((nb_items + 1) / 2, num_cus * 12), rec.eig, rec.V, st, jacobi_conv2(), rec.A, dn, first_item); if (e != hipSuccess) return e; }
-    if (finish_regs) {
-        // the gather prepare kernel does not know the redo list: its counter is cleared here (one fill per chunk)
-        if (!prepare_win) { hipError_t e = hipMemsetAsync(redo, 0, sizeof(int), st); if (e != hipSuccess) return e; }
-        const size_t wl3 = WinT<WB2>::F2_BYTES;
+    if (b == WB) ch.prepare = (fused && ch.solver == SOLVE_QUADS) ? PREPARE_FUSED : PREPARE_WINDOW;
+    else ch.prepare = (b == WB2 && regs && !sw.prepare_gather) ? PREPARE_WINDOW : PREPARE_GATHER;
+    return ch;
+}
+
+// what a stage launcher needs to know about the chunk; d_nb_items (optional): the list's length on the device, nb_items then being the records' capacity
+struct Chunk27 {
+    const float *colors, *pixcov;
+    const uint32_t *mask;
+    const int32_t *list;
+    int first_item, nb_items;
+    Geom27 g;
+    Records27 rec;
+    int *redo, *d_work;
+    int num_cus;
+    hipStream_t st;
+    const int *d_nb_items;
+    float min_eig, *sum;
+    int32_t *cnt;
+};
+Chunk27 chunk27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items, int *d_work, int num_cus,
+                int W, int H, int b, float *records, hipStream_t st, const int *d_nb_items, float min_eig = 0.f, float *sum = nullptr, int32_t *cnt = nullptr)
+{
+    const Chunk27Records r = carve27(records, nb_items);
+    return { colors, pixcov, mask, list, first_item, nb_items, geom27(W, H, b), r.rec, r.redo, d_work, num_cus, st, d_nb_items, min_eig, sum, cnt };
+}
+
+// wavefronts (= workgroups) per CU of a persistent kernel: what its LDS lets a CU hold, `cap` at the most
+int waves_per_cu(int cap, size_t lds_bytes) { return (int)std::min<size_t>(cap, (size_t)160 * 1024 / lds_bytes); }
+dim3 grid_pairs(const Chunk27 &c) { return dim3(std::min((c.nb_items + 1) / 2, c.num_cus * 12)); }
+
+// the kernels that walk items with the whole wavefront, k_bayes27<PHASE> and k_bayes27w<PHASE, B>, share one signature
+using ItemKernel27 = decltype(&k_bayes27<1>);
+hipError_t launch_items(ItemKernel27 kernel, const Chunk27 &c, WorkGroup27 queues, int per_cu, size_t lds, const int *redo)
+{
+    hipLaunchKernelGGL(kernel, dim3(std::min(c.nb_items, c.num_cus * per_cu)), dim3(64), lds, c.st, c.colors, c.pixcov, c.mask, c.list, c.first_item, c.nb_items,
+                       work_group(c.d_work, queues), c.g, c.min_eig, c.rec, c.sum, c.cnt, redo, c.d_nb_items);
+    return hipGetLastError();
+}
+
+// PREPARE: the records A = C - N, C, noise + mean; the window kernels also clear the counter of c.redo, if there is one (the gather kernel does not know it)
+hipError_t launch_prepare(const Chunk27 &c, Prepare27 form)
+{
+    const bool win = form == PREPARE_WINDOW, def = c.g.b == WB;
+    const size_t lds = win ? (def ? W1L<WB>::BYTES : W1L<WB2>::BYTES) : bcd_bayes27_lds_bytes(c.g.b) - 3 * MSZ * sizeof(float);
+    return launch_items(win ? (def ? &k_bayes27w<1, WB> : &k_bayes27w<1, WB2>) : &k_bayes27<1>, c, WORK_PREPARE, waves_per_cu(20, lds), lds, win ? c.redo : nullptr);
+}
+
+// SOLVE: eig, V and E o Phi (over A) of every record
+hipError_t launch_solve(const Chunk27 &c)
+{
+    return bcd_launch_jacobi27_batch(c.rec.A, c.nb_items, work_group(c.d_work, WORK_SOLVE), (int)grid_pairs(c).x, c.rec.eig, c.rec.V, c.st, bcd_bayes27_chain_conv2(),
+                                     c.rec.A, c.d_nb_items, c.first_item);
+}
+
+// PREPARE + SOLVE of the default search radius in one kernel (the prepare group's queues hand out pairs)
+hipError_t launch_prepare_solve(const Chunk27 &c)
+{
+    hipLaunchKernelGGL(k_prepare_solve27<WB>, grid_pairs(c), dim3(64), W1L<WB>::BYTES, c.st, c.colors, c.pixcov, c.mask, c.list, c.first_item, c.nb_items,
+                       work_group(c.d_work, WORK_PREPARE), c.g, c.rec, c.redo, bcd_bayes27_chain_conv2(), c.d_nb_items);
+    return hipGetLastError();
+}
+
+// the register-resident finish; the items whose sweep inverse fails its checks (rare) are appended to c.redo and counted in *d_spectral
+template <int B> hipError_t launch_finish_regs(const Chunk27 &c, int *d_spectral)
+{
+    const size_t lds = WinT<B>::F2_BYTES;
+    if (lds > 64 * 1024) { // (b = 12) more dynamic LDS than a kernel gets unasked: granted once per device -- deliberate, the attribute is per device
         static std::atomic<int> granted[64];
         int dev = -1;
         if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-        if (wl3 > 64 * 1024 && (dev < 0 || dev >= 64 || granted[dev].load() == 0)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_finish27w<WB2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl3);
+        if (dev < 0 || dev >= 64 || granted[dev].load() == 0) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_finish27w<B>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
             if (dev >= 0 && dev < 64) granted[dev].store(1);
         }
-        const int per_cu3 = (int)std::min<size_t>(12, (size_t)160 * 1024 / wl3);
-        hipLaunchKernelGGL(k_finish27w<WB2>, dim3(std::min(nb_items, num_cus * per_cu3)), dim3(64), wl3, st, colors, mask, list, first_item, nb_items,
-                           d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, redo, d_spectral, dn);
-        if (!defer_redo)
-            hipLaunchKernelGGL(k_bayes27<2>, dim3(std::min(nb_items, num_cus * 2)), dim3(64), lds2, st, colors, pixcov, mask, list, first_item, nb_items,
-                               d_work + 3 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, (const int *)redo, dn);
-        return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_bayes27<2>, dim3(std::min(nb_items, num_cus * per_cu2)), dim3(64), lds2, st, colors, pixcov, mask, list, first_item, nb_items,
-                       d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, (const int *)nullptr, dn);
+    hipLaunchKernelGGL(k_finish27w<B>, dim3(std::min(c.nb_items, c.num_cus * waves_per_cu(12, lds))), dim3(64), lds, c.st, c.colors, c.mask, c.list, c.first_item,
+                       c.nb_items, work_group(c.d_work, WORK_FINISH), c.g, c.min_eig, c.rec, c.sum, c.cnt, c.redo, d_spectral, c.d_nb_items);
     return hipGetLastError();
+}
+
+// FINISH: clamp, inverses, Step 2, final estimates, aggregation into sum / cnt -- in registers, or through LDS matrices
+hipError_t launch_finish(const Chunk27 &c, Finish27 form, int *d_spectral)
+{
+    if (form == FINISH_REGS) return c.g.b == WB ? launch_finish_regs<WB>(c, d_spectral) : launch_finish_regs<WB2>(c, d_spectral);
+    const bool win = form == FINISH_LDS_WINDOW;
+    const size_t lds = win ? FINISH_LDS_WINDOW_BYTES : bcd_bayes27_lds_bytes(c.g.b);
+    return launch_items(win ? &k_bayes27w<2> : &k_bayes27<2>, c, WORK_FINISH, waves_per_cu(12, lds), lds, nullptr);
+}
+
+// REDO: the LDS finish on the items of c.redo.  Normally an empty list: a small grid -- num_cus * 2, deliberate -- so that its 17 KB workgroups do not queue
+// for LDS behind the kernels of the other scales (a full-size launch that only reads "0 items" was seen waiting 0.7 ms for room); a long list is still
+// processed, by fewer wavefronts
+hipError_t launch_redo(const Chunk27 &c, Redo27 form)
+{
+    const bool win = form == REDO_WINDOW;
+    return launch_items(win ? &k_bayes27w<2> : &k_bayes27<2>, c, WORK_REDO, 2, win ? FINISH_LDS_WINDOW_BYTES : bcd_bayes27_lds_bytes(c.g.b), c.redo);
+}
+
+} // namespace
+
+// Full estimate of items [first_item, first_item + nb_items) of `list`: `records` holds nb_items records (bcd_bayes27_record_bytes() each), d_work
+// BCD_WORK_INTS zeroed ints; d_spectral, defer_redo and d_nb_items: bcd_launch.h
+hipError_t bcd_launch_bayes27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items, int *d_work,
+                              int num_cus, int W, int H, int b, float min_eig, float *records, float *sum, int32_t *cnt, int *d_spectral, hipStream_t st,
+                              int defer_redo, const int *d_nb_items)
+{
+    if (nb_items <= 0) return hipSuccess;
+    const Chunk27 c = chunk27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, W, H, b, records, st, d_nb_items, min_eig, sum, cnt);
+    if (c.g.words > 32) return hipErrorInvalidValue;
+    const Chain27 ch = chain27(b, bcd_bayes27_switches(), bcd_bayes27_fused_prepare_solve() != 0);
+    Chunk27 p = c; // the chunk as the prepare stage sees it
+    if (b == WB) { p.min_eig = 0.f; p.sum = nullptr; p.cnt = nullptr; } // inherited: the default radius's prepare gets no min_eig / sum / cnt (no prepare kernel reads them)
+    if (ch.finish != FINISH_REGS) p.redo = nullptr;                     // inherited: with BCD_HIP_FINISH_LDS nobody reads the redo list, and its counter is not cleared
+    hipError_t e = ch.prepare == PREPARE_FUSED ? launch_prepare_solve(p) : launch_prepare(p, ch.prepare);
+    if (e == hipSuccess && ch.prepare != PREPARE_FUSED) e = launch_solve(c);
+    // inherited: the gather prepare kernel does not know the redo list, its counter is cleared here (one fill per chunk; b = 12 with BCD_HIP_PREPARE_GATHER)
+    if (e == hipSuccess && ch.finish == FINISH_REGS && ch.prepare == PREPARE_GATHER) e = hipMemsetAsync(c.redo, 0, sizeof(int), st);
+    if (e == hipSuccess) e = launch_finish(c, ch.finish, d_spectral);
+    // deliberate (round 4): a caller that looks at the counter anyway (defer_redo) does not launch the walk at all on an empty list -- beside the persistent
+    // kernels of the other scales even the small launch sat 170-470 us on a coarse scale's stream waiting for LDS, with nothing to do
+    if (e == hipSuccess && ch.redo != REDO_NONE && !defer_redo) e = launch_redo(c, ch.redo);
+    return e;
 }
 
 // the deferred redo pass of bcd_launch_bayes27(..., defer_redo = 1): same arguments (the records still hold the chunk)
 hipError_t bcd_launch_bayes27_redo(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items,
                                    int *d_work, int num_cus, int W, int H, int b, float min_eig, float *records, float *sum, int32_t *cnt, hipStream_t st)
 {
-    if (nb_items <= 0 || (b != WB && b != 12)) return hipSuccess;
-    Geom27 g;
-    g.W = W; g.H = H; g.b = b; g.side = 2 * b + 1; g.words = (g.side * g.side + 31) / 32; g.maxS = g.side * g.side;
-    Records27 rec;
-    rec.A = records;
-    rec.V = rec.A + (size_t)nb_items * MSZ;
-    rec.C = rec.V + (size_t)nb_items * MSZ;
-    rec.aux = rec.C + (size_t)nb_items * MSZ;
-    rec.eig = rec.aux + (size_t)nb_items * AUX27;
-    int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP);
-    if (b != WB) { // the large window: the gather kernel walks the list
-        hipLaunchKernelGGL(k_bayes27<2>, dim3(std::min(nb_items, num_cus * 2)), dim3(64), bcd_bayes27_lds_bytes(b), st, colors, pixcov, mask, list, first_item, nb_items,
-                           d_work + 3 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, (const int *)redo);
-        return hipGetLastError();
-    }
-    const size_t wl2 = (size_t)W2_MEM * sizeof(float) + WMEM * sizeof(uint16_t);
-    hipLaunchKernelGGL(k_bayes27w<2>, dim3(std::min(nb_items, num_cus * 2)), dim3(64), wl2, st, colors, pixcov, mask, list, first_item, nb_items,
-                       d_work + 3 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, redo);
-    return hipGetLastError();
+    const Redo27 form = redo_kernel27(b);
+    if (nb_items <= 0 || form == REDO_NONE) return hipSuccess;
+    // inherited: the redo launchers pass no d_nb_items (the list's own counter is the number of items)
+    return launch_redo(chunk27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, W, H, b, records, st, nullptr, min_eig, sum, cnt), form);
 }
 
 // SOLVE and FINISH of a chunk whose records another prepare kernel has filled (k_prepare27t in k_bayes_temporal.hip: A = C - N, C, noise + mean, redo
@@ -2307,37 +1667,11 @@ hipError_t bcd_launch_solve_finish27(const float *colors, const float *pixcov, c
                                      hipStream_t st)
 {
     if (nb_items <= 0) return hipSuccess;
-    Geom27 g;
-    g.W = W; g.H = H; g.b = WB; g.side = 2 * WB + 1; g.words = (g.side * g.side + 31) / 32; g.maxS = g.side * g.side;
-    Records27 rec;
-    rec.A = records;
-    rec.V = rec.A + (size_t)nb_items * MSZ;
-    rec.C = rec.V + (size_t)nb_items * MSZ;
-    rec.aux = rec.C + (size_t)nb_items * MSZ;
-    rec.eig = rec.aux + (size_t)nb_items * AUX27;
-    int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP);
-    { hipError_t e = bcd_launch_jacobi27_batch(rec.A, nb_items, d_work + BCD_WORK_QUEUES * BCD_WORK_STRIDE, std::min((nb_items + 1) / 2, num_cus * 12), rec.eig, rec.V, st,
-                                               jacobi_conv2(), rec.A, nullptr, first_item); if (e != hipSuccess) return e; }
-    const size_t wl3 = WinT<WB>::F2_BYTES;
-    hipLaunchKernelGGL(k_finish27w<WB>, dim3(std::min(nb_items, num_cus * 12)), dim3(64), wl3, st, colors, mask, list, first_item, nb_items,
-                       d_work + 2 * BCD_WORK_QUEUES * BCD_WORK_STRIDE, g, min_eig, rec, sum, cnt, redo, d_spectral, (const int *)nullptr);
-    { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
-    return bcd_launch_bayes27_redo(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, W, H, WB, min_eig, records, sum, cnt, st);
-}
-
-// eigen-decomposition of n symmetric 27 x 27 matrices (28 x 28 zero-padded, row-major): persistent wavefronts, two matrices each
-hipError_t bcd_launch_jacobi27_batch(const float *A, int n, int *d_work, int blocks, float *eig, float *V, hipStream_t st, float conv2, float *Aout,
-                                     const int *d_n /* optional: the number of matrices is min(n, *d_n - first_item), read on the device */, int first_item)
-{
-    if (blocks <= 0) return hipSuccess;
-    // <padded row placement, DPP-fused row rotation>: measured on 65 536 matrices 31.3 ns per matrix without either, 31.1 with the
-    // placement alone (bank conflicts 17 % -> 0.4 % of the LDS cycles), 29.8 with the fused rotation alone (-17 % vector instructions),
-    // 29.4 with both
-    static const bool pairs = [] { const char *e = getenv("BCD_HIP_JACOBI_PAIRS"); return e && e[0] == '1'; }();
-    // (the comparison kernel keeps the plain rule: its residual is then far below what the correction of the finish kernels would notice)
-    if (pairs) hipLaunchKernelGGL((k_jacobi27_batch<true, true>), dim3(blocks), dim3(64), 0, st, A, n, d_work, eig, V, 1e-12f, Aout, d_n, first_item);
-    else hipLaunchKernelGGL(k_jacobi27_quads, dim3(blocks), dim3(64), 0, st, A, n, d_work, eig, V, conv2, Aout, d_n, first_item);
-    return hipGetLastError();
+    // inherited: nullptr for d_nb_items (the caller knows the chunk's length), and the register-resident finish whatever BCD_HIP_FINISH_LDS says
+    const Chunk27 c = chunk27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, W, H, WB, records, st, nullptr, min_eig, sum, cnt);
+    hipError_t e = launch_solve(c);
+    if (e == hipSuccess) e = launch_finish(c, FINISH_REGS, d_spectral);
+    return e == hipSuccess ? launch_redo(c, REDO_WINDOW) : e;
 }
 
 // bcd_hip_selftest_prepare_solve: PREPARE and SOLVE of one chunk (default search radius) into `records` (bcd_bayes27_record_bytes() per item, as
@@ -2346,16 +1680,10 @@ hipError_t bcd_launch_prepare_solve27(const float *colors, const float *pixcov, 
                                       int *d_work, int num_cus, int W, int H, float *records, hipStream_t st, const int *d_nb_items, int fused)
 {
     if (nb_items <= 0) return hipSuccess;
-    Geom27 g;
-    g.W = W; g.H = H; g.b = WB; g.side = 2 * WB + 1; g.words = (g.side * g.side + 31) / 32; g.maxS = g.side * g.side;
-    Records27 rec;
-    rec.A = records;
-    rec.V = rec.A + (size_t)nb_items * MSZ;
-    rec.C = rec.V + (size_t)nb_items * MSZ;
-    rec.aux = rec.C + (size_t)nb_items * MSZ;
-    rec.eig = rec.aux + (size_t)nb_items * AUX27;
-    int *redo = reinterpret_cast<int *>(rec.eig + (size_t)nb_items * KP);
-    return launch_prepare_solve27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, g, rec, redo, st, d_nb_items, fused);
+    const Chunk27 c = chunk27(colors, pixcov, mask, list, first_item, nb_items, d_work, num_cus, W, H, WB, records, st, d_nb_items);
+    if (chain27(WB, bcd_bayes27_switches(), fused != 0).prepare == PREPARE_FUSED) return launch_prepare_solve(c);
+    const hipError_t e = launch_prepare(c, PREPARE_WINDOW);
+    return e == hipSuccess ? launch_solve(c) : e;
 }
 
 hipError_t bcd_launch_count_differing_words(const void *a, const void *b, size_t words, unsigned long long *d_count, hipStream_t st)

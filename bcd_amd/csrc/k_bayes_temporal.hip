@@ -10,15 +10,12 @@
 //   k_bayes_weak_temporal  FALLBACK denoiseOnlyMainPatch (:455-481) with the average over the colour patches of all members of all frames, added to the main
 //                                   patch only
 // Members are gathered from global memory (the gather form of k_bayes27<1>): a member's frame is part of its code.
-#include "bcd_common.h"
+// The record, the work queues and noise_idx are those of the chain: bayes27_record.h.
+#include "bcd_launch.h"
+#include "bayes27_record.h"
 #include <algorithm>
 
-size_t bcd_bayes27_record_bytes(); // (k_bayes27.hip)
-
 namespace {
-
-constexpr int K = 27, KP = 28, LD = 29, JLD = 28, P = 9, MSZ = KP * KP, CHUNK = MSZ / K, AUX27 = 96; // the record geometry of k_bayes27.hip
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 // a frame's pointers by index: a chain of selects on the by-value table (a wave-uniform index keeps them on the scalar unit)
 __device__ inline const float *frame_col(const BcdFrameTable &t, int f)
@@ -43,25 +40,6 @@ __device__ inline const uint32_t *frame_mask(const BcdFrameTable &t, int f)
     return r;
 }
 
-// work distribution of the persistent kernels: the queues of k_bayes27.hip (item = queue + 8 k; a wavefront starts on the queue of its workgroup and
-// moves on when one is empty)
-struct WorkCursor { int q, tried; };
-__device__ inline int work_next(int *work, int nb_items, int lane, WorkCursor &c)
-{
-    while (c.tried < BCD_WORK_QUEUES) {
-        int k = 0;
-        if (lane == 0) k = atomicAdd(work + c.q * BCD_WORK_STRIDE, 1);
-        k = __builtin_amdgcn_readfirstlane(k);
-        const int item = c.q + BCD_WORK_QUEUES * k;
-        if (item < nb_items) return item;
-        c.q = (c.q + 1) % BCD_WORK_QUEUES;
-        ++c.tried;
-    }
-    return -1;
-}
-
-__device__ inline int noise_idx(int i, int j) { return i == j ? i : (i + j == 1 ? 5 : (i + j == 2 ? 4 : 3)); } // 3x3 symmetric block from xx,yy,zz,yz,xz,xy
-
 // member code: frame << 12 | (dl + B) << 8 | (dc + B)
 __device__ inline int code_frame(int code) { return code >> 12; }
 template <int B> __device__ inline int code_pixel(int code, int p, int W) { return p + (((code >> 8) & 15) - B) * W + ((code & 255) - B); }
@@ -83,7 +61,7 @@ __global__ __launch_bounds__(64) void k_prepare27t(BcdFrameTable t, const int32_
     const int lane = threadIdx.x;
     if (blockIdx.x == 0 && lane == 0) rec.redo[0] = 0; // (the chunk's redo list is empty: the finish kernel appends to it two launches later)
 
-    WorkCursor cursor{ (int)(blockIdx.x % BCD_WORK_QUEUES), 0 };
+    WorkCursor cursor = work_begin();
     for (;;) {
         const int slot = work_next(work, nb_items, lane, cursor);
         if (slot < 0) break;
@@ -235,19 +213,16 @@ __global__ __launch_bounds__(64) void k_bayes_weak_temporal(BcdFrameTable t, con
 } // namespace
 
 // PREPARE of items [first_item, first_item + nb_items) of `list` into `records` (nb_items records as bcd_launch_bayes27 lays them out: A | V | C | aux | eig |
-// redo list); d_work: the first BCD_WORK_QUEUES * BCD_WORK_STRIDE ints of the chunk's zeroed work queues
+// redo list); d_work: the chunk's zeroed work queues, of which the kernel takes the prepare group
 hipError_t bcd_launch_prepare27t(const BcdFrameTable &t, const int32_t *list, int first_item, int nb_items, int *d_work, int num_cus, int W, int b,
                                  float *records, hipStream_t st)
 {
     if (nb_items <= 0) return hipSuccess;
     if (b != 6 || t.n < 1 || t.n > BCD_MAX_NEIGHBOURS + 1) return hipErrorInvalidValue;
-    if (bcd_bayes27_record_bytes() != (size_t)(3 * MSZ + AUX27 + KP) * sizeof(float) + 2 * sizeof(int)) return hipErrorInvalidValue; // (the layout below)
-    Records27t rec;
-    rec.A = records;
-    rec.C = rec.A + (size_t)nb_items * MSZ * 2;
-    rec.aux = rec.C + (size_t)nb_items * MSZ;
-    rec.redo = reinterpret_cast<int *>(rec.aux + (size_t)nb_items * AUX27 + (size_t)nb_items * KP);
-    hipLaunchKernelGGL(k_prepare27t<6>, dim3(std::min(nb_items, num_cus * 16)), dim3(64), 0, st, t, list, first_item, nb_items, d_work, W, rec);
+    const Chunk27Records c = carve27(records, nb_items);
+    const Records27t rec{ c.rec.A, c.rec.C, c.rec.aux, c.redo };
+    hipLaunchKernelGGL(k_prepare27t<6>, dim3(std::min(nb_items, num_cus * 16)), dim3(64), 0, st, t, list, first_item, nb_items, work_group(d_work, WORK_PREPARE), W,
+                       rec);
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-"""Schedule of the batched 27 x 27 Jacobi solver (k_bayes27.hip, k_jacobi27_batch): a resolvable 2-(28, 4, 1) design -- 63 blocks of 4 on
+"""Schedule of the batched 27 x 27 Jacobi solver (k_jacobi27_quads in k_jacobi27.hip; the tables JSX / JSY / JPLACE / JIDLE_ROW live in
+bayes27_jacobi.h, next to the device functions that use them): a resolvable 2-(28, 4, 1) design -- 63 blocks of 4 on
 28 points, every pair of points in exactly one block, the blocks split into 9 parallel classes of 7 -- so that one sweep is 9 "super-rounds"
 in each of which the 28 slots are 7 quads (4 neighbouring lanes) and all 6 pairs of a quad are rotated before the rows move again.
 
