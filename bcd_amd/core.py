@@ -266,6 +266,26 @@ def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, mi
     return rc != 0, out
 
 
+def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, drop_layers=0, after_clear=False):
+    """bcd::Denoiser / bcd::MultiscaleDenoiser with colour layers beside neighbouring frames (addLayer, addNeighbourFrame, addNeighbourFrameLayer): layers is a
+    list of (colours, covariances), [0] going through DenoiserInputs; neighbours a list of (ns, hist, [(colours, covariances)]) with the same layers.
+    drop_layers: the last neighbour is given that many layers fewer (denoise() must refuse).  after_clear: clearNeighbourFrames() and a second denoise()
+    follow, whose results replace the first.  Returns (ok, [output per layer])"""
+    H, W, D = hist.shape
+    L, F = len(layers), len(neighbours)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    cols, covs = f32(np.stack([c for c, _ in layers])), f32(np.stack([v for _, v in layers]))
+    nb_cols = f32(np.stack([c for _, _, lay in neighbours for c, _ in lay])) if F else np.zeros((1, H, W, 3), np.float32)
+    nb_covs = f32(np.stack([v for _, _, lay in neighbours for _, v in lay])) if F else np.zeros((1, H, W, 6), np.float32)
+    nb_ns = f32(np.stack([np.asarray(n, np.float32).reshape(H, W, 1) for n, _, _ in neighbours])) if F else np.zeros((1, H, W, 1), np.float32)
+    nb_hists = f32(np.stack([h for _, h, _ in neighbours])) if F else np.zeros((1, H, W, D), np.float32)
+    outs = np.zeros((L, H, W, 3), np.float32)
+    rc = lib().bcdcore_denoise_temporal_layers(_fp(cols), _fp(covs), _fp(f32(ns)), _fp(f32(hist)), _fp(nb_cols), _fp(nb_covs), _fp(nb_ns), _fp(nb_hists), F, L, W, H, D,
+                                               int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed),
+                                               int(drop_layers), 1 if after_clear else 0, _fp(outs))
+    return rc != 0, [outs[k] for k in range(L)]
+
+
 def denoise_moments(layers, ns, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, zero_bad=False, prefilter_factor=0.0,
                     prefilter_layers=False, var_floor=1e-8, devices=None):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with setMomentSelection(true, var_floor): no histogram image; layers[0] = (colours, covariances) is the

@@ -122,13 +122,17 @@ int estimate_cus(const bcd_hip_ctx *ctx, const Work &wk)
 // ... the same share as a percentage of the chip (bcd_hip_scale_stats::cu_share)
 int estimate_share_pct(const bcd_hip_ctx *ctx, const Work &wk) { return ctx->cu_share_pct * (&wk != &ctx->main ? ctx->coarse_share : 100) / 100; }
 
-// what follows on the workspace's side stream comes after what the scale's own stream holds so far
+} // namespace
+
+// what follows on the workspace's side stream comes after what the scale's own stream holds so far (shared with bcd_temporal_layers.hip)
 int fork_aux(bcd_hip_ctx *ctx, Work &wk)
 {
     HIPCHK(ctx, hipEventRecord(wk.ev_fork, wk.stream));
     HIPCHK(ctx, hipStreamWaitEvent(wk.aux, wk.ev_fork, 0));
     return BCD_HIP_OK;
 }
+
+namespace {
 
 // did the last similarity() pass on this workspace leave the range flag raised or overflow its borderline list?  (valid after the
 // stream has been synchronised; the caller then repeats the pass with exact_mode = 1)

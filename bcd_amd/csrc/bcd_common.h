@@ -115,6 +115,20 @@ struct BcdFrameTable {
     int n; // frames in use, 1 .. BCD_MAX_NEIGHBOURS + 1
 };
 
+// ... and the colour layers of those frames (bcd_hip_denoise_temporal_layers): every frame brings the same layers in the same order, the masks are shared
+// by the layers.  k_bayes_weak_temporal_layers serves BCD_TEMPORAL_GROUP layers per wavefront; entries beyond `layers` repeat a valid layer of the same
+// frame (the launcher fills them), so a group's idle slots read memory that exists and flush nothing.
+// G = 4 with five frames compiles to 103 SGPRs (20 group pointers, 4 sums, 5 masks held in scalar registers), just under the 104 of the register file
+// that are addressable: a larger group or more neighbours would spill scalar registers -- re-read --save-temps before raising either.
+#define BCD_TEMPORAL_GROUP 4
+static_assert(BCD_TEMPORAL_GROUP <= 4 && BCD_MAX_NEIGHBOURS <= 4, "k_bayes_weak_temporal_layers keeps (BCD_MAX_NEIGHBOURS + 1) x BCD_TEMPORAL_GROUP pointers in SGPRs: see above");
+struct BcdFrameLayerTable {
+    const float *col[BCD_MAX_NEIGHBOURS + 1][BCD_MAX_LAYERS];
+    const uint32_t *mask[BCD_MAX_NEIGHBOURS + 1];
+    float *sum[BCD_MAX_LAYERS];
+    int n, layers; // frames in use, layers in use
+};
+
 // ---- spike prefilter through a source map (k_spike.hip) ---------------------------------------------------
 // One launch of k_spike_apply gathers up to BCD_SPIKE_MAX_IMAGES images of one depth; the image is blockIdx.y, the pointers travel by value.
 #define BCD_SPIKE_MAX_IMAGES 32

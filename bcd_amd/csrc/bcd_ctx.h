@@ -199,6 +199,13 @@ struct bcd_hip_ctx {
         DevBuf mask[BCD_MAX_NEIGHBOURS + 1];               // [1..]: the cross masks of the scale in progress
         DevBuf count_nb;                                   // |S_f| of the neighbour in progress
         DevBuf host[BCD_MAX_NEIGHBOURS + 1][4], host_out;  // host-buffer entry point: device copies
+        // bcd_hip_denoise_temporal_layers (bcd_temporal_layers.hip): the colour layers of every frame, one slice per layer in each buffer.  The sample counts
+        // and histograms of the levels 1.. are pyr[f][s][1] and [2] above
+        DevBuf lay_pyr[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES][2]; // levels 1.. of every frame: colours, covariances of its layers
+        DevBuf lay_out[MAX_SCALES];                            // the layers' outputs of the levels 1..
+        DevBuf lay_pixcov[BCD_MAX_NEIGHBOURS + 1];             // per-pixel covariances of every frame's layers at the scale in progress
+        DevBuf lay_sum, lay_tmp_lo;                            // the layers' sums of the scale in progress, the merge's scratch
+        DevBuf lay_host[BCD_MAX_NEIGHBOURS + 1][2], lay_host_out; // host-buffer entry point: device copies of the layers' colours, covariances, outputs
     } temporal;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
@@ -281,6 +288,7 @@ float stage_ms(Work &wk, int a, int b);
 int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, const float *d_hist, const float *d_cov, int W, int H, int D, int nb_scales,
                  const bcd_hip_params *prm, float *d_out, const LayerView *lv0);
 int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream);
+int fork_aux(bcd_hip_ctx *ctx, Work &wk); // the side stream waits for what the workspace's stream holds so far
 int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
                       int nb_layers, bool no_hist = false);
 int denoise_layers_checked(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
@@ -296,6 +304,8 @@ inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
 
 // ---- defined in bcd_temporal.hip
 void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
+// the T / C planes of every displacement between the frame and one neighbour, in the main workspace (whose own planes they overwrite)
+int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b);
 
 // ---- defined in bcd_selection.hip
 // one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is

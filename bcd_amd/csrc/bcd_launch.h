@@ -34,6 +34,8 @@ hipError_t bcd_launch_prepare27t(const BcdFrameTable &t, const int32_t *list, in
                                  hipStream_t st);
 hipError_t bcd_launch_bayes_weak_temporal(const BcdFrameTable &t, const int32_t *list, const int32_t *d_nlist, int blocks, int W, int b, float *sum, int32_t *cnt,
                                           hipStream_t st);
+hipError_t bcd_launch_bayes_weak_temporal_layers(const BcdFrameLayerTable &t, const int32_t *list, const int32_t *d_nlist, int blocks, int W, int b, int32_t *cnt,
+                                                 hipStream_t st);
 hipError_t bcd_launch_solve_finish27(const float *colors, const float *pixcov, const uint32_t *mask, const int32_t *list, int first_item, int nb_items, int *d_work,
                                      int num_cus, int W, int H, float min_eig, float *records, float *sum, int32_t *cnt, int *d_spectral, hipStream_t st);
 

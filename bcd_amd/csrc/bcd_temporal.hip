@@ -11,17 +11,8 @@
 
 static_assert(BCD_MAX_NEIGHBOURS == BCD_HIP_MAX_NEIGHBOURS, "the frame table of the kernels holds what the C ABI admits");
 
-namespace {
-
-// the refusals the stage calls share: the geometry rules of bcd_hip_similarity_masks
-int check_cross_stage(bcd_hip_ctx *ctx, int W, int H, int D, int w, int b)
-{
-    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
-    return check_params(ctx, W, H, D, &p);
-}
-
 // the T / C planes of every displacement between the frame and one neighbour, in the main workspace
-int cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b)
+int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b)
 {
     const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
     RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
@@ -29,6 +20,15 @@ int cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d
     wk.planes.ready = false; // (the workspace's planes are overwritten)
     HIPCHK(ctx, bcd_launch_pairdist_cross(d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
     return BCD_HIP_OK;
+}
+
+namespace {
+
+// the refusals the stage calls share: the geometry rules of bcd_hip_similarity_masks
+int check_cross_stage(bcd_hip_ctx *ctx, int W, int H, int D, int w, int b)
+{
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    return check_params(ctx, W, H, D, &p);
 }
 
 // The estimate chain over the members of several frames (patch radius 1, search radius 6): the lists of processed pixels from the states and the TOTAL
@@ -119,7 +119,7 @@ int bcd_hip_similarity_masks_cross(bcd_hip_ctx *ctx, const float *d_hist, const 
     RCCHK(check_cross_stage(ctx, W, H, D, w, b));
     DEVICE_GUARD(ctx);
     Work &wk = ctx->main;
-    RCCHK(cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
+    RCCHK(temporal_cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
     HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask_nb, d_count_nb, wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     return BCD_HIP_OK;
@@ -136,7 +136,7 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_hist, const 
     Work &wk = ctx->main;
     const int n = (2 * b + 1) * (2 * b + 1);
     RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
-    RCCHK(cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
+    RCCHK(temporal_cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
     HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
     HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
@@ -161,6 +161,11 @@ void temporal_free(bcd_hip_ctx *ctx)
     if (t.count_nb.p) (void)hipFree(t.count_nb.p);
     for (auto &frame : t.host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
     if (t.host_out.p) (void)hipFree(t.host_out.p);
+    for (auto &frame : t.lay_pyr) for (auto &level : frame) for (DevBuf &b : level) if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : t.lay_out) if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : t.lay_pixcov) if (b.p) (void)hipFree(b.p);
+    for (DevBuf *b : { &t.lay_sum, &t.lay_tmp_lo, &t.lay_host_out }) if (b->p) (void)hipFree(b->p);
+    for (auto &frame : t.lay_host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
 }
 
 namespace {
@@ -202,7 +207,7 @@ int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, in
         t.col[f] = frames[f].col; t.pixcov[f] = (const float *)tp.pixcov[f].p;
         t.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : (const uint32_t *)tp.mask[f].p;
         if (f == 0) continue;
-        RCCHK(cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
+        RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
         HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
         HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
     }

@@ -1,0 +1,406 @@
+// bcd_temporal_layers.hip -- the colour layers of a frame denoised with similar patches from its neighbour frames ("Layers"):
+// bcd_hip_denoise_temporal_layers[_host] and the stage entry point bcd_hip_bayes_accumulate_temporal_layers.  The selection of a scale -- the in-frame set,
+// the cross sets, the total |S|, the marking, the lists -- reads sample counts and histograms only and is computed once, by the steps of temporal_scale
+// (bcd_temporal.hip); the estimate stage runs per layer: one launch of k_bayes_weak_temporal_layers serves the fallback pixels of every layer on the side
+// stream, the chain of full estimates (k_prepare27t, then the unchanged solver and finish kernels) runs once per layer over the same lists, records and
+// work queues.  The count image is filled once: by the first group of the fallback kernel and by the first layer's finish kernels.
+// Every buffer of the call lives in ctx->temporal (grow-only): the workspace's lay_* slices, which bcd_hip_denoise_layers owns, are not touched.
+#include "bcd_ctx.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+constexpr int NF = BCD_MAX_NEIGHBOURS + 1, ML = BCD_MAX_LAYERS;
+
+// one scale's estimate inputs: [f][k] = frame f (0: the frame itself), layer k
+struct LayerFrames {
+    int nf = 0, L = 0;
+    const float *col[NF][ML], *pixcov[NF][ML];
+    const uint32_t *mask[NF];
+};
+
+bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
+// the part of bayes_temporal_layers behind the fork: the wait for the list lengths, then the full estimates layer by layer -- records and work queues are
+// reused, the redo counter runs on and its total is copied out behind each layer.  The side stream is NOT joined here.
+int layer_chains(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, int W, int H, int b, float min_eig, float *const *d_sum, int32_t *d_count, int cus)
+{
+    constexpr int CHUNK_MAX = 1 << 18; // (the chunk of bayes(): records in flight at a time)
+    const int64_t npix = (int64_t)W * H;
+    Counters::Lists *d_c = &wk.d_counters()->lists;
+    Counters *h = wk.h_counters;
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    const int n_strong = h->lists.n_strong;
+    if (n_strong < 0 || n_strong > npix) return bad(ctx, "temporal estimate: the list exceeds the frame");
+    if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, bcd_bayes27_record_bytes() * (size_t)std::min(n_strong, CHUNK_MAX)));
+    for (int k = 0; k < lf.L; ++k) {
+        BcdFrameTable t = {};
+        t.n = lf.nf;
+        for (int f = 0; f < lf.nf; ++f) { t.col[f] = lf.col[f][k]; t.pixcov[f] = lf.pixcov[f][k]; t.mask[f] = lf.mask[f]; }
+        for (int first = 0; first < n_strong; first += CHUNK_MAX) {
+            const int n = std::min(CHUNK_MAX, n_strong - first);
+            HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream)); // the work queues of the four kernels
+            HIPCHK(ctx, bcd_launch_prepare27t(t, (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, b, (float *)wk.gscratch.p, wk.stream));
+            HIPCHK(ctx, bcd_launch_solve_finish27(t.col[0], t.pixcov[0], t.mask[0], (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, H, min_eig,
+                                                  (float *)wk.gscratch.p, d_sum[k], k == 0 ? d_count : nullptr, &d_c->spectral, wk.stream));
+        }
+        HIPCHK(ctx, hipMemcpyAsync(&h->layer_redo_total[k], &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
+    }
+    return BCD_HIP_OK;
+}
+
+// bayes_temporal (bcd_temporal.hip) for L layers on one selection: the lists once, the layered fallback kernel on the side stream, per layer and chunk the
+// temporal prepare kernel on that layer's images of every frame followed by the solver and finish kernels on its frame-0 colours, the in-frame masks and
+// its sum image.  d_count goes to the fallback kernel and to the first layer's chain only.  redo[k]: the items of layer k that took the redo list; their sum
+// is left in wk.h_counters->lists.spectral beside the list lengths and the sum of |S|.  Synchronises the stream at its end.  Whatever fails behind the fork,
+// nothing is left running on the side stream when the call returns: the accumulators may be the caller's.
+int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
+                          float *const *d_sum, int32_t *d_count, int32_t *redo)
+{
+    constexpr int K = 27;
+    const int64_t npix = (int64_t)W * H;
+    const int L = lf.L;
+    wk.redo.pending = false;
+    RCCHK(ensure(ctx, wk.strong, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.weak, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
+    Counters::Lists *d_c = &wk.d_counters()->lists, *h_c = &wk.h_counters->lists;
+    Counters *h = wk.h_counters;
+    touch(wk); // (the counters and work queues are cleared here, whatever k_scale_begin left)
+    h_c->spectral = 0;
+    HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
+    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim_total, 0, npix, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, &d_c->n_strong, wk.stream, nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(h_c, d_c, offsetof(Counters::Lists, generic_work), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
+    const int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
+    // ---- the fallback pixels of every layer: one launch on the side stream, behind the lists
+    BcdFrameLayerTable t = {};
+    t.n = lf.nf; t.layers = L;
+    for (int f = 0; f < lf.nf; ++f) {
+        t.mask[f] = lf.mask[f];
+        for (int k = 0; k < L; ++k) t.col[f][k] = lf.col[f][k];
+    }
+    for (int k = 0; k < L; ++k) t.sum[k] = d_sum[k];
+    RCCHK(fork_aux(ctx, wk));
+    int rc = BCD_HIP_OK;
+    {
+        const hipError_t e = bcd_launch_bayes_weak_temporal_layers(t, (const int32_t *)wk.weak.p, &d_c->n_weak,
+                                                                   (int)std::min<int64_t>(std::max<int64_t>(1, npix / 7), (int64_t)cus * 32), W, b, d_count, wk.aux);
+        if (e != hipSuccess) { set_err(ctx, std::string("bcd_launch_bayes_weak_temporal_layers: ") + hipGetErrorString(e)); rc = BCD_HIP_EDEVICE; }
+    }
+    // ---- the full estimates on the workspace's own stream, then the join
+    if (rc == BCD_HIP_OK) rc = layer_chains(ctx, wk, lf, W, H, b, min_eig, d_sum, d_count, cus);
+    if (rc != BCD_HIP_OK) {
+        (void)hipStreamSynchronize(wk.aux); // (the fallback kernel adds into the accumulators: it ends before the error is reported)
+        (void)hipStreamSynchronize(wk.stream);
+        return rc;
+    }
+    HIPCHK(ctx, hipEventRecord(wk.ev_join, wk.aux));
+    HIPCHK(ctx, hipStreamWaitEvent(wk.stream, wk.ev_join, 0));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    for (int k = 0; k < L; ++k) redo[k] = h->layer_redo_total[k] - (k == 0 ? 0 : h->layer_redo_total[k - 1]);
+    h_c->spectral = h->layer_redo_total[L - 1]; // the scale's figure: the sum over the layers
+    return BCD_HIP_OK;
+}
+
+// one frame at one pyramid level: its sample counts, histograms and the colours and covariances of its layers
+struct LevelFrame {
+    const float *ns, *hist;
+    const float *col[ML], *cov[ML];
+};
+
+// one scale, frames[0] the frame itself at this level: the steps of temporal_scale with the estimate stage per layer
+int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, int L, int W, int H, int D, const bcd_hip_params *prm, int scale, float *const *d_out)
+{
+    Work &wk = ctx->main;
+    auto &tp = ctx->temporal;
+    const int w = prm->patch_radius, b = prm->search_radius;
+    const float tau = prm->hist_dist_threshold;
+    const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+    RCCHK(ensure(ctx, wk.mask, npix * words * sizeof(uint32_t)));
+    RCCHK(ensure(ctx, wk.nsim, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.state, npix));
+    RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, tp.count_nb, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, tp.lay_sum, (size_t)L * npix * 3 * sizeof(float)));
+    for (int f = 0; f < nf; ++f) {
+        RCCHK(ensure(ctx, tp.lay_pixcov[f], (size_t)L * npix * 6 * sizeof(float)));
+        if (f > 0) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
+    }
+    bcd_hip_scale_stats &st = ctx->stats[scale];
+    memset(&st, 0, sizeof(st));
+    st.width = W; st.height = H;
+    st.main_pixels = (int64_t)std::max(0, W - 2 * w) * std::max(0, H - 2 * w);
+    const bool prof = ctx->profiling;
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
+    // S_0, then per frame the per-pixel covariances of its layers (one launch; it also clears the layers' sums) and, for a neighbour, its cross pass
+    RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
+    int32_t path = 0, borderline = 0, capacity = 0;
+    RCCHK(bcd_hip_similarity_last_path(ctx, &path, &borderline, &capacity));
+    LayerFrames lf;
+    lf.nf = nf; lf.L = L;
+    float *sum[ML];
+    for (int k = 0; k < L; ++k) sum[k] = (float *)tp.lay_sum.p + (size_t)k * npix * 3;
+    for (int f = 0; f < nf; ++f) {
+        BcdLayerTable t = {};
+        for (int k = 0; k < L; ++k) t.a[k] = frames[f].cov[k];
+        HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, L, frames[f].ns, (int64_t)npix, (float *)tp.lay_pixcov[f].p, (float *)tp.lay_sum.p, wk.stream));
+        for (int k = 0; k < L; ++k) { lf.col[f][k] = frames[f].col[k]; lf.pixcov[f][k] = (const float *)tp.lay_pixcov[f].p + (size_t)k * npix * 6; }
+        lf.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : (const uint32_t *)tp.mask[f].p;
+        if (f == 0) continue;
+        RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
+        HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
+        HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
+    }
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
+    RCCHK(bcd_hip_active_set(ctx, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, W, H, w, b, 0, H, prm->marked_skip_probability, prm->use_random_pixel_order,
+                             bcd_hip_scale_seed(prm->order_seed, scale), (uint8_t *)wk.state.p, &st.active_rounds));
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[2], wk.stream));
+    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
+    int32_t redo[ML] = {};
+    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, prm->min_eigen_value, sum, (int32_t *)wk.cnt.p, redo));
+    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
+    {
+        BcdLayerTable t = {};
+        for (int k = 0; k < L; ++k) { t.a[k] = sum[k]; t.o[k] = d_out[k]; }
+        HIPCHK(ctx, bcd_launch_layers_finalize(t, L, (const int32_t *)wk.cnt.p, (int64_t)npix, wk.stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    const Counters::Lists &h = wk.h_counters->lists;
+    st.processed = (int64_t)h.n_strong + h.n_weak; st.fallback = h.n_weak; st.similar_total = h.sim_total; // (the sum of the TOTAL |S|)
+    st.similarity_path = path; st.borderline_pairs = borderline;                                          // (those of the in-frame pass)
+    st.cu_share = ctx->cu_share_pct;
+    st.spectral_inverses = h.spectral;                                                                    // (the sum over the layers)
+    for (int k = 0; k < L; ++k) ctx->layer_spectral[scale][k] = redo[k];
+    if (prof) {
+        st.ms_similarity = stage_ms(wk, 0, 1); // (includes the cross passes)
+        st.ms_active = stage_ms(wk, 1, 2);
+        st.ms_bayes = stage_ms(wk, 2, 3);
+        st.ms_total = stage_ms(wk, 0, 3);
+    }
+    return BCD_HIP_OK;
+}
+
+// the refusals of the two frame calls, before any device work
+int check_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_hip_frame_layers *nb, int n, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+               const bcd_hip_layer *layers, int L)
+{
+    if (n < 0 || n > BCD_HIP_MAX_NEIGHBOURS) return bad(ctx, "the number of neighbour frames must be between 0 and 4 (BCD_HIP_MAX_NEIGHBOURS)");
+    RCCHK(check_layers_call(ctx, ns, hist, W, H, D, nb_scales, prm, layers, L)); // (null images, the number of layers, the parameters, the scales, the frame's own overlaps)
+    if (n > 0 && !nb) return bad(ctx, "null neighbour list");
+    for (int f = 0; f < n; ++f) {
+        if (!nb[f].d_nsamples || !nb[f].d_histograms) return bad(ctx, "null image pointer in a neighbour frame");
+        if (!nb[f].layers) return bad(ctx, "null layer list in a neighbour frame");
+        if (nb[f].reserved) return bad(ctx, "the reserved pointer of a neighbour frame must be NULL");
+        for (int k = 0; k < L; ++k)
+            if (!nb[f].layers[k].d_colors || !nb[f].layers[k].d_covariances) return bad(ctx, "null image pointer in a layer of a neighbour frame");
+    }
+    if (n > 0 && (prm->patch_radius != 1 || prm->search_radius != 6)) {
+        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    const size_t npix = (size_t)W * H, f4 = sizeof(float), no = npix * 3 * f4;
+    for (int k = 0; k < L; ++k) {
+        const void *out = layers[k].d_out;
+        for (int f = 0; f < n; ++f) {
+            if (overlap(out, no, nb[f].d_nsamples, npix * f4) || overlap(out, no, nb[f].d_histograms, npix * D * f4))
+                return bad(ctx, "a layer's output overlaps an image of a neighbour frame");
+            for (int j = 0; j < L; ++j)
+                if (overlap(out, no, nb[f].layers[j].d_colors, npix * 3 * f4) || overlap(out, no, nb[f].layers[j].d_covariances, npix * 6 * f4))
+                    return bad(ctx, "a layer's output overlaps an image of a neighbour frame");
+        }
+    }
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bcd_hip_bayes_accumulate_temporal_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_frame_layers *frames, int nb_frames, int nb_layers, const int32_t *d_nsim_total,
+                                             const uint8_t *d_state, int W, int H, int w, int b, float min_eig, float *const *d_sum, int32_t *d_count, int32_t *h_redo)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    // ---- everything is checked before any device work
+    if (!frames) return bad(ctx, "null frame list");
+    if (nb_frames < 1 || nb_frames > BCD_HIP_MAX_NEIGHBOURS + 1) return bad(ctx, "the number of frames must be between 1 and 5 (the frame and up to BCD_HIP_MAX_NEIGHBOURS neighbours)");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    if (!d_nsim_total || !d_state || !d_sum || !d_count || !h_redo) return bad(ctx, "null image pointer");
+    for (int k = 0; k < nb_layers; ++k) if (!d_sum[k]) return bad(ctx, "null sum image of a layer");
+    for (int f = 0; f < nb_frames; ++f) {
+        if (!frames[f].d_colors || !frames[f].d_pixel_cov || !frames[f].d_mask) return bad(ctx, "null image pointer in a frame");
+        for (int k = 0; k < nb_layers; ++k) if (!frames[f].d_colors[k] || !frames[f].d_pixel_cov[k]) return bad(ctx, "null image pointer in a layer of a frame");
+    }
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = w; p.search_radius = b;
+    RCCHK(check_params(ctx, W, H, 1, &p));
+    if (w != 1 || b != 6) { set_err(ctx, "the estimate over several frames supports patch radius 1 and search radius 6"); return BCD_HIP_EUNSUPPORTED; }
+    {
+        const size_t npix = (size_t)W * H, f4 = sizeof(float), ns = npix * 3 * f4, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+        if (overlap(d_count, npix * 4, d_nsim_total, npix * 4) || overlap(d_count, npix * 4, d_state, npix)) return bad(ctx, "the accumulators overlap each other or the selection");
+        for (int k = 0; k < nb_layers; ++k) {
+            const void *s = d_sum[k];
+            if (overlap(s, ns, d_count, npix * 4) || overlap(s, ns, d_nsim_total, npix * 4) || overlap(s, ns, d_state, npix)) return bad(ctx, "the accumulators overlap each other or the selection");
+            for (int j = 0; j < k; ++j) if (overlap(s, ns, d_sum[j], ns)) return bad(ctx, "two layers share (part of) a sum image");
+        }
+        for (int f = 0; f < nb_frames; ++f) {
+            if (overlap(d_count, npix * 4, frames[f].d_mask, npix * words * 4)) return bad(ctx, "an accumulator overlaps an input image");
+            for (int j = 0; j < nb_layers; ++j) {
+                if (overlap(d_count, npix * 4, frames[f].d_colors[j], ns) || overlap(d_count, npix * 4, frames[f].d_pixel_cov[j], npix * 6 * f4)) return bad(ctx, "an accumulator overlaps an input image");
+                for (int k = 0; k < nb_layers; ++k)
+                    if (overlap(d_sum[k], ns, frames[f].d_colors[j], ns) || overlap(d_sum[k], ns, frames[f].d_pixel_cov[j], npix * 6 * f4) ||
+                        overlap(d_sum[k], ns, frames[f].d_mask, npix * words * 4))
+                        return bad(ctx, "an accumulator overlaps an input image");
+            }
+        }
+    }
+    DEVICE_GUARD(ctx);
+    LayerFrames lf;
+    lf.nf = nb_frames; lf.L = nb_layers;
+    for (int f = 0; f < nb_frames; ++f) {
+        lf.mask[f] = frames[f].d_mask;
+        for (int k = 0; k < nb_layers; ++k) { lf.col[f][k] = frames[f].d_colors[k]; lf.pixcov[f][k] = frames[f].d_pixel_cov[k]; }
+    }
+    return bayes_temporal_layers(ctx, ctx->main, lf, d_nsim_total, d_state, W, H, b, min_eig, d_sum, d_count, h_redo);
+}
+
+int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
+                                    int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_call(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    if (nb_neighbours == 0) return bcd_hip_denoise_layers(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
+    if (nb_layers == 1) {
+        bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
+        for (int f = 0; f < nb_neighbours; ++f)
+            nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
+        RCCHK(bcd_hip_denoise_temporal(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
+        memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+        for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
+        ctx->layer_count = 1;
+        return BCD_HIP_OK;
+    }
+    DEVICE_GUARD(ctx);
+    const int nf = nb_neighbours + 1, S = nb_scales, L = nb_layers;
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+    ctx->layer_count = 0;
+    // ---- the pyramids of every frame: sample counts and histograms summed, the layers' colours averaged and their covariances weighted by the frame's counts
+    std::vector<LevelFrame> lv((size_t)S * nf);
+    std::vector<float *> outs((size_t)S * L);
+    int ws[MAX_SCALES], hs[MAX_SCALES];
+    ws[0] = W; hs[0] = H;
+    for (int f = 0; f < nf; ++f) {
+        LevelFrame &l = lv[f];
+        l.ns = f ? neighbours[f - 1].d_nsamples : d_ns; l.hist = f ? neighbours[f - 1].d_histograms : d_hist;
+        for (int k = 0; k < L; ++k) {
+            l.col[k] = f ? neighbours[f - 1].layers[k].d_colors : layers[k].d_colors;
+            l.cov[k] = f ? neighbours[f - 1].layers[k].d_covariances : layers[k].d_covariances;
+        }
+    }
+    for (int k = 0; k < L; ++k) outs[k] = layers[k].d_out;
+    for (int s = 1; s < S; ++s) {
+        ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
+        const size_t np = (size_t)ws[s] * hs[s];
+        RCCHK(ensure(ctx, tp.lay_out[s], (size_t)L * np * 3 * sizeof(float)));
+        for (int k = 0; k < L; ++k) outs[(size_t)s * L + k] = (float *)tp.lay_out[s].p + (size_t)k * np * 3;
+        for (int f = 0; f < nf; ++f) {
+            DevBuf(&l)[4] = tp.pyr[f][s];
+            DevBuf(&ll)[2] = tp.lay_pyr[f][s];
+            RCCHK(ensure(ctx, l[1], np * sizeof(float)));
+            RCCHK(ensure(ctx, l[2], np * D * sizeof(float)));
+            RCCHK(ensure(ctx, ll[0], (size_t)L * np * 3 * sizeof(float)));
+            RCCHK(ensure(ctx, ll[1], (size_t)L * np * 6 * sizeof(float)));
+            const LevelFrame &fine = lv[(size_t)(s - 1) * nf + f];
+            LevelFrame &coarse = lv[(size_t)s * nf + f];
+            coarse.ns = (const float *)l[1].p; coarse.hist = (const float *)l[2].p;
+            HIPCHK(ctx, bcd_launch_downscale(0, fine.ns, ws[s - 1], hs[s - 1], 1, (float *)l[1].p, st));
+            HIPCHK(ctx, bcd_launch_downscale(0, fine.hist, ws[s - 1], hs[s - 1], D, (float *)l[2].p, st));
+            BcdLayerTable t = {};
+            for (int k = 0; k < L; ++k) { coarse.col[k] = (const float *)ll[0].p + (size_t)k * np * 3; t.a[k] = fine.col[k]; t.o[k] = (float *)ll[0].p + (size_t)k * np * 3; }
+            HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, ws[s - 1], hs[s - 1], st));
+            for (int k = 0; k < L; ++k) { coarse.cov[k] = (const float *)ll[1].p + (size_t)k * np * 6; t.a[k] = fine.cov[k]; t.o[k] = (float *)ll[1].p + (size_t)k * np * 6; }
+            HIPCHK(ctx, bcd_launch_layers_downscale_cov(t, L, fine.ns, ws[s - 1], hs[s - 1], st));
+        }
+    }
+    for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs, one pair of launches for all layers (as merge_layers_on)
+        float *const *out = &outs[(size_t)s * L];
+        RCCHK(temporal_layers_scale(ctx, &lv[(size_t)s * nf], nf, L, ws[s], hs[s], D, prm, s, out));
+        if (s < S - 1) {
+            const int w2 = ws[s] / 2, h2 = hs[s] / 2;
+            const size_t slice = (size_t)w2 * h2 * 3;
+            RCCHK(ensure(ctx, tp.lay_tmp_lo, (size_t)L * slice * sizeof(float)));
+            BcdLayerTable t = {};
+            for (int k = 0; k < L; ++k) { t.a[k] = out[k]; t.o[k] = (float *)tp.lay_tmp_lo.p + k * slice; }
+            HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, ws[s], hs[s], st));
+            for (int k = 0; k < L; ++k) { t.a[k] = (const float *)tp.lay_tmp_lo.p + k * slice; t.b[k] = outs[(size_t)(s + 1) * L + k]; t.o[k] = out[k]; }
+            HIPCHK(ctx, bcd_launch_layers_merge(t, L, w2, h2, ws[s], hs[s], st));
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ctx->layer_count = L;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_denoise_temporal_layers_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H,
+                                         int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    const int L = nb_layers;
+    if (nb_neighbours == 0) {
+        bcd_hip_host_layer hl[BCD_HIP_MAX_LAYERS];
+        for (int k = 0; k < L; ++k) hl[k] = { layers[k].d_colors, layers[k].d_covariances, layers[k].d_out };
+        return bcd_hip_denoise_layers_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, nullptr, hl, L);
+    }
+    if (L == 1) {
+        bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
+        for (int f = 0; f < nb_neighbours; ++f)
+            nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
+        RCCHK(bcd_hip_denoise_temporal_host(ctx, layers[0].d_colors, h_ns, h_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
+        memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+        for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
+        ctx->layer_count = 1;
+        return BCD_HIP_OK;
+    }
+    DEVICE_GUARD(ctx);
+    auto &tp = ctx->temporal;
+    const size_t npix = (size_t)W * H, f4 = sizeof(float), bc = npix * 3 * f4, bv = npix * 6 * f4;
+    hipStream_t st = ctx->main.stream;
+    bcd_hip_frame_layers dev[BCD_HIP_MAX_NEIGHBOURS + 1];
+    std::vector<bcd_hip_frame_layer> dl((size_t)(nb_neighbours + 1) * L);
+    for (int f = 0; f <= nb_neighbours; ++f) { // whole uploads, no streaming
+        const float *ns = f ? neighbours[f - 1].d_nsamples : h_ns, *hist = f ? neighbours[f - 1].d_histograms : h_hist;
+        RCCHK(ensure(ctx, tp.host[f][1], npix * f4));
+        RCCHK(ensure(ctx, tp.host[f][2], npix * D * f4));
+        RCCHK(ensure(ctx, tp.lay_host[f][0], (size_t)L * bc));
+        RCCHK(ensure(ctx, tp.lay_host[f][1], (size_t)L * bv));
+        HIPCHK(ctx, hipMemcpyAsync(tp.host[f][1].p, ns, npix * f4, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(tp.host[f][2].p, hist, npix * D * f4, hipMemcpyHostToDevice, st));
+        for (int k = 0; k < L; ++k) {
+            float *dc = (float *)tp.lay_host[f][0].p + (size_t)k * npix * 3, *dv = (float *)tp.lay_host[f][1].p + (size_t)k * npix * 6;
+            HIPCHK(ctx, hipMemcpyAsync(dc, f ? neighbours[f - 1].layers[k].d_colors : layers[k].d_colors, bc, hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(dv, f ? neighbours[f - 1].layers[k].d_covariances : layers[k].d_covariances, bv, hipMemcpyHostToDevice, st));
+            dl[(size_t)f * L + k] = { dc, dv };
+        }
+        dev[f] = { (const float *)tp.host[f][1].p, (const float *)tp.host[f][2].p, &dl[(size_t)f * L], nullptr };
+    }
+    RCCHK(ensure(ctx, tp.lay_host_out, (size_t)L * bc));
+    bcd_hip_layer lay[BCD_HIP_MAX_LAYERS];
+    for (int k = 0; k < L; ++k) lay[k] = { dl[k].d_colors, dl[k].d_covariances, (float *)tp.lay_host_out.p + (size_t)k * npix * 3 };
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    RCCHK(bcd_hip_denoise_temporal_layers(ctx, dev[0].d_nsamples, dev[0].d_histograms, dev + 1, nb_neighbours, W, H, D, nb_scales, prm, lay, L));
+    for (int k = 0; k < L; ++k) HIPCHK(ctx, hipMemcpyAsync(layers[k].d_out, lay[k].d_out, bc, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+} // extern "C"

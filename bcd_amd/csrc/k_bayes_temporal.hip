@@ -9,6 +9,8 @@
 //                                   aggregate the estimates of the members in S_0 only
 //   k_bayes_weak_temporal  FALLBACK denoiseOnlyMainPatch (:455-481) with the average over the colour patches of all members of all frames, added to the main
 //                                   patch only
+//   k_bayes_weak_temporal_layers    the same for several colour layers on one selection (bcd_hip_denoise_temporal_layers): the masks walked once, G layers
+//                                   summed in registers
 // Members are gathered from global memory (the gather form of k_bayes27<1>): a member's frame is part of its code.
 // The record, the work queues and noise_idx are those of the chain: bayes27_record.h.
 #include "bcd_launch.h"
@@ -210,6 +212,87 @@ __global__ __launch_bounds__(64) void k_bayes_weak_temporal(BcdFrameTable t, con
     }
 }
 
+// k_bayes_weak_temporal for SEVERAL colour layers that share the selection (bcd_hip_denoise_temporal_layers): the lanes, the list walk and the mask walk are
+// those of the kernel above, done ONCE; every decoded member adds its patch pixel of G layers to G x 3 register accumulators.  blockIdx.y takes layers
+// [y G, y G + G).  The member order is the single-layer kernel's and so are the operations on a layer's three sums: before the atomics they are bit for
+// bit those of k_bayes_weak_temporal run on that layer alone.  |S| = 0 gives NaN in every layer.  The layers share ONE count image: `cnt` (null: none) is
+// filled by the first group, once.
+// The pointers travel by value.  The group's (frame, layer) colour pointers are picked once, by select chains on blockIdx.y over statically indexed table
+// entries; the frame's are picked per frame by select chains on the (wave-uniform) frame index, as frame_col does: nothing is indexed dynamically.
+template <int B, int G>
+__global__ __launch_bounds__(64) void k_bayes_weak_temporal_layers(BcdFrameLayerTable t, const int32_t *__restrict__ list, const int32_t *__restrict__ d_nlist,
+                                                                   int W, int32_t *cnt)
+{
+    constexpr int SIDE = 2 * B + 1, WORDS = (SIDE * SIDE + 31) / 32, PER_WAVE = 64 / P, NF = BCD_MAX_NEIGHBOURS + 1, GROUPS = BCD_MAX_LAYERS / G;
+    static_assert(BCD_MAX_LAYERS % G == 0, "the groups tile the table");
+    const int lane = threadIdx.x, slot = lane / P, o = lane - slot * P;
+    const int grp = blockIdx.y, ng = min(G, t.layers - grp * G);
+    const float *gcol[NF][G];
+    float *gsum[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const float *r = t.col[f][j];
+#pragma unroll
+            for (int z = 1; z < GROUPS; ++z) r = grp == z ? t.col[f][z * G + j] : r;
+            gcol[f][j] = r;
+        }
+        float *s = t.sum[j];
+#pragma unroll
+        for (int z = 1; z < GROUPS; ++z) s = grp == z ? t.sum[z * G + j] : s;
+        gsum[j] = s;
+    }
+    const int nlist = *d_nlist;
+    for (int base = blockIdx.x * PER_WAVE; base < nlist; base += gridDim.x * PER_WAVE) {
+        const int item = base + slot;
+        if (slot >= PER_WAVE || item >= nlist) continue;
+        const int p = list[item];
+        const long long pp = (long long)p + (o / 3 - 1) * W + (o % 3 - 1); // patch pixel o of the main patch
+        float a[G][3];
+#pragma unroll
+        for (int j = 0; j < G; ++j) { a[j][0] = 0.f; a[j][1] = 0.f; a[j][2] = 0.f; }
+        int n = 0;
+        for (int f = 0; f < t.n; ++f) {
+            const float *src[G];
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const float *r = gcol[0][j];
+#pragma unroll
+                for (int i = 1; i < NF; ++i) r = f == i ? gcol[i][j] : r;
+                src[j] = r + pp * 3;
+            }
+            const uint32_t *mw = t.mask[0];
+#pragma unroll
+            for (int i = 1; i < NF; ++i) mw = f == i ? t.mask[i] : mw;
+            mw += (size_t)p * WORDS;
+            for (int wd = 0; wd < WORDS; ++wd) {
+                uint32_t m = mw[wd];
+                while (m) {
+                    const int k = wd * 32 + __ffs(m) - 1;
+                    m &= m - 1;
+                    const int kl = k / SIDE, kc = k - kl * SIDE;
+                    const int rel = ((kl - B) * W + (kc - B)) * 3;
+#pragma unroll
+                    for (int j = 0; j < G; ++j) { a[j][0] += src[j][rel]; a[j][1] += src[j][rel + 1]; a[j][2] += src[j][rel + 2]; }
+                    ++n;
+                }
+            }
+        }
+        const float n_inv = 1.f / (float)n;
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            if (j < ng) { // (uniform)
+                float *dst = gsum[j] + pp * 3;
+                unsafeAtomicAdd(dst, n_inv * a[j][0]);
+                unsafeAtomicAdd(dst + 1, n_inv * a[j][1]);
+                unsafeAtomicAdd(dst + 2, n_inv * a[j][2]);
+            }
+        }
+        if (cnt && grp == 0) atomicAdd(cnt + pp, 1);
+    }
+}
+
 } // namespace
 
 // PREPARE of items [first_item, first_item + nb_items) of `list` into `records` (nb_items records as bcd_launch_bayes27 lays them out: A | V | C | aux | eig |
@@ -232,5 +315,29 @@ hipError_t bcd_launch_bayes_weak_temporal(const BcdFrameTable &t, const int32_t 
     if (blocks <= 0) return hipSuccess;
     if (b != 6 || t.n < 1 || t.n > BCD_MAX_NEIGHBOURS + 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bayes_weak_temporal<6>, dim3(blocks), dim3(64), 0, st, t, list, d_nlist, W, sum, cnt);
+    return hipGetLastError();
+}
+
+// the fallback of every layer in one launch: t.n frames, t.layers layers; `blocks` wavefronts per group of layers; cnt: the shared count image or null
+hipError_t bcd_launch_bayes_weak_temporal_layers(const BcdFrameLayerTable &t, const int32_t *list, const int32_t *d_nlist, int blocks, int W, int b, int32_t *cnt,
+                                                 hipStream_t st)
+{
+    if (blocks <= 0) return hipSuccess;
+    if (b != 6 || t.n < 1 || t.n > BCD_MAX_NEIGHBOURS + 1 || t.layers < 1 || t.layers > BCD_MAX_LAYERS) return hipErrorInvalidValue;
+    BcdFrameLayerTable u = t;
+    for (int f = 0; f <= BCD_MAX_NEIGHBOURS; ++f) { // idle slots of a group, unused frames: memory that exists
+        if (f >= t.n) u.mask[f] = t.mask[0];
+        for (int k = 0; k < BCD_MAX_LAYERS; ++k)
+            if (f >= t.n || k >= t.layers) u.col[f][k] = t.col[0][0];
+    }
+    for (int k = t.layers; k < BCD_MAX_LAYERS; ++k) u.sum[k] = nullptr; // (never flushed)
+    const int L = t.layers;
+    if (L == 1)
+        hipLaunchKernelGGL((k_bayes_weak_temporal_layers<6, 1>), dim3(blocks, 1), dim3(64), 0, st, u, list, d_nlist, W, cnt);
+    else if (L == 2)
+        hipLaunchKernelGGL((k_bayes_weak_temporal_layers<6, 2>), dim3(blocks, 1), dim3(64), 0, st, u, list, d_nlist, W, cnt);
+    else
+        hipLaunchKernelGGL((k_bayes_weak_temporal_layers<6, BCD_TEMPORAL_GROUP>), dim3(blocks, (L + BCD_TEMPORAL_GROUP - 1) / BCD_TEMPORAL_GROUP), dim3(64), 0, st, u,
+                           list, d_nlist, W, cnt);
     return hipGetLastError();
 }

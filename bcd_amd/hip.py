@@ -266,6 +266,21 @@ class StageFrame(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_pixel_cov", C.c_void_p), ("d_mask", C.c_void_p)]
 
 
+class FrameLayer(C.Structure):
+    """bcd_hip_frame_layer: one colour layer of a neighbour frame of bcd_hip_denoise_temporal_layers[_host]"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p)]
+
+
+class FrameLayers(C.Structure):
+    """bcd_hip_frame_layers: one neighbour frame of bcd_hip_denoise_temporal_layers[_host]"""
+    _fields_ = [("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("layers", C.POINTER(FrameLayer)), ("reserved", C.c_void_p)]
+
+
+class StageFrameLayers(C.Structure):
+    """bcd_hip_stage_frame_layers: one frame of bcd_hip_bayes_accumulate_temporal_layers"""
+    _fields_ = [("d_colors", C.POINTER(C.c_void_p)), ("d_pixel_cov", C.POINTER(C.c_void_p)), ("d_mask", C.c_void_p)]
+
+
 # every symbol include/bcd_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "bcd_hip_ctx_create", "bcd_hip_ctx_destroy", "bcd_hip_last_error", "bcd_hip_device_count", "bcd_hip_default_params",
@@ -275,6 +290,7 @@ SYMBOLS = [
     "bcd_hip_similarity_masks_moments", "bcd_hip_window_distances_moments", "bcd_hip_denoise_moments", "bcd_hip_denoise_moments_host",
     "bcd_hip_similarity_masks_guide", "bcd_hip_window_distances_guide", "bcd_hip_gate_masks", "bcd_hip_denoise_guided", "bcd_hip_denoise_guided_host",
     "bcd_hip_similarity_masks_cross", "bcd_hip_window_distances_cross", "bcd_hip_bayes_accumulate_temporal", "bcd_hip_denoise_temporal", "bcd_hip_denoise_temporal_host",
+    "bcd_hip_denoise_temporal_layers", "bcd_hip_denoise_temporal_layers_host", "bcd_hip_bayes_accumulate_temporal_layers",
     "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
     "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
@@ -942,6 +958,104 @@ class Context:
         self._chk(L.bcd_hip_denoise_temporal_host(self.h, col.ctypes.data, ns.ctypes.data, hist.ctypes.data, cov.ctypes.data, arr, len(keep), W, H, D, int(nscales),
                                                   C.byref(prm), out.ctypes.data))
         return out
+
+    def bayes_accumulate_temporal_layers(self, frames, nsim_total, state, w, b, min_eig, out=None):
+        """bcd_hip_bayes_accumulate_temporal_layers: `frames` is a list of ([(colours, per-pixel covariances), ...], masks), [0] the frame itself and the
+        others its neighbour frames with their cross masks, every frame with the same layers in the same order; nsim_total = |S_0| + sum |S_f|.
+        -> (list of sum images, the shared count image, items per layer that took the redo list); out: (sums, count) to accumulate into"""
+        torch = self.torch
+        frames = [(list(layers), mask) for (layers, mask) in frames]
+        H, W = nsim_total.shape
+        nl = len(frames[0][0]) if frames else 0
+        if out is None:
+            sums = [torch.zeros((H, W, 3), dtype=torch.float32, device=nsim_total.device) for _ in range(nl)]
+            c = torch.zeros((H, W), dtype=torch.int32, device=nsim_total.device)
+        else:
+            sums, c = out
+            sums = list(sums)
+        arr = (StageFrameLayers * max(len(frames), 1))()
+        keep = []
+        for i, (layers, mask) in enumerate(frames):
+            if len(layers) != nl:
+                raise ValueError("frame %d: %d layers expected" % (i, nl))
+            for (col, pc) in layers:
+                if tuple(col.shape) != (H, W, 3) or tuple(pc.shape) != (H, W, 6):
+                    raise ValueError("frame %d: colours (H, W, 3) and per-pixel covariances (H, W, 6) of the frame's size are expected" % i)
+            if mask.numel() != H * W * (((2 * b + 1) ** 2 + 31) // 32):
+                raise ValueError("frame %d: masks (H, W, words) of the frame's size are expected" % i)
+            cols, pcs = self._ptr_list([col for col, _ in layers]), self._ptr_list([pc for _, pc in layers])
+            keep += [cols, pcs]
+            arr[i].d_colors, arr[i].d_pixel_cov, arr[i].d_mask = cols, pcs, _dp(mask).value
+        redo = (C.c_int32 * max(1, nl))()
+        L = lib()
+        L.bcd_hip_bayes_accumulate_temporal_layers.argtypes = [_VP, C.POINTER(StageFrameLayers), C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                               _VP, _VP, C.POINTER(C.c_int32)]
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(L.bcd_hip_bayes_accumulate_temporal_layers(self.h, arr, len(frames), nl, _dp(nsim_total), _dp(state), W, H, w, b, float(min_eig),
+                                                             self._ptr_list(sums), _dp(c), redo))
+        return sums, c, list(redo)[:nl]
+
+    def _frame_layers_array(self, neighbours, nl, check, ptr):
+        """the bcd_hip_frame_layers array of a list of (ns, hist, [(colours, covariances), ...]); check(i, ns, hist, layers) validates, ptr(a) is an address"""
+        arr = (FrameLayers * max(len(neighbours), 1))()
+        keep = []
+        for i, (ns, hist, layers) in enumerate(neighbours):
+            layers = list(layers)
+            if len(layers) != nl:
+                raise ValueError("neighbour %d: one layer per layer of the frame expected (%d, not %d)" % (i, nl, len(layers)))
+            check(i, ns, hist, layers)
+            la = (FrameLayer * max(nl, 1))()
+            for k, (col, cov) in enumerate(layers):
+                la[k].d_colors, la[k].d_covariances = ptr(col), ptr(cov)
+            keep.append(la)
+            arr[i].d_nsamples, arr[i].d_histograms, arr[i].layers = ptr(ns), ptr(hist), la
+        return arr, keep
+
+    def denoise_temporal_layers(self, ns, hist, layers, neighbours, nscales, prm, outs=None):
+        """bcd_hip_denoise_temporal_layers: the colour layers `layers` -- a list of (colours, covariances) device tensors that share `ns` and `hist` -- denoised
+        with similar patches from up to four neighbour frames, each (ns, hist, [(colours, covariances), ...]) with the same layers in the same order.  One
+        selection per scale serves every layer.  -> the list of outputs"""
+        torch = self.torch
+        H, W, D = hist.shape
+        arr, layers, outs = self._layer_array(layers, outs, H, W, hist.device)
+        neighbours = list(neighbours)
+
+        def check(i, ns_f, hist_f, lay_f):
+            if ns_f.numel() != H * W or tuple(hist_f.shape) != (H, W, D) or any(tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) for c, v in lay_f):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), check, lambda t: _dp(t).value)
+        L = lib()
+        L.bcd_hip_denoise_temporal_layers.argtypes = [_VP, _VP, _VP, C.POINTER(FrameLayers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
+                                                      C.POINTER(Layer), C.c_int]
+        torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_denoise_temporal_layers(self.h, _dp(ns), _dp(hist), nb, len(neighbours), W, H, D, int(nscales), C.byref(prm), arr, len(layers)))
+        return outs
+
+    def denoise_temporal_layers_host(self, ns, hist, layers, neighbours, nscales, prm):
+        """bcd_hip_denoise_temporal_layers_host on NumPy float32 arrays -> the list of denoised layers (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        ns, hist = as32(ns), as32(hist)
+        H, W, D = hist.shape
+        layers = [(as32(c), as32(v)) for c, v in layers]
+        neighbours = [(as32(n), as32(h), [(as32(c), as32(v)) for c, v in lay]) for n, h, lay in neighbours]
+        outs = [np.empty((H, W, 3), np.float32) for _ in layers]
+        arr = (Layer * max(1, len(layers)))()
+        for k, ((col, cov), out) in enumerate(zip(layers, outs)):
+            if col.shape != (H, W, 3) or cov.shape != (H, W, 6):
+                raise ValueError("layer %d: colours must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
+            arr[k].d_colors, arr[k].d_covariances, arr[k].d_out = col.ctypes.data, cov.ctypes.data, out.ctypes.data
+
+        def check(i, ns_f, hist_f, lay_f):
+            if ns_f.size != H * W or hist_f.shape != (H, W, D) or any(c.shape != (H, W, 3) or v.shape != (H, W, 6) for c, v in lay_f):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), check, lambda a: a.ctypes.data)
+        L = lib()
+        L.bcd_hip_denoise_temporal_layers_host.argtypes = [_VP, _VP, _VP, C.POINTER(FrameLayers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
+                                                           C.POINTER(Layer), C.c_int]
+        self._chk(L.bcd_hip_denoise_temporal_layers_host(self.h, ns.ctypes.data, hist.ctypes.data, nb, len(neighbours), W, H, D, int(nscales), C.byref(prm), arr,
+                                                         len(layers)))
+        return outs
 
     def denoise_temporal_stages(self, col, ns, hist, cov, neighbours, prm):
         """One scale of the denoising of a frame with similar patches from neighbouring frames of its sequence, composed from the

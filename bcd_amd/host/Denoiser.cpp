@@ -358,26 +358,60 @@ namespace bcd
 			else if(!m_neighbourFrames.empty())
 			{	// neighbouring frames of the sequence lend their statistics; checked here: sizes, and what the call does not combine with
 				std::vector<bcd_hip_frame> frames(m_neighbourFrames.size());
-				bool ok = m_layers.empty() && !(m_prefilterThresholdStDevFactor > 0.f);
+				const size_t nbOfLayers = m_layers.size();
+				std::vector<bcd_hip_frame_layer> frameLayers(m_neighbourFrames.size() * (nbOfLayers + 1));
+				std::vector<bcd_hip_frame_layers> layeredFrames(m_neighbourFrames.size());
+				auto fits = [&](const DeepImage<float>* i_pImage, int i_depth)
+				{
+					return i_pImage && i_pImage->getWidth() == m_width && i_pImage->getHeight() == m_height && i_pImage->getDepth() == i_depth;
+				};
+				bool ok = !(m_prefilterThresholdStDevFactor > 0.f) && m_neighbourLayers.size() == m_neighbourFrames.size();
 				for(size_t k = 0; ok && k < m_neighbourFrames.size(); ++k)
 				{
 					const DenoiserInputs& f = m_neighbourFrames[k];
-					ok = f.m_pColors && f.m_pNbOfSamples && f.m_pHistograms && f.m_pSampleCovariances
-							&& f.m_pColors->getWidth() == m_width && f.m_pColors->getHeight() == m_height && f.m_pColors->getDepth() == 3
-							&& f.m_pNbOfSamples->getWidth() == m_width && f.m_pNbOfSamples->getHeight() == m_height && f.m_pNbOfSamples->getDepth() == 1
-							&& f.m_pHistograms->getWidth() == m_width && f.m_pHistograms->getHeight() == m_height && f.m_pHistograms->getDepth() == depth
-							&& f.m_pSampleCovariances->getWidth() == m_width && f.m_pSampleCovariances->getHeight() == m_height && f.m_pSampleCovariances->getDepth() == 6;
-					if(ok)
-						frames[k] = { f.m_pColors->getDataPtr(), f.m_pNbOfSamples->getDataPtr(), f.m_pHistograms->getDataPtr(), f.m_pSampleCovariances->getDataPtr(), nullptr };
+					ok = fits(f.m_pColors, 3) && fits(f.m_pNbOfSamples, 1) && fits(f.m_pHistograms, depth) && fits(f.m_pSampleCovariances, 6)
+							&& m_neighbourLayers[k].size() == nbOfLayers; // one layer of the neighbour per added layer of the frame
+					for(size_t j = 0; ok && j < nbOfLayers; ++j)
+						ok = fits(m_neighbourLayers[k][j].m_pColors, 3) && fits(m_neighbourLayers[k][j].m_pSampleCovariances, 6);
+					if(!ok)
+						break;
+					frames[k] = { f.m_pColors->getDataPtr(), f.m_pNbOfSamples->getDataPtr(), f.m_pHistograms->getDataPtr(), f.m_pSampleCovariances->getDataPtr(), nullptr };
+					bcd_hip_frame_layer* pLayers = &frameLayers[k * (nbOfLayers + 1)];
+					pLayers[0] = { f.m_pColors->getDataPtr(), f.m_pSampleCovariances->getDataPtr() }; // the primary images are layer 0
+					for(size_t j = 0; j < nbOfLayers; ++j)
+						pLayers[j + 1] = { m_neighbourLayers[k][j].m_pColors->getDataPtr(), m_neighbourLayers[k][j].m_pSampleCovariances->getDataPtr() };
+					layeredFrames[k] = { f.m_pNbOfSamples->getDataPtr(), f.m_pHistograms->getDataPtr(), pLayers, nullptr };
 				}
 				if(!ok)
 				{
-					cerr << "Aborting denoising: a neighbour frame needs all four images in the frame's size, and neighbour frames do not combine with added layers or the spike prefilter" << endl;
+					cerr << "Aborting denoising: a neighbour frame needs all four images in the frame's size and, beside added layers, exactly one layer "
+							"(addNeighbourFrameLayer) per added layer in that size; neighbour frames do not combine with the spike prefilter" << endl;
 					bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
 					return false;
 				}
-				rc = bcd_hip_denoise_temporal_host(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], frames.data(), int(frames.size()), m_width, m_height, depth, i_nbOfScales, &prm,
-						result.getDataPtr());
+				if(nbOfLayers == 0)
+					rc = bcd_hip_denoise_temporal_host(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], frames.data(), int(frames.size()), m_width, m_height, depth, i_nbOfScales, &prm,
+							result.getDataPtr());
+				else
+				{	// the primary images are layer 0 of every frame: one selection over all frames serves every layer
+					std::vector<bcd_hip_layer> layers(nbOfLayers + 1);
+					layers[0] = { pIn[0], pIn[3], result.getDataPtr() };
+					for(size_t k = 0; k < nbOfLayers; ++k)
+					{
+						layerResults[k].resize(m_width, m_height, 3);
+						layers[k + 1] = { m_layers[k].m_pColors->getDataPtr(), m_layers[k].m_pSampleCovariances->getDataPtr(), layerResults[k].getDataPtr() };
+					}
+					rc = bcd_hip_denoise_temporal_layers_host(rSlot.m_pCtx, pIn[1], pIn[2], layeredFrames.data(), int(layeredFrames.size()), m_width, m_height, depth, i_nbOfScales,
+							&prm, layers.data(), int(layers.size()));
+					if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
+						for(size_t k = 0; k < nbOfLayers; ++k)
+						{
+							float* p = layerResults[k].getDataPtr();
+							for(size_t i = 0, n = size_t(m_nbOfPixels) * 3; i < n; ++i)
+								if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
+									p[i] = 0.f;
+						}
+				}
 				if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
 				{
 					float* p = result.getDataPtr();
@@ -452,6 +486,7 @@ namespace bcd
 		engine.setZeroBadOutputValues(m_zeroBadOutputValues);
 		engine.setLayers(m_layers);
 		engine.setNeighbourFrames(m_neighbourFrames);
+		engine.setNeighbourFrameLayers(m_neighbourLayers);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);

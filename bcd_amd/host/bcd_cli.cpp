@@ -5,6 +5,7 @@
 // order), --device <n>.  --ncores only selects the visiting order (n > 1 with -r 0: the reference's strip list; the loop runs on the HIP device); --use-cuda 0 (a request for the CPU path this
 // build does not have) is declined with a note and served by the device; under BCD_STRICT_CPU_REQUEST=1 it is refused with an error before any file is read.
 // --layer <color.exr> <cov.exr> <out.exr> (repeatable) denoises a further colour layer with the filter of the -i image (one selection of similar patches for all).
+// --neighbour-layer <color.exr> <cov.exr> hands the most recent --neighbour the matching layer (the k-th pairs with the k-th --layer).
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
 #include "Chronometer.h"
 #include "DeepImage.h"
@@ -47,7 +48,8 @@ namespace
 		unsigned m_orderSeed = 1234u;
 		std::vector<int> m_devices = std::vector<int>(1, 0);
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
-		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; };
+		struct NeighbourLayer { string m_colorPath, m_covariancePath; Deepimf m_colorImage, m_covarianceImage; };
+		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ };
 		std::vector<Neighbour> m_neighbours; // --neighbour, in command-line order
 		std::vector<Layer> m_layers; // --layer, in command-line order
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
@@ -75,6 +77,9 @@ namespace
 		cout << "Optional arguments list:" << endl;
 		cout << "    -a <file>            The file path to the .bcd.json file containing arguments for the program" << endl;
 		cout << "    --neighbour <frame>  A neighbouring frame of the sequence that lends its statistics (repeatable, at most 4; expects <frame>_hist.exr / <frame>_cov.exr beside it)" << endl;
+		cout << "    --neighbour-layer <color> <cov>" << endl;
+		cout << "                         a colour layer of the most recent --neighbour: the k-th one pairs with the k-th --layer; every neighbour" << endl;
+		cout << "                         needs exactly one per --layer (one selection over all frames then serves every layer; needs -p 0)" << endl;
 		cout << "    -d <float>           Histogram patch distance threshold (default: " << d.m_histogramPatchDistanceThreshold << ")" << endl;
 		cout << "    -b <int>             Radius of search windows (default: " << d.m_searchWindowRadius << ")" << endl;
 		cout << "    -w <int>             Radius of patches (default: " << d.m_patchRadius << ")" << endl;
@@ -155,6 +160,18 @@ namespace
 				if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamplesImage, (stem + "_hist.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour histogram image file '" << stem << "_hist.exr'" << endl; return false; }
 				Utils::separateNbOfSamplesFromHistogram(rNb.m_histogramImage, rNb.m_nbOfSamplesImage, histAndNbOfSamplesImage);
 				if(!ImageIO::loadMultiChannelsEXR(rNb.m_covarianceImage, (stem + "_cov.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour covariance matrix image file '" << stem << "_cov.exr'" << endl; return false; }
+				continue;
+			}
+			if(flag == "--neighbour-layer")
+			{	// a colour layer of the most recent --neighbour: the k-th one pairs with the k-th --layer
+				if(i + 2 >= argc) { cout << "ERROR in program arguments: expecting <color.exr> <cov.exr> after --neighbour-layer" << endl; return false; }
+				if(a.m_neighbours.empty()) { cout << "ERROR in program arguments: --neighbour-layer follows the --neighbour it belongs to" << endl; return false; }
+				a.m_neighbours.back().m_layers.emplace_back();
+				ProgramArguments::NeighbourLayer& rLayer = a.m_neighbours.back().m_layers.back();
+				rLayer.m_colorPath = argv[i + 1]; rLayer.m_covariancePath = argv[i + 2];
+				i += 2;
+				if(!ImageIO::loadEXR(rLayer.m_colorImage, rLayer.m_colorPath.c_str())) { cout << "ERROR in program arguments: couldn't load neighbour layer color image file '" << rLayer.m_colorPath << "'" << endl; return false; }
+				if(!ImageIO::loadMultiChannelsEXR(rLayer.m_covarianceImage, rLayer.m_covariancePath.c_str())) { cout << "ERROR in program arguments: couldn't load neighbour layer covariance matrix image file '" << rLayer.m_covariancePath << "'" << endl; return false; }
 				continue;
 			}
 			if(flag == "--layer")
@@ -409,6 +426,34 @@ namespace
 			return false;
 		}
 		if(!a.m_layers.empty() && a.m_devices.size() > 1) { cout << "ERROR in program arguments: --layer is not available with several devices" << endl; return false; }
+		// every --neighbour brings one --neighbour-layer per --layer, in the size of the -i image (checked here: nothing has touched a device yet)
+		for(ProgramArguments::Neighbour& rNb : a.m_neighbours)
+		{
+			const int w = a.m_colorImage.getWidth(), h = a.m_colorImage.getHeight();
+			if(rNb.m_layers.size() != a.m_layers.size())
+			{
+				cout << "ERROR in program arguments: neighbour '" << rNb.m_colorPath << "' has " << rNb.m_layers.size() << " --neighbour-layer argument(s) but there are "
+						<< a.m_layers.size() << " --layer argument(s): every neighbour needs one per layer, in the same order" << endl;
+				return false;
+			}
+			for(ProgramArguments::NeighbourLayer& rLayer : rNb.m_layers)
+			{
+				if(rLayer.m_colorImage.getDepth() == 1)
+				{
+					Deepimf rgb(rLayer.m_colorImage.getWidth(), rLayer.m_colorImage.getHeight(), 3);
+					for(int i = 0, n = rLayer.m_colorImage.getSize(); i < n; ++i)
+						rgb.get(3 * i) = rgb.get(3 * i + 1) = rgb.get(3 * i + 2) = rLayer.m_colorImage.get(i);
+					rLayer.m_colorImage = std::move(rgb);
+				}
+				if(rLayer.m_colorImage.getWidth() != w || rLayer.m_colorImage.getHeight() != h || rLayer.m_colorImage.getDepth() != 3
+						|| rLayer.m_covarianceImage.getWidth() != w || rLayer.m_covarianceImage.getHeight() != h || rLayer.m_covarianceImage.getDepth() != 6)
+				{
+					cout << "ERROR in program arguments: neighbour layer '" << rLayer.m_colorPath << "' / '" << rLayer.m_covariancePath << "' is not " << w << "x" << h
+							<< "x3 / " << w << "x" << h << "x6 like the input color image" << endl;
+					return false;
+				}
+			}
+		}
 		return true;
 	}
 
@@ -488,6 +533,8 @@ namespace
 			DenoiserInputs frame;
 			frame.m_pColors = &rNb.m_colorImage; frame.m_pNbOfSamples = &rNb.m_nbOfSamplesImage; frame.m_pHistograms = &rNb.m_histogramImage; frame.m_pSampleCovariances = &rNb.m_covarianceImage;
 			pSettings->addNeighbourFrame(frame);
+			for(ProgramArguments::NeighbourLayer& rLayer : rNb.m_layers)
+				pSettings->addNeighbourFrameLayer(pSettings->getNeighbourFrames().size() - 1, &rLayer.m_colorImage, &rLayer.m_covarianceImage);
 		}
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)

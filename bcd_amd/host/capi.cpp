@@ -595,6 +595,78 @@ int bcdcore_denoise_temporal(const float* col, const float* ns, const float* his
 	return ok ? 1 : 0;
 }
 
+/// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames AND colour layers (addLayer, addNeighbourFrame, addNeighbourFrameLayer).  cols / covs hold
+/// nbOfLayers images of the frame one behind the other (layer 0 = the primary images), nbCols / nbCovs nbOfNeighbours x nbOfLayers images (neighbour-major),
+/// nbNs / nbHists one image per neighbour.  The last neighbour gets dropLayers fewer layers than the frame (> 0: denoise() must refuse).  afterClear != 0:
+/// clearNeighbourFrames() and a second denoise() follow (the plain layered call), whose results replace the first.  Returns denoise()'s bool.
+int bcdcore_denoise_temporal_layers(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs, const float* nbNs,
+		const float* nbHists, int nbOfNeighbours, int nbOfLayers, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder,
+		float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs)
+{
+	const size_t npix = size_t(W) * H;
+	Deepimf nImg(W, H, 1), hImg(W, H, D);
+	nImg.copyDataFrom(ns); hImg.copyDataFrom(hist);
+	std::vector<Deepimf> c(nbOfLayers), v(nbOfLayers), o(nbOfLayers);
+	for(int k = 0; k < nbOfLayers; ++k)
+	{
+		c[k].resize(W, H, 3); v[k].resize(W, H, 6);
+		c[k].copyDataFrom(cols + k * npix * 3); v[k].copyDataFrom(covs + k * npix * 6);
+		o[k] = c[k]; // (the multiscale path wants the output pre-sized like the input)
+	}
+	std::vector<Deepimf> fn(nbOfNeighbours), fh(nbOfNeighbours), fc(size_t(nbOfNeighbours) * nbOfLayers), fv(size_t(nbOfNeighbours) * nbOfLayers);
+	DenoiserInputs in;
+	in.m_pColors = &c[0]; in.m_pNbOfSamples = &nImg; in.m_pHistograms = &hImg; in.m_pSampleCovariances = &v[0];
+	DenoiserOutputs out;
+	out.m_pDenoisedColors = &o[0];
+	DenoiserParameters p;
+	p.m_histogramDistanceThreshold = tau;
+	p.m_searchWindowRadius = b;
+	p.m_minEigenValue = minEig;
+	p.m_useRandomPixelOrder = randomOrder != 0;
+	p.m_markedPixelsSkippingProbability = skipProbability;
+	std::unique_ptr<MultiscaleDenoiser> multi;
+	std::unique_ptr<Denoiser> mono;
+	IDenoiser* d;
+	HipEngineSettings* pSettings;
+	if(nscales > 1) { multi.reset(new MultiscaleDenoiser(nscales)); d = multi.get(); pSettings = multi.get(); }
+	else { mono.reset(new Denoiser()); d = mono.get(); pSettings = mono.get(); }
+	pSettings->setOrderSeed(seed);
+	for(int k = 1; k < nbOfLayers; ++k)
+		pSettings->addLayer(&c[k], &v[k], &o[k]);
+	for(int f = 0; f < nbOfNeighbours; ++f)
+	{
+		fn[f].resize(W, H, 1); fh[f].resize(W, H, D);
+		fn[f].copyDataFrom(nbNs + f * npix); fh[f].copyDataFrom(nbHists + f * npix * D);
+		for(int k = 0; k < nbOfLayers; ++k)
+		{
+			const size_t i = size_t(f) * nbOfLayers + k;
+			fc[i].resize(W, H, 3); fv[i].resize(W, H, 6);
+			fc[i].copyDataFrom(nbCols + i * npix * 3); fv[i].copyDataFrom(nbCovs + i * npix * 6);
+		}
+		DenoiserInputs frame;
+		frame.m_pColors = &fc[size_t(f) * nbOfLayers]; frame.m_pNbOfSamples = &fn[f]; frame.m_pHistograms = &fh[f]; frame.m_pSampleCovariances = &fv[size_t(f) * nbOfLayers];
+		pSettings->addNeighbourFrame(frame);
+		const int given = nbOfLayers - (f == nbOfNeighbours - 1 ? dropLayers : 0);
+		for(int k = 1; k < given; ++k)
+			pSettings->addNeighbourFrameLayer(size_t(f), &fc[size_t(f) * nbOfLayers + k], &fv[size_t(f) * nbOfLayers + k]);
+	}
+	d->setInputs(in);
+	d->setOutputs(out);
+	d->setParameters(p);
+	bool ok = d->denoise();
+	if(ok && afterClear)
+	{
+		pSettings->clearNeighbourFrames();
+		for(int k = 0; k < nbOfLayers; ++k)
+			o[k] = c[k];
+		ok = d->denoise();
+	}
+	if(ok)
+		for(int k = 0; k < nbOfLayers; ++k)
+			o[k].copyDataTo(outs + k * npix * 3);
+	return ok ? 1 : 0;
+}
+
 /// ONE MultiscaleDenoiser (or Denoiser), denoise() called twice with -r 0 and the given m_nbOfCores: the written-back core count must not
 /// change what the second call does (returns 0 on failure, else 1; nbOfCoresAfter[2] = the field after each call)
 int bcdcore_denoise_reuse(const float* col, const float* ns, const float* hist, const float* cov, int W, int H, int D, int nscales, int b,

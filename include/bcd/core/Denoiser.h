@@ -87,12 +87,30 @@ namespace bcd
 		/// A neighbouring frame of the sequence (t - 1, t + 1, ...) that lends its statistics to the frame in DenoiserInputs (bcd_hip_denoise_temporal_host):
 		/// similar patches are also searched in the same window of every neighbour frame, and mean, noise mean and covariance of the estimate come from the
 		/// union of the sets; only the frame itself is denoised.  Each neighbour brings all four images, of the frame's width, height and histogram depth.
-		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with added
-		/// layers, the spike prefilter, the moment selection or feature buffers.  With no neighbour denoise() is what it always was.
-		void addNeighbourFrame(const DenoiserInputs& i_rFrame) { m_neighbourFrames.push_back(i_rFrame); }
-		void clearNeighbourFrames() { m_neighbourFrames.clear(); }
+		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with the spike
+		/// prefilter, the moment selection or feature buffers.  With no neighbour denoise() is what it always was.
+		void addNeighbourFrame(const DenoiserInputs& i_rFrame) { m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); }
+		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); }
 		const std::vector<DenoiserInputs>& getNeighbourFrames() const { return m_neighbourFrames; }
-		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames) { m_neighbourFrames = i_rFrames; }
+		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames) { m_neighbourFrames = i_rFrames; m_neighbourLayers.assign(i_rFrames.size(), std::vector<NeighbourLayer>()); }
+		/// Added layers beside neighbour frames (bcd_hip_denoise_temporal_layers_host): neighbour i_neighbour (the index in the order of addNeighbourFrame) brings
+		/// the colours and sample covariances of one more layer; its k-th call pairs with the k-th addLayer.  denoise() accepts layers beside neighbours when
+		/// every neighbour has exactly one such layer per addLayer, in the frame's size, and refuses anything else.  An index that names no neighbour is ignored.
+		struct NeighbourLayer
+		{
+			const DeepImage<float>* m_pColors;
+			const DeepImage<float>* m_pSampleCovariances;
+		};
+		void addNeighbourFrameLayer(size_t i_neighbour, const DeepImage<float>* i_pColors, const DeepImage<float>* i_pSampleCovariances)
+		{
+			if(i_neighbour < m_neighbourLayers.size())
+			{
+				NeighbourLayer layer = { i_pColors, i_pSampleCovariances };
+				m_neighbourLayers[i_neighbour].push_back(layer);
+			}
+		}
+		const std::vector<std::vector<NeighbourLayer>>& getNeighbourFrameLayers() const { return m_neighbourLayers; }
+		void setNeighbourFrameLayers(const std::vector<std::vector<NeighbourLayer>>& i_rLayers) { m_neighbourLayers = i_rLayers; m_neighbourLayers.resize(m_neighbourFrames.size()); }
 
 	protected:
 		uint32_t m_orderSeed;
@@ -108,6 +126,7 @@ namespace bcd
 		float m_guideThreshold;
 		std::vector<ColorLayer> m_layers;
 		std::vector<DenoiserInputs> m_neighbourFrames;
+		std::vector<std::vector<NeighbourLayer>> m_neighbourLayers; // [neighbour][added layer], as long as m_neighbourFrames
 	};
 
 	/// The engine contexts behind denoise() (device workspaces, pyramids, staging buffers: grow-only, sized by the largest frame seen,

@@ -321,7 +321,8 @@ int bcd_hip_denoise_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const floa
  * (bcd_hip_denoise_host): it delegates.  Motion vectors (a per-pixel window centre in the neighbour frame) are not supported: `reserved` must be NULL.
  * Refused before any device work, with a message, the context staying usable: with neighbours, any geometry but patch radius 1 and search radius 6
  * (BCD_HIP_EUNSUPPORTED); nb_neighbours outside 0 .. 4; a null image; a non-NULL `reserved`; an output that is or overlaps an input; what bcd_hip_denoise
- * refuses.  Layers, kept selections, the moment and the feature-gated selection, row bands and bcd_hip_multi_* do not combine with this call.
+ * refuses.  Kept selections, the moment and the feature-gated selection, row bands and bcd_hip_multi_* do not combine with this call; colour layers do
+ * through bcd_hip_denoise_temporal_layers below.
  * bcd_hip_get_stats: similar_total is the sum of the total |S|, similarity_path that of the in-frame pass, ms_similarity includes the cross passes.
  *   _host: whole uploads (no streaming), the resident call, one download: the same result. */
 typedef struct { const float *d_colors, *d_nsamples, *d_histograms, *d_covariances; const void *reserved; } bcd_hip_frame;
@@ -338,6 +339,48 @@ int bcd_hip_similarity_masks_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
                                    uint32_t *d_mask_nb, int32_t *d_count_nb);
 int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, const float *d_nsamples, const float *d_histograms_nb,
                                    const float *d_nsamples_nb, int W, int H, int D, int patch_radius, int search_radius, int line, int col, float *h_out);
+
+/* ---- the colour layers of a frame denoised with its neighbour frames ("Layers") ----
+ * bcd_hip_denoise_layers and bcd_hip_denoise_temporal combined.  The inputs are
+ *   - the frame's sample counts and histograms;
+ *   - L layers, 1 <= L <= BCD_HIP_MAX_LAYERS, each with colours, covariances and an output;
+ *   - F neighbour frames, 0 <= F <= BCD_HIP_MAX_NEIGHBOURS.  Each neighbour brings its sample counts, its histograms and the same L layers (colours and
+ *     covariances) in the same order.
+ * Layer k of the result is what bcd_hip_denoise_temporal returns for the inputs
+ *   - frame: (colours_k, nsamples, histograms, covariances_k);
+ *   - neighbours: (colours_{f,k}, nsamples_f, histograms_f, covariances_{f,k}).
+ * The arithmetic is the same.  Only the order of the float atomics on the sum image differs: the relation bcd_hip_denoise_layers states for its layers.
+ * Per scale the in-frame set S_0, the cross sets S_1 .. S_F, the total |S|, the marking, the lists of full estimates and fallback pixels and the count
+ * image are computed once; only the estimate stage runs per layer.  Every layer of every frame gets its own pyramid: colours are averaged, covariances are
+ * reduced with the frame's sample counts.  bcd_hip_get_stats describes the shared selection, spectral_inverses being the sum over the layers;
+ * bcd_hip_layer_spectral_inverses answers per layer after this call too.
+ * Delegations: nb_neighbours == 0 IS bcd_hip_denoise_layers, nb_layers == 1 IS bcd_hip_denoise_temporal (likewise for _host).
+ * Refused before any device work, with a message, the context staying usable: everything bcd_hip_denoise_temporal and bcd_hip_denoise_layers refuse; a NULL
+ * layer list in a neighbour; a NULL image in any layer of any frame; a non-NULL `reserved`; an output that is, or overlaps, any input of any frame or
+ * another output; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).  Kept selections, the moment and the
+ * feature-gated selection, the spike prefilter, row bands, bcd_hip_multi_* and motion vectors do not combine with this call.
+ *   _host: every pointer is a host pointer; whole uploads (no streaming, no spike prefilter), the resident call, one download per layer: the same result.
+ *   _bayes_accumulate_temporal_layers: the estimate stage -- the twin of bcd_hip_bayes_accumulate_temporal for nb_layers layers on ONE selection.  frames[f]
+ *             holds host arrays of nb_layers device pointers (the colours and the per-pixel covariances of that frame's layers) and the frame's masks, [0]
+ *             being the frame itself; d_sum is a host array of nb_layers device pointers.  It writes ONE count image, per layer one sum image (accumulated
+ *             into, like the count image: zero them first) and h_redo[k], the items of layer k that took the redo list.  Patch radius 1 and search radius 6
+ *             only (BCD_HIP_EUNSUPPORTED); null pointers, nb_frames outside 1 .. 5, nb_layers outside 1 .. 16, an accumulator that overlaps an input or
+ *             another accumulator are refused before any device work.  Synchronises. */
+typedef struct { const float *d_colors; const float *d_covariances; } bcd_hip_frame_layer;
+typedef struct {
+    const float *d_nsamples, *d_histograms;
+    const bcd_hip_frame_layer *layers; /* nb_layers of them, in the order of the frame's layers */
+    const void *reserved;              /* NULL */
+} bcd_hip_frame_layers;
+int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                    int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers);
+int bcd_hip_denoise_temporal_layers_host(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, const bcd_hip_frame_layers *neighbours /* host pointers */,
+                                         int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers /* host pointers */,
+                                         int nb_layers);
+typedef struct { const float *const *d_colors; const float *const *d_pixel_cov; const uint32_t *d_mask; } bcd_hip_stage_frame_layers; /* [0] = the frame itself */
+int bcd_hip_bayes_accumulate_temporal_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_frame_layers *frames, int nb_frames, int nb_layers, const int32_t *d_nsim_total,
+                                             const uint8_t *d_state, int W, int H, int patch_radius, int search_radius, float min_eigen_value, float *const *d_sum,
+                                             int32_t *d_count, int32_t *h_redo);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
