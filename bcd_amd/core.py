@@ -252,25 +252,47 @@ def denoise_layers(layers, ns, hist, nscales=1, tau=1.0, b=6, min_eig=1e-8, rand
     return rc != 0, [outs[k] for k in range(L)]
 
 
-def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, after_clear=False):
+def _motion_stack(motions, F, H, W):
+    """(fields (max(F, 1), H, W, 2) float32, flags int32[max(F, 1)]) of a list of F motion fields or None entries"""
+    motions = list(motions)
+    if len(motions) != F:
+        raise ValueError("one motion field (or None) per neighbour expected (%d, not %d)" % (F, len(motions)))
+    fields = np.zeros((max(F, 1), H, W, 2), np.float32)
+    flags = (C.c_int * max(F, 1))()
+    for k, mv in enumerate(motions):
+        if mv is not None:
+            fields[k] = np.asarray(mv, np.float32).reshape(H, W, 2)
+            flags[k] = 1
+    return fields, flags
+
+
+def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, after_clear=False, motions=None):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames of the sequence (addNeighbourFrame): neighbours is a list of (col, ns, hist, cov)
     arrays of the frame's size, at most four.  after_clear: clearNeighbourFrames() and a second denoise() follow, whose result replaces the first.
-    Returns (ok, denoised frame)"""
+    motions: None, or per neighbour an (H, W, 2) motion field or None (setNeighbourMotion).  Returns (ok, denoised frame)"""
     H, W, D = hist.shape
     F = len(neighbours)
     stack = lambda k, d: np.ascontiguousarray(np.stack([np.asarray(f[k], np.float32).reshape(H, W, d) for f in neighbours]) if F else np.zeros((1, H, W, d)), np.float32)
     out = np.zeros((H, W, 3), np.float32)
+    if motions is not None:
+        fields, flags = _motion_stack(motions, F, H, W)
+        rc = lib().bcdcore_denoise_temporal_motion(_fp(col), _fp(ns), _fp(hist), _fp(cov), _fp(stack(0, 3)), _fp(stack(1, 1)), _fp(stack(2, D)), _fp(stack(3, 6)), F,
+                                                   _fp(fields), flags, W, H, D, int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0,
+                                                   C.c_float(m), C.c_uint(seed), 1 if after_clear else 0, _fp(out))
+        return rc != 0, out
     rc = lib().bcdcore_denoise_temporal(_fp(col), _fp(ns), _fp(hist), _fp(cov), _fp(stack(0, 3)), _fp(stack(1, 1)), _fp(stack(2, D)), _fp(stack(3, 6)), F, W, H, D,
                                         int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed),
                                         1 if after_clear else 0, _fp(out))
     return rc != 0, out
 
 
-def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, drop_layers=0, after_clear=False):
+def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, drop_layers=0, after_clear=False,
+                            motions=None):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with colour layers beside neighbouring frames (addLayer, addNeighbourFrame, addNeighbourFrameLayer): layers is a
     list of (colours, covariances), [0] going through DenoiserInputs; neighbours a list of (ns, hist, [(colours, covariances)]) with the same layers.
     drop_layers: the last neighbour is given that many layers fewer (denoise() must refuse).  after_clear: clearNeighbourFrames() and a second denoise()
-    follow, whose results replace the first.  Returns (ok, [output per layer])"""
+    follow, whose results replace the first.  motions: None, or per neighbour an (H, W, 2) motion field or None (setNeighbourMotion).
+    Returns (ok, [output per layer])"""
     H, W, D = hist.shape
     L, F = len(layers), len(neighbours)
     f32 = lambda a: np.ascontiguousarray(a, np.float32)
@@ -280,6 +302,12 @@ def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=
     nb_ns = f32(np.stack([np.asarray(n, np.float32).reshape(H, W, 1) for n, _, _ in neighbours])) if F else np.zeros((1, H, W, 1), np.float32)
     nb_hists = f32(np.stack([h for _, h, _ in neighbours])) if F else np.zeros((1, H, W, D), np.float32)
     outs = np.zeros((L, H, W, 3), np.float32)
+    if motions is not None:
+        fields, flags = _motion_stack(motions, F, H, W)
+        rc = lib().bcdcore_denoise_temporal_layers_motion(_fp(cols), _fp(covs), _fp(f32(ns)), _fp(f32(hist)), _fp(nb_cols), _fp(nb_covs), _fp(nb_ns), _fp(nb_hists), F, L,
+                                                          _fp(fields), flags, W, H, D, int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0,
+                                                          C.c_float(m), C.c_uint(seed), int(drop_layers), 1 if after_clear else 0, _fp(outs))
+        return rc != 0, [outs[k] for k in range(L)]
     rc = lib().bcdcore_denoise_temporal_layers(_fp(cols), _fp(covs), _fp(f32(ns)), _fp(f32(hist)), _fp(nb_cols), _fp(nb_covs), _fp(nb_ns), _fp(nb_hists), F, L, W, H, D,
                                                int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed),
                                                int(drop_layers), 1 if after_clear else 0, _fp(outs))

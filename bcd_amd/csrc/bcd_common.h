@@ -129,6 +129,13 @@ struct BcdFrameLayerTable {
     int n, layers; // frames in use, layers in use
 };
 
+// ---- neighbour frames warped by a motion field (k_warp.hip) ------------------------------------------------
+// The colours and covariances of the layers of ONE neighbour frame and their warped twins; the device pointers of one launch travel by value.
+struct BcdWarpLayerTable {
+    const float *col[BCD_MAX_LAYERS], *cov[BCD_MAX_LAYERS];
+    float *ocol[BCD_MAX_LAYERS], *ocov[BCD_MAX_LAYERS];
+};
+
 // ---- spike prefilter through a source map (k_spike.hip) ---------------------------------------------------
 // One launch of k_spike_apply gathers up to BCD_SPIKE_MAX_IMAGES images of one depth; the image is blockIdx.y, the pointers travel by value.
 #define BCD_SPIKE_MAX_IMAGES 32

@@ -206,6 +206,12 @@ struct bcd_hip_ctx {
         DevBuf lay_pixcov[BCD_MAX_NEIGHBOURS + 1];             // per-pixel covariances of every frame's layers at the scale in progress
         DevBuf lay_sum, lay_tmp_lo;                            // the layers' sums of the scale in progress, the merge's scratch
         DevBuf lay_host[BCD_MAX_NEIGHBOURS + 1][2], lay_host_out; // host-buffer entry point: device copies of the layers' colours, covariances, outputs
+        // the motion calls ("Motion"): a neighbour with a motion field is warped at full resolution before its pyramid is built
+        DevBuf warp[BCD_MAX_NEIGHBOURS + 1][4];                // [1..]: the warped colours, sample counts, histograms, covariances of that neighbour
+        DevBuf lay_warp[BCD_MAX_NEIGHBOURS + 1][2];            // [1..]: the warped colours, covariances of its layers, one slice per layer
+        DevBuf valid[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES];      // [1..]: its validity bytes at every level
+        DevBuf pvalid;                                         // patch validity of the neighbour and scale in progress
+        DevBuf motion_host[BCD_MAX_NEIGHBOURS + 1];            // host-buffer entry points: device copies of the motion fields
     } temporal;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
@@ -306,6 +312,13 @@ inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
 void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
 // the T / C planes of every displacement between the frame and one neighbour, in the main workspace (whose own planes they overwrite)
 int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b);
+// the gate of a warped neighbour's cross masks (the stream's next step behind k_masks_cross): pvalid from the level's validity bytes, then the bits and |S_f|
+int temporal_gate(bcd_hip_ctx *ctx, Work &wk, const uint8_t *d_valid, int W, int H, int w, int b, uint32_t *d_mask_nb, int32_t *d_count_nb);
+// the validity levels 1 .. nb_scales - 1 of neighbour f from its level 0 (ctx->temporal.valid[f][0]), on the main stream
+int temporal_valid_levels(bcd_hip_ctx *ctx, int f, int W, int H, int nb_scales);
+// the refusals the motion calls add: the list itself, and a field that overlaps one of `outs` (each W*H*3 floats)
+int temporal_upload_motion(bcd_hip_ctx *ctx, const float *const *h_motion, int nb_neighbours, int W, int H, const float **dev); // (whole uploads; dev[f] NULL for a NULL field)
+int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neighbours, int W, int H, float *const *outs, int nb_outs);
 
 // ---- defined in bcd_selection.hip
 // one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is

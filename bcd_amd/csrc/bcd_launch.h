@@ -29,6 +29,14 @@ hipError_t bcd_launch_masks_cross(const float *T, const uint8_t *Cn, int W, int 
 hipError_t bcd_launch_add_counts(int32_t *nsim, const int32_t *add, int64_t npix, hipStream_t st);
 hipError_t bcd_launch_window_distances_cross(const float *T, const uint8_t *Cn, int W, int H, int w, int b, int r, int c, float *out, hipStream_t st);
 
+// ---- k_warp.hip (includes this header)
+hipError_t bcd_launch_warp_frame(const float *col, const float *ns, const float *hist, const float *cov, const float *mv, int W, int H, int D, float *ocol, float *ons,
+                                 float *ohist, float *ocov, uint8_t *valid, hipStream_t st);
+hipError_t bcd_launch_warp_layers(const BcdWarpLayerTable &t, int layers, const float *mv, int W, int H, uint8_t *valid, hipStream_t st);
+hipError_t bcd_launch_valid_down(const uint8_t *valid, int W, int H, uint8_t *out, hipStream_t st);
+hipError_t bcd_launch_valid_patch(const uint8_t *valid, int W, int H, int w, uint8_t *pvalid, hipStream_t st);
+hipError_t bcd_launch_masks_gate_valid(uint32_t *mask, int32_t *count, const uint8_t *pvalid, int W, int H, int w, int b, hipStream_t st);
+
 // ---- k_bayes_temporal.hip, and the launcher of k_bayes27.hip that runs behind its prepare kernel
 hipError_t bcd_launch_prepare27t(const BcdFrameTable &t, const int32_t *list, int first_item, int nb_items, int *d_work, int num_cus, int W, int b, float *records,
                                  hipStream_t st);

@@ -1,7 +1,9 @@
 // bcd_temporal.hip -- similar patches from neighbouring frames of a sequence: the frame calls bcd_hip_denoise_temporal[_host], the
 // stage entry points of the cross-frame selection and of the estimate over several frames, and the driver glue.  The kernels are in k_similarity_cross.hip
 // and k_bayes_temporal.hip; the planes of one neighbour live in the main workspace's plane buffers (grow-only) and are consumed before the next
-// neighbour's are written.
+// neighbour's are written.  The motion calls (section 16, "Motion": bcd_hip_denoise_temporal_motion[_host], the stages bcd_hip_warp_frame,
+// bcd_hip_valid_downscale, bcd_hip_gate_masks_valid) are here too: temporal_run warps a neighbour that has a motion field (k_warp.hip) before its pyramid is
+// built and gates its cross masks at every scale; the plain call is temporal_run without fields.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -19,6 +21,41 @@ int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const
     RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
     wk.planes.ready = false; // (the workspace's planes are overwritten)
     HIPCHK(ctx, bcd_launch_pairdist_cross(d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    return BCD_HIP_OK;
+}
+
+int temporal_gate(bcd_hip_ctx *ctx, Work &wk, const uint8_t *d_valid, int W, int H, int w, int b, uint32_t *d_mask_nb, int32_t *d_count_nb)
+{
+    DevBuf &pv = ctx->temporal.pvalid;
+    RCCHK(ensure(ctx, pv, (size_t)W * H));
+    HIPCHK(ctx, bcd_launch_valid_patch(d_valid, W, H, w, (uint8_t *)pv.p, wk.stream));
+    HIPCHK(ctx, bcd_launch_masks_gate_valid(d_mask_nb, d_count_nb, (const uint8_t *)pv.p, W, H, w, b, wk.stream));
+    return BCD_HIP_OK;
+}
+
+int temporal_valid_levels(bcd_hip_ctx *ctx, int f, int W, int H, int nb_scales)
+{
+    auto &tp = ctx->temporal;
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s, ws /= 2, hs /= 2) {
+        RCCHK(ensure(ctx, tp.valid[f][s], (size_t)(ws / 2) * (hs / 2)));
+        HIPCHK(ctx, bcd_launch_valid_down((const uint8_t *)tp.valid[f][s - 1].p, ws, hs, (uint8_t *)tp.valid[f][s].p, ctx->main.stream));
+    }
+    return BCD_HIP_OK;
+}
+
+static bool overlap_bytes(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
+int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neighbours, int W, int H, float *const *outs, int nb_outs)
+{
+    if (nb_neighbours > 0 && !motion) return bad(ctx, "null motion list with neighbour frames present (an entry may be NULL: zero motion)");
+    const size_t npix = (size_t)W * H;
+    for (int f = 0; f < nb_neighbours; ++f)
+        for (int k = 0; motion[f] && k < nb_outs; ++k)
+            if (overlap_bytes(outs[k], npix * 3 * sizeof(float), motion[f], npix * 2 * sizeof(float))) return bad(ctx, "an output overlaps a motion field");
     return BCD_HIP_OK;
 }
 
@@ -166,6 +203,11 @@ void temporal_free(bcd_hip_ctx *ctx)
     for (DevBuf &b : t.lay_pixcov) if (b.p) (void)hipFree(b.p);
     for (DevBuf *b : { &t.lay_sum, &t.lay_tmp_lo, &t.lay_host_out }) if (b->p) (void)hipFree(b->p);
     for (auto &frame : t.lay_host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    for (auto &frame : t.warp) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    for (auto &frame : t.lay_warp) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    for (auto &frame : t.valid) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : t.motion_host) if (b.p) (void)hipFree(b.p);
+    if (t.pvalid.p) (void)hipFree(t.pvalid.p);
 }
 
 namespace {
@@ -173,7 +215,9 @@ namespace {
 struct FrameLevel { const float *col, *ns, *hist, *cov; };
 
 // one scale: frames[0] the frame itself at this level
-int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale, float *d_out)
+// valid: null, or per frame the validity bytes of this level (null: the frame is not warped) -- a warped neighbour's cross masks pass the gate
+int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale, float *d_out,
+                   const uint8_t *const *valid = nullptr)
 {
     Work &wk = ctx->main;
     auto &tp = ctx->temporal;
@@ -209,6 +253,7 @@ int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, in
         if (f == 0) continue;
         RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
         HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
+        if (valid && valid[f]) RCCHK(temporal_gate(ctx, wk, valid[f], W, H, w, b, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p));
         HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
     }
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
@@ -266,16 +311,11 @@ int check_temporal_call(bcd_hip_ctx *ctx, const void *col, const void *ns, const
     return BCD_HIP_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int bcd_hip_denoise_temporal(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
-                             const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+// the checked call with at least one neighbour; motion: null, or per neighbour a device motion field (null: that neighbour is read where it lies)
+int temporal_run(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
+                 const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out,
+                 const float *const *motion)
 {
-    if (!ctx) return BCD_HIP_EINVAL;
-    RCCHK(check_temporal_call(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out));
-    if (nb_neighbours == 0) return bcd_hip_denoise(ctx, d_colors, d_nsamples, d_histograms, d_covariances, W, H, D, nb_scales, prm, d_out);
     DEVICE_GUARD(ctx);
     const int nf = nb_neighbours + 1, S = nb_scales;
     auto &tp = ctx->temporal;
@@ -284,7 +324,25 @@ int bcd_hip_denoise_temporal(bcd_hip_ctx *ctx, const float *d_colors, const floa
     int ws[MAX_SCALES], hs[MAX_SCALES];
     ws[0] = W; hs[0] = H;
     lv[0] = { d_colors, d_nsamples, d_histograms, d_covariances };
-    for (int f = 1; f < nf; ++f) lv[f] = { neighbours[f - 1].d_colors, neighbours[f - 1].d_nsamples, neighbours[f - 1].d_histograms, neighbours[f - 1].d_covariances };
+    std::vector<const uint8_t *> valid((size_t)S * nf, nullptr);
+    for (int f = 1; f < nf; ++f) {
+        const bcd_hip_frame &nb = neighbours[f - 1];
+        lv[f] = { nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances };
+        if (!motion || !motion[f - 1]) continue;
+        // the neighbour reprojected into the frame's pixel grid, at full resolution; its pyramid is built from the warped images
+        const size_t npix = (size_t)W * H;
+        DevBuf(&wb)[4] = tp.warp[f];
+        RCCHK(ensure(ctx, wb[0], npix * 3 * sizeof(float)));
+        RCCHK(ensure(ctx, wb[1], npix * sizeof(float)));
+        RCCHK(ensure(ctx, wb[2], npix * D * sizeof(float)));
+        RCCHK(ensure(ctx, wb[3], npix * 6 * sizeof(float)));
+        RCCHK(ensure(ctx, tp.valid[f][0], npix));
+        HIPCHK(ctx, bcd_launch_warp_frame(nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances, motion[f - 1], W, H, D, (float *)wb[0].p, (float *)wb[1].p,
+                                          (float *)wb[2].p, (float *)wb[3].p, (uint8_t *)tp.valid[f][0].p, ctx->main.stream));
+        RCCHK(temporal_valid_levels(ctx, f, W, H, S));
+        lv[f] = { (const float *)wb[0].p, (const float *)wb[1].p, (const float *)wb[2].p, (const float *)wb[3].p };
+        for (int s = 0; s < S; ++s) valid[(size_t)s * nf + f] = (const uint8_t *)tp.valid[f][s].p;
+    }
     for (int s = 1; s < S; ++s) {
         ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
         const size_t np = (size_t)ws[s] * hs[s];
@@ -306,25 +364,21 @@ int bcd_hip_denoise_temporal(bcd_hip_ctx *ctx, const float *d_colors, const floa
     }
     for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs (MultiscaleDenoiser.cpp:453-466), as in bcd_hip_denoise
         float *out = s == 0 ? d_out : (float *)tp.out[s].p;
-        RCCHK(temporal_scale(ctx, &lv[(size_t)s * nf], nf, ws[s], hs[s], D, prm, s, out));
+        RCCHK(temporal_scale(ctx, &lv[(size_t)s * nf], nf, ws[s], hs[s], D, prm, s, out, &valid[(size_t)s * nf]));
         if (s < S - 1) RCCHK(bcd_hip_merge(ctx, out, ws[s], hs[s], (const float *)tp.out[s + 1].p, 3));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
     return BCD_HIP_OK;
 }
 
-int bcd_hip_denoise_temporal_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
-                                  const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *h_out)
+// whole uploads of the frame and its neighbours (no streaming) into ctx->temporal.host, and room for the output: dev[0] the frame, dev[1..] the neighbours
+int upload_frames(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances, const bcd_hip_frame *neighbours,
+                  int nb_neighbours, int W, int H, int D, bcd_hip_frame *dev)
 {
-    if (!ctx) return BCD_HIP_EINVAL;
-    RCCHK(check_temporal_call(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out));
-    if (nb_neighbours == 0) return bcd_hip_denoise_host(ctx, h_colors, h_nsamples, h_histograms, h_covariances, W, H, D, nb_scales, prm, h_out);
-    DEVICE_GUARD(ctx);
     auto &tp = ctx->temporal;
     const size_t npix = (size_t)W * H, bytes[4] = { npix * 3 * sizeof(float), npix * sizeof(float), npix * D * sizeof(float), npix * 6 * sizeof(float) };
     hipStream_t st = ctx->main.stream;
-    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
-    for (int f = 0; f <= nb_neighbours; ++f) { // whole uploads, no streaming
+    for (int f = 0; f <= nb_neighbours; ++f) {
         const float *src[4] = { f ? neighbours[f - 1].d_colors : h_colors, f ? neighbours[f - 1].d_nsamples : h_nsamples, f ? neighbours[f - 1].d_histograms : h_histograms,
                                 f ? neighbours[f - 1].d_covariances : h_covariances };
         for (int k = 0; k < 4; ++k) {
@@ -335,10 +389,152 @@ int bcd_hip_denoise_temporal_host(bcd_hip_ctx *ctx, const float *h_colors, const
     }
     RCCHK(ensure(ctx, tp.host_out, bytes[0]));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+bool any_field(const float *const *motion, int n)
+{
+    for (int f = 0; motion && f < n; ++f) if (motion[f]) return true;
+    return false;
+}
+
+} // namespace
+
+// whole uploads of the motion fields that are not NULL into ctx->temporal.motion_host: dev[f] the device copy, or NULL
+int temporal_upload_motion(bcd_hip_ctx *ctx, const float *const *h_motion, int nb_neighbours, int W, int H, const float **dev)
+{
+    auto &tp = ctx->temporal;
+    const size_t bytes = (size_t)W * H * 2 * sizeof(float);
+    for (int f = 0; f < nb_neighbours; ++f) {
+        dev[f] = nullptr;
+        if (!h_motion[f]) continue;
+        RCCHK(ensure(ctx, tp.motion_host[f + 1], bytes));
+        HIPCHK(ctx, hipMemcpyAsync(tp.motion_host[f + 1].p, h_motion[f], bytes, hipMemcpyHostToDevice, ctx->main.stream));
+        dev[f] = (const float *)tp.motion_host[f + 1].p;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
+}
+
+extern "C" {
+
+int bcd_hip_denoise_temporal(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
+                             const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_temporal_call(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out));
+    if (nb_neighbours == 0) return bcd_hip_denoise(ctx, d_colors, d_nsamples, d_histograms, d_covariances, W, H, D, nb_scales, prm, d_out);
+    return temporal_run(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out, nullptr);
+}
+
+int bcd_hip_denoise_temporal_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                                  const bcd_hip_frame *neighbours, int nb_neighbours, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_temporal_call(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out));
+    if (nb_neighbours == 0) return bcd_hip_denoise_host(ctx, h_colors, h_nsamples, h_histograms, h_covariances, W, H, D, nb_scales, prm, h_out);
+    DEVICE_GUARD(ctx);
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
+    RCCHK(upload_frames(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, dev));
     RCCHK(bcd_hip_denoise_temporal(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, W, H, D, nb_scales, prm,
                                    (float *)tp.host_out.p));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, tp.host_out.p, bytes[0], hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, tp.host_out.p, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+// ---- the motion calls ("Motion") -------------------------------------------------------------------------------------------
+int bcd_hip_denoise_temporal_motion(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
+                                    const bcd_hip_frame *neighbours, int nb_neighbours, const float *const *d_motion, int W, int H, int D, int nb_scales,
+                                    const bcd_hip_params *prm, float *d_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_temporal_call(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out));
+    RCCHK(check_motion_list(ctx, d_motion, nb_neighbours, W, H, &d_out, 1));
+    if (!any_field(d_motion, nb_neighbours))
+        return bcd_hip_denoise_temporal(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out);
+    return temporal_run(ctx, d_colors, d_nsamples, d_histograms, d_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, d_out, d_motion);
+}
+
+int bcd_hip_denoise_temporal_motion_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                                         const bcd_hip_frame *neighbours, int nb_neighbours, const float *const *h_motion, int W, int H, int D, int nb_scales,
+                                         const bcd_hip_params *prm, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_temporal_call(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out));
+    RCCHK(check_motion_list(ctx, h_motion, nb_neighbours, W, H, &h_out, 1));
+    if (!any_field(h_motion, nb_neighbours))
+        return bcd_hip_denoise_temporal_host(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out);
+    DEVICE_GUARD(ctx);
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
+    const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
+    RCCHK(temporal_upload_motion(ctx, h_motion, nb_neighbours, W, H, dmv));
+    RCCHK(upload_frames(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, dev));
+    RCCHK(bcd_hip_denoise_temporal_motion(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, dmv, W, H, D,
+                                          nb_scales, prm, (float *)tp.host_out.p));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, tp.host_out.p, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+// ---- the stage calls of the motion path
+int bcd_hip_warp_frame(bcd_hip_ctx *ctx, const bcd_hip_frame *frame, const float *d_motion, int W, int H, int D, const bcd_hip_warped_frame *out, uint8_t *d_valid)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!frame || !out || !d_valid) return bad(ctx, "null argument");
+    if (!frame->d_colors || !frame->d_nsamples || !frame->d_histograms || !frame->d_covariances) return bad(ctx, "null image pointer in the frame");
+    if (frame->reserved) return bad(ctx, "the reserved pointer of a frame must be NULL");
+    if (!out->d_colors || !out->d_nsamples || !out->d_histograms || !out->d_covariances) return bad(ctx, "null image pointer in the destination");
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = 0; p.search_radius = 0;
+    RCCHK(check_params(ctx, W, H, D, &p));
+    {
+        const size_t npix = (size_t)W * H, f4 = sizeof(float);
+        const void *in[5] = { frame->d_colors, frame->d_nsamples, frame->d_histograms, frame->d_covariances, d_motion };
+        const size_t nin[5] = { npix * 3 * f4, npix * f4, npix * D * f4, npix * 6 * f4, npix * 2 * f4 };
+        const void *dst[5] = { out->d_colors, out->d_nsamples, out->d_histograms, out->d_covariances, d_valid };
+        const size_t ndst[5] = { npix * 3 * f4, npix * f4, npix * D * f4, npix * 6 * f4, npix };
+        for (int i = 0; i < 5; ++i) {
+            for (int j = 0; j < 5; ++j) if (in[j] && overlap(dst[i], ndst[i], in[j], nin[j])) return bad(ctx, "a warp destination overlaps an input image or the motion field");
+            for (int j = 0; j < i; ++j) if (overlap(dst[i], ndst[i], dst[j], ndst[j])) return bad(ctx, "two warp destinations overlap");
+        }
+    }
+    DEVICE_GUARD(ctx);
+    hipStream_t st = ctx->main.stream;
+    HIPCHK(ctx, bcd_launch_warp_frame(frame->d_colors, frame->d_nsamples, frame->d_histograms, frame->d_covariances, d_motion, W, H, D, out->d_colors, out->d_nsamples,
+                                      out->d_histograms, out->d_covariances, d_valid, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_valid_downscale(bcd_hip_ctx *ctx, const uint8_t *d_valid, int W, int H, uint8_t *d_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_valid || !d_out) return bad(ctx, "null argument");
+    if (W < 2 || H < 2 || (int64_t)W * H >= (1ll << 31)) return bad(ctx, "the validity image must be at least 2 x 2 (and below 2^31 pixels)");
+    if (overlap(d_out, (size_t)(W / 2) * (H / 2), d_valid, (size_t)W * H)) return bad(ctx, "the destination overlaps the input");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_valid_down(d_valid, W, H, d_out, ctx->main.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_count, const uint8_t *d_valid, int W, int H, int w, int b)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_mask || !d_count || !d_valid) return bad(ctx, "null argument");
+    RCCHK(check_cross_stage(ctx, W, H, 1, w, b));
+    {
+        const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+        if (overlap(d_mask, npix * words * 4, d_count, npix * 4) || overlap(d_mask, npix * words * 4, d_valid, npix) || overlap(d_count, npix * 4, d_valid, npix))
+            return bad(ctx, "the masks, the counts and the validity image overlap");
+    }
+    DEVICE_GUARD(ctx);
+    RCCHK(temporal_gate(ctx, ctx->main, d_valid, W, H, w, b, d_mask, d_count));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
     return BCD_HIP_OK;
 }
 

@@ -5,6 +5,8 @@
 // stream, the chain of full estimates (k_prepare27t, then the unchanged solver and finish kernels) runs once per layer over the same lists, records and
 // work queues.  The count image is filled once: by the first group of the fallback kernel and by the first layer's finish kernels.
 // Every buffer of the call lives in ctx->temporal (grow-only): the workspace's lay_* slices, which bcd_hip_denoise_layers owns, are not touched.
+// bcd_hip_denoise_temporal_layers_motion[_host] and bcd_hip_warp_layers (section 16, "Motion") are layers_run with motion fields: a neighbour with a field is
+// warped (k_warp.hip) before its pyramid is built, its cross masks pass temporal_gate at every scale.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -118,7 +120,9 @@ struct LevelFrame {
 };
 
 // one scale, frames[0] the frame itself at this level: the steps of temporal_scale with the estimate stage per layer
-int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, int L, int W, int H, int D, const bcd_hip_params *prm, int scale, float *const *d_out)
+// valid: null, or per frame the validity bytes of this level (null: the frame is not warped)
+int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, int L, int W, int H, int D, const bcd_hip_params *prm, int scale, float *const *d_out,
+                          const uint8_t *const *valid = nullptr)
 {
     Work &wk = ctx->main;
     auto &tp = ctx->temporal;
@@ -158,6 +162,7 @@ int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, in
         if (f == 0) continue;
         RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
         HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
+        if (valid && valid[f]) RCCHK(temporal_gate(ctx, wk, valid[f], W, H, w, b, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p));
         HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
     }
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
@@ -271,17 +276,20 @@ int bcd_hip_bayes_accumulate_temporal_layers(bcd_hip_ctx *ctx, const bcd_hip_sta
     return bayes_temporal_layers(ctx, ctx->main, lf, d_nsim_total, d_state, W, H, b, min_eig, d_sum, d_count, h_redo);
 }
 
-int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
-                                    int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
+// the checked device call; motion: null, or per neighbour a device motion field or null
+static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
+                      int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const float *const *motion)
 {
-    if (!ctx) return BCD_HIP_EINVAL;
-    RCCHK(check_call(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
     if (nb_neighbours == 0) return bcd_hip_denoise_layers(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
     if (nb_layers == 1) {
         bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
         for (int f = 0; f < nb_neighbours; ++f)
             nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
-        RCCHK(bcd_hip_denoise_temporal(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
+        if (motion)
+            RCCHK(bcd_hip_denoise_temporal_motion(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, nb, nb_neighbours, motion, W, H, D, nb_scales, prm,
+                                                  layers[0].d_out));
+        else
+            RCCHK(bcd_hip_denoise_temporal(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
         memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
         for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
         ctx->layer_count = 1;
@@ -307,6 +315,35 @@ int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const f
         }
     }
     for (int k = 0; k < L; ++k) outs[k] = layers[k].d_out;
+    std::vector<const uint8_t *> valid((size_t)S * nf, nullptr);
+    for (int f = 1; motion && f < nf; ++f) {
+        if (!motion[f - 1]) continue;
+        // the neighbour reprojected into the frame's pixel grid, at full resolution: sample counts, histograms and the first layer by the frame kernel, the further
+        // layers by the layered one (it writes the same validity bytes again); the pyramid is built from the warped images
+        const size_t npix = (size_t)W * H;
+        LevelFrame &l = lv[f];
+        DevBuf(&wb)[4] = tp.warp[f];
+        DevBuf(&lw)[2] = tp.lay_warp[f];
+        RCCHK(ensure(ctx, wb[0], npix * 3 * sizeof(float)));
+        RCCHK(ensure(ctx, wb[1], npix * sizeof(float)));
+        RCCHK(ensure(ctx, wb[2], npix * D * sizeof(float)));
+        RCCHK(ensure(ctx, wb[3], npix * 6 * sizeof(float)));
+        RCCHK(ensure(ctx, lw[0], (size_t)(L - 1) * npix * 3 * sizeof(float)));
+        RCCHK(ensure(ctx, lw[1], (size_t)(L - 1) * npix * 6 * sizeof(float)));
+        RCCHK(ensure(ctx, tp.valid[f][0], npix));
+        HIPCHK(ctx, bcd_launch_warp_frame(l.col[0], l.ns, l.hist, l.cov[0], motion[f - 1], W, H, D, (float *)wb[0].p, (float *)wb[1].p, (float *)wb[2].p, (float *)wb[3].p,
+                                          (uint8_t *)tp.valid[f][0].p, st));
+        BcdWarpLayerTable t = {};
+        for (int k = 1; k < L; ++k) {
+            t.col[k - 1] = l.col[k]; t.cov[k - 1] = l.cov[k];
+            t.ocol[k - 1] = (float *)lw[0].p + (size_t)(k - 1) * npix * 3; t.ocov[k - 1] = (float *)lw[1].p + (size_t)(k - 1) * npix * 6;
+        }
+        HIPCHK(ctx, bcd_launch_warp_layers(t, L - 1, motion[f - 1], W, H, (uint8_t *)tp.valid[f][0].p, st));
+        RCCHK(temporal_valid_levels(ctx, f, W, H, S));
+        l.ns = (const float *)wb[1].p; l.hist = (const float *)wb[2].p; l.col[0] = (const float *)wb[0].p; l.cov[0] = (const float *)wb[3].p;
+        for (int k = 1; k < L; ++k) { l.col[k] = t.ocol[k - 1]; l.cov[k] = t.ocov[k - 1]; }
+        for (int s = 0; s < S; ++s) valid[(size_t)s * nf + f] = (const uint8_t *)tp.valid[f][s].p;
+    }
     for (int s = 1; s < S; ++s) {
         ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
         const size_t np = (size_t)ws[s] * hs[s];
@@ -333,7 +370,7 @@ int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const f
     }
     for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs, one pair of launches for all layers (as merge_layers_on)
         float *const *out = &outs[(size_t)s * L];
-        RCCHK(temporal_layers_scale(ctx, &lv[(size_t)s * nf], nf, L, ws[s], hs[s], D, prm, s, out));
+        RCCHK(temporal_layers_scale(ctx, &lv[(size_t)s * nf], nf, L, ws[s], hs[s], D, prm, s, out, &valid[(size_t)s * nf]));
         if (s < S - 1) {
             const int w2 = ws[s] / 2, h2 = hs[s] / 2;
             const size_t slice = (size_t)w2 * h2 * 3;
@@ -350,11 +387,38 @@ int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const f
     return BCD_HIP_OK;
 }
 
-int bcd_hip_denoise_temporal_layers_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H,
-                                         int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
+// the outputs of the layers, for check_motion_list
+static void layer_outs(const bcd_hip_layer *layers, int L, float **outs) { for (int k = 0; k < L; ++k) outs[k] = layers[k].d_out; }
+static bool any_field(const float *const *motion, int n)
+{
+    for (int f = 0; motion && f < n; ++f) if (motion[f]) return true;
+    return false;
+}
+
+int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
+                                    int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
 {
     if (!ctx) return BCD_HIP_EINVAL;
-    RCCHK(check_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    RCCHK(check_call(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    return layers_run(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, nullptr);
+}
+
+int bcd_hip_denoise_temporal_layers_motion(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                           const float *const *d_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
+                                           int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_call(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    float *outs[ML];
+    layer_outs(layers, nb_layers, outs);
+    RCCHK(check_motion_list(ctx, d_motion, nb_neighbours, W, H, outs, nb_layers));
+    return layers_run(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, any_field(d_motion, nb_neighbours) ? d_motion : nullptr);
+}
+
+// the checked host call; h_motion: null, or per neighbour a host motion field or null
+static int layers_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H,
+                           int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const float *const *h_motion)
+{
     const int L = nb_layers;
     if (nb_neighbours == 0) {
         bcd_hip_host_layer hl[BCD_HIP_MAX_LAYERS];
@@ -365,7 +429,11 @@ int bcd_hip_denoise_temporal_layers_host(bcd_hip_ctx *ctx, const float *h_ns, co
         bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
         for (int f = 0; f < nb_neighbours; ++f)
             nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
-        RCCHK(bcd_hip_denoise_temporal_host(ctx, layers[0].d_colors, h_ns, h_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
+        if (h_motion)
+            RCCHK(bcd_hip_denoise_temporal_motion_host(ctx, layers[0].d_colors, h_ns, h_hist, layers[0].d_covariances, nb, nb_neighbours, h_motion, W, H, D, nb_scales, prm,
+                                                       layers[0].d_out));
+        else
+            RCCHK(bcd_hip_denoise_temporal_host(ctx, layers[0].d_colors, h_ns, h_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
         memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
         for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
         ctx->layer_count = 1;
@@ -397,9 +465,63 @@ int bcd_hip_denoise_temporal_layers_host(bcd_hip_ctx *ctx, const float *h_ns, co
     bcd_hip_layer lay[BCD_HIP_MAX_LAYERS];
     for (int k = 0; k < L; ++k) lay[k] = { dl[k].d_colors, dl[k].d_covariances, (float *)tp.lay_host_out.p + (size_t)k * npix * 3 };
     HIPCHK(ctx, hipStreamSynchronize(st));
-    RCCHK(bcd_hip_denoise_temporal_layers(ctx, dev[0].d_nsamples, dev[0].d_histograms, dev + 1, nb_neighbours, W, H, D, nb_scales, prm, lay, L));
+    const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
+    if (h_motion) RCCHK(temporal_upload_motion(ctx, h_motion, nb_neighbours, W, H, dmv));
+    RCCHK(layers_run(ctx, dev[0].d_nsamples, dev[0].d_histograms, dev + 1, nb_neighbours, W, H, D, nb_scales, prm, lay, L, h_motion ? dmv : nullptr));
     for (int k = 0; k < L; ++k) HIPCHK(ctx, hipMemcpyAsync(layers[k].d_out, lay[k].d_out, bc, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_denoise_temporal_layers_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H,
+                                         int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    return layers_host_run(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, nullptr);
+}
+
+int bcd_hip_denoise_temporal_layers_motion_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                                const float *const *h_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
+                                                int nb_layers)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+    float *outs[ML];
+    layer_outs(layers, nb_layers, outs);
+    RCCHK(check_motion_list(ctx, h_motion, nb_neighbours, W, H, outs, nb_layers));
+    return layers_host_run(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, any_field(h_motion, nb_neighbours) ? h_motion : nullptr);
+}
+
+int bcd_hip_warp_layers(bcd_hip_ctx *ctx, const bcd_hip_frame_layer *layers, int nb_layers, const float *d_motion, int W, int H, const bcd_hip_warped_layer *out,
+                        uint8_t *d_valid)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!layers || !out || !d_valid) return bad(ctx, "null argument");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k)
+        if (!layers[k].d_colors || !layers[k].d_covariances || !out[k].d_colors || !out[k].d_covariances) return bad(ctx, "null image pointer in a layer");
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = 0; p.search_radius = 0;
+    RCCHK(check_params(ctx, W, H, 1, &p));
+    {
+        const size_t npix = (size_t)W * H, bc = npix * 3 * sizeof(float), bv = npix * 6 * sizeof(float);
+        std::vector<std::pair<const void *, size_t>> in, dst;
+        for (int k = 0; k < nb_layers; ++k) {
+            in.push_back({ layers[k].d_colors, bc }); in.push_back({ layers[k].d_covariances, bv });
+            dst.push_back({ out[k].d_colors, bc }); dst.push_back({ out[k].d_covariances, bv });
+        }
+        if (d_motion) in.push_back({ d_motion, npix * 2 * sizeof(float) });
+        dst.push_back({ d_valid, npix });
+        for (size_t i = 0; i < dst.size(); ++i) {
+            for (const auto &x : in) if (overlap(dst[i].first, dst[i].second, x.first, x.second)) return bad(ctx, "a warp destination overlaps an input image or the motion field");
+            for (size_t j = 0; j < i; ++j) if (overlap(dst[i].first, dst[i].second, dst[j].first, dst[j].second)) return bad(ctx, "two warp destinations overlap");
+        }
+    }
+    DEVICE_GUARD(ctx);
+    BcdWarpLayerTable t = {};
+    for (int k = 0; k < nb_layers; ++k) { t.col[k] = layers[k].d_colors; t.cov[k] = layers[k].d_covariances; t.ocol[k] = out[k].d_colors; t.ocov[k] = out[k].d_covariances; }
+    HIPCHK(ctx, bcd_launch_warp_layers(t, nb_layers, d_motion, W, H, d_valid, ctx->main.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
     return BCD_HIP_OK;
 }
 

@@ -276,6 +276,11 @@ class FrameLayers(C.Structure):
     _fields_ = [("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("layers", C.POINTER(FrameLayer)), ("reserved", C.c_void_p)]
 
 
+class WarpedFrame(C.Structure):
+    """bcd_hip_warped_frame: the destination of bcd_hip_warp_frame"""
+    _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p)]
+
+
 class StageFrameLayers(C.Structure):
     """bcd_hip_stage_frame_layers: one frame of bcd_hip_bayes_accumulate_temporal_layers"""
     _fields_ = [("d_colors", C.POINTER(C.c_void_p)), ("d_pixel_cov", C.POINTER(C.c_void_p)), ("d_mask", C.c_void_p)]
@@ -291,6 +296,8 @@ SYMBOLS = [
     "bcd_hip_similarity_masks_guide", "bcd_hip_window_distances_guide", "bcd_hip_gate_masks", "bcd_hip_denoise_guided", "bcd_hip_denoise_guided_host",
     "bcd_hip_similarity_masks_cross", "bcd_hip_window_distances_cross", "bcd_hip_bayes_accumulate_temporal", "bcd_hip_denoise_temporal", "bcd_hip_denoise_temporal_host",
     "bcd_hip_denoise_temporal_layers", "bcd_hip_denoise_temporal_layers_host", "bcd_hip_bayes_accumulate_temporal_layers",
+    "bcd_hip_denoise_temporal_motion", "bcd_hip_denoise_temporal_motion_host", "bcd_hip_denoise_temporal_layers_motion", "bcd_hip_denoise_temporal_layers_motion_host",
+    "bcd_hip_warp_frame", "bcd_hip_warp_layers", "bcd_hip_valid_downscale", "bcd_hip_gate_masks_valid",
     "bcd_hip_selection_create", "bcd_hip_selection_destroy", "bcd_hip_denoise_layers_keep", "bcd_hip_selection_denoise", "bcd_hip_selection_info", "bcd_hip_selection_read",
     "bcd_hip_accum_moments", "bcd_hip_layer_spectral_inverses", "bcd_hip_denoise_begin", "bcd_hip_denoise_wait", "bcd_hip_denoise_band", "bcd_hip_denoise_bands", "bcd_hip_denoise_host", "bcd_hip_denoise_host_ex", "bcd_hip_last_upload_bytes", "bcd_hip_selftest_pack32", "bcd_hip_set_progress_callback",
     "bcd_hip_multi_create", "bcd_hip_multi_destroy", "bcd_hip_multi_last_error", "bcd_hip_multi_get_stats", "bcd_hip_multi_set_progress_callback", "bcd_hip_multi_set_frame_timeout", "bcd_hip_multi_set_comm_trace", "bcd_hip_multi_get_comm_trace", "bcd_hip_multi_denoise_host",
@@ -1056,6 +1063,143 @@ class Context:
         self._chk(L.bcd_hip_denoise_temporal_layers_host(self.h, ns.ctypes.data, hist.ctypes.data, nb, len(neighbours), W, H, D, int(nscales), C.byref(prm), arr,
                                                          len(layers)))
         return outs
+
+    # ---- motion: neighbour frames reprojected by a motion field ("Motion") ----
+    @staticmethod
+    def _motion_array(motions, n, H, W, ptr, size):
+        """the array of nb_neighbours field pointers (None: zero motion for that neighbour); motions None: a NULL list"""
+        if motions is None:
+            return None
+        motions = list(motions)
+        if len(motions) != n:
+            raise ValueError("one motion field (or None) per neighbour expected (%d, not %d)" % (n, len(motions)))
+        arr = (C.c_void_p * max(1, n))()
+        for i, m in enumerate(motions):
+            if m is None:
+                continue
+            if size(m) != H * W * 2:
+                raise ValueError("motion field %d: (H, W, 2) floats of the frame's size are expected" % i)
+            arr[i] = ptr(m)
+        return arr
+
+    def denoise_temporal_motion(self, col, ns, hist, cov, neighbours, motions, nscales, prm, out=None):
+        """bcd_hip_denoise_temporal_motion: denoise_temporal with neighbour i warped into the frame's pixel grid by motions[i] -- an (H, W, 2) float32 device
+        tensor of (dx, dy) per pixel, or None for zero motion -- and the cross masks gated by the validity of the warped patches.  motions=None passes a NULL list."""
+        torch = self.torch
+        H, W, D = hist.shape
+        neighbours = list(neighbours)
+        arr = (Frame * max(len(neighbours), 1))()
+        for i, f in enumerate(neighbours):
+            if tuple(f[0].shape) != (H, W, 3) or f[1].numel() != H * W or tuple(f[2].shape) != (H, W, D) or tuple(f[3].shape) != (H, W, 6):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (_dp(t).value for t in f)
+        mv = self._motion_array(motions, len(neighbours), H, W, lambda t: _dp(t).value, lambda t: t.numel())
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.float32, device=hist.device)
+        L = lib()
+        L.bcd_hip_denoise_temporal_motion.argtypes = [_VP, _VP, _VP, _VP, _VP, C.POINTER(Frame), C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), _VP]
+        torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_denoise_temporal_motion(self.h, _dp(col), _dp(ns), _dp(hist), _dp(cov), arr, len(neighbours), mv, W, H, D, int(nscales), C.byref(prm), _dp(out)))
+        return out
+
+    def denoise_temporal_motion_host(self, col, ns, hist, cov, neighbours, motions, nscales, prm):
+        """bcd_hip_denoise_temporal_motion_host on NumPy float32 arrays -> the denoised frame (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        col, ns, hist, cov = (as32(a) for a in (col, ns, hist, cov))
+        H, W, D = hist.shape
+        keep = [tuple(as32(a) for a in f) for f in neighbours]
+        arr = (Frame * max(len(keep), 1))()
+        for i, f in enumerate(keep):
+            if f[0].shape != (H, W, 3) or f[1].size != H * W or f[2].shape != (H, W, D) or f[3].shape != (H, W, 6):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (a.ctypes.data for a in f)
+        fields = None if motions is None else [None if m is None else as32(m) for m in motions]
+        mv = self._motion_array(fields, len(keep), H, W, lambda a: a.ctypes.data, lambda a: a.size)
+        out = np.empty((H, W, 3), np.float32)
+        L = lib()
+        L.bcd_hip_denoise_temporal_motion_host.argtypes = [_VP, _VP, _VP, _VP, _VP, C.POINTER(Frame), C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), _VP]
+        self._chk(L.bcd_hip_denoise_temporal_motion_host(self.h, col.ctypes.data, ns.ctypes.data, hist.ctypes.data, cov.ctypes.data, arr, len(keep), mv, W, H, D,
+                                                         int(nscales), C.byref(prm), out.ctypes.data))
+        return out
+
+    def denoise_temporal_layers_motion(self, ns, hist, layers, neighbours, motions, nscales, prm, outs=None):
+        """bcd_hip_denoise_temporal_layers_motion: denoise_temporal_layers with neighbour i warped by motions[i] (an (H, W, 2) device tensor or None) -> the outputs"""
+        torch = self.torch
+        H, W, D = hist.shape
+        arr, layers, outs = self._layer_array(layers, outs, H, W, hist.device)
+        neighbours = list(neighbours)
+
+        def check(i, ns_f, hist_f, lay_f):
+            if ns_f.numel() != H * W or tuple(hist_f.shape) != (H, W, D) or any(tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) for c, v in lay_f):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), check, lambda t: _dp(t).value)
+        mv = self._motion_array(motions, len(neighbours), H, W, lambda t: _dp(t).value, lambda t: t.numel())
+        L = lib()
+        L.bcd_hip_denoise_temporal_layers_motion.argtypes = [_VP, _VP, _VP, C.POINTER(FrameLayers), C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
+                                                             C.POINTER(Layer), C.c_int]
+        torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_denoise_temporal_layers_motion(self.h, _dp(ns), _dp(hist), nb, len(neighbours), mv, W, H, D, int(nscales), C.byref(prm), arr, len(layers)))
+        return outs
+
+    def warp_frame(self, col, ns, hist, cov, motion, out=None):
+        """bcd_hip_warp_frame: the four images of a neighbour gathered through `motion` ((H, W, 2) device tensor, or None: zero motion)
+        -> (colours, sample counts, histograms, covariances, validity (H, W) uint8); out: the five destinations"""
+        torch = self.torch
+        H, W, D = hist.shape
+        if out is None:
+            out = [torch.empty_like(t) for t in (col, ns, hist, cov)] + [torch.empty((H, W), dtype=torch.uint8, device=hist.device)]
+        src, dst = Frame(), WarpedFrame()
+        src.d_colors, src.d_nsamples, src.d_histograms, src.d_covariances = (_dp(t).value for t in (col, ns, hist, cov))
+        dst.d_colors, dst.d_nsamples, dst.d_histograms, dst.d_covariances = (_dp(t).value for t in out[:4])
+        if motion is not None and motion.numel() != H * W * 2:
+            raise ValueError("the motion field must hold (H, W, 2) floats")
+        L = lib()
+        L.bcd_hip_warp_frame.argtypes = [_VP, C.POINTER(Frame), _VP, C.c_int, C.c_int, C.c_int, C.POINTER(WarpedFrame), _VP]
+        torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_warp_frame(self.h, C.byref(src), _dp(motion) if motion is not None else None, W, H, D, C.byref(dst), _dp(out[4])))
+        return tuple(out)
+
+    def warp_layers(self, layers, motion, out=None):
+        """bcd_hip_warp_layers: `layers` is a list of (colours, covariances) device tensors of one neighbour -> ([(colours, covariances), ...], validity (H, W) uint8);
+        out: (list of destination pairs, validity)"""
+        torch = self.torch
+        layers = list(layers)
+        H, W, _ = layers[0][0].shape
+        if out is None:
+            out = ([(torch.empty_like(c), torch.empty_like(v)) for c, v in layers], torch.empty((H, W), dtype=torch.uint8, device=layers[0][0].device))
+        dsts, valid = out
+        src, dst = (FrameLayer * max(1, len(layers)))(), (FrameLayer * max(1, len(layers)))()
+        for k, ((c, v), (oc, ov)) in enumerate(zip(layers, dsts)):
+            if tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) or oc.numel() != H * W * 3 or ov.numel() != H * W * 6:
+                raise ValueError("layer %d: colours (H, W, 3) and covariances (H, W, 6) are expected" % k)
+            src[k].d_colors, src[k].d_covariances, dst[k].d_colors, dst[k].d_covariances = _dp(c).value, _dp(v).value, _dp(oc).value, _dp(ov).value
+        L = lib()
+        L.bcd_hip_warp_layers.argtypes = [_VP, C.POINTER(FrameLayer), C.c_int, _VP, C.c_int, C.c_int, C.POINTER(FrameLayer), _VP]
+        torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_warp_layers(self.h, src, len(layers), _dp(motion) if motion is not None else None, W, H, dst, _dp(valid)))
+        return dsts, valid
+
+    def valid_downscale(self, valid):
+        """bcd_hip_valid_downscale: the validity bytes (H, W) of a level -> those of the next level (H // 2, W // 2)"""
+        H, W = valid.shape
+        out = self.torch.empty((H // 2, W // 2), dtype=self.torch.uint8, device=valid.device)
+        L = lib()
+        L.bcd_hip_valid_downscale.argtypes = [_VP, _VP, C.c_int, C.c_int, _VP]
+        self.torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_valid_downscale(self.h, _dp(valid), W, H, _dp(out)))
+        return out
+
+    def gate_masks_valid(self, mask, count, valid, w, b):
+        """bcd_hip_gate_masks_valid: the cross masks (H, W, words) and counts (H, W) of one neighbour gated IN PLACE by the validity bytes (H, W) of its level"""
+        H, W = valid.shape
+        if mask.numel() != H * W * (((2 * b + 1) ** 2 + 31) // 32) or count.numel() != H * W:
+            raise ValueError("masks (H, W, words) and counts (H, W) of the validity image's size are expected")
+        L = lib()
+        L.bcd_hip_gate_masks_valid.argtypes = [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int]
+        self.torch.cuda.synchronize(self.device)
+        self._chk(L.bcd_hip_gate_masks_valid(self.h, _dp(mask), _dp(count), _dp(valid), W, H, int(w), int(b)))
+        return mask, count
 
     def denoise_temporal_stages(self, col, ns, hist, cov, neighbours, prm):
         """One scale of the denoising of a frame with similar patches from neighbouring frames of its sequence, composed from the

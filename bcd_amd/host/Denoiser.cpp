@@ -365,7 +365,9 @@ namespace bcd
 				{
 					return i_pImage && i_pImage->getWidth() == m_width && i_pImage->getHeight() == m_height && i_pImage->getDepth() == i_depth;
 				};
-				bool ok = !(m_prefilterThresholdStDevFactor > 0.f) && m_neighbourLayers.size() == m_neighbourFrames.size();
+				bool ok = !(m_prefilterThresholdStDevFactor > 0.f) && m_neighbourLayers.size() == m_neighbourFrames.size() && m_neighbourMotion.size() == m_neighbourFrames.size();
+				std::vector<const float*> motion(m_neighbourFrames.size(), nullptr); // (a neighbour without a field: zero motion)
+				bool anyMotion = false;
 				for(size_t k = 0; ok && k < m_neighbourFrames.size(); ++k)
 				{
 					const DenoiserInputs& f = m_neighbourFrames[k];
@@ -373,8 +375,14 @@ namespace bcd
 							&& m_neighbourLayers[k].size() == nbOfLayers; // one layer of the neighbour per added layer of the frame
 					for(size_t j = 0; ok && j < nbOfLayers; ++j)
 						ok = fits(m_neighbourLayers[k][j].m_pColors, 3) && fits(m_neighbourLayers[k][j].m_pSampleCovariances, 6);
+					ok = ok && (!m_neighbourMotion[k] || fits(m_neighbourMotion[k], 2));
 					if(!ok)
 						break;
+					if(m_neighbourMotion[k])
+					{
+						motion[k] = m_neighbourMotion[k]->getDataPtr();
+						anyMotion = true;
+					}
 					frames[k] = { f.m_pColors->getDataPtr(), f.m_pNbOfSamples->getDataPtr(), f.m_pHistograms->getDataPtr(), f.m_pSampleCovariances->getDataPtr(), nullptr };
 					bcd_hip_frame_layer* pLayers = &frameLayers[k * (nbOfLayers + 1)];
 					pLayers[0] = { f.m_pColors->getDataPtr(), f.m_pSampleCovariances->getDataPtr() }; // the primary images are layer 0
@@ -385,11 +393,15 @@ namespace bcd
 				if(!ok)
 				{
 					cerr << "Aborting denoising: a neighbour frame needs all four images in the frame's size and, beside added layers, exactly one layer "
-							"(addNeighbourFrameLayer) per added layer in that size; neighbour frames do not combine with the spike prefilter" << endl;
+							"(addNeighbourFrameLayer) per added layer in that size, a motion field (setNeighbourMotion) has 2 channels in that size; neighbour frames do "
+							"not combine with the spike prefilter" << endl;
 					bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
 					return false;
 				}
-				if(nbOfLayers == 0)
+				if(nbOfLayers == 0 && anyMotion)
+					rc = bcd_hip_denoise_temporal_motion_host(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], frames.data(), int(frames.size()), motion.data(), m_width, m_height, depth,
+							i_nbOfScales, &prm, result.getDataPtr());
+				else if(nbOfLayers == 0)
 					rc = bcd_hip_denoise_temporal_host(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], frames.data(), int(frames.size()), m_width, m_height, depth, i_nbOfScales, &prm,
 							result.getDataPtr());
 				else
@@ -401,8 +413,12 @@ namespace bcd
 						layerResults[k].resize(m_width, m_height, 3);
 						layers[k + 1] = { m_layers[k].m_pColors->getDataPtr(), m_layers[k].m_pSampleCovariances->getDataPtr(), layerResults[k].getDataPtr() };
 					}
-					rc = bcd_hip_denoise_temporal_layers_host(rSlot.m_pCtx, pIn[1], pIn[2], layeredFrames.data(), int(layeredFrames.size()), m_width, m_height, depth, i_nbOfScales,
-							&prm, layers.data(), int(layers.size()));
+					if(anyMotion)
+						rc = bcd_hip_denoise_temporal_layers_motion_host(rSlot.m_pCtx, pIn[1], pIn[2], layeredFrames.data(), int(layeredFrames.size()), motion.data(), m_width, m_height,
+								depth, i_nbOfScales, &prm, layers.data(), int(layers.size()));
+					else
+						rc = bcd_hip_denoise_temporal_layers_host(rSlot.m_pCtx, pIn[1], pIn[2], layeredFrames.data(), int(layeredFrames.size()), m_width, m_height, depth, i_nbOfScales,
+								&prm, layers.data(), int(layers.size()));
 					if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
 						for(size_t k = 0; k < nbOfLayers; ++k)
 						{
@@ -487,6 +503,7 @@ namespace bcd
 		engine.setLayers(m_layers);
 		engine.setNeighbourFrames(m_neighbourFrames);
 		engine.setNeighbourFrameLayers(m_neighbourLayers);
+		engine.setNeighbourMotions(m_neighbourMotion);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);

@@ -6,6 +6,7 @@
 // build does not have) is declined with a note and served by the device; under BCD_STRICT_CPU_REQUEST=1 it is refused with an error before any file is read.
 // --layer <color.exr> <cov.exr> <out.exr> (repeatable) denoises a further colour layer with the filter of the -i image (one selection of similar patches for all).
 // --neighbour-layer <color.exr> <cov.exr> hands the most recent --neighbour the matching layer (the k-th pairs with the k-th --layer).
+// --neighbour-motion <mv.exr> hands the most recent --neighbour its motion field ((dx, dy) in the first two channels).
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
 #include "Chronometer.h"
 #include "DeepImage.h"
@@ -49,7 +50,7 @@ namespace
 		std::vector<int> m_devices = std::vector<int>(1, 0);
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
 		struct NeighbourLayer { string m_colorPath, m_covariancePath; Deepimf m_colorImage, m_covarianceImage; };
-		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ };
+		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ string m_motionPath; Deepimf m_motionImage; /* --neighbour-motion */ };
 		std::vector<Neighbour> m_neighbours; // --neighbour, in command-line order
 		std::vector<Layer> m_layers; // --layer, in command-line order
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
@@ -77,6 +78,9 @@ namespace
 		cout << "Optional arguments list:" << endl;
 		cout << "    -a <file>            The file path to the .bcd.json file containing arguments for the program" << endl;
 		cout << "    --neighbour <frame>  A neighbouring frame of the sequence that lends its statistics (repeatable, at most 4; expects <frame>_hist.exr / <frame>_cov.exr beside it)" << endl;
+		cout << "    --neighbour-motion <mv.exr>" << endl;
+		cout << "                         the motion field of the most recent --neighbour: pixel (x, y) of the frame shows what pixel (x + dx, y + dy) of that" << endl;
+		cout << "                         neighbour shows, (dx, dy) in the first two channels, rounded to whole pixels; NaN marks a disoccluded pixel" << endl;
 		cout << "    --neighbour-layer <color> <cov>" << endl;
 		cout << "                         a colour layer of the most recent --neighbour: the k-th one pairs with the k-th --layer; every neighbour" << endl;
 		cout << "                         needs exactly one per --layer (one selection over all frames then serves every layer; needs -p 0)" << endl;
@@ -160,6 +164,23 @@ namespace
 				if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamplesImage, (stem + "_hist.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour histogram image file '" << stem << "_hist.exr'" << endl; return false; }
 				Utils::separateNbOfSamplesFromHistogram(rNb.m_histogramImage, rNb.m_nbOfSamplesImage, histAndNbOfSamplesImage);
 				if(!ImageIO::loadMultiChannelsEXR(rNb.m_covarianceImage, (stem + "_cov.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour covariance matrix image file '" << stem << "_cov.exr'" << endl; return false; }
+				continue;
+			}
+			if(flag == "--neighbour-motion")
+			{	// the motion field of the most recent --neighbour: (dx, dy) in the first two channels
+				if(i + 1 >= argc) { cout << "ERROR in program arguments: expecting <mv.exr> after --neighbour-motion" << endl; return false; }
+				if(a.m_neighbours.empty()) { cout << "ERROR in program arguments: --neighbour-motion follows the --neighbour it belongs to" << endl; return false; }
+				ProgramArguments::Neighbour& rNb = a.m_neighbours.back();
+				rNb.m_motionPath = argv[++i];
+				Deepimf loaded;
+				if(!ImageIO::loadMultiChannelsEXR(loaded, rNb.m_motionPath.c_str())) { cout << "ERROR in program arguments: couldn't load neighbour motion image file '" << rNb.m_motionPath << "'" << endl; return false; }
+				if(loaded.getDepth() < 2) { cout << "ERROR in program arguments: neighbour motion image '" << rNb.m_motionPath << "' needs two channels (dx, dy)" << endl; return false; }
+				rNb.m_motionImage.resize(loaded.getWidth(), loaded.getHeight(), 2);
+				for(int px = 0, n = loaded.getWidth() * loaded.getHeight(), d = loaded.getDepth(); px < n; ++px)
+				{
+					rNb.m_motionImage.get(2 * px) = loaded.get(d * px);
+					rNb.m_motionImage.get(2 * px + 1) = loaded.get(d * px + 1);
+				}
 				continue;
 			}
 			if(flag == "--neighbour-layer")
@@ -430,6 +451,11 @@ namespace
 		for(ProgramArguments::Neighbour& rNb : a.m_neighbours)
 		{
 			const int w = a.m_colorImage.getWidth(), h = a.m_colorImage.getHeight();
+			if(!rNb.m_motionPath.empty() && (rNb.m_motionImage.getWidth() != w || rNb.m_motionImage.getHeight() != h))
+			{
+				cout << "ERROR in program arguments: neighbour motion image '" << rNb.m_motionPath << "' is not " << w << "x" << h << " like the input color image" << endl;
+				return false;
+			}
 			if(rNb.m_layers.size() != a.m_layers.size())
 			{
 				cout << "ERROR in program arguments: neighbour '" << rNb.m_colorPath << "' has " << rNb.m_layers.size() << " --neighbour-layer argument(s) but there are "
@@ -535,6 +561,8 @@ namespace
 			pSettings->addNeighbourFrame(frame);
 			for(ProgramArguments::NeighbourLayer& rLayer : rNb.m_layers)
 				pSettings->addNeighbourFrameLayer(pSettings->getNeighbourFrames().size() - 1, &rLayer.m_colorImage, &rLayer.m_covarianceImage);
+			if(!rNb.m_motionPath.empty())
+				pSettings->setNeighbourMotion(pSettings->getNeighbourFrames().size() - 1, &rNb.m_motionImage);
 		}
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)

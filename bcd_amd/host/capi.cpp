@@ -547,13 +547,14 @@ int bcdcore_denoise_layers(const float* cols, const float* covs, const float* ns
 
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames of the sequence (addNeighbourFrame): nbCols etc. hold nbOfNeighbours images one behind
 /// the other.  afterClear != 0: clearNeighbourFrames() and a second denoise() follow, whose result replaces the first.  Returns denoise()'s bool.
-int bcdcore_denoise_temporal(const float* col, const float* ns, const float* hist, const float* cov, const float* nbCols, const float* nbNs, const float* nbHists,
-		const float* nbCovs, int nbOfNeighbours, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder, float skipProbability, unsigned seed,
-		int afterClear, float* out)
+/// motions: null, or nbOfNeighbours motion fields (W x H x 2) one behind the other, of which neighbour k's is handed to setNeighbourMotion when hasMotion[k] != 0
+static int denoiseTemporal(const float* col, const float* ns, const float* hist, const float* cov, const float* nbCols, const float* nbNs, const float* nbHists,
+		const float* nbCovs, int nbOfNeighbours, const float* motions, const int* hasMotion, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder,
+		float skipProbability, unsigned seed, int afterClear, float* out)
 {
 	Deepimf cImg(W, H, 3), nImg(W, H, 1), hImg(W, H, D), vImg(W, H, 6), oImg(W, H, 3);
 	cImg.copyDataFrom(col); nImg.copyDataFrom(ns); hImg.copyDataFrom(hist); vImg.copyDataFrom(cov);
-	std::vector<Deepimf> c(nbOfNeighbours), n(nbOfNeighbours), h(nbOfNeighbours), v(nbOfNeighbours);
+	std::vector<Deepimf> c(nbOfNeighbours), n(nbOfNeighbours), h(nbOfNeighbours), v(nbOfNeighbours), mv(nbOfNeighbours);
 	const size_t npix = size_t(W) * H;
 	DenoiserInputs in;
 	in.m_pColors = &cImg; in.m_pNbOfSamples = &nImg; in.m_pHistograms = &hImg; in.m_pSampleCovariances = &vImg;
@@ -579,6 +580,12 @@ int bcdcore_denoise_temporal(const float* col, const float* ns, const float* his
 		DenoiserInputs f;
 		f.m_pColors = &c[k]; f.m_pNbOfSamples = &n[k]; f.m_pHistograms = &h[k]; f.m_pSampleCovariances = &v[k];
 		pSettings->addNeighbourFrame(f);
+		if(motions && hasMotion[k])
+		{
+			mv[k].resize(W, H, 2);
+			mv[k].copyDataFrom(motions + k * npix * 2);
+			pSettings->setNeighbourMotion(size_t(k), &mv[k]);
+		}
 	}
 	d->setInputs(in);
 	d->setOutputs(o);
@@ -595,13 +602,30 @@ int bcdcore_denoise_temporal(const float* col, const float* ns, const float* his
 	return ok ? 1 : 0;
 }
 
+int bcdcore_denoise_temporal(const float* col, const float* ns, const float* hist, const float* cov, const float* nbCols, const float* nbNs, const float* nbHists,
+		const float* nbCovs, int nbOfNeighbours, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder, float skipProbability, unsigned seed,
+		int afterClear, float* out)
+{
+	return denoiseTemporal(col, ns, hist, cov, nbCols, nbNs, nbHists, nbCovs, nbOfNeighbours, nullptr, nullptr, W, H, D, nscales, tau, b, minEig, randomOrder, skipProbability,
+			seed, afterClear, out);
+}
+
+/// ... with motion fields (setNeighbourMotion): motions holds nbOfNeighbours fields of W x H x 2 one behind the other, hasMotion[k] == 0 leaves neighbour k without
+int bcdcore_denoise_temporal_motion(const float* col, const float* ns, const float* hist, const float* cov, const float* nbCols, const float* nbNs, const float* nbHists,
+		const float* nbCovs, int nbOfNeighbours, const float* motions, const int* hasMotion, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder,
+		float skipProbability, unsigned seed, int afterClear, float* out)
+{
+	return denoiseTemporal(col, ns, hist, cov, nbCols, nbNs, nbHists, nbCovs, nbOfNeighbours, motions, hasMotion, W, H, D, nscales, tau, b, minEig, randomOrder,
+			skipProbability, seed, afterClear, out);
+}
+
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames AND colour layers (addLayer, addNeighbourFrame, addNeighbourFrameLayer).  cols / covs hold
 /// nbOfLayers images of the frame one behind the other (layer 0 = the primary images), nbCols / nbCovs nbOfNeighbours x nbOfLayers images (neighbour-major),
 /// nbNs / nbHists one image per neighbour.  The last neighbour gets dropLayers fewer layers than the frame (> 0: denoise() must refuse).  afterClear != 0:
 /// clearNeighbourFrames() and a second denoise() follow (the plain layered call), whose results replace the first.  Returns denoise()'s bool.
-int bcdcore_denoise_temporal_layers(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs, const float* nbNs,
-		const float* nbHists, int nbOfNeighbours, int nbOfLayers, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder,
-		float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs)
+static int denoiseTemporalLayers(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs, const float* nbNs,
+		const float* nbHists, int nbOfNeighbours, int nbOfLayers, const float* motions, const int* hasMotion, int W, int H, int D, int nscales, float tau, int b, float minEig,
+		int randomOrder, float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs)
 {
 	const size_t npix = size_t(W) * H;
 	Deepimf nImg(W, H, 1), hImg(W, H, D);
@@ -613,7 +637,7 @@ int bcdcore_denoise_temporal_layers(const float* cols, const float* covs, const 
 		c[k].copyDataFrom(cols + k * npix * 3); v[k].copyDataFrom(covs + k * npix * 6);
 		o[k] = c[k]; // (the multiscale path wants the output pre-sized like the input)
 	}
-	std::vector<Deepimf> fn(nbOfNeighbours), fh(nbOfNeighbours), fc(size_t(nbOfNeighbours) * nbOfLayers), fv(size_t(nbOfNeighbours) * nbOfLayers);
+	std::vector<Deepimf> fn(nbOfNeighbours), fh(nbOfNeighbours), fc(size_t(nbOfNeighbours) * nbOfLayers), fv(size_t(nbOfNeighbours) * nbOfLayers), mv(nbOfNeighbours);
 	DenoiserInputs in;
 	in.m_pColors = &c[0]; in.m_pNbOfSamples = &nImg; in.m_pHistograms = &hImg; in.m_pSampleCovariances = &v[0];
 	DenoiserOutputs out;
@@ -649,6 +673,12 @@ int bcdcore_denoise_temporal_layers(const float* cols, const float* covs, const 
 		const int given = nbOfLayers - (f == nbOfNeighbours - 1 ? dropLayers : 0);
 		for(int k = 1; k < given; ++k)
 			pSettings->addNeighbourFrameLayer(size_t(f), &fc[size_t(f) * nbOfLayers + k], &fv[size_t(f) * nbOfLayers + k]);
+		if(motions && hasMotion[f])
+		{
+			mv[f].resize(W, H, 2);
+			mv[f].copyDataFrom(motions + f * npix * 2);
+			pSettings->setNeighbourMotion(size_t(f), &mv[f]);
+		}
 	}
 	d->setInputs(in);
 	d->setOutputs(out);
@@ -665,6 +695,23 @@ int bcdcore_denoise_temporal_layers(const float* cols, const float* covs, const 
 		for(int k = 0; k < nbOfLayers; ++k)
 			o[k].copyDataTo(outs + k * npix * 3);
 	return ok ? 1 : 0;
+}
+
+int bcdcore_denoise_temporal_layers(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs, const float* nbNs,
+		const float* nbHists, int nbOfNeighbours, int nbOfLayers, int W, int H, int D, int nscales, float tau, int b, float minEig, int randomOrder,
+		float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs)
+{
+	return denoiseTemporalLayers(cols, covs, ns, hist, nbCols, nbCovs, nbNs, nbHists, nbOfNeighbours, nbOfLayers, nullptr, nullptr, W, H, D, nscales, tau, b, minEig,
+			randomOrder, skipProbability, seed, dropLayers, afterClear, outs);
+}
+
+/// ... with motion fields, as bcdcore_denoise_temporal_motion takes them
+int bcdcore_denoise_temporal_layers_motion(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs,
+		const float* nbNs, const float* nbHists, int nbOfNeighbours, int nbOfLayers, const float* motions, const int* hasMotion, int W, int H, int D, int nscales, float tau,
+		int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs)
+{
+	return denoiseTemporalLayers(cols, covs, ns, hist, nbCols, nbCovs, nbNs, nbHists, nbOfNeighbours, nbOfLayers, motions, hasMotion, W, H, D, nscales, tau, b, minEig,
+			randomOrder, skipProbability, seed, dropLayers, afterClear, outs);
 }
 
 /// ONE MultiscaleDenoiser (or Denoiser), denoise() called twice with -r 0 and the given m_nbOfCores: the written-back core count must not

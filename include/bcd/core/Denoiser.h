@@ -89,10 +89,26 @@ namespace bcd
 		/// union of the sets; only the frame itself is denoised.  Each neighbour brings all four images, of the frame's width, height and histogram depth.
 		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with the spike
 		/// prefilter, the moment selection or feature buffers.  With no neighbour denoise() is what it always was.
-		void addNeighbourFrame(const DenoiserInputs& i_rFrame) { m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); }
-		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); }
+		void addNeighbourFrame(const DenoiserInputs& i_rFrame) { m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); m_neighbourMotion.push_back(nullptr); }
+		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); m_neighbourMotion.clear(); }
 		const std::vector<DenoiserInputs>& getNeighbourFrames() const { return m_neighbourFrames; }
-		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames) { m_neighbourFrames = i_rFrames; m_neighbourLayers.assign(i_rFrames.size(), std::vector<NeighbourLayer>()); }
+		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames)
+		{
+			m_neighbourFrames = i_rFrames;
+			m_neighbourLayers.assign(i_rFrames.size(), std::vector<NeighbourLayer>());
+			m_neighbourMotion.assign(i_rFrames.size(), nullptr);
+		}
+		/// The motion field of neighbour i_neighbour (bcd_hip_denoise_temporal_motion_host): a 2-channel image of the frame's size, (dx, dy) per pixel -- pixel
+		/// (l, c) of the frame shows what pixel (l + round(dy), c + round(dx)) of the neighbour shows, rounding to nearest even; NaN marks a disoccluded pixel.
+		/// The neighbour is reprojected into the frame's pixel grid before its similar patches are searched, and members whose patch holds a pixel without a
+		/// source are left out.  nullptr clears the field (zero motion); clearNeighbourFrames() clears all.  An index that names no neighbour is ignored.
+		void setNeighbourMotion(size_t i_neighbour, const DeepImage<float>* i_pMotion)
+		{
+			if(i_neighbour < m_neighbourMotion.size())
+				m_neighbourMotion[i_neighbour] = i_pMotion;
+		}
+		const std::vector<const DeepImage<float>*>& getNeighbourMotions() const { return m_neighbourMotion; }
+		void setNeighbourMotions(const std::vector<const DeepImage<float>*>& i_rMotions) { m_neighbourMotion = i_rMotions; m_neighbourMotion.resize(m_neighbourFrames.size(), nullptr); }
 		/// Added layers beside neighbour frames (bcd_hip_denoise_temporal_layers_host): neighbour i_neighbour (the index in the order of addNeighbourFrame) brings
 		/// the colours and sample covariances of one more layer; its k-th call pairs with the k-th addLayer.  denoise() accepts layers beside neighbours when
 		/// every neighbour has exactly one such layer per addLayer, in the frame's size, and refuses anything else.  An index that names no neighbour is ignored.
@@ -127,6 +143,7 @@ namespace bcd
 		std::vector<ColorLayer> m_layers;
 		std::vector<DenoiserInputs> m_neighbourFrames;
 		std::vector<std::vector<NeighbourLayer>> m_neighbourLayers; // [neighbour][added layer], as long as m_neighbourFrames
+		std::vector<const DeepImage<float>*> m_neighbourMotion;     // [neighbour] its motion field or nullptr, as long as m_neighbourFrames
 	};
 
 	/// The engine contexts behind denoise() (device workspaces, pyramids, staging buffers: grow-only, sized by the largest frame seen,

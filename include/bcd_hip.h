@@ -318,7 +318,7 @@ int bcd_hip_denoise_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const floa
  * Multiscale: every neighbour gets its own pyramid, built with the reducers of the frame's (colours averaged, counts and histograms summed, covariances
  * weighted by the counts); scale s uses level s of every frame; the merge, the visiting order, the per-scale seeds and the -m / -r semantics are those of
  * bcd_hip_denoise.  The scales run one after the other on the context's main workspace.  With nb_neighbours = 0 the call IS bcd_hip_denoise
- * (bcd_hip_denoise_host): it delegates.  Motion vectors (a per-pixel window centre in the neighbour frame) are not supported: `reserved` must be NULL.
+ * (bcd_hip_denoise_host): it delegates.  Motion vectors arrive through bcd_hip_denoise_temporal_motion below; `reserved` must be NULL.
  * Refused before any device work, with a message, the context staying usable: with neighbours, any geometry but patch radius 1 and search radius 6
  * (BCD_HIP_EUNSUPPORTED); nb_neighbours outside 0 .. 4; a null image; a non-NULL `reserved`; an output that is or overlaps an input; what bcd_hip_denoise
  * refuses.  Kept selections, the moment and the feature-gated selection, row bands and bcd_hip_multi_* do not combine with this call; colour layers do
@@ -358,7 +358,7 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
  * Refused before any device work, with a message, the context staying usable: everything bcd_hip_denoise_temporal and bcd_hip_denoise_layers refuse; a NULL
  * layer list in a neighbour; a NULL image in any layer of any frame; a non-NULL `reserved`; an output that is, or overlaps, any input of any frame or
  * another output; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).  Kept selections, the moment and the
- * feature-gated selection, the spike prefilter, row bands, bcd_hip_multi_* and motion vectors do not combine with this call.
+ * feature-gated selection, the spike prefilter, row bands and bcd_hip_multi_* do not combine with this call; motion vectors arrive through bcd_hip_denoise_temporal_layers_motion below.
  *   _host: every pointer is a host pointer; whole uploads (no streaming, no spike prefilter), the resident call, one download per layer: the same result.
  *   _bayes_accumulate_temporal_layers: the estimate stage -- the twin of bcd_hip_bayes_accumulate_temporal for nb_layers layers on ONE selection.  frames[f]
  *             holds host arrays of nb_layers device pointers (the colours and the per-pixel covariances of that frame's layers) and the frame's masks, [0]
@@ -381,6 +381,59 @@ typedef struct { const float *const *d_colors; const float *const *d_pixel_cov; 
 int bcd_hip_bayes_accumulate_temporal_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_frame_layers *frames, int nb_frames, int nb_layers, const int32_t *d_nsim_total,
                                              const uint8_t *d_state, int W, int H, int patch_radius, int search_radius, float min_eigen_value, float *const *d_sum,
                                              int32_t *d_count, int32_t *h_redo);
+
+/* ---- motion: neighbour frames reprojected by a motion field before the cross passes ("Motion") ----
+ * The temporal calls above search every neighbour in the window around the SAME pixel, which is right for a locked camera only.  The motion calls take
+ * one motion field per neighbour, reproject ("warp") that neighbour into the frame's pixel grid with an integer gather, and then run the calls above on the
+ * warped neighbours, with one addition: an explicit validity gate on the cross masks.  `reserved` of bcd_hip_frame / bcd_hip_frame_layers keeps its
+ * meaning (NULL, or refused): the fields arrive through d_motion.
+ *   - Motion field of neighbour f: W*H*2 floats, interleaved (dx, dy) per pixel in the frame's pixel order.  Pixel (l, c) of the frame shows what pixel
+ *     (l + ry, c + rx) of neighbour f shows, rx = rintf(dx), ry = rintf(dy), round to nearest even.  d_motion has nb_neighbours entries; a NULL entry means
+ *     zero motion for that neighbour (it is neither copied nor gated).
+ *   - Validity: valid_f(l, c) = 1 when dx and dy are finite, |dx|, |dy| < 2^24 and the source pixel lies inside the image, else 0.  A renderer marks a
+ *     disoccluded pixel by writing NaN.
+ *   - Warp: a valid pixel of the warped neighbour takes the source pixel's colours, sample count, histogram and covariance -- in the layered call the
+ *     colours and covariance of every layer -- bit for bit; an invalid pixel is +0.0f in all of them.  Nothing is interpolated: sub-pixel motion is rounded.
+ *   - Coarser scales: the warped neighbour's pyramid is built by the reducers of the frame's; a coarse pixel is valid when all four pixels
+ *     (2l, 2l + 1) x (2c, 2c + 1) the reducers read for it are valid (a last odd line or column is read by no coarse pixel).
+ *   - Gate: pvalid_f(q) = AND of valid_f(q + o) over the (2w+1)^2 patch offsets.  For every main pixel p and window displacement delta, bit delta of the
+ *     cross mask of neighbour f is cleared unless pvalid_f(p + delta); |S_f| is the popcount of what remains.  The gate runs at every scale between the
+ *     cross masks and the sum of the counts, so the marking and the estimate never see a member whose patch holds an invalid pixel.  (A pixel of zeros is
+ *     not reliably dissimilar by itself: its distance terms are 0/0 only where the frame's pixel has a bin above 1.)
+ *   - Everything else is the plain call's: member order, the 3P + 1 rule, the marking on the in-frame masks, multiscale, seeds, statistics.
+ * With every field NULL the calls delegate to their plain twins.  With zero-valued fields every pixel is valid and the result is the plain call's.
+ * Extra device memory per warped neighbour: (10 + D) * 4 bytes per pixel (280 at D = 60), 36 per extra layer, and 4/3 + 1 bytes of validity.
+ * Refused before any device work, with a message, the context staying usable: everything the plain calls refuse; a NULL d_motion with neighbours present; an
+ * output that overlaps a motion field.  Sub-pixel resampling, consistency checks, search radius 12 and the combinations the plain calls exclude stay out.
+ *   _host: every pointer is a host pointer (the fields too); whole uploads, the resident call, one download.
+ * Stage calls (they synchronise):
+ *   _warp_frame: the four images of `frame` gathered through d_motion (NULL: zero motion) into `out`, d_valid W*H bytes.  D % 4 == 0 with 16-byte aligned
+ *             histogram images moves 16 bytes per lane; anything else is served element by element.  A destination that overlaps an input, the field or
+ *             another destination is refused.
+ *   _warp_layers: the same for the colours and covariances of nb_layers layers (1 .. BCD_HIP_MAX_LAYERS).
+ *   _valid_downscale: the validity of the (W / 2) x (H / 2) level; W, H >= 2.
+ *   _gate_masks_valid: d_mask (W*H*words) and d_count (W*H) of one neighbour, as bcd_hip_similarity_masks_cross writes them, gated IN PLACE with the
+ *             validity bytes d_valid of that level.  The window is clipped as there: a bit whose pixel is not a main pixel is cleared, a pixel that is not
+ *             a main pixel gets empty masks and count 0.  Geometry as bcd_hip_similarity_masks_cross. */
+typedef struct { float *d_colors, *d_nsamples, *d_histograms, *d_covariances; } bcd_hip_warped_frame;
+typedef struct { float *d_colors; float *d_covariances; } bcd_hip_warped_layer;
+int bcd_hip_denoise_temporal_motion(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances,
+                                    const bcd_hip_frame *neighbours, int nb_neighbours, const float *const *d_motion /* nb_neighbours entries, each NULL or W*H*2 */,
+                                    int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float *d_out);
+int bcd_hip_denoise_temporal_motion_host(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                                         const bcd_hip_frame *neighbours /* host pointers */, int nb_neighbours, const float *const *h_motion, int W, int H, int D,
+                                         int nb_scales, const bcd_hip_params *prm, float *h_out);
+int bcd_hip_denoise_temporal_layers_motion(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms, const bcd_hip_frame_layers *neighbours,
+                                           int nb_neighbours, const float *const *d_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                                           const bcd_hip_layer *layers, int nb_layers);
+int bcd_hip_denoise_temporal_layers_motion_host(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, const bcd_hip_frame_layers *neighbours,
+                                                int nb_neighbours, const float *const *h_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                                                const bcd_hip_layer *layers /* host pointers */, int nb_layers);
+int bcd_hip_warp_frame(bcd_hip_ctx *ctx, const bcd_hip_frame *frame, const float *d_motion, int W, int H, int D, const bcd_hip_warped_frame *out, uint8_t *d_valid);
+int bcd_hip_warp_layers(bcd_hip_ctx *ctx, const bcd_hip_frame_layer *layers, int nb_layers, const float *d_motion, int W, int H, const bcd_hip_warped_layer *out,
+                        uint8_t *d_valid);
+int bcd_hip_valid_downscale(bcd_hip_ctx *ctx, const uint8_t *d_valid, int W, int H, uint8_t *d_out);
+int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_count, const uint8_t *d_valid, int W, int H, int patch_radius, int search_radius);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
