@@ -102,11 +102,6 @@ void progress_add(bcd_hip_ctx *ctx, double share)
     ctx->progress_fn((float)(ctx->progress_done / ctx->progress_total), ctx->progress_user);
 }
 
-// the estimate chunk: full-estimate items whose records (bcd_bayes27_record_bytes() each) are in flight at a time
-// (round 6: 2^18 instead of 2^17 -- half as many drains of the three persistent kernels on a -m 0 frame: 60.9 -> 60.2-60.5 ms at 1080p; sizes aligned to
-// the eigensolver's 6 144 matrices per round of the grid made no difference)
-constexpr int ESTIMATE_CHUNK = 1 << 18; // 262144 pixels = 2.6 GB of records
-
 // The estimate kernels are persistent (a wavefront per CU slot, items from a counter), so whatever they occupy stays
 // occupied until they end.  In a multiscale call the finest scale is the critical path and the coarse scales have slack: they
 // take a quarter of the slots, which leaves LDS and wave slots on every CU to the finest scale's short kernels (masks,
@@ -1317,18 +1312,14 @@ int check_layers_call(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
         if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
     }
     {
-        const size_t npix = (size_t)W * H;
-        auto overlap = [](const float *a, size_t na, const float *b, size_t nb) {
-            const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + nb * sizeof(float);
-            return a0 < b1 && b0 < a1;
-        };
+        const size_t f1 = (size_t)W * H * sizeof(float), no = 3 * f1; // (one float per pixel, an output)
         for (int k = 0; k < nb_layers; ++k) {
             const float *o = layers[k].d_out;
-            if (overlap(o, npix * 3, d_ns, npix) || (!no_hist && overlap(o, npix * 3, d_hist, npix * D))) return bad(ctx, "a layer's output overlaps the sample counts or the histograms");
+            if (bytes_overlap(o, no, d_ns, f1) || (!no_hist && bytes_overlap(o, no, d_hist, f1 * D))) return bad(ctx, "a layer's output overlaps the sample counts or the histograms");
             for (int j = 0; j < nb_layers; ++j) {
-                if (overlap(o, npix * 3, layers[j].d_colors, npix * 3) || overlap(o, npix * 3, layers[j].d_covariances, npix * 6))
+                if (bytes_overlap(o, no, layers[j].d_colors, 3 * f1) || bytes_overlap(o, no, layers[j].d_covariances, 6 * f1))
                     return bad(ctx, "a layer's output overlaps an input image");
-                if (j != k && overlap(o, npix * 3, layers[j].d_out, npix * 3)) return bad(ctx, "two layers share (part of) an output image");
+                if (j != k && bytes_overlap(o, no, layers[j].d_out, no)) return bad(ctx, "two layers share (part of) an output image");
             }
         }
     }
@@ -1752,19 +1743,16 @@ int bcd_hip_bayes_accumulate_layers(bcd_hip_ctx *ctx, const bcd_hip_stage_layer 
     {
         const size_t npix = (size_t)W * H;
         const size_t words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
-        auto overlap = [](const void *a, size_t na, const void *b_, size_t nb) {
-            const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b_, b1 = b0 + nb;
-            return a0 < b1 && b0 < a1;
-        };
         for (int k = 0; k < nb_layers; ++k) {
             const float *o = layers[k].d_sum;
             const size_t no = npix * 3 * sizeof(float);
-            if (overlap(o, no, d_mask, npix * words * 4) || overlap(o, no, d_nsim, npix * 4) || overlap(o, no, d_state, npix) || overlap(o, no, d_count, npix * 4))
+            if (bytes_overlap(o, no, d_mask, npix * words * 4) || bytes_overlap(o, no, d_nsim, npix * 4) || bytes_overlap(o, no, d_state, npix) ||
+                bytes_overlap(o, no, d_count, npix * 4))
                 return bad(ctx, "a layer's sum image overlaps the selection or the count image");
             for (int j = 0; j < nb_layers; ++j) {
-                if (overlap(o, no, layers[j].d_colors, npix * 3 * sizeof(float)) || overlap(o, no, layers[j].d_pixel_cov, npix * 6 * sizeof(float)))
+                if (bytes_overlap(o, no, layers[j].d_colors, npix * 3 * sizeof(float)) || bytes_overlap(o, no, layers[j].d_pixel_cov, npix * 6 * sizeof(float)))
                     return bad(ctx, "a layer's sum image overlaps an input image");
-                if (j != k && overlap(o, no, layers[j].d_sum, no)) return bad(ctx, "two layers share (part of) a sum image");
+                if (j != k && bytes_overlap(o, no, layers[j].d_sum, no)) return bad(ctx, "two layers share (part of) a sum image");
             }
         }
     }

@@ -1,6 +1,6 @@
-// bcd_ctx.h -- internal to the host orchestration files (bcd_api.hip, bcd_host.hip, bcd_accum.hip, bcd_selection.hip, bcd_selftest.hip): the context, the per-scale
-// workspace with its counter block, the error-handling macros and the helpers more than one of those files needs.  Nothing declared here is part
-// of the C ABI (include/bcd_hip.h): the helpers have hidden visibility.
+// bcd_ctx.h -- internal to the host orchestration files (bcd_api.hip, bcd_host.hip, bcd_accum.hip, bcd_selection.hip, bcd_selftest.hip, bcd_spike.hip,
+// bcd_temporal.hip, bcd_temporal_layers.hip): the context, the per-scale workspace with its counter block, the error-handling macros and the helpers more
+// than one of those files needs.  Nothing declared here is part of the C ABI (include/bcd_hip.h): the helpers have hidden visibility.
 #pragma once
 #include "../../include/bcd_hip.h"
 #include "bcd_common.h"
@@ -9,6 +9,7 @@
 #include <condition_variable>
 #include <cstddef>
 #include <cmath>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -21,6 +22,10 @@ static_assert(BCD_GUIDE_MAX_CHANNELS == BCD_HIP_GUIDE_MAX_CHANNELS, "the floors 
 constexpr int MAX_SCALES = 16;
 constexpr int ROUND_BATCH = 16;
 constexpr int MAX_EVENT_PAIRS = 4096;
+// the estimate chunk: full-estimate items whose records (bcd_bayes27_record_bytes() each) are in flight at a time: 262144 pixels = 2.6 GB of records
+// (round 6: 2^18 instead of 2^17 -- half as many drains of the three persistent kernels on a -m 0 frame: 60.9 -> 60.2-60.5 ms at 1080p; sizes aligned to
+// the eigensolver's 6 144 matrices per round of the grid made no difference)
+constexpr int ESTIMATE_CHUNK = 1 << 18;
 
 // (hidden: what the host files instantiate on these types stays out of the dynamic symbol table, as when they were file-local)
 #pragma GCC visibility push(hidden)
@@ -308,16 +313,48 @@ int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius);
 int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales);
 inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
 
-// ---- defined in bcd_temporal.hip
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  The one overlap predicate of the argument checks
+inline bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
+// ---- defined in bcd_temporal.hip: what the frame call and the layered call (bcd_temporal_layers.hip) of a sequence share
 void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
-// the T / C planes of every displacement between the frame and one neighbour, in the main workspace (whose own planes they overwrite)
-int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b);
-// the gate of a warped neighbour's cross masks (the stream's next step behind k_masks_cross): pvalid from the level's validity bytes, then the bits and |S_f|
-int temporal_gate(bcd_hip_ctx *ctx, Work &wk, const uint8_t *d_valid, int W, int H, int w, int b, uint32_t *d_mask_nb, int32_t *d_count_nb);
-// the validity levels 1 .. nb_scales - 1 of neighbour f from its level 0 (ctx->temporal.valid[f][0]), on the main stream
-int temporal_valid_levels(bcd_hip_ctx *ctx, int f, int W, int H, int nb_scales);
-// the refusals the motion calls add: the list itself, and a field that overlaps one of `outs` (each W*H*3 floats)
+// does [out, out + bytes) overlap one of a frame's images (a null image: not looked at)?
+bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const void *ns, const void *hist, const void *cov, size_t npix, int D);
+// what the selection of a scale reads of one frame: sample counts and histograms at this level; valid: null, or the validity bytes of a warped neighbour
+struct TemporalSelFrame { const float *ns, *hist; const uint8_t *valid; };
+struct TemporalPath { int32_t path = 0, borderline = 0; }; // of the in-frame pass (bcd_hip_similarity_last_path)
+// The selection stage of one scale, frames[0] the frame itself, from stage event 0 to stage event 2: the stats header of ctx->stats[scale], the in-frame masks
+// (wk.mask, wk.nsim) by bcd_hip_similarity_masks, per neighbour f the cross planes, k_masks_cross into ctx->temporal.mask[f], the gate of a warped neighbour and
+// the count sum, then the marking (wk.state).  per_pixel_cov() enqueues the caller's per-pixel covariances between stage events 0 and 1.
+int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
+                    const std::function<int()> &per_pixel_cov, TemporalPath *path);
+// the masks temporal_select left for frame f
+inline const uint32_t *temporal_mask(const bcd_hip_ctx *ctx, int f) { return (const uint32_t *)(f == 0 ? ctx->main.mask.p : ctx->temporal.mask[f].p); }
+// the tail of a scale (the stream is synchronised): the figures of wk.h_counters->lists and of the in-frame pass, and with profiling the four timers
+void temporal_stats_tail(bcd_hip_ctx *ctx, int scale, const TemporalPath &path);
+// The lists of an estimate over several frames on wk.stream: the buffers, the cleared counters, k_active_lists on the states and the TOTAL |S|, the copy of the list
+// lengths and the sum of |S| to wk.h_counters->lists (not waited for).  -> the CU slots of the chain, the grid of the fallback kernel
+struct TemporalLists { int cus, weak_grid; };
+int temporal_lists(bcd_hip_ctx *ctx, Work &wk, const int32_t *d_nsim_total, const uint8_t *d_state, int64_t npix, TemporalLists *out);
+// The full estimates of one image over wk.strong[0 .. n_strong): per chunk of ESTIMATE_CHUNK records the work-queue clear, the temporal prepare kernel on every
+// frame of `t`, then the solver and finish kernels on t's frame 0 into d_sum (and d_count, unless null: a further layer).  The redo counter runs on.
+int temporal_full_chain(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, float *d_sum, int32_t *d_count, int n_strong, int cus, int W, int H, int b, float min_eig);
+// The motion set-up of neighbour f (1..) that has a field: its four images warped into ctx->temporal.warp[f] (-> warped: colours, sample counts, histograms,
+// covariances) with the validity bytes of level 0, `more` (null: none) further layers by k_warp_layers, the validity levels 1 .. S - 1, and column f of the table
+// valid[s * nf + f]
+int temporal_warp_neighbour(bcd_hip_ctx *ctx, int f, int nf, const float *col, const float *ns, const float *hist, const float *cov, const float *motion, int W, int H,
+                            int D, int S, const BcdWarpLayerTable *more, int nb_more, const uint8_t **valid, const float *warped[4]);
+inline bool any_field(const float *const *motion, int n)
+{
+    for (int f = 0; motion && f < n; ++f) if (motion[f]) return true;
+    return false;
+}
 int temporal_upload_motion(bcd_hip_ctx *ctx, const float *const *h_motion, int nb_neighbours, int W, int H, const float **dev); // (whole uploads; dev[f] NULL for a NULL field)
+// the refusals the motion calls add: the list itself, and a field that overlaps one of `outs` (each W*H*3 floats)
 int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neighbours, int W, int H, float *const *outs, int nb_outs);
 
 // ---- defined in bcd_selection.hip

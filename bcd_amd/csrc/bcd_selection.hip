@@ -107,12 +107,6 @@ int reuse_build_level(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &
     return build_level_layers(ctx, fine, coarse, ns_fine, W, H, st);
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-
 } // namespace
 
 int selection_store(bcd_hip_ctx *ctx, Work &wk, int scale, const float *d_ns, int W, int H, int b, const int32_t *d_count, const bcd_hip_scale_stats &st)
@@ -266,11 +260,11 @@ int bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, c
         const size_t npix = (size_t)W * H, f = sizeof(float);
         for (int k = 0; k < L; ++k) {
             const float *o = layers[k].d_out;
-            if (d_nsamples && overlap(o, npix * 3 * f, d_nsamples, npix * f)) return bad(ctx, "a layer's output overlaps the sample counts");
+            if (d_nsamples && bytes_overlap(o, npix * 3 * f, d_nsamples, npix * f)) return bad(ctx, "a layer's output overlaps the sample counts");
             for (int j = 0; j < L; ++j) {
-                if (overlap(o, npix * 3 * f, layers[j].d_colors, npix * 3 * f) || overlap(o, npix * 3 * f, layers[j].d_covariances, npix * 6 * f))
+                if (bytes_overlap(o, npix * 3 * f, layers[j].d_colors, npix * 3 * f) || bytes_overlap(o, npix * 3 * f, layers[j].d_covariances, npix * 6 * f))
                     return bad(ctx, "a layer's output overlaps an input image");
-                if (j != k && overlap(o, npix * 3 * f, layers[j].d_out, npix * 3 * f)) return bad(ctx, "two layers share (part of) an output image");
+                if (j != k && bytes_overlap(o, npix * 3 * f, layers[j].d_out, npix * 3 * f)) return bad(ctx, "two layers share (part of) an output image");
             }
         }
     }

@@ -7,9 +7,10 @@
 namespace {
 
 struct Range {
-    uintptr_t a0, a1;
-    Range(const void *p, size_t bytes) : a0((uintptr_t)p), a1((uintptr_t)p + bytes) {}
-    bool overlaps(const Range &o) const { return a0 < o.a1 && o.a0 < a1; }
+    const void *p;
+    size_t bytes;
+    Range(const void *p_, size_t n) : p(p_), bytes(n) {}
+    bool overlaps(const Range &o) const { return bytes_overlap(p, bytes, o.p, o.bytes); }
 };
 
 // no output may be (or overlap) an input or another output

@@ -4,6 +4,9 @@
 // neighbour's are written.  The motion calls (section 16, "Motion": bcd_hip_denoise_temporal_motion[_host], the stages bcd_hip_warp_frame,
 // bcd_hip_valid_downscale, bcd_hip_gate_masks_valid) are here too: temporal_run warps a neighbour that has a motion field (k_warp.hip) before its pyramid is
 // built and gates its cross masks at every scale; the plain call is temporal_run without fields.
+// What the layered calls (bcd_temporal_layers.hip) share with the frame calls is defined here and declared in bcd_ctx.h: the selection stage of a scale
+// (temporal_select) and its stats tail (temporal_stats_tail), the lists and the chain of full estimates of the estimate stage (temporal_lists,
+// temporal_full_chain), the motion set-up of a neighbour (temporal_warp_neighbour).
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -13,7 +16,9 @@
 
 static_assert(BCD_MAX_NEIGHBOURS == BCD_HIP_MAX_NEIGHBOURS, "the frame table of the kernels holds what the C ABI admits");
 
-// the T / C planes of every displacement between the frame and one neighbour, in the main workspace
+namespace {
+
+// the T / C planes of every displacement between the frame and one neighbour, in the main workspace (whose own planes they overwrite)
 int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b)
 {
     const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
@@ -24,6 +29,7 @@ int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const
     return BCD_HIP_OK;
 }
 
+// the gate of a warped neighbour's cross masks (the stream's next step behind k_masks_cross): pvalid from the level's validity bytes, then the bits and |S_f|
 int temporal_gate(bcd_hip_ctx *ctx, Work &wk, const uint8_t *d_valid, int W, int H, int w, int b, uint32_t *d_mask_nb, int32_t *d_count_nb)
 {
     DevBuf &pv = ctx->temporal.pvalid;
@@ -33,20 +39,27 @@ int temporal_gate(bcd_hip_ctx *ctx, Work &wk, const uint8_t *d_valid, int W, int
     return BCD_HIP_OK;
 }
 
-int temporal_valid_levels(bcd_hip_ctx *ctx, int f, int W, int H, int nb_scales)
+} // namespace
+
+int temporal_warp_neighbour(bcd_hip_ctx *ctx, int f, int nf, const float *col, const float *ns, const float *hist, const float *cov, const float *motion, int W, int H,
+                            int D, int S, const BcdWarpLayerTable *more, int nb_more, const uint8_t **valid, const float *warped[4])
 {
     auto &tp = ctx->temporal;
-    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s, ws /= 2, hs /= 2) {
+    hipStream_t st = ctx->main.stream;
+    const size_t npix = (size_t)W * H, floats[4] = { npix * 3, npix, npix * D, npix * 6 };
+    DevBuf(&wb)[4] = tp.warp[f];
+    for (int k = 0; k < 4; ++k) RCCHK(ensure(ctx, wb[k], floats[k] * sizeof(float)));
+    RCCHK(ensure(ctx, tp.valid[f][0], npix));
+    uint8_t *v0 = (uint8_t *)tp.valid[f][0].p;
+    HIPCHK(ctx, bcd_launch_warp_frame(col, ns, hist, cov, motion, W, H, D, (float *)wb[0].p, (float *)wb[1].p, (float *)wb[2].p, (float *)wb[3].p, v0, st));
+    if (more) HIPCHK(ctx, bcd_launch_warp_layers(*more, nb_more, motion, W, H, v0, st)); // (it writes the same validity bytes again)
+    for (int s = 1, ws = W, hs = H; s < S; ++s, ws /= 2, hs /= 2) {
         RCCHK(ensure(ctx, tp.valid[f][s], (size_t)(ws / 2) * (hs / 2)));
-        HIPCHK(ctx, bcd_launch_valid_down((const uint8_t *)tp.valid[f][s - 1].p, ws, hs, (uint8_t *)tp.valid[f][s].p, ctx->main.stream));
+        HIPCHK(ctx, bcd_launch_valid_down((const uint8_t *)tp.valid[f][s - 1].p, ws, hs, (uint8_t *)tp.valid[f][s].p, st));
     }
+    for (int k = 0; k < 4; ++k) warped[k] = (const float *)wb[k].p;
+    for (int s = 0; s < S; ++s) valid[(size_t)s * nf + f] = (const uint8_t *)tp.valid[f][s].p;
     return BCD_HIP_OK;
-}
-
-static bool overlap_bytes(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
 }
 
 int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neighbours, int W, int H, float *const *outs, int nb_outs)
@@ -55,7 +68,47 @@ int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neigh
     const size_t npix = (size_t)W * H;
     for (int f = 0; f < nb_neighbours; ++f)
         for (int k = 0; motion[f] && k < nb_outs; ++k)
-            if (overlap_bytes(outs[k], npix * 3 * sizeof(float), motion[f], npix * 2 * sizeof(float))) return bad(ctx, "an output overlaps a motion field");
+            if (bytes_overlap(outs[k], npix * 3 * sizeof(float), motion[f], npix * 2 * sizeof(float))) return bad(ctx, "an output overlaps a motion field");
+    return BCD_HIP_OK;
+}
+
+bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const void *ns, const void *hist, const void *cov, size_t npix, int D)
+{
+    const size_t f4 = sizeof(float);
+    return (col && bytes_overlap(out, bytes, col, npix * 3 * f4)) || (ns && bytes_overlap(out, bytes, ns, npix * f4)) ||
+           (hist && bytes_overlap(out, bytes, hist, npix * D * f4)) || (cov && bytes_overlap(out, bytes, cov, npix * 6 * f4));
+}
+
+int temporal_lists(bcd_hip_ctx *ctx, Work &wk, const int32_t *d_nsim_total, const uint8_t *d_state, int64_t npix, TemporalLists *out)
+{
+    constexpr int K = 27;
+    wk.redo.pending = false;
+    RCCHK(ensure(ctx, wk.strong, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.weak, npix * sizeof(int32_t)));
+    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
+    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
+    Counters::Lists *d_c = &wk.d_counters()->lists, *h_c = &wk.h_counters->lists;
+    touch(wk); // (the counters and work queues are cleared here, whatever k_scale_begin left)
+    h_c->spectral = 0;
+    HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
+    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim_total, 0, npix, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, &d_c->n_strong, wk.stream, nullptr));
+    HIPCHK(ctx, hipMemcpyAsync(h_c, d_c, offsetof(Counters::Lists, generic_work), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
+    out->cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
+    out->weak_grid = (int)std::min<int64_t>(std::max<int64_t>(1, npix / 7), (int64_t)out->cus * 32);
+    return BCD_HIP_OK;
+}
+
+int temporal_full_chain(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, float *d_sum, int32_t *d_count, int n_strong, int cus, int W, int H, int b, float min_eig)
+{
+    if (n_strong < 0 || n_strong > (int64_t)W * H) return bad(ctx, "temporal estimate: the list exceeds the frame");
+    if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, bcd_bayes27_record_bytes() * (size_t)std::min(n_strong, ESTIMATE_CHUNK)));
+    for (int first = 0; first < n_strong; first += ESTIMATE_CHUNK) {
+        const int n = std::min(ESTIMATE_CHUNK, n_strong - first);
+        HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream)); // the work queues of the four kernels
+        HIPCHK(ctx, bcd_launch_prepare27t(t, (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, b, (float *)wk.gscratch.p, wk.stream));
+        HIPCHK(ctx, bcd_launch_solve_finish27(t.col[0], t.pixcov[0], t.mask[0], (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, H, min_eig,
+                                              (float *)wk.gscratch.p, d_sum, d_count, &wk.d_counters()->lists.spectral, wk.stream));
+    }
     return BCD_HIP_OK;
 }
 
@@ -68,49 +121,21 @@ int check_cross_stage(bcd_hip_ctx *ctx, int W, int H, int D, int w, int b)
     return check_params(ctx, W, H, D, &p);
 }
 
-// The estimate chain over the members of several frames (patch radius 1, search radius 6): the lists of processed pixels from the states and the TOTAL
-// |S|, the fallback kernel over all frames, and per chunk of full estimates the temporal prepare kernel followed by the unchanged solver and finish
-// kernels on the frame's own colours and in-frame masks.  The list lengths and the sum of |S| are in wk.h_counters->lists when the call returns (it
-// waits for them once, before the first chunk, and synchronises the stream at its end).
+// The estimate stage over the members of several frames (patch radius 1, search radius 6): the lists, the fallback kernel over all frames, the wait for the
+// list lengths, one chain of full estimates on the frame's own colours and in-frame masks, the redo count.  The list lengths and the sum of |S| are in
+// wk.h_counters->lists when the call returns (it synchronises the stream at its end).
 int bayes_temporal(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
                    float *d_sum, int32_t *d_count)
 {
-    constexpr int K = 27, CHUNK_MAX = 1 << 18; // (the chunk of bayes(): records in flight at a time)
-    const int64_t npix = (int64_t)W * H;
-    wk.redo.pending = false;
-    RCCHK(ensure(ctx, wk.strong, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.weak, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
-    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
+    TemporalLists ls;
+    RCCHK(temporal_lists(ctx, wk, d_nsim_total, d_state, (int64_t)W * H, &ls));
     Counters::Lists *d_c = &wk.d_counters()->lists, *h_c = &wk.h_counters->lists;
-    touch(wk); // (the counters and work queues are cleared here, whatever k_scale_begin left)
-    h_c->spectral = 0;
-    HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
-    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim_total, 0, npix, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, &d_c->n_strong, wk.stream, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(h_c, d_c, offsetof(Counters::Lists, generic_work), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
-    const int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
-    HIPCHK(ctx, bcd_launch_bayes_weak_temporal(t, (const int32_t *)wk.weak.p, &d_c->n_weak, (int)std::min<int64_t>(std::max<int64_t>(1, npix / 7), (int64_t)cus * 32), W, b,
-                                               d_sum, d_count, wk.stream));
+    HIPCHK(ctx, bcd_launch_bayes_weak_temporal(t, (const int32_t *)wk.weak.p, &d_c->n_weak, ls.weak_grid, W, b, d_sum, d_count, wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    const int n_strong = h_c->n_strong;
-    if (n_strong < 0 || n_strong > npix) return bad(ctx, "temporal estimate: the list exceeds the frame");
-    if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, bcd_bayes27_record_bytes() * (size_t)std::min(n_strong, CHUNK_MAX)));
-    for (int first = 0; first < n_strong; first += CHUNK_MAX) {
-        const int n = std::min(CHUNK_MAX, n_strong - first);
-        HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream)); // the work queues of the four kernels
-        HIPCHK(ctx, bcd_launch_prepare27t(t, (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, b, (float *)wk.gscratch.p, wk.stream));
-        HIPCHK(ctx, bcd_launch_solve_finish27(t.col[0], t.pixcov[0], t.mask[0], (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, H, min_eig,
-                                              (float *)wk.gscratch.p, d_sum, d_count, &d_c->spectral, wk.stream));
-    }
+    RCCHK(temporal_full_chain(ctx, wk, t, d_sum, d_count, h_c->n_strong, ls.cus, W, H, b, min_eig));
     HIPCHK(ctx, hipMemcpyAsync(&h_c->spectral, &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     return BCD_HIP_OK;
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
 }
 
 } // namespace
@@ -131,14 +156,14 @@ int bcd_hip_bayes_accumulate_temporal(bcd_hip_ctx *ctx, const bcd_hip_stage_fram
     RCCHK(check_params(ctx, W, H, 1, &p));
     if (w != 1 || b != 6) { set_err(ctx, "the estimate over several frames supports patch radius 1 and search radius 6"); return BCD_HIP_EUNSUPPORTED; }
     {
-        const size_t npix = (size_t)W * H, f4 = sizeof(float), words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
-        if (overlap(d_sum, npix * 3 * f4, d_count, npix * 4) || overlap(d_sum, npix * 3 * f4, d_nsim_total, npix * 4) || overlap(d_sum, npix * 3 * f4, d_state, npix) ||
-            overlap(d_count, npix * 4, d_nsim_total, npix * 4) || overlap(d_count, npix * 4, d_state, npix))
+        const size_t npix = (size_t)W * H, f4 = sizeof(float), words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32, nsum = npix * 3 * f4, ncnt = npix * 4;
+        if (bytes_overlap(d_sum, nsum, d_count, ncnt) || bytes_overlap(d_sum, nsum, d_nsim_total, npix * 4) || bytes_overlap(d_sum, nsum, d_state, npix) ||
+            bytes_overlap(d_count, ncnt, d_nsim_total, npix * 4) || bytes_overlap(d_count, ncnt, d_state, npix))
             return bad(ctx, "the accumulators overlap each other or the selection");
         for (int f = 0; f < nb_frames; ++f)
             for (const void *o : { (const void *)d_sum, (const void *)d_count })
-                if (overlap(o, o == d_sum ? npix * 3 * f4 : npix * 4, frames[f].d_colors, npix * 3 * f4) || overlap(o, o == d_sum ? npix * 3 * f4 : npix * 4, frames[f].d_pixel_cov, npix * 6 * f4) ||
-                    overlap(o, o == d_sum ? npix * 3 * f4 : npix * 4, frames[f].d_mask, npix * words * 4))
+                if (overlaps_frame_images(o, o == d_sum ? nsum : ncnt, frames[f].d_colors, nullptr, nullptr, frames[f].d_pixel_cov, npix, 0) ||
+                    bytes_overlap(o, o == d_sum ? nsum : ncnt, frames[f].d_mask, npix * words * 4))
                     return bad(ctx, "an accumulator overlaps an input image");
     }
     DEVICE_GUARD(ctx);
@@ -210,14 +235,8 @@ void temporal_free(bcd_hip_ctx *ctx)
     if (t.pvalid.p) (void)hipFree(t.pvalid.p);
 }
 
-namespace {
-
-struct FrameLevel { const float *col, *ns, *hist, *cov; };
-
-// one scale: frames[0] the frame itself at this level
-// valid: null, or per frame the validity bytes of this level (null: the frame is not warped) -- a warped neighbour's cross masks pass the gate
-int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale, float *d_out,
-                   const uint8_t *const *valid = nullptr)
+int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
+                    const std::function<int()> &per_pixel_cov, TemporalPath *path)
 {
     Work &wk = ctx->main;
     auto &tp = ctx->temporal;
@@ -227,13 +246,9 @@ int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, in
     RCCHK(ensure(ctx, wk.mask, npix * words * sizeof(uint32_t)));
     RCCHK(ensure(ctx, wk.nsim, npix * sizeof(int32_t)));
     RCCHK(ensure(ctx, wk.state, npix));
-    RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
     RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
     RCCHK(ensure(ctx, tp.count_nb, npix * sizeof(int32_t)));
-    for (int f = 0; f < nf; ++f) {
-        RCCHK(ensure(ctx, tp.pixcov[f], npix * 6 * sizeof(float)));
-        if (f > 0) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
-    }
+    for (int f = 1; f < nf; ++f) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
     bcd_hip_scale_stats &st = ctx->stats[scale];
     memset(&st, 0, sizeof(st));
     st.width = W; st.height = H;
@@ -242,41 +257,73 @@ int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, in
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
     // S_0: today's set, by the code that computes it today (its verdict and re-runs are inside the call); the cross passes follow it, ahead of the marking
     RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
-    int32_t path = 0, borderline = 0, capacity = 0;
-    RCCHK(bcd_hip_similarity_last_path(ctx, &path, &borderline, &capacity));
-    BcdFrameTable t = {};
-    t.n = nf;
-    for (int f = 0; f < nf; ++f) {
-        HIPCHK(ctx, bcd_launch_pixel_cov(frames[f].cov, frames[f].ns, (int64_t)npix, (float *)tp.pixcov[f].p, wk.stream));
-        t.col[f] = frames[f].col; t.pixcov[f] = (const float *)tp.pixcov[f].p;
-        t.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : (const uint32_t *)tp.mask[f].p;
-        if (f == 0) continue;
+    int32_t capacity = 0;
+    RCCHK(bcd_hip_similarity_last_path(ctx, &path->path, &path->borderline, &capacity));
+    RCCHK(per_pixel_cov());
+    for (int f = 1; f < nf; ++f) {
+        uint32_t *mask = (uint32_t *)tp.mask[f].p;
+        int32_t *count = (int32_t *)tp.count_nb.p;
         RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
-        HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
-        if (valid && valid[f]) RCCHK(temporal_gate(ctx, wk, valid[f], W, H, w, b, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p));
-        HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
+        HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, mask, count, wk.stream));
+        if (frames[f].valid) RCCHK(temporal_gate(ctx, wk, frames[f].valid, W, H, w, b, mask, count)); // (a warped neighbour)
+        HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, count, (int64_t)npix, wk.stream));
     }
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
     RCCHK(bcd_hip_active_set(ctx, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, W, H, w, b, 0, H, prm->marked_skip_probability, prm->use_random_pixel_order,
                              bcd_hip_scale_seed(prm->order_seed, scale), (uint8_t *)wk.state.p, &st.active_rounds));
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[2], wk.stream));
-    HIPCHK(ctx, hipMemsetAsync(wk.sum.p, 0, npix * 3 * sizeof(float), wk.stream));
-    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
-    RCCHK(bayes_temporal(ctx, wk, t, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, prm->min_eigen_value, (float *)wk.sum.p, (int32_t *)wk.cnt.p));
-    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
-    HIPCHK(ctx, bcd_launch_finalize((const float *)wk.sum.p, (const int32_t *)wk.cnt.p, (int64_t)npix, d_out, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+void temporal_stats_tail(bcd_hip_ctx *ctx, int scale, const TemporalPath &path)
+{
+    Work &wk = ctx->main;
+    bcd_hip_scale_stats &st = ctx->stats[scale];
     const Counters::Lists &h = wk.h_counters->lists;
     st.processed = (int64_t)h.n_strong + h.n_weak; st.fallback = h.n_weak; st.similar_total = h.sim_total; // (the sum of the TOTAL |S|)
-    st.similarity_path = path; st.borderline_pairs = borderline;                                          // (those of the in-frame pass)
+    st.similarity_path = path.path; st.borderline_pairs = path.borderline;                                // (those of the in-frame pass)
     st.cu_share = ctx->cu_share_pct;
-    st.spectral_inverses = h.spectral;
-    if (prof) {
+    st.spectral_inverses = h.spectral;                                                                    // (a layered call: the sum over the layers)
+    if (ctx->profiling) {
         st.ms_similarity = stage_ms(wk, 0, 1); // (includes the cross passes)
         st.ms_active = stage_ms(wk, 1, 2);
         st.ms_bayes = stage_ms(wk, 2, 3);
         st.ms_total = stage_ms(wk, 0, 3);
     }
+}
+
+namespace {
+
+struct FrameLevel { const float *col, *ns, *hist, *cov; };
+
+// one scale: frames[0] the frame itself at this level
+// valid: per frame the validity bytes of this level (null: the frame is not warped) -- a warped neighbour's cross masks pass the gate
+int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale, float *d_out, const uint8_t *const *valid)
+{
+    Work &wk = ctx->main;
+    auto &tp = ctx->temporal;
+    const size_t npix = (size_t)W * H;
+    RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
+    TemporalSelFrame sel[BCD_MAX_NEIGHBOURS + 1];
+    for (int f = 0; f < nf; ++f) {
+        RCCHK(ensure(ctx, tp.pixcov[f], npix * 6 * sizeof(float)));
+        sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
+    }
+    TemporalPath path;
+    RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int {
+        for (int f = 0; f < nf; ++f) HIPCHK(ctx, bcd_launch_pixel_cov(frames[f].cov, frames[f].ns, (int64_t)npix, (float *)tp.pixcov[f].p, wk.stream));
+        return BCD_HIP_OK;
+    }, &path));
+    BcdFrameTable t = {};
+    t.n = nf;
+    for (int f = 0; f < nf; ++f) { t.col[f] = frames[f].col; t.pixcov[f] = (const float *)tp.pixcov[f].p; t.mask[f] = temporal_mask(ctx, f); }
+    HIPCHK(ctx, hipMemsetAsync(wk.sum.p, 0, npix * 3 * sizeof(float), wk.stream));
+    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
+    RCCHK(bayes_temporal(ctx, wk, t, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, prm->search_radius, prm->min_eigen_value, (float *)wk.sum.p, (int32_t *)wk.cnt.p));
+    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
+    HIPCHK(ctx, bcd_launch_finalize((const float *)wk.sum.p, (const int32_t *)wk.cnt.p, (int64_t)npix, d_out, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    temporal_stats_tail(ctx, scale, path);
     return BCD_HIP_OK;
 }
 
@@ -301,12 +348,10 @@ int check_temporal_call(bcd_hip_ctx *ctx, const void *col, const void *ns, const
         ws /= 2; hs /= 2;
         if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
     }
-    const size_t npix = (size_t)W * H, f4 = sizeof(float), no = npix * 3 * f4;
-    if (overlap(out, no, col, npix * 3 * f4) || overlap(out, no, ns, npix * f4) || overlap(out, no, hist, npix * D * f4) || overlap(out, no, cov, npix * 6 * f4))
-        return bad(ctx, "the output overlaps an input image");
+    const size_t npix = (size_t)W * H, no = npix * 3 * sizeof(float);
+    if (overlaps_frame_images(out, no, col, ns, hist, cov, npix, D)) return bad(ctx, "the output overlaps an input image");
     for (int f = 0; f < n; ++f)
-        if (overlap(out, no, nb[f].d_colors, npix * 3 * f4) || overlap(out, no, nb[f].d_nsamples, npix * f4) || overlap(out, no, nb[f].d_histograms, npix * D * f4) ||
-            overlap(out, no, nb[f].d_covariances, npix * 6 * f4))
+        if (overlaps_frame_images(out, no, nb[f].d_colors, nb[f].d_nsamples, nb[f].d_histograms, nb[f].d_covariances, npix, D))
             return bad(ctx, "the output overlaps an image of a neighbour frame");
     return BCD_HIP_OK;
 }
@@ -330,18 +375,9 @@ int temporal_run(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsample
         lv[f] = { nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances };
         if (!motion || !motion[f - 1]) continue;
         // the neighbour reprojected into the frame's pixel grid, at full resolution; its pyramid is built from the warped images
-        const size_t npix = (size_t)W * H;
-        DevBuf(&wb)[4] = tp.warp[f];
-        RCCHK(ensure(ctx, wb[0], npix * 3 * sizeof(float)));
-        RCCHK(ensure(ctx, wb[1], npix * sizeof(float)));
-        RCCHK(ensure(ctx, wb[2], npix * D * sizeof(float)));
-        RCCHK(ensure(ctx, wb[3], npix * 6 * sizeof(float)));
-        RCCHK(ensure(ctx, tp.valid[f][0], npix));
-        HIPCHK(ctx, bcd_launch_warp_frame(nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances, motion[f - 1], W, H, D, (float *)wb[0].p, (float *)wb[1].p,
-                                          (float *)wb[2].p, (float *)wb[3].p, (uint8_t *)tp.valid[f][0].p, ctx->main.stream));
-        RCCHK(temporal_valid_levels(ctx, f, W, H, S));
-        lv[f] = { (const float *)wb[0].p, (const float *)wb[1].p, (const float *)wb[2].p, (const float *)wb[3].p };
-        for (int s = 0; s < S; ++s) valid[(size_t)s * nf + f] = (const uint8_t *)tp.valid[f][s].p;
+        const float *wp[4];
+        RCCHK(temporal_warp_neighbour(ctx, f, nf, nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances, motion[f - 1], W, H, D, S, nullptr, 0, valid.data(), wp));
+        lv[f] = { wp[0], wp[1], wp[2], wp[3] };
     }
     for (int s = 1; s < S; ++s) {
         ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
@@ -392,12 +428,6 @@ int upload_frames(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsampl
     return BCD_HIP_OK;
 }
 
-bool any_field(const float *const *motion, int n)
-{
-    for (int f = 0; motion && f < n; ++f) if (motion[f]) return true;
-    return false;
-}
-
 } // namespace
 
 // whole uploads of the motion fields that are not NULL into ctx->temporal.motion_host: dev[f] the device copy, or NULL
@@ -413,6 +443,29 @@ int temporal_upload_motion(bcd_hip_ctx *ctx, const float *const *h_motion, int n
         dev[f] = (const float *)tp.motion_host[f + 1].p;
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
+}
+
+// the checked host call with at least one neighbour: whole uploads, the device call on the copies, the output back; h_motion: null, or the list of a motion call
+static int temporal_host_run(bcd_hip_ctx *ctx, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances,
+                             const bcd_hip_frame *neighbours, int nb_neighbours, const float *const *h_motion, int W, int H, int D, int nb_scales,
+                             const bcd_hip_params *prm, float *h_out)
+{
+    DEVICE_GUARD(ctx);
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
+    const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
+    if (h_motion) RCCHK(temporal_upload_motion(ctx, h_motion, nb_neighbours, W, H, dmv));
+    RCCHK(upload_frames(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, dev));
+    float *d_out = (float *)tp.host_out.p;
+    if (h_motion)
+        RCCHK(bcd_hip_denoise_temporal_motion(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, dmv, W, H, D,
+                                              nb_scales, prm, d_out));
+    else
+        RCCHK(bcd_hip_denoise_temporal(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, W, H, D, nb_scales, prm, d_out));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, d_out, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return BCD_HIP_OK;
 }
 
@@ -433,16 +486,7 @@ int bcd_hip_denoise_temporal_host(bcd_hip_ctx *ctx, const float *h_colors, const
     if (!ctx) return BCD_HIP_EINVAL;
     RCCHK(check_temporal_call(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out));
     if (nb_neighbours == 0) return bcd_hip_denoise_host(ctx, h_colors, h_nsamples, h_histograms, h_covariances, W, H, D, nb_scales, prm, h_out);
-    DEVICE_GUARD(ctx);
-    auto &tp = ctx->temporal;
-    hipStream_t st = ctx->main.stream;
-    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
-    RCCHK(upload_frames(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, dev));
-    RCCHK(bcd_hip_denoise_temporal(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, W, H, D, nb_scales, prm,
-                                   (float *)tp.host_out.p));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, tp.host_out.p, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BCD_HIP_OK;
+    return temporal_host_run(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, nullptr, W, H, D, nb_scales, prm, h_out);
 }
 
 // ---- the motion calls ("Motion") -------------------------------------------------------------------------------------------
@@ -467,18 +511,7 @@ int bcd_hip_denoise_temporal_motion_host(bcd_hip_ctx *ctx, const float *h_colors
     RCCHK(check_motion_list(ctx, h_motion, nb_neighbours, W, H, &h_out, 1));
     if (!any_field(h_motion, nb_neighbours))
         return bcd_hip_denoise_temporal_host(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, nb_scales, prm, h_out);
-    DEVICE_GUARD(ctx);
-    auto &tp = ctx->temporal;
-    hipStream_t st = ctx->main.stream;
-    bcd_hip_frame dev[BCD_HIP_MAX_NEIGHBOURS + 1];
-    const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
-    RCCHK(temporal_upload_motion(ctx, h_motion, nb_neighbours, W, H, dmv));
-    RCCHK(upload_frames(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, dev));
-    RCCHK(bcd_hip_denoise_temporal_motion(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, dmv, W, H, D,
-                                          nb_scales, prm, (float *)tp.host_out.p));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, tp.host_out.p, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return BCD_HIP_OK;
+    return temporal_host_run(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, h_motion, W, H, D, nb_scales, prm, h_out);
 }
 
 // ---- the stage calls of the motion path
@@ -498,8 +531,8 @@ int bcd_hip_warp_frame(bcd_hip_ctx *ctx, const bcd_hip_frame *frame, const float
         const void *dst[5] = { out->d_colors, out->d_nsamples, out->d_histograms, out->d_covariances, d_valid };
         const size_t ndst[5] = { npix * 3 * f4, npix * f4, npix * D * f4, npix * 6 * f4, npix };
         for (int i = 0; i < 5; ++i) {
-            for (int j = 0; j < 5; ++j) if (in[j] && overlap(dst[i], ndst[i], in[j], nin[j])) return bad(ctx, "a warp destination overlaps an input image or the motion field");
-            for (int j = 0; j < i; ++j) if (overlap(dst[i], ndst[i], dst[j], ndst[j])) return bad(ctx, "two warp destinations overlap");
+            for (int j = 0; j < 5; ++j) if (in[j] && bytes_overlap(dst[i], ndst[i], in[j], nin[j])) return bad(ctx, "a warp destination overlaps an input image or the motion field");
+            for (int j = 0; j < i; ++j) if (bytes_overlap(dst[i], ndst[i], dst[j], ndst[j])) return bad(ctx, "two warp destinations overlap");
         }
     }
     DEVICE_GUARD(ctx);
@@ -515,7 +548,7 @@ int bcd_hip_valid_downscale(bcd_hip_ctx *ctx, const uint8_t *d_valid, int W, int
     if (!ctx) return BCD_HIP_EINVAL;
     if (!d_valid || !d_out) return bad(ctx, "null argument");
     if (W < 2 || H < 2 || (int64_t)W * H >= (1ll << 31)) return bad(ctx, "the validity image must be at least 2 x 2 (and below 2^31 pixels)");
-    if (overlap(d_out, (size_t)(W / 2) * (H / 2), d_valid, (size_t)W * H)) return bad(ctx, "the destination overlaps the input");
+    if (bytes_overlap(d_out, (size_t)(W / 2) * (H / 2), d_valid, (size_t)W * H)) return bad(ctx, "the destination overlaps the input");
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, bcd_launch_valid_down(d_valid, W, H, d_out, ctx->main.stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
@@ -529,7 +562,7 @@ int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_coun
     RCCHK(check_cross_stage(ctx, W, H, 1, w, b));
     {
         const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
-        if (overlap(d_mask, npix * words * 4, d_count, npix * 4) || overlap(d_mask, npix * words * 4, d_valid, npix) || overlap(d_count, npix * 4, d_valid, npix))
+        if (bytes_overlap(d_mask, npix * words * 4, d_count, npix * 4) || bytes_overlap(d_mask, npix * words * 4, d_valid, npix) || bytes_overlap(d_count, npix * 4, d_valid, npix))
             return bad(ctx, "the masks, the counts and the validity image overlap");
     }
     DEVICE_GUARD(ctx);

@@ -1,12 +1,13 @@
 // bcd_temporal_layers.hip -- the colour layers of a frame denoised with similar patches from its neighbour frames ("Layers"):
 // bcd_hip_denoise_temporal_layers[_host] and the stage entry point bcd_hip_bayes_accumulate_temporal_layers.  The selection of a scale -- the in-frame set,
-// the cross sets, the total |S|, the marking, the lists -- reads sample counts and histograms only and is computed once, by the steps of temporal_scale
-// (bcd_temporal.hip); the estimate stage runs per layer: one launch of k_bayes_weak_temporal_layers serves the fallback pixels of every layer on the side
-// stream, the chain of full estimates (k_prepare27t, then the unchanged solver and finish kernels) runs once per layer over the same lists, records and
-// work queues.  The count image is filled once: by the first group of the fallback kernel and by the first layer's finish kernels.
+// the cross sets, the total |S|, the marking, the lists -- reads sample counts and histograms only and is computed once, by the helpers the frame call uses
+// (temporal_select, temporal_lists; bcd_temporal.hip); the estimate stage runs per layer: one launch of k_bayes_weak_temporal_layers serves the fallback
+// pixels of every layer on the side stream, the chain of full estimates (temporal_full_chain: k_prepare27t, then the unchanged solver and finish kernels) runs
+// once per layer over the same lists, records and work queues.  The count image is filled once: by the first group of the fallback kernel and by the first
+// layer's finish kernels.
 // Every buffer of the call lives in ctx->temporal (grow-only): the workspace's lay_* slices, which bcd_hip_denoise_layers owns, are not touched.
 // bcd_hip_denoise_temporal_layers_motion[_host] and bcd_hip_warp_layers (section 16, "Motion") are layers_run with motion fields: a neighbour with a field is
-// warped (k_warp.hip) before its pyramid is built, its cross masks pass temporal_gate at every scale.
+// warped (temporal_warp_neighbour, with its further layers) before its pyramid is built, its cross masks pass the gate at every scale.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -25,64 +26,35 @@ struct LayerFrames {
     const uint32_t *mask[NF];
 };
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-
-// the part of bayes_temporal_layers behind the fork: the wait for the list lengths, then the full estimates layer by layer -- records and work queues are
+// the part of bayes_temporal_layers behind the fork: the wait for the list lengths, then one chain of full estimates per layer -- records and work queues are
 // reused, the redo counter runs on and its total is copied out behind each layer.  The side stream is NOT joined here.
 int layer_chains(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, int W, int H, int b, float min_eig, float *const *d_sum, int32_t *d_count, int cus)
 {
-    constexpr int CHUNK_MAX = 1 << 18; // (the chunk of bayes(): records in flight at a time)
-    const int64_t npix = (int64_t)W * H;
-    Counters::Lists *d_c = &wk.d_counters()->lists;
     Counters *h = wk.h_counters;
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    const int n_strong = h->lists.n_strong;
-    if (n_strong < 0 || n_strong > npix) return bad(ctx, "temporal estimate: the list exceeds the frame");
-    if (n_strong > 0) RCCHK(ensure(ctx, wk.gscratch, bcd_bayes27_record_bytes() * (size_t)std::min(n_strong, CHUNK_MAX)));
     for (int k = 0; k < lf.L; ++k) {
         BcdFrameTable t = {};
         t.n = lf.nf;
         for (int f = 0; f < lf.nf; ++f) { t.col[f] = lf.col[f][k]; t.pixcov[f] = lf.pixcov[f][k]; t.mask[f] = lf.mask[f]; }
-        for (int first = 0; first < n_strong; first += CHUNK_MAX) {
-            const int n = std::min(CHUNK_MAX, n_strong - first);
-            HIPCHK(ctx, hipMemsetAsync(wk.work_q.p, 0, BCD_WORK_INTS * sizeof(int32_t), wk.stream)); // the work queues of the four kernels
-            HIPCHK(ctx, bcd_launch_prepare27t(t, (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, b, (float *)wk.gscratch.p, wk.stream));
-            HIPCHK(ctx, bcd_launch_solve_finish27(t.col[0], t.pixcov[0], t.mask[0], (const int32_t *)wk.strong.p, first, n, (int *)wk.work_q.p, cus, W, H, min_eig,
-                                                  (float *)wk.gscratch.p, d_sum[k], k == 0 ? d_count : nullptr, &d_c->spectral, wk.stream));
-        }
-        HIPCHK(ctx, hipMemcpyAsync(&h->layer_redo_total[k], &d_c->spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
+        RCCHK(temporal_full_chain(ctx, wk, t, d_sum[k], k == 0 ? d_count : nullptr, h->lists.n_strong, cus, W, H, b, min_eig));
+        HIPCHK(ctx, hipMemcpyAsync(&h->layer_redo_total[k], &wk.d_counters()->lists.spectral, sizeof(int32_t), hipMemcpyDeviceToHost, wk.stream)); // (running total: the layers so far)
     }
     return BCD_HIP_OK;
 }
 
-// bayes_temporal (bcd_temporal.hip) for L layers on one selection: the lists once, the layered fallback kernel on the side stream, per layer and chunk the
-// temporal prepare kernel on that layer's images of every frame followed by the solver and finish kernels on its frame-0 colours, the in-frame masks and
-// its sum image.  d_count goes to the fallback kernel and to the first layer's chain only.  redo[k]: the items of layer k that took the redo list; their sum
-// is left in wk.h_counters->lists.spectral beside the list lengths and the sum of |S|.  Synchronises the stream at its end.  Whatever fails behind the fork,
-// nothing is left running on the side stream when the call returns: the accumulators may be the caller's.
+// bayes_temporal (bcd_temporal.hip) for L layers on one selection: the lists once, the layered fallback kernel on the side stream, per layer one chain of full
+// estimates on that layer's images of every frame, the in-frame masks and its sum image.  d_count goes to the fallback kernel and to the first layer's chain
+// only.  redo[k]: the items of layer k that took the redo list; their sum is left in wk.h_counters->lists.spectral beside the list lengths and the sum of |S|.
+// Synchronises the stream at its end.  Whatever fails behind the fork, nothing is left running on the side stream when the call returns: the accumulators
+// may be the caller's.
 int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
                           float *const *d_sum, int32_t *d_count, int32_t *redo)
 {
-    constexpr int K = 27;
-    const int64_t npix = (int64_t)W * H;
     const int L = lf.L;
-    wk.redo.pending = false;
-    RCCHK(ensure(ctx, wk.strong, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.weak, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.counters, sizeof(Counters)));
-    RCCHK(ensure(ctx, wk.work_q, BCD_WORK_INTS * sizeof(int32_t)));
+    TemporalLists ls;
+    RCCHK(temporal_lists(ctx, wk, d_nsim_total, d_state, (int64_t)W * H, &ls));
     Counters::Lists *d_c = &wk.d_counters()->lists, *h_c = &wk.h_counters->lists;
     Counters *h = wk.h_counters;
-    touch(wk); // (the counters and work queues are cleared here, whatever k_scale_begin left)
-    h_c->spectral = 0;
-    HIPCHK(ctx, hipMemsetAsync(d_c, 0, sizeof(*d_c), wk.stream));
-    HIPCHK(ctx, bcd_launch_active_lists(d_state, d_nsim_total, 0, npix, K + 1, (int32_t *)wk.strong.p, (int32_t *)wk.weak.p, &d_c->n_strong, wk.stream, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(h_c, d_c, offsetof(Counters::Lists, generic_work), hipMemcpyDeviceToHost, wk.stream)); // (the list lengths and the sum of |S|)
-    const int cus = std::max(1, ctx->num_cus * ctx->cu_share_pct / 100);
     // ---- the fallback pixels of every layer: one launch on the side stream, behind the lists
     BcdFrameLayerTable t = {};
     t.n = lf.nf; t.layers = L;
@@ -94,12 +66,11 @@ int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, con
     RCCHK(fork_aux(ctx, wk));
     int rc = BCD_HIP_OK;
     {
-        const hipError_t e = bcd_launch_bayes_weak_temporal_layers(t, (const int32_t *)wk.weak.p, &d_c->n_weak,
-                                                                   (int)std::min<int64_t>(std::max<int64_t>(1, npix / 7), (int64_t)cus * 32), W, b, d_count, wk.aux);
+        const hipError_t e = bcd_launch_bayes_weak_temporal_layers(t, (const int32_t *)wk.weak.p, &d_c->n_weak, ls.weak_grid, W, b, d_count, wk.aux);
         if (e != hipSuccess) { set_err(ctx, std::string("bcd_launch_bayes_weak_temporal_layers: ") + hipGetErrorString(e)); rc = BCD_HIP_EDEVICE; }
     }
     // ---- the full estimates on the workspace's own stream, then the join
-    if (rc == BCD_HIP_OK) rc = layer_chains(ctx, wk, lf, W, H, b, min_eig, d_sum, d_count, cus);
+    if (rc == BCD_HIP_OK) rc = layer_chains(ctx, wk, lf, W, H, b, min_eig, d_sum, d_count, ls.cus);
     if (rc != BCD_HIP_OK) {
         (void)hipStreamSynchronize(wk.aux); // (the fallback kernel adds into the accumulators: it ends before the error is reported)
         (void)hipStreamSynchronize(wk.stream);
@@ -119,78 +90,50 @@ struct LevelFrame {
     const float *col[ML], *cov[ML];
 };
 
-// one scale, frames[0] the frame itself at this level: the steps of temporal_scale with the estimate stage per layer
-// valid: null, or per frame the validity bytes of this level (null: the frame is not warped)
+// one scale, frames[0] the frame itself at this level: the shared selection stage (temporal_select), the estimate stage per layer, the shared stats tail
+// valid: per frame the validity bytes of this level (null: the frame is not warped)
 int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, int L, int W, int H, int D, const bcd_hip_params *prm, int scale, float *const *d_out,
-                          const uint8_t *const *valid = nullptr)
+                          const uint8_t *const *valid)
 {
     Work &wk = ctx->main;
     auto &tp = ctx->temporal;
-    const int w = prm->patch_radius, b = prm->search_radius;
-    const float tau = prm->hist_dist_threshold;
-    const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
-    RCCHK(ensure(ctx, wk.mask, npix * words * sizeof(uint32_t)));
-    RCCHK(ensure(ctx, wk.nsim, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, wk.state, npix));
-    RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
-    RCCHK(ensure(ctx, tp.count_nb, npix * sizeof(int32_t)));
+    const size_t npix = (size_t)W * H;
     RCCHK(ensure(ctx, tp.lay_sum, (size_t)L * npix * 3 * sizeof(float)));
+    TemporalSelFrame sel[NF];
     for (int f = 0; f < nf; ++f) {
         RCCHK(ensure(ctx, tp.lay_pixcov[f], (size_t)L * npix * 6 * sizeof(float)));
-        if (f > 0) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
+        sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
     }
-    bcd_hip_scale_stats &st = ctx->stats[scale];
-    memset(&st, 0, sizeof(st));
-    st.width = W; st.height = H;
-    st.main_pixels = (int64_t)std::max(0, W - 2 * w) * std::max(0, H - 2 * w);
-    const bool prof = ctx->profiling;
-    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
-    // S_0, then per frame the per-pixel covariances of its layers (one launch; it also clears the layers' sums) and, for a neighbour, its cross pass
-    RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
-    int32_t path = 0, borderline = 0, capacity = 0;
-    RCCHK(bcd_hip_similarity_last_path(ctx, &path, &borderline, &capacity));
+    TemporalPath path;
+    RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int { // per frame the per-pixel covariances of its layers: one launch; it also clears the layers' sums
+        for (int f = 0; f < nf; ++f) {
+            BcdLayerTable t = {};
+            for (int k = 0; k < L; ++k) t.a[k] = frames[f].cov[k];
+            HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, L, frames[f].ns, (int64_t)npix, (float *)tp.lay_pixcov[f].p, (float *)tp.lay_sum.p, wk.stream));
+        }
+        return BCD_HIP_OK;
+    }, &path));
     LayerFrames lf;
     lf.nf = nf; lf.L = L;
     float *sum[ML];
     for (int k = 0; k < L; ++k) sum[k] = (float *)tp.lay_sum.p + (size_t)k * npix * 3;
     for (int f = 0; f < nf; ++f) {
-        BcdLayerTable t = {};
-        for (int k = 0; k < L; ++k) t.a[k] = frames[f].cov[k];
-        HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, L, frames[f].ns, (int64_t)npix, (float *)tp.lay_pixcov[f].p, (float *)tp.lay_sum.p, wk.stream));
         for (int k = 0; k < L; ++k) { lf.col[f][k] = frames[f].col[k]; lf.pixcov[f][k] = (const float *)tp.lay_pixcov[f].p + (size_t)k * npix * 6; }
-        lf.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : (const uint32_t *)tp.mask[f].p;
-        if (f == 0) continue;
-        RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
-        HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p, wk.stream));
-        if (valid && valid[f]) RCCHK(temporal_gate(ctx, wk, valid[f], W, H, w, b, (uint32_t *)tp.mask[f].p, (int32_t *)tp.count_nb.p));
-        HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, (const int32_t *)tp.count_nb.p, (int64_t)npix, wk.stream));
+        lf.mask[f] = temporal_mask(ctx, f);
     }
-    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
-    RCCHK(bcd_hip_active_set(ctx, (const uint32_t *)wk.mask.p, (const int32_t *)wk.nsim.p, W, H, w, b, 0, H, prm->marked_skip_probability, prm->use_random_pixel_order,
-                             bcd_hip_scale_seed(prm->order_seed, scale), (uint8_t *)wk.state.p, &st.active_rounds));
-    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[2], wk.stream));
     HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
     int32_t redo[ML] = {};
-    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, prm->min_eigen_value, sum, (int32_t *)wk.cnt.p, redo));
-    if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
+    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, prm->search_radius, prm->min_eigen_value, sum, (int32_t *)wk.cnt.p,
+                                redo));
+    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
     {
         BcdLayerTable t = {};
         for (int k = 0; k < L; ++k) { t.a[k] = sum[k]; t.o[k] = d_out[k]; }
         HIPCHK(ctx, bcd_launch_layers_finalize(t, L, (const int32_t *)wk.cnt.p, (int64_t)npix, wk.stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    const Counters::Lists &h = wk.h_counters->lists;
-    st.processed = (int64_t)h.n_strong + h.n_weak; st.fallback = h.n_weak; st.similar_total = h.sim_total; // (the sum of the TOTAL |S|)
-    st.similarity_path = path; st.borderline_pairs = borderline;                                          // (those of the in-frame pass)
-    st.cu_share = ctx->cu_share_pct;
-    st.spectral_inverses = h.spectral;                                                                    // (the sum over the layers)
+    temporal_stats_tail(ctx, scale, path);
     for (int k = 0; k < L; ++k) ctx->layer_spectral[scale][k] = redo[k];
-    if (prof) {
-        st.ms_similarity = stage_ms(wk, 0, 1); // (includes the cross passes)
-        st.ms_active = stage_ms(wk, 1, 2);
-        st.ms_bayes = stage_ms(wk, 2, 3);
-        st.ms_total = stage_ms(wk, 0, 3);
-    }
     return BCD_HIP_OK;
 }
 
@@ -212,17 +155,12 @@ int check_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_h
         set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
         return BCD_HIP_EUNSUPPORTED;
     }
-    const size_t npix = (size_t)W * H, f4 = sizeof(float), no = npix * 3 * f4;
-    for (int k = 0; k < L; ++k) {
-        const void *out = layers[k].d_out;
-        for (int f = 0; f < n; ++f) {
-            if (overlap(out, no, nb[f].d_nsamples, npix * f4) || overlap(out, no, nb[f].d_histograms, npix * D * f4))
-                return bad(ctx, "a layer's output overlaps an image of a neighbour frame");
-            for (int j = 0; j < L; ++j)
-                if (overlap(out, no, nb[f].layers[j].d_colors, npix * 3 * f4) || overlap(out, no, nb[f].layers[j].d_covariances, npix * 6 * f4))
+    const size_t npix = (size_t)W * H, no = npix * 3 * sizeof(float);
+    for (int k = 0; k < L; ++k)
+        for (int f = 0; f < n; ++f)
+            for (int j = 0; j < L; ++j) // (the neighbour's sample counts and histograms are looked at with each of its layers)
+                if (overlaps_frame_images(layers[k].d_out, no, nb[f].layers[j].d_colors, nb[f].d_nsamples, nb[f].d_histograms, nb[f].layers[j].d_covariances, npix, D))
                     return bad(ctx, "a layer's output overlaps an image of a neighbour frame");
-        }
-    }
     return BCD_HIP_OK;
 }
 
@@ -249,19 +187,19 @@ int bcd_hip_bayes_accumulate_temporal_layers(bcd_hip_ctx *ctx, const bcd_hip_sta
     if (w != 1 || b != 6) { set_err(ctx, "the estimate over several frames supports patch radius 1 and search radius 6"); return BCD_HIP_EUNSUPPORTED; }
     {
         const size_t npix = (size_t)W * H, f4 = sizeof(float), ns = npix * 3 * f4, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
-        if (overlap(d_count, npix * 4, d_nsim_total, npix * 4) || overlap(d_count, npix * 4, d_state, npix)) return bad(ctx, "the accumulators overlap each other or the selection");
+        if (bytes_overlap(d_count, npix * 4, d_nsim_total, npix * 4) || bytes_overlap(d_count, npix * 4, d_state, npix)) return bad(ctx, "the accumulators overlap each other or the selection");
         for (int k = 0; k < nb_layers; ++k) {
             const void *s = d_sum[k];
-            if (overlap(s, ns, d_count, npix * 4) || overlap(s, ns, d_nsim_total, npix * 4) || overlap(s, ns, d_state, npix)) return bad(ctx, "the accumulators overlap each other or the selection");
-            for (int j = 0; j < k; ++j) if (overlap(s, ns, d_sum[j], ns)) return bad(ctx, "two layers share (part of) a sum image");
+            if (bytes_overlap(s, ns, d_count, npix * 4) || bytes_overlap(s, ns, d_nsim_total, npix * 4) || bytes_overlap(s, ns, d_state, npix)) return bad(ctx, "the accumulators overlap each other or the selection");
+            for (int j = 0; j < k; ++j) if (bytes_overlap(s, ns, d_sum[j], ns)) return bad(ctx, "two layers share (part of) a sum image");
         }
         for (int f = 0; f < nb_frames; ++f) {
-            if (overlap(d_count, npix * 4, frames[f].d_mask, npix * words * 4)) return bad(ctx, "an accumulator overlaps an input image");
+            if (bytes_overlap(d_count, npix * 4, frames[f].d_mask, npix * words * 4)) return bad(ctx, "an accumulator overlaps an input image");
             for (int j = 0; j < nb_layers; ++j) {
-                if (overlap(d_count, npix * 4, frames[f].d_colors[j], ns) || overlap(d_count, npix * 4, frames[f].d_pixel_cov[j], npix * 6 * f4)) return bad(ctx, "an accumulator overlaps an input image");
+                if (bytes_overlap(d_count, npix * 4, frames[f].d_colors[j], ns) || bytes_overlap(d_count, npix * 4, frames[f].d_pixel_cov[j], npix * 6 * f4)) return bad(ctx, "an accumulator overlaps an input image");
                 for (int k = 0; k < nb_layers; ++k)
-                    if (overlap(d_sum[k], ns, frames[f].d_colors[j], ns) || overlap(d_sum[k], ns, frames[f].d_pixel_cov[j], npix * 6 * f4) ||
-                        overlap(d_sum[k], ns, frames[f].d_mask, npix * words * 4))
+                    if (bytes_overlap(d_sum[k], ns, frames[f].d_colors[j], ns) || bytes_overlap(d_sum[k], ns, frames[f].d_pixel_cov[j], npix * 6 * f4) ||
+                        bytes_overlap(d_sum[k], ns, frames[f].d_mask, npix * words * 4))
                         return bad(ctx, "an accumulator overlaps an input image");
             }
         }
@@ -276,25 +214,31 @@ int bcd_hip_bayes_accumulate_temporal_layers(bcd_hip_ctx *ctx, const bcd_hip_sta
     return bayes_temporal_layers(ctx, ctx->main, lf, d_nsim_total, d_state, W, H, b, min_eig, d_sum, d_count, h_redo);
 }
 
+// one layer is the frame call (host: of host buffers) on that layer; motion: null, or the list of a motion call
+static int single_layer_call(bcd_hip_ctx *ctx, bool host, const float *ns, const float *hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
+                             int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer &layer, const float *const *motion)
+{
+    bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
+    for (int f = 0; f < nb_neighbours; ++f)
+        nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
+    if (motion)
+        RCCHK((host ? bcd_hip_denoise_temporal_motion_host : bcd_hip_denoise_temporal_motion)(ctx, layer.d_colors, ns, hist, layer.d_covariances, nb, nb_neighbours, motion, W,
+                                                                                             H, D, nb_scales, prm, layer.d_out));
+    else
+        RCCHK((host ? bcd_hip_denoise_temporal_host : bcd_hip_denoise_temporal)(ctx, layer.d_colors, ns, hist, layer.d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm,
+                                                                               layer.d_out));
+    memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+    for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
+    ctx->layer_count = 1;
+    return BCD_HIP_OK;
+}
+
 // the checked device call; motion: null, or per neighbour a device motion field or null
 static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
                       int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const float *const *motion)
 {
     if (nb_neighbours == 0) return bcd_hip_denoise_layers(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
-    if (nb_layers == 1) {
-        bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
-        for (int f = 0; f < nb_neighbours; ++f)
-            nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
-        if (motion)
-            RCCHK(bcd_hip_denoise_temporal_motion(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, nb, nb_neighbours, motion, W, H, D, nb_scales, prm,
-                                                  layers[0].d_out));
-        else
-            RCCHK(bcd_hip_denoise_temporal(ctx, layers[0].d_colors, d_ns, d_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
-        memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
-        for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
-        ctx->layer_count = 1;
-        return BCD_HIP_OK;
-    }
+    if (nb_layers == 1) return single_layer_call(ctx, false, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers[0], motion);
     DEVICE_GUARD(ctx);
     const int nf = nb_neighbours + 1, S = nb_scales, L = nb_layers;
     auto &tp = ctx->temporal;
@@ -322,27 +266,18 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
         // layers by the layered one (it writes the same validity bytes again); the pyramid is built from the warped images
         const size_t npix = (size_t)W * H;
         LevelFrame &l = lv[f];
-        DevBuf(&wb)[4] = tp.warp[f];
         DevBuf(&lw)[2] = tp.lay_warp[f];
-        RCCHK(ensure(ctx, wb[0], npix * 3 * sizeof(float)));
-        RCCHK(ensure(ctx, wb[1], npix * sizeof(float)));
-        RCCHK(ensure(ctx, wb[2], npix * D * sizeof(float)));
-        RCCHK(ensure(ctx, wb[3], npix * 6 * sizeof(float)));
         RCCHK(ensure(ctx, lw[0], (size_t)(L - 1) * npix * 3 * sizeof(float)));
         RCCHK(ensure(ctx, lw[1], (size_t)(L - 1) * npix * 6 * sizeof(float)));
-        RCCHK(ensure(ctx, tp.valid[f][0], npix));
-        HIPCHK(ctx, bcd_launch_warp_frame(l.col[0], l.ns, l.hist, l.cov[0], motion[f - 1], W, H, D, (float *)wb[0].p, (float *)wb[1].p, (float *)wb[2].p, (float *)wb[3].p,
-                                          (uint8_t *)tp.valid[f][0].p, st));
         BcdWarpLayerTable t = {};
         for (int k = 1; k < L; ++k) {
             t.col[k - 1] = l.col[k]; t.cov[k - 1] = l.cov[k];
             t.ocol[k - 1] = (float *)lw[0].p + (size_t)(k - 1) * npix * 3; t.ocov[k - 1] = (float *)lw[1].p + (size_t)(k - 1) * npix * 6;
         }
-        HIPCHK(ctx, bcd_launch_warp_layers(t, L - 1, motion[f - 1], W, H, (uint8_t *)tp.valid[f][0].p, st));
-        RCCHK(temporal_valid_levels(ctx, f, W, H, S));
-        l.ns = (const float *)wb[1].p; l.hist = (const float *)wb[2].p; l.col[0] = (const float *)wb[0].p; l.cov[0] = (const float *)wb[3].p;
+        const float *wp[4];
+        RCCHK(temporal_warp_neighbour(ctx, f, nf, l.col[0], l.ns, l.hist, l.cov[0], motion[f - 1], W, H, D, S, &t, L - 1, valid.data(), wp));
+        l.col[0] = wp[0]; l.ns = wp[1]; l.hist = wp[2]; l.cov[0] = wp[3];
         for (int k = 1; k < L; ++k) { l.col[k] = t.ocol[k - 1]; l.cov[k] = t.ocov[k - 1]; }
-        for (int s = 0; s < S; ++s) valid[(size_t)s * nf + f] = (const uint8_t *)tp.valid[f][s].p;
     }
     for (int s = 1; s < S; ++s) {
         ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
@@ -389,11 +324,6 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
 
 // the outputs of the layers, for check_motion_list
 static void layer_outs(const bcd_hip_layer *layers, int L, float **outs) { for (int k = 0; k < L; ++k) outs[k] = layers[k].d_out; }
-static bool any_field(const float *const *motion, int n)
-{
-    for (int f = 0; motion && f < n; ++f) if (motion[f]) return true;
-    return false;
-}
 
 int bcd_hip_denoise_temporal_layers(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
                                     int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers)
@@ -425,20 +355,7 @@ static int layers_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_h
         for (int k = 0; k < L; ++k) hl[k] = { layers[k].d_colors, layers[k].d_covariances, layers[k].d_out };
         return bcd_hip_denoise_layers_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, nullptr, hl, L);
     }
-    if (L == 1) {
-        bcd_hip_frame nb[BCD_HIP_MAX_NEIGHBOURS];
-        for (int f = 0; f < nb_neighbours; ++f)
-            nb[f] = { neighbours[f].layers[0].d_colors, neighbours[f].d_nsamples, neighbours[f].d_histograms, neighbours[f].layers[0].d_covariances, nullptr };
-        if (h_motion)
-            RCCHK(bcd_hip_denoise_temporal_motion_host(ctx, layers[0].d_colors, h_ns, h_hist, layers[0].d_covariances, nb, nb_neighbours, h_motion, W, H, D, nb_scales, prm,
-                                                       layers[0].d_out));
-        else
-            RCCHK(bcd_hip_denoise_temporal_host(ctx, layers[0].d_colors, h_ns, h_hist, layers[0].d_covariances, nb, nb_neighbours, W, H, D, nb_scales, prm, layers[0].d_out));
-        memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
-        for (int s = 0; s < nb_scales; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses;
-        ctx->layer_count = 1;
-        return BCD_HIP_OK;
-    }
+    if (L == 1) return single_layer_call(ctx, true, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers[0], h_motion);
     DEVICE_GUARD(ctx);
     auto &tp = ctx->temporal;
     const size_t npix = (size_t)W * H, f4 = sizeof(float), bc = npix * 3 * f4, bv = npix * 6 * f4;
@@ -513,8 +430,8 @@ int bcd_hip_warp_layers(bcd_hip_ctx *ctx, const bcd_hip_frame_layer *layers, int
         if (d_motion) in.push_back({ d_motion, npix * 2 * sizeof(float) });
         dst.push_back({ d_valid, npix });
         for (size_t i = 0; i < dst.size(); ++i) {
-            for (const auto &x : in) if (overlap(dst[i].first, dst[i].second, x.first, x.second)) return bad(ctx, "a warp destination overlaps an input image or the motion field");
-            for (size_t j = 0; j < i; ++j) if (overlap(dst[i].first, dst[i].second, dst[j].first, dst[j].second)) return bad(ctx, "two warp destinations overlap");
+            for (const auto &x : in) if (bytes_overlap(dst[i].first, dst[i].second, x.first, x.second)) return bad(ctx, "a warp destination overlaps an input image or the motion field");
+            for (size_t j = 0; j < i; ++j) if (bytes_overlap(dst[i].first, dst[i].second, dst[j].first, dst[j].second)) return bad(ctx, "two warp destinations overlap");
         }
     }
     DEVICE_GUARD(ctx);

@@ -357,6 +357,9 @@ def _dp(t):
     return C.c_void_p(t.data_ptr())
 
 
+_dptr = lambda t: _dp(t).value      # ... as an address, for a structure field
+_hptr = lambda a: a.ctypes.data     # the address of a NumPy array
+
 class Context:
     """bcd_hip_ctx bound to a torch device/stream."""
 
@@ -928,17 +931,23 @@ class Context:
         self._chk(L.bcd_hip_bayes_accumulate_temporal(self.h, arr, len(frames), _dp(nsim_total), _dp(state), W, H, w, b, float(min_eig), _dp(s), _dp(c)))
         return s, c
 
+    @staticmethod
+    def _frame_array(neighbours, H, W, D, ptr, numel):
+        """the bcd_hip_frame array of a list of (col, ns, hist, cov) neighbour frames of the frame's size; ptr(a) is an address, numel(a) a number of elements"""
+        arr = (Frame * max(len(neighbours), 1))()
+        for i, f in enumerate(neighbours):
+            if tuple(f[0].shape) != (H, W, 3) or numel(f[1]) != H * W or tuple(f[2].shape) != (H, W, D) or tuple(f[3].shape) != (H, W, 6):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
+            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (ptr(a) for a in f)
+        return arr
+
     def denoise_temporal(self, col, ns, hist, cov, neighbours, nscales, prm, out=None):
         """bcd_hip_denoise_temporal: the frame (col, ns, hist, cov) denoised with similar patches from up to four neighbour frames of its sequence,
         each a (col, ns, hist, cov) tuple of device tensors of the frame's size.  No neighbour: denoise()."""
         torch = self.torch
         H, W, D = hist.shape
         neighbours = list(neighbours)
-        arr = (Frame * max(len(neighbours), 1))()
-        for i, f in enumerate(neighbours):
-            if tuple(f[0].shape) != (H, W, 3) or f[1].numel() != H * W or tuple(f[2].shape) != (H, W, D) or tuple(f[3].shape) != (H, W, 6):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (_dp(t).value for t in f)
+        arr = self._frame_array(neighbours, H, W, D, _dptr, torch.numel)
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=hist.device)
         L = lib()
@@ -954,11 +963,7 @@ class Context:
         col, ns, hist, cov = (as32(a) for a in (col, ns, hist, cov))
         H, W, D = hist.shape
         keep = [tuple(as32(a) for a in f) for f in neighbours]
-        arr = (Frame * max(len(keep), 1))()
-        for i, f in enumerate(keep):
-            if f[0].shape != (H, W, 3) or f[1].size != H * W or f[2].shape != (H, W, D) or f[3].shape != (H, W, 6):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (a.ctypes.data for a in f)
+        arr = self._frame_array(keep, H, W, D, _hptr, np.size)
         out = np.empty((H, W, 3), np.float32)
         L = lib()
         L.bcd_hip_denoise_temporal_host.argtypes = [_VP, _VP, _VP, _VP, _VP, C.POINTER(Frame), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), _VP]
@@ -1002,15 +1007,18 @@ class Context:
                                                              self._ptr_list(sums), _dp(c), redo))
         return sums, c, list(redo)[:nl]
 
-    def _frame_layers_array(self, neighbours, nl, check, ptr):
-        """the bcd_hip_frame_layers array of a list of (ns, hist, [(colours, covariances), ...]); check(i, ns, hist, layers) validates, ptr(a) is an address"""
+    @staticmethod
+    def _frame_layers_array(neighbours, nl, H, W, D, ptr, numel):
+        """the bcd_hip_frame_layers array of a list of (ns, hist, [(colours, covariances), ...]) of the frame's size; ptr(a) is an address, numel(a) a number of
+        elements"""
         arr = (FrameLayers * max(len(neighbours), 1))()
         keep = []
         for i, (ns, hist, layers) in enumerate(neighbours):
             layers = list(layers)
             if len(layers) != nl:
                 raise ValueError("neighbour %d: one layer per layer of the frame expected (%d, not %d)" % (i, nl, len(layers)))
-            check(i, ns, hist, layers)
+            if numel(ns) != H * W or tuple(hist.shape) != (H, W, D) or any(tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) for c, v in layers):
+                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
             la = (FrameLayer * max(nl, 1))()
             for k, (col, cov) in enumerate(layers):
                 la[k].d_colors, la[k].d_covariances = ptr(col), ptr(cov)
@@ -1026,11 +1034,7 @@ class Context:
         H, W, D = hist.shape
         arr, layers, outs = self._layer_array(layers, outs, H, W, hist.device)
         neighbours = list(neighbours)
-
-        def check(i, ns_f, hist_f, lay_f):
-            if ns_f.numel() != H * W or tuple(hist_f.shape) != (H, W, D) or any(tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) for c, v in lay_f):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-        nb, keep = self._frame_layers_array(neighbours, len(layers), check, lambda t: _dp(t).value)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _dptr, torch.numel)
         L = lib()
         L.bcd_hip_denoise_temporal_layers.argtypes = [_VP, _VP, _VP, C.POINTER(FrameLayers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
                                                       C.POINTER(Layer), C.c_int]
@@ -1052,11 +1056,7 @@ class Context:
             if col.shape != (H, W, 3) or cov.shape != (H, W, 6):
                 raise ValueError("layer %d: colours must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
             arr[k].d_colors, arr[k].d_covariances, arr[k].d_out = col.ctypes.data, cov.ctypes.data, out.ctypes.data
-
-        def check(i, ns_f, hist_f, lay_f):
-            if ns_f.size != H * W or hist_f.shape != (H, W, D) or any(c.shape != (H, W, 3) or v.shape != (H, W, 6) for c, v in lay_f):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-        nb, keep = self._frame_layers_array(neighbours, len(layers), check, lambda a: a.ctypes.data)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _hptr, np.size)
         L = lib()
         L.bcd_hip_denoise_temporal_layers_host.argtypes = [_VP, _VP, _VP, C.POINTER(FrameLayers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
                                                            C.POINTER(Layer), C.c_int]
@@ -1088,12 +1088,8 @@ class Context:
         torch = self.torch
         H, W, D = hist.shape
         neighbours = list(neighbours)
-        arr = (Frame * max(len(neighbours), 1))()
-        for i, f in enumerate(neighbours):
-            if tuple(f[0].shape) != (H, W, 3) or f[1].numel() != H * W or tuple(f[2].shape) != (H, W, D) or tuple(f[3].shape) != (H, W, 6):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (_dp(t).value for t in f)
-        mv = self._motion_array(motions, len(neighbours), H, W, lambda t: _dp(t).value, lambda t: t.numel())
+        arr = self._frame_array(neighbours, H, W, D, _dptr, torch.numel)
+        mv = self._motion_array(motions, len(neighbours), H, W, _dptr, torch.numel)
         if out is None:
             out = torch.empty((H, W, 3), dtype=torch.float32, device=hist.device)
         L = lib()
@@ -1109,13 +1105,9 @@ class Context:
         col, ns, hist, cov = (as32(a) for a in (col, ns, hist, cov))
         H, W, D = hist.shape
         keep = [tuple(as32(a) for a in f) for f in neighbours]
-        arr = (Frame * max(len(keep), 1))()
-        for i, f in enumerate(keep):
-            if f[0].shape != (H, W, 3) or f[1].size != H * W or f[2].shape != (H, W, D) or f[3].shape != (H, W, 6):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-            arr[i].d_colors, arr[i].d_nsamples, arr[i].d_histograms, arr[i].d_covariances = (a.ctypes.data for a in f)
+        arr = self._frame_array(keep, H, W, D, _hptr, np.size)
         fields = None if motions is None else [None if m is None else as32(m) for m in motions]
-        mv = self._motion_array(fields, len(keep), H, W, lambda a: a.ctypes.data, lambda a: a.size)
+        mv = self._motion_array(fields, len(keep), H, W, _hptr, np.size)
         out = np.empty((H, W, 3), np.float32)
         L = lib()
         L.bcd_hip_denoise_temporal_motion_host.argtypes = [_VP, _VP, _VP, _VP, _VP, C.POINTER(Frame), C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), _VP]
@@ -1129,12 +1121,8 @@ class Context:
         H, W, D = hist.shape
         arr, layers, outs = self._layer_array(layers, outs, H, W, hist.device)
         neighbours = list(neighbours)
-
-        def check(i, ns_f, hist_f, lay_f):
-            if ns_f.numel() != H * W or tuple(hist_f.shape) != (H, W, D) or any(tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) for c, v in lay_f):
-                raise ValueError("neighbour %d: images of the frame's width, height and histogram depth are expected" % i)
-        nb, keep = self._frame_layers_array(neighbours, len(layers), check, lambda t: _dp(t).value)
-        mv = self._motion_array(motions, len(neighbours), H, W, lambda t: _dp(t).value, lambda t: t.numel())
+        nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _dptr, torch.numel)
+        mv = self._motion_array(motions, len(neighbours), H, W, _dptr, torch.numel)
         L = lib()
         L.bcd_hip_denoise_temporal_layers_motion.argtypes = [_VP, _VP, _VP, C.POINTER(FrameLayers), C.c_int, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
                                                              C.POINTER(Layer), C.c_int]

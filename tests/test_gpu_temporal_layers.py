@@ -13,6 +13,7 @@ tests/temporal_layers_cases.py), L = 3: the frame itself and a smooth and a text
     clearNeighbourFrames() gives the plain layered call again; a neighbour with a missing layer is refused;
   * bcd_cli --neighbour-layer end to end (the half-float comparison of the other CLI tests); a miscounted --neighbour-layer is an argument error;
   * a plain bcd_hip_denoise_temporal and a bcd_hip_denoise_layers after the layered call equal a fresh context's;
+  * the stage timers, width, height and cu_share of every scale of the frame call and of the layered call, with profiling on and off;
   * every refusal of the frame call, then a successful call on the same context."""
 import numpy as np
 import pytest
@@ -160,6 +161,41 @@ def test_plain_calls_after_the_layered_call_equal_a_fresh_context_s():
     assert rel_linf(out["after"][0], out["fresh"][0]) <= TOL
     for k in range(L):
         assert rel_linf(out["after"][2][k], out["fresh"][2][k]) <= TOL, k
+
+
+def test_stage_timers_and_geometry_of_the_temporal_calls(hipctx):
+    """bcd_hip_denoise_temporal and bcd_hip_denoise_temporal_layers (two layers) at 64x44, two scales, one neighbour, m = 1: with profiling on, the four stage
+    timers of every scale are finite and not negative and the total is at least each part; width, height and cu_share are the level's; with profiling off the
+    timers are zero.  No timer is compared with a number of milliseconds."""
+    W, H, S, F = 64, 44, 2, 1
+    prm = params(1.0, 1)
+    timers = ("ms_similarity", "ms_active", "ms_bayes", "ms_total")
+    calls = (("temporal", lambda: single(hipctx, W, H, S, F, prm, 0)), ("temporal-layers", lambda: layered(hipctx, W, H, S, F, prm, nl=2)))
+
+    def geometry(name):
+        for s in range(S):
+            st = hipctx.stats(s)
+            assert (st.width, st.height, st.cu_share) == (W >> s, H >> s, 100), (name, s, st.width, st.height, st.cu_share)
+
+    hipctx.set_profiling(True)
+    try:
+        for name, call in calls:
+            call()
+            geometry(name)
+            for s in range(S):
+                st = hipctx.stats(s)
+                ms = [float(getattr(st, t)) for t in timers]
+                print("%s %dx%d scale %d: %s" % (name, W, H, s, " ".join("%s=%.4f" % (t, v) for t, v in zip(timers, ms))))
+                assert all(np.isfinite(v) and v >= 0 for v in ms), (name, s, ms)
+                assert all(ms[3] >= v for v in ms[:3]), (name, s, ms)
+    finally:
+        hipctx.set_profiling(False)
+    for name, call in calls:
+        call()
+        geometry(name)
+        for s in range(S):
+            st = hipctx.stats(s)
+            assert all(getattr(st, t) == 0 for t in timers), (name, s)
 
 
 def test_refusals_of_the_frame_call_then_a_successful_call(hipctx):
