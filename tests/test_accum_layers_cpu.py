@@ -25,13 +25,13 @@ def block(W=5, H=3, L=2, extra=0, **kw):
 def info_rc(buf, size=None):
     a = np.frombuffer(buf, np.uint8)
     out = bh.LayersHeader()
-    rc = bh._layers_api().bcd_hip_accum_layers_state_info(a.ctypes.data_as(C.c_void_p), len(buf) if size is None else size, C.byref(out))
+    rc = bh.lib().bcd_hip_accum_layers_state_info(a.ctypes.data_as(C.c_void_p), len(buf) if size is None else size, C.byref(out))
     return rc, out
 
 
 def test_layer_entry_points_refuse_a_null_accumulator():
     """in the manner of test_splat_entry_points_refuse_a_null_accumulator: no device is touched, nothing is enqueued"""
-    L = bh._layers_api()
+    L = bh.lib()
     h = C.c_void_p()
     n, b = C.c_int(7), C.c_int64(7)
     one = (C.c_void_p * 1)()
@@ -67,7 +67,7 @@ def test_well_formed_block_is_accepted():
     assert d == {"magic": b"BCDACCLY", "version": 1, "header_bytes": 64, "width": 7, "height": 4, "nb_layers": 3, "nb_planes": 27}
     info, planes = bh.accum_layers_state_planes(bytearray(s))
     assert info == d and planes.shape == (3, 9, 4, 7) and planes.dtype == np.float32
-    assert bh._layers_api().bcd_hip_accum_layers_state_info(C.c_char_p(s), C.c_int64(len(s)), None) == 0     # (out may be NULL)
+    assert bh.lib().bcd_hip_accum_layers_state_info(C.c_char_p(s), C.c_int64(len(s)), None) == 0     # (out may be NULL)
     for L in (1, 15):
         assert info_rc(block(L=L))[0] == 0
 
@@ -103,7 +103,7 @@ def test_size_argument_is_the_whole_block():
     s = block()
     assert info_rc(s, len(s))[0] == 0
     assert info_rc(s, len(s) - 4)[0] == EINVAL and info_rc(s, len(s) + 4)[0] == EINVAL and info_rc(s, 63)[0] == EINVAL
-    assert bh._layers_api().bcd_hip_accum_layers_state_info(None, C.c_int64(len(s)), None) == EINVAL
+    assert bh.lib().bcd_hip_accum_layers_state_info(None, C.c_int64(len(s)), None) == EINVAL
 
 
 def test_a_v1_state_is_not_a_layer_block_and_the_reverse():

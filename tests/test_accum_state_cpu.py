@@ -27,7 +27,7 @@ def state(W=5, H=3, bins=20, extra=0, **kw):
 
 
 def info_rc(buf, size=None):
-    L = bh._state_api()
+    L = bh.lib()
     a = np.frombuffer(buf, np.uint8)
     out = bh.StateHeader()
     return L.bcd_hip_accum_state_info(a.ctypes.data_as(C.c_void_p), len(buf) if size is None else size, C.byref(out)), out

@@ -17,11 +17,10 @@ def test_default_plan_params():
 
 def test_plan_rejects_a_null_accumulator():
     L = bh.lib()
-    L.bcd_hip_accum_plan.argtypes = bh.PLAN_ARGTYPES
     pix = (C.c_int32 * 4)(*[-7] * 4)
     summ = bh.PlanSummary(-1, -1, -1, -1.0)
     prm = bh.default_plan_params()
-    rc = L.bcd_hip_accum_plan(None, C.byref(prm), 4, 0, None, None, C.cast(pix, C.c_void_p), 4, C.cast(C.pointer(summ), C.c_void_p))
+    rc = L.bcd_hip_accum_plan(None, C.byref(prm), 4, 0, None, None, C.cast(pix, C.c_void_p), 4, C.byref(summ))
     assert rc == -1                                              # BCD_HIP_EINVAL
     assert list(pix) == [-7] * 4 and summ.planned == -1
 

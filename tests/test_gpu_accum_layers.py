@@ -310,7 +310,7 @@ def test_refusals_leave_the_state_alone(hipctx):
     for bad_count in (0, 16, -1):
         if bad_count == 0:                                     # (Python's layers=0 is the plain accumulator: the C entry point)
             h = bh.C.c_void_p()
-            rc = bh._layers_api().bcd_hip_accum_create_layers(hipctx.h, W, H, 20, 2.2, 2.5, 0, 0, bh.C.byref(h))
+            rc = bh.lib().bcd_hip_accum_create_layers(hipctx.h, W, H, 20, 2.2, 2.5, 0, 0, bh.C.byref(h))
             assert rc == -1 and not h.value
         else:
             with pytest.raises(bh.BcdHipError, match="rc=-1"):

@@ -278,7 +278,7 @@ def test_merge_keeps_stream_order_across_contexts(hipctx):
 
 def test_refusals_leave_the_state_untouched(hipctx):
     W, H = 23, 17
-    L = bh._state_api()
+    L = bh.lib()
     acc = hipctx.accumulator(W, H)
     k = feed(acc, np.random.default_rng(11), W, H)
     good = acc.export_state()

@@ -161,7 +161,6 @@ def test_plan_is_non_destructive_repeatable_and_validated(hipctx):
         assert bits_equal(x, y)
 
     L = bh.lib()
-    L.bcd_hip_accum_plan.argtypes = bh.PLAN_ARGTYPES
     N, B = W * H, 100
     err = torch.full((N,), -2.0, device="cuda")
     cnt = torch.full((N,), -3, dtype=torch.int32, device="cuda")
@@ -170,19 +169,20 @@ def test_plan_is_non_destructive_repeatable_and_validated(hipctx):
     keep = [t.clone() for t in (err, cnt, pix, summ)]
     ok = bh.default_plan_params()
     dp = lambda t: C.c_void_p(t.data_ptr())
-    cases = [(None, ok, B, dp(pix), B, dp(summ)), (acc.h, None, B, dp(pix), B, dp(summ)), (acc.h, ok, B, None, B, dp(summ)),
-             (acc.h, ok, B, dp(pix), B, None), (acc.h, ok, B, dp(pix), B - 1, dp(summ)), (acc.h, ok, -1, dp(pix), B, dp(summ)),
-             (acc.h, ok, 1 << 31, dp(pix), 1 << 32, dp(summ))]
+    ds = lambda t: C.cast(dp(t), C.POINTER(bh.PlanSummary))      # (the summary lives on the device: its address as the prototype's struct pointer)
+    cases = [(None, ok, B, dp(pix), B, ds(summ)), (acc.h, None, B, dp(pix), B, ds(summ)), (acc.h, ok, B, None, B, ds(summ)),
+             (acc.h, ok, B, dp(pix), B, None), (acc.h, ok, B, dp(pix), B - 1, ds(summ)), (acc.h, ok, -1, dp(pix), B, ds(summ)),
+             (acc.h, ok, 1 << 31, dp(pix), 1 << 32, ds(summ))]
     for kw in ({"threshold": float("nan")}, {"threshold": -1.0}, {"threshold": float("inf")}, {"eps": 0.0}, {"eps": float("nan")},
                {"min_samples": float("nan")}, {"min_samples": -1.0}, {"max_per_pixel": 0}, {"max_per_pixel": 65536}):
-        cases.append((acc.h, bh.default_plan_params(**kw), B, dp(pix), B, dp(summ)))
+        cases.append((acc.h, bh.default_plan_params(**kw), B, dp(pix), B, ds(summ)))
     for h, prm, budget, p, cap, s in cases:
         rc = L.bcd_hip_accum_plan(h, C.byref(prm) if prm is not None else None, budget, 0, dp(err), dp(cnt), p, cap, s)
         assert rc == -1
     torch.cuda.synchronize()
     for x, y in zip((err, cnt, pix, summ), keep):
         assert torch.equal(x, y)
-    assert L.bcd_hip_accum_plan(acc.h, C.byref(ok), B, 0, dp(err), dp(cnt), dp(pix), B, dp(summ)) == 0
+    assert L.bcd_hip_accum_plan(acc.h, C.byref(ok), B, 0, dp(err), dp(cnt), dp(pix), B, ds(summ)) == 0
     torch.cuda.synchronize()
     assert int(summ[0]) == B and int(cnt.sum()) == B
     acc.close()

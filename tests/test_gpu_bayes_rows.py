@@ -321,8 +321,6 @@ def test_word_carries_the_verdict_of_the_deferred_similarity_pass(hipctx):
     import bcd_amd.hip as bh
     import torch
     L = bh.lib()
-    L.bcd_hip_similarity_masks_deferred.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    L.bcd_hip_similarity_masks_verdict.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     _, ns_a, hist_a, _, _ = ol.synth_inputs(40, 30, 16, 21, 0.3, 0.0)              # an ordinary frame
     W, H = 128, 160                                                              # one pixel outside the range the production distance kernels guard
     _, ns_b, hist_b, _ = core.synthetic_scene(W, H, 16, 4, 0.2, 0.0)
@@ -430,7 +428,7 @@ def test_chain_marking_batch_word_speculative_estimate(order):
 def test_bad_calls_are_refused_before_any_device_work_then_a_good_call(hipctx):
     import torch
     import bcd_amd.hip as bh
-    L = bh._rows_api()
+    L = bh.lib()
     rng = np.random.default_rng(6)
     c = rc.case("sizes dense")
     H, W, _ = c.col.shape

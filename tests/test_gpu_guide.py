@@ -258,9 +258,6 @@ def test_refusals_leave_the_context_usable(hipctx):
     D = c["hist"].shape[2]
     out_a, out_b = torch.empty_like(d_col), torch.empty_like(d_col)
     L = bh.lib()
-    bh._selection_api()
-    L.bcd_hip_denoise_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.c_float, C.POINTER(bh.Layer), C.c_int,
-                                         C.POINTER(bh.Guide), C.c_void_p]
     EINVAL, EUNSUPPORTED = -1, -4
     good_floors = (C.c_float * 8)(*([1e-4] * 8))
 

@@ -266,7 +266,6 @@ def test_invalid_calls_are_refused_before_any_device_work(hipctx):
     d_col, d_ns, d_hist, d_cov = dev(col, ns, hist, cov)
     out_a, out_b = torch.empty_like(d_col), torch.empty_like(d_col)
     L = bh.lib()
-    L.bcd_hip_denoise_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.POINTER(bh.Layer), C.c_int]
 
     def call(layers, n=None, ns_ptr=d_ns.data_ptr(), hist_ptr=d_hist.data_ptr(), w=W, h=H, d=D, S=1, p=prm, null_list=False):
         arr = (bh.Layer * max(1, len(layers)))()

@@ -302,8 +302,6 @@ def test_invalid_stage_calls_are_refused_before_any_device_work(hipctx):
     s_a, s_b = torch.zeros((H, W, 3), device="cuda"), torch.zeros((H, W, 3), device="cuda")
     cnt = torch.zeros((H, W), dtype=torch.int32, device="cuda")
     L = bh.lib()
-    L.bcd_hip_bayes_accumulate_layers.argtypes = [C.c_void_p, C.POINTER(bh.StageLayer), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                                  C.c_void_p, C.POINTER(C.c_int32)]
 
     def call(layers, n=None, mask=d["mask"].data_ptr(), count=cnt.data_ptr(), w=1, b=6, width=W, null_list=False):
         arr = (bh.StageLayer * max(1, len(layers)))()
@@ -351,8 +349,6 @@ def test_sixteen_layer_redo_counters_leave_the_similarity_verdict_alone(hipctx):
     mask = torch.zeros((H, W, ((2 * b + 1) ** 2 + 31) // 32), dtype=torch.int32, device="cuda")
     cnt = torch.zeros((H, W), dtype=torch.int32, device="cuda")
     L = bh.lib()
-    L.bcd_hip_similarity_masks_deferred.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    L.bcd_hip_similarity_masks_verdict.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     assert L.bcd_hip_similarity_masks_deferred(hipctx.h, d_hist.data_ptr(), d_ns.data_ptr(), W, H, hist.shape[2], 1, b, 1.0, mask.data_ptr(), cnt.data_ptr()) == 0
     hipctx.synchronize()
     redo_masks = C.c_int(-1)

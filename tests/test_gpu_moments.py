@@ -161,8 +161,6 @@ def test_refusals_leave_the_context_usable(hipctx):
     (d_col, d_cov), d_ns = c["d_layers"][0], c["d_ns"]
     out_a, out_b = torch.empty_like(d_col), torch.empty_like(d_col)
     L = bh.lib()
-    bh._selection_api()
-    L.bcd_hip_denoise_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.c_float, C.POINTER(bh.Layer), C.c_int, C.c_void_p]
     EINVAL, EUNSUPPORTED = -1, -4
 
     def call(layers, n=None, ns=d_ns.data_ptr(), w_=W, h_=H, scales=3, p=prm, floor=EPS, sel=None, null_list=False):

@@ -234,8 +234,6 @@ def test_refusals_then_a_good_call(hipctx):
     with pytest.raises(ValueError):                                                    # a miscounted list never reaches the library
         hipctx.denoise_temporal_motion(*d, nb, mv * 2, 1, prm)
     L = bh.lib()
-    L.bcd_hip_denoise_temporal_motion.argtypes = [C.c_void_p] * 5 + [C.POINTER(bh.Frame), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params),
-                                                  C.c_void_p]
     one = (bh.Frame * 1)()
     one[0].d_colors, one[0].d_nsamples, one[0].d_histograms, one[0].d_covariances = (x.data_ptr() for x in nb[0])
     fields = (C.c_void_p * 1)(mv[0].data_ptr())

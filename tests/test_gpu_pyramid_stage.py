@@ -247,11 +247,6 @@ def _ptrs(bufs):
 def test_layer_batched_forms_at_tiny_and_block_boundary_sizes(hipctx, W, H, L):
     import bcd_amd.hip as bh
     lib = bh.lib()
-    lib.bcd_hip_layers_pixel_cov.argtypes = [_VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP]
-    lib.bcd_hip_layers_finalize.argtypes = [_VP, _VP, _VP, C.c_int, _VP, C.c_int64]
-    lib.bcd_hip_layers_downscale_avg.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int]
-    lib.bcd_hip_layers_downscale_cov.argtypes = [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int]
-    lib.bcd_hip_layers_merge.argtypes = [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int]
     o = ol.oracle_ops()
     h, w, npix = H // 2, W // 2, W * H
     scale = [np.float32(2.0 ** ((5 * k) % 17 - 8)) for k in range(L)]              # a magnitude of its own per layer: 2^-8 ... 2^8

@@ -267,7 +267,7 @@ def test_invalid_calls_are_refused_and_leave_the_selection_alone(hipctx):
     (d_col, d_cov), d_ns, d_hist, prm = c["d_layers"][0], c["d_ns"], c["d_hist"], c["prm"]
     H, W, D = c["host"][2].shape
     out_a, out_b = torch.empty_like(d_col), torch.empty_like(d_col)
-    L = bh._selection_api()
+    L = bh.lib()
     EINVAL = -1
 
     def reuse(layers, n=None, handle=sel.h, ns_ptr=None, null_list=False):

@@ -143,7 +143,6 @@ def _child():
 
     h = C.c_void_p()
     chk(lib.bcd_hip_ctx_create(C.byref(h), 0, None), "bcd_hip_ctx_create")
-    lib.bcd_hip_selftest_sparse_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     cases = sc.pattern_cases() + sc.length_cases() + sc.multi_piece_cases()
     for case in cases:
         n = case.words.size

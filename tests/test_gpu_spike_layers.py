@@ -318,9 +318,6 @@ def test_invalid_calls_are_refused_before_any_device_work(hipctx):
     d_moved = torch.empty(1, dtype=torch.int32, device="cuda")
     L = bh.lib()
     VP = C.c_void_p
-    L.bcd_hip_spike_map.argtypes = [VP, VP, C.c_int, C.c_int, C.c_float, VP, VP]
-    L.bcd_hip_spike_apply.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int]
-    L.bcd_hip_spike_filter_layers.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, C.POINTER(bh.SpikeLayer), C.c_int, VP, VP]
     p = lambda t: t.data_ptr()
     err = lambda: L.bcd_hip_last_error(hipctx.h).decode()
 

@@ -159,7 +159,6 @@ def test_refusals_of_the_frame_call_then_a_successful_call(hipctx):
     refused(lambda: hipctx.denoise_temporal(*d, nb, 1, prm, out=nb[0][0]))           # ... of a neighbour
     refused(lambda: hipctx.denoise_temporal(*d, nb, 9, prm))         # too many scales for the image
     L = bh.lib()
-    L.bcd_hip_denoise_temporal.argtypes = [C.c_void_p] * 5 + [C.POINTER(bh.Frame), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.c_void_p]
     one = (bh.Frame * 1)()
     one[0].d_colors, one[0].d_nsamples, one[0].d_histograms, one[0].d_covariances = (t.data_ptr() for t in nb[0])
     ptrs = [t.data_ptr() for t in d]

@@ -226,8 +226,6 @@ def test_refusals_of_the_frame_call_then_a_successful_call(hipctx):
     with pytest.raises(ValueError):                                  # a neighbour with a missing layer never reaches the library
         hipctx.denoise_temporal_layers(ns, hist, lay, [(fr[1][0], fr[1][1], fr[1][2][:2])], 1, prm, outs=outs)
     lib = bh.lib()
-    lib.bcd_hip_denoise_temporal_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(bh.FrameLayers), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                    C.POINTER(bh.Params), C.POINTER(bh.Layer), C.c_int]
     la = (bh.Layer * L)()
     for k in range(L):
         la[k].d_colors, la[k].d_covariances, la[k].d_out = lay[k][0].data_ptr(), lay[k][1].data_ptr(), outs[k].data_ptr()

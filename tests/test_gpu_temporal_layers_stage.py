@@ -288,8 +288,6 @@ def test_refusals_leave_the_context_usable(hipctx):
     refused(lambda: hipctx.bayes_accumulate_temporal_layers(frames, nsim, state, 1, 6, case.min_eig, out=([sums[0], frames[1][0][1][0]], cnt)))  # a sum that is an input
     refused(lambda: hipctx.bayes_accumulate_temporal_layers(frames, nsim, state, 1, 6, case.min_eig, out=(sums, nsim)))                 # the count image is |S|
     L = bh.lib()
-    L.bcd_hip_bayes_accumulate_temporal_layers.argtypes = [C.c_void_p, C.POINTER(bh.StageFrameLayers), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                           C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     cols = (C.c_void_p * 2)(frames[0][0][0][0].data_ptr(), None)
     pcs = (C.c_void_p * 2)(frames[0][0][0][1].data_ptr(), frames[0][0][1][1].data_ptr())
     one = (bh.StageFrameLayers * 1)()

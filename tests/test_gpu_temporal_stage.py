@@ -300,8 +300,6 @@ def test_estimate_refusals_leave_the_context_usable(hipctx):
     with pytest.raises(bh.BcdHipError):                              # more than four neighbours
         hipctx.bayes_accumulate_temporal(frames * 3, nsim, state, 1, 6, case.min_eig)
     L = bh.lib()
-    L.bcd_hip_bayes_accumulate_temporal.argtypes = [C.c_void_p, C.POINTER(bh.StageFrame), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                    C.c_float, C.c_void_p, C.c_void_p]
     one = (bh.StageFrame * 1)()
     one[0].d_colors, one[0].d_pixel_cov, one[0].d_mask = frames[0][0].data_ptr(), frames[0][1].data_ptr(), None
     s = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")

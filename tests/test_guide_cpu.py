@@ -40,13 +40,6 @@ def test_null_context_is_refused():
     host_layer = (bh.HostLayer * 1)()
     opt = bh.LayersHostOptions(0.0, 0, 0)
     g = bh.Guide(None, None, 1, None, 1.0)
-    L.bcd_hip_similarity_masks_guide.argtypes = [C.c_void_p, C.POINTER(bh.Guide), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.bcd_hip_window_distances_guide.argtypes = [C.c_void_p, C.POINTER(bh.Guide), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.bcd_hip_gate_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.bcd_hip_denoise_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.c_float, C.POINTER(bh.Layer), C.c_int,
-                                         C.POINTER(bh.Guide), C.c_void_p]
-    L.bcd_hip_denoise_guided_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.POINTER(bh.LayersHostOptions),
-                                              C.c_float, C.POINTER(bh.HostLayer), C.c_int, C.POINTER(bh.Guide)]
     assert L.bcd_hip_similarity_masks_guide(None, C.byref(g), 8, 8, 1, 2, None, None) == EINVAL
     assert L.bcd_hip_window_distances_guide(None, C.byref(g), 8, 8, 1, 2, 3, 3, None) == EINVAL
     assert L.bcd_hip_gate_masks(None, None, None, None, 8, 8, 2) == EINVAL

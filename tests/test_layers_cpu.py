@@ -38,15 +38,11 @@ def test_header_declares_and_library_exports_the_layered_call():
 
 def test_layered_call_without_a_context_is_an_error_not_a_crash():
     L = bh.lib()
-    L.bcd_hip_denoise_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.POINTER(bh.Layer), C.c_int]
     arr = (bh.Layer * 1)()
     assert L.bcd_hip_denoise_layers(None, None, None, 8, 8, 60, 1, None, arr, 1) == -1
     n = C.c_int32(7)
-    L.bcd_hip_layer_spectral_inverses.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
     assert L.bcd_hip_layer_spectral_inverses(None, 0, 0, C.byref(n)) == -1
     arr = (bh.StageLayer * 1)()
-    L.bcd_hip_bayes_accumulate_layers.argtypes = [C.c_void_p, C.POINTER(bh.StageLayer), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                                  C.c_void_p, C.POINTER(C.c_int32)]
     assert L.bcd_hip_bayes_accumulate_layers(None, arr, 1, None, None, None, 8, 8, 1, 6, 1e-8, None, None) == -1
     for fn, args in (("bcd_hip_layers_pixel_cov", (None, 1, None, 8, 8, None, None)), ("bcd_hip_layers_finalize", (None, None, 1, None, C.c_int64(64))),
                      ("bcd_hip_layers_downscale_avg", (None, None, 1, 8, 8)), ("bcd_hip_layers_downscale_cov", (None, None, 1, None, 8, 8)), ("bcd_hip_layers_merge", (None, None, 1, 8, 8))):

@@ -32,11 +32,6 @@ def test_null_context_is_refused():
     layer = (bh.Layer * 1)()
     host_layer = (bh.HostLayer * 1)()
     opt = bh.LayersHostOptions(0.0, 0, 0)
-    L.bcd_hip_similarity_masks_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    L.bcd_hip_window_distances_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p]
-    L.bcd_hip_denoise_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.c_float, C.POINTER(bh.Layer), C.c_int, C.c_void_p]
-    L.bcd_hip_denoise_moments_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(bh.Params), C.POINTER(bh.LayersHostOptions), C.c_float,
-                                               C.POINTER(bh.HostLayer), C.c_int]
     assert L.bcd_hip_similarity_masks_moments(None, None, None, 8, 8, 1, 6, 1.0, 1e-8, None, None) == EINVAL
     assert L.bcd_hip_window_distances_moments(None, None, None, 8, 8, 1, 6, 1e-8, 3, 3, None) == EINVAL
     assert L.bcd_hip_denoise_moments(None, None, 8, 8, 1, C.byref(prm), 1e-8, layer, 1, None) == EINVAL

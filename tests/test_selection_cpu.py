@@ -76,14 +76,13 @@ def test_the_new_entry_points_are_declared_with_the_issues_arguments():
 
 def test_without_a_device_nothing_is_created():
     import torch
-    L = bh._selection_api()
+    L = bh.lib()
     h = C.c_void_p()
     assert L.bcd_hip_selection_create(None, C.byref(h)) == -1 and not h.value        # no context, no selection
     assert L.bcd_hip_selection_create(None, None) == -1
     assert L.bcd_hip_selection_denoise(None, None, None, 1) == -1
     assert L.bcd_hip_selection_read(None, 0, None, None, None, None) == -1
     assert L.bcd_hip_selection_info(None, C.byref(bh.SelectionInfo())) == -1
-    L.bcd_hip_accum_moments.argtypes = [C.c_void_p] * 4
     assert L.bcd_hip_accum_moments(None, None, None, None) == -1
     L.bcd_hip_selection_destroy(None)                                                  # (a null handle is ignored)
     if torch.cuda.is_available():

@@ -93,14 +93,9 @@ def test_header_declares_and_library_exports_the_new_entry_points():
 
 def test_new_calls_without_a_context_are_errors_not_crashes():
     L = bh.lib()
-    L.bcd_hip_spike_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
     assert L.bcd_hip_spike_map(None, None, 8, 8, 2.0, None, None) == -1
-    L.bcd_hip_spike_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     assert L.bcd_hip_spike_apply(None, None, 8, 8, 3, None, None, 1) == -1
-    L.bcd_hip_spike_filter_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                              C.POINTER(bh.SpikeLayer), C.c_int, C.c_void_p, C.c_void_p]
     assert L.bcd_hip_spike_filter_layers(None, None, None, 8, 8, 60, 2.0, None, None, None, 1, None, None) == -1
-    L.bcd_hip_denoise_layers_host_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     opt = bh.LayersHostOptions(2.0, 0, 1)
     assert L.bcd_hip_denoise_layers_host_ex(None, None, None, 8, 8, 60, 1, None, C.byref(opt), None, 2) == -1
 

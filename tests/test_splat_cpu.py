@@ -51,7 +51,7 @@ def test_filter_table_refuses_bad_arguments():
         bh.filter_table("mitchell", 2.0)
     with pytest.raises(ValueError):
         bh.filter_table("gaussian", 1.5, param=-1.0)
-    L = bh._splat_api()
+    L = bh.lib()
     out = np.zeros(16, np.float32)
     assert L.bcd_hip_filter_table(7, 1.0, 1.0, 0.0, 4, out.ctypes.data_as(C.c_void_p)) == EINVAL
     assert L.bcd_hip_filter_table(0, 1.0, 1.0, 0.0, 4, None) == EINVAL
@@ -60,7 +60,7 @@ def test_filter_table_refuses_bad_arguments():
 
 def test_splat_entry_points_refuse_a_null_accumulator():
     """in the manner of test_device_entry_points_fail_loudly_without_gpu: no device is touched, nothing is enqueued"""
-    L = bh._splat_api()
+    L = bh.lib()
     t = np.ones(4, np.float32)
     assert L.bcd_hip_accum_set_filter(None, 1.0, 1.0, 2, t.ctypes.data_as(C.c_void_p)) == EINVAL
     assert L.bcd_hip_accum_set_filter(None, 1.0, 1.0, 2, None) == EINVAL

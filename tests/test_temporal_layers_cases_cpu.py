@@ -98,12 +98,8 @@ def test_calls_without_a_context_are_errors_not_crashes():
     import bcd_amd.hip as bh
     lib = bh.lib()
     prm = bh.default_params()
-    lib.bcd_hip_denoise_temporal_layers.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.POINTER(bh.Params), C.c_void_p, C.c_int]
-    lib.bcd_hip_denoise_temporal_layers_host.argtypes = lib.bcd_hip_denoise_temporal_layers.argtypes
     assert lib.bcd_hip_denoise_temporal_layers(None, None, None, None, 1, 8, 8, 20, 1, C.byref(prm), None, 2) == -1
     assert lib.bcd_hip_denoise_temporal_layers_host(None, None, None, None, 1, 8, 8, 20, 1, C.byref(prm), None, 2) == -1
-    lib.bcd_hip_bayes_accumulate_temporal_layers.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                             C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.bcd_hip_bayes_accumulate_temporal_layers(None, None, 2, 2, None, None, 8, 8, 1, 6, 1e-8, None, None, None) == -1
 
 

@@ -44,7 +44,6 @@ def main():
     ctx = bh.Context(0, torch.cuda.current_stream())
     g = torch.Generator(device="cuda").manual_seed(1)
     L = bh.lib()
-    L.bcd_hip_accum_plan.argtypes = bh.PLAN_ARGTYPES
     prm = bh.default_plan_params()
     res = {}
     for name, (W, H) in (("1080p", (1920, 1080)), ("4k", (3840, 2160))):
@@ -58,7 +57,7 @@ def main():
             B = spp * N
             pixels = torch.empty((max(B, 1),), dtype=torch.int32, device="cuda")
             args = (acc.h, C.byref(prm), B, 0, C.c_void_p(err.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(pixels.data_ptr()),
-                    pixels.numel(), C.c_void_p(summ.data_ptr()))
+                    pixels.numel(), C.cast(C.c_void_p(summ.data_ptr()), C.POINTER(bh.PlanSummary)))
 
             def run():
                 assert L.bcd_hip_accum_plan(*args) == 0

@@ -38,10 +38,6 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     L_ = bh.lib()
-    L_.bcd_hip_spike_map.argtypes = [VP, VP, C.c_int, C.c_int, C.c_float, VP, VP]
-    L_.bcd_hip_spike_apply.argtypes = [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, C.c_int]
-    L_.bcd_hip_spike_filter_layers.argtypes = [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP, VP, C.POINTER(bh.SpikeLayer), C.c_int, VP, VP]
-    L_.bcd_hip_spike_filter.argtypes = [VP] + [VP] * 4 + [C.c_int] * 3 + [C.c_float] + [VP] * 4
     ctx = bh.Context(0)
     counts = [int(x) for x in a.layers.split(",")]
     res = dict(library=bh.LIB_PATH, reps=a.reps, factor=a.factor, frames={})
