@@ -98,6 +98,12 @@ class WarpedFrame(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p)]
 
 
+class GuideImages(C.Structure):
+    """the feature and variance images of one neighbour frame of bcd_hip_denoise_temporal_guided[_host] ("Features")"""
+    _c_name_ = "bcd_hip_guide_images"
+    _fields_ = [("features", C.c_void_p), ("variances", C.c_void_p)]
+
+
 class BandJob(C.Structure):
     _c_name_ = "bcd_hip_band_job"
     _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p),
@@ -240,6 +246,12 @@ PROTOTYPES = {
     "bcd_hip_warp_layers": (I, [P, S(FrameLayer), I, P, I, I, P, P]),
     "bcd_hip_valid_downscale": (I, [P, P, I, I, P]),
     "bcd_hip_gate_masks_valid": (I, [P, P, P, P, I, I, I, I]),
+    # ---- features: the cross-frame selection gated by auxiliary feature buffers ("Features")
+    "bcd_hip_denoise_temporal_guided": (I, [P, P, P, S(FrameLayers), I, P, I, I, I, I, S(Params), S(Layer), I, S(Guide), S(GuideImages)]),
+    "bcd_hip_denoise_temporal_guided_host": (I, [P, P, P, S(FrameLayers), I, P, I, I, I, I, S(Params), S(Layer), I, S(Guide), S(GuideImages)]),
+    "bcd_hip_similarity_masks_guide_cross": (I, [P, S(Guide), S(GuideImages), I, I, I, I, P, P]),
+    "bcd_hip_window_distances_guide_cross": (I, [P, S(Guide), S(GuideImages), I, I, I, I, I, I, P]),
+    "bcd_hip_warp_features": (I, [P, S(GuideImages), I, P, I, I, P, P, P]),
     # (row bands, for multi-GPU tiling)
     "bcd_hip_denoise_band": (I, [P, P, P, P, P, I, I, I, I, I, S(Params), U32, P, P]),
     "bcd_hip_denoise_bands": (I, [P, S(BandJob), I, S(Params)]),

@@ -266,10 +266,16 @@ def _motion_stack(motions, F, H, W):
     return fields, flags
 
 
-def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, after_clear=False, motions=None):
+def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, after_clear=False, motions=None,
+                     features=None, neighbour_features=None, **guide):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames of the sequence (addNeighbourFrame): neighbours is a list of (col, ns, hist, cov)
     arrays of the frame's size, at most four.  after_clear: clearNeighbourFrames() and a second denoise() follow, whose result replaces the first.
-    motions: None, or per neighbour an (H, W, 2) motion field or None (setNeighbourMotion).  Returns (ok, denoised frame)"""
+    motions: None, or per neighbour an (H, W, 2) motion field or None (setNeighbourMotion).  features / neighbour_features (and variances, neighbour_variances,
+    floors, threshold): the feature buffers of denoise_temporal_layers, which then serves the call with one layer.  Returns (ok, denoised frame)"""
+    if features is not None or neighbour_features is not None:
+        ok, outs = denoise_temporal_layers(ns, hist, [(col, cov)], [(f[1], f[2], [(f[0], f[3])]) for f in neighbours], nscales, tau, b, min_eig, random_order, m, seed,
+                                           after_clear=after_clear, motions=motions, features=features, neighbour_features=neighbour_features, **guide)
+        return ok, outs[0]
     H, W, D = hist.shape
     F = len(neighbours)
     stack = lambda k, d: np.ascontiguousarray(np.stack([np.asarray(f[k], np.float32).reshape(H, W, d) for f in neighbours]) if F else np.zeros((1, H, W, d)), np.float32)
@@ -287,12 +293,15 @@ def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, mi
 
 
 def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, drop_layers=0, after_clear=False,
-                            motions=None):
+                            motions=None, features=None, neighbour_features=None, variances=None, neighbour_variances=None, floors=(), threshold=1.0,
+                            neighbours_with_features=None, moment_selection=False, devices=None):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with colour layers beside neighbouring frames (addLayer, addNeighbourFrame, addNeighbourFrameLayer): layers is a
     list of (colours, covariances), [0] going through DenoiserInputs; neighbours a list of (ns, hist, [(colours, covariances)]) with the same layers.
     drop_layers: the last neighbour is given that many layers fewer (denoise() must refuse).  after_clear: clearNeighbourFrames() and a second denoise()
     follow, whose results replace the first.  motions: None, or per neighbour an (H, W, 2) motion field or None (setNeighbourMotion).
-    Returns (ok, [output per layer])"""
+    features (H, W, F) with floors and threshold (and variances): setGuideFeatures; neighbour_features, one (H, W, F') per neighbour (and neighbour_variances):
+    setNeighbourGuideFeatures -- the call is then bcd_hip_denoise_temporal_guided_host.  neighbours_with_features: only that many neighbours get theirs;
+    moment_selection, devices: setMomentSelection(true), setDevices (denoise() must refuse these).  Returns (ok, [output per layer])"""
     H, W, D = hist.shape
     L, F = len(layers), len(neighbours)
     f32 = lambda a: np.ascontiguousarray(a, np.float32)
@@ -302,6 +311,23 @@ def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=
     nb_ns = f32(np.stack([np.asarray(n, np.float32).reshape(H, W, 1) for n, _, _ in neighbours])) if F else np.zeros((1, H, W, 1), np.float32)
     nb_hists = f32(np.stack([h for _, h, _ in neighbours])) if F else np.zeros((1, H, W, D), np.float32)
     outs = np.zeros((L, H, W, 3), np.float32)
+    if features is not None or neighbour_features is not None:
+        if features is None:
+            raise ValueError("neighbour_features go with features: the gate covers the frame and every neighbour, or nothing")
+        p = lambda a: None if a is None else _fp(a)
+        feat, var = f32(features), None if variances is None else f32(variances)
+        nfeat = f32(np.stack([f32(x) for x in neighbour_features])) if neighbour_features else None
+        nvar = f32(np.stack([f32(x) for x in neighbour_variances])) if neighbour_variances else None
+        fl = f32(np.asarray(floors, np.float32).reshape(-1))
+        fields, flags = _motion_stack(motions, F, H, W) if motions is not None else (None, None)
+        devs = (C.c_int * len(devices))(*devices) if devices else None
+        given = (len(neighbour_features) if neighbour_features else 0) if neighbours_with_features is None else int(neighbours_with_features)
+        rc = lib().bcdcore_denoise_temporal_guided(_fp(cols), _fp(covs), _fp(f32(ns)), _fp(f32(hist)), _fp(nb_cols), _fp(nb_covs), _fp(nb_ns), _fp(nb_hists), F, L, p(fields),
+                                                   flags, W, H, D, int(nscales), C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed),
+                                                   1 if after_clear else 0, _fp(feat), p(var), feat.shape[2], _fp(fl) if fl.size else None, int(fl.size), C.c_float(threshold),
+                                                   p(nfeat), p(nvar), nfeat.shape[3] if nfeat is not None else feat.shape[2], given, 1 if moment_selection else 0, devs,
+                                                   len(devices) if devices else 0, _fp(outs))
+        return rc != 0, [outs[k] for k in range(L)]
     if motions is not None:
         fields, flags = _motion_stack(motions, F, H, W)
         rc = lib().bcdcore_denoise_temporal_layers_motion(_fp(cols), _fp(covs), _fp(f32(ns)), _fp(f32(hist)), _fp(nb_cols), _fp(nb_covs), _fp(nb_ns), _fp(nb_hists), F, L,

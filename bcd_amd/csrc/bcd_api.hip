@@ -602,6 +602,14 @@ void bayes_counts(const Work &wk, int64_t *n_strong, int64_t *n_weak, int64_t *s
 // its buffers too -- every layer of the call is a follower (up to BCD_MAX_LAYERS of them), and the redo counter starts at zero: spectral[0] = 0.
 } // namespace
 
+// what the temporal calls (bcd_temporal.hip) share with the guided scale: declared in bcd_ctx.h
+int guide_gate_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const float *d_variances, int W, int H, int w, int b, uint32_t *d_mask, int32_t *d_count)
+{
+    return guide_gate(ctx, wk, d_features, d_variances, W, H, w, b, d_mask, d_count);
+}
+
+int distance_timing_events(bcd_hip_ctx *ctx, Work &wk, hipEvent_t *e0, hipEvent_t *e1) { return timing_events(ctx, wk, e0, e1); }
+
 int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state,
                   const float *const *pixcov, float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral,
                   const KeptLists *kept)

@@ -217,6 +217,16 @@ struct bcd_hip_ctx {
         DevBuf valid[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES];      // [1..]: its validity bytes at every level
         DevBuf pvalid;                                         // patch validity of the neighbour and scale in progress
         DevBuf motion_host[BCD_MAX_NEIGHBOURS + 1];            // host-buffer entry points: device copies of the motion fields
+        // bcd_hip_denoise_temporal_guided ("Features"): [..][0] features, [..][1] their variances; frame 0's levels 1.. are ctx->guide_pyr
+        DevBuf guide_pyr[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES][2]; // [1..]: levels 1.. of every neighbour's feature images
+        DevBuf guide_warp[BCD_MAX_NEIGHBOURS + 1][2];            // [1..]: the warped feature images of a neighbour that has a motion field
+        DevBuf guide_host[BCD_MAX_NEIGHBOURS + 1][2];            // host-buffer entry point: device copies of every frame's feature images
+        // the call in progress: per frame and pyramid level the feature and variance images (v null: none); F, floors and threshold are ctx->guide's.
+        // temporal_select gates the in-frame and the cross masks of a scale when `on`
+        struct {
+            bool on = false;
+            const float *f[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES] = {}, *v[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES] = {};
+        } guide;
     } temporal;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
@@ -312,6 +322,11 @@ int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int 
 int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius);
 int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales);
 inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
+// the gate of a guided selection with ctx->guide's channels, floors and threshold, behind a selection pass on wk.stream: the feature masks of (d_features,
+// d_variances) into wk.gate_mask / wk.gate_nsim, then d_mask &= them and d_count = the bits that remain (the code path of a guided scale)
+int guide_gate_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const float *d_variances, int W, int H, int w, int b, uint32_t *d_mask, int32_t *d_count);
+// an event pair for the distance kernel of a pass outside bcd_api.hip (bcd_hip_kernel_time); both null once the pool is used up
+int distance_timing_events(bcd_hip_ctx *ctx, Work &wk, hipEvent_t *e0, hipEvent_t *e1);
 
 // do the byte ranges [a, a + na) and [b, b + nb) share a byte?  The one overlap predicate of the argument checks
 inline bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb)
@@ -325,11 +340,20 @@ void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
 // does [out, out + bytes) overlap one of a frame's images (a null image: not looked at)?
 bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const void *ns, const void *hist, const void *cov, size_t npix, int D);
 // what the selection of a scale reads of one frame: sample counts and histograms at this level; valid: null, or the validity bytes of a warped neighbour
-struct TemporalSelFrame { const float *ns, *hist; const uint8_t *valid; };
+// feat, var: null, or -- in a bcd_hip_denoise_temporal_guided call -- the frame's feature and variance images at this level (var null: no variances)
+struct TemporalSelFrame { const float *ns, *hist; const uint8_t *valid; const float *feat = nullptr, *var = nullptr; };
+// with a guided temporal call in progress (temporal_guide_begin), the feature images of frame f at level `scale`; else nothing
+inline void temporal_guide_level(const bcd_hip_ctx *ctx, int f, int scale, TemporalSelFrame *sel)
+{
+    const auto &g = ctx->temporal.guide;
+    if (g.on) { sel->feat = g.f[f][scale]; sel->var = g.v[f][scale]; }
+}
 struct TemporalPath { int32_t path = 0, borderline = 0; }; // of the in-frame pass (bcd_hip_similarity_last_path)
 // The selection stage of one scale, frames[0] the frame itself, from stage event 0 to stage event 2: the stats header of ctx->stats[scale], the in-frame masks
 // (wk.mask, wk.nsim) by bcd_hip_similarity_masks, per neighbour f the cross planes, k_masks_cross into ctx->temporal.mask[f], the gate of a warped neighbour and
 // the count sum, then the marking (wk.state).  per_pixel_cov() enqueues the caller's per-pixel covariances between stage events 0 and 1.
+// Guide mode (frames[0].feat given, "Features"): the in-frame masks pass guide_gate_masks behind bcd_hip_similarity_masks, and every neighbour's cross masks
+// are ANDed with its cross feature mask (k_pairdist_guide_cross into the plane buffers, k_masks_cross with tau_g into wk.gate_mask) ahead of the count sum.
 int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
                     const std::function<int()> &per_pixel_cov, TemporalPath *path);
 // the masks temporal_select left for frame f
@@ -356,6 +380,12 @@ inline bool any_field(const float *const *motion, int n)
 int temporal_upload_motion(bcd_hip_ctx *ctx, const float *const *h_motion, int nb_neighbours, int W, int H, const float **dev); // (whole uploads; dev[f] NULL for a NULL field)
 // the refusals the motion calls add: the list itself, and a field that overlaps one of `outs` (each W*H*3 floats)
 int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neighbours, int W, int H, float *const *outs, int nb_outs);
+// "Features": the set-up of a guided temporal call on the main stream, every pointer a device pointer: ctx->guide's channels, floors and threshold and the
+// frame's feature pyramid (guide_begin; ctx->guide.on stays false), per neighbour the warp of its feature images when it has a motion field (k_warp_features,
+// which writes the validity bytes temporal_warp_neighbour writes again), its pyramid by guide_begin's rule, and ctx->temporal.guide.  temporal_guide_end
+// switches the mode off
+int temporal_guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const bcd_hip_guide_images *nb, int nb_neighbours, const float *const *motion, int W, int H, int nb_scales);
+inline void temporal_guide_end(bcd_hip_ctx *ctx) { ctx->temporal.guide.on = false; }
 
 // ---- defined in bcd_selection.hip
 // one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is

@@ -33,6 +33,7 @@ hipError_t bcd_launch_window_distances_cross(const float *T, const uint8_t *Cn, 
 hipError_t bcd_launch_warp_frame(const float *col, const float *ns, const float *hist, const float *cov, const float *mv, int W, int H, int D, float *ocol, float *ons,
                                  float *ohist, float *ocov, uint8_t *valid, hipStream_t st);
 hipError_t bcd_launch_warp_layers(const BcdWarpLayerTable &t, int layers, const float *mv, int W, int H, uint8_t *valid, hipStream_t st);
+hipError_t bcd_launch_warp_features(const float *feat, const float *var, int F, const float *mv, int W, int H, float *ofeat, float *ovar, uint8_t *valid, hipStream_t st);
 hipError_t bcd_launch_valid_down(const uint8_t *valid, int W, int H, uint8_t *out, hipStream_t st);
 hipError_t bcd_launch_valid_patch(const uint8_t *valid, int W, int H, int w, uint8_t *pvalid, hipStream_t st);
 hipError_t bcd_launch_masks_gate_valid(uint32_t *mask, int32_t *count, const uint8_t *pvalid, int W, int H, int w, int b, hipStream_t st);
@@ -56,6 +57,11 @@ hipError_t bcd_launch_pairdist_guide(const float *features, const float *varianc
                                      hipStream_t st);
 hipError_t bcd_launch_gate_masks(uint32_t *mask, const uint32_t *gate, int32_t *nsim, int W, int H, int b, hipStream_t st);
 hipError_t bcd_launch_scale_inplace(float *x, float a, int64_t n, hipStream_t st);
+
+// ---- k_similarity_guide_cross.hip
+int bcd_pairdist_guide_cross_band(int F, int has_var, int b); // displacement lines per staging; 0: a geometry the kernel does not serve
+hipError_t bcd_launch_pairdist_guide_cross(const float *featA, const float *varA, const float *featB, const float *varB, int F, const float *floors, int W, int H,
+                                           int b, float *T, uint8_t *Cn, hipStream_t st);
 
 // ---- k_similarity_fast.hip
 int bcd_pairdist_rw_supported(int D);

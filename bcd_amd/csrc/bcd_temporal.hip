@@ -4,6 +4,9 @@
 // neighbour's are written.  The motion calls (section 16, "Motion": bcd_hip_denoise_temporal_motion[_host], the stages bcd_hip_warp_frame,
 // bcd_hip_valid_downscale, bcd_hip_gate_masks_valid) are here too: temporal_run warps a neighbour that has a motion field (k_warp.hip) before its pyramid is
 // built and gates its cross masks at every scale; the plain call is temporal_run without fields.
+// The feature gate of the cross-frame selection (section 16, "Features") is here as well: temporal_select's guide mode, the set-up of a guided temporal call
+// (temporal_guide_begin) and the stages bcd_hip_similarity_masks_guide_cross, bcd_hip_window_distances_guide_cross, bcd_hip_warp_features; the kernels are in
+// k_similarity_guide_cross.hip and k_warp.hip.
 // What the layered calls (bcd_temporal_layers.hip) share with the frame calls is defined here and declared in bcd_ctx.h: the selection stage of a scale
 // (temporal_select) and its stats tail (temporal_stats_tail), the lists and the chain of full estimates of the estimate stage (temporal_lists,
 // temporal_full_chain), the motion set-up of a neighbour (temporal_warp_neighbour).
@@ -26,6 +29,38 @@ int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const
     RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
     wk.planes.ready = false; // (the workspace's planes are overwritten)
     HIPCHK(ctx, bcd_launch_pairdist_cross(d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    return BCD_HIP_OK;
+}
+
+// "Features": the T / C planes of every displacement between the feature images of the frame and of one neighbour, in the same plane buffers -- the histogram
+// planes of that neighbour are consumed by then.  The kernel is timed like the other distance kernels (bcd_hip_kernel_time)
+int temporal_guide_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_feat, const float *d_var, const float *d_feat_nb, const float *d_var_nb, int F,
+                                const float *floors, int W, int H, int b)
+{
+    const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
+    wk.planes.ready = false; // (the workspace's planes are overwritten)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RCCHK(distance_timing_events(ctx, wk, &e0, &e1));
+    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    HIPCHK(ctx, bcd_launch_pairdist_guide_cross(d_feat, d_var, d_feat_nb, d_var_nb, F, floors, W, H, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
+    return BCD_HIP_OK;
+}
+
+// "Features": the gate of one neighbour's cross masks, behind k_masks_cross (and the validity gate) on wk.stream: the cross feature planes, k_masks_cross on
+// them with tau_g into the workspace's gate buffers, then mask &= G_j and |S_j| = the bits that remain.  Channels, floors and threshold are ctx->guide's
+int temporal_guide_gate(bcd_hip_ctx *ctx, Work &wk, const TemporalSelFrame &frame, const TemporalSelFrame &nb, int W, int H, int w, int b, uint32_t *d_mask_nb,
+                        int32_t *d_count_nb)
+{
+    const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
+    RCCHK(ensure(ctx, wk.gate_mask, npix * words * sizeof(uint32_t)));
+    RCCHK(ensure(ctx, wk.gate_nsim, npix * sizeof(int32_t)));
+    RCCHK(temporal_guide_cross_planes(ctx, wk, frame.feat, frame.var, nb.feat, nb.var, ctx->guide.F, ctx->guide.floors, W, H, b));
+    HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, ctx->guide.tau, (uint32_t *)wk.gate_mask.p, (int32_t *)wk.gate_nsim.p,
+                                       wk.stream));
+    HIPCHK(ctx, bcd_launch_gate_masks(d_mask_nb, (const uint32_t *)wk.gate_mask.p, d_count_nb, W, H, b, wk.stream));
     return BCD_HIP_OK;
 }
 
@@ -233,6 +268,9 @@ void temporal_free(bcd_hip_ctx *ctx)
     for (auto &frame : t.valid) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
     for (DevBuf &b : t.motion_host) if (b.p) (void)hipFree(b.p);
     if (t.pvalid.p) (void)hipFree(t.pvalid.p);
+    for (auto &frame : t.guide_pyr) for (auto &level : frame) for (DevBuf &b : level) if (b.p) (void)hipFree(b.p);
+    for (auto &frame : t.guide_warp) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    for (auto &frame : t.guide_host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
 }
 
 int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
@@ -259,6 +297,8 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
     RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
     int32_t capacity = 0;
     RCCHK(bcd_hip_similarity_last_path(ctx, &path->path, &path->borderline, &capacity));
+    const bool guided = frames[0].feat != nullptr; // ("Features": S_0 is gated as a guided scale gates it, every S_j by its cross feature mask)
+    if (guided) RCCHK(guide_gate_masks(ctx, wk, frames[0].feat, frames[0].var, W, H, w, b, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
     RCCHK(per_pixel_cov());
     for (int f = 1; f < nf; ++f) {
         uint32_t *mask = (uint32_t *)tp.mask[f].p;
@@ -266,6 +306,7 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
         RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
         HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, mask, count, wk.stream));
         if (frames[f].valid) RCCHK(temporal_gate(ctx, wk, frames[f].valid, W, H, w, b, mask, count)); // (a warped neighbour)
+        if (guided) RCCHK(temporal_guide_gate(ctx, wk, frames[0], frames[f], W, H, w, b, mask, count));
         HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, count, (int64_t)npix, wk.stream));
     }
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));
@@ -308,6 +349,7 @@ int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, in
     for (int f = 0; f < nf; ++f) {
         RCCHK(ensure(ctx, tp.pixcov[f], npix * 6 * sizeof(float)));
         sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
+        temporal_guide_level(ctx, f, scale, &sel[f]);
     }
     TemporalPath path;
     RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int {
@@ -568,6 +610,133 @@ int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_coun
     DEVICE_GUARD(ctx);
     RCCHK(temporal_gate(ctx, ctx->main, d_valid, W, H, w, b, d_mask, d_count));
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
+}
+
+} // extern "C"
+
+// =====================================================================================================================
+// "Features" (DESIGN.md section 16): the feature gate of the cross-frame selection.  temporal_select does the gating (above); here are the set-up of a guided
+// temporal call and the stage calls.  The frame calls bcd_hip_denoise_temporal_guided[_host] are in bcd_temporal_layers.hip, beside the layered calls they run.
+// =====================================================================================================================
+int temporal_guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const bcd_hip_guide_images *nb, int nb_neighbours, const float *const *motion, int W, int H, int nb_scales)
+{
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    const int F = g->nb_channels;
+    const bool var = g->variances != nullptr;
+    const size_t npix = (size_t)W * H;
+    tp.guide.on = false;
+    RCCHK(guide_begin(ctx, g, g->features, g->variances, W, H, nb_scales));
+    ctx->guide.on = false; // (no scale of bcd_hip_denoise runs in this call: temporal_select reads the constants and the frame's pyramid)
+    for (int s = 0; s < MAX_SCALES; ++s)
+        for (int f = 0; f <= BCD_MAX_NEIGHBOURS; ++f) { tp.guide.f[f][s] = f == 0 ? ctx->guide.f[s] : nullptr; tp.guide.v[f][s] = f == 0 ? ctx->guide.v[s] : nullptr; }
+    for (int f = 1; f <= nb_neighbours; ++f) {
+        const float *feat = nb[f - 1].features, *vv = var ? nb[f - 1].variances : nullptr;
+        if (motion && motion[f - 1]) { // gathered by the source pixels and the validity of the neighbour's other images, at full resolution
+            DevBuf(&gw)[2] = tp.guide_warp[f];
+            RCCHK(ensure(ctx, gw[0], npix * F * sizeof(float)));
+            if (var) RCCHK(ensure(ctx, gw[1], npix * F * sizeof(float)));
+            RCCHK(ensure(ctx, tp.valid[f][0], npix));
+            HIPCHK(ctx, bcd_launch_warp_features(feat, vv, F, motion[f - 1], W, H, (float *)gw[0].p, var ? (float *)gw[1].p : nullptr, (uint8_t *)tp.valid[f][0].p, st));
+            feat = (const float *)gw[0].p;
+            vv = var ? (const float *)gw[1].p : nullptr;
+        }
+        tp.guide.f[f][0] = feat; tp.guide.v[f][0] = vv;
+        for (int s = 1, ws = W, hs = H; s < nb_scales && s < MAX_SCALES; ++s, ws /= 2, hs /= 2) { // guide_begin's rule
+            const size_t np = (size_t)(ws / 2) * (hs / 2);
+            DevBuf(&l)[2] = tp.guide_pyr[f][s];
+            RCCHK(ensure(ctx, l[0], np * F * sizeof(float)));
+            HIPCHK(ctx, bcd_launch_downscale(1, tp.guide.f[f][s - 1], ws, hs, F, (float *)l[0].p, st));
+            tp.guide.f[f][s] = (const float *)l[0].p;
+            if (!var) continue;
+            RCCHK(ensure(ctx, l[1], np * F * sizeof(float)));
+            HIPCHK(ctx, bcd_launch_downscale(1, tp.guide.v[f][s - 1], ws, hs, F, (float *)l[1].p, st));
+            HIPCHK(ctx, bcd_launch_scale_inplace((float *)l[1].p, 0.25f, (int64_t)np * F, st));
+            tp.guide.v[f][s] = (const float *)l[1].p;
+        }
+    }
+    tp.guide.on = true;
+    return BCD_HIP_OK;
+}
+
+namespace {
+
+// the refusals the two stage calls of the cross feature gate share: the geometry of bcd_hip_similarity_masks_cross, the guide's own rules, the neighbour's images
+int check_guide_cross_stage(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const bcd_hip_guide_images *nb, int W, int H, int w, int b)
+{
+    RCCHK(check_cross_stage(ctx, W, H, BCD_HIP_GUIDE_MAX_CHANNELS, w, b)); // (indices of W*H*F floats stay below 2^31 for every F)
+    RCCHK(check_guide(ctx, g, -1));                                        // (-1: the in-frame kernel is not launched)
+    if (!nb || !nb->features) return bad(ctx, "null feature image of the neighbour frame");
+    if ((g->variances == nullptr) != (nb->variances == nullptr)) return bad(ctx, "feature variances must be given for both frames or for neither");
+    if (bcd_pairdist_guide_cross_band(g->nb_channels, g->variances != nullptr, b) < 1) {
+        set_err(ctx, "the cross feature distance kernel cannot be launched for this number of channels and search radius (LDS)");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bcd_hip_similarity_masks_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour, int W, int H, int w, int b,
+                                         uint32_t *d_mask, int32_t *d_count)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_mask || !d_count) return bad(ctx, "bad argument");
+    RCCHK(check_guide_cross_stage(ctx, guide, neighbour, W, H, w, b));
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    RCCHK(temporal_guide_cross_planes(ctx, wk, guide->features, guide->variances, neighbour->features, neighbour->variances, guide->nb_channels, guide->floors, W, H, b));
+    HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, guide->threshold, d_mask, d_count, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_window_distances_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour, int W, int H, int w, int b, int line,
+                                         int col, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!h_out) return bad(ctx, "bad argument");
+    RCCHK(check_guide_cross_stage(ctx, guide, neighbour, W, H, w, b));
+    if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    const int n = (2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
+    RCCHK(temporal_guide_cross_planes(ctx, wk, guide->features, guide->variances, neighbour->features, neighbour->variances, guide->nb_channels, guide->floors, W, H, b));
+    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_warp_features(bcd_hip_ctx *ctx, const bcd_hip_guide_images *in, int nb_channels, const float *d_motion, int W, int H, float *d_features_out,
+                          float *d_variances_out, uint8_t *d_valid)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!in || !in->features || !d_features_out || !d_valid) return bad(ctx, "null argument");
+    if (nb_channels < 1 || nb_channels > BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "the number of feature channels must be between 1 and 8 (BCD_HIP_GUIDE_MAX_CHANNELS)");
+    if ((in->variances == nullptr) != (d_variances_out == nullptr)) return bad(ctx, "a variance destination must be given exactly when there is a variance image");
+    bcd_hip_params p; bcd_hip_default_params(&p); p.patch_radius = 0; p.search_radius = 0;
+    RCCHK(check_params(ctx, W, H, BCD_HIP_GUIDE_MAX_CHANNELS, &p));
+    {
+        const size_t npix = (size_t)W * H, nf = npix * nb_channels * sizeof(float);
+        const void *src[3] = { in->features, in->variances, d_motion };
+        const size_t nsrc[3] = { nf, nf, npix * 2 * sizeof(float) };
+        const void *dst[3] = { d_features_out, d_valid, d_variances_out };
+        const size_t ndst[3] = { nf, npix, nf };
+        for (int i = 0; i < 3; ++i) {
+            if (!dst[i]) continue;
+            for (int j = 0; j < 3; ++j) if (src[j] && bytes_overlap(dst[i], ndst[i], src[j], nsrc[j])) return bad(ctx, "a warp destination overlaps an input image or the motion field");
+            for (int j = 0; j < i; ++j) if (bytes_overlap(dst[i], ndst[i], dst[j], ndst[j])) return bad(ctx, "two warp destinations overlap");
+        }
+    }
+    DEVICE_GUARD(ctx);
+    hipStream_t st = ctx->main.stream;
+    HIPCHK(ctx, bcd_launch_warp_features(in->features, in->variances, nb_channels, d_motion, W, H, d_features_out, d_variances_out, d_valid, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return BCD_HIP_OK;
 }
 

@@ -8,6 +8,8 @@
 // Every buffer of the call lives in ctx->temporal (grow-only): the workspace's lay_* slices, which bcd_hip_denoise_layers owns, are not touched.
 // bcd_hip_denoise_temporal_layers_motion[_host] and bcd_hip_warp_layers (section 16, "Motion") are layers_run with motion fields: a neighbour with a field is
 // warped (temporal_warp_neighbour, with its further layers) before its pyramid is built, its cross masks pass the gate at every scale.
+// bcd_hip_denoise_temporal_guided[_host] (section 16, "Features") are layers_run / layers_host_run with the guide mode of temporal_select switched on by
+// temporal_guide_begin (bcd_temporal.hip): the feature pyramids of every frame, the warped features of a neighbour with a field.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -103,6 +105,7 @@ int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, in
     for (int f = 0; f < nf; ++f) {
         RCCHK(ensure(ctx, tp.lay_pixcov[f], (size_t)L * npix * 6 * sizeof(float)));
         sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
+        temporal_guide_level(ctx, f, scale, &sel[f]);
     }
     TemporalPath path;
     RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int { // per frame the per-pixel covariances of its layers: one launch; it also clears the layers' sums
@@ -408,6 +411,102 @@ int bcd_hip_denoise_temporal_layers_motion_host(bcd_hip_ctx *ctx, const float *h
     layer_outs(layers, nb_layers, outs);
     RCCHK(check_motion_list(ctx, h_motion, nb_neighbours, W, H, outs, nb_layers));
     return layers_host_run(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, any_field(h_motion, nb_neighbours) ? h_motion : nullptr);
+}
+
+// ---- "Features": the layered motion call with the selection gated by auxiliary feature buffers ----------------------------------
+// the refusals of the two guided frame calls with at least one neighbour, before any device work (the pointers are compared as addresses: device or host)
+static int check_guided_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_hip_frame_layers *neighbours, int n, const float *const *motion, int W, int H,
+                             int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int L, const bcd_hip_guide *guide,
+                             const bcd_hip_guide_images *ng)
+{
+    RCCHK(check_call(ctx, ns, hist, neighbours, n, W, H, D, nb_scales, prm, layers, L));
+    float *outs[ML];
+    layer_outs(layers, L, outs);
+    if (motion) RCCHK(check_motion_list(ctx, motion, n, W, H, outs, L)); // (a NULL list: nothing is warped)
+    if ((int64_t)W * H >= (1ll << 31) / BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "image too large for 32-bit DeepImage indices");
+    RCCHK(check_guide(ctx, guide, prm->search_radius));
+    if (!ng) return bad(ctx, "null list of the neighbour frames' feature images");
+    const bool var = guide->variances != nullptr;
+    for (int f = 0; f < n; ++f) {
+        if (!ng[f].features) return bad(ctx, "null feature image of a neighbour frame");
+        if ((ng[f].variances != nullptr) != var) return bad(ctx, "feature variances must be given for every frame or for none");
+    }
+    if (bcd_pairdist_guide_cross_band(guide->nb_channels, var, prm->search_radius) < 1) {
+        set_err(ctx, "the cross feature distance kernel cannot be launched for this number of channels and search radius (LDS)");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    const size_t npix = (size_t)W * H, no = npix * 3 * sizeof(float), nfeat = npix * guide->nb_channels * sizeof(float);
+    for (int k = 0; k < L; ++k)
+        for (int f = 0; f <= n; ++f) {
+            const float *feat = f ? ng[f - 1].features : guide->features, *vv = f ? ng[f - 1].variances : guide->variances;
+            if (bytes_overlap(outs[k], no, feat, nfeat) || (vv && bytes_overlap(outs[k], no, vv, nfeat))) return bad(ctx, "a layer's output overlaps a feature or variance image");
+        }
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_denoise_temporal_guided(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                    const float *const *d_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers,
+                                    const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_hist) return bad(ctx, "the guided temporal call needs histograms: there is no cross-frame selection from means and covariances");
+    if (nb_neighbours == 0) return bcd_hip_denoise_guided(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, 0.f, layers, nb_layers, guide, nullptr);
+    RCCHK(check_guided_call(ctx, d_ns, d_hist, neighbours, nb_neighbours, d_motion, W, H, D, nb_scales, prm, layers, nb_layers, guide, neighbour_guides));
+    int rc;
+    {
+        DEVICE_GUARD(ctx);
+        rc = temporal_guide_begin(ctx, guide, neighbour_guides, nb_neighbours, d_motion, W, H, nb_scales);
+    }
+    if (rc == BCD_HIP_OK)
+        rc = layers_run(ctx, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, any_field(d_motion, nb_neighbours) ? d_motion : nullptr);
+    temporal_guide_end(ctx);
+    return rc;
+}
+
+// every pointer a host pointer: whole uploads of the feature images (and of the motion fields, which warp them) into ctx->temporal.guide_host, the set-up on
+// the device copies, then the layered host call -- its own uploads, the resident call, one download per layer -- with the guide mode on
+int bcd_hip_denoise_temporal_guided_host(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                         const float *const *h_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers,
+                                         int nb_layers, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!h_hist) return bad(ctx, "the guided temporal call needs histograms: there is no cross-frame selection from means and covariances");
+    if (nb_neighbours == 0) {
+        if (!layers) return bad(ctx, "null layer list");
+        if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+        bcd_hip_host_layer hl[BCD_HIP_MAX_LAYERS];
+        for (int k = 0; k < nb_layers; ++k) hl[k] = { layers[k].d_colors, layers[k].d_covariances, layers[k].d_out };
+        return bcd_hip_denoise_guided_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, nullptr, 0.f, hl, nb_layers, guide);
+    }
+    RCCHK(check_guided_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, h_motion, W, H, D, nb_scales, prm, layers, nb_layers, guide, neighbour_guides));
+    const float *const *motion = any_field(h_motion, nb_neighbours) ? h_motion : nullptr;
+    int rc;
+    {
+        DEVICE_GUARD(ctx);
+        auto &tp = ctx->temporal;
+        hipStream_t st = ctx->main.stream;
+        const size_t bytes = (size_t)W * H * guide->nb_channels * sizeof(float);
+        const bool var = guide->variances != nullptr;
+        bcd_hip_guide dg = *guide;
+        bcd_hip_guide_images dn[BCD_HIP_MAX_NEIGHBOURS];
+        for (int f = 0; f <= nb_neighbours; ++f) {
+            const float *src[2] = { f ? neighbour_guides[f - 1].features : guide->features, f ? neighbour_guides[f - 1].variances : guide->variances };
+            for (int k = 0; k < (var ? 2 : 1); ++k) {
+                RCCHK(ensure(ctx, tp.guide_host[f][k], bytes));
+                HIPCHK(ctx, hipMemcpyAsync(tp.guide_host[f][k].p, src[k], bytes, hipMemcpyHostToDevice, st));
+            }
+            const float *df = (const float *)tp.guide_host[f][0].p, *dv = var ? (const float *)tp.guide_host[f][1].p : nullptr;
+            if (f == 0) { dg.features = df; dg.variances = dv; }
+            else dn[f - 1] = { df, dv };
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st)); // (the sources are pageable host memory of the caller)
+        const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
+        if (motion) RCCHK(temporal_upload_motion(ctx, motion, nb_neighbours, W, H, dmv));
+        rc = temporal_guide_begin(ctx, &dg, dn, nb_neighbours, motion ? dmv : nullptr, W, H, nb_scales);
+    }
+    if (rc == BCD_HIP_OK) rc = layers_host_run(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, motion);
+    temporal_guide_end(ctx);
+    return rc;
 }
 
 int bcd_hip_warp_layers(bcd_hip_ctx *ctx, const bcd_hip_frame_layer *layers, int nb_layers, const float *d_motion, int W, int H, const bcd_hip_warped_layer *out,

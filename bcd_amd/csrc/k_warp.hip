@@ -6,6 +6,7 @@
 // survives), an invalid one is +0.0f in every image.  A NULL field is zero motion.
 //   k_warp_frame<D>      colours, sample counts, histograms, covariances of one neighbour and the validity byte
 //   k_warp_layers        the colours and covariances of L layers of one neighbour and the validity byte
+//   k_warp_features<F>   the feature image of a neighbour's guide (F floats per pixel) and, when it has one, the variance image, and the validity byte
 //   k_valid_down         validity of the next pyramid level: every child the reducers read (k_pointwise.hip: 2l, 2l + 1 x 2c, 2c + 1) is valid
 //   k_valid_patch        pvalid(q) = AND of valid(q + o) over the patch, 0 where q is not a main pixel
 //   k_masks_gate_valid   bit delta of the cross mask of main pixel p is cleared unless pvalid(p + delta); the new |S_f|
@@ -104,6 +105,19 @@ __global__ __launch_bounds__(WARP_BLOCK) void k_warp_layers(BcdWarpLayerTable t,
     }
 }
 
+// the gather of k_warp_layers for one (var, ovar null) or two images of F floats per pixel, F = 1 .. BCD_GUIDE_MAX_CHANNELS ("Features")
+template <int F>
+__global__ __launch_bounds__(WARP_BLOCK) void k_warp_features(const float *__restrict__ feat, const float *__restrict__ var, const float *__restrict__ mv, int W, int H,
+                                                              float *__restrict__ ofeat, float *__restrict__ ovar, uint8_t *__restrict__ valid)
+{
+    __shared__ uint32_t s_src[WARP_BLOCK];
+    const size_t npix = (size_t)W * H, base = (size_t)blockIdx.x * WARP_BLOCK;
+    const int n = (int)(npix - base < (size_t)WARP_BLOCK ? npix - base : (size_t)WARP_BLOCK);
+    warp_sources(mv, W, H, base, n, s_src, valid);
+    warp_move<F>(feat, ofeat, s_src, base, n);
+    if (var) warp_move<F>(var, ovar, s_src, base, n);
+}
+
 // validity of the (W / 2) x (H / 2) level from that of the W x H level
 __global__ __launch_bounds__(256) void k_valid_down(const uint8_t *__restrict__ valid, int W, int H, uint8_t *__restrict__ out)
 {
@@ -184,6 +198,28 @@ hipError_t bcd_launch_warp_layers(const BcdWarpLayerTable &t, int layers, const 
 {
     hipLaunchKernelGGL(k_warp_layers, dim3((unsigned)(((size_t)W * H + WARP_BLOCK - 1) / WARP_BLOCK)), dim3(WARP_BLOCK), 0, st, t, layers, mv, W, H, valid);
     return hipGetLastError();
+}
+
+// feat, ofeat: W*H*F floats; var, ovar: the same, or both null
+hipError_t bcd_launch_warp_features(const float *feat, const float *var, int F, const float *mv, int W, int H, float *ofeat, float *ovar, uint8_t *valid, hipStream_t st)
+{
+    if (W <= 0 || H <= 0 || !feat || !ofeat || !valid || (var == nullptr) != (ovar == nullptr)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((size_t)W * H + WARP_BLOCK - 1) / WARP_BLOCK)), block(WARP_BLOCK);
+#define BCD_WARPF_CASE(FF) \
+    case FF: hipLaunchKernelGGL((k_warp_features<FF>), grid, block, 0, st, feat, var, mv, W, H, ofeat, ovar, valid); return hipGetLastError();
+    switch (F) {
+        BCD_WARPF_CASE(1)
+        BCD_WARPF_CASE(2)
+        BCD_WARPF_CASE(3)
+        BCD_WARPF_CASE(4)
+        BCD_WARPF_CASE(5)
+        BCD_WARPF_CASE(6)
+        BCD_WARPF_CASE(7)
+        BCD_WARPF_CASE(8)
+        default: break;
+    }
+#undef BCD_WARPF_CASE
+    return hipErrorInvalidValue;
 }
 
 // out: (W / 2) x (H / 2) bytes; nothing to do (and nothing launched) when that level is empty

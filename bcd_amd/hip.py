@@ -6,7 +6,7 @@ import weakref
 
 from . import _prototypes
 from ._prototypes import (ACCUM_MAX_LAYERS, MAX_LAYERS, MULTI_ID_BYTES, PROGRESS_FN, SELECTION_MAX_SCALES, STATE_HEADER_BYTES, BandJob, Frame, FrameLayer,
-                          FrameLayers, Guide, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
+                          FrameLayers, Guide, GuideImages, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
                           PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
                           StateHeader, WarpedFrame)
 
@@ -886,6 +886,115 @@ class Context:
         self.torch.cuda.synchronize(self.device)
         self._chk(lib().bcd_hip_gate_masks_valid(self.h, _dp(mask), _dp(count), _dp(valid), W, H, int(w), int(b)))
         return mask, count
+
+    # ---- features: the cross-frame selection gated by auxiliary feature buffers ("Features") ----
+    @staticmethod
+    def _guide_images(features, variances, shape, ptr):
+        """the bcd_hip_guide_images of one neighbour: features and optional variances of the frame's feature shape; ptr(a) is an address"""
+        if tuple(features.shape) != tuple(shape) or (variances is not None and tuple(variances.shape) != tuple(shape)):
+            raise ValueError("a neighbour's features (and variances) must have the shape of the frame's features, %r" % (tuple(shape),))
+        return GuideImages(ptr(features), None if variances is None else ptr(variances))
+
+    def _guide_images_array(self, neighbour_features, neighbour_variances, n, shape, ptr):
+        feats = list(neighbour_features)
+        vrs = [None] * len(feats) if neighbour_variances is None else list(neighbour_variances)
+        if len(feats) != n or len(vrs) != n:
+            raise ValueError("one feature image (and one variance image, or none at all) per neighbour expected")
+        arr = (GuideImages * max(1, n))()
+        for i, (f, v) in enumerate(zip(feats, vrs)):
+            arr[i] = self._guide_images(f, v, shape, ptr)
+        return arr
+
+    def denoise_temporal_guided(self, ns, hist, layers, neighbours, nscales, prm, features, neighbour_features, variances=None, neighbour_variances=None, floors=(),
+                                threshold=1.0, motions=None, outs=None):
+        """bcd_hip_denoise_temporal_guided: denoise_temporal_layers_motion with the in-frame and the cross-frame selection gated by feature buffers.  features /
+        variances: (H, W, F) device tensors of the frame; neighbour_features / neighbour_variances: one per neighbour (variances for every frame or for none);
+        floors F numbers, threshold tau_g; motions: None (nothing is warped) or one (H, W, 2) tensor or None per neighbour -> the outputs"""
+        torch = self.torch
+        H, W, D = hist.shape
+        arr, layers, outs = self._layer_array(layers, outs, H, W, hist.device)
+        neighbours = list(neighbours)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _dptr, torch.numel)
+        mv = self._motion_array(motions, len(neighbours), H, W, _dptr, torch.numel)
+        if tuple(features.shape[:2]) != (H, W):
+            raise ValueError("features must be %dx%dxF" % (H, W))
+        g, alive = self._guide(features, variances, floors, threshold)
+        ng = self._guide_images_array(neighbour_features, neighbour_variances, len(neighbours), features.shape, _dptr)
+        torch.cuda.synchronize(self.device)
+        self._chk(lib().bcd_hip_denoise_temporal_guided(self.h, _dp(ns), _dp(hist), nb, len(neighbours), mv, W, H, D, int(nscales), C.byref(prm), arr, len(layers),
+                                                        C.byref(g), ng))
+        del alive, keep
+        return outs
+
+    def denoise_temporal_guided_host(self, ns, hist, layers, neighbours, nscales, prm, features, neighbour_features, variances=None, neighbour_variances=None,
+                                     floors=(), threshold=1.0, motions=None):
+        """bcd_hip_denoise_temporal_guided_host on NumPy float32 arrays -> the list of denoised layers (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        ns, hist = as32(ns), as32(hist)
+        H, W, D = hist.shape
+        neighbours = [(as32(n), as32(h), [(as32(c), as32(v)) for c, v in lay]) for n, h, lay in neighbours]
+        arr, layers, outs = _host_layer_array(layers, H, W, Layer)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _hptr, np.size)
+        fields = None if motions is None else [None if m is None else as32(m) for m in motions]
+        mv = self._motion_array(fields, len(neighbours), H, W, _hptr, np.size)
+        g, alive = self._guide(features, variances, floors, threshold, host=True)
+        if tuple(alive[0].shape[:2]) != (H, W):
+            raise ValueError("features must be %dx%dxF" % (H, W))
+        nfeat = [as32(f) for f in neighbour_features]
+        nvar = None if neighbour_variances is None else [as32(v) for v in neighbour_variances]
+        ng = self._guide_images_array(nfeat, nvar, len(neighbours), alive[0].shape, _hptr)
+        self._chk(lib().bcd_hip_denoise_temporal_guided_host(self.h, ns.ctypes.data, hist.ctypes.data, nb, len(neighbours), mv, W, H, D, int(nscales), C.byref(prm),
+                                                             arr, len(layers), C.byref(g), ng))
+        del alive, keep, fields
+        return outs
+
+    def similarity_masks_guide_cross(self, features, variances, features_nb, variances_nb, floors, threshold, w, b, out=None):
+        """bcd_hip_similarity_masks_guide_cross: the cross feature mask G_j and its counts between the frame's features (H, W, F) (optional variances) and a
+        neighbour's, in the layouts of similarity_masks_cross.  out: (mask (H, W, words) int32, count (H, W) int32) contiguous device tensors to fill"""
+        torch = self.torch
+        H, W, _ = features.shape
+        if out is None:
+            out = _mask_and_count(H, W, b, features.device)
+        mask, cnt = out
+        if mask.numel() != H * W * (((2 * b + 1) ** 2 + 31) // 32) or cnt.numel() != H * W or mask.dtype != torch.int32 or cnt.dtype != torch.int32:
+            raise ValueError("out must be ((H, W, words) int32, (H, W) int32)")
+        g, alive = self._guide(features, variances, floors, threshold)
+        ng = self._guide_images(features_nb, variances_nb, features.shape, _dptr)
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(lib().bcd_hip_similarity_masks_guide_cross(self.h, C.byref(g), C.byref(ng), W, H, int(w), int(b), _dp(mask), _dp(cnt)))
+        del alive
+        return mask, cnt
+
+    def window_distances_guide_cross(self, features, variances, features_nb, variances_nb, floors, w, b, line, column):
+        """bcd_hip_window_distances_guide_cross: the (2b+1)^2 cross feature distances of one main pixel of the frame to its window in the neighbour, +inf outside"""
+        import numpy as np
+        H, W, _ = features.shape
+        out = np.empty(((2 * b + 1) ** 2,), np.float32)
+        g, alive = self._guide(features, variances, floors, 1.0)
+        ng = self._guide_images(features_nb, variances_nb, features.shape, _dptr)
+        self.torch.cuda.synchronize(self.device)
+        self._chk(lib().bcd_hip_window_distances_guide_cross(self.h, C.byref(g), C.byref(ng), W, H, int(w), int(b), int(line), int(column), _fptr(out)))
+        del alive
+        return out
+
+    def warp_features(self, features, variances, motion, out=None):
+        """bcd_hip_warp_features: the feature image (H, W, F) of a neighbour, and its variance image or None, gathered through `motion` ((H, W, 2) device
+        tensor, or None: zero motion) -> (features, variances or None, validity (H, W) uint8); out: the three destinations (the second None without variances)"""
+        torch = self.torch
+        H, W, F = features.shape
+        if out is None:
+            out = (torch.empty_like(features), None if variances is None else torch.empty_like(variances), torch.empty((H, W), dtype=torch.uint8, device=features.device))
+        of, ov, valid = out
+        if of.numel() != H * W * F or (ov is not None and ov.numel() != H * W * F) or valid.numel() != H * W:
+            raise ValueError("destinations of the sources' sizes and (H, W) validity bytes are expected")
+        if motion is not None and motion.numel() != H * W * 2:
+            raise ValueError("the motion field must hold (H, W, 2) floats")
+        src = self._guide_images(features, variances, features.shape, _dptr)
+        torch.cuda.synchronize(self.device)
+        self._chk(lib().bcd_hip_warp_features(self.h, C.byref(src), F, _dp(motion) if motion is not None else None, W, H, _dp(of), _dp(ov) if ov is not None else None,
+                                              _dp(valid)))
+        return of, ov, valid
 
     def denoise_temporal_stages(self, col, ns, hist, cov, neighbours, prm):
         """One scale of the denoising of a frame with similar patches from neighbouring frames of its sequence, composed from the

@@ -145,6 +145,32 @@ namespace bcd
 			cerr << "Aborting denoising: " << m_guideFloors.size() << " feature floors for " << depth << " feature channels" << endl;
 			return false;
 		}
+		// beside neighbour frames every neighbour brings its own feature buffers (setNeighbourGuideFeatures), shaped like the frame's
+		for(size_t k = 0; k < m_neighbourFrames.size(); ++k)
+		{
+			const NeighbourGuide guide = k < m_neighbourGuides.size() ? m_neighbourGuides[k] : NeighbourGuide();
+			if(!guide.m_pFeatures)
+			{
+				cerr << "Aborting denoising: neighbour frame " << k + 1 << " has no feature buffers (setNeighbourGuideFeatures) while the frame has (setGuideFeatures)" << endl;
+				return false;
+			}
+			if(guide.m_pFeatures->getWidth() != w || guide.m_pFeatures->getHeight() != h || guide.m_pFeatures->getDepth() != depth)
+			{
+				cerr << "Aborting denoising: the feature image of neighbour frame " << k + 1 << " must be " << w << "x" << h << "x" << depth << " like the frame's feature image (it is "
+						<< guide.m_pFeatures->getWidth() << "x" << guide.m_pFeatures->getHeight() << "x" << guide.m_pFeatures->getDepth() << ")" << endl;
+				return false;
+			}
+			if((guide.m_pVariances != nullptr) != (m_pGuideVariances != nullptr))
+			{
+				cerr << "Aborting denoising: feature variances must be given for the frame and every neighbour frame or for none (neighbour frame " << k + 1 << " differs)" << endl;
+				return false;
+			}
+			if(guide.m_pVariances && (guide.m_pVariances->getWidth() != w || guide.m_pVariances->getHeight() != h || guide.m_pVariances->getDepth() != depth))
+			{
+				cerr << "Aborting denoising: the feature variance image of neighbour frame " << k + 1 << " must be " << w << "x" << h << "x" << depth << " like the feature image" << endl;
+				return false;
+			}
+		}
 		return true;
 	}
 
@@ -204,9 +230,14 @@ namespace bcd
 			cerr << "Aborting denoising: the selection from means and covariances (setMomentSelection) is not available over several devices" << endl;
 			return false;
 		}
-		if(!m_neighbourFrames.empty() && (m_devices.size() > 1 || m_momentSelection || m_pGuideFeatures))
+		if(!m_neighbourFrames.empty() && m_devices.size() > 1)
 		{
-			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available over several devices, with the moment selection or with feature buffers" << endl;
+			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available over several devices" << endl;
+			return false;
+		}
+		if(!m_neighbourFrames.empty() && m_momentSelection)
+		{
+			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available with the moment selection: there is no cross-frame selection from means and covariances" << endl;
 			return false;
 		}
 		if(!inputsOutputsAreOk() || !layersAreOk() || !guideIsOk())
@@ -320,7 +351,7 @@ namespace bcd
 			bcd_hip_host_options opt;
 			opt.spike_factor = m_prefilterThresholdStDevFactor;
 			opt.zero_bad_values = m_zeroBadOutputValues ? 1 : 0;
-			if(m_pGuideFeatures)
+			if(m_pGuideFeatures && m_neighbourFrames.empty())
 			{	// the selection gated by the feature buffers: with histograms or, under setMomentSelection, without; the primary images are layer 0
 				std::vector<bcd_hip_host_layer> layers(m_layers.size() + 1);
 				layers[0].h_colors = pIn[0]; layers[0].h_covariances = pIn[3]; layers[0].h_out = result.getDataPtr();
@@ -398,7 +429,37 @@ namespace bcd
 					bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
 					return false;
 				}
-				if(nbOfLayers == 0 && anyMotion)
+				if(m_pGuideFeatures)
+				{	// the gate of the feature buffers on the in-frame and on every cross-frame selection (guideIsOk has checked the neighbours' buffers); the
+					// primary images are layer 0 of every frame, added layers and motion fields as without the guide
+					std::vector<bcd_hip_layer> layers(nbOfLayers + 1);
+					layers[0] = { pIn[0], pIn[3], result.getDataPtr() };
+					for(size_t k = 0; k < nbOfLayers; ++k)
+					{
+						layerResults[k].resize(m_width, m_height, 3);
+						layers[k + 1] = { m_layers[k].m_pColors->getDataPtr(), m_layers[k].m_pSampleCovariances->getDataPtr(), layerResults[k].getDataPtr() };
+					}
+					bcd_hip_guide guide;
+					guide.features = m_pGuideFeatures->getDataPtr();
+					guide.variances = m_pGuideVariances ? m_pGuideVariances->getDataPtr() : nullptr;
+					guide.nb_channels = m_pGuideFeatures->getDepth();
+					guide.floors = m_guideFloors.data();
+					guide.threshold = m_guideThreshold;
+					std::vector<bcd_hip_guide_images> neighbourGuides(m_neighbourFrames.size());
+					for(size_t k = 0; k < m_neighbourFrames.size(); ++k)
+						neighbourGuides[k] = { m_neighbourGuides[k].m_pFeatures->getDataPtr(), m_neighbourGuides[k].m_pVariances ? m_neighbourGuides[k].m_pVariances->getDataPtr() : nullptr };
+					rc = bcd_hip_denoise_temporal_guided_host(rSlot.m_pCtx, pIn[1], pIn[2], layeredFrames.data(), int(layeredFrames.size()), anyMotion ? motion.data() : nullptr, m_width,
+							m_height, depth, i_nbOfScales, &prm, layers.data(), int(layers.size()), &guide, neighbourGuides.data());
+					if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
+						for(size_t k = 0; k < nbOfLayers; ++k)
+						{
+							float* p = layerResults[k].getDataPtr();
+							for(size_t i = 0, n = size_t(m_nbOfPixels) * 3; i < n; ++i)
+								if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
+									p[i] = 0.f;
+						}
+				}
+				else if(nbOfLayers == 0 && anyMotion)
 					rc = bcd_hip_denoise_temporal_motion_host(rSlot.m_pCtx, pIn[0], pIn[1], pIn[2], pIn[3], frames.data(), int(frames.size()), motion.data(), m_width, m_height, depth,
 							i_nbOfScales, &prm, result.getDataPtr());
 				else if(nbOfLayers == 0)
@@ -504,6 +565,7 @@ namespace bcd
 		engine.setNeighbourFrames(m_neighbourFrames);
 		engine.setNeighbourFrameLayers(m_neighbourLayers);
 		engine.setNeighbourMotions(m_neighbourMotion);
+		engine.setNeighbourGuides(m_neighbourGuides);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);

@@ -7,6 +7,8 @@
 // --layer <color.exr> <cov.exr> <out.exr> (repeatable) denoises a further colour layer with the filter of the -i image (one selection of similar patches for all).
 // --neighbour-layer <color.exr> <cov.exr> hands the most recent --neighbour the matching layer (the k-th pairs with the k-th --layer).
 // --neighbour-motion <mv.exr> hands the most recent --neighbour its motion field ((dx, dy) in the first two channels).
+// --neighbour-features <f.exr> / --neighbour-feature-variances <v.exr> hand the most recent --neighbour its feature buffers: with --features the gate covers
+// the search in the neighbours too (every neighbour then needs them).
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
 #include "Chronometer.h"
 #include "DeepImage.h"
@@ -50,7 +52,7 @@ namespace
 		std::vector<int> m_devices = std::vector<int>(1, 0);
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
 		struct NeighbourLayer { string m_colorPath, m_covariancePath; Deepimf m_colorImage, m_covarianceImage; };
-		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ string m_motionPath; Deepimf m_motionImage; /* --neighbour-motion */ };
+		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ string m_motionPath; Deepimf m_motionImage; /* --neighbour-motion */ string m_featurePath, m_featureVariancePath; Deepimf m_featureImage, m_featureVarianceImage; /* --neighbour-features, --neighbour-feature-variances */ };
 		std::vector<Neighbour> m_neighbours; // --neighbour, in command-line order
 		std::vector<Layer> m_layers; // --layer, in command-line order
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
@@ -81,6 +83,11 @@ namespace
 		cout << "    --neighbour-motion <mv.exr>" << endl;
 		cout << "                         the motion field of the most recent --neighbour: pixel (x, y) of the frame shows what pixel (x + dx, y + dy) of that" << endl;
 		cout << "                         neighbour shows, (dx, dy) in the first two channels, rounded to whole pixels; NaN marks a disoccluded pixel" << endl;
+		cout << "    --neighbour-features <file>" << endl;
+		cout << "                         the feature buffers of the most recent --neighbour, channels as --features: with --features every neighbour needs" << endl;
+		cout << "                         them, and a patch of a neighbour stays similar only if its features agree with the frame's" << endl;
+		cout << "    --neighbour-feature-variances <file>" << endl;
+		cout << "                         the variances of that neighbour's features (given exactly when --feature-variances is)" << endl;
 		cout << "    --neighbour-layer <color> <cov>" << endl;
 		cout << "                         a colour layer of the most recent --neighbour: the k-th one pairs with the k-th --layer; every neighbour" << endl;
 		cout << "                         needs exactly one per --layer (one selection over all frames then serves every layer; needs -p 0)" << endl;
@@ -180,6 +187,21 @@ namespace
 				{
 					rNb.m_motionImage.get(2 * px) = loaded.get(d * px);
 					rNb.m_motionImage.get(2 * px + 1) = loaded.get(d * px + 1);
+				}
+				continue;
+			}
+			if(flag == "--neighbour-features" || flag == "--neighbour-feature-variances")
+			{	// the feature buffers of the most recent --neighbour
+				const bool variances = flag == "--neighbour-feature-variances";
+				if(i + 1 >= argc) { cout << "ERROR in program arguments: expecting <file.exr> after " << flag << endl; return false; }
+				if(a.m_neighbours.empty()) { cout << "ERROR in program arguments: " << flag << " follows the --neighbour it belongs to" << endl; return false; }
+				ProgramArguments::Neighbour& rNb = a.m_neighbours.back();
+				string& rPath = variances ? rNb.m_featureVariancePath : rNb.m_featurePath;
+				rPath = argv[++i];
+				if(!ImageIO::loadMultiChannelsEXR(variances ? rNb.m_featureVarianceImage : rNb.m_featureImage, rPath.c_str()))
+				{
+					cout << "ERROR in program arguments: couldn't load neighbour feature " << (variances ? "variance " : "") << "image file '" << rPath << "'" << endl;
+					return false;
 				}
 				continue;
 			}
@@ -334,6 +356,39 @@ namespace
 		}
 		if(!a.m_momentSelection && !nbOfSamplesArgument.empty()) { cout << "ERROR in program arguments: --nsamples goes with --moment-selection" << endl; return false; }
 		if(a.m_featurePath.empty() && (!a.m_featureVariancePath.empty() || !a.m_featureFloors.empty())) { cout << "ERROR in program arguments: --feature-variances and --feature-floors go with --features" << endl; return false; }
+		for(const ProgramArguments::Neighbour& rNb : a.m_neighbours)
+		{	// the feature gate covers the frame and every neighbour, or nothing (checked here: nothing has touched a device yet)
+			if(!a.m_featurePath.empty() && rNb.m_featurePath.empty())
+			{
+				cout << "ERROR in program arguments: neighbour '" << rNb.m_colorPath << "' has no --neighbour-features while --features is given: every neighbour needs its feature buffers" << endl;
+				return false;
+			}
+			if(a.m_featurePath.empty() && (!rNb.m_featurePath.empty() || !rNb.m_featureVariancePath.empty()))
+			{
+				cout << "ERROR in program arguments: neighbour '" << rNb.m_colorPath << "' has --neighbour-features but there is no --features for the frame" << endl;
+				return false;
+			}
+			if(rNb.m_featurePath.empty() && !rNb.m_featureVariancePath.empty())
+			{
+				cout << "ERROR in program arguments: --neighbour-feature-variances goes with --neighbour-features (neighbour '" << rNb.m_colorPath << "')" << endl;
+				return false;
+			}
+			if(!a.m_featurePath.empty() && a.m_featureVariancePath.empty() != rNb.m_featureVariancePath.empty())
+			{
+				cout << "ERROR in program arguments: feature variances go with the frame and every neighbour or with none: --feature-variances is "
+						<< (a.m_featureVariancePath.empty() ? "absent" : "given") << ", --neighbour-feature-variances of neighbour '" << rNb.m_colorPath << "' is "
+						<< (rNb.m_featureVariancePath.empty() ? "absent" : "given") << endl;
+				return false;
+			}
+			for(const Deepimf* pImage : { &rNb.m_featureImage, &rNb.m_featureVarianceImage })
+				if(!a.m_featurePath.empty() && (pImage == &rNb.m_featureImage || !rNb.m_featureVariancePath.empty())
+						&& (pImage->getWidth() != a.m_featureImage.getWidth() || pImage->getHeight() != a.m_featureImage.getHeight() || pImage->getDepth() != a.m_featureImage.getDepth()))
+				{
+					cout << "ERROR in program arguments: the feature images of neighbour '" << rNb.m_colorPath << "' must be " << a.m_featureImage.getWidth() << "x" << a.m_featureImage.getHeight()
+							<< "x" << a.m_featureImage.getDepth() << " like the --features image (one is " << pImage->getWidth() << "x" << pImage->getHeight() << "x" << pImage->getDepth() << ")" << endl;
+					return false;
+				}
+		}
 		if(!a.m_featurePath.empty())
 		{	// (checked here: nothing has touched a device yet)
 			const int depth = a.m_featureImage.getDepth();
@@ -563,6 +618,8 @@ namespace
 				pSettings->addNeighbourFrameLayer(pSettings->getNeighbourFrames().size() - 1, &rLayer.m_colorImage, &rLayer.m_covarianceImage);
 			if(!rNb.m_motionPath.empty())
 				pSettings->setNeighbourMotion(pSettings->getNeighbourFrames().size() - 1, &rNb.m_motionImage);
+			if(!rNb.m_featurePath.empty())
+				pSettings->setNeighbourGuideFeatures(pSettings->getNeighbourFrames().size() - 1, &rNb.m_featureImage, rNb.m_featureVariancePath.empty() ? nullptr : &rNb.m_featureVarianceImage);
 		}
 		std::vector<Deepimf> layerOutputs(args.m_layers.size());
 		for(size_t k = 0; k < args.m_layers.size(); ++k)

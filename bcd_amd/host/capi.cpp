@@ -623,9 +623,19 @@ int bcdcore_denoise_temporal_motion(const float* col, const float* ns, const flo
 /// nbOfLayers images of the frame one behind the other (layer 0 = the primary images), nbCols / nbCovs nbOfNeighbours x nbOfLayers images (neighbour-major),
 /// nbNs / nbHists one image per neighbour.  The last neighbour gets dropLayers fewer layers than the frame (> 0: denoise() must refuse).  afterClear != 0:
 /// clearNeighbourFrames() and a second denoise() follow (the plain layered call), whose results replace the first.  Returns denoise()'s bool.
+/// i_pGuide (bcdcore_denoise_temporal_guided): setGuideFeatures on the frame and setNeighbourGuideFeatures on the first nbOfNeighboursWithFeatures neighbours --
+/// features W x H x nbOfChannels, the neighbours' W x H x nbOfNeighbourChannels one behind the other, variances of the same sizes or null --, and the settings
+/// the combination must refuse: momentSelection != 0 -> setMomentSelection(true), nbOfDevices > 0 -> setDevices.
+struct TemporalGuide
+{
+	const float* features; const float* variances; int nbOfChannels; const float* floors; int nbOfFloors; float threshold;
+	const float* nbFeatures; const float* nbVariances; int nbOfNeighbourChannels; int nbOfNeighboursWithFeatures;
+	int momentSelection; const int* devices; int nbOfDevices;
+};
+
 static int denoiseTemporalLayers(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs, const float* nbNs,
 		const float* nbHists, int nbOfNeighbours, int nbOfLayers, const float* motions, const int* hasMotion, int W, int H, int D, int nscales, float tau, int b, float minEig,
-		int randomOrder, float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs)
+		int randomOrder, float skipProbability, unsigned seed, int dropLayers, int afterClear, float* outs, const TemporalGuide* i_pGuide = nullptr)
 {
 	const size_t npix = size_t(W) * H;
 	Deepimf nImg(W, H, 1), hImg(W, H, D);
@@ -680,6 +690,26 @@ static int denoiseTemporalLayers(const float* cols, const float* covs, const flo
 			pSettings->setNeighbourMotion(size_t(f), &mv[f]);
 		}
 	}
+	Deepimf gf, gv;
+	std::vector<Deepimf> nf(nbOfNeighbours), nv(nbOfNeighbours);
+	if(i_pGuide)
+	{
+		const TemporalGuide& g = *i_pGuide;
+		gf.resize(W, H, g.nbOfChannels); gf.copyDataFrom(g.features);
+		if(g.variances) { gv.resize(W, H, g.nbOfChannels); gv.copyDataFrom(g.variances); }
+		pSettings->setGuideFeatures(&gf, g.variances ? &gv : nullptr, std::vector<float>(g.floors, g.floors + g.nbOfFloors), g.threshold);
+		for(int f = 0; f < nbOfNeighbours && f < g.nbOfNeighboursWithFeatures; ++f)
+		{
+			const size_t n = npix * g.nbOfNeighbourChannels;
+			nf[f].resize(W, H, g.nbOfNeighbourChannels); nf[f].copyDataFrom(g.nbFeatures + f * n);
+			if(g.nbVariances) { nv[f].resize(W, H, g.nbOfNeighbourChannels); nv[f].copyDataFrom(g.nbVariances + f * n); }
+			pSettings->setNeighbourGuideFeatures(size_t(f), &nf[f], g.nbVariances ? &nv[f] : nullptr);
+		}
+		if(g.momentSelection)
+			pSettings->setMomentSelection(true);
+		if(g.devices && g.nbOfDevices > 0)
+			pSettings->setDevices(std::vector<int>(g.devices, g.devices + g.nbOfDevices));
+	}
 	d->setInputs(in);
 	d->setOutputs(out);
 	d->setParameters(p);
@@ -712,6 +742,20 @@ int bcdcore_denoise_temporal_layers_motion(const float* cols, const float* covs,
 {
 	return denoiseTemporalLayers(cols, covs, ns, hist, nbCols, nbCovs, nbNs, nbHists, nbOfNeighbours, nbOfLayers, motions, hasMotion, W, H, D, nscales, tau, b, minEig,
 			randomOrder, skipProbability, seed, dropLayers, afterClear, outs);
+}
+
+/// ... with feature buffers on the frame (setGuideFeatures) and on the neighbours (setNeighbourGuideFeatures): see TemporalGuide.  motions may be null
+int bcdcore_denoise_temporal_guided(const float* cols, const float* covs, const float* ns, const float* hist, const float* nbCols, const float* nbCovs, const float* nbNs,
+		const float* nbHists, int nbOfNeighbours, int nbOfLayers, const float* motions, const int* hasMotion, int W, int H, int D, int nscales, float tau, int b, float minEig,
+		int randomOrder, float skipProbability, unsigned seed, int afterClear, const float* features, const float* variances, int nbOfChannels, const float* floors,
+		int nbOfFloors, float threshold, const float* nbFeatures, const float* nbVariances, int nbOfNeighbourChannels, int nbOfNeighboursWithFeatures, int momentSelection,
+		const int* devices, int nbOfDevices, float* outs)
+{
+	if(!features || !floors || nbOfChannels < 1 || nbOfNeighbourChannels < 1) return 0;
+	const TemporalGuide guide = { features, variances, nbOfChannels, floors, nbOfFloors, threshold, nbFeatures, nbVariances, nbOfNeighbourChannels,
+			nbFeatures ? nbOfNeighboursWithFeatures : 0, momentSelection, devices, nbOfDevices };
+	return denoiseTemporalLayers(cols, covs, ns, hist, nbCols, nbCovs, nbNs, nbHists, nbOfNeighbours, nbOfLayers, motions, hasMotion, W, H, D, nscales, tau, b, minEig,
+			randomOrder, skipProbability, seed, 0, afterClear, outs, &guide);
 }
 
 /// ONE MultiscaleDenoiser (or Denoiser), denoise() called twice with -r 0 and the given m_nbOfCores: the written-back core count must not

@@ -71,7 +71,7 @@ namespace bcd
 		/// cannot see.  i_pFeatures: W x H x F, 1 <= F <= 8; i_pVariances: the variance of each pixel's feature MEAN, same size, or null; i_rFloors: one
 		/// value per channel, finite and >= 0 (without variances: the squared tolerance of the channel; 0 switches the channel off); i_threshold: finite,
 		/// >= 0, 1 = "one tolerance rms".  Non-owning pointers, like DenoiserInputs.  A null features pointer switches the gate off.  Added layers, the
-		/// prefilter switches and the moment selection work as without it; one device only.
+		/// prefilter switches and the moment selection work as without it; one device only.  Beside neighbour frames: see setNeighbourGuideFeatures.
 		void setGuideFeatures(const DeepImage<float>* i_pFeatures, const DeepImage<float>* i_pVariances, const std::vector<float>& i_rFloors, float i_threshold = 1.f)
 		{
 			m_pGuideFeatures = i_pFeatures;
@@ -88,16 +88,40 @@ namespace bcd
 		/// similar patches are also searched in the same window of every neighbour frame, and mean, noise mean and covariance of the estimate come from the
 		/// union of the sets; only the frame itself is denoised.  Each neighbour brings all four images, of the frame's width, height and histogram depth.
 		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with the spike
-		/// prefilter, the moment selection or feature buffers.  With no neighbour denoise() is what it always was.
-		void addNeighbourFrame(const DenoiserInputs& i_rFrame) { m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); m_neighbourMotion.push_back(nullptr); }
-		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); m_neighbourMotion.clear(); }
+		/// prefilter or the moment selection; feature buffers need setNeighbourGuideFeatures for every neighbour.  With no neighbour denoise() is what it always was.
+		void addNeighbourFrame(const DenoiserInputs& i_rFrame)
+		{
+			m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); m_neighbourMotion.push_back(nullptr); m_neighbourGuides.emplace_back();
+		}
+		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); m_neighbourMotion.clear(); m_neighbourGuides.clear(); }
 		const std::vector<DenoiserInputs>& getNeighbourFrames() const { return m_neighbourFrames; }
 		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames)
 		{
 			m_neighbourFrames = i_rFrames;
 			m_neighbourLayers.assign(i_rFrames.size(), std::vector<NeighbourLayer>());
 			m_neighbourMotion.assign(i_rFrames.size(), nullptr);
+			m_neighbourGuides.assign(i_rFrames.size(), NeighbourGuide());
 		}
+		/// The feature buffers of neighbour i_neighbour (bcd_hip_denoise_temporal_guided_host): with setGuideFeatures and neighbour frames, the gate that protects
+		/// the search inside the frame protects the search in the neighbours too -- a patch of a neighbour stays similar only if its features agree with the
+		/// frame's.  i_pFeatures: the frame's feature size and channel count; i_pVariances: given exactly when the frame's guide has variances.  Floors and
+		/// threshold are those of setGuideFeatures.  A neighbour with a motion field has its features reprojected with its other images.  denoise() refuses a
+		/// neighbour without features while setGuideFeatures is in force.  clearNeighbourFrames() clears all.  An index that names no neighbour is ignored.
+		struct NeighbourGuide
+		{
+			const DeepImage<float>* m_pFeatures = nullptr;
+			const DeepImage<float>* m_pVariances = nullptr;
+		};
+		void setNeighbourGuideFeatures(size_t i_neighbour, const DeepImage<float>* i_pFeatures, const DeepImage<float>* i_pVariances)
+		{
+			if(i_neighbour < m_neighbourGuides.size())
+			{
+				m_neighbourGuides[i_neighbour].m_pFeatures = i_pFeatures;
+				m_neighbourGuides[i_neighbour].m_pVariances = i_pFeatures ? i_pVariances : nullptr;
+			}
+		}
+		const std::vector<NeighbourGuide>& getNeighbourGuides() const { return m_neighbourGuides; }
+		void setNeighbourGuides(const std::vector<NeighbourGuide>& i_rGuides) { m_neighbourGuides = i_rGuides; m_neighbourGuides.resize(m_neighbourFrames.size()); }
 		/// The motion field of neighbour i_neighbour (bcd_hip_denoise_temporal_motion_host): a 2-channel image of the frame's size, (dx, dy) per pixel -- pixel
 		/// (l, c) of the frame shows what pixel (l + round(dy), c + round(dx)) of the neighbour shows, rounding to nearest even; NaN marks a disoccluded pixel.
 		/// The neighbour is reprojected into the frame's pixel grid before its similar patches are searched, and members whose patch holds a pixel without a
@@ -144,6 +168,7 @@ namespace bcd
 		std::vector<DenoiserInputs> m_neighbourFrames;
 		std::vector<std::vector<NeighbourLayer>> m_neighbourLayers; // [neighbour][added layer], as long as m_neighbourFrames
 		std::vector<const DeepImage<float>*> m_neighbourMotion;     // [neighbour] its motion field or nullptr, as long as m_neighbourFrames
+		std::vector<NeighbourGuide> m_neighbourGuides;              // [neighbour] its feature buffers, as long as m_neighbourFrames
 	};
 
 	/// The engine contexts behind denoise() (device workspaces, pyramids, staging buffers: grow-only, sized by the largest frame seen,

@@ -321,8 +321,8 @@ int bcd_hip_denoise_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const floa
  * (bcd_hip_denoise_host): it delegates.  Motion vectors arrive through bcd_hip_denoise_temporal_motion below; `reserved` must be NULL.
  * Refused before any device work, with a message, the context staying usable: with neighbours, any geometry but patch radius 1 and search radius 6
  * (BCD_HIP_EUNSUPPORTED); nb_neighbours outside 0 .. 4; a null image; a non-NULL `reserved`; an output that is or overlaps an input; what bcd_hip_denoise
- * refuses.  Kept selections, the moment and the feature-gated selection, row bands and bcd_hip_multi_* do not combine with this call; colour layers do
- * through bcd_hip_denoise_temporal_layers below.
+ * refuses.  Kept selections, the moment selection, row bands and bcd_hip_multi_* do not combine with this call; colour layers do through
+ * bcd_hip_denoise_temporal_layers below, the feature-gated selection through bcd_hip_denoise_temporal_guided further down.
  * bcd_hip_get_stats: similar_total is the sum of the total |S|, similarity_path that of the in-frame pass, ms_similarity includes the cross passes.
  *   _host: whole uploads (no streaming), the resident call, one download: the same result. */
 typedef struct { const float *d_colors, *d_nsamples, *d_histograms, *d_covariances; const void *reserved; } bcd_hip_frame;
@@ -357,8 +357,9 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
  * Delegations: nb_neighbours == 0 IS bcd_hip_denoise_layers, nb_layers == 1 IS bcd_hip_denoise_temporal (likewise for _host).
  * Refused before any device work, with a message, the context staying usable: everything bcd_hip_denoise_temporal and bcd_hip_denoise_layers refuse; a NULL
  * layer list in a neighbour; a NULL image in any layer of any frame; a non-NULL `reserved`; an output that is, or overlaps, any input of any frame or
- * another output; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).  Kept selections, the moment and the
- * feature-gated selection, the spike prefilter, row bands and bcd_hip_multi_* do not combine with this call; motion vectors arrive through bcd_hip_denoise_temporal_layers_motion below.
+ * another output; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).  Kept selections, the moment
+ * selection, the spike prefilter, row bands and bcd_hip_multi_* do not combine with this call; motion vectors arrive through
+ * bcd_hip_denoise_temporal_layers_motion below, the feature-gated selection through bcd_hip_denoise_temporal_guided.
  *   _host: every pointer is a host pointer; whole uploads (no streaming, no spike prefilter), the resident call, one download per layer: the same result.
  *   _bayes_accumulate_temporal_layers: the estimate stage -- the twin of bcd_hip_bayes_accumulate_temporal for nb_layers layers on ONE selection.  frames[f]
  *             holds host arrays of nb_layers device pointers (the colours and the per-pixel covariances of that frame's layers) and the frame's masks, [0]
@@ -434,6 +435,62 @@ int bcd_hip_warp_layers(bcd_hip_ctx *ctx, const bcd_hip_frame_layer *layers, int
                         uint8_t *d_valid);
 int bcd_hip_valid_downscale(bcd_hip_ctx *ctx, const uint8_t *d_valid, int W, int H, uint8_t *d_out);
 int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_count, const uint8_t *d_valid, int W, int H, int patch_radius, int search_radius);
+
+/* ---- features: the cross-frame selection gated by auxiliary feature buffers ("Features") ----
+ * The gate of bcd_hip_denoise_guided protects the in-frame search; this one protects the cross-frame search too.  Across frames there is motion: an object
+ * that moved, or a warp whose rounded or stale vectors land on another surface, and at low sample counts the histogram distance cannot tell the two surfaces
+ * apart.  Inputs are those of bcd_hip_denoise_temporal_layers_motion plus a guide (bcd_hip_guide: F channels, 1 <= F <= 8, features f0, optional variances
+ * v0, host floors eps_k, threshold tau_g) and, per neighbour j = 1 .. N, a feature image fj of W*H*F floats and a variance image vj exactly when the frame
+ * has one.  Floors and threshold are the guide's, for every frame and every scale.  float32, no contraction, the correctly rounded division:
+ * 1. Cross feature planes.  For pixel x of the frame and pixel y = x + delta of neighbour j, y inside the image, channels k = 0 .. F-1 in order, from
+ *    s = 0.f, n = 0:
+ *        d = f0_k(x) - fj_k(y)
+ *        q = (v0_k(x) + vj_k(y)) + eps_k                             (no variances: q = 0.f + eps_k)
+ *        if (q > 0.f) { t = (d * d) / q;  if (t == t) { s = s + t; n = n + 1; } }
+ *        T_delta(x) = s,  C_delta(x) = n
+ *    The term of bcd_hip_denoise_guided with the second operand read from the neighbour: a NaN term is skipped, an infinite term counts.  There is no
+ *    symmetry between two frames, so all (2b+1)^2 displacements are evaluated; plane k = (dl + b)(2b + 1) + (dc + b) is mask bit k.
+ * 2. Cross feature mask G_j(p): what bcd_hip_similarity_masks_cross makes of its planes, made of these with tau_g -- the (2w+1)^2 entries added in patch
+ *    row-major order from 0.f, integer counts, one division, the test <= tau_g, NaN never similar, the clipped window, the main-pixel rule, the bit layout
+ *    and empty masks off the main pixels.
+ * 3. Gate.  S_0 is gated as in bcd_hip_denoise_guided (the mask ANDed with the in-frame feature mask of bcd_hip_similarity_masks_guide, |S_0| the
+ *    popcount); for every neighbour, cross mask &= G_j and |S_j| is the popcount; total |S| = |S_0| + sum |S_j|.  A pure AND with no special case for
+ *    delta = 0.  The gates run at every scale, ahead of the sum of the counts and the marking.
+ * 4. Motion.  A neighbour with a motion field has its features and variances gathered by the same source pixel and the same validity as its other images: a
+ *    valid pixel is copied bit for bit, an invalid pixel becomes +0.0f.  The gather happens at full resolution, before the pyramid is built.  The validity
+ *    gate of the motion calls stays; the three ANDs commute.
+ * 5. Pyramid, for every frame: features bcd_hip_downscale_avg (D = F), variances bcd_hip_downscale_avg times 0.25f; a warped neighbour's pyramid is built
+ *    from the warped images.
+ * 6. Everything else is the plain calls': member order, the 3P + 1 rule, marking on the (gated) in-frame masks, estimate, fallback, multiscale, seeds,
+ *    layers on one selection.  bcd_hip_get_stats describes the gated selection; similar_total is the sum of the gated total |S|.
+ * A neighbour whose features and variances ARE the frame's gives G_j equal, bit for bit, to the in-frame feature mask of bcd_hip_similarity_masks_guide.
+ *   _denoise_temporal_guided: L = 1 .. 16 layers, d_motion NULL (nothing is warped) or nb_neighbours entries, each NULL or W*H*2 floats.  nb_neighbours == 0 IS
+ *             bcd_hip_denoise_guided (histograms, sel = NULL).  Refused before any device work, with a message, the context staying usable: everything
+ *             bcd_hip_denoise_temporal_layers_motion and bcd_hip_denoise_guided refuse; a NULL guide, neighbour_guides or neighbour feature pointer;
+ *             variances present in some frames and not in others; d_histograms == NULL (there is no cross-frame moment selection); an output that overlaps a
+ *             feature or variance image of any frame; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).
+ *   _denoise_temporal_guided_host: the same, every pointer a host pointer: whole uploads, the resident call, one download per layer.
+ *   _similarity_masks_guide_cross: G_j and its counts alone, outputs as bcd_hip_similarity_masks_cross.
+ *   _window_distances_guide_cross: the twin of bcd_hip_window_distances_cross: the (2b+1)^2 cross feature distances of one main pixel, +inf outside.
+ *   _warp_features: the gather of bcd_hip_warp_layers for the feature image (and the variance image: d_variances_out is NULL exactly when in->variances is)
+ *             of nb_channels floats per pixel; d_valid W*H bytes.  A destination that overlaps an input, the field or another destination is refused.
+ * The stage calls accept what bcd_hip_similarity_masks_cross accepts (w <= 2, b <= 15) with F <= 8, refuse the rest before any device work, and synchronise.
+ * Kept selections, the moment selection, the spike prefilter, search radius 12, row bands and bcd_hip_multi_* do not combine with these calls. */
+typedef struct { const float *features; const float *variances; /* NULL iff the guide's are */ } bcd_hip_guide_images;
+int bcd_hip_denoise_temporal_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                    const float *const *d_motion /* NULL: nothing is warped; else nb_neighbours entries, each NULL or W*H*2 */, int W, int H, int D,
+                                    int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const bcd_hip_guide *guide,
+                                    const bcd_hip_guide_images *neighbour_guides /* nb_neighbours */);
+int bcd_hip_denoise_temporal_guided_host(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms, const bcd_hip_frame_layers *neighbours /* host pointers */,
+                                         int nb_neighbours, const float *const *h_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
+                                         const bcd_hip_layer *layers /* host pointers */, int nb_layers, const bcd_hip_guide *guide /* host images */,
+                                         const bcd_hip_guide_images *neighbour_guides /* host images */);
+int bcd_hip_similarity_masks_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour, int W, int H, int patch_radius,
+                                         int search_radius, uint32_t *d_mask, int32_t *d_count);
+int bcd_hip_window_distances_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour, int W, int H, int patch_radius,
+                                         int search_radius, int line, int col, float *h_out);
+int bcd_hip_warp_features(bcd_hip_ctx *ctx, const bcd_hip_guide_images *in, int nb_channels, const float *d_motion, int W, int H, float *d_features_out,
+                          float *d_variances_out /* NULL iff in->variances */, uint8_t *d_valid);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
