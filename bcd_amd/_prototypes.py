@@ -252,6 +252,11 @@ PROTOTYPES = {
     "bcd_hip_similarity_masks_guide_cross": (I, [P, S(Guide), S(GuideImages), I, I, I, I, P, P]),
     "bcd_hip_window_distances_guide_cross": (I, [P, S(Guide), S(GuideImages), I, I, I, I, I, I, P]),
     "bcd_hip_warp_features": (I, [P, S(GuideImages), I, P, I, I, P, P, P]),
+    # ---- moments: the cross-frame selection from means and covariances, without histograms ("Moments")
+    "bcd_hip_similarity_masks_moments_cross": (I, [P, P, P, P, P, I, I, I, I, F, F, I, P, P]),
+    "bcd_hip_window_distances_moments_cross": (I, [P, P, P, P, P, I, I, I, I, F, I, I, P]),
+    "bcd_hip_denoise_temporal_moments": (I, [P, P, S(FrameLayers), I, P, I, I, I, S(Params), F, S(Layer), I, S(Guide), S(GuideImages)]),
+    "bcd_hip_denoise_temporal_moments_host": (I, [P, P, S(FrameLayers), I, P, I, I, I, S(Params), F, S(Layer), I, S(Guide), S(GuideImages)]),
     # (row bands, for multi-GPU tiling)
     "bcd_hip_denoise_band": (I, [P, P, P, P, P, I, I, I, I, I, S(Params), U32, P, P]),
     "bcd_hip_denoise_bands": (I, [P, S(BandJob), I, S(Params)]),

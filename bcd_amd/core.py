@@ -340,6 +340,42 @@ def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=
     return rc != 0, [outs[k] for k in range(L)]
 
 
+def denoise_temporal_moments(ns, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, var_floor=1e-8, motions=None,
+                             features=None, neighbour_features=None, variances=None, neighbour_variances=None, floors=(), threshold=1.0, moment_selection=True,
+                             plain_neighbours=0, drop_layers=0, devices=None):
+    """bcd::Denoiser / bcd::MultiscaleDenoiser under setMomentSelection(true, var_floor) with neighbour frames added by addNeighbourFrameMoments: no histogram
+    anywhere (bcd_hip_denoise_temporal_moments_host).  layers: a list of (colours, covariances), [0] the guide going through DenoiserInputs; neighbours: a list of
+    (ns, [(colours, covariances)]) with the same layers; motions: None, or per neighbour an (H, W, 2) field or None; features (with neighbour_features, one per
+    neighbour, floors, threshold and optional variances for every frame): the feature gate.  For the refusals denoise() owes: moment_selection=False leaves
+    setMomentSelection off, the first plain_neighbours neighbours are added by addNeighbourFrame, the last neighbour gets drop_layers layers fewer, devices:
+    setDevices.  Returns (ok, [output per layer])"""
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    p = lambda a: None if a is None else _fp(a)
+    ns = f32(ns)
+    H, W = ns.shape[0], ns.shape[1]
+    L, F = len(layers), len(neighbours)
+    cols, covs = f32(np.stack([c for c, _ in layers])), f32(np.stack([v for _, v in layers]))
+    nb_cols = f32(np.stack([c for _, lay in neighbours for c, _ in lay])) if F else np.zeros((1, H, W, 3), np.float32)
+    nb_covs = f32(np.stack([v for _, lay in neighbours for _, v in lay])) if F else np.zeros((1, H, W, 6), np.float32)
+    nb_ns = f32(np.stack([np.asarray(n, np.float32).reshape(H, W, 1) for n, _ in neighbours])) if F else np.zeros((1, H, W, 1), np.float32)
+    outs = np.zeros((L, H, W, 3), np.float32)
+    fields, flags = _motion_stack(motions, F, H, W) if motions is not None else (None, None)
+    feat = var = nfeat = nvar = None
+    fl = f32(np.asarray(floors, np.float32).reshape(-1))
+    if features is not None:
+        feat, var = f32(features), None if variances is None else f32(variances)
+        nfeat = f32(np.stack([f32(x) for x in neighbour_features])) if neighbour_features else None
+        nvar = f32(np.stack([f32(x) for x in neighbour_variances])) if neighbour_variances else None
+        if F and (nfeat is None or nfeat.shape != (F,) + feat.shape or (nvar is not None and nvar.shape != nfeat.shape)):
+            raise ValueError("one feature image (and one variance image, or none at all) per neighbour expected, shaped like the frame's")
+    devs = (C.c_int * len(devices))(*devices) if devices else None
+    rc = lib().bcdcore_denoise_temporal_moments(_fp(cols), _fp(covs), _fp(ns), _fp(nb_cols), _fp(nb_covs), _fp(nb_ns), F, L, p(fields), flags, W, H, int(nscales),
+                                                C.c_float(tau), b, C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed), C.c_float(var_floor), p(feat),
+                                                p(var), feat.shape[2] if feat is not None else 0, _fp(fl) if fl.size else None, int(fl.size), C.c_float(threshold), p(nfeat),
+                                                p(nvar), 1 if moment_selection else 0, int(plain_neighbours), int(drop_layers), devs, len(devices) if devices else 0, _fp(outs))
+    return rc != 0, [outs[k] for k in range(L)]
+
+
 def denoise_moments(layers, ns, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, zero_bad=False, prefilter_factor=0.0,
                     prefilter_layers=False, var_floor=1e-8, devices=None):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with setMomentSelection(true, var_floor): no histogram image; layers[0] = (colours, covariances) is the

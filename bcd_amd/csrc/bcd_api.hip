@@ -610,6 +610,12 @@ int guide_gate_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const 
 
 int distance_timing_events(bcd_hip_ctx *ctx, Work &wk, hipEvent_t *e0, hipEvent_t *e1) { return timing_events(ctx, wk, e0, e1); }
 
+int moments_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixcov, int W, int H, int w, int b, float tau, float var_floor, uint32_t *d_mask,
+                  int32_t *d_count)
+{
+    return similarity_moments(ctx, wk, d_colors, d_pixcov, W, H, w, b, tau, var_floor, d_mask, d_count);
+}
+
 int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state,
                   const float *const *pixcov, float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral,
                   const KeptLists *kept)

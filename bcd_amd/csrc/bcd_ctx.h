@@ -327,6 +327,9 @@ inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
 int guide_gate_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const float *d_variances, int W, int H, int w, int b, uint32_t *d_mask, int32_t *d_count);
 // an event pair for the distance kernel of a pass outside bcd_api.hip (bcd_hip_kernel_time); both null once the pool is used up
 int distance_timing_events(bcd_hip_ctx *ctx, Work &wk, hipEvent_t *e0, hipEvent_t *e1);
+// similarity_moments for a caller outside bcd_api.hip: the in-frame masks and counts of the moment selection on wk.stream (d_pixcov complete on that stream)
+int moments_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixcov, int W, int H, int w, int b, float tau, float var_floor, uint32_t *d_mask,
+                  int32_t *d_count);
 
 // do the byte ranges [a, a + na) and [b, b + nb) share a byte?  The one overlap predicate of the argument checks
 inline bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb)
@@ -341,7 +344,9 @@ void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
 bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const void *ns, const void *hist, const void *cov, size_t npix, int D);
 // what the selection of a scale reads of one frame: sample counts and histograms at this level; valid: null, or the validity bytes of a warped neighbour
 // feat, var: null, or -- in a bcd_hip_denoise_temporal_guided call -- the frame's feature and variance images at this level (var null: no variances)
-struct TemporalSelFrame { const float *ns, *hist; const uint8_t *valid; const float *feat = nullptr, *var = nullptr; };
+// col, pixcov: null, or -- in a bcd_hip_denoise_temporal_moments call ("Moments") -- the guide layer's colours and per-pixel covariances at this level; hist is
+// null then.  pixcov is what per_pixel_cov() produces: temporal_select enqueues it ahead of the in-frame pass in that mode
+struct TemporalSelFrame { const float *ns, *hist; const uint8_t *valid; const float *feat = nullptr, *var = nullptr; const float *col = nullptr, *pixcov = nullptr; };
 // with a guided temporal call in progress (temporal_guide_begin), the feature images of frame f at level `scale`; else nothing
 inline void temporal_guide_level(const bcd_hip_ctx *ctx, int f, int scale, TemporalSelFrame *sel)
 {
@@ -354,6 +359,8 @@ struct TemporalPath { int32_t path = 0, borderline = 0; }; // of the in-frame pa
 // the count sum, then the marking (wk.state).  per_pixel_cov() enqueues the caller's per-pixel covariances between stage events 0 and 1.
 // Guide mode (frames[0].feat given, "Features"): the in-frame masks pass guide_gate_masks behind bcd_hip_similarity_masks, and every neighbour's cross masks
 // are ANDed with its cross feature mask (k_pairdist_guide_cross into the plane buffers, k_masks_cross with tau_g into wk.gate_mask) ahead of the count sum.
+// Moments mode (ctx->moments.on, "Moments"): per_pixel_cov() comes first, the in-frame masks come from similarity_moments on frames[0].col / .pixcov (path 3)
+// and every cross pass from the moment cross launchers on frames[f].col / .pixcov; no histogram is read.
 int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
                     const std::function<int()> &per_pixel_cov, TemporalPath *path);
 // the masks temporal_select left for frame f

@@ -63,6 +63,14 @@ int bcd_pairdist_guide_cross_band(int F, int has_var, int b); // displacement li
 hipError_t bcd_launch_pairdist_guide_cross(const float *featA, const float *varA, const float *featB, const float *varB, int F, const float *floors, int W, int H,
                                            int b, float *T, uint8_t *Cn, hipStream_t st);
 
+// ---- k_similarity_moments_cross.hip
+int bcd_pairdist_moments_cross_band(int b);              // displacement lines per staging; 0: a search radius the kernel does not serve
+int bcd_masks_moments_cross_fused_applies(int w, int b); // the form without planes: patch radius 1, search radius 1 .. 6
+hipError_t bcd_launch_pairdist_moments_cross(const float *colA, const float *pixcovA, const float *colB, const float *pixcovB, int W, int H, int b, float var_floor,
+                                             float *T, uint8_t *Cn, hipStream_t st);
+hipError_t bcd_launch_masks_moments_cross_fused(const float *colA, const float *pixcovA, const float *colB, const float *pixcovB, int W, int H, int b, float tau,
+                                                float var_floor, uint32_t *mask, int32_t *count, hipStream_t st);
+
 // ---- k_similarity_fast.hip
 int bcd_pairdist_rw_supported(int D);
 int bcd_pairdist_rw_tile_lines();

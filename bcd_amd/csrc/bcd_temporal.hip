@@ -7,12 +7,16 @@
 // The feature gate of the cross-frame selection (section 16, "Features") is here as well: temporal_select's guide mode, the set-up of a guided temporal call
 // (temporal_guide_begin) and the stages bcd_hip_similarity_masks_guide_cross, bcd_hip_window_distances_guide_cross, bcd_hip_warp_features; the kernels are in
 // k_similarity_guide_cross.hip and k_warp.hip.
+// The cross-frame selection from means and covariances (section 16, "Moments") is temporal_select's moments mode; its stages
+// bcd_hip_similarity_masks_moments_cross and bcd_hip_window_distances_moments_cross are here, the kernels in k_similarity_moments_cross.hip, the frame calls
+// bcd_hip_denoise_temporal_moments[_host] in bcd_temporal_layers.hip.
 // What the layered calls (bcd_temporal_layers.hip) share with the frame calls is defined here and declared in bcd_ctx.h: the selection stage of a scale
 // (temporal_select) and its stats tail (temporal_stats_tail), the lists and the chain of full estimates of the estimate stage (temporal_lists,
 // temporal_full_chain), the motion set-up of a neighbour (temporal_warp_neighbour).
 #include "bcd_ctx.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -61,6 +65,50 @@ int temporal_guide_gate(bcd_hip_ctx *ctx, Work &wk, const TemporalSelFrame &fram
     HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, ctx->guide.tau, (uint32_t *)wk.gate_mask.p, (int32_t *)wk.gate_nsim.p,
                                        wk.stream));
     HIPCHK(ctx, bcd_launch_gate_masks(d_mask_nb, (const uint32_t *)wk.gate_mask.p, d_count_nb, W, H, b, wk.stream));
+    return BCD_HIP_OK;
+}
+
+// "Moments": the form of the moment cross pass that `form` asks for (0: the production choice) at this geometry -- 1 the planes, 2 the kernel without planes.
+// The production choice is the fused kernel where it applies (w = 1, b <= 6: the only geometry of the frame calls) and the planes elsewhere: at 1080p, b = 6 the
+// cross stage of one neighbour takes 2.32 ms fused against 3.40 ms as planes + k_masks_cross (docs/EXPERIMENTS.md section 27)
+constexpr int MOMENTS_CROSS_PRODUCTION_FORM = 2;
+int moments_cross_form(int form, int w, int b)
+{
+    if (form == 0) form = MOMENTS_CROSS_PRODUCTION_FORM;
+    return form == 2 && !bcd_masks_moments_cross_fused_applies(w, b) ? 1 : form;
+}
+
+// "Moments": the T / C planes of every displacement between the guide layers of the frame and of one neighbour, in the same plane buffers; the kernel is timed
+// like the other distance kernels (bcd_hip_kernel_time)
+int temporal_moments_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_col, const float *d_pixcov, const float *d_col_nb, const float *d_pixcov_nb, int W, int H,
+                                  int b, float var_floor)
+{
+    const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
+    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
+    wk.planes.ready = false; // (the workspace's planes are overwritten)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RCCHK(distance_timing_events(ctx, wk, &e0, &e1));
+    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    HIPCHK(ctx, bcd_launch_pairdist_moments_cross(d_col, d_pixcov, d_col_nb, d_pixcov_nb, W, H, b, var_floor, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
+    if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
+    return BCD_HIP_OK;
+}
+
+// "Moments": the cross masks and counts of one neighbour on wk.stream, in the form `form` (1 or 2, from moments_cross_form)
+int temporal_moments_cross_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_col, const float *d_pixcov, const float *d_col_nb, const float *d_pixcov_nb, int W, int H,
+                                 int w, int b, float tau, float var_floor, int form, uint32_t *d_mask_nb, int32_t *d_count_nb)
+{
+    if (form == 2) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        RCCHK(distance_timing_events(ctx, wk, &e0, &e1));
+        if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+        HIPCHK(ctx, bcd_launch_masks_moments_cross_fused(d_col, d_pixcov, d_col_nb, d_pixcov_nb, W, H, b, tau, var_floor, d_mask_nb, d_count_nb, wk.stream));
+        if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
+        return BCD_HIP_OK;
+    }
+    RCCHK(temporal_moments_cross_planes(ctx, wk, d_col, d_pixcov, d_col_nb, d_pixcov_nb, W, H, b, var_floor));
+    HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, d_mask_nb, d_count_nb, wk.stream));
     return BCD_HIP_OK;
 }
 
@@ -294,17 +342,30 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
     const bool prof = ctx->profiling;
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[0], wk.stream));
     // S_0: today's set, by the code that computes it today (its verdict and re-runs are inside the call); the cross passes follow it, ahead of the marking
-    RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
-    int32_t capacity = 0;
-    RCCHK(bcd_hip_similarity_last_path(ctx, &path->path, &path->borderline, &capacity));
+    const bool moments = ctx->moments.on; // ("Moments": the per-pixel covariances first, S_0 by similarity_moments, every S_j by the moment cross pass)
+    const float eps = ctx->moments.var_floor;
+    if (moments) {
+        RCCHK(per_pixel_cov());
+        RCCHK(moments_masks(ctx, wk, frames[0].col, frames[0].pixcov, W, H, w, b, tau, eps, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
+        path->path = 3; path->borderline = 0;
+    } else {
+        RCCHK(bcd_hip_similarity_masks(ctx, frames[0].hist, frames[0].ns, W, H, D, w, b, tau, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
+        int32_t capacity = 0;
+        RCCHK(bcd_hip_similarity_last_path(ctx, &path->path, &path->borderline, &capacity));
+    }
     const bool guided = frames[0].feat != nullptr; // ("Features": S_0 is gated as a guided scale gates it, every S_j by its cross feature mask)
     if (guided) RCCHK(guide_gate_masks(ctx, wk, frames[0].feat, frames[0].var, W, H, w, b, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
-    RCCHK(per_pixel_cov());
+    if (!moments) RCCHK(per_pixel_cov());
     for (int f = 1; f < nf; ++f) {
         uint32_t *mask = (uint32_t *)tp.mask[f].p;
         int32_t *count = (int32_t *)tp.count_nb.p;
-        RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
-        HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, mask, count, wk.stream));
+        if (moments) {
+            RCCHK(temporal_moments_cross_masks(ctx, wk, frames[0].col, frames[0].pixcov, frames[f].col, frames[f].pixcov, W, H, w, b, tau, eps, moments_cross_form(0, w, b),
+                                               mask, count));
+        } else {
+            RCCHK(temporal_cross_planes(ctx, wk, frames[0].hist, frames[0].ns, frames[f].hist, frames[f].ns, W, H, D, b));
+            HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, mask, count, wk.stream));
+        }
         if (frames[f].valid) RCCHK(temporal_gate(ctx, wk, frames[f].valid, W, H, w, b, mask, count)); // (a warped neighbour)
         if (guided) RCCHK(temporal_guide_gate(ctx, wk, frames[0], frames[f], W, H, w, b, mask, count));
         HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, count, (int64_t)npix, wk.stream));
@@ -706,6 +767,50 @@ int bcd_hip_window_distances_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *
     const int n = (2 * b + 1) * (2 * b + 1);
     RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
     RCCHK(temporal_guide_cross_planes(ctx, wk, guide->features, guide->variances, neighbour->features, neighbour->variances, guide->nb_channels, guide->floors, W, H, b));
+    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+// ---- "Moments": the stage calls of the cross-frame moment selection; what they accept is what bcd_hip_similarity_masks_moments accepts
+static int check_moments_cross_stage(bcd_hip_ctx *ctx, int W, int H, int w, int b, float var_floor)
+{
+    if (!(var_floor >= 0.f) || !std::isfinite(var_floor)) return bad(ctx, "the variance floor must be finite and not negative");
+    return check_cross_stage(ctx, W, H, 1, w, b);
+}
+
+int bcd_hip_similarity_masks_moments_cross(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, const float *d_colors_nb, const float *d_pixel_cov_nb, int W,
+                                           int H, int w, int b, float tau, float var_floor, int form, uint32_t *d_mask_nb, int32_t *d_count_nb)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_colors || !d_pixel_cov || !d_colors_nb || !d_pixel_cov_nb || !d_mask_nb || !d_count_nb) return bad(ctx, "bad argument");
+    if (form < 0 || form > 2) return bad(ctx, "the form of the moment cross pass must be 0 (production), 1 (planes) or 2 (fused)");
+    RCCHK(check_moments_cross_stage(ctx, W, H, w, b, var_floor));
+    if (form == 2 && !bcd_masks_moments_cross_fused_applies(w, b)) {
+        set_err(ctx, "the fused moment cross pass serves patch radius 1 and search radius 1 to 6");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    RCCHK(temporal_moments_cross_masks(ctx, wk, d_colors, d_pixel_cov, d_colors_nb, d_pixel_cov_nb, W, H, w, b, tau, var_floor, moments_cross_form(form, w, b), d_mask_nb,
+                                       d_count_nb));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_window_distances_moments_cross(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, const float *d_colors_nb, const float *d_pixel_cov_nb, int W,
+                                           int H, int w, int b, float var_floor, int line, int col, float *h_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_colors || !d_pixel_cov || !d_colors_nb || !d_pixel_cov_nb || !h_out) return bad(ctx, "bad argument");
+    RCCHK(check_moments_cross_stage(ctx, W, H, w, b, var_floor));
+    if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
+    DEVICE_GUARD(ctx);
+    Work &wk = ctx->main;
+    const int n = (2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
+    RCCHK(temporal_moments_cross_planes(ctx, wk, d_colors, d_pixel_cov, d_colors_nb, d_pixel_cov_nb, W, H, b, var_floor));
     HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
     HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));

@@ -10,9 +10,12 @@
 // warped (temporal_warp_neighbour, with its further layers) before its pyramid is built, its cross masks pass the gate at every scale.
 // bcd_hip_denoise_temporal_guided[_host] (section 16, "Features") are layers_run / layers_host_run with the guide mode of temporal_select switched on by
 // temporal_guide_begin (bcd_temporal.hip): the feature pyramids of every frame, the warped features of a neighbour with a field.
+// bcd_hip_denoise_temporal_moments[_host] (section 16, "Moments") are the same drivers with ctx->moments set: no histogram image is read, uploaded, warped or
+// reduced, temporal_select selects from layer 0's colours and per-pixel covariances, and a single layer takes the layered path too.
 #include "bcd_ctx.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -106,6 +109,7 @@ int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, in
         RCCHK(ensure(ctx, tp.lay_pixcov[f], (size_t)L * npix * 6 * sizeof(float)));
         sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
         temporal_guide_level(ctx, f, scale, &sel[f]);
+        if (ctx->moments.on) { sel[f].col = frames[f].col[0]; sel[f].pixcov = (const float *)tp.lay_pixcov[f].p; } // ("Moments": the guide layer is layer 0)
     }
     TemporalPath path;
     RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int { // per frame the per-pixel covariances of its layers: one launch; it also clears the layers' sums
@@ -141,14 +145,15 @@ int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, in
 }
 
 // the refusals of the two frame calls, before any device work
+// (no_hist: a call of the moment selection -- there are no histogram images, `hist`, D and the neighbours' d_histograms are not looked at)
 int check_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_hip_frame_layers *nb, int n, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
-               const bcd_hip_layer *layers, int L)
+               const bcd_hip_layer *layers, int L, bool no_hist = false)
 {
     if (n < 0 || n > BCD_HIP_MAX_NEIGHBOURS) return bad(ctx, "the number of neighbour frames must be between 0 and 4 (BCD_HIP_MAX_NEIGHBOURS)");
-    RCCHK(check_layers_call(ctx, ns, hist, W, H, D, nb_scales, prm, layers, L)); // (null images, the number of layers, the parameters, the scales, the frame's own overlaps)
+    RCCHK(check_layers_call(ctx, ns, hist, W, H, D, nb_scales, prm, layers, L, no_hist)); // (null images, the number of layers, the parameters, the scales, the frame's own overlaps)
     if (n > 0 && !nb) return bad(ctx, "null neighbour list");
     for (int f = 0; f < n; ++f) {
-        if (!nb[f].d_nsamples || !nb[f].d_histograms) return bad(ctx, "null image pointer in a neighbour frame");
+        if (!nb[f].d_nsamples || (!nb[f].d_histograms && !no_hist)) return bad(ctx, "null image pointer in a neighbour frame");
         if (!nb[f].layers) return bad(ctx, "null layer list in a neighbour frame");
         if (nb[f].reserved) return bad(ctx, "the reserved pointer of a neighbour frame must be NULL");
         for (int k = 0; k < L; ++k)
@@ -162,12 +167,17 @@ int check_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_h
     for (int k = 0; k < L; ++k)
         for (int f = 0; f < n; ++f)
             for (int j = 0; j < L; ++j) // (the neighbour's sample counts and histograms are looked at with each of its layers)
-                if (overlaps_frame_images(layers[k].d_out, no, nb[f].layers[j].d_colors, nb[f].d_nsamples, nb[f].d_histograms, nb[f].layers[j].d_covariances, npix, D))
+                if (overlaps_frame_images(layers[k].d_out, no, nb[f].layers[j].d_colors, nb[f].d_nsamples, no_hist ? nullptr : nb[f].d_histograms,
+                                          nb[f].layers[j].d_covariances, npix, D))
                     return bad(ctx, "a layer's output overlaps an image of a neighbour frame");
     return BCD_HIP_OK;
 }
 
 } // namespace
+
+static int guided_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, const float *const *h_motion,
+                           int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const bcd_hip_guide *guide,
+                           const bcd_hip_guide_images *neighbour_guides);
 
 extern "C" {
 
@@ -240,8 +250,9 @@ static int single_layer_call(bcd_hip_ctx *ctx, bool host, const float *ns, const
 static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, int W, int H, int D,
                       int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const float *const *motion)
 {
+    const bool moments = ctx->moments.on; // ("Moments": no histogram images, D = 0, at least one neighbour; one layer takes the layered path too)
     if (nb_neighbours == 0) return bcd_hip_denoise_layers(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, layers, nb_layers);
-    if (nb_layers == 1) return single_layer_call(ctx, false, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers[0], motion);
+    if (nb_layers == 1 && !moments) return single_layer_call(ctx, false, d_ns, d_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers[0], motion);
     DEVICE_GUARD(ctx);
     const int nf = nb_neighbours + 1, S = nb_scales, L = nb_layers;
     auto &tp = ctx->temporal;
@@ -255,7 +266,7 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
     ws[0] = W; hs[0] = H;
     for (int f = 0; f < nf; ++f) {
         LevelFrame &l = lv[f];
-        l.ns = f ? neighbours[f - 1].d_nsamples : d_ns; l.hist = f ? neighbours[f - 1].d_histograms : d_hist;
+        l.ns = f ? neighbours[f - 1].d_nsamples : d_ns; l.hist = moments ? nullptr : f ? neighbours[f - 1].d_histograms : d_hist;
         for (int k = 0; k < L; ++k) {
             l.col[k] = f ? neighbours[f - 1].layers[k].d_colors : layers[k].d_colors;
             l.cov[k] = f ? neighbours[f - 1].layers[k].d_covariances : layers[k].d_covariances;
@@ -278,8 +289,8 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
             t.ocol[k - 1] = (float *)lw[0].p + (size_t)(k - 1) * npix * 3; t.ocov[k - 1] = (float *)lw[1].p + (size_t)(k - 1) * npix * 6;
         }
         const float *wp[4];
-        RCCHK(temporal_warp_neighbour(ctx, f, nf, l.col[0], l.ns, l.hist, l.cov[0], motion[f - 1], W, H, D, S, &t, L - 1, valid.data(), wp));
-        l.col[0] = wp[0]; l.ns = wp[1]; l.hist = wp[2]; l.cov[0] = wp[3];
+        RCCHK(temporal_warp_neighbour(ctx, f, nf, l.col[0], l.ns, l.hist, l.cov[0], motion[f - 1], W, H, D, S, L > 1 ? &t : nullptr, L - 1, valid.data(), wp));
+        l.col[0] = wp[0]; l.ns = wp[1]; l.hist = moments ? nullptr : wp[2]; l.cov[0] = wp[3]; // ("Moments": D = 0, nothing of a histogram is gathered)
         for (int k = 1; k < L; ++k) { l.col[k] = t.ocol[k - 1]; l.cov[k] = t.ocov[k - 1]; }
     }
     for (int s = 1; s < S; ++s) {
@@ -291,14 +302,14 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
             DevBuf(&l)[4] = tp.pyr[f][s];
             DevBuf(&ll)[2] = tp.lay_pyr[f][s];
             RCCHK(ensure(ctx, l[1], np * sizeof(float)));
-            RCCHK(ensure(ctx, l[2], np * D * sizeof(float)));
+            if (!moments) RCCHK(ensure(ctx, l[2], np * D * sizeof(float)));
             RCCHK(ensure(ctx, ll[0], (size_t)L * np * 3 * sizeof(float)));
             RCCHK(ensure(ctx, ll[1], (size_t)L * np * 6 * sizeof(float)));
             const LevelFrame &fine = lv[(size_t)(s - 1) * nf + f];
             LevelFrame &coarse = lv[(size_t)s * nf + f];
-            coarse.ns = (const float *)l[1].p; coarse.hist = (const float *)l[2].p;
+            coarse.ns = (const float *)l[1].p; coarse.hist = moments ? nullptr : (const float *)l[2].p; // ("Moments": the pyramids have no histogram level)
             HIPCHK(ctx, bcd_launch_downscale(0, fine.ns, ws[s - 1], hs[s - 1], 1, (float *)l[1].p, st));
-            HIPCHK(ctx, bcd_launch_downscale(0, fine.hist, ws[s - 1], hs[s - 1], D, (float *)l[2].p, st));
+            if (!moments) HIPCHK(ctx, bcd_launch_downscale(0, fine.hist, ws[s - 1], hs[s - 1], D, (float *)l[2].p, st));
             BcdLayerTable t = {};
             for (int k = 0; k < L; ++k) { coarse.col[k] = (const float *)ll[0].p + (size_t)k * np * 3; t.a[k] = fine.col[k]; t.o[k] = (float *)ll[0].p + (size_t)k * np * 3; }
             HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, ws[s - 1], hs[s - 1], st));
@@ -358,7 +369,8 @@ static int layers_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_h
         for (int k = 0; k < L; ++k) hl[k] = { layers[k].d_colors, layers[k].d_covariances, layers[k].d_out };
         return bcd_hip_denoise_layers_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, nullptr, hl, L);
     }
-    if (L == 1) return single_layer_call(ctx, true, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers[0], h_motion);
+    const bool moments = ctx->moments.on; // ("Moments": no histogram image is uploaded)
+    if (L == 1 && !moments) return single_layer_call(ctx, true, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers[0], h_motion);
     DEVICE_GUARD(ctx);
     auto &tp = ctx->temporal;
     const size_t npix = (size_t)W * H, f4 = sizeof(float), bc = npix * 3 * f4, bv = npix * 6 * f4;
@@ -368,18 +380,18 @@ static int layers_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_h
     for (int f = 0; f <= nb_neighbours; ++f) { // whole uploads, no streaming
         const float *ns = f ? neighbours[f - 1].d_nsamples : h_ns, *hist = f ? neighbours[f - 1].d_histograms : h_hist;
         RCCHK(ensure(ctx, tp.host[f][1], npix * f4));
-        RCCHK(ensure(ctx, tp.host[f][2], npix * D * f4));
+        if (!moments) RCCHK(ensure(ctx, tp.host[f][2], npix * D * f4));
         RCCHK(ensure(ctx, tp.lay_host[f][0], (size_t)L * bc));
         RCCHK(ensure(ctx, tp.lay_host[f][1], (size_t)L * bv));
         HIPCHK(ctx, hipMemcpyAsync(tp.host[f][1].p, ns, npix * f4, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(tp.host[f][2].p, hist, npix * D * f4, hipMemcpyHostToDevice, st));
+        if (!moments) HIPCHK(ctx, hipMemcpyAsync(tp.host[f][2].p, hist, npix * D * f4, hipMemcpyHostToDevice, st));
         for (int k = 0; k < L; ++k) {
             float *dc = (float *)tp.lay_host[f][0].p + (size_t)k * npix * 3, *dv = (float *)tp.lay_host[f][1].p + (size_t)k * npix * 6;
             HIPCHK(ctx, hipMemcpyAsync(dc, f ? neighbours[f - 1].layers[k].d_colors : layers[k].d_colors, bc, hipMemcpyHostToDevice, st));
             HIPCHK(ctx, hipMemcpyAsync(dv, f ? neighbours[f - 1].layers[k].d_covariances : layers[k].d_covariances, bv, hipMemcpyHostToDevice, st));
             dl[(size_t)f * L + k] = { dc, dv };
         }
-        dev[f] = { (const float *)tp.host[f][1].p, (const float *)tp.host[f][2].p, &dl[(size_t)f * L], nullptr };
+        dev[f] = { (const float *)tp.host[f][1].p, moments ? nullptr : (const float *)tp.host[f][2].p, &dl[(size_t)f * L], nullptr };
     }
     RCCHK(ensure(ctx, tp.lay_host_out, (size_t)L * bc));
     bcd_hip_layer lay[BCD_HIP_MAX_LAYERS];
@@ -417,9 +429,9 @@ int bcd_hip_denoise_temporal_layers_motion_host(bcd_hip_ctx *ctx, const float *h
 // the refusals of the two guided frame calls with at least one neighbour, before any device work (the pointers are compared as addresses: device or host)
 static int check_guided_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_hip_frame_layers *neighbours, int n, const float *const *motion, int W, int H,
                              int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int L, const bcd_hip_guide *guide,
-                             const bcd_hip_guide_images *ng)
+                             const bcd_hip_guide_images *ng, bool no_hist = false)
 {
-    RCCHK(check_call(ctx, ns, hist, neighbours, n, W, H, D, nb_scales, prm, layers, L));
+    RCCHK(check_call(ctx, ns, hist, neighbours, n, W, H, D, nb_scales, prm, layers, L, no_hist));
     float *outs[ML];
     layer_outs(layers, L, outs);
     if (motion) RCCHK(check_motion_list(ctx, motion, n, W, H, outs, L)); // (a NULL list: nothing is warped)
@@ -449,7 +461,7 @@ int bcd_hip_denoise_temporal_guided(bcd_hip_ctx *ctx, const float *d_ns, const f
                                     const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides)
 {
     if (!ctx) return BCD_HIP_EINVAL;
-    if (!d_hist) return bad(ctx, "the guided temporal call needs histograms: there is no cross-frame selection from means and covariances");
+    if (!d_hist) return bad(ctx, "the guided temporal call needs histograms: the cross-frame selection from means and covariances is bcd_hip_denoise_temporal_moments");
     if (nb_neighbours == 0) return bcd_hip_denoise_guided(ctx, d_ns, d_hist, W, H, D, nb_scales, prm, 0.f, layers, nb_layers, guide, nullptr);
     RCCHK(check_guided_call(ctx, d_ns, d_hist, neighbours, nb_neighbours, d_motion, W, H, D, nb_scales, prm, layers, nb_layers, guide, neighbour_guides));
     int rc;
@@ -470,7 +482,7 @@ int bcd_hip_denoise_temporal_guided_host(bcd_hip_ctx *ctx, const float *h_ns, co
                                          int nb_layers, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides)
 {
     if (!ctx) return BCD_HIP_EINVAL;
-    if (!h_hist) return bad(ctx, "the guided temporal call needs histograms: there is no cross-frame selection from means and covariances");
+    if (!h_hist) return bad(ctx, "the guided temporal call needs histograms: the cross-frame selection from means and covariances is bcd_hip_denoise_temporal_moments");
     if (nb_neighbours == 0) {
         if (!layers) return bad(ctx, "null layer list");
         if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
@@ -479,6 +491,16 @@ int bcd_hip_denoise_temporal_guided_host(bcd_hip_ctx *ctx, const float *h_ns, co
         return bcd_hip_denoise_guided_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, nullptr, 0.f, hl, nb_layers, guide);
     }
     RCCHK(check_guided_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, h_motion, W, H, D, nb_scales, prm, layers, nb_layers, guide, neighbour_guides));
+    return guided_host_run(ctx, h_ns, h_hist, neighbours, nb_neighbours, h_motion, W, H, D, nb_scales, prm, layers, nb_layers, guide, neighbour_guides);
+}
+
+} // extern "C"
+
+// the checked guided host call with at least one neighbour (h_hist NULL and D = 0: a call of the moment selection, ctx->moments set)
+static int guided_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours, const float *const *h_motion,
+                           int W, int H, int D, int nb_scales, const bcd_hip_params *prm, const bcd_hip_layer *layers, int nb_layers, const bcd_hip_guide *guide,
+                           const bcd_hip_guide_images *neighbour_guides)
+{
     const float *const *motion = any_field(h_motion, nb_neighbours) ? h_motion : nullptr;
     int rc;
     {
@@ -506,6 +528,76 @@ int bcd_hip_denoise_temporal_guided_host(bcd_hip_ctx *ctx, const float *h_ns, co
     }
     if (rc == BCD_HIP_OK) rc = layers_host_run(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers, motion);
     temporal_guide_end(ctx);
+    return rc;
+}
+
+// ---- "Moments": the layered motion call, optionally feature-gated, with every selection made from means and covariances -------------
+// the refusals of the two frame calls with at least one neighbour, before any device work (the pointers are compared as addresses: device or host)
+static int check_moments_call(bcd_hip_ctx *ctx, const float *ns, const bcd_hip_frame_layers *neighbours, int n, const float *const *motion, int W, int H, int nb_scales,
+                              const bcd_hip_params *prm, const bcd_hip_layer *layers, int L, const bcd_hip_guide *guide, const bcd_hip_guide_images *ng)
+{
+    if ((guide == nullptr) != (ng == nullptr)) return bad(ctx, "guide and neighbour_guides must both be NULL or both be given");
+    if (guide) return check_guided_call(ctx, ns, nullptr, neighbours, n, motion, W, H, 0, nb_scales, prm, layers, L, guide, ng, true);
+    RCCHK(check_call(ctx, ns, nullptr, neighbours, n, W, H, 0, nb_scales, prm, layers, L, true));
+    float *outs[ML];
+    layer_outs(layers, L, outs);
+    if (motion) RCCHK(check_motion_list(ctx, motion, n, W, H, outs, L)); // (a NULL list: nothing is warped)
+    return BCD_HIP_OK;
+}
+
+// what both frame calls refuse ahead of their delegations
+static int check_moments_head(bcd_hip_ctx *ctx, int nb_neighbours, float var_floor)
+{
+    if (!(var_floor >= 0.f) || !std::isfinite(var_floor)) return bad(ctx, "the variance floor must be finite and not negative");
+    if (nb_neighbours < 0 || nb_neighbours > BCD_HIP_MAX_NEIGHBOURS) return bad(ctx, "the number of neighbour frames must be between 0 and 4 (BCD_HIP_MAX_NEIGHBOURS)");
+    return BCD_HIP_OK;
+}
+
+extern "C" {
+
+int bcd_hip_denoise_temporal_moments(bcd_hip_ctx *ctx, const float *d_ns, const bcd_hip_frame_layers *neighbours, int nb_neighbours, const float *const *d_motion, int W,
+                                     int H, int nb_scales, const bcd_hip_params *prm, float var_floor, const bcd_hip_layer *layers, int nb_layers,
+                                     const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_moments_head(ctx, nb_neighbours, var_floor));
+    if (nb_neighbours == 0)
+        return guide ? bcd_hip_denoise_guided(ctx, d_ns, nullptr, W, H, 0, nb_scales, prm, var_floor, layers, nb_layers, guide, nullptr)
+                     : bcd_hip_denoise_moments(ctx, d_ns, W, H, nb_scales, prm, var_floor, layers, nb_layers, nullptr);
+    RCCHK(check_moments_call(ctx, d_ns, neighbours, nb_neighbours, d_motion, W, H, nb_scales, prm, layers, nb_layers, guide, neighbour_guides));
+    const float *const *motion = any_field(d_motion, nb_neighbours) ? d_motion : nullptr;
+    int rc = BCD_HIP_OK;
+    if (guide) {
+        DEVICE_GUARD(ctx);
+        rc = temporal_guide_begin(ctx, guide, neighbour_guides, nb_neighbours, motion, W, H, nb_scales);
+    }
+    ctx->moments.on = true; ctx->moments.var_floor = var_floor;
+    if (rc == BCD_HIP_OK) rc = layers_run(ctx, d_ns, nullptr, neighbours, nb_neighbours, W, H, 0, nb_scales, prm, layers, nb_layers, motion);
+    ctx->moments.on = false;
+    temporal_guide_end(ctx);
+    return rc;
+}
+
+int bcd_hip_denoise_temporal_moments_host(bcd_hip_ctx *ctx, const float *h_ns, const bcd_hip_frame_layers *neighbours, int nb_neighbours, const float *const *h_motion, int W,
+                                          int H, int nb_scales, const bcd_hip_params *prm, float var_floor, const bcd_hip_layer *layers, int nb_layers,
+                                          const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    RCCHK(check_moments_head(ctx, nb_neighbours, var_floor));
+    if (nb_neighbours == 0) {
+        if (!layers) return bad(ctx, "null layer list");
+        if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+        bcd_hip_host_layer hl[BCD_HIP_MAX_LAYERS];
+        for (int k = 0; k < nb_layers; ++k) hl[k] = { layers[k].d_colors, layers[k].d_covariances, layers[k].d_out };
+        return guide ? bcd_hip_denoise_guided_host(ctx, h_ns, nullptr, W, H, 0, nb_scales, prm, nullptr, var_floor, hl, nb_layers, guide)
+                     : bcd_hip_denoise_moments_host(ctx, h_ns, W, H, nb_scales, prm, nullptr, var_floor, hl, nb_layers);
+    }
+    RCCHK(check_moments_call(ctx, h_ns, neighbours, nb_neighbours, h_motion, W, H, nb_scales, prm, layers, nb_layers, guide, neighbour_guides));
+    ctx->moments.on = true; ctx->moments.var_floor = var_floor;
+    int rc;
+    if (guide) rc = guided_host_run(ctx, h_ns, nullptr, neighbours, nb_neighbours, h_motion, W, H, 0, nb_scales, prm, layers, nb_layers, guide, neighbour_guides);
+    else rc = layers_host_run(ctx, h_ns, nullptr, neighbours, nb_neighbours, W, H, 0, nb_scales, prm, layers, nb_layers, any_field(h_motion, nb_neighbours) ? h_motion : nullptr);
+    ctx->moments.on = false;
     return rc;
 }
 

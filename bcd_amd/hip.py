@@ -996,6 +996,104 @@ class Context:
                                               _dp(valid)))
         return of, ov, valid
 
+    # ---- moments: the cross-frame selection from means and covariances, without histograms ("Moments") ----
+    def similarity_masks_moments_cross(self, col, pixcov, col_nb, pixcov_nb, w, b, tau, var_floor=1e-8, form=0, out=None):
+        """bcd_hip_similarity_masks_moments_cross: the cross masks and counts between the guide layer of a frame -- colours (H, W, 3), per-pixel covariances
+        (H, W, 6) -- and that of a neighbour, in the layouts of similarity_masks_cross.  form: 0 the production choice, 1 planes, 2 fused (w = 1, b <= 6).
+        out: (mask (H, W, words) int32, count (H, W) int32) contiguous device tensors to fill"""
+        torch = self.torch
+        H, W, _ = col.shape
+        if out is None:
+            out = _mask_and_count(H, W, b, col.device)
+        mask, cnt = out
+        if mask.numel() != H * W * (((2 * b + 1) ** 2 + 31) // 32) or cnt.numel() != H * W or mask.dtype != torch.int32 or cnt.dtype != torch.int32:
+            raise ValueError("out must be ((H, W, words) int32, (H, W) int32)")
+        if col_nb.numel() != H * W * 3 or pixcov.numel() != H * W * 6 or pixcov_nb.numel() != H * W * 6:
+            raise ValueError("colours (H, W, 3) and per-pixel covariances (H, W, 6) of one size are expected for both frames")
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(lib().bcd_hip_similarity_masks_moments_cross(self.h, _dp(col), _dp(pixcov), _dp(col_nb), _dp(pixcov_nb), W, H, int(w), int(b), float(tau),
+                                                               float(var_floor), int(form), _dp(mask), _dp(cnt)))
+        return mask, cnt
+
+    def window_distances_moments_cross(self, col, pixcov, col_nb, pixcov_nb, w, b, line, column, var_floor=1e-8):
+        """bcd_hip_window_distances_moments_cross: the (2b+1)^2 cross moment distances of one main pixel of the frame to its window in the neighbour, +inf outside"""
+        import numpy as np
+        H, W, _ = col.shape
+        if col_nb.numel() != H * W * 3 or pixcov.numel() != H * W * 6 or pixcov_nb.numel() != H * W * 6:
+            raise ValueError("colours (H, W, 3) and per-pixel covariances (H, W, 6) of one size are expected for both frames")
+        out = np.empty(((2 * b + 1) ** 2,), np.float32)
+        self.torch.cuda.synchronize(self.device)
+        self._chk(lib().bcd_hip_window_distances_moments_cross(self.h, _dp(col), _dp(pixcov), _dp(col_nb), _dp(pixcov_nb), W, H, int(w), int(b), float(var_floor),
+                                                               int(line), int(column), _fptr(out)))
+        return out
+
+    @staticmethod
+    def _moment_frames_array(neighbours, nl, H, W, ptr, numel):
+        """the bcd_hip_frame_layers array of a list of (ns, [(colours, covariances), ...]) of the frame's size, with NULL histograms"""
+        arr = (FrameLayers * max(len(neighbours), 1))()
+        keep = []
+        for i, (ns, layers) in enumerate(neighbours):
+            layers = list(layers)
+            if len(layers) != nl:
+                raise ValueError("neighbour %d: one layer per layer of the frame expected (%d, not %d)" % (i, nl, len(layers)))
+            if numel(ns) != H * W or any(tuple(c.shape) != (H, W, 3) or tuple(v.shape) != (H, W, 6) for c, v in layers):
+                raise ValueError("neighbour %d: images of the frame's width and height are expected" % i)
+            la = (FrameLayer * max(nl, 1))()
+            for k, (col, cov) in enumerate(layers):
+                la[k].d_colors, la[k].d_covariances = ptr(col), ptr(cov)
+            keep.append(la)
+            arr[i].d_nsamples, arr[i].d_histograms, arr[i].layers = ptr(ns), None, la
+        return arr, keep
+
+    def denoise_temporal_moments(self, ns, layers, neighbours, nscales, prm, var_floor=1e-8, motions=None, features=None, neighbour_features=None, variances=None,
+                                 neighbour_variances=None, floors=(), threshold=1.0, outs=None):
+        """bcd_hip_denoise_temporal_moments: the colour layers `layers` -- (colours, covariances) device tensors that share `ns`, layers[0] the guide layer of the
+        selection -- denoised with similar patches from up to four neighbour frames, each (ns, [(colours, covariances), ...]), every selection made from means and
+        covariances: no histogram anywhere.  motions: None or one (H, W, 2) tensor or None per neighbour; features (with neighbour_features, and variances for every
+        frame or none): the feature gate of denoise_temporal_guided -> the list of outputs"""
+        torch = self.torch
+        H, W = ns.shape[:2]
+        arr, layers, outs = self._layer_array(layers, outs, H, W, ns.device)
+        neighbours = list(neighbours)
+        nb, keep = self._moment_frames_array(neighbours, len(layers), H, W, _dptr, torch.numel)
+        mv = self._motion_array(motions, len(neighbours), H, W, _dptr, torch.numel)
+        g = ng = alive = None
+        if features is not None:
+            if tuple(features.shape[:2]) != (H, W):
+                raise ValueError("features must be %dx%dxF" % (H, W))
+            g, alive = self._guide(features, variances, floors, threshold)
+            ng = self._guide_images_array(neighbour_features if neighbour_features is not None else [], neighbour_variances, len(neighbours), features.shape, _dptr)
+        torch.cuda.synchronize(self.device)
+        self._chk(lib().bcd_hip_denoise_temporal_moments(self.h, _dp(ns), nb, len(neighbours), mv, W, H, int(nscales), C.byref(prm), float(var_floor), arr, len(layers),
+                                                         None if g is None else C.byref(g), ng))
+        del alive, keep
+        return outs
+
+    def denoise_temporal_moments_host(self, ns, layers, neighbours, nscales, prm, var_floor=1e-8, motions=None, features=None, neighbour_features=None, variances=None,
+                                      neighbour_variances=None, floors=(), threshold=1.0):
+        """bcd_hip_denoise_temporal_moments_host on NumPy float32 arrays -> the list of denoised layers (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        ns = as32(ns)
+        H, W = ns.shape[:2]
+        neighbours = [(as32(n), [(as32(c), as32(v)) for c, v in lay]) for n, lay in neighbours]
+        arr, layers, outs = _host_layer_array(layers, H, W, Layer)
+        nb, keep = self._moment_frames_array(neighbours, len(layers), H, W, _hptr, np.size)
+        fields = None if motions is None else [None if m is None else as32(m) for m in motions]
+        mv = self._motion_array(fields, len(neighbours), H, W, _hptr, np.size)
+        g = ng = alive = nfeat = nvar = None
+        if features is not None:
+            g, alive = self._guide(features, variances, floors, threshold, host=True)
+            if tuple(alive[0].shape[:2]) != (H, W):
+                raise ValueError("features must be %dx%dxF" % (H, W))
+            nfeat = [as32(f) for f in (neighbour_features if neighbour_features is not None else [])]
+            nvar = None if neighbour_variances is None else [as32(v) for v in neighbour_variances]
+            ng = self._guide_images_array(nfeat, nvar, len(neighbours), alive[0].shape, _hptr)
+        self._chk(lib().bcd_hip_denoise_temporal_moments_host(self.h, ns.ctypes.data, nb, len(neighbours), mv, W, H, int(nscales), C.byref(prm), float(var_floor), arr,
+                                                              len(layers), None if g is None else C.byref(g), ng))
+        del alive, keep, fields, nfeat, nvar
+        return outs
+
     def denoise_temporal_stages(self, col, ns, hist, cov, neighbours, prm):
         """One scale of the denoising of a frame with similar patches from neighbouring frames of its sequence, composed from the
         stage calls: in-frame masks, cross masks of every neighbour, the marking on the in-frame masks and the total |S|, the estimate over the members of

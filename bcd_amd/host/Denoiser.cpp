@@ -235,16 +235,51 @@ namespace bcd
 			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available over several devices" << endl;
 			return false;
 		}
-		if(!m_neighbourFrames.empty() && m_momentSelection)
+		// neighbour frames under the moment selection (bcd_hip_denoise_temporal_moments_host): every neighbour must have been added by addNeighbourFrameMoments
+		size_t nbOfMomentNeighbours = 0;
+		for(size_t k = 0; k < m_neighbourFrames.size(); ++k)
+			nbOfMomentNeighbours += (k < m_neighbourMoments.size() && m_neighbourMoments[k]) ? 1 : 0;
+		if(nbOfMomentNeighbours > 0 && !m_momentSelection)
 		{
-			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available with the moment selection: there is no cross-frame selection from means and covariances" << endl;
+			cerr << "Aborting denoising: neighbour frames added by addNeighbourFrameMoments need the selection from means and covariances (setMomentSelection(true))" << endl;
 			return false;
 		}
+		if(!m_neighbourFrames.empty() && m_momentSelection && nbOfMomentNeighbours != m_neighbourFrames.size())
+		{
+			cerr << "Aborting denoising: neighbour frames (addNeighbourFrame) are not available with the moment selection: the cross-frame selection from means and covariances takes "
+					"neighbours added by addNeighbourFrameMoments, and every neighbour must be added that way" << endl;
+			return false;
+		}
+		const bool momentNeighbours = m_momentSelection && !m_neighbourFrames.empty();
 		if(!inputsOutputsAreOk() || !layersAreOk() || !guideIsOk())
 			return false;
 		m_width = m_inputs.m_pColors->getWidth();
 		m_height = m_inputs.m_pColors->getHeight();
 		m_nbOfPixels = m_width * m_height;
+		if(momentNeighbours)
+		{	// the size checks of the moment neighbours, before any device is asked for
+			auto fits = [&](const DeepImage<float>* i_pImage, int i_depth)
+			{
+				return i_pImage && i_pImage->getWidth() == m_width && i_pImage->getHeight() == m_height && i_pImage->getDepth() == i_depth;
+			};
+			const size_t nbOfLayers = m_layers.size();
+			bool ok = !(m_prefilterThresholdStDevFactor > 0.f) && m_neighbourLayers.size() == m_neighbourFrames.size() && m_neighbourMotion.size() == m_neighbourFrames.size();
+			for(size_t k = 0; ok && k < m_neighbourFrames.size(); ++k)
+			{
+				const DenoiserInputs& f = m_neighbourFrames[k];
+				ok = fits(f.m_pColors, 3) && fits(f.m_pNbOfSamples, 1) && fits(f.m_pSampleCovariances, 6) && m_neighbourLayers[k].size() == nbOfLayers;
+				for(size_t j = 0; ok && j < nbOfLayers; ++j)
+					ok = fits(m_neighbourLayers[k][j].m_pColors, 3) && fits(m_neighbourLayers[k][j].m_pSampleCovariances, 6);
+				ok = ok && (!m_neighbourMotion[k] || fits(m_neighbourMotion[k], 2));
+			}
+			if(!ok)
+			{
+				cerr << "Aborting denoising: a neighbour frame of the moment selection (addNeighbourFrameMoments) needs colours, sample counts and covariances in the frame's size "
+						"and, beside added layers, exactly one layer (addNeighbourFrameLayer) per added layer in that size, a motion field (setNeighbourMotion) has 2 channels in "
+						"that size; neighbour frames do not combine with the spike prefilter" << endl;
+				return false;
+			}
+		}
 		// src/core/Denoiser.cpp:99-110,241-265: m_useCuda is a REQUEST in the reference -- "true" is declined with a note when the GPU path cannot serve
 		// the call (no device, patch radius != 1) and the other path runs.  This library has one path, the HIP device, so it declines the opposite
 		// request the same way: m_useCuda = false (--use-cuda 0) is answered with a note on cout and the device result, which is the CPU path's
@@ -351,7 +386,61 @@ namespace bcd
 			bcd_hip_host_options opt;
 			opt.spike_factor = m_prefilterThresholdStDevFactor;
 			opt.zero_bad_values = m_zeroBadOutputValues ? 1 : 0;
-			if(m_pGuideFeatures && m_neighbourFrames.empty())
+			if(momentNeighbours)
+			{	// neighbour frames lend their means and covariances: no histogram anywhere; the primary images are layer 0 of every frame (sizes checked above)
+				const size_t nbOfLayers = m_layers.size(), nbOfNeighbours = m_neighbourFrames.size();
+				std::vector<bcd_hip_frame_layer> frameLayers(nbOfNeighbours * (nbOfLayers + 1));
+				std::vector<bcd_hip_frame_layers> layeredFrames(nbOfNeighbours);
+				std::vector<const float*> motion(nbOfNeighbours, nullptr);
+				bool anyMotion = false;
+				for(size_t k = 0; k < nbOfNeighbours; ++k)
+				{
+					const DenoiserInputs& f = m_neighbourFrames[k];
+					bcd_hip_frame_layer* pLayers = &frameLayers[k * (nbOfLayers + 1)];
+					pLayers[0] = { f.m_pColors->getDataPtr(), f.m_pSampleCovariances->getDataPtr() };
+					for(size_t j = 0; j < nbOfLayers; ++j)
+						pLayers[j + 1] = { m_neighbourLayers[k][j].m_pColors->getDataPtr(), m_neighbourLayers[k][j].m_pSampleCovariances->getDataPtr() };
+					layeredFrames[k] = { f.m_pNbOfSamples->getDataPtr(), nullptr, pLayers, nullptr };
+					if(m_neighbourMotion[k])
+					{
+						motion[k] = m_neighbourMotion[k]->getDataPtr();
+						anyMotion = true;
+					}
+				}
+				std::vector<bcd_hip_layer> layers(nbOfLayers + 1);
+				layers[0] = { pIn[0], pIn[3], result.getDataPtr() };
+				for(size_t k = 0; k < nbOfLayers; ++k)
+				{
+					layerResults[k].resize(m_width, m_height, 3);
+					layers[k + 1] = { m_layers[k].m_pColors->getDataPtr(), m_layers[k].m_pSampleCovariances->getDataPtr(), layerResults[k].getDataPtr() };
+				}
+				bcd_hip_guide guide;
+				std::vector<bcd_hip_guide_images> neighbourGuides(nbOfNeighbours);
+				if(m_pGuideFeatures)
+				{	// (guideIsOk has checked the neighbours' buffers)
+					guide.features = m_pGuideFeatures->getDataPtr();
+					guide.variances = m_pGuideVariances ? m_pGuideVariances->getDataPtr() : nullptr;
+					guide.nb_channels = m_pGuideFeatures->getDepth();
+					guide.floors = m_guideFloors.data();
+					guide.threshold = m_guideThreshold;
+					for(size_t k = 0; k < nbOfNeighbours; ++k)
+						neighbourGuides[k] = { m_neighbourGuides[k].m_pFeatures->getDataPtr(), m_neighbourGuides[k].m_pVariances ? m_neighbourGuides[k].m_pVariances->getDataPtr() : nullptr };
+				}
+				rc = bcd_hip_denoise_temporal_moments_host(rSlot.m_pCtx, pIn[1], layeredFrames.data(), int(nbOfNeighbours), anyMotion ? motion.data() : nullptr, m_width, m_height,
+						i_nbOfScales, &prm, m_momentVarianceFloor, layers.data(), int(layers.size()), m_pGuideFeatures ? &guide : nullptr,
+						m_pGuideFeatures ? neighbourGuides.data() : nullptr);
+				if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
+				{
+					for(size_t k = 0; k <= nbOfLayers; ++k)
+					{
+						float* p = k == 0 ? result.getDataPtr() : layerResults[k - 1].getDataPtr();
+						for(size_t i = 0, n = size_t(m_nbOfPixels) * 3; i < n; ++i)
+							if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
+								p[i] = 0.f;
+					}
+				}
+			}
+			else if(m_pGuideFeatures && m_neighbourFrames.empty())
 			{	// the selection gated by the feature buffers: with histograms or, under setMomentSelection, without; the primary images are layer 0
 				std::vector<bcd_hip_host_layer> layers(m_layers.size() + 1);
 				layers[0].h_colors = pIn[0]; layers[0].h_covariances = pIn[3]; layers[0].h_out = result.getDataPtr();
@@ -566,6 +655,7 @@ namespace bcd
 		engine.setNeighbourFrameLayers(m_neighbourLayers);
 		engine.setNeighbourMotions(m_neighbourMotion);
 		engine.setNeighbourGuides(m_neighbourGuides);
+		engine.setNeighbourMomentFlags(m_neighbourMoments);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);

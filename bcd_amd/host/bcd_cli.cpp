@@ -7,6 +7,7 @@
 // --layer <color.exr> <cov.exr> <out.exr> (repeatable) denoises a further colour layer with the filter of the -i image (one selection of similar patches for all).
 // --neighbour-layer <color.exr> <cov.exr> hands the most recent --neighbour the matching layer (the k-th pairs with the k-th --layer).
 // --neighbour-motion <mv.exr> hands the most recent --neighbour its motion field ((dx, dy) in the first two channels).
+// --neighbour-nsamples <file|n> hands the most recent --neighbour its sample counts under --moment-selection, where no <frame>_hist.exr is loaded.
 // --neighbour-features <f.exr> / --neighbour-feature-variances <v.exr> hand the most recent --neighbour its feature buffers: with --features the gate covers
 // the search in the neighbours too (every neighbour then needs them).
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
@@ -52,7 +53,7 @@ namespace
 		std::vector<int> m_devices = std::vector<int>(1, 0);
 		struct Layer { string m_colorPath, m_covariancePath, m_outputPath; Deepimf m_colorImage, m_covarianceImage; };
 		struct NeighbourLayer { string m_colorPath, m_covariancePath; Deepimf m_colorImage, m_covarianceImage; };
-		struct Neighbour { string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ string m_motionPath; Deepimf m_motionImage; /* --neighbour-motion */ string m_featurePath, m_featureVariancePath; Deepimf m_featureImage, m_featureVarianceImage; /* --neighbour-features, --neighbour-feature-variances */ };
+		struct Neighbour { string m_nbOfSamplesArgument; /* --neighbour-nsamples */ string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ string m_motionPath; Deepimf m_motionImage; /* --neighbour-motion */ string m_featurePath, m_featureVariancePath; Deepimf m_featureImage, m_featureVarianceImage; /* --neighbour-features, --neighbour-feature-variances */ };
 		std::vector<Neighbour> m_neighbours; // --neighbour, in command-line order
 		std::vector<Layer> m_layers; // --layer, in command-line order
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
@@ -80,6 +81,9 @@ namespace
 		cout << "Optional arguments list:" << endl;
 		cout << "    -a <file>            The file path to the .bcd.json file containing arguments for the program" << endl;
 		cout << "    --neighbour <frame>  A neighbouring frame of the sequence that lends its statistics (repeatable, at most 4; expects <frame>_hist.exr / <frame>_cov.exr beside it)" << endl;
+		cout << "    --neighbour-nsamples <file|n>" << endl;
+		cout << "                         with --moment-selection (no <frame>_hist.exr is loaded then): the sample counts of the most recent --neighbour, a" << endl;
+		cout << "                         one-channel EXR image or one number for every pixel; without it a numeric --nsamples serves every neighbour" << endl;
 		cout << "    --neighbour-motion <mv.exr>" << endl;
 		cout << "                         the motion field of the most recent --neighbour: pixel (x, y) of the frame shows what pixel (x + dx, y + dy) of that" << endl;
 		cout << "                         neighbour shows, (dx, dy) in the first two channels, rounded to whole pixels; NaN marks a disoccluded pixel" << endl;
@@ -166,11 +170,16 @@ namespace
 				rNb.m_colorPath = argv[++i];
 				if(rNb.m_colorPath.length() <= 4) { cout << "ERROR in program arguments: '" << rNb.m_colorPath << "' is no .exr file name" << endl; return false; }
 				const string stem = rNb.m_colorPath.substr(0, rNb.m_colorPath.length() - 4);
-				Deepimf histAndNbOfSamplesImage;
+				// (its histograms and sample counts are loaded once the whole command line is read: under --moment-selection there is no <frame>_hist.exr)
 				if(!ImageIO::loadEXR(rNb.m_colorImage, rNb.m_colorPath.c_str())) { cout << "ERROR in program arguments: couldn't load neighbour color image file '" << rNb.m_colorPath << "'" << endl; return false; }
-				if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamplesImage, (stem + "_hist.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour histogram image file '" << stem << "_hist.exr'" << endl; return false; }
-				Utils::separateNbOfSamplesFromHistogram(rNb.m_histogramImage, rNb.m_nbOfSamplesImage, histAndNbOfSamplesImage);
 				if(!ImageIO::loadMultiChannelsEXR(rNb.m_covarianceImage, (stem + "_cov.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour covariance matrix image file '" << stem << "_cov.exr'" << endl; return false; }
+				continue;
+			}
+			if(flag == "--neighbour-nsamples")
+			{	// with --moment-selection: the sample counts of the most recent --neighbour, a one-channel EXR image or one number for every pixel
+				if(i + 1 >= argc) { cout << "ERROR in program arguments: expecting <file|n> after --neighbour-nsamples" << endl; return false; }
+				if(a.m_neighbours.empty()) { cout << "ERROR in program arguments: --neighbour-nsamples follows the --neighbour it belongs to" << endl; return false; }
+				a.m_neighbours.back().m_nbOfSamplesArgument = argv[++i];
 				continue;
 			}
 			if(flag == "--neighbour-motion")
@@ -459,6 +468,41 @@ namespace
 			a.m_histogramImage.clearAndFreeMemory();
 			missingHist = false;
 		}
+		for(ProgramArguments::Neighbour& rNb : a.m_neighbours)
+		{	// the sample counts (and, without --moment-selection, the histograms) of every neighbour; nothing has touched a device yet
+			const string stem = rNb.m_colorPath.substr(0, rNb.m_colorPath.length() - 4);
+			if(!a.m_momentSelection)
+			{
+				if(!rNb.m_nbOfSamplesArgument.empty()) { cout << "ERROR in program arguments: --neighbour-nsamples goes with --moment-selection" << endl; return false; }
+				Deepimf histAndNbOfSamplesImage;
+				if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamplesImage, (stem + "_hist.exr").c_str())) { cout << "ERROR in program arguments: couldn't load neighbour histogram image file '" << stem << "_hist.exr'" << endl; return false; }
+				Utils::separateNbOfSamplesFromHistogram(rNb.m_histogramImage, rNb.m_nbOfSamplesImage, histAndNbOfSamplesImage);
+				continue;
+			}
+			// --moment-selection: no <frame>_hist.exr is loaded; --neighbour-nsamples of this neighbour, failing that a numeric --nsamples
+			char* pEnd = nullptr;
+			strtof(nbOfSamplesArgument.c_str(), &pEnd);
+			const bool numericFrameCount = !nbOfSamplesArgument.empty() && pEnd != nbOfSamplesArgument.c_str() && *pEnd == '\0';
+			const string& rArgument = rNb.m_nbOfSamplesArgument.empty() && numericFrameCount ? nbOfSamplesArgument : rNb.m_nbOfSamplesArgument;
+			if(rArgument.empty())
+			{
+				cout << "ERROR in program arguments: with --moment-selection neighbour '" << rNb.m_colorPath << "' needs its sample counts: --neighbour-nsamples <file|n> after its "
+						"--neighbour, or a numeric --nsamples for every frame" << endl;
+				return false;
+			}
+			const float count = strtof(rArgument.c_str(), &pEnd);
+			if(pEnd != rArgument.c_str() && *pEnd == '\0')
+			{
+				if(!(count > 0.f) || std::isinf(count)) return badValue("--neighbour-nsamples", "expecting a positive number or an EXR file");
+				rNb.m_nbOfSamplesImage.resize(rNb.m_colorImage.getWidth(), rNb.m_colorImage.getHeight(), 1);
+				rNb.m_nbOfSamplesImage.fill(count);
+			}
+			else if(!ImageIO::loadMultiChannelsEXR(rNb.m_nbOfSamplesImage, rArgument.c_str()) || rNb.m_nbOfSamplesImage.getDepth() != 1)
+			{
+				cout << "ERROR in program arguments: couldn't load a one-channel sample count image from '" << rArgument << "'" << endl;
+				return false;
+			}
+		}
 		if(missingColor || missingHist || missingCov || missingOutput)
 		{
 			cout << "ERROR: Missing required program argument(s):";
@@ -612,8 +656,12 @@ namespace
 		for(ProgramArguments::Neighbour& rNb : args.m_neighbours)
 		{
 			DenoiserInputs frame;
-			frame.m_pColors = &rNb.m_colorImage; frame.m_pNbOfSamples = &rNb.m_nbOfSamplesImage; frame.m_pHistograms = &rNb.m_histogramImage; frame.m_pSampleCovariances = &rNb.m_covarianceImage;
-			pSettings->addNeighbourFrame(frame);
+			frame.m_pColors = &rNb.m_colorImage; frame.m_pNbOfSamples = &rNb.m_nbOfSamplesImage; frame.m_pSampleCovariances = &rNb.m_covarianceImage;
+			frame.m_pHistograms = args.m_momentSelection ? nullptr : &rNb.m_histogramImage;
+			if(args.m_momentSelection)
+				pSettings->addNeighbourFrameMoments(frame);
+			else
+				pSettings->addNeighbourFrame(frame);
 			for(ProgramArguments::NeighbourLayer& rLayer : rNb.m_layers)
 				pSettings->addNeighbourFrameLayer(pSettings->getNeighbourFrames().size() - 1, &rLayer.m_colorImage, &rLayer.m_covarianceImage);
 			if(!rNb.m_motionPath.empty())

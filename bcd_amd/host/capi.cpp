@@ -758,6 +758,108 @@ int bcdcore_denoise_temporal_guided(const float* cols, const float* covs, const 
 			randomOrder, skipProbability, seed, 0, afterClear, outs, &guide);
 }
 
+/// bcd::Denoiser / bcd::MultiscaleDenoiser under setMomentSelection(true) with neighbour frames added by addNeighbourFrameMoments (no histogram anywhere):
+/// cols / covs hold nbOfLayers images of the frame (layer 0 = the primary images), nbCols / nbCovs nbOfNeighbours x nbOfLayers images (neighbour-major), nbNs one
+/// image per neighbour; motions / hasMotion as bcdcore_denoise_temporal_motion takes them (motions may be null); features null: no feature gate, else as
+/// bcdcore_denoise_temporal_guided (every neighbour gets its feature buffers).  For the refusals denoise() owes: momentSelection == 0 leaves setMomentSelection
+/// off, the first nbOfPlainNeighbours neighbours are added by addNeighbourFrame (with a histogram image of ones), the last neighbour gets dropLayers fewer
+/// layers than the frame, nbOfDevices > 0 -> setDevices.  Returns denoise()'s bool.
+int bcdcore_denoise_temporal_moments(const float* cols, const float* covs, const float* ns, const float* nbCols, const float* nbCovs, const float* nbNs, int nbOfNeighbours,
+		int nbOfLayers, const float* motions, const int* hasMotion, int W, int H, int nscales, float tau, int b, float minEig, int randomOrder, float skipProbability,
+		unsigned seed, float varianceFloor, const float* features, const float* variances, int nbOfChannels, const float* floors, int nbOfFloors, float threshold,
+		const float* nbFeatures, const float* nbVariances, int momentSelection, int nbOfPlainNeighbours, int dropLayers, const int* devices, int nbOfDevices, float* outs)
+{
+	if(nbOfLayers < 1 || nbOfNeighbours < 0 || (features && (!floors || nbOfChannels < 1 || (nbOfNeighbours > 0 && !nbFeatures)))) return 0;
+	const size_t npix = size_t(W) * H;
+	Deepimf nImg(W, H, 1), ones(W, H, 12);
+	nImg.copyDataFrom(ns);
+	ones.fill(1.f);
+	std::vector<Deepimf> c(nbOfLayers), v(nbOfLayers), o(nbOfLayers);
+	for(int k = 0; k < nbOfLayers; ++k)
+	{
+		c[k].resize(W, H, 3); v[k].resize(W, H, 6);
+		c[k].copyDataFrom(cols + k * npix * 3); v[k].copyDataFrom(covs + k * npix * 6);
+		o[k] = c[k]; // (the multiscale path wants the output pre-sized like the input)
+	}
+	std::vector<Deepimf> fn(nbOfNeighbours), fc(size_t(nbOfNeighbours) * nbOfLayers), fv(size_t(nbOfNeighbours) * nbOfLayers), mv(nbOfNeighbours), nf(nbOfNeighbours), nv(nbOfNeighbours);
+	DenoiserInputs in;
+	in.m_pColors = &c[0]; in.m_pNbOfSamples = &nImg; in.m_pHistograms = nullptr; in.m_pSampleCovariances = &v[0];
+	DenoiserOutputs out;
+	out.m_pDenoisedColors = &o[0];
+	DenoiserParameters p;
+	p.m_histogramDistanceThreshold = tau;
+	p.m_searchWindowRadius = b;
+	p.m_minEigenValue = minEig;
+	p.m_useRandomPixelOrder = randomOrder != 0;
+	p.m_markedPixelsSkippingProbability = skipProbability;
+	std::unique_ptr<MultiscaleDenoiser> multi;
+	std::unique_ptr<Denoiser> mono;
+	IDenoiser* d;
+	HipEngineSettings* pSettings;
+	if(nscales > 1) { multi.reset(new MultiscaleDenoiser(nscales)); d = multi.get(); pSettings = multi.get(); }
+	else { mono.reset(new Denoiser()); d = mono.get(); pSettings = mono.get(); }
+	pSettings->setOrderSeed(seed);
+	if(momentSelection)
+		pSettings->setMomentSelection(true, varianceFloor);
+	else
+		in.m_pHistograms = &ones;
+	for(int k = 1; k < nbOfLayers; ++k)
+		pSettings->addLayer(&c[k], &v[k], &o[k]);
+	Deepimf gf, gv;
+	if(features)
+	{
+		gf.resize(W, H, nbOfChannels); gf.copyDataFrom(features);
+		if(variances) { gv.resize(W, H, nbOfChannels); gv.copyDataFrom(variances); }
+		pSettings->setGuideFeatures(&gf, variances ? &gv : nullptr, std::vector<float>(floors, floors + nbOfFloors), threshold);
+	}
+	for(int f = 0; f < nbOfNeighbours; ++f)
+	{
+		fn[f].resize(W, H, 1);
+		fn[f].copyDataFrom(nbNs + f * npix);
+		for(int k = 0; k < nbOfLayers; ++k)
+		{
+			const size_t i = size_t(f) * nbOfLayers + k;
+			fc[i].resize(W, H, 3); fv[i].resize(W, H, 6);
+			fc[i].copyDataFrom(nbCols + i * npix * 3); fv[i].copyDataFrom(nbCovs + i * npix * 6);
+		}
+		DenoiserInputs frame;
+		frame.m_pColors = &fc[size_t(f) * nbOfLayers]; frame.m_pNbOfSamples = &fn[f]; frame.m_pHistograms = nullptr; frame.m_pSampleCovariances = &fv[size_t(f) * nbOfLayers];
+		if(f < nbOfPlainNeighbours)
+		{
+			frame.m_pHistograms = &ones;
+			pSettings->addNeighbourFrame(frame);
+		}
+		else
+			pSettings->addNeighbourFrameMoments(frame);
+		const int given = nbOfLayers - (f == nbOfNeighbours - 1 ? dropLayers : 0);
+		for(int k = 1; k < given; ++k)
+			pSettings->addNeighbourFrameLayer(size_t(f), &fc[size_t(f) * nbOfLayers + k], &fv[size_t(f) * nbOfLayers + k]);
+		if(motions && hasMotion && hasMotion[f])
+		{
+			mv[f].resize(W, H, 2);
+			mv[f].copyDataFrom(motions + f * npix * 2);
+			pSettings->setNeighbourMotion(size_t(f), &mv[f]);
+		}
+		if(features)
+		{
+			const size_t n = npix * nbOfChannels;
+			nf[f].resize(W, H, nbOfChannels); nf[f].copyDataFrom(nbFeatures + f * n);
+			if(nbVariances) { nv[f].resize(W, H, nbOfChannels); nv[f].copyDataFrom(nbVariances + f * n); }
+			pSettings->setNeighbourGuideFeatures(size_t(f), &nf[f], nbVariances ? &nv[f] : nullptr);
+		}
+	}
+	if(devices && nbOfDevices > 0)
+		pSettings->setDevices(std::vector<int>(devices, devices + nbOfDevices));
+	d->setInputs(in);
+	d->setOutputs(out);
+	d->setParameters(p);
+	const bool ok = d->denoise();
+	if(ok)
+		for(int k = 0; k < nbOfLayers; ++k)
+			o[k].copyDataTo(outs + k * npix * 3);
+	return ok ? 1 : 0;
+}
+
 /// ONE MultiscaleDenoiser (or Denoiser), denoise() called twice with -r 0 and the given m_nbOfCores: the written-back core count must not
 /// change what the second call does (returns 0 on failure, else 1; nbOfCoresAfter[2] = the field after each call)
 int bcdcore_denoise_reuse(const float* col, const float* ns, const float* hist, const float* cov, int W, int H, int D, int nscales, int b,

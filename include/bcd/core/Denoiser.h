@@ -88,12 +88,25 @@ namespace bcd
 		/// similar patches are also searched in the same window of every neighbour frame, and mean, noise mean and covariance of the estimate come from the
 		/// union of the sets; only the frame itself is denoised.  Each neighbour brings all four images, of the frame's width, height and histogram depth.
 		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with the spike
-		/// prefilter or the moment selection; feature buffers need setNeighbourGuideFeatures for every neighbour.  With no neighbour denoise() is what it always was.
+		/// prefilter; under the moment selection see addNeighbourFrameMoments; feature buffers need setNeighbourGuideFeatures for every neighbour.  With no neighbour denoise() is what it always was.
 		void addNeighbourFrame(const DenoiserInputs& i_rFrame)
 		{
 			m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); m_neighbourMotion.push_back(nullptr); m_neighbourGuides.emplace_back();
+			m_neighbourMoments.push_back(0);
 		}
-		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); m_neighbourMotion.clear(); m_neighbourGuides.clear(); }
+		/// A neighbouring frame for the selection from means and covariances (setMomentSelection(true); bcd_hip_denoise_temporal_moments_host): colours, sample
+		/// counts and sample covariances of the frame's size, m_pHistograms may be null and is not looked at.  addNeighbourFrameLayer, setNeighbourMotion and
+		/// setNeighbourGuideFeatures index it like any other neighbour.  denoise() serves neighbour frames under the moment selection only when EVERY neighbour
+		/// was added this way, refuses such neighbours without setMomentSelection(true), and keeps its refusal of addNeighbourFrame under the moment selection.
+		void addNeighbourFrameMoments(const DenoiserInputs& i_rFrame)
+		{
+			addNeighbourFrame(i_rFrame);
+			m_neighbourMoments.back() = 1;
+		}
+		void clearNeighbourFrames() { m_neighbourFrames.clear(); m_neighbourLayers.clear(); m_neighbourMotion.clear(); m_neighbourGuides.clear(); m_neighbourMoments.clear(); }
+		/// per neighbour 1 when it was added by addNeighbourFrameMoments, else 0
+		const std::vector<char>& getNeighbourMomentFlags() const { return m_neighbourMoments; }
+		void setNeighbourMomentFlags(const std::vector<char>& i_rFlags) { m_neighbourMoments = i_rFlags; m_neighbourMoments.resize(m_neighbourFrames.size(), 0); }
 		const std::vector<DenoiserInputs>& getNeighbourFrames() const { return m_neighbourFrames; }
 		void setNeighbourFrames(const std::vector<DenoiserInputs>& i_rFrames)
 		{
@@ -101,6 +114,7 @@ namespace bcd
 			m_neighbourLayers.assign(i_rFrames.size(), std::vector<NeighbourLayer>());
 			m_neighbourMotion.assign(i_rFrames.size(), nullptr);
 			m_neighbourGuides.assign(i_rFrames.size(), NeighbourGuide());
+			m_neighbourMoments.assign(i_rFrames.size(), 0);
 		}
 		/// The feature buffers of neighbour i_neighbour (bcd_hip_denoise_temporal_guided_host): with setGuideFeatures and neighbour frames, the gate that protects
 		/// the search inside the frame protects the search in the neighbours too -- a patch of a neighbour stays similar only if its features agree with the
@@ -169,6 +183,7 @@ namespace bcd
 		std::vector<std::vector<NeighbourLayer>> m_neighbourLayers; // [neighbour][added layer], as long as m_neighbourFrames
 		std::vector<const DeepImage<float>*> m_neighbourMotion;     // [neighbour] its motion field or nullptr, as long as m_neighbourFrames
 		std::vector<NeighbourGuide> m_neighbourGuides;              // [neighbour] its feature buffers, as long as m_neighbourFrames
+		std::vector<char> m_neighbourMoments;                       // [neighbour] 1: added by addNeighbourFrameMoments, as long as m_neighbourFrames
 	};
 
 	/// The engine contexts behind denoise() (device workspaces, pyramids, staging buffers: grow-only, sized by the largest frame seen,

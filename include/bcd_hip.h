@@ -467,7 +467,7 @@ int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_coun
  *   _denoise_temporal_guided: L = 1 .. 16 layers, d_motion NULL (nothing is warped) or nb_neighbours entries, each NULL or W*H*2 floats.  nb_neighbours == 0 IS
  *             bcd_hip_denoise_guided (histograms, sel = NULL).  Refused before any device work, with a message, the context staying usable: everything
  *             bcd_hip_denoise_temporal_layers_motion and bcd_hip_denoise_guided refuse; a NULL guide, neighbour_guides or neighbour feature pointer;
- *             variances present in some frames and not in others; d_histograms == NULL (there is no cross-frame moment selection); an output that overlaps a
+ *             variances present in some frames and not in others; d_histograms == NULL (the cross-frame moment selection is bcd_hip_denoise_temporal_moments); an output that overlaps a
  *             feature or variance image of any frame; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).
  *   _denoise_temporal_guided_host: the same, every pointer a host pointer: whole uploads, the resident call, one download per layer.
  *   _similarity_masks_guide_cross: G_j and its counts alone, outputs as bcd_hip_similarity_masks_cross.
@@ -491,6 +491,63 @@ int bcd_hip_window_distances_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *
                                          int search_radius, int line, int col, float *h_out);
 int bcd_hip_warp_features(bcd_hip_ctx *ctx, const bcd_hip_guide_images *in, int nb_channels, const float *d_motion, int W, int H, float *d_features_out,
                           float *d_variances_out /* NULL iff in->variances */, uint8_t *d_valid);
+
+/* ---- moments: the cross-frame selection from means and covariances, without histograms ("Moments") ----
+ * A producer without histograms (a film with a running mean and variance, bcd_hip_accum_moments) denoises single frames through bcd_hip_denoise_moments; these
+ * calls let it use neighbour frames too.  Inputs are those of bcd_hip_denoise_temporal_layers_motion without any histogram image, the variance floor of
+ * bcd_hip_denoise_moments and, optionally, the guide of bcd_hip_denoise_temporal_guided.  layers[0] is the guide layer of the selection and is denoised like
+ * the others; every neighbour brings the same layers in the same order.  float32, no contraction, the correctly rounded division:
+ * 1. Cross moment planes.  For pixel x of the frame and pixel y = x + delta of neighbour j, y inside the image, with m0, mj the colours of layer 0 of the frame
+ *    and of the neighbour, v0, vj the xx, yy, zz entries of their per-pixel covariances (what bcd_hip_pixel_cov returns for that frame's covariances and its
+ *    own sample counts) and eps the one var_floor of the call, channels k = 0, 1, 2 in order, from s = 0.f, n = 0:
+ *        d = m0_k(x) - mj_k(y)
+ *        q = (v0_k(x) + vj_k(y)) + eps
+ *        if (q > 0.f) { s = s + (d * d) / q; n = n + 1; }
+ *        T_delta(x) = s,  C_delta(x) = n
+ *    The term of bcd_hip_similarity_masks_moments with the second operand read from the neighbour: a NaN q is not counted, a NaN or infinite term IS counted
+ *    and makes the pair dissimilar (the feature term above skips a NaN term; this one does not).  There is no symmetry between two frames, so all (2b+1)^2
+ *    displacements are evaluated.
+ * 2. Cross mask: what bcd_hip_similarity_masks_cross makes of its planes, made of these with prm->hist_dist_threshold -- the (2w+1)^2 entries of T added in
+ *    patch row-major order from 0.f, the counts summed as integers, one division, the test <= tau, NaN never similar, the clipped window, the main-pixel
+ *    rule, mask bit (dl + b)(2b + 1) + (dc + b), empty masks off the main pixels.
+ * 3. S_0 is the in-frame pass of bcd_hip_denoise_moments (similarity path 3).  The total |S|, the marking on the in-frame masks, member order, the 3P + 1
+ *    rule, estimate, fallback, layers on one selection, seeds and merges are those of bcd_hip_denoise_temporal_layers.
+ * 4. Pyramid, for every frame, that of bcd_hip_denoise_moments: colours averaged, counts summed, covariances weighted by that frame's counts; there is no
+ *    histogram level.
+ * 5. Motion.  A neighbour with a field has its sample counts and every layer's colours and covariances gathered as in the motion calls; nothing of a
+ *    histogram is gathered.  The validity gate of the motion calls stays: a warped-out pixel has mean 0 and variance 0, which is not reliably dissimilar
+ *    (against a dark, low-variance pixel of the frame the term is small, and with eps = 0 it is 0/0 only where the frame's variance is 0 too).
+ * 6. Feature gate, with a guide: S_0 and every S_j are gated exactly as in bcd_hip_denoise_temporal_guided.
+ * A neighbour whose colours and per-pixel covariances ARE the frame's gives the in-frame masks of bcd_hip_similarity_masks_moments, bit for bit.
+ *   _denoise_temporal_moments: L = 1 .. 16 layers; neighbours[f].d_histograms is ignored and may be NULL; d_motion NULL (nothing is warped) or nb_neighbours
+ *             entries, each NULL or W*H*2 floats; guide NULL (no feature gate) with neighbour_guides NULL, or both given.  nb_neighbours == 0 IS
+ *             bcd_hip_denoise_moments (sel = NULL), with a guide bcd_hip_denoise_guided with NULL histograms (neighbour_guides is not looked at then).
+ *             bcd_hip_get_stats reports similarity_path 3, similar_total the sum of the total |S|, ms_similarity with the cross passes; the distance kernels
+ *             are timed for bcd_hip_kernel_time.  Refused before any device work, with a message, the context staying usable: everything
+ *             bcd_hip_denoise_temporal_layers_motion and bcd_hip_denoise_moments refuse, histogram pointers aside; with a guide, what
+ *             bcd_hip_denoise_temporal_guided refuses; guide and neighbour_guides not both NULL or both given; an output that overlaps any input; with
+ *             neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).
+ *   _denoise_temporal_moments_host: the same, every pointer a host pointer: whole uploads, the resident call, one download per layer.
+ *   _similarity_masks_moments_cross: the cross masks and counts of one neighbour alone, outputs as bcd_hip_similarity_masks_cross.  d_pixel_cov and
+ *             d_pixel_cov_nb are per-pixel covariances (W*H*6).  form 0 is the production choice, 1 the planes (a distance kernel, then the mask kernel of
+ *             bcd_hip_similarity_masks_cross), 2 one fused kernel that writes no planes and serves patch radius 1 with search radius 1 .. 6 -- elsewhere
+ *             form 2 returns BCD_HIP_EUNSUPPORTED.  Every form gives the same masks and counts, bit for bit.
+ *   _window_distances_moments_cross: the twin of bcd_hip_window_distances_cross: the (2b+1)^2 cross moment distances of one main pixel, +inf outside.
+ * The stage calls accept what bcd_hip_similarity_masks_moments accepts (w <= 2, b <= 15, a finite var_floor >= 0), refuse the rest before any device work,
+ * and synchronise.  Kept selections, the spike prefilter, row bands, bcd_hip_multi_* and any search radius other than 6 do not combine with the frame calls. */
+int bcd_hip_similarity_masks_moments_cross(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, const float *d_colors_nb, const float *d_pixel_cov_nb,
+                                           int W, int H, int patch_radius, int search_radius, float threshold, float var_floor, int form, uint32_t *d_mask_nb,
+                                           int32_t *d_count_nb);
+int bcd_hip_window_distances_moments_cross(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, const float *d_colors_nb, const float *d_pixel_cov_nb,
+                                           int W, int H, int patch_radius, int search_radius, float var_floor, int line, int col, float *h_out);
+int bcd_hip_denoise_temporal_moments(bcd_hip_ctx *ctx, const float *d_nsamples, const bcd_hip_frame_layers *neighbours /* d_histograms ignored, may be NULL */,
+                                     int nb_neighbours, const float *const *d_motion /* NULL: nothing is warped; else nb_neighbours entries, each NULL or W*H*2 */,
+                                     int W, int H, int nb_scales, const bcd_hip_params *prm, float var_floor, const bcd_hip_layer *layers, int nb_layers,
+                                     const bcd_hip_guide *guide /* NULL: no feature gate */, const bcd_hip_guide_images *neighbour_guides /* NULL iff guide is */);
+int bcd_hip_denoise_temporal_moments_host(bcd_hip_ctx *ctx, const float *h_nsamples, const bcd_hip_frame_layers *neighbours /* host pointers */, int nb_neighbours,
+                                          const float *const *h_motion, int W, int H, int nb_scales, const bcd_hip_params *prm, float var_floor,
+                                          const bcd_hip_layer *layers /* host pointers */, int nb_layers, const bcd_hip_guide *guide /* host images */,
+                                          const bcd_hip_guide_images *neighbour_guides /* host images */);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
