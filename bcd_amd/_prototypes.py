@@ -74,6 +74,13 @@ class StageFrame(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_pixel_cov", C.c_void_p), ("d_mask", C.c_void_p)]
 
 
+class SequenceInfo(C.Structure):
+    """what bcd_hip_sequence_info reports"""
+    _c_name_ = "bcd_hip_sequence_info"
+    _fields_ = [("frames_pushed", C.c_int64), ("frames_popped", C.c_int64), ("device_bytes", C.c_int64), ("bytes_uploaded", C.c_int64),
+                ("pyramids_built", C.c_int64), ("cross_computed", C.c_int64), ("cross_transposed", C.c_int64)]
+
+
 class FrameLayer(C.Structure):
     """one colour layer of a neighbour frame of bcd_hip_denoise_temporal_layers[_host]"""
     _c_name_ = "bcd_hip_frame_layer"
@@ -233,6 +240,20 @@ PROTOTYPES = {
     "bcd_hip_bayes_accumulate_temporal": (I, [P, S(StageFrame), I, P, P, I, I, I, I, F, P, P]),
     "bcd_hip_similarity_masks_cross": (I, [P, P, P, P, P, I, I, I, I, I, F, P, P]),
     "bcd_hip_window_distances_cross": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    # ---- a sequence denoised through a sliding window that reuses cross masks ("Sequences")
+    "bcd_hip_transpose_masks_cross": (I, [P, P, I, I, I, P, P]),
+    "bcd_hip_sequence_create": (I, [P, I, I, I, I, I, S(Params), P]),
+    "bcd_hip_sequence_push": (I, [P, P, P, P, P]),
+    "bcd_hip_sequence_push_host": (I, [P, P, P, P, P]),
+    "bcd_hip_sequence_end": (I, [P]),
+    "bcd_hip_sequence_ready": (I, [P]),
+    "bcd_hip_sequence_pop": (I, [P, P, P]),
+    "bcd_hip_sequence_pop_host": (I, [P, P, P]),
+    "bcd_hip_sequence_set_reuse": (I, [P, I]),
+    "bcd_hip_sequence_last_masks": (I, [P, I, I, P, P]),
+    "bcd_hip_sequence_info": (I, [P, S(SequenceInfo)]),
+    "bcd_hip_sequence_reset": (I, [P]),
+    "bcd_hip_sequence_destroy": (None, [P]),
     # ---- the colour layers of a frame denoised with its neighbour frames ("Layers")
     "bcd_hip_denoise_temporal_layers": (I, [P, P, P, S(FrameLayers), I, I, I, I, I, S(Params), S(Layer), I]),
     "bcd_hip_denoise_temporal_layers_host": (I, [P, P, P, S(FrameLayers), I, I, I, I, I, S(Params), S(Layer), I]),

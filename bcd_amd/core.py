@@ -292,6 +292,20 @@ def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, mi
     return rc != 0, out
 
 
+def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, unsupported=0):
+    """bcd::SequenceDenoiser: frames is a list of (col, ns, hist, cov) arrays of one size, pushed one by one and popped as they become ready; frame t comes out
+    denoised with the frames t - radius .. t + radius that exist (what denoise_temporal returns for it with those neighbours in ascending order), every
+    frame uploaded once and every pair of frames searched once.  unsupported: bits of settings the sequence must refuse (bcdcore_denoise_sequence).
+    Returns (ok, [denoised frame per frame])"""
+    T = len(frames)
+    H, W, D = frames[0][2].shape
+    stack = lambda k, d: np.ascontiguousarray(np.stack([np.asarray(f[k], np.float32).reshape(H, W, d) for f in frames]), np.float32)
+    outs = np.zeros((T, H, W, 3), np.float32)
+    rc = lib().bcdcore_denoise_sequence(_fp(stack(0, 3)), _fp(stack(1, 1)), _fp(stack(2, D)), _fp(stack(3, 6)), T, W, H, D, int(nscales), int(radius), C.c_float(tau),
+                                        int(w), int(b), C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed), int(unsupported), _fp(outs))
+    return rc != 0, [outs[k] for k in range(T)]
+
+
 def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, drop_layers=0, after_clear=False,
                             motions=None, features=None, neighbour_features=None, variances=None, neighbour_variances=None, floors=(), threshold=1.0,
                             neighbours_with_features=None, moment_selection=False, devices=None):

@@ -1,5 +1,5 @@
 // bcd_ctx.h -- internal to the host orchestration files (bcd_api.hip, bcd_host.hip, bcd_accum.hip, bcd_selection.hip, bcd_selftest.hip, bcd_spike.hip,
-// bcd_temporal.hip, bcd_temporal_layers.hip): the context, the per-scale workspace with its counter block, the error-handling macros and the helpers more
+// bcd_temporal.hip, bcd_temporal_layers.hip, bcd_sequence.hip): the context, the per-scale workspace with its counter block, the error-handling macros and the helpers more
 // than one of those files needs.  Nothing declared here is part of the C ABI (include/bcd_hip.h): the helpers have hidden visibility.
 #pragma once
 #include "../../include/bcd_hip.h"
@@ -346,7 +346,13 @@ bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const
 // feat, var: null, or -- in a bcd_hip_denoise_temporal_guided call -- the frame's feature and variance images at this level (var null: no variances)
 // col, pixcov: null, or -- in a bcd_hip_denoise_temporal_moments call ("Moments") -- the guide layer's colours and per-pixel covariances at this level; hist is
 // null then.  pixcov is what per_pixel_cov() produces: temporal_select enqueues it ahead of the in-frame pass in that mode
-struct TemporalSelFrame { const float *ns, *hist; const uint8_t *valid; const float *feat = nullptr, *var = nullptr; const float *col = nullptr, *pixcov = nullptr; };
+// transpose_from, mask_dst: null, or -- in a pop of a sequence (bcd_sequence.hip, "Sequences") -- the kept cross masks of the pair with the roles swapped, from
+// which this neighbour's masks come by k_masks_transpose in place of a cross pass, and the buffer that takes this neighbour's masks in place of
+// ctx->temporal.mask[f] (the sequence keeps them there).  With both null every call takes the branches it took before they existed
+struct TemporalSelFrame {
+    const float *ns, *hist; const uint8_t *valid; const float *feat = nullptr, *var = nullptr; const float *col = nullptr, *pixcov = nullptr;
+    const uint32_t *transpose_from = nullptr; uint32_t *mask_dst = nullptr;
+};
 // with a guided temporal call in progress (temporal_guide_begin), the feature images of frame f at level `scale`; else nothing
 inline void temporal_guide_level(const bcd_hip_ctx *ctx, int f, int scale, TemporalSelFrame *sel)
 {
@@ -363,6 +369,11 @@ struct TemporalPath { int32_t path = 0, borderline = 0; }; // of the in-frame pa
 // and every cross pass from the moment cross launchers on frames[f].col / .pixcov; no histogram is read.
 int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
                     const std::function<int()> &per_pixel_cov, TemporalPath *path);
+// the estimate stage over the members of several frames (patch radius 1, search radius 6) on wk.stream, synchronised at its end: temporal_lists, the fallback
+// kernel over all frames, one chain of full estimates on the frame's own colours and in-frame masks; the list lengths and the sum of |S| are in
+// wk.h_counters->lists when it returns
+int bayes_temporal(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
+                   float *d_sum, int32_t *d_count);
 // the masks temporal_select left for frame f
 inline const uint32_t *temporal_mask(const bcd_hip_ctx *ctx, int f) { return (const uint32_t *)(f == 0 ? ctx->main.mask.p : ctx->temporal.mask[f].p); }
 // the tail of a scale (the stream is synchronised): the figures of wk.h_counters->lists and of the in-frame pass, and with profiling the four timers

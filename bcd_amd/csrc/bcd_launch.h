@@ -29,6 +29,10 @@ hipError_t bcd_launch_masks_cross(const float *T, const uint8_t *Cn, int W, int 
 hipError_t bcd_launch_add_counts(int32_t *nsim, const int32_t *add, int64_t npix, hipStream_t st);
 hipError_t bcd_launch_window_distances_cross(const float *T, const uint8_t *Cn, int W, int H, int w, int b, int r, int c, float *out, hipStream_t st);
 
+// ---- k_masks_transpose.hip (includes this header)
+hipError_t bcd_launch_masks_transpose(const uint32_t *in, int W, int H, int b, uint32_t *out, int32_t *count, hipStream_t st);
+hipError_t bcd_launch_mask_popcount(const uint32_t *mask, int64_t npix, int words, int32_t *count, hipStream_t st);
+
 // ---- k_warp.hip (includes this header)
 hipError_t bcd_launch_warp_frame(const float *col, const float *ns, const float *hist, const float *cov, const float *mv, int W, int H, int D, float *ocol, float *ons,
                                  float *ohist, float *ocov, uint8_t *valid, hipStream_t st);

@@ -204,6 +204,8 @@ int check_cross_stage(bcd_hip_ctx *ctx, int W, int H, int D, int w, int b)
     return check_params(ctx, W, H, D, &p);
 }
 
+} // namespace
+
 // The estimate stage over the members of several frames (patch radius 1, search radius 6): the lists, the fallback kernel over all frames, the wait for the
 // list lengths, one chain of full estimates on the frame's own colours and in-frame masks, the redo count.  The list lengths and the sum of |S| are in
 // wk.h_counters->lists when the call returns (it synchronises the stream at its end).
@@ -220,8 +222,6 @@ int bayes_temporal(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, const int
     HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     return BCD_HIP_OK;
 }
-
-} // namespace
 
 extern "C" {
 
@@ -334,7 +334,7 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
     RCCHK(ensure(ctx, wk.state, npix));
     RCCHK(ensure(ctx, wk.cnt, npix * sizeof(int32_t)));
     RCCHK(ensure(ctx, tp.count_nb, npix * sizeof(int32_t)));
-    for (int f = 1; f < nf; ++f) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
+    for (int f = 1; f < nf; ++f) if (!frames[f].mask_dst) RCCHK(ensure(ctx, tp.mask[f], npix * words * sizeof(uint32_t)));
     bcd_hip_scale_stats &st = ctx->stats[scale];
     memset(&st, 0, sizeof(st));
     st.width = W; st.height = H;
@@ -357,9 +357,11 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
     if (guided) RCCHK(guide_gate_masks(ctx, wk, frames[0].feat, frames[0].var, W, H, w, b, (uint32_t *)wk.mask.p, (int32_t *)wk.nsim.p));
     if (!moments) RCCHK(per_pixel_cov());
     for (int f = 1; f < nf; ++f) {
-        uint32_t *mask = (uint32_t *)tp.mask[f].p;
+        uint32_t *mask = frames[f].mask_dst ? frames[f].mask_dst : (uint32_t *)tp.mask[f].p; // ("Sequences": the sequence's own buffer)
         int32_t *count = (int32_t *)tp.count_nb.p;
-        if (moments) {
+        if (frames[f].transpose_from) { // ("Sequences": the pair was searched from the other side; no planes are written)
+            HIPCHK(ctx, bcd_launch_masks_transpose(frames[f].transpose_from, W, H, b, mask, count, wk.stream));
+        } else if (moments) {
             RCCHK(temporal_moments_cross_masks(ctx, wk, frames[0].col, frames[0].pixcov, frames[f].col, frames[f].pixcov, W, H, w, b, tau, eps, moments_cross_form(0, w, b),
                                                mask, count));
         } else {

@@ -7,7 +7,7 @@ import weakref
 from . import _prototypes
 from ._prototypes import (ACCUM_MAX_LAYERS, MAX_LAYERS, MULTI_ID_BYTES, PROGRESS_FN, SELECTION_MAX_SCALES, STATE_HEADER_BYTES, BandJob, Frame, FrameLayer,
                           FrameLayers, Guide, GuideImages, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
-                          PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
+                          PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SequenceInfo, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
                           StateHeader, WarpedFrame)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -487,6 +487,29 @@ class Context:
         torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
         self._chk(lib().bcd_hip_similarity_masks_cross(self.h, _dp(hist), _dp(ns), _dp(hist_nb), _dp(ns_nb), W, H, D, w, b, tau, _dp(mask), _dp(cnt)))
         return mask, cnt
+
+    def transpose_masks_cross(self, mask, b, out=None):
+        """bcd_hip_transpose_masks_cross: the cross masks of a frame pair with the roles of the frames swapped -- out(p) bit k = mask(p + delta_k) bit
+        (nbits - 1 - k) inside the image, else 0 -- and their popcounts.  mask: (H, W, words) int32 as similarity_masks_cross returns it; b: 1 .. 6.
+        out: (mask, count) contiguous device tensors to fill, count may be None.  Returns (mask, count)"""
+        torch = self.torch
+        H, W, words = mask.shape
+        if out is None:
+            out = (torch.zeros_like(mask), torch.zeros((H, W), dtype=torch.int32, device=mask.device))
+        omask, cnt = out
+        if tuple(omask.shape) != (H, W, words) or omask.dtype != torch.int32 or mask.dtype != torch.int32:
+            raise ValueError("masks must be (H, W, words) int32")
+        if cnt is not None and (tuple(cnt.shape) != (H, W) or cnt.dtype != torch.int32):
+            raise ValueError("the counts must be (H, W) int32")
+        if b >= 1 and words != ((2 * b + 1) ** 2 + 31) // 32:
+            raise ValueError("a mask of search radius %d has %d words per pixel" % (b, ((2 * b + 1) ** 2 + 31) // 32))
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(lib().bcd_hip_transpose_masks_cross(self.h, _dp(mask), W, H, b, _dp(omask), _dp(cnt) if cnt is not None else None))
+        return omask, cnt
+
+    def sequence(self, W, H, D, nscales, radius, prm):
+        """a Sequence of this context: frames of W x H with D bins, denoised with their neighbours within `radius` frames through a sliding window"""
+        return Sequence(self, W, H, D, nscales, radius, prm)
 
     def window_distances_cross(self, hist, ns, hist_nb, ns_nb, w, b, line, column):
         """bcd_hip_window_distances_cross: the (2b+1)^2 patch distances of one main pixel of the frame to its window in the neighbour frame, +inf outside"""
@@ -1688,6 +1711,110 @@ class Selection:
     def close(self):
         if self.h:
             lib().bcd_hip_selection_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sequence:
+    """bcd_hip_sequence: the frames of an animation pushed one by one and popped denoised, each with its neighbours within `radius` frames (what
+    Context.denoise_temporal returns for it).  Every frame is copied and its pyramid built once; every pair of frames is searched once -- the second
+    cross pass of a pair is a transposition of the first one's masks"""
+
+    def __init__(self, ctx, W, H, D, nscales, radius, prm):
+        h = _VP()
+        ctx._chk(lib().bcd_hip_sequence_create(ctx.h, int(W), int(H), int(D), int(nscales), int(radius), C.byref(prm), C.byref(h)))
+        self.ctx, self.h = ctx, h
+        self.W, self.H, self.D, self.nscales, self.radius = int(W), int(H), int(D), int(nscales), int(radius)
+        self.b = prm.search_radius
+        ctx._selections.add(self)                                    # (closed with the context, like a selection)
+
+    def _handle(self):
+        if not self.h:
+            raise BcdHipError("the sequence is closed")
+        return self.h
+
+    def _check(self, col, ns, hist, cov):
+        H, W, D = self.H, self.W, self.D
+        nns = ns.numel() if hasattr(ns, "numel") else ns.size
+        shapes = (tuple(col.shape), int(nns), tuple(hist.shape), tuple(cov.shape))
+        if shapes != ((H, W, 3), H * W, (H, W, D), (H, W, 6)):
+            raise ValueError("a frame of this sequence is colours %dx%dx3, sample counts %dx%d, histograms %dx%dx%d, covariances %dx%dx6" % (H, W, H, W, H, W, D, H, W))
+
+    def push(self, col, ns, hist, cov):
+        """bcd_hip_sequence_push: the next frame, device tensors (copied: they are free again on return)"""
+        h = self._handle()
+        self._check(col, ns, hist, cov)
+        self.ctx.torch.cuda.synchronize(self.ctx.device)
+        self.ctx._chk(lib().bcd_hip_sequence_push(h, _dp(col), _dp(ns), _dp(hist), _dp(cov)))
+
+    def push_host(self, col, ns, hist, cov):
+        """bcd_hip_sequence_push_host: the next frame, NumPy arrays (uploaded once)"""
+        import numpy as np
+        h = self._handle()
+        col, ns, hist, cov = (np.ascontiguousarray(a, np.float32) for a in (col, ns, hist, cov))
+        self._check(col, ns, hist, cov)
+        self.ctx._chk(lib().bcd_hip_sequence_push_host(h, _hptr(col), _hptr(ns), _hptr(hist), _hptr(cov)))
+
+    def end(self):
+        """no further frame follows: the frames still held become ready"""
+        self.ctx._chk(lib().bcd_hip_sequence_end(self._handle()))
+
+    def ready(self):
+        """frames that can be popped now"""
+        return lib().bcd_hip_sequence_ready(self._handle())
+
+    def pop(self, out=None):
+        """bcd_hip_sequence_pop -> (frame index, the denoised frame as a (H, W, 3) device tensor)"""
+        h = self._handle()
+        torch = self.ctx.torch
+        if out is None:
+            out = torch.empty((self.H, self.W, 3), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+        idx = C.c_int64(-1)
+        torch.cuda.synchronize(self.ctx.device)
+        self.ctx._chk(lib().bcd_hip_sequence_pop(h, _dp(out), C.byref(idx)))
+        return idx.value, out
+
+    def pop_host(self):
+        """bcd_hip_sequence_pop_host -> (frame index, the denoised frame as a (H, W, 3) NumPy array)"""
+        import numpy as np
+        h = self._handle()
+        out = np.empty((self.H, self.W, 3), np.float32)
+        idx = C.c_int64(-1)
+        self.ctx._chk(lib().bcd_hip_sequence_pop_host(h, _hptr(out), C.byref(idx)))
+        return idx.value, out
+
+    def set_reuse(self, on):
+        """False: every pair is searched directly from both sides (comparisons, tests)"""
+        self.ctx._chk(lib().bcd_hip_sequence_set_reuse(self._handle(), int(bool(on))))
+
+    def last_masks(self, neighbour, scale=0):
+        """bcd_hip_sequence_last_masks -> (mask, count) of the last popped frame at `scale`: neighbour 0 its in-frame set, 1 .. its neighbours in ascending
+        frame order"""
+        h = self._handle()
+        hh, ww = (self.H >> scale, self.W >> scale) if 0 <= scale < self.nscales else (1, 1)
+        mask, cnt = _mask_and_count(hh, ww, self.b, "cuda:%d" % self.ctx.device)
+        self.ctx.torch.cuda.synchronize(self.ctx.device)             # (the fills ran on torch's stream)
+        self.ctx._chk(lib().bcd_hip_sequence_last_masks(h, int(neighbour), int(scale), _dp(mask), _dp(cnt)))
+        return mask, cnt
+
+    def info(self):
+        """bcd_hip_sequence_info as a dict: frames_pushed, frames_popped, device_bytes, bytes_uploaded, pyramids_built, cross_computed, cross_transposed"""
+        i = SequenceInfo()
+        self.ctx._chk(lib().bcd_hip_sequence_info(self._handle(), C.byref(i)))
+        return {k: getattr(i, k) for k, _ in SequenceInfo._fields_}
+
+    def reset(self):
+        """forgets every frame and counter; the buffers stay"""
+        self.ctx._chk(lib().bcd_hip_sequence_reset(self._handle()))
+
+    def close(self):
+        if self.h:
+            lib().bcd_hip_sequence_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -11,12 +11,15 @@
 // --neighbour-features <f.exr> / --neighbour-feature-variances <v.exr> hand the most recent --neighbour its feature buffers: with --features the gate covers
 // the search in the neighbours too (every neighbour then needs them).
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
+// --sequence-in <pattern with %d> --sequence-out <pattern with %d> --first a --last b --temporal-radius R denoises the frames a .. b of an animation, each with
+// its neighbours within R frames, through bcd::SequenceDenoiser (every frame uploaded once, every pair of frames searched once); it replaces -i / -o.
 #include "Chronometer.h"
 #include "DeepImage.h"
 #include "Denoiser.h"
 #include "ImageIO.h"
 #include "MultiscaleDenoiser.h"
 #include "ParametersIO.h"
+#include "SequenceDenoiser.h"
 #include "SpikeRemovalFilter.h"
 #include "Utils.h"
 
@@ -95,6 +98,11 @@ namespace
 		cout << "    --neighbour-layer <color> <cov>" << endl;
 		cout << "                         a colour layer of the most recent --neighbour: the k-th one pairs with the k-th --layer; every neighbour" << endl;
 		cout << "                         needs exactly one per --layer (one selection over all frames then serves every layer; needs -p 0)" << endl;
+		cout << "    --sequence-in <pattern> --sequence-out <pattern> --first <a> --last <b> [--temporal-radius <R>]" << endl;
+		cout << "                         in place of -i / -o: the frames a .. b of an animation, the patterns holding one %d (or %04d ...) for the frame number;" << endl;
+		cout << "                         every frame is denoised with its neighbours within R frames (1 or 2, default 1) and written to its output name." << endl;
+		cout << "                         Expects <frame>_hist.exr / <frame>_cov.exr beside every input, as --neighbour does; needs -p 0, -w 1, -b 6 and a single" << endl;
+		cout << "                         device; not with -i, -o, -h, -c, --neighbour, --layer, --features or --moment-selection" << endl;
 		cout << "    -d <float>           Histogram patch distance threshold (default: " << d.m_histogramPatchDistanceThreshold << ")" << endl;
 		cout << "    -b <int>             Radius of search windows (default: " << d.m_searchWindowRadius << ")" << endl;
 		cout << "    -w <int>             Radius of patches (default: " << d.m_patchRadius << ")" << endl;
@@ -591,6 +599,138 @@ namespace
 				p[i] = 0.f;
 	}
 
+	// "frames/shot.%04d.exr" with one integer conversion and nothing else after a '%'
+	bool isFramePattern(const string& i_rPattern)
+	{
+		const size_t pos = i_rPattern.find('%');
+		if(pos == string::npos || i_rPattern.find('%', pos + 1) != string::npos)
+			return false;
+		size_t i = pos + 1;
+		while(i < i_rPattern.size() && isdigit((unsigned char)i_rPattern[i])) ++i;
+		return i < i_rPattern.size() && i_rPattern[i] == 'd' && i - pos <= 4;
+	}
+
+	string frameName(const string& i_rPattern, int i_frame)
+	{
+		std::vector<char> buffer(i_rPattern.size() + 32);
+		snprintf(buffer.data(), buffer.size(), i_rPattern.c_str(), i_frame);
+		return string(buffer.data());
+	}
+
+	// --sequence-in: the frames --first .. --last through bcd::SequenceDenoiser.  Everything is checked before the first file is read or a device is asked for
+	int launchSequenceDenoising(int argc, const char** argv)
+	{
+		ProgramArguments a;
+		a.m_prefilterSpikes = true; // (the CLI's default: the sequence has no prefilter, so -p 0 must be said)
+		string inPattern, outPattern;
+		int first = 0, last = -1, radius = 1;
+		bool hasFirst = false, hasLast = false;
+		auto argumentError = [](const string& i_rMessage) { cout << "ERROR in program arguments: " << i_rMessage << endl; return 1; };
+		for(int i = 1; i < argc; ++i)
+		{
+			const string flag = argv[i];
+			if(flag == "--help") { printUsage(); return 1; }
+			for(const char* pOther : { "-i", "-o", "-h", "-c", "-a", "--neighbour", "--neighbour-nsamples", "--neighbour-motion", "--neighbour-features", "--neighbour-feature-variances",
+					"--neighbour-layer", "--layer", "--prefilter-layers", "--moment-selection", "--nsamples", "--features", "--feature-variances", "--feature-floors",
+					"--feature-threshold", "--devices" })
+				if(flag == pOther)
+					return argumentError(flag + " is not available with --sequence-in (a sequence reads <frame>.exr, <frame>_hist.exr and <frame>_cov.exr of every frame and writes "
+							"--sequence-out; one colour layer, histogram selection, one device)");
+			if(i + 1 >= argc) return argumentError("expecting a value after " + flag);
+			const char* value = argv[++i];
+			if(flag == "--sequence-in") inPattern = value;
+			else if(flag == "--sequence-out") outPattern = value;
+			else if(flag == "--first") { first = atoi(value); hasFirst = true; }
+			else if(flag == "--last") { last = atoi(value); hasLast = true; }
+			else if(flag == "--temporal-radius") radius = atoi(value);
+			else if(flag == "-d") { a.m_histogramPatchDistanceThreshold = float(atof(value)); if(a.m_histogramPatchDistanceThreshold <= 0.f) return argumentError(string("expecting a positive floating number") + " after " + "-d"); }
+			else if(flag == "-b") a.m_searchWindowRadius = atoi(value);
+			else if(flag == "-w") a.m_patchRadius = atoi(value);
+			else if(flag == "-e") { a.m_minEigenValue = float(atof(value)); if(a.m_minEigenValue <= 0.f) return argumentError(string("expecting a positive floating number") + " after " + "-e"); }
+			else if(flag == "-r") { const int v = atoi(value); if(v != 0 && v != 1) return argumentError(string("expecting 0 or 1") + " after " + "-r"); a.m_useRandomPixelOrder = v == 1; }
+			else if(flag == "-p") { const int v = atoi(value); if(v != 0 && v != 1) return argumentError(string("expecting 0 or 1") + " after " + "-p"); a.m_prefilterSpikes = v == 1; }
+			else if(flag == "-m") { a.m_markedPixelsSkippingProbability = float(atof(value)); if(a.m_markedPixelsSkippingProbability < 0.f || a.m_markedPixelsSkippingProbability > 1.f) return argumentError(string("expecting a floating number between 0 and 1") + " after " + "-m"); }
+			else if(flag == "-s") { a.m_nbOfScales = atoi(value); if(a.m_nbOfScales <= 0) return argumentError(string("expecting a positive integer") + " after " + "-s"); }
+			else if(flag == "--ncores") a.m_nbOfCores = atoi(value);
+			else if(flag == "--use-cuda") a.m_useCuda = atoi(value) == 1;
+			else if(flag == "--seed") a.m_orderSeed = unsigned(strtoul(value, nullptr, 10));
+			else if(flag == "--device") a.m_devices.assign(1, atoi(value));
+			else if(flag == "--p-factor") {}
+			else return argumentError("unknown argument " + flag + " (beside --sequence-in)");
+		}
+		if(!isFramePattern(inPattern)) return argumentError("--sequence-in needs a file pattern with one %d for the frame number, like frames/shot.%04d.exr");
+		if(!isFramePattern(outPattern)) return argumentError("--sequence-out <pattern with %d> is required beside --sequence-in");
+		if(inPattern == outPattern) return argumentError("--sequence-out would overwrite the --sequence-in frames");
+		if(!hasFirst || !hasLast || first < 0 || last < first) return argumentError("--first <a> and --last <b> with 0 <= a <= b are required beside --sequence-in");
+		if(radius < 1 || radius > 2) return argumentError("--temporal-radius must be 1 or 2");
+		if(a.m_prefilterSpikes) return argumentError("--sequence-in is not available with the spike prefilter: add -p 0");
+		if(a.m_patchRadius != 1 || a.m_searchWindowRadius != 6) return argumentError("--sequence-in needs -w 1 and -b 6 (neighbour frames support no other geometry)");
+		if(frameName(inPattern, first).length() <= 4) return argumentError("'" + frameName(inPattern, first) + "' is no .exr file name");
+
+		DenoiserParameters parameters;
+		parameters.m_histogramDistanceThreshold = a.m_histogramPatchDistanceThreshold;
+		parameters.m_patchRadius = a.m_patchRadius;
+		parameters.m_searchWindowRadius = a.m_searchWindowRadius;
+		parameters.m_minEigenValue = a.m_minEigenValue;
+		parameters.m_useRandomPixelOrder = a.m_useRandomPixelOrder;
+		parameters.m_markedPixelsSkippingProbability = a.m_markedPixelsSkippingProbability;
+		parameters.m_nbOfCores = a.m_nbOfCores;
+		parameters.m_useCuda = a.m_useCuda;
+		SequenceDenoiser sequence(a.m_nbOfScales, radius);
+		sequence.setParameters(parameters);
+		sequence.setOrderSeed(a.m_orderSeed);
+		sequence.setDevices(a.m_devices);
+		sequence.setZeroBadOutputValues(true);
+		if(!sequence.settingsAreOk())
+			return 1;
+		auto popReady = [&]() -> int
+		{
+			while(sequence.ready() > 0)
+			{
+				Deepimf out;
+				DenoiserOutputs outputs;
+				outputs.m_pDenoisedColors = &out;
+				if(!sequence.popFrame(outputs))
+					return 2;
+				checkAndPutToZeroNegativeInfNaNValues(out);
+				const string path = frameName(outPattern, first + int(sequence.getLastFrameIndex()));
+				if(!ImageIO::writeEXR(out, path.c_str()))
+				{
+					cerr << "Couldn't write " << path << ": " << ImageIO::lastError() << endl;
+					return 3;
+				}
+				cout << "Written denoised frame " << first + sequence.getLastFrameIndex() << " in file " << path << endl;
+			}
+			return 0;
+		};
+		for(int frame = first; frame <= last; ++frame)
+		{
+			const string path = frameName(inPattern, frame), stem = path.substr(0, path.length() - 4);
+			Deepimf color, histAndNbOfSamples, hist, nbOfSamples, cov;
+			if(!ImageIO::loadEXR(color, path.c_str())) return argumentError("couldn't load input color image file '" + path + "'");
+			if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamples, (stem + "_hist.exr").c_str())) return argumentError("couldn't load input histogram image file '" + stem + "_hist.exr'");
+			if(!ImageIO::loadMultiChannelsEXR(cov, (stem + "_cov.exr").c_str())) return argumentError("couldn't load input covariance matrix image file '" + stem + "_cov.exr'");
+			Utils::separateNbOfSamplesFromHistogram(hist, nbOfSamples, histAndNbOfSamples);
+			if(color.getDepth() == 1)
+			{	// grey colour file, as for -i
+				Deepimf rgb(color.getWidth(), color.getHeight(), 3);
+				for(int i = 0, n = color.getSize(); i < n; ++i)
+					rgb.get(3 * i) = rgb.get(3 * i + 1) = rgb.get(3 * i + 2) = color.get(i);
+				color = std::move(rgb);
+			}
+			DenoiserInputs inputs;
+			inputs.m_pColors = &color; inputs.m_pNbOfSamples = &nbOfSamples; inputs.m_pHistograms = &hist; inputs.m_pSampleCovariances = &cov;
+			if(!sequence.pushFrame(inputs))
+				return 2;
+			if(frame == last && !sequence.end())
+				return 2;
+			const int rc = popReady();
+			if(rc != 0)
+				return rc;
+		}
+		return 0;
+	}
+
 	int launchBayesianCollaborativeDenoising(int argc, const char** argv)
 	{
 		// --use-cuda 0 asks for the reference's CPU/OpenMP loop, which this build does not have (one product path: the HIP device).  The library
@@ -606,6 +746,9 @@ namespace
 					return 2;
 				}
 		}
+		for(int i = 1; i < argc; ++i)
+			if(string(argv[i]) == "--sequence-in" || string(argv[i]) == "--sequence-out")
+				return launchSequenceDenoising(argc, argv);
 		ProgramArguments args;
 		if(!parseProgramArguments(argc, argv, args))
 			return 1;

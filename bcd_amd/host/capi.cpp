@@ -4,6 +4,7 @@
 #include "DeviceSamplesAccumulator.h"
 #include "MultiscaleDenoiser.h"
 #include "SamplesAccumulator.h"
+#include "SequenceDenoiser.h"
 #include "SpikeRemovalFilter.h"
 #include "SyntheticScene.h"
 #include "Utils.h"
@@ -617,6 +618,67 @@ int bcdcore_denoise_temporal_motion(const float* col, const float* ns, const flo
 {
 	return denoiseTemporal(col, ns, hist, cov, nbCols, nbNs, nbHists, nbCovs, nbOfNeighbours, motions, hasMotion, W, H, D, nscales, tau, b, minEig, randomOrder,
 			skipProbability, seed, afterClear, out);
+}
+
+/// bcd::SequenceDenoiser over nbOfFrames frames held one behind the other in cols / nss / hists / covs: every frame is pushed, popped as soon as it is ready
+/// (after end() for the last ones) and written to outs in frame order.  unsupported: settings a sequence must refuse before any device is asked for -- bit 0
+/// addLayer, bit 1 addNeighbourFrame, bit 2 setMomentSelection(true), bit 3 setSpikePrefilter(2), bit 4 two devices, bit 5 a second frame of another size.
+/// Returns 1 when every push and pop succeeded and the frames came in order, else 0.
+int bcdcore_denoise_sequence(const float* cols, const float* nss, const float* hists, const float* covs, int nbOfFrames, int W, int H, int D, int nscales, int radius,
+		float tau, int w, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int unsupported, float* outs)
+{
+	const size_t npix = size_t(W) * H;
+	SequenceDenoiser sequence(nscales, radius);
+	DenoiserParameters p;
+	p.m_histogramDistanceThreshold = tau;
+	p.m_patchRadius = w;
+	p.m_searchWindowRadius = b;
+	p.m_minEigenValue = minEig;
+	p.m_useRandomPixelOrder = randomOrder != 0;
+	p.m_markedPixelsSkippingProbability = skipProbability;
+	sequence.setParameters(p);
+	sequence.setOrderSeed(seed);
+	Deepimf extra(W, H, 3), extraCov(W, H, 6), extraOut;
+	DenoiserInputs extraFrame;
+	if(unsupported & 1) sequence.addLayer(&extra, &extraCov, &extraOut);
+	if(unsupported & 2) sequence.addNeighbourFrame(extraFrame);
+	if(unsupported & 4) sequence.setMomentSelection(true);
+	if(unsupported & 8) sequence.setSpikePrefilter(2.f);
+	if(unsupported & 16) sequence.setDevices(std::vector<int>{ 0, 1 });
+	int popped = 0;
+	auto popReady = [&]() -> bool
+	{
+		while(sequence.ready() > 0)
+		{
+			Deepimf out;
+			DenoiserOutputs o;
+			o.m_pDenoisedColors = &out;
+			if(!sequence.popFrame(o) || sequence.getLastFrameIndex() != popped || out.getWidth() != W || out.getHeight() != H || out.getDepth() != 3)
+				return false;
+			out.copyDataTo(outs + size_t(popped) * npix * 3);
+			++popped;
+		}
+		return true;
+	};
+	for(int k = 0; k < nbOfFrames; ++k)
+	{
+		const bool otherSize = (unsupported & 32) && k == 1;
+		const int wk = otherSize ? W - 1 : W;
+		Deepimf c(wk, H, 3), n(wk, H, 1), h(wk, H, D), v(wk, H, 6);
+		if(!otherSize)
+		{
+			c.copyDataFrom(cols + k * npix * 3); n.copyDataFrom(nss + k * npix); h.copyDataFrom(hists + k * npix * D); v.copyDataFrom(covs + k * npix * 6);
+		}
+		DenoiserInputs f;
+		f.m_pColors = &c; f.m_pNbOfSamples = &n; f.m_pHistograms = &h; f.m_pSampleCovariances = &v;
+		if(!sequence.pushFrame(f))
+			return 0;
+		if(k == nbOfFrames - 1 && !sequence.end())
+			return 0;
+		if(!popReady())
+			return 0;
+	}
+	return popped == nbOfFrames ? 1 : 0;
 }
 
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames AND colour layers (addLayer, addNeighbourFrame, addNeighbourFrameLayer).  cols / covs hold

@@ -340,6 +340,59 @@ int bcd_hip_similarity_masks_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
 int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, const float *d_nsamples, const float *d_histograms_nb,
                                    const float *d_nsamples_nb, int W, int H, int D, int patch_radius, int search_radius, int line, int col, float *h_out);
 
+/* ---- a sequence denoised through a sliding window that reuses cross masks ("Sequences") ----
+ * Within one call the cross passes (frame -> neighbour) and (neighbour -> frame) look at different pixel pairs; between two calls they look at the SAME pairs
+ * with the roles swapped, and the cross distance is bit for bit symmetric under that swap (diff changes sign exactly and is squared, n1 n2 and b1 + b2
+ * commute, bins and patch offsets are summed in the same order).  So the cross masks of (B -> A) are a transposition of those of (A -> B).
+ *   _transpose_masks_cross: side = 2b + 1, nbits = side^2, words = (nbits + 31) / 32, delta_k = (k / side - b, k % side - b).  For every pixel p and every
+ *             k < nbits: if p + delta_k lies in the image, out(p) bit k = in(p + delta_k) bit (nbits - 1 - k); otherwise the bit is 0.  Bits >= nbits of the
+ *             last word are 0.  count(p) = popcount of the output mask; d_count_out may be NULL.  No main-pixel rule is applied: real cross masks never hold
+ *             a bit towards or at a pixel that is not a main pixel, so the transposed masks do not either.  d_mask_in / d_mask_out: W*H*words uint32 in the
+ *             layout of bcd_hip_similarity_masks_cross.  Search radius 1 .. 6 (larger: BCD_HIP_EUNSUPPORTED -- neighbour frames exist at b = 6 only).
+ *             Refused before any device work, with a message, the context staying usable: a null pointer, a non-positive size, b < 1, an output that
+ *             overlaps the input or the counts.  Synchronises.
+ * The sequence object keeps the last 2 radius + 1 frames resident, copies (or uploads) every frame once, builds its pyramid and per-pixel covariances once,
+ * and runs the cross pass of every unordered pair of frames once: popping frame t, a neighbour f > t is searched as bcd_hip_denoise_temporal searches it and
+ * the masks of every scale are kept with the pair (24 B per pixel and level); a neighbour f < t takes its masks from _transpose_masks_cross on the kept
+ * masks of (f, t), and no distance plane is written.
+ *   Definition.  Frame t of a sequence of T frames comes out as what bcd_hip_denoise_temporal returns for frame t with the neighbours
+ *   max(0, t - radius) .. min(T - 1, t + radius) except t, in ascending frame order, with the sequence's nb_scales and params (the same order_seed for every
+ *   frame).  The in-frame masks, every cross mask, |S|, the marking and the lists are bit for bit those of that call; the frame differs by the order of the
+ *   float atomics only.  After a pop bcd_hip_get_stats describes that frame as after that call.  A frame without neighbours (T = 1) is bcd_hip_denoise.
+ *   Protocol.  _push copies the four images (device to device; _push_host: from host memory) -- the caller's buffers are free again when it returns.  A push
+ *   of frame p is refused ("pop first") while p > next_pop + radius.  _end says no further frame follows.  _ready is the number of frames that can be popped
+ *   now: frame t can once frame t + radius is pushed, or after _end.  _pop writes the next frame (W*H*3 floats; _pop_host: to host memory) and its index.
+ *   _set_reuse(0) searches every pair directly (for comparisons and tests; default 1).  _last_masks copies, after a pop, the masks (and their counts) of
+ *   neighbour `neighbour` of the popped frame at `scale`: 0 the in-frame set, 1 .. the neighbours in ascending frame order.  _reset forgets every frame and
+ *   counter and keeps the buffers.  _destroy frees them; a sequence must be destroyed before its context.
+ *   Scope: histogram selection, one colour layer, patch radius 1, search radius 6, radius 1 .. 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS).  Colour layers, motion
+ *   fields (a warped neighbour breaks the symmetry), the feature gate, the moment selection, the spike prefilter, row bands and several GPUs are out.
+ *   Refused before any device work, with a message: what bcd_hip_denoise_temporal refuses; a radius outside 1 .. 2; any other geometry
+ *   (BCD_HIP_EUNSUPPORTED); a null image; a push beyond the ring or after _end; a pop that is not ready.
+ * A sequence handle is an opaque pointer, written by _create and passed as void *. */
+int bcd_hip_transpose_masks_cross(bcd_hip_ctx *ctx, const uint32_t *d_mask_in, int W, int H, int search_radius, uint32_t *d_mask_out, int32_t *d_count_out);
+/* (a struct tag, not a typedef: the entry point that fills it has the same name) */
+struct bcd_hip_sequence_info {
+    int64_t frames_pushed, frames_popped;
+    int64_t device_bytes;       /* held by the sequence's own buffers */
+    int64_t bytes_uploaded;     /* host to device, by _push_host */
+    int64_t pyramids_built;     /* one per pushed frame */
+    int64_t cross_computed;     /* cross passes run (all scales of a pair count as one) */
+    int64_t cross_transposed;   /* cross passes replaced by a transposition */
+};
+int bcd_hip_sequence_create(bcd_hip_ctx *ctx, int W, int H, int D, int nb_scales, int radius, const bcd_hip_params *prm, void **out);
+int bcd_hip_sequence_push(void *seq, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances);
+int bcd_hip_sequence_push_host(void *seq, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances);
+int bcd_hip_sequence_end(void *seq);
+int bcd_hip_sequence_ready(void *seq);
+int bcd_hip_sequence_pop(void *seq, float *d_out, int64_t *frame_index);
+int bcd_hip_sequence_pop_host(void *seq, float *h_out, int64_t *frame_index);
+int bcd_hip_sequence_set_reuse(void *seq, int on);
+int bcd_hip_sequence_last_masks(void *seq, int neighbour, int scale, uint32_t *d_mask, int32_t *d_count);
+int bcd_hip_sequence_info(void *seq, struct bcd_hip_sequence_info *info);
+int bcd_hip_sequence_reset(void *seq);
+void bcd_hip_sequence_destroy(void *seq);
+
 /* ---- the colour layers of a frame denoised with its neighbour frames ("Layers") ----
  * bcd_hip_denoise_layers and bcd_hip_denoise_temporal combined.  The inputs are
  *   - the frame's sample counts and histograms;
