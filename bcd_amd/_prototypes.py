@@ -111,6 +111,27 @@ class GuideImages(C.Structure):
     _fields_ = [("features", C.c_void_p), ("variances", C.c_void_p)]
 
 
+class SequenceMode(C.Structure):
+    """the mode of bcd_hip_sequence_create_mode ("Modes"); feature_floors: the address of a HOST array of nb_features floats"""
+    _c_name_ = "bcd_hip_sequence_mode"
+    _fields_ = [("nb_layers", C.c_int32), ("moments", C.c_int32), ("var_floor", C.c_float), ("nb_features", C.c_int32), ("feature_variances", C.c_int32),
+                ("feature_floors", C.c_void_p), ("feature_threshold", C.c_float), ("reserved", C.c_void_p)]
+
+
+class SequenceFrame(C.Structure):
+    """one frame of bcd_hip_sequence_push_frame[_host]; layers: the address of nb_layers FrameLayer records"""
+    _c_name_ = "bcd_hip_sequence_frame"
+    _fields_ = [("nsamples", C.c_void_p), ("histograms", C.c_void_p), ("layers", C.c_void_p), ("features", C.c_void_p), ("variances", C.c_void_p),
+                ("reserved", C.c_void_p)]
+
+
+class SequenceModeInfo(C.Structure):
+    """what bcd_hip_sequence_mode_info reports"""
+    _c_name_ = "bcd_hip_sequence_mode_info"
+    _fields_ = [("nb_layers", C.c_int32), ("moments", C.c_int32), ("nb_features", C.c_int32), ("feature_variances", C.c_int32),
+                ("cross_feature_passes", C.c_int64), ("reserved", C.c_int64)]
+
+
 class BandJob(C.Structure):
     _c_name_ = "bcd_hip_band_job"
     _fields_ = [("d_colors", C.c_void_p), ("d_nsamples", C.c_void_p), ("d_histograms", C.c_void_p), ("d_covariances", C.c_void_p),
@@ -278,6 +299,13 @@ PROTOTYPES = {
     "bcd_hip_window_distances_moments_cross": (I, [P, P, P, P, P, I, I, I, I, F, I, I, P]),
     "bcd_hip_denoise_temporal_moments": (I, [P, P, S(FrameLayers), I, P, I, I, I, S(Params), F, S(Layer), I, S(Guide), S(GuideImages)]),
     "bcd_hip_denoise_temporal_moments_host": (I, [P, P, S(FrameLayers), I, P, I, I, I, S(Params), F, S(Layer), I, S(Guide), S(GuideImages)]),
+    # ---- sequences in a mode: colour layers, the moment selection, the feature gate ("Modes")
+    "bcd_hip_sequence_create_mode": (I, [P, I, I, I, I, I, S(Params), S(SequenceMode), P]),
+    "bcd_hip_sequence_push_frame": (I, [P, S(SequenceFrame)]),
+    "bcd_hip_sequence_push_frame_host": (I, [P, S(SequenceFrame)]),
+    "bcd_hip_sequence_pop_layers": (I, [P, P, I, P]),
+    "bcd_hip_sequence_pop_layers_host": (I, [P, P, I, P]),
+    "bcd_hip_sequence_mode_info": (I, [P, S(SequenceModeInfo)]),
     # (row bands, for multi-GPU tiling)
     "bcd_hip_denoise_band": (I, [P, P, P, P, P, I, I, I, I, I, S(Params), U32, P, P]),
     "bcd_hip_denoise_bands": (I, [P, S(BandJob), I, S(Params)]),

@@ -292,12 +292,40 @@ def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, mi
     return rc != 0, out
 
 
-def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, unsupported=0):
+def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, unsupported=0, layers=None, features=None,
+                     feature_variances=None, feature_floors=(), feature_threshold=1.0, var_floor=1e-8, break_settings=0):
     """bcd::SequenceDenoiser: frames is a list of (col, ns, hist, cov) arrays of one size, pushed one by one and popped as they become ready; frame t comes out
     denoised with the frames t - radius .. t + radius that exist (what denoise_temporal returns for it with those neighbours in ascending order), every
     frame uploaded once and every pair of frames searched once.  unsupported: bits of settings the sequence must refuse (bcdcore_denoise_sequence).
-    Returns (ok, [denoised frame per frame])"""
+    Returns (ok, [denoised frame per frame]).
+    With `layers` (per frame a list of further (colours, covariances) beside the frame's own, which are layer 0), a frame whose hist is None (every frame:
+    the selection from means and covariances with `var_floor`) or `features` (per frame an (H, W, F) image; feature_variances the same or None, with
+    feature_floors and feature_threshold) the class runs with setFrameSettings(true) and the result is (ok, [[layer 0, layer 1, ...] per frame]);
+    break_settings: bits of settings that must be refused then (bcdcore_denoise_sequence_modes)"""
     T = len(frames)
+    if layers is not None or features is not None or frames[0][2] is None or break_settings:
+        H, W = np.asarray(frames[0][0]).shape[:2]
+        hist = frames[0][2] is not None
+        D = np.asarray(frames[0][2]).shape[2] if hist else 0
+        lay = [[(f[0], f[3])] + list(layers[k] if layers is not None else []) for k, f in enumerate(frames)]
+        L = len(lay[0])
+        if any(len(x) != L for x in lay) or any((f[2] is not None) != hist for f in frames):
+            raise ValueError("every frame brings the same layers, and histograms or none")
+        as32 = lambda a, d: np.asarray(a, np.float32).reshape(H, W, d)
+        cols = np.ascontiguousarray(np.stack([np.stack([as32(c, 3) for c, _ in x]) for x in lay]), np.float32)
+        covs = np.ascontiguousarray(np.stack([np.stack([as32(v, 6) for _, v in x]) for x in lay]), np.float32)
+        nss = np.ascontiguousarray(np.stack([as32(f[1], 1) for f in frames]), np.float32)
+        hists = np.ascontiguousarray(np.stack([as32(f[2], D) for f in frames]), np.float32) if hist else None
+        F = np.asarray(features[0]).shape[2] if features is not None else 0
+        feats = np.ascontiguousarray(np.stack([as32(a, F) for a in features]), np.float32) if features is not None else None
+        fvars = np.ascontiguousarray(np.stack([as32(a, F) for a in feature_variances]), np.float32) if feature_variances is not None else None
+        floors = np.ascontiguousarray(feature_floors, np.float32)
+        outs = np.zeros((T, L, H, W, 3), np.float32)
+        opt = lambda a: None if a is None else _fp(a)
+        rc = lib().bcdcore_denoise_sequence_modes(_fp(cols), _fp(nss), opt(hists), _fp(covs), opt(feats), opt(fvars), T, L, F, _fp(floors) if floors.size else None,
+                                                  int(floors.size), C.c_float(feature_threshold), C.c_float(var_floor), W, H, D, int(nscales), int(radius), C.c_float(tau),
+                                                  int(w), int(b), C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed), int(break_settings), _fp(outs))
+        return rc != 0, [[outs[k, j] for j in range(L)] for k in range(T)]
     H, W, D = frames[0][2].shape
     stack = lambda k, d: np.ascontiguousarray(np.stack([np.asarray(f[k], np.float32).reshape(H, W, d) for f in frames]), np.float32)
     outs = np.zeros((T, H, W, 3), np.float32)

@@ -227,6 +227,7 @@ struct bcd_hip_ctx {
             bool on = false;
             const float *f[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES] = {}, *v[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES] = {};
         } guide;
+        int64_t guide_cross_passes = 0; // cross feature passes launched so far (temporal_guide_gate: one per gated neighbour and scale); a sequence reports its share
     } temporal;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
     hipEvent_t ev_pyramid = nullptr;
@@ -348,7 +349,8 @@ bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const
 // null then.  pixcov is what per_pixel_cov() produces: temporal_select enqueues it ahead of the in-frame pass in that mode
 // transpose_from, mask_dst: null, or -- in a pop of a sequence (bcd_sequence.hip, "Sequences") -- the kept cross masks of the pair with the roles swapped, from
 // which this neighbour's masks come by k_masks_transpose in place of a cross pass, and the buffer that takes this neighbour's masks in place of
-// ctx->temporal.mask[f] (the sequence keeps them there).  With both null every call takes the branches it took before they existed
+// ctx->temporal.mask[f] (the sequence keeps them there).  With both null every call takes the branches it took before they existed.  In guide mode the kept
+// masks are the gated ones, so a neighbour with transpose_from passes no feature gate (the transposition distributes over the AND, which is idempotent)
 struct TemporalSelFrame {
     const float *ns, *hist; const uint8_t *valid; const float *feat = nullptr, *var = nullptr; const float *col = nullptr, *pixcov = nullptr;
     const uint32_t *transpose_from = nullptr; uint32_t *mask_dst = nullptr;
@@ -374,6 +376,16 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
 // wk.h_counters->lists when it returns
 int bayes_temporal(bcd_hip_ctx *ctx, Work &wk, const BcdFrameTable &t, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
                    float *d_sum, int32_t *d_count);
+// ---- defined in bcd_temporal_layers.hip: the layered estimate stage, shared with the pops of a sequence (bcd_sequence.hip)
+// one scale's estimate inputs: [f][k] = frame f (0: the frame itself), layer k
+struct LayerFrames {
+    int nf = 0, L = 0;
+    const float *col[BCD_MAX_NEIGHBOURS + 1][BCD_MAX_LAYERS], *pixcov[BCD_MAX_NEIGHBOURS + 1][BCD_MAX_LAYERS];
+    const uint32_t *mask[BCD_MAX_NEIGHBOURS + 1];
+};
+// bayes_temporal for L layers on one selection (see its definition); redo[k]: the items of layer k that took the redo list
+int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
+                          float *const *d_sum, int32_t *d_count, int32_t *redo);
 // the masks temporal_select left for frame f
 inline const uint32_t *temporal_mask(const bcd_hip_ctx *ctx, int f) { return (const uint32_t *)(f == 0 ? ctx->main.mask.p : ctx->temporal.mask[f].p); }
 // the tail of a scale (the stream is synchronised): the figures of wk.h_counters->lists and of the in-frame pass, and with profiling the four timers

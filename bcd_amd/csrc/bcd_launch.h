@@ -122,6 +122,8 @@ hipError_t bcd_launch_spike_rows(const float *col, const float *ns, const float 
 hipError_t bcd_launch_accumulate_samples(const float *samples, const float *weights, int64_t npix, int spp, int nbins, float gamma, float maxval, float *ons,
                                          float *omean, float *ocov, float *ohist, hipStream_t st);
 hipError_t bcd_launch_layers_pixel_cov_clear(const BcdLayerTable &t, int layers, const float *ns, int64_t npix, float *pixcov, float *sum, hipStream_t st);
+// ... the covariances alone (a push of a sequence; the pops clear the sums).  t.a[k] and pixcov 8 B aligned
+hipError_t bcd_launch_layers_pixel_cov(const BcdLayerTable &t, int layers, const float *ns, int64_t npix, float *pixcov, hipStream_t st);
 hipError_t bcd_launch_layers_finalize(const BcdLayerTable &t, int layers, const int32_t *cnt, int64_t npix, hipStream_t st);
 hipError_t bcd_launch_layers_downscale_avg(const BcdLayerTable &t, int layers, int W, int H, hipStream_t st);
 hipError_t bcd_launch_layers_downscale_cov(const BcdLayerTable &t, int layers, const float *ns, int W, int H, hipStream_t st);

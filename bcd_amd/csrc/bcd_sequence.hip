@@ -5,9 +5,14 @@
 // the cross masks of every pair (a, b), a < b <= a + R, from the pop of frame a until the pop of frame b, which takes them through k_masks_transpose
 // (k_masks_transpose.hip) instead of a second cross pass.  A pop runs the scales coarse to fine through the code of the frame call: temporal_select (with the
 // sequence's members of TemporalSelFrame), bayes_temporal, the finalisation, bcd_hip_merge.
+// A sequence in a mode (bcd_hip_sequence_create_mode; section 16, "Modes") holds L colour layers per slot, no histogram when it selects from means and
+// covariances, and the levels of the feature pyramid when it gates: the moment and the feature cross distances are symmetric as the histogram distance is, the
+// transposition distributes over the AND of the gate, so the kept (gated) masks are transposed as they are and a transposed neighbour runs neither a cross pass
+// nor temporal_guide_gate.  Its pops run temporal_select in the mode and the layered estimate of bcd_temporal_layers.hip (bayes_temporal_layers).
 #include "bcd_ctx.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -18,6 +23,8 @@ constexpr int SEQ_MAX_SLOTS = 2 * SEQ_MAX_RADIUS + 1;
 struct SeqSlot {
     DevBuf lv[MAX_SCALES][4]; // per level: colours, sample counts, histograms, covariances ([0]: the copy of the pushed frame)
     DevBuf pixcov[MAX_SCALES]; // per level: the per-pixel covariances
+    // ("Modes": colours, covariances and per-pixel covariances hold one slice per layer, [2] stays empty in a moments sequence)
+    DevBuf guide[MAX_SCALES][2]; // per level, with the feature gate: the features and their variances
     DevBuf pair[SEQ_MAX_RADIUS][MAX_SCALES]; // [d - 1]: the cross masks of (this frame -> this frame + d) at every level
     int64_t pair_frame[SEQ_MAX_RADIUS];      // ... valid for this frame index (-1: not kept)
 };
@@ -39,6 +46,14 @@ struct bcd_hip_sequence {
     int last_nb = 0;
     int64_t last_nbs[BCD_HIP_MAX_NEIGHBOURS];
     int64_t held = 0, uploaded = 0, pyramids = 0, computed = 0, transposed = 0;
+    // ---- the mode (bcd_hip_sequence_create_mode; DESIGN.md section 16, "Modes").  A sequence of bcd_hip_sequence_create is L = 1, histograms, no gate
+    bool by_mode = false;                    // created by bcd_hip_sequence_create_mode: the _frame / _layers calls are open
+    int L = 1, F = 0;                        // colour layers; feature channels (0: no gate)
+    bool moments = false, fvar = false;      // selection from means and covariances (D = 0, no histogram stored); every frame brings feature variances
+    float var_floor = 0.f, floors[BCD_GUIDE_MAX_CHANNELS] = {}, ftau = 0.f;
+    int64_t feature_passes = 0;              // cross feature passes its pops launched
+    bool plain() const { return L == 1 && !moments && F == 0; }   // today's sequence, on today's path
+    bool layered() const { return moments || L > 1; }             // the estimate of bcd_temporal_layers.hip (one layer of histograms: that of bcd_temporal.hip)
 };
 
 namespace {
@@ -59,7 +74,7 @@ void forget(bcd_hip_sequence *q)
     q->pushed = q->popped = 0;
     q->ended = false;
     q->last_frame = -1; q->last_nb = 0;
-    q->uploaded = q->pyramids = q->computed = q->transposed = 0;
+    q->uploaded = q->pyramids = q->computed = q->transposed = q->feature_passes = 0;
     for (SeqSlot &s : q->slot) for (int64_t &f : s.pair_frame) f = -1;
 }
 
@@ -75,6 +90,7 @@ int push(bcd_hip_sequence *q, const float *col, const float *ns, const float *hi
 {
     if (!q) return BCD_HIP_EINVAL;
     bcd_hip_ctx *ctx = q->ctx;
+    if (!q->plain()) return bad(ctx, "this sequence was created in a mode (bcd_hip_sequence_create_mode): its frames are pushed by bcd_hip_sequence_push_frame");
     if (!col || !ns || !hist || !cov) return bad(ctx, "null image pointer");
     if (q->ended) return bad(ctx, "the sequence has ended: no further frame can be pushed (bcd_hip_sequence_reset starts another)");
     if (q->pushed > q->popped + q->R) return bad(ctx, "pop first: the ring holds every frame the next pop needs");
@@ -107,6 +123,172 @@ int push(bcd_hip_sequence *q, const float *col, const float *ns, const float *hi
     return BCD_HIP_OK;
 }
 
+// a push in a mode: the frame's images into its slot, every pyramid level by the reducers of the matching frame call (layers_run of bcd_temporal_layers.hip
+// for a layered estimate, temporal_run for one layer of histograms; the feature levels by guide_begin's rule), the per-pixel covariances of all layers of a
+// level in one launch; synchronised
+int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyKind kind)
+{
+    if (!q) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = q->ctx;
+    if (!q->by_mode) return bad(ctx, "this sequence was created by bcd_hip_sequence_create: its frames are pushed by bcd_hip_sequence_push");
+    if (!fm) return bad(ctx, "null frame");
+    if (fm->reserved) return bad(ctx, "the reserved pointer of a frame must be NULL");
+    if (!fm->nsamples) return bad(ctx, "null image pointer");
+    if (q->moments && fm->histograms) return bad(ctx, "a moments sequence takes no histograms: the frame's histograms must be NULL");
+    if (!q->moments && !fm->histograms) return bad(ctx, "a histogram sequence needs the frame's histograms");
+    if (!fm->layers) return bad(ctx, "null layer list");
+    for (int k = 0; k < q->L; ++k) if (!fm->layers[k].d_colors || !fm->layers[k].d_covariances) return bad(ctx, "null image pointer in a layer");
+    if (q->F == 0 && (fm->features || fm->variances)) return bad(ctx, "the sequence has no feature gate: the frame's features and variances must be NULL");
+    if (q->F > 0 && !fm->features) return bad(ctx, "null feature image");
+    if (q->F > 0 && (fm->variances != nullptr) != q->fvar) return bad(ctx, "feature variances must be given for every frame or for none, as the mode says");
+    if (q->plain()) return push(q, fm->layers[0].d_colors, fm->nsamples, fm->histograms, fm->layers[0].d_covariances, kind);
+    if (q->ended) return bad(ctx, "the sequence has ended: no further frame can be pushed (bcd_hip_sequence_reset starts another)");
+    if (q->pushed > q->popped + q->R) return bad(ctx, "pop first: the ring holds every frame the next pop needs");
+    DEVICE_GUARD(ctx);
+    hipStream_t st = ctx->main.stream;
+    SeqSlot &sl = q->slot[q->pushed % q->N];
+    const int D = q->D, L = q->L, F = q->F;
+    const size_t f4 = sizeof(float);
+    for (int s = 0; s < q->S; ++s) {
+        const size_t np = (size_t)q->ws[s] * q->hs[s];
+        RCCHK(seq_ensure(q, sl.lv[s][0], L * np * 3 * f4));
+        RCCHK(seq_ensure(q, sl.lv[s][1], np * f4));
+        if (!q->moments) RCCHK(seq_ensure(q, sl.lv[s][2], np * D * f4));
+        RCCHK(seq_ensure(q, sl.lv[s][3], L * np * 6 * f4));
+        RCCHK(seq_ensure(q, sl.pixcov[s], L * np * 6 * f4));
+        if (F) RCCHK(seq_ensure(q, sl.guide[s][0], np * F * f4));
+        if (F && q->fvar) RCCHK(seq_ensure(q, sl.guide[s][1], np * F * f4));
+        float *col = (float *)sl.lv[s][0].p, *ns = (float *)sl.lv[s][1].p, *hist = (float *)sl.lv[s][2].p, *cov = (float *)sl.lv[s][3].p;
+        float *feat = (float *)sl.guide[s][0].p, *var = (float *)sl.guide[s][1].p;
+        if (s == 0) {
+            int64_t bytes = (int64_t)(np * f4);
+            HIPCHK(ctx, hipMemcpyAsync(ns, fm->nsamples, np * f4, kind, st));
+            if (!q->moments) { HIPCHK(ctx, hipMemcpyAsync(hist, fm->histograms, np * D * f4, kind, st)); bytes += (int64_t)(np * D * f4); }
+            for (int k = 0; k < L; ++k) {
+                HIPCHK(ctx, hipMemcpyAsync(col + k * np * 3, fm->layers[k].d_colors, np * 3 * f4, kind, st));
+                HIPCHK(ctx, hipMemcpyAsync(cov + k * np * 6, fm->layers[k].d_covariances, np * 6 * f4, kind, st));
+                bytes += (int64_t)(np * 9 * f4);
+            }
+            if (F) { HIPCHK(ctx, hipMemcpyAsync(feat, fm->features, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
+            if (F && q->fvar) { HIPCHK(ctx, hipMemcpyAsync(var, fm->variances, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
+            if (kind == hipMemcpyHostToDevice) q->uploaded += bytes;
+        } else {
+            const int wf = q->ws[s - 1], hf = q->hs[s - 1];
+            const size_t npf = (size_t)wf * hf;
+            const float *fcol = (const float *)sl.lv[s - 1][0].p, *fns = (const float *)sl.lv[s - 1][1].p, *fhist = (const float *)sl.lv[s - 1][2].p;
+            const float *fcov = (const float *)sl.lv[s - 1][3].p;
+            HIPCHK(ctx, bcd_launch_downscale(0, fns, wf, hf, 1, ns, st));
+            if (!q->moments) HIPCHK(ctx, bcd_launch_downscale(0, fhist, wf, hf, D, hist, st));
+            if (q->layered()) {
+                BcdLayerTable t = {};
+                for (int k = 0; k < L; ++k) { t.a[k] = fcol + k * npf * 3; t.o[k] = col + k * np * 3; }
+                HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, wf, hf, st));
+                for (int k = 0; k < L; ++k) { t.a[k] = fcov + k * npf * 6; t.o[k] = cov + k * np * 6; }
+                HIPCHK(ctx, bcd_launch_layers_downscale_cov(t, L, fns, wf, hf, st));
+            } else {
+                HIPCHK(ctx, bcd_launch_downscale(1, fcol, wf, hf, 3, col, st));
+                HIPCHK(ctx, bcd_launch_downscale_cov(fcov, fns, wf, hf, cov, st));
+            }
+            if (F) HIPCHK(ctx, bcd_launch_downscale(1, (const float *)sl.guide[s - 1][0].p, wf, hf, F, feat, st));
+            if (F && q->fvar) { // (the variance of a mean of four)
+                HIPCHK(ctx, bcd_launch_downscale(1, (const float *)sl.guide[s - 1][1].p, wf, hf, F, var, st));
+                HIPCHK(ctx, bcd_launch_scale_inplace(var, 0.25f, (int64_t)np * F, st));
+            }
+        }
+        if (q->layered()) {
+            BcdLayerTable t = {};
+            for (int k = 0; k < L; ++k) t.a[k] = cov + k * np * 6;
+            HIPCHK(ctx, bcd_launch_layers_pixel_cov(t, L, ns, (int64_t)np, (float *)sl.pixcov[s].p, st));
+        } else {
+            HIPCHK(ctx, bcd_launch_pixel_cov(cov, ns, (int64_t)np, (float *)sl.pixcov[s].p, st));
+        }
+    }
+    for (int64_t &f : sl.pair_frame) f = -1; // (the slot's earlier frame: its pairs were consumed R pops ago)
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ++q->pushed;
+    ++q->pyramids;
+    return BCD_HIP_OK;
+}
+
+// what the selection stage of scale s reads of frame t (sel[0], fr[0]) and of its neighbours nbs[0 .. nn) in ascending order, with the buffers that take their
+// masks: a neighbour above t is searched as the frame call searches it and its (gated) masks stay with the pair (t, f); one below takes the kept masks of (f, t)
+int pop_frames(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, const SeqSlot **fr, TemporalSelFrame *sel)
+{
+    const size_t mb = mask_bytes((size_t)q->ws[s] * q->hs[s], q->prm.search_radius);
+    SeqSlot &me = q->slot[t % q->N];
+    auto level = [&](const SeqSlot &sl) {
+        TemporalSelFrame f = { (const float *)sl.lv[s][1].p, q->moments ? nullptr : (const float *)sl.lv[s][2].p, nullptr };
+        if (q->F) { f.feat = (const float *)sl.guide[s][0].p; f.var = q->fvar ? (const float *)sl.guide[s][1].p : nullptr; }
+        if (q->moments) { f.col = (const float *)sl.lv[s][0].p; f.pixcov = (const float *)sl.pixcov[s].p; } // (the guide layer is layer 0: the first slice)
+        return f;
+    };
+    fr[0] = &me;
+    sel[0] = level(me);
+    for (int i = 1, below = 0; i <= nn; ++i) {
+        const int64_t f = nbs[i - 1];
+        SeqSlot &nb = q->slot[f % q->N];
+        fr[i] = &nb;
+        sel[i] = level(nb);
+        if (f > t) {
+            DevBuf &keep = me.pair[f - t - 1][s];
+            RCCHK(seq_ensure(q, keep, mb));
+            sel[i].mask_dst = (uint32_t *)keep.p;
+        } else {
+            DevBuf &dst = q->low[below++][s];
+            RCCHK(seq_ensure(q, dst, mb));
+            sel[i].mask_dst = (uint32_t *)dst.p;
+            if (q->reuse && nb.pair_frame[t - f - 1] == f) sel[i].transpose_from = (const uint32_t *)nb.pair[t - f - 1][s].p;
+        }
+    }
+    return BCD_HIP_OK;
+}
+
+// one scale of a pop with a layered estimate: temporal_layers_scale (bcd_temporal_layers.hip) on the slots -- the per-pixel covariances are the pushes', the
+// per-pop part of k_layers_pixel_cov_clear is the clear of the sums
+int pop_scale_layers(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, float *const *d_out)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    Work &wk = ctx->main;
+    auto &tp = ctx->temporal;
+    const int W = q->ws[s], H = q->hs[s], b = q->prm.search_radius, nf = nn + 1, L = q->L;
+    const size_t npix = (size_t)W * H, mb = mask_bytes(npix, b);
+    RCCHK(ensure(ctx, tp.lay_sum, (size_t)L * npix * 3 * sizeof(float)));
+    RCCHK(seq_ensure(q, q->self[s], mb));
+    const SeqSlot *fr[BCD_HIP_MAX_NEIGHBOURS + 1];
+    TemporalSelFrame sel[BCD_HIP_MAX_NEIGHBOURS + 1];
+    RCCHK(pop_frames(q, t, nbs, nn, s, fr, sel));
+    TemporalPath path;
+    RCCHK(temporal_select(ctx, sel, nf, W, H, q->D, &q->prm, s, [&]() -> int {
+        HIPCHK(ctx, hipMemsetAsync(tp.lay_sum.p, 0, (size_t)L * npix * 3 * sizeof(float), wk.stream));
+        return BCD_HIP_OK;
+    }, &path));
+    HIPCHK(ctx, hipMemcpyAsync(q->self[s].p, wk.mask.p, mb, hipMemcpyDeviceToDevice, wk.stream));
+    LayerFrames lf;
+    lf.nf = nf; lf.L = L;
+    float *sum[BCD_MAX_LAYERS];
+    for (int k = 0; k < L; ++k) sum[k] = (float *)tp.lay_sum.p + (size_t)k * npix * 3;
+    for (int f = 0; f < nf; ++f) {
+        for (int k = 0; k < L; ++k) {
+            lf.col[f][k] = (const float *)fr[f]->lv[s][0].p + (size_t)k * npix * 3;
+            lf.pixcov[f][k] = (const float *)fr[f]->pixcov[s].p + (size_t)k * npix * 6;
+        }
+        lf.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : sel[f].mask_dst;
+    }
+    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
+    int32_t redo[BCD_MAX_LAYERS] = {};
+    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, q->prm.min_eigen_value, sum, (int32_t *)wk.cnt.p, redo));
+    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
+    {
+        BcdLayerTable tb = {};
+        for (int k = 0; k < L; ++k) { tb.a[k] = sum[k]; tb.o[k] = d_out[k]; }
+        HIPCHK(ctx, bcd_launch_layers_finalize(tb, L, (const int32_t *)wk.cnt.p, (int64_t)npix, wk.stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    temporal_stats_tail(ctx, s, path);
+    for (int k = 0; k < L; ++k) ctx->layer_spectral[s][k] = redo[k];
+    return BCD_HIP_OK;
+}
+
 // one scale of a pop: frame t with the neighbours nbs[0 .. nn) in ascending order
 int pop_scale(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, float *d_out)
 {
@@ -118,25 +300,7 @@ int pop_scale(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s,
     RCCHK(seq_ensure(q, q->self[s], mb));
     const SeqSlot *fr[BCD_HIP_MAX_NEIGHBOURS + 1];
     TemporalSelFrame sel[BCD_HIP_MAX_NEIGHBOURS + 1];
-    SeqSlot &me = q->slot[t % q->N];
-    fr[0] = &me;
-    sel[0] = { (const float *)me.lv[s][1].p, (const float *)me.lv[s][2].p, nullptr };
-    for (int i = 1, below = 0; i < nf; ++i) {
-        const int64_t f = nbs[i - 1];
-        SeqSlot &nb = q->slot[f % q->N];
-        fr[i] = &nb;
-        sel[i] = { (const float *)nb.lv[s][1].p, (const float *)nb.lv[s][2].p, nullptr };
-        if (f > t) { // searched as the frame call searches it; the masks stay with the pair (t, f)
-            DevBuf &keep = me.pair[f - t - 1][s];
-            RCCHK(seq_ensure(q, keep, mb));
-            sel[i].mask_dst = (uint32_t *)keep.p;
-        } else {     // the pair (f, t) was searched by the pop of f
-            DevBuf &dst = q->low[below++][s];
-            RCCHK(seq_ensure(q, dst, mb));
-            sel[i].mask_dst = (uint32_t *)dst.p;
-            if (q->reuse && nb.pair_frame[t - f - 1] == f) sel[i].transpose_from = (const uint32_t *)nb.pair[t - f - 1][s].p;
-        }
-    }
+    RCCHK(pop_frames(q, t, nbs, nn, s, fr, sel));
     TemporalPath path;
     RCCHK(temporal_select(ctx, sel, nf, W, H, q->D, &q->prm, s, []() -> int { return BCD_HIP_OK; } /* (computed by the pushes) */, &path));
     HIPCHK(ctx, hipMemcpyAsync(q->self[s].p, wk.mask.p, mb, hipMemcpyDeviceToDevice, wk.stream));
@@ -157,8 +321,80 @@ int pop_scale(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s,
     return BCD_HIP_OK;
 }
 
-// the next frame into d_out (device memory)
-int pop(bcd_hip_sequence *q, float *d_out, int64_t *frame_index)
+// a frame without neighbours in a mode: the matching single-frame call on the slot's copies
+int pop_single(bcd_hip_sequence *q, const SeqSlot &me, float *const *d_out)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    const size_t npix = (size_t)q->W * q->H;
+    bcd_hip_layer lay[BCD_HIP_MAX_LAYERS];
+    for (int k = 0; k < q->L; ++k) lay[k] = { (const float *)me.lv[0][0].p + k * npix * 3, (const float *)me.lv[0][3].p + k * npix * 6, d_out[k] };
+    const float *ns = (const float *)me.lv[0][1].p, *hist = q->moments ? nullptr : (const float *)me.lv[0][2].p;
+    if (q->F) {
+        const bcd_hip_guide g = { (const float *)me.guide[0][0].p, q->fvar ? (const float *)me.guide[0][1].p : nullptr, q->F, q->floors, q->ftau };
+        return bcd_hip_denoise_guided(ctx, ns, hist, q->W, q->H, q->D, q->S, &q->prm, q->var_floor, lay, q->L, &g, nullptr);
+    }
+    if (q->moments) return bcd_hip_denoise_moments(ctx, ns, q->W, q->H, q->S, &q->prm, q->var_floor, lay, q->L, nullptr);
+    return bcd_hip_denoise_layers(ctx, ns, hist, q->W, q->H, q->D, q->S, &q->prm, lay, q->L);
+}
+
+// the scales of a pop in a mode, coarse to fine: the context carries the mode as it does inside the matching frame call (the moment selection, the guide's
+// channels, floors and threshold) while they run
+int pop_scales_mode(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, float *const *d_out)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    const int L = q->L, S = q->S;
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    struct ModeOn {
+        bcd_hip_ctx *c;
+        ModeOn(bcd_hip_ctx *ctx, const bcd_hip_sequence *q) : c(ctx)
+        {
+            if (q->F) {
+                auto &G = c->guide;
+                G.on = false; G.F = q->F; G.tau = q->ftau;
+                for (int k = 0; k < BCD_GUIDE_MAX_CHANNELS; ++k) G.floors[k] = k < q->F ? q->floors[k] : 0.f;
+            }
+            c->temporal.guide.on = false; // (the slots' levels travel in TemporalSelFrame)
+            c->moments.on = q->moments; c->moments.var_floor = q->var_floor;
+        }
+        ~ModeOn() { c->moments.on = false; }
+    } mode_on(ctx, q);
+    const int64_t passes = tp.guide_cross_passes;
+    memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+    ctx->layer_count = 0;
+    for (int s = 1; s < S; ++s) RCCHK(seq_ensure(q, q->out[s], (size_t)L * q->ws[s] * q->hs[s] * 3 * sizeof(float)));
+    float *outs[MAX_SCALES][BCD_MAX_LAYERS];
+    for (int s = 0; s < S; ++s)
+        for (int k = 0; k < L; ++k) outs[s][k] = s == 0 ? d_out[k] : (float *)q->out[s].p + (size_t)k * q->ws[s] * q->hs[s] * 3;
+    int rc = BCD_HIP_OK;
+    for (int s = S - 1; s >= 0 && rc == BCD_HIP_OK; --s) {
+        if (!q->layered()) { // one layer of histograms with the gate: the estimate and the merge of bcd_hip_denoise_temporal
+            rc = pop_scale(q, t, nbs, nn, s, outs[s][0]);
+            if (rc == BCD_HIP_OK && s < S - 1) rc = bcd_hip_merge(ctx, outs[s][0], q->ws[s], q->hs[s], outs[s + 1][0], 3);
+            continue;
+        }
+        rc = pop_scale_layers(q, t, nbs, nn, s, outs[s]);
+        if (rc != BCD_HIP_OK || s == S - 1) continue;
+        // the merge is mergeOutputs, one pair of launches for all layers (as in layers_run)
+        const int w2 = q->ws[s] / 2, h2 = q->hs[s] / 2;
+        const size_t slice = (size_t)w2 * h2 * 3;
+        RCCHK(ensure(ctx, tp.lay_tmp_lo, (size_t)L * slice * sizeof(float)));
+        BcdLayerTable tb = {};
+        for (int k = 0; k < L; ++k) { tb.a[k] = outs[s][k]; tb.o[k] = (float *)tp.lay_tmp_lo.p + k * slice; }
+        HIPCHK(ctx, bcd_launch_layers_downscale_avg(tb, L, q->ws[s], q->hs[s], st));
+        for (int k = 0; k < L; ++k) { tb.a[k] = (const float *)tp.lay_tmp_lo.p + k * slice; tb.b[k] = outs[s + 1][k]; tb.o[k] = outs[s][k]; }
+        HIPCHK(ctx, bcd_launch_layers_merge(tb, L, w2, h2, q->ws[s], q->hs[s], st));
+    }
+    q->feature_passes += tp.guide_cross_passes - passes;
+    RCCHK(rc);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (!q->layered()) for (int s = 0; s < S; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses; // (as the frame call of one layer reports it)
+    ctx->layer_count = L;
+    return BCD_HIP_OK;
+}
+
+// the next frame into d_out[0 .. L) (device memory)
+int pop(bcd_hip_sequence *q, float *const *d_out, int64_t *frame_index)
 {
     bcd_hip_ctx *ctx = q->ctx;
     const int64_t t = q->popped, last = q->pushed - 1;
@@ -166,14 +402,17 @@ int pop(bcd_hip_sequence *q, float *d_out, int64_t *frame_index)
     int nn = 0;
     for (int64_t f = std::max<int64_t>(0, t - q->R); f <= std::min(last, t + q->R); ++f) if (f != t) nbs[nn++] = f;
     SeqSlot &me = q->slot[t % q->N];
-    if (nn == 0) { // a sequence of one frame: the plain call on the slot's copy
+    if (nn == 0 && !q->plain()) {
+        RCCHK(pop_single(q, me, d_out));
+    } else if (nn == 0) { // a sequence of one frame: the plain call on the slot's copy
         RCCHK(bcd_hip_denoise(ctx, (const float *)me.lv[0][0].p, (const float *)me.lv[0][1].p, (const float *)me.lv[0][2].p, (const float *)me.lv[0][3].p, q->W, q->H, q->D,
-                              q->S, &q->prm, d_out));
+                              q->S, &q->prm, d_out[0]));
     } else {
         DEVICE_GUARD(ctx);
-        for (int s = 1; s < q->S; ++s) RCCHK(seq_ensure(q, q->out[s], (size_t)q->ws[s] * q->hs[s] * 3 * sizeof(float)));
-        for (int s = q->S - 1; s >= 0; --s) { // coarse to fine, merged as in bcd_hip_denoise_temporal
-            float *out = s == 0 ? d_out : (float *)q->out[s].p;
+        if (!q->plain()) RCCHK(pop_scales_mode(q, t, nbs, nn, d_out));
+        for (int s = 1; q->plain() && s < q->S; ++s) RCCHK(seq_ensure(q, q->out[s], (size_t)q->ws[s] * q->hs[s] * 3 * sizeof(float)));
+        for (int s = q->S - 1; q->plain() && s >= 0; --s) { // coarse to fine, merged as in bcd_hip_denoise_temporal
+            float *out = s == 0 ? d_out[0] : (float *)q->out[s].p;
             RCCHK(pop_scale(q, t, nbs, nn, s, out));
             if (s < q->S - 1) RCCHK(bcd_hip_merge(ctx, out, q->ws[s], q->hs[s], (const float *)q->out[s + 1].p, 3));
         }
@@ -279,22 +518,134 @@ int bcd_hip_sequence_pop(void *seq, float *d_out, int64_t *frame_index)
 {
     bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
     if (!q) return BCD_HIP_EINVAL;
+    if (!q->plain()) return bad(q->ctx, "this sequence was created in a mode (bcd_hip_sequence_create_mode): its frames are popped by bcd_hip_sequence_pop_layers");
     RCCHK(check_pop(q, d_out));
-    return pop(q, d_out, frame_index);
+    return pop(q, &d_out, frame_index);
+}
+
+// the layers of the next frame through the sequence's own device copy to host memory
+static int pop_to_host(bcd_hip_sequence *q, float *const *h_out, int64_t *frame_index)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    DEVICE_GUARD(ctx);
+    const size_t bytes = (size_t)q->W * q->H * 3 * sizeof(float);
+    RCCHK(seq_ensure(q, q->host_out, q->L * bytes));
+    float *dev[BCD_HIP_MAX_LAYERS];
+    for (int k = 0; k < q->L; ++k) dev[k] = (float *)q->host_out.p + (size_t)k * q->W * q->H * 3;
+    RCCHK(pop(q, dev, frame_index));
+    for (int k = 0; k < q->L; ++k) HIPCHK(ctx, hipMemcpyAsync(h_out[k], dev[k], bytes, hipMemcpyDeviceToHost, ctx->main.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
 }
 
 int bcd_hip_sequence_pop_host(void *seq, float *h_out, int64_t *frame_index)
 {
     bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
     if (!q) return BCD_HIP_EINVAL;
+    if (!q->plain()) return bad(q->ctx, "this sequence was created in a mode (bcd_hip_sequence_create_mode): its frames are popped by bcd_hip_sequence_pop_layers_host");
     RCCHK(check_pop(q, h_out));
+    return pop_to_host(q, &h_out, frame_index);
+}
+
+// ---- "Modes": colour layers, the moment selection, the feature gate -------------------------------------------------------------
+int bcd_hip_sequence_create_mode(bcd_hip_ctx *ctx, int W, int H, int D, int nb_scales, int radius, const bcd_hip_params *prm, const bcd_hip_sequence_mode *mode, void **out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!out) return bad(ctx, "null handle pointer");
+    *out = nullptr;
+    if (!mode) return bad(ctx, "null mode");
+    if (mode->reserved) return bad(ctx, "the reserved pointer of a mode must be NULL");
+    const int L = mode->nb_layers, F = mode->nb_features;
+    if (L < 1 || L > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    if (F < 0 || F > BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "the number of feature channels must be between 1 and 8 (BCD_HIP_GUIDE_MAX_CHANNELS), or 0 for no feature gate");
+    if ((mode->moments != 0 && mode->moments != 1) || (mode->feature_variances != 0 && mode->feature_variances != 1)) return bad(ctx, "the flags of a mode must be 0 or 1");
+    const bool moments = mode->moments == 1, fvar = mode->feature_variances == 1;
+    if (moments && (!(mode->var_floor >= 0.f) || !std::isfinite(mode->var_floor))) return bad(ctx, "the variance floor must be finite and not negative");
+    if (F == 0 && fvar) return bad(ctx, "feature variances without feature channels");
+    if (L == 1 && !moments && F == 0) { // today's sequence, on today's path
+        RCCHK(bcd_hip_sequence_create(ctx, W, H, D, nb_scales, radius, prm, out));
+        ((bcd_hip_sequence *)*out)->by_mode = true;
+        return BCD_HIP_OK;
+    }
+    RCCHK(check_params(ctx, W, H, moments ? 1 : D, prm)); // ("Moments": no histogram, D is not looked at)
+    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
+    if (radius < 1 || radius > SEQ_MAX_RADIUS) return bad(ctx, "the temporal radius of a sequence must be 1 or 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS)");
+    if (prm->patch_radius != 1 || prm->search_radius != 6) {
+        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
+        ws /= 2; hs /= 2;
+        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
+    }
+    if (F > 0) { // what bcd_hip_denoise_temporal_guided refuses of a guide (the images come with the frames: any address stands for them here)
+        static const float present = 0.f;
+        const bcd_hip_guide g = { &present, fvar ? &present : nullptr, F, mode->feature_floors, mode->feature_threshold };
+        if ((int64_t)W * H >= (1ll << 31) / BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "image too large for 32-bit DeepImage indices");
+        RCCHK(check_guide(ctx, &g, prm->search_radius));
+        if (bcd_pairdist_guide_cross_band(F, fvar, prm->search_radius) < 1) {
+            set_err(ctx, "the cross feature distance kernel cannot be launched for this number of channels and search radius (LDS)");
+            return BCD_HIP_EUNSUPPORTED;
+        }
+    }
+    bcd_hip_sequence *q = new (std::nothrow) bcd_hip_sequence;
+    if (!q) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
+    q->ctx = ctx;
+    q->W = W; q->H = H; q->D = moments ? 0 : D; q->S = nb_scales; q->R = radius; q->N = 2 * radius + 1;
+    q->prm = *prm;
+    for (int s = 0; s < MAX_SCALES; ++s) { q->ws[s] = s ? q->ws[s - 1] / 2 : W; q->hs[s] = s ? q->hs[s - 1] / 2 : H; }
+    q->by_mode = true;
+    q->L = L; q->F = F; q->moments = moments; q->fvar = fvar;
+    q->var_floor = moments ? mode->var_floor : 0.f;
+    for (int k = 0; k < F; ++k) q->floors[k] = mode->feature_floors[k];
+    q->ftau = F ? mode->feature_threshold : 0.f;
+    forget(q);
+    *out = q;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_sequence_push_frame(void *seq, const bcd_hip_sequence_frame *frame) { return push_frame((bcd_hip_sequence *)seq, frame, hipMemcpyDeviceToDevice); }
+
+int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *frame) { return push_frame((bcd_hip_sequence *)seq, frame, hipMemcpyHostToDevice); }
+
+static int check_pop_layers(bcd_hip_sequence *q, float *const *outs, int nb_layers)
+{
     bcd_hip_ctx *ctx = q->ctx;
-    DEVICE_GUARD(ctx);
-    const size_t bytes = (size_t)q->W * q->H * 3 * sizeof(float);
-    RCCHK(seq_ensure(q, q->host_out, bytes));
-    RCCHK(pop(q, (float *)q->host_out.p, frame_index));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, q->host_out.p, bytes, hipMemcpyDeviceToHost, ctx->main.stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    if (!q->by_mode) return bad(ctx, "this sequence was created by bcd_hip_sequence_create: its frames are popped by bcd_hip_sequence_pop");
+    if (!outs) return bad(ctx, "null output list");
+    if (nb_layers != q->L) return bad(ctx, "the number of outputs is not the number of layers of the sequence");
+    for (int k = 0; k < nb_layers; ++k) {
+        if (!outs[k]) return bad(ctx, "null output pointer");
+        for (int j = 0; j < k; ++j)
+            if (bytes_overlap(outs[k], (size_t)q->W * q->H * 3 * sizeof(float), outs[j], (size_t)q->W * q->H * 3 * sizeof(float))) return bad(ctx, "two layers share (part of) an output image");
+    }
+    return check_pop(q, outs[0]);
+}
+
+int bcd_hip_sequence_pop_layers(void *seq, float *const *d_outs, int nb_layers, int64_t *frame_index)
+{
+    bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
+    if (!q) return BCD_HIP_EINVAL;
+    RCCHK(check_pop_layers(q, d_outs, nb_layers));
+    return pop(q, d_outs, frame_index);
+}
+
+int bcd_hip_sequence_pop_layers_host(void *seq, float *const *h_outs, int nb_layers, int64_t *frame_index)
+{
+    bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
+    if (!q) return BCD_HIP_EINVAL;
+    RCCHK(check_pop_layers(q, h_outs, nb_layers));
+    return pop_to_host(q, h_outs, frame_index);
+}
+
+int bcd_hip_sequence_mode_info(void *seq, struct bcd_hip_sequence_mode_info *info)
+{
+    const bcd_hip_sequence *q = (const bcd_hip_sequence *)seq;
+    if (!q) return BCD_HIP_EINVAL;
+    if (!info) return bad(q->ctx, "null info pointer");
+    info->nb_layers = q->L; info->moments = q->moments; info->nb_features = q->F; info->feature_variances = q->fvar;
+    info->cross_feature_passes = q->feature_passes;
+    info->reserved = 0;
     return BCD_HIP_OK;
 }
 
@@ -313,7 +664,9 @@ int bcd_hip_sequence_last_masks(void *seq, int neighbour, int scale, uint32_t *d
     bcd_hip_ctx *ctx = q->ctx;
     if (!d_mask) return bad(ctx, "null mask pointer");
     if (q->last_frame < 0) return bad(ctx, "no frame has been popped");
-    if (q->last_nb == 0) return bad(ctx, "the last frame had no neighbour: it went through bcd_hip_denoise, which keeps no masks");
+    if (q->last_nb == 0)
+        return bad(ctx, q->plain() ? "the last frame had no neighbour: it went through bcd_hip_denoise, which keeps no masks"
+                                   : "the last frame had no neighbour: it went through the single-frame call of its mode, which keeps no masks");
     if (neighbour < 0 || neighbour > q->last_nb) return bad(ctx, "no such neighbour of the last frame");
     if (scale < 0 || scale >= q->S) return bad(ctx, "no such scale");
     const int64_t t = q->last_frame;
@@ -364,6 +717,7 @@ void bcd_hip_sequence_destroy(void *seq)
         for (SeqSlot &s : q->slot) {
             for (auto &level : s.lv) for (DevBuf &b : level) drop(b);
             for (DevBuf &b : s.pixcov) drop(b);
+            for (auto &level : s.guide) for (DevBuf &b : level) drop(b);
             for (auto &d : s.pair) for (DevBuf &b : d) drop(b);
         }
         for (DevBuf &b : q->out) drop(b);

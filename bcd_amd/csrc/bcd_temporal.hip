@@ -61,6 +61,7 @@ int temporal_guide_gate(bcd_hip_ctx *ctx, Work &wk, const TemporalSelFrame &fram
     const size_t npix = (size_t)W * H, words = ((size_t)(2 * b + 1) * (2 * b + 1) + 31) / 32;
     RCCHK(ensure(ctx, wk.gate_mask, npix * words * sizeof(uint32_t)));
     RCCHK(ensure(ctx, wk.gate_nsim, npix * sizeof(int32_t)));
+    ++ctx->temporal.guide_cross_passes;
     RCCHK(temporal_guide_cross_planes(ctx, wk, frame.feat, frame.var, nb.feat, nb.var, ctx->guide.F, ctx->guide.floors, W, H, b));
     HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, ctx->guide.tau, (uint32_t *)wk.gate_mask.p, (int32_t *)wk.gate_nsim.p,
                                        wk.stream));
@@ -369,7 +370,8 @@ int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, in
             HIPCHK(ctx, bcd_launch_masks_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, tau, mask, count, wk.stream));
         }
         if (frames[f].valid) RCCHK(temporal_gate(ctx, wk, frames[f].valid, W, H, w, b, mask, count)); // (a warped neighbour)
-        if (guided) RCCHK(temporal_guide_gate(ctx, wk, frames[0], frames[f], W, H, w, b, mask, count));
+        // ("Sequences": kept masks are the gated ones, and transposition distributes over the AND -- a transposed neighbour is not gated again)
+        if (guided && !frames[f].transpose_from) RCCHK(temporal_guide_gate(ctx, wk, frames[0], frames[f], W, H, w, b, mask, count));
         HIPCHK(ctx, bcd_launch_add_counts((int32_t *)wk.nsim.p, count, (int64_t)npix, wk.stream));
     }
     if (prof) HIPCHK(ctx, hipEventRecord(wk.ev_stage[1], wk.stream));

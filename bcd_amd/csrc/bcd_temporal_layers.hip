@@ -24,13 +24,6 @@ namespace {
 
 constexpr int NF = BCD_MAX_NEIGHBOURS + 1, ML = BCD_MAX_LAYERS;
 
-// one scale's estimate inputs: [f][k] = frame f (0: the frame itself), layer k
-struct LayerFrames {
-    int nf = 0, L = 0;
-    const float *col[NF][ML], *pixcov[NF][ML];
-    const uint32_t *mask[NF];
-};
-
 // the part of bayes_temporal_layers behind the fork: the wait for the list lengths, then one chain of full estimates per layer -- records and work queues are
 // reused, the redo counter runs on and its total is copied out behind each layer.  The side stream is NOT joined here.
 int layer_chains(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, int W, int H, int b, float min_eig, float *const *d_sum, int32_t *d_count, int cus)
@@ -46,6 +39,8 @@ int layer_chains(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, int W, int H
     }
     return BCD_HIP_OK;
 }
+
+} // namespace
 
 // bayes_temporal (bcd_temporal.hip) for L layers on one selection: the lists once, the layered fallback kernel on the side stream, per layer one chain of full
 // estimates on that layer's images of every frame, the in-frame masks and its sum image.  d_count goes to the fallback kernel and to the first layer's chain
@@ -88,6 +83,8 @@ int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, con
     h_c->spectral = h->layer_redo_total[L - 1]; // the scale's figure: the sum over the layers
     return BCD_HIP_OK;
 }
+
+namespace {
 
 // one frame at one pyramid level: its sample counts, histograms and the colours and covariances of its layers
 struct LevelFrame {

@@ -387,6 +387,22 @@ __global__ __launch_bounds__(256) void k_layers_pixel_cov_clear(BcdLayerTable t,
     float *s3 = sum + (k * npix + i) * 3;
     s3[0] = 0.f; s3[1] = 0.f; s3[2] = 0.f;
 }
+// k_layers_pixel_cov_clear without the clear, for a sequence (bcd_sequence.hip): the per-pixel covariances of a pushed frame's layers are computed once, by
+// its push, and the sums are cleared by every pop.  The same products per value; the six entries of a pixel (24 B, 8 B aligned: t.a[k] and pixcov are 8 B
+// aligned, as every slice of a hipMalloc'ed buffer of whole pixels is) travel as three float2
+__global__ __launch_bounds__(256) void k_layers_pixel_cov(BcdLayerTable t, const float *__restrict__ ns, uint32_t npix, float *__restrict__ pixcov)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= npix) return;
+    const size_t k = blockIdx.y;
+    const float inv = 1.f / ns[i];
+    const float2 *src = reinterpret_cast<const float2 *>(t.a[k] + 6 * (size_t)i);
+    float2 *dst = reinterpret_cast<float2 *>(pixcov + (k * npix + i) * 6);
+    const float2 v0 = src[0], v1 = src[1], v2 = src[2];
+    dst[0] = make_float2(v0.x * inv, v0.y * inv);
+    dst[1] = make_float2(v1.x * inv, v1.y * inv);
+    dst[2] = make_float2(v2.x * inv, v2.y * inv);
+}
 // t.a: the layer's sum image, t.o: its output; cnt: the shared count image
 __global__ __launch_bounds__(256) void k_layers_finalize(BcdLayerTable t, const int32_t *__restrict__ cnt, uint32_t npix)
 {
@@ -598,6 +614,14 @@ hipError_t bcd_launch_layers_pixel_cov_clear(const BcdLayerTable &t, int layers,
 {
     if (layers < 1 || layers > BCD_MAX_LAYERS || npix <= 0 || npix >= (int64_t)1 << 31) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_layers_pixel_cov_clear, dim3(nblk(npix, 256), layers), dim3(256), 0, st, t, ns, (uint32_t)npix, pixcov, sum);
+    return hipGetLastError();
+}
+hipError_t bcd_launch_layers_pixel_cov(const BcdLayerTable &t, int layers, const float *ns, int64_t npix, float *pixcov, hipStream_t st)
+{
+    if (layers < 1 || layers > BCD_MAX_LAYERS || npix <= 0 || npix >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    if ((uintptr_t)pixcov % 8) return hipErrorInvalidValue;
+    for (int k = 0; k < layers; ++k) if ((uintptr_t)t.a[k] % 8) return hipErrorInvalidValue; // (float2 loads)
+    hipLaunchKernelGGL(k_layers_pixel_cov, dim3(nblk(npix, 256), layers), dim3(256), 0, st, t, ns, (uint32_t)npix, pixcov);
     return hipGetLastError();
 }
 hipError_t bcd_launch_layers_finalize(const BcdLayerTable &t, int layers, const int32_t *cnt, int64_t npix, hipStream_t st)

@@ -7,7 +7,7 @@ import weakref
 from . import _prototypes
 from ._prototypes import (ACCUM_MAX_LAYERS, MAX_LAYERS, MULTI_ID_BYTES, PROGRESS_FN, SELECTION_MAX_SCALES, STATE_HEADER_BYTES, BandJob, Frame, FrameLayer,
                           FrameLayers, Guide, GuideImages, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
-                          PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SequenceInfo, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
+                          PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SequenceFrame, SequenceInfo, SequenceMode, SequenceModeInfo, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
                           StateHeader, WarpedFrame)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -507,9 +507,17 @@ class Context:
         self._chk(lib().bcd_hip_transpose_masks_cross(self.h, _dp(mask), W, H, b, _dp(omask), _dp(cnt) if cnt is not None else None))
         return omask, cnt
 
-    def sequence(self, W, H, D, nscales, radius, prm):
-        """a Sequence of this context: frames of W x H with D bins, denoised with their neighbours within `radius` frames through a sliding window"""
-        return Sequence(self, W, H, D, nscales, radius, prm)
+    def sequence(self, W, H, D, nscales, radius, prm, layers=None, moments=False, var_floor=1e-8, features=0, feature_variances=False, feature_floors=(),
+                 feature_threshold=1.0):
+        """a Sequence of this context: frames of W x H with D bins, denoised with their neighbours within `radius` frames through a sliding window.
+        With none of the keywords: bcd_hip_sequence_create (one colour layer, histograms, no gate).  layers=L (1 .. 16), moments=True (selection from means
+        and covariances with `var_floor`; D is not looked at), features=F (1 .. 8 channels of a feature gate with `feature_variances`, `feature_floors`,
+        `feature_threshold`): bcd_hip_sequence_create_mode -- push / pop then take and return the layers"""
+        if layers is None and not moments and not features:
+            return Sequence(self, W, H, D, nscales, radius, prm)
+        mode = dict(layers=1 if layers is None else int(layers), moments=bool(moments), var_floor=float(var_floor), features=int(features),
+                    feature_variances=bool(feature_variances), feature_floors=tuple(float(x) for x in feature_floors), feature_threshold=float(feature_threshold))
+        return Sequence(self, W, H, D, nscales, radius, prm, mode)
 
     def window_distances_cross(self, hist, ns, hist_nb, ns_nb, w, b, line, column):
         """bcd_hip_window_distances_cross: the (2b+1)^2 patch distances of one main pixel of the frame to its window in the neighbour frame, +inf outside"""
@@ -1725,9 +1733,19 @@ class Sequence:
     Context.denoise_temporal returns for it).  Every frame is copied and its pyramid built once; every pair of frames is searched once -- the second
     cross pass of a pair is a transposition of the first one's masks"""
 
-    def __init__(self, ctx, W, H, D, nscales, radius, prm):
+    def __init__(self, ctx, W, H, D, nscales, radius, prm, mode=None):
         h = _VP()
-        ctx._chk(lib().bcd_hip_sequence_create(ctx.h, int(W), int(H), int(D), int(nscales), int(radius), C.byref(prm), C.byref(h)))
+        self.mode = mode
+        if mode is None:
+            ctx._chk(lib().bcd_hip_sequence_create(ctx.h, int(W), int(H), int(D), int(nscales), int(radius), C.byref(prm), C.byref(h)))
+        else:
+            # ("Modes": push(ns, hist or None, [(colours, covariances), ...], features, variances), pop() -> (index, [layer, ...]))
+            floors = (C.c_float * max(1, len(mode["feature_floors"])))(*mode["feature_floors"])
+            if mode["features"] and len(mode["feature_floors"]) != mode["features"]:
+                raise ValueError("feature_floors must hold one floor per feature channel")
+            m = SequenceMode(mode["layers"], int(mode["moments"]), mode["var_floor"], mode["features"], int(mode["feature_variances"]),
+                             C.addressof(floors) if mode["features"] else None, mode["feature_threshold"], None)
+            ctx._chk(lib().bcd_hip_sequence_create_mode(ctx.h, int(W), int(H), int(D), int(nscales), int(radius), C.byref(prm), C.byref(m), C.byref(h)))
         self.ctx, self.h = ctx, h
         self.W, self.H, self.D, self.nscales, self.radius = int(W), int(H), int(D), int(nscales), int(radius)
         self.b = prm.search_radius
@@ -1745,17 +1763,61 @@ class Sequence:
         if shapes != ((H, W, 3), H * W, (H, W, D), (H, W, 6)):
             raise ValueError("a frame of this sequence is colours %dx%dx3, sample counts %dx%d, histograms %dx%dx%d, covariances %dx%dx6" % (H, W, H, W, H, W, D, H, W))
 
-    def push(self, col, ns, hist, cov):
-        """bcd_hip_sequence_push: the next frame, device tensors (copied: they are free again on return)"""
+    def _frame(self, ns, hist, layers, features, variances, ptr):
+        """the bcd_hip_sequence_frame of a frame in a mode (+ the objects it points into): ns, hist (None in a moments sequence), a list of (colours,
+        covariances), features / variances (H, W, F) or None; ptr(a) is an address.  Shapes are checked here, the mode's rules by the library"""
+        H, W, D, m = self.H, self.W, self.D, self.mode
+        layers = list(layers)
+        nns = ns.numel() if hasattr(ns, "numel") else ns.size
+        if int(nns) != H * W or (hist is not None and tuple(hist.shape) != (H, W, D)):
+            raise ValueError("a frame of this sequence has sample counts %dx%d and histograms %dx%dx%d" % (H, W, H, W, D))
+        for k, (col, cov) in enumerate(layers):
+            if tuple(col.shape) != (H, W, 3) or tuple(cov.shape) != (H, W, 6):
+                raise ValueError("layer %d: colours must be %dx%dx3 and covariances %dx%dx6" % (k, H, W, H, W))
+        for a in (features, variances):
+            if a is not None and tuple(a.shape) != (H, W, m["features"]):
+                raise ValueError("features and variances must be %dx%dx%d" % (H, W, m["features"]))
+        arr = (FrameLayer * max(1, m["layers"]))()
+        for k, (col, cov) in enumerate(layers[:m["layers"]]):
+            arr[k] = FrameLayer(ptr(col), ptr(cov))
+        opt = lambda a: None if a is None else ptr(a)
+        # (a frame with too few layers reaches the library with a NULL layer and is refused there; one with too many is refused here)
+        if len(layers) > m["layers"]:
+            raise ValueError("a frame of this sequence has %d layers" % m["layers"])
+        return SequenceFrame(ptr(ns), opt(hist), C.addressof(arr), opt(features), opt(variances), None), (arr, layers, ns, hist, features, variances)
+
+    def _mode_args(self, frame, features, variances):
+        """(ns, hist, layers, features, variances) of a push in a mode: features and variances may follow the layers positionally"""
+        if not 3 <= len(frame) <= 5:
+            raise TypeError("a frame of a sequence in a mode is (ns, hist or None, [(colours, covariances), ...][, features[, variances]])")
+        rest = list(frame[3:]) + [None, None]
+        return frame[0], frame[1], frame[2], rest[0] if features is None else features, rest[1] if variances is None else variances
+
+    def push(self, *frame, features=None, variances=None):
+        """bcd_hip_sequence_push: the next frame, device tensors (copied: they are free again on return) -- (col, ns, hist, cov).
+        In a mode (bcd_hip_sequence_push_frame): (ns, hist or None, [(colours, covariances), ...], features=None, variances=None)"""
         h = self._handle()
+        if self.mode is not None:
+            f, keep = self._frame(*self._mode_args(frame, features, variances), ptr=_dptr)
+            self.ctx.torch.cuda.synchronize(self.ctx.device)
+            self.ctx._chk(lib().bcd_hip_sequence_push_frame(h, C.byref(f)))
+            return
+        col, ns, hist, cov = frame
         self._check(col, ns, hist, cov)
         self.ctx.torch.cuda.synchronize(self.ctx.device)
         self.ctx._chk(lib().bcd_hip_sequence_push(h, _dp(col), _dp(ns), _dp(hist), _dp(cov)))
 
-    def push_host(self, col, ns, hist, cov):
-        """bcd_hip_sequence_push_host: the next frame, NumPy arrays (uploaded once)"""
+    def push_host(self, *frame, features=None, variances=None):
+        """bcd_hip_sequence_push_host: the next frame, NumPy arrays (uploaded once); the arguments of push"""
         import numpy as np
         h = self._handle()
+        if self.mode is not None:
+            as32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+            ns, hist, layers, features, variances = self._mode_args(frame, features, variances)
+            f, keep = self._frame(as32(ns), as32(hist), [(as32(c), as32(v)) for c, v in layers], as32(features), as32(variances), ptr=_hptr)
+            self.ctx._chk(lib().bcd_hip_sequence_push_frame_host(h, C.byref(f)))
+            return
+        col, ns, hist, cov = frame
         col, ns, hist, cov = (np.ascontiguousarray(a, np.float32) for a in (col, ns, hist, cov))
         self._check(col, ns, hist, cov)
         self.ctx._chk(lib().bcd_hip_sequence_push_host(h, _hptr(col), _hptr(ns), _hptr(hist), _hptr(cov)))
@@ -1769,9 +1831,17 @@ class Sequence:
         return lib().bcd_hip_sequence_ready(self._handle())
 
     def pop(self, out=None):
-        """bcd_hip_sequence_pop -> (frame index, the denoised frame as a (H, W, 3) device tensor)"""
+        """bcd_hip_sequence_pop -> (frame index, the denoised frame as a (H, W, 3) device tensor); in a mode (bcd_hip_sequence_pop_layers) the list of the
+        denoised layers in its place (`out`: a list of tensors to write into)"""
         h = self._handle()
         torch = self.ctx.torch
+        if self.mode is not None:
+            outs = [torch.empty((self.H, self.W, 3), dtype=torch.float32, device="cuda:%d" % self.ctx.device) for _ in range(self.mode["layers"])] if out is None else list(out)
+            ptrs = (C.c_void_p * max(1, len(outs)))(*[_dptr(o) for o in outs])
+            idx = C.c_int64(-1)
+            torch.cuda.synchronize(self.ctx.device)
+            self.ctx._chk(lib().bcd_hip_sequence_pop_layers(h, ptrs, len(outs), C.byref(idx)))
+            return idx.value, outs
         if out is None:
             out = torch.empty((self.H, self.W, 3), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
         idx = C.c_int64(-1)
@@ -1783,8 +1853,13 @@ class Sequence:
         """bcd_hip_sequence_pop_host -> (frame index, the denoised frame as a (H, W, 3) NumPy array)"""
         import numpy as np
         h = self._handle()
-        out = np.empty((self.H, self.W, 3), np.float32)
         idx = C.c_int64(-1)
+        if self.mode is not None:                                     # (bcd_hip_sequence_pop_layers_host -> the list of the denoised layers)
+            outs = [np.empty((self.H, self.W, 3), np.float32) for _ in range(self.mode["layers"])]
+            ptrs = (C.c_void_p * len(outs))(*[_hptr(o) for o in outs])
+            self.ctx._chk(lib().bcd_hip_sequence_pop_layers_host(h, ptrs, len(outs), C.byref(idx)))
+            return idx.value, outs
+        out = np.empty((self.H, self.W, 3), np.float32)
         self.ctx._chk(lib().bcd_hip_sequence_pop_host(h, _hptr(out), C.byref(idx)))
         return idx.value, out
 
@@ -1807,6 +1882,13 @@ class Sequence:
         i = SequenceInfo()
         self.ctx._chk(lib().bcd_hip_sequence_info(self._handle(), C.byref(i)))
         return {k: getattr(i, k) for k, _ in SequenceInfo._fields_}
+
+    def mode_info(self):
+        """bcd_hip_sequence_mode_info as a dict: nb_layers, moments, nb_features, feature_variances, cross_feature_passes (the cross feature passes the pops
+        launched: one per gated neighbour and scale, none for a transposed neighbour)"""
+        i = SequenceModeInfo()
+        self.ctx._chk(lib().bcd_hip_sequence_mode_info(self._handle(), C.byref(i)))
+        return {k: getattr(i, k) for k, _ in SequenceModeInfo._fields_ if k != "reserved"}
 
     def reset(self):
         """forgets every frame and counter; the buffers stay"""

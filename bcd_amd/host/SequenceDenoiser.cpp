@@ -10,6 +10,7 @@
 #include <iostream>
 #include <limits>
 #include <omp.h>
+#include <vector>
 
 using namespace std;
 
@@ -18,7 +19,7 @@ namespace bcd
 
 	SequenceDenoiser::SequenceDenoiser(int i_nbOfScales, int i_temporalRadius) :
 			m_nbOfScales(i_nbOfScales), m_temporalRadius(i_temporalRadius), m_pCtx(nullptr), m_pSequence(nullptr), m_width(0), m_height(0), m_depth(0),
-			m_lastFrameIndex(-1)
+			m_lastFrameIndex(-1), m_frameSettings(false), m_plain(true), m_nbOfLayers(1), m_moments(false), m_nbOfFeatures(0), m_featureVariances(false)
 	{
 	}
 
@@ -62,11 +63,60 @@ namespace bcd
 			cerr << "Aborting denoising: a sequence is not available over several devices" << endl;
 			return false;
 		}
-		if(!m_layers.empty() || !m_neighbourFrames.empty() || m_momentSelection || m_pGuideFeatures || m_prefilterThresholdStDevFactor > 0.f)
+		if(!m_frameSettings && (!m_layers.empty() || !m_neighbourFrames.empty() || m_momentSelection || m_pGuideFeatures || m_prefilterThresholdStDevFactor > 0.f))
 		{
 			cerr << "Aborting denoising: a sequence takes no added colour layers, no neighbour frames of its own (the window supplies them), no moment selection, no "
 					"feature buffers and no spike prefilter" << endl;
 			return false;
+		}
+		if(!m_neighbourFrames.empty() || m_prefilterThresholdStDevFactor > 0.f)
+		{
+			cerr << "Aborting denoising: a sequence takes no neighbour frames of its own (the window supplies them) and no spike prefilter" << endl;
+			return false;
+		}
+		if(m_layers.size() + 1 > size_t(BCD_HIP_MAX_LAYERS))
+		{
+			cerr << "Aborting denoising: at most " << BCD_HIP_MAX_LAYERS - 1 << " added colour layers" << endl;
+			return false;
+		}
+		if(m_momentSelection && (!(m_momentVarianceFloor >= 0.f) || !(m_momentVarianceFloor <= std::numeric_limits<float>::max())))
+		{
+			cerr << "Aborting denoising: the variance floor of the moment selection must be finite and not negative" << endl;
+			return false;
+		}
+		if(m_pGuideFeatures)
+		{
+			const int f = m_pGuideFeatures->getDepth();
+			if(m_pGuideFeatures->isEmpty() || f < 1 || f > BCD_HIP_GUIDE_MAX_CHANNELS)
+			{
+				cerr << "Aborting denoising: the feature image must have 1 to " << BCD_HIP_GUIDE_MAX_CHANNELS << " channels" << endl;
+				return false;
+			}
+			if(int(m_guideFloors.size()) != f)
+			{
+				cerr << "Aborting denoising: one feature floor per feature channel expected (" << f << ", not " << m_guideFloors.size() << ")" << endl;
+				return false;
+			}
+			bool counts = m_pGuideVariances != nullptr;
+			for(float x : m_guideFloors)
+			{
+				if(!(x >= 0.f) || !(x <= std::numeric_limits<float>::max()))
+				{
+					cerr << "Aborting denoising: a feature floor must be finite and not negative" << endl;
+					return false;
+				}
+				counts = counts || x > 0.f;
+			}
+			if(!(m_guideThreshold >= 0.f) || !(m_guideThreshold <= std::numeric_limits<float>::max()))
+			{
+				cerr << "Aborting denoising: the feature threshold must be finite and not negative" << endl;
+				return false;
+			}
+			if(!counts)
+			{
+				cerr << "Aborting denoising: no feature channel can count: every floor is 0 and there are no variances" << endl;
+				return false;
+			}
 		}
 		return true;
 	}
@@ -76,14 +126,14 @@ namespace bcd
 		const DeepImage<float>* images[4] = { i_rFrame.m_pColors, i_rFrame.m_pNbOfSamples, i_rFrame.m_pHistograms, i_rFrame.m_pSampleCovariances };
 		const char* names[4] = { "color", "number of samples", "histogram", "covariance" };
 		for(int i = 0; i < 4; ++i)
-			if(!images[i] || images[i]->isEmpty())
+			if((i != 2 || !m_momentSelection) && (!images[i] || images[i]->isEmpty())) // (the moment selection looks at no histogram)
 			{
 				cerr << "Aborting denoising: nullptr or empty input " << names[i] << " image" << endl;
 				return false;
 			}
 		const int w = images[0]->getWidth(), h = images[0]->getHeight();
 		for(int i = 1; i < 4; ++i)
-			if(images[i]->getWidth() != w || images[i]->getHeight() != h)
+			if((i != 2 || !m_momentSelection) && (images[i]->getWidth() != w || images[i]->getHeight() != h))
 			{
 				cerr << "Aborting denoising: input " << names[i] << " image is " << images[i]->getWidth() << "x" << images[i]->getHeight()
 						<< " but input color image is " << w << "x" << h << endl;
@@ -94,10 +144,41 @@ namespace bcd
 			cerr << "Aborting denoising: expected depths 3 / 1 / 6 for color / number of samples / covariance images" << endl;
 			return false;
 		}
-		if(m_pSequence && (w != m_width || h != m_height || images[2]->getDepth() != m_depth))
+		for(size_t k = 0; k < m_layers.size(); ++k)
+		{
+			const DeepImage<float>* c = m_layers[k].m_pColors;
+			const DeepImage<float>* v = m_layers[k].m_pSampleCovariances;
+			if(!c || !v || c->getWidth() != w || c->getHeight() != h || c->getDepth() != 3 || v->getWidth() != w || v->getHeight() != h || v->getDepth() != 6)
+			{
+				cerr << "Aborting denoising: added layer " << k << " needs colours " << w << "x" << h << "x3 and covariances " << w << "x" << h << "x6" << endl;
+				return false;
+			}
+		}
+		if(m_pGuideFeatures)
+		{
+			if(m_pGuideFeatures->getWidth() != w || m_pGuideFeatures->getHeight() != h)
+			{
+				cerr << "Aborting denoising: the feature image is not " << w << "x" << h << endl;
+				return false;
+			}
+			if(m_pGuideVariances && (m_pGuideVariances->getWidth() != w || m_pGuideVariances->getHeight() != h || m_pGuideVariances->getDepth() != m_pGuideFeatures->getDepth()))
+			{
+				cerr << "Aborting denoising: the feature variances do not have the size of the features" << endl;
+				return false;
+			}
+		}
+		const int depth = m_momentSelection ? 0 : images[2]->getDepth();
+		if(m_pSequence && (w != m_width || h != m_height || depth != m_depth))
 		{
 			cerr << "Aborting denoising: every frame of a sequence has the size of its first frame (" << m_width << "x" << m_height << ", " << m_depth
 					<< " histogram channels)" << endl;
+			return false;
+		}
+		if(m_pSequence && (int(m_layers.size()) + 1 != m_nbOfLayers || m_momentSelection != m_moments || (m_pGuideFeatures ? m_pGuideFeatures->getDepth() : 0) != m_nbOfFeatures ||
+				(m_pGuideVariances != nullptr) != m_featureVariances))
+		{
+			cerr << "Aborting denoising: every frame of a sequence has the layers, the selection and the feature buffers (with or without variances) of its first frame"
+					<< endl;
 			return false;
 		}
 		return true;
@@ -109,7 +190,7 @@ namespace bcd
 			return false;
 		if(!m_pSequence)
 		{
-			const int w = i_rFrame.m_pColors->getWidth(), h = i_rFrame.m_pColors->getHeight(), depth = i_rFrame.m_pHistograms->getDepth();
+			const int w = i_rFrame.m_pColors->getWidth(), h = i_rFrame.m_pColors->getHeight(), depth = m_momentSelection ? 0 : i_rFrame.m_pHistograms->getDepth();
 			for(int s = 1, ws = w, hs = h; s < m_nbOfScales; ++s)
 			{
 				ws /= 2; hs /= 2;
@@ -137,17 +218,47 @@ namespace bcd
 				return false;
 			}
 			m_pCtx = pCtx;
-			if(bcd_hip_sequence_create(pCtx, w, h, depth, m_nbOfScales, m_temporalRadius, &prm, &m_pSequence) != BCD_HIP_OK)
+			// the mode is that of the first frame: its layers (the frame's colours are layer 0), the selection, the feature buffers
+			bcd_hip_sequence_mode mode = {};
+			mode.nb_layers = int(m_layers.size()) + 1;
+			mode.moments = m_momentSelection ? 1 : 0;
+			mode.var_floor = m_momentVarianceFloor;
+			mode.nb_features = m_pGuideFeatures ? m_pGuideFeatures->getDepth() : 0;
+			mode.feature_variances = m_pGuideVariances ? 1 : 0;
+			mode.feature_floors = m_pGuideFeatures ? m_guideFloors.data() : nullptr;
+			mode.feature_threshold = m_guideThreshold;
+			m_plain = mode.nb_layers == 1 && !mode.moments && mode.nb_features == 0; // (today's sequence: bcd_hip_sequence_create and its push and pop)
+			const int rc = m_plain ? bcd_hip_sequence_create(pCtx, w, h, depth, m_nbOfScales, m_temporalRadius, &prm, &m_pSequence)
+					: bcd_hip_sequence_create_mode(pCtx, w, h, depth, m_nbOfScales, m_temporalRadius, &prm, &mode, &m_pSequence);
+			if(rc != BCD_HIP_OK)
 			{
 				cerr << "Aborting denoising: " << bcd_hip_last_error(pCtx) << endl;
 				m_pSequence = nullptr;
 				return false;
 			}
+			m_nbOfLayers = mode.nb_layers; m_moments = m_momentSelection; m_nbOfFeatures = mode.nb_features; m_featureVariances = mode.feature_variances != 0;
 			m_width = w; m_height = h; m_depth = depth;
 			m_lastFrameIndex = -1;
 		}
-		if(bcd_hip_sequence_push_host(m_pSequence, i_rFrame.m_pColors->getDataPtr(), i_rFrame.m_pNbOfSamples->getDataPtr(), i_rFrame.m_pHistograms->getDataPtr(),
-				i_rFrame.m_pSampleCovariances->getDataPtr()) != BCD_HIP_OK)
+		int rc;
+		if(m_plain)
+			rc = bcd_hip_sequence_push_host(m_pSequence, i_rFrame.m_pColors->getDataPtr(), i_rFrame.m_pNbOfSamples->getDataPtr(), i_rFrame.m_pHistograms->getDataPtr(),
+					i_rFrame.m_pSampleCovariances->getDataPtr());
+		else
+		{
+			std::vector<bcd_hip_frame_layer> layers(m_nbOfLayers);
+			layers[0] = { i_rFrame.m_pColors->getDataPtr(), i_rFrame.m_pSampleCovariances->getDataPtr() };
+			for(size_t k = 0; k < m_layers.size(); ++k)
+				layers[k + 1] = { m_layers[k].m_pColors->getDataPtr(), m_layers[k].m_pSampleCovariances->getDataPtr() };
+			bcd_hip_sequence_frame frame = {};
+			frame.nsamples = i_rFrame.m_pNbOfSamples->getDataPtr();
+			frame.histograms = m_moments ? nullptr : i_rFrame.m_pHistograms->getDataPtr();
+			frame.layers = layers.data();
+			frame.features = m_pGuideFeatures ? m_pGuideFeatures->getDataPtr() : nullptr;
+			frame.variances = m_pGuideVariances ? m_pGuideVariances->getDataPtr() : nullptr;
+			rc = bcd_hip_sequence_push_frame_host(m_pSequence, &frame);
+		}
+		if(rc != BCD_HIP_OK)
 		{
 			cerr << "Aborting denoising: " << bcd_hip_last_error(static_cast<bcd_hip_ctx*>(m_pCtx)) << endl;
 			return false;
@@ -179,20 +290,43 @@ namespace bcd
 			cerr << "Aborting denoising: no frame of the sequence is ready (push its later neighbours, or call end())" << endl;
 			return false;
 		}
+		if(int(m_layers.size()) + 1 != m_nbOfLayers)
+		{
+			cerr << "Aborting denoising: the sequence has " << m_nbOfLayers - 1 << " added layers: as many must be registered when a frame is popped (their outputs are written)" << endl;
+			return false;
+		}
+		for(const ColorLayer& l : m_layers)
+			if(!l.m_pDenoisedColors)
+			{
+				cerr << "Aborting denoising: nullptr for the output image of an added layer" << endl;
+				return false;
+			}
 		Deepimf result(m_width, m_height, 3);
+		std::vector<Deepimf> more(m_layers.size(), Deepimf(m_width, m_height, 3));
 		int64_t index = -1;
-		if(bcd_hip_sequence_pop_host(m_pSequence, result.getDataPtr(), &index) != BCD_HIP_OK)
+		int rc;
+		if(m_plain)
+			rc = bcd_hip_sequence_pop_host(m_pSequence, result.getDataPtr(), &index);
+		else
+		{
+			std::vector<float*> outs(1, result.getDataPtr());
+			for(Deepimf& m : more) outs.push_back(m.getDataPtr());
+			rc = bcd_hip_sequence_pop_layers_host(m_pSequence, outs.data(), m_nbOfLayers, &index);
+		}
+		if(rc != BCD_HIP_OK)
 		{
 			cerr << "Aborting denoising: " << bcd_hip_last_error(static_cast<bcd_hip_ctx*>(m_pCtx)) << endl;
 			return false;
 		}
 		if(m_zeroBadOutputValues)
-		{
-			float* p = result.getDataPtr();
-			for(size_t i = 0, n = size_t(m_width) * m_height * 3; i < n; ++i)
-				if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
-					p[i] = 0.f;
-		}
+			for(int k = 0; k < m_nbOfLayers; ++k)
+			{
+				float* p = k ? more[k - 1].getDataPtr() : result.getDataPtr();
+				for(size_t i = 0, n = size_t(m_width) * m_height * 3; i < n; ++i)
+					if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
+						p[i] = 0.f;
+			}
+		for(size_t k = 0; k < m_layers.size(); ++k) *m_layers[k].m_pDenoisedColors = std::move(more[k]);
 		*o_rOutputs.m_pDenoisedColors = std::move(result);
 		m_lastFrameIndex = index;
 		return true;

@@ -13,6 +13,8 @@
 // -a <file.bcd.json> (advertised but never parsed by the reference, main.cpp:107) loads a preset; later flags override it.
 // --sequence-in <pattern with %d> --sequence-out <pattern with %d> --first a --last b --temporal-radius R denoises the frames a .. b of an animation, each with
 // its neighbours within R frames, through bcd::SequenceDenoiser (every frame uploaded once, every pair of frames searched once); it replaces -i / -o.
+// Beside it --sequence-layer <colours> <covariances> <output> (patterns), --sequence-moments <floor> --sequence-nsamples <pattern> and --sequence-features
+// <pattern> with --sequence-feature-variances / -floors / -threshold give every frame its colour layers, the moment selection and the feature gate.
 #include "Chronometer.h"
 #include "DeepImage.h"
 #include "Denoiser.h"
@@ -103,6 +105,14 @@ namespace
 		cout << "                         every frame is denoised with its neighbours within R frames (1 or 2, default 1) and written to its output name." << endl;
 		cout << "                         Expects <frame>_hist.exr / <frame>_cov.exr beside every input, as --neighbour does; needs -p 0, -w 1, -b 6 and a single" << endl;
 		cout << "                         device; not with -i, -o, -h, -c, --neighbour, --layer, --features or --moment-selection" << endl;
+		cout << "    --sequence-layer <colours pattern> <covariances pattern> <output pattern>" << endl;
+		cout << "                         beside --sequence-in: a further colour layer of every frame (repeatable, at most 15), denoised with the frame's selection" << endl;
+		cout << "    --sequence-moments <var floor> --sequence-nsamples <pattern>" << endl;
+		cout << "                         beside --sequence-in: every selection from means and covariances; no <frame>_hist.exr is read, the sample counts of" << endl;
+		cout << "                         every frame come from a one-channel EXR image" << endl;
+		cout << "    --sequence-features <pattern> --sequence-feature-floors <a,b,...> [--sequence-feature-variances <pattern>] [--sequence-feature-threshold <float>]" << endl;
+		cout << "                         beside --sequence-in: the feature buffers of every frame gate the selection inside the frame and across frames," << endl;
+		cout << "                         with the meanings of --features, --feature-floors, --feature-variances and --feature-threshold" << endl;
 		cout << "    -d <float>           Histogram patch distance threshold (default: " << d.m_histogramPatchDistanceThreshold << ")" << endl;
 		cout << "    -b <int>             Radius of search windows (default: " << d.m_searchWindowRadius << ")" << endl;
 		cout << "    -w <int>             Radius of patches (default: " << d.m_patchRadius << ")" << endl;
@@ -625,6 +635,13 @@ namespace
 		string inPattern, outPattern;
 		int first = 0, last = -1, radius = 1;
 		bool hasFirst = false, hasLast = false;
+		// colour layers, the moment selection and the feature gate of a sequence: file patterns per frame (SequenceDenoiser::setFrameSettings)
+		struct SequenceLayer { string m_colorPattern, m_covariancePattern, m_outputPattern; };
+		std::vector<SequenceLayer> layers;
+		bool moments = false;
+		float momentFloor = 1e-8f, featureThreshold = 1.f;
+		string nbOfSamplesPattern, featurePattern, featureVariancePattern;
+		std::vector<float> featureFloors;
 		auto argumentError = [](const string& i_rMessage) { cout << "ERROR in program arguments: " << i_rMessage << endl; return 1; };
 		for(int i = 1; i < argc; ++i)
 		{
@@ -637,8 +654,53 @@ namespace
 					return argumentError(flag + " is not available with --sequence-in (a sequence reads <frame>.exr, <frame>_hist.exr and <frame>_cov.exr of every frame and writes "
 							"--sequence-out; one colour layer, histogram selection, one device)");
 			if(i + 1 >= argc) return argumentError("expecting a value after " + flag);
+			if(flag == "--sequence-layer")
+			{	// one further colour layer of every frame: its colours, its covariances, its output -- three patterns with the frame number
+				if(i + 3 >= argc) return argumentError("expecting <colour pattern> <covariance pattern> <output pattern> after --sequence-layer");
+				SequenceLayer layer = { argv[i + 1], argv[i + 2], argv[i + 3] };
+				if(!isFramePattern(layer.m_colorPattern) || !isFramePattern(layer.m_covariancePattern) || !isFramePattern(layer.m_outputPattern))
+					return argumentError("--sequence-layer needs three file patterns with one %d each: colours, covariances, output");
+				if(layer.m_outputPattern == layer.m_colorPattern || layer.m_outputPattern == layer.m_covariancePattern)
+					return argumentError("the output of a --sequence-layer would overwrite its input");
+				layers.push_back(layer);
+				i += 3;
+				continue;
+			}
 			const char* value = argv[++i];
-			if(flag == "--sequence-in") inPattern = value;
+			if(flag == "--sequence-moments")
+			{	// the selection from means and covariances: the variance floor; the sample counts come from --sequence-nsamples, no <frame>_hist.exr is read
+				char* pEnd = nullptr;
+				momentFloor = strtof(value, &pEnd);
+				if(pEnd == value || *pEnd || !(momentFloor >= 0.f) || std::isinf(momentFloor)) return argumentError("expecting a finite non-negative variance floor after --sequence-moments");
+				moments = true;
+			}
+			else if(flag == "--sequence-nsamples") nbOfSamplesPattern = value;
+			else if(flag == "--sequence-features") featurePattern = value;
+			else if(flag == "--sequence-feature-variances") featureVariancePattern = value;
+			else if(flag == "--sequence-feature-floors")
+			{	// "0.01,0.01,1e-4", as --feature-floors
+				featureFloors.clear();
+				const string list(value);
+				for(size_t pos = 0; pos <= list.size();)
+				{
+					size_t end = list.find(',', pos);
+					if(end == string::npos) end = list.size();
+					const string item = list.substr(pos, end - pos);
+					char* pEnd = nullptr;
+					const float floor = strtof(item.c_str(), &pEnd);
+					if(item.empty() || *pEnd || !(floor >= 0.f) || std::isinf(floor))
+						return argumentError("expecting a list of finite non-negative floating numbers like 0.01,0.01,1e-4 after --sequence-feature-floors");
+					featureFloors.push_back(floor);
+					pos = end + 1;
+				}
+			}
+			else if(flag == "--sequence-feature-threshold")
+			{
+				char* pEnd = nullptr;
+				featureThreshold = strtof(value, &pEnd);
+				if(pEnd == value || *pEnd || !(featureThreshold >= 0.f) || std::isinf(featureThreshold)) return argumentError("expecting a finite non-negative number after --sequence-feature-threshold");
+			}
+			else if(flag == "--sequence-in") inPattern = value;
 			else if(flag == "--sequence-out") outPattern = value;
 			else if(flag == "--first") { first = atoi(value); hasFirst = true; }
 			else if(flag == "--last") { last = atoi(value); hasLast = true; }
@@ -666,6 +728,22 @@ namespace
 		if(a.m_prefilterSpikes) return argumentError("--sequence-in is not available with the spike prefilter: add -p 0");
 		if(a.m_patchRadius != 1 || a.m_searchWindowRadius != 6) return argumentError("--sequence-in needs -w 1 and -b 6 (neighbour frames support no other geometry)");
 		if(frameName(inPattern, first).length() <= 4) return argumentError("'" + frameName(inPattern, first) + "' is no .exr file name");
+		if(layers.size() > 15) return argumentError("at most 15 --sequence-layer arguments");
+		for(const SequenceLayer& rLayer : layers)
+			if(rLayer.m_outputPattern == inPattern || rLayer.m_outputPattern == outPattern) return argumentError("the output of a --sequence-layer would overwrite another file of the sequence");
+		if(moments && !isFramePattern(nbOfSamplesPattern)) return argumentError("--sequence-moments needs --sequence-nsamples <pattern with %d>: the sample counts of every frame (no <frame>_hist.exr is read)");
+		if(!moments && !nbOfSamplesPattern.empty()) return argumentError("--sequence-nsamples goes with --sequence-moments");
+		if(featurePattern.empty() && (!featureVariancePattern.empty() || !featureFloors.empty())) return argumentError("--sequence-feature-variances and --sequence-feature-floors go with --sequence-features");
+		if(!featurePattern.empty())
+		{
+			if(!isFramePattern(featurePattern) || (!featureVariancePattern.empty() && !isFramePattern(featureVariancePattern)))
+				return argumentError("--sequence-features and --sequence-feature-variances need a file pattern with one %d");
+			if(featureFloors.empty() || featureFloors.size() > 8) return argumentError("--sequence-features needs --sequence-feature-floors <a,b,...>, one number per feature channel (1 to 8)");
+			bool counts = !featureVariancePattern.empty();
+			for(float floor : featureFloors) counts = counts || floor > 0.f;
+			if(!counts) return argumentError("every --sequence-feature-floors value is 0 and there are no --sequence-feature-variances: no feature channel can count");
+		}
+		const bool frameSettings = !layers.empty() || moments || !featurePattern.empty();
 
 		DenoiserParameters parameters;
 		parameters.m_histogramDistanceThreshold = a.m_histogramPatchDistanceThreshold;
@@ -681,8 +759,11 @@ namespace
 		sequence.setOrderSeed(a.m_orderSeed);
 		sequence.setDevices(a.m_devices);
 		sequence.setZeroBadOutputValues(true);
+		sequence.setFrameSettings(frameSettings);
+		if(moments) sequence.setMomentSelection(true, momentFloor);
 		if(!sequence.settingsAreOk())
 			return 1;
+		std::vector<Deepimf> layerOutputs(layers.size());
 		auto popReady = [&]() -> int
 		{
 			while(sequence.ready() > 0)
@@ -690,8 +771,20 @@ namespace
 				Deepimf out;
 				DenoiserOutputs outputs;
 				outputs.m_pDenoisedColors = &out;
+				sequence.clearLayers(); // (a pop writes the layers registered now: only their outputs are looked at)
+				for(Deepimf& rOut : layerOutputs) sequence.addLayer(nullptr, nullptr, &rOut);
 				if(!sequence.popFrame(outputs))
 					return 2;
+				for(size_t k = 0; k < layers.size(); ++k)
+				{
+					checkAndPutToZeroNegativeInfNaNValues(layerOutputs[k]);
+					const string layerPath = frameName(layers[k].m_outputPattern, first + int(sequence.getLastFrameIndex()));
+					if(!ImageIO::writeEXR(layerOutputs[k], layerPath.c_str()))
+					{
+						cerr << "Couldn't write " << layerPath << ": " << ImageIO::lastError() << endl;
+						return 3;
+					}
+				}
 				checkAndPutToZeroNegativeInfNaNValues(out);
 				const string path = frameName(outPattern, first + int(sequence.getLastFrameIndex()));
 				if(!ImageIO::writeEXR(out, path.c_str()))
@@ -708,9 +801,35 @@ namespace
 			const string path = frameName(inPattern, frame), stem = path.substr(0, path.length() - 4);
 			Deepimf color, histAndNbOfSamples, hist, nbOfSamples, cov;
 			if(!ImageIO::loadEXR(color, path.c_str())) return argumentError("couldn't load input color image file '" + path + "'");
-			if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamples, (stem + "_hist.exr").c_str())) return argumentError("couldn't load input histogram image file '" + stem + "_hist.exr'");
+			if(moments)
+			{
+				const string nsPath = frameName(nbOfSamplesPattern, frame);
+				if(!ImageIO::loadMultiChannelsEXR(nbOfSamples, nsPath.c_str()) || nbOfSamples.getDepth() != 1) return argumentError("couldn't load a one-channel sample count image from '" + nsPath + "'");
+			}
+			else if(!ImageIO::loadMultiChannelsEXR(histAndNbOfSamples, (stem + "_hist.exr").c_str())) return argumentError("couldn't load input histogram image file '" + stem + "_hist.exr'");
 			if(!ImageIO::loadMultiChannelsEXR(cov, (stem + "_cov.exr").c_str())) return argumentError("couldn't load input covariance matrix image file '" + stem + "_cov.exr'");
-			Utils::separateNbOfSamplesFromHistogram(hist, nbOfSamples, histAndNbOfSamples);
+			if(!moments) Utils::separateNbOfSamplesFromHistogram(hist, nbOfSamples, histAndNbOfSamples);
+			// the frame's further layers and feature buffers: registered for this push (the class checks their sizes against the frame)
+			std::vector<Deepimf> layerColors(layers.size()), layerCovariances(layers.size());
+			Deepimf features, featureVariances;
+			sequence.clearLayers();
+			for(size_t k = 0; k < layers.size(); ++k)
+			{
+				const string colorPath = frameName(layers[k].m_colorPattern, frame), covariancePath = frameName(layers[k].m_covariancePattern, frame);
+				if(!ImageIO::loadEXR(layerColors[k], colorPath.c_str())) return argumentError("couldn't load layer color image file '" + colorPath + "'");
+				if(!ImageIO::loadMultiChannelsEXR(layerCovariances[k], covariancePath.c_str())) return argumentError("couldn't load layer covariance image file '" + covariancePath + "'");
+				sequence.addLayer(&layerColors[k], &layerCovariances[k], &layerOutputs[k]);
+			}
+			if(!featurePattern.empty())
+			{
+				const string featurePath = frameName(featurePattern, frame);
+				if(!ImageIO::loadMultiChannelsEXR(features, featurePath.c_str())) return argumentError("couldn't load feature image file '" + featurePath + "'");
+				if(!featureVariancePattern.empty() && !ImageIO::loadMultiChannelsEXR(featureVariances, frameName(featureVariancePattern, frame).c_str()))
+					return argumentError("couldn't load feature variance image file '" + frameName(featureVariancePattern, frame) + "'");
+				if(features.getDepth() != int(featureFloors.size()))
+					return argumentError(std::to_string(featureFloors.size()) + " --sequence-feature-floors for " + std::to_string(features.getDepth()) + " feature channels of '" + featurePath + "'");
+				sequence.setGuideFeatures(&features, featureVariancePattern.empty() ? nullptr : &featureVariances, featureFloors, featureThreshold);
+			}
 			if(color.getDepth() == 1)
 			{	// grey colour file, as for -i
 				Deepimf rgb(color.getWidth(), color.getHeight(), 3);
@@ -719,9 +838,10 @@ namespace
 				color = std::move(rgb);
 			}
 			DenoiserInputs inputs;
-			inputs.m_pColors = &color; inputs.m_pNbOfSamples = &nbOfSamples; inputs.m_pHistograms = &hist; inputs.m_pSampleCovariances = &cov;
+			inputs.m_pColors = &color; inputs.m_pNbOfSamples = &nbOfSamples; inputs.m_pHistograms = moments ? nullptr : &hist; inputs.m_pSampleCovariances = &cov;
 			if(!sequence.pushFrame(inputs))
 				return 2;
+			sequence.setGuideFeatures(nullptr, nullptr, featureFloors, featureThreshold); // (the frame's images end with this iteration)
 			if(frame == last && !sequence.end())
 				return 2;
 			const int rc = popReady();

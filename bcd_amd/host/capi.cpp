@@ -681,6 +681,91 @@ int bcdcore_denoise_sequence(const float* cols, const float* nss, const float* h
 	return popped == nbOfFrames ? 1 : 0;
 }
 
+/// bcd::SequenceDenoiser with setFrameSettings(true): per frame nbOfLayers layers (cols / covs frame-major, layer 0 the DenoiserInputs images; outs the same
+/// way), histograms (hists null: setMomentSelection(true, varFloor), D is not looked at) and nbOfChannels feature channels (features null: no gate; variances
+/// null: none) with nbOfFloors floors and the threshold.  break_: settings the class must refuse before a device is asked for -- bit 0 addNeighbourFrame, bit 1
+/// the spike prefilter, bit 2 two devices, bit 3 the second frame with one layer fewer, bit 4 the second frame without its variances (or, without variances,
+/// without its features), bit 5 no layer registered when the first frame is popped.  Returns 1 when every push and pop succeeded in order, else 0.
+int bcdcore_denoise_sequence_modes(const float* cols, const float* nss, const float* hists, const float* covs, const float* features, const float* variances, int nbOfFrames,
+		int nbOfLayers, int nbOfChannels, const float* floors, int nbOfFloors, float threshold, float varFloor, int W, int H, int D, int nscales, int radius, float tau,
+		int w, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int break_, float* outs)
+{
+	const size_t npix = size_t(W) * H;
+	SequenceDenoiser sequence(nscales, radius);
+	DenoiserParameters p;
+	p.m_histogramDistanceThreshold = tau;
+	p.m_patchRadius = w;
+	p.m_searchWindowRadius = b;
+	p.m_minEigenValue = minEig;
+	p.m_useRandomPixelOrder = randomOrder != 0;
+	p.m_markedPixelsSkippingProbability = skipProbability;
+	sequence.setParameters(p);
+	sequence.setOrderSeed(seed);
+	sequence.setFrameSettings(true);
+	if(!hists) sequence.setMomentSelection(true, varFloor);
+	DenoiserInputs extraFrame;
+	if(break_ & 1) sequence.addNeighbourFrame(extraFrame);
+	if(break_ & 2) sequence.setSpikePrefilter(2.f);
+	if(break_ & 4) sequence.setDevices(std::vector<int>{ 0, 1 });
+	const std::vector<float> floorList(floors, floors + (floors ? nbOfFloors : 0));
+	const int L = nbOfLayers;
+	int popped = 0;
+	std::vector<Deepimf> layerOuts(L > 1 ? L - 1 : 0);
+	std::vector<Deepimf> lc, lv;
+	Deepimf feat, var;
+	auto registerLayers = [&](int n)
+	{
+		sequence.clearLayers();
+		for(int k = 1; k < n; ++k) sequence.addLayer(&lc[k - 1], &lv[k - 1], &layerOuts[k - 1]);
+	};
+	auto popReady = [&]() -> bool
+	{
+		while(sequence.ready() > 0)
+		{
+			Deepimf out;
+			DenoiserOutputs o;
+			o.m_pDenoisedColors = &out;
+			if((break_ & 32) && popped == 0) sequence.clearLayers();
+			if(!sequence.popFrame(o) || sequence.getLastFrameIndex() != popped || out.getWidth() != W || out.getHeight() != H || out.getDepth() != 3)
+				return false;
+			out.copyDataTo(outs + (size_t(popped) * L) * npix * 3);
+			for(int k = 1; k < L; ++k)
+			{
+				if(layerOuts[k - 1].getWidth() != W || layerOuts[k - 1].getHeight() != H || layerOuts[k - 1].getDepth() != 3) return false;
+				layerOuts[k - 1].copyDataTo(outs + (size_t(popped) * L + k) * npix * 3);
+			}
+			++popped;
+		}
+		return true;
+	};
+	for(int f = 0; f < nbOfFrames; ++f)
+	{
+		Deepimf c(W, H, 3), n(W, H, 1), h, v(W, H, 6);
+		c.copyDataFrom(cols + (size_t(f) * L) * npix * 3); n.copyDataFrom(nss + f * npix); v.copyDataFrom(covs + (size_t(f) * L) * npix * 6);
+		if(hists) { h = Deepimf(W, H, D); h.copyDataFrom(hists + f * npix * D); }
+		lc.assign(L - 1, Deepimf(W, H, 3)); lv.assign(L - 1, Deepimf(W, H, 6));
+		for(int k = 1; k < L; ++k) { lc[k - 1].copyDataFrom(cols + (size_t(f) * L + k) * npix * 3); lv[k - 1].copyDataFrom(covs + (size_t(f) * L + k) * npix * 6); }
+		registerLayers((break_ & 8) && f == 1 ? L - 1 : L);
+		if(features)
+		{
+			const bool drop = (break_ & 16) && f == 1;
+			feat = Deepimf(W, H, nbOfChannels); feat.copyDataFrom(features + f * npix * nbOfChannels);
+			if(variances) { var = Deepimf(W, H, nbOfChannels); var.copyDataFrom(variances + f * npix * nbOfChannels); }
+			sequence.setGuideFeatures(drop && !variances ? nullptr : &feat, variances && !drop ? &var : nullptr, floorList, threshold);
+		}
+		DenoiserInputs in;
+		in.m_pColors = &c; in.m_pNbOfSamples = &n; in.m_pHistograms = hists ? &h : nullptr; in.m_pSampleCovariances = &v;
+		if(!sequence.pushFrame(in))
+			return 0;
+		if(f == nbOfFrames - 1 && !sequence.end())
+			return 0;
+		registerLayers(L);
+		if(!popReady())
+			return 0;
+	}
+	return popped == nbOfFrames ? 1 : 0;
+}
+
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames AND colour layers (addLayer, addNeighbourFrame, addNeighbourFrameLayer).  cols / covs hold
 /// nbOfLayers images of the frame one behind the other (layer 0 = the primary images), nbCols / nbCovs nbOfNeighbours x nbOfLayers images (neighbour-major),
 /// nbNs / nbHists one image per neighbour.  The last neighbour gets dropLayers fewer layers than the frame (> 0: denoise() must refuse).  afterClear != 0:

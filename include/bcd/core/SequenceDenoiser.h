@@ -16,9 +16,17 @@ namespace bcd
 
 	/// Usage: setParameters / setOrderSeed / setDevice as on a Denoiser, then per frame pushFrame(), and popFrame() while ready() > 0; after the last frame
 	/// end(), and popFrame() until ready() is 0.  Frame t can be popped once frame t + R is pushed, or after end(); a push is refused while the window is
-	/// full (pop first).  The settings of HipEngineSettings that a sequence does not serve -- added layers, neighbour frames of its own, the moment
-	/// selection, feature buffers, the spike prefilter, several devices -- make pushFrame() return false, like a patch radius other than 1, a search
-	/// radius other than 6 or a temporal radius outside 1 .. 2; every refusal comes before any device is asked for, with a message on cerr.
+	/// full (pop first).
+	/// After setFrameSettings(true), colour layers, the moment selection and feature buffers have the semantics of HipEngineSettings, per pushed frame:
+	///  - addLayer / setLayers: the layers registered when pushFrame() is called are that frame's added layers (colours and covariances are read; the
+	///    DenoiserInputs colours are layer 0); the layers registered when popFrame() is called receive the popped frame's outputs in m_pDenoisedColors;
+	///  - setMomentSelection(true, floor): every selection from means and covariances; DenoiserInputs::m_pHistograms may stay null and is not looked at;
+	///  - setGuideFeatures: the features (and variances) set when pushFrame() is called are that frame's; floors and threshold are those of the first frame.
+	/// The first frame fixes the mode: the number of layers, the selection, the feature channels and whether there are variances; reset() frees it.
+	/// The settings a sequence does not serve -- neighbour frames of its own, motion fields, the spike prefilter, several devices -- make pushFrame() return
+	/// false, like a patch radius other than 1, a search radius other than 6, a temporal radius outside 1 .. 2, more than 15 added layers, a feature image
+	/// outside 1 .. 8 channels, floors that are negative, not finite, of another count or unable to count, a frame that differs from the first frame's
+	/// mode; every refusal comes before any device is asked for, with a message on cerr.
 	class SequenceDenoiser : public HipEngineSettings
 	{
 	public:
@@ -32,6 +40,10 @@ namespace bcd
 		void setParameters(const DenoiserParameters& i_rParameters) { m_parameters = i_rParameters; }
 		int getNbOfScales() const { return m_nbOfScales; }
 		int getTemporalRadius() const { return m_temporalRadius; }
+		/// true: added layers, the moment selection and feature buffers are taken per pushed frame, as described above.  false (default): a sequence with any
+		/// of them set is refused with the message it always had -- one colour layer, histogram selection, no gate
+		void setFrameSettings(bool i_enabled) { m_frameSettings = i_enabled; }
+		bool getFrameSettings() const { return m_frameSettings; }
 
 		/// the next frame: the four images are uploaded before the call returns.  The first frame fixes width, height and histogram depth
 		bool pushFrame(const DenoiserInputs& i_rFrame);
@@ -60,6 +72,13 @@ namespace bcd
 		void* m_pSequence; // bcd_hip_sequence_* handle
 		int m_width, m_height, m_depth;
 		int64_t m_lastFrameIndex;
+		bool m_frameSettings;  // setFrameSettings
+		// the mode of the sequence in progress (that of its first frame)
+		bool m_plain;          // one layer, histograms, no feature gate: bcd_hip_sequence_create and its push and pop
+		int m_nbOfLayers;
+		bool m_moments;
+		int m_nbOfFeatures;
+		bool m_featureVariances;
 	};
 
 } // namespace bcd

@@ -365,8 +365,9 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
  *   _set_reuse(0) searches every pair directly (for comparisons and tests; default 1).  _last_masks copies, after a pop, the masks (and their counts) of
  *   neighbour `neighbour` of the popped frame at `scale`: 0 the in-frame set, 1 .. the neighbours in ascending frame order.  _reset forgets every frame and
  *   counter and keeps the buffers.  _destroy frees them; a sequence must be destroyed before its context.
- *   Scope: histogram selection, one colour layer, patch radius 1, search radius 6, radius 1 .. 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS).  Colour layers, motion
- *   fields (a warped neighbour breaks the symmetry), the feature gate, the moment selection, the spike prefilter, row bands and several GPUs are out.
+ *   Scope: histogram selection, one colour layer, patch radius 1, search radius 6, radius 1 .. 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS).  Colour layers, the
+ *   feature gate and the moment selection come through bcd_hip_sequence_create_mode further down; motion fields (a warped neighbour breaks the symmetry),
+ *   the spike prefilter, row bands and several GPUs are out.
  *   Refused before any device work, with a message: what bcd_hip_denoise_temporal refuses; a radius outside 1 .. 2; any other geometry
  *   (BCD_HIP_EUNSUPPORTED); a null image; a push beyond the ring or after _end; a pop that is not ready.
  * A sequence handle is an opaque pointer, written by _create and passed as void *. */
@@ -601,6 +602,63 @@ int bcd_hip_denoise_temporal_moments_host(bcd_hip_ctx *ctx, const float *h_nsamp
                                           const float *const *h_motion, int W, int H, int nb_scales, const bcd_hip_params *prm, float var_floor,
                                           const bcd_hip_layer *layers /* host pointers */, int nb_layers, const bcd_hip_guide *guide /* host images */,
                                           const bcd_hip_guide_images *neighbour_guides /* host images */);
+
+/* ---- sequences in a mode: colour layers, the moment selection, the feature gate ("Sequences", "Modes") ----
+ * The cross moment term (d = m0(x) - mj(y), q = (v0(x) + vj(y)) + eps, d d / q) and the cross feature term of bcd_hip_denoise_temporal_guided have the form of the
+ * histogram term: with the roles of the two frames swapped d changes sign and is squared, the one addition inside q commutes, and the pixel pairs of a patch
+ * are visited in the same row-major order.  So their cross masks of (B -> A) are the transposition (bcd_hip_transpose_masks_cross) of those of (A -> B), bit
+ * for bit; the transposition distributes over the AND of the gate, so the GATED masks a pop keeps for a pair are transposed as they are.
+ *   Mode.  nb_layers L = 1 .. 16 colour layers; moments 0: selection from histograms, 1: from means and covariances with var_floor, layer 0 being the guide
+ *   layer (no histogram is stored and D is not looked at); nb_features F = 0: no feature gate, 1 .. 8: the gate of bcd_hip_guide with feature_variances (0 / 1:
+ *   every frame brings variances or none does), feature_floors (HOST array of F floats) and feature_threshold.  `reserved` must be NULL.
+ *   Definition.  Frame t of T comes out, per layer, as what the matching frame call returns for frame t with the neighbours max(0, t - radius) ..
+ *   min(T - 1, t + radius) except t in ascending order, no motion field, the sequence's params: bcd_hip_denoise_temporal_layers (histograms, no gate),
+ *   bcd_hip_denoise_temporal_guided (histograms with the gate), bcd_hip_denoise_temporal_moments (moments, with or without the gate).  In-frame masks, cross
+ *   masks, |S|, marking, lists, bcd_hip_get_stats and bcd_hip_layer_spectral_inverses are bit for bit those of that call; the layers differ by the order of
+ *   float atomics only.  A frame without neighbours (T = 1) is bcd_hip_denoise_layers, bcd_hip_denoise_guided or bcd_hip_denoise_moments.
+ *   A transposed neighbour runs neither a cross pass nor its cross feature pass; the in-frame set of every frame is computed and gated per pop.
+ *   _create_mode: with L = 1, histograms and no gate the sequence is the one bcd_hip_sequence_create makes and takes its path; it then accepts the plain
+ *             and the _frame / _layers calls alike.  Any other mode accepts only _push_frame[_host] and _pop_layers[_host], and a sequence made by
+ *             bcd_hip_sequence_create only the plain calls.  _end, _ready, _set_reuse, _last_masks, _info, _reset and _destroy serve every sequence.
+ *   _push_frame[_host]: one frame -- sample counts, histograms (NULL exactly in a moments sequence), L layers, features and variances as the mode says.
+ *             Everything is copied or uploaded once, every pyramid level and the per-pixel covariances of all layers are built once.
+ *   _pop_layers[_host]: nb_layers must be L; outs[k] takes layer k (W*H*3 floats).
+ *   _mode_info: the mode, and cross_feature_passes: the cross feature passes launched (one per gated neighbour and scale) -- 0 for a transposed neighbour.
+ *   Refused before any device work, with a message, the context staying usable: what the matching frame call refuses for the mode and geometry (anything but
+ *   patch radius 1 and search radius 6: BCD_HIP_EUNSUPPORTED); L outside 1 .. 16, F outside 0 .. 8; a guide that cannot count; a negative or non-finite floor,
+ *   threshold or var_floor; a cross feature kernel that cannot be launched; a non-NULL `reserved`; a push whose shape does not match the mode; a pop with a
+ *   wrong layer count or a null output; a plain call on a sequence of another mode and the reverse.
+ *   Out of scope: motion fields (a warped pair is not symmetric, and its pyramids are per pair), the spike prefilter, row bands, several GPUs. */
+typedef struct bcd_hip_sequence_mode {
+    int32_t      nb_layers;
+    int32_t      moments;
+    float        var_floor;
+    int32_t      nb_features;
+    int32_t      feature_variances;
+    const float *feature_floors;
+    float        feature_threshold;
+    const void  *reserved;
+} bcd_hip_sequence_mode;
+typedef struct bcd_hip_sequence_frame {
+    const float *nsamples;
+    const float *histograms;
+    const bcd_hip_frame_layer *layers;
+    const float *features;
+    const float *variances;
+    const void  *reserved;
+} bcd_hip_sequence_frame;
+struct bcd_hip_sequence_mode_info {
+    int32_t nb_layers, moments, nb_features, feature_variances;
+    int64_t cross_feature_passes;
+    int64_t reserved;
+};
+int bcd_hip_sequence_create_mode(bcd_hip_ctx *ctx, int W, int H, int D, int nb_scales, int radius, const bcd_hip_params *prm, const bcd_hip_sequence_mode *mode,
+                                 void **out);
+int bcd_hip_sequence_push_frame(void *seq, const bcd_hip_sequence_frame *frame /* device images */);
+int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *frame /* host images */);
+int bcd_hip_sequence_pop_layers(void *seq, float *const *d_outs, int nb_layers, int64_t *frame_index);
+int bcd_hip_sequence_pop_layers_host(void *seq, float *const *h_outs, int nb_layers, int64_t *frame_index);
+int bcd_hip_sequence_mode_info(void *seq, struct bcd_hip_sequence_mode_info *info);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
