@@ -1,7 +1,8 @@
 """Host restatement of the splatted add's definition (include/bcd_hip.h, bcd_hip_accum_add_splatted) in NumPy float32: expands samples at
 continuous positions into the (line, col, r, g, b, w * f) stream that bcd::SamplesAccumulator::addSample would be fed -- for each sample
 in order, line ascending, col ascending -- and counts the samples that contribute and those that are dropped.  The expected statistics
-are oracle_lib.oracle_ops()["accumulate"](stream, W, H)."""
+are oracle_lib.oracle_ops()["accumulate"](stream, W, H).  tests/splat_cases.py holds the constructed cases (radii of every neighbour-range
+class, positions on the comparisons, the index clamp, tile-sized frames) and a gather model of the kernel that is checked against this."""
 import numpy as np
 
 F32 = np.float32
