@@ -192,7 +192,7 @@ class StateHeader(C.Structure):
                 ("samples_added", C.c_int64), ("dropped", C.c_int64), ("reserved", C.c_uint8 * 8)]
 
 
-STATE_HEADER_BYTES = 64  # BCD_HIP_ACCUM_STATE_HEADER_BYTES, BCD_HIP_ACCUM_LAYERS_HEADER_BYTES
+STATE_HEADER_BYTES = 64  # BCD_HIP_ACCUM_STATE_HEADER_BYTES, BCD_HIP_ACCUM_LAYERS_HEADER_BYTES, BCD_HIP_ACCUM_FEATURES_HEADER_BYTES
 ACCUM_MAX_LAYERS = MAX_LAYERS - 1  # BCD_HIP_ACCUM_MAX_LAYERS
 
 
@@ -201,6 +201,16 @@ class LayersHeader(C.Structure):
     _c_name_ = "bcd_hip_accum_layers_header"
     _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
                 ("nb_layers", C.c_int32), ("nb_planes", C.c_uint32), ("reserved", C.c_uint8 * 32)]
+
+
+ACCUM_MAX_FEATURES = 8  # BCD_HIP_ACCUM_MAX_FEATURES (= BCD_HIP_GUIDE_MAX_CHANNELS)
+
+
+class FeaturesHeader(C.Structure):
+    """the 64-byte header of a serialised feature block (version 1, include/bcd_hip.h)"""
+    _c_name_ = "bcd_hip_accum_features_header"
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("nb_features", C.c_int32), ("nb_planes", C.c_uint32), ("reserved", C.c_uint8 * 32)]
 
 
 class HostStreamResult(C.Structure):
@@ -409,6 +419,18 @@ PROTOTYPES = {
     "bcd_hip_accum_export_layers": (I, [P, P, I64]),
     "bcd_hip_accum_import_layers": (I, [P, P, I64]),
     "bcd_hip_accum_merge_layers_state": (I, [P, P, I64]),
+    # (auxiliary feature channels beside the beauty)
+    "bcd_hip_accum_create_features": (I, [P, I, I, I, F, F, I64, I, I, P]),
+    "bcd_hip_accum_nb_features": (I, [P, P]),
+    "bcd_hip_accum_add_dense_features": (I, [P, P, P, I, I, I, I, P, I, P]),
+    "bcd_hip_accum_add_scattered_features": (I, [P, P, P, P, I64, P, P]),
+    "bcd_hip_accum_add_splatted_features": (I, [P, P, P, P, I64, P, P]),
+    "bcd_hip_accum_feature_statistics": (I, [P, P, P]),
+    "bcd_hip_accum_features_state_info": (I, [P, I64, S(FeaturesHeader)]),
+    "bcd_hip_accum_features_state_bytes": (I, [P, P]),
+    "bcd_hip_accum_export_features": (I, [P, P, I64]),
+    "bcd_hip_accum_import_features": (I, [P, P, I64]),
+    "bcd_hip_accum_merge_features_state": (I, [P, P, I64]),
     "bcd_hip_zero_bad_values": (I, [P, P, I64]),
     # (self-tests and measurement aids)
     "bcd_hip_selftest_division": (I, [P, U32, I64, P]),

@@ -122,6 +122,50 @@ def device_accumulate_layers(calls, layer_rgb, W, H, radius=None, table=None, ba
     return (ns, mean, cov, hist), [(lmean[k], lcov[k]) for k in range(L)], (counts[0], counts[1])
 
 
+def device_accumulate_features(calls, features, W, H, layer_rgb=None, radius=None, table=None, batch=0, state_path=None, layers_path=None,
+                               features_path=None, merge_again=False, nbins=20, gamma=2.2, maxval=2.5, device=0):
+    """mixed calls through the batch forms of a bcd::DeviceSamplesAccumulator with feature channels: calls (n, 7) float32 as for device_splat,
+    features (n, F) the feature channels of the same calls, layer_rgb (L, n, 3) or None (no layers); runs of one kind go through addSamples /
+    splatSamples in pieces of at most `batch` calls; state_path, features_path (and layers_path with layers): saveState + saveFeatures
+    (+ saveLayers) at the end, loaded into a second accumulator whose statistics are returned; merge_again: the files are then merged into
+    it once more.  -> ((ns, mean, cov, hist), [(mean, cov) per layer], (feature means, variances of the means), (samples accumulated, dropped))"""
+    calls = np.ascontiguousarray(calls, np.float32)
+    features = np.ascontiguousarray(features, np.float32)
+    n, F = calls.shape[0], features.shape[1]
+    L = 0 if layer_rgb is None else layer_rgb.shape[0]
+    layer_rgb = np.ascontiguousarray(layer_rgb if L else np.zeros((1, 1, 3)), np.float32)
+    assert calls.ndim == 2 and calls.shape[1] == 7 and features.shape == (n, F) and (L == 0 or layer_rgb.shape == (L, n, 3))
+    if table is not None:
+        table = np.ascontiguousarray(table, np.float32)
+        assert table.ndim == 2 and table.shape[0] == table.shape[1]
+    mk = lambda *shape: np.empty(shape, np.float32)
+    ns, mean, cov, hist = mk(H, W, 1), mk(H, W, 3), mk(H, W, 6), mk(H, W, 3 * nbins)
+    lmean, lcov = mk(max(L, 1), H, W, 3), mk(max(L, 1), H, W, 6)
+    fmean, fvar = mk(H, W, max(F, 1)), mk(H, W, max(F, 1))
+    counts = (C.c_longlong * 2)()
+    rx, ry = radius if radius is not None else (0.0, 0.0)
+    path = lambda p: None if p is None else os.fsencode(str(p))
+    rc = lib().bcdcore_device_accumulate_features(_fp(calls), C.c_longlong(n), _fp(layer_rgb), int(L), _fp(features), int(F), W, H, nbins, C.c_float(gamma),
+                                                  C.c_float(maxval), int(device), C.c_float(rx), C.c_float(ry),
+                                                  int(table.shape[0]) if table is not None else 0, _fp(table) if table is not None else None,
+                                                  C.c_longlong(batch), C.c_char_p(path(state_path)), C.c_char_p(path(layers_path)),
+                                                  C.c_char_p(path(features_path)), int(bool(merge_again)), _fp(ns), _fp(mean), _fp(cov), _fp(hist),
+                                                  _fp(lmean), _fp(lcov), _fp(fmean), _fp(fvar), counts)
+    if rc != 0:
+        lib().bcdcore_device_accumulate_error.restype = C.c_char_p
+        raise RuntimeError("DeviceSamplesAccumulator: " + lib().bcdcore_device_accumulate_error().decode())
+    return (ns, mean, cov, hist), [(lmean[k], lcov[k]) for k in range(L)], (fmean, fvar), (counts[0], counts[1])
+
+
+def device_features_refusals(nb_layers, nb_features, device=0):
+    """what a bcd::DeviceSamplesAccumulator with these counts answers, with or without a device: -> (isValid() after the constructor, the
+    messages of lastError() after the constructor, addSample, splatSample, addSamples without features, addSamples and splatSamples with
+    null features; a seventh line if a refused add was applied)"""
+    buf = C.create_string_buffer(4096)
+    valid = lib().bcdcore_device_features_refusals(int(nb_layers), int(nb_features), int(device), buf, len(buf))
+    return bool(valid), buf.value.decode().split("\n")[:-1]
+
+
 def device_plan(samples, W, H, budget, offset=0, threshold=0.0, eps=1e-3, min_samples=2.0, max_per_pixel=16, nbins=20, gamma=2.2, maxval=2.5,
                 device=0, invalid_first=False):
     """the stream through bcd::DeviceSamplesAccumulator::addSample (left in its host buffer), then planSamples -> (pixel list, summary dict);

@@ -21,6 +21,8 @@ struct bcd_hip_accum {
     DevBuf state;                  // (11 + 3 nbins) planes of N floats
     int nlayers = 0;               // extra colour layers (bcd_hip_accum_create_layers)
     DevBuf layers;                 // nlayers x 9 planes of N floats: 3 colour sums, 6 second moments, layer after layer
+    int nfeat = 0;                 // auxiliary feature channels (bcd_hip_accum_create_features)
+    DevBuf features;               // nfeat x 2 planes of N floats: the weighted sum and the weighted sum of squares, channel after channel
     DevBuf dropped;                // unsigned long long: scattered samples with an index outside [0, N)
     DevBuf keys[2], vals[2], sort; // scattered-add scratch (grow-only)
     int64_t capacity = 0;          // > 0: samples per sorted chunk, scratch allocated at create time
@@ -50,6 +52,7 @@ namespace {
 
 size_t accum_state_bytes(const bcd_hip_accum *a) { return (size_t)(11 + 3 * a->nbins) * (size_t)a->N * sizeof(float); }
 size_t accum_layer_bytes(const bcd_hip_accum *a) { return (size_t)(9 * a->nlayers) * (size_t)a->N * sizeof(float); }
+size_t accum_feature_bytes(const bcd_hip_accum *a) { return (size_t)(2 * a->nfeat) * (size_t)a->N * sizeof(float); }
 
 // scratch of the scattered path for chunks of n samples
 int accum_scratch(bcd_hip_accum *a, int64_t n)
@@ -104,9 +107,9 @@ int accum_splat_scratch(bcd_hip_accum *a)
 
 } // namespace
 
-// create and create_layers (nb_layers = 0: no layer planes)
+// create, create_layers and create_features (nb_layers = 0: no layer planes; nb_features = 0: no feature planes)
 static int accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
-                        bcd_hip_accum **acc)
+                        int nb_features, bcd_hip_accum **acc)
 {
     if (W <= 0 || H <= 0 || (int64_t)W * H >= ((int64_t)1 << 31)) return bad(ctx, "frame size must be positive and below 2^31 pixels");
     if (nb_bins < 2) return bad(ctx, "nb_bins must be >= 2");
@@ -119,8 +122,10 @@ static int accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma
     a->N = (int64_t)W * H;
     a->capacity = max_batch_samples;
     a->nlayers = nb_layers;
+    a->nfeat = nb_features;
     int rc = ensure(ctx, a->state, accum_state_bytes(a));
     if (rc == BCD_HIP_OK && nb_layers > 0) rc = ensure(ctx, a->layers, accum_layer_bytes(a));
+    if (rc == BCD_HIP_OK && nb_features > 0) rc = ensure(ctx, a->features, accum_feature_bytes(a));
     if (rc == BCD_HIP_OK) rc = ensure(ctx, a->dropped, sizeof(unsigned long long));
     if (rc == BCD_HIP_OK && hipEventCreateWithFlags(&a->ev_merge, hipEventDisableTiming) != hipSuccess) {
         a->ev_merge = nullptr;
@@ -141,7 +146,7 @@ int bcd_hip_accum_create(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamm
     if (!ctx) return BCD_HIP_EINVAL;
     if (!acc) return bad(ctx, "null accumulator handle");
     *acc = nullptr;
-    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, 0, acc);
+    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, 0, 0, acc);
 }
 
 int bcd_hip_accum_create_layers(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
@@ -151,7 +156,26 @@ int bcd_hip_accum_create_layers(bcd_hip_ctx *ctx, int W, int H, int nb_bins, flo
     if (!acc) return bad(ctx, "null accumulator handle");
     *acc = nullptr;
     if (nb_layers < 1 || nb_layers > BCD_HIP_ACCUM_MAX_LAYERS) return bad(ctx, "nb_layers must be in [1, 15]");
-    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, nb_layers, acc);
+    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, nb_layers, 0, acc);
+}
+
+int bcd_hip_accum_create_features(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
+                                  int nb_features, bcd_hip_accum **acc)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!acc) return bad(ctx, "null accumulator handle");
+    *acc = nullptr;
+    if (nb_layers < 0 || nb_layers > BCD_HIP_ACCUM_MAX_LAYERS) return bad(ctx, "nb_layers must be in [0, 15]");
+    if (nb_features < 1 || nb_features > BCD_HIP_ACCUM_MAX_FEATURES) return bad(ctx, "nb_features must be in [1, 8]");
+    return accum_create(ctx, W, H, nb_bins, gamma, max_value, max_batch_samples, nb_layers, nb_features, acc);
+}
+
+int bcd_hip_accum_nb_features(bcd_hip_accum *acc, int *nb_features)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    if (!nb_features) return bad(acc->ctx, "null feature count");
+    *nb_features = acc->nfeat;
+    return BCD_HIP_OK;
 }
 
 int bcd_hip_accum_nb_layers(bcd_hip_accum *acc, int *nb_layers)
@@ -170,7 +194,7 @@ void bcd_hip_accum_destroy(bcd_hip_accum *acc)
     for (DevBuf *b : { &acc->state, &acc->dropped, &acc->keys[0], &acc->keys[1], &acc->vals[0], &acc->vals[1], &acc->sort, &acc->plan_red,
                        &acc->plan_c, &acc->plan_ends, &acc->plan_err, &acc->plan_cnt, &acc->plan_tmp })
         if (b->p) (void)hipFree(b->p);
-    for (DevBuf *b : { &acc->table, &acc->cells, &acc->layers })
+    for (DevBuf *b : { &acc->table, &acc->cells, &acc->layers, &acc->features })
         if (b->p) (void)hipFree(b->p);
     if (acc->table_stage) (void)hipHostFree(acc->table_stage);
     if (acc->filter_ev) (void)hipEventDestroy(acc->filter_ev);
@@ -190,6 +214,7 @@ int bcd_hip_accum_reset(bcd_hip_accum *acc)
     DEVICE_GUARD(ctx);
     HIPCHK(ctx, hipMemsetAsync(acc->state.p, 0, accum_state_bytes(acc), ctx->stream));
     if (acc->nlayers > 0) HIPCHK(ctx, hipMemsetAsync(acc->layers.p, 0, accum_layer_bytes(acc), ctx->stream));
+    if (acc->nfeat > 0) HIPCHK(ctx, hipMemsetAsync(acc->features.p, 0, accum_feature_bytes(acc), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(acc->dropped.p, 0, sizeof(unsigned long long), ctx->stream));
     acc->submitted = 0;
     return BCD_HIP_OK;
@@ -200,8 +225,17 @@ namespace {
 // the refusals of the adds: a plain add would move a layered accumulator's weight sums without its layers
 int accum_check_layered(bcd_hip_accum *acc, bool layered_call)
 {
+    if (acc->nfeat > 0) return bad(acc->ctx, "the accumulator has feature channels: use the _features form of this add");
     if (layered_call && acc->nlayers == 0) return bad(acc->ctx, "the accumulator has no layers (bcd_hip_accum_create_layers)");
     if (!layered_call && acc->nlayers > 0) return bad(acc->ctx, "the accumulator has colour layers: use the _layers form of this add");
+    return BCD_HIP_OK;
+}
+
+// the refusals of a _features add: the layer list is there exactly when the accumulator has layers
+int accum_check_featured(bcd_hip_accum *acc, const float *const *d_layers)
+{
+    if (acc->nfeat == 0) return bad(acc->ctx, "the accumulator has no feature channels (bcd_hip_accum_create_features)");
+    if (d_layers && acc->nlayers == 0) return bad(acc->ctx, "a layer list on an accumulator without layers");
     return BCD_HIP_OK;
 }
 
@@ -224,11 +258,14 @@ BcdAccumLayerIn accum_layer_offset(const bcd_hip_accum *acc, const BcdAccumLayer
     return o;
 }
 
-// the three adds; layers: the table of a _layers call, or nullptr on an accumulator without layers
+// the three adds; layers: the table of a _layers call, or nullptr on an accumulator without layers; d_features: the samples' feature
+// channels on an accumulator with features (never null there), laid out like the beauty's samples of the call
 int accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
-                    const float *const *d_layer_samples, int layer_channels);
-int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb);
-int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb);
+                    const float *const *d_layer_samples, int layer_channels, const float *d_features);
+int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb,
+                        const float *d_features);
+int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb,
+                       const float *d_features);
 
 } // namespace
 
@@ -236,7 +273,7 @@ int bcd_hip_accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const fl
 {
     if (!acc) return BCD_HIP_EINVAL;
     RCCHK(accum_check_layered(acc, false));
-    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, nullptr, 3);
+    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, nullptr, 3, nullptr);
 }
 
 int bcd_hip_accum_add_dense_layers(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
@@ -244,14 +281,14 @@ int bcd_hip_accum_add_dense_layers(bcd_hip_accum *acc, const float *d_samples, c
 {
     if (!acc) return BCD_HIP_EINVAL;
     RCCHK(accum_check_layered(acc, true));
-    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, d_layer_samples, layer_channels);
+    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, d_layer_samples, layer_channels, nullptr);
 }
 
 int bcd_hip_accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n)
 {
     if (!acc) return BCD_HIP_EINVAL;
     RCCHK(accum_check_layered(acc, false));
-    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, nullptr);
+    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, nullptr, nullptr);
 }
 
 int bcd_hip_accum_add_scattered_layers(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n,
@@ -259,14 +296,14 @@ int bcd_hip_accum_add_scattered_layers(bcd_hip_accum *acc, const int32_t *d_pixe
 {
     if (!acc) return BCD_HIP_EINVAL;
     RCCHK(accum_check_layered(acc, true));
-    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, d_layer_rgb);
+    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, d_layer_rgb, nullptr);
 }
 
 int bcd_hip_accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n)
 {
     if (!acc) return BCD_HIP_EINVAL;
     RCCHK(accum_check_layered(acc, false));
-    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, nullptr);
+    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, nullptr, nullptr);
 }
 
 int bcd_hip_accum_add_splatted_layers(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n,
@@ -274,13 +311,40 @@ int bcd_hip_accum_add_splatted_layers(bcd_hip_accum *acc, const float *d_xy, con
 {
     if (!acc) return BCD_HIP_EINVAL;
     RCCHK(accum_check_layered(acc, true));
-    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, d_layer_rgb);
+    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, d_layer_rgb, nullptr);
+}
+
+int bcd_hip_accum_add_dense_features(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
+                                     const float *const *d_layer_samples, int layer_channels, const float *d_features)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_featured(acc, d_layer_samples));
+    if (!d_features) return bad(acc->ctx, "null features");
+    return accum_add_dense(acc, d_samples, d_weights, row_begin, rows, spp, channels, d_layer_samples, layer_channels, d_features);
+}
+
+int bcd_hip_accum_add_scattered_features(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n,
+                                         const float *const *d_layer_rgb, const float *d_features)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_featured(acc, d_layer_rgb));
+    if (n > 0 && !d_features) return bad(acc->ctx, "null features");
+    return accum_add_scattered(acc, d_pixel, d_rgb, d_weights, n, d_layer_rgb, d_features);
+}
+
+int bcd_hip_accum_add_splatted_features(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n,
+                                        const float *const *d_layer_rgb, const float *d_features)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    RCCHK(accum_check_featured(acc, d_layer_rgb));
+    if (n > 0 && !d_features) return bad(acc->ctx, "null features");
+    return accum_add_splatted(acc, d_xy, d_rgb, d_weights, n, d_layer_rgb, d_features);
 }
 
 namespace {
 
 int accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
-                    const float *const *d_layer_samples, int layer_channels)
+                    const float *const *d_layer_samples, int layer_channels, const float *d_features)
 {
     bcd_hip_ctx *ctx = acc->ctx;
     if (!d_samples) return bad(ctx, "null samples");
@@ -297,11 +361,15 @@ int accum_add_dense(bcd_hip_accum *acc, const float *d_samples, const float *d_w
     if (acc->nlayers > 0)
         HIPCHK(ctx, bcd_launch_accum_dense_layers(in, acc->nlayers, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, layer_channels,
                                                   (float *)acc->layers.p, ctx->stream));
+    if (acc->nfeat > 0)
+        HIPCHK(ctx, bcd_launch_feat_dense(d_features, acc->nfeat, d_weights, (int64_t)row_begin * acc->W, npix, acc->N, spp, (float *)acc->features.p,
+                                          ctx->stream));
     acc->submitted += npix * spp;
     return BCD_HIP_OK;
 }
 
-int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb)
+int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb,
+                        const float *d_features)
 {
     bcd_hip_ctx *ctx = acc->ctx;
     if (n < 0) return bad(ctx, "negative sample count");
@@ -324,6 +392,9 @@ int accum_add_scattered(bcd_hip_accum *acc, const int32_t *d_pixel, const float 
         if (acc->nlayers > 0) // (on the chunk's sorted keys and values, before the next chunk overwrites them)
             HIPCHK(ctx, bcd_launch_accum_segments_layers(k1, v1, m, acc->N, accum_layer_offset(acc, in, b * 3), acc->nlayers,
                                                          d_weights ? d_weights + b : nullptr, (float *)acc->layers.p, ctx->stream));
+        if (acc->nfeat > 0) // (the features too)
+            HIPCHK(ctx, bcd_launch_feat_segments(k1, v1, m, acc->N, d_features + b * acc->nfeat, acc->nfeat, d_weights ? d_weights + b : nullptr,
+                                                 (float *)acc->features.p, ctx->stream));
     }
     acc->submitted += n;
     return BCD_HIP_OK;
@@ -372,7 +443,8 @@ int bcd_hip_accum_set_filter(bcd_hip_accum *acc, float radius_x, float radius_y,
 
 namespace {
 
-int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb)
+int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n, const float *const *d_layer_rgb,
+                       const float *d_features)
 {
     bcd_hip_ctx *ctx = acc->ctx;
     if (!acc->has_filter) return bad(ctx, "the accumulator has no filter (bcd_hip_accum_set_filter)");
@@ -413,6 +485,10 @@ int accum_add_splatted(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb
         for (int l = 0; l < acc->nlayers; ++l)
             HIPCHK(ctx, bcd_launch_splat(acc->cells.p, v1, xy, in.src[l] + 3 * b, w, acc->W, acc->H, acc->filter_f, g, (const float *)acc->table.p, cap,
                                          acc->nbins, acc->gamma, acc->maxval, (float *)acc->layers.p + (size_t)l * 9 * (size_t)acc->N, ctx->stream, true));
+        // the features on the same cells and sorted values; their staging arrays are sized from the channel count (cap is cut to fit)
+        if (acc->nfeat > 0)
+            HIPCHK(ctx, bcd_launch_feat_splat(acc->cells.p, v1, xy, d_features + b * acc->nfeat, acc->nfeat, w, acc->W, acc->H, acc->filter_f, g,
+                                              (const float *)acc->table.p, cap, (float *)acc->features.p, ctx->stream));
     }
     acc->submitted += n;
     return BCD_HIP_OK;
@@ -484,6 +560,20 @@ int bcd_hip_accum_layer_statistics(bcd_hip_accum *acc, float *const *d_mean, flo
     return BCD_HIP_OK;
 }
 
+int bcd_hip_accum_feature_statistics(bcd_hip_accum *acc, float *d_features, float *d_variances)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (acc->nfeat == 0) return bad(ctx, "the accumulator has no feature channels (bcd_hip_accum_create_features)");
+    if (!d_features) return bad(ctx, "null output");
+    const uintptr_t f = (uintptr_t)d_features, v = (uintptr_t)d_variances, bytes = (uintptr_t)acc->N * acc->nfeat * sizeof(float);
+    if (d_variances && f < v + bytes && v < f + bytes) return bad(ctx, "the feature and variance outputs overlap");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_feat_snapshot((const float *)acc->state.p, (const float *)acc->features.p, acc->N, acc->nfeat, d_features, d_variances,
+                                         ctx->stream));
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_accum_info(bcd_hip_accum *acc, int64_t *samples_added, int64_t *dropped)
 {
     if (!acc) return BCD_HIP_EINVAL;
@@ -546,6 +636,7 @@ namespace {
 constexpr size_t STATE_CHUNK = (size_t)64 << 20; // bound of a staging / scratch chunk
 const char STATE_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'S', 'T' };
 const char LAYERS_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'L', 'Y' };
+const char FEATURES_MAGIC[8] = { 'B', 'C', 'D', 'A', 'C', 'C', 'F', 'T' };
 
 // what is wrong with a serialised layer block of `bytes` bytes (its header copied to *hd), or nullptr
 const char *layers_problem(const void *h, int64_t bytes, bcd_hip_accum_layers_header *hd)
@@ -573,6 +664,35 @@ int accum_check_layers(bcd_hip_accum *a, const void *h, int64_t bytes)
     if (const char *why = layers_problem(h, bytes, &hd)) return bad(a->ctx, (std::string("not an accumulator layer block (version 1): ") + why).c_str());
     if (hd.width != a->W || hd.height != a->H) return bad(a->ctx, "layer block of another frame size");
     if (hd.nb_layers != a->nlayers) return bad(a->ctx, "layer block with another number of layers");
+    return BCD_HIP_OK;
+}
+
+// what is wrong with a serialised feature block of `bytes` bytes (its header copied to *hd), or nullptr
+const char *features_problem(const void *h, int64_t bytes, bcd_hip_accum_features_header *hd)
+{
+    if (!h) return "null feature block";
+    if (bytes < BCD_HIP_ACCUM_FEATURES_HEADER_BYTES) return "shorter than the 64-byte header";
+    memcpy(hd, h, sizeof(*hd));
+    if (memcmp(hd->magic, FEATURES_MAGIC, 8) != 0) return "bad magic (not BCDACCFT)";
+    if (hd->version != BCD_HIP_ACCUM_FEATURES_VERSION) return "unsupported version (not 1)";
+    if (hd->header_bytes != BCD_HIP_ACCUM_FEATURES_HEADER_BYTES) return "header_bytes is not 64";
+    if (hd->nb_features < 1 || hd->nb_features > BCD_HIP_ACCUM_MAX_FEATURES) return "nb_features outside [1, 8]";
+    if (hd->width <= 0 || hd->height <= 0 || (int64_t)hd->width * hd->height >= ((int64_t)1 << 31)) return "width and height must be positive, below 2^31 pixels";
+    if (hd->nb_planes != (uint32_t)(2 * hd->nb_features)) return "nb_planes is not 2 nb_features";
+    if (bytes != BCD_HIP_ACCUM_FEATURES_HEADER_BYTES + 4 * (int64_t)hd->nb_planes * hd->width * hd->height) return "size is not 64 + 8 nb_features W H bytes";
+    for (uint8_t r : hd->reserved)
+        if (r != 0) return "reserved bytes are not zero";
+    return nullptr;
+}
+
+// a well-formed feature block of this accumulator's frame size and channel count?
+int accum_check_features(bcd_hip_accum *a, const void *h, int64_t bytes)
+{
+    if (a->nfeat == 0) return bad(a->ctx, "the accumulator has no feature channels (bcd_hip_accum_create_features)");
+    bcd_hip_accum_features_header hd;
+    if (const char *why = features_problem(h, bytes, &hd)) return bad(a->ctx, (std::string("not an accumulator feature block (version 1): ") + why).c_str());
+    if (hd.width != a->W || hd.height != a->H) return bad(a->ctx, "feature block of another frame size");
+    if (hd.nb_features != a->nfeat) return bad(a->ctx, "feature block with another number of channels");
     return BCD_HIP_OK;
 }
 
@@ -611,6 +731,7 @@ int accum_check_pair(bcd_hip_accum *dst, bcd_hip_accum *src)
     if (dst == src) return bad(dst->ctx, "an accumulator cannot be merged into itself");
     if (dst->W != src->W || dst->H != src->H || dst->nbins != src->nbins) return bad(dst->ctx, "accumulators of different frame sizes or bin counts");
     if (dst->nlayers != src->nlayers) return bad(dst->ctx, "accumulators with different numbers of layers");
+    if (dst->nfeat != src->nfeat) return bad(dst->ctx, "accumulators with different numbers of feature channels");
     if (memcmp(&dst->gamma, &src->gamma, sizeof(float)) != 0 || memcmp(&dst->maxval, &src->maxval, sizeof(float)) != 0)
         return bad(dst->ctx, "accumulators with different gamma or max value");
     return BCD_HIP_OK;
@@ -768,20 +889,21 @@ int bcd_hip_accum_merge(bcd_hip_accum *dst, bcd_hip_accum *src)
     DEVICE_GUARD(ctx);
     // ... comes before the reads on dst's stream
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, src->ev_merge, 0));
-    const size_t S = accum_state_bytes(dst), SL = accum_layer_bytes(dst);
+    const size_t S = accum_state_bytes(dst), SL = accum_layer_bytes(dst), SF = accum_feature_bytes(dst);
     const char *env = getenv("BCD_HIP_ACCUM_MERGE_COPY"); // 1: the chunked copy of a cross-device merge on one device too (tests)
     if (sctx->device == ctx->device && !(env && env[0] == '1')) {
         HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->state.p, (const float *)src->state.p, (int64_t)(S / 4), ctx->num_cus, ctx->stream));
         if (SL) HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->layers.p, (const float *)src->layers.p, (int64_t)(SL / 4), ctx->num_cus, ctx->stream));
+        if (SF) HIPCHK(ctx, bcd_launch_accum_merge((float *)dst->features.p, (const float *)src->features.p, (int64_t)(SF / 4), ctx->num_cus, ctx->stream));
         HIPCHK(ctx, bcd_launch_accum_counter((unsigned long long *)dst->dropped.p, (const unsigned long long *)src->dropped.p, 0, 1, ctx->stream));
     } else {
         // src's state in chunks into dst-side scratch (peer copies; no peer access needed), each chunk merged after its copy
         RCCHK(accum_chunks(dst, false));
         const size_t c = dst->chunk_bytes;
-        for (int part = 0; part < 2; ++part) { // the shared state, then the layer planes
-            uint8_t *st = (uint8_t *)(part ? dst->layers.p : dst->state.p);
-            const uint8_t *ss = (const uint8_t *)(part ? src->layers.p : src->state.p);
-            const size_t bytes = part ? SL : S;
+        for (int part = 0; part < 3; ++part) { // the shared state, then the layer planes, then the feature planes
+            uint8_t *st = (uint8_t *)(part == 0 ? dst->state.p : part == 1 ? dst->layers.p : dst->features.p);
+            const uint8_t *ss = (const uint8_t *)(part == 0 ? src->state.p : part == 1 ? src->layers.p : src->features.p);
+            const size_t bytes = part == 0 ? S : part == 1 ? SL : SF;
             for (size_t off = 0, i = 0; off < bytes; off += c, ++i) {
                 void *buf = dst->chunk[i & 1];
                 const size_t len = std::min(c, bytes - off);
@@ -865,6 +987,70 @@ int bcd_hip_accum_merge_layers_state(bcd_hip_accum *acc, const void *h_layers, i
     RCCHK(accum_check_layers(acc, h_layers, bytes));
     DEVICE_GUARD(ctx);
     return accum_from_host(acc, acc->layers.p, accum_layer_bytes(acc), (const uint8_t *)h_layers + BCD_HIP_ACCUM_LAYERS_HEADER_BYTES, true);
+}
+
+// ---- the feature block: the feature planes beside the v1 state and the layer block -----------------------------
+static_assert(sizeof(bcd_hip_accum_features_header) == BCD_HIP_ACCUM_FEATURES_HEADER_BYTES && offsetof(bcd_hip_accum_features_header, version) == 8 &&
+                  offsetof(bcd_hip_accum_features_header, header_bytes) == 12 && offsetof(bcd_hip_accum_features_header, width) == 16 &&
+                  offsetof(bcd_hip_accum_features_header, height) == 20 && offsetof(bcd_hip_accum_features_header, nb_features) == 24 &&
+                  offsetof(bcd_hip_accum_features_header, nb_planes) == 28 && offsetof(bcd_hip_accum_features_header, reserved) == 32,
+              "bcd_hip_accum_features_header layout (version 1)");
+
+int bcd_hip_accum_features_state_info(const void *h_features, int64_t bytes, bcd_hip_accum_features_header *out)
+{
+    bcd_hip_accum_features_header hd;
+    if (features_problem(h_features, bytes, &hd)) return BCD_HIP_EINVAL;
+    if (out) *out = hd;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_features_state_bytes(bcd_hip_accum *acc, int64_t *bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    if (!bytes) return bad(acc->ctx, "null size");
+    if (acc->nfeat == 0) return bad(acc->ctx, "the accumulator has no feature channels (bcd_hip_accum_create_features)");
+    *bytes = BCD_HIP_ACCUM_FEATURES_HEADER_BYTES + (int64_t)accum_feature_bytes(acc);
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_accum_export_features(bcd_hip_accum *acc, void *h_features, int64_t capacity)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    if (acc->nfeat == 0) return bad(ctx, "the accumulator has no feature channels (bcd_hip_accum_create_features)");
+    const size_t S = accum_feature_bytes(acc);
+    if (!h_features) return bad(ctx, "null feature block buffer");
+    if (capacity < BCD_HIP_ACCUM_FEATURES_HEADER_BYTES + (int64_t)S) return bad(ctx, "buffer smaller than bcd_hip_accum_features_state_bytes");
+    DEVICE_GUARD(ctx);
+    RCCHK(accum_chunks(acc, true));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (no staging copy is in flight after it)
+    bcd_hip_accum_features_header hd;
+    memset(&hd, 0, sizeof(hd));
+    memcpy(hd.magic, FEATURES_MAGIC, 8);
+    hd.version = BCD_HIP_ACCUM_FEATURES_VERSION;
+    hd.header_bytes = BCD_HIP_ACCUM_FEATURES_HEADER_BYTES;
+    hd.width = acc->W; hd.height = acc->H; hd.nb_features = acc->nfeat;
+    hd.nb_planes = (uint32_t)(2 * acc->nfeat);
+    memcpy(h_features, &hd, sizeof(hd));
+    return accum_to_host(acc, acc->features.p, S, (uint8_t *)h_features + BCD_HIP_ACCUM_FEATURES_HEADER_BYTES);
+}
+
+int bcd_hip_accum_import_features(bcd_hip_accum *acc, const void *h_features, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    RCCHK(accum_check_features(acc, h_features, bytes));
+    DEVICE_GUARD(ctx);
+    return accum_from_host(acc, acc->features.p, accum_feature_bytes(acc), (const uint8_t *)h_features + BCD_HIP_ACCUM_FEATURES_HEADER_BYTES, false);
+}
+
+int bcd_hip_accum_merge_features_state(bcd_hip_accum *acc, const void *h_features, int64_t bytes)
+{
+    if (!acc) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = acc->ctx;
+    RCCHK(accum_check_features(acc, h_features, bytes));
+    DEVICE_GUARD(ctx);
+    return accum_from_host(acc, acc->features.p, accum_feature_bytes(acc), (const uint8_t *)h_features + BCD_HIP_ACCUM_FEATURES_HEADER_BYTES, true);
 }
 
 } // extern "C"

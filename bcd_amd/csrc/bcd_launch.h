@@ -223,3 +223,12 @@ hipError_t bcd_launch_accum_plan(const float *st, int64_t N, float eps, float mi
                                  hipStream_t s);
 hipError_t bcd_launch_accum_merge(float *dst, const float *src, int64_t n, int num_cus, hipStream_t s);
 hipError_t bcd_launch_accum_counter(unsigned long long *dst, const unsigned long long *src, unsigned long long add, int keep, hipStream_t s);
+
+// ---- k_accum_features.hip (F: feature channels, 1 .. 8; ft: the 2 F feature planes; feat: F consecutive floats per sample)
+hipError_t bcd_launch_feat_dense(const float *feat, int F, const float *weights, int64_t p0, int64_t npix, int64_t N, int k, float *ft, hipStream_t s);
+hipError_t bcd_launch_feat_segments(const uint32_t *keys, const uint32_t *vals, int64_t n, int64_t N, const float *feat, int F, const float *weights, float *ft,
+                                    hipStream_t s);
+int bcd_feat_splat_max_staged(int ts, int F);
+hipError_t bcd_launch_feat_splat(const void *cells, const uint32_t *vals, const float *xy, const float *feat, int F, const float *weights, int W, int H,
+                                 const float *filter, const int *geom, const float *T, int cap, float *ft, hipStream_t s);
+hipError_t bcd_launch_feat_snapshot(const float *st, const float *ft, int64_t N, int F, float *omean, float *ovar, hipStream_t s);

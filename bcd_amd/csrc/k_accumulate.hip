@@ -19,11 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "accum_kernels.h"
 #include "bcd_common.h"
 
 namespace {
-
-enum { ACC_W = 0, ACC_W2 = 1, ACC_M = 2, ACC_C = 5, ACC_H = 11 };
 
 // the binning of one colour channel, SamplesAccumulator.cpp:66-90 (same expressions as k_accumulate_samples)
 __device__ inline void acc_bin(float x, int nbins, float gamma, float maxval, int &lo, float &lw, float &hw)
@@ -244,24 +243,6 @@ __global__ __launch_bounds__(256) void k_accum_segments_layers(const uint32_t *_
 // continuous positions go through the accumulator's reconstruction filter to every pixel of their footprint.  Gather form: the n samples
 // are sorted by their CELL (the pixel floor(x), floor(y) on the frame extended by (kx, ky)), and one thread per destination pixel merges
 // the runs of the cells around it by batch position -- the pixel's contributions in stream order, no float atomics.
-struct SplatFilter {
-    float rx, ry, inv_rx, inv_ry;
-    int ts;     // the table is ts x ts
-    int kx, ky; // K of the definition: the key frame is extended by it, the candidate pixels of a sample are c0 +- kx, l0 +- ky
-    int nx, ny; // cells further than this from a pixel hold no sample that passes dx < rx (nx <= kx: smallest m with m + 0.5 >= rx)
-};
-
-// the filter value of the definition for pixel (col, line) and a sample at (x, y); 0: the pixel is not in the sample's footprint
-__device__ inline float splat_weight(const SplatFilter &F, const float *T, float x, float y, int col, int line)
-{
-    const float dx = fabsf(((float)col + 0.5f) - x), dy = fabsf(((float)line + 0.5f) - y);
-    if (!(dx < F.rx && dy < F.ry)) return 0.f;
-    int ix = (int)(dx * F.inv_rx * (float)F.ts), iy = (int)(dy * F.inv_ry * (float)F.ts);
-    ix = ix < F.ts - 1 ? ix : F.ts - 1;
-    iy = iy < F.ts - 1 ? iy : F.ts - 1;
-    return T[iy * F.ts + ix];
-}
-
 // step 1: key = the sample's cell on the extended frame, value = position in the batch.  Samples that contribute nothing (position not
 // finite or outside the extended frame, empty footprint: a pure function of the sample and the filter) get the past-the-end key and are
 // counted as dropped (integer atomics, one per wavefront)
@@ -306,109 +287,37 @@ __global__ __launch_bounds__(256) void k_accum_splat_cells(const uint32_t *__res
     if (i == n - 1 || keys[i + 1] != key) cells[key].y = (uint32_t)(i + 1);
 }
 
-// step 4.  A workgroup of 256 threads owns a tile of SPLAT_TX x SPLAT_TY destination pixels (a wavefront: 2 lines of 32 pixels, 128
-// consecutive bytes of every plane per line).  Its RING: the cells of the tile's pixels plus (nx, ny) on each side, row-major.
-#define SPLAT_TX 32
-#define SPLAT_TY 8
-#define SPLAT_MAX_NB 3                                                                       // nx, ny <= 3 (radii <= 3)
-#define SPLAT_RING_MAX ((SPLAT_TX + 2 * SPLAT_MAX_NB) * (SPLAT_TY + 2 * SPLAT_MAX_NB))       // 38 x 14 = 532 cells
-#define SPLAT_ROWS_MAX (2 * SPLAT_MAX_NB + 1)
+// step 4 (the tile, its ring and the merge of a pixel's runs: accum_kernels.h)
 #define SPLAT_SAMPLE_BYTES 28                                                                // staged: position, x, y, r, g, b, weight
-#define SPLAT_LDS_BYTES (64 * 1024)
-#define SPLAT_NONE 0xffffffffu
 
-// the samples of the ring's cells: STAGED in LDS (index = slot in the staged arrays), or read from the sorted arrays in global memory
-// (index = place in the sorted batch) when the ring's samples do not fit the staging arrays -- the same values in the same order
+// the samples of the ring's cells with their colours and weights
 template <bool STAGED>
-struct SplatRuns {
-    const uint32_t *g0, *b0;                          // LDS, per ring cell: start in the sorted batch; start in the staged arrays (b0[rc + 1]: end)
-    const uint32_t *s_pos;                            // LDS staging arrays
-    const float *s_x, *s_y, *s_r, *s_g, *s_b, *s_w;
-    const uint32_t *vals;                             // the sorted batch positions and the batch itself
-    const float *xy, *rgb, *weights;
-    __device__ uint32_t begin(int rc) const { return STAGED ? b0[rc] : g0[rc]; }
-    __device__ uint32_t count(int rc) const { return b0[rc + 1] - b0[rc]; }
-    __device__ uint32_t pos(uint32_t i) const { return STAGED ? s_pos[i] : vals[i]; }
-    __device__ void position(uint32_t i, float &x, float &y) const
-    {
-        if (STAGED) { x = s_x[i]; y = s_y[i]; }
-        else { const int64_t e = vals[i]; x = xy[2 * e]; y = xy[2 * e + 1]; }
-    }
+struct SplatRuns : SplatKeys<STAGED> {
+    const float *s_r, *s_g, *s_b, *s_w;               // LDS staging arrays
+    const float *rgb, *weights;                       // the batch itself
     __device__ void colour(uint32_t i, float &R, float &G, float &B, float &w) const
     {
         if (STAGED) { R = s_r[i]; G = s_g[i]; B = s_b[i]; w = s_w[i]; }
-        else { const int64_t e = vals[i]; R = rgb[3 * e]; G = rgb[3 * e + 1]; B = rgb[3 * e + 2]; w = weights ? weights[e] : 1.f; }
+        else { const int64_t e = this->vals[i]; R = rgb[3 * e]; G = rgb[3 * e + 1]; B = rgb[3 * e + 2]; w = weights ? weights[e] : 1.f; }
     }
 };
 
-// the earliest sample at batch position >= next, in the 2 nx + 1 cells rc0.. of one ring row, that has pixel (col, line) in its footprint:
-// its position (SPLAT_NONE: none), index and filter value.  Every run ascends in position.
-template <bool STAGED>
-__device__ inline void splat_row_next(const SplatRuns<STAGED> &S, const SplatFilter &F, const float *T, int rc0, int col, int line, uint32_t next,
-                                      uint32_t &bpos, uint32_t &bidx, float &bf)
-{
-    bpos = SPLAT_NONE; bidx = 0; bf = 0.f;
-    for (int c = 0; c <= 2 * F.nx; ++c) {
-        const uint32_t b = S.begin(rc0 + c), cnt = S.count(rc0 + c);
-        uint32_t lo = 0, hi = cnt;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (S.pos(b + mid) < next) lo = mid + 1;
-            else hi = mid;
-        }
-        for (uint32_t k = lo; k < cnt; ++k) {
-            const uint32_t p = S.pos(b + k);
-            if (p >= bpos) break; // (later than the best of the cells before)
-            float x, y;
-            S.position(b + k, x, y);
-            const float f = splat_weight(F, T, x, y, col, line);
-            if (f != 0.f) { bpos = p; bidx = b + k; bf = f; break; }
-        }
-    }
-}
-
-// one destination pixel: merges the 2 ny + 1 ring rows' candidates by batch position and adds each contribution as k_accum_segments does.
-// rc0: the ring cell at the top left of the pixel's neighbourhood; RW: cells per ring row.  LAYER: st is a layer's nine planes and the
+// one destination pixel: adds each contribution of splat_merge as k_accum_segments does.  LAYER: st is a layer's nine planes and the
 // colours are the layer's -- the sums alone, no bins
 template <bool STAGED, bool LAYER>
 __device__ inline void splat_pixel(const SplatRuns<STAGED> &S, const SplatFilter &F, const float *T, int rc0, int RW, int col, int line, int64_t p,
                                    int64_t N, int nbins, float gamma, float maxval, float *__restrict__ st)
 {
-    uint32_t cpos[SPLAT_ROWS_MAX], cidx[SPLAT_ROWS_MAX];
-    float cf[SPLAT_ROWS_MAX];
-#pragma unroll
-    for (int r = 0; r < SPLAT_ROWS_MAX; ++r) { cpos[r] = SPLAT_NONE; cidx[r] = 0; cf[r] = 0.f; }
-    for (int r = 0; r <= 2 * F.ny; ++r) {
-        uint32_t np, ni;
-        float nf;
-        splat_row_next(S, F, T, rc0 + r * RW, col, line, 0u, np, ni, nf);
-#pragma unroll
-        for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
-            if (q == r) { cpos[q] = np; cidx[q] = ni; cf[q] = nf; }
-    }
     float *hp = LAYER ? st : st + (int64_t)ACC_H * N + p;
     typename std::conditional<LAYER, LayerSums, AccSums>::type s;
     bool loaded = false;
-    for (;;) {
-        uint32_t best = SPLAT_NONE, idx = 0;
-        float f = 0.f;
-        int br = 0;
-#pragma unroll
-        for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
-            if (cpos[q] < best) { best = cpos[q]; idx = cidx[q]; f = cf[q]; br = q; }
-        if (best == SPLAT_NONE) break;
+    splat_merge(S, F, T, rc0, RW, col, line, [&](uint32_t idx, float f) {
         if (!loaded) { s.load(st, N, p); loaded = true; }
         float R, G, B, w;
         S.colour(idx, R, G, B, w);
         if constexpr (LAYER) s.add(R, G, B, w * f);
         else acc_add_sample(s, hp, N, R, G, B, w * f, nbins, gamma, maxval);
-        uint32_t np, ni;
-        float nf;
-        splat_row_next(S, F, T, rc0 + br * RW, col, line, best + 1u, np, ni, nf);
-#pragma unroll
-        for (int q = 0; q < SPLAT_ROWS_MAX; ++q)
-            if (q == br) { cpos[q] = np; cidx[q] = ni; cf[q] = nf; }
-    }
+    });
     if (loaded) s.store(st, N, p); // (a pixel without contributions does not touch its planes)
 }
 
@@ -427,49 +336,12 @@ __global__ __launch_bounds__(256) void k_accum_splat(const uint2 *__restrict__ c
     float *s_x = (float *)(s_pos + cap), *s_y = s_x + cap, *s_r = s_y + cap, *s_g = s_r + cap, *s_b = s_g + cap, *s_w = s_b + cap;
     const int px0 = (int)(blockIdx.x % (unsigned)tiles_x) * SPLAT_TX, py0 = (int)(blockIdx.x / (unsigned)tiles_x) * SPLAT_TY;
     const int RW = SPLAT_TX + 2 * F.nx, RC = RW * (SPLAT_TY + 2 * F.ny);
-    const int We = W + 2 * F.kx, He = H + 2 * F.ky;
-    for (int e = t; e < tt; e += 256) s_T[e] = T[e];
-    // pixel (col, line) is cell (col + kx, line + ky) of the extended frame
-    for (int rc = t; rc < RC; rc += 256) {
-        const int ex = px0 + F.kx - F.nx + rc % RW, ey = py0 + F.ky - F.ny + rc / RW;
-        uint2 c = make_uint2(0u, 0u);
-        if (ex < We && ey < He) c = cells[(int64_t)ey * We + ex];
-        s_g0[rc] = c.x;
-        s_b0[rc] = c.y - c.x;
-    }
-    __syncthreads();
-    if (t < 64) { // counts -> exclusive scan (one wavefront, `per` consecutive cells per lane)
-        const int per = (RC + 63) / 64, a = t * per;
-        uint32_t sum = 0;
-        for (int k = 0; k < per; ++k)
-            if (a + k < RC) sum += s_b0[a + k];
-        uint32_t incl = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(incl, o);
-            if (t >= o) incl += v;
-        }
-        uint32_t run = incl - sum;
-        for (int k = 0; k < per; ++k)
-            if (a + k < RC) {
-                const uint32_t c = s_b0[a + k];
-                s_b0[a + k] = run;
-                run += c;
-            }
-        if (t == 63) s_b0[RC] = incl;
-    }
-    __syncthreads();
-    const uint32_t total = s_b0[RC];
+    const uint32_t total = splat_ring_load(cells, T, F, W, H, px0, py0, s_T, s_g0, s_b0);
     if (total == 0) return;
     const bool staged = total <= (uint32_t)cap; // (uniform over the workgroup)
     if (staged) {
         for (uint32_t j = t; j < total; j += 256) {
-            int lo = 0, hi = RC; // the cell of slot j: the last one with b0 <= j
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (s_b0[mid] <= j) lo = mid;
-                else hi = mid;
-            }
-            const int64_t e = vals[s_g0[lo] + (j - s_b0[lo])];
+            const int64_t e = splat_slot_sample(s_g0, s_b0, RC, vals, j);
             s_pos[j] = (uint32_t)e;
             s_x[j] = xy[2 * e]; s_y[j] = xy[2 * e + 1];
             s_r[j] = rgb[3 * e]; s_g[j] = rgb[3 * e + 1]; s_b[j] = rgb[3 * e + 2];
@@ -482,10 +354,10 @@ __global__ __launch_bounds__(256) void k_accum_splat(const uint2 *__restrict__ c
     const int64_t N = (int64_t)W * H, p = (int64_t)line * W + col;
     const int rc0 = ly * RW + lx;
     if (staged) {
-        const SplatRuns<true> S = { s_g0, s_b0, s_pos, s_x, s_y, s_r, s_g, s_b, s_w, vals, xy, rgb, weights };
+        const SplatRuns<true> S = { { s_g0, s_b0, s_pos, s_x, s_y, vals, xy }, s_r, s_g, s_b, s_w, rgb, weights };
         splat_pixel<true, LAYER>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
     } else {
-        const SplatRuns<false> S = { s_g0, s_b0, s_pos, s_x, s_y, s_r, s_g, s_b, s_w, vals, xy, rgb, weights };
+        const SplatRuns<false> S = { { s_g0, s_b0, s_pos, s_x, s_y, vals, xy }, s_r, s_g, s_b, s_w, rgb, weights };
         splat_pixel<false, LAYER>(S, F, s_T, rc0, RW, col, line, p, N, nbins, gamma, maxval, st);
     }
 }
@@ -717,8 +589,6 @@ __global__ void k_accum_counter(unsigned long long *dst, const unsigned long lon
     *dst = (keep ? *dst : 0ull) + (src ? *src : 0ull) + add;
 }
 
-inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 } // namespace
 
 // dense passes of k >= BCD_ACCUM_STAGE_SPP samples stage the pixel's histogram in LDS
@@ -783,17 +653,6 @@ hipError_t bcd_launch_accum_segments_layers(const uint32_t *keys, const uint32_t
 }
 
 // ---- splatted add ---------------------------------------------------------------------------------------------------------------------
-namespace {
-SplatFilter splat_filter(const float *f, const int *g)
-{
-    SplatFilter F;
-    F.rx = f[0]; F.ry = f[1]; F.inv_rx = f[2]; F.inv_ry = f[3];
-    F.ts = g[0]; F.kx = g[1]; F.ky = g[2]; F.nx = g[3]; F.ny = g[4];
-    return F;
-}
-size_t splat_fixed_lds(int ts) { return ((size_t)ts * ts + 2 * SPLAT_RING_MAX + 4) * sizeof(float); }
-} // namespace
-
 // cells of a tile's ring, and the largest number of samples the staging arrays of a workgroup can hold beside a ts x ts table
 int bcd_splat_ring_cells(int nx, int ny) { return (SPLAT_TX + 2 * nx) * (SPLAT_TY + 2 * ny); }
 int bcd_splat_max_staged(int ts) { return (int)((SPLAT_LDS_BYTES - splat_fixed_lds(ts)) / SPLAT_SAMPLE_BYTES); }

@@ -5,8 +5,8 @@ import os
 import weakref
 
 from . import _prototypes
-from ._prototypes import (ACCUM_MAX_LAYERS, MAX_LAYERS, MULTI_ID_BYTES, PROGRESS_FN, SELECTION_MAX_SCALES, STATE_HEADER_BYTES, BandJob, Frame, FrameLayer,
-                          FrameLayers, Guide, GuideImages, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
+from ._prototypes import (ACCUM_MAX_FEATURES, ACCUM_MAX_LAYERS, MAX_LAYERS, MULTI_ID_BYTES, PROGRESS_FN, SELECTION_MAX_SCALES, STATE_HEADER_BYTES, BandJob,
+                          FeaturesHeader, Frame, FrameLayer, FrameLayers, Guide, GuideImages, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
                           PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SequenceFrame, SequenceInfo, SequenceMode, SequenceModeInfo, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
                           StateHeader, WarpedFrame)
 
@@ -73,6 +73,26 @@ def accum_layers_state_planes(buf):
     a = _state_buffer(buf)
     info = accum_layers_state_info(a)
     return info, a[STATE_HEADER_BYTES:].view("<f4").reshape(info["nb_layers"], 9, info["height"], info["width"])
+
+
+def accum_features_state_info(buf):
+    """the header of a serialised feature block as a dict (bcd_hip_accum_features_state_info: host only, no GPU needed); ValueError if the
+    buffer is not a well-formed block of its exact size"""
+    a = _state_buffer(buf)
+    h = FeaturesHeader()
+    rc = lib().bcd_hip_accum_features_state_info(a.ctypes.data_as(_VP) if a.size else None, a.size, C.byref(h))
+    if rc != 0:
+        raise ValueError("not a serialised accumulator feature block (version 1) of %d bytes: rc=%d" % (a.size, rc))
+    return {"magic": bytes(h.magic), "version": h.version, "header_bytes": h.header_bytes, "width": h.width, "height": h.height,
+            "nb_features": h.nb_features, "nb_planes": h.nb_planes}
+
+
+def accum_features_state_planes(buf):
+    """(header dict, float32 (nb_features, 2, H, W) view of the planes) of a serialised feature block: per channel the weighted sum, then
+    the weighted sum of squares"""
+    a = _state_buffer(buf)
+    info = accum_features_state_info(a)
+    return info, a[STATE_HEADER_BYTES:].view("<f4").reshape(info["nb_features"], 2, info["height"], info["width"])
 
 
 def default_plan_params(**kw):
@@ -1325,10 +1345,11 @@ class Context:
                                                    gamma, maxval, _dp(ns), _dp(mean), _dp(cov), _dp(hist)))
         return ns, mean, cov, hist
 
-    def accumulator(self, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0, layers=0):
+    def accumulator(self, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0, layers=0, features=0):
         """persistent device SamplesAccumulator of a W x H frame (bcd_hip_accum_*); capacity > 0: scattered batches of up to that many
-        samples never allocate; layers > 0: that many extra colour layers accumulated beside the beauty (bcd_hip_accum_create_layers)"""
-        return Accumulator(self, W, H, nbins, gamma, maxval, capacity, layers)
+        samples never allocate; layers > 0: that many extra colour layers accumulated beside the beauty (bcd_hip_accum_create_layers);
+        features > 0: that many auxiliary feature channels averaged beside the beauty (bcd_hip_accum_create_features)"""
+        return Accumulator(self, W, H, nbins, gamma, maxval, capacity, layers, features)
 
     def zero_bad_values(self, img):
         self._chk(lib().bcd_hip_zero_bad_values(self.h, _dp(img), img.numel()))
@@ -1424,10 +1445,12 @@ class Accumulator:
     """bcd_hip_accum: running sums in HBM, fed in batches (dense rows or scattered samples, each pixel in stream order), snapshots
     that go straight into Context.denoise"""
 
-    def __init__(self, ctx, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0, layers=0):
-        self.ctx, self.W, self.H, self.nbins, self.layers = ctx, W, H, nbins, int(layers)
+    def __init__(self, ctx, W, H, nbins=20, gamma=2.2, maxval=2.5, capacity=0, layers=0, features=0):
+        self.ctx, self.W, self.H, self.nbins, self.layers, self.features = ctx, W, H, nbins, int(layers), int(features)
         h = _VP()
-        if layers:                                                   # (0: the plain accumulator; anything else is checked by the library)
+        if features:                                                 # (0: no feature channels; anything else is checked by the library)
+            ctx._chk(lib().bcd_hip_accum_create_features(ctx.h, W, H, nbins, gamma, maxval, capacity, int(layers), int(features), C.byref(h)))
+        elif layers:                                                 # (0: the plain accumulator; anything else is checked by the library)
             ctx._chk(lib().bcd_hip_accum_create_layers(ctx.h, W, H, nbins, gamma, maxval, capacity, int(layers), C.byref(h)))
         else:
             ctx._chk(lib().bcd_hip_accum_create(ctx.h, W, H, nbins, gamma, maxval, capacity, C.byref(h)))
@@ -1453,13 +1476,36 @@ class Accumulator:
         self._chk(lib().bcd_hip_accum_nb_layers(self.h, C.byref(n)))
         return n.value
 
-    def add_dense(self, samples, weights=None, row0=0, layers=None):
+    def nb_features(self):
+        n = C.c_int(0)
+        self._chk(lib().bcd_hip_accum_nb_features(self.h, C.byref(n)))
+        return n.value
+
+    def _feature_args(self, features, layers, lead, layer_shape):
+        """(layer list or None, feature pointer) of a _features add; features: a float32 tensor of shape lead + (F,), required exactly when the
+        accumulator has feature channels (a plain add on such an accumulator, or features on one without, is refused by the library)"""
+        assert tuple(features.shape) == tuple(lead) + (self.features,) and features.dtype == self.ctx.torch.float32, \
+            "features: one float32 value per sample and channel, laid out like the samples"
+        arr = None
+        if layers is not None:
+            layers = list(layers)
+            assert len(layers) == self.layers, "one tensor per layer expected"
+            arr = self._layer_list(layers, layer_shape)
+        return arr, (_dp(features) if features.numel() else None)
+
+    def add_dense(self, samples, weights=None, row0=0, layers=None, features=None):
         """samples: (rows, W, k, 3 | 4) device tensor, the k samples of a pixel in accumulation order; weights: (rows, W, k) or None;
-        layers: on an accumulator with layers, one (rows, W, k, 3 | 4) tensor per layer (all of one channel count)"""
+        layers: on an accumulator with layers, one (rows, W, k, 3 | 4) tensor per layer (all of one channel count); features: on an
+        accumulator with feature channels, a (rows, W, k, F) tensor"""
         rows, W, k, ch = samples.shape
         assert W == self.W, "samples must cover whole rows of the frame"
         assert weights is None or tuple(weights.shape) == (rows, W, k)
         wp = _dp(weights) if weights is not None else None
+        if features is not None:
+            lch = next((t.shape[3] for t in (layers or ()) if t is not None), 3)
+            arr, fp = self._feature_args(features, layers, (rows, W, k), lambda t: tuple(t.shape) == (rows, W, k, lch))
+            self._chk(lib().bcd_hip_accum_add_dense_features(self.h, _dp(samples), wp, int(row0), rows, k, ch, arr, lch, fp))
+            return
         if layers is None:
             self._chk(lib().bcd_hip_accum_add_dense(self.h, _dp(samples), wp, int(row0), rows, k, ch))
             return
@@ -1469,13 +1515,17 @@ class Accumulator:
         arr = self._layer_list(layers, lambda t: tuple(t.shape) == (rows, W, k, lch))
         self._chk(lib().bcd_hip_accum_add_dense_layers(self.h, _dp(samples), wp, int(row0), rows, k, ch, arr, lch))
 
-    def add_samples(self, pixel, rgb, weights=None, layers=None):
+    def add_samples(self, pixel, rgb, weights=None, layers=None, features=None):
         """pixel: (n,) int32 line * W + col (others are dropped and counted); rgb: (n, 3); weights: (n,) or None; layers: on an
-        accumulator with layers, one (n, 3) tensor per layer"""
+        accumulator with layers, one (n, 3) tensor per layer; features: on an accumulator with feature channels, an (n, F) tensor"""
         n = pixel.shape[0]
         assert pixel.dtype == self.ctx.torch.int32 and tuple(rgb.shape) == (n, 3)
         assert weights is None or tuple(weights.shape) == (n,)
         wp = _dp(weights) if weights is not None else None
+        if features is not None:
+            arr, fp = self._feature_args(features, layers, (n,), lambda t: tuple(t.shape) == (n, 3))
+            self._chk(lib().bcd_hip_accum_add_scattered_features(self.h, _dp(pixel), _dp(rgb), wp, n, arr, fp))
+            return
         if layers is None:
             self._chk(lib().bcd_hip_accum_add_scattered(self.h, _dp(pixel), _dp(rgb), wp, n))
             return
@@ -1502,14 +1552,20 @@ class Accumulator:
                 raise ValueError("a filter table must be a square 2-D array")
         self._chk(lib().bcd_hip_accum_set_filter(self.h, rx, ry, table.shape[0], table.ctypes.data_as(_VP)))
 
-    def add_splatted(self, xy, rgb, weights=None, layers=None):
+    def add_splatted(self, xy, rgb, weights=None, layers=None, features=None):
         """xy: (n, 2) float32 continuous positions (x, y), pixel (col, line) covering [col, col + 1) x [line, line + 1); rgb: (n, 3);
         weights: (n,) or None.  Every sample goes to the pixels of its filter footprint, each pixel in stream order.  layers: on an
-        accumulator with layers, one (n, 3) tensor per layer"""
+        accumulator with layers, one (n, 3) tensor per layer; features: on an accumulator with feature channels, an (n, F) tensor"""
         n = xy.shape[0]
         assert tuple(xy.shape) == (n, 2) and tuple(rgb.shape) == (n, 3) and xy.dtype == self.ctx.torch.float32
         assert weights is None or tuple(weights.shape) == (n,)
         args = (self.h, _dp(xy) if n else None, _dp(rgb) if n else None, _dp(weights) if weights is not None and n else None, n)
+        if features is not None:
+            arr, fp = self._feature_args(features, layers if n else None, (n,), lambda t: tuple(t.shape) == (n, 3))
+            if layers is not None and not n:
+                arr = (_VP * max(1, self.layers))()
+            self._chk(lib().bcd_hip_accum_add_splatted_features(*args, arr, fp))
+            return
         if layers is None:
             self._chk(lib().bcd_hip_accum_add_splatted(*args))
             return
@@ -1534,6 +1590,20 @@ class Accumulator:
             means[k], covs[k] = _dp(m).value, _dp(c).value
         self._chk(lib().bcd_hip_accum_layer_statistics(self.h, means, covs))
         return out
+
+    def feature_statistics(self, out=None, variances=True):
+        """-> (features (H, W, F), variances (H, W, F) or None), fresh tensors or the pair of `out`: every channel's weighted mean over
+        the pixel's samples and the variance of that mean (bcd_hip_accum_feature_statistics); state unchanged.  They go into
+        Context.denoise_guided(..., features, variances=...) and similarity_masks_guide unchanged"""
+        torch = self.ctx.torch
+        if out is None:
+            mk = lambda: torch.empty((self.H, self.W, max(self.features, 1)), dtype=torch.float32, device="cuda:%d" % self.ctx.device)
+            out = (mk(), mk() if variances else None)
+        f, v = out
+        assert tuple(f.shape) == (self.H, self.W, f.shape[2]) and (v is None or tuple(v.shape) == tuple(f.shape))
+        assert f.shape[2] == self.features or self.features == 0, "one value per pixel and channel expected"
+        self._chk(lib().bcd_hip_accum_feature_statistics(self.h, _dp(f), _dp(v) if v is not None else None))
+        return f, v
 
     def moments(self, out=None):
         """-> (ns (H, W, 1), mean (H, W, 3), cov (H, W, 6)), fresh tensors or the three of `out`: statistics() without the histograms, bit for bit
@@ -1605,7 +1675,7 @@ class Accumulator:
 
     def merge(self, other):
         """adds other's state into this one, in stream order on both contexts (other may live on another context or device); the layer
-        planes too (both sides must have the same number of layers)"""
+        and the feature planes too (both sides must have the same number of layers and of feature channels)"""
         self._chk(lib().bcd_hip_accum_merge(self.h, other.h if other is not None else None))
 
     # ---- the layer block (bcd_hip_accum_export_layers / _import_layers / _merge_layers_state): a checkpoint of an accumulator with layers
@@ -1631,6 +1701,30 @@ class Accumulator:
         """adds a serialised layer block into the layers' planes (one fp32 add per element)"""
         a = _state_buffer(buf)
         self._chk(lib().bcd_hip_accum_merge_layers_state(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
+
+    # ---- the feature block (bcd_hip_accum_export_features / _import_features / _merge_features_state): a checkpoint of an accumulator with
+    # feature channels is export_state() plus export_features_state() (plus export_layers_state() if it has layers)
+    def features_state_bytes(self):
+        n = C.c_int64(0)
+        self._chk(lib().bcd_hip_accum_features_state_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def export_features_state(self):
+        """the serialised feature block (header + the feature planes) as a numpy uint8 array; synchronises, the state is unchanged"""
+        import numpy as np
+        out = np.empty(self.features_state_bytes(), np.uint8)
+        self._chk(lib().bcd_hip_accum_export_features(self.h, out.ctypes.data_as(_VP), out.size))
+        return out
+
+    def import_features_state(self, buf):
+        """replaces the feature planes with a serialised block of the same frame size and channel count"""
+        a = _state_buffer(buf)
+        self._chk(lib().bcd_hip_accum_import_features(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
+
+    def merge_features_state(self, buf):
+        """adds a serialised feature block into the feature planes (one fp32 add per element)"""
+        a = _state_buffer(buf)
+        self._chk(lib().bcd_hip_accum_merge_features_state(self.h, a.ctypes.data_as(_VP) if a.size else None, a.size))
 
     def info(self):
         """(samples accumulated, samples dropped) since create / the last reset; synchronises"""

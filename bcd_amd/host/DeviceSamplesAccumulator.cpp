@@ -2,6 +2,7 @@
 // addSample appends to a pinned host batch; a full batch (or a snapshot) copies it to the device and applies it through the
 // scattered add, which keeps every pixel's samples in call order.  While the device works on one batch the next one fills.
 // splatSample does the same with continuous positions through the splatted add; a batch holds calls of one kind only.
+// Layers' colours and feature channels ride in pinned arrays of their own beside the batch.
 #include "DeviceSamplesAccumulator.h"
 #include "bcd_hip.h"
 
@@ -30,7 +31,26 @@ namespace bcd
 			int i_device) :
 			m_width(i_width), m_height(i_height), m_nbOfBins(i_rHistogramParameters.m_nbOfBins), m_nbOfLayers(i_nbOfLayers)
 	{
-		if(i_nbOfLayers < 0 || i_nbOfLayers > BCD_HIP_ACCUM_MAX_LAYERS)
+		setUp(i_rHistogramParameters, i_device);
+	}
+
+	DeviceSamplesAccumulator::DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_nbOfLayers,
+			int i_nbOfFeatures, int i_device) :
+			m_width(i_width), m_height(i_height), m_nbOfBins(i_rHistogramParameters.m_nbOfBins), m_nbOfLayers(i_nbOfLayers), m_nbOfFeatures(i_nbOfFeatures)
+	{
+		if(i_nbOfFeatures < 1 || i_nbOfFeatures > BCD_HIP_ACCUM_MAX_FEATURES)
+		{
+			m_error = "the number of feature channels must be in [1, 8]";
+			m_nbOfFeatures = 0;
+			return;
+		}
+		setUp(i_rHistogramParameters, i_device);
+	}
+
+	void DeviceSamplesAccumulator::setUp(const HistogramParameters& i_rHistogramParameters, int i_device)
+	{
+		const int i_width = m_width, i_height = m_height;
+		if(m_nbOfLayers < 0 || m_nbOfLayers > BCD_HIP_ACCUM_MAX_LAYERS)
 		{
 			m_error = "the number of layers must be in [0, 15]";
 			m_nbOfLayers = 0;
@@ -51,12 +71,16 @@ namespace bcd
 		const size_t statsBytes = size_t(i_width) * size_t(i_height) * (10 + 3 * size_t(m_nbOfBins)) * sizeof(float);
 		const size_t layerBatchBytes = size_t(m_nbOfLayers) * size_t(s_batchCapacity) * 3 * sizeof(float);
 		const size_t layerStatsBytes = size_t(m_nbOfLayers) * size_t(i_width) * size_t(i_height) * 9 * sizeof(float);
+		const size_t featureBatchBytes = size_t(m_nbOfFeatures) * size_t(s_batchCapacity) * sizeof(float);
+		const size_t featureStatsBytes = size_t(m_nbOfFeatures) * size_t(i_width) * size_t(i_height) * 2 * sizeof(float);
 		if(hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess
 				|| hipHostMalloc((void**)&m_pHostPixel, size_t(s_batchCapacity) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess
 				|| hipHostMalloc((void**)&m_pHostRgbw, size_t(s_batchCapacity) * 4 * sizeof(float), hipHostMallocDefault) != hipSuccess
 				|| hipMalloc(&m_pDeviceBatch, batchBytes) != hipSuccess || hipMalloc(&m_pDeviceStats, statsBytes) != hipSuccess
 				|| (m_nbOfLayers > 0 && (hipHostMalloc((void**)&m_pHostLayerRgb, layerBatchBytes, hipHostMallocDefault) != hipSuccess
-						|| hipMalloc(&m_pDeviceLayerRgb, layerBatchBytes) != hipSuccess || hipMalloc(&m_pDeviceLayerStats, layerStatsBytes) != hipSuccess)))
+						|| hipMalloc(&m_pDeviceLayerRgb, layerBatchBytes) != hipSuccess || hipMalloc(&m_pDeviceLayerStats, layerStatsBytes) != hipSuccess))
+				|| (m_nbOfFeatures > 0 && (hipHostMalloc((void**)&m_pHostFeatures, featureBatchBytes, hipHostMallocDefault) != hipSuccess
+						|| hipMalloc(&m_pDeviceFeatures, featureBatchBytes) != hipSuccess || hipMalloc(&m_pDeviceFeatureStats, featureStatsBytes) != hipSuccess)))
 		{
 			m_batchCopied = ev;
 			m_error = "out of device or pinned host memory";
@@ -66,7 +90,9 @@ namespace bcd
 		m_batchCopied = ev;
 		if(bcd_hip_ctx_create(&m_pContext, i_device, m_stream) != BCD_HIP_OK)
 			m_error = "bcd_hip_ctx_create failed";
-		else if((m_nbOfLayers > 0 ? bcd_hip_accum_create_layers(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma,
+		else if((m_nbOfFeatures > 0 ? bcd_hip_accum_create_features(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma,
+						i_rHistogramParameters.m_maxValue, s_batchCapacity, m_nbOfLayers, m_nbOfFeatures, &m_pAccum)
+				: m_nbOfLayers > 0 ? bcd_hip_accum_create_layers(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma,
 						i_rHistogramParameters.m_maxValue, s_batchCapacity, m_nbOfLayers, &m_pAccum)
 				: bcd_hip_accum_create(m_pContext, i_width, i_height, m_nbOfBins, i_rHistogramParameters.m_gamma, i_rHistogramParameters.m_maxValue,
 						s_batchCapacity, &m_pAccum)) != BCD_HIP_OK)
@@ -88,6 +114,9 @@ namespace bcd
 		if(m_pDeviceLayerRgb) (void)hipFree(m_pDeviceLayerRgb);
 		if(m_pDeviceLayerStats) (void)hipFree(m_pDeviceLayerStats);
 		if(m_pHostLayerRgb) (void)hipHostFree(m_pHostLayerRgb);
+		if(m_pDeviceFeatures) (void)hipFree(m_pDeviceFeatures);
+		if(m_pDeviceFeatureStats) (void)hipFree(m_pDeviceFeatureStats);
+		if(m_pHostFeatures) (void)hipHostFree(m_pHostFeatures);
 		if(m_pHostPixel) (void)hipHostFree(m_pHostPixel);
 		if(m_pHostRgbw) (void)hipHostFree(m_pHostRgbw);
 		if(m_pHostXy) (void)hipHostFree(m_pHostXy);
@@ -101,9 +130,21 @@ namespace bcd
 		m_error = std::string(i_pWhat) + ": " + (m_pContext ? bcd_hip_last_error(m_pContext) : "no context");
 	}
 
+	bool DeviceSamplesAccumulator::refusedForFeatures(const char* i_pCall, bool i_withFeatures, const float* i_pFeatures, const float* const* i_ppLayerRgb) const
+	{
+		const char* why = nullptr;
+		if(!i_withFeatures)
+			why = m_nbOfFeatures > 0 ? ": an accumulator with feature channels takes the batch form with the samples' features" : nullptr;
+		else if(m_nbOfFeatures == 0) why = ": the accumulator has no feature channels";
+		else if(!i_pFeatures) why = ": null features";
+		else if((i_ppLayerRgb != nullptr) != (m_nbOfLayers > 0)) why = m_nbOfLayers > 0 ? ": null layer colours" : ": layer colours on an accumulator without layers";
+		if(why) m_error = std::string(i_pCall) + why;
+		return why != nullptr;
+	}
+
 	void DeviceSamplesAccumulator::addSample(int i_line, int i_column, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight)
 	{
-		if(!isValid())
+		if(refusedForFeatures("addSample", false, nullptr, nullptr) || !isValid())
 			return;
 		if(m_nbOfLayers > 0)
 		{
@@ -123,32 +164,40 @@ namespace bcd
 
 	void DeviceSamplesAccumulator::addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* i_pWeights, int64_t i_nbOfSamples)
 	{
-		if(!isValid())
+		if(refusedForFeatures("addSamples", false, nullptr, nullptr) || !isValid())
 			return;
 		if(m_nbOfLayers > 0)
 		{
 			m_error = "addSamples: an accumulator with layers takes the layers' colours too";
 			return;
 		}
-		appendBatch(false, i_pPixelIndices, i_pRgb, nullptr, i_pWeights, i_nbOfSamples);
+		appendBatch(false, i_pPixelIndices, i_pRgb, nullptr, nullptr, i_pWeights, i_nbOfSamples);
 	}
 
 	void DeviceSamplesAccumulator::addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights,
 			int64_t i_nbOfSamples)
 	{
-		if(!isValid())
+		if(refusedForFeatures("addSamples", false, nullptr, nullptr) || !isValid())
 			return;
 		if(m_nbOfLayers == 0 || !i_ppLayerRgb)
 		{
 			m_error = m_nbOfLayers == 0 ? "addSamples: the accumulator has no layers" : "addSamples: null layer colours";
 			return;
 		}
-		appendBatch(false, i_pPixelIndices, i_pRgb, i_ppLayerRgb, i_pWeights, i_nbOfSamples);
+		appendBatch(false, i_pPixelIndices, i_pRgb, i_ppLayerRgb, nullptr, i_pWeights, i_nbOfSamples);
+	}
+
+	void DeviceSamplesAccumulator::addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pFeatures,
+			const float* i_pWeights, int64_t i_nbOfSamples)
+	{
+		if(refusedForFeatures("addSamples", true, i_pFeatures, i_ppLayerRgb) || !isValid())
+			return;
+		appendBatch(false, i_pPixelIndices, i_pRgb, i_ppLayerRgb, i_pFeatures, i_pWeights, i_nbOfSamples);
 	}
 
 	// n samples into the pending batch (i_pKeys: pixel indices, or positions for splats), flushed whenever it is full
 	void DeviceSamplesAccumulator::appendBatch(bool i_splat, const void* i_pKeys, const float* i_pRgb, const float* const* i_ppLayerRgb,
-			const float* i_pWeights, int64_t i_nbOfSamples)
+			const float* i_pFeatures, const float* i_pWeights, int64_t i_nbOfSamples)
 	{
 		for(int l = 0; i_ppLayerRgb && l < m_nbOfLayers; ++l)
 			if(!i_ppLayerRgb[l])
@@ -166,6 +215,8 @@ namespace bcd
 			std::memcpy(m_pHostRgbw + 3 * m_pending, i_pRgb + 3 * done, size_t(n) * 3 * sizeof(float));
 			for(int l = 0; i_ppLayerRgb && l < m_nbOfLayers; ++l)
 				std::memcpy(m_pHostLayerRgb + 3 * (size_t(l) * s_batchCapacity + m_pending), i_ppLayerRgb[l] + 3 * done, size_t(n) * 3 * sizeof(float));
+			if(i_pFeatures)
+				std::memcpy(m_pHostFeatures + size_t(m_nbOfFeatures) * m_pending, i_pFeatures + size_t(m_nbOfFeatures) * done, size_t(n) * m_nbOfFeatures * sizeof(float));
 			float* w = m_pHostRgbw + 3 * s_batchCapacity + m_pending;
 			if(i_pWeights) std::memcpy(w, i_pWeights + done, size_t(n) * sizeof(float));
 			else std::fill(w, w + n, 1.f);
@@ -227,7 +278,7 @@ namespace bcd
 
 	void DeviceSamplesAccumulator::splatSample(float i_x, float i_y, float i_sampleR, float i_sampleG, float i_sampleB, float i_weight)
 	{
-		if(!isValid())
+		if(refusedForFeatures("splatSample", false, nullptr, nullptr) || !isValid())
 			return;
 		if(m_nbOfLayers > 0)
 		{
@@ -259,12 +310,14 @@ namespace bcd
 			m_error = "splatSamples: no filter (setFilter)";
 			return;
 		}
+		if(refusedForFeatures("splatSamples", false, nullptr, nullptr))
+			return;
 		if(m_nbOfLayers > 0)
 		{
 			m_error = "splatSamples: an accumulator with layers takes the layers' colours too";
 			return;
 		}
-		appendBatch(true, i_pPositions, i_pRgb, nullptr, i_pWeights, i_nbOfSamples);
+		appendBatch(true, i_pPositions, i_pRgb, nullptr, nullptr, i_pWeights, i_nbOfSamples);
 	}
 
 	void DeviceSamplesAccumulator::splatSamples(const float* i_pPositions, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights,
@@ -277,12 +330,27 @@ namespace bcd
 			m_error = "splatSamples: no filter (setFilter)";
 			return;
 		}
+		if(refusedForFeatures("splatSamples", false, nullptr, nullptr))
+			return;
 		if(m_nbOfLayers == 0 || !i_ppLayerRgb)
 		{
 			m_error = m_nbOfLayers == 0 ? "splatSamples: the accumulator has no layers" : "splatSamples: null layer colours";
 			return;
 		}
-		appendBatch(true, i_pPositions, i_pRgb, i_ppLayerRgb, i_pWeights, i_nbOfSamples);
+		appendBatch(true, i_pPositions, i_pRgb, i_ppLayerRgb, nullptr, i_pWeights, i_nbOfSamples);
+	}
+
+	void DeviceSamplesAccumulator::splatSamples(const float* i_pPositions, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pFeatures,
+			const float* i_pWeights, int64_t i_nbOfSamples)
+	{
+		if(refusedForFeatures("splatSamples", true, i_pFeatures, i_ppLayerRgb) || !isValid())
+			return;
+		if(!m_hasFilter)
+		{
+			m_error = "splatSamples: no filter (setFilter)";
+			return;
+		}
+		appendBatch(true, i_pPositions, i_pRgb, i_ppLayerRgb, i_pFeatures, i_pWeights, i_nbOfSamples);
 	}
 
 	bool DeviceSamplesAccumulator::flush() const
@@ -308,6 +376,8 @@ namespace bcd
 			dLayers[l] = d;
 			ok = hipMemcpyAsync(d, m_pHostLayerRgb + 3 * size_t(l) * cap, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
 		}
+		if(ok && m_nbOfFeatures > 0) // (and the feature channels)
+			ok = hipMemcpyAsync(m_pDeviceFeatures, m_pHostFeatures, size_t(n) * m_nbOfFeatures * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
 		if(!ok || hipEventRecord((hipEvent_t)m_batchCopied, st) != hipSuccess)
 		{
 			m_error = "batch upload failed";
@@ -315,6 +385,18 @@ namespace bcd
 		}
 		m_copyInFlight = true;
 		m_pending = 0;
+		if(m_nbOfFeatures > 0)
+		{
+			const float* const* layers = m_nbOfLayers > 0 ? dLayers : nullptr;
+			const int rc = m_pendingSplats ? bcd_hip_accum_add_splatted_features(m_pAccum, (const float*)m_pDeviceXy, dRgb, dW, n, layers, (const float*)m_pDeviceFeatures)
+					: bcd_hip_accum_add_scattered_features(m_pAccum, dPix, dRgb, dW, n, layers, (const float*)m_pDeviceFeatures);
+			if(rc != BCD_HIP_OK)
+			{
+				fail(m_pendingSplats ? "bcd_hip_accum_add_splatted_features" : "bcd_hip_accum_add_scattered_features");
+				return false;
+			}
+			return true;
+		}
 		if(m_nbOfLayers > 0)
 		{
 			const int rc = m_pendingSplats ? bcd_hip_accum_add_splatted_layers(m_pAccum, (const float*)m_pDeviceXy, dRgb, dW, n, dLayers)
@@ -437,6 +519,51 @@ namespace bcd
 		return true;
 	}
 
+	DeviceSamplesAccumulator::DeviceFeatureStatistics DeviceSamplesAccumulator::computeDeviceFeatureStatistics() const
+	{
+		DeviceFeatureStatistics s;
+		if(!isValid() || m_nbOfFeatures == 0)
+			return s;
+		flush();
+		float* p = (float*)m_pDeviceFeatureStats;
+		const size_t n = size_t(m_width) * size_t(m_height) * size_t(m_nbOfFeatures);
+		if(bcd_hip_accum_feature_statistics(m_pAccum, p, p + n) != BCD_HIP_OK)
+		{
+			fail("bcd_hip_accum_feature_statistics");
+			return s;
+		}
+		s.m_pFeatures = p;
+		s.m_pVariances = p + n;
+		s.m_nbOfChannels = m_nbOfFeatures;
+		return s;
+	}
+
+	bool DeviceSamplesAccumulator::getFeatureStatistics(Deepimf& o_rMean, Deepimf& o_rVarianceOfMean) const
+	{
+		if(!isValid())
+			return false;
+		if(m_nbOfFeatures == 0)
+		{
+			m_error = "getFeatureStatistics: the accumulator has no feature channels";
+			return false;
+		}
+		const DeviceFeatureStatistics d = computeDeviceFeatureStatistics();
+		if(!d.m_pFeatures)
+			return false;
+		o_rMean.resize(m_width, m_height, m_nbOfFeatures);
+		o_rVarianceOfMean.resize(m_width, m_height, m_nbOfFeatures);
+		const size_t bytes = size_t(m_width) * size_t(m_height) * size_t(m_nbOfFeatures) * sizeof(float);
+		hipStream_t st = (hipStream_t)m_stream;
+		if(hipMemcpyAsync(o_rMean.getDataPtr(), d.m_pFeatures, bytes, hipMemcpyDeviceToHost, st) != hipSuccess
+				|| hipMemcpyAsync(o_rVarianceOfMean.getDataPtr(), d.m_pVariances, bytes, hipMemcpyDeviceToHost, st) != hipSuccess
+				|| hipStreamSynchronize(st) != hipSuccess)
+		{
+			m_error = "feature statistics download failed";
+			return false;
+		}
+		return true;
+	}
+
 	SamplesStatisticsImages DeviceSamplesAccumulator::extractSamplesStatistics()
 	{
 		SamplesStatisticsImages out = getSamplesStatistics();
@@ -535,32 +662,48 @@ namespace bcd
 
 	bool DeviceSamplesAccumulator::saveState(const std::string& i_rPath) const
 	{
-		return toFile(i_rPath, false);
+		return toFile(i_rPath, BLOCK_STATE);
 	}
 
 	bool DeviceSamplesAccumulator::saveLayers(const std::string& i_rPath) const
 	{
-		return toFile(i_rPath, true);
+		return toFile(i_rPath, BLOCK_LAYERS);
 	}
 
 	bool DeviceSamplesAccumulator::loadLayers(const std::string& i_rPath)
 	{
-		return fromFile(i_rPath, false, true);
+		return fromFile(i_rPath, false, BLOCK_LAYERS);
 	}
 
 	bool DeviceSamplesAccumulator::mergeLayers(const std::string& i_rPath)
 	{
-		return fromFile(i_rPath, true, true);
+		return fromFile(i_rPath, true, BLOCK_LAYERS);
 	}
 
-	bool DeviceSamplesAccumulator::toFile(const std::string& i_rPath, bool i_layers) const
+	bool DeviceSamplesAccumulator::saveFeatures(const std::string& i_rPath) const
+	{
+		return toFile(i_rPath, BLOCK_FEATURES);
+	}
+
+	bool DeviceSamplesAccumulator::loadFeatures(const std::string& i_rPath)
+	{
+		return fromFile(i_rPath, false, BLOCK_FEATURES);
+	}
+
+	bool DeviceSamplesAccumulator::mergeFeatures(const std::string& i_rPath)
+	{
+		return fromFile(i_rPath, true, BLOCK_FEATURES);
+	}
+
+	bool DeviceSamplesAccumulator::toFile(const std::string& i_rPath, Block i_block) const
 	{
 		if(!isValid() || !flush())
 			return false;
 		int64_t bytes = 0;
-		if((i_layers ? bcd_hip_accum_layers_state_bytes(m_pAccum, &bytes) : bcd_hip_accum_state_bytes(m_pAccum, &bytes)) != BCD_HIP_OK)
+		if((i_block == BLOCK_FEATURES ? bcd_hip_accum_features_state_bytes(m_pAccum, &bytes)
+				: i_block == BLOCK_LAYERS ? bcd_hip_accum_layers_state_bytes(m_pAccum, &bytes) : bcd_hip_accum_state_bytes(m_pAccum, &bytes)) != BCD_HIP_OK)
 		{
-			fail(i_layers ? "bcd_hip_accum_layers_state_bytes" : "bcd_hip_accum_state_bytes");
+			fail(i_block == BLOCK_FEATURES ? "bcd_hip_accum_features_state_bytes" : i_block == BLOCK_LAYERS ? "bcd_hip_accum_layers_state_bytes" : "bcd_hip_accum_state_bytes");
 			return false;
 		}
 		const int fd = open(i_rPath.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
@@ -579,20 +722,22 @@ namespace bcd
 			unlink(i_rPath.c_str());
 			return false;
 		}
-		const int rc = i_layers ? bcd_hip_accum_export_layers(m_pAccum, p, bytes) : bcd_hip_accum_export(m_pAccum, p, bytes);
+		const int rc = i_block == BLOCK_FEATURES ? bcd_hip_accum_export_features(m_pAccum, p, bytes)
+				: i_block == BLOCK_LAYERS ? bcd_hip_accum_export_layers(m_pAccum, p, bytes) : bcd_hip_accum_export(m_pAccum, p, bytes);
 		munmap(p, size_t(bytes));
 		if(rc != BCD_HIP_OK)
 		{
-			fail(i_layers ? "bcd_hip_accum_export_layers" : "bcd_hip_accum_export");
+			fail(i_block == BLOCK_FEATURES ? "bcd_hip_accum_export_features" : i_block == BLOCK_LAYERS ? "bcd_hip_accum_export_layers" : "bcd_hip_accum_export");
 			unlink(i_rPath.c_str());
 			return false;
 		}
 		return true;
 	}
 
-	bool DeviceSamplesAccumulator::fromFile(const std::string& i_rPath, bool i_merge, bool i_layers)
+	bool DeviceSamplesAccumulator::fromFile(const std::string& i_rPath, bool i_merge, Block i_block)
 	{
-		const char* what = i_layers ? (i_merge ? "mergeLayers" : "loadLayers") : (i_merge ? "mergeState" : "loadState");
+		const char* what = i_block == BLOCK_FEATURES ? (i_merge ? "mergeFeatures" : "loadFeatures")
+				: i_block == BLOCK_LAYERS ? (i_merge ? "mergeLayers" : "loadLayers") : (i_merge ? "mergeState" : "loadState");
 		if(!isValid() || !flush())
 			return false;
 		const int fd = open(i_rPath.c_str(), O_RDONLY);
@@ -618,7 +763,9 @@ namespace bcd
 		}
 		(void)madvise(p, bytes, MADV_SEQUENTIAL);
 		// both calls return once the mapping is no longer needed
-		const int rc = i_layers ? (i_merge ? bcd_hip_accum_merge_layers_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import_layers(m_pAccum, p, int64_t(bytes)))
+		const int rc = i_block == BLOCK_FEATURES
+				? (i_merge ? bcd_hip_accum_merge_features_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import_features(m_pAccum, p, int64_t(bytes)))
+				: i_block == BLOCK_LAYERS ? (i_merge ? bcd_hip_accum_merge_layers_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import_layers(m_pAccum, p, int64_t(bytes)))
 				: (i_merge ? bcd_hip_accum_merge_state(m_pAccum, p, int64_t(bytes)) : bcd_hip_accum_import(m_pAccum, p, int64_t(bytes)));
 		munmap(p, bytes);
 		if(rc != BCD_HIP_OK)

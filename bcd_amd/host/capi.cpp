@@ -223,6 +223,119 @@ int bcdcore_device_accumulate_layers(const float* s, long long n, const float* l
 	return 0;
 }
 
+// mixed calls through the batch forms of a bcd::DeviceSamplesAccumulator with `nbFeatures` feature channels and `nbLayers` (0: none) colour
+// layers: s, layerRgb, batch and the filter as for bcdcore_device_accumulate_layers, features [n][nbFeatures] the feature channels of the same
+// calls.  statePath / layersPath / featuresPath (all or none; layersPath is not used without layers): the blocks are saved at the end and
+// loaded into a second accumulator, whose statistics are the ones returned; mergeAgain: the same files are then merged into it once more
+// (every running sum doubles).  fmean, fvar [H][W][nbFeatures]; lmean, lcov as there; counts[2]: samples accumulated / dropped
+int bcdcore_device_accumulate_features(const float* s, long long n, const float* layerRgb, int nbLayers, const float* features, int nbFeatures, int W,
+		int H, int nbins, float gamma, float maxval, int device, float radiusX, float radiusY, int tableSize, const float* table, long long batch,
+		const char* statePath, const char* layersPath, const char* featuresPath, int mergeAgain, float* ns, float* mean, float* cov, float* hist,
+		float* lmean, float* lcov, float* fmean, float* fvar, long long* counts)
+{
+	HistogramParameters hp;
+	hp.m_nbOfBins = nbins; hp.m_gamma = gamma; hp.m_maxValue = maxval;
+	g_deviceAccumulateError.clear();
+	DeviceSamplesAccumulator first(W, H, hp, nbLayers, nbFeatures, device);
+	if(!first.isValid() || first.nbOfLayers() != nbLayers || first.nbOfFeatures() != nbFeatures) { g_deviceAccumulateError = first.lastError(); return -1; }
+	if(table && !first.setFilter(radiusX, radiusY, tableSize, table)) { g_deviceAccumulateError = first.lastError(); return -1; }
+	std::vector<int32_t> pixels;
+	std::vector<float> keys, rgb, weights;
+	std::vector<const float*> layerPointers((size_t)nbLayers);
+	if(batch < 1) batch = n > 0 ? n : 1;
+	for(long long i = 0; i < n; )
+	{
+		const bool splat = s[7 * i] != 0.f;
+		long long e = i + 1;
+		while(e < n && e - i < batch && (s[7 * e] != 0.f) == splat) ++e;
+		const size_t m = size_t(e - i);
+		pixels.resize(m); keys.resize(2 * m); rgb.resize(3 * m); weights.resize(m);
+		for(size_t j = 0; j < m; ++j)
+		{
+			const float* p = s + 7 * (i + (long long)j);
+			const int line = int(p[1]), col = int(p[2]);
+			pixels[j] = (line < 0 || line >= H || col < 0 || col >= W) ? -1 : line * W + col;
+			keys[2 * j] = p[1]; keys[2 * j + 1] = p[2];
+			rgb[3 * j] = p[3]; rgb[3 * j + 1] = p[4]; rgb[3 * j + 2] = p[5];
+			weights[j] = p[6];
+		}
+		for(int l = 0; l < nbLayers; ++l)
+			layerPointers[(size_t)l] = layerRgb + 3 * ((long long)l * n + i);
+		const float* const* layers = nbLayers > 0 ? layerPointers.data() : nullptr;
+		if(splat) first.splatSamples(keys.data(), rgb.data(), layers, features + (long long)nbFeatures * i, weights.data(), (int64_t)m);
+		else first.addSamples(pixels.data(), rgb.data(), layers, features + (long long)nbFeatures * i, weights.data(), (int64_t)m);
+		i = e;
+	}
+	std::unique_ptr<DeviceSamplesAccumulator> second;
+	DeviceSamplesAccumulator* acc = &first;
+	if(statePath && featuresPath)
+	{
+		if(!first.saveState(statePath) || !first.saveFeatures(featuresPath) || (nbLayers > 0 && !first.saveLayers(layersPath)))
+		{
+			g_deviceAccumulateError = first.lastError();
+			return -1;
+		}
+		second.reset(new DeviceSamplesAccumulator(W, H, hp, nbLayers, nbFeatures, device));
+		if(!second->isValid() || !second->loadState(statePath) || !second->loadFeatures(featuresPath) || (nbLayers > 0 && !second->loadLayers(layersPath))
+				|| (mergeAgain && (!second->mergeState(statePath) || !second->mergeFeatures(featuresPath) || (nbLayers > 0 && !second->mergeLayers(layersPath)))))
+		{
+			g_deviceAccumulateError = second->lastError();
+			return -1;
+		}
+		acc = second.get();
+	}
+	counts[0] = acc->nbOfAccumulatedSamples();
+	counts[1] = acc->nbOfDroppedSamples();
+	for(int l = 0; l < nbLayers; ++l)
+	{
+		Deepimf m, c;
+		if(!acc->getLayerStatistics(l, m, c)) { g_deviceAccumulateError = acc->lastError(); return -1; }
+		m.copyDataTo(lmean + (size_t)l * W * H * 3);
+		c.copyDataTo(lcov + (size_t)l * W * H * 6);
+	}
+	Deepimf fm, fv;
+	if(!acc->getFeatureStatistics(fm, fv)) { g_deviceAccumulateError = acc->lastError(); return -1; }
+	const DeviceSamplesAccumulator::DeviceFeatureStatistics d = acc->computeDeviceFeatureStatistics();
+	if(!d.m_pFeatures || !d.m_pVariances || d.m_nbOfChannels != nbFeatures) { g_deviceAccumulateError = acc->lastError(); return -1; }
+	fm.copyDataTo(fmean);
+	fv.copyDataTo(fvar);
+	SamplesStatisticsImages st = acc->getSamplesStatistics();
+	if(!acc->lastError().empty()) { g_deviceAccumulateError = acc->lastError(); return -1; }
+	st.m_nbOfSamplesImage.copyDataTo(ns);
+	st.m_meanImage.copyDataTo(mean);
+	st.m_covarImage.copyDataTo(cov);
+	st.m_histoImage.copyDataTo(hist);
+	return 0;
+}
+
+// the refusals of a bcd::DeviceSamplesAccumulator(8 x 8, nbLayers, nbFeatures) that need no device: `messages` receives, one per line,
+// lastError() after the constructor, after addSample, splatSample, the batch addSamples without features, addSamples with null features and
+// splatSamples with null features.  Returns isValid() after the constructor
+int bcdcore_device_features_refusals(int nbLayers, int nbFeatures, int device, char* messages, int capacity)
+{
+	HistogramParameters hp;
+	DeviceSamplesAccumulator acc(8, 8, hp, nbLayers, nbFeatures, device);
+	const int valid = acc.isValid() ? 1 : 0;
+	std::string out = acc.lastError() + "\n";
+	const float one[3] = { 1.f, 1.f, 1.f }, xy[2] = { 1.f, 1.f };
+	const std::vector<const float*> layerColours(16, one);
+	const float* const* layers = layerColours.data();
+	const int32_t zero = 0;
+	acc.addSample(0, 0, 1.f, 1.f, 1.f);
+	out += acc.lastError() + "\n";
+	acc.splatSample(1.f, 1.f, 1.f, 1.f, 1.f);
+	out += acc.lastError() + "\n";
+	acc.addSamples(&zero, one, nullptr, 1);
+	out += acc.lastError() + "\n";
+	acc.addSamples(&zero, one, nbLayers > 0 ? layers : nullptr, nullptr, nullptr, 1);
+	out += acc.lastError() + "\n";
+	acc.splatSamples(xy, one, nbLayers > 0 ? layers : nullptr, nullptr, nullptr, 1);
+	out += acc.lastError() + "\n";
+	if(valid && acc.nbOfAccumulatedSamples() != 0) out += "a refused add was applied\n";
+	std::snprintf(messages, size_t(capacity), "%s", out.c_str());
+	return valid;
+}
+
 // the same stream through bcd::DeviceSamplesAccumulator::addSample (no explicit flush), then one planSamples; pixels[budget] receives the
 // list, summary[4] planned / active / unsampled / max_error.  invalidFirst: two invalid planSamples come first (a budget of 2^31 while the
 // samples are still buffered, then max_per_pixel 0), and each must return false with a message.  Returns the number of planned samples,

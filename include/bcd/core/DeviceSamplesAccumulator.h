@@ -7,6 +7,9 @@
 // bcd_hip_accum_*_layers entry points of bcd_hip.h, which define them exactly).  Such an accumulator is fed through the batch forms of
 // addSamples / splatSamples that take the layers' colour arrays; the single-sample addSample / splatSample have no form with layers and
 // are refused on it (message in lastError()), as are the batch forms without layers.
+// Feature channels: an accumulator constructed with a feature count keeps two more running sums per channel (the bcd_hip_accum_*_features
+// entry points of bcd_hip.h, which define them exactly) and snapshots them into the feature and variance images of a bcd_hip_guide.  It is
+// fed through the batch forms of addSamples / splatSamples that take the samples' feature channels; every other add is refused on it.
 #ifndef DEVICE_SAMPLES_ACCUMULATOR_H
 #define DEVICE_SAMPLES_ACCUMULATOR_H
 
@@ -61,10 +64,24 @@ namespace bcd
 			const float* m_pCovariances = nullptr;
 		};
 
+		/// the feature statistics on the device, owned by the accumulator and valid until the next feature snapshot or destruction: the
+		/// features and variances of a bcd_hip_guide with nb_channels = m_nbOfChannels, width * height * m_nbOfChannels floats each
+		struct DeviceFeatureStatistics
+		{
+			const float* m_pFeatures = nullptr;  ///< every channel's weighted mean over the pixel's samples
+			const float* m_pVariances = nullptr; ///< the variance of that mean
+			int m_nbOfChannels = 0;
+		};
+
 		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_device = 0);
 		/// with i_nbOfLayers extra colour layers, in [1, 15] (otherwise the accumulator is not valid)
 		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_nbOfLayers, int i_device);
+		/// with i_nbOfLayers extra colour layers, in [0, 15], and i_nbOfFeatures auxiliary feature channels, in [1, 8] (otherwise the
+		/// accumulator is not valid)
+		DeviceSamplesAccumulator(int i_width, int i_height, const HistogramParameters& i_rHistogramParameters, int i_nbOfLayers, int i_nbOfFeatures,
+				int i_device);
 		int nbOfLayers() const { return m_nbOfLayers; }
+		int nbOfFeatures() const { return m_nbOfFeatures; }
 		~DeviceSamplesAccumulator();
 		DeviceSamplesAccumulator(const DeviceSamplesAccumulator&) = delete;
 		DeviceSamplesAccumulator& operator=(const DeviceSamplesAccumulator&) = delete;
@@ -80,6 +97,11 @@ namespace bcd
 
 		/// the same with the layers' colours: i_ppLayerRgb[nbOfLayers()], each [n][3], same pixels, weights and order as the beauty's
 		void addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights, int64_t i_nbOfSamples);
+
+		/// the same with the samples' feature channels, on an accumulator with features: i_pFeatures [n][nbOfFeatures()]; i_ppLayerRgb is
+		/// nullptr exactly when the accumulator has no layers
+		void addSamples(const int32_t* i_pPixelIndices, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pFeatures, const float* i_pWeights,
+				int64_t i_nbOfSamples);
 
 		/// Pixel reconstruction filter of splatSample / splatSamples (bcd_hip_accum_set_filter in bcd_hip.h, which defines the splat exactly):
 		/// radii in (0, 3], a table of i_tableSize x i_tableSize finite values >= 0 (row = y index), i_tableSize in [1, 64]; a null table
@@ -98,6 +120,10 @@ namespace bcd
 		/// the same with the layers' colours: i_ppLayerRgb[nbOfLayers()], each [n][3]
 		void splatSamples(const float* i_pPositions, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights, int64_t i_nbOfSamples);
 
+		/// the same with the samples' feature channels: i_pFeatures [n][nbOfFeatures()]; i_ppLayerRgb is nullptr exactly without layers
+		void splatSamples(const float* i_pPositions, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pFeatures, const float* i_pWeights,
+				int64_t i_nbOfSamples);
+
 		/// copy of the statistics accumulated so far (the accumulator goes on)
 		SamplesStatisticsImages getSamplesStatistics() const;
 		/// moves the statistics out; the accumulator must not be used afterwards
@@ -110,6 +136,12 @@ namespace bcd
 		std::vector<DeviceLayerStatistics> computeDeviceLayerStatistics() const;
 		/// host copy of layer i_layer's mean (depth 3) and covariance (depth 6) images; synchronises
 		bool getLayerStatistics(int i_layer, Deepimf& o_rMean, Deepimf& o_rCovariances) const;
+
+		/// enqueues a snapshot of the feature channels into device buffers owned by the accumulator (no host copy, no synchronisation);
+		/// null pointers on failure or without features
+		DeviceFeatureStatistics computeDeviceFeatureStatistics() const;
+		/// host copy of the feature means and of the variances of those means (depth nbOfFeatures() each); synchronises
+		bool getFeatureStatistics(Deepimf& o_rMean, Deepimf& o_rVarianceOfMean) const;
 
 		/// where the next i_budget samples go: o_pixelIndices receives the planned pixel indices (line * width + column) in ascending order,
 		/// each pixel repeated as many times as it gets samples.  The samples buffered by addSample are applied first; the statistics are
@@ -138,6 +170,12 @@ namespace bcd
 		bool loadLayers(const std::string& i_rPath);
 		bool mergeLayers(const std::string& i_rPath);
 
+		/// The feature block (bcd_hip_accum_export_features / _import_features / _merge_features_state in bcd_hip.h): the feature channels'
+		/// running sums, a file of its own.  A checkpoint of an accumulator with features is saveState plus saveFeatures (plus saveLayers).
+		bool saveFeatures(const std::string& i_rPath) const;
+		bool loadFeatures(const std::string& i_rPath);
+		bool mergeFeatures(const std::string& i_rPath);
+
 		/// back to an empty accumulator (the frame geometry and the device buffers are kept)
 		void reset();
 		/// samples accumulated / skipped since construction or the last reset (synchronises)
@@ -149,9 +187,15 @@ namespace bcd
 		bool flush() const;
 		void fail(const char* i_pWhat) const;
 		/// loadState / mergeState: the mapped file through bcd_hip_accum_import (merge = false) or _merge_state
-		bool fromFile(const std::string& i_rPath, bool i_merge, bool i_layers = false);
-		bool toFile(const std::string& i_rPath, bool i_layers) const;
-		void appendBatch(bool i_splat, const void* i_pKeys, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pWeights, int64_t i_nbOfSamples);
+		enum Block { BLOCK_STATE = 0, BLOCK_LAYERS = 1, BLOCK_FEATURES = 2 };
+		bool fromFile(const std::string& i_rPath, bool i_merge, Block i_block = BLOCK_STATE);
+		bool toFile(const std::string& i_rPath, Block i_block) const;
+		void appendBatch(bool i_splat, const void* i_pKeys, const float* i_pRgb, const float* const* i_ppLayerRgb, const float* i_pFeatures,
+				const float* i_pWeights, int64_t i_nbOfSamples);
+		void setUp(const HistogramParameters& i_rHistogramParameters, int i_device);
+		/// the refusals of the forms without features on an accumulator with features, and of the batch forms with them elsewhere (decided
+		/// from the arguments and the counts alone, before the device is looked at)
+		bool refusedForFeatures(const char* i_pCall, bool i_withFeatures, const float* i_pFeatures, const float* const* i_ppLayerRgb) const;
 
 	private:
 		int m_width, m_height, m_nbOfBins;
@@ -159,6 +203,10 @@ namespace bcd
 		float* m_pHostLayerRgb = nullptr;    // the layers' colours of the pending batch [layer][capacity][3] (pinned), and their device copy
 		void* m_pDeviceLayerRgb = nullptr;
 		void* m_pDeviceLayerStats = nullptr; // per layer mean | cov of computeDeviceLayerStatistics
+		int m_nbOfFeatures = 0;
+		float* m_pHostFeatures = nullptr;    // the feature channels of the pending batch [capacity][nbOfFeatures] (pinned), and their device copy
+		void* m_pDeviceFeatures = nullptr;
+		void* m_pDeviceFeatureStats = nullptr; // features | variances of computeDeviceFeatureStatistics
 		bcd_hip_ctx* m_pContext = nullptr;
 		bcd_hip_accum* m_pAccum = nullptr;
 		bool m_isValid = true;

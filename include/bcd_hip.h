@@ -1148,6 +1148,77 @@ int  bcd_hip_accum_layers_state_bytes(bcd_hip_accum *acc, int64_t *bytes);
 int  bcd_hip_accum_export_layers(bcd_hip_accum *acc, void *h_layers, int64_t capacity);
 int  bcd_hip_accum_import_layers(bcd_hip_accum *acc, const void *h_layers, int64_t bytes);
 int  bcd_hip_accum_merge_layers_state(bcd_hip_accum *acc, const void *h_layers, int64_t bytes);
+/* Auxiliary feature channels beside the beauty ("Features"): an accumulator created with nb_features = F channels
+ * (albedo, normal, depth, object id ...) keeps, per channel k, two more running sums -- s1_k = sum w x_k and s2_k = sum w x_k x_k, 8 bytes per
+ * pixel and channel -- in a buffer of its own, plane-major, channel after channel (s1_0, s2_0, s1_1, ...).  Its snapshot is the pair of
+ * images of a bcd_hip_guide: the weighted mean of every channel and the variance of that mean, W*H*F floats each, pixel-interleaved, so
+ * that samples go in and bcd_hip_denoise_guided comes out without leaving the device.  The weight sum and the squared-weight sum are the
+ * beauty's.  The shared state, the layers, their formats and every entry point above behave as on an accumulator without features,
+ * except that the plain and the _layers adds are refused.
+ *   Rule: every add takes the samples' feature channels beside the beauty's colours.  Each pixel is owned by one thread and receives its
+ *     contributions in stream order with the beauty's weight (for splats w * f, one multiplication), float32, no contraction, no float
+ *     atomics:   s1_k += w * x_k;   s2_k += (w * x_k) * x_k;   the operations of addSample on the first colour channel.
+ *   Snapshot, per pixel and channel, from the beauty's wsum and w2sum:
+ *         inv = 1.f / wsum;   mean = inv * s1;   cv = s2 * inv;   cv -= mean * mean;
+ *         r = w2sum / (wsum * wsum);   bias = 1.f / (1 - r);   v = cv * bias;   vm = v * r;   variance = (vm > 0.f) ? vm : 0.f;
+ *     mean and v have the bits of mean[0] and cov[0] of a SamplesAccumulator (the host class, bcd_hip_accum_*) fed the same stream with
+ *     R = x_k.  vm is the variance of the weighted mean (unit weights: v / n), the `variances` of bcd_hip_guide.  The clamp stores +0 for
+ *     whatever is not a positive number -- negative round-off, NaN, a zero of either sign: an infinite depth gives mean = inf and
+ *     variance 0 (inf against inf is a skipped NaN term of the guide distance, inf against finite a counted infinite one); a pixel with
+ *     one sample gives its value and 0 * inf = NaN -> 0; a pixel without samples gives mean NaN and variance 0.  s2 / n - mean^2
+ *     cancels in float32: a channel of magnitude M resolves variances down to about 1e-7 M^2, so normalise depth (and any channel of
+ *     large magnitude) to order 1 before accumulating it.
+ *   create_features: nb_layers in [0, BCD_HIP_ACCUM_MAX_LAYERS], nb_features in [1, BCD_HIP_ACCUM_MAX_FEATURES], otherwise EINVAL;
+ *           everything else is create / create_layers.  With max_batch_samples > 0 no later add allocates (the feature kernels read the
+ *           caller's buffers and need no scratch).  nb_features: 0 for an accumulator made by create or create_layers.
+ *   add_dense_features / add_scattered_features / add_splatted_features: the arguments of the _layers form, then d_features: a DEVICE
+ *           pointer to [sample][F] floats, laid out like the beauty's samples of that call (dense: ((line - row_begin) * W + col) * spp + i;
+ *           scattered and splatted: [n][F]).  The layer list is NULL exactly when the accumulator has no layers.  Dropped samples are
+ *           dropped for the features too and counted once.  Batches split into chunks as the other forms do; no bit depends on the
+ *           split, nor on the alignment of d_features (aligned buffers are read with wider loads).
+ *   feature_statistics: d_features, d_variances: W*H*F floats each; d_variances may be NULL.  Enqueued on the context's stream, no
+ *           synchronisation, the state unchanged.
+ *   reset clears the feature planes; merge needs equal nb_features on both sides (EINVAL otherwise) and adds the feature planes too, one
+ *           fp32 add per float on either of its paths; plan, statistics, moments, layer_statistics and the v1 state and layer block
+ *           calls act as on an accumulator without features.
+ *   Feature block: the serialised feature planes, a block of its own beside the v1 state and the layer block: a 64-byte little-endian
+ *           header -- magic "BCDACCFT" 0, version (1) 8, header_bytes (64) 12, width 16, height 20, nb_features 24, nb_planes =
+ *           2 * nb_features 28, 32 zero reserved bytes 32 -- then the planes as they sit in HBM; exactly 64 + 8 * nb_features * W * H bytes.
+ *   features_state_info: host only (no device, no context): EINVAL unless magic, version, header_bytes, nb_features in [1, 8], positive
+ *           sizes below 2^31 pixels, nb_planes, the exact size and zero reserved bytes hold.  out may be NULL.
+ *   features_state_bytes / export_features / import_features / merge_features_state: as their layer counterparts, through the same
+ *           staging chunks.  export synchronises.
+ *   Refusals, EINVAL with a message before any device work, the state untouched and the context usable: nb_features or nb_layers out of
+ *           range; a plain or _layers add on an accumulator with features (it would move the weight sums without the features); a
+ *           _features add, feature_statistics or a feature block call on an accumulator without features; a null d_features; a layer
+ *           list without layers, no list with them, a null entry; a malformed block, another frame size, another channel count;
+ *           feature_statistics with a null d_features or outputs that overlap. */
+#define BCD_HIP_ACCUM_MAX_FEATURES BCD_HIP_GUIDE_MAX_CHANNELS
+int  bcd_hip_accum_create_features(bcd_hip_ctx *ctx, int W, int H, int nb_bins, float gamma, float max_value, int64_t max_batch_samples, int nb_layers,
+                                   int nb_features, bcd_hip_accum **acc);
+int  bcd_hip_accum_nb_features(bcd_hip_accum *acc, int *nb_features);
+int  bcd_hip_accum_add_dense_features(bcd_hip_accum *acc, const float *d_samples, const float *d_weights, int row_begin, int rows, int spp, int channels,
+                                      const float *const *d_layer_samples, int layer_channels, const float *d_features);
+int  bcd_hip_accum_add_scattered_features(bcd_hip_accum *acc, const int32_t *d_pixel, const float *d_rgb, const float *d_weights, int64_t n,
+                                          const float *const *d_layer_rgb, const float *d_features);
+int  bcd_hip_accum_add_splatted_features(bcd_hip_accum *acc, const float *d_xy, const float *d_rgb, const float *d_weights, int64_t n,
+                                         const float *const *d_layer_rgb, const float *d_features);
+int  bcd_hip_accum_feature_statistics(bcd_hip_accum *acc, float *d_features, float *d_variances);
+typedef struct bcd_hip_accum_features_header {
+    char     magic[8];       /* the 8 bytes BCDACCFT, no terminator */
+    uint32_t version;        /* 1 */
+    uint32_t header_bytes;   /* 64: offset of the first plane */
+    int32_t  width, height, nb_features;
+    uint32_t nb_planes;      /* 2 * nb_features */
+    uint8_t  reserved[32];   /* zero */
+} bcd_hip_accum_features_header;
+#define BCD_HIP_ACCUM_FEATURES_VERSION 1
+#define BCD_HIP_ACCUM_FEATURES_HEADER_BYTES 64
+int  bcd_hip_accum_features_state_info(const void *h_features, int64_t bytes, bcd_hip_accum_features_header *out);
+int  bcd_hip_accum_features_state_bytes(bcd_hip_accum *acc, int64_t *bytes);
+int  bcd_hip_accum_export_features(bcd_hip_accum *acc, void *h_features, int64_t capacity);
+int  bcd_hip_accum_import_features(bcd_hip_accum *acc, const void *h_features, int64_t bytes);
+int  bcd_hip_accum_merge_features_state(bcd_hip_accum *acc, const void *h_features, int64_t bytes);
 /* checkAndPutToZeroNegativeInfNaNValues   src/cli/main.cpp:389-420 */
 int bcd_hip_zero_bad_values(bcd_hip_ctx *ctx, float *d_img, int64_t n);
 
