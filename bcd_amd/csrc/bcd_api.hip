@@ -874,20 +874,20 @@ int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView 
     return BCD_HIP_OK;
 }
 
-// merge_on for the extra layers' outputs: two launches for all of them
-int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int H, const LayerView &lo)
+// merge_on for the extra layers' outputs: two launches for all of them.  scratch: the buffer that takes the reduced outputs, one slice per layer (the
+// workspace's lay_tmp_lo in a frame's own calls, ctx->temporal.lay_tmp_lo in the temporal calls and the pops of a sequence)
+int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, DevBuf &scratch, const LayerView &hi, int W, int H, const LayerView &lo)
 {
     const int w2 = W / 2, h2 = H / 2;
     const size_t slice = (size_t)w2 * h2 * 3;
-    RCCHK(ensure(ctx, wk.lay_tmp_lo, (size_t)hi.n * slice * sizeof(float)));
+    RCCHK(ensure(ctx, scratch, (size_t)hi.n * slice * sizeof(float)));
     BcdLayerTable t = {};
-    for (int k = 0; k < hi.n; ++k) { t.a[k] = hi.out[k]; t.o[k] = (float *)wk.lay_tmp_lo.p + k * slice; }
+    for (int k = 0; k < hi.n; ++k) { t.a[k] = hi.out[k]; t.o[k] = (float *)scratch.p + k * slice; }
     HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, hi.n, W, H, wk.stream));
-    for (int k = 0; k < hi.n; ++k) { t.a[k] = (const float *)wk.lay_tmp_lo.p + k * slice; t.b[k] = lo.out[k]; t.o[k] = hi.out[k]; }
+    for (int k = 0; k < hi.n; ++k) { t.a[k] = (const float *)scratch.p + k * slice; t.b[k] = lo.out[k]; t.o[k] = hi.out[k]; }
     HIPCHK(ctx, bcd_launch_layers_merge(t, hi.n, w2, h2, W, H, wk.stream));
     return BCD_HIP_OK;
 }
-
 
 int work_init(bcd_hip_ctx *ctx, Work &w, hipStream_t stream)
 {
@@ -1220,7 +1220,7 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
                         if (hipStreamWaitEvent(w->stream, ctx->extra[s + 1].ev_done, 0) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
                         rc = merge_on(ctx, *w, out[s], ws[s], hh[s], out[s + 1], 3);
                         if (rc != BCD_HIP_OK) break;
-                        if (lvp) rc = merge_layers_on(ctx, *w, lvp[s], ws[s], hh[s], lvp[s + 1]);
+                        if (lvp) rc = merge_layers_on(ctx, *w, w->lay_tmp_lo, lvp[s], ws[s], hh[s], lvp[s + 1]);
                         if (rc != BCD_HIP_OK) break;
                     }
                     if (s != 0) {
@@ -1254,7 +1254,7 @@ int denoise_impl(bcd_hip_ctx *ctx, const float *d_colors, const float *d_ns, con
     for (int s = nb_scales - 1; s >= 0; --s) {
         RCCHK(mono(ctx, ctx->main, col[s], ns[s], hs[s], cv[s], ws[s], hh[s], D, prm, bcd_hip_scale_seed(prm->order_seed, s), s, out[s], lvp ? &lvp[s] : nullptr));
         if (s < nb_scales - 1) RCCHK(bcd_hip_merge(ctx, out[s], ws[s], hh[s], out[s + 1], 3));
-        if (s < nb_scales - 1 && lvp) RCCHK(merge_layers_on(ctx, ctx->main, lvp[s], ws[s], hh[s], lvp[s + 1]));
+        if (s < nb_scales - 1 && lvp) RCCHK(merge_layers_on(ctx, ctx->main, ctx->main.lay_tmp_lo, lvp[s], ws[s], hh[s], lvp[s + 1]));
     }
     if (lvp) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return BCD_HIP_OK;
@@ -1281,8 +1281,19 @@ int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius)
     return BCD_HIP_OK;
 }
 
-// level s + 1 of the features is downscale_avg of level s, level s + 1 of the variances downscale_avg of level s times 0.25f (the variance of a mean of
-// four); threshold and floors are those of level 0.  On the context's stream: every scale's stream waits for what that stream holds (ev_pyramid)
+// one level of a feature pyramid from the W x H level above it: the features are downscale_avg of the finer ones, the variances (d_var null: none)
+// downscale_avg of the finer ones times 0.25f (the variance of a mean of four)
+int guide_build_level(bcd_hip_ctx *ctx, const float *d_feat, const float *d_var, int W, int H, int F, float *d_feat_out, float *d_var_out, hipStream_t st)
+{
+    HIPCHK(ctx, bcd_launch_downscale(1, d_feat, W, H, F, d_feat_out, st));
+    if (!d_var) return BCD_HIP_OK;
+    HIPCHK(ctx, bcd_launch_downscale(1, d_var, W, H, F, d_var_out, st));
+    HIPCHK(ctx, bcd_launch_scale_inplace(d_var_out, 0.25f, (int64_t)(W / 2) * (H / 2) * F, st));
+    return BCD_HIP_OK;
+}
+
+// the levels of the guide's pyramid by guide_build_level; threshold and floors are those of level 0.  On the context's stream: every scale's stream waits for
+// what that stream holds (ev_pyramid)
 int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales)
 {
     const int F = g->nb_channels;
@@ -1295,14 +1306,10 @@ int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_feature
     for (int s = 1, ws = W, hs = H; s < nb_scales && s < MAX_SCALES; ++s) {
         const size_t np = (size_t)(ws / 2) * (hs / 2);
         RCCHK(ensure(ctx, ctx->guide_pyr[s][0], np * F * sizeof(float)));
-        HIPCHK(ctx, bcd_launch_downscale(1, G.f[s - 1], ws, hs, F, (float *)ctx->guide_pyr[s][0].p, ctx->stream));
+        if (d_variances) RCCHK(ensure(ctx, ctx->guide_pyr[s][1], np * F * sizeof(float)));
+        RCCHK(guide_build_level(ctx, G.f[s - 1], G.v[s - 1], ws, hs, F, (float *)ctx->guide_pyr[s][0].p, (float *)ctx->guide_pyr[s][1].p, ctx->stream));
         G.f[s] = (const float *)ctx->guide_pyr[s][0].p;
-        if (d_variances) {
-            RCCHK(ensure(ctx, ctx->guide_pyr[s][1], np * F * sizeof(float)));
-            HIPCHK(ctx, bcd_launch_downscale(1, G.v[s - 1], ws, hs, F, (float *)ctx->guide_pyr[s][1].p, ctx->stream));
-            HIPCHK(ctx, bcd_launch_scale_inplace((float *)ctx->guide_pyr[s][1].p, 0.25f, (int64_t)np * F, ctx->stream));
-            G.v[s] = (const float *)ctx->guide_pyr[s][1].p;
-        }
+        if (d_variances) G.v[s] = (const float *)ctx->guide_pyr[s][1].p;
         ws /= 2; hs /= 2;
     }
     G.on = true;
@@ -1855,7 +1862,7 @@ int bcd_hip_layers_merge(bcd_hip_ctx *ctx, float *const *d_hi, const float *cons
     LayerView hi, lo;
     hi.n = lo.n = nb_layers;
     for (int k = 0; k < nb_layers; ++k) { hi.out[k] = d_hi[k]; lo.out[k] = const_cast<float *>(d_lo[k]); }
-    return merge_layers_on(ctx, ctx->main, hi, W, H, lo); // (the frame's own two launches)
+    return merge_layers_on(ctx, ctx->main, ctx->main.lay_tmp_lo, hi, W, H, lo); // (the frame's own two launches)
 }
 
 int bcd_hip_bayes_last_redo_count(bcd_hip_ctx *ctx, int32_t *count)

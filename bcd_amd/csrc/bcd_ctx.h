@@ -318,11 +318,14 @@ int denoise_layers_checked(bcd_hip_ctx *ctx, const float *d_ns, const float *d_h
 int layers_follow(bcd_hip_ctx *ctx, Work &wk, const LayerView &lv, const uint32_t *d_mask, const int32_t *d_nsim, const uint8_t *d_state, const float *const *pixcov,
                   float *const *sum, int W, int H, int w, int b, float min_eig, const int32_t *d_count, int32_t *spectral, const KeptLists *kept = nullptr);
 int build_level_layers(bcd_hip_ctx *ctx, const LayerView &fine, const LayerView &coarse, const float *ns_fine, int W, int H, hipStream_t st);
-int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, const LayerView &hi, int W, int H, const LayerView &lo);
+int merge_layers_on(bcd_hip_ctx *ctx, Work &wk, DevBuf &scratch, const LayerView &hi, int W, int H, const LayerView &lo); // (scratch: grown to one reduced slice per layer)
 // the guide of a bcd_hip_denoise_guided call: its refusals (no device work), then -- on the context's stream -- its pyramid and ctx->guide; guide_end switches it off
 int check_guide(bcd_hip_ctx *ctx, const bcd_hip_guide *g, int search_radius);
 int guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const float *d_features, const float *d_variances, int W, int H, int nb_scales);
 inline void guide_end(bcd_hip_ctx *ctx) { ctx->guide.on = false; }
+// one level of a feature pyramid from the W x H level above it (guide_begin, temporal_guide_begin, the push of a sequence): the features averaged, the
+// variances (d_var null: none) averaged and multiplied by 0.25f
+int guide_build_level(bcd_hip_ctx *ctx, const float *d_feat, const float *d_var, int W, int H, int F, float *d_feat_out, float *d_var_out, hipStream_t st);
 // the gate of a guided selection with ctx->guide's channels, floors and threshold, behind a selection pass on wk.stream: the feature masks of (d_features,
 // d_variances) into wk.gate_mask / wk.gate_nsim, then d_mask &= them and d_count = the bits that remain (the code path of a guided scale)
 int guide_gate_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_features, const float *d_variances, int W, int H, int w, int b, uint32_t *d_mask, int32_t *d_count);
@@ -332,6 +335,16 @@ int distance_timing_events(bcd_hip_ctx *ctx, Work &wk, hipEvent_t *e0, hipEvent_
 int moments_masks(bcd_hip_ctx *ctx, Work &wk, const float *d_colors, const float *d_pixcov, int W, int H, int w, int b, float tau, float var_floor, uint32_t *d_mask,
                   int32_t *d_count);
 
+// every DevBuf of an array of them, of any shape, freed and emptied: free_bufs(a, sizeof a)
+inline void free_bufs(void *first, size_t bytes)
+{
+    DevBuf *b = static_cast<DevBuf *>(first);
+    for (size_t i = 0; i < bytes / sizeof(DevBuf); ++i) {
+        if (b[i].p) (void)hipFree(b[i].p);
+        b[i] = DevBuf();
+    }
+}
+
 // do the byte ranges [a, a + na) and [b, b + nb) share a byte?  The one overlap predicate of the argument checks
 inline bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
@@ -339,7 +352,7 @@ inline bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb)
     return a0 < b1 && b0 < a1;
 }
 
-// ---- defined in bcd_temporal.hip: what the frame call and the layered call (bcd_temporal_layers.hip) of a sequence share
+// ---- defined in bcd_temporal.hip: what the frame calls, the layered calls (bcd_temporal_layers.hip) and the sequence (bcd_sequence.hip) share
 void temporal_free(bcd_hip_ctx *ctx); // (bcd_hip_ctx_destroy)
 // does [out, out + bytes) overlap one of a frame's images (a null image: not looked at)?
 bool overlaps_frame_images(const void *out, size_t bytes, const void *col, const void *ns, const void *hist, const void *cov, size_t npix, int D);
@@ -386,10 +399,34 @@ struct LayerFrames {
 // bayes_temporal for L layers on one selection (see its definition); redo[k]: the items of layer k that took the redo list
 int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, const int32_t *d_nsim_total, const uint8_t *d_state, int W, int H, int b, float min_eig,
                           float *const *d_sum, int32_t *d_count, int32_t *redo);
-// the masks temporal_select left for frame f
-inline const uint32_t *temporal_mask(const bcd_hip_ctx *ctx, int f) { return (const uint32_t *)(f == 0 ? ctx->main.mask.p : ctx->temporal.mask[f].p); }
 // the tail of a scale (the stream is synchronised): the figures of wk.h_counters->lists and of the in-frame pass, and with profiling the four timers
 void temporal_stats_tail(bcd_hip_ctx *ctx, int scale, const TemporalPath &path);
+// The refusals a call with neighbour frames makes of its geometry, in this order: the scale count, the temporal radius of a sequence (sequence_radius null: a
+// frame call), with neighbours the patch and search radius, the image size against the scale count
+int check_temporal_geometry(bcd_hip_ctx *ctx, int W, int H, int nb_scales, const bcd_hip_params *prm, bool neighbours, const int *sequence_radius);
+// one frame at one pyramid level, as temporal_build_level and temporal_scale see it
+struct TemporalFrame {
+    TemporalSelFrame sel = { nullptr, nullptr, nullptr }; // by the caller: ns, hist (null: "Moments"), valid, feat, var, transpose_from, mask_dst (temporal_scale adds col, pixcov)
+    const float *col[BCD_MAX_LAYERS] = {}, *cov[BCD_MAX_LAYERS] = {}; // the colours and covariances of its layers
+    float *pixcov = nullptr; // the per-pixel covariances of its layers, one slice per layer: temporal_scale computes them from cov, or a sequence's push has
+};
+// Level s of a frame from its W x H level s - 1, on st: sample counts and histograms summed (hist null: none), the colours averaged and the covariances
+// weighted by the counts -- of one layer by the reducers of bcd_hip_denoise (its colours first), of a layered estimate by build_level_layers.  `coarse`
+// holds the destinations
+int temporal_build_level(bcd_hip_ctx *ctx, const TemporalFrame &fine, const TemporalFrame &coarse, int L, bool layered, int W, int H, int D, hipStream_t st);
+// one scale of a call with neighbour frames, as its caller tabulates it
+struct TemporalScale {
+    int nf = 0, L = 1;
+    bool layered = false;       // the estimate of bayes_temporal_layers (L > 1, or "Moments"), else bayes_temporal on one layer of histograms
+    bool pixcov_ready = false;  // the frames' per-pixel covariances are complete (the pushes of a sequence), else they are computed from fr[f].cov
+    TemporalFrame fr[BCD_MAX_NEIGHBOURS + 1]; // [0]: the frame itself
+    float *sum = nullptr;       // the sums, one slice per layer
+    float *out[BCD_MAX_LAYERS] = {};
+    uint32_t *self_copy = nullptr; // null, or what takes a copy of the in-frame masks (self[s] of a sequence)
+};
+// The one scale stage: temporal_select, the cleared accumulators, the estimate and finalisation of the kind sc.layered names, temporal_stats_tail and, layered,
+// ctx->layer_spectral[scale].  A neighbour's masks are in sc.fr[f].sel.mask_dst, or in ctx->temporal.mask[f] where that is null
+int temporal_scale(bcd_hip_ctx *ctx, const TemporalScale &sc, int W, int H, int D, const bcd_hip_params *prm, int scale);
 // The lists of an estimate over several frames on wk.stream: the buffers, the cleared counters, k_active_lists on the states and the TOTAL |S|, the copy of the list
 // lengths and the sum of |S| to wk.h_counters->lists (not waited for).  -> the CU slots of the chain, the grid of the fallback kernel
 struct TemporalLists { int cus, weak_grid; };

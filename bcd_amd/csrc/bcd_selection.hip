@@ -329,7 +329,7 @@ int bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, c
                     if (s < S - 1) {
                         if (await(done[s + 1]) < 0) { rc = BCD_HIP_EDEVICE; break; }
                         if (hipStreamWaitEvent(w->stream, ctx->extra[s + 1].ev_done, 0) != hipSuccess) { rc = BCD_HIP_EDEVICE; break; }
-                        rc = merge_layers_on(ctx, *w, lvs[s], sel->sc[s].W, sel->sc[s].H, lvs[s + 1]);
+                        rc = merge_layers_on(ctx, *w, w->lay_tmp_lo, lvs[s], sel->sc[s].W, sel->sc[s].H, lvs[s + 1]);
                         if (rc != BCD_HIP_OK) break;
                     }
                     if (s != 0) {
@@ -350,7 +350,7 @@ int bcd_hip_selection_denoise(bcd_hip_selection *sel, const float *d_nsamples, c
             RCCHK(reuse_build_level(ctx, lvs[s - 1], lvs[s], ns[s - 1], ns_built[s], sel->sc[s - 1].W, sel->sc[s - 1].H, ctx->stream));
         for (int s = S - 1; s >= 0; --s) { // coarse to fine, one after the other
             RCCHK(reuse_scale(ctx, sel, ctx->main, s, lvs[s], ns[s]));
-            if (s < S - 1) RCCHK(merge_layers_on(ctx, ctx->main, lvs[s], sel->sc[s].W, sel->sc[s].H, lvs[s + 1]));
+            if (s < S - 1) RCCHK(merge_layers_on(ctx, ctx->main, ctx->main.lay_tmp_lo, lvs[s], sel->sc[s].W, sel->sc[s].H, lvs[s + 1]));
         }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream)); // (the last merge)

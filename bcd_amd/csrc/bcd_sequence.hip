@@ -3,12 +3,14 @@
 // every pair of frames twice, build every frame's pyramid 2R + 1 times and (through the host entry points) upload every frame 2R + 1 times.  The sequence
 // keeps the last 2R + 1 frames in a ring of slots -- a push copies the frame once and builds its pyramid levels and their per-pixel covariances once -- and
 // the cross masks of every pair (a, b), a < b <= a + R, from the pop of frame a until the pop of frame b, which takes them through k_masks_transpose
-// (k_masks_transpose.hip) instead of a second cross pass.  A pop runs the scales coarse to fine through the code of the frame call: temporal_select (with the
-// sequence's members of TemporalSelFrame), bayes_temporal, the finalisation, bcd_hip_merge.
+// (k_masks_transpose.hip) instead of a second cross pass.  A push builds the levels with the reducers of the frame calls (temporal_build_level,
+// guide_build_level); a pop runs the scales coarse to fine through the scale stage of the frame calls (temporal_scale, bcd_temporal.hip) with the slots'
+// images, the pushes' per-pixel covariances and the sequence's members of TemporalSelFrame in its table, and merges them as the matching frame call does.
 // A sequence in a mode (bcd_hip_sequence_create_mode; section 16, "Modes") holds L colour layers per slot, no histogram when it selects from means and
 // covariances, and the levels of the feature pyramid when it gates: the moment and the feature cross distances are symmetric as the histogram distance is, the
 // transposition distributes over the AND of the gate, so the kept (gated) masks are transposed as they are and a transposed neighbour runs neither a cross pass
-// nor temporal_guide_gate.  Its pops run temporal_select in the mode and the layered estimate of bcd_temporal_layers.hip (bayes_temporal_layers).
+// nor temporal_guide_gate.  There is one push, one pop and one construction: a sequence of bcd_hip_sequence_create is the mode of one layer, histograms and
+// no gate; L > 1 or moments take the layered estimate (bayes_temporal_layers), one layer of histograms, gated or not, bayes_temporal.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -52,7 +54,7 @@ struct bcd_hip_sequence {
     bool moments = false, fvar = false;      // selection from means and covariances (D = 0, no histogram stored); every frame brings feature variances
     float var_floor = 0.f, floors[BCD_GUIDE_MAX_CHANNELS] = {}, ftau = 0.f;
     int64_t feature_passes = 0;              // cross feature passes its pops launched
-    bool plain() const { return L == 1 && !moments && F == 0; }   // today's sequence, on today's path
+    bool plain() const { return L == 1 && !moments && F == 0; }   // what bcd_hip_sequence_create builds: its entry points, and it reports no layers
     bool layered() const { return moments || L > 1; }             // the estimate of bcd_temporal_layers.hip (one layer of histograms: that of bcd_temporal.hip)
 };
 
@@ -84,64 +86,25 @@ int64_t ready_count(const bcd_hip_sequence *q)
     return q->ended ? q->pushed - q->popped : std::max<int64_t>(0, q->pushed - q->R - q->popped);
 }
 
-// a push: the four images into the frame's slot (kind: device to device, or host to device), its pyramid levels by the reducers of temporal_run, the per-pixel
-// covariances of every level; synchronised, so the caller's buffers are free when it returns
-int push(bcd_hip_sequence *q, const float *col, const float *ns, const float *hist, const float *cov, hipMemcpyKind kind)
+// slot sl at level s as temporal_build_level and temporal_scale see it: every image the mode stores, the layers as slices of the slot's buffers
+TemporalFrame slot_level(const bcd_hip_sequence *q, const SeqSlot &sl, int s)
 {
-    if (!q) return BCD_HIP_EINVAL;
-    bcd_hip_ctx *ctx = q->ctx;
-    if (!q->plain()) return bad(ctx, "this sequence was created in a mode (bcd_hip_sequence_create_mode): its frames are pushed by bcd_hip_sequence_push_frame");
-    if (!col || !ns || !hist || !cov) return bad(ctx, "null image pointer");
-    if (q->ended) return bad(ctx, "the sequence has ended: no further frame can be pushed (bcd_hip_sequence_reset starts another)");
-    if (q->pushed > q->popped + q->R) return bad(ctx, "pop first: the ring holds every frame the next pop needs");
-    DEVICE_GUARD(ctx);
-    hipStream_t st = ctx->main.stream;
-    SeqSlot &sl = q->slot[q->pushed % q->N];
-    const int D = q->D;
-    const float *src[4] = { col, ns, hist, cov };
-    for (int s = 0; s < q->S; ++s) {
-        const size_t np = (size_t)q->ws[s] * q->hs[s], bytes[4] = { np * 3 * sizeof(float), np * sizeof(float), np * D * sizeof(float), np * 6 * sizeof(float) };
-        for (int k = 0; k < 4; ++k) RCCHK(seq_ensure(q, sl.lv[s][k], bytes[k]));
-        RCCHK(seq_ensure(q, sl.pixcov[s], bytes[3]));
-        float *l[4] = { (float *)sl.lv[s][0].p, (float *)sl.lv[s][1].p, (float *)sl.lv[s][2].p, (float *)sl.lv[s][3].p };
-        if (s == 0) {
-            for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(l[k], src[k], bytes[k], kind, st));
-            if (kind == hipMemcpyHostToDevice) q->uploaded += (int64_t)(bytes[0] + bytes[1] + bytes[2] + bytes[3]);
-        } else {
-            const float *fine[4] = { (const float *)sl.lv[s - 1][0].p, (const float *)sl.lv[s - 1][1].p, (const float *)sl.lv[s - 1][2].p, (const float *)sl.lv[s - 1][3].p };
-            HIPCHK(ctx, bcd_launch_downscale(1, fine[0], q->ws[s - 1], q->hs[s - 1], 3, l[0], st));
-            HIPCHK(ctx, bcd_launch_downscale(0, fine[1], q->ws[s - 1], q->hs[s - 1], 1, l[1], st));
-            HIPCHK(ctx, bcd_launch_downscale(0, fine[2], q->ws[s - 1], q->hs[s - 1], D, l[2], st));
-            HIPCHK(ctx, bcd_launch_downscale_cov(fine[3], fine[1], q->ws[s - 1], q->hs[s - 1], l[3], st));
-        }
-        HIPCHK(ctx, bcd_launch_pixel_cov(l[3], l[1], (int64_t)np, (float *)sl.pixcov[s].p, st));
-    }
-    for (int64_t &f : sl.pair_frame) f = -1; // (the slot's earlier frame: its pairs were consumed R pops ago)
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    ++q->pushed;
-    ++q->pyramids;
-    return BCD_HIP_OK;
+    const size_t np = (size_t)q->ws[s] * q->hs[s];
+    TemporalFrame f;
+    f.sel.ns = (const float *)sl.lv[s][1].p;
+    f.sel.hist = q->moments ? nullptr : (const float *)sl.lv[s][2].p;
+    if (q->F) { f.sel.feat = (const float *)sl.guide[s][0].p; f.sel.var = q->fvar ? (const float *)sl.guide[s][1].p : nullptr; }
+    for (int k = 0; k < q->L; ++k) { f.col[k] = (const float *)sl.lv[s][0].p + k * np * 3; f.cov[k] = (const float *)sl.lv[s][3].p + k * np * 6; }
+    f.pixcov = (float *)sl.pixcov[s].p;
+    return f;
 }
 
-// a push in a mode: the frame's images into its slot, every pyramid level by the reducers of the matching frame call (layers_run of bcd_temporal_layers.hip
-// for a layered estimate, temporal_run for one layer of histograms; the feature levels by guide_begin's rule), the per-pixel covariances of all layers of a
-// level in one launch; synchronised
+// a push, behind the refusals of its entry point: the frame's images into its slot (kind: device to device, or host to device), every pyramid level by the
+// reducers of the matching frame call (temporal_build_level, guide_build_level), the per-pixel covariances of all layers of a level in one launch;
+// synchronised, so the caller's buffers are free when it returns
 int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyKind kind)
 {
-    if (!q) return BCD_HIP_EINVAL;
     bcd_hip_ctx *ctx = q->ctx;
-    if (!q->by_mode) return bad(ctx, "this sequence was created by bcd_hip_sequence_create: its frames are pushed by bcd_hip_sequence_push");
-    if (!fm) return bad(ctx, "null frame");
-    if (fm->reserved) return bad(ctx, "the reserved pointer of a frame must be NULL");
-    if (!fm->nsamples) return bad(ctx, "null image pointer");
-    if (q->moments && fm->histograms) return bad(ctx, "a moments sequence takes no histograms: the frame's histograms must be NULL");
-    if (!q->moments && !fm->histograms) return bad(ctx, "a histogram sequence needs the frame's histograms");
-    if (!fm->layers) return bad(ctx, "null layer list");
-    for (int k = 0; k < q->L; ++k) if (!fm->layers[k].d_colors || !fm->layers[k].d_covariances) return bad(ctx, "null image pointer in a layer");
-    if (q->F == 0 && (fm->features || fm->variances)) return bad(ctx, "the sequence has no feature gate: the frame's features and variances must be NULL");
-    if (q->F > 0 && !fm->features) return bad(ctx, "null feature image");
-    if (q->F > 0 && (fm->variances != nullptr) != q->fvar) return bad(ctx, "feature variances must be given for every frame or for none, as the mode says");
-    if (q->plain()) return push(q, fm->layers[0].d_colors, fm->nsamples, fm->histograms, fm->layers[0].d_covariances, kind);
     if (q->ended) return bad(ctx, "the sequence has ended: no further frame can be pushed (bcd_hip_sequence_reset starts another)");
     if (q->pushed > q->popped + q->R) return bad(ctx, "pop first: the ring holds every frame the next pop needs");
     DEVICE_GUARD(ctx);
@@ -158,49 +121,30 @@ int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyK
         RCCHK(seq_ensure(q, sl.pixcov[s], L * np * 6 * f4));
         if (F) RCCHK(seq_ensure(q, sl.guide[s][0], np * F * f4));
         if (F && q->fvar) RCCHK(seq_ensure(q, sl.guide[s][1], np * F * f4));
-        float *col = (float *)sl.lv[s][0].p, *ns = (float *)sl.lv[s][1].p, *hist = (float *)sl.lv[s][2].p, *cov = (float *)sl.lv[s][3].p;
-        float *feat = (float *)sl.guide[s][0].p, *var = (float *)sl.guide[s][1].p;
+        const TemporalFrame l = slot_level(q, sl, s);
         if (s == 0) {
             int64_t bytes = (int64_t)(np * f4);
-            HIPCHK(ctx, hipMemcpyAsync(ns, fm->nsamples, np * f4, kind, st));
-            if (!q->moments) { HIPCHK(ctx, hipMemcpyAsync(hist, fm->histograms, np * D * f4, kind, st)); bytes += (int64_t)(np * D * f4); }
+            HIPCHK(ctx, hipMemcpyAsync(sl.lv[0][1].p, fm->nsamples, np * f4, kind, st));
+            if (!q->moments) { HIPCHK(ctx, hipMemcpyAsync(sl.lv[0][2].p, fm->histograms, np * D * f4, kind, st)); bytes += (int64_t)(np * D * f4); }
             for (int k = 0; k < L; ++k) {
-                HIPCHK(ctx, hipMemcpyAsync(col + k * np * 3, fm->layers[k].d_colors, np * 3 * f4, kind, st));
-                HIPCHK(ctx, hipMemcpyAsync(cov + k * np * 6, fm->layers[k].d_covariances, np * 6 * f4, kind, st));
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<float *>(l.col[k]), fm->layers[k].d_colors, np * 3 * f4, kind, st));
+                HIPCHK(ctx, hipMemcpyAsync(const_cast<float *>(l.cov[k]), fm->layers[k].d_covariances, np * 6 * f4, kind, st));
                 bytes += (int64_t)(np * 9 * f4);
             }
-            if (F) { HIPCHK(ctx, hipMemcpyAsync(feat, fm->features, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
-            if (F && q->fvar) { HIPCHK(ctx, hipMemcpyAsync(var, fm->variances, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
+            if (F) { HIPCHK(ctx, hipMemcpyAsync(sl.guide[0][0].p, fm->features, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
+            if (F && q->fvar) { HIPCHK(ctx, hipMemcpyAsync(sl.guide[0][1].p, fm->variances, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
             if (kind == hipMemcpyHostToDevice) q->uploaded += bytes;
         } else {
-            const int wf = q->ws[s - 1], hf = q->hs[s - 1];
-            const size_t npf = (size_t)wf * hf;
-            const float *fcol = (const float *)sl.lv[s - 1][0].p, *fns = (const float *)sl.lv[s - 1][1].p, *fhist = (const float *)sl.lv[s - 1][2].p;
-            const float *fcov = (const float *)sl.lv[s - 1][3].p;
-            HIPCHK(ctx, bcd_launch_downscale(0, fns, wf, hf, 1, ns, st));
-            if (!q->moments) HIPCHK(ctx, bcd_launch_downscale(0, fhist, wf, hf, D, hist, st));
-            if (q->layered()) {
-                BcdLayerTable t = {};
-                for (int k = 0; k < L; ++k) { t.a[k] = fcol + k * npf * 3; t.o[k] = col + k * np * 3; }
-                HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, wf, hf, st));
-                for (int k = 0; k < L; ++k) { t.a[k] = fcov + k * npf * 6; t.o[k] = cov + k * np * 6; }
-                HIPCHK(ctx, bcd_launch_layers_downscale_cov(t, L, fns, wf, hf, st));
-            } else {
-                HIPCHK(ctx, bcd_launch_downscale(1, fcol, wf, hf, 3, col, st));
-                HIPCHK(ctx, bcd_launch_downscale_cov(fcov, fns, wf, hf, cov, st));
-            }
-            if (F) HIPCHK(ctx, bcd_launch_downscale(1, (const float *)sl.guide[s - 1][0].p, wf, hf, F, feat, st));
-            if (F && q->fvar) { // (the variance of a mean of four)
-                HIPCHK(ctx, bcd_launch_downscale(1, (const float *)sl.guide[s - 1][1].p, wf, hf, F, var, st));
-                HIPCHK(ctx, bcd_launch_scale_inplace(var, 0.25f, (int64_t)np * F, st));
-            }
+            const TemporalFrame fine = slot_level(q, sl, s - 1);
+            RCCHK(temporal_build_level(ctx, fine, l, L, q->layered(), q->ws[s - 1], q->hs[s - 1], D, st));
+            if (F) RCCHK(guide_build_level(ctx, fine.sel.feat, fine.sel.var, q->ws[s - 1], q->hs[s - 1], F, (float *)sl.guide[s][0].p, (float *)sl.guide[s][1].p, st));
         }
         if (q->layered()) {
             BcdLayerTable t = {};
-            for (int k = 0; k < L; ++k) t.a[k] = cov + k * np * 6;
-            HIPCHK(ctx, bcd_launch_layers_pixel_cov(t, L, ns, (int64_t)np, (float *)sl.pixcov[s].p, st));
+            for (int k = 0; k < L; ++k) t.a[k] = l.cov[k];
+            HIPCHK(ctx, bcd_launch_layers_pixel_cov(t, L, l.sel.ns, (int64_t)np, l.pixcov, st));
         } else {
-            HIPCHK(ctx, bcd_launch_pixel_cov(cov, ns, (int64_t)np, (float *)sl.pixcov[s].p, st));
+            HIPCHK(ctx, bcd_launch_pixel_cov(l.cov[0], l.sel.ns, (int64_t)np, l.pixcov, st));
         }
     }
     for (int64_t &f : sl.pair_frame) f = -1; // (the slot's earlier frame: its pairs were consumed R pops ago)
@@ -210,118 +154,68 @@ int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyK
     return BCD_HIP_OK;
 }
 
-// what the selection stage of scale s reads of frame t (sel[0], fr[0]) and of its neighbours nbs[0 .. nn) in ascending order, with the buffers that take their
-// masks: a neighbour above t is searched as the frame call searches it and its (gated) masks stay with the pair (t, f); one below takes the kept masks of (f, t)
-int pop_frames(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, const SeqSlot **fr, TemporalSelFrame *sel)
+// bcd_hip_sequence_push[_host]: its refusals, then the push of a frame of one layer
+int push_images(bcd_hip_sequence *q, const float *col, const float *ns, const float *hist, const float *cov, hipMemcpyKind kind)
 {
-    const size_t mb = mask_bytes((size_t)q->ws[s] * q->hs[s], q->prm.search_radius);
+    if (!q) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = q->ctx;
+    if (!q->plain()) return bad(ctx, "this sequence was created in a mode (bcd_hip_sequence_create_mode): its frames are pushed by bcd_hip_sequence_push_frame");
+    if (!col || !ns || !hist || !cov) return bad(ctx, "null image pointer");
+    const bcd_hip_frame_layer layer = { col, cov };
+    const bcd_hip_sequence_frame fm = { ns, hist, &layer, nullptr, nullptr, nullptr };
+    return push_frame(q, &fm, kind);
+}
+
+// bcd_hip_sequence_push_frame[_host]: its refusals, then the push
+int push_mode_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyKind kind)
+{
+    if (!q) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = q->ctx;
+    if (!q->by_mode) return bad(ctx, "this sequence was created by bcd_hip_sequence_create: its frames are pushed by bcd_hip_sequence_push");
+    if (!fm) return bad(ctx, "null frame");
+    if (fm->reserved) return bad(ctx, "the reserved pointer of a frame must be NULL");
+    if (!fm->nsamples) return bad(ctx, "null image pointer");
+    if (q->moments && fm->histograms) return bad(ctx, "a moments sequence takes no histograms: the frame's histograms must be NULL");
+    if (!q->moments && !fm->histograms) return bad(ctx, "a histogram sequence needs the frame's histograms");
+    if (!fm->layers) return bad(ctx, "null layer list");
+    for (int k = 0; k < q->L; ++k) if (!fm->layers[k].d_colors || !fm->layers[k].d_covariances) return bad(ctx, "null image pointer in a layer");
+    if (q->F == 0 && (fm->features || fm->variances)) return bad(ctx, "the sequence has no feature gate: the frame's features and variances must be NULL");
+    if (q->F > 0 && !fm->features) return bad(ctx, "null feature image");
+    if (q->F > 0 && (fm->variances != nullptr) != q->fvar) return bad(ctx, "feature variances must be given for every frame or for none, as the mode says");
+    return push_frame(q, fm, kind);
+}
+
+// One scale of a pop, frame t with the neighbours nbs[0 .. nn) in ascending order: the table of temporal_scale on the slots.  The per-pixel covariances are
+// the pushes'; a neighbour above t is searched as the frame call searches it and its (gated) masks stay with the pair (t, f); one below takes the kept masks
+// of (f, t) through the transposition; the in-frame masks are copied to self[s]
+int pop_scale(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, const LayerView &out)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    const int W = q->ws[s], H = q->hs[s], L = q->L;
+    const size_t npix = (size_t)W * H, mb = mask_bytes(npix, q->prm.search_radius);
+    TemporalScale sc;
+    sc.nf = nn + 1; sc.L = L; sc.layered = q->layered(); sc.pixcov_ready = true;
+    DevBuf &sum = sc.layered ? ctx->temporal.lay_sum : ctx->main.sum;
+    RCCHK(ensure(ctx, sum, (size_t)L * npix * 3 * sizeof(float)));
+    RCCHK(seq_ensure(q, q->self[s], mb));
+    sc.sum = (float *)sum.p;
+    sc.self_copy = (uint32_t *)q->self[s].p;
+    for (int k = 0; k < L; ++k) sc.out[k] = out.out[k];
     SeqSlot &me = q->slot[t % q->N];
-    auto level = [&](const SeqSlot &sl) {
-        TemporalSelFrame f = { (const float *)sl.lv[s][1].p, q->moments ? nullptr : (const float *)sl.lv[s][2].p, nullptr };
-        if (q->F) { f.feat = (const float *)sl.guide[s][0].p; f.var = q->fvar ? (const float *)sl.guide[s][1].p : nullptr; }
-        if (q->moments) { f.col = (const float *)sl.lv[s][0].p; f.pixcov = (const float *)sl.pixcov[s].p; } // (the guide layer is layer 0: the first slice)
-        return f;
-    };
-    fr[0] = &me;
-    sel[0] = level(me);
+    sc.fr[0] = slot_level(q, me, s);
     for (int i = 1, below = 0; i <= nn; ++i) {
         const int64_t f = nbs[i - 1];
         SeqSlot &nb = q->slot[f % q->N];
-        fr[i] = &nb;
-        sel[i] = level(nb);
-        if (f > t) {
-            DevBuf &keep = me.pair[f - t - 1][s];
-            RCCHK(seq_ensure(q, keep, mb));
-            sel[i].mask_dst = (uint32_t *)keep.p;
-        } else {
-            DevBuf &dst = q->low[below++][s];
-            RCCHK(seq_ensure(q, dst, mb));
-            sel[i].mask_dst = (uint32_t *)dst.p;
-            if (q->reuse && nb.pair_frame[t - f - 1] == f) sel[i].transpose_from = (const uint32_t *)nb.pair[t - f - 1][s].p;
-        }
+        sc.fr[i] = slot_level(q, nb, s);
+        DevBuf &dst = f > t ? me.pair[f - t - 1][s] : q->low[below++][s];
+        RCCHK(seq_ensure(q, dst, mb));
+        sc.fr[i].sel.mask_dst = (uint32_t *)dst.p;
+        if (f < t && q->reuse && nb.pair_frame[t - f - 1] == f) sc.fr[i].sel.transpose_from = (const uint32_t *)nb.pair[t - f - 1][s].p;
     }
-    return BCD_HIP_OK;
+    return temporal_scale(ctx, sc, W, H, q->D, &q->prm, s);
 }
 
-// one scale of a pop with a layered estimate: temporal_layers_scale (bcd_temporal_layers.hip) on the slots -- the per-pixel covariances are the pushes', the
-// per-pop part of k_layers_pixel_cov_clear is the clear of the sums
-int pop_scale_layers(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, float *const *d_out)
-{
-    bcd_hip_ctx *ctx = q->ctx;
-    Work &wk = ctx->main;
-    auto &tp = ctx->temporal;
-    const int W = q->ws[s], H = q->hs[s], b = q->prm.search_radius, nf = nn + 1, L = q->L;
-    const size_t npix = (size_t)W * H, mb = mask_bytes(npix, b);
-    RCCHK(ensure(ctx, tp.lay_sum, (size_t)L * npix * 3 * sizeof(float)));
-    RCCHK(seq_ensure(q, q->self[s], mb));
-    const SeqSlot *fr[BCD_HIP_MAX_NEIGHBOURS + 1];
-    TemporalSelFrame sel[BCD_HIP_MAX_NEIGHBOURS + 1];
-    RCCHK(pop_frames(q, t, nbs, nn, s, fr, sel));
-    TemporalPath path;
-    RCCHK(temporal_select(ctx, sel, nf, W, H, q->D, &q->prm, s, [&]() -> int {
-        HIPCHK(ctx, hipMemsetAsync(tp.lay_sum.p, 0, (size_t)L * npix * 3 * sizeof(float), wk.stream));
-        return BCD_HIP_OK;
-    }, &path));
-    HIPCHK(ctx, hipMemcpyAsync(q->self[s].p, wk.mask.p, mb, hipMemcpyDeviceToDevice, wk.stream));
-    LayerFrames lf;
-    lf.nf = nf; lf.L = L;
-    float *sum[BCD_MAX_LAYERS];
-    for (int k = 0; k < L; ++k) sum[k] = (float *)tp.lay_sum.p + (size_t)k * npix * 3;
-    for (int f = 0; f < nf; ++f) {
-        for (int k = 0; k < L; ++k) {
-            lf.col[f][k] = (const float *)fr[f]->lv[s][0].p + (size_t)k * npix * 3;
-            lf.pixcov[f][k] = (const float *)fr[f]->pixcov[s].p + (size_t)k * npix * 6;
-        }
-        lf.mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : sel[f].mask_dst;
-    }
-    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
-    int32_t redo[BCD_MAX_LAYERS] = {};
-    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, q->prm.min_eigen_value, sum, (int32_t *)wk.cnt.p, redo));
-    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
-    {
-        BcdLayerTable tb = {};
-        for (int k = 0; k < L; ++k) { tb.a[k] = sum[k]; tb.o[k] = d_out[k]; }
-        HIPCHK(ctx, bcd_launch_layers_finalize(tb, L, (const int32_t *)wk.cnt.p, (int64_t)npix, wk.stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    temporal_stats_tail(ctx, s, path);
-    for (int k = 0; k < L; ++k) ctx->layer_spectral[s][k] = redo[k];
-    return BCD_HIP_OK;
-}
-
-// one scale of a pop: frame t with the neighbours nbs[0 .. nn) in ascending order
-int pop_scale(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s, float *d_out)
-{
-    bcd_hip_ctx *ctx = q->ctx;
-    Work &wk = ctx->main;
-    const int W = q->ws[s], H = q->hs[s], b = q->prm.search_radius, nf = nn + 1;
-    const size_t npix = (size_t)W * H, mb = mask_bytes(npix, b);
-    RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
-    RCCHK(seq_ensure(q, q->self[s], mb));
-    const SeqSlot *fr[BCD_HIP_MAX_NEIGHBOURS + 1];
-    TemporalSelFrame sel[BCD_HIP_MAX_NEIGHBOURS + 1];
-    RCCHK(pop_frames(q, t, nbs, nn, s, fr, sel));
-    TemporalPath path;
-    RCCHK(temporal_select(ctx, sel, nf, W, H, q->D, &q->prm, s, []() -> int { return BCD_HIP_OK; } /* (computed by the pushes) */, &path));
-    HIPCHK(ctx, hipMemcpyAsync(q->self[s].p, wk.mask.p, mb, hipMemcpyDeviceToDevice, wk.stream));
-    BcdFrameTable tb = {};
-    tb.n = nf;
-    for (int i = 0; i < nf; ++i) {
-        tb.col[i] = (const float *)fr[i]->lv[s][0].p;
-        tb.pixcov[i] = (const float *)fr[i]->pixcov[s].p;
-        tb.mask[i] = i == 0 ? (const uint32_t *)wk.mask.p : sel[i].mask_dst;
-    }
-    HIPCHK(ctx, hipMemsetAsync(wk.sum.p, 0, npix * 3 * sizeof(float), wk.stream));
-    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
-    RCCHK(bayes_temporal(ctx, wk, tb, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, b, q->prm.min_eigen_value, (float *)wk.sum.p, (int32_t *)wk.cnt.p));
-    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
-    HIPCHK(ctx, bcd_launch_finalize((const float *)wk.sum.p, (const int32_t *)wk.cnt.p, (int64_t)npix, d_out, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    temporal_stats_tail(ctx, s, path);
-    return BCD_HIP_OK;
-}
-
-// a frame without neighbours in a mode: the matching single-frame call on the slot's copies
+// a frame without neighbours: the matching single-frame call on the slot's copies (a sequence of bcd_hip_sequence_create: the plain call, which reports no layers)
 int pop_single(bcd_hip_sequence *q, const SeqSlot &me, float *const *d_out)
 {
     bcd_hip_ctx *ctx = q->ctx;
@@ -329,6 +223,7 @@ int pop_single(bcd_hip_sequence *q, const SeqSlot &me, float *const *d_out)
     bcd_hip_layer lay[BCD_HIP_MAX_LAYERS];
     for (int k = 0; k < q->L; ++k) lay[k] = { (const float *)me.lv[0][0].p + k * npix * 3, (const float *)me.lv[0][3].p + k * npix * 6, d_out[k] };
     const float *ns = (const float *)me.lv[0][1].p, *hist = q->moments ? nullptr : (const float *)me.lv[0][2].p;
+    if (q->plain()) return bcd_hip_denoise(ctx, lay[0].d_colors, ns, hist, lay[0].d_covariances, q->W, q->H, q->D, q->S, &q->prm, d_out[0]);
     if (q->F) {
         const bcd_hip_guide g = { (const float *)me.guide[0][0].p, q->fvar ? (const float *)me.guide[0][1].p : nullptr, q->F, q->floors, q->ftau };
         return bcd_hip_denoise_guided(ctx, ns, hist, q->W, q->H, q->D, q->S, &q->prm, q->var_floor, lay, q->L, &g, nullptr);
@@ -337,14 +232,15 @@ int pop_single(bcd_hip_sequence *q, const SeqSlot &me, float *const *d_out)
     return bcd_hip_denoise_layers(ctx, ns, hist, q->W, q->H, q->D, q->S, &q->prm, lay, q->L);
 }
 
-// the scales of a pop in a mode, coarse to fine: the context carries the mode as it does inside the matching frame call (the moment selection, the guide's
-// channels, floors and threshold) while they run
-int pop_scales_mode(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, float *const *d_out)
+// the scales of a pop, coarse to fine: the context carries the mode as it does inside the matching frame call (the moment selection, the guide's channels,
+// floors and threshold) while they run.  A sequence in a mode reports its layers as the layered frame call does; one of bcd_hip_sequence_create, like
+// bcd_hip_denoise_temporal, leaves ctx->layer_spectral and ctx->layer_count alone
+int pop_scales(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, float *const *d_out)
 {
     bcd_hip_ctx *ctx = q->ctx;
     const int L = q->L, S = q->S;
+    const bool layered = q->layered(), report_layers = !q->plain();
     auto &tp = ctx->temporal;
-    hipStream_t st = ctx->main.stream;
     struct ModeOn {
         bcd_hip_ctx *c;
         ModeOn(bcd_hip_ctx *ctx, const bcd_hip_sequence *q) : c(ctx)
@@ -360,35 +256,28 @@ int pop_scales_mode(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, 
         ~ModeOn() { c->moments.on = false; }
     } mode_on(ctx, q);
     const int64_t passes = tp.guide_cross_passes;
-    memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
-    ctx->layer_count = 0;
+    if (report_layers) {
+        memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
+        ctx->layer_count = 0;
+    }
     for (int s = 1; s < S; ++s) RCCHK(seq_ensure(q, q->out[s], (size_t)L * q->ws[s] * q->hs[s] * 3 * sizeof(float)));
-    float *outs[MAX_SCALES][BCD_MAX_LAYERS];
-    for (int s = 0; s < S; ++s)
-        for (int k = 0; k < L; ++k) outs[s][k] = s == 0 ? d_out[k] : (float *)q->out[s].p + (size_t)k * q->ws[s] * q->hs[s] * 3;
+    LayerView outs[MAX_SCALES];
+    for (int s = 0; s < S; ++s) {
+        outs[s].n = L;
+        for (int k = 0; k < L; ++k) outs[s].out[k] = s == 0 ? d_out[k] : (float *)q->out[s].p + (size_t)k * q->ws[s] * q->hs[s] * 3;
+    }
     int rc = BCD_HIP_OK;
-    for (int s = S - 1; s >= 0 && rc == BCD_HIP_OK; --s) {
-        if (!q->layered()) { // one layer of histograms with the gate: the estimate and the merge of bcd_hip_denoise_temporal
-            rc = pop_scale(q, t, nbs, nn, s, outs[s][0]);
-            if (rc == BCD_HIP_OK && s < S - 1) rc = bcd_hip_merge(ctx, outs[s][0], q->ws[s], q->hs[s], outs[s + 1][0], 3);
-            continue;
-        }
-        rc = pop_scale_layers(q, t, nbs, nn, s, outs[s]);
+    for (int s = S - 1; s >= 0 && rc == BCD_HIP_OK; --s) { // merged as in the matching frame call: the layers in one pair of launches, one layer of histograms by bcd_hip_merge
+        rc = pop_scale(q, t, nbs, nn, s, outs[s]);
         if (rc != BCD_HIP_OK || s == S - 1) continue;
-        // the merge is mergeOutputs, one pair of launches for all layers (as in layers_run)
-        const int w2 = q->ws[s] / 2, h2 = q->hs[s] / 2;
-        const size_t slice = (size_t)w2 * h2 * 3;
-        RCCHK(ensure(ctx, tp.lay_tmp_lo, (size_t)L * slice * sizeof(float)));
-        BcdLayerTable tb = {};
-        for (int k = 0; k < L; ++k) { tb.a[k] = outs[s][k]; tb.o[k] = (float *)tp.lay_tmp_lo.p + k * slice; }
-        HIPCHK(ctx, bcd_launch_layers_downscale_avg(tb, L, q->ws[s], q->hs[s], st));
-        for (int k = 0; k < L; ++k) { tb.a[k] = (const float *)tp.lay_tmp_lo.p + k * slice; tb.b[k] = outs[s + 1][k]; tb.o[k] = outs[s][k]; }
-        HIPCHK(ctx, bcd_launch_layers_merge(tb, L, w2, h2, q->ws[s], q->hs[s], st));
+        rc = layered ? merge_layers_on(ctx, ctx->main, tp.lay_tmp_lo, outs[s], q->ws[s], q->hs[s], outs[s + 1])
+                     : bcd_hip_merge(ctx, outs[s].out[0], q->ws[s], q->hs[s], outs[s + 1].out[0], 3);
     }
     q->feature_passes += tp.guide_cross_passes - passes;
     RCCHK(rc);
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (!q->layered()) for (int s = 0; s < S; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses; // (as the frame call of one layer reports it)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    if (!report_layers) return BCD_HIP_OK;
+    if (!layered) for (int s = 0; s < S; ++s) ctx->layer_spectral[s][0] = ctx->stats[s].spectral_inverses; // (as the frame call of one layer reports it)
     ctx->layer_count = L;
     return BCD_HIP_OK;
 }
@@ -402,21 +291,11 @@ int pop(bcd_hip_sequence *q, float *const *d_out, int64_t *frame_index)
     int nn = 0;
     for (int64_t f = std::max<int64_t>(0, t - q->R); f <= std::min(last, t + q->R); ++f) if (f != t) nbs[nn++] = f;
     SeqSlot &me = q->slot[t % q->N];
-    if (nn == 0 && !q->plain()) {
+    if (nn == 0) {
         RCCHK(pop_single(q, me, d_out));
-    } else if (nn == 0) { // a sequence of one frame: the plain call on the slot's copy
-        RCCHK(bcd_hip_denoise(ctx, (const float *)me.lv[0][0].p, (const float *)me.lv[0][1].p, (const float *)me.lv[0][2].p, (const float *)me.lv[0][3].p, q->W, q->H, q->D,
-                              q->S, &q->prm, d_out[0]));
     } else {
         DEVICE_GUARD(ctx);
-        if (!q->plain()) RCCHK(pop_scales_mode(q, t, nbs, nn, d_out));
-        for (int s = 1; q->plain() && s < q->S; ++s) RCCHK(seq_ensure(q, q->out[s], (size_t)q->ws[s] * q->hs[s] * 3 * sizeof(float)));
-        for (int s = q->S - 1; q->plain() && s >= 0; --s) { // coarse to fine, merged as in bcd_hip_denoise_temporal
-            float *out = s == 0 ? d_out[0] : (float *)q->out[s].p;
-            RCCHK(pop_scale(q, t, nbs, nn, s, out));
-            if (s < q->S - 1) RCCHK(bcd_hip_merge(ctx, out, q->ws[s], q->hs[s], (const float *)q->out[s + 1].p, 3));
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+        RCCHK(pop_scales(q, t, nbs, nn, d_out));
         for (int i = 0; i < nn; ++i) {
             const int64_t f = nbs[i];
             if (f > t) { me.pair_frame[f - t - 1] = t; ++q->computed; continue; }
@@ -429,6 +308,39 @@ int pop(bcd_hip_sequence *q, float *const *d_out, int64_t *frame_index)
     for (int i = 0; i < nn; ++i) q->last_nbs[i] = nbs[i];
     if (frame_index) *frame_index = t;
     ++q->popped;
+    return BCD_HIP_OK;
+}
+
+// what the two create calls share behind their own refusals of the mode: the refusals of the parameters, of the geometry and of the guide, then the sequence
+int create(bcd_hip_ctx *ctx, int W, int H, int D, int nb_scales, int radius, const bcd_hip_params *prm, const bcd_hip_sequence_mode &mode, bool by_mode, void **out)
+{
+    const int L = mode.nb_layers, F = mode.nb_features;
+    const bool moments = mode.moments == 1, fvar = mode.feature_variances == 1;
+    RCCHK(check_params(ctx, W, H, moments ? 1 : D, prm)); // ("Moments": no histogram, D is not looked at)
+    RCCHK(check_temporal_geometry(ctx, W, H, nb_scales, prm, true, &radius));
+    if (F > 0) { // what bcd_hip_denoise_temporal_guided refuses of a guide (the images come with the frames: any address stands for them here)
+        static const float present = 0.f;
+        const bcd_hip_guide g = { &present, fvar ? &present : nullptr, F, mode.feature_floors, mode.feature_threshold };
+        if ((int64_t)W * H >= (1ll << 31) / BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "image too large for 32-bit DeepImage indices");
+        RCCHK(check_guide(ctx, &g, prm->search_radius));
+        if (bcd_pairdist_guide_cross_band(F, fvar, prm->search_radius) < 1) {
+            set_err(ctx, "the cross feature distance kernel cannot be launched for this number of channels and search radius (LDS)");
+            return BCD_HIP_EUNSUPPORTED;
+        }
+    }
+    bcd_hip_sequence *q = new (std::nothrow) bcd_hip_sequence;
+    if (!q) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
+    q->ctx = ctx;
+    q->W = W; q->H = H; q->D = moments ? 0 : D; q->S = nb_scales; q->R = radius; q->N = 2 * radius + 1;
+    q->prm = *prm;
+    for (int s = 0; s < MAX_SCALES; ++s) { q->ws[s] = s ? q->ws[s - 1] / 2 : W; q->hs[s] = s ? q->hs[s - 1] / 2 : H; }
+    q->by_mode = by_mode;
+    q->L = L; q->F = F; q->moments = moments; q->fvar = fvar;
+    q->var_floor = moments ? mode.var_floor : 0.f;
+    for (int k = 0; k < F; ++k) q->floors[k] = mode.feature_floors[k];
+    q->ftau = F ? mode.feature_threshold : 0.f;
+    forget(q);
+    *out = q;
     return BCD_HIP_OK;
 }
 
@@ -468,36 +380,18 @@ int bcd_hip_sequence_create(bcd_hip_ctx *ctx, int W, int H, int D, int nb_scales
     if (!ctx) return BCD_HIP_EINVAL;
     if (!out) return bad(ctx, "null handle pointer");
     *out = nullptr;
-    RCCHK(check_params(ctx, W, H, D, prm));
-    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
-    if (radius < 1 || radius > SEQ_MAX_RADIUS) return bad(ctx, "the temporal radius of a sequence must be 1 or 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS)");
-    if (prm->patch_radius != 1 || prm->search_radius != 6) {
-        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
-        return BCD_HIP_EUNSUPPORTED;
-    }
-    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
-        ws /= 2; hs /= 2;
-        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
-    }
-    bcd_hip_sequence *q = new (std::nothrow) bcd_hip_sequence;
-    if (!q) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
-    q->ctx = ctx;
-    q->W = W; q->H = H; q->D = D; q->S = nb_scales; q->R = radius; q->N = 2 * radius + 1;
-    q->prm = *prm;
-    for (int s = 0; s < MAX_SCALES; ++s) { q->ws[s] = s ? q->ws[s - 1] / 2 : W; q->hs[s] = s ? q->hs[s - 1] / 2 : H; }
-    forget(q);
-    *out = q;
-    return BCD_HIP_OK;
+    const bcd_hip_sequence_mode one_histogram_layer = { 1, 0, 0.f, 0, 0, nullptr, 0.f, nullptr };
+    return create(ctx, W, H, D, nb_scales, radius, prm, one_histogram_layer, false, out);
 }
 
 int bcd_hip_sequence_push(void *seq, const float *d_colors, const float *d_nsamples, const float *d_histograms, const float *d_covariances)
 {
-    return push((bcd_hip_sequence *)seq, d_colors, d_nsamples, d_histograms, d_covariances, hipMemcpyDeviceToDevice);
+    return push_images((bcd_hip_sequence *)seq, d_colors, d_nsamples, d_histograms, d_covariances, hipMemcpyDeviceToDevice);
 }
 
 int bcd_hip_sequence_push_host(void *seq, const float *h_colors, const float *h_nsamples, const float *h_histograms, const float *h_covariances)
 {
-    return push((bcd_hip_sequence *)seq, h_colors, h_nsamples, h_histograms, h_covariances, hipMemcpyHostToDevice);
+    return push_images((bcd_hip_sequence *)seq, h_colors, h_nsamples, h_histograms, h_covariances, hipMemcpyHostToDevice);
 }
 
 int bcd_hip_sequence_end(void *seq)
@@ -562,51 +456,12 @@ int bcd_hip_sequence_create_mode(bcd_hip_ctx *ctx, int W, int H, int D, int nb_s
     const bool moments = mode->moments == 1, fvar = mode->feature_variances == 1;
     if (moments && (!(mode->var_floor >= 0.f) || !std::isfinite(mode->var_floor))) return bad(ctx, "the variance floor must be finite and not negative");
     if (F == 0 && fvar) return bad(ctx, "feature variances without feature channels");
-    if (L == 1 && !moments && F == 0) { // today's sequence, on today's path
-        RCCHK(bcd_hip_sequence_create(ctx, W, H, D, nb_scales, radius, prm, out));
-        ((bcd_hip_sequence *)*out)->by_mode = true;
-        return BCD_HIP_OK;
-    }
-    RCCHK(check_params(ctx, W, H, moments ? 1 : D, prm)); // ("Moments": no histogram, D is not looked at)
-    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
-    if (radius < 1 || radius > SEQ_MAX_RADIUS) return bad(ctx, "the temporal radius of a sequence must be 1 or 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS)");
-    if (prm->patch_radius != 1 || prm->search_radius != 6) {
-        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
-        return BCD_HIP_EUNSUPPORTED;
-    }
-    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
-        ws /= 2; hs /= 2;
-        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
-    }
-    if (F > 0) { // what bcd_hip_denoise_temporal_guided refuses of a guide (the images come with the frames: any address stands for them here)
-        static const float present = 0.f;
-        const bcd_hip_guide g = { &present, fvar ? &present : nullptr, F, mode->feature_floors, mode->feature_threshold };
-        if ((int64_t)W * H >= (1ll << 31) / BCD_HIP_GUIDE_MAX_CHANNELS) return bad(ctx, "image too large for 32-bit DeepImage indices");
-        RCCHK(check_guide(ctx, &g, prm->search_radius));
-        if (bcd_pairdist_guide_cross_band(F, fvar, prm->search_radius) < 1) {
-            set_err(ctx, "the cross feature distance kernel cannot be launched for this number of channels and search radius (LDS)");
-            return BCD_HIP_EUNSUPPORTED;
-        }
-    }
-    bcd_hip_sequence *q = new (std::nothrow) bcd_hip_sequence;
-    if (!q) { set_err(ctx, "out of host memory"); return BCD_HIP_ENOMEM; }
-    q->ctx = ctx;
-    q->W = W; q->H = H; q->D = moments ? 0 : D; q->S = nb_scales; q->R = radius; q->N = 2 * radius + 1;
-    q->prm = *prm;
-    for (int s = 0; s < MAX_SCALES; ++s) { q->ws[s] = s ? q->ws[s - 1] / 2 : W; q->hs[s] = s ? q->hs[s - 1] / 2 : H; }
-    q->by_mode = true;
-    q->L = L; q->F = F; q->moments = moments; q->fvar = fvar;
-    q->var_floor = moments ? mode->var_floor : 0.f;
-    for (int k = 0; k < F; ++k) q->floors[k] = mode->feature_floors[k];
-    q->ftau = F ? mode->feature_threshold : 0.f;
-    forget(q);
-    *out = q;
-    return BCD_HIP_OK;
+    return create(ctx, W, H, D, nb_scales, radius, prm, *mode, true, out);
 }
 
-int bcd_hip_sequence_push_frame(void *seq, const bcd_hip_sequence_frame *frame) { return push_frame((bcd_hip_sequence *)seq, frame, hipMemcpyDeviceToDevice); }
+int bcd_hip_sequence_push_frame(void *seq, const bcd_hip_sequence_frame *frame) { return push_mode_frame((bcd_hip_sequence *)seq, frame, hipMemcpyDeviceToDevice); }
 
-int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *frame) { return push_frame((bcd_hip_sequence *)seq, frame, hipMemcpyHostToDevice); }
+int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *frame) { return push_mode_frame((bcd_hip_sequence *)seq, frame, hipMemcpyHostToDevice); }
 
 static int check_pop_layers(bcd_hip_sequence *q, float *const *outs, int nb_layers)
 {
@@ -713,17 +568,16 @@ void bcd_hip_sequence_destroy(void *seq)
     if (!q) return;
     {
         DeviceGuard guard(q->ctx);
-        auto drop = [](DevBuf &b) { if (b.p) (void)hipFree(b.p); };
         for (SeqSlot &s : q->slot) {
-            for (auto &level : s.lv) for (DevBuf &b : level) drop(b);
-            for (DevBuf &b : s.pixcov) drop(b);
-            for (auto &level : s.guide) for (DevBuf &b : level) drop(b);
-            for (auto &d : s.pair) for (DevBuf &b : d) drop(b);
+            free_bufs(s.lv, sizeof s.lv);
+            free_bufs(s.pixcov, sizeof s.pixcov);
+            free_bufs(s.guide, sizeof s.guide);
+            free_bufs(s.pair, sizeof s.pair);
         }
-        for (DevBuf &b : q->out) drop(b);
-        for (DevBuf &b : q->self) drop(b);
-        for (auto &l : q->low) for (DevBuf &b : l) drop(b);
-        drop(q->host_out);
+        free_bufs(q->out, sizeof q->out);
+        free_bufs(q->self, sizeof q->self);
+        free_bufs(q->low, sizeof q->low);
+        free_bufs(&q->host_out, sizeof q->host_out);
     }
     delete q;
 }

@@ -10,9 +10,11 @@
 // The cross-frame selection from means and covariances (section 16, "Moments") is temporal_select's moments mode; its stages
 // bcd_hip_similarity_masks_moments_cross and bcd_hip_window_distances_moments_cross are here, the kernels in k_similarity_moments_cross.hip, the frame calls
 // bcd_hip_denoise_temporal_moments[_host] in bcd_temporal_layers.hip.
-// What the layered calls (bcd_temporal_layers.hip) share with the frame calls is defined here and declared in bcd_ctx.h: the selection stage of a scale
-// (temporal_select) and its stats tail (temporal_stats_tail), the lists and the chain of full estimates of the estimate stage (temporal_lists,
-// temporal_full_chain), the motion set-up of a neighbour (temporal_warp_neighbour).
+// What the frame calls, the layered calls (bcd_temporal_layers.hip) and the pops and pushes of a sequence (bcd_sequence.hip) share is defined here and
+// declared in bcd_ctx.h: the one scale stage (temporal_scale: temporal_select, the estimate of either kind, the finalisation, temporal_stats_tail), the one
+// pyramid level of a frame (temporal_build_level), the geometry refusals of a call with neighbour frames (check_temporal_geometry), the lists and the chain of
+// full estimates of the estimate stage (temporal_lists, temporal_full_chain), the motion set-up of a neighbour (temporal_warp_neighbour).  The drivers --
+// temporal_run here, layers_run, the pop of a sequence -- fill the tables of temporal_scale and merge the scales.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -25,29 +27,38 @@ static_assert(BCD_MAX_NEIGHBOURS == BCD_HIP_MAX_NEIGHBOURS, "the frame table of 
 
 namespace {
 
-// the T / C planes of every displacement between the frame and one neighbour, in the main workspace (whose own planes they overwrite)
-int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b)
+// what the three kinds of cross planes share ahead of their kernel: room for the T / C planes of every displacement in the main workspace's plane buffers
+// (whose own planes they overwrite) and, for a kernel that is timed like the other distance kernels (bcd_hip_kernel_time), the event pair with its first
+// event recorded.  -> *e1 (null: untimed, or the pool is used up), which the caller records behind the kernel
+int cross_planes_begin(bcd_hip_ctx *ctx, Work &wk, int W, int H, int b, bool timed, hipEvent_t *e1)
 {
     const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
     RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
     RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
     wk.planes.ready = false; // (the workspace's planes are overwritten)
+    hipEvent_t e0 = nullptr;
+    *e1 = nullptr;
+    if (timed) RCCHK(distance_timing_events(ctx, wk, &e0, e1));
+    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    return BCD_HIP_OK;
+}
+
+// the T / C planes of every displacement between the frame and one neighbour
+int temporal_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_hist, const float *d_ns, const float *d_hist_nb, const float *d_ns_nb, int W, int H, int D, int b)
+{
+    hipEvent_t e1;
+    RCCHK(cross_planes_begin(ctx, wk, W, H, b, false, &e1));
     HIPCHK(ctx, bcd_launch_pairdist_cross(d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
     return BCD_HIP_OK;
 }
 
 // "Features": the T / C planes of every displacement between the feature images of the frame and of one neighbour, in the same plane buffers -- the histogram
-// planes of that neighbour are consumed by then.  The kernel is timed like the other distance kernels (bcd_hip_kernel_time)
+// planes of that neighbour are consumed by then.  The kernel is timed
 int temporal_guide_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_feat, const float *d_var, const float *d_feat_nb, const float *d_var_nb, int F,
                                 const float *floors, int W, int H, int b)
 {
-    const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
-    RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
-    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
-    wk.planes.ready = false; // (the workspace's planes are overwritten)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    RCCHK(distance_timing_events(ctx, wk, &e0, &e1));
-    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    hipEvent_t e1;
+    RCCHK(cross_planes_begin(ctx, wk, W, H, b, true, &e1));
     HIPCHK(ctx, bcd_launch_pairdist_guide_cross(d_feat, d_var, d_feat_nb, d_var_nb, F, floors, W, H, b, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
     if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
     return BCD_HIP_OK;
@@ -80,17 +91,11 @@ int moments_cross_form(int form, int w, int b)
 }
 
 // "Moments": the T / C planes of every displacement between the guide layers of the frame and of one neighbour, in the same plane buffers; the kernel is timed
-// like the other distance kernels (bcd_hip_kernel_time)
 int temporal_moments_cross_planes(bcd_hip_ctx *ctx, Work &wk, const float *d_col, const float *d_pixcov, const float *d_col_nb, const float *d_pixcov_nb, int W, int H,
                                   int b, float var_floor)
 {
-    const size_t npix = (size_t)W * H, n = (size_t)(2 * b + 1) * (2 * b + 1);
-    RCCHK(ensure(ctx, wk.T, npix * n * sizeof(float)));
-    RCCHK(ensure(ctx, wk.Cn, count_plane_bytes(npix, (int)n)));
-    wk.planes.ready = false; // (the workspace's planes are overwritten)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    RCCHK(distance_timing_events(ctx, wk, &e0, &e1));
-    if (e0) HIPCHK(ctx, hipEventRecord(e0, wk.stream));
+    hipEvent_t e1;
+    RCCHK(cross_planes_begin(ctx, wk, W, H, b, true, &e1));
     HIPCHK(ctx, bcd_launch_pairdist_moments_cross(d_col, d_pixcov, d_col_nb, d_pixcov_nb, W, H, b, var_floor, (float *)wk.T.p, (uint8_t *)wk.Cn.p, wk.stream));
     if (e1) HIPCHK(ctx, hipEventRecord(e1, wk.stream));
     return BCD_HIP_OK;
@@ -205,6 +210,17 @@ int check_cross_stage(bcd_hip_ctx *ctx, int W, int H, int D, int w, int b)
     return check_params(ctx, W, H, D, &p);
 }
 
+// the tail of the three bcd_hip_window_distances_*_cross calls, behind the planes on wk.stream: the window of one main pixel, through ctx->tmp_lo to the host
+int window_distances_tail(bcd_hip_ctx *ctx, Work &wk, int W, int H, int w, int b, int line, int col, float *h_out)
+{
+    const int n = (2 * b + 1) * (2 * b + 1);
+    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
+    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    return BCD_HIP_OK;
+}
+
 } // namespace
 
 // The estimate stage over the members of several frames (patch radius 1, search radius 6): the lists, the fallback kernel over all frames, the wait for the
@@ -280,13 +296,8 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_hist, const 
     if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
     DEVICE_GUARD(ctx);
     Work &wk = ctx->main;
-    const int n = (2 * b + 1) * (2 * b + 1);
-    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
     RCCHK(temporal_cross_planes(ctx, wk, d_hist, d_ns, d_hist_nb, d_ns_nb, W, H, D, b));
-    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    return BCD_HIP_OK;
+    return window_distances_tail(ctx, wk, W, H, w, b, line, col, h_out);
 }
 
 } // extern "C"
@@ -300,26 +311,28 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_hist, const 
 void temporal_free(bcd_hip_ctx *ctx)
 {
     auto &t = ctx->temporal;
-    for (auto &frame : t.pyr) for (auto &level : frame) for (DevBuf &b : level) if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : t.out) if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : t.pixcov) if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : t.mask) if (b.p) (void)hipFree(b.p);
-    if (t.count_nb.p) (void)hipFree(t.count_nb.p);
-    for (auto &frame : t.host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
-    if (t.host_out.p) (void)hipFree(t.host_out.p);
-    for (auto &frame : t.lay_pyr) for (auto &level : frame) for (DevBuf &b : level) if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : t.lay_out) if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : t.lay_pixcov) if (b.p) (void)hipFree(b.p);
-    for (DevBuf *b : { &t.lay_sum, &t.lay_tmp_lo, &t.lay_host_out }) if (b->p) (void)hipFree(b->p);
-    for (auto &frame : t.lay_host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
-    for (auto &frame : t.warp) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
-    for (auto &frame : t.lay_warp) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
-    for (auto &frame : t.valid) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : t.motion_host) if (b.p) (void)hipFree(b.p);
-    if (t.pvalid.p) (void)hipFree(t.pvalid.p);
-    for (auto &frame : t.guide_pyr) for (auto &level : frame) for (DevBuf &b : level) if (b.p) (void)hipFree(b.p);
-    for (auto &frame : t.guide_warp) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
-    for (auto &frame : t.guide_host) for (DevBuf &b : frame) if (b.p) (void)hipFree(b.p);
+    free_bufs(t.pyr, sizeof t.pyr);
+    free_bufs(t.out, sizeof t.out);
+    free_bufs(t.pixcov, sizeof t.pixcov);
+    free_bufs(t.mask, sizeof t.mask);
+    free_bufs(&t.count_nb, sizeof t.count_nb);
+    free_bufs(t.host, sizeof t.host);
+    free_bufs(&t.host_out, sizeof t.host_out);
+    free_bufs(t.lay_pyr, sizeof t.lay_pyr);
+    free_bufs(t.lay_out, sizeof t.lay_out);
+    free_bufs(t.lay_pixcov, sizeof t.lay_pixcov);
+    free_bufs(&t.lay_sum, sizeof t.lay_sum);
+    free_bufs(&t.lay_tmp_lo, sizeof t.lay_tmp_lo);
+    free_bufs(t.lay_host, sizeof t.lay_host);
+    free_bufs(&t.lay_host_out, sizeof t.lay_host_out);
+    free_bufs(t.warp, sizeof t.warp);
+    free_bufs(t.lay_warp, sizeof t.lay_warp);
+    free_bufs(t.valid, sizeof t.valid);
+    free_bufs(&t.pvalid, sizeof t.pvalid);
+    free_bufs(t.motion_host, sizeof t.motion_host);
+    free_bufs(t.guide_pyr, sizeof t.guide_pyr);
+    free_bufs(t.guide_warp, sizeof t.guide_warp);
+    free_bufs(t.guide_host, sizeof t.guide_host);
 }
 
 int temporal_select(bcd_hip_ctx *ctx, const TemporalSelFrame *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale,
@@ -398,41 +411,119 @@ void temporal_stats_tail(bcd_hip_ctx *ctx, int scale, const TemporalPath &path)
     }
 }
 
+int temporal_build_level(bcd_hip_ctx *ctx, const TemporalFrame &fine, const TemporalFrame &coarse, int L, bool layered, int W, int H, int D, hipStream_t st)
+{
+    if (!layered) HIPCHK(ctx, bcd_launch_downscale(1, fine.col[0], W, H, 3, const_cast<float *>(coarse.col[0]), st));
+    HIPCHK(ctx, bcd_launch_downscale(0, fine.sel.ns, W, H, 1, const_cast<float *>(coarse.sel.ns), st));
+    if (fine.sel.hist) HIPCHK(ctx, bcd_launch_downscale(0, fine.sel.hist, W, H, D, const_cast<float *>(coarse.sel.hist), st));
+    if (!layered) {
+        HIPCHK(ctx, bcd_launch_downscale_cov(fine.cov[0], fine.sel.ns, W, H, const_cast<float *>(coarse.cov[0]), st));
+        return BCD_HIP_OK;
+    }
+    LayerView lf, lc;
+    lf.n = lc.n = L;
+    for (int k = 0; k < L; ++k) { lf.col[k] = fine.col[k]; lf.cov[k] = fine.cov[k]; lc.col[k] = coarse.col[k]; lc.cov[k] = coarse.cov[k]; }
+    return build_level_layers(ctx, lf, lc, fine.sel.ns, W, H, st);
+}
+
 namespace {
 
-struct FrameLevel { const float *col, *ns, *hist, *cov; };
+constexpr int NF = BCD_MAX_NEIGHBOURS + 1, ML = BCD_MAX_LAYERS;
 
-// one scale: frames[0] the frame itself at this level
-// valid: per frame the validity bytes of this level (null: the frame is not warped) -- a warped neighbour's cross masks pass the gate
-int temporal_scale(bcd_hip_ctx *ctx, const FrameLevel *frames, int nf, int W, int H, int D, const bcd_hip_params *prm, int scale, float *d_out, const uint8_t *const *valid)
+// the estimate of one layer of histograms and its finalisation (the stage-3 event between them): bayes_temporal on the frames' first layers
+int scale_estimate(bcd_hip_ctx *ctx, Work &wk, const TemporalScale &sc, const uint32_t *const *mask, int W, int H, const bcd_hip_params *prm)
 {
-    Work &wk = ctx->main;
-    auto &tp = ctx->temporal;
-    const size_t npix = (size_t)W * H;
-    RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
-    TemporalSelFrame sel[BCD_MAX_NEIGHBOURS + 1];
-    for (int f = 0; f < nf; ++f) {
-        RCCHK(ensure(ctx, tp.pixcov[f], npix * 6 * sizeof(float)));
-        sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
-        temporal_guide_level(ctx, f, scale, &sel[f]);
-    }
-    TemporalPath path;
-    RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int {
-        for (int f = 0; f < nf; ++f) HIPCHK(ctx, bcd_launch_pixel_cov(frames[f].cov, frames[f].ns, (int64_t)npix, (float *)tp.pixcov[f].p, wk.stream));
-        return BCD_HIP_OK;
-    }, &path));
     BcdFrameTable t = {};
-    t.n = nf;
-    for (int f = 0; f < nf; ++f) { t.col[f] = frames[f].col; t.pixcov[f] = (const float *)tp.pixcov[f].p; t.mask[f] = temporal_mask(ctx, f); }
-    HIPCHK(ctx, hipMemsetAsync(wk.sum.p, 0, npix * 3 * sizeof(float), wk.stream));
-    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
-    RCCHK(bayes_temporal(ctx, wk, t, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, prm->search_radius, prm->min_eigen_value, (float *)wk.sum.p, (int32_t *)wk.cnt.p));
+    t.n = sc.nf;
+    for (int f = 0; f < sc.nf; ++f) { t.col[f] = sc.fr[f].col[0]; t.pixcov[f] = sc.fr[f].pixcov; t.mask[f] = mask[f]; }
+    RCCHK(bayes_temporal(ctx, wk, t, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, prm->search_radius, prm->min_eigen_value, sc.sum, (int32_t *)wk.cnt.p));
     if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
-    HIPCHK(ctx, bcd_launch_finalize((const float *)wk.sum.p, (const int32_t *)wk.cnt.p, (int64_t)npix, d_out, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    temporal_stats_tail(ctx, scale, path);
+    HIPCHK(ctx, bcd_launch_finalize(sc.sum, (const int32_t *)wk.cnt.p, (int64_t)W * H, sc.out[0], wk.stream));
     return BCD_HIP_OK;
 }
+
+// the layered estimate and its finalisation: bayes_temporal_layers on every layer of the frames; redo[k]: the items of layer k that took the redo list
+int scale_estimate_layers(bcd_hip_ctx *ctx, Work &wk, const TemporalScale &sc, const uint32_t *const *mask, int W, int H, const bcd_hip_params *prm, int32_t *redo)
+{
+    const int L = sc.L;
+    const size_t npix = (size_t)W * H;
+    LayerFrames lf;
+    lf.nf = sc.nf; lf.L = L;
+    float *sum[ML];
+    for (int k = 0; k < L; ++k) sum[k] = sc.sum + (size_t)k * npix * 3;
+    for (int f = 0; f < sc.nf; ++f) {
+        for (int k = 0; k < L; ++k) { lf.col[f][k] = sc.fr[f].col[k]; lf.pixcov[f][k] = sc.fr[f].pixcov + (size_t)k * npix * 6; }
+        lf.mask[f] = mask[f];
+    }
+    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, prm->search_radius, prm->min_eigen_value, sum, (int32_t *)wk.cnt.p,
+                                redo));
+    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
+    BcdLayerTable t = {};
+    for (int k = 0; k < L; ++k) { t.a[k] = sum[k]; t.o[k] = sc.out[k]; }
+    HIPCHK(ctx, bcd_launch_layers_finalize(t, L, (const int32_t *)wk.cnt.p, (int64_t)npix, wk.stream));
+    return BCD_HIP_OK;
+}
+
+} // namespace
+
+// One scale of every call with neighbour frames (the frame calls, the layered calls, the pops of a sequence), sc.fr[0] the frame itself at this level: the
+// selection stage (temporal_select), the cleared accumulators, the estimate of the kind sc.layered names, the finalisation, the stats tail.  Where the
+// per-pixel covariances come from, where a neighbour's masks go and whether the in-frame masks are copied out is all in `sc`
+int temporal_scale(bcd_hip_ctx *ctx, const TemporalScale &sc, int W, int H, int D, const bcd_hip_params *prm, int scale)
+{
+    Work &wk = ctx->main;
+    const int nf = sc.nf, L = sc.L;
+    const size_t npix = (size_t)W * H, sum_bytes = npix * 3 * sizeof(float);
+    TemporalSelFrame sel[NF];
+    for (int f = 0; f < nf; ++f) {
+        sel[f] = sc.fr[f].sel;
+        if (ctx->moments.on) { sel[f].col = sc.fr[f].col[0]; sel[f].pixcov = sc.fr[f].pixcov; } // ("Moments": the guide layer is layer 0)
+    }
+    TemporalPath path;
+    // the per-pixel covariances of every frame unless the pushes of a sequence computed them; a layered estimate clears its sums here: in the one launch
+    // that produces the covariances of a frame's layers (so once per frame: there is no layered launcher that leaves the sums alone), or by hipMemsetAsync
+    RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int {
+        if (sc.pixcov_ready && sc.layered) HIPCHK(ctx, hipMemsetAsync(sc.sum, 0, L * sum_bytes, wk.stream));
+        for (int f = 0; f < nf && !sc.pixcov_ready; ++f) {
+            const TemporalFrame &fr = sc.fr[f];
+            if (!sc.layered) { HIPCHK(ctx, bcd_launch_pixel_cov(fr.cov[0], fr.sel.ns, (int64_t)npix, fr.pixcov, wk.stream)); continue; }
+            BcdLayerTable t = {};
+            for (int k = 0; k < L; ++k) t.a[k] = fr.cov[k];
+            HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, L, fr.sel.ns, (int64_t)npix, fr.pixcov, sc.sum, wk.stream));
+        }
+        return BCD_HIP_OK;
+    }, &path));
+    const size_t words = ((size_t)(2 * prm->search_radius + 1) * (2 * prm->search_radius + 1) + 31) / 32;
+    if (sc.self_copy) HIPCHK(ctx, hipMemcpyAsync(sc.self_copy, wk.mask.p, npix * words * sizeof(uint32_t), hipMemcpyDeviceToDevice, wk.stream));
+    const uint32_t *mask[NF]; // what temporal_select left: the in-frame masks, and per neighbour the caller's buffer or the context's
+    for (int f = 0; f < nf; ++f) mask[f] = f == 0 ? (const uint32_t *)wk.mask.p : sel[f].mask_dst ? sel[f].mask_dst : (const uint32_t *)ctx->temporal.mask[f].p;
+    if (!sc.layered) HIPCHK(ctx, hipMemsetAsync(sc.sum, 0, sum_bytes, wk.stream));
+    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
+    int32_t redo[ML] = {};
+    RCCHK(sc.layered ? scale_estimate_layers(ctx, wk, sc, mask, W, H, prm, redo) : scale_estimate(ctx, wk, sc, mask, W, H, prm));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
+    temporal_stats_tail(ctx, scale, path);
+    for (int k = 0; sc.layered && k < L; ++k) ctx->layer_spectral[scale][k] = redo[k];
+    return BCD_HIP_OK;
+}
+
+int check_temporal_geometry(bcd_hip_ctx *ctx, int W, int H, int nb_scales, const bcd_hip_params *prm, bool neighbours, const int *sequence_radius)
+{
+    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
+    if (sequence_radius && (*sequence_radius < 1 || *sequence_radius > BCD_HIP_MAX_NEIGHBOURS / 2))
+        return bad(ctx, "the temporal radius of a sequence must be 1 or 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS)");
+    if (neighbours && (prm->patch_radius != 1 || prm->search_radius != 6)) {
+        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
+        return BCD_HIP_EUNSUPPORTED;
+    }
+    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
+        ws /= 2; hs /= 2;
+        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
+    }
+    return BCD_HIP_OK;
+}
+
+namespace {
 
 // the refusals of the two frame calls, before any device work
 int check_temporal_call(bcd_hip_ctx *ctx, const void *col, const void *ns, const void *hist, const void *cov, const bcd_hip_frame *nb, int n, int W, int H, int D,
@@ -446,15 +537,7 @@ int check_temporal_call(bcd_hip_ctx *ctx, const void *col, const void *ns, const
         if (nb[f].reserved) return bad(ctx, "the reserved pointer of a neighbour frame must be NULL");
     }
     RCCHK(check_params(ctx, W, H, D, prm));
-    if (nb_scales < 1 || nb_scales > MAX_SCALES) return bad(ctx, "bad number of scales");
-    if (n > 0 && (prm->patch_radius != 1 || prm->search_radius != 6)) {
-        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
-        return BCD_HIP_EUNSUPPORTED;
-    }
-    for (int s = 1, ws = W, hs = H; s < nb_scales; ++s) {
-        ws /= 2; hs /= 2;
-        if (ws < 2 * prm->patch_radius + 1 || hs < 2 * prm->patch_radius + 1) return bad(ctx, "too many scales for this image size");
-    }
+    RCCHK(check_temporal_geometry(ctx, W, H, nb_scales, prm, n > 0, nullptr));
     const size_t npix = (size_t)W * H, no = npix * 3 * sizeof(float);
     if (overlaps_frame_images(out, no, col, ns, hist, cov, npix, D)) return bad(ctx, "the output overlaps an input image");
     for (int f = 0; f < n; ++f)
@@ -471,20 +554,26 @@ int temporal_run(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsample
     DEVICE_GUARD(ctx);
     const int nf = nb_neighbours + 1, S = nb_scales;
     auto &tp = ctx->temporal;
+    Work &wk = ctx->main;
     // ---- the pyramids (MultiscaleDenoiser.cpp:41-53) of every frame: level s has the dimensions of level s - 1 halved
-    std::vector<FrameLevel> lv((size_t)S * nf);
+    std::vector<TemporalFrame> lv((size_t)S * nf, TemporalFrame());
+    auto level = [](const float *col, const float *ns, const float *hist, const float *cov) {
+        TemporalFrame l = {};
+        l.sel.ns = ns; l.sel.hist = hist; l.col[0] = col; l.cov[0] = cov;
+        return l;
+    };
     int ws[MAX_SCALES], hs[MAX_SCALES];
     ws[0] = W; hs[0] = H;
-    lv[0] = { d_colors, d_nsamples, d_histograms, d_covariances };
+    lv[0] = level(d_colors, d_nsamples, d_histograms, d_covariances);
     std::vector<const uint8_t *> valid((size_t)S * nf, nullptr);
     for (int f = 1; f < nf; ++f) {
         const bcd_hip_frame &nb = neighbours[f - 1];
-        lv[f] = { nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances };
+        lv[f] = level(nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances);
         if (!motion || !motion[f - 1]) continue;
         // the neighbour reprojected into the frame's pixel grid, at full resolution; its pyramid is built from the warped images
         const float *wp[4];
         RCCHK(temporal_warp_neighbour(ctx, f, nf, nb.d_colors, nb.d_nsamples, nb.d_histograms, nb.d_covariances, motion[f - 1], W, H, D, S, nullptr, 0, valid.data(), wp));
-        lv[f] = { wp[0], wp[1], wp[2], wp[3] };
+        lv[f] = level(wp[0], wp[1], wp[2], wp[3]);
     }
     for (int s = 1; s < S; ++s) {
         ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
@@ -496,21 +585,28 @@ int temporal_run(bcd_hip_ctx *ctx, const float *d_colors, const float *d_nsample
             RCCHK(ensure(ctx, l[1], np * sizeof(float)));
             RCCHK(ensure(ctx, l[2], np * D * sizeof(float)));
             RCCHK(ensure(ctx, l[3], np * 6 * sizeof(float)));
-            const FrameLevel &fine = lv[(size_t)(s - 1) * nf + f];
-            hipStream_t st = ctx->main.stream;
-            HIPCHK(ctx, bcd_launch_downscale(1, fine.col, ws[s - 1], hs[s - 1], 3, (float *)l[0].p, st));
-            HIPCHK(ctx, bcd_launch_downscale(0, fine.ns, ws[s - 1], hs[s - 1], 1, (float *)l[1].p, st));
-            HIPCHK(ctx, bcd_launch_downscale(0, fine.hist, ws[s - 1], hs[s - 1], D, (float *)l[2].p, st));
-            HIPCHK(ctx, bcd_launch_downscale_cov(fine.cov, fine.ns, ws[s - 1], hs[s - 1], (float *)l[3].p, st));
-            lv[(size_t)s * nf + f] = { (const float *)l[0].p, (const float *)l[1].p, (const float *)l[2].p, (const float *)l[3].p };
+            lv[(size_t)s * nf + f] = level((const float *)l[0].p, (const float *)l[1].p, (const float *)l[2].p, (const float *)l[3].p);
+            RCCHK(temporal_build_level(ctx, lv[(size_t)(s - 1) * nf + f], lv[(size_t)s * nf + f], 1, false, ws[s - 1], hs[s - 1], D, wk.stream));
         }
     }
     for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs (MultiscaleDenoiser.cpp:453-466), as in bcd_hip_denoise
-        float *out = s == 0 ? d_out : (float *)tp.out[s].p;
-        RCCHK(temporal_scale(ctx, &lv[(size_t)s * nf], nf, ws[s], hs[s], D, prm, s, out, &valid[(size_t)s * nf]));
-        if (s < S - 1) RCCHK(bcd_hip_merge(ctx, out, ws[s], hs[s], (const float *)tp.out[s + 1].p, 3));
+        const size_t npix = (size_t)ws[s] * hs[s];
+        TemporalScale sc;
+        sc.nf = nf;
+        RCCHK(ensure(ctx, wk.sum, npix * 3 * sizeof(float)));
+        sc.sum = (float *)wk.sum.p;
+        sc.out[0] = s == 0 ? d_out : (float *)tp.out[s].p;
+        for (int f = 0; f < nf; ++f) {
+            TemporalFrame &fr = sc.fr[f] = lv[(size_t)s * nf + f];
+            RCCHK(ensure(ctx, tp.pixcov[f], npix * 6 * sizeof(float)));
+            fr.pixcov = (float *)tp.pixcov[f].p;
+            fr.sel.valid = valid[(size_t)s * nf + f]; // (null: the frame is not warped -- a warped neighbour's cross masks pass the gate)
+            temporal_guide_level(ctx, f, s, &fr.sel);
+        }
+        RCCHK(temporal_scale(ctx, sc, ws[s], hs[s], D, prm, s));
+        if (s < S - 1) RCCHK(bcd_hip_merge(ctx, sc.out[0], ws[s], hs[s], (const float *)tp.out[s + 1].p, 3));
     }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
     return BCD_HIP_OK;
 }
 
@@ -708,17 +804,14 @@ int temporal_guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const bcd_hip
             vv = var ? (const float *)gw[1].p : nullptr;
         }
         tp.guide.f[f][0] = feat; tp.guide.v[f][0] = vv;
-        for (int s = 1, ws = W, hs = H; s < nb_scales && s < MAX_SCALES; ++s, ws /= 2, hs /= 2) { // guide_begin's rule
+        for (int s = 1, ws = W, hs = H; s < nb_scales && s < MAX_SCALES; ++s, ws /= 2, hs /= 2) {
             const size_t np = (size_t)(ws / 2) * (hs / 2);
             DevBuf(&l)[2] = tp.guide_pyr[f][s];
             RCCHK(ensure(ctx, l[0], np * F * sizeof(float)));
-            HIPCHK(ctx, bcd_launch_downscale(1, tp.guide.f[f][s - 1], ws, hs, F, (float *)l[0].p, st));
+            if (var) RCCHK(ensure(ctx, l[1], np * F * sizeof(float)));
+            RCCHK(guide_build_level(ctx, tp.guide.f[f][s - 1], tp.guide.v[f][s - 1], ws, hs, F, (float *)l[0].p, (float *)l[1].p, st));
             tp.guide.f[f][s] = (const float *)l[0].p;
-            if (!var) continue;
-            RCCHK(ensure(ctx, l[1], np * F * sizeof(float)));
-            HIPCHK(ctx, bcd_launch_downscale(1, tp.guide.v[f][s - 1], ws, hs, F, (float *)l[1].p, st));
-            HIPCHK(ctx, bcd_launch_scale_inplace((float *)l[1].p, 0.25f, (int64_t)np * F, st));
-            tp.guide.v[f][s] = (const float *)l[1].p;
+            if (var) tp.guide.v[f][s] = (const float *)l[1].p;
         }
     }
     tp.guide.on = true;
@@ -768,13 +861,8 @@ int bcd_hip_window_distances_guide_cross(bcd_hip_ctx *ctx, const bcd_hip_guide *
     if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
     DEVICE_GUARD(ctx);
     Work &wk = ctx->main;
-    const int n = (2 * b + 1) * (2 * b + 1);
-    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
     RCCHK(temporal_guide_cross_planes(ctx, wk, guide->features, guide->variances, neighbour->features, neighbour->variances, guide->nb_channels, guide->floors, W, H, b));
-    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    return BCD_HIP_OK;
+    return window_distances_tail(ctx, wk, W, H, w, b, line, col, h_out);
 }
 
 // ---- "Moments": the stage calls of the cross-frame moment selection; what they accept is what bcd_hip_similarity_masks_moments accepts
@@ -812,13 +900,8 @@ int bcd_hip_window_distances_moments_cross(bcd_hip_ctx *ctx, const float *d_colo
     if (line < w || line > H - 1 - w || col < w || col > W - 1 - w) return bad(ctx, "not a main pixel");
     DEVICE_GUARD(ctx);
     Work &wk = ctx->main;
-    const int n = (2 * b + 1) * (2 * b + 1);
-    RCCHK(ensure(ctx, ctx->tmp_lo, n * sizeof(float)));
     RCCHK(temporal_moments_cross_planes(ctx, wk, d_colors, d_pixel_cov, d_colors_nb, d_pixel_cov_nb, W, H, b, var_floor));
-    HIPCHK(ctx, bcd_launch_window_distances_cross((const float *)wk.T.p, (const uint8_t *)wk.Cn.p, W, H, w, b, line, col, (float *)ctx->tmp_lo.p, wk.stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out, ctx->tmp_lo.p, n * sizeof(float), hipMemcpyDeviceToHost, wk.stream));
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    return BCD_HIP_OK;
+    return window_distances_tail(ctx, wk, W, H, w, b, line, col, h_out);
 }
 
 int bcd_hip_warp_features(bcd_hip_ctx *ctx, const bcd_hip_guide_images *in, int nb_channels, const float *d_motion, int W, int H, float *d_features_out,

@@ -1,7 +1,8 @@
 // bcd_temporal_layers.hip -- the colour layers of a frame denoised with similar patches from its neighbour frames ("Layers"):
-// bcd_hip_denoise_temporal_layers[_host] and the stage entry point bcd_hip_bayes_accumulate_temporal_layers.  The selection of a scale -- the in-frame set,
-// the cross sets, the total |S|, the marking, the lists -- reads sample counts and histograms only and is computed once, by the helpers the frame call uses
-// (temporal_select, temporal_lists; bcd_temporal.hip); the estimate stage runs per layer: one launch of k_bayes_weak_temporal_layers serves the fallback
+// bcd_hip_denoise_temporal_layers[_host] and the stage entry point bcd_hip_bayes_accumulate_temporal_layers.  layers_run builds the pyramids
+// (temporal_build_level) and fills the table of the scale stage every call with neighbour frames runs (temporal_scale; bcd_temporal.hip).  The selection of a
+// scale -- the in-frame set, the cross sets, the total |S|, the marking, the lists -- reads sample counts and histograms only and is computed once
+// (temporal_select, temporal_lists); the estimate stage (bayes_temporal_layers, here) runs per layer: one launch of k_bayes_weak_temporal_layers serves the fallback
 // pixels of every layer on the side stream, the chain of full estimates (temporal_full_chain: k_prepare27t, then the unchanged solver and finish kernels) runs
 // once per layer over the same lists, records and work queues.  The count image is filled once: by the first group of the fallback kernel and by the first
 // layer's finish kernels.
@@ -22,7 +23,7 @@
 
 namespace {
 
-constexpr int NF = BCD_MAX_NEIGHBOURS + 1, ML = BCD_MAX_LAYERS;
+constexpr int ML = BCD_MAX_LAYERS;
 
 // the part of bayes_temporal_layers behind the fork: the wait for the list lengths, then one chain of full estimates per layer -- records and work queues are
 // reused, the redo counter runs on and its total is copied out behind each layer.  The side stream is NOT joined here.
@@ -86,61 +87,6 @@ int bayes_temporal_layers(bcd_hip_ctx *ctx, Work &wk, const LayerFrames &lf, con
 
 namespace {
 
-// one frame at one pyramid level: its sample counts, histograms and the colours and covariances of its layers
-struct LevelFrame {
-    const float *ns, *hist;
-    const float *col[ML], *cov[ML];
-};
-
-// one scale, frames[0] the frame itself at this level: the shared selection stage (temporal_select), the estimate stage per layer, the shared stats tail
-// valid: per frame the validity bytes of this level (null: the frame is not warped)
-int temporal_layers_scale(bcd_hip_ctx *ctx, const LevelFrame *frames, int nf, int L, int W, int H, int D, const bcd_hip_params *prm, int scale, float *const *d_out,
-                          const uint8_t *const *valid)
-{
-    Work &wk = ctx->main;
-    auto &tp = ctx->temporal;
-    const size_t npix = (size_t)W * H;
-    RCCHK(ensure(ctx, tp.lay_sum, (size_t)L * npix * 3 * sizeof(float)));
-    TemporalSelFrame sel[NF];
-    for (int f = 0; f < nf; ++f) {
-        RCCHK(ensure(ctx, tp.lay_pixcov[f], (size_t)L * npix * 6 * sizeof(float)));
-        sel[f] = { frames[f].ns, frames[f].hist, valid[f] };
-        temporal_guide_level(ctx, f, scale, &sel[f]);
-        if (ctx->moments.on) { sel[f].col = frames[f].col[0]; sel[f].pixcov = (const float *)tp.lay_pixcov[f].p; } // ("Moments": the guide layer is layer 0)
-    }
-    TemporalPath path;
-    RCCHK(temporal_select(ctx, sel, nf, W, H, D, prm, scale, [&]() -> int { // per frame the per-pixel covariances of its layers: one launch; it also clears the layers' sums
-        for (int f = 0; f < nf; ++f) {
-            BcdLayerTable t = {};
-            for (int k = 0; k < L; ++k) t.a[k] = frames[f].cov[k];
-            HIPCHK(ctx, bcd_launch_layers_pixel_cov_clear(t, L, frames[f].ns, (int64_t)npix, (float *)tp.lay_pixcov[f].p, (float *)tp.lay_sum.p, wk.stream));
-        }
-        return BCD_HIP_OK;
-    }, &path));
-    LayerFrames lf;
-    lf.nf = nf; lf.L = L;
-    float *sum[ML];
-    for (int k = 0; k < L; ++k) sum[k] = (float *)tp.lay_sum.p + (size_t)k * npix * 3;
-    for (int f = 0; f < nf; ++f) {
-        for (int k = 0; k < L; ++k) { lf.col[f][k] = frames[f].col[k]; lf.pixcov[f][k] = (const float *)tp.lay_pixcov[f].p + (size_t)k * npix * 6; }
-        lf.mask[f] = temporal_mask(ctx, f);
-    }
-    HIPCHK(ctx, hipMemsetAsync(wk.cnt.p, 0, npix * sizeof(int32_t), wk.stream));
-    int32_t redo[ML] = {};
-    RCCHK(bayes_temporal_layers(ctx, wk, lf, (const int32_t *)wk.nsim.p, (const uint8_t *)wk.state.p, W, H, prm->search_radius, prm->min_eigen_value, sum, (int32_t *)wk.cnt.p,
-                                redo));
-    if (ctx->profiling) HIPCHK(ctx, hipEventRecord(wk.ev_stage[3], wk.stream));
-    {
-        BcdLayerTable t = {};
-        for (int k = 0; k < L; ++k) { t.a[k] = sum[k]; t.o[k] = d_out[k]; }
-        HIPCHK(ctx, bcd_launch_layers_finalize(t, L, (const int32_t *)wk.cnt.p, (int64_t)npix, wk.stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(wk.stream));
-    temporal_stats_tail(ctx, scale, path);
-    for (int k = 0; k < L; ++k) ctx->layer_spectral[scale][k] = redo[k];
-    return BCD_HIP_OK;
-}
-
 // the refusals of the two frame calls, before any device work
 // (no_hist: a call of the moment selection -- there are no histogram images, `hist`, D and the neighbours' d_histograms are not looked at)
 int check_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_hip_frame_layers *nb, int n, int W, int H, int D, int nb_scales, const bcd_hip_params *prm,
@@ -156,10 +102,7 @@ int check_call(bcd_hip_ctx *ctx, const float *ns, const float *hist, const bcd_h
         for (int k = 0; k < L; ++k)
             if (!nb[f].layers[k].d_colors || !nb[f].layers[k].d_covariances) return bad(ctx, "null image pointer in a layer of a neighbour frame");
     }
-    if (n > 0 && (prm->patch_radius != 1 || prm->search_radius != 6)) {
-        set_err(ctx, "neighbour frames are supported with patch radius 1 and search radius 6");
-        return BCD_HIP_EUNSUPPORTED;
-    }
+    RCCHK(check_temporal_geometry(ctx, W, H, nb_scales, prm, n > 0, nullptr)); // (check_layers_call has passed the scales: what can fail here is the radii)
     const size_t npix = (size_t)W * H, no = npix * 3 * sizeof(float);
     for (int k = 0; k < L; ++k)
         for (int f = 0; f < n; ++f)
@@ -257,26 +200,27 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
     memset(ctx->layer_spectral, 0, sizeof(ctx->layer_spectral));
     ctx->layer_count = 0;
     // ---- the pyramids of every frame: sample counts and histograms summed, the layers' colours averaged and their covariances weighted by the frame's counts
-    std::vector<LevelFrame> lv((size_t)S * nf);
-    std::vector<float *> outs((size_t)S * L);
+    std::vector<TemporalFrame> lv((size_t)S * nf, TemporalFrame());
+    LayerView outs[MAX_SCALES]; // (the outputs of every level, for the stage and the merge)
     int ws[MAX_SCALES], hs[MAX_SCALES];
     ws[0] = W; hs[0] = H;
     for (int f = 0; f < nf; ++f) {
-        LevelFrame &l = lv[f];
-        l.ns = f ? neighbours[f - 1].d_nsamples : d_ns; l.hist = moments ? nullptr : f ? neighbours[f - 1].d_histograms : d_hist;
+        TemporalFrame &l = lv[f];
+        l.sel.ns = f ? neighbours[f - 1].d_nsamples : d_ns; l.sel.hist = moments ? nullptr : f ? neighbours[f - 1].d_histograms : d_hist;
         for (int k = 0; k < L; ++k) {
             l.col[k] = f ? neighbours[f - 1].layers[k].d_colors : layers[k].d_colors;
             l.cov[k] = f ? neighbours[f - 1].layers[k].d_covariances : layers[k].d_covariances;
         }
     }
-    for (int k = 0; k < L; ++k) outs[k] = layers[k].d_out;
+    outs[0].n = L;
+    for (int k = 0; k < L; ++k) outs[0].out[k] = layers[k].d_out;
     std::vector<const uint8_t *> valid((size_t)S * nf, nullptr);
     for (int f = 1; motion && f < nf; ++f) {
         if (!motion[f - 1]) continue;
         // the neighbour reprojected into the frame's pixel grid, at full resolution: sample counts, histograms and the first layer by the frame kernel, the further
         // layers by the layered one (it writes the same validity bytes again); the pyramid is built from the warped images
         const size_t npix = (size_t)W * H;
-        LevelFrame &l = lv[f];
+        TemporalFrame &l = lv[f];
         DevBuf(&lw)[2] = tp.lay_warp[f];
         RCCHK(ensure(ctx, lw[0], (size_t)(L - 1) * npix * 3 * sizeof(float)));
         RCCHK(ensure(ctx, lw[1], (size_t)(L - 1) * npix * 6 * sizeof(float)));
@@ -286,15 +230,16 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
             t.ocol[k - 1] = (float *)lw[0].p + (size_t)(k - 1) * npix * 3; t.ocov[k - 1] = (float *)lw[1].p + (size_t)(k - 1) * npix * 6;
         }
         const float *wp[4];
-        RCCHK(temporal_warp_neighbour(ctx, f, nf, l.col[0], l.ns, l.hist, l.cov[0], motion[f - 1], W, H, D, S, L > 1 ? &t : nullptr, L - 1, valid.data(), wp));
-        l.col[0] = wp[0]; l.ns = wp[1]; l.hist = moments ? nullptr : wp[2]; l.cov[0] = wp[3]; // ("Moments": D = 0, nothing of a histogram is gathered)
+        RCCHK(temporal_warp_neighbour(ctx, f, nf, l.col[0], l.sel.ns, l.sel.hist, l.cov[0], motion[f - 1], W, H, D, S, L > 1 ? &t : nullptr, L - 1, valid.data(), wp));
+        l.col[0] = wp[0]; l.sel.ns = wp[1]; l.sel.hist = moments ? nullptr : wp[2]; l.cov[0] = wp[3]; // ("Moments": D = 0, nothing of a histogram is gathered)
         for (int k = 1; k < L; ++k) { l.col[k] = t.ocol[k - 1]; l.cov[k] = t.ocov[k - 1]; }
     }
     for (int s = 1; s < S; ++s) {
         ws[s] = ws[s - 1] / 2; hs[s] = hs[s - 1] / 2;
         const size_t np = (size_t)ws[s] * hs[s];
         RCCHK(ensure(ctx, tp.lay_out[s], (size_t)L * np * 3 * sizeof(float)));
-        for (int k = 0; k < L; ++k) outs[(size_t)s * L + k] = (float *)tp.lay_out[s].p + (size_t)k * np * 3;
+        outs[s].n = L;
+        for (int k = 0; k < L; ++k) outs[s].out[k] = (float *)tp.lay_out[s].p + (size_t)k * np * 3;
         for (int f = 0; f < nf; ++f) {
             DevBuf(&l)[4] = tp.pyr[f][s];
             DevBuf(&ll)[2] = tp.lay_pyr[f][s];
@@ -302,31 +247,28 @@ static int layers_run(bcd_hip_ctx *ctx, const float *d_ns, const float *d_hist, 
             if (!moments) RCCHK(ensure(ctx, l[2], np * D * sizeof(float)));
             RCCHK(ensure(ctx, ll[0], (size_t)L * np * 3 * sizeof(float)));
             RCCHK(ensure(ctx, ll[1], (size_t)L * np * 6 * sizeof(float)));
-            const LevelFrame &fine = lv[(size_t)(s - 1) * nf + f];
-            LevelFrame &coarse = lv[(size_t)s * nf + f];
-            coarse.ns = (const float *)l[1].p; coarse.hist = moments ? nullptr : (const float *)l[2].p; // ("Moments": the pyramids have no histogram level)
-            HIPCHK(ctx, bcd_launch_downscale(0, fine.ns, ws[s - 1], hs[s - 1], 1, (float *)l[1].p, st));
-            if (!moments) HIPCHK(ctx, bcd_launch_downscale(0, fine.hist, ws[s - 1], hs[s - 1], D, (float *)l[2].p, st));
-            BcdLayerTable t = {};
-            for (int k = 0; k < L; ++k) { coarse.col[k] = (const float *)ll[0].p + (size_t)k * np * 3; t.a[k] = fine.col[k]; t.o[k] = (float *)ll[0].p + (size_t)k * np * 3; }
-            HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, ws[s - 1], hs[s - 1], st));
-            for (int k = 0; k < L; ++k) { coarse.cov[k] = (const float *)ll[1].p + (size_t)k * np * 6; t.a[k] = fine.cov[k]; t.o[k] = (float *)ll[1].p + (size_t)k * np * 6; }
-            HIPCHK(ctx, bcd_launch_layers_downscale_cov(t, L, fine.ns, ws[s - 1], hs[s - 1], st));
+            TemporalFrame &coarse = lv[(size_t)s * nf + f];
+            coarse.sel.ns = (const float *)l[1].p; coarse.sel.hist = moments ? nullptr : (const float *)l[2].p; // ("Moments": the pyramids have no histogram level)
+            for (int k = 0; k < L; ++k) { coarse.col[k] = (const float *)ll[0].p + (size_t)k * np * 3; coarse.cov[k] = (const float *)ll[1].p + (size_t)k * np * 6; }
+            RCCHK(temporal_build_level(ctx, lv[(size_t)(s - 1) * nf + f], coarse, L, true, ws[s - 1], hs[s - 1], D, st));
         }
     }
-    for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs, one pair of launches for all layers (as merge_layers_on)
-        float *const *out = &outs[(size_t)s * L];
-        RCCHK(temporal_layers_scale(ctx, &lv[(size_t)s * nf], nf, L, ws[s], hs[s], D, prm, s, out, &valid[(size_t)s * nf]));
-        if (s < S - 1) {
-            const int w2 = ws[s] / 2, h2 = hs[s] / 2;
-            const size_t slice = (size_t)w2 * h2 * 3;
-            RCCHK(ensure(ctx, tp.lay_tmp_lo, (size_t)L * slice * sizeof(float)));
-            BcdLayerTable t = {};
-            for (int k = 0; k < L; ++k) { t.a[k] = out[k]; t.o[k] = (float *)tp.lay_tmp_lo.p + k * slice; }
-            HIPCHK(ctx, bcd_launch_layers_downscale_avg(t, L, ws[s], hs[s], st));
-            for (int k = 0; k < L; ++k) { t.a[k] = (const float *)tp.lay_tmp_lo.p + k * slice; t.b[k] = outs[(size_t)(s + 1) * L + k]; t.o[k] = out[k]; }
-            HIPCHK(ctx, bcd_launch_layers_merge(t, L, w2, h2, ws[s], hs[s], st));
+    for (int s = S - 1; s >= 0; --s) { // coarse to fine; the merge is mergeOutputs, one pair of launches for all layers
+        const size_t npix = (size_t)ws[s] * hs[s];
+        TemporalScale sc;
+        sc.nf = nf; sc.L = L; sc.layered = true;
+        RCCHK(ensure(ctx, tp.lay_sum, (size_t)L * npix * 3 * sizeof(float)));
+        sc.sum = (float *)tp.lay_sum.p;
+        for (int k = 0; k < L; ++k) sc.out[k] = outs[s].out[k];
+        for (int f = 0; f < nf; ++f) {
+            TemporalFrame &fr = sc.fr[f] = lv[(size_t)s * nf + f];
+            RCCHK(ensure(ctx, tp.lay_pixcov[f], (size_t)L * npix * 6 * sizeof(float)));
+            fr.pixcov = (float *)tp.lay_pixcov[f].p;
+            fr.sel.valid = valid[(size_t)s * nf + f]; // (null: the frame is not warped)
+            temporal_guide_level(ctx, f, s, &fr.sel);
         }
+        RCCHK(temporal_scale(ctx, sc, ws[s], hs[s], D, prm, s));
+        if (s < S - 1) RCCHK(merge_layers_on(ctx, ctx->main, tp.lay_tmp_lo, outs[s], ws[s], hs[s], outs[s + 1]));
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     ctx->layer_count = L;
