@@ -173,6 +173,16 @@ class SpikeLayer(C.Structure):
     _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p), ("d_colors_out", C.c_void_p), ("d_covariances_out", C.c_void_p)]
 
 
+class SpikeLayerInplace(C.Structure):
+    _c_name_ = "bcd_hip_spike_layer_inplace"
+    _fields_ = [("d_colors", C.c_void_p), ("d_covariances", C.c_void_p)]
+
+
+class TemporalHostOptions(C.Structure):
+    _c_name_ = "bcd_hip_temporal_host_options"
+    _fields_ = [("spike_factor", C.c_float), ("reserved", C.c_void_p)]
+
+
 class PlanParams(C.Structure):
     """adaptive sample planning, bcd_hip_accum_plan"""
     _c_name_ = "bcd_hip_plan_params"
@@ -316,6 +326,10 @@ PROTOTYPES = {
     "bcd_hip_sequence_pop_layers": (I, [P, P, I, P]),
     "bcd_hip_sequence_pop_layers_host": (I, [P, P, I, P]),
     "bcd_hip_sequence_mode_info": (I, [P, S(SequenceModeInfo)]),
+    # ---- the spike prefilter in every frame of temporal calls and sequences ("Prefilter")
+    "bcd_hip_denoise_temporal_host_ex": (I, [P, P, P, S(FrameLayers), I, P, I, I, I, I, S(Params), F, S(Layer), I, S(Guide), S(GuideImages), S(TemporalHostOptions)]),
+    "bcd_hip_sequence_set_prefilter": (I, [P, F]),
+    "bcd_hip_sequence_prefilter_info": (I, [P, P, P]),
     # (row bands, for multi-GPU tiling)
     "bcd_hip_denoise_band": (I, [P, P, P, P, P, I, I, I, I, I, S(Params), U32, P, P]),
     "bcd_hip_denoise_bands": (I, [P, S(BandJob), I, S(Params)]),
@@ -383,6 +397,8 @@ PROTOTYPES = {
     "bcd_hip_spike_map": (I, [P, P, I, I, F, P, P]),
     "bcd_hip_spike_apply": (I, [P, P, I, I, I, P, P, I]),
     "bcd_hip_spike_filter_layers": (I, [P, P, P, I, I, I, F, P, P, S(SpikeLayer), I, P, P]),
+    "bcd_hip_spike_apply_inplace": (I, [P, P, I, I, P, P, I, P]),
+    "bcd_hip_spike_filter_layers_inplace": (I, [P, P, P, I, I, I, F, S(SpikeLayerInplace), I, P, P]),
     # (SamplesAccumulator: a whole frame at once, then the persistent device accumulator)
     "bcd_hip_accumulate_samples": (I, [P, P, P, I, I, I, I, F, F, P, P, P, P]),
     "bcd_hip_accum_create": (I, [P, I, I, I, F, F, I64, P]),

@@ -310,6 +310,28 @@ def _motion_stack(motions, F, H, W):
     return fields, flags
 
 
+def _takes_prefilter_frames(fn):
+    """adds two keywords to a wrapper of a call with neighbour frames or of a sequence.  prefilter_frames=<factor>: > 0 sets setSpikePrefilter(factor) and
+    setSpikePrefilterFrames(true) on the denoiser the call builds -- every frame passes through the spike prefilter on its own
+    (bcd_hip_denoise_temporal_host_ex, bcd_hip_sequence_set_prefilter); 0 (the default): the call as it always was.  prefilter_without_switch=<factor> (for
+    tests of the refusals): setSpikePrefilter(factor) alone, which denoise() must refuse beside neighbour frames and in a sequence"""
+    import functools
+
+    @functools.wraps(fn)
+    def call(*args, prefilter_frames=0.0, prefilter_without_switch=0.0, **kw):
+        if prefilter_frames < 0 or prefilter_without_switch < 0 or (prefilter_frames and prefilter_without_switch):
+            raise ValueError("prefilter_frames and prefilter_without_switch are factors >= 0, and one of them at most is given")
+        if not prefilter_frames and not prefilter_without_switch:
+            return fn(*args, **kw)
+        lib().bcdcore_set_frame_prefilter(C.c_float(prefilter_frames or prefilter_without_switch), 1 if prefilter_frames else 0)
+        try:
+            return fn(*args, **kw)
+        finally:
+            lib().bcdcore_set_frame_prefilter(C.c_float(0.0), 0)
+    return call
+
+
+@_takes_prefilter_frames
 def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, after_clear=False, motions=None,
                      features=None, neighbour_features=None, **guide):
     """bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames of the sequence (addNeighbourFrame): neighbours is a list of (col, ns, hist, cov)
@@ -336,6 +358,7 @@ def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, mi
     return rc != 0, out
 
 
+@_takes_prefilter_frames
 def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, unsupported=0, layers=None, features=None,
                      feature_variances=None, feature_floors=(), feature_threshold=1.0, var_floor=1e-8, break_settings=0):
     """bcd::SequenceDenoiser: frames is a list of (col, ns, hist, cov) arrays of one size, pushed one by one and popped as they become ready; frame t comes out
@@ -378,6 +401,7 @@ def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-
     return rc != 0, [outs[k] for k in range(T)]
 
 
+@_takes_prefilter_frames
 def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, drop_layers=0, after_clear=False,
                             motions=None, features=None, neighbour_features=None, variances=None, neighbour_variances=None, floors=(), threshold=1.0,
                             neighbours_with_features=None, moment_selection=False, devices=None):
@@ -426,6 +450,7 @@ def denoise_temporal_layers(ns, hist, layers, neighbours, nscales=1, tau=1.0, b=
     return rc != 0, [outs[k] for k in range(L)]
 
 
+@_takes_prefilter_frames
 def denoise_temporal_moments(ns, layers, neighbours, nscales=1, tau=1.0, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, var_floor=1e-8, motions=None,
                              features=None, neighbour_features=None, variances=None, neighbour_variances=None, floors=(), threshold=1.0, moment_selection=True,
                              plain_neighbours=0, drop_layers=0, devices=None):

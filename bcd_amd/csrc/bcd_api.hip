@@ -1011,6 +1011,7 @@ void bcd_hip_ctx_destroy(bcd_hip_ctx *ctx)
     for (DevBuf &hb : ctx->lay_host) if (hb.p) (void)hipFree(hb.p);
     for (DevBuf &hb : ctx->lay_host_f) if (hb.p) (void)hipFree(hb.p);
     if (ctx->spike_map.p) (void)hipFree(ctx->spike_map.p);
+    for (DevBuf *hb : { &ctx->spike_count, &ctx->spike_list, &ctx->spike_stage }) if (hb->p) (void)hipFree(hb->p);
     for (int s = 0; s < MAX_SCALES; ++s)
         for (int k = 0; k < 5; ++k) if (ctx->pyr[s][k].p) (void)hipFree(ctx->pyr[s][k].p);
     for (int s = 0; s < MAX_SCALES; ++s)

@@ -143,6 +143,15 @@ struct BcdSpikeTable {
     const float *src[BCD_SPIKE_MAX_IMAGES];
     float *dst[BCD_SPIKE_MAX_IMAGES];
 };
+// The in-place gather (k_spike_inplace.hip) moves images of mixed depths in one launch: the sample counts, the histograms and the colours and covariances
+// of BCD_MAX_LAYERS layers at most.  stage_off[k]: where the staging rows of image k start, in floats (a multiple of 4)
+#define BCD_SPIKE_INPLACE_MAX_IMAGES (2 + 2 * BCD_MAX_LAYERS)
+#define BCD_SPIKE_INPLACE_MAX_DEPTH (1 << 24) // (64 pixels' values are indexed with an int)
+struct BcdSpikeInplaceTable {
+    float *img[BCD_SPIKE_INPLACE_MAX_IMAGES];
+    size_t stage_off[BCD_SPIKE_INPLACE_MAX_IMAGES];
+    int depth[BCD_SPIKE_INPLACE_MAX_IMAGES];
+};
 
 // ---- colour layers of the device accumulator (bcd_hip_accum_*_layers) ----------------------------------
 // The layer is blockIdx.y; the per-layer device pointers of one launch travel by value.  The beauty is layer 0 of bcd_hip_denoise_layers,

@@ -180,6 +180,8 @@ struct bcd_hip_ctx {
     DevBuf lay_host[3];            // host-buffer entry point of the layers: device copies of the extra layers' colours, covariances, outputs
     DevBuf lay_host_f[2];          // ... and, when the spike prefilter covers them, the second set of slices: their colours and covariances gathered through the map
     DevBuf spike_map;              // the source map of the spike prefilter (bcd_hip_spike_filter_layers without a map of the caller's, the host-buffer layers): W*H int32
+    // the in-place gather (spike_gather_inplace): the moved count and the list cursor (two int32), the (destination, source) pairs, the staged source values
+    DevBuf spike_count, spike_list, spike_stage;
     DevBuf lay_pyr[MAX_SCALES][3]; // extra colour layers: colours, cov, out of every layer at that pyramid level, one slice per layer
     int32_t layer_spectral[MAX_SCALES][BCD_MAX_LAYERS]; // per scale and layer of the last layered call: full estimates that took the spectral inverse
     int layer_count = 0;                                // layers of that call (0: none yet)
@@ -227,6 +229,8 @@ struct bcd_hip_ctx {
             bool on = false;
             const float *f[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES] = {}, *v[BCD_MAX_NEIGHBOURS + 1][MAX_SCALES] = {};
         } guide;
+        // bcd_hip_denoise_temporal_host_ex in progress with a factor ("Prefilter"): the host calls filter every frame's uploaded copies in place behind their uploads
+        float prefilter = 0.f;
         int64_t guide_cross_passes = 0; // cross feature passes launched so far (temporal_guide_gate: one per gated neighbour and scale); a sequence reports its share
     } temporal;
     DevBuf host_stage[9];      // host-buffer entry points: device copies of the four inputs, the output, the prefiltered inputs (grow-only)
@@ -453,6 +457,14 @@ int check_motion_list(bcd_hip_ctx *ctx, const float *const *motion, int nb_neigh
 // switches the mode off
 int temporal_guide_begin(bcd_hip_ctx *ctx, const bcd_hip_guide *g, const bcd_hip_guide_images *nb, int nb_neighbours, const float *const *motion, int W, int H, int nb_scales);
 inline void temporal_guide_end(bcd_hip_ctx *ctx) { ctx->temporal.guide.on = false; }
+
+// ---- defined in bcd_spike.hip: the spike prefilter in place ("In place"), on ctx->stream; each synchronises once, for the moved count
+// (h_moved: null, or where it goes).  Neither checks an argument: the public entry points and the animation paths have
+// the in-place gather of t's n images through d_map
+int spike_gather_inplace(bcd_hip_ctx *ctx, const int32_t *d_map, size_t npix, BcdSpikeInplaceTable &t, int n, int32_t *h_moved);
+// one resident frame: the map of d_col[0] into d_map (null: ctx->spike_map), then the sample counts, the histograms (null: none) and the L layers gathered
+int spike_filter_frame_inplace(bcd_hip_ctx *ctx, float *d_ns, float *d_hist, int W, int H, int D, float factor, float *const *d_col, float *const *d_cov, int L,
+                               int32_t *d_map, int32_t *h_moved);
 
 // ---- defined in bcd_selection.hip
 // one scale of a bcd_hip_denoise_layers_keep call, at the end of its chain (the stream is synchronised, wk.h_counters->lists holds the list lengths, `st` is

@@ -133,6 +133,12 @@ hipError_t bcd_launch_layers_merge(const BcdLayerTable &t, int layers, int w, in
 hipError_t bcd_launch_spike_map(const float *col, int W, int H, float factor, int32_t *map, int32_t *d_moved, hipStream_t st);
 hipError_t bcd_launch_spike_apply(const BcdSpikeTable &t, int n, const int32_t *map, int W, int H, int depth, hipStream_t st);
 
+// ---- k_spike_inplace.hip
+hipError_t bcd_launch_spike_moved_count(const int32_t *map, uint32_t npix, int32_t *d_count, hipStream_t st);
+hipError_t bcd_launch_spike_compact(const int32_t *map, uint32_t npix, int32_t *d_cursor, int2 *list, uint32_t capacity, hipStream_t st);
+size_t bcd_spike_stage_floats(BcdSpikeInplaceTable &t, int n, uint32_t moved);
+hipError_t bcd_launch_spike_stage(const BcdSpikeInplaceTable &t, int n, const int2 *list, uint32_t moved, float *stage, hipStream_t st);
+
 // ---- k_active.hip
 hipError_t bcd_launch_active_init(const int32_t *nsim, int W, int H, int w, int row_begin, int row_end, float skip_prob, uint32_t seed, int row_offset, uint8_t *state,
                                   hipStream_t st);

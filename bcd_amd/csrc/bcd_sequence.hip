@@ -54,6 +54,9 @@ struct bcd_hip_sequence {
     bool moments = false, fvar = false;      // selection from means and covariances (D = 0, no histogram stored); every frame brings feature variances
     float var_floor = 0.f, floors[BCD_GUIDE_MAX_CHANNELS] = {}, ftau = 0.f;
     int64_t feature_passes = 0;              // cross feature passes its pops launched
+    // ---- the spike prefilter (bcd_hip_sequence_set_prefilter; DESIGN.md section 16, "Prefilter"): every frame is filtered once, in place in its slot, by its push
+    float prefilter = 0.f;                   // the factor (0: off)
+    int64_t filtered = 0, moved = 0;         // frames filtered, pixels they moved
     bool plain() const { return L == 1 && !moments && F == 0; }   // what bcd_hip_sequence_create builds: its entry points, and it reports no layers
     bool layered() const { return moments || L > 1; }             // the estimate of bcd_temporal_layers.hip (one layer of histograms: that of bcd_temporal.hip)
 };
@@ -76,7 +79,7 @@ void forget(bcd_hip_sequence *q)
     q->pushed = q->popped = 0;
     q->ended = false;
     q->last_frame = -1; q->last_nb = 0;
-    q->uploaded = q->pyramids = q->computed = q->transposed = q->feature_passes = 0;
+    q->uploaded = q->pyramids = q->computed = q->transposed = q->feature_passes = q->filtered = q->moved = 0;
     for (SeqSlot &s : q->slot) for (int64_t &f : s.pair_frame) f = -1;
 }
 
@@ -134,6 +137,15 @@ int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyK
             if (F) { HIPCHK(ctx, hipMemcpyAsync(sl.guide[0][0].p, fm->features, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
             if (F && q->fvar) { HIPCHK(ctx, hipMemcpyAsync(sl.guide[0][1].p, fm->variances, np * F * f4, kind, st)); bytes += (int64_t)(np * F * f4); }
             if (kind == hipMemcpyHostToDevice) q->uploaded += bytes;
+            if (q->prefilter > 0.f) { // the frame's own decision, in place: the pyramid and the per-pixel covariances below come from the filtered level 0
+                float *col[BCD_MAX_LAYERS], *cov[BCD_MAX_LAYERS];
+                for (int k = 0; k < L; ++k) { col[k] = const_cast<float *>(l.col[k]); cov[k] = const_cast<float *>(l.cov[k]); }
+                int32_t moved = 0;
+                RCCHK(spike_filter_frame_inplace(ctx, (float *)sl.lv[0][1].p, q->moments ? nullptr : (float *)sl.lv[0][2].p, q->W, q->H, D, q->prefilter, col, cov, L, nullptr,
+                                                 &moved));
+                ++q->filtered;
+                q->moved += moved;
+            }
         } else {
             const TemporalFrame fine = slot_level(q, sl, s - 1);
             RCCHK(temporal_build_level(ctx, fine, l, L, q->layered(), q->ws[s - 1], q->hs[s - 1], D, st));
@@ -509,6 +521,28 @@ int bcd_hip_sequence_set_reuse(void *seq, int on)
     bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
     if (!q) return BCD_HIP_EINVAL;
     q->reuse = on != 0;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_sequence_set_prefilter(void *seq, float factor)
+{
+    bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
+    if (!q) return BCD_HIP_EINVAL;
+    bcd_hip_ctx *ctx = q->ctx;
+    if (!std::isfinite(factor)) return bad(ctx, "the spike factor must be finite");
+    if (q->pushed > 0) return bad(ctx, "the prefilter is set while the sequence holds no frame: after its creation or bcd_hip_sequence_reset");
+    if (factor > 0.f && (q->W < 3 || q->H < 3)) return bad(ctx, "image smaller than 3x3");
+    q->prefilter = factor > 0.f ? factor : 0.f;
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_sequence_prefilter_info(void *seq, int64_t *frames_filtered, int64_t *pixels_moved)
+{
+    const bcd_hip_sequence *q = (const bcd_hip_sequence *)seq;
+    if (!q) return BCD_HIP_EINVAL;
+    if (!frames_filtered || !pixels_moved) return bad(q->ctx, "null info pointer");
+    *frames_filtered = q->filtered;
+    *pixels_moved = q->moved;
     return BCD_HIP_OK;
 }
 

@@ -1,5 +1,7 @@
 // bcd_spike.hip -- the spike prefilter through a source map (bcd_hip_spike_map, bcd_hip_spike_apply, bcd_hip_spike_filter_layers): every argument is
-// checked before any device work, everything is enqueued on the context's stream, no call synchronises.
+// checked before any device work, everything is enqueued on the context's stream, no call synchronises -- but the in-place forms
+// (bcd_hip_spike_apply_inplace, bcd_hip_spike_filter_layers_inplace; spike_gather_inplace below, which the animation paths call too), which read the
+// number of moved pixels back once to size their list and staging buffer.
 #include "bcd_ctx.h"
 
 #include <vector>
@@ -30,7 +32,56 @@ int check_frame(bcd_hip_ctx *ctx, int W, int H)
     return BCD_HIP_OK;
 }
 
+// no two of them share a byte
+bool all_apart(const std::vector<Range> &r)
+{
+    for (size_t k = 0; k < r.size(); ++k)
+        for (size_t j = 0; j < k; ++j) if (r[k].overlaps(r[j])) return false;
+    return true;
+}
+
 } // namespace
+
+// The in-place gather of t's n images (t.img, t.depth) through d_map on the context's stream.  k_spike_moved_count counts the moved pixels (one atomic per
+// workgroup of 4096 pixels -- the counter of bcd_launch_spike_map, one atomic per wavefront on one word, costs more than the map itself); the count is read
+// back -- the one synchronisation -- and sizes the list and the staging buffer; with no moved pixel nothing further is launched.  No argument is checked here
+int spike_gather_inplace(bcd_hip_ctx *ctx, const int32_t *d_map, size_t npix, BcdSpikeInplaceTable &t, int n, int32_t *h_moved)
+{
+    RCCHK(ensure(ctx, ctx->spike_count, 2 * sizeof(int32_t)));
+    int32_t *d_cnt = (int32_t *)ctx->spike_count.p;
+    HIPCHK(ctx, bcd_launch_spike_moved_count(d_map, (uint32_t)npix, d_cnt, ctx->stream));
+    int32_t moved = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&moved, d_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_moved) *h_moved = moved;
+    if (moved <= 0) return BCD_HIP_OK;
+    const size_t floats = bcd_spike_stage_floats(t, n, (uint32_t)moved);
+    RCCHK(ensure(ctx, ctx->spike_list, (size_t)moved * sizeof(int2)));
+    RCCHK(ensure(ctx, ctx->spike_stage, floats * sizeof(float)));
+    HIPCHK(ctx, bcd_launch_spike_compact(d_map, (uint32_t)npix, d_cnt + 1, (int2 *)ctx->spike_list.p, (uint32_t)moved, ctx->stream));
+    HIPCHK(ctx, bcd_launch_spike_stage(t, n, (const int2 *)ctx->spike_list.p, (uint32_t)moved, (float *)ctx->spike_stage.p, ctx->stream));
+    return BCD_HIP_OK;
+}
+
+// The spike prefilter of one resident frame in place: the map of d_col[0] into d_map (null: the context's scratch map), then one in-place gather of the
+// sample counts, the histograms (null: none) and the colours and covariances of the L layers.  Synchronises once.  No argument is checked here
+int spike_filter_frame_inplace(bcd_hip_ctx *ctx, float *d_ns, float *d_hist, int W, int H, int D, float factor, float *const *d_col, float *const *d_cov, int L,
+                               int32_t *d_map, int32_t *h_moved)
+{
+    const size_t np = (size_t)W * H;
+    if (!d_map) {
+        RCCHK(ensure(ctx, ctx->spike_map, np * sizeof(int32_t)));
+        d_map = (int32_t *)ctx->spike_map.p;
+    }
+    HIPCHK(ctx, bcd_launch_spike_map(d_col[0], W, H, factor, d_map, nullptr, ctx->stream));
+    BcdSpikeInplaceTable t = {};
+    int n = 0;
+    t.img[n] = d_ns; t.depth[n++] = 1;
+    if (d_hist) { t.img[n] = d_hist; t.depth[n++] = D; }
+    for (int k = 0; k < L; ++k) { t.img[n] = d_col[k]; t.depth[n++] = 3; }
+    for (int k = 0; k < L; ++k) { t.img[n] = d_cov[k]; t.depth[n++] = 6; }
+    return spike_gather_inplace(ctx, d_map, np, t, n, h_moved);
+}
 
 extern "C" {
 
@@ -119,6 +170,59 @@ int bcd_hip_spike_filter_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const
     for (int k = 0; k < nb_layers; ++k) { t.src[k] = layers[k].d_covariances; t.dst[k] = layers[k].d_covariances_out; }
     HIPCHK(ctx, bcd_launch_spike_apply(t, nb_layers, d_map, W, H, 6, ctx->stream));
     return BCD_HIP_OK;
+}
+
+int bcd_hip_spike_apply_inplace(bcd_hip_ctx *ctx, const int32_t *d_map, int W, int H, const int32_t *depths, float *const *d_images, int nb_images, int32_t *h_moved)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_map) return bad(ctx, "null map pointer");
+    if (!depths || !d_images) return bad(ctx, "null image or depth list");
+    RCCHK(check_frame(ctx, W, H));
+    if (nb_images < 1 || nb_images > BCD_SPIKE_MAX_IMAGES) return bad(ctx, "the number of images must be between 1 and 32");
+    const size_t np = (size_t)W * H;
+    BcdSpikeInplaceTable t = {};
+    {
+        std::vector<Range> r{ Range(d_map, np * sizeof(int32_t)) };
+        for (int k = 0; k < nb_images; ++k) {
+            if (!d_images[k]) return bad(ctx, "null image pointer in a list");
+            if (depths[k] < 1) return bad(ctx, "the depth must be at least 1");
+            if (depths[k] > BCD_SPIKE_INPLACE_MAX_DEPTH) return bad(ctx, "the depth must be at most 2^24");
+            t.img[k] = d_images[k]; t.depth[k] = depths[k];
+            r.push_back(Range(d_images[k], np * (size_t)depths[k] * sizeof(float)));
+        }
+        if (!all_apart(r)) return bad(ctx, "two images overlap, or an image overlaps the map");
+    }
+    DEVICE_GUARD(ctx);
+    return spike_gather_inplace(ctx, d_map, np, t, nb_images, h_moved);
+}
+
+int bcd_hip_spike_filter_layers_inplace(bcd_hip_ctx *ctx, float *d_nsamples, float *d_histograms, int W, int H, int D, float factor,
+                                        const bcd_hip_spike_layer_inplace *layers, int nb_layers, int32_t *d_map, int32_t *h_moved)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_nsamples) return bad(ctx, "null image pointer");
+    if (!layers) return bad(ctx, "null layer list");
+    if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+    for (int k = 0; k < nb_layers; ++k)
+        if (!layers[k].d_colors || !layers[k].d_covariances) return bad(ctx, "null image pointer in a layer");
+    RCCHK(check_frame(ctx, W, H));
+    if (d_histograms && D < 1) return bad(ctx, "the depth must be at least 1");
+    if (d_histograms && D > BCD_SPIKE_INPLACE_MAX_DEPTH) return bad(ctx, "the depth must be at most 2^24");
+    const size_t np = (size_t)W * H, f = sizeof(float);
+    float *col[BCD_HIP_MAX_LAYERS], *cov[BCD_HIP_MAX_LAYERS];
+    {
+        std::vector<Range> r{ Range(d_nsamples, np * f) };
+        if (d_histograms) r.push_back(Range(d_histograms, np * D * f));
+        for (int k = 0; k < nb_layers; ++k) {
+            col[k] = layers[k].d_colors; cov[k] = layers[k].d_covariances;
+            r.push_back(Range(col[k], np * 3 * f));
+            r.push_back(Range(cov[k], np * 6 * f));
+        }
+        if (d_map) r.push_back(Range(d_map, np * sizeof(int32_t)));
+        if (!all_apart(r)) return bad(ctx, "two images overlap, or an image overlaps the map");
+    }
+    DEVICE_GUARD(ctx);
+    return spike_filter_frame_inplace(ctx, d_nsamples, d_histograms, W, H, D, factor, col, cov, nb_layers, d_map, h_moved);
 }
 
 } // extern "C"

@@ -661,6 +661,10 @@ static int temporal_host_run(bcd_hip_ctx *ctx, const float *h_colors, const floa
     const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
     if (h_motion) RCCHK(temporal_upload_motion(ctx, h_motion, nb_neighbours, W, H, dmv));
     RCCHK(upload_frames(ctx, h_colors, h_nsamples, h_histograms, h_covariances, neighbours, nb_neighbours, W, H, D, dev));
+    for (int f = 0; tp.prefilter > 0.f && f <= nb_neighbours; ++f) { // ("Prefilter": every frame on its own, in its own pixel grid, in place in its uploaded copies)
+        float *col = (float *)tp.host[f][0].p, *cov = (float *)tp.host[f][3].p;
+        RCCHK(spike_filter_frame_inplace(ctx, (float *)tp.host[f][1].p, (float *)tp.host[f][2].p, W, H, D, tp.prefilter, &col, &cov, 1, nullptr, nullptr));
+    }
     float *d_out = (float *)tp.host_out.p;
     if (h_motion)
         RCCHK(bcd_hip_denoise_temporal_motion(ctx, dev[0].d_colors, dev[0].d_nsamples, dev[0].d_histograms, dev[0].d_covariances, dev + 1, nb_neighbours, dmv, W, H, D,

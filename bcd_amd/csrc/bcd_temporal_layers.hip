@@ -336,6 +336,11 @@ static int layers_host_run(bcd_hip_ctx *ctx, const float *h_ns, const float *h_h
     bcd_hip_layer lay[BCD_HIP_MAX_LAYERS];
     for (int k = 0; k < L; ++k) lay[k] = { dl[k].d_colors, dl[k].d_covariances, (float *)tp.lay_host_out.p + (size_t)k * npix * 3 };
     HIPCHK(ctx, hipStreamSynchronize(st));
+    for (int f = 0; tp.prefilter > 0.f && f <= nb_neighbours; ++f) { // ("Prefilter": every frame on its own, in its own pixel grid, in place in its uploaded copies)
+        float *col[BCD_HIP_MAX_LAYERS], *cov[BCD_HIP_MAX_LAYERS];
+        for (int k = 0; k < L; ++k) { col[k] = const_cast<float *>(dl[(size_t)f * L + k].d_colors); cov[k] = const_cast<float *>(dl[(size_t)f * L + k].d_covariances); }
+        RCCHK(spike_filter_frame_inplace(ctx, (float *)tp.host[f][1].p, moments ? nullptr : (float *)tp.host[f][2].p, W, H, D, tp.prefilter, col, cov, L, nullptr, nullptr));
+    }
     const float *dmv[BCD_HIP_MAX_NEIGHBOURS];
     if (h_motion) RCCHK(temporal_upload_motion(ctx, h_motion, nb_neighbours, W, H, dmv));
     RCCHK(layers_run(ctx, dev[0].d_nsamples, dev[0].d_histograms, dev + 1, nb_neighbours, W, H, D, nb_scales, prm, lay, L, h_motion ? dmv : nullptr));
@@ -537,6 +542,54 @@ int bcd_hip_denoise_temporal_moments_host(bcd_hip_ctx *ctx, const float *h_ns, c
     if (guide) rc = guided_host_run(ctx, h_ns, nullptr, neighbours, nb_neighbours, h_motion, W, H, 0, nb_scales, prm, layers, nb_layers, guide, neighbour_guides);
     else rc = layers_host_run(ctx, h_ns, nullptr, neighbours, nb_neighbours, W, H, 0, nb_scales, prm, layers, nb_layers, any_field(h_motion, nb_neighbours) ? h_motion : nullptr);
     ctx->moments.on = false;
+    return rc;
+}
+
+// ---- "Prefilter": the host frame calls behind one entry point, every frame through the spike prefilter on its own -------------------
+int bcd_hip_denoise_temporal_host_ex(bcd_hip_ctx *ctx, const float *h_ns, const float *h_hist, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
+                                     const float *const *h_motion, int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float var_floor,
+                                     const bcd_hip_layer *layers, int nb_layers, const bcd_hip_guide *guide, const bcd_hip_guide_images *neighbour_guides,
+                                     const bcd_hip_temporal_host_options *opt)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (opt && opt->reserved) return bad(ctx, "the reserved pointer of the options must be NULL");
+    if (opt && !std::isfinite(opt->spike_factor)) return bad(ctx, "the spike factor must be finite");
+    const float factor = opt ? opt->spike_factor : 0.f;
+    if (factor > 0.f && (W < 3 || H < 3)) return bad(ctx, "image smaller than 3x3");
+    if (factor > 0.f && nb_neighbours == 0) { // the single-frame host call of the mode with the factor over every layer
+        if (!layers) return bad(ctx, "null layer list");
+        if (nb_layers < 1 || nb_layers > BCD_HIP_MAX_LAYERS) return bad(ctx, "the number of layers must be between 1 and 16 (BCD_HIP_MAX_LAYERS)");
+        bcd_hip_host_layer hl[BCD_HIP_MAX_LAYERS];
+        for (int k = 0; k < nb_layers; ++k) hl[k] = { layers[k].d_colors, layers[k].d_covariances, layers[k].d_out };
+        const bcd_hip_layers_host_options so = { factor, 0, 1 };
+        // (the refusals the delegated call makes of these arguments ahead of ITS single-frame delegation: the layered calls check the whole call and the
+        // motion list, the guided and the moment call go straight to the single-frame call)
+        if (h_hist && !guide) {
+            RCCHK(check_call(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers));
+            float *outs[ML];
+            layer_outs(layers, nb_layers, outs);
+            if (h_motion) RCCHK(check_motion_list(ctx, h_motion, nb_neighbours, W, H, outs, nb_layers));
+        }
+        if (!h_hist) {
+            RCCHK(check_moments_head(ctx, nb_neighbours, var_floor));
+            return guide ? bcd_hip_denoise_guided_host(ctx, h_ns, nullptr, W, H, 0, nb_scales, prm, &so, var_floor, hl, nb_layers, guide)
+                         : bcd_hip_denoise_moments_host(ctx, h_ns, W, H, nb_scales, prm, &so, var_floor, hl, nb_layers);
+        }
+        return guide ? bcd_hip_denoise_guided_host(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, &so, 0.f, hl, nb_layers, guide)
+                     : bcd_hip_denoise_layers_host_ex(ctx, h_ns, h_hist, W, H, D, nb_scales, prm, &so, hl, nb_layers);
+    }
+    // the existing host call that takes exactly these arguments; with a factor its uploads are followed by the in-place filter of every frame
+    ctx->temporal.prefilter = factor > 0.f ? factor : 0.f;
+    int rc;
+    if (!h_hist)
+        rc = bcd_hip_denoise_temporal_moments_host(ctx, h_ns, neighbours, nb_neighbours, h_motion, W, H, nb_scales, prm, var_floor, layers, nb_layers, guide, neighbour_guides);
+    else if (guide)
+        rc = bcd_hip_denoise_temporal_guided_host(ctx, h_ns, h_hist, neighbours, nb_neighbours, h_motion, W, H, D, nb_scales, prm, layers, nb_layers, guide, neighbour_guides);
+    else if (h_motion)
+        rc = bcd_hip_denoise_temporal_layers_motion_host(ctx, h_ns, h_hist, neighbours, nb_neighbours, h_motion, W, H, D, nb_scales, prm, layers, nb_layers);
+    else
+        rc = bcd_hip_denoise_temporal_layers_host(ctx, h_ns, h_hist, neighbours, nb_neighbours, W, H, D, nb_scales, prm, layers, nb_layers);
+    ctx->temporal.prefilter = 0.f;
     return rc;
 }
 

@@ -7,8 +7,8 @@ import weakref
 from . import _prototypes
 from ._prototypes import (ACCUM_MAX_FEATURES, ACCUM_MAX_LAYERS, MAX_LAYERS, MULTI_ID_BYTES, PROGRESS_FN, SELECTION_MAX_SCALES, STATE_HEADER_BYTES, BandJob,
                           FeaturesHeader, Frame, FrameLayer, FrameLayers, Guide, GuideImages, HostLayer, HostOptions, HostStreamResult, Layer, LayersHeader, LayersHostOptions, MultiStats, Params,
-                          PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SequenceFrame, SequenceInfo, SequenceMode, SequenceModeInfo, SpikeLayer, StageFrame, StageFrameLayers, StageLayer,
-                          StateHeader, WarpedFrame)
+                          PlanParams, PlanSummary, ScaleStats, SelectionInfo, SelectionScale, SequenceFrame, SequenceInfo, SequenceMode, SequenceModeInfo, SpikeLayer, SpikeLayerInplace, StageFrame, StageFrameLayers, StageLayer,
+                          StateHeader, TemporalHostOptions, WarpedFrame)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BCD_HIP_LIB") or os.path.join(_HERE, "lib", "libbcd_hip.so")   # (BCD_HIP_LIB: tools load instrumented builds)
@@ -1145,6 +1145,61 @@ class Context:
         del alive, keep, fields, nfeat, nvar
         return outs
 
+    def denoise_temporal_layers_motion_host(self, ns, hist, layers, neighbours, motions, nscales, prm):
+        """bcd_hip_denoise_temporal_layers_motion_host on NumPy float32 arrays: denoise_temporal_layers_host with per neighbour an (H, W, 2) motion field or
+        None -> the list of denoised layers (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        ns, hist = as32(ns), as32(hist)
+        H, W, D = hist.shape
+        neighbours = [(as32(n), as32(h), [(as32(c), as32(v)) for c, v in lay]) for n, h, lay in neighbours]
+        arr, layers, outs = _host_layer_array(layers, H, W, Layer)
+        nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _hptr, np.size)
+        fields = None if motions is None else [None if m is None else as32(m) for m in motions]
+        mv = self._motion_array(fields, len(neighbours), H, W, _hptr, np.size)
+        self._chk(lib().bcd_hip_denoise_temporal_layers_motion_host(self.h, ns.ctypes.data, hist.ctypes.data, nb, len(neighbours), mv, W, H, D, int(nscales), C.byref(prm),
+                                                                    arr, len(layers)))
+        del keep, fields
+        return outs
+
+    # ---- the spike prefilter in every frame of a host frame call (DESIGN.md section 16, "Prefilter") ----
+    def denoise_temporal_host_ex(self, ns, hist, layers, neighbours, nscales, prm, spike_factor=None, var_floor=1e-8, motions=None, features=None,
+                                 neighbour_features=None, variances=None, neighbour_variances=None, floors=(), threshold=1.0, reserved=None):
+        """bcd_hip_denoise_temporal_host_ex on NumPy float32 arrays: the host frame call that takes these arguments (hist None: the moment selection, its
+        neighbours (ns, [(colours, covariances), ...]); else (ns, hist, [...]); features: the feature gate; motions: the motion fields), every frame passed
+        through the spike prefilter on its own when spike_factor > 0 (None: a NULL options pointer) -> the list of denoised layers (H, W, 3)"""
+        import numpy as np
+        as32 = lambda a: np.ascontiguousarray(a, np.float32)
+        ns = as32(ns)
+        H, W = ns.shape[:2]
+        moments = hist is None
+        D = 0
+        arr, layers, outs = _host_layer_array(layers, H, W, Layer)
+        if moments:
+            neighbours = [(as32(f[0]), [(as32(c), as32(v)) for c, v in f[-1]]) for f in neighbours]
+            nb, keep = self._moment_frames_array(neighbours, len(layers), H, W, _hptr, np.size)
+        else:
+            hist = as32(hist)
+            D = hist.shape[2]
+            neighbours = [(as32(n), as32(h), [(as32(c), as32(v)) for c, v in lay]) for n, h, lay in neighbours]
+            nb, keep = self._frame_layers_array(neighbours, len(layers), H, W, D, _hptr, np.size)
+        fields = None if motions is None else [None if m is None else as32(m) for m in motions]
+        mv = self._motion_array(fields, len(neighbours), H, W, _hptr, np.size)
+        g = ng = alive = nfeat = nvar = None
+        if features is not None:
+            g, alive = self._guide(features, variances, floors, threshold, host=True)
+            if tuple(alive[0].shape[:2]) != (H, W):
+                raise ValueError("features must be %dx%dxF" % (H, W))
+            nfeat = [as32(f) for f in (neighbour_features if neighbour_features is not None else [])]
+            nvar = None if neighbour_variances is None else [as32(v) for v in neighbour_variances]
+            ng = self._guide_images_array(nfeat, nvar, len(neighbours), alive[0].shape, _hptr)
+        opt = None if spike_factor is None else TemporalHostOptions(float(spike_factor), reserved)
+        self._chk(lib().bcd_hip_denoise_temporal_host_ex(self.h, ns.ctypes.data, None if moments else hist.ctypes.data, nb, len(neighbours), mv, W, H, D, int(nscales),
+                                                         C.byref(prm), float(var_floor), arr, len(layers), None if g is None else C.byref(g), ng,
+                                                         None if opt is None else C.byref(opt)))
+        del alive, keep, fields, nfeat, nvar
+        return outs
+
     def denoise_temporal_stages(self, col, ns, hist, cov, neighbours, prm):
         """One scale of the denoising of a frame with similar patches from neighbouring frames of its sequence, composed from the
         stage calls: in-frame masks, cross masks of every neighbour, the marking on the in-frame masks and the total |S|, the estimate over the members of
@@ -1334,6 +1389,34 @@ class Context:
                                                     _dp(o_hist) if hist is not None else None, arr, len(layers), _dp(m) if own_map else None, _dp(moved) if count else None))
         res = (o_ns, o_hist, outs, m)
         return res + (int(moved.item()),) if count else res
+
+    def spike_apply_inplace(self, map, images):
+        """bcd_hip_spike_apply_inplace: every image of the list (H x W x depth tensors of any depths, at most 32) gathered through the map IN PLACE: pixel p
+        ends with the values pixel map[p] held before the call.  Synchronises.  -> the number of moved pixels"""
+        images = list(images)
+        H, W = map.shape[:2]
+        depths = (C.c_int32 * max(1, len(images)))(*[a.numel() // (H * W) for a in images])
+        moved = C.c_int32(-1)
+        self.torch.cuda.synchronize(self.device)                     # (the fills ran on torch's stream)
+        self._chk(lib().bcd_hip_spike_apply_inplace(self.h, _dp(map), W, H, depths, self._ptr_list(images), len(images), C.byref(moved)))
+        return moved.value
+
+    def spike_filter_layers_inplace(self, ns, hist, layers, factor, own_map=True):
+        """bcd_hip_spike_filter_layers_inplace: spike_filter_layers IN PLACE on `ns`, `hist` (None: the form without histograms) and the (colours, covariances)
+        of `layers`.  Synchronises.  -> (map or None without own_map, moved pixels)"""
+        torch = self.torch
+        layers = list(layers)
+        H, W = ns.shape[:2]
+        D = hist.shape[-1] if hist is not None else 0
+        m = torch.empty((H, W), dtype=torch.int32, device=ns.device) if own_map else None
+        arr = (SpikeLayerInplace * max(1, len(layers)))()
+        for k, (c, v) in enumerate(layers):
+            arr[k].d_colors, arr[k].d_covariances = _dp(c).value, _dp(v).value
+        moved = C.c_int32(-1)
+        torch.cuda.synchronize(self.device)
+        self._chk(lib().bcd_hip_spike_filter_layers_inplace(self.h, _dp(ns), _dp(hist) if hist is not None else None, W, H, D, factor, arr, len(layers),
+                                                            _dp(m) if own_map else None, C.byref(moved)))
+        return m, moved.value
 
     def accumulate_samples(self, samples, weights=None, nbins=20, gamma=2.2, maxval=2.5):
         """samples: (H, W, spp, 3) device tensor; weights: (H, W, spp) or None"""
@@ -1960,6 +2043,17 @@ class Sequence:
     def set_reuse(self, on):
         """False: every pair is searched directly from both sides (comparisons, tests)"""
         self.ctx._chk(lib().bcd_hip_sequence_set_reuse(self._handle(), int(bool(on))))
+
+    def set_prefilter(self, factor):
+        """bcd_hip_sequence_set_prefilter: every frame pushed from now on passes through the spike prefilter with this factor, once, in place in its slot
+        (<= 0: off).  Accepted while the sequence holds no frame"""
+        self.ctx._chk(lib().bcd_hip_sequence_set_prefilter(self._handle(), float(factor)))
+
+    def prefilter_info(self):
+        """bcd_hip_sequence_prefilter_info -> (frames filtered, pixels moved) since the creation or the last reset"""
+        n, m = C.c_int64(0), C.c_int64(0)
+        self.ctx._chk(lib().bcd_hip_sequence_prefilter_info(self._handle(), C.byref(n), C.byref(m)))
+        return n.value, m.value
 
     def last_masks(self, neighbour, scale=0):
         """bcd_hip_sequence_last_masks -> (mask, count) of the last popped frame at `scale`: neighbour 0 its in-frame set, 1 .. its neighbours in ascending

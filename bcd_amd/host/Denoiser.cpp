@@ -8,6 +8,7 @@
 #include "bcd_hip.h"
 
 #include <functional>
+#include <cmath>
 #include <cstdlib>
 #include <iostream>
 #include <limits>
@@ -82,7 +83,7 @@ namespace bcd
 			cerr << "Aborting denoising: colour layers are not available over several devices (row bands take one layer per call)" << endl;
 			return false;
 		}
-		if(m_prefilterThresholdStDevFactor > 0.f && !m_prefilterLayers)
+		if(m_prefilterThresholdStDevFactor > 0.f && !m_prefilterLayers && !(m_prefilterFrames && !m_neighbourFrames.empty())) // (beside neighbour frames setSpikePrefilterFrames covers every layer)
 		{
 			cerr << "Aborting denoising: the spike prefilter moves whole pixels by the primary colours and is not available with added colour layers (setSpikePrefilterLayers(true) gathers every layer through its decision)" << endl;
 			return false;
@@ -251,11 +252,18 @@ namespace bcd
 			return false;
 		}
 		const bool momentNeighbours = m_momentSelection && !m_neighbourFrames.empty();
+		// setSpikePrefilterFrames(true): every frame of a call with neighbour frames passes through the prefilter (bcd_hip_denoise_temporal_host_ex)
+		const bool prefilterFrames = m_prefilterFrames && m_prefilterThresholdStDevFactor > 0.f && !m_neighbourFrames.empty();
 		if(!inputsOutputsAreOk() || !layersAreOk() || !guideIsOk())
 			return false;
 		m_width = m_inputs.m_pColors->getWidth();
 		m_height = m_inputs.m_pColors->getHeight();
 		m_nbOfPixels = m_width * m_height;
+		if(prefilterFrames && (m_width < 3 || m_height < 3 || !std::isfinite(m_prefilterThresholdStDevFactor)))
+		{
+			cerr << "Aborting denoising: the spike prefilter of every frame (setSpikePrefilterFrames) needs a finite factor and frames of at least 3x3 pixels" << endl;
+			return false;
+		}
 		if(momentNeighbours)
 		{	// the size checks of the moment neighbours, before any device is asked for
 			auto fits = [&](const DeepImage<float>* i_pImage, int i_depth)
@@ -263,7 +271,7 @@ namespace bcd
 				return i_pImage && i_pImage->getWidth() == m_width && i_pImage->getHeight() == m_height && i_pImage->getDepth() == i_depth;
 			};
 			const size_t nbOfLayers = m_layers.size();
-			bool ok = !(m_prefilterThresholdStDevFactor > 0.f) && m_neighbourLayers.size() == m_neighbourFrames.size() && m_neighbourMotion.size() == m_neighbourFrames.size();
+			bool ok = (!(m_prefilterThresholdStDevFactor > 0.f) || m_prefilterFrames) && m_neighbourLayers.size() == m_neighbourFrames.size() && m_neighbourMotion.size() == m_neighbourFrames.size();
 			for(size_t k = 0; ok && k < m_neighbourFrames.size(); ++k)
 			{
 				const DenoiserInputs& f = m_neighbourFrames[k];
@@ -426,6 +434,14 @@ namespace bcd
 					for(size_t k = 0; k < nbOfNeighbours; ++k)
 						neighbourGuides[k] = { m_neighbourGuides[k].m_pFeatures->getDataPtr(), m_neighbourGuides[k].m_pVariances ? m_neighbourGuides[k].m_pVariances->getDataPtr() : nullptr };
 				}
+				if(prefilterFrames)
+				{
+					const bcd_hip_temporal_host_options frameOpt = { m_prefilterThresholdStDevFactor, nullptr };
+					rc = bcd_hip_denoise_temporal_host_ex(rSlot.m_pCtx, pIn[1], nullptr, layeredFrames.data(), int(nbOfNeighbours), anyMotion ? motion.data() : nullptr, m_width,
+							m_height, 0, i_nbOfScales, &prm, m_momentVarianceFloor, layers.data(), int(layers.size()), m_pGuideFeatures ? &guide : nullptr,
+							m_pGuideFeatures ? neighbourGuides.data() : nullptr, &frameOpt);
+				}
+				else
 				rc = bcd_hip_denoise_temporal_moments_host(rSlot.m_pCtx, pIn[1], layeredFrames.data(), int(nbOfNeighbours), anyMotion ? motion.data() : nullptr, m_width, m_height,
 						i_nbOfScales, &prm, m_momentVarianceFloor, layers.data(), int(layers.size()), m_pGuideFeatures ? &guide : nullptr,
 						m_pGuideFeatures ? neighbourGuides.data() : nullptr);
@@ -485,7 +501,7 @@ namespace bcd
 				{
 					return i_pImage && i_pImage->getWidth() == m_width && i_pImage->getHeight() == m_height && i_pImage->getDepth() == i_depth;
 				};
-				bool ok = !(m_prefilterThresholdStDevFactor > 0.f) && m_neighbourLayers.size() == m_neighbourFrames.size() && m_neighbourMotion.size() == m_neighbourFrames.size();
+				bool ok = (!(m_prefilterThresholdStDevFactor > 0.f) || m_prefilterFrames) && m_neighbourLayers.size() == m_neighbourFrames.size() && m_neighbourMotion.size() == m_neighbourFrames.size();
 				std::vector<const float*> motion(m_neighbourFrames.size(), nullptr); // (a neighbour without a field: zero motion)
 				bool anyMotion = false;
 				for(size_t k = 0; ok && k < m_neighbourFrames.size(); ++k)
@@ -518,7 +534,41 @@ namespace bcd
 					bcd_hip_set_progress_callback(rSlot.m_pCtx, nullptr, nullptr);
 					return false;
 				}
-				if(m_pGuideFeatures)
+				if(prefilterFrames)
+				{	// every frame through the spike prefilter on its own, then the call its arguments name: layers, motion fields and the feature gate as without it
+					std::vector<bcd_hip_layer> layers(nbOfLayers + 1);
+					layers[0] = { pIn[0], pIn[3], result.getDataPtr() };
+					for(size_t k = 0; k < nbOfLayers; ++k)
+					{
+						layerResults[k].resize(m_width, m_height, 3);
+						layers[k + 1] = { m_layers[k].m_pColors->getDataPtr(), m_layers[k].m_pSampleCovariances->getDataPtr(), layerResults[k].getDataPtr() };
+					}
+					bcd_hip_guide guide;
+					std::vector<bcd_hip_guide_images> neighbourGuides(m_neighbourFrames.size());
+					if(m_pGuideFeatures)
+					{	// (guideIsOk has checked the neighbours' buffers)
+						guide.features = m_pGuideFeatures->getDataPtr();
+						guide.variances = m_pGuideVariances ? m_pGuideVariances->getDataPtr() : nullptr;
+						guide.nb_channels = m_pGuideFeatures->getDepth();
+						guide.floors = m_guideFloors.data();
+						guide.threshold = m_guideThreshold;
+						for(size_t k = 0; k < m_neighbourFrames.size(); ++k)
+							neighbourGuides[k] = { m_neighbourGuides[k].m_pFeatures->getDataPtr(), m_neighbourGuides[k].m_pVariances ? m_neighbourGuides[k].m_pVariances->getDataPtr() : nullptr };
+					}
+					const bcd_hip_temporal_host_options frameOpt = { m_prefilterThresholdStDevFactor, nullptr };
+					rc = bcd_hip_denoise_temporal_host_ex(rSlot.m_pCtx, pIn[1], pIn[2], layeredFrames.data(), int(layeredFrames.size()), anyMotion ? motion.data() : nullptr, m_width,
+							m_height, depth, i_nbOfScales, &prm, 0.f, layers.data(), int(layers.size()), m_pGuideFeatures ? &guide : nullptr,
+							m_pGuideFeatures ? neighbourGuides.data() : nullptr, &frameOpt);
+					if(rc == BCD_HIP_OK && m_zeroBadOutputValues)
+						for(size_t k = 0; k < nbOfLayers; ++k)
+						{
+							float* p = layerResults[k].getDataPtr();
+							for(size_t i = 0, n = size_t(m_nbOfPixels) * 3; i < n; ++i)
+								if(!(p[i] >= 0.f) || !(p[i] <= std::numeric_limits<float>::max()))
+									p[i] = 0.f;
+						}
+				}
+				else if(m_pGuideFeatures)
 				{	// the gate of the feature buffers on the in-frame and on every cross-frame selection (guideIsOk has checked the neighbours' buffers); the
 					// primary images are layer 0 of every frame, added layers and motion fields as without the guide
 					std::vector<bcd_hip_layer> layers(nbOfLayers + 1);
@@ -657,6 +707,7 @@ namespace bcd
 		engine.setNeighbourGuides(m_neighbourGuides);
 		engine.setNeighbourMomentFlags(m_neighbourMoments);
 		engine.setSpikePrefilterLayers(m_prefilterLayers);
+		engine.setSpikePrefilterFrames(m_prefilterFrames);
 		engine.setMomentSelection(m_momentSelection, m_momentVarianceFloor);
 		engine.setGuideFeatures(m_pGuideFeatures, m_pGuideVariances, m_guideFloors, m_guideThreshold);
 		const bool ok = engine.denoiseWithNbOfScales(m_nbOfScales);

@@ -63,13 +63,13 @@ namespace bcd
 			cerr << "Aborting denoising: a sequence is not available over several devices" << endl;
 			return false;
 		}
-		if(!m_frameSettings && (!m_layers.empty() || !m_neighbourFrames.empty() || m_momentSelection || m_pGuideFeatures || m_prefilterThresholdStDevFactor > 0.f))
+		if(!m_frameSettings && (!m_layers.empty() || !m_neighbourFrames.empty() || m_momentSelection || m_pGuideFeatures || (m_prefilterThresholdStDevFactor > 0.f && !m_prefilterFrames)))
 		{
 			cerr << "Aborting denoising: a sequence takes no added colour layers, no neighbour frames of its own (the window supplies them), no moment selection, no "
 					"feature buffers and no spike prefilter" << endl;
 			return false;
 		}
-		if(!m_neighbourFrames.empty() || m_prefilterThresholdStDevFactor > 0.f)
+		if(!m_neighbourFrames.empty() || (m_prefilterThresholdStDevFactor > 0.f && !m_prefilterFrames)) // (setSpikePrefilterFrames(true): every pushed frame is prefiltered once)
 		{
 			cerr << "Aborting denoising: a sequence takes no neighbour frames of its own (the window supplies them) and no spike prefilter" << endl;
 			return false;
@@ -200,6 +200,12 @@ namespace bcd
 					return false;
 				}
 			}
+			const bool prefilter = m_prefilterFrames && m_prefilterThresholdStDevFactor > 0.f;
+			if(prefilter && (w < 3 || h < 3 || !(m_prefilterThresholdStDevFactor <= std::numeric_limits<float>::max())))
+			{
+				cerr << "Aborting denoising: the spike prefilter of every frame (setSpikePrefilterFrames) needs a finite factor and frames of at least 3x3 pixels" << endl;
+				return false;
+			}
 			bcd_hip_params prm;
 			bcd_hip_default_params(&prm);
 			prm.hist_dist_threshold = m_parameters.m_histogramDistanceThreshold;
@@ -233,6 +239,13 @@ namespace bcd
 			if(rc != BCD_HIP_OK)
 			{
 				cerr << "Aborting denoising: " << bcd_hip_last_error(pCtx) << endl;
+				m_pSequence = nullptr;
+				return false;
+			}
+			if(prefilter && bcd_hip_sequence_set_prefilter(m_pSequence, m_prefilterThresholdStDevFactor) != BCD_HIP_OK)
+			{	// (the factor of the first frame serves the sequence, like its mode)
+				cerr << "Aborting denoising: " << bcd_hip_last_error(pCtx) << endl;
+				bcd_hip_sequence_destroy(m_pSequence);
 				m_pSequence = nullptr;
 				return false;
 			}

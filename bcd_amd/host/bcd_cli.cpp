@@ -61,6 +61,7 @@ namespace
 		struct Neighbour { string m_nbOfSamplesArgument; /* --neighbour-nsamples */ string m_colorPath; Deepimf m_colorImage, m_nbOfSamplesImage, m_histogramImage, m_covarianceImage; std::vector<NeighbourLayer> m_layers; /* --neighbour-layer */ string m_motionPath; Deepimf m_motionImage; /* --neighbour-motion */ string m_featurePath, m_featureVariancePath; Deepimf m_featureImage, m_featureVarianceImage; /* --neighbour-features, --neighbour-feature-variances */ };
 		std::vector<Neighbour> m_neighbours; // --neighbour, in command-line order
 		std::vector<Layer> m_layers; // --layer, in command-line order
+		bool m_prefilterFrames = false; // --prefilter-frames: -p 1 beside --neighbour* or --sequence-in, every frame prefiltered on its own (setSpikePrefilterFrames)
 		bool m_prefilterLayers = false; // --prefilter-layers: -p 1 beside --layer, every layer gathered through the decision taken on the -i colours
 		bool m_momentSelection = false; // --moment-selection: similar patches from the -i colours and the -c covariances, no histogram file
 		float m_momentVarianceFloor = 1.e-8f;
@@ -99,11 +100,11 @@ namespace
 		cout << "                         the variances of that neighbour's features (given exactly when --feature-variances is)" << endl;
 		cout << "    --neighbour-layer <color> <cov>" << endl;
 		cout << "                         a colour layer of the most recent --neighbour: the k-th one pairs with the k-th --layer; every neighbour" << endl;
-		cout << "                         needs exactly one per --layer (one selection over all frames then serves every layer; needs -p 0)" << endl;
+		cout << "                         needs exactly one per --layer (one selection over all frames then serves every layer; needs -p 0 or --prefilter-frames)" << endl;
 		cout << "    --sequence-in <pattern> --sequence-out <pattern> --first <a> --last <b> [--temporal-radius <R>]" << endl;
 		cout << "                         in place of -i / -o: the frames a .. b of an animation, the patterns holding one %d (or %04d ...) for the frame number;" << endl;
 		cout << "                         every frame is denoised with its neighbours within R frames (1 or 2, default 1) and written to its output name." << endl;
-		cout << "                         Expects <frame>_hist.exr / <frame>_cov.exr beside every input, as --neighbour does; needs -p 0, -w 1, -b 6 and a single" << endl;
+		cout << "                         Expects <frame>_hist.exr / <frame>_cov.exr beside every input, as --neighbour does; needs -p 0 or --prefilter-frames, -w 1, -b 6 and a single" << endl;
 		cout << "                         device; not with -i, -o, -h, -c, --neighbour, --layer, --features or --moment-selection" << endl;
 		cout << "    --sequence-layer <colours pattern> <covariances pattern> <output pattern>" << endl;
 		cout << "                         beside --sequence-in: a further colour layer of every frame (repeatable, at most 15), denoised with the frame's selection" << endl;
@@ -134,6 +135,9 @@ namespace
 		cout << "    --prefilter-layers   with -p 1 (given or by default) and --layer: the spike prefilter decides on the -i colours which neighbour" << endl;
 		cout << "                         replaces a pixel, and every layer's colours and covariances are gathered through that decision on the device;" << endl;
 		cout << "                         no effect with -p 0" << endl;
+		cout << "    --prefilter-frames   with -p 1 (given or by default) beside --neighbour* or --sequence-in: every frame -- the -i frame and each neighbour," << endl;
+		cout << "                         every frame of a sequence -- passes through the spike prefilter on its own, all its layers following the decision" << endl;
+		cout << "                         taken on its own colours; feature buffers and motion fields are not moved; no effect with -p 0" << endl;
 		cout << "    --moment-selection [floor]" << endl;
 		cout << "                         select similar patches from the -i colours and the -c covariances instead of histograms: no histogram file is" << endl;
 		cout << "                         looked for, -d then thresholds the variance-normalised squared difference of the pixel means (1 on average between" << endl;
@@ -167,6 +171,7 @@ namespace
 			const string flag = argv[i];
 			if(flag == "--help") { printUsage(); return false; }
 			if(flag == "--prefilter-layers") { a.m_prefilterLayers = true; continue; }
+			if(flag == "--prefilter-frames") { a.m_prefilterFrames = true; continue; }
 			if(flag == "--moment-selection")
 			{
 				a.m_momentSelection = true;
@@ -558,7 +563,7 @@ namespace
 			}
 			if(rLayer.m_outputPath == a.m_denoisedOutputFilePath) { cout << "ERROR in program arguments: layer output '" << rLayer.m_outputPath << "' is also the -o output" << endl; return false; }
 		}
-		if(!a.m_layers.empty() && a.m_prefilterSpikes && !a.m_prefilterLayers)
+		if(!a.m_layers.empty() && a.m_prefilterSpikes && !a.m_prefilterLayers && !(a.m_prefilterFrames && !a.m_neighbours.empty())) // (beside neighbours --prefilter-frames covers every layer)
 		{
 			cout << "ERROR in program arguments: --layer is not available with the spike prefilter (it moves whole pixels by the -i colours): add -p 0, or --prefilter-layers to gather every layer through its decision" << endl;
 			return false;
@@ -631,7 +636,7 @@ namespace
 	int launchSequenceDenoising(int argc, const char** argv)
 	{
 		ProgramArguments a;
-		a.m_prefilterSpikes = true; // (the CLI's default: the sequence has no prefilter, so -p 0 must be said)
+		a.m_prefilterSpikes = true; // (the CLI's default: the sequence takes the prefilter through --prefilter-frames only, else -p 0 must be said)
 		string inPattern, outPattern;
 		int first = 0, last = -1, radius = 1;
 		bool hasFirst = false, hasLast = false;
@@ -647,6 +652,7 @@ namespace
 		{
 			const string flag = argv[i];
 			if(flag == "--help") { printUsage(); return 1; }
+			if(flag == "--prefilter-frames") { a.m_prefilterFrames = true; continue; }
 			for(const char* pOther : { "-i", "-o", "-h", "-c", "-a", "--neighbour", "--neighbour-nsamples", "--neighbour-motion", "--neighbour-features", "--neighbour-feature-variances",
 					"--neighbour-layer", "--layer", "--prefilter-layers", "--moment-selection", "--nsamples", "--features", "--feature-variances", "--feature-floors",
 					"--feature-threshold", "--devices" })
@@ -717,7 +723,7 @@ namespace
 			else if(flag == "--use-cuda") a.m_useCuda = atoi(value) == 1;
 			else if(flag == "--seed") a.m_orderSeed = unsigned(strtoul(value, nullptr, 10));
 			else if(flag == "--device") a.m_devices.assign(1, atoi(value));
-			else if(flag == "--p-factor") {}
+			else if(flag == "--p-factor") { const float v = float(atof(value)); if(v > 0.f) a.m_prefilterThresholdStDevFactor = v; } // (read by --prefilter-frames)
 			else return argumentError("unknown argument " + flag + " (beside --sequence-in)");
 		}
 		if(!isFramePattern(inPattern)) return argumentError("--sequence-in needs a file pattern with one %d for the frame number, like frames/shot.%04d.exr");
@@ -725,7 +731,7 @@ namespace
 		if(inPattern == outPattern) return argumentError("--sequence-out would overwrite the --sequence-in frames");
 		if(!hasFirst || !hasLast || first < 0 || last < first) return argumentError("--first <a> and --last <b> with 0 <= a <= b are required beside --sequence-in");
 		if(radius < 1 || radius > 2) return argumentError("--temporal-radius must be 1 or 2");
-		if(a.m_prefilterSpikes) return argumentError("--sequence-in is not available with the spike prefilter: add -p 0");
+		if(a.m_prefilterSpikes && !a.m_prefilterFrames) return argumentError("--sequence-in is not available with the spike prefilter: add -p 0, or --prefilter-frames");
 		if(a.m_patchRadius != 1 || a.m_searchWindowRadius != 6) return argumentError("--sequence-in needs -w 1 and -b 6 (neighbour frames support no other geometry)");
 		if(frameName(inPattern, first).length() <= 4) return argumentError("'" + frameName(inPattern, first) + "' is no .exr file name");
 		if(layers.size() > 15) return argumentError("at most 15 --sequence-layer arguments");
@@ -760,6 +766,11 @@ namespace
 		sequence.setDevices(a.m_devices);
 		sequence.setZeroBadOutputValues(true);
 		sequence.setFrameSettings(frameSettings);
+		if(a.m_prefilterSpikes && a.m_prefilterFrames)
+		{	// every pushed frame is prefiltered once, in place in its slot
+			sequence.setSpikePrefilterFrames(true);
+			sequence.setSpikePrefilter(a.m_prefilterThresholdStDevFactor);
+		}
 		if(moments) sequence.setMomentSelection(true, momentFloor);
 		if(!sequence.settingsAreOk())
 			return 1;
@@ -912,6 +923,7 @@ namespace
 		if(prefilterOnDevice)
 			pSettings->setSpikePrefilter(args.m_prefilterThresholdStDevFactor);
 		pSettings->setSpikePrefilterLayers(args.m_prefilterLayers);
+		pSettings->setSpikePrefilterFrames(args.m_prefilterFrames);
 		pSettings->setMomentSelection(args.m_momentSelection, args.m_momentVarianceFloor);
 		if(!args.m_featurePath.empty())
 			pSettings->setGuideFeatures(&args.m_featureImage, args.m_featureVariancePath.empty() ? nullptr : &args.m_featureVarianceImage, args.m_featureFloors, args.m_featureThreshold);

@@ -430,6 +430,18 @@ void bcdcore_release_engines() { releaseEngines(); }
 
 // runs bcd::Denoiser (nscales == 1) or bcd::MultiscaleDenoiser through the IDenoiser interface; returns denoise()'s bool.
 // Null pointers are forwarded as null images to exercise the validation path.
+/// The spike prefilter of the denoise_temporal* / denoise_sequence* wrappers, whose argument lists are fixed: what the calling thread's next such call sets on
+/// its denoiser -- setSpikePrefilter(factor) when factor > 0 and setSpikePrefilterFrames(framesSwitch != 0).  The Python wrapper sets it ahead of the call and
+/// puts it back to (0, 0) behind it; per thread, so that two threads' calls do not see each other's setting
+static thread_local float t_prefilterFactor = 0.f;
+static thread_local bool t_prefilterFramesSwitch = false;
+void bcdcore_set_frame_prefilter(float factor, int framesSwitch) { t_prefilterFactor = factor; t_prefilterFramesSwitch = framesSwitch != 0; }
+static void applyFramePrefilter(bcd::HipEngineSettings& io_rSettings)
+{
+	if(t_prefilterFactor > 0.f)
+		io_rSettings.setSpikePrefilter(t_prefilterFactor);
+	io_rSettings.setSpikePrefilterFrames(t_prefilterFramesSwitch);
+}
 static int g_lastProgressValues = 0;
 /// number of distinct progress values the last bcdcore_denoise reported
 int bcdcore_last_progress_values() { return g_lastProgressValues; }
@@ -687,6 +699,7 @@ static int denoiseTemporal(const float* col, const float* ns, const float* hist,
 	if(nscales > 1) { multi.reset(new MultiscaleDenoiser(nscales)); d = multi.get(); pSettings = multi.get(); }
 	else { mono.reset(new Denoiser()); d = mono.get(); pSettings = mono.get(); }
 	pSettings->setOrderSeed(seed);
+	applyFramePrefilter(*pSettings);
 	for(int k = 0; k < nbOfNeighbours; ++k)
 	{
 		c[k].resize(W, H, 3); n[k].resize(W, H, 1); h[k].resize(W, H, D); v[k].resize(W, H, 6);
@@ -751,6 +764,7 @@ int bcdcore_denoise_sequence(const float* cols, const float* nss, const float* h
 	p.m_markedPixelsSkippingProbability = skipProbability;
 	sequence.setParameters(p);
 	sequence.setOrderSeed(seed);
+	applyFramePrefilter(sequence);
 	Deepimf extra(W, H, 3), extraCov(W, H, 6), extraOut;
 	DenoiserInputs extraFrame;
 	if(unsupported & 1) sequence.addLayer(&extra, &extraCov, &extraOut);
@@ -814,6 +828,7 @@ int bcdcore_denoise_sequence_modes(const float* cols, const float* nss, const fl
 	p.m_markedPixelsSkippingProbability = skipProbability;
 	sequence.setParameters(p);
 	sequence.setOrderSeed(seed);
+	applyFramePrefilter(sequence);
 	sequence.setFrameSettings(true);
 	if(!hists) sequence.setMomentSelection(true, varFloor);
 	DenoiserInputs extraFrame;
@@ -925,6 +940,7 @@ static int denoiseTemporalLayers(const float* cols, const float* covs, const flo
 	if(nscales > 1) { multi.reset(new MultiscaleDenoiser(nscales)); d = multi.get(); pSettings = multi.get(); }
 	else { mono.reset(new Denoiser()); d = mono.get(); pSettings = mono.get(); }
 	pSettings->setOrderSeed(seed);
+	applyFramePrefilter(*pSettings);
 	for(int k = 1; k < nbOfLayers; ++k)
 		pSettings->addLayer(&c[k], &v[k], &o[k]);
 	for(int f = 0; f < nbOfNeighbours; ++f)
@@ -1059,6 +1075,7 @@ int bcdcore_denoise_temporal_moments(const float* cols, const float* covs, const
 	if(nscales > 1) { multi.reset(new MultiscaleDenoiser(nscales)); d = multi.get(); pSettings = multi.get(); }
 	else { mono.reset(new Denoiser()); d = mono.get(); pSettings = mono.get(); }
 	pSettings->setOrderSeed(seed);
+	applyFramePrefilter(*pSettings);
 	if(momentSelection)
 		pSettings->setMomentSelection(true, varianceFloor);
 	else

@@ -19,7 +19,7 @@ namespace bcd
 	class HipEngineSettings
 	{
 	public:
-		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false), m_momentSelection(false), m_momentVarianceFloor(1e-8f),
+		HipEngineSettings() : m_orderSeed(1234u), m_devices(1, 0), m_prefilterThresholdStDevFactor(0.f), m_zeroBadOutputValues(false), m_prefilterLayers(false), m_prefilterFrames(false), m_momentSelection(false), m_momentVarianceFloor(1e-8f),
 				m_pGuideFeatures(nullptr), m_pGuideVariances(nullptr), m_guideThreshold(1.f) {}
 
 		/// seed of the visiting order of -r 1 (the reference seeds its shuffle from the wall clock, src/core/Denoiser.cpp:418)
@@ -59,6 +59,13 @@ namespace bcd
 		/// device (bcd_hip_denoise_layers_host_ex).  false (default): the combination is refused, as it always was.
 		void setSpikePrefilterLayers(bool i_enabled) { m_prefilterLayers = i_enabled; }
 		bool getSpikePrefilterLayers() const { return m_prefilterLayers; }
+		/// true: a spike prefilter beside neighbour frames (addNeighbourFrame, addNeighbourFrameMoments) and in a SequenceDenoiser is accepted: EVERY frame is
+		/// prefiltered on its own -- its sample counts, its histograms and all its layers gathered through the decision taken on its own primary colours, in its
+		/// own pixel grid (before a motion field reprojects it); feature buffers are not moved (bcd_hip_denoise_temporal_host_ex,
+		/// bcd_hip_sequence_set_prefilter).  Beside neighbour frames the switch covers every layer of every frame and setSpikePrefilterLayers is not consulted.
+		/// Without neighbour frames it changes nothing.  false (default): the combinations are refused, as they always were.
+		void setSpikePrefilterFrames(bool i_enabled) { m_prefilterFrames = i_enabled; }
+		bool getSpikePrefilterFrames() const { return m_prefilterFrames; }
 		/// true: similar patches are selected from the primary colours and sample covariances (bcd_hip_denoise_moments_host) and NO histogram image is
 		/// required -- DenoiserInputs::m_pHistograms may stay null.  m_histogramDistanceThreshold then thresholds the variance-normalised squared
 		/// difference of the pixel means (expectation 1 between pixels of equal signal), not the chi-square histogram distance.  i_varFloor (finite, >= 0)
@@ -87,8 +94,8 @@ namespace bcd
 		/// A neighbouring frame of the sequence (t - 1, t + 1, ...) that lends its statistics to the frame in DenoiserInputs (bcd_hip_denoise_temporal_host):
 		/// similar patches are also searched in the same window of every neighbour frame, and mean, noise mean and covariance of the estimate come from the
 		/// union of the sets; only the frame itself is denoised.  Each neighbour brings all four images, of the frame's width, height and histogram depth.
-		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; not together with the spike
-		/// prefilter; under the moment selection see addNeighbourFrameMoments; feature buffers need setNeighbourGuideFeatures for every neighbour.  With no neighbour denoise() is what it always was.
+		/// Non-owning pointers, like DenoiserInputs.  At most 4 neighbours, patch radius 1 and search radius 6, one device; together with the spike
+		/// prefilter only under setSpikePrefilterFrames(true); under the moment selection see addNeighbourFrameMoments; feature buffers need setNeighbourGuideFeatures for every neighbour.  With no neighbour denoise() is what it always was.
 		void addNeighbourFrame(const DenoiserInputs& i_rFrame)
 		{
 			m_neighbourFrames.push_back(i_rFrame); m_neighbourLayers.emplace_back(); m_neighbourMotion.push_back(nullptr); m_neighbourGuides.emplace_back();
@@ -172,6 +179,7 @@ namespace bcd
 		float m_prefilterThresholdStDevFactor;
 		bool m_zeroBadOutputValues;
 		bool m_prefilterLayers;
+		bool m_prefilterFrames;
 		bool m_momentSelection;
 		float m_momentVarianceFloor;
 		const DeepImage<float>* m_pGuideFeatures;

@@ -23,7 +23,8 @@ namespace bcd
 	///  - setMomentSelection(true, floor): every selection from means and covariances; DenoiserInputs::m_pHistograms may stay null and is not looked at;
 	///  - setGuideFeatures: the features (and variances) set when pushFrame() is called are that frame's; floors and threshold are those of the first frame.
 	/// The first frame fixes the mode: the number of layers, the selection, the feature channels and whether there are variances; reset() frees it.
-	/// The settings a sequence does not serve -- neighbour frames of its own, motion fields, the spike prefilter, several devices -- make pushFrame() return
+	/// The settings a sequence does not serve -- neighbour frames of its own, motion fields, the spike prefilter without setSpikePrefilterFrames(true) (with it every
+	/// pushed frame is prefiltered once, on its own: bcd_hip_sequence_set_prefilter), several devices -- make pushFrame() return
 	/// false, like a patch radius other than 1, a search radius other than 6, a temporal radius outside 1 .. 2, more than 15 added layers, a feature image
 	/// outside 1 .. 8 channels, floors that are negative, not finite, of another count or unable to count, a frame that differs from the first frame's
 	/// mode; every refusal comes before any device is asked for, with a message on cerr.

@@ -366,8 +366,8 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
  *   neighbour `neighbour` of the popped frame at `scale`: 0 the in-frame set, 1 .. the neighbours in ascending frame order.  _reset forgets every frame and
  *   counter and keeps the buffers.  _destroy frees them; a sequence must be destroyed before its context.
  *   Scope: histogram selection, one colour layer, patch radius 1, search radius 6, radius 1 .. 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS).  Colour layers, the
- *   feature gate and the moment selection come through bcd_hip_sequence_create_mode further down; motion fields (a warped neighbour breaks the symmetry),
- *   the spike prefilter, row bands and several GPUs are out.
+ *   feature gate and the moment selection come through bcd_hip_sequence_create_mode further down, the spike prefilter through
+ *   bcd_hip_sequence_set_prefilter; motion fields (a warped neighbour breaks the symmetry), row bands and several GPUs are out.
  *   Refused before any device work, with a message: what bcd_hip_denoise_temporal refuses; a radius outside 1 .. 2; any other geometry
  *   (BCD_HIP_EUNSUPPORTED); a null image; a push beyond the ring or after _end; a pop that is not ready.
  * A sequence handle is an opaque pointer, written by _create and passed as void *. */
@@ -412,9 +412,10 @@ void bcd_hip_sequence_destroy(void *seq);
  * Refused before any device work, with a message, the context staying usable: everything bcd_hip_denoise_temporal and bcd_hip_denoise_layers refuse; a NULL
  * layer list in a neighbour; a NULL image in any layer of any frame; a non-NULL `reserved`; an output that is, or overlaps, any input of any frame or
  * another output; with neighbours, any geometry but patch radius 1 and search radius 6 (BCD_HIP_EUNSUPPORTED).  Kept selections, the moment
- * selection, the spike prefilter, row bands and bcd_hip_multi_* do not combine with this call; motion vectors arrive through
+ * selection, row bands and bcd_hip_multi_* do not combine with this call (the spike prefilter: bcd_hip_denoise_temporal_host_ex); motion vectors arrive through
  * bcd_hip_denoise_temporal_layers_motion below, the feature-gated selection through bcd_hip_denoise_temporal_guided.
- *   _host: every pointer is a host pointer; whole uploads (no streaming, no spike prefilter), the resident call, one download per layer: the same result.
+ *   _host: every pointer is a host pointer; whole uploads (no streaming, no spike prefilter: that is bcd_hip_denoise_temporal_host_ex), the resident call, one
+ *             download per layer: the same result.
  *   _bayes_accumulate_temporal_layers: the estimate stage -- the twin of bcd_hip_bayes_accumulate_temporal for nb_layers layers on ONE selection.  frames[f]
  *             holds host arrays of nb_layers device pointers (the colours and the per-pixel covariances of that frame's layers) and the frame's masks, [0]
  *             being the frame itself; d_sum is a host array of nb_layers device pointers.  It writes ONE count image, per layer one sum image (accumulated
@@ -529,7 +530,8 @@ int bcd_hip_gate_masks_valid(bcd_hip_ctx *ctx, uint32_t *d_mask, int32_t *d_coun
  *   _warp_features: the gather of bcd_hip_warp_layers for the feature image (and the variance image: d_variances_out is NULL exactly when in->variances is)
  *             of nb_channels floats per pixel; d_valid W*H bytes.  A destination that overlaps an input, the field or another destination is refused.
  * The stage calls accept what bcd_hip_similarity_masks_cross accepts (w <= 2, b <= 15) with F <= 8, refuse the rest before any device work, and synchronise.
- * Kept selections, the moment selection, the spike prefilter, search radius 12, row bands and bcd_hip_multi_* do not combine with these calls. */
+ * Kept selections, the moment selection, search radius 12, row bands and bcd_hip_multi_* do not combine with these calls; the spike prefilter comes through
+ * bcd_hip_denoise_temporal_host_ex (a resident caller composes bcd_hip_spike_filter_layers with the call). */
 typedef struct { const float *features; const float *variances; /* NULL iff the guide's are */ } bcd_hip_guide_images;
 int bcd_hip_denoise_temporal_guided(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms, const bcd_hip_frame_layers *neighbours, int nb_neighbours,
                                     const float *const *d_motion /* NULL: nothing is warped; else nb_neighbours entries, each NULL or W*H*2 */, int W, int H, int D,
@@ -588,7 +590,8 @@ int bcd_hip_warp_features(bcd_hip_ctx *ctx, const bcd_hip_guide_images *in, int 
  *             form 2 returns BCD_HIP_EUNSUPPORTED.  Every form gives the same masks and counts, bit for bit.
  *   _window_distances_moments_cross: the twin of bcd_hip_window_distances_cross: the (2b+1)^2 cross moment distances of one main pixel, +inf outside.
  * The stage calls accept what bcd_hip_similarity_masks_moments accepts (w <= 2, b <= 15, a finite var_floor >= 0), refuse the rest before any device work,
- * and synchronise.  Kept selections, the spike prefilter, row bands, bcd_hip_multi_* and any search radius other than 6 do not combine with the frame calls. */
+ * and synchronise.  Kept selections, row bands, bcd_hip_multi_* and any search radius other than 6 do not combine with the frame calls; the spike prefilter
+ * comes through bcd_hip_denoise_temporal_host_ex (a resident caller composes bcd_hip_spike_filter_layers with the call). */
 int bcd_hip_similarity_masks_moments_cross(bcd_hip_ctx *ctx, const float *d_colors, const float *d_pixel_cov, const float *d_colors_nb, const float *d_pixel_cov_nb,
                                            int W, int H, int patch_radius, int search_radius, float threshold, float var_floor, int form, uint32_t *d_mask_nb,
                                            int32_t *d_count_nb);
@@ -628,7 +631,8 @@ int bcd_hip_denoise_temporal_moments_host(bcd_hip_ctx *ctx, const float *h_nsamp
  *   patch radius 1 and search radius 6: BCD_HIP_EUNSUPPORTED); L outside 1 .. 16, F outside 0 .. 8; a guide that cannot count; a negative or non-finite floor,
  *   threshold or var_floor; a cross feature kernel that cannot be launched; a non-NULL `reserved`; a push whose shape does not match the mode; a pop with a
  *   wrong layer count or a null output; a plain call on a sequence of another mode and the reverse.
- *   Out of scope: motion fields (a warped pair is not symmetric, and its pyramids are per pair), the spike prefilter, row bands, several GPUs. */
+ *   Out of scope: motion fields (a warped pair is not symmetric, and its pyramids are per pair), row bands, several GPUs.  The spike prefilter comes
+ *   through bcd_hip_sequence_set_prefilter below. */
 typedef struct bcd_hip_sequence_mode {
     int32_t      nb_layers;
     int32_t      moments;
@@ -659,6 +663,39 @@ int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *fr
 int bcd_hip_sequence_pop_layers(void *seq, float *const *d_outs, int nb_layers, int64_t *frame_index);
 int bcd_hip_sequence_pop_layers_host(void *seq, float *const *h_outs, int nb_layers, int64_t *frame_index);
 int bcd_hip_sequence_mode_info(void *seq, struct bcd_hip_sequence_mode_info *info);
+
+/* ---- the spike prefilter in every frame of temporal calls and sequences ("Prefilter") ----
+ * Every frame is prefiltered on its own: the frame and each neighbour pass through bcd_hip_spike_filter_layers with the factor -- the sample counts, the
+ * histograms (unless in moment selection) and all L layers, the decision coming from that frame's own layer-0 colours -- and the result is what the existing
+ * call returns for the filtered frames; bcd_hip_get_stats reports likewise.  Feature and variance images are not moved (the precedent of
+ * bcd_hip_denoise_guided_host with a factor).  Motion fields are not moved: a neighbour is filtered in its own pixel grid BEFORE it is warped.  Every layer
+ * always follows the decision.  The filter runs in place (bcd_hip_spike_filter_layers_inplace) on the copies the library owns: no second set of frame
+ * buffers is allocated.
+ *   _denoise_temporal_host_ex: with opt == NULL or spike_factor <= 0 the call IS the existing host call that takes exactly these arguments, and delegates:
+ *             h_histograms NULL: bcd_hip_denoise_temporal_moments_host; else with a guide: bcd_hip_denoise_temporal_guided_host; else with h_motion:
+ *             bcd_hip_denoise_temporal_layers_motion_host; else bcd_hip_denoise_temporal_layers_host (var_floor is read in moment selection only).  With
+ *             spike_factor > 0 the uploaded copies of every frame are filtered behind the uploads, then the same call runs.  nb_neighbours == 0 with a factor
+ *             is the matching single-frame host call with that factor and filter_layers = 1 (bcd_hip_denoise_layers_host_ex, bcd_hip_denoise_guided_host,
+ *             bcd_hip_denoise_moments_host).  Refused before any device work: what the delegated call refuses; a non-NULL `reserved`; a NaN or infinite
+ *             factor; W or H < 3 with a factor.
+ *   The resident frame calls take no prefilter argument -- their inputs are the caller's const buffers: a resident caller composes
+ *   bcd_hip_spike_filter_layers (or _inplace, on buffers it may change) with the call.
+ *   _sequence_set_prefilter: factor <= 0: off (the default).  Accepted only while the sequence holds no frame -- after its creation or _reset --, refused
+ *             with a message otherwise, as are a NaN or infinite factor and a frame smaller than 3x3 with a factor.  It serves every mode.  Frame t then pops
+ *             as what the frame call of its mode returns for frames that were each filtered as above: masks, |S|, marking, lists and stats are bit for bit
+ *             those of that call, the frame differs by the order of the float atomics only.  Each frame is filtered once, by its push, in place in its
+ *             slot, ahead of its pyramid and per-pixel covariances; device pushes and host pushes take the same path; the slot's features stay as pushed.
+ *             Both directions of a pair see the same filtered frames, so the reuse counters equal those of a run without the prefilter.
+ *   _sequence_prefilter_info: frames filtered and pixels moved since the creation or the last _reset (struct bcd_hip_sequence_info keeps its layout).
+ * Out of scope: a temporal spike decision (outliers judged against other frames), moving feature images, row bands and several GPUs. */
+typedef struct { float spike_factor; const void *reserved; /* NULL */ } bcd_hip_temporal_host_options;
+int bcd_hip_denoise_temporal_host_ex(bcd_hip_ctx *ctx, const float *h_nsamples, const float *h_histograms /* NULL: moment selection */,
+                                     const bcd_hip_frame_layers *neighbours, int nb_neighbours, const float *const *h_motion /* NULL or nb_neighbours entries */,
+                                     int W, int H, int D, int nb_scales, const bcd_hip_params *prm, float var_floor /* moment selection only */,
+                                     const bcd_hip_layer *layers, int nb_layers, const bcd_hip_guide *guide /* NULL: no gate */,
+                                     const bcd_hip_guide_images *neighbour_guides, const bcd_hip_temporal_host_options *opt);
+int bcd_hip_sequence_set_prefilter(void *seq, float factor);   /* <= 0: off (the default) */
+int bcd_hip_sequence_prefilter_info(void *seq, int64_t *frames_filtered, int64_t *pixels_moved);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
@@ -943,6 +980,26 @@ typedef struct { const float *d_colors, *d_covariances; float *d_colors_out, *d_
 int bcd_hip_spike_filter_layers(bcd_hip_ctx *ctx, const float *d_nsamples, const float *d_histograms /* NULL: no histogram */, int W, int H, int D, float factor,
                                 float *o_nsamples, float *o_histograms /* NULL iff d_histograms is */, const bcd_hip_spike_layer *layers, int nb_layers /* 1..16 */,
                                 int32_t *d_map /* NULL: the context's scratch */, int32_t *d_moved /* NULL or device int32 */);
+/* In place ("In place"): for frames that already sit in buffers of their owner -- the slot of a sequence, the uploaded copies of a host
+ * call -- where a second copy of every image is the wrong price for moving a few percent of the pixels.
+ * Definition: with m(p) = M[p] when 0 <= M[p] < W*H, else p (the rule of _apply), after the call every image holds at pixel p, bit for bit, the values it
+ *   held BEFORE the call at pixel m(p).  Maps have chains (p <- q <- r), swaps, longer cycles and fan-out: the moved pixels (m(p) != p) are listed, their
+ *   source values of every image are copied to a staging buffer of the context (grow-only), and a second kernel copies them to their destinations.  Only
+ *   moved pixels are read or written; the order of the list varies from run to run and the result does not depend on it.
+ *   _apply_inplace: nb_images (1..32) images, image k of depth depths[k] (1 .. 2^24; `depths` a HOST array), gathered through the map in one call.
+ *   _filter_layers_inplace: the map from layers[0].d_colors (into d_map, or the context's scratch map), then one in-place gather of the sample counts, the
+ *            histograms (NULL: none, D is not read) and every layer's colours and covariances.  The images end with the bits bcd_hip_spike_filter_layers
+ *            writes into its separate outputs, and d_map with its map.
+ *   h_moved: NULL, or one HOST int32 that receives the number of moved pixels.
+ * Both calls read that number back to size the list and the staging buffer: they synchronise once; with no moved pixel nothing further is launched.
+ * Checked before any device work (BCD_HIP_EINVAL and a message, the context staying usable): null pointers, W or H < 3, W*H >= 2^31, a depth < 1 (or above
+ * 2^24), the image and layer counts, images that overlap each other or the map, histograms given with D < 1. */
+int bcd_hip_spike_apply_inplace(bcd_hip_ctx *ctx, const int32_t *d_map, int W, int H, const int32_t *depths /* HOST array, nb_images entries, each >= 1 */,
+                                float *const *d_images, int nb_images /* 1..32 */, int32_t *h_moved /* NULL or one host int32 */);
+typedef struct { float *d_colors, *d_covariances; } bcd_hip_spike_layer_inplace;
+int bcd_hip_spike_filter_layers_inplace(bcd_hip_ctx *ctx, float *d_nsamples, float *d_histograms /* NULL: none */, int W, int H, int D, float factor,
+                                        const bcd_hip_spike_layer_inplace *layers, int nb_layers /* 1..16 */,
+                                        int32_t *d_map /* NULL: the context's scratch map */, int32_t *h_moved);
 /* SamplesAccumulator::addSample + getSamplesStatistics for a whole frame   src/core/SamplesAccumulator.cpp:44-141
  * (lets a GPU renderer keep the statistics in HBM).  d_samples: W*H*spp*3 floats, the spp samples of a pixel contiguous
  * and in accumulation order; d_weights: W*H*spp floats or NULL (all 1).  Outputs in DeepImage layout, hist depth 3*nb_bins.
