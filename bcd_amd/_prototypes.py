@@ -330,6 +330,11 @@ PROTOTYPES = {
     "bcd_hip_denoise_temporal_host_ex": (I, [P, P, P, S(FrameLayers), I, P, I, I, I, I, S(Params), F, S(Layer), I, S(Guide), S(GuideImages), S(TemporalHostOptions)]),
     "bcd_hip_sequence_set_prefilter": (I, [P, F]),
     "bcd_hip_sequence_prefilter_info": (I, [P, P, P]),
+    # ---- sequences that take per-step motion fields ("Sequences with motion")
+    "bcd_hip_compose_motion": (I, [P, P, P, I, I, P]),
+    "bcd_hip_sequence_push_frame_motion": (I, [P, S(SequenceFrame), P, P]),
+    "bcd_hip_sequence_push_frame_motion_host": (I, [P, S(SequenceFrame), P, P]),
+    "bcd_hip_sequence_motion_info": (I, [P, P, P]),
     # (row bands, for multi-GPU tiling)
     "bcd_hip_denoise_band": (I, [P, P, P, P, P, I, I, I, I, I, S(Params), U32, P, P]),
     "bcd_hip_denoise_bands": (I, [P, S(BandJob), I, S(Params)]),

@@ -360,7 +360,7 @@ def denoise_temporal(col, ns, hist, cov, neighbours, nscales=1, tau=1.0, b=6, mi
 
 @_takes_prefilter_frames
 def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-8, random_order=True, m=1.0, seed=1234, unsupported=0, layers=None, features=None,
-                     feature_variances=None, feature_floors=(), feature_threshold=1.0, var_floor=1e-8, break_settings=0):
+                     feature_variances=None, feature_floors=(), feature_threshold=1.0, var_floor=1e-8, break_settings=0, motions=None, break_motion=0):
     """bcd::SequenceDenoiser: frames is a list of (col, ns, hist, cov) arrays of one size, pushed one by one and popped as they become ready; frame t comes out
     denoised with the frames t - radius .. t + radius that exist (what denoise_temporal returns for it with those neighbours in ascending order), every
     frame uploaded once and every pair of frames searched once.  unsupported: bits of settings the sequence must refuse (bcdcore_denoise_sequence).
@@ -368,9 +368,13 @@ def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-
     With `layers` (per frame a list of further (colours, covariances) beside the frame's own, which are layer 0), a frame whose hist is None (every frame:
     the selection from means and covariances with `var_floor`) or `features` (per frame an (H, W, F) image; feature_variances the same or None, with
     feature_floors and feature_threshold) the class runs with setFrameSettings(true) and the result is (ok, [[layer 0, layer 1, ...] per frame]);
-    break_settings: bits of settings that must be refused then (bcdcore_denoise_sequence_modes)"""
+    break_settings: bits of settings that must be refused then (bcdcore_denoise_sequence_modes).
+    motions: None, or per frame None or a (prev, next) pair -- the (H, W, 2) motion fields of that frame towards the frame before and after it, each an array or
+    None (SequenceDenoiser::setFrameMotion; bcdcore_denoise_sequence_motion); break_motion: bits of what a field must be refused for (1: three channels, 2:
+    another width).  The result has the shape it has without motions"""
     T = len(frames)
-    if layers is not None or features is not None or frames[0][2] is None or break_settings:
+    modes = layers is not None or features is not None or frames[0][2] is None or break_settings
+    if modes or motions is not None:
         H, W = np.asarray(frames[0][0]).shape[:2]
         hist = frames[0][2] is not None
         D = np.asarray(frames[0][2]).shape[2] if hist else 0
@@ -389,10 +393,24 @@ def denoise_sequence(frames, radius=1, nscales=1, tau=1.0, w=1, b=6, min_eig=1e-
         floors = np.ascontiguousarray(feature_floors, np.float32)
         outs = np.zeros((T, L, H, W, 3), np.float32)
         opt = lambda a: None if a is None else _fp(a)
-        rc = lib().bcdcore_denoise_sequence_modes(_fp(cols), _fp(nss), opt(hists), _fp(covs), opt(feats), opt(fvars), T, L, F, _fp(floors) if floors.size else None,
-                                                  int(floors.size), C.c_float(feature_threshold), C.c_float(var_floor), W, H, D, int(nscales), int(radius), C.c_float(tau),
-                                                  int(w), int(b), C.c_float(min_eig), 1 if random_order else 0, C.c_float(m), C.c_uint(seed), int(break_settings), _fp(outs))
-        return rc != 0, [[outs[k, j] for j in range(L)] for k in range(T)]
+        args = (_fp(cols), _fp(nss), opt(hists), _fp(covs), opt(feats), opt(fvars), T, L, F, _fp(floors) if floors.size else None, int(floors.size),
+                C.c_float(feature_threshold), C.c_float(var_floor), W, H, D, int(nscales), int(radius), C.c_float(tau), int(w), int(b), C.c_float(min_eig),
+                1 if random_order else 0, C.c_float(m), C.c_uint(seed), int(break_settings), _fp(outs))
+        if motions is None:
+            rc = lib().bcdcore_denoise_sequence_modes(*args)
+        else:
+            motions = list(motions)
+            if len(motions) != T:
+                raise ValueError("one (prev, next) pair of motion fields (or None) per frame expected (%d, not %d)" % (T, len(motions)))
+            fields = np.zeros((T, 2, H, W, 2), np.float32)
+            flags = (C.c_int * (2 * T))()
+            for k, pair in enumerate(motions):
+                for d, mv in enumerate(pair if pair is not None else (None, None)):
+                    if mv is not None:
+                        fields[k, d] = as32(mv, 2)
+                        flags[2 * k + d] = 1
+            rc = lib().bcdcore_denoise_sequence_motion(*args, _fp(fields), flags, int(break_motion))
+        return rc != 0, [[outs[k, j] for j in range(L)] for k in range(T)] if modes else [outs[k, 0] for k in range(T)]
     H, W, D = frames[0][2].shape
     stack = lambda k, d: np.ascontiguousarray(np.stack([np.asarray(f[k], np.float32).reshape(H, W, d) for f in frames]), np.float32)
     outs = np.zeros((T, H, W, 3), np.float32)

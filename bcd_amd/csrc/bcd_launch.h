@@ -42,6 +42,9 @@ hipError_t bcd_launch_valid_down(const uint8_t *valid, int W, int H, uint8_t *ou
 hipError_t bcd_launch_valid_patch(const uint8_t *valid, int W, int H, int w, uint8_t *pvalid, hipStream_t st);
 hipError_t bcd_launch_masks_gate_valid(uint32_t *mask, int32_t *count, const uint8_t *pvalid, int W, int H, int w, int b, hipStream_t st);
 
+// ---- k_motion_compose.hip (includes this header)
+hipError_t bcd_launch_motion_compose(const float *a, const float *b, int W, int H, float *out, hipStream_t st);
+
 // ---- k_bayes_temporal.hip, and the launcher of k_bayes27.hip that runs behind its prepare kernel
 hipError_t bcd_launch_prepare27t(const BcdFrameTable &t, const int32_t *list, int first_item, int nb_items, int *d_work, int num_cus, int W, int b, float *records,
                                  hipStream_t st);

@@ -11,6 +11,9 @@
 // transposition distributes over the AND of the gate, so the kept (gated) masks are transposed as they are and a transposed neighbour runs neither a cross pass
 // nor temporal_guide_gate.  There is one push, one pop and one construction: a sequence of bcd_hip_sequence_create is the mode of one layer, histograms and
 // no gate; L > 1 or moments take the layered estimate (bayes_temporal_layers), one layer of histograms, gated or not, bayes_temporal.
+// A frame may be pushed with its two step motion fields (bcd_hip_sequence_push_frame_motion; section 16, "Sequences with motion"): a pop then warps every
+// neighbour whose direction has a field from its slot, as the motion frame calls warp it (pop_motion, warp_slot), composing the field of a neighbour two frames
+// away from the steps (bcd_hip_compose_motion, k_motion_compose.hip); a pair is kept and transposed only when neither of its directions has a field.
 #include "bcd_ctx.h"
 
 #include <algorithm>
@@ -29,6 +32,14 @@ struct SeqSlot {
     DevBuf guide[MAX_SCALES][2]; // per level, with the feature gate: the features and their variances
     DevBuf pair[SEQ_MAX_RADIUS][MAX_SCALES]; // [d - 1]: the cross masks of (this frame -> this frame + d) at every level
     int64_t pair_frame[SEQ_MAX_RADIUS];      // ... valid for this frame index (-1: not kept)
+    DevBuf motion[2];                        // "Sequences with motion": the pushed step fields, [0] this frame -> the one before it, [1] -> the one after it
+    bool has_motion[2] = { false, false };   // ... of the slot's frame (false: NULL was pushed, zero motion); the buffers exist from the first field on
+};
+// a neighbour of the pop in progress that has a field: its warped levels (in the buffers of ctx->temporal that the motion calls use) and their validity bytes
+struct SeqWarped {
+    bool on = false;
+    TemporalFrame lv[MAX_SCALES];
+    const uint8_t *valid[MAX_SCALES];
 };
 #pragma GCC visibility pop
 
@@ -57,6 +68,10 @@ struct bcd_hip_sequence {
     // ---- the spike prefilter (bcd_hip_sequence_set_prefilter; DESIGN.md section 16, "Prefilter"): every frame is filtered once, in place in its slot, by its push
     float prefilter = 0.f;                   // the factor (0: off)
     int64_t filtered = 0, moved = 0;         // frames filtered, pixels they moved
+    // ---- motion (bcd_hip_sequence_push_frame_motion; DESIGN.md section 16, "Sequences with motion"): a neighbour whose direction has a field is warped per pop
+    DevBuf composed[2];                      // the fields frame t -> t - 2 and t -> t + 2 of the pop in progress, where both of their steps have a field
+    SeqWarped warped[BCD_HIP_MAX_NEIGHBOURS + 1]; // [1..]: the neighbours of the pop in progress
+    int64_t nb_warped = 0, nb_composed = 0;  // neighbours warped, fields composed by the pops
     bool plain() const { return L == 1 && !moments && F == 0; }   // what bcd_hip_sequence_create builds: its entry points, and it reports no layers
     bool layered() const { return moments || L > 1; }             // the estimate of bcd_temporal_layers.hip (one layer of histograms: that of bcd_temporal.hip)
 };
@@ -79,7 +94,7 @@ void forget(bcd_hip_sequence *q)
     q->pushed = q->popped = 0;
     q->ended = false;
     q->last_frame = -1; q->last_nb = 0;
-    q->uploaded = q->pyramids = q->computed = q->transposed = q->feature_passes = q->filtered = q->moved = 0;
+    q->uploaded = q->pyramids = q->computed = q->transposed = q->feature_passes = q->filtered = q->moved = q->nb_warped = q->nb_composed = 0;
     for (SeqSlot &s : q->slot) for (int64_t &f : s.pair_frame) f = -1;
 }
 
@@ -104,8 +119,9 @@ TemporalFrame slot_level(const bcd_hip_sequence *q, const SeqSlot &sl, int s)
 
 // a push, behind the refusals of its entry point: the frame's images into its slot (kind: device to device, or host to device), every pyramid level by the
 // reducers of the matching frame call (temporal_build_level, guide_build_level), the per-pixel covariances of all layers of a level in one launch;
-// synchronised, so the caller's buffers are free when it returns
-int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyKind kind)
+// synchronised, so the caller's buffers are free when it returns.  motion[0], motion[1]: null, or the step fields towards the frame before and after it, which
+// are copied as they are (the prefilter does not move them)
+int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, const float *const *motion, hipMemcpyKind kind)
 {
     bcd_hip_ctx *ctx = q->ctx;
     if (q->ended) return bad(ctx, "the sequence has ended: no further frame can be pushed (bcd_hip_sequence_reset starts another)");
@@ -160,6 +176,14 @@ int push_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyK
         }
     }
     for (int64_t &f : sl.pair_frame) f = -1; // (the slot's earlier frame: its pairs were consumed R pops ago)
+    for (int d = 0; d < 2; ++d) {
+        const size_t bytes = (size_t)q->W * q->H * 2 * f4;
+        sl.has_motion[d] = motion[d] != nullptr;
+        if (!motion[d]) continue;
+        RCCHK(seq_ensure(q, sl.motion[d], bytes));
+        HIPCHK(ctx, hipMemcpyAsync(sl.motion[d].p, motion[d], bytes, kind, st));
+        if (kind == hipMemcpyHostToDevice) q->uploaded += (int64_t)bytes;
+    }
     HIPCHK(ctx, hipStreamSynchronize(st));
     ++q->pushed;
     ++q->pyramids;
@@ -175,11 +199,12 @@ int push_images(bcd_hip_sequence *q, const float *col, const float *ns, const fl
     if (!col || !ns || !hist || !cov) return bad(ctx, "null image pointer");
     const bcd_hip_frame_layer layer = { col, cov };
     const bcd_hip_sequence_frame fm = { ns, hist, &layer, nullptr, nullptr, nullptr };
-    return push_frame(q, &fm, kind);
+    const float *const still[2] = { nullptr, nullptr };
+    return push_frame(q, &fm, still, kind);
 }
 
-// bcd_hip_sequence_push_frame[_host]: its refusals, then the push
-int push_mode_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMemcpyKind kind)
+// bcd_hip_sequence_push_frame[_motion][_host]: its refusals, then the push (a push without fields is one with both fields NULL)
+int push_mode_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, const float *motion_prev, const float *motion_next, hipMemcpyKind kind)
 {
     if (!q) return BCD_HIP_EINVAL;
     bcd_hip_ctx *ctx = q->ctx;
@@ -194,7 +219,8 @@ int push_mode_frame(bcd_hip_sequence *q, const bcd_hip_sequence_frame *fm, hipMe
     if (q->F == 0 && (fm->features || fm->variances)) return bad(ctx, "the sequence has no feature gate: the frame's features and variances must be NULL");
     if (q->F > 0 && !fm->features) return bad(ctx, "null feature image");
     if (q->F > 0 && (fm->variances != nullptr) != q->fvar) return bad(ctx, "feature variances must be given for every frame or for none, as the mode says");
-    return push_frame(q, fm, kind);
+    const float *const motion[2] = { motion_prev, motion_next };
+    return push_frame(q, fm, motion, kind);
 }
 
 // One scale of a pop, frame t with the neighbours nbs[0 .. nn) in ascending order: the table of temporal_scale on the slots.  The per-pixel covariances are
@@ -219,10 +245,26 @@ int pop_scale(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, int s,
         const int64_t f = nbs[i - 1];
         SeqSlot &nb = q->slot[f % q->N];
         sc.fr[i] = slot_level(q, nb, s);
+        const SeqWarped &wn = q->warped[i];
+        if (wn.on) { // ("Sequences with motion": the warped level, its per-pixel covariances as the frame call computes them, the validity bytes for the gate)
+            auto &tp = ctx->temporal;
+            sc.fr[i] = wn.lv[s];
+            DevBuf &pc = sc.layered ? tp.lay_pixcov[i] : tp.pixcov[i];
+            RCCHK(ensure(ctx, pc, (size_t)L * npix * 6 * sizeof(float)));
+            sc.fr[i].pixcov = (float *)pc.p;
+            sc.fr[i].sel.valid = wn.valid[s];
+            if (sc.layered) {
+                BcdLayerTable lt = {};
+                for (int k = 0; k < L; ++k) lt.a[k] = sc.fr[i].cov[k];
+                HIPCHK(ctx, bcd_launch_layers_pixel_cov(lt, L, sc.fr[i].sel.ns, (int64_t)npix, sc.fr[i].pixcov, ctx->main.stream));
+            } else {
+                HIPCHK(ctx, bcd_launch_pixel_cov(sc.fr[i].cov[0], sc.fr[i].sel.ns, (int64_t)npix, sc.fr[i].pixcov, ctx->main.stream));
+            }
+        }
         DevBuf &dst = f > t ? me.pair[f - t - 1][s] : q->low[below++][s];
         RCCHK(seq_ensure(q, dst, mb));
         sc.fr[i].sel.mask_dst = (uint32_t *)dst.p;
-        if (f < t && q->reuse && nb.pair_frame[t - f - 1] == f) sc.fr[i].sel.transpose_from = (const uint32_t *)nb.pair[t - f - 1][s].p;
+        if (!wn.on && f < t && q->reuse && nb.pair_frame[t - f - 1] == f) sc.fr[i].sel.transpose_from = (const uint32_t *)nb.pair[t - f - 1][s].p;
     }
     return temporal_scale(ctx, sc, W, H, q->D, &q->prm, s);
 }
@@ -294,6 +336,116 @@ int pop_scales(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn, float
     return BCD_HIP_OK;
 }
 
+// "Sequences with motion": the step fields whose composition is the field frame `from` -> frame `to` (1 or 2 frames apart, both in the ring): *a, then *b in the
+// pixel order of the frame between them (null: zero motion; one step: *b is null)
+void direction(const bcd_hip_sequence *q, int64_t from, int64_t to, const float **a, const float **b)
+{
+    const int d = to > from ? 1 : 0;
+    const int64_t mid = to > from ? from + 1 : from - 1;
+    auto step = [&](int64_t f) { const SeqSlot &s = q->slot[f % q->N]; return s.has_motion[d] ? (const float *)s.motion[d].p : nullptr; };
+    *a = step(from);
+    *b = mid == to ? nullptr : step(mid);
+}
+
+bool still(const bcd_hip_sequence *q, int64_t from, int64_t to)
+{
+    const float *a, *b;
+    direction(q, from, to, &a, &b);
+    return !a && !b;
+}
+
+// neighbour i (1..) of a pop with nf frames, in slot `nb`, reprojected by `field` as the matching frame call reprojects it: level 0 by temporal_warp_neighbour
+// (further layers by k_warp_layers), the slot's features by bcd_launch_warp_features, the levels 1.. by the reducers of the frame calls
+int warp_slot(bcd_hip_sequence *q, int i, int nf, const SeqSlot &nb, const float *field)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    auto &tp = ctx->temporal;
+    hipStream_t st = ctx->main.stream;
+    const int W = q->W, H = q->H, D = q->D, S = q->S, L = q->L, F = q->F;
+    const size_t npix = (size_t)W * H, f4 = sizeof(float);
+    const bool layered = q->layered();
+    SeqWarped &wn = q->warped[i];
+    const TemporalFrame src = slot_level(q, nb, 0);
+    BcdWarpLayerTable t = {};
+    if (L > 1) {
+        DevBuf(&lw)[2] = tp.lay_warp[i];
+        RCCHK(ensure(ctx, lw[0], (size_t)(L - 1) * npix * 3 * f4));
+        RCCHK(ensure(ctx, lw[1], (size_t)(L - 1) * npix * 6 * f4));
+        for (int k = 1; k < L; ++k) {
+            t.col[k - 1] = src.col[k]; t.cov[k - 1] = src.cov[k];
+            t.ocol[k - 1] = (float *)lw[0].p + (size_t)(k - 1) * npix * 3; t.ocov[k - 1] = (float *)lw[1].p + (size_t)(k - 1) * npix * 6;
+        }
+    }
+    TemporalFrame &l0 = wn.lv[0] = TemporalFrame();
+    if (F) { // (the validity bytes it writes are written again below)
+        DevBuf(&gw)[2] = tp.guide_warp[i];
+        RCCHK(ensure(ctx, gw[0], npix * F * f4));
+        if (q->fvar) RCCHK(ensure(ctx, gw[1], npix * F * f4));
+        RCCHK(ensure(ctx, tp.valid[i][0], npix));
+        HIPCHK(ctx, bcd_launch_warp_features(src.sel.feat, src.sel.var, F, field, W, H, (float *)gw[0].p, q->fvar ? (float *)gw[1].p : nullptr, (uint8_t *)tp.valid[i][0].p, st));
+        l0.sel.feat = (const float *)gw[0].p;
+        l0.sel.var = q->fvar ? (const float *)gw[1].p : nullptr;
+    }
+    const uint8_t *valid[MAX_SCALES * (BCD_HIP_MAX_NEIGHBOURS + 1)] = {};
+    const float *wp[4];
+    RCCHK(temporal_warp_neighbour(ctx, i, nf, src.col[0], src.sel.ns, src.sel.hist, src.cov[0], field, W, H, D, S, L > 1 ? &t : nullptr, L - 1, valid, wp));
+    l0.col[0] = wp[0]; l0.sel.ns = wp[1]; l0.sel.hist = q->moments ? nullptr : wp[2]; l0.cov[0] = wp[3];
+    for (int k = 1; k < L; ++k) { l0.col[k] = t.ocol[k - 1]; l0.cov[k] = t.ocov[k - 1]; }
+    for (int s = 0; s < S; ++s) wn.valid[s] = valid[(size_t)s * nf + i];
+    for (int s = 1; s < S; ++s) {
+        const size_t np = (size_t)q->ws[s] * q->hs[s];
+        DevBuf(&l)[4] = tp.pyr[i][s];
+        TemporalFrame &coarse = wn.lv[s] = TemporalFrame();
+        RCCHK(ensure(ctx, l[1], np * f4));
+        if (!q->moments) RCCHK(ensure(ctx, l[2], np * D * f4));
+        coarse.sel.ns = (const float *)l[1].p; coarse.sel.hist = q->moments ? nullptr : (const float *)l[2].p;
+        if (layered) {
+            DevBuf(&ll)[2] = tp.lay_pyr[i][s];
+            RCCHK(ensure(ctx, ll[0], (size_t)L * np * 3 * f4));
+            RCCHK(ensure(ctx, ll[1], (size_t)L * np * 6 * f4));
+            for (int k = 0; k < L; ++k) { coarse.col[k] = (const float *)ll[0].p + (size_t)k * np * 3; coarse.cov[k] = (const float *)ll[1].p + (size_t)k * np * 6; }
+        } else {
+            RCCHK(ensure(ctx, l[0], np * 3 * f4));
+            RCCHK(ensure(ctx, l[3], np * 6 * f4));
+            coarse.col[0] = (const float *)l[0].p; coarse.cov[0] = (const float *)l[3].p;
+        }
+        RCCHK(temporal_build_level(ctx, wn.lv[s - 1], coarse, L, layered, q->ws[s - 1], q->hs[s - 1], D, st));
+        if (F) {
+            DevBuf(&g)[2] = tp.guide_pyr[i][s];
+            RCCHK(ensure(ctx, g[0], np * F * f4));
+            if (q->fvar) RCCHK(ensure(ctx, g[1], np * F * f4));
+            RCCHK(guide_build_level(ctx, wn.lv[s - 1].sel.feat, wn.lv[s - 1].sel.var, q->ws[s - 1], q->hs[s - 1], F, (float *)g[0].p, (float *)g[1].p, st));
+            coarse.sel.feat = (const float *)g[0].p;
+            coarse.sel.var = q->fvar ? (const float *)g[1].p : nullptr;
+        }
+    }
+    wn.on = true;
+    ++q->nb_warped;
+    return BCD_HIP_OK;
+}
+
+// the motion set-up of a pop: per neighbour the field of its direction -- a step field, or two of them composed -- and, where there is one, the warped neighbour
+int pop_motion(bcd_hip_sequence *q, int64_t t, const int64_t *nbs, int nn)
+{
+    bcd_hip_ctx *ctx = q->ctx;
+    for (SeqWarped &w : q->warped) w.on = false;
+    for (int i = 1; i <= nn; ++i) {
+        const int64_t f = nbs[i - 1];
+        const float *a, *b;
+        direction(q, t, f, &a, &b);
+        const float *field = a ? a : b;
+        if (a && b) {
+            DevBuf &dst = q->composed[f > t ? 1 : 0];
+            RCCHK(seq_ensure(q, dst, (size_t)q->W * q->H * 2 * sizeof(float)));
+            HIPCHK(ctx, bcd_launch_motion_compose(a, b, q->W, q->H, (float *)dst.p, ctx->main.stream));
+            ++q->nb_composed;
+            field = (const float *)dst.p;
+        }
+        if (field) RCCHK(warp_slot(q, i, nn + 1, q->slot[f % q->N], field));
+    }
+    return BCD_HIP_OK;
+}
+
 // the next frame into d_out[0 .. L) (device memory)
 int pop(bcd_hip_sequence *q, float *const *d_out, int64_t *frame_index)
 {
@@ -307,10 +459,12 @@ int pop(bcd_hip_sequence *q, float *const *d_out, int64_t *frame_index)
         RCCHK(pop_single(q, me, d_out));
     } else {
         DEVICE_GUARD(ctx);
+        RCCHK(pop_motion(q, t, nbs, nn));
         RCCHK(pop_scales(q, t, nbs, nn, d_out));
         for (int i = 0; i < nn; ++i) {
             const int64_t f = nbs[i];
-            if (f > t) { me.pair_frame[f - t - 1] = t; ++q->computed; continue; }
+            // (a pair is kept for the transposition exactly when neither of its directions has a field: frame f is in the ring, so both are known)
+            if (f > t) { if (still(q, t, f) && still(q, f, t)) me.pair_frame[f - t - 1] = t; ++q->computed; continue; }
             int64_t &kept = q->slot[f % q->N].pair_frame[t - f - 1];
             if (q->reuse && kept == f) ++q->transposed; else ++q->computed;
             kept = -1; // (no later frame needs the pair)
@@ -471,9 +625,9 @@ int bcd_hip_sequence_create_mode(bcd_hip_ctx *ctx, int W, int H, int D, int nb_s
     return create(ctx, W, H, D, nb_scales, radius, prm, *mode, true, out);
 }
 
-int bcd_hip_sequence_push_frame(void *seq, const bcd_hip_sequence_frame *frame) { return push_mode_frame((bcd_hip_sequence *)seq, frame, hipMemcpyDeviceToDevice); }
+int bcd_hip_sequence_push_frame(void *seq, const bcd_hip_sequence_frame *frame) { return push_mode_frame((bcd_hip_sequence *)seq, frame, nullptr, nullptr, hipMemcpyDeviceToDevice); }
 
-int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *frame) { return push_mode_frame((bcd_hip_sequence *)seq, frame, hipMemcpyHostToDevice); }
+int bcd_hip_sequence_push_frame_host(void *seq, const bcd_hip_sequence_frame *frame) { return push_mode_frame((bcd_hip_sequence *)seq, frame, nullptr, nullptr, hipMemcpyHostToDevice); }
 
 static int check_pop_layers(bcd_hip_sequence *q, float *const *outs, int nb_layers)
 {
@@ -546,6 +700,41 @@ int bcd_hip_sequence_prefilter_info(void *seq, int64_t *frames_filtered, int64_t
     return BCD_HIP_OK;
 }
 
+// ---- "Sequences with motion"  --------------------------------------------------------------------------------------------------
+int bcd_hip_compose_motion(bcd_hip_ctx *ctx, const float *d_a, const float *d_b, int W, int H, float *d_out)
+{
+    if (!ctx) return BCD_HIP_EINVAL;
+    if (!d_a || !d_b || !d_out) return bad(ctx, "null motion field pointer");
+    if (W <= 0 || H <= 0) return bad(ctx, "empty image");
+    if ((int64_t)W * H >= (1ll << 30)) return bad(ctx, "image too large for 32-bit DeepImage indices");
+    const size_t bytes = (size_t)W * H * 2 * sizeof(float);
+    if (bytes_overlap(d_out, bytes, d_a, bytes) || bytes_overlap(d_out, bytes, d_b, bytes)) return bad(ctx, "the composed field overlaps an input field (the composition is not done in place)");
+    DEVICE_GUARD(ctx);
+    HIPCHK(ctx, bcd_launch_motion_compose(d_a, d_b, W, H, d_out, ctx->main.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->main.stream));
+    return BCD_HIP_OK;
+}
+
+int bcd_hip_sequence_push_frame_motion(void *seq, const bcd_hip_sequence_frame *frame, const float *d_motion_prev, const float *d_motion_next)
+{
+    return push_mode_frame((bcd_hip_sequence *)seq, frame, d_motion_prev, d_motion_next, hipMemcpyDeviceToDevice);
+}
+
+int bcd_hip_sequence_push_frame_motion_host(void *seq, const bcd_hip_sequence_frame *frame, const float *h_motion_prev, const float *h_motion_next)
+{
+    return push_mode_frame((bcd_hip_sequence *)seq, frame, h_motion_prev, h_motion_next, hipMemcpyHostToDevice);
+}
+
+int bcd_hip_sequence_motion_info(void *seq, int64_t *neighbours_warped, int64_t *fields_composed)
+{
+    const bcd_hip_sequence *q = (const bcd_hip_sequence *)seq;
+    if (!q) return BCD_HIP_EINVAL;
+    if (!neighbours_warped || !fields_composed) return bad(q->ctx, "null info pointer");
+    *neighbours_warped = q->nb_warped;
+    *fields_composed = q->nb_composed;
+    return BCD_HIP_OK;
+}
+
 int bcd_hip_sequence_last_masks(void *seq, int neighbour, int scale, uint32_t *d_mask, int32_t *d_count)
 {
     bcd_hip_sequence *q = (bcd_hip_sequence *)seq;
@@ -607,10 +796,12 @@ void bcd_hip_sequence_destroy(void *seq)
             free_bufs(s.pixcov, sizeof s.pixcov);
             free_bufs(s.guide, sizeof s.guide);
             free_bufs(s.pair, sizeof s.pair);
+            free_bufs(s.motion, sizeof s.motion);
         }
         free_bufs(q->out, sizeof q->out);
         free_bufs(q->self, sizeof q->self);
         free_bufs(q->low, sizeof q->low);
+        free_bufs(q->composed, sizeof q->composed);
         free_bufs(&q->host_out, sizeof q->host_out);
     }
     delete q;

@@ -527,6 +527,21 @@ class Context:
         self._chk(lib().bcd_hip_transpose_masks_cross(self.h, _dp(mask), W, H, b, _dp(omask), _dp(cnt) if cnt is not None else None))
         return omask, cnt
 
+    def compose_motion(self, a, b, out=None):
+        """bcd_hip_compose_motion: the motion field frame t -> v from a (t -> u) and b (u -> v, in frame-u pixel order), (H, W, 2) float32 device tensors ->
+        the composed field, integer-valued, (NaN, NaN) where a step is broken ("Sequences with motion").  out: the tensor to fill"""
+        torch = self.torch
+        if a.dim() != 3 or a.shape[2] != 2 or tuple(b.shape) != tuple(a.shape) or a.dtype != torch.float32 or b.dtype != torch.float32:
+            raise ValueError("the motion fields must be (H, W, 2) float32 tensors of one size")
+        H, W, _ = a.shape
+        if out is None:
+            out = torch.empty((H, W, 2), dtype=torch.float32, device=a.device)
+        if out.numel() != H * W * 2 or out.dtype != torch.float32:
+            raise ValueError("out must hold (H, W, 2) floats")
+        torch.cuda.synchronize(self.device)                          # (the fills ran on torch's stream)
+        self._chk(lib().bcd_hip_compose_motion(self.h, _dp(a), _dp(b), W, H, _dp(out)))
+        return out
+
     def sequence(self, W, H, D, nscales, radius, prm, layers=None, moments=False, var_floor=1e-8, features=0, feature_variances=False, feature_floors=(),
                  feature_threshold=1.0):
         """a Sequence of this context: frames of W x H with D bins, denoised with their neighbours within `radius` frames through a sliding window.
@@ -1970,29 +1985,54 @@ class Sequence:
         rest = list(frame[3:]) + [None, None]
         return frame[0], frame[1], frame[2], rest[0] if features is None else features, rest[1] if variances is None else variances
 
-    def push(self, *frame, features=None, variances=None):
+    def _fields(self, motion, numel, conv=lambda a: a):
+        """the step fields of a push from its keywords motion_prev / motion_next: None (zero motion) or (H, W, 2) floats each; only a sequence in a mode
+        takes them.  -> None when neither keyword was given (a push without fields), else (prev, next)"""
+        if set(motion) - {"motion_prev", "motion_next"}:
+            raise TypeError("unexpected keyword %r" % sorted(set(motion) - {"motion_prev", "motion_next"})[0])
+        if not motion:
+            return None
+        if self.mode is None:
+            raise ValueError("motion fields are pushed to a sequence in a mode (Context.sequence(..., layers=1) is the plain sequence as one)")
+        fields = tuple(None if motion.get(k) is None else conv(motion[k]) for k in ("motion_prev", "motion_next"))
+        for m in fields:
+            if m is not None and numel(m) != self.H * self.W * 2:
+                raise ValueError("a motion field of this sequence holds (%d, %d, 2) floats" % (self.H, self.W))
+        return fields
+
+    def push(self, *frame, features=None, variances=None, **motion):
         """bcd_hip_sequence_push: the next frame, device tensors (copied: they are free again on return) -- (col, ns, hist, cov).
-        In a mode (bcd_hip_sequence_push_frame): (ns, hist or None, [(colours, covariances), ...], features=None, variances=None)"""
+        In a mode (bcd_hip_sequence_push_frame): (ns, hist or None, [(colours, covariances), ...], features=None, variances=None); motion_prev / motion_next
+        (bcd_hip_sequence_push_frame_motion, when either keyword is given): the (H, W, 2) fields of this frame towards the frame before and after it,
+        None: zero motion"""
         h = self._handle()
+        fields = self._fields(motion, lambda m: m.numel())
         if self.mode is not None:
             f, keep = self._frame(*self._mode_args(frame, features, variances), ptr=_dptr)
             self.ctx.torch.cuda.synchronize(self.ctx.device)
-            self.ctx._chk(lib().bcd_hip_sequence_push_frame(h, C.byref(f)))
+            if fields is None:
+                self.ctx._chk(lib().bcd_hip_sequence_push_frame(h, C.byref(f)))
+            else:
+                self.ctx._chk(lib().bcd_hip_sequence_push_frame_motion(h, C.byref(f), *(None if m is None else _dp(m) for m in fields)))
             return
         col, ns, hist, cov = frame
         self._check(col, ns, hist, cov)
         self.ctx.torch.cuda.synchronize(self.ctx.device)
         self.ctx._chk(lib().bcd_hip_sequence_push(h, _dp(col), _dp(ns), _dp(hist), _dp(cov)))
 
-    def push_host(self, *frame, features=None, variances=None):
+    def push_host(self, *frame, features=None, variances=None, **motion):
         """bcd_hip_sequence_push_host: the next frame, NumPy arrays (uploaded once); the arguments of push"""
         import numpy as np
         h = self._handle()
+        as32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        fields = self._fields(motion, np.size, as32)
         if self.mode is not None:
-            as32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
             ns, hist, layers, features, variances = self._mode_args(frame, features, variances)
             f, keep = self._frame(as32(ns), as32(hist), [(as32(c), as32(v)) for c, v in layers], as32(features), as32(variances), ptr=_hptr)
-            self.ctx._chk(lib().bcd_hip_sequence_push_frame_host(h, C.byref(f)))
+            if fields is None:
+                self.ctx._chk(lib().bcd_hip_sequence_push_frame_host(h, C.byref(f)))
+            else:
+                self.ctx._chk(lib().bcd_hip_sequence_push_frame_motion_host(h, C.byref(f), *(None if m is None else C.c_void_p(_hptr(m)) for m in fields)))
             return
         col, ns, hist, cov = frame
         col, ns, hist, cov = (np.ascontiguousarray(a, np.float32) for a in (col, ns, hist, cov))
@@ -2053,6 +2093,12 @@ class Sequence:
         """bcd_hip_sequence_prefilter_info -> (frames filtered, pixels moved) since the creation or the last reset"""
         n, m = C.c_int64(0), C.c_int64(0)
         self.ctx._chk(lib().bcd_hip_sequence_prefilter_info(self._handle(), C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    def motion_info(self):
+        """bcd_hip_sequence_motion_info -> (neighbours warped, fields composed) by the pops since the creation or the last reset"""
+        n, m = C.c_int64(0), C.c_int64(0)
+        self.ctx._chk(lib().bcd_hip_sequence_motion_info(self._handle(), C.byref(n), C.byref(m)))
         return n.value, m.value
 
     def last_masks(self, neighbour, scale=0):

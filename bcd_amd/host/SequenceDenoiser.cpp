@@ -19,7 +19,8 @@ namespace bcd
 
 	SequenceDenoiser::SequenceDenoiser(int i_nbOfScales, int i_temporalRadius) :
 			m_nbOfScales(i_nbOfScales), m_temporalRadius(i_temporalRadius), m_pCtx(nullptr), m_pSequence(nullptr), m_width(0), m_height(0), m_depth(0),
-			m_lastFrameIndex(-1), m_frameSettings(false), m_plain(true), m_nbOfLayers(1), m_moments(false), m_nbOfFeatures(0), m_featureVariances(false)
+			m_lastFrameIndex(-1), m_frameSettings(false), m_plain(true), m_nbOfLayers(1), m_moments(false), m_nbOfFeatures(0), m_featureVariances(false),
+			m_pMotionPrev(nullptr), m_pMotionNext(nullptr)
 	{
 	}
 
@@ -186,8 +187,18 @@ namespace bcd
 
 	bool SequenceDenoiser::pushFrame(const DenoiserInputs& i_rFrame)
 	{
+		const Deepimf* motion[2] = { m_pMotionPrev, m_pMotionNext }; // (setFrameMotion serves this push only)
+		m_pMotionPrev = m_pMotionNext = nullptr;
 		if(!settingsAreOk() || !frameIsOk(i_rFrame))
 			return false;
+		for(int d = 0; d < 2; ++d)
+			if(motion[d] && (motion[d]->getDepth() != 2 || motion[d]->getWidth() != i_rFrame.m_pColors->getWidth() || motion[d]->getHeight() != i_rFrame.m_pColors->getHeight()))
+			{
+				cerr << "Aborting denoising: the motion field of a frame towards the " << (d ? "next" : "previous") << " frame needs 2 channels and the frame's size ("
+						<< i_rFrame.m_pColors->getWidth() << "x" << i_rFrame.m_pColors->getHeight() << "), not " << motion[d]->getWidth() << "x" << motion[d]->getHeight() << "x"
+						<< motion[d]->getDepth() << endl;
+				return false;
+			}
 		if(!m_pSequence)
 		{
 			const int w = i_rFrame.m_pColors->getWidth(), h = i_rFrame.m_pColors->getHeight(), depth = m_momentSelection ? 0 : i_rFrame.m_pHistograms->getDepth();
@@ -233,9 +244,10 @@ namespace bcd
 			mode.feature_variances = m_pGuideVariances ? 1 : 0;
 			mode.feature_floors = m_pGuideFeatures ? m_guideFloors.data() : nullptr;
 			mode.feature_threshold = m_guideThreshold;
-			m_plain = mode.nb_layers == 1 && !mode.moments && mode.nb_features == 0; // (today's sequence: bcd_hip_sequence_create and its push and pop)
-			const int rc = m_plain ? bcd_hip_sequence_create(pCtx, w, h, depth, m_nbOfScales, m_temporalRadius, &prm, &m_pSequence)
-					: bcd_hip_sequence_create_mode(pCtx, w, h, depth, m_nbOfScales, m_temporalRadius, &prm, &mode, &m_pSequence);
+			// (one layer, histograms, no gate: the sequence of bcd_hip_sequence_create with its push and pop -- made by bcd_hip_sequence_create_mode, which builds the
+			// same object and also takes a later frame that brings motion fields)
+			m_plain = mode.nb_layers == 1 && !mode.moments && mode.nb_features == 0;
+			const int rc = bcd_hip_sequence_create_mode(pCtx, w, h, depth, m_nbOfScales, m_temporalRadius, &prm, &mode, &m_pSequence);
 			if(rc != BCD_HIP_OK)
 			{
 				cerr << "Aborting denoising: " << bcd_hip_last_error(pCtx) << endl;
@@ -254,7 +266,7 @@ namespace bcd
 			m_lastFrameIndex = -1;
 		}
 		int rc;
-		if(m_plain)
+		if(m_plain && !motion[0] && !motion[1])
 			rc = bcd_hip_sequence_push_host(m_pSequence, i_rFrame.m_pColors->getDataPtr(), i_rFrame.m_pNbOfSamples->getDataPtr(), i_rFrame.m_pHistograms->getDataPtr(),
 					i_rFrame.m_pSampleCovariances->getDataPtr());
 		else
@@ -269,7 +281,9 @@ namespace bcd
 			frame.layers = layers.data();
 			frame.features = m_pGuideFeatures ? m_pGuideFeatures->getDataPtr() : nullptr;
 			frame.variances = m_pGuideVariances ? m_pGuideVariances->getDataPtr() : nullptr;
-			rc = bcd_hip_sequence_push_frame_host(m_pSequence, &frame);
+			rc = motion[0] || motion[1] ? bcd_hip_sequence_push_frame_motion_host(m_pSequence, &frame, motion[0] ? motion[0]->getDataPtr() : nullptr,
+							motion[1] ? motion[1]->getDataPtr() : nullptr)
+					: bcd_hip_sequence_push_frame_host(m_pSequence, &frame);
 		}
 		if(rc != BCD_HIP_OK)
 		{

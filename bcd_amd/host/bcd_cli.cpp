@@ -15,6 +15,8 @@
 // its neighbours within R frames, through bcd::SequenceDenoiser (every frame uploaded once, every pair of frames searched once); it replaces -i / -o.
 // Beside it --sequence-layer <colours> <covariances> <output> (patterns), --sequence-moments <floor> --sequence-nsamples <pattern> and --sequence-features
 // <pattern> with --sequence-feature-variances / -floors / -threshold give every frame its colour layers, the moment selection and the feature gate.
+// --sequence-motion-prev <pattern> and --sequence-motion-next <pattern> give every frame its motion field towards the frame before and after it
+// (SequenceDenoiser::setFrameMotion); the file of the first frame (prev) and of the last frame (next) may be missing.
 #include "Chronometer.h"
 #include "DeepImage.h"
 #include "Denoiser.h"
@@ -28,6 +30,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <vector>
 #include <memory>
@@ -108,6 +111,10 @@ namespace
 		cout << "                         device; not with -i, -o, -h, -c, --neighbour, --layer, --features or --moment-selection" << endl;
 		cout << "    --sequence-layer <colours pattern> <covariances pattern> <output pattern>" << endl;
 		cout << "                         beside --sequence-in: a further colour layer of every frame (repeatable, at most 15), denoised with the frame's selection" << endl;
+		cout << "    --sequence-motion-prev <pattern> --sequence-motion-next <pattern>" << endl;
+		cout << "                         beside --sequence-in: the motion field of every frame towards the frame before it / after it ((dx, dy) in the first two" << endl;
+		cout << "                         channels, as --neighbour-motion); a neighbour frame is warped by the field, fields two frames away are composed from" << endl;
+		cout << "                         the steps.  The file of frame --first (prev) and of frame --last (next) may be missing: zero motion" << endl;
 		cout << "    --sequence-moments <var floor> --sequence-nsamples <pattern>" << endl;
 		cout << "                         beside --sequence-in: every selection from means and covariances; no <frame>_hist.exr is read, the sample counts of" << endl;
 		cout << "                         every frame come from a one-channel EXR image" << endl;
@@ -646,6 +653,7 @@ namespace
 		bool moments = false;
 		float momentFloor = 1e-8f, featureThreshold = 1.f;
 		string nbOfSamplesPattern, featurePattern, featureVariancePattern;
+		string motionPattern[2]; // --sequence-motion-prev, --sequence-motion-next
 		std::vector<float> featureFloors;
 		auto argumentError = [](const string& i_rMessage) { cout << "ERROR in program arguments: " << i_rMessage << endl; return 1; };
 		for(int i = 1; i < argc; ++i)
@@ -706,6 +714,8 @@ namespace
 				featureThreshold = strtof(value, &pEnd);
 				if(pEnd == value || *pEnd || !(featureThreshold >= 0.f) || std::isinf(featureThreshold)) return argumentError("expecting a finite non-negative number after --sequence-feature-threshold");
 			}
+			else if(flag == "--sequence-motion-prev") motionPattern[0] = value;
+			else if(flag == "--sequence-motion-next") motionPattern[1] = value;
 			else if(flag == "--sequence-in") inPattern = value;
 			else if(flag == "--sequence-out") outPattern = value;
 			else if(flag == "--first") { first = atoi(value); hasFirst = true; }
@@ -749,6 +759,9 @@ namespace
 			for(float floor : featureFloors) counts = counts || floor > 0.f;
 			if(!counts) return argumentError("every --sequence-feature-floors value is 0 and there are no --sequence-feature-variances: no feature channel can count");
 		}
+		for(const string& rPattern : motionPattern)
+			if(!rPattern.empty() && !isFramePattern(rPattern))
+				return argumentError("--sequence-motion-prev and --sequence-motion-next need a file pattern with one %d for the frame number");
 		const bool frameSettings = !layers.empty() || moments || !featurePattern.empty();
 
 		DenoiserParameters parameters;
@@ -848,6 +861,25 @@ namespace
 					rgb.get(3 * i) = rgb.get(3 * i + 1) = rgb.get(3 * i + 2) = color.get(i);
 				color = std::move(rgb);
 			}
+			// the frame's motion fields, (dx, dy) in the first two channels; the first frame has no frame before it and the last none after it: their files may be missing
+			Deepimf motion[2];
+			for(int d = 0; d < 2; ++d)
+			{
+				if(motionPattern[d].empty()) continue;
+				const string motionPath = frameName(motionPattern[d], frame);
+				if(frame == (d ? last : first) && !std::ifstream(motionPath.c_str()).good()) continue;
+				Deepimf loaded;
+				if(!ImageIO::loadMultiChannelsEXR(loaded, motionPath.c_str())) return argumentError("couldn't load motion image file '" + motionPath + "'");
+				if(loaded.getDepth() < 2) return argumentError("motion image '" + motionPath + "' needs two channels (dx, dy)");
+				motion[d].resize(loaded.getWidth(), loaded.getHeight(), 2);
+				const int depth = loaded.getDepth();
+				for(size_t px = 0, n = size_t(loaded.getWidth()) * loaded.getHeight(); px < n; ++px)
+				{
+					motion[d].get(int(2 * px)) = loaded.get(int(depth * px));
+					motion[d].get(int(2 * px + 1)) = loaded.get(int(depth * px + 1));
+				}
+			}
+			sequence.setFrameMotion(motion[0].isEmpty() ? nullptr : &motion[0], motion[1].isEmpty() ? nullptr : &motion[1]);
 			DenoiserInputs inputs;
 			inputs.m_pColors = &color; inputs.m_pNbOfSamples = &nbOfSamples; inputs.m_pHistograms = moments ? nullptr : &hist; inputs.m_pSampleCovariances = &cov;
 			if(!sequence.pushFrame(inputs))
@@ -877,9 +909,20 @@ namespace
 					return 2;
 				}
 		}
+		bool sequenceIn = false, sequenceOut = false, sequenceMotion = false;
 		for(int i = 1; i < argc; ++i)
-			if(string(argv[i]) == "--sequence-in" || string(argv[i]) == "--sequence-out")
-				return launchSequenceDenoising(argc, argv);
+		{
+			sequenceIn = sequenceIn || string(argv[i]) == "--sequence-in";
+			sequenceOut = sequenceOut || string(argv[i]) == "--sequence-out";
+			sequenceMotion = sequenceMotion || string(argv[i]) == "--sequence-motion-prev" || string(argv[i]) == "--sequence-motion-next";
+		}
+		if(sequenceMotion && !sequenceIn)
+		{
+			cout << "ERROR in program arguments: --sequence-motion-prev and --sequence-motion-next go with --sequence-in (beside -i a neighbour's field is --neighbour-motion)" << endl;
+			return 1;
+		}
+		if(sequenceIn || sequenceOut)
+			return launchSequenceDenoising(argc, argv);
 		ProgramArguments args;
 		if(!parseProgramArguments(argc, argv, args))
 			return 1;

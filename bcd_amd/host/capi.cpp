@@ -813,9 +813,13 @@ int bcdcore_denoise_sequence(const float* cols, const float* nss, const float* h
 /// null: none) with nbOfFloors floors and the threshold.  break_: settings the class must refuse before a device is asked for -- bit 0 addNeighbourFrame, bit 1
 /// the spike prefilter, bit 2 two devices, bit 3 the second frame with one layer fewer, bit 4 the second frame without its variances (or, without variances,
 /// without its features), bit 5 no layer registered when the first frame is popped.  Returns 1 when every push and pop succeeded in order, else 0.
-int bcdcore_denoise_sequence_modes(const float* cols, const float* nss, const float* hists, const float* covs, const float* features, const float* variances, int nbOfFrames,
+/// motions (bcdcore_denoise_sequence_motion; null: no frame brings a field): per frame two W x H x 2 fields one behind the other, towards the frame before and
+/// after it, hasMotion 2 flags per frame (0: nullptr for that field) -> setFrameMotion ahead of every push.  breakMotion: what pushFrame must refuse before a
+/// device is asked for -- bit 0 the first field given has 3 channels, bit 1 it is one pixel narrower than the frame.
+static int denoiseSequenceModes(const float* cols, const float* nss, const float* hists, const float* covs, const float* features, const float* variances, int nbOfFrames,
 		int nbOfLayers, int nbOfChannels, const float* floors, int nbOfFloors, float threshold, float varFloor, int W, int H, int D, int nscales, int radius, float tau,
-		int w, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int break_, float* outs)
+		int w, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int break_, float* outs, const float* motions, const int* hasMotion,
+		int breakMotion)
 {
 	const size_t npix = size_t(W) * H;
 	SequenceDenoiser sequence(nscales, radius);
@@ -883,6 +887,20 @@ int bcdcore_denoise_sequence_modes(const float* cols, const float* nss, const fl
 		}
 		DenoiserInputs in;
 		in.m_pColors = &c; in.m_pNbOfSamples = &n; in.m_pHistograms = hists ? &h : nullptr; in.m_pSampleCovariances = &v;
+		Deepimf field[2];
+		for(int d = 0; motions && d < 2; ++d)
+		{
+			if(!hasMotion[2 * f + d]) continue;
+			if(breakMotion)
+			{
+				field[d] = Deepimf((breakMotion & 2) ? W - 1 : W, H, (breakMotion & 1) ? 3 : 2);
+				breakMotion = 0;
+				continue;
+			}
+			field[d] = Deepimf(W, H, 2);
+			field[d].copyDataFrom(motions + (size_t(f) * 2 + d) * npix * 2);
+		}
+		if(motions) sequence.setFrameMotion(field[0].isEmpty() ? nullptr : &field[0], field[1].isEmpty() ? nullptr : &field[1]);
 		if(!sequence.pushFrame(in))
 			return 0;
 		if(f == nbOfFrames - 1 && !sequence.end())
@@ -892,6 +910,24 @@ int bcdcore_denoise_sequence_modes(const float* cols, const float* nss, const fl
 			return 0;
 	}
 	return popped == nbOfFrames ? 1 : 0;
+}
+
+int bcdcore_denoise_sequence_modes(const float* cols, const float* nss, const float* hists, const float* covs, const float* features, const float* variances, int nbOfFrames,
+		int nbOfLayers, int nbOfChannels, const float* floors, int nbOfFloors, float threshold, float varFloor, int W, int H, int D, int nscales, int radius, float tau,
+		int w, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int break_, float* outs)
+{
+	return denoiseSequenceModes(cols, nss, hists, covs, features, variances, nbOfFrames, nbOfLayers, nbOfChannels, floors, nbOfFloors, threshold, varFloor, W, H, D, nscales,
+			radius, tau, w, b, minEig, randomOrder, skipProbability, seed, break_, outs, nullptr, nullptr, 0);
+}
+
+/// bcdcore_denoise_sequence_modes with per-step motion fields (SequenceDenoiser::setFrameMotion), see denoiseSequenceModes
+int bcdcore_denoise_sequence_motion(const float* cols, const float* nss, const float* hists, const float* covs, const float* features, const float* variances, int nbOfFrames,
+		int nbOfLayers, int nbOfChannels, const float* floors, int nbOfFloors, float threshold, float varFloor, int W, int H, int D, int nscales, int radius, float tau,
+		int w, int b, float minEig, int randomOrder, float skipProbability, unsigned seed, int break_, float* outs, const float* motions, const int* hasMotion,
+		int breakMotion)
+{
+	return denoiseSequenceModes(cols, nss, hists, covs, features, variances, nbOfFrames, nbOfLayers, nbOfChannels, floors, nbOfFloors, threshold, varFloor, W, H, D, nscales,
+			radius, tau, w, b, minEig, randomOrder, skipProbability, seed, break_, outs, motions, hasMotion, breakMotion);
 }
 
 /// bcd::Denoiser / bcd::MultiscaleDenoiser with neighbouring frames AND colour layers (addLayer, addNeighbourFrame, addNeighbourFrameLayer).  cols / covs hold

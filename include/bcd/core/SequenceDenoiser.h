@@ -23,7 +23,9 @@ namespace bcd
 	///  - setMomentSelection(true, floor): every selection from means and covariances; DenoiserInputs::m_pHistograms may stay null and is not looked at;
 	///  - setGuideFeatures: the features (and variances) set when pushFrame() is called are that frame's; floors and threshold are those of the first frame.
 	/// The first frame fixes the mode: the number of layers, the selection, the feature channels and whether there are variances; reset() frees it.
-	/// The settings a sequence does not serve -- neighbour frames of its own, motion fields, the spike prefilter without setSpikePrefilterFrames(true) (with it every
+	/// setFrameMotion(prev, next) gives the next pushed frame its motion fields towards the frame before and after it (bcd_hip_sequence_push_frame_motion): a
+	/// neighbour whose direction has a field is warped into the frame's pixel grid, fields two frames away are composed from the steps.
+	/// The settings a sequence does not serve -- neighbour frames of its own, setNeighbourMotion, the spike prefilter without setSpikePrefilterFrames(true) (with it every
 	/// pushed frame is prefiltered once, on its own: bcd_hip_sequence_set_prefilter), several devices -- make pushFrame() return
 	/// false, like a patch radius other than 1, a search radius other than 6, a temporal radius outside 1 .. 2, more than 15 added layers, a feature image
 	/// outside 1 .. 8 channels, floors that are negative, not finite, of another count or unable to count, a frame that differs from the first frame's
@@ -46,6 +48,10 @@ namespace bcd
 		void setFrameSettings(bool i_enabled) { m_frameSettings = i_enabled; }
 		bool getFrameSettings() const { return m_frameSettings; }
 
+		/// the motion fields of the NEXT pushFrame(), which clears them: i_pPrev the field of that frame towards the frame before it, i_pNext towards the frame
+		/// after it, (dx, dy) per pixel as in HipEngineSettings::setNeighbourMotion; nullptr: zero motion.  A field needs 2 channels and the frame's size:
+		/// anything else makes pushFrame() return false with a message, before a device is asked for.  The images are read by pushFrame()
+		void setFrameMotion(const Deepimf* i_pPrev, const Deepimf* i_pNext) { m_pMotionPrev = i_pPrev; m_pMotionNext = i_pNext; }
 		/// the next frame: the four images are uploaded before the call returns.  The first frame fixes width, height and histogram depth
 		bool pushFrame(const DenoiserInputs& i_rFrame);
 		/// no further frame follows: the frames still held become ready
@@ -80,6 +86,8 @@ namespace bcd
 		bool m_moments;
 		int m_nbOfFeatures;
 		bool m_featureVariances;
+		const Deepimf* m_pMotionPrev; // setFrameMotion: of the next push
+		const Deepimf* m_pMotionNext;
 	};
 
 } // namespace bcd

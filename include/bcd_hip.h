@@ -367,7 +367,8 @@ int bcd_hip_window_distances_cross(bcd_hip_ctx *ctx, const float *d_histograms, 
  *   counter and keeps the buffers.  _destroy frees them; a sequence must be destroyed before its context.
  *   Scope: histogram selection, one colour layer, patch radius 1, search radius 6, radius 1 .. 2 (2 radius <= BCD_HIP_MAX_NEIGHBOURS).  Colour layers, the
  *   feature gate and the moment selection come through bcd_hip_sequence_create_mode further down, the spike prefilter through
- *   bcd_hip_sequence_set_prefilter; motion fields (a warped neighbour breaks the symmetry), row bands and several GPUs are out.
+ *   bcd_hip_sequence_set_prefilter, per-step motion fields through bcd_hip_sequence_push_frame_motion (a warped pair is not transposed); row bands and
+ *   several GPUs are out.
  *   Refused before any device work, with a message: what bcd_hip_denoise_temporal refuses; a radius outside 1 .. 2; any other geometry
  *   (BCD_HIP_EUNSUPPORTED); a null image; a push beyond the ring or after _end; a pop that is not ready.
  * A sequence handle is an opaque pointer, written by _create and passed as void *. */
@@ -631,8 +632,8 @@ int bcd_hip_denoise_temporal_moments_host(bcd_hip_ctx *ctx, const float *h_nsamp
  *   patch radius 1 and search radius 6: BCD_HIP_EUNSUPPORTED); L outside 1 .. 16, F outside 0 .. 8; a guide that cannot count; a negative or non-finite floor,
  *   threshold or var_floor; a cross feature kernel that cannot be launched; a non-NULL `reserved`; a push whose shape does not match the mode; a pop with a
  *   wrong layer count or a null output; a plain call on a sequence of another mode and the reverse.
- *   Out of scope: motion fields (a warped pair is not symmetric, and its pyramids are per pair), row bands, several GPUs.  The spike prefilter comes
- *   through bcd_hip_sequence_set_prefilter below. */
+ *   Out of scope: row bands, several GPUs.  The spike prefilter comes through bcd_hip_sequence_set_prefilter below, motion fields through
+ *   bcd_hip_sequence_push_frame_motion further down (a warped pair is not symmetric and its pyramids are per pair: it is computed from both sides). */
 typedef struct bcd_hip_sequence_mode {
     int32_t      nb_layers;
     int32_t      moments;
@@ -696,6 +697,34 @@ int bcd_hip_denoise_temporal_host_ex(bcd_hip_ctx *ctx, const float *h_nsamples, 
                                      const bcd_hip_guide_images *neighbour_guides, const bcd_hip_temporal_host_options *opt);
 int bcd_hip_sequence_set_prefilter(void *seq, float factor);   /* <= 0: off (the default) */
 int bcd_hip_sequence_prefilter_info(void *seq, int64_t *frames_filtered, int64_t *pixels_moved);
+
+/* ---- sequences that take per-step motion fields ("Sequences with motion") ----
+ * A renderer produces the vector of a pixel to the previous frame and at best to the next one; a window of radius 2 needs the fields two frames away, which are
+ * compositions of the steps.
+ *   _compose_motion: a is the field frame t -> frame u, b the field frame u -> frame v in frame-u pixel order, out the field t -> v; each W*H*2 floats,
+ *             interleaved (dx, dy), in the convention of bcd_hip_warp_frame.  Per pixel p = (l, c): (dx1, dy1) = a(p); p is broken when dx1 or dy1 is not
+ *             finite or |.| >= 2^24, or when q = (l + rintf(dy1), c + rintf(dx1)) lies outside the image; otherwise (dx2, dy2) = b(q) and p is broken when
+ *             these are not finite or |.| >= 2^24; otherwise sx = rintf(dx1) + rintf(dx2), sy likewise, as int32, and p is broken when |sx| or |sy| >= 2^24.
+ *             A broken pixel stores (NaN, NaN), any other ((float)sx, (float)sy).  For any images X, warp(warp(X, b), a) == warp(X, out) bit for bit, the
+ *             validity of the right side being valid_a(p) AND valid_b(q(p)); whether the final source lies inside the image is the warp's own rule.
+ *             Refused before any device work, the context staying usable: a null pointer, W or H <= 0, out overlapping a or b.  Synchronises.
+ *   _sequence_push_frame_motion[_host]: _push_frame[_host] with the fields frame t -> t - 1 (motion_prev) and t -> t + 1 (motion_next) of the pushed frame t,
+ *             W*H*2 floats each; either may be NULL: zero motion.  Accepted by every sequence of _create_mode (one of bcd_hip_sequence_create refuses it, like
+ *             _push_frame); _push_frame[_host] is this call with both fields NULL.  The fields are copied into the slot (8 B per pixel each, allocated when the
+ *             first field arrives) and are not touched by the spike prefilter: a frame is filtered in its own grid at its push and warped afterwards.
+ *   Definition.  Frame t pops as what the matching frame call -- bcd_hip_denoise_temporal_layers_motion, bcd_hip_denoise_temporal_guided or
+ *   bcd_hip_denoise_temporal_moments with d_motion -- returns for frame t with the neighbours max(0, t - radius) .. min(T - 1, t + radius) except t in ascending
+ *   order, the field of neighbour t -+ 1 being the pushed step field, that of t - 2 compose(prev[t], prev[t - 1]) and that of t + 2
+ *   compose(next[t], next[t + 1]); in a composition one NULL operand yields the other as it is, two yield NULL.  Masks, |S|, marking, lists,
+ *   bcd_hip_get_stats and bcd_hip_layer_spectral_inverses are bit for bit those of that call; the layers differ by the order of float atomics only.
+ *   A neighbour whose direction t -> f has a field is warped from its slot per pop (its pyramid and per-pixel covariances are built from the warped images, its
+ *   cross masks pass the validity gate).  A pair (t, f) is kept and transposed exactly when both directions, t -> f and f -> t, are NULL: with every field NULL
+ *   the sequence takes the path of _push_frame, counters included.
+ *   _sequence_motion_info: neighbours warped and fields composed by the pops since the creation or the last _reset. */
+int bcd_hip_compose_motion(bcd_hip_ctx *ctx, const float *d_a, const float *d_b, int W, int H, float *d_out);
+int bcd_hip_sequence_push_frame_motion(void *seq, const bcd_hip_sequence_frame *frame /* device images */, const float *d_motion_prev, const float *d_motion_next);
+int bcd_hip_sequence_push_frame_motion_host(void *seq, const bcd_hip_sequence_frame *frame /* host images */, const float *h_motion_prev, const float *h_motion_next);
+int bcd_hip_sequence_motion_info(void *seq, int64_t *neighbours_warped, int64_t *fields_composed);
 
 /* row-block variant for multi-GPU tiling: the images are a horizontal band of a larger frame;
  * only main pixels on local lines [main_row_begin, main_row_end) are processed, and instead of the
